@@ -43,11 +43,12 @@ HBM_PEAK_GBS = 8000.0
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=100)     # a run pays ~1 ms once (clocks ramp up after the sync): keep it < 2 %
+    ap.add_argument("--steps", type=int, default=100,     # a run pays ~1 ms once (clocks ramp up after the sync): keep it < 2 %
+                    help="timed steps of the headline figure (in all, over every block); `ms_per_step` is their mean time")
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--blocks", type=int, default=12,
-                    help="the --steps block is timed this many times (each bracketed by barrier + synchronize); `value` is the "
-                         "median block's rate, min / max are reported beside it (>= 10 keeps the timed region above 150 ms at --steps 20)")
+    ap.add_argument("--blocks", type=int, default=1,
+                    help="the --steps timed steps are split into this many blocks (sizes differ by one at most), each bracketed "
+                         "by barrier + synchronize; the rates of the fastest / median / slowest block are reported beside `value`")
     ap.add_argument("--bag", type=int, default=50000, help="instances per bag (BASELINE metric: 50000)")
     ap.add_argument("--eval-mode", action="store_true", help="no dropout (secondary figure)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -74,7 +75,14 @@ def parse():
                     help="f32 bags only (mmf_amil_desc::gemm): f32 = exact-fp32 MFMA (the BASELINE metric's arithmetic, default); "
                          "bf16x3 = every fp32 operand as the sum of three bf16 values on the bf16 matrix cores, fp32 accumulation "
                          "(fp32-equivalent error: tests/test_gpu_split.py).  The default run reports it as the extra leg `gemm_bf16x3`")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (its outputs, loss and every parameter "
+                         "gradient) as DIR/<name>.npy in float32; the inputs are seeded, so runs with the same arguments can be "
+                         "compared output for output")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def flops_per_bag(N, L=1024, H=256, D=256):
@@ -120,6 +128,7 @@ def make_step(model, x, dev, flat=None, world=1, autograd=False):
     c = torch.tensor([0.0], device=dev)
     inv = 1.0 / world
     params = list(model.parameters())
+    last = [None]                 # the last step's outputs: step.outputs() reads them after the timed steps
     if not autograd:
         # the one-call step: gradients of loss / world are WRITTEN (not accumulated) into the flat buffer
         if flat is None:
@@ -130,8 +139,10 @@ def make_step(model, x, dev, flat=None, world=1, autograd=False):
             out = model.nll_step(x, Y, c, alpha=0.0, loss_scale=inv, grad_out=views, accumulate=False)
             if world > 1:
                 dist.all_reduce(flat, op=dist.ReduceOp.SUM)   # RCCL over xGMI: one collective per step
+            last[0] = out
             return out[4]
 
+        fused.outputs = lambda: step_outputs(model, last[0], views)
         return fused
 
     def step():
@@ -140,13 +151,15 @@ def make_step(model, x, dev, flat=None, world=1, autograd=False):
         else:
             for p in params:
                 p.grad = None
-        hazards, S, Y_hat, _ = model(path_features=x)
+        hazards, S, Y_hat, A_raw = model(path_features=x)
         loss = loss_fn(hazards=hazards, S=S, Y=Y, c=c)
         (loss * inv if world > 1 else loss).backward()
         if world > 1:
             dist.all_reduce(flat, op=dist.ReduceOp.SUM)   # RCCL over xGMI: one collective per step
+        last[0] = (hazards, S, Y_hat, A_raw, loss)
         return loss
 
+    step.outputs = lambda: step_outputs(model, last[0], [p.grad for p in params])
     return step
 
 
@@ -165,23 +178,57 @@ def make_step_inflight(model, x, dev, world, n_streams, autograd=False):
     pipe = BagsInFlight(model, n_streams, dev)
     xs = distinct_bags(x, n_streams)
     turn = [0]
+    last = [None, 0]              # the last bag's outputs and gradient slot: step.outputs() reads them after the timed steps
 
     def step():
-        xi = xs[turn[0] % n_streams]
+        slot = turn[0] % n_streams
+        xi = xs[slot]
         turn[0] += 1
         if autograd:
             def bag():
-                hazards, S, Y_hat, _ = model(path_features=xi)
+                hazards, S, Y_hat, A_raw = model(path_features=xi)
                 loss = loss_fn(hazards=hazards, S=S, Y=Y, c=c)
+                last[0] = [t.detach() for t in (hazards, S, Y_hat, A_raw, loss)]
                 return loss * inv if world > 1 else loss
             loss = pipe.run(bag, accumulate=False)
         else:
-            loss = pipe.run_fused(model, xi, Y, c, 0.0, loss_scale=inv, accumulate=False)[4]
+            out = pipe.run_fused(model, xi, Y, c, 0.0, loss_scale=inv, accumulate=False)
+            last[0], loss = out, out[4]
         if world > 1:
             pipe.all_reduce_slot()       # RCCL over xGMI: one collective per bag, on the bag's stream
+        last[1] = slot
         return loss
 
+    step.outputs = lambda: step_outputs(model, last[0], flat_views(model, pipe.slots[last[1]]))
     return step
+
+
+def step_outputs(model, outs, grads):
+    """What a caller of the timed step receives: (hazards, S, Y_hat, A_raw, loss[, risk]) and every parameter gradient,
+    by name (tensors; read them after a synchronize)."""
+    names = ("hazards", "S", "Y_hat", "A_raw", "loss", "risk")
+    res = {k: v for k, v in zip(names, outs) if v is not None}
+    for (name, _), g in zip(model.named_parameters(), grads):
+        res["grad." + name] = g
+    return res
+
+
+def dump_outputs(out_dir, arrays, limit_bytes=64 << 20):
+    """Write each named tensor as out_dir/<name>.npy: float64 stays float64, everything else (bf16, fp32, the int64 Y_hat)
+    becomes float32.  When the arrays together exceed `limit_bytes`, every array above an equal share of it is replaced by
+    the same seeded sample of that many of its (flattened) elements, in index order, so two runs stay comparable."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    host = {k: v.detach().to(torch.float64 if v.dtype == torch.float64 else torch.float32).cpu().numpy()
+            for k, v in arrays.items()}
+    share = limit_bytes // max(len(host), 1)
+    total = sum(a.nbytes for a in host.values())
+    for name, a in host.items():
+        if total > limit_bytes and a.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def distinct_bags(x, n):
@@ -195,23 +242,30 @@ def distinct_bags(x, n):
     return out
 
 
-def time_blocks(step, steps, warmup, world, blocks):
-    """`warmup` untimed steps, then `blocks` timed blocks of EXACTLY `steps` steps each; every block is bracketed by a
-    barrier + torch.cuda.synchronize() on both sides and its time is the MAX over ranks.  Returns the list of block times
-    (seconds).  Why blocks: one block of the default 20-100 steps is 15-75 ms of GPU time, short enough for the clock ramp
-    after an idle period and for one host hiccup to move the figure by several percent; the median over >= 10 blocks does
-    not move, and min / max are reported beside it."""
+def split_steps(steps, blocks):
+    """`steps` timed steps as `blocks` block sizes (at most `steps` blocks, sizes differ by one at most)."""
+    blocks = max(1, min(blocks, steps))
+    q, r = divmod(steps, blocks)
+    return [q + 1] * r + [q] * (blocks - r)
+
+
+def time_blocks(step, sizes, warmup, world):
+    """`warmup` untimed steps, then one timed block per entry of `sizes`, of EXACTLY that many steps; every block is
+    bracketed by a barrier + torch.cuda.synchronize() on both sides and its time is the MAX over ranks.  Returns the list
+    of block times (seconds).  One block of 20-100 steps is 15-75 ms of GPU time, short enough for the clock ramp after an
+    idle period and for one host hiccup to move the figure by several percent: the median over several blocks does not
+    move, and min / max are reported beside it."""
     import torch
     import torch.distributed as dist
     for _ in range(warmup):
         step()
     out = []
-    for _ in range(blocks):          # a fixed count: with N > 1 every step holds a collective, all ranks issue the same number
+    for n in sizes:                  # a fixed count: with N > 1 every step holds a collective, all ranks issue the same number
         if world > 1:
             dist.barrier()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        for _ in range(steps):
+        for _ in range(n):
             step()
         torch.cuda.synchronize()
         if world > 1:
@@ -233,7 +287,7 @@ def median(v):
 
 def time_steps(step, steps, warmup, world, blocks=5):
     """Median block time (seconds per `steps` steps) of `blocks` blocks: the figure the secondary legs quote."""
-    return median(time_blocks(step, steps, warmup, world, blocks))
+    return median(time_blocks(step, [steps] * blocks, warmup, world))
 
 
 def step_percentiles(step, steps):
@@ -790,17 +844,21 @@ def main():
     step = (make_step(model, x, dev, flat, world, ag) if inflight == 1
             else make_step_inflight(model, x, dev, world, inflight, ag))
 
-    blocks = time_blocks(step, args.steps, args.warmup, world, max(1, args.blocks))
-    dt = median(blocks)
+    sizes = split_steps(args.steps, args.blocks)
+    blocks = time_blocks(step, sizes, args.warmup, world)
+    dt = sum(blocks)                 # exactly args.steps timed steps
     ms_per_step = 1e3 * dt / args.steps
     value = world * args.steps / dt
+    rates = [world * n / b for n, b in zip(sizes, blocks)]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, step.outputs())
 
     out = {
         "metric": "bags/sec fwd+bwd, path-AMIL 50k x 1024 synthetic bag" if N == 50000 else f"bags/sec fwd+bwd, path-AMIL {N} x 1024 synthetic bag",
         "value": value, "unit": "bags/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
         "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "blocks": {"count": len(blocks), "steps_per_block": args.steps, "timed_region_ms": 1e3 * sum(blocks),
-                   "value_median": value, "value_min": world * args.steps / max(blocks), "value_max": world * args.steps / min(blocks)},
+        "blocks": {"count": len(blocks), "steps_per_block": sizes, "timed_region_ms": 1e3 * dt,
+                   "value_median": median(rates), "value_min": min(rates), "value_max": max(rates)},
         "dtype": args.dtype if args.gemm == "f32" or bf16 else "f32 (bf16x3 split operands on the bf16 MFMA, f32 accumulate)", "data": "synthetic",
         "config": {"workload": f"path_attention_mil small gated K=4, one {N}x1024 N(0,1) {'bf16 ' if bf16 else ''}bag per GPU per step, "
                                f"nll_surv alpha=0, {'eval' if args.eval_mode else 'train (1 dropout mask)'} mode, "
@@ -816,10 +874,11 @@ def main():
         # rank 0 only: this leg must NOT contain the collective (the other ranks are already at the final barrier)
         local_step = make_step(model, x, dev, flat, 1, ag)
         if inflight > 1 and world == 1:      # the strictly sequential figure beside it (same run)
-            b1 = time_blocks(local_step, args.steps, args.warmup, 1, max(1, args.blocks))
-            d1 = median(b1)
+            b1 = time_blocks(local_step, sizes, args.warmup, 1)
+            d1 = sum(b1)
+            r1 = [n / b for n, b in zip(sizes, b1)]
             out["one_bag_in_flight"] = {"value": args.steps / d1, "ms_per_step": 1e3 * d1 / args.steps,
-                                        "value_min": args.steps / max(b1), "value_max": args.steps / min(b1), "blocks": len(b1)}
+                                        "value_min": min(r1), "value_max": max(r1), "blocks": len(b1)}
             # SURVEY 8(d) defines the metric as ONE bag per GPU per step: that figure at top level, beside `value`
             out["value_one_bag_per_step"] = args.steps / d1
             out["ms_per_step_one_bag"] = 1e3 * d1 / args.steps

@@ -5,7 +5,10 @@ in order, whatever the program says.  Which pool stream shares a queue with whic
 made before (measured, tools/r4_mm_queue.py: with the 7th pool stream as the side stream the multimodal step takes 1.07
 ms, with any of its neighbours 0.89 -- and the two-bags-in-flight rate falls back to one bag at a time the same way).
 `stream_beside` therefore PROBES: ~1 ms of streaming kernels on the reference stream, a tiny kernel on the candidate that
-waits for their start only; the candidate is kept when its kernel finishes while the reference stream is still busy."""
+waits for their start only; the candidate is kept when its kernel finishes while the reference stream is still busy.
+The hardware queues are counted per stream priority (GPU_MAX_HW_QUEUES, 4 by default; some hosts set 2): when no stream of
+the default priority runs beside all the others -- a third stream on a 2-queue host -- the higher priorities' streams, on
+queues of their own, are probed the same way."""
 from __future__ import annotations
 
 import torch
@@ -41,13 +44,16 @@ def stream_beside(others, device=None, tries: int = 12) -> torch.cuda.Stream:
         device = torch.device("cuda", torch.cuda.current_device())
     if torch.cuda.is_current_stream_capturing():
         return torch.cuda.Stream(device)
-    last = None
-    for _ in range(tries):
-        last = torch.cuda.Stream(device)
-        try:
-            if all(_runs_beside(o, last, device) for o in others):
+    fallback = None
+    for prio in range(0, torch.cuda.Stream.priority_range()[1] - 1, -1):   # the default priority (0) first, then higher ones
+        for _ in range(tries):
+            last = torch.cuda.Stream(device, priority=prio)
+            if fallback is None:
+                fallback = last
+            try:
+                if all(_runs_beside(o, last, device) for o in others):
+                    return last
+            except torch.cuda.OutOfMemoryError:  # no room for the probe's operand: an unmeasured stream is still a correct one
+                torch.cuda.synchronize(device)
                 return last
-        except torch.cuda.OutOfMemoryError:  # no room for the probe's operand: an unmeasured stream is still a correct one
-            torch.cuda.synchronize(device)
-            return last
-    return last                              # nothing passed (one hardware queue?): still correct, just not concurrent
+    return fallback                          # nothing passed (one hardware queue?): still correct, just not concurrent

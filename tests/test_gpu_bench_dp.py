@@ -38,8 +38,8 @@ def test_two_rank_rehearsal_counts_collectives(tmp_path, inflight):
     assert out["scaling"] == "weak" and out["value"] > 0
     counts = [json.load(open(f"{tag}.rank{k}")) for k in range(2)]
     assert counts[0] == counts[1], counts                       # equal on every rank, or RCCL would hang
-    # one all-reduce per bag (warm-up + timed blocks) + one MAX all-reduce of the block time per block
-    assert counts[0]["all_reduce"] == warmup + steps * blocks + blocks, counts
+    # one all-reduce per bag (warm-up + the `steps` timed steps, split into blocks) + one MAX all-reduce of the block time per block
+    assert counts[0]["all_reduce"] == warmup + steps + blocks, counts
 
 
 def test_bench_launches_its_own_ranks(tmp_path):
@@ -58,7 +58,7 @@ def test_bench_launches_its_own_ranks(tmp_path):
     out = json.loads(line[0])
     assert out["n_gpus"] == 2 and out["steps"] == steps and out["config"]["bags_in_flight"] == 2
     counts = [json.load(open(f"{tag}.rank{k}")) for k in range(2)]
-    assert counts[0] == counts[1] and counts[0]["all_reduce"] == warmup + steps * blocks + blocks, counts
+    assert counts[0] == counts[1] and counts[0]["all_reduce"] == warmup + steps + blocks, counts
 
 
 def test_gpus_flag_must_match_the_world_size():
