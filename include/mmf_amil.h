@@ -177,6 +177,38 @@ int mmf_amil_nll_step(const mmf_amil_desc* desc, const void* x, int32_t x_bf16, 
                       const mmf_surv_head* head, const mmf_nll_target* target, float* A_raw,
                       const mmf_amil_grads* grads, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Grouped training step: the G bags of one gradient-accumulation window in ONE launch chain.
+ *   The reference trains with batch_size = 1 and accumulates gc bags before each optimizer step
+ *   (utils/core_utils.py:200-247: loss / gc + loss_reg; loss.backward(); step every gc bags), over the per-bag forward of
+ *   models/model_attention_mil_path.py:50-61 and nll_surv (utils/loss_utils.py:22-39).  The parameters do not change inside
+ *   a window, so its bags are independent forward passes on the same weights and their summed gradient is ONE contraction
+ *   over all of their rows.  Here the row-parallel GEMMs and the split-K weight-gradient GEMMs run once over the
+ *   concatenated rows (sum N); only pooling, the head, the loss and K-prep are per bag (one workgroup per bag, one launch).
+ *   x: the bags' rows concatenated, [sum N x L] fp32 (bf16 bags are not supported here: the bf16 path serves 100k-row
+ *   bags, which fill the GPU on their own).  desc->N = offsets[G]; desc->seed is not read (each bag has its own seed);
+ *   desc->seed_dev, sync and trace as usual.
+ *   head / target: the per-bag arrays are G long -- logits, hazards, S [G x K]; Y_hat, risk, loss, Y, c [G].
+ *   Gradients: those of sum_g loss_g * loss_scale, overwritten, or added under target->accumulate, as G calls of
+ *   mmf_amil_nll_step with accumulate would leave them (to fp32 rounding).  Bag g's dropout masks are the ones
+ *   mmf_amil_nll_step draws for that bag alone with desc->seed = seeds[g] (bag-local row indices).
+ *   Returns MMF_ERR_ARG for gemm = MMF_GEMM_BF16X3 or grads->dx != NULL; MMF_ERR_SHAPE for G outside 1..MMF_GROUP_MAX, an
+ *   empty bag, offsets that are not strictly increasing from 0, desc->N != offsets[G], or totals beyond the limits of the
+ *   single-bag entry points (applied to sum N).  No workgroup waits for another; calls are deterministic.
+ * mmf_amil_group_workspace_bytes: the workspace of that window, or 0 when the offset table is invalid.
+ * ------------------------------------------------------------------------------------------- */
+#define MMF_GROUP_MAX 64
+typedef struct mmf_bag_group {
+  int32_t G;                 /* bags in the group, 1 .. MMF_GROUP_MAX */
+  const int64_t* offsets;    /* HOST [G + 1]: bag g = rows offsets[g] .. offsets[g + 1] - 1 of x; offsets[0] = 0 */
+  const uint32_t* seeds;     /* HOST [G]: dropout seed of each bag */
+} mmf_bag_group;
+
+size_t mmf_amil_group_workspace_bytes(const int64_t* offsets, int32_t G, int32_t L, int32_t H, int32_t D, int32_t gated);
+int mmf_amil_nll_step_group(const mmf_amil_desc* desc, const mmf_bag_group* group, const float* x, void* workspace,
+                            size_t workspace_bytes, const mmf_surv_head* head, const mmf_nll_target* target,
+                            float* A_raw /* [sum N] */, const mmf_amil_grads* grads, void* stream);
+
 /* The hazard head's training step on a feature vector that is already on the device: what
  *   `hazards, S, Y_hat = head(classifier(feat)); loss = NLLSurvLoss(alpha)(hazards, S, Y, c); (loss * loss_scale).backward()`
  * computes between the embedding and the loss (models/model_mm_attention_mil.py:190-191 with fusion = 'concat': feat is the

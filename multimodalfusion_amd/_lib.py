@@ -12,7 +12,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MMF_LIB_PATH") or os.path.join(_HERE, "libmmf_amil.so")   # override: diagnostic builds only
 
-ABI_VERSION = 11
+ABI_VERSION = 12
 
 c_f32p = C.c_void_p   # device pointers travel as integers (tensor.data_ptr())
 
@@ -49,6 +49,11 @@ class NllTarget(C.Structure):
     _fields_ = [("Y", C.c_void_p), ("c", C.c_void_p), ("alpha", C.c_float), ("eps", C.c_float),
                 ("loss_scale", C.c_float), ("loss", C.c_void_p), ("dWk", C.c_void_p), ("dbk", C.c_void_p),
                 ("accumulate", C.c_int32)]
+
+
+class BagGroup(C.Structure):
+    """mmf_bag_group: the bags of one grouped step (host arrays)."""
+    _fields_ = [("G", C.c_int32), ("offsets", C.POINTER(C.c_int64)), ("seeds", C.POINTER(C.c_uint32))]
 
 
 class MaxnetDesc(C.Structure):
@@ -92,6 +97,11 @@ SYMBOLS = {
                                         C.POINTER(SurvHead), C.c_void_p, C.c_void_p, C.c_void_p]),
     "mmf_amil_nll_step": (C.c_int, [C.POINTER(AmilDesc), C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t,
                                     C.POINTER(SurvHead), C.POINTER(NllTarget), C.c_void_p, C.POINTER(AmilGrads), C.c_void_p]),
+    "mmf_amil_group_workspace_bytes": (C.c_size_t, [C.POINTER(C.c_int64), C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                                     C.c_int32]),
+    "mmf_amil_nll_step_group": (C.c_int, [C.POINTER(AmilDesc), C.POINTER(BagGroup), C.c_void_p, C.c_void_p, C.c_size_t,
+                                          C.POINTER(SurvHead), C.POINTER(NllTarget), C.c_void_p, C.POINTER(AmilGrads),
+                                          C.c_void_p]),
     "mmf_surv_head_nll_step": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(SurvHead), C.POINTER(NllTarget), C.c_void_p,
                                          C.c_void_p]),
     "mmf_amil_infer_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),

@@ -61,7 +61,8 @@ __global__ __launch_bounds__(256) void bwd_prep_kernel(BwdPrepParams p) {
 // K-dh : NN GEMM with on-the-fly A operand
 // =============================================================================================
 // MODE < 0: gate / dropout switches read at run time; MODE = 2 * gated + dropout: compiled in (wide tiles)
-template <int ROWS, int NT, int MODE = -1>
+// SEG: grouped step -- the mask index of row i is seg_ridx[i] + k (bag-local row, bag seed) instead of i * D + k
+template <int ROWS, int NT, int MODE = -1, bool SEG = false>
 struct LoadP_K {   // A[i][k] = dP, k-contiguous image
   using Map = KMap<ROWS, NT>;
   GateBwdCtx g;
@@ -70,6 +71,20 @@ struct LoadP_K {   // A[i][k] = dP, k-contiguous image
   uint32_t thr;
   float dscale;
   unsigned voff[Map::NV];
+  uint32_t rbase[SEG ? Map::NV : 1];
+  __device__ inline void init_seg(const uint32_t* ridx, int nrows) {
+    if constexpr (SEG) {
+#pragma unroll
+      for (int i = 0; i < Map::NV; ++i) {
+        const int rr = row0 + Map::row(tid, i);
+        rbase[i] = (Map::valid(tid, i) && rr < nrows) ? ridx[rr] : 0u;
+      }
+    }
+  }
+  __device__ inline uint32_t idx_of(int i, int rr, int c) const {
+    if constexpr (SEG) return rbase[i] + (uint32_t)c;
+    else return (uint32_t)rr * (uint32_t)g.D + (uint32_t)c;
+  }
   float dsr[Map::NV];
   float4 ra4[Map::NV], rb4[Map::NV], wc4;
   __device__ inline void init(const GateBwdCtx& g_, int row0_, int nrows) {
@@ -132,7 +147,7 @@ struct LoadP_K {   // A[i][k] = dP, k-contiguous image
     for (int i = 0; i < Map::NV; ++i) {
       if (!Map::valid(tid, i)) continue;
       int rr = row0 + Map::row(tid, i);
-      uint32_t idx = (uint32_t)rr * (uint32_t)g.D + (uint32_t)c;
+      uint32_t idx = idx_of(i, rr, c);
       float dummy;
       float4 o;
       o.x = gate_dp_t<GATED, DROP, PART>(g, ra4[i].x, rb4[i].x, wc4.x, dsr[i], idx + 0, thr, dscale, dummy);
@@ -154,7 +169,7 @@ struct LoadP_K {   // A[i][k] = dP, k-contiguous image
     for (int i = 0; i < Map::NV; ++i) {
       if (!Map::valid(tid, i)) continue;
       int rr = row0 + Map::row(tid, i);
-      uint32_t idx = (uint32_t)rr * (uint32_t)g.D + (uint32_t)c;
+      uint32_t idx = idx_of(i, rr, c);
       float dummy;
       float4 o;
       o.x = gate_dp(g, part, ra4[i].x, rb4[i].x, wc4.x, dsr[i], idx + 0, thr, dscale, dummy);
@@ -489,8 +504,10 @@ __device__ inline void dh_split_mainloop(const LA& la0, const LB& lb0, int nk, f
   }
 }
 
-template <class T, bool FUSED, int MODE = -1>
+// SEG (grouped step, never FUSED): row i's pooling term is p_i dM[bag i] and its dP masks index through seg_ridx
+template <class T, bool FUSED, int MODE = -1, bool SEG = false>
 __global__ __launch_bounds__(T::NT) void bwd_dh_kernel(BwdDhParams p) {
+  static_assert(!(SEG && (FUSED || T::SPLIT)), "the grouped step runs K-prep on its own and the exact-fp32 tiles");
   extern __shared__ __align__(16) float lds[];
   int mt, nt;
   if (!tile_of_block(blockIdx.x, p.mt_count, p.nt_count, mt, nt)) return;
@@ -502,7 +519,7 @@ __global__ __launch_bounds__(T::NT) void bwd_dh_kernel(BwdDhParams p) {
   constexpr bool SGATED = T::SPLIT && MODE >= 2;
   std::conditional_t<T::SPLIT,
                      std::conditional_t<SGATED, SplitP_K<T::BM, T::NT, (SGATED ? MODE : 2)>, SplitP_U<T::BM, T::NT, (T::SPLIT && !SGATED ? MODE : 0)>>,
-                     LoadP_K<T::BM, T::NT, MODE>> la;
+                     LoadP_K<T::BM, T::NT, MODE, SEG>> la;
   if constexpr (FUSED) {
     // ---- K-prep for this tile's rows: p_i = softmax weight, ds_i = p_i (dM.h_i - dM.M) + gA_i ----------
     // g_i = dM.h_i: every wave takes a contiguous share of the rows; lanes cover float4 pieces of h with 8
@@ -582,6 +599,7 @@ __global__ __launch_bounds__(T::NT) void bwd_dh_kernel(BwdDhParams p) {
     la.init_lds(p.g, row0, (int)p.N, ds_l);
   } else {
     la.init(p.g, row0, (int)p.N);
+    if constexpr (SEG && !T::SPLIT) la.init_seg(p.seg_ridx, (int)p.N);
   }
   std::conditional_t<T::SPLIT, SplitWab_M<T::BN, T::NT, SGATED>, LoadWab_M<T::BN, T::NT>> lb;
   lb.init(p.Wa, p.Wb, p.H, p.g.D, col0, p.g.gated != 0);
@@ -613,7 +631,7 @@ __global__ __launch_bounds__(T::NT) void bwd_dh_kernel(BwdDhParams p) {
 #pragma unroll
     for (int nb = 0; nb < T::NB; ++nb) {
       const int col = col0 + epilogue_col<T>(nb);
-      dm4[nb] = (p.dM && col < p.H) ? ld4(p.dM + col) : zero4();
+      dm4[nb] = (!SEG && p.dM && col < p.H) ? ld4(p.dM + col) : zero4();
     }
     if (p.relu_bits) {
       // relu'(u) . keep comes as one bit per element from the forward (LinearParams::relu_bits): 16 ballot words per
@@ -640,11 +658,12 @@ __global__ __launch_bounds__(T::NT) void bwd_dh_kernel(BwdDhParams p) {
         transpose_block(acc[mb][nb], blk, lane, v);
         const int r = wm * (T::BM / T::WM) + mb * 32 + rr, col = col0 + (wn * T::NB + nb) * 32 + 4 * c4;
         if (col >= p.H) continue;
-        const float4 dm = dm4[nb];
+        const float4 dm_c = dm4[nb];
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
           const int row = row0 + r + 8 * t;
           const float pi = FUSED ? p_l[r + 8 * t] : p.p[row < p.N ? row : (int)p.N - 1];
+          const float4 dm = SEG ? ld4(p.dM + (size_t)p.seg_bag[row < p.N ? row : (int)p.N - 1] * p.H + col) : dm_c;
           const float raw[4] = {(v[t].x + pi * dm.x) * p.scale_h, (v[t].y + pi * dm.y) * p.scale_h,
                                 (v[t].z + pi * dm.z) * p.scale_h, (v[t].w + pi * dm.w) * p.scale_h};
           float o[4];
@@ -666,11 +685,12 @@ __global__ __launch_bounds__(T::NT) void bwd_dh_kernel(BwdDhParams p) {
           transpose_half(acch[nb][0], acch[nb][1], blk, lane, v);
           const int r = wm * (T::BM / T::WM) + T::MB * 32 + rr, col = col0 + (wn * T::NB + nb) * 32 + 4 * c4;
           if (col >= p.H) continue;
-          const float4 dm = dm4[nb];
+          const float4 dm_c = dm4[nb];
 #pragma unroll
           for (int t = 0; t < 2; ++t) {
             const int row = row0 + r + 8 * t;
             const float pi = FUSED ? p_l[r + 8 * t] : p.p[row < p.N ? row : (int)p.N - 1];
+            const float4 dm = SEG ? ld4(p.dM + (size_t)p.seg_bag[row < p.N ? row : (int)p.N - 1] * p.H + col) : dm_c;
             const float raw[4] = {(v[t].x + pi * dm.x) * p.scale_h, (v[t].y + pi * dm.y) * p.scale_h,
                                   (v[t].z + pi * dm.z) * p.scale_h, (v[t].w + pi * dm.w) * p.scale_h};
             float o[4];
@@ -710,11 +730,12 @@ __global__ __launch_bounds__(T::NT) void bwd_dh_kernel(BwdDhParams p) {
       transpose_block(acc[mb][nb], blk, lane, v);
       const int r = (wm * T::MB + mb) * 32 + rr, col = col0 + (wn * T::NB + nb) * 32 + 4 * c4;
       if (col >= p.H) continue;
-      const float4 dm = dm4[nb];
+      const float4 dm_c = dm4[nb];
 #pragma unroll
       for (int t = 0; t < 4; ++t) {
         const int row = row0 + r + 8 * t;
         if (row >= p.N) continue;
+        const float4 dm = SEG ? ld4(p.dM + (size_t)p.seg_bag[row] * p.H + col) : dm_c;
         const float4 h4 = hv[s][t];
         const float pi = pv[s][t];
         float4 du;
@@ -825,8 +846,12 @@ struct LoadA_M_Plain {
 //   ungated: DT = ROWS, columns = d pre-tanh.
 // DROP: 0 / 1 = attention dropout off / on, compiled in (the large-bag tile: the kernel is instantiated per value);
 //       -1 = tested per element at run time (small tile)
+// DROP = 2: dropout with the grouped step's per-instance mask index (TnParams::seg_ridx)
 template <int ROWS, int NT, bool GATED, int DROP = -1>
 struct LoadA_M_Gate {
+  static constexpr bool SEG = DROP == 2;
+  rsrc_t rrix;
+  uint32_t rix[SEG ? MMap<(GATED ? ROWS / 2 : ROWS), NT>::NV : 1];
   static constexpr int DT = GATED ? ROWS / 2 : ROWS;
   using Map = MMap<DT, NT>;
   static_assert(NT % Map::VPR == 0 && Map::EXACT, "a thread must own the same columns in every vector slot");
@@ -869,6 +894,7 @@ struct LoadA_M_Gate {
       ra4[i] = bld4(ra, voff[i], k0 * db);
       if (GATED) rb4[i] = bld4(rb, voff[i], k0 * db);
       dsr[i] = bld1(rds, voff_ds[i], k0 * 4u);    // 0 beyond the split's last instance => dP = 0 there
+      if constexpr (SEG) rix[i] = __float_as_uint(bld1(rrix, voff_ds[i], k0 * 4u));
     }
   }
   __device__ inline void store(float* lds) {
@@ -878,7 +904,9 @@ struct LoadA_M_Gate {
 #pragma unroll
     for (int i = 0; i < Map::NV; ++i) {
       const int k = kbase + kt_loaded * KC + Map::krow(tid, i);
-      const uint32_t idx = (uint32_t)k * (uint32_t)g.D + (uint32_t)c;
+      uint32_t idx;
+      if constexpr (SEG) idx = rix[i] + (uint32_t)c;
+      else idx = (uint32_t)k * (uint32_t)g.D + (uint32_t)c;
       const float dsv = dsr[i];
       const float av[4] = {ra4[i].x, ra4[i].y, ra4[i].z, ra4[i].w};
       const float bv[4] = {rb4[i].x, rb4[i].y, rb4[i].z, rb4[i].w};
@@ -1095,6 +1123,7 @@ __device__ inline void tn_gate_tile(const TnParams& p, const TnProblem& q,
   const int D = p.g.D, d0 = tm * DT;
   LA la;
   la.init(p.g, d0, kbase, kmax, do_sum);
+  if constexpr (!T::SPLIT && DROP == 2) la.rrix = make_rsrc(p.seg_ridx, (unsigned)(kmax > 0 ? kmax : 0) * 4u);
   f32x16 acc[T::MB][T::NB];
   if constexpr (T::SPLIT) split_mainloop<T, 2>(la, lb, nk, lds, acc);
   else gemm_mainloop<T>(la, lb, nk, lds, acc, nullptr, last_groups);
@@ -1425,6 +1454,87 @@ int launch_bwd_dh(BwdDhParams p, hipStream_t st) {
   return launch_tiled<T>("bwd_dh_kernel", bwd_dh_kernel<T, false>, p, grid_for_tiles(p.mt_count, p.nt_count), st);
 }
 
+// Grouped step: the same tile plan as launch_bwd_dh without fused prep (K-prep ran as group_bwd_prep_kernel), the SEG
+// instantiations.  Wide tiles take whole 32-row blocks only (the half block's epilogue needs fused prep).
+template <int ROWS>
+static int launch_bwd_dh_wide_seg(BwdDhParams p, hipStream_t st) {
+  using T = Tile<ROWS, 256, 1, 8, true, false>;
+  p.mt_count = (int)((p.N + T::BM - 1) / T::BM); p.nt_count = p.H / 256;
+  return launch_tiled<T>("bwd_dh_kernel", bwd_dh_kernel<T, false, -1, true>, p, grid_for_tiles(p.mt_count, p.nt_count), st);
+}
+int launch_bwd_dh_seg(BwdDhParams p, hipStream_t st) {
+  if (p.g.D % KC != 0 || p.H % 4 != 0) return MMF_ERR_SHAPE;
+  if (p.fused_prep || p.split || !p.seg_bag || !p.seg_ridx || !p.dM || !p.p || !p.h) return MMF_ERR_ARG;
+  if (p.N <= 0) return MMF_OK;
+  if (use_wide_tiles(p.N, p.H, 0)) {
+    switch (pick_wide_rows(p.N, p.H / 256, false, p.concurrent != 0, DH_MAX_ROWS)) {
+#define MMF_WIDE_CASE(R) case R: return launch_bwd_dh_wide_seg<R>(p, st);
+      MMF_WIDE_CASE(64) MMF_WIDE_CASE(96) MMF_WIDE_CASE(128) MMF_WIDE_CASE(160) MMF_WIDE_CASE(192)
+#undef MMF_WIDE_CASE
+      default: return launch_bwd_dh_wide_seg<224>(p, st);
+    }
+  }
+  const int ntn = (p.H + 127) / 128;
+  if ((p.N / 128) * ntn >= 256) {
+    using T = Tile<128, 128, 2, 2, true, false>;
+    p.mt_count = (int)((p.N + 127) / 128); p.nt_count = ntn;
+    return launch_tiled<T>("bwd_dh_kernel", bwd_dh_kernel<T, false, -1, true>, p, grid_for_tiles(p.mt_count, p.nt_count), st);
+  }
+  using T = Tile<64, 64, 2, 2, true, false>;
+  p.mt_count = (int)((p.N + 63) / 64); p.nt_count = (p.H + 63) / 64;
+  static const int env_deep = tune_int("MMF_DEEP", 1);
+  static const int deep_cap = tune_int("MMF_DEEP_MAX", 1024);
+  p.deep = env_deep && (int64_t)p.mt_count * p.nt_count <= deep_cap && p.g.gated && (2 * p.g.D / KC) % 4 == 0 ? 1 : 0;
+  return launch_tiled<T>("bwd_dh_kernel", bwd_dh_kernel<T, false, -1, true>, p, grid_for_tiles(p.mt_count, p.nt_count), st);
+}
+
+// Grouped K-prep: one wave per instance (as bwd_prep_kernel), with the softmax statistics, M and dM of the instance's
+// bag (p.stats [G x 2], p.M / p.dM [G x H]); dM.M is recomputed when a wave's next instance lies in another bag.
+__global__ __launch_bounds__(256) void group_bwd_prep_kernel(BwdPrepParams p, const int* bag) {
+  __shared__ float red[4];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  int cur = -1;
+  float dmm = 0.f, m = 0.f, inv = 1.f;
+  const float* dM = p.dM;
+  float dbc = 0.f;
+  const int64_t nw = (int64_t)gridDim.x * 4;
+  for (int64_t i = (int64_t)blockIdx.x * 4 + wave; i < p.N; i += nw) {
+    const int b = __builtin_amdgcn_readfirstlane(bag[i]);
+    if (b != cur) {
+      cur = b;
+      dM = p.dM + (size_t)b * p.H;
+      const float* M = p.M + (size_t)b * p.H;
+      float t = 0.f;
+      for (int c = lane; c < p.H; c += 64) t += dM[c] * M[c];
+      dmm = wave_sum(t);
+      m = p.stats[2 * b];
+      inv = 1.0f / p.stats[2 * b + 1];
+    }
+    const float* hr = p.h + (size_t)i * p.H;
+    float gsum = 0.f;
+    for (int c = 4 * lane; c < p.H; c += 256) {
+      float4 hv = ld4(hr + c), dv = ld4(dM + c);
+      gsum += hv.x * dv.x + hv.y * dv.y + hv.z * dv.z + hv.w * dv.w;
+    }
+    gsum = wave_sum(gsum);
+    if (lane == 0) {
+      float pi = __expf(p.A_raw[i] - m) * inv;
+      float d = pi * (gsum - dmm) + (p.gA ? p.gA[i] : 0.f);
+      p.p[i] = pi;
+      p.ds[i] = d;
+      dbc += d;
+    }
+  }
+  if (lane == 0) red[wave] = dbc;
+  __syncthreads();
+  if (tid == 0) p.dbc_part[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
+}
+int launch_group_bwd_prep(BwdPrepParams p, const int* bag, hipStream_t st) {
+  if (!bag || p.n_groups < 1) return MMF_ERR_ARG;
+  { ProfScope ps("group_bwd_prep_kernel", st); hipLaunchKernelGGL(group_bwd_prep_kernel, dim3(p.n_groups), dim3(256), 0, st, p, bag); }
+  return hipGetLastError() == hipSuccess ? MMF_OK : MMF_ERR_LAUNCH;
+}
+
 int launch_nn(NnParams p, hipStream_t st) {
   if (p.K % KC != 0 || p.lda % 4 != 0 || p.ldb % 4 != 0 || p.N % 4 != 0) return MMF_ERR_SHAPE;
   if (p.M <= 0) return MMF_OK;
@@ -1461,6 +1571,9 @@ int tn_splits(int64_t K, int total_tiles, int tile) {
 // the large-bag tile is instantiated per attention-dropout state (no per-element test in the gate tiles' staging path)
 template <class T>
 static int launch_tn_grid(const TnParams& p, int grid, hipStream_t st) {
+  if constexpr (!T::SPLIT) {      // grouped step with attention dropout: per-bag mask index of every instance
+    if (p.seg_ridx && p.g.drop_p > 0.f) return launch_tiled<T>("tn_kernel", tn_kernel<T, 2>, p, grid, st);
+  }
   if constexpr (T::BM == 256 || T::SPLIT) {
     const char* name = T::SPLIT ? "tn_split_kernel" : "tn_kernel";
     if (p.g.drop_p > 0.f) return launch_tiled<T>(name, tn_kernel<T, 1>, p, grid, st);

@@ -44,7 +44,7 @@ struct PartSrc {
   int S;                // partials per tile
 };
 
-template <class T, int ACT, bool DROP>
+template <class T, int ACT, bool DROP, bool SEG = false>
 __device__ inline void linear_epilogue(const LinearParams& p, f32x16 (&acc)[T::MB][T::NB], f32x4acc (*acch)[2], float* lds,
                                        int row0, int col0, const PartSrc ps = PartSrc{}) {
 #ifdef MMF_DIAG_NOEPI         /* diagnostic build: main loop only (results are wrong) */
@@ -78,7 +78,9 @@ __device__ inline void linear_epilogue(const LinearParams& p, f32x16 (&acc)[T::M
       const int row = row0 + r + 8 * t;
       const bool ok = col_ok && row < p.M;
       float y[4] = {v[t].x + b4.x, v[t].y + b4.y, v[t].z + b4.z, v[t].w + b4.w};
-      const uint32_t idx = (uint32_t)row * (uint32_t)p.N + (uint32_t)col;
+      uint32_t idx;
+      if constexpr (SEG) idx = (row < p.M ? p.seg_ridx[row] : 0u) + (uint32_t)col;   // bag-local index + bag seed term
+      else idx = (uint32_t)row * (uint32_t)p.N + (uint32_t)col;
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         if constexpr (ACT == ACT_RELU) y[e] = fmaxf(y[e], 0.f);
@@ -202,7 +204,7 @@ __device__ inline bool ksplit_publish(const LinearParams& p, f32x16 (&acc)[T::MB
   return flag[0] == (unsigned)(S - 1);
 }
 
-template <class T>
+template <class T, bool SEG = false>
 __global__ __launch_bounds__(T::NT) void linear_nt_kernel(LinearParams p) {
   extern __shared__ __align__(16) float lds[];
   MMF_KSTAMP(kernel_t0);
@@ -238,6 +240,10 @@ __global__ __launch_bounds__(T::NT) void linear_nt_kernel(LinearParams p) {
     if (!ksplit_publish<T>(p, acc, acch, lds, mt * p.nt_count + nt, ks, ps)) return;
   }
   const bool drop = p.drop_p > 0.f;
+  if constexpr (SEG) {          // grouped step: ReLU + dropout with per-bag masks (launch_linear_seg)
+    linear_epilogue<T, ACT_RELU, true, true>(p, acc, acch, lds, row0, col0, ps);
+    return;
+  }
   if (p.act == ACT_RELU) {
     if (drop) linear_epilogue<T, ACT_RELU, true>(p, acc, acch, lds, row0, col0, ps);
     else linear_epilogue<T, ACT_RELU, false>(p, acc, acch, lds, row0, col0, ps);
@@ -327,21 +333,21 @@ struct LoadGateW {
   }
 };
 
-template <class T, bool GATED>
+template <class T, bool GATED, bool SEG = false>
 __device__ inline void gate_fwd_tile(const GateFwdParams& p, float* lds, int row0, int nt);
 
-template <class T, bool GATED>
+template <class T, bool GATED, bool SEG = false>
 __global__ __launch_bounds__(T::NT) void gate_fwd_kernel(GateFwdParams p) {
   extern __shared__ __align__(16) float lds[];
   int mt, nt;
   if (!tile_of_block(blockIdx.x, p.mt_count, p.nt_count, mt, nt)) return;
-  gate_fwd_tile<T, GATED>(p, lds, (int)p.row_begin + mt * T::BM, nt);
+  gate_fwd_tile<T, GATED, SEG>(p, lds, (int)p.row_begin + mt * T::BM, nt);
 }
 
 // Two tile heights in ONE launch: the bag's rows are cut into regions of tall (TB) or short (TS) tiles, taken by
 // consecutive ranges of workgroups (GateFwdParams::reg; launch_gate_fwd plans them).  TB and TS have the same thread
 // count and column width.
-template <class TB, class TS, bool GATED>
+template <class TB, class TS, bool GATED, bool SEG = false>
 __global__ __launch_bounds__(TB::NT) void gate_fwd_mixed_kernel(GateFwdParams p) {
   static_assert(TB::NT == TS::NT && TB::BN == TS::BN, "mixed tiles share the launch shape");
   extern __shared__ __align__(16) float lds[];
@@ -350,11 +356,11 @@ __global__ __launch_bounds__(TB::NT) void gate_fwd_mixed_kernel(GateFwdParams p)
     if ((int)blockIdx.x >= p.reg[i].grid_begin) r = i;
   int mt, nt;
   if (!tile_of_block(blockIdx.x - p.reg[r].grid_begin, p.reg[r].mt_count, p.nt_count, mt, nt)) return;
-  if (p.reg[r].tall) gate_fwd_tile<TB, GATED>(p, lds, (int)p.reg[r].row0 + mt * TB::BM, nt);
-  else gate_fwd_tile<TS, GATED>(p, lds, (int)p.reg[r].row0 + mt * TS::BM, nt);
+  if (p.reg[r].tall) gate_fwd_tile<TB, GATED, SEG>(p, lds, (int)p.reg[r].row0 + mt * TB::BM, nt);
+  else gate_fwd_tile<TS, GATED, SEG>(p, lds, (int)p.reg[r].row0 + mt * TS::BM, nt);
 }
 
-template <class T, bool GATED>
+template <class T, bool GATED, bool SEG>
 __device__ inline void gate_fwd_tile(const GateFwdParams& p, float* lds, int row0, int nt) {
   constexpr int DT = GATED ? T::BN / 2 : T::BN;   // attention dims covered by one tile
   const int d0 = nt * DT;
@@ -431,7 +437,9 @@ __device__ inline void gate_fwd_tile(const GateFwdParams& p, float* lds, int row
             if constexpr (GATED) st4(p.b + o, make_float4(bv[0], bv[1], bv[2], bv[3]));
           }
           const float wc[4] = {wc4.x, wc4.y, wc4.z, wc4.w};
-          const uint32_t idx = (uint32_t)row * (uint32_t)p.D + (uint32_t)d;
+          uint32_t idx;
+          if constexpr (SEG) idx = p.seg_ridx[row] + (uint32_t)d;     // grouped step: bag-local mask index
+          else idx = (uint32_t)row * (uint32_t)p.D + (uint32_t)d;
           if (drop) {       // decided once per row, not per element
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
@@ -471,13 +479,12 @@ __device__ inline void gate_fwd_tile(const GateFwdParams& p, float* lds, int row
 // =============================================================================================
 constexpr int POOL_MAX_ROWS = 8192;
 
-__global__ __launch_bounds__(256) void pool_partial_kernel(PoolParams p) {
+// one partial group: rows r0 .. r1 - 1 -> A_raw of those rows and partials[g] = {max, sum e, sum e h}
+__device__ __forceinline__ void pool_partial_rows(const PoolParams& p, int g, int64_t r0, int64_t r1) {
   __shared__ float s_lds[POOL_MAX_ROWS];
   __shared__ float red[256];
   __shared__ __align__(16) float vred[1024];   // RG * VPR == 256 float4 slots
-  const int tid = threadIdx.x, g = blockIdx.x;
-  const int64_t r0 = (int64_t)g * p.rows_per_group;
-  const int64_t r1 = r0 + p.rows_per_group < p.N ? r0 + p.rows_per_group : p.N;
+  const int tid = threadIdx.x;
   const int nrows = r1 > r0 ? (int)(r1 - r0) : 0;
   const float bc = p.bc ? p.bc[0] : 0.f;
 
@@ -539,6 +546,13 @@ __global__ __launch_bounds__(256) void pool_partial_kernel(PoolParams p) {
     out[0] = nrows > 0 ? m : -INFINITY;
     out[1] = l;
   }
+}
+
+__global__ __launch_bounds__(256) void pool_partial_kernel(PoolParams p) {
+  const int g = blockIdx.x;
+  const int64_t r0 = (int64_t)g * p.rows_per_group;
+  const int64_t r1 = r0 + p.rows_per_group < p.N ? r0 + p.rows_per_group : p.N;
+  pool_partial_rows(p, g, r0, r1);
 }
 
 // Head tail (HeadTail; head_tail_kernel below): the classifier, the hazards and -- when a label is given -- nll_surv
@@ -833,11 +847,11 @@ bool use_wide_tiles(int64_t M, int N, int split) {
   return env && N % 256 == 0 && M * (int64_t)(N / 256) >= min_rows;
 }
 
-template <int ROWS>
+template <int ROWS, bool SEG = false>
 static int launch_linear_wide(LinearParams p, hipStream_t st) {
   using T = TileW<ROWS>;
   p.mt_count = (int)((p.M + T::BM - 1) / T::BM); p.nt_count = p.N / 256;
-  return launch_tiled<T>("linear_nt_kernel", linear_nt_kernel<T>, p, grid_for_tiles(p.mt_count, p.nt_count), st);
+  return launch_tiled<T>("linear_nt_kernel", linear_nt_kernel<T, SEG>, p, grid_for_tiles(p.mt_count, p.nt_count), st);
 }
 
 int split_min_rows() {
@@ -880,7 +894,9 @@ size_t linear_ksplit_floats(int64_t M, int N, int K, int nseg, int kseg) {
   return (size_t)S * (size_t)((M + 63) / 64) * (size_t)((N + 63) / 64) * 64 * 64;
 }
 
-int launch_linear(LinearParams p, hipStream_t st) {
+// SEG: the grouped step's projection (ReLU + dropout with per-bag masks, fp32 mode only); the plan is the same
+template <bool SEG>
+static int launch_linear_impl(LinearParams p, hipStream_t st) {
   if (p.K % KC != 0 || (p.nseg > 1 && p.kseg % KC != 0)) return MMF_ERR_SHAPE;
   if (p.ldx % 4 != 0) return MMF_ERR_ALIGN;
   if (p.M <= 0) return MMF_OK;
@@ -895,16 +911,16 @@ int launch_linear(LinearParams p, hipStream_t st) {
   }
   if (use_wide_tiles(p.M, p.N, can_split)) {
     switch (pick_wide_rows(p.M, p.N / 256, p.allow_half != 0, p.concurrent != 0, 240)) {
-#define MMF_WIDE_CASE(R) case R: return launch_linear_wide<R>(p, st);
+#define MMF_WIDE_CASE(R) case R: return launch_linear_wide<R, SEG>(p, st);
       MMF_WIDE_CASE(64) MMF_WIDE_CASE(80) MMF_WIDE_CASE(96) MMF_WIDE_CASE(112) MMF_WIDE_CASE(128)
       MMF_WIDE_CASE(144) MMF_WIDE_CASE(160) MMF_WIDE_CASE(176) MMF_WIDE_CASE(192) MMF_WIDE_CASE(208) MMF_WIDE_CASE(240)
 #undef MMF_WIDE_CASE
-      default: return launch_linear_wide<224>(p, st);
+      default: return launch_linear_wide<224, SEG>(p, st);
     }
   }
   if (!can_split && use_big_tiles(p.M, p.N)) {
     p.mt_count = (int)((p.M + 127) / 128); p.nt_count = (p.N + 127) / 128;
-    return launch_tiled<TileNT128>("linear_nt_kernel", linear_nt_kernel<TileNT128>, p, grid_for_tiles(p.mt_count, p.nt_count), st);
+    return launch_tiled<TileNT128>("linear_nt_kernel", linear_nt_kernel<TileNT128, SEG>, p, grid_for_tiles(p.mt_count, p.nt_count), st);
   }
   p.mt_count = (int)((p.M + 63) / 64); p.nt_count = (p.N + 63) / 64;
   if (can_split && p.M >= split_min_rows()) {
@@ -916,7 +932,7 @@ int launch_linear(LinearParams p, hipStream_t st) {
     if (S > 1 && p.mt_count * p.nt_count <= p.ktick_words) {
       p.ksplit = S;
       p.deep = short_grid((int64_t)p.mt_count * p.nt_count * S) ? 1 : 0;        // (K / KC / S) % 4 == 0 by linear_ksplit
-      return launch_tiled<TileNT64>("linear_nt_kernel", linear_nt_kernel<TileNT64>, p, grid_for_tiles(p.mt_count, p.nt_count * S), st);
+      return launch_tiled<TileNT64>("linear_nt_kernel", linear_nt_kernel<TileNT64, SEG>, p, grid_for_tiles(p.mt_count, p.nt_count * S), st);
     }
   }
   // a segmented (radio: M = 512, K = 4 x 1024) or otherwise long-K projection on <= 128 workgroups leaves half the CUs
@@ -924,11 +940,17 @@ int launch_linear(LinearParams p, hipStream_t st) {
   static const int half_tiles = tune_int("MMF_LINEAR_HALF_TILES", 0);   // A/B switch (off: measured slower or equal)
   static const int deep_seg = tune_int("MMF_DEEP_SEG", 1);      // A/B switch: deep prefetch for segmented inputs too
   p.deep = short_grid(p.mt_count * p.nt_count) && (p.K / KC) % 4 == 0 && (p.nseg == 1 || (deep_seg && p.kseg % (4 * KC) == 0)) ? 1 : 0;
-  if (half_tiles && !p.deep && p.mt_count * p.nt_count <= 128 && p.M > 32 && p.K >= 1024) {   // (short plain grids: deep prefetch instead)
+  if (!SEG && half_tiles && !p.deep && p.mt_count * p.nt_count <= 128 && p.M > 32 && p.K >= 1024) {   // (short plain grids: deep prefetch instead)
     p.mt_count = (int)((p.M + 31) / 32);
     return launch_tiled<TileNT32>("linear_nt_kernel", linear_nt_kernel<TileNT32>, p, grid_for_tiles(p.mt_count, p.nt_count), st);
   }
-  return launch_tiled<TileNT64>("linear_nt_kernel", linear_nt_kernel<TileNT64>, p, grid_for_tiles(p.mt_count, p.nt_count), st);
+  return launch_tiled<TileNT64>("linear_nt_kernel", linear_nt_kernel<TileNT64, SEG>, p, grid_for_tiles(p.mt_count, p.nt_count), st);
+}
+
+int launch_linear(LinearParams p, hipStream_t st) { return launch_linear_impl<false>(p, st); }
+int launch_linear_seg(LinearParams p, hipStream_t st) {
+  if (!p.seg_ridx || p.split || p.act != ACT_RELU) return MMF_ERR_ARG;
+  return p.drop_p > 0.f ? launch_linear_impl<true>(p, st) : launch_linear_impl<false>(p, st);
 }
 
 int gate_parts(int D, int gated, int64_t N) {
@@ -937,7 +959,8 @@ int gate_parts(int D, int gated, int64_t N) {
   return gated ? (D + 63) / 64 : (D + 127) / 128;
 }
 
-int launch_gate_fwd(GateFwdParams p, hipStream_t st) {
+template <bool SEG>
+static int launch_gate_fwd_impl(GateFwdParams p, hipStream_t st) {
   if (p.H % KC != 0 || p.D % 32 != 0) return MMF_ERR_SHAPE;
   if (p.N <= 0) return MMF_OK;
   // BN = 128 always (64 gated dims, or 128 ungated dims, per tile) so that gate_parts() is size independent
@@ -956,8 +979,8 @@ int launch_gate_fwd(GateFwdParams p, hipStream_t st) {
     }
     q.deep = short_grid(q.mt_count * q.nt_count) && (q.H / KC) % 4 == 0 ? 1 : 0;
     const int grid = grid_for_tiles(q.mt_count, q.nt_count);
-    return q.gated ? launch_tiled<TS>("gate_fwd_kernel", gate_fwd_kernel<TS, true>, q, grid, st)
-                   : launch_tiled<TS>("gate_fwd_kernel", gate_fwd_kernel<TS, false>, q, grid, st);
+    return q.gated ? launch_tiled<TS>("gate_fwd_kernel", gate_fwd_kernel<TS, true, SEG>, q, grid, st)
+                   : launch_tiled<TS>("gate_fwd_kernel", gate_fwd_kernel<TS, false, SEG>, q, grid, st);
   };
   // 128-row tiles only once they fill most of the 512 slots (two workgroups per CU): a 10k bag is 316 tall tiles -- every
   // CU busy for a tall tile's time, 60 of them twice -- or 628 short ones in 1.2 rounds: measured 40.6 vs 35.1 us (round 4,
@@ -1009,16 +1032,22 @@ int launch_gate_fwd(GateFwdParams p, hipStream_t st) {
     if (split)
       return p.gated ? launch_tiled<SB>("gate_fwd_split_kernel", gate_fwd_mixed_kernel<SB, SS, true>, p, grid, st)
                      : launch_tiled<SB>("gate_fwd_split_kernel", gate_fwd_mixed_kernel<SB, SS, false>, p, grid, st);
-    return p.gated ? launch_tiled<TileNT128>("gate_fwd_kernel", gate_fwd_mixed_kernel<TileNT128, TS, true>, p, grid, st)
-                   : launch_tiled<TileNT128>("gate_fwd_kernel", gate_fwd_mixed_kernel<TileNT128, TS, false>, p, grid, st);
+    return p.gated ? launch_tiled<TileNT128>("gate_fwd_kernel", gate_fwd_mixed_kernel<TileNT128, TS, true, SEG>, p, grid, st)
+                   : launch_tiled<TileNT128>("gate_fwd_kernel", gate_fwd_mixed_kernel<TileNT128, TS, false, SEG>, p, grid, st);
   }
   p.mt_count = (int)mt;
   const int grid = grid_for_tiles(p.mt_count, p.nt_count);
   if (split)
     return p.gated ? launch_tiled<SB>("gate_fwd_split_kernel", gate_fwd_kernel<SB, true>, p, grid, st)
                    : launch_tiled<SB>("gate_fwd_split_kernel", gate_fwd_kernel<SB, false>, p, grid, st);
-  return p.gated ? launch_tiled<TileNT128>("gate_fwd_kernel", gate_fwd_kernel<TileNT128, true>, p, grid, st)
-                 : launch_tiled<TileNT128>("gate_fwd_kernel", gate_fwd_kernel<TileNT128, false>, p, grid, st);
+  return p.gated ? launch_tiled<TileNT128>("gate_fwd_kernel", gate_fwd_kernel<TileNT128, true, SEG>, p, grid, st)
+                 : launch_tiled<TileNT128>("gate_fwd_kernel", gate_fwd_kernel<TileNT128, false, SEG>, p, grid, st);
+}
+
+int launch_gate_fwd(GateFwdParams p, hipStream_t st) { return launch_gate_fwd_impl<false>(p, st); }
+int launch_gate_fwd_seg(GateFwdParams p, hipStream_t st) {
+  if (!p.seg_ridx || p.split) return MMF_ERR_ARG;
+  return p.drop_p > 0.f ? launch_gate_fwd_impl<true>(p, st) : launch_gate_fwd_impl<false>(p, st);
 }
 
 int pool_groups(int64_t N) {
@@ -1079,6 +1108,127 @@ void debug_stamps_fwd(unsigned long long* out8) {
 #else
   for (int i = 0; i < 8; ++i) out8[i] = 0;
 #endif
+}
+
+}  // namespace mmf
+
+// =============================================================================================
+// Grouped step (mmf_amil_nll_step_group): the per-row segment tables, pooling per bag, merge + head tail per bag
+// =============================================================================================
+namespace mmf {
+
+// row -> bag, and the bag-local dropout index base of the row for the H-wide (h) and D-wide (a, b) mask sites
+__global__ __launch_bounds__(256) void group_rows_kernel(GroupRowsParams p) {
+  __shared__ int64_t off[GROUP_MAX + 1];
+  const int G = p.s.G;
+  for (int i = threadIdx.x; i <= G; i += 256) off[i] = p.s.off[i];
+  __syncthreads();
+  const int64_t row = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (row >= off[G]) return;
+  int lo = 0, hi = G - 1;                  // last bag whose first row is <= row
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (off[mid] <= row) lo = mid; else hi = mid - 1;
+  }
+  const uint32_t local = (uint32_t)(row - off[lo]), base = p.s.ibase[lo];
+  p.ridx_h[row] = local * (uint32_t)p.H + base;
+  p.ridx_d[row] = local * (uint32_t)p.D + base;
+  p.bag[row] = lo;
+}
+
+int launch_group_rows(const GroupRowsParams& p, hipStream_t st) {
+  const int64_t R = p.s.off[p.s.G];
+  ProfScope ps("group_rows_kernel", st);
+  hipLaunchKernelGGL(group_rows_kernel, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, st, p);
+  return hipGetLastError() == hipSuccess ? MMF_OK : MMF_ERR_LAUNCH;
+}
+
+// partial group b of the window: the rows of one bag only
+__global__ __launch_bounds__(256) void group_pool_partial_kernel(PoolParams p, SegTable s) {
+  const int b = blockIdx.x;
+  int g = 0;
+  for (int i = 1; i < s.G; ++i)            // wave-uniform: scalar loads of the table
+    if (b >= s.gbeg[i]) g = i;
+  const int64_t r0 = s.off[g] + (int64_t)(b - s.gbeg[g]) * s.rows_per_group;
+  const int64_t r1 = r0 + s.rows_per_group < s.off[g + 1] ? r0 + s.rows_per_group : s.off[g + 1];
+  pool_partial_rows(p, b, r0, r1);
+}
+
+constexpr int GROUP_BAG_MAX_PARTIALS = GROUP_POOL_GROUPS + 64;
+// one workgroup per bag: merge the bag's partials (M_g, stats_g), then the head tail of that bag
+__global__ __launch_bounds__(1024) void group_tail_kernel(PoolParams p, SegTable s) {
+  __shared__ float tail_sm[1024 + 160];
+  __shared__ float wl[GROUP_BAG_MAX_PARTIALS];
+  __shared__ float red[32];
+  const int g = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int gb = s.gbeg[g], n = s.gbeg[g + 1] - gb, H = p.H, K = p.tail.K;
+  PoolParams q = p;                        // this bag's slice of every per-bag array
+  q.M = p.M + (size_t)g * H;
+  q.stats = p.stats + 2 * g;
+  q.merge_in_tail = 1;
+  HeadTail& t = q.tail;
+  t.logits += (size_t)g * K; t.hazards += (size_t)g * K; t.S += (size_t)g * K; t.Y_hat += g;
+  if (t.risk) t.risk += g;
+  t.Y += g; t.c += g; t.loss += g;
+  t.dM += (size_t)g * H;
+  t.dWk += (size_t)g * K * H; t.dbk += (size_t)g * K;
+  t.accumulate = 0;                        // per-bag slabs; the reduce launch sums them over the bags
+  TailPre pre;
+  tail_preload(q, pre);
+  const int stride = 2 + H;
+  const float* part = p.partials + (size_t)gb * stride;
+  float m = -INFINITY;
+  for (int i = tid; i < n; i += 1024) m = fmaxf(m, part[(size_t)i * stride]);
+  m = wave_max(m);
+  if (lane == 0) red[wave] = m;
+  __syncthreads();
+  m = red[0];
+#pragma unroll
+  for (int i = 1; i < 16; ++i) m = fmaxf(m, red[i]);
+  float l = 0.f;
+  for (int i = tid; i < n; i += 1024) {
+    const float mg = part[(size_t)i * stride];
+    const float w = mg > -INFINITY ? __expf(mg - m) : 0.f;
+    wl[i] = w;
+    l += part[(size_t)i * stride + 1] * w;
+  }
+  l = wave_sum(l);
+  if (lane == 0) red[16 + wave] = l;
+  __syncthreads();
+  l = 0.f;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) l += red[16 + i];
+  if (tid < H) {                           // pool_merge_kernel's order: 32 interleaved slices, then the slices in order
+    const float* col = part + 2 + tid;
+    float acc = 0.f;
+    for (int sl = 0; sl < 32; ++sl) {
+      float a = 0.f;
+      for (int i = sl; i < n; i += 32) a += col[(size_t)i * stride] * wl[i];
+      acc += a;
+    }
+    const float mv = acc / l;
+    q.M[tid] = mv;
+    tail_sm[tid] = mv;
+  }
+  if (tid == 0) { q.stats[0] = m; q.stats[1] = l; }
+  head_tail(q, pre, tail_sm);
+}
+
+int launch_group_pool(PoolParams p, const SegTable& s, hipStream_t st) {
+  if (p.H != 256 && p.H != 512 && p.H != 1024) return MMF_ERR_SHAPE;
+  if (!p.tail.Wk || p.tail.K < 1 || p.tail.K > 32 || s.G < 1 || s.G > GROUP_MAX) return MMF_ERR_SHAPE;
+  if (s.rows_per_group < 1 || s.rows_per_group > POOL_MAX_ROWS) return MMF_ERR_SHAPE;
+  for (int g = 0; g < s.G; ++g)
+    if (s.gbeg[g + 1] - s.gbeg[g] > GROUP_BAG_MAX_PARTIALS) return MMF_ERR_SHAPE;
+  {
+    ProfScope ps("group_pool_partial_kernel", st);
+    hipLaunchKernelGGL(group_pool_partial_kernel, dim3(s.gbeg[s.G]), dim3(256), 0, st, p, s);
+  }
+  {
+    ProfScope ps("group_tail_kernel", st);
+    hipLaunchKernelGGL(group_tail_kernel, dim3(s.G), dim3(1024), 0, st, p, s);
+  }
+  return hipGetLastError() == hipSuccess ? MMF_OK : MMF_ERR_LAUNCH;
 }
 
 }  // namespace mmf

@@ -255,7 +255,7 @@ using namespace mmf;
 
 extern "C" {
 
-int mmf_abi_version(void) { return 11; }
+int mmf_abi_version(void) { return 12; }
 
 const char* mmf_strerror(int code) {
   switch (code) {
@@ -630,6 +630,190 @@ int mmf_amil_nll_step(const mmf_amil_desc* d, const void* x, int32_t x_bf16, voi
   const float* xf = static_cast<const float*>(x);
   if (int e = amil_forward_impl(d, xf, workspace, workspace_bytes, nullptr, A_raw, stream, false, &tl)) return e;
   return amil_backward_impl(d, xf, workspace, workspace_bytes, nullptr, A_raw, nullptr, nullptr, grads, stream, acc);
+}
+
+// ---- grouped step: the bags of one accumulation window as one launch chain ------------------------------------
+namespace mmf {
+// hash_u32(key, i) = mix(i * 0x9E3779B1 + key), so bag g's masks -- key drop_key(seed_g, site), bag-local index i -- are
+// those of key drop_key(0, site) at index i + seed_g * inverse(0x9E3779B1) (mod 2^32): one key per launch, and the bag
+// enters through the per-row index base that group_rows_kernel writes.
+static uint32_t hash_mul_inverse() {
+  const uint32_t a = 0x9E3779B1u;
+  uint32_t x = a;                       // Newton: correct to 3, 6, 12, 24, 48 bits
+  for (int i = 0; i < 5; ++i) x *= 2u - a * x;
+  return x;
+}
+
+static int group_plan(const int64_t* offsets, int G, SegTable& s) {
+  if (!offsets) return MMF_ERR_ARG;
+  if (G < 1 || G > GROUP_MAX) return MMF_ERR_SHAPE;
+  if (offsets[0] != 0) return MMF_ERR_SHAPE;
+  for (int g = 0; g < G; ++g)
+    if (offsets[g + 1] <= offsets[g]) return MMF_ERR_SHAPE;      // empty or decreasing
+  s = SegTable{};
+  s.G = G;
+  const int64_t R = offsets[G];
+  int64_t rpg = (R + GROUP_POOL_GROUPS - 1) / GROUP_POOL_GROUPS;   // ~one pooling group per CU over the window
+  if (rpg < 64) rpg = 64;
+  if (rpg > 8192) return MMF_ERR_SHAPE;                               // POOL_MAX_ROWS
+  s.rows_per_group = (int)rpg;
+  int gb = 0;
+  for (int g = 0; g <= G; ++g) {
+    s.off[g] = offsets[g];
+    s.gbeg[g] = gb;
+    if (g < G) gb += (int)((offsets[g + 1] - offsets[g] + rpg - 1) / rpg);
+  }
+  return MMF_OK;
+}
+
+struct GroupWs {
+  AmilWs w;
+  float *M, *dM, *stats, *wk, *bk, *partials;
+  uint32_t *ridx_h, *ridx_d;
+  int* bag;
+  size_t bytes;
+};
+static GroupWs carve_group(void* base, const SegTable& s, int L, int H, int D, int gated) {
+  GroupWs g{};
+  const int64_t R = s.off[s.G];
+  g.w = carve(base, R, L, H, D, gated);
+  char* p = static_cast<char*>(base);
+  size_t off = g.w.bytes;
+  auto take = [&](size_t nfloat) {
+    float* r = reinterpret_cast<float*>(p + off);
+    off += align_up(nfloat * sizeof(float), 256);
+    return r;
+  };
+  g.M = take((size_t)s.G * H);
+  g.dM = take((size_t)s.G * H);
+  g.stats = take((size_t)2 * s.G);
+  g.wk = take((size_t)s.G * 32 * H);          // per-bag classifier gradients (K <= 32), summed by the reduce launch
+  g.bk = take((size_t)s.G * 32);
+  g.partials = take((size_t)s.gbeg[s.G] * (2 + H));
+  g.ridx_h = reinterpret_cast<uint32_t*>(take((size_t)R));
+  g.ridx_d = reinterpret_cast<uint32_t*>(take((size_t)R));
+  g.bag = reinterpret_cast<int*>(take((size_t)R));
+  g.bytes = off;
+  return g;
+}
+}  // namespace mmf
+
+size_t mmf_amil_group_workspace_bytes(const int64_t* offsets, int32_t G, int32_t L, int32_t H, int32_t D, int32_t gated) {
+  SegTable s;
+  if (group_plan(offsets, G, s)) return 0;
+  return carve_group(nullptr, s, L, H, D, gated).bytes;
+}
+
+int mmf_amil_nll_step_group(const mmf_amil_desc* d, const mmf_bag_group* group, const float* x, void* workspace,
+                            size_t workspace_bytes, const mmf_surv_head* head, const mmf_nll_target* target,
+                            float* A_raw, const mmf_amil_grads* g, void* stream) {
+  if (!d || !group || !target || !g) return MMF_ERR_ARG;
+  if (d->gemm != MMF_GEMM_F32 || g->dx) return MMF_ERR_ARG;
+  if (!group->seeds) return MMF_ERR_ARG;
+  SegTable s;
+  if (int e = group_plan(group->offsets, group->G, s)) return e;
+  if (d->N != s.off[s.G]) return MMF_ERR_SHAPE;
+  if (int e = check_desc(d)) return e;
+  HeadTail tl;
+  if (int e = head_tail_of(head, target, d->H, tl)) return e;
+  if (!x || !workspace || !A_raw) return MMF_ERR_ARG;
+  if (!g->dW1 || !g->db1 || !g->dWa || !g->dba || !g->dWc || !g->dbc) return MMF_ERR_ARG;
+  if (d->gated && (!g->dWb || !g->dbb)) return MMF_ERR_ARG;
+  if (!aligned16(x) || !aligned16(workspace) || !aligned16(d->W1) || !aligned16(d->Wa) || (d->gated && !aligned16(d->Wb)) ||
+      !aligned16(g->dW1) || !aligned16(g->dWa) || (d->gated && !aligned16(g->dWb)))
+    return MMF_ERR_ALIGN;
+  GroupWs gw = carve_group(workspace, s, d->L, d->H, d->D, d->gated);
+  if (gw.bytes > workspace_bytes) return MMF_ERR_WORKSPACE;
+  const AmilWs& w = gw.w;
+  const uint32_t inv = hash_mul_inverse();
+  for (int b = 0; b < s.G; ++b) s.ibase[b] = group->seeds[b] * inv;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  TraceScope ts(d->trace);
+  const uint32_t* const seed_dev = d->seed_dev;
+  const int64_t R = d->N;
+  const int K = head->K;
+
+  GroupRowsParams rp0{};
+  rp0.s = s; rp0.H = d->H; rp0.D = d->D; rp0.ridx_h = gw.ridx_h; rp0.ridx_d = gw.ridx_d; rp0.bag = gw.bag;
+  if (int e = launch_group_rows(rp0, st)) return e;
+
+  LinearParams lp{};
+  lp.x[0] = x; lp.nseg = 1; lp.kseg = d->L; lp.ldx = d->L;
+  lp.w = d->W1; lp.bias = d->b1; lp.y = w.h;
+  lp.M = R; lp.N = d->H; lp.K = d->L;
+  lp.act = ACT_RELU; lp.drop_p = d->p_h; lp.drop_key = drop_key(0, 0); lp.seed_dev = seed_dev;
+  lp.relu_bits = w.relu_bits;
+  lp.allow_half = 1; lp.concurrent = d->concurrent ? 1 : 0;
+  lp.kpart = w.kpart; lp.ktick = d->sync; lp.ktick_words = d->sync ? d->sync_words : 0;
+  lp.seg_ridx = gw.ridx_h;
+  if (int e = launch_linear_seg(lp, st)) return e;
+
+  GateFwdParams gp{};
+  gp.h = w.h; gp.Wa = d->Wa; gp.ba = d->ba; gp.Wb = d->Wb; gp.bb = d->bb; gp.Wc = d->Wc;
+  gp.a = w.a; gp.b = w.b; gp.s_part = w.s_part;
+  gp.N = R; gp.H = d->H; gp.D = d->D; gp.gated = d->gated;
+  gp.drop_p = d->p_att; gp.key_a = drop_key(0, 1); gp.key_b = drop_key(0, 2); gp.seed_dev = seed_dev;
+  gp.seg_ridx = gw.ridx_d;
+  if (int e = launch_gate_fwd_seg(gp, st)) return e;
+
+  PoolParams pp{};
+  pp.s_part = w.s_part; pp.n_parts = w.parts; pp.bc = d->bc; pp.h = w.h; pp.N = R; pp.H = d->H;
+  pp.A_raw = A_raw; pp.partials = gw.partials; pp.M = gw.M; pp.stats = gw.stats;
+  pp.tail = tl; pp.tail.dM = gw.dM; pp.tail.dWk = gw.wk; pp.tail.dbk = gw.bk;
+  if (int e = launch_group_pool(pp, s, st)) return e;
+
+  BwdPrepParams bp{};
+  bp.h = w.h; bp.A_raw = A_raw; bp.stats = gw.stats; bp.dM = gw.dM; bp.M = gw.M; bp.gA = nullptr;
+  bp.N = R; bp.H = d->H; bp.p = w.p; bp.ds = w.ds; bp.dbc_part = w.dbc_part;
+  bp.n_groups = (int)((R + 3) / 4 < PREP_GROUPS ? (R + 3) / 4 : PREP_GROUPS);
+  if (int e = launch_group_bwd_prep(bp, gw.bag, st)) return e;
+
+  GateBwdCtx gc{};
+  gc.a = w.a; gc.b = w.b; gc.ds = w.ds; gc.Wc = d->Wc; gc.D = d->D; gc.gated = d->gated;
+  gc.drop_p = d->p_att; gc.key_a = drop_key(0, 1); gc.key_b = drop_key(0, 2); gc.seed_dev = seed_dev;
+
+  BwdDhParams dp{};
+  dp.g = gc; dp.Wa = d->Wa; dp.Wb = d->Wb; dp.p = w.p; dp.dM = gw.dM; dp.h = w.h; dp.du = w.du;
+  dp.relu_bits = w.relu_bits;
+  dp.concurrent = d->concurrent ? 1 : 0;
+  dp.N = R; dp.H = d->H; dp.scale_h = d->p_h > 0.f ? 1.0f / (1.0f - d->p_h) : 1.0f;
+  dp.seg_ridx = gw.ridx_d; dp.seg_bag = gw.bag;
+  if (int e = launch_bwd_dh_seg(dp, st)) return e;
+
+  TnParams tp{};
+  tp.nprob = 2; tp.K = R; tp.splits = w.splits; tp.k_per_split = w.k_per_split; tp.g = gc; tp.tile = w.tile;
+  tp.seg_ridx = gw.ridx_d;
+  TnProblem& q1 = tp.prob[0];   // dW1[H x L] = du^T . x over every row of the window ; db1 = colsum(du)
+  q1.kind = TN_A_PLAIN; q1.A = w.du; q1.lda = d->H; q1.M = d->H;
+  q1.B = x; q1.ldb = d->L; q1.Ncols = d->L;
+  q1.out = w.slab_w1; q1.split_stride = (size_t)d->H * d->L; q1.ldc = d->L;
+  q1.colsum = w.cs_b1; q1.colsum_stride = d->H; q1.colsum2 = nullptr; q1.colsum2_stride = 0;
+  TnProblem& q2 = tp.prob[1];   // dWab = dP^T . h ; (dba|dbb) = colsum(dP) ; dWc = colsum(ds.a_d.b_d)
+  q2.kind = TN_A_GATE; q2.A = nullptr; q2.lda = 0; q2.M = w.mstk;
+  q2.B = w.h; q2.ldb = d->H; q2.Ncols = d->H;
+  q2.out = w.slab_wab; q2.split_stride = (size_t)w.mstk * d->H; q2.ldc = d->H;
+  q2.colsum = w.cs_bab; q2.colsum_stride = w.mstk; q2.colsum2 = w.cs_wc; q2.colsum2_stride = d->D;
+  q2.splits = w.splits_g; q2.k_per_split = w.k_per_split_g;
+  if (int e = launch_tn(tp, st)) return e;
+
+  ReduceParams rp{};
+  int n = 0;
+  auto seg = [&](const float* in, float* out, int len, int nsplit, size_t stride) {
+    rp.seg[n].in = in; rp.seg[n].out = out; rp.seg[n].len = len; rp.seg[n].nsplit = nsplit; rp.seg[n].stride = stride; ++n;
+  };
+  seg(w.slab_w1, g->dW1, d->H * d->L, w.splits, (size_t)d->H * d->L);
+  seg(w.slab_wab, g->dWa, d->D * d->H, w.splits_g, (size_t)w.mstk * d->H);
+  if (d->gated) seg(w.slab_wab + (size_t)d->D * d->H, g->dWb, d->D * d->H, w.splits_g, (size_t)w.mstk * d->H);
+  seg(w.cs_b1, g->db1, d->H, w.splits, d->H);
+  seg(w.cs_bab, g->dba, d->D, w.splits_g, w.mstk);
+  if (d->gated) seg(w.cs_bab + d->D, g->dbb, d->D, w.splits_g, w.mstk);
+  seg(w.cs_wc, g->dWc, d->D, w.splits_g, d->D);
+  seg(w.dbc_part, g->dbc, 1, bp.n_groups, 1);
+  seg(gw.wk, target->dWk, K * d->H, s.G, (size_t)K * d->H);      // classifier: the bags' slabs in bag order
+  seg(gw.bk, target->dbk, K, s.G, (size_t)K);
+  rp.nseg = n;
+  rp.accumulate = target->accumulate ? 1 : 0;
+  return launch_reduce(rp, st);
 }
 
 int mmf_surv_head_nll_step(const float* feat, int32_t F, const mmf_surv_head* head, const mmf_nll_target* target,

@@ -42,6 +42,9 @@ struct LinearParams {      // y[M x N] = drop(act(concat_k(x_s)[M x K] . W[N x K
   float* kpart;
   unsigned* ktick;
   int ktick_words;
+  // grouped step (mmf_amil_nll_step_group): [M] per-row dropout index base, (row - bag start) * N + seed term of the
+  // row's bag (group_rows_kernel).  Read only by the SEG instantiations; null otherwise.
+  const uint32_t* seg_ridx;
 };
 // K split launch_linear will use for this shape when it is given partial-tile space and tick words; 1 = none
 int linear_ksplit(int64_t M, int N, int K, int nseg, int kseg);
@@ -65,6 +68,7 @@ struct GateFwdParams {
   int nreg;
   int deep;                     // set by launch_gate_fwd: short grid, use the deep-prefetch main loop
   int split;                    // 1: the split-operand core (mmf_gemm_split.h) where the shape has a tile for it
+  const uint32_t* seg_ridx;     // grouped step: [N] dropout index base per row (width D), or null (LinearParams::seg_ridx)
 };
 
 // Optional tail behind K-merge, ONE single-workgroup launch (head_tail_kernel; for small bags it does the merge too):
@@ -187,6 +191,10 @@ struct BwdDhParams {       // du = (dP.Wab + p dM) * relu'(h) * scale_h
   int fused_prep;
   const float *A_raw, *stats, *Mpool, *gA;
   float *p_out, *ds_out, *dbc_part;
+  // grouped step (SEG instantiations, never fused): dM is [G x H], row i takes dM of bag seg_bag[i]; dP's masks index
+  // through seg_ridx (GateFwdParams::seg_ridx)
+  const uint32_t* seg_ridx;
+  const int* seg_bag;
 };
 
 enum : int { TN_A_PLAIN = 0, TN_A_GATE = 1 };
@@ -217,6 +225,7 @@ struct TnParams {
   // launch_tn() packs the tiles of one (split, problem) -- which read the same A or B panel -- next to each other
   // there, so a panel is fetched from HBM once per XCD instead of once per tile.
   uint16_t map[512];
+  const uint32_t* seg_ridx;   // grouped step with attention dropout: dP's mask index base per instance, or null
 };
 
 struct NnParams {          // C[M x N] = A[M x K] . B[K x N]   (plain; radio: dh0 = du.W1)
@@ -232,8 +241,10 @@ struct ReduceSeg { const float* in; float* out; int len; int nsplit; size_t stri
 struct ReduceParams { ReduceSeg seg[12]; int nseg; int accumulate; };   // accumulate: out += sum instead of out = sum
 
 int launch_linear(LinearParams p, hipStream_t st);
+int launch_linear_seg(LinearParams p, hipStream_t st);   // grouped step: the dropout epilogue indexes through p.seg_ridx
 int gate_parts(int D, int gated, int64_t N);
 int launch_gate_fwd(GateFwdParams p, hipStream_t st);
+int launch_gate_fwd_seg(GateFwdParams p, hipStream_t st);
 int pool_groups(int64_t N);
 int launch_pool(PoolParams p, hipStream_t st);
 int launch_score_sum(const float* s_part, int n_parts, const float* bc, float* A, int64_t N, hipStream_t st);
@@ -241,6 +252,7 @@ int launch_head_tail(PoolParams p, hipStream_t st);    // head_tail_kernel alone
 int launch_pool_merge(PoolParams p, hipStream_t st);   // single-workgroup merge of p.n_groups partials -> M, stats
 int launch_bwd_prep(BwdPrepParams p, hipStream_t st);
 int launch_bwd_dh(BwdDhParams p, hipStream_t st);
+int launch_bwd_dh_seg(BwdDhParams p, hipStream_t st);     // grouped step: per-row bag dM and mask index, no fused prep
 // split-operand mode on bags below the wide tiles: instances from which the small split tiles (64-row GEMM tiles, 128 x 128
 // TN tile) are taken instead of the exact-fp32 ones (default 1: every bag, which keeps an instance's score independent of its bag's size)
 int split_min_rows();
@@ -254,6 +266,26 @@ int tn_tile_dim(int64_t K, int D_gate);                    // 256: one 8-wave 25
 int tn_splits(int64_t K, int total_tiles, int tile);
 int launch_nn(NnParams p, hipStream_t st);
 int launch_reduce(ReduceParams p, hipStream_t st);
+
+// ---- grouped step (mmf_amil_nll_step_group): G bags of one accumulation window as one launch chain ----------------
+constexpr int GROUP_MAX = 64;              // MMF_GROUP_MAX
+constexpr int GROUP_POOL_GROUPS = 256;     // pooling partial groups planned over the window (plus at most one per bag)
+struct SegTable {
+  int G;
+  int rows_per_group;                      // pooling: rows per partial group (groups never straddle a bag)
+  int64_t off[GROUP_MAX + 1];              // bag g = rows off[g] .. off[g + 1] - 1
+  int gbeg[GROUP_MAX + 1];                 // bag g's pooling partials are gbeg[g] .. gbeg[g + 1] - 1
+  uint32_t ibase[GROUP_MAX];               // seed_g * inverse(0x9E3779B1): hash_u32(drop_key(0, s), i + ibase) ==
+                                           // hash_u32(drop_key(seed_g, s), i)
+};
+struct GroupRowsParams { SegTable s; int H, D; uint32_t *ridx_h, *ridx_d; int* bag; };
+int launch_group_rows(const GroupRowsParams& p, hipStream_t st);
+// pooling over every bag (partials never straddle a bag), then one 1024-thread workgroup per bag: merge + head tail.
+// p.M / p.stats / p.tail outputs are per-bag arrays ([G x H], [G x 2], [G x K], [G]); tail.dWk / dbk are per-bag slabs
+// [G x K x H], [G x K] (overwritten; the reduce launch sums them); tail.dM is [G x H].
+int launch_group_pool(PoolParams p, const SegTable& s, hipStream_t st);
+// ds_i / p_i with the statistics, M and dM of row i's bag
+int launch_group_bwd_prep(BwdPrepParams p, const int* bag, hipStream_t st);
 int set_dyn_lds(const void* kern, int bytes);
 void debug_stamps_fwd(unsigned long long* out8);
 void debug_stamps_bwd(unsigned long long* out8);

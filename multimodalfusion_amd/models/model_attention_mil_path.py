@@ -6,7 +6,8 @@ import torch
 import torch.nn as nn
 
 from ..utils.utils import initialize_weights
-from .model_modules import AMIL_SIZES, amil_stack, amil_stack_head, amil_stack_nll_step, make_amil_stack
+from .model_modules import (AMIL_SIZES, amil_stack, amil_stack_head, amil_stack_nll_step, amil_stack_nll_step_group,
+                            make_amil_stack)
 
 
 class MIL_Attention_fc_path(nn.Module):
@@ -50,3 +51,14 @@ class MIL_Attention_fc_surv_path(MIL_Attention_fc_path):
             raise RuntimeError("nll_step needs every parameter of the head to require grad")
         return amil_stack_nll_step(self.attention_net_WSI, self.classifier, path_features, self.training, label, c,
                                    alpha, loss_scale, grad_out, accumulate)
+
+    def nll_step_group(self, bags, labels, censors, alpha=0.0, loss_scale=1.0, grad_out=None, accumulate=None, seeds=None):
+        """nll_step for the G bags of one accumulation window in ONE C-ABI call (ops.amil_nll_step_group): the stack's
+        GEMMs run once over all of their rows.  bags: a list of [N_g x 1024] fp32 device tensors or an (x_cat, sizes)
+        pair; labels / censors: G values.  Gradients of sum_g loss_g * loss_scale, same conventions as nll_step; in train
+        mode bag g draws the dropout seed the g-th of G nll_step calls would (or `seeds[g]` when given).  Returns (hazards [G x K], S [G x K],
+        Y_hat [G x 1], [A_raw [1 x N_g]], loss [G], risk [G])."""
+        if any(not p.requires_grad for p in self.parameters()):
+            raise RuntimeError("nll_step_group needs every parameter of the head to require grad")
+        return amil_stack_nll_step_group(self.attention_net_WSI, self.classifier, bags, self.training, labels, censors,
+                                         alpha, loss_scale, grad_out, accumulate, seeds)

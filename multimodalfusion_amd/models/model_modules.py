@@ -265,19 +265,13 @@ def amil_stack(seq, x, training):
     return ops.amil_pool(x, lin.weight, lin.bias, Wa, ba, Wb, bb, Wc, bc, gated, p_h, p_att, seed)
 
 
-def amil_stack_nll_step(seq, classifier, x, training, Y, c, alpha, loss_scale=1.0, grad_out=None, accumulate=None,
-                        dx_out=None):
-    """The whole training step of one bag -- stack, classifier / hazard head, nll_surv and the backward -- as ONE C-ABI
-    call (ops.amil_nll_step), gradients of loss * loss_scale ADDED to the parameters' .grad exactly as
-    `(loss * loss_scale).backward()` would (parameters whose .grad is None get a fresh buffer, as autograd does; when
-    all of them are None the kernels write instead of accumulate and nothing is zero-filled).
-    grad_out: instead of .grad, a list of gradient tensors in the order of [*seq.parameters(), *classifier.parameters()]
-    (pipeline.BagsInFlight hands in views of a stream's gradient slot) with `accumulate` said explicitly.
-    dx_out: an [N x L] fp32 tensor that receives the gradient with respect to the bag (overwritten), for a head whose bag
-    is itself computed (the radio head's reduce_dim).
-    Returns (hazards, S, Y_hat, A_raw, loss, risk), all detached."""
+def _stack_step_setup(seq, classifier, device, training, grad_out, accumulate):
+    """The gradient conventions shared by the one-call steps (amil_stack_nll_step, amil_stack_nll_step_group): gradients
+    go to `grad_out` (tensors in the order of [*seq.parameters(), *classifier.parameters()], `accumulate` as given) or to
+    .grad -- parameters whose .grad is None get a fresh buffer, as autograd does; when all of them are None the kernels
+    write instead of accumulate and nothing is zero-filled.  Returns (gated, stack, (Wk, bk), grads, accumulate, p_h,
+    p_att)."""
     import torch
-    from .. import ops
     lin, att = seq[0], seq[3]
     gated = isinstance(att, Attn_Net_Gated)
     Wa, ba, Wb, bb, Wc, bc = att.stack_params()
@@ -292,7 +286,7 @@ def amil_stack_nll_step(seq, classifier, x, training, Y, c, alpha, loss_scale=1.
         accumulate = len(missing) < len(live)
         if missing:
             n = sum(p.numel() for p in missing)
-            flat = (torch.zeros if accumulate else torch.empty)(n, dtype=torch.float32, device=x.device)
+            flat = (torch.zeros if accumulate else torch.empty)(n, dtype=torch.float32, device=device)
             off = 0
             for p in missing:
                 p.grad = flat[off:off + p.numel()].view_as(p)
@@ -300,11 +294,58 @@ def amil_stack_nll_step(seq, classifier, x, training, Y, c, alpha, loss_scale=1.
         grads = [None if p is None else p.grad for p in params]
     p_h = seq[2].p if training else 0.0
     p_att = 0.25 if (training and att.att_dropout) else 0.0
+    return gated, (lin.weight, lin.bias, Wa, ba, Wb, bb, Wc, bc), (classifier.weight, classifier.bias), grads, \
+        accumulate, p_h, p_att
+
+
+def amil_stack_nll_step(seq, classifier, x, training, Y, c, alpha, loss_scale=1.0, grad_out=None, accumulate=None,
+                        dx_out=None):
+    """The whole training step of one bag -- stack, classifier / hazard head, nll_surv and the backward -- as ONE C-ABI
+    call (ops.amil_nll_step), gradients of loss * loss_scale ADDED to the parameters' .grad exactly as
+    `(loss * loss_scale).backward()` would (parameters whose .grad is None get a fresh buffer, as autograd does; when
+    all of them are None the kernels write instead of accumulate and nothing is zero-filled).
+    grad_out: instead of .grad, a list of gradient tensors in the order of [*seq.parameters(), *classifier.parameters()]
+    (pipeline.BagsInFlight hands in views of a stream's gradient slot) with `accumulate` said explicitly.
+    dx_out: an [N x L] fp32 tensor that receives the gradient with respect to the bag (overwritten), for a head whose bag
+    is itself computed (the radio head's reduce_dim).
+    Returns (hazards, S, Y_hat, A_raw, loss, risk), all detached."""
+    import torch
+    from .. import ops
+    gated, stack, cls, grads, accumulate, p_h, p_att = _stack_step_setup(seq, classifier, x.device, training, grad_out,
+                                                                         accumulate)
     seed = ops.next_dropout_seed() if training else 0
     with torch.no_grad():
-        return ops.amil_nll_step(x, (lin.weight, lin.bias, Wa, ba, Wb, bb, Wc, bc), classifier.weight, classifier.bias,
+        return ops.amil_nll_step(x, stack, cls[0], cls[1],
                                  gated, Y, c, alpha, grads, loss_scale=loss_scale, accumulate=accumulate,
                                  p_h=p_h, p_att=p_att, seed=seed, dx=dx_out)
+
+
+def amil_stack_nll_step_group(seq, classifier, bags, training, Y, c, alpha, loss_scale=1.0, grad_out=None,
+                              accumulate=None, seeds=None):
+    """amil_stack_nll_step for the G bags of one accumulation window in ONE C-ABI call (ops.amil_nll_step_group): the
+    gradients of sum_g loss_g * loss_scale, with the same .grad / grad_out conventions (_stack_step_setup).  bags: a list
+    or tuple of [N_g x L] fp32 device tensors (concatenated once on the device), or a pre-concatenated pair
+    (x_cat [sum N x L] tensor, sizes: a list / tuple of ints).  In train mode one ops.next_dropout_seed() is drawn per bag,
+    in bag order -- bag g gets the masks of the g-th of G nll_step calls -- unless `seeds` gives them (the training loop
+    draws each bag's seed when the bag arrives).
+    Returns (hazards [G x K], S [G x K], Y_hat [G x 1], [A_raw [1 x N_g]], loss [G], risk [G]), all detached."""
+    import torch
+    from .. import ops
+    if (isinstance(bags, (tuple, list)) and len(bags) == 2 and torch.is_tensor(bags[0])
+            and isinstance(bags[1], (list, tuple)) and all(isinstance(n, int) for n in bags[1])):
+        x_cat, sizes = bags
+    else:
+        if not all(torch.is_tensor(b) for b in bags):
+            raise TypeError("bags: a list of [N x L] tensors or an (x_cat, sizes) pair")
+        sizes = [int(b.shape[0]) for b in bags]
+        x_cat = torch.cat(list(bags), 0) if len(bags) > 1 else bags[0]
+    gated, stack, cls, grads, accumulate, p_h, p_att = _stack_step_setup(seq, classifier, x_cat.device, training,
+                                                                         grad_out, accumulate)
+    if seeds is None:
+        seeds = [ops.next_dropout_seed() for _ in sizes] if training else None
+    with torch.no_grad():
+        return ops.amil_nll_step_group(x_cat, sizes, stack, cls[0], cls[1], gated, Y, c, alpha, grads,
+                                       loss_scale=loss_scale, accumulate=accumulate, p_h=p_h, p_att=p_att, seeds=seeds)
 
 
 def amil_stack_head(seq, classifier, x, training):

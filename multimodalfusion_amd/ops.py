@@ -345,6 +345,83 @@ def amil_nll_step(x, stack, Wk, bk, gated, Y, c, alpha, grads, loss_scale=1.0, a
     return (out[K:2 * K].view(1, K), out[2 * K:3 * K].view(1, K), Y_hat, A_raw, out[3 * K].view(()), out[3 * K + 1:].view(1))
 
 
+GROUP_MAX = 64       # include/mmf_amil.h: MMF_GROUP_MAX
+
+
+def group_row_limit(L, H, D):
+    """Most rows one grouped call takes (the single-bag limits of include/mmf_amil.h applied to sum N: 32-bit mask
+    indices, every [sum N x *] operand < 2 GiB, pooling groups of <= 8192 rows)."""
+    return min(((1 << 32) - 1) // max(H, D), ((1 << 31) - 1) // (4 * max(L, 2 * D)), 256 * 8192)
+
+
+def amil_nll_step_group(x_cat, sizes, stack, Wk, bk, gated, Y, c, alpha, grads, loss_scale=1.0, accumulate=False, p_h=0.0,
+                        p_att=0.0, seeds=None, eps=1e-7):
+    """The G bags of one accumulation window in ONE C-ABI call (include/mmf_amil.h: mmf_amil_nll_step_group): the stack's
+    GEMMs run once over the concatenated rows, pooling / head / loss per bag.  x_cat: [sum N x L] fp32, the bags' rows in
+    order; sizes: the G bag sizes (host ints); Y, c: G labels / censorships; seeds: G dropout seeds (train mode).
+    grads as amil_nll_step: those of sum_g loss_g * loss_scale, added to when `accumulate`.
+    Returns (hazards [G x K], S [G x K], Y_hat [G x 1], [A_raw of bag g: [1 x N_g] views of one buffer], loss [G]
+    (unscaled), risk [G])."""
+    if x_cat.dtype != torch.float32:
+        raise _lib.MmfError("the grouped step takes fp32 bags only (bf16 bags: one amil_nll_step per bag)")
+    x_cat = _f32c(x_cat)
+    sizes = [int(n) for n in sizes]
+    G = len(sizes)
+    if G < 1 or G > GROUP_MAX:
+        raise _lib.MmfError(f"a group holds 1 .. {GROUP_MAX} bags, got {G}")
+    if min(sizes) < 1:
+        raise _lib.MmfError("empty bag in the group")
+    W1, b1, Wa, ba, Wb, bb, Wc, bc = stack
+    W1, b1, Wa, ba, Wc, bc, Wk, bk = map(_f32c, (W1, b1, Wa, ba, Wc, bc, Wk, bk))
+    Wb, bb = _f32c(Wb), _f32c(bb)
+    if x_cat.dim() != 2 or x_cat.shape[0] != sum(sizes):
+        raise _lib.MmfError(f"x_cat must be [sum N x L] = [{sum(sizes)} x L], got {tuple(x_cat.shape)}")
+    R, L = x_cat.shape
+    H, D, K = W1.shape[0], Wa.shape[0], Wk.shape[0]
+    if W1.shape[1] != L or Wa.shape[1] != H or Wc.numel() != D or Wk.shape[1] != H or K > 32:
+        raise _lib.MmfError("attention stack / classifier shapes do not match the bags")
+    dW1, db1, dWa, dba, dWb, dbb, dWc, dbc, dWk, dbk = grads
+    for g_, w_ in ((dW1, W1), (db1, b1), (dWa, Wa), (dba, ba), (dWc, Wc), (dbc, bc), (dWk, Wk), (dbk, bk)) + \
+            (((dWb, Wb), (dbb, bb)) if gated else ()):
+        if g_ is None or g_.dtype != torch.float32 or g_.shape != w_.shape or not g_.is_contiguous():
+            raise _lib.MmfError("gradient buffers must be contiguous float32 tensors shaped like their parameters")
+    dev = x_cat.device
+    Y = torch.as_tensor(Y).reshape(-1)
+    c = torch.as_tensor(c).reshape(-1)
+    if Y.numel() != G or c.numel() != G:
+        raise _lib.MmfError(f"{G} bags need {G} labels and censorships, got {Y.numel()} / {c.numel()}")
+    if not Y.is_cuda and bool(((Y < 0) | (Y >= K)).any()):
+        raise IndexError(f"nll_surv: label out of range [0, {K})")
+    Y = Y.to(device=dev, dtype=torch.int64).contiguous()
+    c = c.to(device=dev, dtype=torch.float32).contiguous()
+    seeds = [0] * G if seeds is None else [int(v) & 0xFFFFFFFF for v in seeds]
+    if len(seeds) != G:
+        raise _lib.MmfError(f"{G} bags need {G} dropout seeds")
+    offs = (C.c_int64 * (G + 1))()
+    for i, n in enumerate(sizes):
+        offs[i + 1] = offs[i] + n
+    sd = (C.c_uint32 * G)(*seeds)
+    grp = _lib.BagGroup(G=G, offsets=offs, seeds=sd)
+    d = _amil_desc(R, L, H, D, gated, W1, b1, Wa, ba, Wb, bb, Wc, bc, p_h, p_att, 0, _seed_word)
+    l = lib()
+    nbytes = l.mmf_amil_group_workspace_bytes(offs, G, L, H, D, d.gated)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    A_raw = torch.empty((R,), dtype=torch.float32, device=dev)
+    logits, hz, S = torch.empty((G, K), device=dev), torch.empty((G, K), device=dev), torch.empty((G, K), device=dev)
+    loss, risk = torch.empty((G,), device=dev), torch.empty((G,), device=dev)
+    Y_hat = torch.empty((G, 1), dtype=torch.int64, device=dev)
+    hd = SurvHead(Wk=ptr(Wk), bk=ptr(bk), K=K, logits=ptr(logits), hazards=ptr(hz), S=ptr(S), Y_hat=ptr(Y_hat),
+                  risk=ptr(risk))
+    tg = NllTarget(Y=ptr(Y), c=ptr(c), alpha=float(alpha), eps=float(eps), loss_scale=float(loss_scale),
+                   loss=ptr(loss), dWk=ptr(dWk), dbk=ptr(dbk), accumulate=1 if accumulate else 0)
+    g = AmilGrads(dW1=ptr(dW1), db1=ptr(db1), dWa=ptr(dWa), dba=ptr(dba), dWb=ptr(dWb) if gated else None,
+                  dbb=ptr(dbb) if gated else None, dWc=ptr(dWc), dbc=ptr(dbc), dx=None)
+    check(l.mmf_amil_nll_step_group(C.byref(d), C.byref(grp), ptr(x_cat), ptr(ws), nbytes, C.byref(hd), C.byref(tg),
+                                    ptr(A_raw), C.byref(g), stream_ptr()), "mmf_amil_nll_step_group")
+    A_list = [v.view(1, -1) for v in torch.split(A_raw, sizes)]
+    return hz, S, Y_hat, A_list, loss, risk
+
+
 def amil_head(x, W1, b1, Wa, ba, Wb, bb, Wc, bc, Wk, bk, gated, p_h=0.0, p_att=0.0, seed=0):
     if not torch.is_grad_enabled() and p_h == 0.0 and p_att == 0.0:       # inference consumers: no-save kernels
         M, A_raw = amil_infer(x, W1, b1, Wa, ba, Wb, bb, Wc, bc, gated)

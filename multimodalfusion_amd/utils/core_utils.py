@@ -163,6 +163,52 @@ class _Window:
         return True
 
 
+class _BagGroup:
+    """train_loop_survival(group=True): the eligible bags of the current window, held on the device until one grouped
+    call (model.nll_step_group) runs them.  Each bag is copied straight into its rows of one reusable device buffer (no
+    concatenation pass); its dropout seed is drawn when it arrives, so bag g of the loader gets the masks the per-bag
+    route gives it.  A bag that would take the group past ops.GROUP_MAX bags or the row limit flushes what is held first
+    (the window then runs as several grouped calls, accumulating)."""
+
+    def __init__(self):
+        self.buf = None
+        self.reset()
+
+    def reset(self):
+        self.rows, self.sizes, self.labels, self.cs, self.seeds, self.slots = 0, [], [], [], [], []
+
+    def add(self, model, x, label, c, seed, slot, device, flush):
+        from .. import ops
+        n, L = int(x.shape[0]), int(x.shape[1])
+        lin, att = model.attention_net_WSI[0], model.attention_net_WSI[3]
+        limit = ops.group_row_limit(L, lin.out_features, att.stack_params()[0].shape[0])
+        if self.sizes and (len(self.sizes) >= ops.GROUP_MAX or self.rows + n > limit):
+            flush()
+        need = self.rows + n
+        if self.buf is None or self.buf.shape[1] != L or self.buf.shape[0] < need or self.buf.device != device:
+            grown = torch.empty((max(need, 2 * self.buf.shape[0] if self.buf is not None else need), L),
+                                dtype=torch.float32, device=device)
+            if self.rows:
+                grown[:self.rows].copy_(self.buf[:self.rows])
+            self.buf = grown
+        self.buf[self.rows:need].copy_(x, non_blocking=True)
+        self.rows = need
+        self.sizes.append(n); self.labels.append(label.reshape(1)); self.cs.append(c.reshape(1))
+        self.seeds.append(seed); self.slots.append(slot)
+
+    def run(self, model, alpha, loss_scale):
+        """One grouped call over the held bags -> [(loader slot, loss [1], risk [1])]; the group is empty afterwards."""
+        if not self.sizes:
+            return []
+        seeds = self.seeds if model.training else None
+        _, _, _, _, loss, risk = model.nll_step_group((self.buf[:self.rows], list(self.sizes)), torch.cat(self.labels),
+                                                      torch.cat(self.cs), alpha=alpha, loss_scale=loss_scale,
+                                                      seeds=seeds)
+        out = [(slot, loss[g:g + 1], risk[g:g + 1]) for g, slot in enumerate(self.slots)]
+        self.reset()
+        return out
+
+
 def _window_of(model, optimizer, world, grad_buffer, inflight, device):
     key = (world, inflight, id(model))
     w = getattr(optimizer, "_mmf_window", None)
@@ -249,7 +295,7 @@ def _fused_mm_ok(model, loss_fn, feats):
 
 
 def train_loop_survival(epoch, model, loader, optimizer, n_classes, mode, writer=None, loss_fn=None, reg_fn=None,
-                        lambda_reg=0., gc=16, t_bin=None, dp=False, grad_buffer=None, inflight=1):
+                        lambda_reg=0., gc=16, t_bin=None, dp=False, grad_buffer=None, inflight=1, group=False):
     """utils/core_utils.py:173-264: same per-bag order (forward, loss, regulariser added AFTER the /gc division,
     backward), and the same window rule -- the optimizer steps after loader position b when (b + 1) % gc == 0 and bag b
     was not skipped; skipped bags (missing modality) contribute nothing but still occupy their position.
@@ -261,7 +307,14 @@ def train_loop_survival(epoch, model, loader, optimizer, n_classes, mode, writer
                 issues exactly one collective per window boundary, whatever it skipped;
       FlatAdam  fused L1 + Adam tail (optim.py); reg_fn must then be l1_reg_all, or l1_reg_modules with a FlatAdam
                 built with the matching `l1_modules`;
-      inflight  > 1 (needs FlatAdam): the window's bags run round-robin on that many HIP streams (pipeline.py)."""
+      inflight  > 1 (needs FlatAdam): the window's bags run round-robin on that many HIP streams (pipeline.py);
+      group     the pathology head's fp32 bags (those the one-call step takes, exact-fp32 GEMMs) are held on the device as
+                they arrive and run as ONE grouped call per window (model.nll_step_group: one launch chain over their
+                concatenated rows), issued before the window's boundary and, for a trailing partial window, at the end
+                of the epoch; more than ops.GROUP_MAX bags or the row limit split it into several calls.  Each bag's
+                dropout seed is drawn when it arrives; a bag the grouped call does not take flushes the group and runs
+                alone.  Losses and risks are logged in loader order as before.  Not with inflight > 1 or dp on several
+                ranks."""
     from ..feed import RankShard
     from .utils import l1_reg_all, l1_reg_modules
     device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
@@ -269,6 +322,10 @@ def train_loop_survival(epoch, model, loader, optimizer, n_classes, mode, writer
     world, rank = 1, 0
     if dp and torch.distributed.is_available() and torch.distributed.is_initialized():
         world, rank = torch.distributed.get_world_size(), torch.distributed.get_rank()
+    if group and inflight > 1:
+        raise ValueError("group=True runs a window as one grouped call: not together with inflight > 1")
+    if group and world > 1:
+        raise ValueError("group=True is single-GPU for now: not together with dp on several ranks")
     win = _window_of(model, optimizer, world, grad_buffer, inflight, device)
     fused_tail, pipe = win.fused, win.pipe
     if fused_tail:
@@ -283,6 +340,18 @@ def train_loop_survival(epoch, model, loader, optimizer, n_classes, mode, writer
     n_total = shard.n_total if shard is not None else None
     losses, regs, all_risk, all_c, all_t = [], [], [], [], []
     n_pos = 0
+    held = None
+    if group:
+        from .. import ops
+        held = getattr(win, "group", None)
+        if held is None:
+            held = win.group = _BagGroup()
+        alpha_g = getattr(loss_fn, "alpha", 0.0)
+
+        def flush():      # the held bags' losses / risks land in their loader slots
+            for slot, loss_g, risk_g in held.run(model, alpha_g, 1.0 / G):
+                losses[slot] = loss_g.reshape(())
+                all_risk[slot] = risk_g.reshape(-1)
     for i, batch in enumerate(shard if shard is not None else loader):
         radio_features, path_features, genomic_features, label, event_time, c = batch
         pos = shard.position(i) if shard is not None else i
@@ -294,7 +363,11 @@ def train_loop_survival(epoch, model, loader, optimizer, n_classes, mode, writer
                 # the reference's gather (utils/loss_utils.py:30-33) raises on such a label; on the device the kernels
                 # would write a NaN loss instead, which only shows in the epoch mean -- so check while it is on the host
                 raise IndexError(f"survival bin label {label.tolist()} outside [0, {n_classes})")
-            feats, label, c = _to_device(radio_features, path_features, genomic_features, label, c, device)
+            # group: a host bag goes straight from the loader into its rows of the group buffer (an empty slice of it
+            # stands in while the route is decided)
+            direct = group and torch.is_tensor(path_features) and not path_features.is_cuda
+            feats, label, c = _to_device(radio_features, path_features[:0] if direct else path_features,
+                                         genomic_features, label, c, device)
 
             def forward_loss():
                 hazards, S, Y_hat, _ = model(**feats)
@@ -305,11 +378,21 @@ def train_loop_survival(epoch, model, loader, optimizer, n_classes, mode, writer
                 raise NotImplementedError(type(loss_fn))
 
             fused_step = _fused_step_ok(model, loss_fn, feats)
+            grouped = group and fused_step and feats["path_features"].dtype == torch.float32 and ops._gemm == 0
+            if group and not grouped:
+                flush()                  # the bags held so far run first: the window keeps loader order
+                if direct:
+                    feats["path_features"] = path_features.to(device, non_blocking=True)
             fused_cox = (not fused_step) and pipe is None and _fused_cox_ok(model, loss_fn, feats)
             fused_mm = (not fused_step) and (not fused_cox) and pipe is None and _fused_mm_ok(model, loss_fn, feats)
             fused_radio = (not fused_step) and (not fused_cox) and (not fused_mm) and pipe is None \
                 and _fused_radio_ok(model, loss_fn, feats)
-            if fused_radio:
+            if grouped:
+                # held for the window's grouped call; its loss and risk fill these slots when the group runs
+                held.add(model, path_features if direct else feats["path_features"], label, c,
+                         ops.next_dropout_seed() if model.training else 0, len(losses), device, flush)
+                loss = risk = None
+            elif fused_radio:
                 _, _, _, _, loss, risk = model.nll_step(label, c, alpha=loss_fn.alpha, loss_scale=1.0 / G, **feats)
                 fused_step = True
             elif fused_mm:
@@ -345,13 +428,13 @@ def train_loop_survival(epoch, model, loader, optimizer, n_classes, mode, writer
                 loss_reg = optimizer.l1_value() if (reg_fn is not None and lambda_reg) else 0
             else:
                 loss_reg = 0 if reg_fn is None else reg_fn(model) * lambda_reg
-            losses.append(loss.detach())
+            losses.append(None if grouped else loss.detach())
             regs.append(loss_reg.detach() if torch.is_tensor(loss_reg) else torch.tensor(float(loss_reg), device=device))
-            all_risk.append(risk.detach().reshape(-1))
+            all_risk.append(None if grouped else risk.detach().reshape(-1))
             all_c.append(c.detach().reshape(-1))
             all_t.append(np.asarray(event_time).reshape(-1))
             # the reference: loss = loss / gc + loss_reg ; backward (core_utils.py:242-243)
-            if fused_step:
+            if fused_step or grouped:
                 if not fused_tail and torch.is_tensor(loss_reg) and loss_reg.requires_grad:
                     loss_reg.backward()          # the autograd L1 term touches parameters only
             elif pipe is None:
@@ -361,7 +444,11 @@ def train_loop_survival(epoch, model, loader, optimizer, n_classes, mode, writer
         # (batch_idx + 1) % gc == 0.  With world > 1 `last` belongs to rank world - 1 and must exist in the loader.
         last = pos + (world - 1 - rank)
         if (last + 1) % G == 0 and (n_total is None or last < n_total):
+            if group:
+                flush()
             win.boundary(last_bag_ran=(not skipped) if rank == world - 1 else False)
+    if group:
+        flush()                      # a trailing partial window: run, accumulated and not stepped, as in the reference
     if pipe is not None:
         pipe.join()                  # the epoch's statistics below read tensors produced on the side streams
         win.fold()                   # a trailing partial window stays accumulated in the bucket, as in the reference

@@ -1,0 +1,48 @@
+"""Compare the gfx950 assembly of two `build.py --keep-temps` builds kernel by kernel: which kernels of the first build
+are instruction for instruction the same in the second.  Labels, comments and the kernel's own (mangled) name are
+normalised; a kernel whose name gained a defaulted template argument (`..., false>` / `..., -1, false>`) is matched to
+its new name.  Metadata lines (.amdhsa_*) are reported separately from instructions.
+usage: isa_diff.py OLD_BUILD_DIR NEW_BUILD_DIR [UNIT ...]   (units default: mmf_amil_fwd mmf_amil_bwd)"""
+import difflib
+import os
+import re
+import sys
+
+
+def kernels(path):
+    out = {}
+    for m in re.finditer(r"; -- Begin function (\S+)\n(.*?); -- End function", open(path).read(), re.S):
+        body = re.sub(r"\.Lfunc_end\d+|\.LBB\d+_\d+|\.Ltmp\d+", "L", m.group(2).replace(m.group(1), "FN"))
+        lines = [l.split(";")[0].rstrip() for l in body.splitlines()]
+        out[m.group(1)] = [l for l in lines if l]
+    return out
+
+
+def main():
+    old, new = sys.argv[1], sys.argv[2]
+    units = sys.argv[3:] or ["mmf_amil_fwd", "mmf_amil_bwd"]
+    for u in units:
+        f = f"{u}-hip-amdgcn-amd-amdhsa-gfx950.s"
+        a, b = kernels(os.path.join(old, f)), kernels(os.path.join(new, f))
+        same = meta_only = 0
+        for k, v in sorted(a.items()):
+            cands = [n for n in b if n == k or n.replace("Lb0EEEv", "EEv") == k or n.replace("ELb0EEEvNS", "EEvNS") == k]
+            if not cands:
+                print(f"{u}: {k}: not found in the new build")
+                continue
+            w = b[cands[0]]
+            if w == v:
+                same += 1
+                continue
+            d = [l for l in difflib.unified_diff(v, w, lineterm="", n=0) if not l.startswith(("---", "+++", "@@"))]
+            if all(".amdhsa_" in l for l in d):
+                meta_only += 1
+                print(f"{u}: {k}: instructions identical; metadata {' / '.join(l.strip() for l in d)}")
+            else:
+                print(f"{u}: {k}: {sum(1 for l in d if l.startswith('-'))} lines -> {sum(1 for l in d if l.startswith('+'))}")
+        print(f"{u}: {len(a)} kernels: {same} identical, {meta_only} identical instructions (metadata differs), "
+              f"{len(a) - same - meta_only} differ")
+
+
+if __name__ == "__main__":
+    main()
