@@ -65,16 +65,21 @@ def build(force: bool = False, keep_temps: bool = False, verbose: bool = True) -
     if keep_temps:
         # static checks of the hand-synchronised kernels in the ISA just written (tools/isa_check.py): no instruction may touch
         # the destination of a hand-issued load before its hand-placed wait, the waits must be covered by younger VM
-        # operations, no scratch beside a hand-counted queue, no packed-fp32 VALU in the two units built without SLP
+        # operations, no scratch beside a hand-counted queue, no packed-fp32 VALU in the two units built without SLP;
+        # and in every unit, no device-scope store may reach an atomic (a grid barrier's or a K-split ticket) unwaited
         tools = os.path.join(os.path.dirname(HERE), "tools")
         if os.path.exists(os.path.join(tools, "isa_check.py")):
             sys.path.insert(0, tools)
             import isa_check
-            units = [os.path.join(OBJ, u + "-hip-amdgcn-amd-amdhsa-gfx950.s") for u in ("mmf_amil_bf16_fwd2", "mmf_amil_bf16_dh2")]
             bad = []
-            for u in units:
-                if os.path.exists(u):
-                    bad += isa_check.check_file(u, verbose=verbose)
+            for s in srcs:
+                u = os.path.join(OBJ, s.replace(".hip", "") + "-hip-amdgcn-amd-amdhsa-gfx950.s")
+                if not os.path.exists(u):
+                    continue
+                if s in ("mmf_amil_bf16_fwd2.hip", "mmf_amil_bf16_dh2.hip"):
+                    bad += isa_check.check_file(u, verbose=verbose)          # rules 1 - 4
+                else:
+                    bad += isa_check.check_handoff_file(u, verbose=verbose)  # rule 4
             if bad:
                 raise RuntimeError("ISA check failed:\n  " + "\n  ".join(bad))
     if jobs or force or _stale(LIB, objs):

@@ -48,9 +48,11 @@ __device__ inline MxDrop mx_drop(float p) {
 }
 
 // FENCED = false: nothing but values written with device-scope stores and read with device-scope loads crosses this barrier
-// (the risks at barrier 1), so the release / acquire fences -- an L2 write-back and an invalidate -- are left out: the
-// __syncthreads in front has waited for the stores (workgroup-scope release = vmcnt(0); a device-scope store is complete when
-// it is visible at the coherent level), the ticket is an agent-scope atomic.
+// (the risks at barrier 1), so the release / acquire fences -- an L2 write-back and an invalidate -- are left out.  The
+// CALLER orders those stores before the ticket: the lanes that store wait for them (s_waitcnt vmcnt(0); a device-scope store
+// is complete when it is visible at the coherent level) before they reach the __syncthreads in front, and thread 0 takes
+// the agent-scope ticket only behind that barrier.  The __syncthreads itself waits for no global store: a workgroup-scope
+// release is no vmcnt wait on gfx950 (tools/isa_check.py, rule 4).
 // `mid` runs on every thread between the two workgroup barriers, i.e. while thread 0 takes its ticket and polls: loads that
 // depend on nothing another workgroup writes are requested there and travel during the wait.
 template <bool FENCED = true, class Mid>
@@ -85,7 +87,8 @@ constexpr int MX_WP = 68;
 #define MX_ISSUE_FENCE() do { asm volatile("" ::: "memory"); __builtin_amdgcn_sched_barrier(0); } while (0)
 typedef float mx_v4f __attribute__((ext_vector_type(4)));
 // The risks, all that crosses barrier 1, are written and read at DEVICE scope (the sc1 bit: through to / from the level the
-// XCDs' L2s are coherent at), so that barrier needs no L2 write-back / invalidate around its ticket.
+// XCDs' L2s are coherent at), so that barrier needs no L2 write-back / invalidate around its ticket.  A relaxed store is not
+// waited for by anything that follows it: the writer waits for it by hand before the barrier (mx_grid_barrier<false>).
 __device__ inline void mx_st_dev(float* p, float v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ inline float mx_ld_dev(const float* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 // v_mfma_f32_4x4x1 with CBSZ = 4: the A values of block ABID (lanes 4 ABID .. 4 ABID + 3) serve all 16 blocks.  A register
@@ -332,8 +335,10 @@ __global__ __launch_bounds__(256) void maxnet_cox_step_kernel(MaxnetStepParams p
     for (int r = 0; r < R; ++r) red[wave * R + r] = part[r];
   }
   __syncthreads();
-  if (tid < R && r0 + tid < B)       // device-scope store: every workgroup reads every risk right behind barrier 1
+  if (tid < R && r0 + tid < B) {     // device-scope store: every workgroup reads every risk right behind barrier 1
     mx_st_dev(p.risk + r0 + tid, red[tid] + red[R + tid] + red[2 * R + tid] + red[3 * R + tid] + bcv);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // landed before the barrier, and with it before the ticket; ahead of
+  }                                                      // mid(), so that its prefetch loads are not held back by it
   MX_STAMP(2);
   constexpr int SG3 = 32;
   float w3[2][SG3];                             // dy0's first two stages of W1 rows (phase 3), requested while the barrier waits

@@ -81,19 +81,32 @@ def test_group_matches_oracle_per_bag(sizes, gated, K, train, dropout, monkeypat
     G = len(sizes)
     scale = 1.0 / G
     res, _, _ = run_group(metas, monkeypatch, scale)
-    gsum, kinks = None, set()
-    for g, mm in enumerate(metas):
-        ref = cases.run_path(mm)
-        one = dict(hazards=res["hazards"][g:g + 1], S=res["S"][g:g + 1], A_raw=res["A"][g], loss=float(res["loss"][g]),
-                   grads={})
-        compare(one, dict(ref, grads={}), f"bag {g}")
-        assert abs(float(res["risk"][g]) + float(res["S"][g].sum())) < 1e-5
-        gsum = {k: scale * v for k, v in ref["grads"].items()} if gsum is None else \
-            {k: gsum[k] + scale * v for k, v in ref["grads"].items()}
+    check_group(res, scale, *group_oracle(metas))
+
+
+def group_oracle(metas):
+    """-> (the fp64 oracle of each bag alone, the union of the bags' ReLU-kink units)"""
+    refs, kinks = [], set()
+    for mm in metas:
+        refs.append(cases.run_path(mm))
         sd, x, _ = cases.path_inputs(mm)
         kinks |= relu_kink_units(sd, x)
+    return refs, kinks
+
+
+def check_group(res, scale, refs, kinks, tag=""):
+    """A grouped step's results (run_group's layout) per bag against that bag's oracle, and its gradients against the
+    oracle's sum_g scale * grads_g."""
+    gsum = None
+    for g, ref in enumerate(refs):
+        one = dict(hazards=res["hazards"][g:g + 1], S=res["S"][g:g + 1], A_raw=res["A"][g], loss=float(res["loss"][g]),
+                   grads={})
+        compare(one, dict(ref, grads={}), f"{tag}bag {g}")
+        assert abs(float(res["risk"][g]) + float(res["S"][g].sum())) < 1e-5, f"{tag}bag {g}"
+        gsum = {k: scale * v for k, v in ref["grads"].items()} if gsum is None else \
+            {k: gsum[k] + scale * v for k, v in ref["grads"].items()}
     compare(dict(hazards=0, S=0, A_raw=0, loss=0.0, grads=res["grads"]), dict(hazards=0, S=0, A_raw=0, loss=0.0, grads=gsum),
-            "summed grads", kink_units=kinks)
+            f"{tag}summed grads", kink_units=kinks)
 
 
 @pytest.mark.parametrize("sizes,gated,K,train,dropout", [CASES[0], CASES[1], CASES[5], CASES[7]])

@@ -17,6 +17,18 @@ the asm statement, the data lands later.  That is only correct if
 
 It also reports packed-fp32 VALU instructions (v_pk_*_f32) per kernel: the two hand-scheduled bf16 kernels are built
 without SLP vectorisation (build.py: FILE_FLAGS) and must contain none.
+
+Rule 4 covers every unit (build.py runs it on all of them; rules 1-3 stay with the two bf16 units): a device-scope handoff
+must be ordered before the ticket that announces it.  A value another workgroup reads right behind a grid barrier or a
+K-split ticket is written with a device-scope store (the sc1 bit), and its writer may only take the ticket (an atomic)
+once that store has completed.  A workgroup barrier does not wait for it: on gfx950 a workgroup-scope release is no
+vmcnt wait at all.  Within one kernel, in text order,
+
+  4. a global_/buffer_/flat_store* carrying sc1 opens a pending handoff; an s_waitcnt with vmcnt(0) closes it (vmcnt(N),
+     N > 0, does not); a global_/buffer_/flat_atomic* while a handoff is pending is a finding, which names the kernel, the
+     store's line and the atomic's line.
+
+HANDOFF_ALLOW lists kernels whose flagged handoff is ordered some other way, each with the reason.
 """
 import os
 import re
@@ -27,6 +39,9 @@ DEFAULT = [os.path.join(ROOT, "multimodalfusion_amd", "_build", u + "-hip-amdgcn
            for u in ("mmf_amil_bf16_fwd2", "mmf_amil_bf16_dh2")]
 NO_PACKED = ("amil_fwd_fused2_bf16_kernel", "dh2_bf16_kernel")       # kernels that must hold no v_pk_*_f32
 NO_SCRATCH = ("amil_fwd_fused2_bf16_kernel",)                          # kernels whose hand-counted queue forbids scratch
+
+# kernel-name substring -> why its sc1 store ... atomic sequence is ordered although no vmcnt(0) lies between them
+HANDOFF_ALLOW = {}
 
 REG = re.compile(r"\bv(\d+)\b|\bv\[(\d+):(\d+)\]")
 
@@ -137,6 +152,40 @@ def check_kernel(name, body, scratch_bytes):
     return bad, n_loads, n_waits
 
 
+DEV_STORE = re.compile(r"(global|buffer|flat)_store\w*\s.*\bsc1\b")
+ATOMIC = re.compile(r"(global|buffer|flat)_atomic\w*\s")
+VMCNT0 = re.compile(r"\bvmcnt\(0\)")
+
+
+def check_handoffs(name, body):
+    """Rule 4 on one kernel -> list of violation strings."""
+    if any(k in name for k in HANDOFF_ALLOW):
+        return []
+    bad, pending = [], None
+    for ln, t, _ in body:
+        if t.startswith("s_waitcnt") and VMCNT0.search(t):
+            pending = None
+        elif DEV_STORE.match(t):
+            pending = pending or ln
+        elif ATOMIC.match(t) and pending is not None:
+            bad.append(f"{name}: device-scope store at line {pending} reaches the atomic at line {ln} with no "
+                       f"s_waitcnt vmcnt(0) between them")
+    return bad
+
+
+def check_handoff_file(path, verbose=True):
+    """Rule 4 alone on every kernel of one .s file (build.py --keep-temps: every unit)."""
+    bad = []
+    ks = kernels(open(path).read())
+    for name, body in ks.items():
+        bad += check_handoffs(name, body)
+    if verbose:
+        n = sum(1 for body in ks.values() for _, t, _ in body if DEV_STORE.match(t))
+        print(f"{os.path.basename(path)[:28]}: {len(ks)} kernels, {n} device-scope stores -> "
+              f"{'OK' if not bad else str(len(bad)) + ' unordered handoffs'}")
+    return bad
+
+
 def scratch_sizes(s):
     out = {}
     for m in re.finditer(r"\.amdhsa_kernel (\S+)(.*?)\.end_amdhsa_kernel", s, re.S):
@@ -151,6 +200,7 @@ def check_file(path, verbose=True):
     bad_all = []
     for name, body in kernels(s).items():
         bad, nl, nw = check_kernel(name, body, sc.get(name))
+        bad += check_handoffs(name, body)
         npk = sum(1 for _, t, _ in body if re.match(r"v_pk_\w+_f32", t))
         if verbose:
             print(f"{os.path.basename(path)[:28]} {name[7:64]}: {len(body)} instructions, {nl} hand-issued loads in {nw} "
