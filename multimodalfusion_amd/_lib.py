@@ -10,7 +10,7 @@ import ctypes as C
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("MMF_LIB_PATH") or os.path.join(_HERE, "libmmf_amil.so")   # override: diagnostic builds only
+LIB_PATH = os.environ.get("MMF_LIB_PATH") or os.path.join(_HERE, "libmmf_amil.so")   # override: the tuning build (tools/diag_build.py)
 
 ABI_VERSION = 12
 
@@ -168,10 +168,6 @@ SYMBOLS = {
     "mmf_trace_destroy": (None, [C.c_void_p]),
     "mmf_trace_dump": (C.c_int, [C.c_void_p, C.c_char_p, C.c_size_t]),
 }
-# exported by the diagnostic builds only (tools/diag_build.py, -DMMF_STAMPS)
-DIAG_SYMBOLS = {
-    "mmf_debug_stamps": (None, [C.c_int, C.POINTER(C.c_uint64)]),
-}
 
 
 class KernelTrace:
@@ -234,11 +230,6 @@ def lib() -> C.CDLL:
             fn = getattr(l, name)          # AttributeError if the symbol is not exported
             fn.restype = res
             fn.argtypes = args
-        for name, (res, args) in DIAG_SYMBOLS.items():
-            if hasattr(l, name):
-                fn = getattr(l, name)
-                fn.restype = res
-                fn.argtypes = args
         v = l.mmf_abi_version()
         if v != ABI_VERSION:
             raise MmfError(f"libmmf_amil.so ABI version {v}, binding expects {ABI_VERSION}: rebuild")

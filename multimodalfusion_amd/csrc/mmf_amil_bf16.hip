@@ -20,37 +20,6 @@
 
 namespace mmf {
 
-// Diagnostic build only (-DMMF_STAMPS): per-kernel phase cycles, kernel k in slots [8k, 8k+8):
-// {prologue, main loop, epilogue, -, -, -, -, waves}.  The shipped library contains none of this.
-#ifdef MMF_STAMPS
-static __device__ unsigned long long g_bst[32];
-__device__ inline unsigned long long real_now() {      // constant 100 MHz counter: calibrates the shader clock
-  unsigned long long t;
-  asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-  return t;
-}
-#define BST_BEGIN() unsigned long long bst_real = real_now(), bst_prev = stamp_now(), bst_t
-#define BST_MARK(k, slot) do { bst_t = stamp_now(); if ((threadIdx.x & 63) == 0) atomicAdd(&g_bst[8 * (k) + (slot)], bst_t - bst_prev); bst_prev = bst_t; } while (0)
-#define BST_COUNT(k) do { if ((threadIdx.x & 63) == 0) { atomicAdd(&g_bst[8 * (k) + 7], 1ull); atomicAdd(&g_bst[8 * (k) + 6], real_now() - bst_real); } } while (0)
-#else
-#define BST_BEGIN()
-#define BST_MARK(k, slot)
-#define BST_COUNT(k)
-#endif
-enum { BST_LIN = 0, BST_GATE = 1, BST_DH = 2, BST_TN = 3 };   // the fused forward uses BST_LIN: {projection loop, its epilogue, gate phase, pooling}
-
-void debug_stamps_fwd2(unsigned long long* out8);   // mmf_amil_bf16_fwd2.hip
-void debug_stamps_bf16(unsigned long long* out32) {
-#ifdef MMF_STAMPS
-  hipMemcpyFromSymbol(out32, HIP_SYMBOL(g_bst), 32 * sizeof(unsigned long long));
-  unsigned long long z[32] = {0};
-  hipMemcpyToSymbol(HIP_SYMBOL(g_bst), z, sizeof z);
-  debug_stamps_fwd2(out32);
-#else
-  for (int i = 0; i < 32; ++i) out32[i] = 0;
-#endif
-}
-
 template <class T, class P>
 static int launch_tiled_b(const char* name, void (*kern)(P), const P& p, int grid, int lds_bytes, hipStream_t st) {
   if (int e = set_dyn_lds(reinterpret_cast<const void*>(kern), lds_bytes)) return e;
@@ -125,15 +94,12 @@ __global__ __launch_bounds__(T::NT) void linear_bf16_dma_kernel(LinearBfParams p
   int mt, nt;
   if (!tile_of_block(blockIdx.x, p.mt_count, p.nt_count, mt, nt)) return;
   const int row0 = mt * T::BM, col0 = nt * T::BN;
-  BST_BEGIN();
   DmaK<T::BM, T::NT> la;
   la.init(p.x, p.K, row0, (int)p.M);
   DmaK<T::BN, T::NT> lb;
   lb.init(p.w, p.K, col0, p.N);
   f32x16 acc[T::MB][T::NB];
-  BST_MARK(BST_LIN, 0);
   gemm_mainloop_dma<T>(la, lb, p.K / 64, ldsc, acc);
-  BST_MARK(BST_LIN, 1);
   float* lds = reinterpret_cast<float*>(ldsc);
 
   const uint32_t thr = drop_threshold(p.drop_p);
@@ -163,8 +129,6 @@ __global__ __launch_bounds__(T::NT) void linear_bf16_dma_kernel(LinearBfParams p
       *reinterpret_cast<uint2*>(p.y + (size_t)row * p.N + col) = pack4(y[0], y[1], y[2], y[3]);
     }
   });
-  BST_MARK(BST_LIN, 2);
-  BST_COUNT(BST_LIN);
 }
 
 int launch_linear_bf16(LinearBfParams p, hipStream_t st) {
@@ -227,15 +191,12 @@ __global__ __launch_bounds__(T::NT) void gate_bf16_kernel(GateBfParams p) {
   int mt, nt;
   if (!tile_of_block(blockIdx.x, p.mt_count, p.nt_count, mt, nt)) return;
   const int row0 = mt * T::BM, d0 = nt * DT;
-  BST_BEGIN();
   LoadK<T::BM, T::NT> la;
   la.init(reinterpret_cast<const float*>(p.h), p.H / 2, row0, (int)p.N);
   LoadGateWB<T::BN, T::NT, GATED> lb;
   lb.init(p.Wa, p.Wb, p.H, p.D, d0);
   f32x16 acc[T::MB][T::NB];
-  BST_MARK(BST_GATE, 0);
   gemm_mainloop<T>(la, lb, p.H / 64, lds, acc);
-  BST_MARK(BST_GATE, 1);
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave / T::WN, wn = wave % T::WN;
@@ -319,8 +280,6 @@ __global__ __launch_bounds__(T::NT) void gate_bf16_kernel(GateBfParams p) {
       p.s_part[(size_t)nt * p.N + row] = s;
     }
   }
-  BST_MARK(BST_GATE, 2);
-  BST_COUNT(BST_GATE);
 }
 
 int gate_parts_bf16(int D, int gated) { return gated ? (D + 127) / 128 : (D + 255) / 256; }
@@ -449,7 +408,6 @@ __global__ __launch_bounds__(512) void amil_fwd_fused_bf16_kernel(FusedFwdParams
   float* e_l = sred + 8 * 128;                                   // [128]
   float* vred = e_l + 128;                                       // [4][256]
   float* red = vred + 4 * 256;                                   // [16]
-  BST_BEGIN();
 
   // ---------------- phase 1: u = x.W1^T (K = L), three-stage LDS-DMA pipeline -------------------------------
   f32x16 acc[T::MB][T::NB];
@@ -460,7 +418,6 @@ __global__ __launch_bounds__(512) void amil_fwd_fused_bf16_kernel(FusedFwdParams
     lb.init(p.w1, p.L, 0, 256);
     gemm_mainloop_dma<T>(la, lb, p.L / 64, lds, acc);
   }
-  BST_MARK(BST_LIN, 0);
   // the wave's stationary gate weights: B-fragments of rows 32 w + r of Wa (nb 0) and Wb (nb 1), all of K = 256;
   // issued now, consumed after the epilogue below
   float4 wfr[2][16];
@@ -517,7 +474,6 @@ __global__ __launch_bounds__(512) void amil_fwd_fused_bf16_kernel(FusedFwdParams
     wc[4 * q4] = t.x; wc[4 * q4 + 1] = t.y; wc[4 * q4 + 2] = t.z; wc[4 * q4 + 3] = t.w;
   }
   __syncthreads();                                         // h tile complete
-  BST_MARK(BST_LIN, 1);
 
   // ---------------- phase 2: [128 x 256] h tile . [64 weight rows of this wave]^T, weights in registers ----------
   const uint32_t thr_a = drop_threshold(p.p_att);
@@ -609,7 +565,6 @@ __global__ __launch_bounds__(512) void amil_fwd_fused_bf16_kernel(FusedFwdParams
     }
   }
   __syncthreads();
-  BST_MARK(BST_LIN, 2);
 
   // ---------------- scores of the tile, online-softmax partial ------------------------------------------------
   const float bc = p.bc[0];
@@ -651,8 +606,6 @@ __global__ __launch_bounds__(512) void amil_fwd_fused_bf16_kernel(FusedFwdParams
   float* out = p.partials + (size_t)mt * (2 + 256);
   if (tid < 256) out[2 + tid] = vred[tid] + vred[256 + tid] + vred[512 + tid] + vred[768 + tid];
   if (tid == 0) { out[0] = m; out[1] = red[8] + red[9]; }
-  BST_MARK(BST_LIN, 3);
-  BST_COUNT(BST_LIN);
 }
 
 int fused_fwd_tiles(int64_t N) { return (int)((N + 127) / 128); }
@@ -813,7 +766,6 @@ __global__ __launch_bounds__(T::NT) void dh_bf16_kernel(DhBfParams p) {
   float* g_l = p_l + T::BM;
   float* red = g_l + T::BM;
   float* dwc_l = red + 16;
-  BST_BEGIN();
   {
     // ---- K-prep for this tile's rows: p_i = softmax weight, ds_i = p_i (dM.h_i - dM.M) + gA_i ----------
     // g_i = dM.h_i: every wave takes BM/NW rows; lanes cover 16-byte pieces of h, 8 independent loads in flight
@@ -907,9 +859,7 @@ __global__ __launch_bounds__(T::NT) void dh_bf16_kernel(DhBfParams p) {
   LoadK<T::BN, T::NT> lb;
   lb.init(reinterpret_cast<const float*>(p.WabT), mstk / 2, col0, p.H);
   f32x16 acc[T::MB][T::NB];
-  BST_MARK(BST_DH, 0);
   gemm_mainloop<T>(la, lb, mstk / 64, lds, acc);
-  BST_MARK(BST_DH, 1);
   if (nt == 0) {                               // per-tile dWc partial: sum the waves' rows (the loop's last barrier has passed)
     for (int d = tid; d < p.g.D; d += T::NT) {
       float s = 0.f;
@@ -951,8 +901,6 @@ __global__ __launch_bounds__(T::NT) void dh_bf16_kernel(DhBfParams p) {
       *reinterpret_cast<uint2*>(p.du + (size_t)row * p.H + col) = pack4(d0, d1, d2, d3);
     }
   });
-  BST_MARK(BST_DH, 2);
-  BST_COUNT(BST_DH);
 }
 
 int dh_bf16_row_tiles(int64_t N) { return (int)((N + 127) / 128); }   // upper bound of mt_count (128-row tiles)
@@ -1100,16 +1048,9 @@ __device__ inline void tn_mainloop(LA& la, LB& lb, int nk, char* lds, f32x16 (&a
     char* cur = lds + (kt & 1) * T::STAGE_BYTES;
     char* nxt = lds + ((kt + 1) & 1) * T::STAGE_BYTES;
     const bool more = kt + 1 < nk;
-#ifdef MMF_DIAG_NOLOAD        /* diagnostic builds (tools/diag_build.py): timing only, results are wrong */
-    const bool stage = false;
-#else
-    const bool stage = more;
-#endif
-    if (stage) { la.load(kt + 1); lb.load(kt + 1); }
-#ifndef MMF_DIAG_NOMFMA
+    if (more) { la.load(kt + 1); lb.load(kt + 1); }
     tn_compute_chunk<T>(cur, cur + T::A_BYTES, acc, wm, wn, lane);
-#endif
-    if (stage) { la.store(nxt); lb.store(nxt + T::A_BYTES); }
+    if (more) { la.store(nxt); lb.store(nxt + T::A_BYTES); }
     __syncthreads();
   }
 }
@@ -1169,7 +1110,6 @@ __global__ __launch_bounds__(T::NT) void tn_bf16_kernel(TnBfParams p) {
   const int kmax = (int)((kb64 + p.k_per_split) < p.K ? (kb64 + p.k_per_split) : p.K);
   const int nk = (kmax - kbase + TNB_KCH - 1) / TNB_KCH;
   const bool do_sum = tn == 0 && q.colsum != nullptr;
-  BST_BEGIN();
 
   LoadTPlain<T::BN, T::NT, T::B_PITCH> lb;
   lb.init(q.B, q.ldb, tn * T::BN, q.Ncols, kbase, kmax, false);
@@ -1178,13 +1118,10 @@ __global__ __launch_bounds__(T::NT) void tn_bf16_kernel(TnBfParams p) {
     la.init(q.A, q.lda, tm * T::BM, q.M, kbase, kmax, do_sum);
     f32x16 acc[T::MB][T::NB];
     tn_mainloop<T>(la, lb, nk, ldsb, acc);
-    BST_MARK(BST_TN, 1);
     float* fl = reinterpret_cast<float*>(ldsb);
     tnb_store<T>(q, split, tn, acc, fl, [&](int r) { const int row = tm * T::BM + r; return row < q.M ? row : -1; });
     if (do_sum) colsum8_reduce_store<T::BM, T::NT>(fl, la.cs, q.colsum + (size_t)split * q.colsum_stride, tm * T::BM, q.M);
   }
-  BST_MARK(BST_TN, 2);
-  BST_COUNT(BST_TN);
 }
 
 int tn_bf16_splits(int64_t K, int total_tiles) {

@@ -10,7 +10,7 @@
 //             dP operand is BUILT (a, b, ds, Wc -> 2 x 8 values per thread and instance, models/model_modules.py:105-110
 //             backwards) into the other LDS stage -- and written to HBM for the TN kernel, with the dWc sums taken on the
 //             way -- in the same scheduling region as the MFMAs of chunk kt: a SIMD issues a wave's own vector instructions
-//             in the shadow of its MFMAs (tools/coissue.hip), and the build is the longer of the two.  The weights never
+//             in the shadow of its MFMAs, and the build is the longer of the two.  The weights never
 //             touch LDS: [Wa ; Wb]^T is stored in MFMA-fragment order (CvtSeg::transpose 5), a wave loads only the 64
 //             features it multiplies, 1 KB of contiguous memory per instruction, each fragment re-filled for the next
 //             chunk right behind the MFMAs that used it.

@@ -44,35 +44,6 @@ constexpr int F2_LDS_BYTES = F2_MISC + (4 * 128 + 128 + 16 + 8 * 256 + 3 * 256) 
 
 typedef float f32x4v __attribute__((ext_vector_type(4)));
 
-// Diagnostic build only (-DMMF_STAMPS): phase cycles {main loop, epilogue 1, gate phase, pooling, -, -, real time, waves}
-#ifdef MMF_STAMPS
-static __device__ unsigned long long g_bst2[8];
-__device__ inline unsigned long long real_now2() {
-  unsigned long long t;
-  asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-  return t;
-}
-#define B2_BEGIN() unsigned long long b2_real = real_now2(), b2_prev = stamp_now(), b2_t
-#define B2_MARK(slot) do { b2_t = stamp_now(); if ((threadIdx.x & 63) == 0) atomicAdd(&g_bst2[slot], b2_t - b2_prev); b2_prev = b2_t; } while (0)
-#define B2_COUNT() do { if ((threadIdx.x & 63) == 0) { atomicAdd(&g_bst2[7], 1ull); atomicAdd(&g_bst2[6], real_now2() - b2_real); } } while (0)
-#else
-#define B2_BEGIN()
-#define B2_MARK(slot)
-#define B2_COUNT()
-#endif
-void debug_stamps_fwd2(unsigned long long* out8) {       // overwrites out8 when this kernel ran since the last call
-#ifdef MMF_STAMPS
-  unsigned long long v[8];
-  hipMemcpyFromSymbol(v, HIP_SYMBOL(g_bst2), sizeof v);
-  if (v[7] == 0) return;
-  for (int i = 0; i < 8; ++i) out8[i] = v[i];
-  unsigned long long z[8] = {0};
-  hipMemcpyToSymbol(HIP_SYMBOL(g_bst2), z, sizeof z);
-#else
-  (void)out8;
-#endif
-}
-
 // A-fragment load hidden from the compiler's wait bookkeeping (the x stream's LDS-DMAs share the in-order VM
 // counter; completion is counted by hand in the main loop, cdna_hip_programming.md "mixing load KINDS in one k-loop")
 template <int IMM>
@@ -105,9 +76,6 @@ __device__ inline void f2_chunk(const char* xs, const f32x4v (&wf)[8], f32x16 (&
   for (int q = 0; q < 4; ++q) {
     if (q + 1 < 4) rd(q + 1, (q + 1) & 1);
     hook(q);                                               // vector-ALU work that rides in the MFMAs' shadow
-#ifdef MMF_F2_REV_SCHED
-    __builtin_amdgcn_sched_barrier(0);
-#endif
 #pragma unroll
     for (int fb = 0; fb < 2; ++fb)
 #pragma unroll
@@ -138,12 +106,6 @@ __global__ __launch_bounds__(256, 2) void amil_fwd_fused2_bf16_kernel(FusedFwdPa
     gpar[tid] = va; gpar[256 + tid] = vb; gpar[512 + tid] = vc;
   }
 
-#ifdef MMF_F2_DEBUG      /* timing experiments (wrong results): phases switched off by bits of MMF_F2_DEBUG_MASK */
-  const int dbg = p.stagger;
-#else
-  constexpr int dbg = 0;
-#endif
-  B2_BEGIN();
   // ---------------- phase 1: u^T = W1 . x^T (K = L) ------------------------------------------------------------
   f32x16 acc[2][4];                                               // [feature block fb][instance block ib]
 #pragma unroll
@@ -178,10 +140,7 @@ __global__ __launch_bounds__(256, 2) void amil_fwd_fused2_bf16_kernel(FusedFwdPa
       ldw_asm<0>(w[0], rw, vw0, so); ldw_asm<1024>(w[1], rw, vw0, so); ldw_asm<2048>(w[2], rw, vw0, so); ldw_asm<3072>(w[3], rw, vw0, so);
       ldw_asm<0>(w[4], rw, vw1, so); ldw_asm<1024>(w[5], rw, vw1, so); ldw_asm<2048>(w[6], rw, vw1, so); ldw_asm<3072>(w[7], rw, vw1, so);
     };
-#ifndef MMF_F2_STAGE_BASE
-#define MMF_F2_STAGE_BASE 0
-#endif
-    auto stage = [&](int kt) { return lds + MMF_F2_STAGE_BASE + (kt % 3) * F2_STAGE; };
+    auto stage = [&](int kt) { return lds + (kt % 3) * F2_STAGE; };
     const int nk = p.L / 64;                                      // even (launcher)
     // Queue order per iteration: [W(kt+1) x 8] [x(kt+2) x 4]; before chunk kt+1 is read everything up to W(kt+1) has landed
     // (vmcnt(4)), x(kt+2) may still be in flight.  The loop body is BRANCH-FREE on purpose: the weight fragments are outputs
@@ -192,10 +151,7 @@ __global__ __launch_bounds__(256, 2) void amil_fwd_fused2_bf16_kernel(FusedFwdPa
     // The streaming phase outranks the partner workgroup's vector-bound phases on the SIMD (issue is arbitrated by priority,
     // then age): its loads and MFMAs are what the memory pipe waits for.  Measured -4 us of 121; raising the vector-bound
     // phases instead changes nothing.
-#ifndef MMF_F2_PRIO
-#define MMF_F2_PRIO 1
-#endif
-    __builtin_amdgcn_s_setprio(MMF_F2_PRIO);
+    __builtin_amdgcn_s_setprio(1);
     load_w(0, wf0);
     lx.issue(0, stage(0));
     lx.issue(1, stage(1));
@@ -208,17 +164,12 @@ __global__ __launch_bounds__(256, 2) void amil_fwd_fused2_bf16_kernel(FusedFwdPa
     // epilogue only applies them.  Element e = ((fb 4 + ib) 4 + g) 4 + j of this lane is hashed in chunk e / 8.
     {
       auto iter = [&](int kt, f32x4v (&wcur)[8], f32x4v (&wnext)[8]) {
-#ifdef MMF_F2_COND_LOAD     /* diagnostic build (tools/diag_build.py f2cond*): the weight refill as a CONDITIONAL definition of the
-                               asm-loaded registers, as an intermediate round-3 version had it -- what the branch-free loop replaced */
-        if (kt + 1 < nk) load_w(kt + 1, wnext);
-#else
-        if (!(dbg & 2)) load_w(kt + 1, wnext);
-#endif
-        if (!(dbg & 1)) lx.issue(kt + 2, stage(kt + 2), kt + 2 < nk ? 0u : 0x80000000u);
+        load_w(kt + 1, wnext);
+        lx.issue(kt + 2, stage(kt + 2), kt + 2 < nk ? 0u : 0x80000000u);
         uint32_t bits = 0;
         const uint32_t sC = __builtin_amdgcn_readfirstlane((uint32_t)(((kt >> 1) & 3) * 8192 + (kt >> 3) * 32 + (kt & 1) * 16) * 0x9E3779B1u);
         __builtin_amdgcn_sched_barrier(0);
-        if (!(dbg & 4)) f2_chunk(stage(kt), wcur, acc, r, hh, [&](int q) {
+        f2_chunk(stage(kt), wcur, acc, r, hh, [&](int q) {
           if constexpr (HLOOP) {
 #pragma unroll
             for (int i2 = 0; i2 < 2; ++i2) {
@@ -237,7 +188,7 @@ __global__ __launch_bounds__(256, 2) void amil_fwd_fused2_bf16_kernel(FusedFwdPa
           km[0] |= w == 0 ? b : 0u; km[1] |= w == 1 ? b : 0u; km[2] |= w == 2 ? b : 0u; km[3] |= w == 3 ? b : 0u;
         }
         __builtin_amdgcn_sched_barrier(0);
-        if (dbg & 3) wait_vmcnt<0>(); else wait_vmcnt<4>();
+        wait_vmcnt<4>();
         // the fragments are defined HERE as far as the compiler is concerned: nothing may read or move them before the wait
         asm volatile("" : "+v"(wnext[0]), "+v"(wnext[1]), "+v"(wnext[2]), "+v"(wnext[3]), "+v"(wnext[4]), "+v"(wnext[5]), "+v"(wnext[6]), "+v"(wnext[7]));
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -255,7 +206,6 @@ __global__ __launch_bounds__(256, 2) void amil_fwd_fused2_bf16_kernel(FusedFwdPa
   }
 
   __builtin_amdgcn_s_setprio(0);
-  B2_MARK(0);
   // Everything below derives its lane-dependent addresses from a thread index the compiler cannot see through: left alone it
   // computes the epilogues' LDS / store offsets at the top of the kernel and parks them in scratch across the main loop.
   int tid_late = threadIdx.x;
@@ -300,11 +250,10 @@ __global__ __launch_bounds__(256, 2) void amil_fwd_fused2_bf16_kernel(FusedFwdPa
 #pragma unroll
   for (int s = 0; s < 16; ++s) wg0[s] = bld4(rg, vg, (unsigned)s * 1024u);
   __syncthreads();                                         // h tile complete
-  B2_MARK(1);
   // saved activations go out through buffer stores: rows beyond the bag fall outside num_records and are dropped
   // (forward-only calls: zero-size resources drop every store, so that no phase below needs a branch)
   const unsigned act_bytes = (unsigned)p.N * 512u;
-  const bool keep_h = p.h && !(dbg & 128);
+  const bool keep_h = p.h != nullptr;
   const rsrc_t rh = make_rsrc(keep_h ? (const void*)p.h : (const void*)p.x, keep_h ? act_bytes : 0u);
   const rsrc_t rsa = make_rsrc(p.a ? (const void*)p.a : (const void*)p.x, p.a ? act_bytes : 0u),
                rsb = make_rsrc(p.a ? (const void*)p.b : (const void*)p.x, p.a ? act_bytes : 0u);
@@ -315,7 +264,7 @@ __global__ __launch_bounds__(256, 2) void amil_fwd_fused2_bf16_kernel(FusedFwdPa
   // i < 8 is pre-tanh, i >= 8 pre-sigmoid of dim dbase + 8 ((i >> 2) & 1) + 4 hh + (i & 3)), then its activations:
   // 32 quarter-rate instructions (exp2, rcp) and ~120 others -- tanh / sigmoid, bf16 rounding, a / b stores (16
   // contiguous bytes per lane after the half swap), score partial: about twice the block's MFMA time.  A SIMD does not run
-  // one wave's vector work beside its partner's dense MFMA stream (tools/coissue.hip), but it does issue a wave's OWN
+  // one wave's vector work beside its partner's dense MFMA stream, but it does issue a wave's OWN
   // vector instructions in the shadow of that wave's MFMAs.  So block k's 16 (dependent) MFMAs are issued one by one
   // with ONE SLICE of block k - 1's activations behind each -- one activation of one accumulator element per slice, the
   // slices pinned in place (sched_barrier): left to itself the scheduler bunched the vector work into runs of 150-300
@@ -366,24 +315,11 @@ __global__ __launch_bounds__(256, 2) void amil_fwd_fused2_bf16_kernel(FusedFwdPa
 #pragma unroll
       for (int s = 0; s < 16; ++s) {
         fh[(s + 3) & 3] = *reinterpret_cast<const float4*>(hb + (s + 3 < 16 ? ibM : ibN) * 32 * F2_HROW + 32 * ((s + 3) & 15));
-#ifndef MMF_F2_GATE_NOMM      /* diagnostic builds (wrong results): the gate phase without its MFMAs / without its activations */
         accM = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_of(w[s]), frag_of(fh[s & 3]), accM, 0, 0, 0);
-#else
-        asm volatile("" :: "v"(w[s].x), "v"(fh[s & 3].x));
-#endif
-#ifdef MMF_F2_GATE_NOACT
-        if (MODE == 1) { if (s == 0) sc[ibA] += accA[0] + accA[15]; } else
-#endif
         if constexpr (MODE == 0) {                         // whole 512-byte rows of h per wave instruction
           const int R = 8 * s + (tid >> 5), c = tid & 31;
           const float4 v = *reinterpret_cast<const float4*>(lds + F2_HIMG + R * F2_HROW + 16 * c);
-#ifndef MMF_F2_NOHSTORE
           bst4(rh, (unsigned)(row0 + R) * 512u + 16u * (unsigned)c, v);
-#else
-          asm volatile("" :: "v"(v.x), "v"(v.y), "v"(v.z), "v"(v.w));
-#endif
-        } else if (dbg & 16) {
-          if (s == 0) sc[ibA] += accA[0] + accA[15];
         } else {
           // Element e = 0..15 of the block: g = e >> 3 (dims 8 g ..), j = (e >> 1) & 3, even e: tanh of accA[4 g + j], odd e:
           // sigmoid of accA[8 + 4 g + j].  An activation is a dependent chain (scale, exp2, 1 +, rcp, [2 x - 1]) of long-latency
@@ -440,41 +376,33 @@ __global__ __launch_bounds__(256, 2) void amil_fwd_fused2_bf16_kernel(FusedFwdPa
               ob[q] = sb[0]; ob[2 + q] = sb[1];
             }
             const unsigned o = (unsigned)row * 512u + (unsigned)(dbA + 8 * hl) * 2u;
-#ifndef MMF_F2_NOSTORE
             bst4(rsa, o, make_float4(__uint_as_float(oa[0]), __uint_as_float(oa[1]), __uint_as_float(oa[2]), __uint_as_float(oa[3])));
             bst4(rsb, o, make_float4(__uint_as_float(ob[0]), __uint_as_float(ob[1]), __uint_as_float(ob[2]), __uint_as_float(ob[3])));
-#else
-            asm volatile("" :: "v"(oa[0]), "v"(oa[1]), "v"(oa[2]), "v"(oa[3]), "v"(ob[0]), "v"(ob[1]), "v"(ob[2]), "v"(ob[3]), "v"(o));
-#endif
           }
         }
-#ifndef MMF_F2_GATE_NOWN
         if (s >= 8 && s < 12) wn[4 * slot + s - 8] = bld4(rg, vg, nw + (unsigned)((4 * slot + s - 8) * 1024));
-#endif
         if (s == 15) bias_init(accA, gp + dbN);
         __builtin_amdgcn_sched_barrier(0);
       }
     };
-    if (!(dbg & 8)) {
-      constexpr std::integral_constant<int, 0> copy_h{};
-      constexpr std::integral_constant<int, 1> acts{};
-      const int d0 = 16 * wave;
-      bias_init(ag0, gpar + 4 * hh + d0);
-      blk(copy_h, wg0, ag0, 0, 1, ag1, 0, 0, wg1, 0, 65536u, d0);          // block (0, 0); ag1 then accumulates block (0, 1)
+    constexpr std::integral_constant<int, 0> copy_h{};
+    constexpr std::integral_constant<int, 1> acts{};
+    const int d0 = 16 * wave;
+    bias_init(ag0, gpar + 4 * hh + d0);
+    blk(copy_h, wg0, ag0, 0, 1, ag1, 0, 0, wg1, 0, 65536u, d0);          // block (0, 0); ag1 then accumulates block (0, 1)
 #pragma unroll 1
-      for (int p2 = 0; p2 < 2; ++p2) {
-        asm volatile("" ::: "memory");                     // gate parameters and h fragments are re-read every round
-        const int db = 128 * p2 + d0;                      // passes ps = 2 p2 (weights wg0) and ps + 1 (wg1)
-        const unsigned n1 = __builtin_amdgcn_readfirstlane((unsigned)(2 * p2 + 1) * 65536u);   // passes 4, 5 do not exist: read as zero
-        blk(acts, wg0, ag1, 1, 2, ag0, db, 0, wg1, 1, n1, db);
-        blk(acts, wg0, ag0, 2, 3, ag1, db, 1, wg1, 2, n1, db);
-        blk(acts, wg0, ag1, 3, 0, ag0, db, 2, wg1, 3, n1, db + 64);
-        blk(acts, wg1, ag0, 0, 1, ag1, db, 3, wg0, 0, n1 + 65536u, db + 64);
-        blk(acts, wg1, ag1, 1, 2, ag0, db + 64, 0, wg0, 1, n1 + 65536u, db + 64);
-        blk(acts, wg1, ag0, 2, 3, ag1, db + 64, 1, wg0, 2, n1 + 65536u, db + 64);
-        blk(acts, wg1, ag1, 3, 0, ag0, db + 64, 2, wg0, 3, n1 + 65536u, db + 128);
-        blk(acts, wg0, ag0, 0, 1, ag1, db + 64, 3, wg1, 0, n1 + 131072u, db + 128);   // p2 = 1: the empty 17th block
-      }
+    for (int p2 = 0; p2 < 2; ++p2) {
+      asm volatile("" ::: "memory");                     // gate parameters and h fragments are re-read every round
+      const int db = 128 * p2 + d0;                      // passes ps = 2 p2 (weights wg0) and ps + 1 (wg1)
+      const unsigned n1 = __builtin_amdgcn_readfirstlane((unsigned)(2 * p2 + 1) * 65536u);   // passes 4, 5 do not exist: read as zero
+      blk(acts, wg0, ag1, 1, 2, ag0, db, 0, wg1, 1, n1, db);
+      blk(acts, wg0, ag0, 2, 3, ag1, db, 1, wg1, 2, n1, db);
+      blk(acts, wg0, ag1, 3, 0, ag0, db, 2, wg1, 3, n1, db + 64);
+      blk(acts, wg1, ag0, 0, 1, ag1, db, 3, wg0, 0, n1 + 65536u, db + 64);
+      blk(acts, wg1, ag1, 1, 2, ag0, db + 64, 0, wg0, 1, n1 + 65536u, db + 64);
+      blk(acts, wg1, ag0, 2, 3, ag1, db + 64, 1, wg0, 2, n1 + 65536u, db + 64);
+      blk(acts, wg1, ag1, 3, 0, ag0, db + 64, 2, wg0, 3, n1 + 65536u, db + 128);
+      blk(acts, wg0, ag0, 0, 1, ag1, db + 64, 3, wg1, 0, n1 + 131072u, db + 128);   // p2 = 1: the empty 17th block
     }
   };
   if (drop) gate_phase(std::true_type{}); else gate_phase(std::false_type{});
@@ -484,7 +412,6 @@ __global__ __launch_bounds__(256, 2) void amil_fwd_fused2_bf16_kernel(FusedFwdPa
     if (hh == 0) sred[wave * 128 + 32 * ib + r] = s;
   }
   __syncthreads();
-  B2_MARK(2);
 
   // ---------------- scores of the tile, online-softmax partial, pooling partial ----------------------------------------
   const float bc = p.bc[0];
@@ -503,23 +430,21 @@ __global__ __launch_bounds__(256, 2) void amil_fwd_fused2_bf16_kernel(FusedFwdPa
   const float lsum = wave_sum(ev);
   if (lane == 0) red[8 + wave] = lsum;
   __syncthreads();
-  if (!(dbg & 32)) {
-    const int fg = tid & 31, ig = tid >> 5;                // 8 features x 16 instances per thread
-    float v[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  const int fg = tid & 31, ig = tid >> 5;                // 8 features x 16 instances per thread
+  float v[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 #pragma unroll 4
-    for (int i = 0; i < 16; ++i) {
-      const int R = 16 * ig + i;
-      const float4 raw = *reinterpret_cast<const float4*>(lds + F2_HIMG + R * F2_HROW + 16 * fg);
-      float hv[8];
-      unpack8(raw, hv);
-      const float e = e_l[R];
+  for (int i = 0; i < 16; ++i) {
+    const int R = 16 * ig + i;
+    const float4 raw = *reinterpret_cast<const float4*>(lds + F2_HIMG + R * F2_HROW + 16 * fg);
+    float hv[8];
+    unpack8(raw, hv);
+    const float e = e_l[R];
 #pragma unroll
-      for (int k = 0; k < 8; ++k) v[k] += e * hv[k];
-    }
-    float* o = vred + ig * 256 + 8 * fg;
-    st4(o, make_float4(v[0], v[1], v[2], v[3]));
-    st4(o + 4, make_float4(v[4], v[5], v[6], v[7]));
+    for (int k = 0; k < 8; ++k) v[k] += e * hv[k];
   }
+  float* o = vred + ig * 256 + 8 * fg;
+  st4(o, make_float4(v[0], v[1], v[2], v[3]));
+  st4(o + 4, make_float4(v[4], v[5], v[6], v[7]));
   __syncthreads();
   float* out = p.partials + (size_t)mt * (2 + 256);
   {
@@ -530,8 +455,6 @@ __global__ __launch_bounds__(256, 2) void amil_fwd_fused2_bf16_kernel(FusedFwdPa
   }
   if (tid == 0) { out[0] = m; out[1] = red[8] + red[9]; }
   }
-  B2_MARK(3);
-  B2_COUNT();
 }
 
 bool fused_fwd2_ok(int64_t N, int L, int H, int D) {
@@ -542,21 +465,13 @@ bool fused_fwd2_ok(int64_t N, int L, int H, int D) {
 int launch_fused_fwd2_bf16(FusedFwdParams p, int gated, hipStream_t st) {
   if (!gated || p.D != 256 || p.L % 128 != 0 || !p.w1f || !p.wabf) return MMF_ERR_SHAPE;
   p.mt_count = fused_fwd_tiles(p.N);
-  static const int dbg = tune_int("MMF_F2_DEBUG_MASK", 0);
   static const int hl = tune_int("MMF_F2_HLOOP", 1);       // A/B switch
-  p.stagger = dbg;
   p.hash_in_loop = hl;
   const bool hloop = p.p_h > 0.f && p.L == 1024 && p.hash_in_loop;
   auto kern = hloop ? amil_fwd_fused2_bf16_kernel<true> : amil_fwd_fused2_bf16_kernel<false>;
-  static const int lds_env = tune_int("MMF_F2_LDS", 0);     // experiment: > 80 KB forces one workgroup per CU
-#ifdef MMF_F2_REV_GPAR
-  const int lds_bytes = lds_env > 0 ? lds_env : F2_LDS_BYTES;       // experiment: any size (the gate parameters are not in LDS)
-#else
-  const int lds_bytes = lds_env > F2_LDS_BYTES ? lds_env : F2_LDS_BYTES;
-#endif
-  if (int e = set_dyn_lds(reinterpret_cast<const void*>(kern), lds_bytes)) return e;
+  if (int e = set_dyn_lds(reinterpret_cast<const void*>(kern), F2_LDS_BYTES)) return e;
   ProfScope ps("amil_fwd_fused_bf16_kernel", st);
-  hipLaunchKernelGGL(kern, dim3(p.mt_count), dim3(256), lds_bytes, st, p);
+  hipLaunchKernelGGL(kern, dim3(p.mt_count), dim3(256), F2_LDS_BYTES, st, p);
   return hipGetLastError() == hipSuccess ? MMF_OK : MMF_ERR_LAUNCH;
 }
 

@@ -515,7 +515,6 @@ __global__ __launch_bounds__(T::NT) void bwd_dh_kernel(BwdDhParams p) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   float* ds_l = lds + 2 * T::STAGE_FLOATS;     // [BM] ds, [BM] p, behind the staging buffers (FUSED only)
   float* p_l = ds_l + T::BM;
-  MMF_KSTAMP(k0);
   constexpr bool SGATED = T::SPLIT && MODE >= 2;
   std::conditional_t<T::SPLIT,
                      std::conditional_t<SGATED, SplitP_K<T::BM, T::NT, (SGATED ? MODE : 2)>, SplitP_U<T::BM, T::NT, (T::SPLIT && !SGATED ? MODE : 0)>>,
@@ -606,7 +605,6 @@ __global__ __launch_bounds__(T::NT) void bwd_dh_kernel(BwdDhParams p) {
   f32x16 acc[T::MB][T::NB];
   f32x4acc acch[T::NB][2];                   // the half block's accumulators (Tile::HALF; unused otherwise)
   const int nk = (p.g.gated ? 2 : 1) * p.g.D / (T::SPLIT ? SKC : KC);
-  MMF_KSTAMP(k1);
   if constexpr (SGATED) {
     dh_split_mainloop<T>(la, lb, nk, lds, acc);
   } else if constexpr (T::SPLIT) {
@@ -617,7 +615,6 @@ __global__ __launch_bounds__(T::NT) void bwd_dh_kernel(BwdDhParams p) {
   } else {
     gemm_mainloop<T, decltype(la), decltype(lb), FUSED && MODE >= 0>(la, lb, nk, lds, acc, acch);
   }
-  MMF_KSTAMP(k2);
   // ---- epilogue: du = (acc + p dM) relu'(h) scale_h, row-major.  The h values (and p) of block b+1 are requested
   // before block b is transposed and stored: with the reload inside the block (first version) every one of the
   // wave's blocks waited a full memory latency for its own h.  A load only waits for the stores issued BEFORE it
@@ -748,12 +745,6 @@ __global__ __launch_bounds__(T::NT) void bwd_dh_kernel(BwdDhParams p) {
     }
     }
   }
-#ifdef MMF_STAMPS
-  MMF_KSTAMP(k3);
-  if ((threadIdx.x & 63) == 0) {     // K-dh: prologue (K-prep), main loop, epilogue, waves
-    atomicAdd(&g_stamps[4], k1 - k0); atomicAdd(&g_stamps[5], k2 - k1); atomicAdd(&g_stamps[6], k3 - k2); atomicAdd(&g_stamps[7], 1ull);
-  }
-#endif
 }
 
 // =============================================================================================
@@ -955,9 +946,6 @@ struct SplitA_M_Plain {
     voff = c < ncols ? (unsigned)(8 * kh) * ldb + (unsigned)c * 4u : OOB;
   }
   __device__ inline void load(int kt) {
-#ifdef MMF_SDIAG_NOGLOAD
-    if (kt >= 4) return;
-#endif
     const unsigned soff = kbase_b + (unsigned)(kt * SKC) * ldb;
 #pragma unroll
     for (int j = 0; j < 8; ++j) r[j] = bld1(rs, voff, soff + (unsigned)j * ldb);
@@ -1182,15 +1170,6 @@ __global__ __launch_bounds__(T::NT) void tn_kernel(TnParams p) {
   int last_groups = 0;
   if constexpr (!T::SPLIT) last_groups = nk > 0 ? ((kmax - kbase) - (nk - 1) * KC + 2 * T::G - 1) / (2 * T::G) : 0;
   const bool do_sum = tn == 0 && q.colsum != nullptr;
-#ifdef MMF_STAMPS             /* workgroup life time by tile kind: [0] sum plain, [1] sum gate, [2] count plain, [3] count gate */
-  struct TnLife {
-    unsigned long long t0; int kind;
-    __device__ ~TnLife() {
-      const unsigned long long t1 = stamp_now();
-      if (threadIdx.x == 0) { atomicAdd(&g_stamps[kind], t1 - t0); atomicAdd(&g_stamps[2 + kind], 1ull); }
-    }
-  } life{stamp_now(), q.kind == TN_A_PLAIN ? 0 : 1};
-#endif
 
   std::conditional_t<T::SPLIT, SplitM<T::BN, T::NT>, LoadM<T::BN, T::NT>> lb;
   lb.init(q.B, q.ldb, tn * T::BN, q.Ncols, kbase, kmax);
@@ -1198,7 +1177,7 @@ __global__ __launch_bounds__(T::NT) void tn_kernel(TnParams p) {
     std::conditional_t<T::SPLIT, SplitA_M_Plain<T::BM, T::NT>, LoadA_M_Plain<T::BM, T::NT>> la;
     la.init(q.A, q.lda, tm * T::BM, q.M, kbase, kmax, do_sum);
     f32x16 acc[T::MB][T::NB];
-    if constexpr (T::SPLIT) split_mainloop<T, 2, decltype(la), decltype(lb), true>(la, lb, nk, lds, acc);
+    if constexpr (T::SPLIT) split_mainloop<T, 2>(la, lb, nk, lds, acc);
     else gemm_mainloop<T>(la, lb, nk, lds, acc, nullptr, last_groups);
     tn_store<T>(q, split, tn, acc, lds, [&](int r) { const int row = tm * T::BM + r; return row < q.M ? row : -1; });
     if (do_sum) {
@@ -1662,17 +1641,6 @@ int launch_reduce(ReduceParams p, hipStream_t st) {
   if (blocks == 0) return MMF_OK;
   { ProfScope ps("reduce_kernel", st); hipLaunchKernelGGL(reduce_kernel, dim3(blocks), dim3(256), 0, st, p); }
   return hipGetLastError() == hipSuccess ? MMF_OK : MMF_ERR_LAUNCH;
-}
-
-// diagnostic: read and clear this translation unit's phase stamps (zeros unless built with -DMMF_STAMPS)
-void debug_stamps_bwd(unsigned long long* out8) {
-#ifdef MMF_STAMPS
-  hipMemcpyFromSymbol(out8, HIP_SYMBOL(g_stamps), 8 * sizeof(unsigned long long));
-  unsigned long long z[8] = {0};
-  hipMemcpyToSymbol(HIP_SYMBOL(g_stamps), z, sizeof z);
-#else
-  for (int i = 0; i < 8; ++i) out8[i] = 0;
-#endif
 }
 
 }  // namespace mmf

@@ -8,7 +8,6 @@
 //   K-merge M = softmax(A_raw).h, (max, denom)        models/model_attention_mil_path.py:53-56
 #include <cstdlib>
 
-#define MMF_STAMP_FIRST_STAGE      /* stamps builds: this unit owns g_stamps[2..3] for the main loops' first stage */
 #include "mmf_gemm_core.h"
 #include "mmf_gemm_split.h"
 #include "mmf_kernels.h"
@@ -47,14 +46,6 @@ struct PartSrc {
 template <class T, int ACT, bool DROP, bool SEG = false>
 __device__ inline void linear_epilogue(const LinearParams& p, f32x16 (&acc)[T::MB][T::NB], f32x4acc (*acch)[2], float* lds,
                                        int row0, int col0, const PartSrc ps = PartSrc{}) {
-#ifdef MMF_DIAG_NOEPI         /* diagnostic build: main loop only (results are wrong) */
-  {
-    float t = 0.f;
-    for_each_c<T>(acc, [&](int, int, float v) { t += v; });
-    if (t == 1.2345e30f) p.y[0] = t;
-    return;
-  }
-#endif
   const uint32_t thr = drop_threshold(p.drop_p);
   const float scale = DROP ? 1.0f / (1.0f - p.drop_p) : 1.0f;
   const uint32_t dkey = p.drop_key + (p.seed_dev ? *p.seed_dev : 0u);   // device-resident part of the seed, if any
@@ -96,9 +87,6 @@ __device__ inline void linear_epilogue(const LinearParams& p, f32x16 (&acc)[T::M
           if (lane == 4 * t + e) mine = bal;
         }
       }
-#ifdef MMF_DIAG_NOSTORE       /* diagnostic build: everything but the global stores (results are wrong) */
-      if (y[0] == 1.2345e30f)
-#endif
       if (ok) st4(p.y + (size_t)row * p.N + col, make_float4(y[0], y[1], y[2], y[3]));
     }
     if (p.relu_bits && lane < 4 * NTR) {
@@ -207,7 +195,6 @@ __device__ inline bool ksplit_publish(const LinearParams& p, f32x16 (&acc)[T::MB
 template <class T, bool SEG = false>
 __global__ __launch_bounds__(T::NT) void linear_nt_kernel(LinearParams p) {
   extern __shared__ __align__(16) float lds[];
-  MMF_KSTAMP(kernel_t0);
   const int S = p.ksplit > 1 ? p.ksplit : 1;
   int mt, ntk;
   // the (column tile, K split) pairs of one row tile are 8 workgroups apart: one XCD, whose L2 serves the shared x rows
@@ -224,17 +211,12 @@ __global__ __launch_bounds__(T::NT) void linear_nt_kernel(LinearParams p) {
 
   f32x16 acc[T::MB][T::NB];
   f32x4acc acch[T::NB][2];                   // the half block's accumulators (Tile::HALF; unused otherwise)
-  MMF_KSTAMP(k0);
   if constexpr (T::NT == 256 && T::BM <= 64) {
     if (p.deep) gemm_mainloop_deep<T, 4>(la, lb, nk, lds, acc);      // short grid: see gemm_mainloop_deep
     else gemm_mainloop<T>(la, lb, nk, lds, acc);
   } else {
     gemm_mainloop<T>(la, lb, nk, lds, acc, acch);
   }
-  MMF_KSTAMP(k1);
-#ifdef MMF_STAMPS
-  if ((threadIdx.x & 63) == 0) atomicAdd(&g_stamps[4], k0 - kernel_t0);     // entry -> loaders initialised
-#endif
   PartSrc ps{};                              // S = 0: the epilogue takes the tile from the accumulators
   if (S > 1) {
     if (!ksplit_publish<T>(p, acc, acch, lds, mt * p.nt_count + nt, ks, ps)) return;
@@ -254,12 +236,6 @@ __global__ __launch_bounds__(T::NT) void linear_nt_kernel(LinearParams p) {
   } else {
     linear_epilogue<T, -1, false>(p, acc, acch, lds, row0, col0, ps);
   }
-#ifdef MMF_STAMPS
-  MMF_KSTAMP(k2);
-  if ((threadIdx.x & 63) == 0) {
-    atomicAdd(&g_stamps[5], k1 - k0); atomicAdd(&g_stamps[6], k2 - k1); atomicAdd(&g_stamps[7], 1ull);
-  }
-#endif
 }
 
 // The same projection on the bf16 matrix cores (mmf_gemm_split.h: 3-way operand split, fp32-equivalent accuracy).
@@ -274,7 +250,7 @@ __global__ __launch_bounds__(T::NT) void linear_nt_split_kernel(LinearParams p) 
   SplitK<T::BN, T::NT> lb;
   lb.init(p.w, p.K, col0, p.N);
   f32x16 acc[T::MB][T::NB];
-  split_mainloop<T, 4, decltype(la), decltype(lb), true>(la, lb, p.K / SKC, lds, acc);
+  split_mainloop<T, 4>(la, lb, p.K / SKC, lds, acc);
   const bool drop = p.drop_p > 0.f;
   if (p.act == ACT_RELU) {
     if (drop) linear_epilogue<T, ACT_RELU, true>(p, acc, nullptr, lds, row0, col0);
@@ -380,14 +356,6 @@ __device__ inline void gate_fwd_tile(const GateFwdParams& p, float* lds, int row
     gemm_mainloop<T>(la, lb, p.H / KC, lds, acc);
   }
 
-#ifdef MMF_DIAG_NOEPI         /* diagnostic build: main loop only (results are wrong) */
-  {
-    float t = 0.f;
-    for_each_c<T>(acc, [&](int, int, float v) { t += v; });
-    if (t == 1.2345e30f) p.s_part[0] = t;
-    return;
-  }
-#endif
   // ---- epilogue (row-major, float4): activations, stores of a / b, per-row partial score ----------------
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave / T::WN, wn = wave % T::WN;
@@ -984,7 +952,7 @@ static int launch_gate_fwd_impl(GateFwdParams p, hipStream_t st) {
   };
   // 128-row tiles only once they fill most of the 512 slots (two workgroups per CU): a 10k bag is 316 tall tiles -- every
   // CU busy for a tall tile's time, 60 of them twice -- or 628 short ones in 1.2 rounds: measured 40.6 vs 35.1 us (round 4,
-  // tools/r4_mid_try.sh; 12,288 rows: 40.3 vs 35.3; from 12,800 rows the tall tiles win, 14k: 41.0 vs 44.0)
+  // DESIGN.md §5, profiles/r04/d_mid_size_knobs.txt; 12,288 rows: 40.3 vs 35.3; from 12,800 rows the tall tiles win, 14k: 41.0 vs 44.0)
   static const int big_min = tune_int("MMF_GATE_BIG_MIN", 400);
   const bool big = (p.N / 128) * p.nt_count >= big_min;
   if (!big) return small(p);
@@ -1097,17 +1065,6 @@ int launch_head_tail(PoolParams p, hipStream_t st) {
   ProfScope ps("head_tail_kernel", st);
   hipLaunchKernelGGL(head_tail_kernel, dim3(1), dim3(1024), 0, st, p);
   return hipGetLastError() == hipSuccess ? MMF_OK : MMF_ERR_LAUNCH;
-}
-
-// diagnostic: read and clear this translation unit's phase stamps (zeros unless built with -DMMF_STAMPS)
-void debug_stamps_fwd(unsigned long long* out8) {
-#ifdef MMF_STAMPS
-  hipMemcpyFromSymbol(out8, HIP_SYMBOL(g_stamps), 8 * sizeof(unsigned long long));
-  unsigned long long z[8] = {0};
-  hipMemcpyToSymbol(HIP_SYMBOL(g_stamps), z, sizeof z);
-#else
-  for (int i = 0; i < 8; ++i) out8[i] = 0;
-#endif
 }
 
 }  // namespace mmf

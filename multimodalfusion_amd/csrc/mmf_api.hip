@@ -115,7 +115,7 @@ static AmilWs carve(void* base, int64_t N, int L, int H, int D, int gated, bool 
   w.k_per_split = (int)((kps + 3) / 4 * 4);
   if (w.k_per_split < 4) w.k_per_split = 4;
   // A gate tile builds its A operand (dP from a, b, ds) in the staging path and lives ~8 % longer per K row than a
-  // dW1 tile (stamps: 710 k vs 659 k cycles with equal splits), so the whole launch waited for the gate tiles.  The
+  // dW1 tile (in-kernel cycle stamps: 710 k vs 659 k with equal splits), so the whole launch waited for the gate tiles.  The
   // workgroups the uniform split leaves over (256 - 6 x 42 = 4) go to the gate problem: 44 splits of 36 chunks beside
   // 42 of 38 at N = 50k.  Large-bag tile only, at most 12 % more splits.
   w.splits_g = splits; w.k_per_split_g = w.k_per_split;
@@ -1075,9 +1075,7 @@ int mmf_maxnet_cox_step(const mmf_maxnet_desc* d, const double* times, const flo
   const size_t n = (size_t)d->B * 256;
   const size_t nt = (size_t)256 * maxnet_step_dp_pitch(d->B);
   p.y0 = w; p.y1 = w + n; p.dp1 = w + 2 * n; p.dp0 = p.dp1 + nt; p.dr = p.dp0 + nt;
-  float* after = p.dr + (size_t)((d->B + 63) / 64 * 64);
-  p.stamps = reinterpret_cast<unsigned long long*>(after);      // read by tools/stamps_maxnet.py only
-  p.dwc_part = after + 32;
+  p.dwc_part = p.dr + (size_t)((d->B + 63) / 64 * 64);
   p.bar = d->sync;
   p.risk = risk; p.loss = loss;
   p.dW0 = g->dW0; p.db0 = g->db0; p.dW1 = g->dW1; p.db1 = g->db1; p.dWc = g->dWc; p.dbc = g->dbc;
@@ -1162,16 +1160,6 @@ int mmf_kron_backward(const float* g, const float* const* o, int32_t m, int32_t 
   p.g = g; p.m = m; p.dim = dim; p.B = B; p.drop = make_drop(1, drop_p, seed, site, seed_dev);
   return launch_kron_bwd(p, static_cast<hipStream_t>(stream));
 }
-
-/* diagnostic builds only (-DMMF_STAMPS): which = 0 forward TU, 1 backward TU; out8 = {load, mfma, store, barrier cycles, chunks};
- * which = 2: bf16 TU, writes 32 values (4 kernels x {prologue, main loop, epilogue, -, -, -, -, waves}) */
-#ifdef MMF_STAMPS       /* exported by the diagnostic libraries only (tools/diag_build.py -> multimodalfusion_amd/_diag/) */
-void mmf_debug_stamps(int which, unsigned long long* out8) {
-  if (which == 0) debug_stamps_fwd(out8);
-  else if (which == 1) debug_stamps_bwd(out8);
-  else debug_stamps_bf16(out8);
-}
-#endif
 
 static int xreduce_params(const mmf_xreduce_io* io, float drop_p, uint32_t seed, const uint32_t* seed_dev, bool bwd,
                           XReduceParams& p) {

@@ -121,7 +121,6 @@ struct FusedFwdParams {     // fused forward (H = 256): instance projection + ga
   float p_h, p_att; uint32_t key_h, key_a, key_b; const uint32_t* seed_dev;
   int mt_count;
   int hash_in_loop;             // second form: projection dropout bits hashed inside the main loop (L == 1024)
-  int stagger;                  // diagnostic builds only (-DMMF_F2_DEBUG): mask of phases to leave out
 };
 int fused_fwd_tiles(int64_t N);
 bool fused_fwd_ok(int64_t N, int L, int H, int D);
@@ -135,6 +134,5 @@ bool dh2_bf16_ok(int64_t N, int H, int D, int gated);   // second form (mmf_amil
 int launch_dh2_bf16(DhBfParams p, hipStream_t st);
 int tn_bf16_splits(int64_t K, int total_tiles);
 int launch_tn_bf16(TnBfParams p, hipStream_t st);
-void debug_stamps_bf16(unsigned long long* out32);
 
 }  // namespace mmf

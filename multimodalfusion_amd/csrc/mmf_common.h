@@ -10,8 +10,8 @@ namespace mmf {
 
 // ---- launch-plan tuning knobs ------------------------------------------------------------
 // The shipped library takes its launch plan from the call's arguments alone: tune_int() is the constant default.
-// Only a tuning build (-DMMF_TUNE: tools/diag_build.py tune -> _diag/libmmf_tune.so, loaded through MMF_LIB_PATH by
-// the sweep scripts under tools/) reads the environment, once per process and knob.
+// Only a tuning build (-DMMF_TUNE: tools/diag_build.py tune -> _diag/libmmf_tune.so, loaded through MMF_LIB_PATH for
+// a sweep, tools/README.md) reads the environment, once per process and knob.
 #ifdef MMF_TUNE
 inline int tune_int(const char* name, int dflt) {
   const char* v = getenv(name);

@@ -390,67 +390,31 @@ __device__ inline void compute_chunk(const float* __restrict__ As, const float* 
   FragB<T> fb[2];
   FragH<T> fh;
   const int arow_h = wm * (T::BM / T::WM) + T::MB * 32, brow0 = wn * T::NB * 32;
-#ifdef MMF_DIAG_NOFRAG       /* diagnostic build: fragments read once per chunk only (results are wrong) */
-  read_b<T>(Bs, 0, brow, hh, fb[0]); read_b<T>(Bs, 1, brow, hh, fb[1]);
-  read_a<T>(As, 0, 0, MBH, arow, hh, fa[0]); read_a<T>(As, 1, 0, MBH, arow, hh, fa[1]);
-#else
   read_b<T>(Bs, 0, brow, hh, fb[0]);
   read_a<T>(As, 0, 0, MBH, arow, hh, fa[0]);
-#endif
 #pragma unroll
   for (int s = 0; s < NS; ++s) {
     const int g = s / NP, part = s % NP;
     const int lo = part == 0 ? 0 : MBH, hi = part == 0 ? MBH : T::MB;
-#ifndef MMF_DIAG_NOFRAG
     if (s + 1 < NS) {                            // prefetch the fragments of step s + 1
       const int g1 = (s + 1) / NP, part1 = (s + 1) % NP;
       if (part1 == 0) read_b<T>(Bs, g1, brow, hh, fb[g1 & 1]);
       read_a<T>(As, g1, part1 == 0 ? 0 : MBH, part1 == 0 ? MBH : T::MB, arow, hh, fa[(s + 1) & 1]);
     }
-#endif
     if constexpr (T::HALF) {                     // the half block's fragments: read in the first part of group g,
       if (part == 0) read_half<T>(As, Bs, g, arow_h, brow0, lane, fh);   // multiplied behind its last part
     }
     hook(s);
-#ifndef MMF_DIAG_NOSCHED
     __builtin_amdgcn_sched_barrier(0);
-#endif
-#ifndef MMF_DIAG_NOMFMA      /* diagnostic builds (tools/diag_build.py): timing only, results are wrong */
     // ng_valid: fragment groups of this chunk that hold data (split-K launches cut K at multiples of 4 instances, so
     // every workgroup's LAST chunk is partly zero fill); one scalar branch per step, same registers as without it
     if (g < ng_valid) mfma_part<T>(fa[s & 1], fb[g & 1], lo, hi, acc);
     if constexpr (T::HALF) {
       if (part == NP - 1) mfma_half<T>(fh, *reinterpret_cast<f32x4acc (*)[T::NB][2]>(acch));
     }
-#endif
-#ifndef MMF_DIAG_NOSCHED
     __builtin_amdgcn_sched_barrier(0);
-#endif
   }
 }
-
-// Diagnostic build only (-DMMF_STAMPS): s_memtime phase stamps of the main loop, summed per wave into a
-// per-translation-unit device array that no kernel reads (guide: "In-kernel stamps").  The shipped
-// library is built without the macro and contains no stamp.
-#ifdef MMF_STAMPS
-static __device__ unsigned long long g_stamps[8];
-__device__ inline unsigned long long stamp_now() {
-  unsigned long long t;
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-  __builtin_amdgcn_sched_barrier(0);
-  return t;
-}
-#ifdef MMF_STAMPS_LIGHT        /* kernel-level stamps only: nothing inside the main loop */
-#define MMF_STAMP(var)
-#else
-#define MMF_STAMP(var) unsigned long long var = stamp_now()
-#endif
-#define MMF_KSTAMP(var) unsigned long long var = stamp_now()
-#else
-#define MMF_STAMP(var)
-#define MMF_KSTAMP(var)
-#endif
 
 // DEPHASE (8-wave tiles only): the two waves of a SIMD (w and w + 4) run the same code in phase, so they stall in the
 // same unit at the same moment.  With DEPHASE the second group stages half a chunk out of phase: it writes chunk
@@ -476,54 +440,32 @@ __device__ inline void gemm_mainloop(LA& la, LB& lb, int nk, float* lds, f32x16 
         for (int i = 0; i < 4; ++i) acch[nb][c][i] = 0.f;
   }
   if (nk <= 0) return;
-#if defined(MMF_STAMPS) && !defined(MMF_STAMPS_LIGHT)
-  unsigned long long s_load = 0, s_mfma = 0, s_store = 0, s_bar = 0;
-#endif
-#if defined(MMF_STAMPS) && defined(MMF_STAMP_FIRST_STAGE)
-  const unsigned long long t_enter = stamp_now();
-#endif
   la.load(0);
   lb.load(0);
   la.store(lds);
   lb.store(lds + T::A_FLOATS);
   const bool late = DEPHASE && T::NT == 512 && wave >= 4;
-#ifndef MMF_DIAG_NOLOAD
   if (late && nk > 1) { la.load(1); lb.load(1); }
-#endif
   __syncthreads();
-#if defined(MMF_STAMPS) && defined(MMF_STAMP_FIRST_STAGE)   /* [2]: first stage (load + LDS write + barrier), [3]: count */
-  if (lane == 0) { atomicAdd(&g_stamps[2], stamp_now() - t_enter); atomicAdd(&g_stamps[3], 1ull); }
-#endif
   // Static priority for the second-dispatched half of an 8-wave workgroup (MI355X_MICROARCH.md, two waves per SIMD, item 4):
   // the younger wave of every SIMD loses each issue arbitration otherwise.  Measured on the 50k step, same box, two alternating
   // pairs: K-dh -2.3 us, the projection -0.8, the gate -0.5; the TN tiles (m-contiguous operands) +1.0, so they keep priority 0.
-#ifndef MMF_GEMM_PRIO
-#define MMF_GEMM_PRIO 1
-#endif
-  constexpr bool half_prio = MMF_GEMM_PRIO && T::NT == 512 && T::A_KCONTIG;
+  constexpr bool half_prio = T::NT == 512 && T::A_KCONTIG;
   if (half_prio && wave >= 4) __builtin_amdgcn_s_setprio(1);
   for (int kt = 0; kt < nk; ++kt) {
     float* cur = lds + (kt & 1) * T::STAGE_FLOATS;
     float* nxt = lds + ((kt + 1) & 1) * T::STAGE_FLOATS;
     const bool more = kt + 1 < nk;
     const bool more2 = kt + 2 < nk;
-    MMF_STAMP(t0);
-    MMF_STAMP(t1);
     // a K range that ends inside its last chunk: only the first `last_groups` fragment groups of that chunk hold data,
     // the rest is zero fill -- and multiplying zeros costs what multiplying data costs (see compute_chunk: ng_valid)
     const int ng_valid = more ? (1 << 30) : last_groups;
     compute_chunk<T>(cur, cur + T::A_FLOATS, acc, wm, wn, lane, [&](int s) {
       if (!more) return;
-#ifdef MMF_DIAG_NOLOAD
-      return;
-#endif
       constexpr int NS = chunk_steps<T>();
       if constexpr (NS == 8 && !DEPHASE && has_halves<LA>::value && has_halves<LB>::value) {
         // plain copies on both sides: one half-operand per step, so that no step issues more than 2-4 VMEM or LDS
         // instructions per lane (the 4-slot schedule wrote a whole operand, 30 KB per CU, in one burst)
-#ifdef MMF_DIAG_NOGLOAD
-        if (s < 4) return;
-#endif
         switch (s) {
           case 0: la.load_half(kt + 1, 0); break;
           case 1: la.load_half(kt + 1, 1); break;
@@ -538,11 +480,6 @@ __device__ inline void gemm_mainloop(LA& la, LB& lb, int nk, float* lds, f32x16 
       }
       if (s % (NS / 4) != 0) return;
       const int q = s / (NS / 4);
-#ifdef MMF_DIAG_NOGLOAD        /* diagnostic build: LDS writes of stale registers, no global loads (results are wrong) */
-      if (q == 2) la.store(nxt);
-      else if (q == 3) lb.store(nxt + T::A_FLOATS);
-      return;
-#endif
       if (late) {
         if (q == 0) la.store(nxt);
         else if (q == 1) lb.store(nxt + T::A_FLOATS);
@@ -555,24 +492,9 @@ __device__ inline void gemm_mainloop(LA& la, LB& lb, int nk, float* lds, f32x16 
       else if (q == 2) la.store(nxt);
       else lb.store(nxt + T::A_FLOATS);
     }, acch, ng_valid);
-    MMF_STAMP(t2);
-    MMF_STAMP(t3);
-#ifndef MMF_DIAG_NOBAR        /* diagnostic build: no barrier between chunks (results are wrong) */
     __syncthreads();
-#endif
-    MMF_STAMP(t4);
-#if defined(MMF_STAMPS) && !defined(MMF_STAMPS_LIGHT)
-    s_load += t1 - t0; s_mfma += t2 - t1; s_store += t3 - t2; s_bar += t4 - t3;
-#endif
   }
   if (half_prio) __builtin_amdgcn_s_setprio(0);
-#if defined(MMF_STAMPS) && !defined(MMF_STAMPS_LIGHT)
-  if (lane == 0) {
-    atomicAdd(&g_stamps[0], s_load); atomicAdd(&g_stamps[1], s_mfma);
-    atomicAdd(&g_stamps[2], s_store); atomicAdd(&g_stamps[3], s_bar);
-    atomicAdd(&g_stamps[4], (unsigned long long)nk);
-  }
-#endif
 }
 
 // Deep register prefetch for SHORT grids (small bags: a few dozen workgroups, one per CU, nothing else on the CU to
@@ -666,20 +588,8 @@ __device__ inline void epilogue_rows(f32x16 (&acc)[T::MB][T::NB], float* lds, F&
   const int r = lane & 31, hh = lane >> 5;
   float* blk = lds + wave * (32 * EPI_STRIDE);
   const int rr = lane >> 3, c4 = lane & 7;
-#ifdef MMF_DIAG_EPI1          /* diagnostic build: only the first row block is written out (results are wrong) */
-  constexpr int MB_OUT = 1;
-  {
-    float t = 0.f;
-    for (int mb = 1; mb < T::MB; ++mb)
-      for (int nb = 0; nb < T::NB; ++nb)
-        for (int i = 0; i < 16; ++i) t += acc[mb][nb][i];
-    if (t == 1.2345e30f) blk[0] = t;
-  }
-#else
-  constexpr int MB_OUT = T::MB;
-#endif
 #pragma unroll
-  for (int mb = 0; mb < MB_OUT; ++mb)
+  for (int mb = 0; mb < T::MB; ++mb)
 #pragma unroll
     for (int nb = 0; nb < T::NB; ++nb) {
 #pragma unroll

@@ -61,11 +61,7 @@ __device__ inline unsigned lds_addr(const void* p) {       // LDS byte address o
   return (unsigned)(unsigned long long)(lds_char*)(p);
 }
 __device__ inline void dma16(const DmaRsrc& rs, unsigned lds_dst, unsigned voff, unsigned soff) {
-#ifdef MMF_DMA_M0NOP
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 4\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds\n\ts_nop 4"
-#else
   asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds"
-#endif
                :: "s"(lds_dst), "v"(voff), "s"(rs.w), "s"(soff) : "memory");   // M0 is written and consumed inside this one statement
 }
 
@@ -128,7 +124,6 @@ __device__ inline void compute_chunk_swz(const char* As, const char* Bs, f32x16 
     if (q + 1 < 4) rd(q + 1, (q + 1) & 1);
     hook(q);
     __builtin_amdgcn_sched_barrier(0);
-#ifndef MMF_DIAG_NOMFMA
 #pragma unroll
     for (int mb = 0; mb < T::MB; ++mb)
 #pragma unroll
@@ -137,7 +132,6 @@ __device__ inline void compute_chunk_swz(const char* As, const char* Bs, f32x16 
         const float bv[4] = {fb[q & 1][nb].x, fb[q & 1][nb].y, fb[q & 1][nb].z, fb[q & 1][nb].w};
         acc[mb][nb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_bf16(av), frag_bf16(bv), acc[mb][nb], 0, 0, 0);
       }
-#endif
     __builtin_amdgcn_sched_barrier(0);
   }
 }
@@ -177,21 +171,16 @@ __device__ inline void gemm_mainloop_dma(LA& la, LB& lb, int nk, char* lds, f32x
   for (int kt = 0; kt < nk; ++kt) {
     char* cur = stage(kt);
     const bool more = kt + 1 < nk, more_d = kt + DIST < nk;
-#ifdef MMF_DIAG_NOLOAD
-    const bool st1 = false, std_ = false;
-#else
-    const bool st1 = more, std_ = more_d;
-#endif
-    if (st1) {
+    if (more) {
       if constexpr (!LA::DMA) la.load(kt + 1);
       if constexpr (!LB::DMA) lb.load(kt + 1);
     }
-    if (std_) {      // the stage being refilled was last read in iteration kt - 1 (DIST 2) / is chunk kt+1's own (DIST 1)
+    if (more_d) {      // the stage being refilled was last read in iteration kt - 1 (DIST 2) / is chunk kt+1's own (DIST 1)
       if constexpr (LA::DMA) la.issue(kt + DIST, stage(kt + DIST));
       if constexpr (LB::DMA) lb.issue(kt + DIST, stage(kt + DIST) + T::A_BYTES);
     }
     compute_chunk_swz<T>(cur, cur + T::A_BYTES, acc, wm, wn, lane, [&](int q) {
-      if (!st1) return;
+      if (!more) return;
       if (q == 2) { if constexpr (!LA::DMA) la.store(stage(kt + 1)); }
       if (q == 3) { if constexpr (!LB::DMA) lb.store(stage(kt + 1) + T::A_BYTES); }
     });

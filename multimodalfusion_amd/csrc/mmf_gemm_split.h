@@ -58,15 +58,10 @@ __device__ inline void split_pair(float x0, float x1, uint32_t& p0, uint32_t& p1
   r0 -= __uint_as_float(p1 << 16); r1 -= __uint_as_float(p1 & 0xFFFF0000u);
   p2 = cvt_pk_bf16(r0, r1);
 }
-#ifdef MMF_SDIAG_NOLDSW        /* diagnostic build: the split is computed, nothing is written to LDS (results are wrong) */
-__device__ inline void st_u2(float* p, uint32_t a, uint32_t b) { asm volatile("" :: "v"(a), "v"(b), "v"(p)); }
-__device__ inline void st_u4(float* p, uint32_t a, uint32_t b, uint32_t c, uint32_t d) { asm volatile("" :: "v"(a), "v"(b), "v"(c), "v"(d), "v"(p)); }
-#else
 __device__ inline void st_u2(float* p, uint32_t a, uint32_t b) { *reinterpret_cast<uint2*>(p) = make_uint2(a, b); }
 __device__ inline void st_u4(float* p, uint32_t a, uint32_t b, uint32_t c, uint32_t d) {
   *reinterpret_cast<uint4*>(p) = make_uint4(a, b, c, d);
 }
-#endif
 // Vector slot idx of a k-contiguous chunk image (4 float4 per row) -> tile row.  Not idx / 4: the 16 lanes that share
 // a ds_write_b64 pass must land on 32 distinct banks, and 4 CONSECUTIVE rows do not (row stride 112 bytes = 28 banks:
 // rows r and r + 1 overlap in 4 banks, a 2-way conflict on half of every pass).  Rows r, r + 2, r + 4, r + 6 do
@@ -126,9 +121,6 @@ struct SplitK {
     }
   }
   __device__ inline void load(int kt) {
-#ifdef MMF_SDIAG_NOGLOAD
-    if (kt >= 4) return;
-#endif
     const unsigned soff = (unsigned)(kt * SKC) * 4u;
 #pragma unroll
     for (int i = 0; i < NV; ++i) r[i] = bld4(rs, voff[i], soff);
@@ -142,12 +134,6 @@ struct SplitK {
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
       const int idx = slot(tid, i);
-#ifdef MMF_SDIAG_NOSPLIT       /* LDS writes of unsplit data: the staging path without its VALU work */
-      st_u2(lds + krow(idx) * SROW_F + 2 * (idx & 3), __float_as_uint(r[i].x), __float_as_uint(r[i].y));
-      st_u2(lds + krow(idx) * SROW_F + 8 + 2 * (idx & 3), __float_as_uint(r[i].z), __float_as_uint(r[i].w));
-      st_u2(lds + krow(idx) * SROW_F + 16 + 2 * (idx & 3), __float_as_uint(r[i].x), __float_as_uint(r[i].w));
-      continue;
-#endif
       split_store4(lds + krow(idx) * SROW_F, idx & 3, r[i]);
     }
   }
@@ -220,9 +206,6 @@ struct SplitM {
     }
   }
   __device__ inline void load(int kt) {
-#ifdef MMF_SDIAG_NOGLOAD
-    if (kt >= 4) return;
-#endif
     const unsigned soff = kbase_b + (unsigned)(kt * SKC) * ldb;
 #pragma unroll
     for (int i = 0; i < NV; ++i)
@@ -244,11 +227,6 @@ struct SplitM {
 struct FragS { f32x4 p[3]; };        // a row's three plane halves (8 bf16 each) for one lane
 
 __device__ inline void read_frag(const float* row, FragS& f) {
-#ifdef MMF_SDIAG_NOFRAG        /* diagnostic build: fragments come from registers, not LDS (results are wrong) */
-#pragma unroll
-  for (int q = 0; q < 3; ++q) f.p[q] = f32x4{(float)(size_t)row, 1.f, 2.f, (float)q};
-  return;
-#endif
 #pragma unroll
   for (int q = 0; q < 3; ++q) f.p[q] = *reinterpret_cast<const f32x4*>(row + 8 * q);
 }
@@ -299,9 +277,7 @@ __device__ inline void compute_chunk_split(const float* __restrict__ As, const f
 #pragma unroll
         for (int nb = 0; nb < T::NB; ++nb) {
           const int mb = s * GM + m;
-#ifndef MMF_SDIAG_NOMFMA      /* diagnostic builds (tools/diag_build.py): timing only, results are wrong */
           if (mb < T::MB) acc[mb][nb] = mfma_bf(fa[s & 1][m].p[TI[t]], fb[nb].p[TJ[t]], acc[mb][nb]);
-#endif
         }
     __builtin_amdgcn_sched_barrier(0);
   }
@@ -317,9 +293,7 @@ struct has_absorb : std::false_type {};
 template <class L>
 struct has_absorb<L, std::void_t<decltype(std::declval<L&>().absorb(std::declval<const L&>()))>> : std::true_type {};
 
-// STAMP (diagnostic -DMMF_STAMPS builds only): per wave, s_memtime ticks inside the chunks' work and at their barriers,
-// summed into g_stamps[0 / 1] (waves 0-3) and [2 / 3] (waves 4-7), chunk count in [4]
-template <class T, int D, class LA, class LB, bool STAMP = false>
+template <class T, int D, class LA, class LB>
 __device__ inline void split_mainloop(LA& la0, const LB& lb0, int nk, float* lds, f32x16 (&acc)[T::MB][T::NB]) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave / T::WN, wn = wave % T::WN;
@@ -342,23 +316,13 @@ __device__ inline void split_mainloop(LA& la0, const LB& lb0, int nk, float* lds
   __syncthreads();
   constexpr int NS = split_steps<T>();
   static_assert((D & 1) == 0, "an even D keeps the LDS stage of copy j fixed");
-#ifdef MMF_STAMPS
-  unsigned long long st_work = 0, st_bar = 0;
-#endif
   for (int kt0 = 0; kt0 < nk; kt0 += D) {
 #pragma unroll
     for (int j = 0; j < D; ++j) {
       const int kt = kt0 + j;
       float* cur = lds + (j & 1) * T::STAGE_FLOATS;
       float* nxt = lds + ((j + 1) & 1) * T::STAGE_FLOATS;
-#ifdef MMF_STAMPS
-      unsigned long long st0 = 0;
-      if constexpr (STAMP) st0 = stamp_now();
-#endif
       compute_chunk_split<T>(cur, cur + T::A_FLOATS, acc, wm, wn, lane, [&](int s) {
-#ifdef MMF_SDIAG_NOSTAGE
-        return;
-#endif
         // requests in the first steps (copy j has been written out: reuse it); the split + LDS writes of chunk kt+1 in
         // PIECES spread evenly over the chunk's steps
         if (s == 0) la[j].load(kt + D);
@@ -366,7 +330,7 @@ __device__ inline void split_mainloop(LA& la0, const LB& lb0, int nk, float* lds
         constexpr int PA = LA::PIECES, PT = LA::PIECES + LB::PIECES;
         // D = 2 (the TN kernel: no registers for a deeper ring): the pieces go to the LAST steps, so that a request has
         // 1.5+ chunks to land instead of 1 -- with the pieces up front the whole workgroup waited at the barrier for
-        // its slowest load (no-barrier diagnostic build: 207 -> 180 us)
+        // its slowest load (207 -> 180 us with the barrier left out)
         constexpr bool LATE = D == 2 && PT <= NS;
 #pragma unroll
         for (int q = 0; q < PT; ++q)
@@ -375,27 +339,9 @@ __device__ inline void split_mainloop(LA& la0, const LB& lb0, int nk, float* lds
             else lb[(j + 1) % D].store_piece(nxt + T::A_FLOATS, q - PA);
           }
       });
-#ifdef MMF_STAMPS
-      unsigned long long st1 = 0;
-      if constexpr (STAMP) st1 = stamp_now();
-#endif
-#ifndef MMF_SDIAG_NOBAR
       __syncthreads();
-#endif
-#ifdef MMF_STAMPS
-      if constexpr (STAMP) { st_work += st1 - st0; st_bar += stamp_now() - st1; }
-#endif
     }
   }
-#ifdef MMF_STAMPS
-  if constexpr (STAMP) {
-    if (lane == 0) {
-      const int grp = wave >= 4 ? 2 : 0;
-      atomicAdd(&g_stamps[grp], st_work); atomicAdd(&g_stamps[grp + 1], st_bar);
-      if (wave == 0) atomicAdd(&g_stamps[4], (unsigned long long)nk);
-    }
-  }
-#endif
   if constexpr (has_absorb<LA>::value) {
 #pragma unroll
     for (int j = 0; j < D; ++j) la0.absorb(la[j]);

@@ -287,8 +287,6 @@ int launch_group_pool(PoolParams p, const SegTable& s, hipStream_t st);
 // ds_i / p_i with the statistics, M and dM of row i's bag
 int launch_group_bwd_prep(BwdPrepParams p, const int* bag, hipStream_t st);
 int set_dyn_lds(const void* kern, int bytes);
-void debug_stamps_fwd(unsigned long long* out8);
-void debug_stamps_bwd(unsigned long long* out8);
 
 // Optional per-kernel timing with HIP events on the launch stream: records into the mmf_trace of the ABI call in
 // progress (mmf_amil_desc::trace, thread-local while the call runs); no cost when the call carries none.

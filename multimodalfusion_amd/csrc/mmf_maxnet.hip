@@ -60,14 +60,10 @@ __device__ inline void mx_grid_barrier(unsigned* cnt, int nw, Mid&& mid) {
   __syncthreads();
   mid();
   if (threadIdx.x == 0) {
-#ifndef MMF_MX_NOFENCE               // (diagnostic build: the barrier without its fences -- results are wrong, the time is the point)
     if (FENCED) __threadfence();     // release: this workgroup's stores are visible device-wide
-#endif
     __hip_atomic_fetch_add(cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     while (__hip_atomic_load(cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < (unsigned)nw) __builtin_amdgcn_s_sleep(1);
-#ifndef MMF_MX_NOFENCE
     if (FENCED) __threadfence();     // acquire
-#endif
   }
   __syncthreads();
 }
@@ -97,13 +93,7 @@ __device__ inline float mx_ld_dev(const float* p) { return __hip_atomic_load(p, 
 #define MX_MFMA_K(acc, areg, bval, q) acc = __builtin_amdgcn_mfma_f32_4x4x1f32(areg, bval, acc, 4, q, 0)
 template <int R, bool VEC, class Pre>
 __device__ inline void mx_rows_gemm(const float* __restrict__ xs, const float* __restrict__ W, int ldw, int K, float* wl,
-                                    float (&acc)[R], Pre&& pre, unsigned long long* dbg = nullptr) {
-#ifdef MMF_STAMPS
-#define MX_GSTAMP(i) do { if (dbg && blockIdx.x == 0 && threadIdx.x == 0) dbg[i] = __builtin_readcyclecounter(); } while (0)
-#else
-#define MX_GSTAMP(i)
-  (void)dbg;
-#endif
+                                    float (&acc)[R], Pre&& pre) {
   const int tid = threadIdx.x;
   typedef mx_v4f v4f;
   // four accumulator sets, k mod 4: a chain of dependent 4x4x1 MFMAs advances one instruction per ~44 cycles (measured: 64 of
@@ -186,16 +176,13 @@ __device__ inline void mx_rows_gemm(const float* __restrict__ xs, const float* _
   fetch(0, stage0);
   if (K > 64) fetch(64, stage1);
   pre();
-  MX_GSTAMP(0);
 #pragma unroll 1
   for (int k0 = 0; k0 < K; k0 += 128) {
     __syncthreads();                 // the previous chunk has been read by everybody
     put(stage0);
     __syncthreads();
-    if (k0 == 0) MX_GSTAMP(1);
     if (k0 + 128 < K) fetch(k0 + 128, stage0);
     chunk(k0);
-    if (k0 == 0) MX_GSTAMP(2);
     if (k0 + 64 < K) {
       __syncthreads();
       put(stage1);
@@ -204,7 +191,6 @@ __device__ inline void mx_rows_gemm(const float* __restrict__ xs, const float* _
       chunk(k0 + 64);
     }
   }
-  MX_GSTAMP(3);
 #pragma unroll
   for (int r = 0; r < 4; ++r) acc[r] = (accq[0][r] + accq[1][r]) + (accq[2][r] + accq[3][r]);
 }
@@ -268,18 +254,11 @@ __device__ inline void mx_stage(float* dst, int n, Src&& src) {
   }
 }
 
-#ifdef MMF_STAMPS
-#define MX_STAMP(i) do { if (blockIdx.x == 0 && threadIdx.x == 0 && p.stamps) p.stamps[i] = __builtin_readcyclecounter(); } while (0)
-#else
-#define MX_STAMP(i)
-#endif
-
 template <int NW>
 __global__ __launch_bounds__(256) void maxnet_cox_step_kernel(MaxnetStepParams p) {
   constexpr int R = MX_R, MX_NW = NW, MX_NS = MX_H / NW;     // output features per workgroup in phase 4
   constexpr int BP = NW * MX_R;                              // row pitch of the transposed dpre arrays: every workgroup's rows
   extern __shared__ __align__(16) float sm[];
-  MX_STAMP(0);
   float* xs = sm;                               // [256][R] layer input of this workgroup's rows
   float* wl = xs + 256 * R;                     // [256][68] staged weights; phases 2-4: scratch
   float* red = wl + 256 * MX_WP;                // [4][R] + misc
@@ -304,7 +283,6 @@ __global__ __launch_bounds__(256) void maxnet_cox_step_kernel(MaxnetStepParams p
   };
   if (G <= 64 && (G & 3) == 0 && (reinterpret_cast<uintptr_t>(p.W0) & 15) == 0) mx_rows_narrow<R>(xs, p.W0, G, acc, stage_x);
   else mx_rows_gemm<R, false>(xs, p.W0, G, G, wl, acc, stage_x);
-  MX_STAMP(1);
   {
     const float b = p.b0[tid];
 #pragma unroll
@@ -320,7 +298,7 @@ __global__ __launch_bounds__(256) void maxnet_cox_step_kernel(MaxnetStepParams p
     __syncthreads();                            // every thread is done with xs as layer 0's input
 #pragma unroll
     for (int r = 0; r < R; ++r) xs[tid * R + r] = y0d[r];
-  }, p.stamps ? p.stamps + 12 : nullptr);
+  });
   float part[R];
 #pragma unroll
   for (int r = 0; r < R; ++r) {
@@ -339,7 +317,6 @@ __global__ __launch_bounds__(256) void maxnet_cox_step_kernel(MaxnetStepParams p
     mx_st_dev(p.risk + r0 + tid, red[tid] + red[R + tid] + red[2 * R + tid] + red[3 * R + tid] + bcv);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // landed before the barrier, and with it before the ticket; ahead of
   }                                                      // mid(), so that its prefetch loads are not held back by it
-  MX_STAMP(2);
   constexpr int SG3 = 32;
   float w3[2][SG3];                             // dy0's first two stages of W1 rows (phase 3), requested while the barrier waits
   mx_grid_barrier<false>(p.bar, MX_NW, [&]() {
@@ -348,7 +325,6 @@ __global__ __launch_bounds__(256) void maxnet_cox_step_kernel(MaxnetStepParams p
 #pragma unroll
     for (int u = 0; u < SG3; ++u) w3[1][u] = p.W1[(size_t)(SG3 + u) * MX_H + tid];
   });
-  MX_STAMP(3);
 
   // ---------------- phase 2: Cox over the whole batch, gradient of this workgroup's rows ---------------------------------
   float* th = wl;                               // [256] theta
@@ -418,7 +394,6 @@ __global__ __launch_bounds__(256) void maxnet_cox_step_kernel(MaxnetStepParams p
   if (blockIdx.x == 0 && tid == 0) p.loss[0] = -((lp[0] + lp[1]) + (lp[2] + lp[3])) * invB;
   __syncthreads();
 
-  MX_STAMP(4);
   // ---------------- phase 3: d pre-activations of this workgroup's rows --------------------------------------------------
   float* dps = xs;                              // [256][R] dpre1 of these rows (layer 1's outputs n)
   {
@@ -494,7 +469,6 @@ __global__ __launch_bounds__(256) void maxnet_cox_step_kernel(MaxnetStepParams p
     }
     st4(p.dp0 + (size_t)tid * BP + r0, float4{d0[0], d0[1], d0[2], d0[3]});
   }
-  MX_STAMP(5);
   // (tried: y0, dpre1, dpre0, dr and the dWc shares at device scope and this barrier without its fences too -- 32.3 -> 34.3 us:
   // eight write-through scalar stores per thread instead of two 16-byte ones cost phase 3 more than the fences cost here)
   // phase 4's LDS map (wl is free from here on); the first block of x rows -- an input, nothing another workgroup writes --
@@ -507,7 +481,6 @@ __global__ __launch_bounds__(256) void maxnet_cox_step_kernel(MaxnetStepParams p
   const int XB = (256 * MX_WP - 24 * 256 - 256) / G;   // rows of x that fit behind d1s / d0s / rb and in front of cw
   const int xb0 = B < XB ? B : XB;
   mx_grid_barrier(p.bar + 1, MX_NW, [&]() { mx_stage(xl, xb0 * G, [&](int e) { return p.x[e]; }); });
-  MX_STAMP(6);
 
   // ---------------- phase 4: weight gradients, 8 output features per workgroup ------------------------------------------
   const int n0 = blockIdx.x * MX_NS;
@@ -543,7 +516,6 @@ __global__ __launch_bounds__(256) void maxnet_cox_step_kernel(MaxnetStepParams p
   }
   cw[(tid % MX_NS) * MX_NW + tid / MX_NS] = cshare;
   __syncthreads();
-  MX_STAMP(8);
   {
     float a[MX_NS];
     // dW1[n0 + i][k = tid] = sum_b dpre1[b][n0 + i] y0[b][k]: 32 batch rows per stage, the next stage in flight.  4 x 4 x 1
@@ -592,7 +564,6 @@ __global__ __launch_bounds__(256) void maxnet_cox_step_kernel(MaxnetStepParams p
       *o = p.accumulate ? *o + a[i] : a[i];
     }
   }
-  MX_STAMP(9);
   {                                              // dW0[n0 + i][g] = sum_b dpre0[b][n0 + i] x[b][g]   (G <= 256)
     // (tried: the same 4 x 4 x 1 blocks as dW1, lane = column, the waves splitting the batch and meeting in LDS -- 4.8 -> 5.5 k
     // cycles at G = 36: two 16-row groups per wave do not pay for the extra reduction)
@@ -633,7 +604,6 @@ __global__ __launch_bounds__(256) void maxnet_cox_step_kernel(MaxnetStepParams p
       *o = p.accumulate ? *o + sum : sum;
     }
   }
-  MX_STAMP(10);
   {                                              // db1 / db0 of the slice: 16 lanes per (array, feature), rows interleaved
     constexpr int NSUM = 2 * MX_NS;              // 16 (or 8) sums
     const int sidx = tid >> 4, sub = tid & 15;   // 256 threads = 16 sums x 16 lanes
@@ -651,7 +621,6 @@ __global__ __launch_bounds__(256) void maxnet_cox_step_kernel(MaxnetStepParams p
       *o = p.accumulate ? *o + sacc : sacc;
     }
   }
-  MX_STAMP(11);
   if (tid < MX_NS) {                            // the shares of column n0 + tid in workgroup order, eight interleaved partial sums
     float cpart[8];
 #pragma unroll
@@ -672,7 +641,6 @@ __global__ __launch_bounds__(256) void maxnet_cox_step_kernel(MaxnetStepParams p
       p.dbc[0] = p.accumulate ? p.dbc[0] + t : t;
     }
   }
-  MX_STAMP(7);
   // the tick words go back to zero: the last workgroup to get here knows that everybody has passed both barriers
   __syncthreads();
   if (tid == 0) {
@@ -696,7 +664,7 @@ static int maxnet_step_workgroups(int B) {
 int maxnet_step_dp_pitch(int B) { return maxnet_step_workgroups(B) * MX_R; }     // BP of the kernel the launcher picks
 
 size_t maxnet_step_workspace_floats(int B) {
-  return (size_t)2 * B * MX_H + (size_t)2 * MX_H * maxnet_step_dp_pitch(B) + (size_t)((B + 63) / 64 * 64) + 32 + (size_t)MX_NW_MAX * MX_H;
+  return (size_t)2 * B * MX_H + (size_t)2 * MX_H * maxnet_step_dp_pitch(B) + (size_t)((B + 63) / 64 * 64) + (size_t)MX_NW_MAX * MX_H;
 }
 
 bool maxnet_step_ok(int B, int G, int H0, int H1) { return B >= 1 && B <= 256 && G >= 1 && G <= 256 && H0 == MX_H && H1 == MX_H; }

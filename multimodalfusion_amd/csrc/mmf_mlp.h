@@ -114,7 +114,6 @@ struct MaxnetStepParams {
   float loss_scale;
   float *y0, *y1, *dp1, *dp0, *dr;   // workspace: y0, y1 [B][256]; dp1, dp0 TRANSPOSED [256][maxnet_step_dp_pitch(B)]; dr [B]
   float* dwc_part;                   // workspace: [32 workgroups][256] shares of dWc
-  unsigned long long* stamps;        // -DMMF_STAMPS builds: 8 words of wall-clock stamps written by workgroup 0, else null
   unsigned* bar;                     // 3 tick words
   float *risk, *loss;
   float *dW0, *db0, *dW1, *db1, *dWc, *dbc;

@@ -175,7 +175,7 @@ class MM_MIL_Attention_fc_surv(MM_MIL_Attention_fc):
         dev = (path_x if path_x is not None else kwargs[self.modalities[0]] if "radio" in order
                else kwargs["genomic_features"]).device
         # the side stream costs this step ~0.12 ms of host time (stream switches, four cross-stream waits) and pays from
-        # 20k fp32 rows on (tools/r4_mm_fork.sh: 20k 0.60 -> 0.54 ms, 50k 1.02 -> 0.89; 10k 0.43 -> 0.45; bf16 100k 0.59 -> 0.56)
+        # 20k fp32 rows on (20k 0.60 -> 0.54 ms, 50k 1.02 -> 0.89; 10k 0.43 -> 0.45; bf16 100k 0.59 -> 0.56)
         fork = self._fork_ok(path_x, getattr(self, "mmf_fork_min_one_call", 80_000))
         grads = {}                                   # parameter -> gradient tensor of this step
 
@@ -364,7 +364,7 @@ class MM_MIL_Attention_fc_surv(MM_MIL_Attention_fc):
         if "path" in self.mode:
             # with the small branches on the side stream the pathology stack plans its wide tiles for 224 CUs (the hint of
             # mmf_amil_desc::concurrent): the branches' kernels then find CUs while a projection / K-dh launch is resident
-            # instead of waiting for it to drain (as one hipGraph 1.13 -> 1.05 ms, tools/r4_mm_try.sh)
+            # instead of waiting for it to drain (as one hipGraph 1.13 -> 1.05 ms)
             prev = ops.set_concurrent(True) if fork else None
             M_path, A_raw["pathology"] = amil_stack(self.attention_net_WSI, kwargs["path_features"], self.training)
             if fork:

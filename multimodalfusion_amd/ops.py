@@ -219,7 +219,7 @@ def amil_pool(x, W1, b1, Wa, ba, Wb, bb, Wc, bc, gated, p_h=0.0, p_att=0.0, seed
 class AmilHeadFn(torch.autograd.Function):
     """Attention stack + classifier/hazard head as ONE autograd node (models/model_attention_mil_path.py:52-61):
     (x, stack params, Wk, bk) -> (hazards, S, Y_hat, A_raw).  Same kernels as AmilPoolFn + SurvHeadFn; one node less
-    on a path where a 1k-10k bag step is bound by host dispatch (tools/host_split2.py)."""
+    on a path where a 1k-10k bag step is bound by host dispatch."""
 
     @staticmethod
     def forward(ctx, x, W1, b1, Wa, ba, Wb, bb, Wc, bc, Wk, bk, gated, p_h, p_att, seed):

@@ -2,7 +2,7 @@
 
 HIP multiplexes a process's streams onto a handful of hardware queues; two streams that land on the same queue execute
 in order, whatever the program says.  Which pool stream shares a queue with which depends on how many streams the process
-made before (measured, tools/r4_mm_queue.py: with the 7th pool stream as the side stream the multimodal step takes 1.07
+made before (measured, DESIGN.md §4e: with the 7th pool stream as the side stream the multimodal step takes 1.07
 ms, with any of its neighbours 0.89 -- and the two-bags-in-flight rate falls back to one bag at a time the same way).
 `stream_beside` therefore PROBES: ~1 ms of streaming kernels on the reference stream, a tiny kernel on the candidate that
 waits for their start only; the candidate is kept when its kernel finishes while the reference stream is still busy.

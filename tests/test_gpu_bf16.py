@@ -180,7 +180,7 @@ def test_mm_with_bf16_path_bag_tracks_the_fp32_run():
 def test_bf16_step_is_bit_reproducible(N, mode, monkeypatch):
     """Two 4-wave workgroups share a CU in the fused forward and in K-dh (second forms): any cross-wave race or missed hazard
     shows as a handful of differing elements in a few tiles of a few launches (round 3 found one that way: packed-fp32
-    instructions in the fused forward, tools/f2_debug.py).  Scores and every gradient must be bit-identical over repeated
+    instructions in the fused forward).  Scores and every gradient must be bit-identical over repeated
     forward + backward passes -- in eval mode (the <false> instantiations of the two kernels) and in train mode with a pinned
     dropout seed, without and with attention dropout: the <true> instantiations that training and bench.py run (keep-bits
     hashed inside the fused forward's main loop; K-dh's attention-dropout variant), alone and with two bags in flight."""

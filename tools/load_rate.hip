@@ -3,7 +3,8 @@
 //   pattern 0: k-contiguous rows of a big [N x 1024] matrix (128-B row segments, HBM stream)   -- the x operand
 //   pattern 1: a 1 MB matrix re-read by every workgroup (L2-resident)                          -- the W1 operand
 //   pattern 2: m-contiguous [32 rows x 512 B] slabs of the big matrix                          -- the TN operands
-// Build: hipcc --offload-arch=gfx950 -O3 tools/load_rate.hip -o gpurun_out/load_rate
+// Usage: hipcc --offload-arch=gfx950 -O3 tools/load_rate.hip -o multimodalfusion_amd/_diag/load_rate &&
+//        timeout -k 10 120 multimodalfusion_amd/_diag/load_rate
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>

@@ -1,5 +1,6 @@
 // Calibration: fp32 MFMA (v_mfma_f32_32x32x2_f32) issue rate from registers, W waves per SIMD.
-// Build: hipcc --offload-arch=gfx950 -O3 tools/mfma_peak.hip -o gpurun_out/mfma_peak
+// Usage: hipcc --offload-arch=gfx950 -O3 tools/mfma_peak.hip -o multimodalfusion_amd/_diag/mfma_peak &&
+//        timeout -k 10 120 multimodalfusion_amd/_diag/mfma_peak
 #include <hip/hip_runtime.h>
 #include <cstdio>
 typedef float f32x16 __attribute__((ext_vector_type(16)));

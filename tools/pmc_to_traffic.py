@@ -1,4 +1,4 @@
-"""profiles/traffic.json entry from the PMC pass directories of one workload (see tools/profile_r03.sh).
+"""profiles/traffic.json entry from the PMC pass directories of one workload (`rocprofv3 --pmc` runs, one pass each).
 usage: pmc_to_traffic.py <instances> <f32|bf16> <source label> <dir> [<dir> ...]   -> prints the JSON object"""
 import collections, csv, glob, json, sys
 N, dtype, source = int(sys.argv[1]), sys.argv[2], sys.argv[3]
