@@ -7,7 +7,8 @@ import torch.nn as nn
 
 from .. import ops
 from ..utils.utils import initialize_weights
-from .model_modules import AMIL_SIZES, amil_stack, amil_stack_head, amil_stack_nll_step, make_amil_stack
+from .model_modules import (AMIL_SIZES, amil_stack, amil_stack_head, amil_stack_nll_step, hand_over_grads,
+                            make_amil_stack)
 
 
 class MIL_Attention_fc_radio(nn.Module):
@@ -59,6 +60,10 @@ class MIL_Attention_fc_surv_radio(MIL_Attention_fc_radio):
             raise RuntimeError("nll_step needs every parameter of the head to require grad")
         bags = [kwargs[m] for m in self.modalities]
         many = len(bags) > 1
+        rd_out = head_out = None                # grad_out: reduce_dim's two entries first, then the head's
+        if grad_out is not None:
+            grad_out = list(grad_out)
+            rd_out, head_out = (grad_out[:2], grad_out[2:]) if many else (None, grad_out)
         with torch.no_grad():
             if many:
                 ctx = HandCtx((True, True) + (False,) * len(bags))
@@ -66,21 +71,12 @@ class MIL_Attention_fc_surv_radio(MIL_Attention_fc_radio):
                 dx = torch.empty_like(x)
             else:
                 x, dx = bags[0], None
-            head_out = None if grad_out is None else list(grad_out)[2 if many else 0:]
             out = amil_stack_nll_step(self.attention_net_radio, self.classifier, x, self.training, label, c, alpha,
                                       loss_scale, head_out, accumulate, dx_out=dx)
             if many:
-                dW, db = LinearCatFn.backward(ctx, dx)[:2]
                 W, b = self.reduce_dim.weight, self.reduce_dim.bias
-                if grad_out is not None:
-                    gW, gb = list(grad_out)[:2]
-                    (gW.add_(dW), gb.add_(db)) if accumulate else (gW.copy_(dW), gb.copy_(db))
-                else:
-                    for p, g in ((W, dW), (b, db)):
-                        if p.grad is None:
-                            p.grad = g
-                        else:
-                            p.grad.add_(g)
+                dW, db = LinearCatFn.backward(ctx, dx)[:2]
+                hand_over_grads((W, b), {W: dW, b: db}, rd_out, accumulate)
         return out
 
     def forward(self, **kwargs):

@@ -7,7 +7,7 @@ import torch.nn as nn
 
 from .. import ops
 from ..utils.utils import init_max_weights
-from .model_modules import SNN_Block, snn_stack
+from .model_modules import SNN_Block, snn_stack, step_grad_buffers
 
 
 OMIC_SIZES = {"small": (256, 256), "big": (1024, 256)}         # hidden widths of the SNN (model_genomic.py:17)
@@ -79,14 +79,7 @@ class MaxNet(MaxNet_base):
         x = genomic_features
         params = [self.fc_omic[0][0].weight, self.fc_omic[0][0].bias, self.fc_omic[1][0].weight, self.fc_omic[1][0].bias,
                   self.classifier.weight, self.classifier.bias]
-        if grad_out is not None:
-            grads, accumulate = list(grad_out), bool(accumulate)
-        else:
-            missing = [p for p in params if p.grad is None]
-            accumulate = len(missing) < len(params)
-            for p in missing:
-                p.grad = (torch.zeros_like if accumulate else torch.empty_like)(p)
-            grads = [p.grad for p in params]
+        grads, accumulate = step_grad_buffers(params, x.device, grad_out, accumulate)
         if not (torch.is_tensor(times) and times.is_cuda and times.dtype == torch.float64):
             times = self._times_to_device(np.asarray(times.cpu() if torch.is_tensor(times) else times, dtype=np.float64), x.device)
         tr = self.training

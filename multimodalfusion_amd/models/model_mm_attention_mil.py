@@ -14,12 +14,15 @@ about each defect -- the signature and the mathematics are kept, nothing else is
 """
 from __future__ import annotations
 
+import contextlib
+
 import torch
 import torch.nn as nn
 
 from .. import ops
 from ..utils.utils import initialize_weights
-from .model_modules import Attn_Net, Attn_Net_Gated, SNN_Block, XlinearFusion, amil_stack, snn_stack
+from .model_modules import (Attn_Net, Attn_Net_Gated, SNN_Block, XlinearFusion, amil_stack, hand_over_grads, snn_stack,
+                            stack_args)
 
 
 class MM_MIL_Attention_fc(nn.Module):
@@ -126,13 +129,21 @@ class MM_MIL_Attention_fc_surv(MM_MIL_Attention_fc):
             st = pool[cur.cuda_stream] = stream_beside([cur], device)
         return st
 
-    def _fork_ok(self, path_x, min_units=120_000):
+    def _fork(self, path_x, min_units=120_000):
+        """The side-stream fork of forward() and nll_step: (cur, side, branch) -- the current stream, the side stream
+        (ordered after the work cur has queued) and a context manager that issues on it -- or (None, None, a null context)
+        when the branches stay on the current stream."""
         # worth it only while the step is GPU-bound, i.e. the pathology stack runs for longer than the host needs to
         # issue the step (~0.9 ms): >= 30k fp32 instances / >= 120k bf16 instances (measured: 50k fp32 1.30 -> 1.07 ms;
         # 100k bf16 is host-bound and the extra stream calls cost 0.05 ms)
-        return (getattr(self, "mmf_side_stream", True)          # set False on an instance to keep everything on one stream
+        if not (getattr(self, "mmf_side_stream", True)          # set False on an instance to keep everything on one stream
                 and path_x is not None and path_x.is_cuda and ("radio" in self.mode or "omic" in self.mode)
-                and path_x.shape[0] * (1 if path_x.dtype == torch.bfloat16 else 4) >= min_units)
+                and path_x.shape[0] * (1 if path_x.dtype == torch.bfloat16 else 4) >= min_units):
+            return None, None, contextlib.nullcontext
+        cur = torch.cuda.current_stream(path_x.device)
+        side = self._side_stream(path_x.device)
+        side.wait_stream(cur)
+        return cur, side, lambda: torch.cuda.stream(side)
 
     def _concat_order(self):
         has = lambda k: k in self.mode
@@ -143,6 +154,18 @@ class MM_MIL_Attention_fc_surv(MM_MIL_Attention_fc):
         if has("omic") and has("path") and not has("radio"):
             return ["omic", "path"]
         return ["radio", "path", "omic"]
+
+    def _concat_layout(self):
+        """(order, {branch: slice of the fused vector}, width of the fused vector): the embeddings side by side in
+        _concat_order()."""
+        order = self._concat_order()
+        width = {"radio": self.attention_net_radio[0].out_features, "path": self.attention_net_WSI[0].out_features,
+                 "omic": self.fc_omic[-1][0].out_features}
+        cols, F = {}, 0
+        for k in order:
+            cols[k] = slice(F, F + width[k])
+            F += width[k]
+        return order, cols, F
 
     def nll_step(self, label, c, alpha=0.0, loss_scale=1.0, grad_out=None, accumulate=None, **kwargs):
         """Extension of the reference surface (the training-loop mirror uses it, utils/core_utils.py): the whole training
@@ -157,36 +180,22 @@ class MM_MIL_Attention_fc_surv(MM_MIL_Attention_fc):
         None receives the fresh buffer, as autograd does) -- or to `grad_out`, tensors in self.parameters() order,
         overwritten unless `accumulate`.  Returns (hazards, S, Y_hat, A_raw dict, loss, risk), detached."""
         from ..ops import AmilPoolFn, HandCtx, LinearCatFn, _dense_bwd_raw, _dense_fwd_raw
-        if self.fusion == "tensor" and not (self.mm.skip and len(self._concat_order()) * self.mm.reduce[0][0][0].weight.shape[0] <= 384):
+        order, cols, F = self._concat_layout()
+        if self.fusion == "tensor" and not (self.mm.skip and len(order) * self.mm.reduce[0][0][0].weight.shape[0] <= 384):
             raise NotImplementedError("nll_step covers the XlinearFusion configuration the heads use (skip, one patient)")
         params = list(self.parameters())
         if any(not p.requires_grad for p in params):
             raise RuntimeError("nll_step needs every parameter to require grad")
         tr = self.training
-        order = self._concat_order()
-        width = {"radio": self.attention_net_radio[0].out_features, "path": self.attention_net_WSI[0].out_features,
-                 "omic": self.fc_omic[-1][0].out_features}
-        off, o = {}, 0
-        for k in order:
-            off[k] = o
-            o += width[k]
-        F = o
         path_x = kwargs.get("path_features") if "path" in order else None
         dev = (path_x if path_x is not None else kwargs[self.modalities[0]] if "radio" in order
                else kwargs["genomic_features"]).device
-        # the side stream costs this step ~0.12 ms of host time (stream switches, four cross-stream waits) and pays from
-        # 20k fp32 rows on (DESIGN.md §4e: 20k 0.60 -> 0.54 ms, 50k 1.02 -> 0.89; 10k 0.43 -> 0.45; bf16 100k 0.59 -> 0.56)
-        fork = self._fork_ok(path_x, getattr(self, "mmf_fork_min_one_call", 80_000))
         grads = {}                                   # parameter -> gradient tensor of this step
 
-        def stack_args(seq):
-            lin, att = seq[0], seq[3]
-            gated = isinstance(att, Attn_Net_Gated)
-            Wa, ba, Wb, bb, Wc, bc = att.stack_params()
-            p_h = seq[2].p if tr else 0.0
-            p_att = 0.25 if (tr and att.att_dropout) else 0.0
+        def stack_forward(ctx, seq, x, k):
+            gated, ps, p_h, p_att = stack_args(seq, tr)
             seed = ops.next_dropout_seed() if tr else 0
-            return (lin.weight, lin.bias, Wa, ba, Wb, bb, Wc, bc), (gated, p_h, p_att, seed)
+            return ps, AmilPoolFn.forward(ctx, x, *ps, gated, p_h, p_att, seed, M_out=feat[:, cols[k]])[1]
 
         def stack_backward(ctx, ps, g):
             out = AmilPoolFn.backward(ctx, g, None)
@@ -197,15 +206,10 @@ class MM_MIL_Attention_fc_surv(MM_MIL_Attention_fc):
 
         with torch.no_grad():
             feat = torch.empty((1, F), dtype=torch.float32, device=dev)
-            slot = lambda k: feat[:, off[k]:off[k] + width[k]]
-            if fork:
-                cur = torch.cuda.current_stream(dev)
-                side = self._side_stream(dev)
-                side.wait_stream(cur)
-                branch = lambda: torch.cuda.stream(side)
-            else:
-                import contextlib
-                branch = contextlib.nullcontext
+            # the side stream costs this step ~0.12 ms of host time (stream switches, four cross-stream waits) and pays from
+            # 20k fp32 rows on (20k 0.60 -> 0.54 ms, 50k 1.02 -> 0.89; 10k 0.43 -> 0.45; bf16 100k 0.59 -> 0.56)
+            cur, side, branch = self._fork(path_x, getattr(self, "mmf_fork_min_one_call", 80_000))
+            fork = side is not None
             A_raw = {}
             # ---- forward: python order (and with it the dropout-seed order) radio, path, omic as in forward()
             if "radio" in order:
@@ -217,15 +221,13 @@ class MM_MIL_Attention_fc_surv(MM_MIL_Attention_fc):
                         h_radio = LinearCatFn.forward(ctx_cat, self.reduce_dim.weight, self.reduce_dim.bias, *xs)
                     else:
                         h_radio = xs[0]
-                    ps_r, cfg = stack_args(self.attention_net_radio)
                     ctx_r = HandCtx((ctx_cat is not None,) + (True,) * 8 + (False,) * 4)
-                    _, A_raw["radiology"] = AmilPoolFn.forward(ctx_r, h_radio, *ps_r, *cfg, M_out=slot("radio"))
+                    ps_r, A_raw["radiology"] = stack_forward(ctx_r, self.attention_net_radio, h_radio, "radio")
             if "path" in order:
-                ps_p, cfg = stack_args(self.attention_net_WSI)
                 ctx_p = HandCtx((False,) + (True,) * 8 + (False,) * 4)
                 prev = ops.set_concurrent(True) if fork else None      # see forward(): 224-CU tile plan beside the branches
                 try:
-                    _, A_raw["pathology"] = AmilPoolFn.forward(ctx_p, path_x, *ps_p, *cfg, M_out=slot("path"))
+                    ps_p, A_raw["pathology"] = stack_forward(ctx_p, self.attention_net_WSI, path_x, "path")
                 finally:
                     if fork:
                         ops.set_concurrent(prev)
@@ -242,7 +244,7 @@ class MM_MIL_Attention_fc_surv(MM_MIL_Attention_fc):
                         lin, adrop = blk[0], blk[2]
                         acts.append(_dense_fwd_raw(acts[-1], lin.weight, lin.bias, "selu", "alpha" if tr else "none",
                                                    adrop.p if tr else 0.0, seed, i, word,
-                                                   out=slot("omic") if i == nblk - 1 else None))
+                                                   out=feat[:, cols["omic"]] if i == nblk - 1 else None))
             if fork:
                 cur.wait_stream(side)
             if self.fusion == "concat":
@@ -252,7 +254,7 @@ class MM_MIL_Attention_fc_surv(MM_MIL_Attention_fc):
                 hazards, S, Y_hat, loss, risk, dfeat = ops.surv_head_nll_step(feat, Wk, bk, label, c, alpha, dWk, dbk,
                                                                               loss_scale=loss_scale)
                 grads[Wk], grads[bk] = dWk, dbk
-                dslot = lambda k: dfeat[:, off[k]:off[k] + width[k]]
+                dslot = lambda k: dfeat[:, cols[k]]
             else:
                 # ---- XlinearFusion (one node's forward / backward bodies, run by hand), classifier[0] + ReLU + Dropout,
                 # then classifier[3] + hazards + loss + their backward in one launch (forward() lines 182-188)
@@ -267,7 +269,7 @@ class MM_MIL_Attention_fc_surv(MM_MIL_Attention_fc):
                 weights += [fus.encoder1[0].weight, fus.encoder1[0].bias, fus.encoder2[0].weight, fus.encoder2[0].bias]
                 p_f = fus.dropout_rate if tr else 0.0
                 ctx_x = HandCtx((False,) * 3 + (True,) * (len(order) + len(weights)))
-                MMv = XFusionFn.forward(ctx_x, len(order), p_f, seed_f, *[slot(k) for k in order], *weights)
+                MMv = XFusionFn.forward(ctx_x, len(order), p_f, seed_f, *[feat[:, cols[k]] for k in order], *weights)
                 c0, c3 = self.classifier[0], self.classifier[3]
                 p_c = self.classifier[2].p if tr else 0.0
                 kind_c = "dropout" if tr else "none"
@@ -308,45 +310,14 @@ class MM_MIL_Attention_fc_surv(MM_MIL_Attention_fc):
             if fork:
                 cur.wait_stream(side)
             # ---- hand the gradients over (parameters of branches outside `mode` took no part: no gradient, as in autograd)
-            if grad_out is not None:
-                dst, src = [], []
-                for p, t in zip(params, grad_out):
-                    if p in grads:
-                        dst.append(t)
-                        src.append(grads[p])
-                    elif not accumulate:
-                        t.zero_()
-                if accumulate:
-                    torch._foreach_add_(dst, src)
-                else:
-                    torch._foreach_copy_(dst, src)
-            else:
-                dst, src = [], []
-                for p in params:
-                    g = grads.get(p)
-                    if g is None:
-                        continue
-                    if p.grad is None:
-                        p.grad = g
-                    else:
-                        dst.append(p.grad)
-                        src.append(g)
-                if dst:
-                    torch._foreach_add_(dst, src)
+            hand_over_grads(params, grads, grad_out, accumulate)
         return hazards, S, Y_hat, A_raw, loss, risk
 
     def forward(self, **kwargs):
         A_raw = {}
         path_x = kwargs.get("path_features") if "path" in self.mode else None
-        fork = self._fork_ok(path_x)
-        if fork:
-            cur = torch.cuda.current_stream(path_x.device)
-            side = self._side_stream(path_x.device)
-            side.wait_stream(cur)
-            branch = lambda: torch.cuda.stream(side)
-        else:
-            import contextlib
-            branch = contextlib.nullcontext
+        cur, side, branch = self._fork(path_x)
+        fork = side is not None
         joined = []
         # python order (and with it the dropout-seed order) stays radio, path, omic, fusion
         if "radio" in self.mode:

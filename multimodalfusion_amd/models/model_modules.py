@@ -4,6 +4,7 @@ They are parameter containers: the arithmetic of a whole attention stack runs in
 HIP kernels called by the heads (ops.amil_pool)."""
 from __future__ import annotations
 
+import torch
 import torch.nn as nn
 
 
@@ -200,7 +201,6 @@ class XlinearFusion(nn.Module):
 
     def forward(self, v_list: list, seed=None):
         """Dropout sites under one seed: o_i -> i, post-fusion -> 8, encoder1 -> 9, encoder2 -> 10."""
-        import torch
         from .. import ops
         tr = self.training
         if tr and seed is None:
@@ -250,52 +250,74 @@ def make_amil_stack(size: str, gated: bool, att_dropout: bool) -> nn.Sequential:
                          scorer(L=hidden, D=att, dropout=att_dropout, n_classes=1))
 
 
+def stack_args(seq, training):
+    """(gated, (W1, b1, Wa, ba, Wb, bb, Wc, bc), p_h, p_att) of a make_amil_stack Sequential.  Dropout probabilities
+    follow nn.Module.training exactly as the reference's nn.Dropout layers do (the 0.25 after the ReLU is always there in
+    train mode; the two inside the attention net only when it was built with dropout=True).  The caller draws the seed."""
+    lin, att = seq[0], seq[3]
+    Wa, ba, Wb, bb, Wc, bc = att.stack_params()
+    return (isinstance(att, Attn_Net_Gated), (lin.weight, lin.bias, Wa, ba, Wb, bb, Wc, bc),
+            seq[2].p if training else 0.0, 0.25 if (training and att.att_dropout) else 0.0)
+
+
 def amil_stack(seq, x, training):
     """Run Sequential(Linear, ReLU, Dropout(0.25), Attn_Net*) + softmax pooling on the GPU.
-    Returns (M [1 x H], A_raw [1 x N]).  Dropout probabilities follow nn.Module.training exactly as
-    the reference's nn.Dropout layers do (the 0.25 after the ReLU is always there in train mode;
-    the two inside the attention net only when it was built with dropout=True)."""
+    Returns (M [1 x H], A_raw [1 x N])."""
     from .. import ops
-    lin, att = seq[0], seq[3]
-    gated = isinstance(att, Attn_Net_Gated)
-    Wa, ba, Wb, bb, Wc, bc = att.stack_params()
-    p_h = seq[2].p if training else 0.0
-    p_att = 0.25 if (training and att.att_dropout) else 0.0
+    gated, stack, p_h, p_att = stack_args(seq, training)
     seed = ops.next_dropout_seed() if training else 0
-    return ops.amil_pool(x, lin.weight, lin.bias, Wa, ba, Wb, bb, Wc, bc, gated, p_h, p_att, seed)
+    return ops.amil_pool(x, *stack, gated, p_h, p_att, seed)
 
 
-def _stack_step_setup(seq, classifier, device, training, grad_out, accumulate):
-    """The gradient conventions shared by the one-call steps (amil_stack_nll_step, amil_stack_nll_step_group): gradients
-    go to `grad_out` (tensors in the order of [*seq.parameters(), *classifier.parameters()], `accumulate` as given) or to
-    .grad -- parameters whose .grad is None get a fresh buffer, as autograd does; when all of them are None the kernels
-    write instead of accumulate and nothing is zero-filled.  Returns (gated, stack, (Wk, bk), grads, accumulate, p_h,
-    p_att)."""
-    import torch
-    lin, att = seq[0], seq[3]
-    gated = isinstance(att, Attn_Net_Gated)
-    Wa, ba, Wb, bb, Wc, bc = att.stack_params()
-    params = [lin.weight, lin.bias, Wa, ba, Wb, bb, Wc, bc, classifier.weight, classifier.bias]
-    live = [p for p in params if p is not None]
+def step_grad_buffers(params, device, grad_out, accumulate):
+    """The gradient destinations of a one-call step whose kernels write or accumulate in place: `grad_out` (tensors in
+    the order of the non-None `params`; `accumulate` as given) or .grad -- parameters whose .grad is None get a fresh
+    buffer, as autograd does (slices of one flat buffer; when all of them are None the kernels write instead of
+    accumulate and nothing is zero-filled).  A None in `params` (an ungated stack's Wb, bb) maps to None.
+    Returns (destinations in `params` order, accumulate)."""
     if grad_out is not None:
         it = iter(grad_out)
-        grads = [None if p is None else next(it) for p in params]
-        accumulate = bool(accumulate)
-    else:
-        missing = [p for p in live if p.grad is None]
-        accumulate = len(missing) < len(live)
-        if missing:
-            n = sum(p.numel() for p in missing)
-            flat = (torch.zeros if accumulate else torch.empty)(n, dtype=torch.float32, device=device)
-            off = 0
-            for p in missing:
-                p.grad = flat[off:off + p.numel()].view_as(p)
-                off += p.numel()
-        grads = [None if p is None else p.grad for p in params]
-    p_h = seq[2].p if training else 0.0
-    p_att = 0.25 if (training and att.att_dropout) else 0.0
-    return gated, (lin.weight, lin.bias, Wa, ba, Wb, bb, Wc, bc), (classifier.weight, classifier.bias), grads, \
-        accumulate, p_h, p_att
+        return [None if p is None else next(it) for p in params], bool(accumulate)
+    live = [p for p in params if p is not None]
+    missing = [p for p in live if p.grad is None]
+    accumulate = len(missing) < len(live)
+    if missing:
+        flat = (torch.zeros if accumulate else torch.empty)(sum(p.numel() for p in missing), dtype=torch.float32,
+                                                             device=device)
+        off = 0
+        for p in missing:
+            p.grad = flat[off:off + p.numel()].view_as(p)
+            off += p.numel()
+    return [None if p is None else p.grad for p in params], accumulate
+
+
+def hand_over_grads(params, grads, grad_out, accumulate):
+    """Hands over the fresh gradients of a composed one-call step (grads: {parameter: gradient}; a parameter missing from
+    it took no part, as in autograd).  `grad_out` (tensors in `params` order) is overwritten, or added to when
+    `accumulate`, in one _foreach call; entries of parameters without a gradient are zeroed unless accumulating.
+    Otherwise a None .grad takes the gradient tensor itself and the set ones are added to in one _foreach_add_."""
+    dst, src = [], []
+    if grad_out is not None:
+        for p, t in zip(params, grad_out):
+            g = grads.get(p)
+            if g is not None:
+                dst.append(t)
+                src.append(g)
+            elif not accumulate:
+                t.zero_()
+        (torch._foreach_add_ if accumulate else torch._foreach_copy_)(dst, src)
+        return
+    for p in params:
+        g = grads.get(p)
+        if g is None:
+            continue
+        if p.grad is None:
+            p.grad = g
+        else:
+            dst.append(p.grad)
+            src.append(g)
+    if dst:
+        torch._foreach_add_(dst, src)
 
 
 def amil_stack_nll_step(seq, classifier, x, training, Y, c, alpha, loss_scale=1.0, grad_out=None, accumulate=None,
@@ -309,27 +331,25 @@ def amil_stack_nll_step(seq, classifier, x, training, Y, c, alpha, loss_scale=1.
     dx_out: an [N x L] fp32 tensor that receives the gradient with respect to the bag (overwritten), for a head whose bag
     is itself computed (the radio head's reduce_dim).
     Returns (hazards, S, Y_hat, A_raw, loss, risk), all detached."""
-    import torch
     from .. import ops
-    gated, stack, cls, grads, accumulate, p_h, p_att = _stack_step_setup(seq, classifier, x.device, training, grad_out,
-                                                                         accumulate)
+    gated, stack, p_h, p_att = stack_args(seq, training)
+    Wk, bk = classifier.weight, classifier.bias
+    grads, accumulate = step_grad_buffers([*stack, Wk, bk], x.device, grad_out, accumulate)
     seed = ops.next_dropout_seed() if training else 0
     with torch.no_grad():
-        return ops.amil_nll_step(x, stack, cls[0], cls[1],
-                                 gated, Y, c, alpha, grads, loss_scale=loss_scale, accumulate=accumulate,
+        return ops.amil_nll_step(x, stack, Wk, bk, gated, Y, c, alpha, grads, loss_scale=loss_scale, accumulate=accumulate,
                                  p_h=p_h, p_att=p_att, seed=seed, dx=dx_out)
 
 
 def amil_stack_nll_step_group(seq, classifier, bags, training, Y, c, alpha, loss_scale=1.0, grad_out=None,
                               accumulate=None, seeds=None):
     """amil_stack_nll_step for the G bags of one accumulation window in ONE C-ABI call (ops.amil_nll_step_group): the
-    gradients of sum_g loss_g * loss_scale, with the same .grad / grad_out conventions (_stack_step_setup).  bags: a list
+    gradients of sum_g loss_g * loss_scale, with the same .grad / grad_out conventions (step_grad_buffers).  bags: a list
     or tuple of [N_g x L] fp32 device tensors (concatenated once on the device), or a pre-concatenated pair
     (x_cat [sum N x L] tensor, sizes: a list / tuple of ints).  In train mode one ops.next_dropout_seed() is drawn per bag,
     in bag order -- bag g gets the masks of the g-th of G nll_step calls -- unless `seeds` gives them (the training loop
     draws each bag's seed when the bag arrives).
     Returns (hazards [G x K], S [G x K], Y_hat [G x 1], [A_raw [1 x N_g]], loss [G], risk [G]), all detached."""
-    import torch
     from .. import ops
     if (isinstance(bags, (tuple, list)) and len(bags) == 2 and torch.is_tensor(bags[0])
             and isinstance(bags[1], (list, tuple)) and all(isinstance(n, int) for n in bags[1])):
@@ -339,23 +359,19 @@ def amil_stack_nll_step_group(seq, classifier, bags, training, Y, c, alpha, loss
             raise TypeError("bags: a list of [N x L] tensors or an (x_cat, sizes) pair")
         sizes = [int(b.shape[0]) for b in bags]
         x_cat = torch.cat(list(bags), 0) if len(bags) > 1 else bags[0]
-    gated, stack, cls, grads, accumulate, p_h, p_att = _stack_step_setup(seq, classifier, x_cat.device, training,
-                                                                         grad_out, accumulate)
+    gated, stack, p_h, p_att = stack_args(seq, training)
+    Wk, bk = classifier.weight, classifier.bias
+    grads, accumulate = step_grad_buffers([*stack, Wk, bk], x_cat.device, grad_out, accumulate)
     if seeds is None:
         seeds = [ops.next_dropout_seed() for _ in sizes] if training else None
     with torch.no_grad():
-        return ops.amil_nll_step_group(x_cat, sizes, stack, cls[0], cls[1], gated, Y, c, alpha, grads,
+        return ops.amil_nll_step_group(x_cat, sizes, stack, Wk, bk, gated, Y, c, alpha, grads,
                                        loss_scale=loss_scale, accumulate=accumulate, p_h=p_h, p_att=p_att, seeds=seeds)
 
 
 def amil_stack_head(seq, classifier, x, training):
     """amil_stack followed by the classifier / hazard head as one autograd node -> (hazards, S, Y_hat, A_raw)."""
     from .. import ops
-    lin, att = seq[0], seq[3]
-    gated = isinstance(att, Attn_Net_Gated)
-    Wa, ba, Wb, bb, Wc, bc = att.stack_params()
-    p_h = seq[2].p if training else 0.0
-    p_att = 0.25 if (training and att.att_dropout) else 0.0
+    gated, stack, p_h, p_att = stack_args(seq, training)
     seed = ops.next_dropout_seed() if training else 0
-    return ops.amil_head(x, lin.weight, lin.bias, Wa, ba, Wb, bb, Wc, bc, classifier.weight, classifier.bias,
-                         gated, p_h, p_att, seed)
+    return ops.amil_head(x, *stack, classifier.weight, classifier.bias, gated, p_h, p_att, seed)

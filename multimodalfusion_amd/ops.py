@@ -294,6 +294,54 @@ class AmilHeadFn(torch.autograd.Function):
         return dx, dW1, db1, dWa, dba, dWb, dbb, dWc, dbc, dWk, dbk, None, None, None, None
 
 
+def _check_grad_buffers(pairs):
+    for g_, w_ in pairs:
+        if g_ is None or g_.dtype != torch.float32 or g_.shape != w_.shape or not g_.is_contiguous():
+            raise _lib.MmfError("gradient buffers must be contiguous float32 tensors shaped like their parameters")
+
+
+def _stack_step_operands(stack, Wk, bk, gated, grads, L, what):
+    """stack (W1, b1, Wa, ba, Wb, bb, Wc, bc) and classifier (Wk, bk) of a one-call step as contiguous fp32, checked
+    against the bag width L and the gradient buffers grads (dW1, ..., dbk).  Returns (the ten operands, AmilGrads with no
+    dx)."""
+    W1, b1, Wa, ba, Wb, bb, Wc, bc, Wk, bk = ws = tuple(map(_f32c, (*stack, Wk, bk)))
+    H, D = W1.shape[0], Wa.shape[0]
+    if W1.shape[1] != L or Wa.shape[1] != H or Wc.numel() != D or Wk.shape[1] != H or Wk.shape[0] > 32:
+        raise _lib.MmfError(f"attention stack / classifier shapes do not match the {what}")
+    dW1, db1, dWa, dba, dWb, dbb, dWc, dbc, dWk, dbk = grads
+    _check_grad_buffers(((dW1, W1), (db1, b1), (dWa, Wa), (dba, ba), (dWc, Wc), (dbc, bc), (dWk, Wk), (dbk, bk)) +
+                        (((dWb, Wb), (dbb, bb)) if gated else ()))
+    return ws, AmilGrads(dW1=ptr(dW1), db1=ptr(db1), dWa=ptr(dWa), dba=ptr(dba), dWb=ptr(dWb) if gated else None,
+                         dbb=ptr(dbb) if gated else None, dWc=ptr(dWc), dbc=ptr(dbc), dx=None)
+
+
+def _nll_head(Wk, bk, Y, c, alpha, eps, loss_scale, dWk, dbk, accumulate, dev, G=0):
+    """The classifier + hazards + nll_surv part of a one-call step: labels / censorships on the device, the outputs and
+    the SurvHead / NllTarget structs.  G = 0: one bag (Y, c: one value each; the outputs share one buffer); G > 0: G bags
+    (Y, c: [G] each).  Returns (hd, tg, (hazards, S, Y_hat, loss, risk), keep); keep holds the other tensors the structs
+    point to (the device Y, c and the logits), which must stay alive until the launch."""
+    K = Wk.shape[0]
+    if not Y.is_cuda and bool(((Y < 0) | (Y >= K)).any()):
+        raise IndexError(f"nll_surv: label out of range [0, {K})")
+    if G:
+        Y = Y.to(device=dev, dtype=torch.int64).contiguous()
+        c = c.to(device=dev, dtype=torch.float32).contiguous()
+        logits, hz, S = torch.empty((G, K), device=dev), torch.empty((G, K), device=dev), torch.empty((G, K), device=dev)
+        loss, risk = torch.empty((G,), device=dev), torch.empty((G,), device=dev)
+    else:
+        Y = Y.reshape(1).to(device=dev, dtype=torch.int64)
+        c = c.reshape(1).to(device=dev, dtype=torch.float32)
+        out = torch.empty((3 * K + 2,), dtype=torch.float32, device=dev)       # logits, hazards, S, loss, risk
+        logits, hz, S = out[0:K], out[K:2 * K].view(1, K), out[2 * K:3 * K].view(1, K)
+        loss, risk = out[3 * K].view(()), out[3 * K + 1:].view(1)
+    Y_hat = torch.empty((G or 1, 1), dtype=torch.int64, device=dev)
+    hd = SurvHead(Wk=ptr(Wk), bk=ptr(bk), K=K, logits=ptr(logits), hazards=ptr(hz), S=ptr(S), Y_hat=ptr(Y_hat),
+                  risk=ptr(risk))
+    tg = NllTarget(Y=ptr(Y), c=ptr(c), alpha=float(alpha), eps=float(eps), loss_scale=float(loss_scale),
+                   loss=ptr(loss), dWk=ptr(dWk), dbk=ptr(dbk), accumulate=1 if accumulate else 0)
+    return hd, tg, (hz, S, Y_hat, loss, risk), (Y, c, logits)
+
+
 def amil_nll_step(x, stack, Wk, bk, gated, Y, c, alpha, grads, loss_scale=1.0, accumulate=False, p_h=0.0, p_att=0.0,
                   seed=0, eps=1e-7, dx=None):
     """(dx: optional [N x L] fp32 tensor that receives d(loss * loss_scale)/dx -- the radio head, whose bag is
@@ -306,43 +354,25 @@ def amil_nll_step(x, stack, Wk, bk, gated, Y, c, alpha, grads, loss_scale=1.0, a
     Returns (hazards [1 x K], S [1 x K], Y_hat [1 x 1], A_raw [1 x N], loss (0-dim, unscaled), risk [1])."""
     bf16 = x.dtype == torch.bfloat16
     x = x.contiguous() if bf16 else _f32c(x)
-    W1, b1, Wa, ba, Wb, bb, Wc, bc = stack
-    W1, b1, Wa, ba, Wc, bc, Wk, bk = map(_f32c, (W1, b1, Wa, ba, Wc, bc, Wk, bk))
-    Wb, bb = _f32c(Wb), _f32c(bb)
     if x.dim() != 2:
         raise _lib.MmfError(f"bag must be [N x L], got {tuple(x.shape)}")
     N, L = x.shape
-    H, D, K = W1.shape[0], Wa.shape[0], Wk.shape[0]
-    if W1.shape[1] != L or Wa.shape[1] != H or Wc.numel() != D or Wk.shape[1] != H or K > 32:
-        raise _lib.MmfError("attention stack / classifier shapes do not match the bag")
-    dW1, db1, dWa, dba, dWb, dbb, dWc, dbc, dWk, dbk = grads
-    for g_, w_ in ((dW1, W1), (db1, b1), (dWa, Wa), (dba, ba), (dWc, Wc), (dbc, bc), (dWk, Wk), (dbk, bk)) + \
-            (((dWb, Wb), (dbb, bb)) if gated else ()):
-        if g_ is None or g_.dtype != torch.float32 or g_.shape != w_.shape or not g_.is_contiguous():
-            raise _lib.MmfError("gradient buffers must be contiguous float32 tensors shaped like their parameters")
+    (W1, b1, Wa, ba, Wb, bb, Wc, bc, Wk, bk), g = _stack_step_operands(stack, Wk, bk, gated, grads, L, "bag")
+    H, D = W1.shape[0], Wa.shape[0]
     dev = x.device
-    if not Y.is_cuda and bool(((Y < 0) | (Y >= K)).any()):
-        raise IndexError(f"nll_surv: label out of range [0, {K})")
-    Y = Y.reshape(1).to(device=dev, dtype=torch.int64)
-    c = c.reshape(1).to(device=dev, dtype=torch.float32)
+    hd, tg, (hz, S, Y_hat, loss, risk), _keep = _nll_head(Wk, bk, Y, c, alpha, eps, loss_scale, grads[8], grads[9],
+                                                          accumulate, dev)
     d = _amil_desc(N, L, H, D, gated, W1, b1, Wa, ba, Wb, bb, Wc, bc, p_h, p_att, seed, _seed_word)
     l = lib()
     nbytes = (l.mmf_amil_bf16_workspace_bytes if bf16 else l.mmf_amil_workspace_bytes)(N, L, H, D, d.gated)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     A_raw = torch.empty((1, N), dtype=torch.float32, device=dev)
-    out = torch.empty((3 * K + 2,), dtype=torch.float32, device=dev)       # logits, hazards, S, loss, risk
-    Y_hat = torch.empty((1, 1), dtype=torch.int64, device=dev)
-    hd = SurvHead(Wk=ptr(Wk), bk=ptr(bk), K=K, logits=ptr(out[0:K]), hazards=ptr(out[K:2 * K]), S=ptr(out[2 * K:3 * K]),
-                  Y_hat=ptr(Y_hat), risk=ptr(out[3 * K + 1:]))
-    tg = NllTarget(Y=ptr(Y), c=ptr(c), alpha=float(alpha), eps=float(eps), loss_scale=float(loss_scale),
-                   loss=ptr(out[3 * K:]), dWk=ptr(dWk), dbk=ptr(dbk), accumulate=1 if accumulate else 0)
-    g = AmilGrads(dW1=ptr(dW1), db1=ptr(db1), dWa=ptr(dWa), dba=ptr(dba), dWb=ptr(dWb) if gated else None,
-                  dbb=ptr(dbb) if gated else None, dWc=ptr(dWc), dbc=ptr(dbc), dx=ptr(dx))
     if dx is not None and (bf16 or dx.dtype != torch.float32 or dx.shape != x.shape or not dx.is_contiguous()):
         raise _lib.MmfError("dx must be a contiguous float32 tensor shaped like an fp32 bag")
+    g.dx = ptr(dx)
     check(l.mmf_amil_nll_step(C.byref(d), ptr(x), 1 if bf16 else 0, ptr(ws), nbytes, C.byref(hd), C.byref(tg),
                               ptr(A_raw), C.byref(g), stream_ptr()), "mmf_amil_nll_step")
-    return (out[K:2 * K].view(1, K), out[2 * K:3 * K].view(1, K), Y_hat, A_raw, out[3 * K].view(()), out[3 * K + 1:].view(1))
+    return hz, S, Y_hat, A_raw, loss, risk
 
 
 GROUP_MAX = 64       # include/mmf_amil.h: MMF_GROUP_MAX
@@ -371,29 +401,18 @@ def amil_nll_step_group(x_cat, sizes, stack, Wk, bk, gated, Y, c, alpha, grads, 
         raise _lib.MmfError(f"a group holds 1 .. {GROUP_MAX} bags, got {G}")
     if min(sizes) < 1:
         raise _lib.MmfError("empty bag in the group")
-    W1, b1, Wa, ba, Wb, bb, Wc, bc = stack
-    W1, b1, Wa, ba, Wc, bc, Wk, bk = map(_f32c, (W1, b1, Wa, ba, Wc, bc, Wk, bk))
-    Wb, bb = _f32c(Wb), _f32c(bb)
     if x_cat.dim() != 2 or x_cat.shape[0] != sum(sizes):
         raise _lib.MmfError(f"x_cat must be [sum N x L] = [{sum(sizes)} x L], got {tuple(x_cat.shape)}")
     R, L = x_cat.shape
-    H, D, K = W1.shape[0], Wa.shape[0], Wk.shape[0]
-    if W1.shape[1] != L or Wa.shape[1] != H or Wc.numel() != D or Wk.shape[1] != H or K > 32:
-        raise _lib.MmfError("attention stack / classifier shapes do not match the bags")
-    dW1, db1, dWa, dba, dWb, dbb, dWc, dbc, dWk, dbk = grads
-    for g_, w_ in ((dW1, W1), (db1, b1), (dWa, Wa), (dba, ba), (dWc, Wc), (dbc, bc), (dWk, Wk), (dbk, bk)) + \
-            (((dWb, Wb), (dbb, bb)) if gated else ()):
-        if g_ is None or g_.dtype != torch.float32 or g_.shape != w_.shape or not g_.is_contiguous():
-            raise _lib.MmfError("gradient buffers must be contiguous float32 tensors shaped like their parameters")
+    (W1, b1, Wa, ba, Wb, bb, Wc, bc, Wk, bk), g = _stack_step_operands(stack, Wk, bk, gated, grads, L, "bags")
+    H, D = W1.shape[0], Wa.shape[0]
     dev = x_cat.device
     Y = torch.as_tensor(Y).reshape(-1)
     c = torch.as_tensor(c).reshape(-1)
     if Y.numel() != G or c.numel() != G:
         raise _lib.MmfError(f"{G} bags need {G} labels and censorships, got {Y.numel()} / {c.numel()}")
-    if not Y.is_cuda and bool(((Y < 0) | (Y >= K)).any()):
-        raise IndexError(f"nll_surv: label out of range [0, {K})")
-    Y = Y.to(device=dev, dtype=torch.int64).contiguous()
-    c = c.to(device=dev, dtype=torch.float32).contiguous()
+    hd, tg, (hz, S, Y_hat, loss, risk), _keep = _nll_head(Wk, bk, Y, c, alpha, eps, loss_scale, grads[8], grads[9],
+                                                          accumulate, dev, G)
     seeds = [0] * G if seeds is None else [int(v) & 0xFFFFFFFF for v in seeds]
     if len(seeds) != G:
         raise _lib.MmfError(f"{G} bags need {G} dropout seeds")
@@ -407,15 +426,6 @@ def amil_nll_step_group(x_cat, sizes, stack, Wk, bk, gated, Y, c, alpha, grads, 
     nbytes = l.mmf_amil_group_workspace_bytes(offs, G, L, H, D, d.gated)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     A_raw = torch.empty((R,), dtype=torch.float32, device=dev)
-    logits, hz, S = torch.empty((G, K), device=dev), torch.empty((G, K), device=dev), torch.empty((G, K), device=dev)
-    loss, risk = torch.empty((G,), device=dev), torch.empty((G,), device=dev)
-    Y_hat = torch.empty((G, 1), dtype=torch.int64, device=dev)
-    hd = SurvHead(Wk=ptr(Wk), bk=ptr(bk), K=K, logits=ptr(logits), hazards=ptr(hz), S=ptr(S), Y_hat=ptr(Y_hat),
-                  risk=ptr(risk))
-    tg = NllTarget(Y=ptr(Y), c=ptr(c), alpha=float(alpha), eps=float(eps), loss_scale=float(loss_scale),
-                   loss=ptr(loss), dWk=ptr(dWk), dbk=ptr(dbk), accumulate=1 if accumulate else 0)
-    g = AmilGrads(dW1=ptr(dW1), db1=ptr(db1), dWa=ptr(dWa), dba=ptr(dba), dWb=ptr(dWb) if gated else None,
-                  dbb=ptr(dbb) if gated else None, dWc=ptr(dWc), dbc=ptr(dbc), dx=None)
     check(l.mmf_amil_nll_step_group(C.byref(d), C.byref(grp), ptr(x_cat), ptr(ws), nbytes, C.byref(hd), C.byref(tg),
                                     ptr(A_raw), C.byref(g), stream_ptr()), "mmf_amil_nll_step_group")
     A_list = [v.view(1, -1) for v in torch.split(A_raw, sizes)]
@@ -613,24 +623,13 @@ def surv_head_nll_step(feat, Wk, bk, Y, c, alpha, dWk, dbk, loss_scale=1.0, accu
     K = Wk.shape[0]
     if Wk.shape[1] != F or F > 1024 or K > 32:
         raise _lib.MmfError("surv_head_nll_step: classifier does not match the feature vector (F <= 1024, K <= 32)")
-    for g_, w_ in ((dWk, Wk), (dbk, bk)):
-        if g_ is None or g_.dtype != torch.float32 or g_.shape != w_.shape or not g_.is_contiguous():
-            raise _lib.MmfError("gradient buffers must be contiguous float32 tensors shaped like their parameters")
+    _check_grad_buffers(((dWk, Wk), (dbk, bk)))
     dev = feat.device
-    if not Y.is_cuda and bool(((Y < 0) | (Y >= K)).any()):
-        raise IndexError(f"nll_surv: label out of range [0, {K})")
-    Y = Y.reshape(1).to(device=dev, dtype=torch.int64)
-    c = c.reshape(1).to(device=dev, dtype=torch.float32)
-    out = torch.empty((3 * K + 2,), dtype=torch.float32, device=dev)       # logits, hazards, S, loss, risk
-    Y_hat = torch.empty((1, 1), dtype=torch.int64, device=dev)
+    hd, tg, (hz, S, Y_hat, loss, risk), _keep = _nll_head(Wk, bk, Y, c, alpha, eps, loss_scale, dWk, dbk, accumulate, dev)
     dfeat = torch.empty((1, F), dtype=torch.float32, device=dev)
-    hd = SurvHead(Wk=ptr(Wk), bk=ptr(bk), K=K, logits=ptr(out[0:K]), hazards=ptr(out[K:2 * K]), S=ptr(out[2 * K:3 * K]),
-                  Y_hat=ptr(Y_hat), risk=ptr(out[3 * K + 1:]))
-    tg = NllTarget(Y=ptr(Y), c=ptr(c), alpha=float(alpha), eps=float(eps), loss_scale=float(loss_scale),
-                   loss=ptr(out[3 * K:]), dWk=ptr(dWk), dbk=ptr(dbk), accumulate=1 if accumulate else 0)
     check(lib().mmf_surv_head_nll_step(ptr(feat), F, C.byref(hd), C.byref(tg), ptr(dfeat), stream_ptr()),
           "mmf_surv_head_nll_step")
-    return (out[K:2 * K].view(1, K), out[2 * K:3 * K].view(1, K), Y_hat, out[3 * K].view(()), out[3 * K + 1:].view(1), dfeat)
+    return hz, S, Y_hat, loss, risk, dfeat
 
 
 class HandCtx:
