@@ -209,6 +209,38 @@ int mmf_amil_nll_step_group(const mmf_amil_desc* desc, const mmf_bag_group* grou
                             size_t workspace_bytes, const mmf_surv_head* head, const mmf_nll_target* target,
                             float* A_raw /* [sum N] */, const mmf_amil_grads* grads, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Grouped training step of the radiology head: mmf_amil_nll_step_group behind the head's reduce_dim
+ *   (models/model_attention_mil_radio.py:80-82: cat(modalities, axis=1) -> Linear(nseg * kseg, L), no activation).  The
+ *   bags' modality segments are concatenated by rows, segment by segment; reduce_dim runs once over all rows into the
+ *   workspace, the stack chain of mmf_amil_nll_step_group follows on that, and reduce_dim's backward joins the chain:
+ *   its input gradient du . W1 over all rows, its weight gradient as one split-K TN launch of nseg problems (d
+ *   reduce_dim.bias folded into one of them), its sums in the stack's reduce launch.  What bag g gets -- outputs,
+ *   dropout masks, its share of every gradient -- is what MIL_Attention_fc_surv_radio.nll_step computes for it alone
+ *   with desc->seed = seeds[g].
+ *   desc: the stack (desc->L == kseg, the width of reduce_dim's output); desc->N = offsets[G].  grads->dx must be NULL
+ *   (the gradient of reduce_dim's output stays in the workspace).  rd->dW / rd->db follow target->accumulate, as the
+ *   stack's gradients do.
+ *   Returns as mmf_amil_nll_step_group, and MMF_ERR_SHAPE for nseg outside 2..4, kseg != desc->L or an
+ *   [offsets[G] x nseg * kseg] input of 2 GiB or more; MMF_ERR_ALIGN for a misaligned segment, reduce_dim weight or dW.
+ * mmf_radio_group_workspace_bytes: the workspace of that window (L = kseg), or 0 when the offset table or nseg is invalid.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct mmf_radio_reduce {
+  const float* const* x;     /* HOST [nseg] device pointers, each [sum N x kseg]: modality m of every bag, in bag order */
+  int32_t nseg, kseg;        /* 2..4 modalities of kseg features each */
+  const float* W;            /* reduce_dim.weight [kseg x nseg * kseg] */
+  const float* bias;         /* reduce_dim.bias [kseg] */
+  float* dW;                 /* [kseg x nseg * kseg] */
+  float* db;                 /* [kseg] */
+} mmf_radio_reduce;
+
+size_t mmf_radio_group_workspace_bytes(const int64_t* offsets, int32_t G, int32_t nseg, int32_t kseg, int32_t H,
+                                       int32_t D, int32_t gated);
+int mmf_radio_nll_step_group(const mmf_amil_desc* desc, const mmf_bag_group* group, const mmf_radio_reduce* rd,
+                             void* workspace, size_t workspace_bytes, const mmf_surv_head* head,
+                             const mmf_nll_target* target, float* A_raw /* [sum N] */, const mmf_amil_grads* grads,
+                             void* stream);
+
 /* The hazard head's training step on a feature vector that is already on the device: what
  *   `hazards, S, Y_hat = head(classifier(feat)); loss = NLLSurvLoss(alpha)(hazards, S, Y, c); (loss * loss_scale).backward()`
  * computes between the embedding and the loss (models/model_mm_attention_mil.py:190-191 with fusion = 'concat': feat is the

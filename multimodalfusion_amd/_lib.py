@@ -56,6 +56,12 @@ class BagGroup(C.Structure):
     _fields_ = [("G", C.c_int32), ("offsets", C.POINTER(C.c_int64)), ("seeds", C.POINTER(C.c_uint32))]
 
 
+class RadioReduce(C.Structure):
+    """mmf_radio_reduce: the radiology head's reduce_dim in a grouped step (x: host array of nseg device pointers)."""
+    _fields_ = [("x", C.POINTER(C.c_void_p)), ("nseg", C.c_int32), ("kseg", C.c_int32), ("W", c_f32p),
+                ("bias", c_f32p), ("dW", c_f32p), ("db", c_f32p)]
+
+
 class MaxnetDesc(C.Structure):
     """struct mmf_maxnet_desc (include/mmf_amil.h)."""
     _fields_ = [("B", C.c_int32), ("G", C.c_int32), ("H0", C.c_int32), ("H1", C.c_int32),
@@ -102,6 +108,11 @@ SYMBOLS = {
     "mmf_amil_nll_step_group": (C.c_int, [C.POINTER(AmilDesc), C.POINTER(BagGroup), C.c_void_p, C.c_void_p, C.c_size_t,
                                           C.POINTER(SurvHead), C.POINTER(NllTarget), C.c_void_p, C.POINTER(AmilGrads),
                                           C.c_void_p]),
+    "mmf_radio_group_workspace_bytes": (C.c_size_t, [C.POINTER(C.c_int64), C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                                      C.c_int32, C.c_int32]),
+    "mmf_radio_nll_step_group": (C.c_int, [C.POINTER(AmilDesc), C.POINTER(BagGroup), C.POINTER(RadioReduce), C.c_void_p,
+                                           C.c_size_t, C.POINTER(SurvHead), C.POINTER(NllTarget), C.c_void_p,
+                                           C.POINTER(AmilGrads), C.c_void_p]),
     "mmf_surv_head_nll_step": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(SurvHead), C.POINTER(NllTarget), C.c_void_p,
                                          C.c_void_p]),
     "mmf_amil_infer_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),

@@ -698,23 +698,28 @@ static GroupWs carve_group(void* base, const SegTable& s, int L, int H, int D, i
 }
 }  // namespace mmf
 
-size_t mmf_amil_group_workspace_bytes(const int64_t* offsets, int32_t G, int32_t L, int32_t H, int32_t D, int32_t gated) {
-  SegTable s;
-  if (group_plan(offsets, G, s)) return 0;
-  return carve_group(nullptr, s, L, H, D, gated).bytes;
-}
+namespace mmf {
+// reduce_dim's backward on the grouped chain's launches (mmf_radio_nll_step_group): its input gradient du . W1 over every
+// row, its weight-gradient problems in a TN launch of their own after the stack's (or, tuning, in the stack's launch,
+// ahead of the stack's two: they are the long ones), its sums in the stack's reduce launch
+struct GroupExtra {
+  float* dx;                    // [R x L] <- du . W1
+  TnProblem prob[4]; int nprob;
+  int separate;                 // 1: the problems as a TN launch of their own; 0 (tuning): in the stack's launch
+  int splits, k_per_split;
+  ReduceSeg seg[2]; int nseg;
+};
 
-int mmf_amil_nll_step_group(const mmf_amil_desc* d, const mmf_bag_group* group, const float* x, void* workspace,
-                            size_t workspace_bytes, const mmf_surv_head* head, const mmf_nll_target* target,
-                            float* A_raw, const mmf_amil_grads* g, void* stream) {
+// the call contract both grouped entry points share; fills the segment table (with each bag's mask index base) and the tail
+static int group_check(const mmf_amil_desc* d, const mmf_bag_group* group, const void* x, const void* workspace,
+                       const mmf_surv_head* head, const mmf_nll_target* target, const float* A_raw,
+                       const mmf_amil_grads* g, SegTable& s, HeadTail& tl) {
   if (!d || !group || !target || !g) return MMF_ERR_ARG;
   if (d->gemm != MMF_GEMM_F32 || g->dx) return MMF_ERR_ARG;
   if (!group->seeds) return MMF_ERR_ARG;
-  SegTable s;
   if (int e = group_plan(group->offsets, group->G, s)) return e;
   if (d->N != s.off[s.G]) return MMF_ERR_SHAPE;
   if (int e = check_desc(d)) return e;
-  HeadTail tl;
   if (int e = head_tail_of(head, target, d->H, tl)) return e;
   if (!x || !workspace || !A_raw) return MMF_ERR_ARG;
   if (!g->dW1 || !g->db1 || !g->dWa || !g->dba || !g->dWc || !g->dbc) return MMF_ERR_ARG;
@@ -722,16 +727,19 @@ int mmf_amil_nll_step_group(const mmf_amil_desc* d, const mmf_bag_group* group, 
   if (!aligned16(x) || !aligned16(workspace) || !aligned16(d->W1) || !aligned16(d->Wa) || (d->gated && !aligned16(d->Wb)) ||
       !aligned16(g->dW1) || !aligned16(g->dWa) || (d->gated && !aligned16(g->dWb)))
     return MMF_ERR_ALIGN;
-  GroupWs gw = carve_group(workspace, s, d->L, d->H, d->D, d->gated);
-  if (gw.bytes > workspace_bytes) return MMF_ERR_WORKSPACE;
-  const AmilWs& w = gw.w;
   const uint32_t inv = hash_mul_inverse();
   for (int b = 0; b < s.G; ++b) s.ibase[b] = group->seeds[b] * inv;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  TraceScope ts(d->trace);
+  return MMF_OK;
+}
+
+// the stack's chain over the window's rows x [sum N x L]: per-row tables, projection, gate, pooling + head tail per bag,
+// K-prep, K-dh, (du . W1), split-K TN, reduce
+static int group_chain(const mmf_amil_desc* d, const SegTable& s, const float* x, const GroupWs& gw, const HeadTail& tl,
+                       int K, const mmf_nll_target* target, float* A_raw, const mmf_amil_grads* g,
+                       const GroupExtra* ex, hipStream_t st) {
+  const AmilWs& w = gw.w;
   const uint32_t* const seed_dev = d->seed_dev;
   const int64_t R = d->N;
-  const int K = head->K;
 
   GroupRowsParams rp0{};
   rp0.s = s; rp0.H = d->H; rp0.D = d->D; rp0.ridx_h = gw.ridx_h; rp0.ridx_d = gw.ridx_d; rp0.bag = gw.bag;
@@ -780,21 +788,36 @@ int mmf_amil_nll_step_group(const mmf_amil_desc* d, const mmf_bag_group* group, 
   dp.seg_ridx = gw.ridx_d; dp.seg_bag = gw.bag;
   if (int e = launch_bwd_dh_seg(dp, st)) return e;
 
+  if (ex && ex->dx) {   // d(x) = du . W1: du carries every bag's ReLU and dropout masks
+    NnParams np{};
+    np.A = w.du; np.lda = d->H; np.B = d->W1; np.ldb = d->L; np.C = ex->dx; np.ldc = d->L;
+    np.M = R; np.N = d->L; np.K = d->H;
+    if (int e = launch_nn(np, st)) return e;
+  }
+
   TnParams tp{};
-  tp.nprob = 2; tp.K = R; tp.splits = w.splits; tp.k_per_split = w.k_per_split; tp.g = gc; tp.tile = w.tile;
+  const int nx = ex && !ex->separate ? ex->nprob : 0;
+  for (int i = 0; i < nx; ++i) tp.prob[i] = ex->prob[i];
+  tp.nprob = nx + 2; tp.K = R; tp.splits = w.splits; tp.k_per_split = w.k_per_split; tp.g = gc; tp.tile = w.tile;
   tp.seg_ridx = gw.ridx_d;
-  TnProblem& q1 = tp.prob[0];   // dW1[H x L] = du^T . x over every row of the window ; db1 = colsum(du)
+  TnProblem& q1 = tp.prob[nx];       // dW1[H x L] = du^T . x over every row of the window ; db1 = colsum(du)
   q1.kind = TN_A_PLAIN; q1.A = w.du; q1.lda = d->H; q1.M = d->H;
   q1.B = x; q1.ldb = d->L; q1.Ncols = d->L;
   q1.out = w.slab_w1; q1.split_stride = (size_t)d->H * d->L; q1.ldc = d->L;
   q1.colsum = w.cs_b1; q1.colsum_stride = d->H; q1.colsum2 = nullptr; q1.colsum2_stride = 0;
-  TnProblem& q2 = tp.prob[1];   // dWab = dP^T . h ; (dba|dbb) = colsum(dP) ; dWc = colsum(ds.a_d.b_d)
+  TnProblem& q2 = tp.prob[nx + 1];   // dWab = dP^T . h ; (dba|dbb) = colsum(dP) ; dWc = colsum(ds.a_d.b_d)
   q2.kind = TN_A_GATE; q2.A = nullptr; q2.lda = 0; q2.M = w.mstk;
   q2.B = w.h; q2.ldb = d->H; q2.Ncols = d->H;
   q2.out = w.slab_wab; q2.split_stride = (size_t)w.mstk * d->H; q2.ldc = d->H;
   q2.colsum = w.cs_bab; q2.colsum_stride = w.mstk; q2.colsum2 = w.cs_wc; q2.colsum2_stride = d->D;
   q2.splits = w.splits_g; q2.k_per_split = w.k_per_split_g;
   if (int e = launch_tn(tp, st)) return e;
+  if (ex && ex->separate) {
+    TnParams tr{};
+    for (int i = 0; i < ex->nprob; ++i) tr.prob[i] = ex->prob[i];
+    tr.nprob = ex->nprob; tr.K = R; tr.splits = ex->splits; tr.k_per_split = ex->k_per_split; tr.tile = w.tile;
+    if (int e = launch_tn(tr, st)) return e;
+  }
 
   ReduceParams rp{};
   int n = 0;
@@ -811,9 +834,136 @@ int mmf_amil_nll_step_group(const mmf_amil_desc* d, const mmf_bag_group* group, 
   seg(w.dbc_part, g->dbc, 1, bp.n_groups, 1);
   seg(gw.wk, target->dWk, K * d->H, s.G, (size_t)K * d->H);      // classifier: the bags' slabs in bag order
   seg(gw.bk, target->dbk, K, s.G, (size_t)K);
+  if (ex) {
+    constexpr int cap = (int)(sizeof(rp.seg) / sizeof(rp.seg[0]));   // gated: 10 + dW_r, db_r = every slot
+    if (n + ex->nseg > cap) return MMF_ERR_SHAPE;
+    for (int i = 0; i < ex->nseg; ++i) seg(ex->seg[i].in, ex->seg[i].out, ex->seg[i].len, ex->seg[i].nsplit, ex->seg[i].stride);
+  }
   rp.nseg = n;
   rp.accumulate = target->accumulate ? 1 : 0;
   return launch_reduce(rp, st);
+}
+
+// the radio window's workspace: the stack's (carve_group, L = kseg) and reduce_dim's output, its gradient, the split-K
+// slabs of dW_r / db_r and the partial tiles of a K-split reduce_dim forward
+struct RadioWs {
+  GroupWs gw;
+  float *xr, *dxr, *slab, *cs, *kpart;
+  int splits, k_per_split, separate;
+  size_t bytes;
+};
+static RadioWs carve_radio(void* base, const SegTable& s, int nseg, int kseg, int H, int D, int gated) {
+  RadioWs r{};
+  const int64_t R = s.off[s.G];
+  const int L = kseg;
+  r.gw = carve_group(base, s, L, H, D, gated);
+  char* p = static_cast<char*>(base);
+  size_t off = r.gw.bytes;
+  auto take = [&](size_t nfloat) {
+    float* q = reinterpret_cast<float*>(p + off);
+    off += align_up(nfloat * sizeof(float), 256);
+    return q;
+  };
+  // dW_r as a TN launch of its own after the stack's, planned over its own tiles (mmf_linear_backward's plan), or as
+  // more problems of the stack's launch, planned with the stack's tiles (fewer splits).  Measured: the
+  // separate launch is faster, 1.295 vs 1.366 ms at 16 x 512 rows.  The slabs are sized by the separate plan, which has
+  // at least as many splits.
+  const int td = r.gw.w.tile, mstk = gated ? 2 * D : D;
+  auto cdiv = [](int a, int b) { return (a + b - 1) / b; };
+  const int t_stack = cdiv(H, td) * cdiv(L, td) + cdiv(mstk, td) * cdiv(H, td);
+  const int t_rd = nseg * cdiv(L, td) * cdiv(kseg, td);
+  const int most = tn_splits(R, t_rd, td);
+  static const int env = tune_int("MMF_RADIO_TN_SEPARATE", 1);   // tuning override: 0 = in the stack's TN launch
+  r.separate = env ? 1 : 0;
+  r.splits = r.separate ? most : tn_splits(R, t_stack + t_rd, td);
+  const int64_t kps = (R + r.splits - 1) / r.splits;
+  r.k_per_split = (int)((kps + 3) / 4 * 4);
+  if (r.k_per_split < 4) r.k_per_split = 4;
+  r.xr = take((size_t)R * L);
+  r.dxr = take((size_t)R * L);
+  r.slab = take((size_t)most * L * nseg * kseg);
+  r.cs = take((size_t)most * L);
+  const size_t kf = linear_ksplit_floats(R, L, nseg * kseg, nseg, kseg);
+  r.kpart = kf ? take(kf) : nullptr;
+  r.bytes = off;
+  return r;
+}
+}  // namespace mmf
+
+size_t mmf_amil_group_workspace_bytes(const int64_t* offsets, int32_t G, int32_t L, int32_t H, int32_t D, int32_t gated) {
+  SegTable s;
+  if (group_plan(offsets, G, s)) return 0;
+  return carve_group(nullptr, s, L, H, D, gated).bytes;
+}
+
+int mmf_amil_nll_step_group(const mmf_amil_desc* d, const mmf_bag_group* group, const float* x, void* workspace,
+                            size_t workspace_bytes, const mmf_surv_head* head, const mmf_nll_target* target,
+                            float* A_raw, const mmf_amil_grads* g, void* stream) {
+  SegTable s;
+  HeadTail tl;
+  if (int e = group_check(d, group, x, workspace, head, target, A_raw, g, s, tl)) return e;
+  GroupWs gw = carve_group(workspace, s, d->L, d->H, d->D, d->gated);
+  if (gw.bytes > workspace_bytes) return MMF_ERR_WORKSPACE;
+  TraceScope ts(d->trace);
+  return group_chain(d, s, x, gw, tl, head->K, target, A_raw, g, nullptr, static_cast<hipStream_t>(stream));
+}
+
+size_t mmf_radio_group_workspace_bytes(const int64_t* offsets, int32_t G, int32_t nseg, int32_t kseg, int32_t H,
+                                       int32_t D, int32_t gated) {
+  SegTable s;
+  if (group_plan(offsets, G, s) || nseg < 2 || nseg > 4 || kseg < 1) return 0;
+  return carve_radio(nullptr, s, nseg, kseg, H, D, gated).bytes;
+}
+
+int mmf_radio_nll_step_group(const mmf_amil_desc* d, const mmf_bag_group* group, const mmf_radio_reduce* rd,
+                             void* workspace, size_t workspace_bytes, const mmf_surv_head* head,
+                             const mmf_nll_target* target, float* A_raw, const mmf_amil_grads* g, void* stream) {
+  if (!rd || !rd->x) return MMF_ERR_ARG;
+  if (rd->nseg < 2 || rd->nseg > 4) return MMF_ERR_SHAPE;
+  SegTable s;
+  HeadTail tl;
+  if (int e = group_check(d, group, rd->x[0], workspace, head, target, A_raw, g, s, tl)) return e;
+  const int nseg = rd->nseg, kseg = rd->kseg, L = d->L;
+  if (kseg != L) return MMF_ERR_SHAPE;
+  const int64_t R = d->N;
+  if (R * nseg * (int64_t)kseg * 4 >= (int64_t)1 << 31) return MMF_ERR_SHAPE;     // the [sum N x nseg*kseg] input < 2 GiB
+  if (!rd->W || !rd->bias || !rd->dW || !rd->db) return MMF_ERR_ARG;
+  for (int m = 0; m < nseg; ++m)
+    if (!rd->x[m]) return MMF_ERR_ARG;
+  for (int m = 0; m < nseg; ++m)
+    if (!aligned16(rd->x[m])) return MMF_ERR_ALIGN;
+  if (!aligned16(rd->W) || !aligned16(rd->dW)) return MMF_ERR_ALIGN;
+  RadioWs r = carve_radio(workspace, s, nseg, kseg, d->H, d->D, d->gated);
+  if (r.bytes > workspace_bytes) return MMF_ERR_WORKSPACE;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  TraceScope ts(d->trace);
+
+  // reduce_dim over the modality segments, every row of the window: mmf_linear_forward's plan (a short window takes its
+  // K split over the segments, under desc->sync)
+  LinearParams lr{};
+  for (int m = 0; m < nseg; ++m) lr.x[m] = rd->x[m];
+  lr.nseg = nseg; lr.kseg = kseg; lr.ldx = kseg;
+  lr.w = rd->W; lr.bias = rd->bias; lr.y = r.xr; lr.M = R; lr.N = L; lr.K = nseg * kseg;
+  lr.act = ACT_NONE; lr.drop_p = 0.f; lr.drop_key = drop_key(0, 0); lr.seed_dev = d->seed_dev;
+  if (r.kpart && d->sync && d->sync_words > 0) { lr.kpart = r.kpart; lr.ktick = d->sync; lr.ktick_words = d->sync_words; }
+  if (int e = launch_linear(lr, st)) return e;
+
+  GroupExtra ex{};
+  ex.dx = r.dxr;
+  ex.separate = r.separate; ex.splits = r.splits; ex.k_per_split = r.k_per_split;
+  ex.nprob = nseg;
+  for (int m = 0; m < nseg; ++m) {   // dW_r[:, m kseg : (m + 1) kseg] = dxr^T . x_m ; db_r = colsum(dxr) with the first
+    TnProblem& q = ex.prob[m];
+    q.kind = TN_A_PLAIN; q.A = r.dxr; q.lda = L; q.M = L;
+    q.B = rd->x[m]; q.ldb = kseg; q.Ncols = kseg;
+    q.out = r.slab + (size_t)m * kseg; q.split_stride = (size_t)L * nseg * kseg; q.ldc = nseg * kseg;
+    q.colsum = m == 0 ? r.cs : nullptr; q.colsum_stride = L;
+    q.splits = r.splits; q.k_per_split = r.k_per_split;
+  }
+  ex.seg[0] = ReduceSeg{r.slab, rd->dW, L * nseg * kseg, r.splits, (size_t)L * nseg * kseg, 0, 0};
+  ex.seg[1] = ReduceSeg{r.cs, rd->db, L, r.splits, (size_t)L, 0, 0};
+  ex.nseg = 2;
+  return group_chain(d, s, r.xr, r.gw, tl, head->K, target, A_raw, g, &ex, st);
 }
 
 int mmf_surv_head_nll_step(const float* feat, int32_t F, const mmf_surv_head* head, const mmf_nll_target* target,

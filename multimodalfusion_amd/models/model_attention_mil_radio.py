@@ -7,8 +7,8 @@ import torch.nn as nn
 
 from .. import ops
 from ..utils.utils import initialize_weights
-from .model_modules import (AMIL_SIZES, amil_stack, amil_stack_head, amil_stack_nll_step, hand_over_grads,
-                            make_amil_stack)
+from .model_modules import (AMIL_SIZES, amil_stack, amil_stack_head, amil_stack_nll_step, amil_stack_nll_step_group,
+                            hand_over_grads, make_amil_stack, stack_args, step_grad_buffers)
 
 
 class MIL_Attention_fc_radio(nn.Module):
@@ -78,6 +78,45 @@ class MIL_Attention_fc_surv_radio(MIL_Attention_fc_radio):
                 dW, db = LinearCatFn.backward(ctx, dx)[:2]
                 hand_over_grads((W, b), {W: dW, b: db}, rd_out, accumulate)
         return out
+
+    def nll_step_group(self, bags, labels, censors, alpha=0.0, loss_scale=1.0, grad_out=None, accumulate=None, seeds=None):
+        """nll_step for the G bags of one accumulation window in ONE C-ABI call (ops.radio_nll_step_group): reduce_dim and
+        the stack's GEMMs run once over all of their rows.  bags: a list of G {modality: [n_g x 1024]} dicts, or a
+        pre-stacked pair (x [n_mod x sum N x 1024] tensor, sizes) with the modalities in self.modalities order;
+        labels / censors: G values.  Gradients of sum_g loss_g * loss_scale, same .grad / grad_out conventions as
+        nll_step; in train mode bag g draws the dropout seed the g-th of G nll_step calls would (or `seeds[g]` when
+        given).  One modality (no reduce_dim): the pathology head's grouped step on it.
+        Returns (hazards [G x K], S [G x K], Y_hat [G x 1], [A_raw [1 x N_g]], loss [G], risk [G]), detached."""
+        from .. import ops
+        if any(not p.requires_grad for p in self.parameters()):
+            raise RuntimeError("nll_step_group needs every parameter of the head to require grad")
+        nmod = len(self.modalities)
+        if (isinstance(bags, (tuple, list)) and len(bags) == 2 and torch.is_tensor(bags[0])
+                and isinstance(bags[1], (list, tuple)) and all(isinstance(n, int) for n in bags[1])):
+            x, sizes = bags
+            if x.dim() != 3 or x.shape[0] != nmod:
+                raise ops._lib.MmfError(f"pre-stacked bags must be [{nmod} x sum N x k], got {tuple(x.shape)}")
+            xs = list(x.unbind(0))
+        else:
+            if not all(isinstance(b, dict) for b in bags):
+                raise TypeError("bags: a list of {modality: [n x k]} dicts or an (x [n_mod x sum N x k], sizes) pair")
+            for b in bags:
+                if len({tuple(b[m].shape) for m in self.modalities}) != 1:
+                    raise ops._lib.MmfError("the modalities of a bag must have the same [n x k] shape")
+            sizes = [int(b[self.modalities[0]].shape[0]) for b in bags]
+            xs = [torch.cat([b[m] for b in bags], 0) if len(bags) > 1 else bags[0][m] for m in self.modalities]
+        if nmod == 1:
+            return amil_stack_nll_step_group(self.attention_net_radio, self.classifier, (xs[0], list(sizes)), self.training,
+                                             labels, censors, alpha, loss_scale, grad_out, accumulate, seeds)
+        gated, stack, p_h, p_att = stack_args(self.attention_net_radio, self.training)
+        Wr, br, Wk, bk = self.reduce_dim.weight, self.reduce_dim.bias, self.classifier.weight, self.classifier.bias
+        grads, accumulate = step_grad_buffers([Wr, br, *stack, Wk, bk], xs[0].device, grad_out, accumulate)
+        if seeds is None:
+            seeds = [ops.next_dropout_seed() for _ in sizes] if self.training else None
+        with torch.no_grad():
+            return ops.radio_nll_step_group(xs, sizes, Wr, br, stack, Wk, bk, gated, labels, censors, alpha, grads,
+                                            loss_scale=loss_scale, accumulate=accumulate, p_h=p_h, p_att=p_att,
+                                            seeds=seeds)
 
     def forward(self, **kwargs):
         bags = [kwargs[m] for m in self.modalities]

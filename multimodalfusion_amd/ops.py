@@ -384,6 +384,40 @@ def group_row_limit(L, H, D):
     return min(((1 << 32) - 1) // max(H, D), ((1 << 31) - 1) // (4 * max(L, 2 * D)), 256 * 8192)
 
 
+def radio_group_row_limit(nseg, L, H, D):
+    """Most rows one grouped radio call takes: group_row_limit of the stack, and the [sum N x nseg * L] input of
+    reduce_dim < 2 GiB (131,071 rows at four 1024-wide modalities)."""
+    return min(group_row_limit(L, H, D), ((1 << 31) - 1) // (4 * nseg * L))
+
+
+def _group_table(sizes, rows, Y, c, seeds):
+    """The bag table of a grouped call: sizes checked against the rows given, G labels / censorships / seeds.
+    Returns (sizes, Y, c, offsets (host int64 [G + 1]), BagGroup); the BagGroup points into the offsets and seeds arrays,
+    which it keeps alive as attributes."""
+    sizes = [int(n) for n in sizes]
+    G = len(sizes)
+    if G < 1 or G > GROUP_MAX:
+        raise _lib.MmfError(f"a group holds 1 .. {GROUP_MAX} bags, got {G}")
+    if min(sizes) < 1:
+        raise _lib.MmfError("empty bag in the group")
+    if rows is not None and rows != sum(sizes):
+        raise _lib.MmfError(f"the bags hold {rows} rows, their sizes add up to {sum(sizes)}")
+    Y = torch.as_tensor(Y).reshape(-1)
+    c = torch.as_tensor(c).reshape(-1)
+    if Y.numel() != G or c.numel() != G:
+        raise _lib.MmfError(f"{G} bags need {G} labels and censorships, got {Y.numel()} / {c.numel()}")
+    seeds = [0] * G if seeds is None else [int(v) & 0xFFFFFFFF for v in seeds]
+    if len(seeds) != G:
+        raise _lib.MmfError(f"{G} bags need {G} dropout seeds")
+    offs = (C.c_int64 * (G + 1))()
+    for i, n in enumerate(sizes):
+        offs[i + 1] = offs[i] + n
+    sd = (C.c_uint32 * G)(*seeds)
+    grp = _lib.BagGroup(G=G, offsets=offs, seeds=sd)
+    grp._keep = (offs, sd)
+    return sizes, Y, c, offs, grp
+
+
 def amil_nll_step_group(x_cat, sizes, stack, Wk, bk, gated, Y, c, alpha, grads, loss_scale=1.0, accumulate=False, p_h=0.0,
                         p_att=0.0, seeds=None, eps=1e-7):
     """The G bags of one accumulation window in ONE C-ABI call (include/mmf_amil.h: mmf_amil_nll_step_group): the stack's
@@ -395,32 +429,16 @@ def amil_nll_step_group(x_cat, sizes, stack, Wk, bk, gated, Y, c, alpha, grads, 
     if x_cat.dtype != torch.float32:
         raise _lib.MmfError("the grouped step takes fp32 bags only (bf16 bags: one amil_nll_step per bag)")
     x_cat = _f32c(x_cat)
-    sizes = [int(n) for n in sizes]
+    sizes, Y, c, offs, grp = _group_table(sizes, None, Y, c, seeds)
     G = len(sizes)
-    if G < 1 or G > GROUP_MAX:
-        raise _lib.MmfError(f"a group holds 1 .. {GROUP_MAX} bags, got {G}")
-    if min(sizes) < 1:
-        raise _lib.MmfError("empty bag in the group")
     if x_cat.dim() != 2 or x_cat.shape[0] != sum(sizes):
         raise _lib.MmfError(f"x_cat must be [sum N x L] = [{sum(sizes)} x L], got {tuple(x_cat.shape)}")
     R, L = x_cat.shape
     (W1, b1, Wa, ba, Wb, bb, Wc, bc, Wk, bk), g = _stack_step_operands(stack, Wk, bk, gated, grads, L, "bags")
     H, D = W1.shape[0], Wa.shape[0]
     dev = x_cat.device
-    Y = torch.as_tensor(Y).reshape(-1)
-    c = torch.as_tensor(c).reshape(-1)
-    if Y.numel() != G or c.numel() != G:
-        raise _lib.MmfError(f"{G} bags need {G} labels and censorships, got {Y.numel()} / {c.numel()}")
     hd, tg, (hz, S, Y_hat, loss, risk), _keep = _nll_head(Wk, bk, Y, c, alpha, eps, loss_scale, grads[8], grads[9],
                                                           accumulate, dev, G)
-    seeds = [0] * G if seeds is None else [int(v) & 0xFFFFFFFF for v in seeds]
-    if len(seeds) != G:
-        raise _lib.MmfError(f"{G} bags need {G} dropout seeds")
-    offs = (C.c_int64 * (G + 1))()
-    for i, n in enumerate(sizes):
-        offs[i + 1] = offs[i] + n
-    sd = (C.c_uint32 * G)(*seeds)
-    grp = _lib.BagGroup(G=G, offsets=offs, seeds=sd)
     d = _amil_desc(R, L, H, D, gated, W1, b1, Wa, ba, Wb, bb, Wc, bc, p_h, p_att, 0, _seed_word)
     l = lib()
     nbytes = l.mmf_amil_group_workspace_bytes(offs, G, L, H, D, d.gated)
@@ -428,6 +446,50 @@ def amil_nll_step_group(x_cat, sizes, stack, Wk, bk, gated, Y, c, alpha, grads, 
     A_raw = torch.empty((R,), dtype=torch.float32, device=dev)
     check(l.mmf_amil_nll_step_group(C.byref(d), C.byref(grp), ptr(x_cat), ptr(ws), nbytes, C.byref(hd), C.byref(tg),
                                     ptr(A_raw), C.byref(g), stream_ptr()), "mmf_amil_nll_step_group")
+    A_list = [v.view(1, -1) for v in torch.split(A_raw, sizes)]
+    return hz, S, Y_hat, A_list, loss, risk
+
+
+def radio_nll_step_group(xs, sizes, Wr, br, stack, Wk, bk, gated, Y, c, alpha, grads, loss_scale=1.0, accumulate=False,
+                         p_h=0.0, p_att=0.0, seeds=None, eps=1e-7):
+    """The radiology head's G bags of one accumulation window in ONE C-ABI call (include/mmf_amil.h:
+    mmf_radio_nll_step_group): reduce_dim over the modality segments and the stack's GEMMs run once over all rows,
+    pooling / head / loss per bag, reduce_dim's backward on the stack's TN and reduce launches.
+    xs: 2 .. 4 modality tensors, each [sum N x k] fp32 (the bags' rows in order); sizes: the G bag sizes; Wr, br:
+    reduce_dim's weight [L x nseg k] and bias [L]; grads = (dWr, dbr, dW1, ..., dbk), those of sum_g loss_g * loss_scale,
+    added to when `accumulate`.  Other arguments as amil_nll_step_group.
+    Returns (hazards [G x K], S [G x K], Y_hat [G x 1], [A_raw [1 x N_g]], loss [G] (unscaled), risk [G])."""
+    xs = list(xs)
+    nseg = len(xs)
+    if nseg < 2 or nseg > 4:
+        raise _lib.MmfError(f"the grouped radio step takes 2 .. 4 modalities, got {nseg}")
+    if any(x.dtype != torch.float32 for x in xs):
+        raise _lib.MmfError("the grouped step takes fp32 bags only")
+    xs = [_f32c(x) for x in xs]
+    if any(x.dim() != 2 or tuple(x.shape) != tuple(xs[0].shape) for x in xs):
+        raise _lib.MmfError("every modality must be one [sum N x k] tensor of the same shape")
+    R, kseg = xs[0].shape
+    sizes, Y, c, offs, grp = _group_table(sizes, R, Y, c, seeds)
+    G = len(sizes)
+    Wr, br = _f32c(Wr), _f32c(br)
+    (W1, b1, Wa, ba, Wb, bb, Wc, bc, Wk, bk), g = _stack_step_operands(stack, Wk, bk, gated, grads[2:], kseg, "bags")
+    H, D = W1.shape[0], Wa.shape[0]
+    if tuple(Wr.shape) != (kseg, nseg * kseg) or tuple(br.shape) != (kseg,):
+        raise _lib.MmfError(f"reduce_dim must be [{kseg} x {nseg * kseg}] with a [{kseg}] bias for {nseg} modalities of {kseg}")
+    dWr, dbr = grads[:2]
+    _check_grad_buffers(((dWr, Wr), (dbr, br)))
+    dev = xs[0].device
+    hd, tg, (hz, S, Y_hat, loss, risk), _keep = _nll_head(Wk, bk, Y, c, alpha, eps, loss_scale, grads[10], grads[11],
+                                                          accumulate, dev, G)
+    d = _amil_desc(R, kseg, H, D, gated, W1, b1, Wa, ba, Wb, bb, Wc, bc, p_h, p_att, 0, _seed_word)
+    segs = (C.c_void_p * nseg)(*[ptr(x) for x in xs])
+    rd = _lib.RadioReduce(x=segs, nseg=nseg, kseg=kseg, W=ptr(Wr), bias=ptr(br), dW=ptr(dWr), db=ptr(dbr))
+    l = lib()
+    nbytes = l.mmf_radio_group_workspace_bytes(offs, G, nseg, kseg, H, D, d.gated)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    A_raw = torch.empty((R,), dtype=torch.float32, device=dev)
+    check(l.mmf_radio_nll_step_group(C.byref(d), C.byref(grp), C.byref(rd), ptr(ws), nbytes, C.byref(hd), C.byref(tg),
+                                     ptr(A_raw), C.byref(g), stream_ptr()), "mmf_radio_nll_step_group")
     A_list = [v.view(1, -1) for v in torch.split(A_raw, sizes)]
     return hz, S, Y_hat, A_list, loss, risk
 

@@ -165,10 +165,11 @@ class _Window:
 
 class _BagGroup:
     """train_loop_survival(group=True): the eligible bags of the current window, held on the device until one grouped
-    call (model.nll_step_group) runs them.  Each bag is copied straight into its rows of one reusable device buffer (no
-    concatenation pass); its dropout seed is drawn when it arrives, so bag g of the loader gets the masks the per-bag
-    route gives it.  A bag that would take the group past ops.GROUP_MAX bags or the row limit flushes what is held first
-    (the window then runs as several grouped calls, accumulating)."""
+    call (model.nll_step_group) runs them.  Each bag is copied straight into its rows of one reusable device buffer
+    [n_mod x rows x L] (no concatenation pass): the pathology head's bag is one [n x L] tensor, the radiology head's one
+    per modality.  Its dropout seed is drawn when it arrives, so bag g of the loader gets the masks the per-bag route
+    gives it.  A bag that would take the group past ops.GROUP_MAX bags or the row limit flushes what is held first (the
+    window then runs as several grouped calls, accumulating)."""
 
     def __init__(self):
         self.buf = None
@@ -177,21 +178,30 @@ class _BagGroup:
     def reset(self):
         self.rows, self.sizes, self.labels, self.cs, self.seeds, self.slots = 0, [], [], [], [], []
 
-    def add(self, model, x, label, c, seed, slot, device, flush):
+    @staticmethod
+    def _row_limit(model, nmod, L):
         from .. import ops
-        n, L = int(x.shape[0]), int(x.shape[1])
-        lin, att = model.attention_net_WSI[0], model.attention_net_WSI[3]
-        limit = ops.group_row_limit(L, lin.out_features, att.stack_params()[0].shape[0])
+        seq = model.attention_net_radio if hasattr(model, "attention_net_radio") else model.attention_net_WSI
+        H, D = seq[0].out_features, seq[3].stack_params()[0].shape[0]
+        return ops.radio_group_row_limit(nmod, L, H, D) if nmod > 1 else ops.group_row_limit(L, H, D)
+
+    def add(self, model, xs, label, c, seed, slot, device, flush):
+        """xs: the bag's [n x L] tensors, one per modality (the pathology head: one)."""
+        from .. import ops
+        nmod, n, L = len(xs), int(xs[0].shape[0]), int(xs[0].shape[1])
+        limit = self._row_limit(model, nmod, L)
         if self.sizes and (len(self.sizes) >= ops.GROUP_MAX or self.rows + n > limit):
             flush()
         need = self.rows + n
-        if self.buf is None or self.buf.shape[1] != L or self.buf.shape[0] < need or self.buf.device != device:
-            grown = torch.empty((max(need, 2 * self.buf.shape[0] if self.buf is not None else need), L),
+        if (self.buf is None or self.buf.shape[0] != nmod or self.buf.shape[2] != L or self.buf.shape[1] < need
+                or self.buf.device != device):
+            grown = torch.empty((nmod, max(need, 2 * self.buf.shape[1] if self.buf is not None else need), L),
                                 dtype=torch.float32, device=device)
             if self.rows:
-                grown[:self.rows].copy_(self.buf[:self.rows])
+                grown[:, :self.rows].copy_(self.buf[:, :self.rows])
             self.buf = grown
-        self.buf[self.rows:need].copy_(x, non_blocking=True)
+        for m, x in enumerate(xs):
+            self.buf[m, self.rows:need].copy_(x, non_blocking=True)
         self.rows = need
         self.sizes.append(n); self.labels.append(label.reshape(1)); self.cs.append(c.reshape(1))
         self.seeds.append(seed); self.slots.append(slot)
@@ -201,9 +211,9 @@ class _BagGroup:
         if not self.sizes:
             return []
         seeds = self.seeds if model.training else None
-        _, _, _, _, loss, risk = model.nll_step_group((self.buf[:self.rows], list(self.sizes)), torch.cat(self.labels),
-                                                      torch.cat(self.cs), alpha=alpha, loss_scale=loss_scale,
-                                                      seeds=seeds)
+        x = self.buf[:, :self.rows] if hasattr(model, "attention_net_radio") else self.buf[0, :self.rows]
+        _, _, _, _, loss, risk = model.nll_step_group((x, list(self.sizes)), torch.cat(self.labels), torch.cat(self.cs),
+                                                      alpha=alpha, loss_scale=loss_scale, seeds=seeds)
         out = [(slot, loss[g:g + 1], risk[g:g + 1]) for g, slot in enumerate(self.slots)]
         self.reset()
         return out
@@ -238,11 +248,11 @@ def _fused_cox_ok(model, loss_fn, feats):
     return x is not None and x.dtype == torch.float32 and model.cox_step_ok(x)
 
 
-def _fused_radio_ok(model, loss_fn, feats):
+def _fused_radio_ok(model, loss_fn, feats, on_host=False):
     """The radiology head's step without an autograd graph (model.nll_step: reduce_dim, then stack + head + loss + backward
     in one call, then reduce_dim's backward).  Only where that is exactly what `model(**feats)` + the stock loss would
     compute: MIL_Attention_fc_surv_radio ITSELF, the stock NLLSurvLoss, fp32 2-D modality bags of one shape on the GPU, no
-    hooks, every parameter trainable."""
+    hooks, every parameter trainable.  on_host: the bags may still be on the host (group=True asks before the copy)."""
     from ..models.model_attention_mil_radio import MIL_Attention_fc_surv_radio
     import torch.nn.modules.module as tm
     if type(loss_fn) is not NLLSurvLoss or type(model).forward is not MIL_Attention_fc_surv_radio.forward:
@@ -250,7 +260,7 @@ def _fused_radio_ok(model, loss_fn, feats):
     if not getattr(model, "mmf_one_call_step", True) or getattr(model.classifier, "out_features", 1 << 30) > 32:
         return False
     bags = [feats.get(m) for m in model.modalities]
-    if any(not (torch.is_tensor(b) and b.is_cuda and b.dim() == 2 and b.dtype == torch.float32) for b in bags):
+    if any(not (torch.is_tensor(b) and (b.is_cuda or on_host) and b.dim() == 2 and b.dtype == torch.float32) for b in bags):
         return False
     if any(b.shape != bags[0].shape for b in bags):
         return False
@@ -308,8 +318,8 @@ def train_loop_survival(epoch, model, loader, optimizer, n_classes, mode, writer
       FlatAdam  fused L1 + Adam tail (optim.py); reg_fn must then be l1_reg_all, or l1_reg_modules with a FlatAdam
                 built with the matching `l1_modules`;
       inflight  > 1 (needs FlatAdam): the window's bags run round-robin on that many HIP streams (pipeline.py);
-      group     the pathology head's fp32 bags (those the one-call step takes, exact-fp32 GEMMs) are held on the device as
-                they arrive and run as ONE grouped call per window (model.nll_step_group: one launch chain over their
+      group     the pathology and radiology heads' fp32 bags (those their one-call steps take, exact-fp32 GEMMs) are held
+                on the device as they arrive and run as ONE grouped call per window (model.nll_step_group: one launch chain over their
                 concatenated rows), issued before the window's boundary and, for a trailing partial window, at the end
                 of the epoch; more than ops.GROUP_MAX bags or the row limit split it into several calls.  Each bag's
                 dropout seed is drawn when it arrives; a bag the grouped call does not take flushes the group and runs
@@ -364,10 +374,12 @@ def train_loop_survival(epoch, model, loader, optimizer, n_classes, mode, writer
                 # would write a NaN loss instead, which only shows in the epoch mean -- so check while it is on the host
                 raise IndexError(f"survival bin label {label.tolist()} outside [0, {n_classes})")
             # group: a host bag goes straight from the loader into its rows of the group buffer (an empty slice of it
-            # stands in while the route is decided)
+            # stands in while the route is decided).  A radiology bag is judged on its host tensors, before any copy.
             direct = group and torch.is_tensor(path_features) and not path_features.is_cuda
-            feats, label, c = _to_device(radio_features, path_features[:0] if direct else path_features,
-                                         genomic_features, label, c, device)
+            grouped_radio = group and ops._gemm == 0 and _fused_radio_ok(model, loss_fn, radio_features, on_host=True)
+            feats, label, c = _to_device({k: r[:0] for k, r in radio_features.items()} if grouped_radio else radio_features,
+                                         path_features[:0] if direct else path_features, genomic_features, label, c,
+                                         device)
 
             def forward_loss():
                 hazards, S, Y_hat, _ = model(**feats)
@@ -378,19 +390,23 @@ def train_loop_survival(epoch, model, loader, optimizer, n_classes, mode, writer
                 raise NotImplementedError(type(loss_fn))
 
             fused_step = _fused_step_ok(model, loss_fn, feats)
-            grouped = group and fused_step and feats["path_features"].dtype == torch.float32 and ops._gemm == 0
+            grouped = grouped_radio or (group and fused_step and feats["path_features"].dtype == torch.float32
+                                        and ops._gemm == 0)
             if group and not grouped:
                 flush()                  # the bags held so far run first: the window keeps loader order
                 if direct:
                     feats["path_features"] = path_features.to(device, non_blocking=True)
             fused_cox = (not fused_step) and pipe is None and _fused_cox_ok(model, loss_fn, feats)
             fused_mm = (not fused_step) and (not fused_cox) and pipe is None and _fused_mm_ok(model, loss_fn, feats)
-            fused_radio = (not fused_step) and (not fused_cox) and (not fused_mm) and pipe is None \
+            fused_radio = (not grouped) and (not fused_step) and (not fused_cox) and (not fused_mm) and pipe is None \
                 and _fused_radio_ok(model, loss_fn, feats)
             if grouped:
                 # held for the window's grouped call; its loss and risk fill these slots when the group runs
-                held.add(model, path_features if direct else feats["path_features"], label, c,
-                         ops.next_dropout_seed() if model.training else 0, len(losses), device, flush)
+                if grouped_radio:
+                    xs = [radio_features[m] for m in model.modalities]
+                else:
+                    xs = [path_features if direct else feats["path_features"]]
+                held.add(model, xs, label, c, ops.next_dropout_seed() if model.training else 0, len(losses), device, flush)
                 loss = risk = None
             elif fused_radio:
                 _, _, _, _, loss, risk = model.nll_step(label, c, alpha=loss_fn.alpha, loss_scale=1.0 / G, **feats)
