@@ -81,6 +81,55 @@ static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t
 
 constexpr int PREP_GROUPS = 512;
 
+// Bump allocator over a caller's workspace: every slot starts on a 256-byte boundary.  With a null base it only counts
+// (the *_workspace_bytes queries); `off` is the size carved so far.
+struct Carver {
+  uintptr_t base;
+  size_t off = 0;
+  explicit Carver(void* b = nullptr) : base(reinterpret_cast<uintptr_t>(b)) {}
+  template <class T> T* take(size_t n) {
+    T* r = reinterpret_cast<T*>(base + off);
+    off += align_up(n * sizeof(T), 256);
+    return r;
+  }
+};
+
+// Rows per split of a split-K TN launch over K >= 1 rows.  Splits are cut at multiples of 4 instances (one MFMA k-step
+// of the TN tile), not of whole 32-instance chunks: all splits then have the same length and end with a partial chunk
+// whose empty fragment groups are skipped.
+static int k_per_split(int64_t K, int splits) {
+  const int64_t kps = (K + splits - 1) / splits;
+  return (int)((kps + 3) / 4 * 4);
+}
+
+// The segments of one reduce launch.  add() refuses a segment past the last slot, and the launch then refuses the list.
+struct ReduceList {
+  ReduceParams p{};
+  int err = MMF_OK;
+  int add(const float* in, float* out, int len, int nsplit, size_t stride) {
+    constexpr int cap = (int)(sizeof(p.seg) / sizeof(p.seg[0]));
+    if (p.nseg == cap) return err = MMF_ERR_SHAPE;
+    p.seg[p.nseg++] = ReduceSeg{in, out, len, nsplit, stride, 0, 0};
+    return MMF_OK;
+  }
+  int launch(int accumulate, hipStream_t st) {
+    if (err) return err;
+    p.accumulate = accumulate;
+    return launch_reduce(p, st);
+  }
+};
+
+// The gradient pointers a stack backward writes, and their alignment (dx: the input gradient, where the entry point
+// takes one)
+static int check_grads(const mmf_amil_desc* d, const mmf_amil_grads* g) {
+  if (!g->dW1 || !g->db1 || !g->dWa || !g->dba || !g->dWc || !g->dbc) return MMF_ERR_ARG;
+  if (d->gated && (!g->dWb || !g->dbb)) return MMF_ERR_ARG;
+  return MMF_OK;
+}
+static bool grads_aligned(const mmf_amil_desc* d, const mmf_amil_grads* g) {
+  return aligned16(g->dW1) && aligned16(g->dWa) && (!d->gated || aligned16(g->dWb)) && (!g->dx || aligned16(g->dx));
+}
+
 struct AmilWs {
   float *M_step, *dM_step;           // [H] each: pooled embedding and its gradient inside mmf_amil_nll_step
   unsigned long long* relu_bits;     // [ceil(N/16)][H/32][8]: h > 0 per element (LinearParams::relu_bits)
@@ -92,15 +141,9 @@ struct AmilWs {
   size_t bytes;
 };
 
-static AmilWs carve(void* base, int64_t N, int L, int H, int D, int gated, bool infer = false) {
+static AmilWs carve(Carver& c, int64_t N, int L, int H, int D, int gated, bool infer = false) {
   AmilWs w{};
-  char* p = static_cast<char*>(base);
-  size_t off = 0;
-  auto take = [&](size_t nfloat) {
-    float* r = reinterpret_cast<float*>(p + off);
-    off += align_up(nfloat * sizeof(float), 256);
-    return r;
-  };
+  auto take = [&](size_t n) { return c.take<float>(n); };
   w.parts = gate_parts(D, gated, N);
   w.groups = pool_groups(N);
   w.mstk = gated ? 2 * D : D;
@@ -109,16 +152,11 @@ static AmilWs carve(void* base, int64_t N, int L, int H, int D, int gated, bool 
   int splits = tn_splits(N, tiles, td);
   w.tile = td;
   w.splits = splits;
-  // splits are cut at multiples of 4 instances (one MFMA k-step of the TN tile), not of whole 32-instance chunks: all
-  // splits then have the same length and end with a partial chunk whose empty fragment groups are skipped
-  int64_t kps = (N + splits - 1) / splits;
-  w.k_per_split = (int)((kps + 3) / 4 * 4);
-  if (w.k_per_split < 4) w.k_per_split = 4;
+  w.k_per_split = k_per_split(N, splits);
   // A gate tile builds its A operand (dP from a, b, ds) in the staging path and lives ~8 % longer per K row than a
   // dW1 tile (in-kernel cycle stamps: 710 k vs 659 k with equal splits), so the whole launch waited for the gate tiles.  The
   // workgroups the uniform split leaves over (256 - 6 x 42 = 4) go to the gate problem: 44 splits of 36 chunks beside
   // 42 of 38 at N = 50k.  Large-bag tile only, at most 12 % more splits.
-  w.splits_g = splits; w.k_per_split_g = w.k_per_split;
   {
     static const int env = mmf::tune_int("MMF_TN_GATE_SPLITS", -1);   // tuning override
     const int t1 = ((H + td - 1) / td) * ((L + td - 1) / td), t2 = tiles - t1;
@@ -130,10 +168,7 @@ static AmilWs carve(void* base, int64_t N, int L, int H, int D, int gated, bool 
       if (sg < splits) sg = splits;
     }
     if (env > 0) sg = env;
-    const int64_t kg = (N + sg - 1) / sg;
-    int kpg = (int)((kg + 3) / 4 * 4);
-    if (kpg < 4) kpg = 4;
-    w.splits_g = sg; w.k_per_split_g = kpg;
+    w.splits_g = sg; w.k_per_split_g = k_per_split(N, sg);
   }
   w.M_step = take(H);
   w.dM_step = take(H);
@@ -145,11 +180,11 @@ static AmilWs carve(void* base, int64_t N, int L, int H, int D, int gated, bool 
     const size_t kf = linear_ksplit_floats(N, H, L, 1, L);
     w.kpart = kf ? take(kf) : nullptr;
   }
-  if (infer) {            // forward-only: nothing is kept for a backward (a, b stay null: K-gate skips their stores)
-    w.bytes = off;
+  if (infer) {            // forward-only: nothing is kept for a backward (relu_bits, a, b stay null: K-gate skips their stores)
+    w.bytes = c.off;
     return w;
   }
-  w.relu_bits = reinterpret_cast<unsigned long long*>(take((size_t)((N + 15) / 16 + 2) * (H / 32) * 8 * 2));
+  w.relu_bits = c.take<unsigned long long>((size_t)((N + 15) / 16 + 2) * (H / 32) * 8);
   w.a = take((size_t)N * D);
   w.b = take(gated ? (size_t)N * D : 0);
   w.p = take((size_t)N);
@@ -161,7 +196,7 @@ static AmilWs carve(void* base, int64_t N, int L, int H, int D, int gated, bool 
   w.cs_b1 = take((size_t)splits * H);
   w.cs_bab = take((size_t)w.splits_g * w.mstk);
   w.cs_wc = take((size_t)w.splits_g * D);
-  w.bytes = off;
+  w.bytes = c.off;
   return w;
 }
 
@@ -181,6 +216,128 @@ static int check_desc(const mmf_amil_desc* d, int elem_bytes = 4) {
   return MMF_OK;
 }
 
+// ---- the fp32 attention stack's launch parameters ------------------------------------------------------------------
+// Built once from the descriptor, the workspace, the input and the seed of the dropout keys for the one-bag chain
+// (amil_forward_impl / amil_backward_impl) and the grouped chain (group_chain); the standalone scorer (mmf_attn_net_*)
+// uses the gate builders with h = x.  Each chain then sets only what is its own.
+//
+// The grouped chain runs the same fields through its `_seg` launchers, where they end up the same or are not read:
+// `split` is derived from desc->gemm and is 0 there, because group_check refuses bf16x3; launch_bwd_dh_seg never reads
+// BwdDhParams::allow_half and refuses fused_prep.  A carve for inference leaves relu_bits, a and b null.
+
+static GateFwdParams gate_fwd_params(const mmf_amil_desc* d, const float* h, float* a, float* b, float* s_part,
+                                     uint32_t seed) {
+  GateFwdParams gp{};
+  gp.h = h; gp.Wa = d->Wa; gp.ba = d->ba; gp.Wb = d->Wb; gp.bb = d->bb; gp.Wc = d->Wc;
+  gp.a = a; gp.b = b; gp.s_part = s_part;
+  gp.N = d->N; gp.H = d->H; gp.D = d->D; gp.gated = d->gated;
+  gp.drop_p = d->p_att; gp.key_a = drop_key(seed, 1); gp.key_b = drop_key(seed, 2); gp.seed_dev = d->seed_dev;
+  return gp;
+}
+
+static GateBwdCtx gate_bwd_ctx(const mmf_amil_desc* d, const float* a, const float* b, const float* ds, uint32_t seed) {
+  GateBwdCtx gc{};
+  gc.a = a; gc.b = b; gc.ds = ds; gc.Wc = d->Wc; gc.D = d->D; gc.gated = d->gated;
+  gc.drop_p = d->p_att; gc.key_a = drop_key(seed, 1); gc.key_b = drop_key(seed, 2); gc.seed_dev = d->seed_dev;
+  return gc;
+}
+
+// d[Wa ; Wb] = dP^T . B ; (dba | dbb) = colsum(dP) ; dWc = colsum(ds . a_d . b_d), dP built from the launch's GateBwdCtx
+static TnProblem tn_gate_problem(const mmf_amil_desc* d, const float* B, float* out, float* cs_bab, float* cs_wc) {
+  const int mstk = d->gated ? 2 * d->D : d->D;
+  TnProblem q{};
+  q.kind = TN_A_GATE; q.A = nullptr; q.lda = 0; q.M = mstk;
+  q.B = B; q.ldb = d->H; q.Ncols = d->H;
+  q.out = out; q.split_stride = (size_t)mstk * d->H; q.ldc = d->H;
+  q.colsum = cs_bab; q.colsum_stride = mstk; q.colsum2 = cs_wc; q.colsum2_stride = d->D;
+  return q;
+}
+
+static LinearParams stack_linear(const mmf_amil_desc* d, const AmilWs& w, const float* x, uint32_t seed) {
+  LinearParams lp{};
+  lp.x[0] = x; lp.nseg = 1; lp.kseg = d->L; lp.ldx = d->L;
+  lp.w = d->W1; lp.bias = d->b1; lp.y = w.h;
+  lp.M = d->N; lp.N = d->H; lp.K = d->L;
+  lp.act = ACT_RELU; lp.drop_p = d->p_h; lp.drop_key = drop_key(seed, 0); lp.seed_dev = d->seed_dev;
+  lp.relu_bits = w.relu_bits;
+  lp.allow_half = 1; lp.concurrent = d->concurrent ? 1 : 0;
+  lp.split = d->gemm == MMF_GEMM_BF16X3;
+  lp.kpart = w.kpart; lp.ktick = d->sync; lp.ktick_words = d->sync ? d->sync_words : 0;
+  return lp;
+}
+
+static GateFwdParams stack_gate_fwd(const mmf_amil_desc* d, const AmilWs& w, uint32_t seed) {
+  GateFwdParams gp = gate_fwd_params(d, w.h, w.a, w.b, w.s_part, seed);
+  gp.split = d->gemm == MMF_GEMM_BF16X3;
+  return gp;
+}
+
+// the pooling launch but for where its partials, M, statistics and head tail go
+static PoolParams stack_pool(const mmf_amil_desc* d, const AmilWs& w, float* A_raw) {
+  PoolParams pp{};
+  pp.s_part = w.s_part; pp.n_parts = w.parts; pp.bc = d->bc; pp.h = w.h; pp.N = d->N; pp.H = d->H;
+  pp.A_raw = A_raw;
+  return pp;
+}
+
+// K-prep as its own launch (softmax weights p, ds = dL/dA and the dbc partials)
+static BwdPrepParams stack_prep(const mmf_amil_desc* d, const AmilWs& w, const float* A_raw, const float* stats,
+                                const float* M, const float* dM, const float* gA) {
+  BwdPrepParams bp{};
+  bp.h = w.h; bp.A_raw = A_raw; bp.stats = stats; bp.dM = dM; bp.M = M; bp.gA = gA;
+  bp.N = d->N; bp.H = d->H; bp.p = w.p; bp.ds = w.ds; bp.dbc_part = w.dbc_part;
+  bp.n_groups = (int)((d->N + 3) / 4 < PREP_GROUPS ? (d->N + 3) / 4 : PREP_GROUPS);
+  return bp;
+}
+
+// K-dh: du = (dP.Wab + p dM) * relu'(h) * scale_h; fused_prep 0 (the one-bag chain may fuse K-prep in)
+static BwdDhParams stack_dh(const mmf_amil_desc* d, const AmilWs& w, const GateBwdCtx& gc, const float* dM) {
+  BwdDhParams dp{};
+  dp.g = gc; dp.Wa = d->Wa; dp.Wb = d->Wb; dp.p = w.p; dp.dM = dM; dp.h = w.h; dp.du = w.du;
+  dp.relu_bits = w.relu_bits;
+  dp.allow_half = 1; dp.concurrent = d->concurrent ? 1 : 0;
+  dp.split = d->gemm == MMF_GEMM_BF16X3;
+  dp.N = d->N; dp.H = d->H; dp.scale_h = d->p_h > 0.f ? 1.0f / (1.0f - d->p_h) : 1.0f;
+  return dp;
+}
+
+// d(input) = du . W1
+static NnParams stack_dx(const mmf_amil_desc* d, const AmilWs& w, float* dx) {
+  NnParams np{};
+  np.A = w.du; np.lda = d->H; np.B = d->W1; np.ldb = d->L; np.C = dx; np.ldc = d->L;
+  np.M = d->N; np.N = d->L; np.K = d->H;
+  return np;
+}
+
+// the stack's two problems, appended to the tp.nprob already there: dW1[H x L] = du^T . x ; db1 = colsum(du), and the
+// gate problem over h with its own (more, shorter) splits
+static void stack_tn(const mmf_amil_desc* d, const AmilWs& w, const float* x, const GateBwdCtx& gc, TnParams& tp) {
+  const int n = tp.nprob;
+  tp.nprob = n + 2; tp.K = d->N; tp.splits = w.splits; tp.k_per_split = w.k_per_split; tp.g = gc; tp.tile = w.tile;
+  tp.split = d->gemm == MMF_GEMM_BF16X3;
+  TnProblem& q1 = tp.prob[n];
+  q1.kind = TN_A_PLAIN; q1.A = w.du; q1.lda = d->H; q1.M = d->H;
+  q1.B = x; q1.ldb = d->L; q1.Ncols = d->L;
+  q1.out = w.slab_w1; q1.split_stride = (size_t)d->H * d->L; q1.ldc = d->L;
+  q1.colsum = w.cs_b1; q1.colsum_stride = d->H; q1.colsum2 = nullptr; q1.colsum2_stride = 0;
+  TnProblem& q2 = tp.prob[n + 1];
+  q2 = tn_gate_problem(d, w.h, w.slab_wab, w.cs_bab, w.cs_wc);
+  q2.splits = w.splits_g; q2.k_per_split = w.k_per_split_g;
+}
+
+// the stack's eight sums (six when ungated): its split-K slabs and the dbc partials of K-prep
+static void stack_reduce(const mmf_amil_desc* d, const AmilWs& w, const mmf_amil_grads* g, int dbc_parts, ReduceList& rl) {
+  const size_t wab_stride = (size_t)w.mstk * d->H;
+  rl.add(w.slab_w1, g->dW1, d->H * d->L, w.splits, (size_t)d->H * d->L);
+  rl.add(w.slab_wab, g->dWa, d->D * d->H, w.splits_g, wab_stride);
+  if (d->gated) rl.add(w.slab_wab + (size_t)d->D * d->H, g->dWb, d->D * d->H, w.splits_g, wab_stride);
+  rl.add(w.cs_b1, g->db1, d->H, w.splits, d->H);
+  rl.add(w.cs_bab, g->dba, d->D, w.splits_g, w.mstk);
+  if (d->gated) rl.add(w.cs_bab + d->D, g->dbb, d->D, w.splits_g, w.mstk);
+  rl.add(w.cs_wc, g->dWc, d->D, w.splits_g, d->D);
+  rl.add(w.dbc_part, g->dbc, 1, dbc_parts, 1);
+}
+
 // ---- bf16-storage path (mmf_bf16.h) ----------------------------------------------------------
 struct AmilWsBf {
   float *M_step, *dM_step;
@@ -193,15 +350,9 @@ struct AmilWsBf {
 
 static AmilWsBf carve_bf16(void* base, int64_t N, int L, int H, int D, int gated, bool infer = false) {
   AmilWsBf w{};
-  char* p = static_cast<char*>(base);
-  size_t off = 0;
-  auto take_b = [&](size_t nbytes) {
-    char* r = p + off;
-    off += align_up(nbytes, 256);
-    return r;
-  };
-  auto take16 = [&](size_t n) { return reinterpret_cast<bf16_t*>(take_b(n * 2)); };
-  auto take32 = [&](size_t n) { return reinterpret_cast<float*>(take_b(n * 4)); };
+  Carver c(base);
+  auto take16 = [&](size_t n) { return c.take<bf16_t>(n); };
+  auto take32 = [&](size_t n) { return c.take<float>(n); };
   w.parts = gate_parts_bf16(D, gated);
   w.groups = pool_groups(N);
   w.mstk = gated ? 2 * D : D;
@@ -224,7 +375,7 @@ static AmilWsBf carve_bf16(void* base, int64_t N, int L, int H, int D, int gated
   }
   w.stats = take32(4);
   if (infer) {
-    w.bytes = off;
+    w.bytes = c.off;
     return w;
   }
   w.a = take16((size_t)N * D);
@@ -239,7 +390,7 @@ static AmilWsBf carve_bf16(void* base, int64_t N, int L, int H, int D, int gated
   w.slab_wab = take32((size_t)w.splits * w.mstk * H);
   w.cs_b1 = take32((size_t)w.splits * H);
   w.cs_bab = take32((size_t)w.splits * w.mstk);
-  w.bytes = off;
+  w.bytes = c.off;
   return w;
 }
 
@@ -271,7 +422,8 @@ const char* mmf_strerror(int code) {
 
 size_t mmf_amil_workspace_bytes(int64_t N, int32_t L, int32_t H, int32_t D, int32_t gated) {
   if (N < 1) N = 1;
-  return carve(nullptr, N, L, H, D, gated).bytes;
+  Carver c;
+  return carve(c, N, L, H, D, gated).bytes;
 }
 
 static int amil_forward_impl(const mmf_amil_desc* d, const float* x, void* workspace, size_t workspace_bytes,
@@ -280,35 +432,17 @@ static int amil_forward_impl(const mmf_amil_desc* d, const float* x, void* works
   if (!x || !workspace || !A_raw) return MMF_ERR_ARG;
   if (!aligned16(x) || !aligned16(workspace) || !aligned16(d->W1) || !aligned16(d->Wa) || (d->gated && !aligned16(d->Wb)))
     return MMF_ERR_ALIGN;
-  AmilWs w = carve(workspace, d->N, d->L, d->H, d->D, d->gated, infer);
+  Carver c(workspace);
+  AmilWs w = carve(c, d->N, d->L, d->H, d->D, d->gated, infer);
   if (w.bytes > workspace_bytes) return MMF_ERR_WORKSPACE;
   if (!M) M = w.M_step;
   hipStream_t st = static_cast<hipStream_t>(stream);
   TraceScope ts(d->trace);
-  const uint32_t* const seed_dev = d->seed_dev;
 
-  LinearParams lp{};
-  lp.x[0] = x; lp.nseg = 1; lp.kseg = d->L; lp.ldx = d->L;
-  lp.w = d->W1; lp.bias = d->b1; lp.y = w.h;
-  lp.M = d->N; lp.N = d->H; lp.K = d->L;
-  lp.act = ACT_RELU; lp.drop_p = d->p_h; lp.drop_key = drop_key(d->seed, 0); lp.seed_dev = seed_dev;
-  lp.relu_bits = infer ? nullptr : w.relu_bits;
-  lp.allow_half = 1; lp.concurrent = d->concurrent ? 1 : 0;
-  lp.split = d->gemm == MMF_GEMM_BF16X3;
-  lp.kpart = w.kpart; lp.ktick = d->sync; lp.ktick_words = d->sync ? d->sync_words : 0;
-  if (int e = launch_linear(lp, st)) return e;
-
-  GateFwdParams gp{};
-  gp.h = w.h; gp.Wa = d->Wa; gp.ba = d->ba; gp.Wb = d->Wb; gp.bb = d->bb; gp.Wc = d->Wc;
-  gp.a = w.a; gp.b = w.b; gp.s_part = w.s_part;
-  gp.N = d->N; gp.H = d->H; gp.D = d->D; gp.gated = d->gated;
-  gp.drop_p = d->p_att; gp.key_a = drop_key(d->seed, 1); gp.key_b = drop_key(d->seed, 2); gp.seed_dev = seed_dev;
-  gp.split = d->gemm == MMF_GEMM_BF16X3;
-  if (int e = launch_gate_fwd(gp, st)) return e;
-
-  PoolParams pp{};
-  pp.s_part = w.s_part; pp.n_parts = w.parts; pp.bc = d->bc; pp.h = w.h; pp.N = d->N; pp.H = d->H;
-  pp.A_raw = A_raw; pp.partials = w.partials; pp.M = M; pp.stats = w.stats;
+  if (int e = launch_linear(stack_linear(d, w, x, d->seed), st)) return e;
+  if (int e = launch_gate_fwd(stack_gate_fwd(d, w, d->seed), st)) return e;
+  PoolParams pp = stack_pool(d, w, A_raw);
+  pp.partials = w.partials; pp.M = M; pp.stats = w.stats;
   if (tail) { pp.tail = *tail; pp.tail.dM = w.dM_step; }
   return launch_pool(pp, st);
 }
@@ -320,7 +454,8 @@ int mmf_amil_forward(const mmf_amil_desc* d, const float* x, void* workspace, si
 
 size_t mmf_amil_infer_workspace_bytes(int64_t N, int32_t L, int32_t H, int32_t D, int32_t gated) {
   if (N < 1) N = 1;
-  return carve(nullptr, N, L, H, D, gated, true).bytes;
+  Carver c;
+  return carve(c, N, L, H, D, gated, true).bytes;
 }
 
 int mmf_amil_infer(const mmf_amil_desc* d, const float* x, void* workspace, size_t workspace_bytes,
@@ -333,29 +468,18 @@ static int amil_backward_impl(const mmf_amil_desc* d, const float* x, void* work
                               const mmf_amil_grads* g, void* stream, int accumulate) {
   if (int e = check_desc(d)) return e;
   if (!x || !workspace || !A_raw || !g) return MMF_ERR_ARG;
-  if (!g->dW1 || !g->db1 || !g->dWa || !g->dba || !g->dWc || !g->dbc) return MMF_ERR_ARG;
-  if (d->gated && (!g->dWb || !g->dbb)) return MMF_ERR_ARG;
-  if (!aligned16(g->dW1) || !aligned16(g->dWa) || (d->gated && !aligned16(g->dWb)) || (g->dx && !aligned16(g->dx)))
-    return MMF_ERR_ALIGN;
-  AmilWs w = carve(workspace, d->N, d->L, d->H, d->D, d->gated);
+  if (int e = check_grads(d, g)) return e;
+  if (!grads_aligned(d, g)) return MMF_ERR_ALIGN;
+  Carver c(workspace);
+  AmilWs w = carve(c, d->N, d->L, d->H, d->D, d->gated);
   if (w.bytes > workspace_bytes) return MMF_ERR_WORKSPACE;
   if (!M) M = w.M_step;          // inside mmf_amil_nll_step the pooled embedding and its gradient live in the workspace
   if (!dM) dM = w.dM_step;
   hipStream_t st = static_cast<hipStream_t>(stream);
   TraceScope ts(d->trace);
-  const uint32_t* const seed_dev = d->seed_dev;
 
-  GateBwdCtx gc{};
-  gc.a = w.a; gc.b = w.b; gc.ds = w.ds; gc.Wc = d->Wc; gc.D = d->D; gc.gated = d->gated;
-  gc.drop_p = d->p_att; gc.key_a = drop_key(d->seed, 1); gc.key_b = drop_key(d->seed, 2); gc.seed_dev = seed_dev;
-
-  BwdDhParams dp{};
-  dp.g = gc; dp.Wa = d->Wa; dp.Wb = d->Wb; dp.p = w.p; dp.dM = dM; dp.h = w.h; dp.du = w.du;
-  dp.relu_bits = w.relu_bits;
-  dp.allow_half = 1; dp.concurrent = d->concurrent ? 1 : 0;
-  dp.split = d->gemm == MMF_GEMM_BF16X3;
-  dp.N = d->N; dp.H = d->H; dp.scale_h = d->p_h > 0.f ? 1.0f / (1.0f - d->p_h) : 1.0f;
-
+  const GateBwdCtx gc = gate_bwd_ctx(d, w.a, w.b, w.ds, d->seed);
+  BwdDhParams dp = stack_dh(d, w, gc, dM);
   // K-prep (softmax weights, ds) either fused into the wide K-dh kernel or as its own launch
   int dbc_groups = bwd_dh_fused_groups(d->N, d->H, 1, d->D, d->gated, dp.split, d->concurrent ? 1 : 0);
   if (dbc_groups > 0 && dbc_groups <= PREP_GROUPS) {
@@ -363,54 +487,22 @@ static int amil_backward_impl(const mmf_amil_desc* d, const float* x, void* work
     dp.A_raw = A_raw; dp.stats = w.stats; dp.Mpool = M; dp.gA = gA;
     dp.p_out = w.p; dp.ds_out = w.ds; dp.dbc_part = w.dbc_part;
   } else {
-    BwdPrepParams bp{};
-    bp.h = w.h; bp.A_raw = A_raw; bp.stats = w.stats; bp.dM = dM; bp.M = M; bp.gA = gA;
-    bp.N = d->N; bp.H = d->H; bp.p = w.p; bp.ds = w.ds; bp.dbc_part = w.dbc_part;
-    bp.n_groups = (int)((d->N + 3) / 4 < PREP_GROUPS ? (d->N + 3) / 4 : PREP_GROUPS);
+    const BwdPrepParams bp = stack_prep(d, w, A_raw, w.stats, M, dM, gA);
     dbc_groups = bp.n_groups;
     if (int e = launch_bwd_prep(bp, st)) return e;
   }
   if (int e = launch_bwd_dh(dp, st)) return e;
-
-  if (g->dx) {   // d(input) = du . W1   (radio: the input is reduce_dim's output)
-    NnParams np{};
-    np.A = w.du; np.lda = d->H; np.B = d->W1; np.ldb = d->L; np.C = g->dx; np.ldc = d->L;
-    np.M = d->N; np.N = d->L; np.K = d->H;
-    if (int e = launch_nn(np, st)) return e;
+  if (g->dx) {   // radio: the input is reduce_dim's output
+    if (int e = launch_nn(stack_dx(d, w, g->dx), st)) return e;
   }
 
   TnParams tp{};
-  tp.nprob = 2; tp.K = d->N; tp.splits = w.splits; tp.k_per_split = w.k_per_split; tp.g = gc; tp.tile = w.tile;
-  tp.split = dp.split;
-  TnProblem& q1 = tp.prob[0];   // dW1[H x L] = du^T . x ; db1 = colsum(du)
-  q1.kind = TN_A_PLAIN; q1.A = w.du; q1.lda = d->H; q1.M = d->H;
-  q1.B = x; q1.ldb = d->L; q1.Ncols = d->L;
-  q1.out = w.slab_w1; q1.split_stride = (size_t)d->H * d->L; q1.ldc = d->L;
-  q1.colsum = w.cs_b1; q1.colsum_stride = d->H; q1.colsum2 = nullptr; q1.colsum2_stride = 0;
-  TnProblem& q2 = tp.prob[1];   // dWab[(2)D x H] = dP^T . h ; (dba|dbb) = colsum(dP) ; dWc = colsum(ds.a_d.b_d)
-  q2.kind = TN_A_GATE; q2.A = nullptr; q2.lda = 0; q2.M = w.mstk;
-  q2.B = w.h; q2.ldb = d->H; q2.Ncols = d->H;
-  q2.out = w.slab_wab; q2.split_stride = (size_t)w.mstk * d->H; q2.ldc = d->H;
-  q2.colsum = w.cs_bab; q2.colsum_stride = w.mstk; q2.colsum2 = w.cs_wc; q2.colsum2_stride = d->D;
-  q2.splits = w.splits_g; q2.k_per_split = w.k_per_split_g;
+  stack_tn(d, w, x, gc, tp);
   if (int e = launch_tn(tp, st)) return e;
 
-  ReduceParams rp{};
-  int n = 0;
-  auto seg = [&](const float* in, float* out, int len, int nsplit, size_t stride) {
-    rp.seg[n].in = in; rp.seg[n].out = out; rp.seg[n].len = len; rp.seg[n].nsplit = nsplit; rp.seg[n].stride = stride; ++n;
-  };
-  seg(w.slab_w1, g->dW1, d->H * d->L, w.splits, (size_t)d->H * d->L);
-  seg(w.slab_wab, g->dWa, d->D * d->H, w.splits_g, (size_t)w.mstk * d->H);
-  if (d->gated) seg(w.slab_wab + (size_t)d->D * d->H, g->dWb, d->D * d->H, w.splits_g, (size_t)w.mstk * d->H);
-  seg(w.cs_b1, g->db1, d->H, w.splits, d->H);
-  seg(w.cs_bab, g->dba, d->D, w.splits_g, w.mstk);
-  if (d->gated) seg(w.cs_bab + d->D, g->dbb, d->D, w.splits_g, w.mstk);
-  seg(w.cs_wc, g->dWc, d->D, w.splits_g, d->D);
-  seg(w.dbc_part, g->dbc, 1, dbc_groups, 1);
-  rp.nseg = n;
-  rp.accumulate = accumulate;
-  return launch_reduce(rp, st);
+  ReduceList rl;
+  stack_reduce(d, w, g, dbc_groups, rl);
+  return rl.launch(accumulate, st);
 }
 
 int mmf_amil_backward(const mmf_amil_desc* d, const float* x, void* workspace, size_t workspace_bytes,
@@ -525,10 +617,9 @@ static int amil_bf16_backward_impl(const mmf_amil_desc* d, const uint16_t* x, vo
                                    const mmf_amil_grads* g, void* stream, int accumulate) {
   if (int e = check_desc_bf16(d)) return e;
   if (!x || !workspace || !A_raw || !g) return MMF_ERR_ARG;
-  if (!g->dW1 || !g->db1 || !g->dWa || !g->dba || !g->dWc || !g->dbc) return MMF_ERR_ARG;
-  if (d->gated && (!g->dWb || !g->dbb)) return MMF_ERR_ARG;
+  if (int e = check_grads(d, g)) return e;
   if (g->dx) return MMF_ERR_ARG;     // the bf16 bag is a leaf: no input gradient on this path
-  if (!aligned16(g->dW1) || !aligned16(g->dWa) || (d->gated && !aligned16(g->dWb))) return MMF_ERR_ALIGN;
+  if (!grads_aligned(d, g)) return MMF_ERR_ALIGN;
   AmilWsBf w = carve_bf16(workspace, d->N, d->L, d->H, d->D, d->gated);
   if (w.bytes > workspace_bytes) return MMF_ERR_WORKSPACE;
   if (!M) M = w.M_step;
@@ -565,22 +656,16 @@ static int amil_bf16_backward_impl(const mmf_amil_desc* d, const uint16_t* x, vo
   q2.colsum = w.cs_bab; q2.colsum_stride = w.mstk;
   if (int e = launch_tn_bf16(tp, st)) return e;
 
-  ReduceParams rp{};
-  int n = 0;
-  auto seg = [&](const float* in, float* out, int len, int nsplit, size_t stride) {
-    rp.seg[n].in = in; rp.seg[n].out = out; rp.seg[n].len = len; rp.seg[n].nsplit = nsplit; rp.seg[n].stride = stride; ++n;
-  };
-  seg(w.slab_w1, g->dW1, d->H * d->L, w.splits, (size_t)d->H * d->L);
-  seg(w.slab_wab, g->dWa, d->D * d->H, w.splits, (size_t)w.mstk * d->H);
-  if (d->gated) seg(w.slab_wab + (size_t)d->D * d->H, g->dWb, d->D * d->H, w.splits, (size_t)w.mstk * d->H);
-  seg(w.cs_b1, g->db1, d->H, w.splits, d->H);
-  seg(w.cs_bab, g->dba, d->D, w.splits, w.mstk);
-  if (d->gated) seg(w.cs_bab + d->D, g->dbb, d->D, w.splits, w.mstk);
-  seg(w.dwc_part, g->dWc, d->D, dh_bf16_tiles_used(d->N, ntn), d->D);
-  seg(w.dbc_part, g->dbc, 1, dh_bf16_tiles_used(d->N, ntn), 1);
-  rp.nseg = n;
-  rp.accumulate = accumulate;
-  return launch_reduce(rp, st);
+  ReduceList rl;
+  rl.add(w.slab_w1, g->dW1, d->H * d->L, w.splits, (size_t)d->H * d->L);
+  rl.add(w.slab_wab, g->dWa, d->D * d->H, w.splits, (size_t)w.mstk * d->H);
+  if (d->gated) rl.add(w.slab_wab + (size_t)d->D * d->H, g->dWb, d->D * d->H, w.splits, (size_t)w.mstk * d->H);
+  rl.add(w.cs_b1, g->db1, d->H, w.splits, d->H);
+  rl.add(w.cs_bab, g->dba, d->D, w.splits, w.mstk);
+  if (d->gated) rl.add(w.cs_bab + d->D, g->dbb, d->D, w.splits, w.mstk);
+  rl.add(w.dwc_part, g->dWc, d->D, dh_bf16_tiles_used(d->N, ntn), d->D);
+  rl.add(w.dbc_part, g->dbc, 1, dh_bf16_tiles_used(d->N, ntn), 1);
+  return rl.launch(accumulate, st);
 }
 
 int mmf_amil_bf16_backward(const mmf_amil_desc* d, const uint16_t* x, void* workspace, size_t workspace_bytes,
@@ -591,7 +676,7 @@ int mmf_amil_bf16_backward(const mmf_amil_desc* d, const uint16_t* x, void* work
 }
 
 // ---- attention stack + hazard head [+ nll_surv + the whole backward] in one call ------------------------------
-static int head_tail_of(const mmf_surv_head* h, const mmf_nll_target* t, int H, HeadTail& tl) {
+static int head_tail_of(const mmf_surv_head* h, const mmf_nll_target* t, HeadTail& tl) {
   if (!h || !h->Wk || !h->bk || !h->logits || !h->hazards || !h->S || !h->Y_hat) return MMF_ERR_ARG;
   if (h->K < 1 || h->K > 32) return MMF_ERR_SHAPE;
   tl = HeadTail{};
@@ -602,7 +687,6 @@ static int head_tail_of(const mmf_surv_head* h, const mmf_nll_target* t, int H, 
     tl.Y = t->Y; tl.c = t->c; tl.alpha = t->alpha; tl.eps = t->eps; tl.loss_scale = t->loss_scale;
     tl.loss = t->loss; tl.dWk = t->dWk; tl.dbk = t->dbk; tl.accumulate = t->accumulate;
   }
-  (void)H;
   return MMF_OK;
 }
 
@@ -610,7 +694,7 @@ int mmf_amil_head_forward(const mmf_amil_desc* d, const void* x, int32_t x_bf16,
                           const mmf_surv_head* head, float* M, float* A_raw, void* stream) {
   if (!d || !M) return MMF_ERR_ARG;
   HeadTail tl;
-  if (int e = head_tail_of(head, nullptr, d->H, tl)) return e;
+  if (int e = head_tail_of(head, nullptr, tl)) return e;
   return x_bf16 ? amil_bf16_forward_impl(d, static_cast<const uint16_t*>(x), workspace, workspace_bytes, M, A_raw, stream, false, &tl)
                 : amil_forward_impl(d, static_cast<const float*>(x), workspace, workspace_bytes, M, A_raw, stream, false, &tl);
 }
@@ -620,7 +704,7 @@ int mmf_amil_nll_step(const mmf_amil_desc* d, const void* x, int32_t x_bf16, voi
                       const mmf_amil_grads* grads, void* stream) {
   if (!d || !target || !grads) return MMF_ERR_ARG;
   HeadTail tl;
-  if (int e = head_tail_of(head, target, d->H, tl)) return e;
+  if (int e = head_tail_of(head, target, tl)) return e;
   const int acc = target->accumulate ? 1 : 0;
   if (x_bf16) {
     const uint16_t* xb = static_cast<const uint16_t*>(x);
@@ -673,27 +757,21 @@ struct GroupWs {
   int* bag;
   size_t bytes;
 };
-static GroupWs carve_group(void* base, const SegTable& s, int L, int H, int D, int gated) {
+static GroupWs carve_group(Carver& c, const SegTable& s, int L, int H, int D, int gated) {
   GroupWs g{};
   const int64_t R = s.off[s.G];
-  g.w = carve(base, R, L, H, D, gated);
-  char* p = static_cast<char*>(base);
-  size_t off = g.w.bytes;
-  auto take = [&](size_t nfloat) {
-    float* r = reinterpret_cast<float*>(p + off);
-    off += align_up(nfloat * sizeof(float), 256);
-    return r;
-  };
+  g.w = carve(c, R, L, H, D, gated);
+  auto take = [&](size_t n) { return c.take<float>(n); };
   g.M = take((size_t)s.G * H);
   g.dM = take((size_t)s.G * H);
   g.stats = take((size_t)2 * s.G);
   g.wk = take((size_t)s.G * 32 * H);          // per-bag classifier gradients (K <= 32), summed by the reduce launch
   g.bk = take((size_t)s.G * 32);
   g.partials = take((size_t)s.gbeg[s.G] * (2 + H));
-  g.ridx_h = reinterpret_cast<uint32_t*>(take((size_t)R));
-  g.ridx_d = reinterpret_cast<uint32_t*>(take((size_t)R));
-  g.bag = reinterpret_cast<int*>(take((size_t)R));
-  g.bytes = off;
+  g.ridx_h = c.take<uint32_t>((size_t)R);
+  g.ridx_d = c.take<uint32_t>((size_t)R);
+  g.bag = c.take<int>((size_t)R);
+  g.bytes = c.off;
   return g;
 }
 }  // namespace mmf
@@ -701,13 +779,12 @@ static GroupWs carve_group(void* base, const SegTable& s, int L, int H, int D, i
 namespace mmf {
 // reduce_dim's backward on the grouped chain's launches (mmf_radio_nll_step_group): its input gradient du . W1 over every
 // row, its weight-gradient problems in a TN launch of their own after the stack's (or, tuning, in the stack's launch,
-// ahead of the stack's two: they are the long ones), its sums in the stack's reduce launch
+// ahead of the stack's two: they are the long ones).  Its sums are entries on the stack's reduce list.
 struct GroupExtra {
   float* dx;                    // [R x L] <- du . W1
   TnProblem prob[4]; int nprob;
   int separate;                 // 1: the problems as a TN launch of their own; 0 (tuning): in the stack's launch
   int splits, k_per_split;
-  ReduceSeg seg[2]; int nseg;
 };
 
 // the call contract both grouped entry points share; fills the segment table (with each bag's mask index base) and the tail
@@ -720,12 +797,11 @@ static int group_check(const mmf_amil_desc* d, const mmf_bag_group* group, const
   if (int e = group_plan(group->offsets, group->G, s)) return e;
   if (d->N != s.off[s.G]) return MMF_ERR_SHAPE;
   if (int e = check_desc(d)) return e;
-  if (int e = head_tail_of(head, target, d->H, tl)) return e;
+  if (int e = head_tail_of(head, target, tl)) return e;
   if (!x || !workspace || !A_raw) return MMF_ERR_ARG;
-  if (!g->dW1 || !g->db1 || !g->dWa || !g->dba || !g->dWc || !g->dbc) return MMF_ERR_ARG;
-  if (d->gated && (!g->dWb || !g->dbb)) return MMF_ERR_ARG;
+  if (int e = check_grads(d, g)) return e;
   if (!aligned16(x) || !aligned16(workspace) || !aligned16(d->W1) || !aligned16(d->Wa) || (d->gated && !aligned16(d->Wb)) ||
-      !aligned16(g->dW1) || !aligned16(g->dWa) || (d->gated && !aligned16(g->dWb)))
+      !grads_aligned(d, g))
     return MMF_ERR_ALIGN;
   const uint32_t inv = hash_mul_inverse();
   for (int b = 0; b < s.G; ++b) s.ibase[b] = group->seeds[b] * inv;
@@ -733,115 +809,61 @@ static int group_check(const mmf_amil_desc* d, const mmf_bag_group* group, const
 }
 
 // the stack's chain over the window's rows x [sum N x L]: per-row tables, projection, gate, pooling + head tail per bag,
-// K-prep, K-dh, (du . W1), split-K TN, reduce
+// K-prep, K-dh, (du . W1), split-K TN.  The masks are those of the seed-0 keys at each row's index base (group_rows_kernel).
+// The stack's and the classifier's sums go on `rl`, for the caller's reduce launch.
 static int group_chain(const mmf_amil_desc* d, const SegTable& s, const float* x, const GroupWs& gw, const HeadTail& tl,
                        int K, const mmf_nll_target* target, float* A_raw, const mmf_amil_grads* g,
-                       const GroupExtra* ex, hipStream_t st) {
+                       const GroupExtra* ex, ReduceList& rl, hipStream_t st) {
   const AmilWs& w = gw.w;
-  const uint32_t* const seed_dev = d->seed_dev;
-  const int64_t R = d->N;
 
   GroupRowsParams rp0{};
   rp0.s = s; rp0.H = d->H; rp0.D = d->D; rp0.ridx_h = gw.ridx_h; rp0.ridx_d = gw.ridx_d; rp0.bag = gw.bag;
   if (int e = launch_group_rows(rp0, st)) return e;
 
-  LinearParams lp{};
-  lp.x[0] = x; lp.nseg = 1; lp.kseg = d->L; lp.ldx = d->L;
-  lp.w = d->W1; lp.bias = d->b1; lp.y = w.h;
-  lp.M = R; lp.N = d->H; lp.K = d->L;
-  lp.act = ACT_RELU; lp.drop_p = d->p_h; lp.drop_key = drop_key(0, 0); lp.seed_dev = seed_dev;
-  lp.relu_bits = w.relu_bits;
-  lp.allow_half = 1; lp.concurrent = d->concurrent ? 1 : 0;
-  lp.kpart = w.kpart; lp.ktick = d->sync; lp.ktick_words = d->sync ? d->sync_words : 0;
+  LinearParams lp = stack_linear(d, w, x, 0);
   lp.seg_ridx = gw.ridx_h;
   if (int e = launch_linear_seg(lp, st)) return e;
 
-  GateFwdParams gp{};
-  gp.h = w.h; gp.Wa = d->Wa; gp.ba = d->ba; gp.Wb = d->Wb; gp.bb = d->bb; gp.Wc = d->Wc;
-  gp.a = w.a; gp.b = w.b; gp.s_part = w.s_part;
-  gp.N = R; gp.H = d->H; gp.D = d->D; gp.gated = d->gated;
-  gp.drop_p = d->p_att; gp.key_a = drop_key(0, 1); gp.key_b = drop_key(0, 2); gp.seed_dev = seed_dev;
+  GateFwdParams gp = stack_gate_fwd(d, w, 0);
   gp.seg_ridx = gw.ridx_d;
   if (int e = launch_gate_fwd_seg(gp, st)) return e;
 
-  PoolParams pp{};
-  pp.s_part = w.s_part; pp.n_parts = w.parts; pp.bc = d->bc; pp.h = w.h; pp.N = R; pp.H = d->H;
-  pp.A_raw = A_raw; pp.partials = gw.partials; pp.M = gw.M; pp.stats = gw.stats;
+  PoolParams pp = stack_pool(d, w, A_raw);
+  pp.partials = gw.partials; pp.M = gw.M; pp.stats = gw.stats;
   pp.tail = tl; pp.tail.dM = gw.dM; pp.tail.dWk = gw.wk; pp.tail.dbk = gw.bk;
   if (int e = launch_group_pool(pp, s, st)) return e;
 
-  BwdPrepParams bp{};
-  bp.h = w.h; bp.A_raw = A_raw; bp.stats = gw.stats; bp.dM = gw.dM; bp.M = gw.M; bp.gA = nullptr;
-  bp.N = R; bp.H = d->H; bp.p = w.p; bp.ds = w.ds; bp.dbc_part = w.dbc_part;
-  bp.n_groups = (int)((R + 3) / 4 < PREP_GROUPS ? (R + 3) / 4 : PREP_GROUPS);
+  const BwdPrepParams bp = stack_prep(d, w, A_raw, gw.stats, gw.M, gw.dM, nullptr);
   if (int e = launch_group_bwd_prep(bp, gw.bag, st)) return e;
 
-  GateBwdCtx gc{};
-  gc.a = w.a; gc.b = w.b; gc.ds = w.ds; gc.Wc = d->Wc; gc.D = d->D; gc.gated = d->gated;
-  gc.drop_p = d->p_att; gc.key_a = drop_key(0, 1); gc.key_b = drop_key(0, 2); gc.seed_dev = seed_dev;
-
-  BwdDhParams dp{};
-  dp.g = gc; dp.Wa = d->Wa; dp.Wb = d->Wb; dp.p = w.p; dp.dM = gw.dM; dp.h = w.h; dp.du = w.du;
-  dp.relu_bits = w.relu_bits;
-  dp.concurrent = d->concurrent ? 1 : 0;
-  dp.N = R; dp.H = d->H; dp.scale_h = d->p_h > 0.f ? 1.0f / (1.0f - d->p_h) : 1.0f;
+  const GateBwdCtx gc = gate_bwd_ctx(d, w.a, w.b, w.ds, 0);
+  BwdDhParams dp = stack_dh(d, w, gc, gw.dM);
   dp.seg_ridx = gw.ridx_d; dp.seg_bag = gw.bag;
   if (int e = launch_bwd_dh_seg(dp, st)) return e;
 
   if (ex && ex->dx) {   // d(x) = du . W1: du carries every bag's ReLU and dropout masks
-    NnParams np{};
-    np.A = w.du; np.lda = d->H; np.B = d->W1; np.ldb = d->L; np.C = ex->dx; np.ldc = d->L;
-    np.M = R; np.N = d->L; np.K = d->H;
-    if (int e = launch_nn(np, st)) return e;
+    if (int e = launch_nn(stack_dx(d, w, ex->dx), st)) return e;
   }
 
   TnParams tp{};
-  const int nx = ex && !ex->separate ? ex->nprob : 0;
-  for (int i = 0; i < nx; ++i) tp.prob[i] = ex->prob[i];
-  tp.nprob = nx + 2; tp.K = R; tp.splits = w.splits; tp.k_per_split = w.k_per_split; tp.g = gc; tp.tile = w.tile;
+  if (ex && !ex->separate) {
+    for (int i = 0; i < ex->nprob; ++i) tp.prob[i] = ex->prob[i];
+    tp.nprob = ex->nprob;
+  }
+  stack_tn(d, w, x, gc, tp);
   tp.seg_ridx = gw.ridx_d;
-  TnProblem& q1 = tp.prob[nx];       // dW1[H x L] = du^T . x over every row of the window ; db1 = colsum(du)
-  q1.kind = TN_A_PLAIN; q1.A = w.du; q1.lda = d->H; q1.M = d->H;
-  q1.B = x; q1.ldb = d->L; q1.Ncols = d->L;
-  q1.out = w.slab_w1; q1.split_stride = (size_t)d->H * d->L; q1.ldc = d->L;
-  q1.colsum = w.cs_b1; q1.colsum_stride = d->H; q1.colsum2 = nullptr; q1.colsum2_stride = 0;
-  TnProblem& q2 = tp.prob[nx + 1];   // dWab = dP^T . h ; (dba|dbb) = colsum(dP) ; dWc = colsum(ds.a_d.b_d)
-  q2.kind = TN_A_GATE; q2.A = nullptr; q2.lda = 0; q2.M = w.mstk;
-  q2.B = w.h; q2.ldb = d->H; q2.Ncols = d->H;
-  q2.out = w.slab_wab; q2.split_stride = (size_t)w.mstk * d->H; q2.ldc = d->H;
-  q2.colsum = w.cs_bab; q2.colsum_stride = w.mstk; q2.colsum2 = w.cs_wc; q2.colsum2_stride = d->D;
-  q2.splits = w.splits_g; q2.k_per_split = w.k_per_split_g;
   if (int e = launch_tn(tp, st)) return e;
   if (ex && ex->separate) {
     TnParams tr{};
     for (int i = 0; i < ex->nprob; ++i) tr.prob[i] = ex->prob[i];
-    tr.nprob = ex->nprob; tr.K = R; tr.splits = ex->splits; tr.k_per_split = ex->k_per_split; tr.tile = w.tile;
+    tr.nprob = ex->nprob; tr.K = d->N; tr.splits = ex->splits; tr.k_per_split = ex->k_per_split; tr.tile = w.tile;
     if (int e = launch_tn(tr, st)) return e;
   }
 
-  ReduceParams rp{};
-  int n = 0;
-  auto seg = [&](const float* in, float* out, int len, int nsplit, size_t stride) {
-    rp.seg[n].in = in; rp.seg[n].out = out; rp.seg[n].len = len; rp.seg[n].nsplit = nsplit; rp.seg[n].stride = stride; ++n;
-  };
-  seg(w.slab_w1, g->dW1, d->H * d->L, w.splits, (size_t)d->H * d->L);
-  seg(w.slab_wab, g->dWa, d->D * d->H, w.splits_g, (size_t)w.mstk * d->H);
-  if (d->gated) seg(w.slab_wab + (size_t)d->D * d->H, g->dWb, d->D * d->H, w.splits_g, (size_t)w.mstk * d->H);
-  seg(w.cs_b1, g->db1, d->H, w.splits, d->H);
-  seg(w.cs_bab, g->dba, d->D, w.splits_g, w.mstk);
-  if (d->gated) seg(w.cs_bab + d->D, g->dbb, d->D, w.splits_g, w.mstk);
-  seg(w.cs_wc, g->dWc, d->D, w.splits_g, d->D);
-  seg(w.dbc_part, g->dbc, 1, bp.n_groups, 1);
-  seg(gw.wk, target->dWk, K * d->H, s.G, (size_t)K * d->H);      // classifier: the bags' slabs in bag order
-  seg(gw.bk, target->dbk, K, s.G, (size_t)K);
-  if (ex) {
-    constexpr int cap = (int)(sizeof(rp.seg) / sizeof(rp.seg[0]));   // gated: 10 + dW_r, db_r = every slot
-    if (n + ex->nseg > cap) return MMF_ERR_SHAPE;
-    for (int i = 0; i < ex->nseg; ++i) seg(ex->seg[i].in, ex->seg[i].out, ex->seg[i].len, ex->seg[i].nsplit, ex->seg[i].stride);
-  }
-  rp.nseg = n;
-  rp.accumulate = target->accumulate ? 1 : 0;
-  return launch_reduce(rp, st);
+  stack_reduce(d, w, g, bp.n_groups, rl);
+  rl.add(gw.wk, target->dWk, K * d->H, s.G, (size_t)K * d->H);      // classifier: the bags' slabs in bag order
+  rl.add(gw.bk, target->dbk, K, s.G, (size_t)K);
+  return MMF_OK;
 }
 
 // the radio window's workspace: the stack's (carve_group, L = kseg) and reduce_dim's output, its gradient, the split-K
@@ -852,18 +874,12 @@ struct RadioWs {
   int splits, k_per_split, separate;
   size_t bytes;
 };
-static RadioWs carve_radio(void* base, const SegTable& s, int nseg, int kseg, int H, int D, int gated) {
+static RadioWs carve_radio(Carver& c, const SegTable& s, int nseg, int kseg, int H, int D, int gated) {
   RadioWs r{};
   const int64_t R = s.off[s.G];
   const int L = kseg;
-  r.gw = carve_group(base, s, L, H, D, gated);
-  char* p = static_cast<char*>(base);
-  size_t off = r.gw.bytes;
-  auto take = [&](size_t nfloat) {
-    float* q = reinterpret_cast<float*>(p + off);
-    off += align_up(nfloat * sizeof(float), 256);
-    return q;
-  };
+  r.gw = carve_group(c, s, L, H, D, gated);
+  auto take = [&](size_t n) { return c.take<float>(n); };
   // dW_r as a TN launch of its own after the stack's, planned over its own tiles (mmf_linear_backward's plan), or as
   // more problems of the stack's launch, planned with the stack's tiles (fewer splits).  Measured: the
   // separate launch is faster, 1.295 vs 1.366 ms at 16 x 512 rows.  The slabs are sized by the separate plan, which has
@@ -876,16 +892,14 @@ static RadioWs carve_radio(void* base, const SegTable& s, int nseg, int kseg, in
   static const int env = tune_int("MMF_RADIO_TN_SEPARATE", 1);   // tuning override: 0 = in the stack's TN launch
   r.separate = env ? 1 : 0;
   r.splits = r.separate ? most : tn_splits(R, t_stack + t_rd, td);
-  const int64_t kps = (R + r.splits - 1) / r.splits;
-  r.k_per_split = (int)((kps + 3) / 4 * 4);
-  if (r.k_per_split < 4) r.k_per_split = 4;
+  r.k_per_split = k_per_split(R, r.splits);
   r.xr = take((size_t)R * L);
   r.dxr = take((size_t)R * L);
   r.slab = take((size_t)most * L * nseg * kseg);
   r.cs = take((size_t)most * L);
   const size_t kf = linear_ksplit_floats(R, L, nseg * kseg, nseg, kseg);
   r.kpart = kf ? take(kf) : nullptr;
-  r.bytes = off;
+  r.bytes = c.off;
   return r;
 }
 }  // namespace mmf
@@ -893,7 +907,8 @@ static RadioWs carve_radio(void* base, const SegTable& s, int nseg, int kseg, in
 size_t mmf_amil_group_workspace_bytes(const int64_t* offsets, int32_t G, int32_t L, int32_t H, int32_t D, int32_t gated) {
   SegTable s;
   if (group_plan(offsets, G, s)) return 0;
-  return carve_group(nullptr, s, L, H, D, gated).bytes;
+  Carver c;
+  return carve_group(c, s, L, H, D, gated).bytes;
 }
 
 int mmf_amil_nll_step_group(const mmf_amil_desc* d, const mmf_bag_group* group, const float* x, void* workspace,
@@ -902,17 +917,22 @@ int mmf_amil_nll_step_group(const mmf_amil_desc* d, const mmf_bag_group* group, 
   SegTable s;
   HeadTail tl;
   if (int e = group_check(d, group, x, workspace, head, target, A_raw, g, s, tl)) return e;
-  GroupWs gw = carve_group(workspace, s, d->L, d->H, d->D, d->gated);
+  Carver c(workspace);
+  GroupWs gw = carve_group(c, s, d->L, d->H, d->D, d->gated);
   if (gw.bytes > workspace_bytes) return MMF_ERR_WORKSPACE;
+  hipStream_t st = static_cast<hipStream_t>(stream);
   TraceScope ts(d->trace);
-  return group_chain(d, s, x, gw, tl, head->K, target, A_raw, g, nullptr, static_cast<hipStream_t>(stream));
+  ReduceList rl;
+  if (int e = group_chain(d, s, x, gw, tl, head->K, target, A_raw, g, nullptr, rl, st)) return e;
+  return rl.launch(target->accumulate ? 1 : 0, st);
 }
 
 size_t mmf_radio_group_workspace_bytes(const int64_t* offsets, int32_t G, int32_t nseg, int32_t kseg, int32_t H,
                                        int32_t D, int32_t gated) {
   SegTable s;
   if (group_plan(offsets, G, s) || nseg < 2 || nseg > 4 || kseg < 1) return 0;
-  return carve_radio(nullptr, s, nseg, kseg, H, D, gated).bytes;
+  Carver c;
+  return carve_radio(c, s, nseg, kseg, H, D, gated).bytes;
 }
 
 int mmf_radio_nll_step_group(const mmf_amil_desc* d, const mmf_bag_group* group, const mmf_radio_reduce* rd,
@@ -933,7 +953,8 @@ int mmf_radio_nll_step_group(const mmf_amil_desc* d, const mmf_bag_group* group,
   for (int m = 0; m < nseg; ++m)
     if (!aligned16(rd->x[m])) return MMF_ERR_ALIGN;
   if (!aligned16(rd->W) || !aligned16(rd->dW)) return MMF_ERR_ALIGN;
-  RadioWs r = carve_radio(workspace, s, nseg, kseg, d->H, d->D, d->gated);
+  Carver c(workspace);
+  RadioWs r = carve_radio(c, s, nseg, kseg, d->H, d->D, d->gated);
   if (r.bytes > workspace_bytes) return MMF_ERR_WORKSPACE;
   hipStream_t st = static_cast<hipStream_t>(stream);
   TraceScope ts(d->trace);
@@ -960,10 +981,11 @@ int mmf_radio_nll_step_group(const mmf_amil_desc* d, const mmf_bag_group* group,
     q.colsum = m == 0 ? r.cs : nullptr; q.colsum_stride = L;
     q.splits = r.splits; q.k_per_split = r.k_per_split;
   }
-  ex.seg[0] = ReduceSeg{r.slab, rd->dW, L * nseg * kseg, r.splits, (size_t)L * nseg * kseg, 0, 0};
-  ex.seg[1] = ReduceSeg{r.cs, rd->db, L, r.splits, (size_t)L, 0, 0};
-  ex.nseg = 2;
-  return group_chain(d, s, r.xr, r.gw, tl, head->K, target, A_raw, g, &ex, st);
+  ReduceList rl;
+  if (int e = group_chain(d, s, r.xr, r.gw, tl, head->K, target, A_raw, g, &ex, rl, st)) return e;
+  rl.add(r.slab, rd->dW, L * nseg * kseg, r.splits, (size_t)L * nseg * kseg);   // gated: the stack's 10 + these 2 = every slot
+  rl.add(r.cs, rd->db, L, r.splits, (size_t)L);
+  return rl.launch(target->accumulate ? 1 : 0, st);
 }
 
 int mmf_surv_head_nll_step(const float* feat, int32_t F, const mmf_surv_head* head, const mmf_nll_target* target,
@@ -971,7 +993,7 @@ int mmf_surv_head_nll_step(const float* feat, int32_t F, const mmf_surv_head* he
   if (!feat || !target || !dfeat) return MMF_ERR_ARG;
   if (F < 1 || F > 1024) return MMF_ERR_SHAPE;
   PoolParams p{};
-  if (int e = head_tail_of(head, target, F, p.tail)) return e;
+  if (int e = head_tail_of(head, target, p.tail)) return e;
   p.tail.dM = dfeat;
   p.M = const_cast<float*>(feat);        // read only: the launch neither merges nor stores M
   p.H = F;
@@ -987,13 +1009,8 @@ struct AttnWs {
 };
 static AttnWs carve_attn(void* base, int64_t N, int H, int D, int gated) {
   AttnWs w{};
-  char* p = static_cast<char*>(base);
-  size_t off = 0;
-  auto take = [&](size_t nfloat) {
-    float* r = reinterpret_cast<float*>(p + off);
-    off += align_up(nfloat * sizeof(float), 256);
-    return r;
-  };
+  Carver c(base);
+  auto take = [&](size_t n) { return c.take<float>(n); };
   w.parts = gate_parts(D, gated, N);
   w.mstk = gated ? 2 * D : D;
   w.tile = tn_tile_dim(N, D);
@@ -1001,16 +1018,14 @@ static AttnWs carve_attn(void* base, int64_t N, int H, int D, int gated) {
   const int dt = gated ? td / 2 : td;
   const int tiles = ((D + dt - 1) / dt) * ((H + td - 1) / td);
   w.splits = tn_splits(N, tiles, td);
-  const int64_t kps = (N + w.splits - 1) / w.splits;
-  w.k_per_split = (int)((kps + 3) / 4 * 4);
-  if (w.k_per_split < 4) w.k_per_split = 4;
+  w.k_per_split = k_per_split(N, w.splits);
   w.a = take((size_t)N * D);
   w.b = take(gated ? (size_t)N * D : 0);
   w.s_part = take((size_t)w.parts * N);
   w.slab = take((size_t)w.splits * w.mstk * H);
   w.cs_bab = take((size_t)w.splits * w.mstk);
   w.cs_wc = take((size_t)w.splits * D);
-  w.bytes = off;
+  w.bytes = c.off;
   return w;
 }
 static int check_attn(const mmf_amil_desc* d) {
@@ -1038,12 +1053,7 @@ int mmf_attn_net_forward(const mmf_amil_desc* d, const float* x, void* workspace
   if (w.bytes > workspace_bytes) return MMF_ERR_WORKSPACE;
   hipStream_t st = static_cast<hipStream_t>(stream);
   TraceScope ts(d->trace);
-  GateFwdParams gp{};
-  gp.h = x; gp.Wa = d->Wa; gp.ba = d->ba; gp.Wb = d->Wb; gp.bb = d->bb; gp.Wc = d->Wc;
-  gp.a = w.a; gp.b = w.b; gp.s_part = w.s_part;
-  gp.N = d->N; gp.H = d->H; gp.D = d->D; gp.gated = d->gated;
-  gp.drop_p = d->p_att; gp.key_a = drop_key(d->seed, 1); gp.key_b = drop_key(d->seed, 2); gp.seed_dev = d->seed_dev;
-  if (int e = launch_gate_fwd(gp, st)) return e;
+  if (int e = launch_gate_fwd(gate_fwd_params(d, x, w.a, w.b, w.s_part, d->seed), st)) return e;
   return launch_score_sum(w.s_part, w.parts, d->bc, A, d->N, st);
 }
 
@@ -1057,9 +1067,7 @@ int mmf_attn_net_backward(const mmf_amil_desc* d, const float* x, void* workspac
   if (w.bytes > workspace_bytes) return MMF_ERR_WORKSPACE;
   hipStream_t st = static_cast<hipStream_t>(stream);
   TraceScope ts(d->trace);
-  GateBwdCtx gc{};      // ds_i = dL/dA_i: the scorer has no softmax behind it here
-  gc.a = w.a; gc.b = w.b; gc.ds = gA; gc.Wc = d->Wc; gc.D = d->D; gc.gated = d->gated;
-  gc.drop_p = d->p_att; gc.key_a = drop_key(d->seed, 1); gc.key_b = drop_key(d->seed, 2); gc.seed_dev = d->seed_dev;
+  const GateBwdCtx gc = gate_bwd_ctx(d, w.a, w.b, gA, d->seed);   // ds_i = dL/dA_i: the scorer has no softmax behind it here
   if (g->dx) {          // dx = dP . [Wa ; Wb]  (K-dh without relu' mask and pooling term)
     BwdDhParams dp{};
     dp.g = gc; dp.Wa = d->Wa; dp.Wb = d->Wb; dp.du = g->dx; dp.N = d->N; dp.H = d->H; dp.scale_h = 1.0f;
@@ -1067,25 +1075,16 @@ int mmf_attn_net_backward(const mmf_amil_desc* d, const float* x, void* workspac
   }
   TnParams tp{};
   tp.nprob = 1; tp.K = d->N; tp.splits = w.splits; tp.k_per_split = w.k_per_split; tp.g = gc; tp.tile = w.tile;
-  TnProblem& q = tp.prob[0];    // d[Wa ; Wb] = dP^T . x ; (dba | dbb) = colsum(dP) ; dWc = colsum(gA . a_d . b_d)
-  q.kind = TN_A_GATE; q.A = nullptr; q.lda = 0; q.M = w.mstk;
-  q.B = x; q.ldb = d->H; q.Ncols = d->H;
-  q.out = w.slab; q.split_stride = (size_t)w.mstk * d->H; q.ldc = d->H;
-  q.colsum = w.cs_bab; q.colsum_stride = w.mstk; q.colsum2 = w.cs_wc; q.colsum2_stride = d->D;
+  tp.prob[0] = tn_gate_problem(d, x, w.slab, w.cs_bab, w.cs_wc);
   if (int e = launch_tn(tp, st)) return e;
-  ReduceParams rp{};
-  int n = 0;
-  auto seg = [&](const float* in, float* out, int len, int nsplit, size_t stride) {
-    rp.seg[n].in = in; rp.seg[n].out = out; rp.seg[n].len = len; rp.seg[n].nsplit = nsplit; rp.seg[n].stride = stride; ++n;
-  };
-  seg(w.slab, g->dWa, d->D * d->H, w.splits, (size_t)w.mstk * d->H);
-  if (d->gated) seg(w.slab + (size_t)d->D * d->H, g->dWb, d->D * d->H, w.splits, (size_t)w.mstk * d->H);
-  seg(w.cs_bab, g->dba, d->D, w.splits, w.mstk);
-  if (d->gated) seg(w.cs_bab + d->D, g->dbb, d->D, w.splits, w.mstk);
-  seg(w.cs_wc, g->dWc, d->D, w.splits, d->D);
-  seg(gA, g->dbc, 1, (int)d->N, 1);         // d(bc) = sum_i dL/dA_i
-  rp.nseg = n;
-  return launch_reduce(rp, st);
+  ReduceList rl;
+  rl.add(w.slab, g->dWa, d->D * d->H, w.splits, (size_t)w.mstk * d->H);
+  if (d->gated) rl.add(w.slab + (size_t)d->D * d->H, g->dWb, d->D * d->H, w.splits, (size_t)w.mstk * d->H);
+  rl.add(w.cs_bab, g->dba, d->D, w.splits, w.mstk);
+  if (d->gated) rl.add(w.cs_bab + d->D, g->dbb, d->D, w.splits, w.mstk);
+  rl.add(w.cs_wc, g->dWc, d->D, w.splits, d->D);
+  rl.add(gA, g->dbc, 1, (int)d->N, 1);         // d(bc) = sum_i dL/dA_i
+  return rl.launch(0, st);
 }
 
 size_t mmf_linear_forward_workspace_bytes(int64_t M, int32_t N, int32_t nseg, int32_t kseg) {
@@ -1123,10 +1122,21 @@ static int linear_bwd_splits(int64_t M, int N, int K) {
   return tn_splits(M, tiles, td);
 }
 
+// mmf_linear_backward's split-K slabs: dW's, then db's
+struct LinearBwdWs { float *slab, *cs; size_t bytes; };
+static LinearBwdWs carve_linear_bwd(void* base, int splits, int N, int K) {
+  Carver c(base);
+  LinearBwdWs w;
+  w.slab = c.take<float>((size_t)splits * N * K);
+  w.cs = c.take<float>((size_t)splits * N);
+  w.bytes = c.off;
+  return w;
+}
+
 size_t mmf_linear_backward_workspace_bytes(int64_t M, int32_t N, int32_t K) {
   const int s = linear_bwd_splits(M, N, K);
   if (s == 1) return 256;
-  return align_up((size_t)s * N * K * 4, 256) + align_up((size_t)s * N * 4, 256);
+  return carve_linear_bwd(nullptr, s, N, K).bytes;
 }
 
 int mmf_linear_backward(const float* dy, const float* const* x_segs, int32_t nseg, int32_t kseg, int64_t M,
@@ -1140,13 +1150,13 @@ int mmf_linear_backward(const float* dy, const float* const* x_segs, int32_t nse
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int splits = linear_bwd_splits(M, N, K);
   if (splits > 1 && (!workspace || workspace_bytes < mmf_linear_backward_workspace_bytes(M, N, K))) return MMF_ERR_WORKSPACE;
-  float* slab = splits > 1 ? static_cast<float*>(workspace) : dW;
-  float* cs = splits > 1 ? reinterpret_cast<float*>(static_cast<char*>(workspace) + align_up((size_t)splits * N * K * 4, 256)) : db;
+  const LinearBwdWs lw = carve_linear_bwd(workspace, splits, N, K);
+  float* slab = splits > 1 ? lw.slab : dW;
+  float* cs = splits > 1 ? lw.cs : db;
 
   TnParams tp{};
   tp.nprob = nseg; tp.K = M; tp.splits = splits; tp.tile = tn_tile_dim(M, 0);
-  int64_t kps = (M + splits - 1) / splits;
-  tp.k_per_split = (int)((kps + 3) / 4 * 4);
+  tp.k_per_split = k_per_split(M, splits);
   for (int i = 0; i < nseg; ++i) {
     if (!x_segs[i]) return MMF_ERR_ARG;
     TnProblem& q = tp.prob[i];
@@ -1157,11 +1167,10 @@ int mmf_linear_backward(const float* dy, const float* const* x_segs, int32_t nse
   }
   if (int e = launch_tn(tp, st)) return e;
   if (splits > 1) {
-    ReduceParams rp{};
-    rp.seg[0] = ReduceSeg{slab, dW, N * K, splits, (size_t)N * K, 0, 0};
-    rp.nseg = 1;
-    if (db) { rp.seg[1] = ReduceSeg{cs, db, N, splits, (size_t)N, 0, 0}; rp.nseg = 2; }
-    if (int e = launch_reduce(rp, st)) return e;
+    ReduceList rl;
+    rl.add(slab, dW, N * K, splits, (size_t)N * K);
+    if (db) rl.add(cs, db, N, splits, (size_t)N);
+    if (int e = rl.launch(0, st)) return e;
   }
   if (dx) {
     if (N % KC != 0) return MMF_ERR_SHAPE;
