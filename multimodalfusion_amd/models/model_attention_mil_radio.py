@@ -55,7 +55,6 @@ class MIL_Attention_fc_surv_radio(MIL_Attention_fc_radio):
         (mmf_amil_nll_step), `reduce_dim`'s backward (mmf_linear_backward).  Gradients are ADDED to .grad (fresh buffers
         where it is None) -- or go to `grad_out`, tensors in self.parameters() order, overwritten unless `accumulate`.
         Returns (hazards, S, Y_hat, A_raw, loss, risk), detached."""
-        from ..ops import HandCtx, LinearCatFn
         if any(not p.requires_grad for p in self.parameters()):
             raise RuntimeError("nll_step needs every parameter of the head to require grad")
         bags = [kwargs[m] for m in self.modalities]
@@ -66,16 +65,15 @@ class MIL_Attention_fc_surv_radio(MIL_Attention_fc_radio):
             rd_out, head_out = (grad_out[:2], grad_out[2:]) if many else (None, grad_out)
         with torch.no_grad():
             if many:
-                ctx = HandCtx((True, True) + (False,) * len(bags))
-                x = LinearCatFn.forward(ctx, self.reduce_dim.weight, self.reduce_dim.bias, *bags)
+                W, b = self.reduce_dim.weight, self.reduce_dim.bias
+                x, saved = ops._linear_cat_fwd_raw(bags, W, b)
                 dx = torch.empty_like(x)
             else:
                 x, dx = bags[0], None
             out = amil_stack_nll_step(self.attention_net_radio, self.classifier, x, self.training, label, c, alpha,
                                       loss_scale, head_out, accumulate, dx_out=dx)
             if many:
-                W, b = self.reduce_dim.weight, self.reduce_dim.bias
-                dW, db = LinearCatFn.backward(ctx, dx)[:2]
+                dW, db, _ = ops._linear_cat_bwd_raw(dx, saved, b is not None, need_dx=False)
                 hand_over_grads((W, b), {W: dW, b: db}, rd_out, accumulate)
         return out
 

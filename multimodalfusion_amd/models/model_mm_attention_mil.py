@@ -179,7 +179,8 @@ class MM_MIL_Attention_fc_surv(MM_MIL_Attention_fc):
         backward calls.  Gradients are ADDED to the parameters' .grad (a parameter whose .grad is
         None receives the fresh buffer, as autograd does) -- or to `grad_out`, tensors in self.parameters() order,
         overwritten unless `accumulate`.  Returns (hazards, S, Y_hat, A_raw dict, loss, risk), detached."""
-        from ..ops import AmilPoolFn, HandCtx, LinearCatFn, _dense_bwd_raw, _dense_fwd_raw
+        from ..ops import (_dense_bwd_raw, _dense_fwd_raw, _linear_cat_bwd_raw, _linear_cat_fwd_raw, _stack_bwd_raw,
+                           _stack_fwd_raw, _xfusion_bwd_raw, _xfusion_fwd_raw)
         order, cols, F = self._concat_layout()
         if self.fusion == "tensor" and not (self.mm.skip and len(order) * self.mm.reduce[0][0][0].weight.shape[0] <= 384):
             raise NotImplementedError("nll_step covers the XlinearFusion configuration the heads use (skip, one patient)")
@@ -192,17 +193,18 @@ class MM_MIL_Attention_fc_surv(MM_MIL_Attention_fc):
                else kwargs["genomic_features"]).device
         grads = {}                                   # parameter -> gradient tensor of this step
 
-        def stack_forward(ctx, seq, x, k):
+        def stack_forward(seq, x, k):
+            """The stack of branch k, its M written into k's slot of feat.  Returns (A_raw, what stack_backward takes)."""
             gated, ps, p_h, p_att = stack_args(seq, tr)
             seed = ops.next_dropout_seed() if tr else 0
-            return ps, AmilPoolFn.forward(ctx, x, *ps, gated, p_h, p_att, seed, M_out=feat[:, cols[k]])[1]
+            saved, _, state = _stack_fwd_raw(x, ps, gated, p_h, p_att, seed, M_out=feat[:, cols[k]])
+            return saved[-1], (ps, saved, state)
 
-        def stack_backward(ctx, ps, g):
-            out = AmilPoolFn.backward(ctx, g, None)
-            for p, gr in zip(ps, out[1:9]):
-                if p is not None:
-                    grads[p] = gr
-            return out[0]
+        def stack_backward(run, g, need_dx=False):
+            ps, saved, state = run
+            dx, ds = _stack_bwd_raw(saved, state, g, None, need_dx)
+            grads.update((p, gr) for p, gr in zip(ps, ds) if p is not None)
+            return dx
 
         with torch.no_grad():
             feat = torch.empty((1, F), dtype=torch.float32, device=dev)
@@ -215,19 +217,16 @@ class MM_MIL_Attention_fc_surv(MM_MIL_Attention_fc):
             if "radio" in order:
                 with branch():
                     xs = [kwargs[m] for m in self.modalities]
-                    ctx_cat = None
+                    cat = None
                     if len(xs) > 1:
-                        ctx_cat = HandCtx((True, True) + (False,) * len(xs))
-                        h_radio = LinearCatFn.forward(ctx_cat, self.reduce_dim.weight, self.reduce_dim.bias, *xs)
+                        h_radio, cat = _linear_cat_fwd_raw(xs, self.reduce_dim.weight, self.reduce_dim.bias)
                     else:
                         h_radio = xs[0]
-                    ctx_r = HandCtx((ctx_cat is not None,) + (True,) * 8 + (False,) * 4)
-                    ps_r, A_raw["radiology"] = stack_forward(ctx_r, self.attention_net_radio, h_radio, "radio")
+                    A_raw["radiology"], run_r = stack_forward(self.attention_net_radio, h_radio, "radio")
             if "path" in order:
-                ctx_p = HandCtx((False,) + (True,) * 8 + (False,) * 4)
                 prev = ops.set_concurrent(True) if fork else None      # see forward(): 224-CU tile plan beside the branches
                 try:
-                    ps_p, A_raw["pathology"] = stack_forward(ctx_p, self.attention_net_WSI, path_x, "path")
+                    A_raw["pathology"], run_p = stack_forward(self.attention_net_WSI, path_x, "path")
                 finally:
                     if fork:
                         ops.set_concurrent(prev)
@@ -256,9 +255,8 @@ class MM_MIL_Attention_fc_surv(MM_MIL_Attention_fc):
                 grads[Wk], grads[bk] = dWk, dbk
                 dslot = lambda k: dfeat[:, cols[k]]
             else:
-                # ---- XlinearFusion (one node's forward / backward bodies, run by hand), classifier[0] + ReLU + Dropout,
-                # then classifier[3] + hazards + loss + their backward in one launch (forward() lines 182-188)
-                from ..ops import XFusionFn
+                # ---- XlinearFusion (XFusionFn's forward / backward), classifier[0] + ReLU + Dropout, then classifier[3] +
+                # hazards + loss + their backward in one launch (forward() lines 182-188)
                 seed_f = ops.next_dropout_seed() if tr else 0
                 word_f = ops._seed_word
                 fus = self.mm
@@ -268,28 +266,26 @@ class MM_MIL_Attention_fc_surv(MM_MIL_Attention_fc):
                         weights += [lin.weight, lin.bias]
                 weights += [fus.encoder1[0].weight, fus.encoder1[0].bias, fus.encoder2[0].weight, fus.encoder2[0].bias]
                 p_f = fus.dropout_rate if tr else 0.0
-                ctx_x = HandCtx((False,) * 3 + (True,) * (len(order) + len(weights)))
-                MMv = XFusionFn.forward(ctx_x, len(order), p_f, seed_f, *[feat[:, cols[k]] for k in order], *weights)
+                MMv, saved_x, state_x = _xfusion_fwd_raw([feat[:, cols[k]] for k in order], weights, p_f, seed_f)
                 c0, c3 = self.classifier[0], self.classifier[3]
                 p_c = self.classifier[2].p if tr else 0.0
                 kind_c = "dropout" if tr else "none"
-                hid = _dense_fwd_raw(MMv, c0.weight, c0.bias, "relu", kind_c, p_c, seed_f & 0xFFFFFFFF, 11, word_f)
+                hid = _dense_fwd_raw(MMv, c0.weight, c0.bias, "relu", kind_c, p_c, seed_f, 11, word_f)
                 dWk, dbk = torch.empty_like(c3.weight), torch.empty_like(c3.bias)
                 hazards, S, Y_hat, loss, risk, dhid = ops.surv_head_nll_step(hid, c3.weight, c3.bias, label, c, alpha,
                                                                              dWk, dbk, loss_scale=loss_scale)
                 grads[c3.weight], grads[c3.bias] = dWk, dbk
                 dMM, grads[c0.weight], grads[c0.bias] = _dense_bwd_raw(dhid, hid, MMv, c0.weight, True, "relu", kind_c, p_c,
-                                                                       seed_f & 0xFFFFFFFF, 11, word=word_f)
-                outx = XFusionFn.backward(ctx_x, dMM)
-                dvs = dict(zip(order, outx[3:3 + len(order)]))
-                for p_, g_ in zip(weights, outx[3 + len(order):]):
-                    grads[p_] = g_
+                                                                       seed_f, 11, word=word_f)
+                dv, dw = _xfusion_bwd_raw(dMM, saved_x, state_x)
+                dvs = dict(zip(order, dv))
+                grads.update(zip(weights, dw))
                 dslot = lambda k: dvs[k]
             if fork:
                 side.wait_stream(cur)
             # ---- backward: the pathology stack on this stream, the small branches beside it
             if "path" in order:
-                stack_backward(ctx_p, ps_p, dslot("path"))
+                stack_backward(run_p, dslot("path"))
             if "omic" in order:
                 with branch():
                     g = dslot("omic")
@@ -303,10 +299,10 @@ class MM_MIL_Attention_fc_surv(MM_MIL_Attention_fc):
                             grads[lin.bias] = db
             if "radio" in order:
                 with branch():
-                    dh = stack_backward(ctx_r, ps_r, dslot("radio"))
-                    if ctx_cat is not None:
-                        out = LinearCatFn.backward(ctx_cat, dh)
-                        grads[self.reduce_dim.weight], grads[self.reduce_dim.bias] = out[0], out[1]
+                    dh = stack_backward(run_r, dslot("radio"), need_dx=cat is not None)
+                    if cat is not None:
+                        W, b = self.reduce_dim.weight, self.reduce_dim.bias
+                        grads[W], grads[b], _ = _linear_cat_bwd_raw(dh, cat, b is not None, need_dx=False)
             if fork:
                 cur.wait_stream(side)
             # ---- hand the gradients over (parameters of branches outside `mode` took no part: no gradient, as in autograd)

@@ -95,15 +95,20 @@ def sync_words(device=None):
     return t
 
 
-def _amil_desc(N, L, H, D, gated, W1, b1, Wa, ba, Wb, bb, Wc, bc, p_h, p_att, seed, seed_word, concurrent=None):
-    sw = sync_words(W1.device if W1 is not None else None)
+def _amil_desc(stack, N, L, H, D, gated, p_h, p_att, seed, seed_word, concurrent=None):
+    """The mmf_amil_desc of one call on stack = (W1, b1, Wa, ba, Wb, bb, Wc, bc).  concurrent: the hint a backward takes
+    from its forward (default: the current one).  The scorer alone (W1 = None: mmf_attn_net_*) gets no tick words, and
+    concurrent / gemm stay 0: those entry points read none of them."""
+    W1, b1, Wa, ba, Wb, bb, Wc, bc = stack
+    full = W1 is not None
+    sw = sync_words(W1.device) if full else None
     return AmilDesc(sync=ptr(sw), sync_words=SYNC_WORDS if sw is not None else 0,
                     N=N, L=L, H=H, D=D, gated=1 if gated else 0,
                     W1=ptr(W1), b1=ptr(b1), Wa=ptr(Wa), ba=ptr(ba),
                     Wb=ptr(Wb) if gated else None, bb=ptr(bb) if gated else None,
                     Wc=ptr(Wc), bc=ptr(bc), p_h=float(p_h), p_att=float(p_att), seed=int(seed) & 0xFFFFFFFF,
-                    seed_dev=ptr(seed_word), trace=_trace, concurrent=_concurrent if concurrent is None else concurrent,
-                    gemm=_gemm)
+                    seed_dev=ptr(seed_word), trace=_trace,
+                    concurrent=(_concurrent if concurrent is None else concurrent) if full else 0, gemm=_gemm if full else 0)
 
 
 def next_dropout_seed() -> int:
@@ -121,93 +126,133 @@ def _f32c(t):
     return t.contiguous()
 
 
-class AmilPoolFn(torch.autograd.Function):
-    """(x, attention-stack params) -> (M [1 x H], A_raw [1 x N]).
+def _stack_operands(stack, L, head=None, what="bag", fused_head=False):
+    """stack (W1, b1, Wa, ba, Wb, bb, Wc, bc) and the classifier head (Wk, bk) behind it, if any, as contiguous fp32
+    (model.half() / .double() must not reach the fp32 kernels), checked against the bag width L; fused_head: the head
+    runs in the tail of the pooling merge kernel (K <= 32).  Returns (stack, head, H, D)."""
+    stack = tuple(map(_f32c, stack))
+    head = None if head is None else tuple(map(_f32c, head))
+    W1, Wa, Wc = stack[0], stack[2], stack[6]
+    H, D = W1.shape[0], Wa.shape[0]
+    if (W1.shape[1] != L or Wa.shape[1] != H or Wc.numel() != D
+            or head is not None and (head[0].shape[1] != H or fused_head and head[0].shape[0] > 32)):
+        raise _lib.MmfError(f"attention stack {'' if head is None else '/ classifier '}shapes do not match the {what}")
+    return stack, head, H, D
 
-    Mirrors `A, h = attention_net(x); A = A.T; A_raw = A; M = softmax(A) @ h`
-    (models/model_attention_mil_path.py:52-56 in the reference).
-    """
+
+def _bag_operands(x, stack, gated, p_h, p_att, seed, seed_word, head=None, fused_head=False):
+    """One bag x [N x L] and its stack for a call: a bf16 bag selects the bf16-storage kernels (include/mmf_amil.h:
+    mmf_amil_bf16_*), the parameters stay fp32.  Returns (bf16, x, stack, head, the call's mmf_amil_desc)."""
+    bf16 = x.dtype == torch.bfloat16
+    x = x.contiguous() if bf16 else _f32c(x)
+    if x.dim() != 2:
+        raise _lib.MmfError(f"bag must be [N x L], got {tuple(x.shape)}")
+    N, L = x.shape
+    stack, head, H, D = _stack_operands(stack, L, head, "bag", fused_head)
+    return bf16, x, stack, head, _amil_desc(stack, N, L, H, D, gated, p_h, p_att, seed, seed_word)
+
+
+def _stack_workspace(d, bf16, dev, infer=False):
+    """(bytes, uint8 tensor) of a one-bag call's workspace: the forward's size, or the no-save kernels' (infer)."""
+    l = lib()
+    if infer:
+        query = l.mmf_amil_bf16_infer_workspace_bytes if bf16 else l.mmf_amil_infer_workspace_bytes
+    else:
+        query = l.mmf_amil_bf16_workspace_bytes if bf16 else l.mmf_amil_workspace_bytes
+    nbytes = query(d.N, d.L, d.H, d.D, d.gated)
+    return nbytes, torch.empty(nbytes, dtype=torch.uint8, device=dev)
+
+
+def _stack_grads(x, stack, gated, need_dx):
+    """Fresh gradient buffers of a stack's backward -- None where the stack has no tensor (the scorer alone: W1, b1; an
+    ungated stack: Wb, bb) -- and of the bag when need_dx.  Returns (the eight gradients, dx, their mmf_amil_grads)."""
+    ds = tuple(None if t is None or not gated and i in (4, 5) else torch.empty_like(t) for i, t in enumerate(stack))
+    dx = torch.empty_like(x) if need_dx else None
+    return ds, dx, AmilGrads(*map(ptr, ds), ptr(dx))
+
+
+def _check_dx(bf16, need_dx):
+    if bf16 and need_dx:
+        raise _lib.MmfError("a bf16 bag is a leaf: no input gradient on the bf16 path")
+
+
+def _stack_fwd_raw(x, stack, gated, p_h=0.0, p_att=0.0, seed=0, head=None, infer=False, M_out=None):
+    """`A, h = attention_net(x); A_raw = A.T; M = softmax(A_raw) @ h` (models/model_attention_mil_path.py:52-56) on one
+    bag x [N x L] (fp32; bf16: the bf16-storage kernels) in one call: mmf_amil[_bf16]_infer (infer: nothing is kept for a
+    backward), mmf_amil[_bf16]_forward, or with head = (Wk, bk) mmf_amil_head_forward, the classifier / hazard head (:58-61)
+    in the tail of the pooling merge kernel (K > 32: the forward + mmf_surv_head_forward).  M_out: the [1 x H] tensor M goes
+    to.  Returns (saved, hd, state) for _stack_bwd_raw: saved = (x, *stack, M, A_raw) as the kernels took them; hd = (Wk,
+    bk, logits / hazards / S [3 x 1 x K], Y_hat) or None; state = (bf16, desc arguments, workspace, seed word, concurrent)
+    as of this forward -- the backward runs later, on the autograd thread after the caller has lowered the hint."""
+    word = None if infer else _seed_word
+    bf16, x, stack, head, d = _bag_operands(x, stack, gated, p_h, p_att, seed, word, head)
+    N, H = d.N, d.H
+    dev = x.device
+    nbytes, ws = _stack_workspace(d, bf16, dev, infer)
+    M = torch.empty((1, H), dtype=torch.float32, device=dev) if M_out is None else M_out
+    A_raw = torch.empty((1, N), dtype=torch.float32, device=dev)
+    hd = None
+    if head is not None:
+        Wk, bk = head
+        K = Wk.shape[0]
+        out = torch.empty((3, 1, K), dtype=torch.float32, device=dev)        # logits, hazards, S
+        Y_hat = torch.empty((1, 1), dtype=torch.int64, device=dev)
+        hd = (Wk, bk, out, Y_hat)
+    l = lib()
+    if hd is not None and K <= 32:
+        sh = SurvHead(Wk=ptr(Wk), bk=ptr(bk), K=K, logits=ptr(out[0]), hazards=ptr(out[1]), S=ptr(out[2]),
+                      Y_hat=ptr(Y_hat), risk=None)
+        check(l.mmf_amil_head_forward(C.byref(d), ptr(x), 1 if bf16 else 0, ptr(ws), nbytes, C.byref(sh), ptr(M),
+                                      ptr(A_raw), stream_ptr()), "mmf_amil_head_forward")
+    else:
+        if infer:
+            fwd_fn, name = ((l.mmf_amil_bf16_infer, "mmf_amil_bf16_infer") if bf16 else (l.mmf_amil_infer, "mmf_amil_infer"))
+        else:
+            fwd_fn, name = ((l.mmf_amil_bf16_forward, "mmf_amil_bf16_forward") if bf16
+                            else (l.mmf_amil_forward, "mmf_amil_forward"))
+        check(fwd_fn(C.byref(d), ptr(x), ptr(ws), nbytes, ptr(M), ptr(A_raw), stream_ptr()), name)
+        if hd is not None:
+            _surv_head_fwd_raw(M, Wk, bk, (out[0], out[1], out[2], Y_hat))
+    return (x, *stack, M, A_raw), hd, (bf16, (N, d.L, H, d.D, gated, p_h, p_att, seed), ws, word, _concurrent)
+
+
+def _stack_bwd_raw(saved, state, gM, gA, need_dx):
+    """mmf_amil[_bf16]_backward of a _stack_fwd_raw call (saved, state: what it returned); gM, gA: the gradients of M and
+    A_raw, None where none reaches it.  Returns (dx or None, the eight stack gradients: None for an ungated Wb, bb)."""
+    x, *stack, M, A_raw = saved
+    bf16, cfg, ws, word, concurrent = state
+    _check_dx(bf16, need_dx)
+    gM = torch.zeros((1, cfg[2]), dtype=torch.float32, device=x.device) if gM is None else _f32c(gM)
+    gA = _f32c(gA)
+    d = _amil_desc(stack, *cfg, word, concurrent)
+    ds, dx, g = _stack_grads(x, stack, cfg[4], need_dx)
+    bwd_fn, name = ((lib().mmf_amil_bf16_backward, "mmf_amil_bf16_backward") if bf16
+                    else (lib().mmf_amil_backward, "mmf_amil_backward"))
+    check(bwd_fn(C.byref(d), ptr(x), ptr(ws), ws.numel(), ptr(M), ptr(A_raw), ptr(gM), ptr(gA), C.byref(g), stream_ptr()),
+          name)
+    return dx, ds
+
+
+class AmilPoolFn(torch.autograd.Function):
+    """(x, attention-stack params) -> (M [1 x H], A_raw [1 x N]): _stack_fwd_raw / _stack_bwd_raw."""
 
     @staticmethod
-    def forward(ctx, x, W1, b1, Wa, ba, Wb, bb, Wc, bc, gated, p_h, p_att, seed, M_out=None):
-        # (M_out: only for callers that run the node by hand -- the multimodal step lets the stack write its embedding
-        # straight into its slot of the concatenated feature vector)
-        # a bf16 bag selects the bf16-storage kernels (include/mmf_amil.h: mmf_amil_bf16_*); parameters stay fp32
-        bf16 = x.dtype == torch.bfloat16
-        x = x.contiguous() if bf16 else _f32c(x)
-        W1, b1, Wa, ba, Wc, bc = map(_f32c, (W1, b1, Wa, ba, Wc, bc))
-        Wb, bb = _f32c(Wb), _f32c(bb)
-        if x.dim() != 2:
-            raise _lib.MmfError(f"bag must be [N x L], got {tuple(x.shape)}")
-        N, L = x.shape
-        H, D = W1.shape[0], Wa.shape[0]
-        if W1.shape[1] != L or Wa.shape[1] != H or Wc.numel() != D:
-            raise _lib.MmfError("attention stack shapes do not match the bag")
-        word = _seed_word
-        d = _amil_desc(N, L, H, D, gated, W1, b1, Wa, ba, Wb, bb, Wc, bc, p_h, p_att, seed, word)
-        l = lib()
-        ws_fn, fwd_fn = ((l.mmf_amil_bf16_workspace_bytes, l.mmf_amil_bf16_forward) if bf16
-                         else (l.mmf_amil_workspace_bytes, l.mmf_amil_forward))
-        nbytes = ws_fn(N, L, H, D, d.gated)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
-        M = torch.empty((1, H), dtype=torch.float32, device=x.device) if M_out is None else M_out
-        A_raw = torch.empty((1, N), dtype=torch.float32, device=x.device)
-        check(fwd_fn(C.byref(d), ptr(x), ptr(ws), nbytes, ptr(M), ptr(A_raw), stream_ptr()),
-              "mmf_amil_bf16_forward" if bf16 else "mmf_amil_forward")
-        ctx.bf16 = bf16
-        ctx.desc_args = (N, L, H, D, bool(gated), float(p_h), float(p_att), int(seed) & 0xFFFFFFFF)
-        ctx.seed_word = word
-        ctx.concurrent = _concurrent          # the backward runs on the autograd thread, after the caller has lowered the hint
-        ctx.ws = ws
-        ctx.save_for_backward(x, W1, b1, Wa, ba, Wb, bb, Wc, bc, M, A_raw)
+    def forward(ctx, x, W1, b1, Wa, ba, Wb, bb, Wc, bc, gated, p_h, p_att, seed):
+        saved, _, ctx.state = _stack_fwd_raw(x, (W1, b1, Wa, ba, Wb, bb, Wc, bc), gated, p_h, p_att, seed)
+        ctx.save_for_backward(*saved)
         ctx.set_materialize_grads(False)      # an unused output (A_raw, mostly) must not cost a zero-fill launch
-        return M, A_raw
+        return saved[-2], saved[-1]
 
     @staticmethod
     def backward(ctx, gM, gA):
-        x, W1, b1, Wa, ba, Wb, bb, Wc, bc, M, A_raw = ctx.saved_tensors
-        N, L, H, D, gated, p_h, p_att, seed = ctx.desc_args
-        dev = x.device
-        gM = torch.zeros((1, H), dtype=torch.float32, device=dev) if gM is None else _f32c(gM)
-        gA = _f32c(gA) if gA is not None else None
-        d = _amil_desc(N, L, H, D, gated, W1, b1, Wa, ba, Wb, bb, Wc, bc, p_h, p_att, seed, ctx.seed_word, ctx.concurrent)
-        new = lambda ref: torch.empty_like(ref)
-        dW1, db1, dWa, dba, dWc, dbc = new(W1), new(b1), new(Wa), new(ba), new(Wc), new(bc)
-        dWb, dbb = (new(Wb), new(bb)) if gated else (None, None)
-        if ctx.bf16 and ctx.needs_input_grad[0]:
-            raise _lib.MmfError("a bf16 bag is a leaf: no input gradient on the bf16 path")
-        dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
-        g = AmilGrads(dW1=ptr(dW1), db1=ptr(db1), dWa=ptr(dWa), dba=ptr(dba), dWb=ptr(dWb), dbb=ptr(dbb),
-                      dWc=ptr(dWc), dbc=ptr(dbc), dx=ptr(dx))
-        ws = ctx.ws
-        bwd_fn = lib().mmf_amil_bf16_backward if ctx.bf16 else lib().mmf_amil_backward
-        check(bwd_fn(C.byref(d), ptr(x), ptr(ws), ws.numel(), ptr(M), ptr(A_raw),
-                     ptr(gM), ptr(gA), C.byref(g), stream_ptr()), "mmf_amil_bf16_backward" if ctx.bf16 else "mmf_amil_backward")
-        return dx, dW1, db1, dWa, dba, dWb, dbb, dWc, dbc, None, None, None, None
+        dx, ds = _stack_bwd_raw(ctx.saved_tensors, ctx.state, gM, gA, ctx.needs_input_grad[0])
+        return (dx, *ds, None, None, None, None)
 
 
 def amil_infer(x, W1, b1, Wa, ba, Wb, bb, Wc, bc, gated):
     """Forward-only attention stack (include/mmf_amil.h: mmf_amil[_bf16]_infer): nothing is saved for a backward."""
-    bf16 = x.dtype == torch.bfloat16
-    x = x.contiguous() if bf16 else _f32c(x)
-    W1, b1, Wa, ba, Wc, bc = map(_f32c, (W1, b1, Wa, ba, Wc, bc))
-    Wb, bb = _f32c(Wb), _f32c(bb)
-    if x.dim() != 2:
-        raise _lib.MmfError(f"bag must be [N x L], got {tuple(x.shape)}")
-    N, L = x.shape
-    H, D = W1.shape[0], Wa.shape[0]
-    if W1.shape[1] != L or Wa.shape[1] != H or Wc.numel() != D:
-        raise _lib.MmfError("attention stack shapes do not match the bag")
-    d = _amil_desc(N, L, H, D, gated, W1, b1, Wa, ba, Wb, bb, Wc, bc, 0.0, 0.0, 0, None)
-    l = lib()
-    ws_fn, fn, name = ((l.mmf_amil_bf16_infer_workspace_bytes, l.mmf_amil_bf16_infer, "mmf_amil_bf16_infer") if bf16
-                       else (l.mmf_amil_infer_workspace_bytes, l.mmf_amil_infer, "mmf_amil_infer"))
-    nbytes = ws_fn(N, L, H, D, d.gated)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
-    M = torch.empty((1, H), dtype=torch.float32, device=x.device)
-    A_raw = torch.empty((1, N), dtype=torch.float32, device=x.device)
-    check(fn(C.byref(d), ptr(x), ptr(ws), nbytes, ptr(M), ptr(A_raw), stream_ptr()), name)
-    return M, A_raw
+    saved = _stack_fwd_raw(x, (W1, b1, Wa, ba, Wb, bb, Wc, bc), gated, infer=True)[0]
+    return saved[-2], saved[-1]
 
 
 def amil_pool(x, W1, b1, Wa, ba, Wb, bb, Wc, bc, gated, p_h=0.0, p_att=0.0, seed=0):
@@ -223,75 +268,21 @@ class AmilHeadFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, W1, b1, Wa, ba, Wb, bb, Wc, bc, Wk, bk, gated, p_h, p_att, seed):
-        bf16 = x.dtype == torch.bfloat16
-        x = x.contiguous() if bf16 else _f32c(x)
-        W1, b1, Wa, ba, Wc, bc, Wk, bk = map(_f32c, (W1, b1, Wa, ba, Wc, bc, Wk, bk))   # model.half() / .double() must not
-        Wb, bb = _f32c(Wb), _f32c(bb)                                                    # reach the fp32 kernels
-        if x.dim() != 2:
-            raise _lib.MmfError(f"bag must be [N x L], got {tuple(x.shape)}")
-        N, L = x.shape
-        H, D, K = W1.shape[0], Wa.shape[0], Wk.shape[0]
-        if W1.shape[1] != L or Wa.shape[1] != H or Wc.numel() != D or Wk.shape[1] != H:
-            raise _lib.MmfError("attention stack / classifier shapes do not match the bag")
-        seed = int(seed) & 0xFFFFFFFF
-        word = _seed_word
-        d = _amil_desc(N, L, H, D, gated, W1, b1, Wa, ba, Wb, bb, Wc, bc, p_h, p_att, seed, word)
-        l = lib()
-        nbytes = (l.mmf_amil_bf16_workspace_bytes if bf16 else l.mmf_amil_workspace_bytes)(N, L, H, D, d.gated)
-        dev = x.device
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        M = torch.empty((1, H), dtype=torch.float32, device=dev)
-        A_raw = torch.empty((1, N), dtype=torch.float32, device=dev)
-        out = torch.empty((3, 1, K), dtype=torch.float32, device=dev)        # logits, hazards, S
-        Y_hat = torch.empty((1, 1), dtype=torch.int64, device=dev)
-        st = stream_ptr()
-        if K <= 32:      # the head runs as the tail of the pooling merge kernel: one launch less
-            hd = SurvHead(Wk=ptr(Wk), bk=ptr(bk), K=K, logits=ptr(out[0]), hazards=ptr(out[1]), S=ptr(out[2]),
-                          Y_hat=ptr(Y_hat), risk=None)
-            check(l.mmf_amil_head_forward(C.byref(d), ptr(x), 1 if bf16 else 0, ptr(ws), nbytes, C.byref(hd), ptr(M),
-                                          ptr(A_raw), st), "mmf_amil_head_forward")
-        else:
-            fwd_fn = l.mmf_amil_bf16_forward if bf16 else l.mmf_amil_forward
-            check(fwd_fn(C.byref(d), ptr(x), ptr(ws), nbytes, ptr(M), ptr(A_raw), st), "mmf_amil_forward")
-            check(l.mmf_surv_head_forward(ptr(M), ptr(Wk), ptr(bk), 1, H, K, ptr(out[0]), ptr(out[1]), ptr(out[2]),
-                                          ptr(Y_hat), st), "mmf_surv_head_forward")
-        ctx.cfg = (N, L, H, D, K, bool(gated), float(p_h), float(p_att), seed, bf16)
-        ctx.seed_word = word
-        ctx.ws = ws
-        ctx.save_for_backward(x, W1, b1, Wa, ba, Wb, bb, Wc, bc, Wk, M, A_raw, out)
+        saved, (Wk, _, out, Y_hat), ctx.state = _stack_fwd_raw(x, (W1, b1, Wa, ba, Wb, bb, Wc, bc), gated, p_h, p_att,
+                                                               seed, head=(Wk, bk))
+        ctx.save_for_backward(Wk, out, *saved)
         ctx.mark_non_differentiable(Y_hat)
         ctx.set_materialize_grads(False)      # no zero-fill launches for the outputs the loss does not use (A_raw, Y_hat)
-        return out[1], out[2], Y_hat, A_raw
+        return out[1], out[2], Y_hat, saved[-1]
 
     @staticmethod
     def backward(ctx, gH, gS, _gY, gA):
-        x, W1, b1, Wa, ba, Wb, bb, Wc, bc, Wk, M, A_raw, out = ctx.saved_tensors
-        N, L, H, D, K, gated, p_h, p_att, seed, bf16 = ctx.cfg
-        if bf16 and ctx.needs_input_grad[0]:
-            raise _lib.MmfError("a bf16 bag is a leaf: no input gradient on the bf16 path")
-        dev = x.device
-        l = lib()
-        st = stream_ptr()
-        gH = _f32c(gH) if gH is not None else None
-        gS = _f32c(gS) if gS is not None else None
-        gA = _f32c(gA) if gA is not None else None
-        dM = torch.empty((1, H), dtype=torch.float32, device=dev)
-        dWk = torch.empty_like(Wk)
-        dbk = torch.empty((K,), dtype=torch.float32, device=dev)
-        check(l.mmf_surv_head_backward(ptr(gH), ptr(gS), ptr(out[1]), ptr(M), ptr(Wk), 1, H, K,
-                                       ptr(dM), ptr(dWk), ptr(dbk), st), "mmf_surv_head_backward")
-        d = _amil_desc(N, L, H, D, gated, W1, b1, Wa, ba, Wb, bb, Wc, bc, p_h, p_att, seed, ctx.seed_word)
-        new = torch.empty_like
-        dW1, db1, dWa, dba, dWc, dbc = new(W1), new(b1), new(Wa), new(ba), new(Wc), new(bc)
-        dWb, dbb = (new(Wb), new(bb)) if gated else (None, None)
-        dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
-        g = AmilGrads(dW1=ptr(dW1), db1=ptr(db1), dWa=ptr(dWa), dba=ptr(dba), dWb=ptr(dWb), dbb=ptr(dbb),
-                      dWc=ptr(dWc), dbc=ptr(dbc), dx=ptr(dx))
-        ws = ctx.ws
-        bwd_fn = l.mmf_amil_bf16_backward if bf16 else l.mmf_amil_backward
-        check(bwd_fn(C.byref(d), ptr(x), ptr(ws), ws.numel(), ptr(M), ptr(A_raw), ptr(dM), ptr(gA), C.byref(g), st),
-              "mmf_amil_backward")
-        return dx, dW1, db1, dWa, dba, dWb, dbb, dWc, dbc, dWk, dbk, None, None, None, None
+        Wk, out, *saved = ctx.saved_tensors
+        need_dx = ctx.needs_input_grad[0]
+        _check_dx(ctx.state[0], need_dx)
+        dM, dWk, dbk = _surv_head_bwd_raw(gH, gS, out[1], saved[-2], Wk)
+        dx, ds = _stack_bwd_raw(saved, ctx.state, dM, gA, need_dx)
+        return (dx, *ds, dWk, dbk, None, None, None, None)
 
 
 def _check_grad_buffers(pairs):
@@ -300,19 +291,15 @@ def _check_grad_buffers(pairs):
             raise _lib.MmfError("gradient buffers must be contiguous float32 tensors shaped like their parameters")
 
 
-def _stack_step_operands(stack, Wk, bk, gated, grads, L, what):
-    """stack (W1, b1, Wa, ba, Wb, bb, Wc, bc) and classifier (Wk, bk) of a one-call step as contiguous fp32, checked
-    against the bag width L and the gradient buffers grads (dW1, ..., dbk).  Returns (the ten operands, AmilGrads with no
-    dx)."""
-    W1, b1, Wa, ba, Wb, bb, Wc, bc, Wk, bk = ws = tuple(map(_f32c, (*stack, Wk, bk)))
-    H, D = W1.shape[0], Wa.shape[0]
-    if W1.shape[1] != L or Wa.shape[1] != H or Wc.numel() != D or Wk.shape[1] != H or Wk.shape[0] > 32:
-        raise _lib.MmfError(f"attention stack / classifier shapes do not match the {what}")
+def _step_grads(stack, Wk, bk, gated, grads):
+    """The gradient buffers grads (dW1, ..., dbc, dWk, dbk) of a one-call step, checked against the stack and classifier
+    (_stack_operands).  Returns their AmilGrads, with no dx."""
+    W1, b1, Wa, ba, Wb, bb, Wc, bc = stack
     dW1, db1, dWa, dba, dWb, dbb, dWc, dbc, dWk, dbk = grads
     _check_grad_buffers(((dW1, W1), (db1, b1), (dWa, Wa), (dba, ba), (dWc, Wc), (dbc, bc), (dWk, Wk), (dbk, bk)) +
                         (((dWb, Wb), (dbb, bb)) if gated else ()))
-    return ws, AmilGrads(dW1=ptr(dW1), db1=ptr(db1), dWa=ptr(dWa), dba=ptr(dba), dWb=ptr(dWb) if gated else None,
-                         dbb=ptr(dbb) if gated else None, dWc=ptr(dWc), dbc=ptr(dbc), dx=None)
+    return AmilGrads(dW1=ptr(dW1), db1=ptr(db1), dWa=ptr(dWa), dba=ptr(dba), dWb=ptr(dWb) if gated else None,
+                     dbb=ptr(dbb) if gated else None, dWc=ptr(dWc), dbc=ptr(dbc), dx=None)
 
 
 def _nll_head(Wk, bk, Y, c, alpha, eps, loss_scale, dWk, dbk, accumulate, dev, G=0):
@@ -352,26 +339,18 @@ def amil_nll_step(x, stack, Wk, bk, gated, Y, c, alpha, grads, loss_scale=1.0, a
     stack = (W1, b1, Wa, ba, Wb, bb, Wc, bc); grads = the matching gradient tensors (dW1, db1, dWa, dba, dWb, dbb, dWc,
     dbc, dWk, dbk), written with d(loss * loss_scale) -- added to when `accumulate`.  Y, c: device tensors [1].
     Returns (hazards [1 x K], S [1 x K], Y_hat [1 x 1], A_raw [1 x N], loss (0-dim, unscaled), risk [1])."""
-    bf16 = x.dtype == torch.bfloat16
-    x = x.contiguous() if bf16 else _f32c(x)
-    if x.dim() != 2:
-        raise _lib.MmfError(f"bag must be [N x L], got {tuple(x.shape)}")
-    N, L = x.shape
-    (W1, b1, Wa, ba, Wb, bb, Wc, bc, Wk, bk), g = _stack_step_operands(stack, Wk, bk, gated, grads, L, "bag")
-    H, D = W1.shape[0], Wa.shape[0]
+    bf16, x, stack, (Wk, bk), d = _bag_operands(x, stack, gated, p_h, p_att, seed, _seed_word, (Wk, bk), fused_head=True)
+    g = _step_grads(stack, Wk, bk, gated, grads)
     dev = x.device
     hd, tg, (hz, S, Y_hat, loss, risk), _keep = _nll_head(Wk, bk, Y, c, alpha, eps, loss_scale, grads[8], grads[9],
                                                           accumulate, dev)
-    d = _amil_desc(N, L, H, D, gated, W1, b1, Wa, ba, Wb, bb, Wc, bc, p_h, p_att, seed, _seed_word)
-    l = lib()
-    nbytes = (l.mmf_amil_bf16_workspace_bytes if bf16 else l.mmf_amil_workspace_bytes)(N, L, H, D, d.gated)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    A_raw = torch.empty((1, N), dtype=torch.float32, device=dev)
+    nbytes, ws = _stack_workspace(d, bf16, dev)
+    A_raw = torch.empty((1, d.N), dtype=torch.float32, device=dev)
     if dx is not None and (bf16 or dx.dtype != torch.float32 or dx.shape != x.shape or not dx.is_contiguous()):
         raise _lib.MmfError("dx must be a contiguous float32 tensor shaped like an fp32 bag")
     g.dx = ptr(dx)
-    check(l.mmf_amil_nll_step(C.byref(d), ptr(x), 1 if bf16 else 0, ptr(ws), nbytes, C.byref(hd), C.byref(tg),
-                              ptr(A_raw), C.byref(g), stream_ptr()), "mmf_amil_nll_step")
+    check(lib().mmf_amil_nll_step(C.byref(d), ptr(x), 1 if bf16 else 0, ptr(ws), nbytes, C.byref(hd), C.byref(tg),
+                                  ptr(A_raw), C.byref(g), stream_ptr()), "mmf_amil_nll_step")
     return hz, S, Y_hat, A_raw, loss, risk
 
 
@@ -434,12 +413,12 @@ def amil_nll_step_group(x_cat, sizes, stack, Wk, bk, gated, Y, c, alpha, grads, 
     if x_cat.dim() != 2 or x_cat.shape[0] != sum(sizes):
         raise _lib.MmfError(f"x_cat must be [sum N x L] = [{sum(sizes)} x L], got {tuple(x_cat.shape)}")
     R, L = x_cat.shape
-    (W1, b1, Wa, ba, Wb, bb, Wc, bc, Wk, bk), g = _stack_step_operands(stack, Wk, bk, gated, grads, L, "bags")
-    H, D = W1.shape[0], Wa.shape[0]
+    stack, (Wk, bk), H, D = _stack_operands(stack, L, (Wk, bk), "bags", fused_head=True)
+    g = _step_grads(stack, Wk, bk, gated, grads)
     dev = x_cat.device
     hd, tg, (hz, S, Y_hat, loss, risk), _keep = _nll_head(Wk, bk, Y, c, alpha, eps, loss_scale, grads[8], grads[9],
                                                           accumulate, dev, G)
-    d = _amil_desc(R, L, H, D, gated, W1, b1, Wa, ba, Wb, bb, Wc, bc, p_h, p_att, 0, _seed_word)
+    d = _amil_desc(stack, R, L, H, D, gated, p_h, p_att, 0, _seed_word)
     l = lib()
     nbytes = l.mmf_amil_group_workspace_bytes(offs, G, L, H, D, d.gated)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
@@ -472,8 +451,8 @@ def radio_nll_step_group(xs, sizes, Wr, br, stack, Wk, bk, gated, Y, c, alpha, g
     sizes, Y, c, offs, grp = _group_table(sizes, R, Y, c, seeds)
     G = len(sizes)
     Wr, br = _f32c(Wr), _f32c(br)
-    (W1, b1, Wa, ba, Wb, bb, Wc, bc, Wk, bk), g = _stack_step_operands(stack, Wk, bk, gated, grads[2:], kseg, "bags")
-    H, D = W1.shape[0], Wa.shape[0]
+    stack, (Wk, bk), H, D = _stack_operands(stack, kseg, (Wk, bk), "bags", fused_head=True)
+    g = _step_grads(stack, Wk, bk, gated, grads[2:])
     if tuple(Wr.shape) != (kseg, nseg * kseg) or tuple(br.shape) != (kseg,):
         raise _lib.MmfError(f"reduce_dim must be [{kseg} x {nseg * kseg}] with a [{kseg}] bias for {nseg} modalities of {kseg}")
     dWr, dbr = grads[:2]
@@ -481,7 +460,7 @@ def radio_nll_step_group(xs, sizes, Wr, br, stack, Wk, bk, gated, Y, c, alpha, g
     dev = xs[0].device
     hd, tg, (hz, S, Y_hat, loss, risk), _keep = _nll_head(Wk, bk, Y, c, alpha, eps, loss_scale, grads[10], grads[11],
                                                           accumulate, dev, G)
-    d = _amil_desc(R, kseg, H, D, gated, W1, b1, Wa, ba, Wb, bb, Wc, bc, p_h, p_att, 0, _seed_word)
+    d = _amil_desc(stack, R, kseg, H, D, gated, p_h, p_att, 0, _seed_word)
     segs = (C.c_void_p * nseg)(*[ptr(x) for x in xs])
     rd = _lib.RadioReduce(x=segs, nseg=nseg, kseg=kseg, W=ptr(Wr), bias=ptr(br), dW=ptr(dWr), db=ptr(dbr))
     l = lib()
@@ -507,49 +486,81 @@ class AttnNetFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, Wa, ba, Wb, bb, Wc, bc, gated, p_att, seed):
-        x, Wa, ba, Wc, bc = map(_f32c, (x, Wa, ba, Wc, bc))
-        Wb, bb = _f32c(Wb), _f32c(bb)
+        x, Wa, ba, Wb, bb, Wc, bc = map(_f32c, (x, Wa, ba, Wb, bb, Wc, bc))
         if x.dim() != 2 or Wa.shape[1] != x.shape[1] or Wc.shape[0] != 1 or Wc.shape[1] != Wa.shape[0]:
             raise _lib.MmfError("Attn_Net: x must be [N x L] and the scorer must have n_classes = 1")
         N, H = x.shape
         D = Wa.shape[0]
-        word = _seed_word
-        d = AmilDesc(N=N, L=H, H=H, D=D, gated=1 if gated else 0, W1=None, b1=None, Wa=ptr(Wa), ba=ptr(ba),
-                     Wb=ptr(Wb) if gated else None, bb=ptr(bb) if gated else None, Wc=ptr(Wc), bc=ptr(bc),
-                     p_h=0.0, p_att=float(p_att), seed=int(seed) & 0xFFFFFFFF, seed_dev=ptr(word), trace=_trace)
+        cfg, word = (N, H, H, D, gated, 0.0, p_att, seed), _seed_word
+        d = _amil_desc((None, None, Wa, ba, Wb, bb, Wc, bc), *cfg, word)
         l = lib()
         nbytes = l.mmf_attn_net_workspace_bytes(N, H, D, d.gated)
         ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
         A = torch.empty((N, 1), dtype=torch.float32, device=x.device)
         check(l.mmf_attn_net_forward(C.byref(d), ptr(x), ptr(ws), nbytes, ptr(A), stream_ptr()), "mmf_attn_net_forward")
-        ctx.cfg = (N, H, D, bool(gated), float(p_att), int(seed) & 0xFFFFFFFF)
-        ctx.seed_word = word
-        ctx.ws = ws
+        ctx.state = (cfg, ws, word)
         ctx.save_for_backward(x, Wa, ba, Wb, bb, Wc, bc)
         return A
 
     @staticmethod
     def backward(ctx, gA):
-        x, Wa, ba, Wb, bb, Wc, bc = ctx.saved_tensors
-        N, H, D, gated, p_att, seed = ctx.cfg
-        gA = _f32c(gA).reshape(N)
-        d = AmilDesc(N=N, L=H, H=H, D=D, gated=1 if gated else 0, W1=None, b1=None, Wa=ptr(Wa), ba=ptr(ba),
-                     Wb=ptr(Wb) if gated else None, bb=ptr(bb) if gated else None, Wc=ptr(Wc), bc=ptr(bc),
-                     p_h=0.0, p_att=p_att, seed=seed, seed_dev=ptr(ctx.seed_word), trace=_trace)
-        new = torch.empty_like
-        dWa, dba, dWc, dbc = new(Wa), new(ba), new(Wc), new(bc)
-        dWb, dbb = (new(Wb), new(bb)) if gated else (None, None)
-        dx = new(x) if ctx.needs_input_grad[0] else None
-        g = AmilGrads(dW1=None, db1=None, dWa=ptr(dWa), dba=ptr(dba), dWb=ptr(dWb), dbb=ptr(dbb), dWc=ptr(dWc),
-                      dbc=ptr(dbc), dx=ptr(dx))
-        ws = ctx.ws
+        x, *scorer = ctx.saved_tensors
+        stack, (cfg, ws, word) = (None, None, *scorer), ctx.state
+        gA = _f32c(gA).reshape(cfg[0])
+        d = _amil_desc(stack, *cfg, word)
+        ds, dx, g = _stack_grads(x, stack, cfg[4], ctx.needs_input_grad[0])
         check(lib().mmf_attn_net_backward(C.byref(d), ptr(x), ptr(ws), ws.numel(), ptr(gA), C.byref(g), stream_ptr()),
               "mmf_attn_net_backward")
-        return dx, dWa, dba, dWb, dbb, dWc, dbc, None, None, None
+        return (dx, *ds[2:], None, None, None)
 
 
 def attn_net(x, Wa, ba, Wb, bb, Wc, bc, gated, p_att=0.0, seed=0):
     return AttnNetFn.apply(x, Wa, ba, Wb, bb, Wc, bc, gated, p_att, seed)
+
+
+def _linear_cat_fwd_raw(xs, W, b):
+    """y = cat(xs, dim=1) @ W.T + b without materialising the concatenation (mmf_linear_forward).
+    Returns (y, saved): saved = (W, *xs) as the kernel took them, for _linear_cat_bwd_raw."""
+    xs = [_f32c(x) for x in xs]
+    W, b = _f32c(W), _f32c(b)
+    M, kseg = xs[0].shape
+    for x in xs:
+        if tuple(x.shape) != (M, kseg):
+            raise _lib.MmfError("all concatenated segments must have the same [M x k] shape")
+    nseg = len(xs)
+    N = W.shape[0]
+    if W.shape[1] != nseg * kseg:
+        raise _lib.MmfError("weight does not match the concatenated width")
+    y = torch.empty((M, N), dtype=torch.float32, device=W.device)
+    segs = (C.c_void_p * nseg)(*[ptr(x) for x in xs])
+    wsb = lib().mmf_linear_forward_workspace_bytes(M, N, nseg, kseg)
+    sw = sync_words(W.device) if wsb else None
+    ws = torch.empty(wsb, dtype=torch.uint8, device=W.device) if sw is not None else None
+    check(lib().mmf_linear_forward(segs, nseg, kseg, M, ptr(W), ptr(b), N, ACT["none"], 0.0, 0, 0, None,
+                                   ptr(y), ptr(ws), wsb if ws is not None else 0, ptr(sw), SYNC_WORDS if sw is not None else 0,
+                                   stream_ptr()), "mmf_linear_forward")
+    return y, (W, *xs)
+
+
+def _linear_cat_bwd_raw(gy, saved, has_bias, need_dx):
+    """(dW, db, dx) of a _linear_cat_fwd_raw call (mmf_linear_backward); db only with a bias, dx only when need_dx."""
+    W, *xs = saved
+    gy = _f32c(gy)
+    M, kseg = xs[0].shape
+    nseg = len(xs)
+    N, K = W.shape
+    l = lib()
+    dW = torch.empty_like(W)
+    db = torch.empty((N,), dtype=torch.float32, device=W.device) if has_bias else None
+    if need_dx and nseg != 1:
+        raise _lib.MmfError("input gradient of a concatenated linear is not provided (bags are leaves)")
+    dx = torch.empty_like(xs[0]) if need_dx else None
+    nbytes = l.mmf_linear_backward_workspace_bytes(M, N, K)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=W.device)
+    segs = (C.c_void_p * nseg)(*[ptr(x) for x in xs])
+    check(l.mmf_linear_backward(ptr(gy), segs, nseg, kseg, M, ptr(W), N, ptr(dW), ptr(db), ptr(dx),
+                                ptr(ws), nbytes, stream_ptr()), "mmf_linear_backward")
+    return dW, db, dx
 
 
 class LinearCatFn(torch.autograd.Function):
@@ -558,52 +569,48 @@ class LinearCatFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, W, b, *xs):
-        xs = [_f32c(x) for x in xs]
-        W, b = _f32c(W), _f32c(b)
-        M, kseg = xs[0].shape
-        for x in xs:
-            if tuple(x.shape) != (M, kseg):
-                raise _lib.MmfError("all concatenated segments must have the same [M x k] shape")
-        nseg = len(xs)
-        N = W.shape[0]
-        if W.shape[1] != nseg * kseg:
-            raise _lib.MmfError("weight does not match the concatenated width")
-        y = torch.empty((M, N), dtype=torch.float32, device=W.device)
-        segs = (C.c_void_p * nseg)(*[ptr(x) for x in xs])
-        wsb = lib().mmf_linear_forward_workspace_bytes(M, N, nseg, kseg)
-        sw = sync_words(W.device) if wsb else None
-        ws = torch.empty(wsb, dtype=torch.uint8, device=W.device) if sw is not None else None
-        check(lib().mmf_linear_forward(segs, nseg, kseg, M, ptr(W), ptr(b), N, ACT["none"], 0.0, 0, 0, None,
-                                       ptr(y), ptr(ws), wsb if ws is not None else 0, ptr(sw), SYNC_WORDS if sw is not None else 0,
-                                       stream_ptr()), "mmf_linear_forward")
-        ctx.save_for_backward(W, *xs)
+        y, saved = _linear_cat_fwd_raw(xs, W, b)
+        ctx.save_for_backward(*saved)
         ctx.has_bias = b is not None
         return y
 
     @staticmethod
     def backward(ctx, gy):
-        W, *xs = ctx.saved_tensors
-        gy = _f32c(gy)
-        M, kseg = xs[0].shape
-        nseg = len(xs)
-        N, K = W.shape
-        l = lib()
-        dW = torch.empty_like(W)
-        db = torch.empty((N,), dtype=torch.float32, device=W.device) if ctx.has_bias else None
-        need_dx = any(ctx.needs_input_grad[2:])
-        if need_dx and nseg != 1:
-            raise _lib.MmfError("input gradient of a concatenated linear is not provided (bags are leaves)")
-        dx = torch.empty_like(xs[0]) if need_dx else None
-        nbytes = l.mmf_linear_backward_workspace_bytes(M, N, K)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=W.device)
-        segs = (C.c_void_p * nseg)(*[ptr(x) for x in xs])
-        check(l.mmf_linear_backward(ptr(gy), segs, nseg, kseg, M, ptr(W), N, ptr(dW), ptr(db), ptr(dx),
-                                    ptr(ws), nbytes, stream_ptr()), "mmf_linear_backward")
+        nseg = len(ctx.needs_input_grad) - 2
+        dW, db, dx = _linear_cat_bwd_raw(gy, ctx.saved_tensors, ctx.has_bias, any(ctx.needs_input_grad[2:]))
         return (dW, db) + ((dx,) if nseg == 1 else (None,) * nseg)
 
 
 def linear_cat(xs, W, b):
     return LinearCatFn.apply(W, b, *xs)
+
+
+def _surv_head_fwd_raw(feat, Wk, bk, out=None):
+    """Classifier + hazards on feat [B x F] (mmf_surv_head_forward).  Returns out = (logits, hazards, S [B x K],
+    Y_hat [B x 1]): the tensors given, or fresh ones."""
+    B, F = feat.shape
+    K = Wk.shape[0]
+    if out is None:
+        logits = torch.empty((B, K), dtype=torch.float32, device=feat.device)
+        out = (logits, torch.empty_like(logits), torch.empty_like(logits),
+               torch.empty((B, 1), dtype=torch.int64, device=feat.device))
+    logits, hazards, S, Y_hat = out
+    check(lib().mmf_surv_head_forward(ptr(feat), ptr(Wk), ptr(bk), B, F, K, ptr(logits), ptr(hazards),
+                                      ptr(S), ptr(Y_hat), stream_ptr()), "mmf_surv_head_forward")
+    return out
+
+
+def _surv_head_bwd_raw(gH, gS, hazards, feat, Wk):
+    """(dfeat, dWk, dbk) of a _surv_head_fwd_raw call (mmf_surv_head_backward); gH, gS: None where no gradient reaches."""
+    B, F = feat.shape
+    K = Wk.shape[0]
+    gH, gS = _f32c(gH), _f32c(gS)
+    dfeat = torch.empty_like(feat)
+    dWk = torch.empty_like(Wk)
+    dbk = torch.empty((K,), dtype=torch.float32, device=feat.device)
+    check(lib().mmf_surv_head_backward(ptr(gH), ptr(gS), ptr(hazards), ptr(feat), ptr(Wk), B, F, K,
+                                       ptr(dfeat), ptr(dWk), ptr(dbk), stream_ptr()), "mmf_surv_head_backward")
+    return dfeat, dWk, dbk
 
 
 class SurvHeadFn(torch.autograd.Function):
@@ -612,15 +619,7 @@ class SurvHeadFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, feat, Wk, bk):
         feat, Wk, bk = _f32c(feat), _f32c(Wk), _f32c(bk)
-        B, F = feat.shape
-        K = Wk.shape[0]
-        dev = feat.device
-        logits = torch.empty((B, K), dtype=torch.float32, device=dev)
-        hazards = torch.empty_like(logits)
-        S = torch.empty_like(logits)
-        Y_hat = torch.empty((B, 1), dtype=torch.int64, device=dev)
-        check(lib().mmf_surv_head_forward(ptr(feat), ptr(Wk), ptr(bk), B, F, K, ptr(logits), ptr(hazards),
-                                          ptr(S), ptr(Y_hat), stream_ptr()), "mmf_surv_head_forward")
+        _, hazards, S, Y_hat = _surv_head_fwd_raw(feat, Wk, bk)
         ctx.save_for_backward(feat, Wk, hazards)
         ctx.mark_non_differentiable(Y_hat)
         ctx.set_materialize_grads(False)
@@ -629,16 +628,7 @@ class SurvHeadFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gH, gS, _gY):
         feat, Wk, hazards = ctx.saved_tensors
-        B, F = feat.shape
-        K = Wk.shape[0]
-        gH = _f32c(gH) if gH is not None else None
-        gS = _f32c(gS) if gS is not None else None
-        dfeat = torch.empty_like(feat)
-        dWk = torch.empty_like(Wk)
-        dbk = torch.empty((K,), dtype=torch.float32, device=feat.device)
-        check(lib().mmf_surv_head_backward(ptr(gH), ptr(gS), ptr(hazards), ptr(feat), ptr(Wk), B, F, K,
-                                           ptr(dfeat), ptr(dWk), ptr(dbk), stream_ptr()), "mmf_surv_head_backward")
-        return dfeat, dWk, dbk
+        return _surv_head_bwd_raw(gH, gS, hazards, feat, Wk)
 
 
 def surv_head(feat, Wk, bk):
@@ -692,24 +682,6 @@ def surv_head_nll_step(feat, Wk, bk, Y, c, alpha, dWk, dbk, loss_scale=1.0, accu
     check(lib().mmf_surv_head_nll_step(ptr(feat), F, C.byref(hd), C.byref(tg), ptr(dfeat), stream_ptr()),
           "mmf_surv_head_nll_step")
     return hz, S, Y_hat, loss, risk, dfeat
-
-
-class HandCtx:
-    """Stands in for the autograd context when a node's forward / backward are run by hand (no graph): the multimodal
-    one-call step drives AmilPoolFn / LinearCatFn directly, on the streams it chooses."""
-
-    def __init__(self, needs_input_grad):
-        self.needs_input_grad = tuple(needs_input_grad)
-        self.saved_tensors = ()
-
-    def save_for_backward(self, *tensors):
-        self.saved_tensors = tensors
-
-    def set_materialize_grads(self, value):
-        pass
-
-    def mark_non_differentiable(self, *tensors):
-        pass
 
 
 class CoxSurvFn(torch.autograd.Function):
@@ -770,39 +742,50 @@ def maxnet_cox_step(x, W0, b0, W1, b1, Wc, bc, times, c, grads, loss_scale=1.0, 
 DROP_KIND = {"none": 0, "dropout": 1, "alpha": 2}
 
 
+def _dense_fwd_raw(x, W, b, act, kind, p, seed, site, word=None, out=None):
+    """y = drop(act(x @ W.T + b)) (mmf_dense_forward) into out, or a fresh [B x N] tensor."""
+    B, K = x.shape
+    N = W.shape[0]
+    y = torch.empty((B, N), dtype=torch.float32, device=x.device) if out is None else out
+    check(lib().mmf_dense_forward(ptr(x), ptr(W), ptr(b), B, K, N, ACT[act], DROP_KIND[kind], float(p),
+                                  int(seed) & 0xFFFFFFFF, int(site), ptr(word), ptr(y), stream_ptr()), "mmf_dense_forward")
+    return y
+
+
+def _dense_bwd_raw(gy, y, x, W, has_bias, act, kind, p, seed, site, need_dx=True, word=None):
+    """(dx, dW, db) of a _dense_fwd_raw call (mmf_dense_backward); dx only when need_dx, db only with a bias."""
+    B, K = x.shape
+    N = W.shape[0]
+    dpre = torch.empty_like(y)
+    dx = torch.empty_like(x) if need_dx else None
+    dW = torch.empty_like(W)
+    db = torch.empty((N,), dtype=torch.float32, device=x.device) if has_bias else None
+    check(lib().mmf_dense_backward(ptr(gy), ptr(y), ptr(x), ptr(W), B, K, N, ACT[act], DROP_KIND[kind], float(p),
+                                   int(seed) & 0xFFFFFFFF, int(site), ptr(word), ptr(dpre), ptr(dx), ptr(dW), ptr(db),
+                                   stream_ptr()), "mmf_dense_backward")
+    return dx, dW, db
+
+
 class DenseFn(torch.autograd.Function):
     """y = drop(act(x @ W.T + b)) for small / odd-shaped layers (SNN blocks, fusion MLPs, classifiers)."""
 
     @staticmethod
     def forward(ctx, x, W, b, act, drop_kind, drop_p, seed, site):
         x, W, b = _f32c(x), _f32c(W), _f32c(b)
-        B, K = x.shape
-        N = W.shape[0]
+        _, K = x.shape
         if W.shape[1] != K:
             raise _lib.MmfError(f"dense: weight {tuple(W.shape)} does not match input {tuple(x.shape)}")
-        y = torch.empty((B, N), dtype=torch.float32, device=x.device)
-        word = _seed_word
-        check(lib().mmf_dense_forward(ptr(x), ptr(W), ptr(b), B, K, N, ACT[act], DROP_KIND[drop_kind], float(drop_p),
-                                      int(seed) & 0xFFFFFFFF, int(site), ptr(word), ptr(y), stream_ptr()), "mmf_dense_forward")
-        ctx.cfg = (act, drop_kind, float(drop_p), int(seed) & 0xFFFFFFFF, int(site), b is not None)
-        ctx.seed_word = word
+        ctx.cfg = (act, drop_kind, drop_p, seed, site)
+        ctx.seed_word = _seed_word
+        ctx.has_bias = b is not None
+        y = _dense_fwd_raw(x, W, b, *ctx.cfg, ctx.seed_word)
         ctx.save_for_backward(x, W, y)
         return y
 
     @staticmethod
     def backward(ctx, gy):
         x, W, y = ctx.saved_tensors
-        act, drop_kind, drop_p, seed, site, has_bias = ctx.cfg
-        gy = _f32c(gy)
-        B, K = x.shape
-        N = W.shape[0]
-        dpre = torch.empty_like(y)
-        dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
-        dW = torch.empty_like(W)
-        db = torch.empty((N,), dtype=torch.float32, device=x.device) if has_bias else None
-        check(lib().mmf_dense_backward(ptr(gy), ptr(y), ptr(x), ptr(W), B, K, N, ACT[act], DROP_KIND[drop_kind],
-                                       drop_p, seed, site, ptr(ctx.seed_word), ptr(dpre), ptr(dx), ptr(dW), ptr(db),
-                                       stream_ptr()), "mmf_dense_backward")
+        dx, dW, db = _dense_bwd_raw(_f32c(gy), y, x, W, ctx.has_bias, *ctx.cfg, ctx.needs_input_grad[0], ctx.seed_word)
         return dx, dW, db, None, None, None, None, None
 
 
@@ -835,64 +818,46 @@ def gate_mul(z, h):
     return GateMulFn.apply(z, h)
 
 
+def _kron_fwd_raw(os_, p, seed, site, word):
+    """[o0,1] (x) [o1,1] ((x) [o2,1]) + dropout of the contiguous fp32 os_ ([B x dim] each) (mmf_kron_forward)."""
+    m = len(os_)
+    B, dim = os_[0].shape
+    out = torch.empty((B, (dim + 1) ** m), dtype=torch.float32, device=os_[0].device)
+    arr = (C.c_void_p * m)(*[ptr(o) for o in os_])
+    check(lib().mmf_kron_forward(arr, m, dim, B, float(p), int(seed) & 0xFFFFFFFF, int(site), ptr(word), ptr(out),
+                                 stream_ptr()), "mmf_kron_forward")
+    return out
+
+
+def _kron_bwd_raw(g, os_, p, seed, site, word):
+    """The gradients of the os_ of a _kron_fwd_raw call (mmf_kron_backward)."""
+    m = len(os_)
+    B, dim = os_[0].shape
+    ds = [torch.empty_like(o) for o in os_]
+    arr = (C.c_void_p * m)(*[ptr(o) for o in os_])
+    darr = (C.c_void_p * m)(*[ptr(d) for d in ds])
+    check(lib().mmf_kron_backward(ptr(g), arr, m, dim, B, float(p), int(seed) & 0xFFFFFFFF, int(site), ptr(word), darr,
+                                  stream_ptr()), "mmf_kron_backward")
+    return ds
+
+
 class KronFn(torch.autograd.Function):
     """[o0,1] (x) [o1,1] ((x) [o2,1]) + post-fusion Dropout (models/model_modules.py:164-171)."""
 
     @staticmethod
     def forward(ctx, drop_p, seed, site, *os_):
         os_ = [_f32c(o) for o in os_]
-        m = len(os_)
-        B, dim = os_[0].shape
-        total = (dim + 1) ** m
-        out = torch.empty((B, total), dtype=torch.float32, device=os_[0].device)
-        arr = (C.c_void_p * m)(*[ptr(o) for o in os_])
-        word = _seed_word
-        check(lib().mmf_kron_forward(arr, m, dim, B, float(drop_p), int(seed) & 0xFFFFFFFF, int(site), ptr(word), ptr(out),
-                                     stream_ptr()), "mmf_kron_forward")
-        ctx.cfg = (float(drop_p), int(seed) & 0xFFFFFFFF, int(site))
-        ctx.seed_word = word
+        ctx.cfg = (drop_p, seed, site, _seed_word)
         ctx.save_for_backward(*os_)
-        return out
+        return _kron_fwd_raw(os_, *ctx.cfg)
 
     @staticmethod
     def backward(ctx, g):
-        os_ = list(ctx.saved_tensors)
-        drop_p, seed, site = ctx.cfg
-        m = len(os_)
-        B, dim = os_[0].shape
-        g = _f32c(g)
-        ds = [torch.empty_like(o) for o in os_]
-        arr = (C.c_void_p * m)(*[ptr(o) for o in os_])
-        darr = (C.c_void_p * m)(*[ptr(d) for d in ds])
-        check(lib().mmf_kron_backward(ptr(g), arr, m, dim, B, drop_p, seed, site, ptr(ctx.seed_word), darr, stream_ptr()),
-              "mmf_kron_backward")
-        return (None, None, None) + tuple(ds)
+        return (None, None, None, *_kron_bwd_raw(_f32c(g), ctx.saved_tensors, *ctx.cfg))
 
 
 def kron_ones(os_, drop_p=0.0, seed=0, site=0):
     return KronFn.apply(drop_p, seed, site, *os_)
-
-
-# ---- raw (no-autograd) launch helpers shared by the fused fusion Function --------------------------------------
-def _dense_fwd_raw(x, W, b, act, kind, p, seed, site, word=None, out=None):
-    B, K = x.shape
-    N = W.shape[0]
-    y = torch.empty((B, N), dtype=torch.float32, device=x.device) if out is None else out
-    check(lib().mmf_dense_forward(ptr(x), ptr(W), ptr(b), B, K, N, ACT[act], DROP_KIND[kind], float(p), seed, site,
-                                  ptr(word), ptr(y), stream_ptr()), "mmf_dense_forward")
-    return y
-
-
-def _dense_bwd_raw(gy, y, x, W, has_bias, act, kind, p, seed, site, need_dx=True, word=None):
-    B, K = x.shape
-    N = W.shape[0]
-    dpre = torch.empty_like(y)
-    dx = torch.empty_like(x) if need_dx else None
-    dW = torch.empty_like(W)
-    db = torch.empty((N,), dtype=torch.float32, device=x.device) if has_bias else None
-    check(lib().mmf_dense_backward(ptr(gy), ptr(y), ptr(x), ptr(W), B, K, N, ACT[act], DROP_KIND[kind], float(p), seed,
-                                   site, ptr(word), ptr(dpre), ptr(dx), ptr(dW), ptr(db), stream_ptr()), "mmf_dense_backward")
-    return dx, dW, db
 
 
 class MlpFn(torch.autograd.Function):
@@ -939,6 +904,70 @@ def mlp(x, layers, seed=0):
     return MlpFn.apply(spec, seed, x, *wb)
 
 
+def _xreduce_io(m, vs, w, hs, zs, gms, os_):
+    io = _lib.XReduceIO(m=m, B=vs[0].shape[0], dim=vs[0].shape[1], sdim=w[0].shape[0])
+    for i in range(m):
+        Wh, bh, Wz, bz, Wo, bo = w[6 * i:6 * i + 6]
+        io.v[i] = ptr(vs[i]); io.Wh[i] = ptr(Wh); io.bh[i] = ptr(bh); io.Wz[i] = ptr(Wz); io.bz[i] = ptr(bz)
+        io.Wo[i] = ptr(Wo); io.bo[i] = ptr(bo)
+        io.h[i] = ptr(hs[i]); io.z[i] = ptr(zs[i]); io.gm[i] = ptr(gms[i]); io.o[i] = ptr(os_[i])
+    return io
+
+
+def _xfusion_fwd_raw(vs, w, p, seed):
+    """The XlinearFusion block (XFusionFn) on vs (m tensors [B x dim]) with weights w: mmf_xreduce_forward, the Kronecker
+    product, encoder1, encoder2.  Returns (e2, saved, state) for _xfusion_bwd_raw."""
+    m = len(vs)
+    vs = [_f32c(t) for t in vs]
+    w = [_f32c(t) for t in w]
+    kind = "dropout" if p > 0 else "none"
+    seed = int(seed) & 0xFFFFFFFF
+    B = vs[0].shape[0]
+    sdim = w[0].shape[0]
+    new = lambda: [torch.empty((B, sdim), dtype=torch.float32, device=vs[0].device) for _ in range(m)]
+    hs, zs, gms, os_ = new(), new(), new(), new()
+    io = _xreduce_io(m, vs, w, hs, zs, gms, os_)
+    word = _seed_word
+    check(lib().mmf_xreduce_forward(C.byref(io), float(p), seed, ptr(word), stream_ptr()), "mmf_xreduce_forward")
+    We1, be1, We2, be2 = w[6 * m:6 * m + 4]
+    kr = _kron_fwd_raw(os_, p, seed, 8, word)
+    e1 = _dense_fwd_raw(kr, We1, be1, "relu", kind, p, seed, 9, word)
+    cat2 = torch.cat([e1] + vs, dim=1)
+    e2 = _dense_fwd_raw(cat2, We2, be2, "relu", kind, p, seed, 10, word)
+    return e2, (*vs, *w, *hs, *zs, *gms, *os_, kr, e1, cat2, e2), (m, float(p), seed, kind, word)
+
+
+def _xfusion_bwd_raw(g, saved, state):
+    """The gradients of a _xfusion_fwd_raw call: (those of the vs, those of the weights in w's order)."""
+    m, p, seed, kind, word = state
+    t = list(saved)
+    vs, t = t[:m], t[m:]
+    w, t = t[:6 * m + 4], t[6 * m + 4:]
+    hs, zs, gms, os_ = t[:m], t[m:2 * m], t[2 * m:3 * m], t[3 * m:4 * m]
+    kr, e1, cat2, e2 = t[4 * m:4 * m + 4]
+    We1, be1, We2, be2 = w[6 * m:6 * m + 4]
+    g = _f32c(g)
+    d_cat2, dWe2, dbe2 = _dense_bwd_raw(g, e2, cat2, We2, True, "relu", kind, p, seed, 10, word=word)
+    H1 = e1.shape[1]
+    d_e1 = d_cat2[:, :H1].contiguous()
+    dim_v = vs[0].shape[1]
+    d_kr, dWe1, dbe1 = _dense_bwd_raw(d_e1, e1, kr, We1, True, "relu", kind, p, seed, 9, word=word)
+    d_os = _kron_bwd_raw(d_kr, os_, p, seed, 8, word)
+    io = _xreduce_io(m, vs, w, hs, zs, gms, os_)
+    dvs = [torch.empty_like(v) for v in vs]
+    grads_w = []
+    for i in range(m):
+        Wh, bh, Wz, bz, Wo, bo = w[6 * i:6 * i + 6]
+        gw = [torch.empty_like(x) for x in (Wh, bh, Wz, bz, Wo, bo)]
+        io.d_o[i] = ptr(d_os[i]); io.dv[i] = ptr(dvs[i])
+        io.dWh[i], io.dbh[i], io.dWz[i], io.dbz[i], io.dWo[i], io.dbo[i] = [ptr(x) for x in gw]
+        grads_w += gw
+    check(lib().mmf_xreduce_backward(C.byref(io), p, seed, ptr(word), stream_ptr()), "mmf_xreduce_backward")
+    for i in range(m):      # skip connection: encoder2 saw the v_i directly
+        dvs[i] += d_cat2[:, H1 + dim_v * i: H1 + dim_v * (i + 1)]
+    return dvs, grads_w + [dWe1, dbe1, dWe2, dbe2]
+
+
 class XFusionFn(torch.autograd.Function):
     """The whole XlinearFusion block (models/model_modules.py:156-178, gate=1, skip=1) as ONE autograd node: the same
     HIP kernels as the composable ops above, but one Python forward and one Python backward instead of ~25 nodes
@@ -949,74 +978,14 @@ class XFusionFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, m, p, seed, *tensors):
-        vs = [_f32c(t) for t in tensors[:m]]
-        w = [_f32c(t) for t in tensors[m:]]
-        kind = "dropout" if p > 0 else "none"
-        seed = int(seed) & 0xFFFFFFFF
-        B = vs[0].shape[0]
-        sdim = w[0].shape[0]
-        new = lambda: [torch.empty((B, sdim), dtype=torch.float32, device=vs[0].device) for _ in range(m)]
-        hs, zs, gms, os_ = new(), new(), new(), new()
-        io = XFusionFn._io(m, vs, w, hs, zs, gms, os_)
-        word = _seed_word
-        check(lib().mmf_xreduce_forward(C.byref(io), float(p), seed, ptr(word), stream_ptr()), "mmf_xreduce_forward")
-        We1, be1, We2, be2 = w[6 * m:6 * m + 4]
-        B, dim = os_[0].shape
-        kr = torch.empty((B, (dim + 1) ** m), dtype=torch.float32, device=vs[0].device)
-        arr = (C.c_void_p * m)(*[ptr(o) for o in os_])
-        check(lib().mmf_kron_forward(arr, m, dim, B, float(p), seed, 8, ptr(word), ptr(kr), stream_ptr()), "mmf_kron_forward")
-        e1 = _dense_fwd_raw(kr, We1, be1, "relu", kind, p, seed, 9, word)
-        cat2 = torch.cat([e1] + vs, dim=1)
-        e2 = _dense_fwd_raw(cat2, We2, be2, "relu", kind, p, seed, 10, word)
-        ctx.cfg = (m, float(p), seed, kind)
-        ctx.seed_word = word
-        ctx.save_for_backward(*vs, *w, *hs, *zs, *gms, *os_, kr, e1, cat2, e2)
+        e2, saved, ctx.state = _xfusion_fwd_raw(tensors[:m], tensors[m:], p, seed)
+        ctx.save_for_backward(*saved)
         return e2
 
     @staticmethod
-    def _io(m, vs, w, hs, zs, gms, os_):
-        io = _lib.XReduceIO(m=m, B=vs[0].shape[0], dim=vs[0].shape[1], sdim=w[0].shape[0])
-        for i in range(m):
-            Wh, bh, Wz, bz, Wo, bo = w[6 * i:6 * i + 6]
-            io.v[i] = ptr(vs[i]); io.Wh[i] = ptr(Wh); io.bh[i] = ptr(bh); io.Wz[i] = ptr(Wz); io.bz[i] = ptr(bz)
-            io.Wo[i] = ptr(Wo); io.bo[i] = ptr(bo)
-            io.h[i] = ptr(hs[i]); io.z[i] = ptr(zs[i]); io.gm[i] = ptr(gms[i]); io.o[i] = ptr(os_[i])
-        return io
-
-    @staticmethod
     def backward(ctx, g):
-        m, p, seed, kind = ctx.cfg
-        t = list(ctx.saved_tensors)
-        vs, t = t[:m], t[m:]
-        w, t = t[:6 * m + 4], t[6 * m + 4:]
-        hs, zs, gms, os_ = t[:m], t[m:2 * m], t[2 * m:3 * m], t[3 * m:4 * m]
-        kr, e1, cat2, e2 = t[4 * m:4 * m + 4]
-        We1, be1, We2, be2 = w[6 * m:6 * m + 4]
-        g = _f32c(g)
-        word = ctx.seed_word
-        d_cat2, dWe2, dbe2 = _dense_bwd_raw(g, e2, cat2, We2, True, "relu", kind, p, seed, 10, word=word)
-        H1 = e1.shape[1]
-        d_e1 = d_cat2[:, :H1].contiguous()
-        dim_v = vs[0].shape[1]
-        d_kr, dWe1, dbe1 = _dense_bwd_raw(d_e1, e1, kr, We1, True, "relu", kind, p, seed, 9, word=word)
-        B, dim = os_[0].shape
-        d_os = [torch.empty_like(o) for o in os_]
-        arr = (C.c_void_p * m)(*[ptr(o) for o in os_])
-        darr = (C.c_void_p * m)(*[ptr(d) for d in d_os])
-        check(lib().mmf_kron_backward(ptr(d_kr), arr, m, dim, B, p, seed, 8, ptr(word), darr, stream_ptr()), "mmf_kron_backward")
-        io = XFusionFn._io(m, vs, w, hs, zs, gms, os_)
-        dvs = [torch.empty_like(v) for v in vs]
-        grads_w = []
-        for i in range(m):
-            Wh, bh, Wz, bz, Wo, bo = w[6 * i:6 * i + 6]
-            gw = [torch.empty_like(x) for x in (Wh, bh, Wz, bz, Wo, bo)]
-            io.d_o[i] = ptr(d_os[i]); io.dv[i] = ptr(dvs[i])
-            io.dWh[i], io.dbh[i], io.dWz[i], io.dbz[i], io.dWo[i], io.dbo[i] = [ptr(x) for x in gw]
-            grads_w += gw
-        check(lib().mmf_xreduce_backward(C.byref(io), p, seed, ptr(word), stream_ptr()), "mmf_xreduce_backward")
-        for i in range(m):      # skip connection: encoder2 saw the v_i directly
-            dvs[i] += d_cat2[:, H1 + dim_v * i: H1 + dim_v * (i + 1)]
-        return (None, None, None) + tuple(dvs) + tuple(grads_w) + (dWe1, dbe1, dWe2, dbe2)
+        dvs, dw = _xfusion_bwd_raw(g, ctx.saved_tensors, ctx.state)
+        return (None, None, None, *dvs, *dw)
 
 
 def xfusion(v_list, weights, p=0.0, seed=0):
