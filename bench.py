@@ -10,18 +10,23 @@ A step = forward + NLLSurvLoss + backward of one bag, every parameter gradient w
 in HBM -- issued as the training-loop mirror issues it (multimodalfusion_amd/utils/core_utils.py): ONE C-ABI call,
 `model.nll_step` -> mmf_amil_nll_step (the head and the loss run as the tail of the pooling merge kernel).  The same
 step through the autograd surface (model(**bag) -> NLLSurvLoss -> .backward(), the calls utils/core_utils.py:200-243
-of the reference makes) is timed beside it (`autograd_surface`; `--autograd` makes it the headline).  N > 1 adds ONE
-RCCL all-reduce (SUM) of the flat gradient buffer per step (one bag per GPU == the reference's --gc N).
+of the reference makes) is the headline with `--autograd`, and is timed beside it with `--full` (`autograd_surface`).
+N > 1 adds ONE RCCL all-reduce (SUM) of the flat gradient buffer per step (one bag per GPU == the reference's --gc N).
 Train mode as `model.train()` with --drop_out off (one Dropout(0.25) mask, the headline mode of
 BASELINE.md); rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the --steps steps, writes --dump-outputs and prints the line: nothing else.  `--full`
+adds, on rank 0 after the headline, every leg that does not feed it (full_legs): the one-bag-at-a-time figure, per-step
+percentiles, per-kernel times and the roofline, the autograd surface beside the one-call step, other bag sizes and
+configurations, the bf16x3 GEMM mode, the PCIe-inclusive rate and the CPU baseline.
 
 Steps are issued round-robin on `--inflight` HIP streams (default 2 for fp32 bags, 3 for bf16 bags), each with its own
 resident bag and its own flat gradient buffer
 (multimodalfusion_amd/pipeline.py): bags are independent until the optimizer step (batch_size = 1 + gradient
 accumulation in the reference), and one bag's kernels leave CUs idle (224 of 256 in the row-parallel GEMMs, every
 kernel's tail, the latency-bound small kernels).  Every step is still one full forward + loss + backward of one bag
-with all gradients materialised (+ one all-reduce when N > 1); `one_bag_in_flight` in the JSON is the strictly
-sequential figure of the same run, and the roofline leg times kernels one bag at a time.
+with all gradients materialised (+ one all-reduce when N > 1); with --full, `one_bag_in_flight` in the JSON is the
+strictly sequential figure of the same run, and the roofline leg times kernels one bag at a time.
 """
 from __future__ import annotations
 
@@ -51,15 +56,20 @@ def parse():
                          "by barrier + synchronize; the rates of the fastest / median / slowest block are reported beside `value`")
     ap.add_argument("--bag", type=int, default=50000, help="instances per bag (BASELINE metric: 50000)")
     ap.add_argument("--eval-mode", action="store_true", help="no dropout (secondary figure)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, run every leg that does not feed it (full_legs): one bag at a time, per-kernel "
+                         "times and roofline, autograd surface, other sizes and configurations, bf16x3 GEMMs, PCIe-inclusive "
+                         "rate, CPU baseline; they never change `value`, `ms_per_step` or what --dump-outputs writes")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-bags", type=int, default=8, help="timed bags of the CPU baseline sample")
     ap.add_argument("--no-extras", dest="extras", action="store_false", default=True,
-                    help="skip the extra legs of the default N = 1 run (other bag sizes, hipGraph steps, BASELINE configs "
-                         "3-5, PCIe-inclusive rate); they never change `value`")
-    ap.add_argument("--extra-sizes", action="store_true", help="(kept for older command lines: the legs are on by default)")
-    ap.add_argument("--graph", action="store_true", help="(kept for older command lines: the legs are on by default)")
+                    help="with --full: skip the extra legs of an N = 1 run (other bag sizes, hipGraph steps, BASELINE configs "
+                         "3-5, PCIe-inclusive rate)")
+    ap.add_argument("--extra-sizes", action="store_true", help="(kept for older command lines: --full runs the legs)")
+    ap.add_argument("--graph", action="store_true", help="(kept for older command lines: --full runs the legs)")
     ap.add_argument("--h2d", action="store_true", default=True,
-                    help="also report the PCIe-inclusive rate (extra key `pcie_inclusive`, never `value`); on by default at N = 1")
+                    help="with --full: also report the PCIe-inclusive rate (extra key `pcie_inclusive`, never `value`); on by "
+                         "default at N = 1")
     ap.add_argument("--no-h2d", dest="h2d", action="store_false")
     ap.add_argument("--inflight", type=int, default=0,
                     help="bags in flight per GPU: steps are issued round-robin on this many HIP streams, each with its "
@@ -744,6 +754,101 @@ def cpu_baseline(N, n_bags, threads=None):
                        f"value_1_thread: one bag on one thread")
 
 
+def full_legs(out, args, model, x, dev, flat, g, world, inflight, sizes):
+    """`--full`: every leg that does not feed the headline, run on rank 0 after it, its figures added to `out`."""
+    import torch
+    N = args.bag
+    bf16 = args.dtype == "bf16"
+    ag = args.autograd
+    # ---- roofline of the dominant kernel, timed live with HIP events on the launch stream ----
+    # rank 0 only: this leg must NOT contain the collective (the other ranks are already at the final barrier)
+    local_step = make_step(model, x, dev, flat, 1, ag)
+    if inflight > 1 and world == 1:      # the strictly sequential figure beside it (same run)
+        b1 = time_blocks(local_step, sizes, args.warmup, 1)
+        d1 = sum(b1)
+        r1 = [n / b for n, b in zip(sizes, b1)]
+        out["one_bag_in_flight"] = {"value": args.steps / d1, "ms_per_step": 1e3 * d1 / args.steps,
+                                    "value_min": min(r1), "value_max": max(r1), "blocks": len(b1)}
+        # SURVEY 8(d) defines the metric as ONE bag per GPU per step: that figure at top level, beside `value`
+        out["value_one_bag_per_step"] = args.steps / d1
+        out["ms_per_step_one_bag"] = 1e3 * d1 / args.steps
+    out["step_ms_device"] = step_percentiles(local_step, max(10, min(args.steps, 50)))
+    prof = kernel_profile(local_step, max(5, min(args.steps, 20)))
+    rl = roofline_of(prof, N, bf16)
+    if rl is not None:
+        out["roofline"] = rl
+    out["kernels_us"] = {k: round(v["avg_us"], 2) for k, v in sorted(prof.items())}
+    for p in model.parameters():
+        p.grad = None
+    if world == 1 and not ag:          # the same bag through the autograd surface, one at a time
+        da = time_steps(make_step(model, x, dev, None, 1, True), args.steps, args.warmup, 1)
+        out["autograd_surface"] = {"one_bag_value": args.steps / da, "ms_per_step": 1e3 * da / args.steps}
+        for p in model.parameters():
+            p.grad = None
+    if args.extras and world == 1:
+        # north_star's other bag sizes: eager (host-bound: Python + autograd + ~12 launches) and as one hipGraph
+        extra = {}
+        k2 = max(args.steps, 200)           # 0.1-0.25 ms steps: a short run would mostly measure the clock ramp
+        for n2 in (1000, 10000):
+            x2 = torch.randn(n2, 1024, device=dev, generator=g)
+            d2 = time_steps(make_step(model, x2, dev, None, 1), k2, args.warmup, 1)
+            ms2 = 1e3 * d2 / k2
+            d3 = time_steps(make_step(model, x2, dev, None, 1, True), args.steps, args.warmup, 1)
+            for p in model.parameters():
+                p.grad = None
+            prof2 = kernel_profile(make_step(model, x2, dev, None, 1), 10)
+            rl2 = roofline_of(prof2, n2, False)
+            extra[str(n2)] = {"bags_per_s": k2 / d2, "ms_per_step": ms2, **size_fractions(n2, ms2),
+                              "autograd_surface_ms_per_step": 1e3 * d3 / args.steps, "roofline": rl2,
+                              "kernels_us": {k: round(v["avg_us"], 2) for k, v in sorted(prof2.items())}}
+        out["other_sizes"] = extra
+        # bag-size sweep, one bag per step: is there a cliff between the small-tile and the wide-tile plans?
+        sweep = {}
+        for n2 in (4000, 10000, 16000, 24000, 40000, 60000):
+            x2 = torch.randn(n2, 1024, device=dev, generator=g)
+            k3 = max(40, min(k2, int(k2 * 10000 / n2)))
+            d2 = time_steps(make_step(model, x2, dev, None, 1), k3, args.warmup, 1)
+            sweep[str(n2)] = {"ms_per_step": 1e3 * d2 / k3, "frac_fp32_mfma_peak": size_fractions(n2, 1e3 * d2 / k3)["frac_fp32_mfma_peak"]}
+            if n2 <= 24000:
+                # mid-size bags leave CUs idle one at a time (39 rows per CU at 10k): the aggregate rate with four bags
+                # in flight on four streams (pipeline.BagsInFlight, a distinct resident bag per stream)
+                d4 = time_steps(make_step_inflight(model, x2, dev, 1, 4), k3, args.warmup, 1)
+                sweep[str(n2)]["four_in_flight_ms_per_bag"] = 1e3 * d4 / k3
+                sweep[str(n2)]["four_in_flight_frac_fp32_mfma_peak"] = size_fractions(n2, 1e3 * d4 / k3)["frac_fp32_mfma_peak"]
+                for p in model.parameters():
+                    p.grad = None
+            del x2
+        out["n_sweep"] = sweep
+        out["graphed_small_bags"] = graph_leg(model, dev, args.steps, g)
+        if not bf16 and args.gemm == "f32":
+            # two bags in flight: this mode keeps the package at its power limit by itself (1,907 bags/s with two,
+            # 1,875 with three, 1,844 with four in the same run)
+            out["gemm_bf16x3"] = gemm_bf16x3_leg(model, x, dev, args.steps, args.warmup, min(inflight, 2))
+            # the same two headline figures in that mode, at top level beside `value` (never instead of it)
+            out["value_gemm_bf16x3"] = out["gemm_bf16x3"]["value"]
+            out["ms_per_step_one_bag_gemm_bf16x3"] = out["gemm_bf16x3"]["ms_per_step_one_bag"]
+        if not bf16 and N == 50000:
+            out["config5_bf16_100k"] = config5_leg(dev, max(10, args.steps), args.warmup, g)
+            out["other_configs"] = other_configs_leg(dev, max(10, min(args.steps, 30)), args.warmup, g)
+    if args.h2d and args.extras and world == 1:
+        out["pcie_inclusive"] = h2d_leg(model, N, dev, max(10, min(args.steps, 30)), args.warmup, bf16)
+    if world == 1 and not args.no_cpu_baseline and not bf16:
+        # the CPU leg runs LAST (nothing on the GPU waits behind it): the metric's bag first, then north_star's other two
+        # sizes (BASELINE config 1 is the 1000 x 1024 CPU run) beside the GPU figures of `other_sizes`
+        out["cpu_baseline"] = cpu_baseline(N, args.cpu_bags)
+        out["gpu_over_cpu"] = out["value"] / out["cpu_baseline"]["value"]
+        if args.extras and N == 50000:
+            small = {}
+            for n2, nb in ((10000, 20), (1000, 100)):
+                cb = cpu_baseline(n2, nb)
+                gpu = out.get("other_sizes", {}).get(str(n2), {}).get("bags_per_s")
+                small[str(n2)] = {"value": cb["value"], "unit": "bags/s", "cores": cb["cores"], "kind": "port",
+                                  "value_1_thread": cb["value_1_thread"], "sample": cb["sample"],
+                                  "thread_probe_s_per_bag": cb["thread_probe_s_per_bag"],
+                                  "gpu_bags_per_s": gpu, "gpu_over_cpu": (gpu / cb["value"]) if gpu else None}
+            out["cpu_baseline_other_sizes"] = small
+
+
 def self_launch(args):
     """`python bench.py --gpus N` started WITHOUT a launcher (no WORLD_SIZE in the environment): start the N ranks ourselves,
     as children (`python -m torch.distributed.run ... bench.py <same arguments>`), before this process has made any GPU
@@ -868,102 +973,17 @@ def main():
                                + (f", {inflight} bags in flight per GPU on {inflight} HIP streams" if inflight > 1 else ""),
                    "instances_per_bag": N, "parallelism": f"dp{world} (one bag per GPU per step)", "bags_in_flight": inflight},
     }
+    tot = flops_per_bag(N)
+    mfma_peak = BF16_MFMA_PEAK_TFLOPS if bf16 else FP32_MFMA_PEAK_TFLOPS
+    out["whole_step"] = {"tflops": tot / (ms_per_step * 1e-3) / 1e12,
+                         ("frac_bf16_mfma_peak" if bf16 else "frac_fp32_mfma_peak"):
+                             tot / (ms_per_step * 1e-3) / 1e12 / mfma_peak,
+                         "algorithmic_gbs": bytes_per_bag(N, bf16) / (ms_per_step * 1e-3) / 1e9,
+                         "frac_hbm_peak": bytes_per_bag(N, bf16) / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS}
 
     if rank == 0:
-        # ---- roofline of the dominant kernel, timed live with HIP events on the launch stream ----
-        # rank 0 only: this leg must NOT contain the collective (the other ranks are already at the final barrier)
-        local_step = make_step(model, x, dev, flat, 1, ag)
-        if inflight > 1 and world == 1:      # the strictly sequential figure beside it (same run)
-            b1 = time_blocks(local_step, sizes, args.warmup, 1)
-            d1 = sum(b1)
-            r1 = [n / b for n, b in zip(sizes, b1)]
-            out["one_bag_in_flight"] = {"value": args.steps / d1, "ms_per_step": 1e3 * d1 / args.steps,
-                                        "value_min": min(r1), "value_max": max(r1), "blocks": len(b1)}
-            # SURVEY 8(d) defines the metric as ONE bag per GPU per step: that figure at top level, beside `value`
-            out["value_one_bag_per_step"] = args.steps / d1
-            out["ms_per_step_one_bag"] = 1e3 * d1 / args.steps
-        out["step_ms_device"] = step_percentiles(local_step, max(10, min(args.steps, 50)))
-        prof = kernel_profile(local_step, max(5, min(args.steps, 20)))
-        rl = roofline_of(prof, N, bf16)
-        if rl is not None:
-            out["roofline"] = rl
-        tot = flops_per_bag(N)
-        mfma_peak = BF16_MFMA_PEAK_TFLOPS if bf16 else FP32_MFMA_PEAK_TFLOPS
-        out["whole_step"] = {"tflops": tot / (ms_per_step * 1e-3) / 1e12,
-                             ("frac_bf16_mfma_peak" if bf16 else "frac_fp32_mfma_peak"):
-                                 tot / (ms_per_step * 1e-3) / 1e12 / mfma_peak,
-                             "algorithmic_gbs": bytes_per_bag(N, bf16) / (ms_per_step * 1e-3) / 1e9,
-                             "frac_hbm_peak": bytes_per_bag(N, bf16) / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS}
-        out["kernels_us"] = {k: round(v["avg_us"], 2) for k, v in sorted(prof.items())}
-        for p in model.parameters():
-            p.grad = None
-        if world == 1 and not ag:          # the same bag through the autograd surface, one at a time
-            da = time_steps(make_step(model, x, dev, None, 1, True), args.steps, args.warmup, 1)
-            out["autograd_surface"] = {"one_bag_value": args.steps / da, "ms_per_step": 1e3 * da / args.steps}
-            for p in model.parameters():
-                p.grad = None
-        if args.extras and world == 1:
-            # north_star's other bag sizes: eager (host-bound: Python + autograd + ~12 launches) and as one hipGraph
-            extra = {}
-            k2 = max(args.steps, 200)           # 0.1-0.25 ms steps: a short run would mostly measure the clock ramp
-            for n2 in (1000, 10000):
-                x2 = torch.randn(n2, 1024, device=dev, generator=g)
-                d2 = time_steps(make_step(model, x2, dev, None, 1), k2, args.warmup, 1)
-                ms2 = 1e3 * d2 / k2
-                d3 = time_steps(make_step(model, x2, dev, None, 1, True), args.steps, args.warmup, 1)
-                for p in model.parameters():
-                    p.grad = None
-                prof2 = kernel_profile(make_step(model, x2, dev, None, 1), 10)
-                rl2 = roofline_of(prof2, n2, False)
-                extra[str(n2)] = {"bags_per_s": k2 / d2, "ms_per_step": ms2, **size_fractions(n2, ms2),
-                                  "autograd_surface_ms_per_step": 1e3 * d3 / args.steps, "roofline": rl2,
-                                  "kernels_us": {k: round(v["avg_us"], 2) for k, v in sorted(prof2.items())}}
-            out["other_sizes"] = extra
-            # bag-size sweep, one bag per step: is there a cliff between the small-tile and the wide-tile plans?
-            sweep = {}
-            for n2 in (4000, 10000, 16000, 24000, 40000, 60000):
-                x2 = torch.randn(n2, 1024, device=dev, generator=g)
-                k3 = max(40, min(k2, int(k2 * 10000 / n2)))
-                d2 = time_steps(make_step(model, x2, dev, None, 1), k3, args.warmup, 1)
-                sweep[str(n2)] = {"ms_per_step": 1e3 * d2 / k3, "frac_fp32_mfma_peak": size_fractions(n2, 1e3 * d2 / k3)["frac_fp32_mfma_peak"]}
-                if n2 <= 24000:
-                    # mid-size bags leave CUs idle one at a time (39 rows per CU at 10k): the aggregate rate with four bags
-                    # in flight on four streams (pipeline.BagsInFlight, a distinct resident bag per stream)
-                    d4 = time_steps(make_step_inflight(model, x2, dev, 1, 4), k3, args.warmup, 1)
-                    sweep[str(n2)]["four_in_flight_ms_per_bag"] = 1e3 * d4 / k3
-                    sweep[str(n2)]["four_in_flight_frac_fp32_mfma_peak"] = size_fractions(n2, 1e3 * d4 / k3)["frac_fp32_mfma_peak"]
-                    for p in model.parameters():
-                        p.grad = None
-                del x2
-            out["n_sweep"] = sweep
-            out["graphed_small_bags"] = graph_leg(model, dev, args.steps, g)
-            if not bf16 and args.gemm == "f32":
-                # two bags in flight: this mode keeps the package at its power limit by itself (1,907 bags/s with two,
-                # 1,875 with three, 1,844 with four in the same run)
-                out["gemm_bf16x3"] = gemm_bf16x3_leg(model, x, dev, args.steps, args.warmup, min(inflight, 2))
-                # the same two headline figures in that mode, at top level beside `value` (never instead of it)
-                out["value_gemm_bf16x3"] = out["gemm_bf16x3"]["value"]
-                out["ms_per_step_one_bag_gemm_bf16x3"] = out["gemm_bf16x3"]["ms_per_step_one_bag"]
-            if not bf16 and N == 50000:
-                out["config5_bf16_100k"] = config5_leg(dev, max(10, args.steps), args.warmup, g)
-                out["other_configs"] = other_configs_leg(dev, max(10, min(args.steps, 30)), args.warmup, g)
-        if args.h2d and args.extras and world == 1:
-            out["pcie_inclusive"] = h2d_leg(model, N, dev, max(10, min(args.steps, 30)), args.warmup, bf16)
-        if world == 1 and not args.no_cpu_baseline and not bf16:
-            # the CPU leg runs LAST (nothing on the GPU waits behind it): the metric's bag first, then north_star's other two
-            # sizes (BASELINE config 1 is the 1000 x 1024 CPU run) beside the GPU figures of `other_sizes`
-            out["cpu_baseline"] = cpu_baseline(N, args.cpu_bags)
-            out["gpu_over_cpu"] = value / out["cpu_baseline"]["value"]
-            if args.extras and N == 50000:
-                small = {}
-                for n2, nb in ((10000, 20), (1000, 100)):
-                    cb = cpu_baseline(n2, nb)
-                    gpu = out.get("other_sizes", {}).get(str(n2), {}).get("bags_per_s")
-                    small[str(n2)] = {"value": cb["value"], "unit": "bags/s", "cores": cb["cores"], "kind": "port",
-                                      "value_1_thread": cb["value_1_thread"], "sample": cb["sample"],
-                                      "thread_probe_s_per_bag": cb["thread_probe_s_per_bag"],
-                                      "gpu_bags_per_s": gpu, "gpu_over_cpu": (gpu / cb["value"]) if gpu else None}
-                out["cpu_baseline_other_sizes"] = small
+        if args.full:
+            full_legs(out, args, model, x, dev, flat, g, world, inflight, sizes)
         print(json.dumps(out), flush=True)
     if world > 1:
         import torch.distributed as dist
