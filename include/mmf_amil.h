@@ -241,6 +241,44 @@ int mmf_radio_nll_step_group(const mmf_amil_desc* desc, const mmf_bag_group* gro
                              const mmf_nll_target* target, float* A_raw /* [sum N] */, const mmf_amil_grads* grads,
                              void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Grouped forward-only pass: G bags evaluated with fixed weights in ONE launch chain -- the per-epoch validation pass
+ *   (utils/core_utils.py:267-355), the final summary (:358-430), embedding export (pre_trained_feature.py:116-162) and
+ *   heat-map scoring (utils/heatmap_utils.py:111-150) run one forward per bag in the reference.  The bags are independent
+ *   forward passes on the same weights: the row-parallel GEMMs run once over the concatenated rows with the one-bag plans of
+ *   sum N rows; only pooling and the head are per bag (one workgroup per bag, one launch).  Nothing is kept for a backward.
+ *   x: the bags' rows concatenated, [sum N x L], fp32 or (x_bf16 != 0) bf16 (uint16_t bits; the one-bag bf16 constraints
+ *   L % 64 == 0, H % 256 == 0 apply).  bf16 windows run the unfused bf16 kernels, which the one-bag route runs for every
+ *   stack but the gated one with H = D = 256; that stack's one-bag route takes a fused forward form, which rounds
+ *   differently, so its bf16 windows return MMF_ERR_SHAPE (evaluate those bags one at a time).  desc->N = offsets[G]; desc->seed and desc->seed_dev are not read (no dropout);
+ *   sync and trace as usual.  group->seeds is not read and may be NULL.
+ *   head: the per-bag arrays are G long -- logits, hazards, S [G x K]; Y_hat, risk (optional) [G]; head == NULL: M only
+ *   (embedding export; M must then be given).  target (optional, needs head): each bag's nll_surv VALUE; only Y, c [G],
+ *   alpha, eps and loss [G] are read (dWk, dbk, loss_scale, accumulate are not).  M: [G x H] or NULL (not stored).
+ *   A_raw: [sum N].  What bag g gets -- A_raw rows, M_g, head outputs, loss_g -- is what the one-bag forward-only route
+ *   (mmf_amil[_bf16]_infer, then mmf_surv_head_forward and mmf_nll_surv) computes for that bag alone, to fp32 rounding.
+ *   Eval mode only: desc->p_h and desc->p_att must be 0, else MMF_ERR_ARG; MMF_ERR_ARG also for gemm = MMF_GEMM_BF16X3.
+ *   MMF_ERR_SHAPE for G outside 1..MMF_GROUP_MAX, an empty bag, offsets that are not strictly increasing from 0,
+ *   desc->N != offsets[G], a head with K > 32, a bf16 window of a gated H = D = 256 stack, or totals beyond the limits of
+ *   the one-bag entry points (applied to sum N).
+ *   No workgroup waits for another; calls are deterministic; the call allocates nothing and keeps no state.
+ * mmf_amil_group_infer_workspace_bytes: the workspace of that window, or 0 when the offset table is invalid.  With x_bf16 it
+ *   is at least the fp32 size, so one buffer serves a window of either storage.
+ * mmf_radio_infer_group: the same behind the radiology head's reduce_dim (mmf_radio_nll_step_group's layout; desc->L ==
+ *   kseg, nseg 2..4, fp32); rd->dW / rd->db are not read.  Returns as mmf_amil_infer_group, and as
+ *   mmf_radio_nll_step_group for rd.  mmf_radio_group_infer_workspace_bytes: its workspace, or 0 (invalid table or nseg).
+ * ------------------------------------------------------------------------------------------- */
+size_t mmf_amil_group_infer_workspace_bytes(const int64_t* offsets, int32_t G, int32_t L, int32_t H, int32_t D,
+                                            int32_t gated, int32_t x_bf16);
+int mmf_amil_infer_group(const mmf_amil_desc* desc, const mmf_bag_group* group, const void* x, int32_t x_bf16,
+                         void* workspace, size_t workspace_bytes, const mmf_surv_head* head, const mmf_nll_target* target,
+                         float* M /* [G x H] or NULL */, float* A_raw /* [sum N] */, void* stream);
+size_t mmf_radio_group_infer_workspace_bytes(const int64_t* offsets, int32_t G, int32_t nseg, int32_t kseg, int32_t H,
+                                             int32_t D, int32_t gated);
+int mmf_radio_infer_group(const mmf_amil_desc* desc, const mmf_bag_group* group, const mmf_radio_reduce* rd,
+                          void* workspace, size_t workspace_bytes, const mmf_surv_head* head,
+                          const mmf_nll_target* target, float* M, float* A_raw, void* stream);
+
 /* The hazard head's training step on a feature vector that is already on the device: what
  *   `hazards, S, Y_hat = head(classifier(feat)); loss = NLLSurvLoss(alpha)(hazards, S, Y, c); (loss * loss_scale).backward()`
  * computes between the embedding and the loss (models/model_mm_attention_mil.py:190-191 with fusion = 'concat': feat is the

@@ -115,6 +115,16 @@ SYMBOLS = {
                                            C.POINTER(AmilGrads), C.c_void_p]),
     "mmf_surv_head_nll_step": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(SurvHead), C.POINTER(NllTarget), C.c_void_p,
                                          C.c_void_p]),
+    "mmf_amil_group_infer_workspace_bytes": (C.c_size_t, [C.POINTER(C.c_int64), C.c_int32, C.c_int32, C.c_int32,
+                                                           C.c_int32, C.c_int32, C.c_int32]),
+    "mmf_amil_infer_group": (C.c_int, [C.POINTER(AmilDesc), C.POINTER(BagGroup), C.c_void_p, C.c_int32, C.c_void_p,
+                                       C.c_size_t, C.POINTER(SurvHead), C.POINTER(NllTarget), C.c_void_p, C.c_void_p,
+                                       C.c_void_p]),
+    "mmf_radio_group_infer_workspace_bytes": (C.c_size_t, [C.POINTER(C.c_int64), C.c_int32, C.c_int32, C.c_int32,
+                                                            C.c_int32, C.c_int32, C.c_int32]),
+    "mmf_radio_infer_group": (C.c_int, [C.POINTER(AmilDesc), C.POINTER(BagGroup), C.POINTER(RadioReduce), C.c_void_p,
+                                        C.c_size_t, C.POINTER(SurvHead), C.POINTER(NllTarget), C.c_void_p, C.c_void_p,
+                                        C.c_void_p]),
     "mmf_amil_infer_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "mmf_amil_infer": (C.c_int, [C.POINTER(AmilDesc), C.c_void_p, C.c_void_p, C.c_size_t,
                                  C.c_void_p, C.c_void_p, C.c_void_p]),

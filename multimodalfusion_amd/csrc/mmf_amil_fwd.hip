@@ -1188,4 +1188,111 @@ int launch_group_pool(PoolParams p, const SegTable& s, hipStream_t st) {
   return hipGetLastError() == hipSuccess ? MMF_OK : MMF_ERR_LAUNCH;
 }
 
+// ---- forward-only grouped pass (mmf_amil_infer_group) ----------------------------------------------------------------
+// One workgroup per bag: merge the bag's partials into M_g (written when p.M is given), then the classifier, hazards, S,
+// Y_hat, risk and -- when labels are given -- the bag's nll_surv value.  No dM, no classifier gradient.  The merge is
+// group_tail_kernel's: the same partials (group_plan: at most GROUP_BAG_MAX_PARTIALS per bag), the same weights in LDS,
+// the same order of additions.
+__global__ __launch_bounds__(1024) void group_infer_tail_kernel(PoolParams p, SegTable s) {
+  __shared__ float Ml[1024];
+  __shared__ float wl[GROUP_BAG_MAX_PARTIALS];
+  __shared__ float z[32], hz[32], Sv[32];
+  __shared__ float red[32];
+  const int g = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int gb = s.gbeg[g], n = s.gbeg[g + 1] - gb, H = p.H;
+  const HeadTail& t = p.tail;
+  const int K = t.K;
+  const int stride = 2 + H;
+  const float* part = p.partials + (size_t)gb * stride;
+  float m = -INFINITY;
+  for (int i = tid; i < n; i += 1024) m = fmaxf(m, part[(size_t)i * stride]);
+  m = wave_max(m);
+  if (lane == 0) red[wave] = m;
+  __syncthreads();
+  m = red[0];
+#pragma unroll
+  for (int i = 1; i < 16; ++i) m = fmaxf(m, red[i]);
+  float l = 0.f;
+  for (int i = tid; i < n; i += 1024) {
+    const float mg = part[(size_t)i * stride];
+    const float w = mg > -INFINITY ? __expf(mg - m) : 0.f;
+    wl[i] = w;
+    l += part[(size_t)i * stride + 1] * w;
+  }
+  l = wave_sum(l);
+  if (lane == 0) red[16 + wave] = l;
+  __syncthreads();
+  l = 0.f;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) l += red[16 + i];
+  if (tid < H) {                           // pool_merge_kernel's order: 32 interleaved slices, then the slices in order
+    const float* col = part + 2 + tid;
+    float acc = 0.f;
+    for (int sl = 0; sl < 32; ++sl) {
+      float a = 0.f;
+      for (int i = sl; i < n; i += 32) a += col[(size_t)i * stride] * wl[i];
+      acc += a;
+    }
+    const float mv = acc / l;
+    if (p.M) p.M[(size_t)g * H + tid] = mv;
+    Ml[tid] = mv;
+  }
+  if (!t.Wk) return;
+  __syncthreads();
+  for (int k = wave; k < K; k += 16) {               // logit k on wave k % 16
+    float acc = 0.f;
+    for (int c = lane; c < H; c += 64) acc += Ml[c] * t.Wk[(size_t)k * H + c];
+    acc = wave_sum(acc);
+    if (lane == 0) z[k] = acc + t.bk[k];
+  }
+  __syncthreads();
+  if (tid != 0) return;
+  float run = 1.f, best = -INFINITY, ssum = 0.f;
+  int arg = 0;
+  for (int k = 0; k < K; ++k) {                      // head_tail's forward, into bag g's rows
+    const float zz = z[k];
+    hz[k] = 1.0f / (1.0f + expf(-zz));
+    run *= (1.0f - hz[k]);
+    Sv[k] = run;
+    ssum += run;
+    t.logits[(size_t)g * K + k] = zz; t.hazards[(size_t)g * K + k] = hz[k]; t.S[(size_t)g * K + k] = run;
+    if (zz > best) { best = zz; arg = k; }
+  }
+  t.Y_hat[g] = arg;
+  if (t.risk) t.risk[g] = -ssum;
+  if (!t.Y) return;
+  const long long y64 = (long long)t.Y[g];
+  float loss;
+  if (y64 < 0 || y64 >= K) {                         // as head_tail: an out-of-range label poisons the value only
+    loss = __builtin_nanf("");
+  } else {
+    const int y = (int)y64;
+    const float c = t.c[g];
+    const float sp_y = y == 0 ? 1.0f : Sv[y - 1];
+    const float unc = -(1.f - c) * (logf(fmaxf(sp_y, t.eps)) + logf(fmaxf(hz[y], t.eps)));
+    const float cen = -c * logf(fmaxf(Sv[y], t.eps));
+    loss = (1.f - t.alpha) * (cen + unc) + t.alpha * unc;
+  }
+  t.loss[g] = loss;
+}
+
+int launch_group_pool_partial(PoolParams p, const SegTable& s, hipStream_t st) {
+  if (p.H != 256 && p.H != 512 && p.H != 1024) return MMF_ERR_SHAPE;
+  if (s.G < 1 || s.G > GROUP_MAX || s.rows_per_group < 1 || s.rows_per_group > POOL_MAX_ROWS) return MMF_ERR_SHAPE;
+  ProfScope ps("group_pool_partial_kernel", st);
+  hipLaunchKernelGGL(group_pool_partial_kernel, dim3(s.gbeg[s.G]), dim3(256), 0, st, p, s);
+  return hipGetLastError() == hipSuccess ? MMF_OK : MMF_ERR_LAUNCH;
+}
+
+int launch_group_infer_tail(PoolParams p, const SegTable& s, hipStream_t st) {
+  if (p.H != 256 && p.H != 512 && p.H != 1024) return MMF_ERR_SHAPE;
+  if (s.G < 1 || s.G > GROUP_MAX) return MMF_ERR_SHAPE;
+  if (p.tail.Wk && (p.tail.K < 1 || p.tail.K > 32)) return MMF_ERR_SHAPE;
+  for (int g = 0; g < s.G; ++g)
+    if (s.gbeg[g + 1] - s.gbeg[g] > GROUP_BAG_MAX_PARTIALS) return MMF_ERR_SHAPE;
+  ProfScope ps("group_infer_tail_kernel", st);
+  hipLaunchKernelGGL(group_infer_tail_kernel, dim3(s.G), dim3(1024), 0, st, p, s);
+  return hipGetLastError() == hipSuccess ? MMF_OK : MMF_ERR_LAUNCH;
+}
+
 }  // namespace mmf

@@ -988,6 +988,194 @@ int mmf_radio_nll_step_group(const mmf_amil_desc* d, const mmf_bag_group* group,
   return rl.launch(target->accumulate ? 1 : 0, st);
 }
 
+// ---- forward-only grouped pass: the bags of an evaluation window as one launch chain -----------------------------
+namespace mmf {
+// the window's forward-only workspace: the one-bag inference carve of R rows (fp32, or bf16: no SEG tables, no masks) and
+// the per-bag pooling partials
+struct GroupInferWs {
+  AmilWs w;
+  AmilWsBf wb;
+  float* partials;
+  size_t bytes;
+};
+static GroupInferWs carve_group_infer(Carver& c, const SegTable& s, int L, int H, int D, int gated, int bf16) {
+  GroupInferWs g{};
+  const int64_t R = s.off[s.G];
+  if (bf16) {
+    g.wb = carve_bf16(reinterpret_cast<void*>(c.base + c.off), R, L, H, D, gated, true);
+    c.off += g.wb.bytes;
+  } else {
+    g.w = carve(c, R, L, H, D, gated, true);
+  }
+  g.partials = c.take<float>((size_t)s.gbeg[s.G] * (2 + H));
+  g.bytes = c.off;
+  return g;
+}
+
+// A bf16 stack whose one-bag route takes a fused forward form (amil_bf16_forward_impl: gated, H = D = 256).  The grouped
+// pass runs the unfused bf16 kernels, which give such a bag other bf16 roundings than its one-bag route, so it refuses
+// those windows; every other bf16 stack takes the unfused kernels one bag at a time too.
+static bool infer_group_bf16_fused(const mmf_amil_desc* d) {
+  return d->gated && d->H == 256 && d->D == 256;
+}
+
+// the call contract both forward-only grouped entry points share; fills the segment table and the head (no gradients)
+static int infer_group_check(const mmf_amil_desc* d, const mmf_bag_group* group, const void* x, int bf16,
+                             const void* workspace, const mmf_surv_head* head, const mmf_nll_target* target,
+                             const float* M, const float* A_raw, SegTable& s, HeadTail& tl) {
+  if (!d || !group) return MMF_ERR_ARG;
+  if (d->gemm != MMF_GEMM_F32 || d->p_h != 0.f || d->p_att != 0.f) return MMF_ERR_ARG;
+  if (int e = group_plan(group->offsets, group->G, s)) return e;
+  if (d->N != s.off[s.G]) return MMF_ERR_SHAPE;
+  if (int e = bf16 ? check_desc_bf16(d) : check_desc(d)) return e;
+  if (bf16 && infer_group_bf16_fused(d)) return MMF_ERR_SHAPE;
+  tl = HeadTail{};
+  if (head) {
+    if (!head->Wk || !head->bk || !head->logits || !head->hazards || !head->S || !head->Y_hat) return MMF_ERR_ARG;
+    if (head->K < 1 || head->K > 32) return MMF_ERR_SHAPE;
+    tl.Wk = head->Wk; tl.bk = head->bk; tl.K = head->K;
+    tl.logits = head->logits; tl.hazards = head->hazards; tl.S = head->S; tl.Y_hat = head->Y_hat; tl.risk = head->risk;
+    if (target) {
+      if (!target->Y || !target->c || !target->loss) return MMF_ERR_ARG;
+      tl.Y = target->Y; tl.c = target->c; tl.alpha = target->alpha; tl.eps = target->eps; tl.loss = target->loss;
+    }
+  } else if (target || !M) {
+    return MMF_ERR_ARG;             // a loss needs the head; without a head the call exists for M
+  }
+  if (!x || !workspace || !A_raw) return MMF_ERR_ARG;
+  if (!aligned16(x) || !aligned16(workspace)) return MMF_ERR_ALIGN;
+  if (!bf16 && (!aligned16(d->W1) || !aligned16(d->Wa) || (d->gated && !aligned16(d->Wb)))) return MMF_ERR_ALIGN;
+  return MMF_OK;
+}
+
+// the fp32 chain over the window's rows x [R x L]: projection and gate with the one-bag plans of R rows (rows are
+// independent, nothing is masked), the pooling partials per bag, the forward-only tail per bag
+static int group_infer_chain(const mmf_amil_desc* d, const SegTable& s, const float* x, const GroupInferWs& gw,
+                             const HeadTail& tl, float* M, float* A_raw, hipStream_t st) {
+  const AmilWs& w = gw.w;
+  if (int e = launch_linear(stack_linear(d, w, x, 0), st)) return e;
+  if (int e = launch_gate_fwd(stack_gate_fwd(d, w, 0), st)) return e;
+  PoolParams pp = stack_pool(d, w, A_raw);
+  pp.partials = gw.partials; pp.M = M; pp.tail = tl;
+  if (int e = launch_group_pool_partial(pp, s, st)) return e;
+  return launch_group_infer_tail(pp, s, st);
+}
+
+// the bf16 chain (stacks whose one-bag route is unfused: infer_group_bf16_fused): weight conversion once per window, then
+// the same unfused bf16 kernels over all R rows (their tiles may straddle bags: rows are independent), the pooling
+// partials per bag from the bf16 h, the forward-only tail per bag
+static int group_infer_chain_bf16(const mmf_amil_desc* d, const SegTable& s, const uint16_t* x, const GroupInferWs& gw,
+                                  const HeadTail& tl, float* M, float* A_raw, hipStream_t st) {
+  const AmilWsBf& w = gw.wb;
+  CvtParams cp{};
+  cp.seg[cp.nseg++] = CvtSeg{d->W1, w.w1, d->H, d->L, d->L, 0, 0, 0};
+  cp.seg[cp.nseg++] = CvtSeg{d->Wa, w.wab, d->D, d->H, d->H, 0, 0, 0};
+  if (d->gated) cp.seg[cp.nseg++] = CvtSeg{d->Wb, w.wab + (size_t)d->D * d->H, d->D, d->H, d->H, 0, 0, 0};
+  if (int e = launch_cvt_bf16(cp, st)) return e;
+
+  LinearBfParams lp{};
+  lp.x = x; lp.w = w.w1; lp.bias = d->b1; lp.y = w.h;
+  lp.M = d->N; lp.N = d->H; lp.K = d->L;
+  lp.drop_p = 0.f; lp.drop_key = drop_key(0, 0); lp.seed_dev = nullptr;
+  if (int e = launch_linear_bf16(lp, st)) return e;
+
+  GateBfParams gp{};
+  gp.h = w.h; gp.Wa = w.wab; gp.Wb = d->gated ? w.wab + (size_t)d->D * d->H : nullptr;
+  gp.ba = d->ba; gp.bb = d->bb; gp.Wc = d->Wc;
+  gp.a = w.a; gp.b = w.b; gp.s_part = w.s_part;           // a / b are null: carved for inference
+  gp.N = d->N; gp.H = d->H; gp.D = d->D; gp.gated = d->gated;
+  gp.drop_p = 0.f; gp.key_a = drop_key(0, 1); gp.key_b = drop_key(0, 2); gp.seed_dev = nullptr;
+  if (int e = launch_gate_bf16(gp, st)) return e;
+
+  PoolBfParams pb{};
+  PoolParams& pp = pb.base;
+  pp.s_part = w.s_part; pp.n_parts = w.parts; pp.bc = d->bc; pp.h = nullptr; pp.N = d->N; pp.H = d->H;
+  pp.A_raw = A_raw; pp.partials = gw.partials; pp.M = M; pp.tail = tl;
+  pb.h = w.h;
+  if (int e = launch_group_pool_partial_bf16(pb, s, st)) return e;
+  return launch_group_infer_tail(pp, s, st);
+}
+}  // namespace mmf
+
+size_t mmf_amil_group_infer_workspace_bytes(const int64_t* offsets, int32_t G, int32_t L, int32_t H, int32_t D,
+                                            int32_t gated, int32_t x_bf16) {
+  SegTable s;
+  if (group_plan(offsets, G, s)) return 0;
+  Carver c;
+  const size_t f32 = carve_group_infer(c, s, L, H, D, gated, 0).bytes;
+  if (!x_bf16) return f32;
+  Carver cb;
+  const size_t b16 = carve_group_infer(cb, s, L, H, D, gated, 1).bytes;
+  return b16 > f32 ? b16 : f32;        // one buffer serves a window of either storage (header)
+}
+
+int mmf_amil_infer_group(const mmf_amil_desc* d, const mmf_bag_group* group, const void* x, int32_t x_bf16,
+                         void* workspace, size_t workspace_bytes, const mmf_surv_head* head, const mmf_nll_target* target,
+                         float* M, float* A_raw, void* stream) {
+  SegTable s;
+  HeadTail tl;
+  const int bf16 = x_bf16 ? 1 : 0;
+  if (int e = infer_group_check(d, group, x, bf16, workspace, head, target, M, A_raw, s, tl)) return e;
+  Carver c(workspace);
+  const GroupInferWs gw = carve_group_infer(c, s, d->L, d->H, d->D, d->gated, bf16);
+  if (gw.bytes > workspace_bytes) return MMF_ERR_WORKSPACE;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  TraceScope ts(d->trace);
+  return bf16 ? group_infer_chain_bf16(d, s, static_cast<const uint16_t*>(x), gw, tl, M, A_raw, st)
+              : group_infer_chain(d, s, static_cast<const float*>(x), gw, tl, M, A_raw, st);
+}
+
+size_t mmf_radio_group_infer_workspace_bytes(const int64_t* offsets, int32_t G, int32_t nseg, int32_t kseg, int32_t H,
+                                             int32_t D, int32_t gated) {
+  SegTable s;
+  if (group_plan(offsets, G, s) || nseg < 2 || nseg > 4 || kseg < 1) return 0;
+  const int64_t R = s.off[s.G];
+  Carver c;
+  carve_group_infer(c, s, kseg, H, D, gated, 0);
+  c.take<float>((size_t)R * kseg);                                            // reduce_dim's output
+  const size_t kf = linear_ksplit_floats(R, kseg, nseg * kseg, nseg, kseg);  // its K-split partial tiles
+  if (kf) c.take<float>(kf);
+  return c.off;
+}
+
+int mmf_radio_infer_group(const mmf_amil_desc* d, const mmf_bag_group* group, const mmf_radio_reduce* rd,
+                          void* workspace, size_t workspace_bytes, const mmf_surv_head* head,
+                          const mmf_nll_target* target, float* M, float* A_raw, void* stream) {
+  if (!rd || !rd->x) return MMF_ERR_ARG;
+  if (rd->nseg < 2 || rd->nseg > 4) return MMF_ERR_SHAPE;
+  SegTable s;
+  HeadTail tl;
+  if (int e = infer_group_check(d, group, rd->x[0], 0, workspace, head, target, M, A_raw, s, tl)) return e;
+  const int nseg = rd->nseg, kseg = rd->kseg, L = d->L;
+  if (kseg != L) return MMF_ERR_SHAPE;
+  const int64_t R = d->N;
+  if (R * nseg * (int64_t)kseg * 4 >= (int64_t)1 << 31) return MMF_ERR_SHAPE;     // the [sum N x nseg*kseg] input < 2 GiB
+  if (!rd->W || !rd->bias) return MMF_ERR_ARG;
+  for (int m = 0; m < nseg; ++m)
+    if (!rd->x[m]) return MMF_ERR_ARG;
+  for (int m = 0; m < nseg; ++m)
+    if (!aligned16(rd->x[m])) return MMF_ERR_ALIGN;
+  if (!aligned16(rd->W)) return MMF_ERR_ALIGN;
+  Carver c(workspace);
+  const GroupInferWs gw = carve_group_infer(c, s, L, d->H, d->D, d->gated, 0);
+  float* xr = c.take<float>((size_t)R * L);
+  const size_t kf = linear_ksplit_floats(R, L, nseg * kseg, nseg, kseg);
+  float* kpart = kf ? c.take<float>(kf) : nullptr;
+  if (c.off > workspace_bytes) return MMF_ERR_WORKSPACE;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  TraceScope ts(d->trace);
+
+  // reduce_dim over the modality segments, every row of the window: mmf_linear_forward's plan
+  LinearParams lr{};
+  for (int m = 0; m < nseg; ++m) lr.x[m] = rd->x[m];
+  lr.nseg = nseg; lr.kseg = kseg; lr.ldx = kseg;
+  lr.w = rd->W; lr.bias = rd->bias; lr.y = xr; lr.M = R; lr.N = L; lr.K = nseg * kseg;
+  lr.act = ACT_NONE; lr.drop_p = 0.f; lr.drop_key = drop_key(0, 0); lr.seed_dev = nullptr;
+  if (kpart && d->sync && d->sync_words > 0) { lr.kpart = kpart; lr.ktick = d->sync; lr.ktick_words = d->sync_words; }
+  if (int e = launch_linear(lr, st)) return e;
+  return group_infer_chain(d, s, xr, gw, tl, M, A_raw, st);
+}
+
 int mmf_surv_head_nll_step(const float* feat, int32_t F, const mmf_surv_head* head, const mmf_nll_target* target,
                            float* dfeat, void* stream) {
   if (!feat || !target || !dfeat) return MMF_ERR_ARG;

@@ -111,6 +111,8 @@ int launch_linear_bf16(LinearBfParams p, hipStream_t st);
 int gate_parts_bf16(int D, int gated);
 int launch_gate_bf16(GateBfParams p, hipStream_t st);
 int launch_pool_bf16(PoolBfParams p, hipStream_t st);
+// forward-only grouped pass: the pooling partials of every bag of a window (partials never straddle a bag; SegTable)
+int launch_group_pool_partial_bf16(PoolBfParams p, const SegTable& s, hipStream_t st);
 struct FusedFwdParams {     // fused forward (H = 256): instance projection + gate scoring + pooling partials
   const bf16_t* x; const bf16_t* w1; const float* b1;
   const bf16_t *Wa, *Wb; const float *ba, *bb, *Wc, *bc;

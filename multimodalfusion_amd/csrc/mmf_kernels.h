@@ -286,6 +286,11 @@ int launch_group_rows(const GroupRowsParams& p, hipStream_t st);
 int launch_group_pool(PoolParams p, const SegTable& s, hipStream_t st);
 // ds_i / p_i with the statistics, M and dM of row i's bag
 int launch_group_bwd_prep(BwdPrepParams p, const int* bag, hipStream_t st);
+// forward-only grouped pass (mmf_amil_infer_group): the pooling partials of launch_group_pool alone, and a tail of one
+// workgroup per bag that merges the bag's partials into M_g (p.M [G x H], or null: not stored) and runs the head's
+// forward (p.tail per-bag outputs as in launch_group_pool; Y given: loss [G] only; dM / dWk / dbk are not read)
+int launch_group_pool_partial(PoolParams p, const SegTable& s, hipStream_t st);
+int launch_group_infer_tail(PoolParams p, const SegTable& s, hipStream_t st);
 int set_dyn_lds(const void* kern, int bytes);
 
 // Optional per-kernel timing with HIP events on the launch stream: records into the mmf_trace of the ABI call in

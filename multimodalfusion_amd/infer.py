@@ -40,25 +40,115 @@ def extract_features(model, **inputs) -> torch.Tensor:
         model.train(was_training)
 
 
-def extract_features_for_subjects(models: dict, subjects, skip=lambda subject_id, modality: False):
+class _ExportGroup:
+    """extract_features_for_subjects(group=True): one head's bags held on the device for one grouped forward-only call
+    (model.forward_group(..., return_features=True)); `entries` are the output slots the call fills."""
+
+    def __init__(self, model):
+        self.model, self.bags, self.entries, self.rows, self.limit = model, [], [], 0, None
+
+    def takes(self, xs):
+        """xs: the bag's tensors (one per modality), or None when the grouped pass does not take the bag."""
+        from .utils.core_utils import _EvalGroup
+        if xs is None:
+            return False
+        limit = _EvalGroup.row_limit(self.model, len(xs), int(xs[0].shape[1]), xs[0].dtype)
+        return int(xs[0].shape[0]) <= limit and (not self.bags or self.bags[0][0].dtype == xs[0].dtype)
+
+    def full(self, xs):
+        from . import ops
+        from .utils.core_utils import _EvalGroup
+        limit = _EvalGroup.row_limit(self.model, len(xs), int(xs[0].shape[1]), xs[0].dtype)
+        return bool(self.bags) and (len(self.bags) >= ops.GROUP_MAX or self.rows + int(xs[0].shape[0]) > limit
+                                    or self.bags[0][0].dtype != xs[0].dtype)
+
+    def add(self, xs, entry):
+        dev = _dev(self.model)
+        self.bags.append([x.to(dev) for x in xs])
+        self.entries.append(entry)
+        self.rows += int(xs[0].shape[0])
+
+    def run(self):
+        if not self.bags:
+            return
+        model = self.model
+        was_training = model.training
+        model.eval()
+        try:
+            if hasattr(model, "attention_net_radio"):
+                bags = [dict(zip(model.modalities, b)) for b in self.bags]
+            else:
+                bags = [b[0] for b in self.bags]
+            M = model.forward_group(bags, return_features=True).cpu()
+        finally:
+            model.train(was_training)
+        for g, entry in enumerate(self.entries):
+            entry[2] = M[g:g + 1]
+        self.bags, self.entries, self.rows = [], [], 0
+
+
+def extract_features_for_subjects(models: dict, subjects, skip=lambda subject_id, modality: False, group=False):
     """The export loop of pre_trained_feature.py:116-162 over an iterable of
     (subject_id, radio_features: dict, path_features, genomic_features) tuples.  `models` maps
     'path' / 'radio' / 'omic' to loaded heads (any subset).  A modality whose tensor is the reference's
     "missing" sentinel (`torch.zeros((1, 1))`, pre_trained_feature.py:122,135,153) is skipped.
-    Yields (subject_id, modality, features_cpu)."""
+    Yields (subject_id, modality, features_cpu).
+    group=True: the path / radio bags of consecutive subjects are embedded by grouped forward-only calls
+    (model.forward_group, up to ops.GROUP_MAX bags or the row limit each); the same items in the same order, each
+    embedding what the per-subject call gives to fp32 rounding.  A bag the grouped pass does not take runs alone."""
+    from .utils.core_utils import _eval_group_bags
     sentinel = torch.zeros((1, 1))
 
     def missing(t):
         return tuple(t.shape) == (1, 1) and torch.equal(t.detach().float().cpu(), sentinel)
 
+    groups = {m: _ExportGroup(models[m]) for m in ("path", "radio") if group and m in models}
+    pending = []                 # [subject_id, modality, features or None] in output order
+
+    def drain():
+        for g in groups.values():
+            g.run()
+        out = [tuple(e) for e in pending]
+        pending.clear()
+        return out
+
+    def item(subject_id, modality, xs, compute):
+        g = groups.get(modality)
+        if g is None or not g.takes(xs):
+            if not pending:
+                return [(subject_id, modality, compute())]
+            pending.append([subject_id, modality, compute()])
+            return []
+        out = drain() if g.full(xs) else []
+        entry = [subject_id, modality, None]
+        pending.append(entry)
+        g.add(xs, entry)
+        return out
+
     for subject_id, radio_features, path_features, genomic_features in subjects:
         if "path" in models and path_features is not None and not missing(path_features) and not skip(subject_id, "path"):
-            yield subject_id, "path", extract_features(models["path"], path_features=path_features)
+            xs = _eval_group_bags(models["path"], {}, path_features) if "path" in groups else None
+            yield from item(subject_id, "path", xs, lambda: extract_features(models["path"], path_features=path_features))
         if ("radio" in models and radio_features and not all(missing(r) for r in radio_features.values())
                 and not skip(subject_id, "radio")):
-            yield subject_id, "radio", extract_features(models["radio"], **radio_features)
+            xs = _eval_group_bags(models["radio"], radio_features, None) if "radio" in groups else None
+            yield from item(subject_id, "radio", xs, lambda: extract_features(models["radio"], **radio_features))
         if "omic" in models and genomic_features is not None and not missing(genomic_features) and not skip(subject_id, "omic"):
-            yield subject_id, "omic", extract_features(models["omic"], genomic_features=genomic_features)
+            yield from item(subject_id, "omic", None,
+                            lambda: extract_features(models["omic"], genomic_features=genomic_features))
+    yield from drain()
+
+
+def _no_grad_iter(it):
+    """Items of a generator, each produced under torch.no_grad()."""
+    it = iter(it)
+    while True:
+        with torch.no_grad():
+            try:
+                A = next(it)
+            except StopIteration:
+                return
+        yield A
 
 
 def infer_patient(model, features, bins=None, label=None, verbose=False):
@@ -83,19 +173,65 @@ def infer_patient(model, features, bins=None, label=None, verbose=False):
     return Y_hat_model, risk, A_final
 
 
-def score_patch_batches(model, feature_batches, ref_scores=None):
+# score_patch_batches(group=True): rows of one grouped scoring call per 256 hidden units.  Up to 128 projection tiles of 64 x
+# 64 (2,048 rows of the `small` head, 1,024 of `big`) a window of fp32 batches keeps the projection plan of a 512-patch
+# batch -- the same four-way K split, the same order of additions -- and with it every score bit for bit.
+SCORE_GROUP_ROWS_PER_256 = 2048
+
+
+def _scores_grouped(model, feature_batches, dev):
+    """The per-batch scores of score_patch_batches, batch after batch, from grouped forward-only calls
+    (ops.amil_infer_group) over consecutive batches.  The caller advances it under torch.no_grad() (_no_grad_iter)."""
+    from . import ops
+    from .models.model_modules import stack_args
+    from .utils.core_utils import _eval_group_bags, _eval_group_head
+    gated, stack, _, _ = stack_args(model.attention_net_WSI, False)
+    cap = SCORE_GROUP_ROWS_PER_256 * 256 // model.attention_net_WSI[0].out_features
+    held, rows = [], 0
+
+    def run():
+        x = torch.cat(held, 0) if len(held) > 1 else held[0]
+        A = ops.amil_infer_group(x, [int(b.shape[0]) for b in held], stack, gated, want_M=True)[4]
+        held.clear()
+        return A
+
+    kind = _eval_group_head(model)
+    for features in feature_batches:
+        # fp32 batches only: a bf16 batch's scores depend on which bf16 kernels run (fused or not), so it keeps its own call
+        xs = _eval_group_bags(model, {}, features, kind) if kind and features.dtype == torch.float32 else None
+        n = int(features.shape[0]) if torch.is_tensor(features) else 0
+        if xs is None or n > cap:
+            if held:
+                yield from run()
+            rows = 0
+            yield model(path_features=features.to(dev), attention_only=True)
+            continue
+        if held and (len(held) >= ops.GROUP_MAX or rows + n > cap or held[0].dtype != features.dtype):
+            yield from run()
+            rows = 0
+        held.append(features.to(dev))
+        rows += n
+    if held:
+        yield from run()
+
+
+def score_patch_batches(model, feature_batches, ref_scores=None, group=False):
     """Attention scoring of utils/heatmap_utils.py:129-141: for every batch of patch embeddings ([n x 1024], n <= 512
     in the reference) the raw attention scores of `model(path_features=features)`; optionally mapped to percentiles
     of `ref_scores` (score2percentile, heatmap_utils.py:32-34).  Batches are independent bags of the SAME head, so
-    they are simply run back to back on the forward-only kernels; yields one [n x 1] float32 numpy array per batch."""
+    they are simply run back to back on the forward-only kernels; yields one [n x 1] float32 numpy array per batch.
+    group=True: consecutive fp32 batches of the pathology head are scored by grouped forward-only calls of at most
+    SCORE_GROUP_ROWS_PER_256 x 256 / H rows, which give the per-batch scores bit for bit; bf16 batches keep one call each."""
     dev = _dev(model)
     was_training = model.training
     model.eval()
     try:
         ref_sorted = np.sort(np.asarray(ref_scores).reshape(-1)) if ref_scores is not None else None
-        for features in feature_batches:
-            with torch.no_grad():
-                A = model(path_features=features.to(dev), attention_only=True)
+        if group and isinstance(model, MIL_Attention_fc_surv_path):
+            scores = _scores_grouped(model, feature_batches, dev)
+        else:
+            scores = (model(path_features=features.to(dev), attention_only=True) for features in feature_batches)
+        for A in _no_grad_iter(scores):
             A = A.view(-1, 1).cpu().numpy()
             if ref_sorted is not None:
                 # scipy.stats.percentileofscore(ref, score) with the default kind='rank', vectorised

@@ -6,8 +6,8 @@ import torch
 import torch.nn as nn
 
 from ..utils.utils import initialize_weights
-from .model_modules import (AMIL_SIZES, amil_stack, amil_stack_head, amil_stack_nll_step, amil_stack_nll_step_group,
-                            make_amil_stack)
+from .model_modules import (AMIL_SIZES, amil_stack, amil_stack_head, amil_stack_infer_group, amil_stack_nll_step,
+                            amil_stack_nll_step_group, make_amil_stack)
 
 
 class MIL_Attention_fc_path(nn.Module):
@@ -62,3 +62,16 @@ class MIL_Attention_fc_surv_path(MIL_Attention_fc_path):
             raise RuntimeError("nll_step_group needs every parameter of the head to require grad")
         return amil_stack_nll_step_group(self.attention_net_WSI, self.classifier, bags, self.training, labels, censors,
                                          alpha, loss_scale, grad_out, accumulate, seeds)
+
+    def forward_group(self, bags, labels=None, censors=None, alpha=0.0, return_features=False):
+        """The eval-mode forward of G bags in ONE C-ABI call (ops.amil_infer_group) -- validation, summary and export
+        evaluate one bag at a time with fixed weights (utils/core_utils.py:267-430 of the reference), and the bags are
+        independent: the stack's GEMMs run once over all of their rows, pooling and the head per bag.  bags: a list of
+        [N_g x 1024] fp32 / bf16 device tensors or an (x_cat, sizes) pair; labels / censors: G values for each bag's
+        NLLSurvLoss(alpha) value, or None.  Each bag gets what `model(path_features=bag)` gives it under no_grad, to fp32
+        rounding.  Returns (hazards [G x K], S [G x K], Y_hat [G x 1], [A_raw [1 x N_g]], loss [G] or None, risk [G]);
+        return_features: M [G x H], the embeddings `model(..., return_features=True)` returns.  Eval mode only."""
+        if self.training:
+            raise RuntimeError("forward_group is the eval-mode pass: call model.eval() first")
+        return amil_stack_infer_group(self.attention_net_WSI, self.classifier, bags, labels, censors, alpha,
+                                      return_features)

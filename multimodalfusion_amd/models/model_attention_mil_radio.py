@@ -7,8 +7,8 @@ import torch.nn as nn
 
 from .. import ops
 from ..utils.utils import initialize_weights
-from .model_modules import (AMIL_SIZES, amil_stack, amil_stack_head, amil_stack_nll_step, amil_stack_nll_step_group,
-                            hand_over_grads, make_amil_stack, stack_args, step_grad_buffers)
+from .model_modules import (AMIL_SIZES, amil_stack, amil_stack_head, amil_stack_infer_group, amil_stack_nll_step,
+                            amil_stack_nll_step_group, hand_over_grads, make_amil_stack, stack_args, step_grad_buffers)
 
 
 class MIL_Attention_fc_radio(nn.Module):
@@ -115,6 +115,46 @@ class MIL_Attention_fc_surv_radio(MIL_Attention_fc_radio):
             return ops.radio_nll_step_group(xs, sizes, Wr, br, stack, Wk, bk, gated, labels, censors, alpha, grads,
                                             loss_scale=loss_scale, accumulate=accumulate, p_h=p_h, p_att=p_att,
                                             seeds=seeds)
+
+    def _stacked(self, bags):
+        """(per-modality [sum N x k] tensors, sizes) of a list of G {modality: [n_g x k]} dicts or of a pre-stacked
+        (x [n_mod x sum N x k], sizes) pair."""
+        nmod = len(self.modalities)
+        if (isinstance(bags, (tuple, list)) and len(bags) == 2 and torch.is_tensor(bags[0])
+                and isinstance(bags[1], (list, tuple)) and all(isinstance(n, int) for n in bags[1])):
+            x, sizes = bags
+            if x.dim() != 3 or x.shape[0] != nmod:
+                raise ops._lib.MmfError(f"pre-stacked bags must be [{nmod} x sum N x k], got {tuple(x.shape)}")
+            return list(x.unbind(0)), list(sizes)
+        if not all(isinstance(b, dict) for b in bags):
+            raise TypeError("bags: a list of {modality: [n x k]} dicts or an (x [n_mod x sum N x k], sizes) pair")
+        for b in bags:
+            if len({tuple(b[m].shape) for m in self.modalities}) != 1:
+                raise ops._lib.MmfError("the modalities of a bag must have the same [n x k] shape")
+        sizes = [int(b[self.modalities[0]].shape[0]) for b in bags]
+        return [torch.cat([b[m] for b in bags], 0) if len(bags) > 1 else bags[0][m] for m in self.modalities], sizes
+
+    def forward_group(self, bags, labels=None, censors=None, alpha=0.0, return_features=False):
+        """The eval-mode forward of G patients in ONE C-ABI call (ops.radio_infer_group): reduce_dim and the stack's
+        GEMMs once over all rows, pooling and the head per bag.  bags as nll_step_group; labels / censors: G values for
+        each bag's NLLSurvLoss(alpha) value, or None.  One modality (no reduce_dim): the pathology head's grouped pass on
+        it.  Each bag gets what `model(**bag)` gives it under no_grad, to fp32 rounding.  Returns (hazards [G x K],
+        S [G x K], Y_hat [G x 1], [A_raw [1 x N_g]], loss [G] or None, risk [G]); return_features: M [G x H].
+        Eval mode only."""
+        if self.training:
+            raise RuntimeError("forward_group is the eval-mode pass: call model.eval() first")
+        xs, sizes = self._stacked(bags)
+        if len(xs) == 1:
+            return amil_stack_infer_group(self.attention_net_radio, self.classifier, (xs[0], sizes), labels, censors,
+                                          alpha, return_features)
+        gated, stack, _, _ = stack_args(self.attention_net_radio, False)
+        Wr, br = self.reduce_dim.weight, self.reduce_dim.bias
+        with torch.no_grad():
+            if return_features:
+                return ops.radio_infer_group(xs, sizes, Wr, br, stack, gated, want_M=True)[5]
+            hz, S, Y_hat, risk, A, _, loss = ops.radio_infer_group(xs, sizes, Wr, br, stack, gated, self.classifier.weight,
+                                                                   self.classifier.bias, labels, censors, alpha)
+        return hz, S, Y_hat, A, loss, risk
 
     def forward(self, **kwargs):
         bags = [kwargs[m] for m in self.modalities]

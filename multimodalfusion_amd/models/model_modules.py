@@ -369,6 +369,33 @@ def amil_stack_nll_step_group(seq, classifier, bags, training, Y, c, alpha, loss
                                        loss_scale=loss_scale, accumulate=accumulate, p_h=p_h, p_att=p_att, seeds=seeds)
 
 
+def _split_bags(bags):
+    """(x_cat, sizes) of a list / tuple of [N_g x L] tensors (concatenated once on the device) or of a pre-concatenated
+    (x_cat [sum N x L] tensor, sizes) pair."""
+    if (isinstance(bags, (tuple, list)) and len(bags) == 2 and torch.is_tensor(bags[0])
+            and isinstance(bags[1], (list, tuple)) and all(isinstance(n, int) for n in bags[1])):
+        return bags[0], list(bags[1])
+    if not all(torch.is_tensor(b) for b in bags):
+        raise TypeError("bags: a list of [N x L] tensors or an (x_cat, sizes) pair")
+    return (torch.cat(list(bags), 0) if len(bags) > 1 else bags[0]), [int(b.shape[0]) for b in bags]
+
+
+def amil_stack_infer_group(seq, classifier, bags, Y=None, c=None, alpha=0.0, return_features=False):
+    """The eval-mode forward of G bags in ONE C-ABI call (ops.amil_infer_group): what `model(**bag)` (and, with labels,
+    NLLSurvLoss(alpha)) computes for each bag alone under torch.no_grad(), to fp32 rounding.  bags as
+    amil_stack_nll_step_group (fp32 or bf16).  return_features: the pooled embeddings M [G x H] only (the head is not
+    run).  Returns (hazards [G x K], S [G x K], Y_hat [G x 1], [A_raw [1 x N_g]], loss [G] or None, risk [G]), or M."""
+    from .. import ops
+    x_cat, sizes = _split_bags(bags)
+    gated, stack, _, _ = stack_args(seq, False)
+    with torch.no_grad():
+        if return_features:
+            return ops.amil_infer_group(x_cat, sizes, stack, gated, want_M=True)[5]
+        hz, S, Y_hat, risk, A, _, loss = ops.amil_infer_group(x_cat, sizes, stack, gated, classifier.weight,
+                                                               classifier.bias, Y, c, alpha)
+    return hz, S, Y_hat, A, loss, risk
+
+
 def amil_stack_head(seq, classifier, x, training):
     """amil_stack followed by the classifier / hazard head as one autograd node -> (hazards, S, Y_hat, A_raw)."""
     from .. import ops

@@ -473,6 +473,149 @@ def radio_nll_step_group(xs, sizes, Wr, br, stack, Wk, bk, gated, Y, c, alpha, g
     return hz, S, Y_hat, A_list, loss, risk
 
 
+def infer_group_row_limit(L, H, D, bf16=False):
+    """Most rows one forward-only grouped call takes (ops.amil_infer_group): group_row_limit, with the [sum N x *]
+    operands of a bf16 window two bytes wide."""
+    if not bf16:
+        return group_row_limit(L, H, D)
+    return min(((1 << 32) - 1) // max(H, D), ((1 << 31) - 1) // (2 * max(L, 2 * D)), 256 * 8192)
+
+
+def infer_group_takes_bf16(gated, H, D):
+    """Whether ops.amil_infer_group takes bf16 bags on this stack.  It runs the unfused bf16 kernels; a gated stack with
+    H = D = 256 (the `small` head) takes the fused forward forms one bag at a time, which round differently, so the C ABI
+    refuses its bf16 windows (MMF_ERR_SHAPE) and such bags are evaluated one at a time."""
+    return not (gated and H == 256 and D == 256)
+
+
+def radio_infer_group_row_limit(nseg, L, H, D):
+    """Most rows one forward-only grouped radio call takes (ops.radio_infer_group): radio_group_row_limit."""
+    return radio_group_row_limit(nseg, L, H, D)
+
+
+def _infer_table(sizes, rows):
+    """The bag table of a forward-only grouped call (no seeds).  Returns (sizes, offsets, BagGroup)."""
+    sizes = [int(n) for n in sizes]
+    G = len(sizes)
+    if G < 1 or G > GROUP_MAX:
+        raise _lib.MmfError(f"a group holds 1 .. {GROUP_MAX} bags, got {G}")
+    if min(sizes) < 1:
+        raise _lib.MmfError("empty bag in the group")
+    if rows != sum(sizes):
+        raise _lib.MmfError(f"the bags hold {rows} rows, their sizes add up to {sum(sizes)}")
+    offs = (C.c_int64 * (G + 1))()
+    for i, n in enumerate(sizes):
+        offs[i + 1] = offs[i] + n
+    grp = _lib.BagGroup(G=G, offsets=offs, seeds=None)
+    grp._keep = (offs,)
+    return sizes, offs, grp
+
+
+def _infer_head(head, Y, c, alpha, eps, G, dev):
+    """The per-bag head outputs of a forward-only grouped call and its SurvHead / NllTarget (None where not asked for).
+    Returns (hd, tg, (hazards, S, Y_hat, risk, loss), keep)."""
+    if head is None:
+        if Y is not None:
+            raise _lib.MmfError("a loss needs the classifier head")
+        return None, None, (None,) * 5, ()
+    Wk, bk = head
+    K = Wk.shape[0]
+    logits, hz, S = (torch.empty((G, K), dtype=torch.float32, device=dev) for _ in range(3))
+    Y_hat = torch.empty((G, 1), dtype=torch.int64, device=dev)
+    risk = torch.empty((G,), dtype=torch.float32, device=dev)
+    hd = SurvHead(Wk=ptr(Wk), bk=ptr(bk), K=K, logits=ptr(logits), hazards=ptr(hz), S=ptr(S), Y_hat=ptr(Y_hat),
+                  risk=ptr(risk))
+    tg, loss, keep = None, None, (logits,)
+    if Y is not None:
+        Y = torch.as_tensor(Y).reshape(-1)
+        c = torch.as_tensor(c).reshape(-1)
+        if Y.numel() != G or c.numel() != G:
+            raise _lib.MmfError(f"{G} bags need {G} labels and censorships, got {Y.numel()} / {c.numel()}")
+        Y = Y.to(device=dev, dtype=torch.int64).contiguous()       # out-of-range labels: NaN loss, as mmf_nll_surv
+        c = c.to(device=dev, dtype=torch.float32).contiguous()
+        loss = torch.empty((G,), dtype=torch.float32, device=dev)
+        tg = NllTarget(Y=ptr(Y), c=ptr(c), alpha=float(alpha), eps=float(eps), loss_scale=1.0, loss=ptr(loss),
+                       dWk=None, dbk=None, accumulate=0)
+        keep = (logits, Y, c)
+    return hd, tg, (hz, S, Y_hat, risk, loss), keep
+
+
+def amil_infer_group(x_cat, sizes, stack, gated, Wk=None, bk=None, Y=None, c=None, alpha=0.0, want_M=False, eps=1e-7):
+    """G bags evaluated with fixed weights in ONE C-ABI call (include/mmf_amil.h: mmf_amil_infer_group): the stack's
+    GEMMs run once over the concatenated rows, pooling and the head per bag; nothing is saved for a backward, no dropout.
+    x_cat: [sum N x L], fp32 or bf16 (the bf16-storage kernels), the bags' rows in order; sizes: the G bag sizes (host
+    ints; bf16 only where infer_group_takes_bf16); Wk, bk: the classifier (K <= 32), or None for M only; Y, c: G labels /
+    censorships for each bag's
+    NLLSurvLoss(alpha) value, or None.  Returns (hazards [G x K], S [G x K], Y_hat [G x 1], risk [G], [A_raw of bag g:
+    [1 x N_g] views of one buffer], M [G x H] or None, loss [G] or None); the head outputs are None without a head."""
+    bf16 = x_cat.dtype == torch.bfloat16
+    x_cat = x_cat.contiguous() if bf16 else _f32c(x_cat)
+    if x_cat.dim() != 2:
+        raise _lib.MmfError(f"x_cat must be [sum N x L], got {tuple(x_cat.shape)}")
+    R, L = x_cat.shape
+    sizes, offs, grp = _infer_table(sizes, R)
+    G = len(sizes)
+    head = None if Wk is None else (Wk, bk)
+    stack, head, H, D = _stack_operands(stack, L, head, "bags", fused_head=True)
+    if head is None and not want_M:
+        raise _lib.MmfError("nothing to compute: give the classifier or ask for M")
+    dev = x_cat.device
+    hd, tg, (hz, S, Y_hat, risk, loss), _keep = _infer_head(head, Y, c, alpha, eps, G, dev)
+    d = _amil_desc(stack, R, L, H, D, gated, 0.0, 0.0, 0, None)
+    l = lib()
+    nbytes = l.mmf_amil_group_infer_workspace_bytes(offs, G, L, H, D, d.gated, 1 if bf16 else 0)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    M = torch.empty((G, H), dtype=torch.float32, device=dev) if want_M else None
+    A_raw = torch.empty((R,), dtype=torch.float32, device=dev)
+    check(l.mmf_amil_infer_group(C.byref(d), C.byref(grp), ptr(x_cat), 1 if bf16 else 0, ptr(ws), nbytes,
+                                 C.byref(hd) if hd is not None else None, C.byref(tg) if tg is not None else None,
+                                 ptr(M), ptr(A_raw), stream_ptr()), "mmf_amil_infer_group")
+    A_list = [v.view(1, -1) for v in torch.split(A_raw, sizes)]
+    return hz, S, Y_hat, risk, A_list, M, loss
+
+
+def radio_infer_group(xs, sizes, Wr, br, stack, gated, Wk=None, bk=None, Y=None, c=None, alpha=0.0, want_M=False,
+                      eps=1e-7):
+    """The radiology head's G bags evaluated in ONE C-ABI call (include/mmf_amil.h: mmf_radio_infer_group): reduce_dim
+    over the modality segments and the stack's GEMMs once over all rows, pooling and the head per bag.  xs: 2 .. 4
+    modality tensors, each [sum N x k] fp32 (the bags' rows in order); Wr, br: reduce_dim [k x nseg k], [k].  Other
+    arguments and the result as amil_infer_group."""
+    xs = list(xs)
+    nseg = len(xs)
+    if nseg < 2 or nseg > 4:
+        raise _lib.MmfError(f"the grouped radio pass takes 2 .. 4 modalities, got {nseg}")
+    if any(x.dtype != torch.float32 for x in xs):
+        raise _lib.MmfError("the grouped radio pass takes fp32 bags only")
+    xs = [_f32c(x) for x in xs]
+    if any(x.dim() != 2 or tuple(x.shape) != tuple(xs[0].shape) for x in xs):
+        raise _lib.MmfError("every modality must be one [sum N x k] tensor of the same shape")
+    R, kseg = xs[0].shape
+    sizes, offs, grp = _infer_table(sizes, R)
+    G = len(sizes)
+    Wr, br = _f32c(Wr), _f32c(br)
+    head = None if Wk is None else (Wk, bk)
+    stack, head, H, D = _stack_operands(stack, kseg, head, "bags", fused_head=True)
+    if head is None and not want_M:
+        raise _lib.MmfError("nothing to compute: give the classifier or ask for M")
+    if tuple(Wr.shape) != (kseg, nseg * kseg) or tuple(br.shape) != (kseg,):
+        raise _lib.MmfError(f"reduce_dim must be [{kseg} x {nseg * kseg}] with a [{kseg}] bias for {nseg} modalities of {kseg}")
+    dev = xs[0].device
+    hd, tg, (hz, S, Y_hat, risk, loss), _keep = _infer_head(head, Y, c, alpha, eps, G, dev)
+    d = _amil_desc(stack, R, kseg, H, D, gated, 0.0, 0.0, 0, None)
+    segs = (C.c_void_p * nseg)(*[ptr(x) for x in xs])
+    rd = _lib.RadioReduce(x=segs, nseg=nseg, kseg=kseg, W=ptr(Wr), bias=ptr(br), dW=None, db=None)
+    l = lib()
+    nbytes = l.mmf_radio_group_infer_workspace_bytes(offs, G, nseg, kseg, H, D, d.gated)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    M = torch.empty((G, H), dtype=torch.float32, device=dev) if want_M else None
+    A_raw = torch.empty((R,), dtype=torch.float32, device=dev)
+    check(l.mmf_radio_infer_group(C.byref(d), C.byref(grp), C.byref(rd), ptr(ws), nbytes,
+                                  C.byref(hd) if hd is not None else None, C.byref(tg) if tg is not None else None,
+                                  ptr(M), ptr(A_raw), stream_ptr()), "mmf_radio_infer_group")
+    A_list = [v.view(1, -1) for v in torch.split(A_raw, sizes)]
+    return hz, S, Y_hat, risk, A_list, M, loss
+
+
 def amil_head(x, W1, b1, Wa, ba, Wb, bb, Wc, bc, Wk, bk, gated, p_h=0.0, p_att=0.0, seed=0):
     if not torch.is_grad_enabled() and p_h == 0.0 and p_att == 0.0:       # inference consumers: no-save kernels
         M, A_raw = amil_infer(x, W1, b1, Wa, ba, Wb, bb, Wc, bc, gated)

@@ -486,16 +486,172 @@ def train_loop_survival(epoch, model, loader, optimizer, n_classes, mode, writer
     return dict(loss_surv=train_loss_surv, loss=train_loss, c_index=c_index, losses=loss_vals, risks=risks)
 
 
+def _eval_group_head(model):
+    """'path' / 'path_fp32' / 'radio' when the grouped forward-only pass (model.forward_group) computes what
+    `model(**feats)` does under no_grad -- the pathology or radiology head ITSELF (an overridden forward or any hook would
+    be bypassed), a classifier of <= 32 classes, the exact-fp32 GEMM mode -- else None.  'path_fp32': a pathology head
+    whose bf16 bags the grouped pass does not take (ops.infer_group_takes_bf16).  Asked once per pass: none of it changes
+    between bags."""
+    from .. import ops
+    from ..models.model_attention_mil_path import MIL_Attention_fc_surv_path
+    from ..models.model_attention_mil_radio import MIL_Attention_fc_surv_radio
+    import torch.nn.modules.module as tm
+    if ops._gemm != 0 or getattr(getattr(model, "classifier", None), "out_features", 1 << 30) > 32:
+        return None
+    kind = {MIL_Attention_fc_surv_path.forward: "path", MIL_Attention_fc_surv_radio.forward: "radio"}.get(type(model).forward)
+    hooked = lambda m: bool(m._forward_hooks or m._forward_pre_hooks or m._backward_hooks or getattr(m, "_backward_pre_hooks", None))
+    if kind is None or any(hooked(m) for m in model.modules()):
+        return None
+    if tm._global_forward_hooks or tm._global_forward_pre_hooks or tm._global_backward_hooks or getattr(tm, "_global_backward_pre_hooks", None):
+        return None
+    if kind == "path":           # bf16 bags too, unless the head's one-bag bf16 route is a fused form
+        from ..models.model_modules import stack_args
+        gated, stack, _, _ = stack_args(model.attention_net_WSI, False)
+        if not ops.infer_group_takes_bf16(gated, stack[0].shape[0], stack[2].shape[0]):
+            kind = "path_fp32"
+    return kind
+
+
+def _eval_group_bags(model, radio_features, path_features, kind=0):
+    """The bag tensors (one per modality) of a subject the grouped forward-only pass takes, or None: a head it takes
+    (_eval_group_head; `kind`: its answer, when the caller asked already), 2-D bags -- fp32 (or bf16 where the head's kind
+    allows it) for the pathology head, fp32 modalities of one shape for the radiology head.  The bags may still be on the
+    host."""
+    kind = _eval_group_head(model) if kind == 0 else kind
+    if kind in ("path", "path_fp32"):
+        xs = [path_features]
+        dtypes = (torch.float32, torch.bfloat16) if kind == "path" else (torch.float32,)
+        if not (torch.is_tensor(path_features) and path_features.dtype in dtypes):
+            return None
+    elif kind == "radio":
+        xs = [radio_features.get(m) if isinstance(radio_features, dict) else None for m in model.modalities]
+        if any(not (torch.is_tensor(x) and x.dtype == torch.float32) for x in xs):
+            return None
+    else:
+        return None
+    if any(x.dim() != 2 or x.shape != xs[0].shape or x.shape[0] < 1 for x in xs):
+        return None
+    return xs
+
+
+class _EvalGroup:
+    """validate_survival / summary_survival(group=True): the eligible bags of an evaluation pass, held on the device until
+    one grouped forward-only call (model.forward_group) runs them.  One per pass: nothing outlives the pass (an exception
+    leaves no held bags behind, and the buffer is freed with it).  As _BagGroup: each bag is copied straight into its rows
+    of one reusable device buffer [n_mod x rows x L] (fp32, or bf16 pathology bags); a bag that would take the group past
+    ops.GROUP_MAX bags or the row limit, or one of the other storage type, flushes what is held first."""
+
+    def __init__(self):
+        self.buf = None
+        self.reset()
+
+    def reset(self):
+        self.rows, self.sizes, self.labels, self.cs, self.slots = 0, [], [], [], []
+
+    @staticmethod
+    def row_limit(model, nmod, L, dtype):
+        from .. import ops
+        seq = model.attention_net_radio if hasattr(model, "attention_net_radio") else model.attention_net_WSI
+        H, D = seq[0].out_features, seq[3].stack_params()[0].shape[0]
+        if nmod > 1:
+            return ops.radio_infer_group_row_limit(nmod, L, H, D)
+        return ops.infer_group_row_limit(L, H, D, bf16=dtype == torch.bfloat16)
+
+    @staticmethod
+    def limit_of(model, xs, cache):
+        """row_limit for the bag xs, memoised in `cache` (a dict the pass keeps) by modality count, width and dtype."""
+        key = (len(xs), int(xs[0].shape[1]), xs[0].dtype)
+        if key not in cache:
+            cache[key] = _EvalGroup.row_limit(model, *key)
+        return cache[key]
+
+    def add(self, xs, label, c, slot, limit, device, flush):
+        """xs: the bag's [n x L] tensors, one per modality (the pathology head: one); label, c: device tensors."""
+        from .. import ops
+        nmod, n, L, dtype = len(xs), int(xs[0].shape[0]), int(xs[0].shape[1]), xs[0].dtype
+        if device.type == "cuda" and device.index is None:        # compare with the buffer's device, which has its index
+            device = torch.device("cuda", torch.cuda.current_device())
+        if self.sizes and (len(self.sizes) >= ops.GROUP_MAX or self.rows + n > limit or self.buf.dtype != dtype):
+            flush()
+        need = self.rows + n
+        if (self.buf is None or self.buf.shape[0] != nmod or self.buf.shape[2] != L or self.buf.shape[1] < need
+                or self.buf.dtype != dtype or self.buf.device != device):
+            grown = torch.empty((nmod, max(need, 2 * self.buf.shape[1] if self.buf is not None else need), L),
+                                dtype=dtype, device=device)
+            if self.rows:
+                grown[:, :self.rows].copy_(self.buf[:, :self.rows])
+            self.buf = grown
+        for m, x in enumerate(xs):
+            self.buf[m, self.rows:need].copy_(x, non_blocking=True)
+        self.rows = need
+        self.sizes.append(n); self.labels.append(label.reshape(1)); self.cs.append(c.reshape(1)); self.slots.append(slot)
+
+    def run(self, model, loss_alpha=None):
+        """One grouped call over the held bags -> [(slot, hazards [1 x K], S [1 x K], loss (0-dim) or None, risk [1])];
+        loss_alpha: each bag's NLLSurvLoss value with that alpha, or None for no loss.  The group is empty afterwards."""
+        if not self.sizes:
+            return []
+        x = self.buf[:, :self.rows] if hasattr(model, "attention_net_radio") else self.buf[0, :self.rows]
+        want = loss_alpha is not None
+        hz, S, _, _, loss, risk = model.forward_group((x, list(self.sizes)), torch.cat(self.labels) if want else None,
+                                                      torch.cat(self.cs) if want else None,
+                                                      alpha=loss_alpha if want else 0.0)
+        out = [(slot, hz[g:g + 1], S[g:g + 1], loss[g] if want else None, risk[g:g + 1])
+               for g, slot in enumerate(self.slots)]
+        self.reset()
+        return out
+
+
 def validate_survival(cur, epoch, model, loader, n_classes, mode, early_stopping=None, writer=None, loss_fn=None,
-                      reg_fn=None, lambda_reg=0., results_dir=None, t_bin=None):
-    """utils/core_utils.py:267-355: eval-mode forward + loss + c-index (early stopping hook kept)."""
+                      reg_fn=None, lambda_reg=0., results_dir=None, t_bin=None, group=False):
+    """utils/core_utils.py:267-355: eval-mode forward + loss + c-index (early stopping hook kept).
+
+    group=True: the bags the grouped forward-only pass takes (_eval_group_bags) are held on the device and run as one
+    model.forward_group call per ops.GROUP_MAX bags or row limit, flushed at the end; each bag's loss and risk land in its
+    loader slot, so every logged quantity is in the order of the per-bag loop.  A bag it does not take flushes the group
+    and runs alone.  The stock NLLSurvLoss value comes from the grouped call, with the alpha the per-bag branch passes;
+    other losses are called on the bag's slice.  reg_fn(model) is evaluated once per pass (the weights are fixed)."""
     device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
     model.eval()
     losses, regs, all_risk, all_c, all_t = [], [], [], [], []
+    if group:
+        held, reg_once, meta, kind, limits = _EvalGroup(), [], {}, _eval_group_head(model), {}
+        kernel_loss = type(loss_fn) is NLLSurvLoss
+
+        def flush():      # the held bags' losses / risks land in their loader slots
+            for slot, hz_g, S_g, loss_g, _ in held.run(model, 0.0 if kernel_loss else None):
+                label_g, c_g, t_g = meta.pop(slot)
+                if isinstance(loss_fn, CoxSurvLoss):
+                    risk_g = hz_g
+                    loss_g = loss_fn(risks=risk_g, times=torch.as_tensor(np.asarray(t_g)), c=c_g)
+                else:
+                    risk_g = -torch.sum(S_g, dim=1)          # the per-bag branch's expression, on the bag's S
+                    if not kernel_loss:
+                        loss_g = loss_fn(hazards=hz_g, S=S_g, Y=label_g, c=c_g, alpha=0)
+                losses[slot] = loss_g
+                all_risk[slot] = risk_g.reshape(-1)
     with torch.no_grad():
         for (radio_features, path_features, genomic_features, label, event_time, c) in loader:
             if _skip(mode, radio_features, path_features, genomic_features):
                 continue
+            xs = _eval_group_bags(model, radio_features, path_features, kind) if group and kind else None
+            limit = _EvalGroup.limit_of(model, xs, limits) if xs is not None else 0
+            if xs is not None and int(xs[0].shape[0]) <= limit:
+                label, c = label.to(device), c.to(device)
+                slot = len(losses)
+                meta[slot] = (label, c, event_time)
+                held.add(xs, label, c, slot, limit, device, flush)
+                if not reg_once:         # the weights are fixed: one value (one device tensor) for the pass
+                    loss_reg = 0 if reg_fn is None else reg_fn(model) * lambda_reg
+                    reg_once.append(loss_reg if torch.is_tensor(loss_reg) else torch.tensor(float(loss_reg), device=device))
+                losses.append(None)
+                regs.append(reg_once[0])
+                all_risk.append(None)
+                all_c.append(c.reshape(-1))
+                all_t.append(np.asarray(event_time).reshape(-1))
+                continue
+            if group:
+                flush()                  # the bags held so far run first
             feats, label, c = _to_device(radio_features, path_features, genomic_features, label, c, device)
             hazards, S, Y_hat, _ = model(**feats)
             if isinstance(loss_fn, CoxSurvLoss):
@@ -510,6 +666,8 @@ def validate_survival(cur, epoch, model, loader, n_classes, mode, early_stopping
             all_risk.append(risk.reshape(-1))
             all_c.append(c.reshape(-1))
             all_t.append(np.asarray(event_time).reshape(-1))
+        if group:
+            flush()
     n = max(len(losses), 1)
     loss_vals = torch.stack(losses).float().cpu().numpy()
     reg_vals = torch.stack(regs).float().cpu().numpy()
@@ -531,12 +689,14 @@ def validate_survival(cur, epoch, model, loader, n_classes, mode, early_stopping
     return False
 
 
-def summary_survival(model, loader, n_classes, mode, t_bin=None, loss_fn=None):
+def summary_survival(model, loader, n_classes, mode, t_bin=None, loss_fn=None, group=False):
     """utils/core_utils.py:358-430: eval-mode pass over a loader -> (patient_results, c_index).
     risk = the head's scalar output for Cox / ranking losses, -sum(S) for the discrete-hazard losses; subjects whose
     required modality is the "missing" sentinel are skipped exactly as in the reference (:379-386).  Subject ids are
     read from `loader.dataset.slides_radio_data['subject_id']` when the loader has one (the reference requires it),
-    else the running index is used.  One device -> host copy at the end instead of one per subject."""
+    else the running index is used.  One device -> host copy at the end instead of one per subject.
+    group=True: as validate_survival(group=True) -- the bags the grouped forward-only pass takes run as grouped calls,
+    each risk lands in its subject's slot (same ids, same order)."""
     from .loss_utils import RankingSurvLoss
     device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
     model.eval()
@@ -546,6 +706,13 @@ def summary_survival(model, loader, n_classes, mode, t_bin=None, loss_fn=None):
         ids = list(ds.slides_radio_data["subject_id"])
     all_ids, all_risk, all_c, all_t, all_y = [], [], [], [], []
     count = 0
+    head_risk = isinstance(loss_fn, (CoxSurvLoss, RankingSurvLoss))
+    if group:
+        held, kind, limits = _EvalGroup(), _eval_group_head(model), {}
+
+        def flush():      # the held bags' risks land in their subjects' slots (the per-bag expressions, on the bag's slice)
+            for slot, hz_g, S_g, _, _ in held.run(model):
+                all_risk[slot] = (hz_g if head_risk else -torch.sum(S_g, dim=1)).reshape(-1)
     with torch.no_grad():
         for (radio_features, path_features, genomic_features, label, event_time, c) in loader:
             n = len(label)
@@ -553,14 +720,29 @@ def summary_survival(model, loader, n_classes, mode, t_bin=None, loss_fn=None):
             count += n
             if _skip(mode, radio_features, path_features, genomic_features):
                 continue
+            xs = _eval_group_bags(model, radio_features, path_features, kind) if group and kind else None
+            limit = _EvalGroup.limit_of(model, xs, limits) if xs is not None else 0
+            if xs is not None and int(xs[0].shape[0]) <= limit:
+                label, c = label.to(device), c.to(device)
+                held.add(xs, label, c, len(all_risk), limit, device, flush)
+                all_ids.extend(sid)
+                all_risk.append(None)
+                all_c.append(c.reshape(-1))
+                all_t.append(np.asarray(event_time).reshape(-1))
+                all_y.append(label.reshape(-1))
+                continue
+            if group:
+                flush()                  # the bags held so far run first
             feats, label, c = _to_device(radio_features, path_features, genomic_features, label, c, device)
             hazards, S, Y_hat, _ = model(**feats)
-            risk = hazards if isinstance(loss_fn, (CoxSurvLoss, RankingSurvLoss)) else -torch.sum(S, dim=1)
+            risk = hazards if head_risk else -torch.sum(S, dim=1)
             all_ids.extend(sid)
             all_risk.append(risk.reshape(-1))
             all_c.append(c.reshape(-1))
             all_t.append(np.asarray(event_time).reshape(-1))
             all_y.append(label.reshape(-1))
+        if group:
+            flush()
     risks = torch.cat(all_risk).cpu().numpy()
     cens = torch.cat(all_c).cpu().numpy()
     labels = torch.cat(all_y).cpu().numpy()
