@@ -216,6 +216,14 @@ static int check_desc(const mmf_amil_desc* d, int elem_bytes = 4) {
   return MMF_OK;
 }
 
+// the pointers every stack forward takes, and their alignment (the bf16 kernels read converted weights: any alignment)
+static int check_operands(const mmf_amil_desc* d, const void* x, const void* workspace, const float* A_raw, bool bf16) {
+  if (!x || !workspace || !A_raw) return MMF_ERR_ARG;
+  if (!aligned16(x) || !aligned16(workspace)) return MMF_ERR_ALIGN;
+  if (!bf16 && (!aligned16(d->W1) || !aligned16(d->Wa) || (d->gated && !aligned16(d->Wb)))) return MMF_ERR_ALIGN;
+  return MMF_OK;
+}
+
 // ---- the fp32 attention stack's launch parameters ------------------------------------------------------------------
 // Built once from the descriptor, the workspace, the input and the seed of the dropout keys for the one-bag chain
 // (amil_forward_impl / amil_backward_impl) and the grouped chain (group_chain); the standalone scorer (mmf_attn_net_*)
@@ -325,15 +333,21 @@ static void stack_tn(const mmf_amil_desc* d, const AmilWs& w, const float* x, co
   q2.splits = w.splits_g; q2.k_per_split = w.k_per_split_g;
 }
 
+// a stack backward's split-K sums, fp32 or bf16 (W: AmilWs / AmilWsBf): dW1 / db1 over `splits` slabs, the gate's over `splits_g`
+template <class W>
+static void reduce_slabs(const mmf_amil_desc* d, const W& w, const mmf_amil_grads* g, int splits, int splits_g, ReduceList& rl) {
+  const size_t wab_stride = (size_t)w.mstk * d->H;
+  rl.add(w.slab_w1, g->dW1, d->H * d->L, splits, (size_t)d->H * d->L);
+  rl.add(w.slab_wab, g->dWa, d->D * d->H, splits_g, wab_stride);
+  if (d->gated) rl.add(w.slab_wab + (size_t)d->D * d->H, g->dWb, d->D * d->H, splits_g, wab_stride);
+  rl.add(w.cs_b1, g->db1, d->H, splits, d->H);
+  rl.add(w.cs_bab, g->dba, d->D, splits_g, w.mstk);
+  if (d->gated) rl.add(w.cs_bab + d->D, g->dbb, d->D, splits_g, w.mstk);
+}
+
 // the stack's eight sums (six when ungated): its split-K slabs and the dbc partials of K-prep
 static void stack_reduce(const mmf_amil_desc* d, const AmilWs& w, const mmf_amil_grads* g, int dbc_parts, ReduceList& rl) {
-  const size_t wab_stride = (size_t)w.mstk * d->H;
-  rl.add(w.slab_w1, g->dW1, d->H * d->L, w.splits, (size_t)d->H * d->L);
-  rl.add(w.slab_wab, g->dWa, d->D * d->H, w.splits_g, wab_stride);
-  if (d->gated) rl.add(w.slab_wab + (size_t)d->D * d->H, g->dWb, d->D * d->H, w.splits_g, wab_stride);
-  rl.add(w.cs_b1, g->db1, d->H, w.splits, d->H);
-  rl.add(w.cs_bab, g->dba, d->D, w.splits_g, w.mstk);
-  if (d->gated) rl.add(w.cs_bab + d->D, g->dbb, d->D, w.splits_g, w.mstk);
+  reduce_slabs(d, w, g, w.splits, w.splits_g, rl);
   rl.add(w.cs_wc, g->dWc, d->D, w.splits_g, d->D);
   rl.add(w.dbc_part, g->dbc, 1, dbc_parts, 1);
 }
@@ -348,9 +362,8 @@ struct AmilWsBf {
   size_t bytes;
 };
 
-static AmilWsBf carve_bf16(void* base, int64_t N, int L, int H, int D, int gated, bool infer = false) {
+static AmilWsBf carve_bf16(Carver& c, int64_t N, int L, int H, int D, int gated, bool infer = false) {
   AmilWsBf w{};
-  Carver c(base);
   auto take16 = [&](size_t n) { return c.take<bf16_t>(n); };
   auto take32 = [&](size_t n) { return c.take<float>(n); };
   w.parts = gate_parts_bf16(D, gated);
@@ -400,6 +413,54 @@ static int check_desc_bf16(const mmf_amil_desc* d) {
   return MMF_OK;
 }
 
+// The bf16 stack's forward launch parameters, as the fp32 builders above, for the one-bag chain (amil_bf16_forward_impl,
+// unfused) and the window's (group_infer_chain_bf16).  The weights as bf16 in the workspace -- fused2: in MFMA-fragment
+// order (same bytes, same slots); bwd: [Wa ; Wb]^T too, in K-dh's k order (mmf_amil_bf16.hip: LoadPB) or its second form's
+static CvtParams stack_cvt_bf16(const mmf_amil_desc* d, const AmilWsBf& w, bool fused2, bool bwd) {
+  CvtParams cp{};
+  auto cvt = [&](const float* src, bf16_t* dst, int rows, int cols, int dst_ld, int c0, int transpose) {
+    cp.seg[cp.nseg++] = CvtSeg{src, dst, rows, cols, dst_ld, c0, transpose, 0};
+  };
+  const bool dh2 = bwd && dh2_bf16_ok(d->N, d->H, d->D, d->gated);
+  cvt(d->W1, w.w1, d->H, d->L, d->L, 0, fused2 ? 3 : 0);
+  cvt(d->Wa, w.wab, d->D, d->H, d->H, 0, fused2 ? 4 : 0);
+  if (bwd) cvt(d->Wa, w.wabT, d->D, d->H, w.mstk, 0, dh2 ? 5 : (d->gated ? 2 : 1));
+  if (d->gated) {
+    if (fused2) cvt(d->Wb, w.wab, d->D, d->H, d->H, 16, 4);
+    else cvt(d->Wb, w.wab + (size_t)d->D * d->H, d->D, d->H, d->H, 0, 0);
+    if (bwd) cvt(d->Wb, w.wabT, d->D, d->H, w.mstk, 32, dh2 ? 5 : 2);
+  }
+  return cp;
+}
+
+static LinearBfParams stack_linear_bf16(const mmf_amil_desc* d, const AmilWsBf& w, const uint16_t* x, uint32_t seed) {
+  LinearBfParams lp{};
+  lp.x = x; lp.w = w.w1; lp.bias = d->b1; lp.y = w.h;
+  lp.M = d->N; lp.N = d->H; lp.K = d->L;
+  lp.drop_p = d->p_h; lp.drop_key = drop_key(seed, 0); lp.seed_dev = d->seed_dev;
+  return lp;
+}
+
+static GateBfParams stack_gate_bf16(const mmf_amil_desc* d, const AmilWsBf& w, uint32_t seed) {
+  GateBfParams gp{};
+  gp.h = w.h; gp.Wa = w.wab; gp.Wb = d->gated ? w.wab + (size_t)d->D * d->H : nullptr;
+  gp.ba = d->ba; gp.bb = d->bb; gp.Wc = d->Wc;
+  gp.a = w.a; gp.b = w.b; gp.s_part = w.s_part;           // a / b are null when carved for inference
+  gp.N = d->N; gp.H = d->H; gp.D = d->D; gp.gated = d->gated;
+  gp.drop_p = d->p_att; gp.key_a = drop_key(seed, 1); gp.key_b = drop_key(seed, 2); gp.seed_dev = d->seed_dev;
+  return gp;
+}
+
+// the pooling launch over the bf16 h but for where its partials, M, statistics and head tail go
+static PoolBfParams stack_pool_bf16(const mmf_amil_desc* d, const AmilWsBf& w, float* A_raw) {
+  PoolBfParams pb{};
+  PoolParams& pp = pb.base;
+  pp.s_part = w.s_part; pp.n_parts = w.parts; pp.bc = d->bc; pp.h = nullptr; pp.N = d->N; pp.H = d->H;
+  pp.A_raw = A_raw;
+  pb.h = w.h;
+  return pb;
+}
+
 }  // namespace mmf
 
 using namespace mmf;
@@ -429,9 +490,7 @@ size_t mmf_amil_workspace_bytes(int64_t N, int32_t L, int32_t H, int32_t D, int3
 static int amil_forward_impl(const mmf_amil_desc* d, const float* x, void* workspace, size_t workspace_bytes,
                              float* M, float* A_raw, void* stream, bool infer, const HeadTail* tail = nullptr) {
   if (int e = check_desc(d)) return e;
-  if (!x || !workspace || !A_raw) return MMF_ERR_ARG;
-  if (!aligned16(x) || !aligned16(workspace) || !aligned16(d->W1) || !aligned16(d->Wa) || (d->gated && !aligned16(d->Wb)))
-    return MMF_ERR_ALIGN;
+  if (int e = check_operands(d, x, workspace, A_raw, false)) return e;
   Carver c(workspace);
   AmilWs w = carve(c, d->N, d->L, d->H, d->D, d->gated, infer);
   if (w.bytes > workspace_bytes) return MMF_ERR_WORKSPACE;
@@ -514,40 +573,25 @@ int mmf_amil_backward(const mmf_amil_desc* d, const float* x, void* workspace, s
 
 size_t mmf_amil_bf16_workspace_bytes(int64_t N, int32_t L, int32_t H, int32_t D, int32_t gated) {
   if (N < 1) N = 1;
-  return carve_bf16(nullptr, N, L, H, D, gated).bytes;
+  Carver c;
+  return carve_bf16(c, N, L, H, D, gated).bytes;
 }
 
 static int amil_bf16_forward_impl(const mmf_amil_desc* d, const uint16_t* x, void* workspace, size_t workspace_bytes,
                                   float* M, float* A_raw, void* stream, bool infer, const HeadTail* tail = nullptr) {
   if (int e = check_desc_bf16(d)) return e;
-  if (!x || !workspace || !A_raw) return MMF_ERR_ARG;
-  if (!aligned16(x) || !aligned16(workspace)) return MMF_ERR_ALIGN;
-  AmilWsBf w = carve_bf16(workspace, d->N, d->L, d->H, d->D, d->gated, infer);
+  if (int e = check_operands(d, x, workspace, A_raw, true)) return e;
+  Carver c(workspace);
+  AmilWsBf w = carve_bf16(c, d->N, d->L, d->H, d->D, d->gated, infer);
   if (w.bytes > workspace_bytes) return MMF_ERR_WORKSPACE;
   if (!M) M = w.M_step;
   hipStream_t st = static_cast<hipStream_t>(stream);
   TraceScope ts(d->trace);
-  const uint32_t* const seed_dev = d->seed_dev;
   HeadTail tl{};
   if (tail) { tl = *tail; tl.dM = w.dM_step; }
 
-  CvtParams cp{};
-  cp.nseg = 0;
-  auto cvt = [&](const float* src, bf16_t* dst, int rows, int cols, int dst_ld, int c0, int transpose) {
-    cp.seg[cp.nseg++] = CvtSeg{src, dst, rows, cols, dst_ld, c0, transpose, 0};
-  };
-  // the fused forward's second form reads W1 / [Wa ; Wb] in MFMA-fragment order (same bytes, same workspace slots)
   const bool fused2 = d->gated && fused_fwd2_ok(d->N, d->L, d->H, d->D);
-  cvt(d->W1, w.w1, d->H, d->L, d->L, 0, fused2 ? 3 : 0);
-  cvt(d->Wa, w.wab, d->D, d->H, d->H, 0, fused2 ? 4 : 0);
-  const bool dh2 = !infer && dh2_bf16_ok(d->N, d->H, d->D, d->gated);         // K-dh's second form: [Wa ; Wb]^T in fragment order
-  if (!infer) cvt(d->Wa, w.wabT, d->D, d->H, w.mstk, 0, dh2 ? 5 : (d->gated ? 2 : 1));     // K-dh's k order (mmf_amil_bf16.hip: LoadPB)
-  if (d->gated) {
-    if (fused2) cvt(d->Wb, w.wab, d->D, d->H, d->H, 16, 4);
-    else cvt(d->Wb, w.wab + (size_t)d->D * d->H, d->D, d->H, d->H, 0, 0);
-    if (!infer) cvt(d->Wb, w.wabT, d->D, d->H, w.mstk, 32, dh2 ? 5 : 2);
-  }
-  if (int e = launch_cvt_bf16(cp, st)) return e;
+  if (int e = launch_cvt_bf16(stack_cvt_bf16(d, w, fused2, !infer), st)) return e;
 
   if (fused2 || (d->gated && d->D == 256 && fused_fwd_ok(d->N, d->L, d->H, d->D))) {   // `small` gated stack: one kernel for projection + scoring + pooling partials
     FusedFwdParams fp{};
@@ -560,7 +604,7 @@ static int amil_bf16_forward_impl(const mmf_amil_desc* d, const uint16_t* x, voi
     fp.N = d->N; fp.L = d->L; fp.D = d->D;
     fp.p_h = d->p_h; fp.p_att = d->p_att;
     fp.key_h = drop_key(d->seed, 0); fp.key_a = drop_key(d->seed, 1); fp.key_b = drop_key(d->seed, 2);
-    fp.seed_dev = seed_dev;
+    fp.seed_dev = d->seed_dev;
     if (fused2) {
       if (int e = launch_fused_fwd2_bf16(fp, d->gated, st)) return e;
     } else
@@ -574,26 +618,10 @@ static int amil_bf16_forward_impl(const mmf_amil_desc* d, const uint16_t* x, voi
     return launch_pool_merge(pm, st);
   }
 
-  LinearBfParams lp{};
-  lp.x = x; lp.w = w.w1; lp.bias = d->b1; lp.y = w.h;
-  lp.M = d->N; lp.N = d->H; lp.K = d->L;
-  lp.drop_p = d->p_h; lp.drop_key = drop_key(d->seed, 0); lp.seed_dev = seed_dev;
-  if (int e = launch_linear_bf16(lp, st)) return e;
-
-  GateBfParams gp{};
-  gp.h = w.h; gp.Wa = w.wab; gp.Wb = d->gated ? w.wab + (size_t)d->D * d->H : nullptr;
-  gp.ba = d->ba; gp.bb = d->bb; gp.Wc = d->Wc;
-  gp.a = w.a; gp.b = w.b; gp.s_part = w.s_part;
-  gp.N = d->N; gp.H = d->H; gp.D = d->D; gp.gated = d->gated;
-  gp.drop_p = d->p_att; gp.key_a = drop_key(d->seed, 1); gp.key_b = drop_key(d->seed, 2); gp.seed_dev = seed_dev;
-  if (int e = launch_gate_bf16(gp, st)) return e;
-
-  PoolBfParams pb{};
-  PoolParams& pp = pb.base;
-  pp.s_part = w.s_part; pp.n_parts = w.parts; pp.bc = d->bc; pp.h = nullptr; pp.N = d->N; pp.H = d->H;
-  pp.A_raw = A_raw; pp.partials = w.partials; pp.M = M; pp.stats = w.stats;
-  pp.tail = tl;
-  pb.h = w.h;
+  if (int e = launch_linear_bf16(stack_linear_bf16(d, w, x, d->seed), st)) return e;
+  if (int e = launch_gate_bf16(stack_gate_bf16(d, w, d->seed), st)) return e;
+  PoolBfParams pb = stack_pool_bf16(d, w, A_raw);
+  pb.base.partials = w.partials; pb.base.M = M; pb.base.stats = w.stats; pb.base.tail = tl;
   return launch_pool_bf16(pb, st);
 }
 
@@ -604,7 +632,8 @@ int mmf_amil_bf16_forward(const mmf_amil_desc* d, const uint16_t* x, void* works
 
 size_t mmf_amil_bf16_infer_workspace_bytes(int64_t N, int32_t L, int32_t H, int32_t D, int32_t gated) {
   if (N < 1) N = 1;
-  return carve_bf16(nullptr, N, L, H, D, gated, true).bytes;
+  Carver c;
+  return carve_bf16(c, N, L, H, D, gated, true).bytes;
 }
 
 int mmf_amil_bf16_infer(const mmf_amil_desc* d, const uint16_t* x, void* workspace, size_t workspace_bytes,
@@ -620,7 +649,8 @@ static int amil_bf16_backward_impl(const mmf_amil_desc* d, const uint16_t* x, vo
   if (int e = check_grads(d, g)) return e;
   if (g->dx) return MMF_ERR_ARG;     // the bf16 bag is a leaf: no input gradient on this path
   if (!grads_aligned(d, g)) return MMF_ERR_ALIGN;
-  AmilWsBf w = carve_bf16(workspace, d->N, d->L, d->H, d->D, d->gated);
+  Carver c(workspace);
+  AmilWsBf w = carve_bf16(c, d->N, d->L, d->H, d->D, d->gated);
   if (w.bytes > workspace_bytes) return MMF_ERR_WORKSPACE;
   if (!M) M = w.M_step;
   if (!dM) dM = w.dM_step;
@@ -657,12 +687,7 @@ static int amil_bf16_backward_impl(const mmf_amil_desc* d, const uint16_t* x, vo
   if (int e = launch_tn_bf16(tp, st)) return e;
 
   ReduceList rl;
-  rl.add(w.slab_w1, g->dW1, d->H * d->L, w.splits, (size_t)d->H * d->L);
-  rl.add(w.slab_wab, g->dWa, d->D * d->H, w.splits, (size_t)w.mstk * d->H);
-  if (d->gated) rl.add(w.slab_wab + (size_t)d->D * d->H, g->dWb, d->D * d->H, w.splits, (size_t)w.mstk * d->H);
-  rl.add(w.cs_b1, g->db1, d->H, w.splits, d->H);
-  rl.add(w.cs_bab, g->dba, d->D, w.splits, w.mstk);
-  if (d->gated) rl.add(w.cs_bab + d->D, g->dbb, d->D, w.splits, w.mstk);
+  reduce_slabs(d, w, g, w.splits, w.splits, rl);
   rl.add(w.dwc_part, g->dWc, d->D, dh_bf16_tiles_used(d->N, ntn), d->D);
   rl.add(w.dbc_part, g->dbc, 1, dh_bf16_tiles_used(d->N, ntn), 1);
   return rl.launch(accumulate, st);
@@ -676,16 +701,17 @@ int mmf_amil_bf16_backward(const mmf_amil_desc* d, const uint16_t* x, void* work
 }
 
 // ---- attention stack + hazard head [+ nll_surv + the whole backward] in one call ------------------------------
-static int head_tail_of(const mmf_surv_head* h, const mmf_nll_target* t, HeadTail& tl) {
+// grads: the target carries the classifier's gradient (training); the forward-only form takes its labels and loss alone
+static int head_tail_of(const mmf_surv_head* h, const mmf_nll_target* t, HeadTail& tl, bool grads = true) {
   if (!h || !h->Wk || !h->bk || !h->logits || !h->hazards || !h->S || !h->Y_hat) return MMF_ERR_ARG;
   if (h->K < 1 || h->K > 32) return MMF_ERR_SHAPE;
   tl = HeadTail{};
   tl.Wk = h->Wk; tl.bk = h->bk; tl.K = h->K;
   tl.logits = h->logits; tl.hazards = h->hazards; tl.S = h->S; tl.Y_hat = h->Y_hat; tl.risk = h->risk;
   if (t) {
-    if (!t->Y || !t->c || !t->loss || !t->dWk || !t->dbk) return MMF_ERR_ARG;
-    tl.Y = t->Y; tl.c = t->c; tl.alpha = t->alpha; tl.eps = t->eps; tl.loss_scale = t->loss_scale;
-    tl.loss = t->loss; tl.dWk = t->dWk; tl.dbk = t->dbk; tl.accumulate = t->accumulate;
+    if (!t->Y || !t->c || !t->loss || (grads && (!t->dWk || !t->dbk))) return MMF_ERR_ARG;
+    tl.Y = t->Y; tl.c = t->c; tl.alpha = t->alpha; tl.eps = t->eps; tl.loss = t->loss;
+    if (grads) { tl.loss_scale = t->loss_scale; tl.dWk = t->dWk; tl.dbk = t->dbk; tl.accumulate = t->accumulate; }
   }
   return MMF_OK;
 }
@@ -787,6 +813,13 @@ struct GroupExtra {
   int splits, k_per_split;
 };
 
+// the window contract every grouped entry point checks after its own refusals and before the head and check_operands
+static int window_plan(const mmf_amil_desc* d, const mmf_bag_group* group, int bf16, SegTable& s) {
+  if (int e = group_plan(group->offsets, group->G, s)) return e;
+  if (d->N != s.off[s.G]) return MMF_ERR_SHAPE;
+  return bf16 ? check_desc_bf16(d) : check_desc(d);
+}
+
 // the call contract both grouped entry points share; fills the segment table (with each bag's mask index base) and the tail
 static int group_check(const mmf_amil_desc* d, const mmf_bag_group* group, const void* x, const void* workspace,
                        const mmf_surv_head* head, const mmf_nll_target* target, const float* A_raw,
@@ -794,15 +827,11 @@ static int group_check(const mmf_amil_desc* d, const mmf_bag_group* group, const
   if (!d || !group || !target || !g) return MMF_ERR_ARG;
   if (d->gemm != MMF_GEMM_F32 || g->dx) return MMF_ERR_ARG;
   if (!group->seeds) return MMF_ERR_ARG;
-  if (int e = group_plan(group->offsets, group->G, s)) return e;
-  if (d->N != s.off[s.G]) return MMF_ERR_SHAPE;
-  if (int e = check_desc(d)) return e;
+  if (int e = window_plan(d, group, 0, s)) return e;
   if (int e = head_tail_of(head, target, tl)) return e;
-  if (!x || !workspace || !A_raw) return MMF_ERR_ARG;
-  if (int e = check_grads(d, g)) return e;
-  if (!aligned16(x) || !aligned16(workspace) || !aligned16(d->W1) || !aligned16(d->Wa) || (d->gated && !aligned16(d->Wb)) ||
-      !grads_aligned(d, g))
-    return MMF_ERR_ALIGN;
+  if (int e = check_grads(d, g)) return e;                   // every null pointer before any alignment
+  if (int e = check_operands(d, x, workspace, A_raw, false)) return e;
+  if (!grads_aligned(d, g)) return MMF_ERR_ALIGN;
   const uint32_t inv = hash_mul_inverse();
   for (int b = 0; b < s.G; ++b) s.ibase[b] = group->seeds[b] * inv;
   return MMF_OK;
@@ -902,6 +931,38 @@ static RadioWs carve_radio(Carver& c, const SegTable& s, int nseg, int kseg, int
   r.bytes = c.off;
   return r;
 }
+
+// What both radio entry points check around the window's contract: the modality list before it (x[0] is the stack's
+// input there), reduce_dim's operands after it.  grads: dW / db are written (training); forward-only reads neither.
+static int radio_modalities(const mmf_radio_reduce* rd) {
+  if (!rd || !rd->x) return MMF_ERR_ARG;
+  return rd->nseg < 2 || rd->nseg > 4 ? MMF_ERR_SHAPE : MMF_OK;
+}
+static int radio_operands(const mmf_amil_desc* d, const mmf_radio_reduce* rd, bool grads) {
+  const int nseg = rd->nseg, kseg = rd->kseg;
+  if (kseg != d->L) return MMF_ERR_SHAPE;
+  if (d->N * nseg * (int64_t)kseg * 4 >= (int64_t)1 << 31) return MMF_ERR_SHAPE;     // the [sum N x nseg*kseg] input < 2 GiB
+  if (!rd->W || !rd->bias || (grads && (!rd->dW || !rd->db))) return MMF_ERR_ARG;
+  for (int m = 0; m < nseg; ++m)
+    if (!rd->x[m]) return MMF_ERR_ARG;
+  for (int m = 0; m < nseg; ++m)
+    if (!aligned16(rd->x[m])) return MMF_ERR_ALIGN;
+  if (!aligned16(rd->W) || (grads && !aligned16(rd->dW))) return MMF_ERR_ALIGN;
+  return MMF_OK;
+}
+
+// reduce_dim over the modality segments, every row of the window, into y: mmf_linear_forward's plan (a short window takes
+// its K split over the segments, under desc->sync).  seed_dev: training passes desc->seed_dev on, forward-only none.
+static LinearParams radio_linear(const mmf_amil_desc* d, const mmf_radio_reduce* rd, float* y, float* kpart,
+                                 const uint32_t* seed_dev) {
+  LinearParams lr{};
+  for (int m = 0; m < rd->nseg; ++m) lr.x[m] = rd->x[m];
+  lr.nseg = rd->nseg; lr.kseg = rd->kseg; lr.ldx = rd->kseg;
+  lr.w = rd->W; lr.bias = rd->bias; lr.y = y; lr.M = d->N; lr.N = d->L; lr.K = rd->nseg * rd->kseg;
+  lr.act = ACT_NONE; lr.drop_p = 0.f; lr.drop_key = drop_key(0, 0); lr.seed_dev = seed_dev;
+  if (kpart && d->sync && d->sync_words > 0) { lr.kpart = kpart; lr.ktick = d->sync; lr.ktick_words = d->sync_words; }
+  return lr;
+}
 }  // namespace mmf
 
 size_t mmf_amil_group_workspace_bytes(const int64_t* offsets, int32_t G, int32_t L, int32_t H, int32_t D, int32_t gated) {
@@ -938,36 +999,18 @@ size_t mmf_radio_group_workspace_bytes(const int64_t* offsets, int32_t G, int32_
 int mmf_radio_nll_step_group(const mmf_amil_desc* d, const mmf_bag_group* group, const mmf_radio_reduce* rd,
                              void* workspace, size_t workspace_bytes, const mmf_surv_head* head,
                              const mmf_nll_target* target, float* A_raw, const mmf_amil_grads* g, void* stream) {
-  if (!rd || !rd->x) return MMF_ERR_ARG;
-  if (rd->nseg < 2 || rd->nseg > 4) return MMF_ERR_SHAPE;
+  if (int e = radio_modalities(rd)) return e;
   SegTable s;
   HeadTail tl;
   if (int e = group_check(d, group, rd->x[0], workspace, head, target, A_raw, g, s, tl)) return e;
+  if (int e = radio_operands(d, rd, true)) return e;
   const int nseg = rd->nseg, kseg = rd->kseg, L = d->L;
-  if (kseg != L) return MMF_ERR_SHAPE;
-  const int64_t R = d->N;
-  if (R * nseg * (int64_t)kseg * 4 >= (int64_t)1 << 31) return MMF_ERR_SHAPE;     // the [sum N x nseg*kseg] input < 2 GiB
-  if (!rd->W || !rd->bias || !rd->dW || !rd->db) return MMF_ERR_ARG;
-  for (int m = 0; m < nseg; ++m)
-    if (!rd->x[m]) return MMF_ERR_ARG;
-  for (int m = 0; m < nseg; ++m)
-    if (!aligned16(rd->x[m])) return MMF_ERR_ALIGN;
-  if (!aligned16(rd->W) || !aligned16(rd->dW)) return MMF_ERR_ALIGN;
   Carver c(workspace);
   RadioWs r = carve_radio(c, s, nseg, kseg, d->H, d->D, d->gated);
   if (r.bytes > workspace_bytes) return MMF_ERR_WORKSPACE;
   hipStream_t st = static_cast<hipStream_t>(stream);
   TraceScope ts(d->trace);
-
-  // reduce_dim over the modality segments, every row of the window: mmf_linear_forward's plan (a short window takes its
-  // K split over the segments, under desc->sync)
-  LinearParams lr{};
-  for (int m = 0; m < nseg; ++m) lr.x[m] = rd->x[m];
-  lr.nseg = nseg; lr.kseg = kseg; lr.ldx = kseg;
-  lr.w = rd->W; lr.bias = rd->bias; lr.y = r.xr; lr.M = R; lr.N = L; lr.K = nseg * kseg;
-  lr.act = ACT_NONE; lr.drop_p = 0.f; lr.drop_key = drop_key(0, 0); lr.seed_dev = d->seed_dev;
-  if (r.kpart && d->sync && d->sync_words > 0) { lr.kpart = r.kpart; lr.ktick = d->sync; lr.ktick_words = d->sync_words; }
-  if (int e = launch_linear(lr, st)) return e;
+  if (int e = launch_linear(radio_linear(d, rd, r.xr, r.kpart, d->seed_dev), st)) return e;
 
   GroupExtra ex{};
   ex.dx = r.dxr;
@@ -1001,12 +1044,8 @@ struct GroupInferWs {
 static GroupInferWs carve_group_infer(Carver& c, const SegTable& s, int L, int H, int D, int gated, int bf16) {
   GroupInferWs g{};
   const int64_t R = s.off[s.G];
-  if (bf16) {
-    g.wb = carve_bf16(reinterpret_cast<void*>(c.base + c.off), R, L, H, D, gated, true);
-    c.off += g.wb.bytes;
-  } else {
-    g.w = carve(c, R, L, H, D, gated, true);
-  }
+  if (bf16) g.wb = carve_bf16(c, R, L, H, D, gated, true);
+  else g.w = carve(c, R, L, H, D, gated, true);
   g.partials = c.take<float>((size_t)s.gbeg[s.G] * (2 + H));
   g.bytes = c.off;
   return g;
@@ -1025,27 +1064,15 @@ static int infer_group_check(const mmf_amil_desc* d, const mmf_bag_group* group,
                              const float* M, const float* A_raw, SegTable& s, HeadTail& tl) {
   if (!d || !group) return MMF_ERR_ARG;
   if (d->gemm != MMF_GEMM_F32 || d->p_h != 0.f || d->p_att != 0.f) return MMF_ERR_ARG;
-  if (int e = group_plan(group->offsets, group->G, s)) return e;
-  if (d->N != s.off[s.G]) return MMF_ERR_SHAPE;
-  if (int e = bf16 ? check_desc_bf16(d) : check_desc(d)) return e;
+  if (int e = window_plan(d, group, bf16, s)) return e;
   if (bf16 && infer_group_bf16_fused(d)) return MMF_ERR_SHAPE;
   tl = HeadTail{};
   if (head) {
-    if (!head->Wk || !head->bk || !head->logits || !head->hazards || !head->S || !head->Y_hat) return MMF_ERR_ARG;
-    if (head->K < 1 || head->K > 32) return MMF_ERR_SHAPE;
-    tl.Wk = head->Wk; tl.bk = head->bk; tl.K = head->K;
-    tl.logits = head->logits; tl.hazards = head->hazards; tl.S = head->S; tl.Y_hat = head->Y_hat; tl.risk = head->risk;
-    if (target) {
-      if (!target->Y || !target->c || !target->loss) return MMF_ERR_ARG;
-      tl.Y = target->Y; tl.c = target->c; tl.alpha = target->alpha; tl.eps = target->eps; tl.loss = target->loss;
-    }
+    if (int e = head_tail_of(head, target, tl, false)) return e;
   } else if (target || !M) {
     return MMF_ERR_ARG;             // a loss needs the head; without a head the call exists for M
   }
-  if (!x || !workspace || !A_raw) return MMF_ERR_ARG;
-  if (!aligned16(x) || !aligned16(workspace)) return MMF_ERR_ALIGN;
-  if (!bf16 && (!aligned16(d->W1) || !aligned16(d->Wa) || (d->gated && !aligned16(d->Wb)))) return MMF_ERR_ALIGN;
-  return MMF_OK;
+  return check_operands(d, x, workspace, A_raw, bf16);
 }
 
 // the fp32 chain over the window's rows x [R x L]: projection and gate with the one-bag plans of R rows (rows are
@@ -1067,33 +1094,30 @@ static int group_infer_chain(const mmf_amil_desc* d, const SegTable& s, const fl
 static int group_infer_chain_bf16(const mmf_amil_desc* d, const SegTable& s, const uint16_t* x, const GroupInferWs& gw,
                                   const HeadTail& tl, float* M, float* A_raw, hipStream_t st) {
   const AmilWsBf& w = gw.wb;
-  CvtParams cp{};
-  cp.seg[cp.nseg++] = CvtSeg{d->W1, w.w1, d->H, d->L, d->L, 0, 0, 0};
-  cp.seg[cp.nseg++] = CvtSeg{d->Wa, w.wab, d->D, d->H, d->H, 0, 0, 0};
-  if (d->gated) cp.seg[cp.nseg++] = CvtSeg{d->Wb, w.wab + (size_t)d->D * d->H, d->D, d->H, d->H, 0, 0, 0};
-  if (int e = launch_cvt_bf16(cp, st)) return e;
-
-  LinearBfParams lp{};
-  lp.x = x; lp.w = w.w1; lp.bias = d->b1; lp.y = w.h;
-  lp.M = d->N; lp.N = d->H; lp.K = d->L;
-  lp.drop_p = 0.f; lp.drop_key = drop_key(0, 0); lp.seed_dev = nullptr;
+  if (int e = launch_cvt_bf16(stack_cvt_bf16(d, w, false, false), st)) return e;
+  LinearBfParams lp = stack_linear_bf16(d, w, x, 0);
+  lp.seed_dev = nullptr;              // nothing is masked (infer_group_check): this chain passes no seed word on
   if (int e = launch_linear_bf16(lp, st)) return e;
-
-  GateBfParams gp{};
-  gp.h = w.h; gp.Wa = w.wab; gp.Wb = d->gated ? w.wab + (size_t)d->D * d->H : nullptr;
-  gp.ba = d->ba; gp.bb = d->bb; gp.Wc = d->Wc;
-  gp.a = w.a; gp.b = w.b; gp.s_part = w.s_part;           // a / b are null: carved for inference
-  gp.N = d->N; gp.H = d->H; gp.D = d->D; gp.gated = d->gated;
-  gp.drop_p = 0.f; gp.key_a = drop_key(0, 1); gp.key_b = drop_key(0, 2); gp.seed_dev = nullptr;
+  GateBfParams gp = stack_gate_bf16(d, w, 0);
+  gp.seed_dev = nullptr;
   if (int e = launch_gate_bf16(gp, st)) return e;
-
-  PoolBfParams pb{};
-  PoolParams& pp = pb.base;
-  pp.s_part = w.s_part; pp.n_parts = w.parts; pp.bc = d->bc; pp.h = nullptr; pp.N = d->N; pp.H = d->H;
-  pp.A_raw = A_raw; pp.partials = gw.partials; pp.M = M; pp.tail = tl;
-  pb.h = w.h;
+  PoolBfParams pb = stack_pool_bf16(d, w, A_raw);
+  pb.base.partials = gw.partials; pb.base.M = M; pb.base.tail = tl;
   if (int e = launch_group_pool_partial_bf16(pb, s, st)) return e;
-  return launch_group_infer_tail(pp, s, st);
+  return launch_group_infer_tail(pb.base, s, st);
+}
+
+// the radio window's forward-only workspace: the stack's (L = kseg), reduce_dim's output, its K-split partial tiles
+struct RadioInferWs { GroupInferWs gw; float *xr, *kpart; size_t bytes; };
+static RadioInferWs carve_radio_infer(Carver& c, const SegTable& s, int nseg, int kseg, int H, int D, int gated) {
+  RadioInferWs r{};
+  const int64_t R = s.off[s.G];
+  r.gw = carve_group_infer(c, s, kseg, H, D, gated, 0);
+  r.xr = c.take<float>((size_t)R * kseg);
+  const size_t kf = linear_ksplit_floats(R, kseg, nseg * kseg, nseg, kseg);
+  r.kpart = kf ? c.take<float>(kf) : nullptr;
+  r.bytes = c.off;
+  return r;
 }
 }  // namespace mmf
 
@@ -1129,51 +1153,25 @@ size_t mmf_radio_group_infer_workspace_bytes(const int64_t* offsets, int32_t G, 
                                              int32_t D, int32_t gated) {
   SegTable s;
   if (group_plan(offsets, G, s) || nseg < 2 || nseg > 4 || kseg < 1) return 0;
-  const int64_t R = s.off[s.G];
   Carver c;
-  carve_group_infer(c, s, kseg, H, D, gated, 0);
-  c.take<float>((size_t)R * kseg);                                            // reduce_dim's output
-  const size_t kf = linear_ksplit_floats(R, kseg, nseg * kseg, nseg, kseg);  // its K-split partial tiles
-  if (kf) c.take<float>(kf);
-  return c.off;
+  return carve_radio_infer(c, s, nseg, kseg, H, D, gated).bytes;
 }
 
 int mmf_radio_infer_group(const mmf_amil_desc* d, const mmf_bag_group* group, const mmf_radio_reduce* rd,
                           void* workspace, size_t workspace_bytes, const mmf_surv_head* head,
                           const mmf_nll_target* target, float* M, float* A_raw, void* stream) {
-  if (!rd || !rd->x) return MMF_ERR_ARG;
-  if (rd->nseg < 2 || rd->nseg > 4) return MMF_ERR_SHAPE;
+  if (int e = radio_modalities(rd)) return e;
   SegTable s;
   HeadTail tl;
   if (int e = infer_group_check(d, group, rd->x[0], 0, workspace, head, target, M, A_raw, s, tl)) return e;
-  const int nseg = rd->nseg, kseg = rd->kseg, L = d->L;
-  if (kseg != L) return MMF_ERR_SHAPE;
-  const int64_t R = d->N;
-  if (R * nseg * (int64_t)kseg * 4 >= (int64_t)1 << 31) return MMF_ERR_SHAPE;     // the [sum N x nseg*kseg] input < 2 GiB
-  if (!rd->W || !rd->bias) return MMF_ERR_ARG;
-  for (int m = 0; m < nseg; ++m)
-    if (!rd->x[m]) return MMF_ERR_ARG;
-  for (int m = 0; m < nseg; ++m)
-    if (!aligned16(rd->x[m])) return MMF_ERR_ALIGN;
-  if (!aligned16(rd->W)) return MMF_ERR_ALIGN;
+  if (int e = radio_operands(d, rd, false)) return e;
   Carver c(workspace);
-  const GroupInferWs gw = carve_group_infer(c, s, L, d->H, d->D, d->gated, 0);
-  float* xr = c.take<float>((size_t)R * L);
-  const size_t kf = linear_ksplit_floats(R, L, nseg * kseg, nseg, kseg);
-  float* kpart = kf ? c.take<float>(kf) : nullptr;
-  if (c.off > workspace_bytes) return MMF_ERR_WORKSPACE;
+  const RadioInferWs r = carve_radio_infer(c, s, rd->nseg, rd->kseg, d->H, d->D, d->gated);
+  if (r.bytes > workspace_bytes) return MMF_ERR_WORKSPACE;
   hipStream_t st = static_cast<hipStream_t>(stream);
   TraceScope ts(d->trace);
-
-  // reduce_dim over the modality segments, every row of the window: mmf_linear_forward's plan
-  LinearParams lr{};
-  for (int m = 0; m < nseg; ++m) lr.x[m] = rd->x[m];
-  lr.nseg = nseg; lr.kseg = kseg; lr.ldx = kseg;
-  lr.w = rd->W; lr.bias = rd->bias; lr.y = xr; lr.M = R; lr.N = L; lr.K = nseg * kseg;
-  lr.act = ACT_NONE; lr.drop_p = 0.f; lr.drop_key = drop_key(0, 0); lr.seed_dev = nullptr;
-  if (kpart && d->sync && d->sync_words > 0) { lr.kpart = kpart; lr.ktick = d->sync; lr.ktick_words = d->sync_words; }
-  if (int e = launch_linear(lr, st)) return e;
-  return group_infer_chain(d, s, xr, gw, tl, M, A_raw, st);
+  if (int e = launch_linear(radio_linear(d, rd, r.xr, r.kpart, nullptr), st)) return e;
+  return group_infer_chain(d, s, r.xr, r.gw, tl, M, A_raw, st);
 }
 
 int mmf_surv_head_nll_step(const float* feat, int32_t F, const mmf_surv_head* head, const mmf_nll_target* target,

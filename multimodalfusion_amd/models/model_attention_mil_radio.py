@@ -88,23 +88,9 @@ class MIL_Attention_fc_surv_radio(MIL_Attention_fc_radio):
         from .. import ops
         if any(not p.requires_grad for p in self.parameters()):
             raise RuntimeError("nll_step_group needs every parameter of the head to require grad")
-        nmod = len(self.modalities)
-        if (isinstance(bags, (tuple, list)) and len(bags) == 2 and torch.is_tensor(bags[0])
-                and isinstance(bags[1], (list, tuple)) and all(isinstance(n, int) for n in bags[1])):
-            x, sizes = bags
-            if x.dim() != 3 or x.shape[0] != nmod:
-                raise ops._lib.MmfError(f"pre-stacked bags must be [{nmod} x sum N x k], got {tuple(x.shape)}")
-            xs = list(x.unbind(0))
-        else:
-            if not all(isinstance(b, dict) for b in bags):
-                raise TypeError("bags: a list of {modality: [n x k]} dicts or an (x [n_mod x sum N x k], sizes) pair")
-            for b in bags:
-                if len({tuple(b[m].shape) for m in self.modalities}) != 1:
-                    raise ops._lib.MmfError("the modalities of a bag must have the same [n x k] shape")
-            sizes = [int(b[self.modalities[0]].shape[0]) for b in bags]
-            xs = [torch.cat([b[m] for b in bags], 0) if len(bags) > 1 else bags[0][m] for m in self.modalities]
-        if nmod == 1:
-            return amil_stack_nll_step_group(self.attention_net_radio, self.classifier, (xs[0], list(sizes)), self.training,
+        xs, sizes = self._stacked(bags)
+        if len(xs) == 1:
+            return amil_stack_nll_step_group(self.attention_net_radio, self.classifier, (xs[0], sizes), self.training,
                                              labels, censors, alpha, loss_scale, grad_out, accumulate, seeds)
         gated, stack, p_h, p_att = stack_args(self.attention_net_radio, self.training)
         Wr, br, Wk, bk = self.reduce_dim.weight, self.reduce_dim.bias, self.classifier.weight, self.classifier.bias

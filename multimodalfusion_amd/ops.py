@@ -305,16 +305,20 @@ def _step_grads(stack, Wk, bk, gated, grads):
 def _nll_head(Wk, bk, Y, c, alpha, eps, loss_scale, dWk, dbk, accumulate, dev, G=0):
     """The classifier + hazards + nll_surv part of a one-call step: labels / censorships on the device, the outputs and
     the SurvHead / NllTarget structs.  G = 0: one bag (Y, c: one value each; the outputs share one buffer); G > 0: G bags
-    (Y, c: [G] each).  Returns (hd, tg, (hazards, S, Y_hat, loss, risk), keep); keep holds the other tensors the structs
-    point to (the device Y, c and the logits), which must stay alive until the launch."""
+    (Y, c: [G] each).  A forward-only call passes no gradient buffers (dWk = dbk = None) and may pass no labels (Y = None:
+    no NllTarget, no loss); on purpose its out-of-range host labels go through to a NaN loss, as mmf_nll_surv's, where
+    a training step raises.  Returns (hd, tg, (hazards, S, Y_hat, loss, risk), keep); keep holds the other tensors the
+    structs point to (the device Y, c and the logits), which must stay alive until the launch."""
     K = Wk.shape[0]
-    if not Y.is_cuda and bool(((Y < 0) | (Y >= K)).any()):
+    if dWk is not None and not Y.is_cuda and bool(((Y < 0) | (Y >= K)).any()):
         raise IndexError(f"nll_surv: label out of range [0, {K})")
     if G:
-        Y = Y.to(device=dev, dtype=torch.int64).contiguous()
-        c = c.to(device=dev, dtype=torch.float32).contiguous()
-        logits, hz, S = torch.empty((G, K), device=dev), torch.empty((G, K), device=dev), torch.empty((G, K), device=dev)
-        loss, risk = torch.empty((G,), device=dev), torch.empty((G,), device=dev)
+        logits, hz, S = (torch.empty((G, K), dtype=torch.float32, device=dev) for _ in range(3))
+        risk = torch.empty((G,), dtype=torch.float32, device=dev)
+        if Y is not None:
+            Y = Y.to(device=dev, dtype=torch.int64).contiguous()
+            c = c.to(device=dev, dtype=torch.float32).contiguous()
+            loss = torch.empty((G,), dtype=torch.float32, device=dev)
     else:
         Y = Y.reshape(1).to(device=dev, dtype=torch.int64)
         c = c.reshape(1).to(device=dev, dtype=torch.float32)
@@ -324,6 +328,8 @@ def _nll_head(Wk, bk, Y, c, alpha, eps, loss_scale, dWk, dbk, accumulate, dev, G
     Y_hat = torch.empty((G or 1, 1), dtype=torch.int64, device=dev)
     hd = SurvHead(Wk=ptr(Wk), bk=ptr(bk), K=K, logits=ptr(logits), hazards=ptr(hz), S=ptr(S), Y_hat=ptr(Y_hat),
                   risk=ptr(risk))
+    if Y is None:
+        return hd, None, (hz, S, Y_hat, None, risk), (logits,)
     tg = NllTarget(Y=ptr(Y), c=ptr(c), alpha=float(alpha), eps=float(eps), loss_scale=float(loss_scale),
                    loss=ptr(loss), dWk=ptr(dWk), dbk=ptr(dbk), accumulate=1 if accumulate else 0)
     return hd, tg, (hz, S, Y_hat, loss, risk), (Y, c, logits)
@@ -369,8 +375,9 @@ def radio_group_row_limit(nseg, L, H, D):
     return min(group_row_limit(L, H, D), ((1 << 31) - 1) // (4 * nseg * L))
 
 
-def _group_table(sizes, rows, Y, c, seeds):
-    """The bag table of a grouped call: sizes checked against the rows given, G labels / censorships / seeds.
+def _group_table(sizes, rows, Y, c, seeds=None, train=True):
+    """The bag table of a grouped call: sizes checked against the rows given, G labels / censorships (None: a forward-only
+    call without a loss) and, for a training call, G dropout seeds (a forward-only table carries none).
     Returns (sizes, Y, c, offsets (host int64 [G + 1]), BagGroup); the BagGroup points into the offsets and seeds arrays,
     which it keeps alive as attributes."""
     sizes = [int(n) for n in sizes]
@@ -381,20 +388,58 @@ def _group_table(sizes, rows, Y, c, seeds):
         raise _lib.MmfError("empty bag in the group")
     if rows is not None and rows != sum(sizes):
         raise _lib.MmfError(f"the bags hold {rows} rows, their sizes add up to {sum(sizes)}")
-    Y = torch.as_tensor(Y).reshape(-1)
-    c = torch.as_tensor(c).reshape(-1)
-    if Y.numel() != G or c.numel() != G:
-        raise _lib.MmfError(f"{G} bags need {G} labels and censorships, got {Y.numel()} / {c.numel()}")
-    seeds = [0] * G if seeds is None else [int(v) & 0xFFFFFFFF for v in seeds]
-    if len(seeds) != G:
-        raise _lib.MmfError(f"{G} bags need {G} dropout seeds")
+    if Y is not None or train:
+        Y = torch.as_tensor(Y).reshape(-1)
+        c = torch.as_tensor(c).reshape(-1)
+        if Y.numel() != G or c.numel() != G:
+            raise _lib.MmfError(f"{G} bags need {G} labels and censorships, got {Y.numel()} / {c.numel()}")
+    sd = None
+    if train:
+        seeds = [0] * G if seeds is None else [int(v) & 0xFFFFFFFF for v in seeds]
+        if len(seeds) != G:
+            raise _lib.MmfError(f"{G} bags need {G} dropout seeds")
+        sd = (C.c_uint32 * G)(*seeds)
     offs = (C.c_int64 * (G + 1))()
     for i, n in enumerate(sizes):
         offs[i + 1] = offs[i] + n
-    sd = (C.c_uint32 * G)(*seeds)
     grp = _lib.BagGroup(G=G, offsets=offs, seeds=sd)
     grp._keep = (offs, sd)
     return sizes, Y, c, offs, grp
+
+
+def _radio_operands(xs, Wr, br, kind, dWr=None, dbr=None):
+    """The modality tensors xs (2 .. 4, each [sum N x k] fp32) and reduce_dim (Wr [k x nseg k], br [k]; dWr, dbr: its
+    gradient buffers, None for a forward-only call) of a grouped radio `kind` ("step" / "pass"), checked.
+    Returns (xs, R, nseg, k, RadioReduce)."""
+    xs = list(xs)
+    nseg = len(xs)
+    if nseg < 2 or nseg > 4:
+        raise _lib.MmfError(f"the grouped radio {kind} takes 2 .. 4 modalities, got {nseg}")
+    if any(x.dtype != torch.float32 for x in xs):
+        raise _lib.MmfError(f"the grouped {'step' if kind == 'step' else 'radio pass'} takes fp32 bags only")
+    xs = [_f32c(x) for x in xs]
+    if any(x.dim() != 2 or tuple(x.shape) != tuple(xs[0].shape) for x in xs):
+        raise _lib.MmfError("every modality must be one [sum N x k] tensor of the same shape")
+    R, kseg = xs[0].shape
+    Wr, br = _f32c(Wr), _f32c(br)
+    if tuple(Wr.shape) != (kseg, nseg * kseg) or tuple(br.shape) != (kseg,):
+        raise _lib.MmfError(f"reduce_dim must be [{kseg} x {nseg * kseg}] with a [{kseg}] bias for {nseg} modalities of {kseg}")
+    if kind == "step":
+        _check_grad_buffers(((dWr, Wr), (dbr, br)))
+    segs = (C.c_void_p * nseg)(*[ptr(x) for x in xs])
+    return xs, R, nseg, kseg, _lib.RadioReduce(x=segs, nseg=nseg, kseg=kseg, W=ptr(Wr), bias=ptr(br), dW=ptr(dWr),
+                                               db=ptr(dbr))
+
+
+def _run_group(query, qargs, name, d, grp, lead, hd, tg, tail, A_raw, sizes):
+    """One grouped C-ABI call: the workspace of `query`(*qargs), then `name`(desc, group, *lead, workspace, bytes, head,
+    target, *tail, stream).  Returns A_raw split per bag: [1 x N_g] views."""
+    l = lib()
+    nbytes = getattr(l, query)(*qargs)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=A_raw.device)
+    check(getattr(l, name)(C.byref(d), C.byref(grp), *lead, ptr(ws), nbytes, hd and C.byref(hd), tg and C.byref(tg), *tail,
+                           stream_ptr()), name)
+    return [v.view(1, -1) for v in torch.split(A_raw, sizes)]
 
 
 def amil_nll_step_group(x_cat, sizes, stack, Wk, bk, gated, Y, c, alpha, grads, loss_scale=1.0, accumulate=False, p_h=0.0,
@@ -419,13 +464,9 @@ def amil_nll_step_group(x_cat, sizes, stack, Wk, bk, gated, Y, c, alpha, grads, 
     hd, tg, (hz, S, Y_hat, loss, risk), _keep = _nll_head(Wk, bk, Y, c, alpha, eps, loss_scale, grads[8], grads[9],
                                                           accumulate, dev, G)
     d = _amil_desc(stack, R, L, H, D, gated, p_h, p_att, 0, _seed_word)
-    l = lib()
-    nbytes = l.mmf_amil_group_workspace_bytes(offs, G, L, H, D, d.gated)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     A_raw = torch.empty((R,), dtype=torch.float32, device=dev)
-    check(l.mmf_amil_nll_step_group(C.byref(d), C.byref(grp), ptr(x_cat), ptr(ws), nbytes, C.byref(hd), C.byref(tg),
-                                    ptr(A_raw), C.byref(g), stream_ptr()), "mmf_amil_nll_step_group")
-    A_list = [v.view(1, -1) for v in torch.split(A_raw, sizes)]
+    A_list = _run_group("mmf_amil_group_workspace_bytes", (offs, G, L, H, D, d.gated), "mmf_amil_nll_step_group", d, grp,
+                        (ptr(x_cat),), hd, tg, (ptr(A_raw), C.byref(g)), A_raw, sizes)
     return hz, S, Y_hat, A_list, loss, risk
 
 
@@ -438,38 +479,18 @@ def radio_nll_step_group(xs, sizes, Wr, br, stack, Wk, bk, gated, Y, c, alpha, g
     reduce_dim's weight [L x nseg k] and bias [L]; grads = (dWr, dbr, dW1, ..., dbk), those of sum_g loss_g * loss_scale,
     added to when `accumulate`.  Other arguments as amil_nll_step_group.
     Returns (hazards [G x K], S [G x K], Y_hat [G x 1], [A_raw [1 x N_g]], loss [G] (unscaled), risk [G])."""
-    xs = list(xs)
-    nseg = len(xs)
-    if nseg < 2 or nseg > 4:
-        raise _lib.MmfError(f"the grouped radio step takes 2 .. 4 modalities, got {nseg}")
-    if any(x.dtype != torch.float32 for x in xs):
-        raise _lib.MmfError("the grouped step takes fp32 bags only")
-    xs = [_f32c(x) for x in xs]
-    if any(x.dim() != 2 or tuple(x.shape) != tuple(xs[0].shape) for x in xs):
-        raise _lib.MmfError("every modality must be one [sum N x k] tensor of the same shape")
-    R, kseg = xs[0].shape
+    xs, R, nseg, kseg, rd = _radio_operands(xs, Wr, br, "step", *grads[:2])
     sizes, Y, c, offs, grp = _group_table(sizes, R, Y, c, seeds)
     G = len(sizes)
-    Wr, br = _f32c(Wr), _f32c(br)
     stack, (Wk, bk), H, D = _stack_operands(stack, kseg, (Wk, bk), "bags", fused_head=True)
     g = _step_grads(stack, Wk, bk, gated, grads[2:])
-    if tuple(Wr.shape) != (kseg, nseg * kseg) or tuple(br.shape) != (kseg,):
-        raise _lib.MmfError(f"reduce_dim must be [{kseg} x {nseg * kseg}] with a [{kseg}] bias for {nseg} modalities of {kseg}")
-    dWr, dbr = grads[:2]
-    _check_grad_buffers(((dWr, Wr), (dbr, br)))
     dev = xs[0].device
     hd, tg, (hz, S, Y_hat, loss, risk), _keep = _nll_head(Wk, bk, Y, c, alpha, eps, loss_scale, grads[10], grads[11],
                                                           accumulate, dev, G)
     d = _amil_desc(stack, R, kseg, H, D, gated, p_h, p_att, 0, _seed_word)
-    segs = (C.c_void_p * nseg)(*[ptr(x) for x in xs])
-    rd = _lib.RadioReduce(x=segs, nseg=nseg, kseg=kseg, W=ptr(Wr), bias=ptr(br), dW=ptr(dWr), db=ptr(dbr))
-    l = lib()
-    nbytes = l.mmf_radio_group_workspace_bytes(offs, G, nseg, kseg, H, D, d.gated)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     A_raw = torch.empty((R,), dtype=torch.float32, device=dev)
-    check(l.mmf_radio_nll_step_group(C.byref(d), C.byref(grp), C.byref(rd), ptr(ws), nbytes, C.byref(hd), C.byref(tg),
-                                     ptr(A_raw), C.byref(g), stream_ptr()), "mmf_radio_nll_step_group")
-    A_list = [v.view(1, -1) for v in torch.split(A_raw, sizes)]
+    A_list = _run_group("mmf_radio_group_workspace_bytes", (offs, G, nseg, kseg, H, D, d.gated), "mmf_radio_nll_step_group",
+                        d, grp, (C.byref(rd),), hd, tg, (ptr(A_raw), C.byref(g)), A_raw, sizes)
     return hz, S, Y_hat, A_list, loss, risk
 
 
@@ -493,51 +514,20 @@ def radio_infer_group_row_limit(nseg, L, H, D):
     return radio_group_row_limit(nseg, L, H, D)
 
 
-def _infer_table(sizes, rows):
-    """The bag table of a forward-only grouped call (no seeds).  Returns (sizes, offsets, BagGroup)."""
-    sizes = [int(n) for n in sizes]
-    G = len(sizes)
-    if G < 1 or G > GROUP_MAX:
-        raise _lib.MmfError(f"a group holds 1 .. {GROUP_MAX} bags, got {G}")
-    if min(sizes) < 1:
-        raise _lib.MmfError("empty bag in the group")
-    if rows != sum(sizes):
-        raise _lib.MmfError(f"the bags hold {rows} rows, their sizes add up to {sum(sizes)}")
-    offs = (C.c_int64 * (G + 1))()
-    for i, n in enumerate(sizes):
-        offs[i + 1] = offs[i] + n
-    grp = _lib.BagGroup(G=G, offsets=offs, seeds=None)
-    grp._keep = (offs,)
-    return sizes, offs, grp
-
-
-def _infer_head(head, Y, c, alpha, eps, G, dev):
-    """The per-bag head outputs of a forward-only grouped call and its SurvHead / NllTarget (None where not asked for).
-    Returns (hd, tg, (hazards, S, Y_hat, risk, loss), keep)."""
+def _infer_operands(stack, L, Wk, bk, Y, c, alpha, eps, want_M, G, dev):
+    """The stack, the optional classifier (Wk = None: M only) and the per-bag outputs of a forward-only grouped call.
+    Returns (stack, H, D, hd, tg, (hazards, S, Y_hat, loss, risk), M, keep); hd, tg and the outputs are None where not
+    asked for."""
+    stack, head, H, D = _stack_operands(stack, L, None if Wk is None else (Wk, bk), "bags", fused_head=True)
+    if head is None and not want_M:
+        raise _lib.MmfError("nothing to compute: give the classifier or ask for M")
+    if head is None and Y is not None:
+        raise _lib.MmfError("a loss needs the classifier head")
+    M = torch.empty((G, H), dtype=torch.float32, device=dev) if want_M else None
     if head is None:
-        if Y is not None:
-            raise _lib.MmfError("a loss needs the classifier head")
-        return None, None, (None,) * 5, ()
-    Wk, bk = head
-    K = Wk.shape[0]
-    logits, hz, S = (torch.empty((G, K), dtype=torch.float32, device=dev) for _ in range(3))
-    Y_hat = torch.empty((G, 1), dtype=torch.int64, device=dev)
-    risk = torch.empty((G,), dtype=torch.float32, device=dev)
-    hd = SurvHead(Wk=ptr(Wk), bk=ptr(bk), K=K, logits=ptr(logits), hazards=ptr(hz), S=ptr(S), Y_hat=ptr(Y_hat),
-                  risk=ptr(risk))
-    tg, loss, keep = None, None, (logits,)
-    if Y is not None:
-        Y = torch.as_tensor(Y).reshape(-1)
-        c = torch.as_tensor(c).reshape(-1)
-        if Y.numel() != G or c.numel() != G:
-            raise _lib.MmfError(f"{G} bags need {G} labels and censorships, got {Y.numel()} / {c.numel()}")
-        Y = Y.to(device=dev, dtype=torch.int64).contiguous()       # out-of-range labels: NaN loss, as mmf_nll_surv
-        c = c.to(device=dev, dtype=torch.float32).contiguous()
-        loss = torch.empty((G,), dtype=torch.float32, device=dev)
-        tg = NllTarget(Y=ptr(Y), c=ptr(c), alpha=float(alpha), eps=float(eps), loss_scale=1.0, loss=ptr(loss),
-                       dWk=None, dbk=None, accumulate=0)
-        keep = (logits, Y, c)
-    return hd, tg, (hz, S, Y_hat, risk, loss), keep
+        return stack, H, D, None, None, (None,) * 5, M, ()
+    hd, tg, outs, keep = _nll_head(*head, Y, c, alpha, eps, 1.0, None, None, False, dev, G)
+    return stack, H, D, hd, tg, outs, M, keep
 
 
 def amil_infer_group(x_cat, sizes, stack, gated, Wk=None, bk=None, Y=None, c=None, alpha=0.0, want_M=False, eps=1e-7):
@@ -553,24 +543,15 @@ def amil_infer_group(x_cat, sizes, stack, gated, Wk=None, bk=None, Y=None, c=Non
     if x_cat.dim() != 2:
         raise _lib.MmfError(f"x_cat must be [sum N x L], got {tuple(x_cat.shape)}")
     R, L = x_cat.shape
-    sizes, offs, grp = _infer_table(sizes, R)
-    G = len(sizes)
-    head = None if Wk is None else (Wk, bk)
-    stack, head, H, D = _stack_operands(stack, L, head, "bags", fused_head=True)
-    if head is None and not want_M:
-        raise _lib.MmfError("nothing to compute: give the classifier or ask for M")
-    dev = x_cat.device
-    hd, tg, (hz, S, Y_hat, risk, loss), _keep = _infer_head(head, Y, c, alpha, eps, G, dev)
+    sizes, Y, c, offs, grp = _group_table(sizes, R, Y, c, train=False)
+    G, dev = len(sizes), x_cat.device
+    stack, H, D, hd, tg, (hz, S, Y_hat, loss, risk), M, _keep = _infer_operands(stack, L, Wk, bk, Y, c, alpha, eps, want_M,
+                                                                                G, dev)
     d = _amil_desc(stack, R, L, H, D, gated, 0.0, 0.0, 0, None)
-    l = lib()
-    nbytes = l.mmf_amil_group_infer_workspace_bytes(offs, G, L, H, D, d.gated, 1 if bf16 else 0)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    M = torch.empty((G, H), dtype=torch.float32, device=dev) if want_M else None
     A_raw = torch.empty((R,), dtype=torch.float32, device=dev)
-    check(l.mmf_amil_infer_group(C.byref(d), C.byref(grp), ptr(x_cat), 1 if bf16 else 0, ptr(ws), nbytes,
-                                 C.byref(hd) if hd is not None else None, C.byref(tg) if tg is not None else None,
-                                 ptr(M), ptr(A_raw), stream_ptr()), "mmf_amil_infer_group")
-    A_list = [v.view(1, -1) for v in torch.split(A_raw, sizes)]
+    A_list = _run_group("mmf_amil_group_infer_workspace_bytes", (offs, G, L, H, D, d.gated, 1 if bf16 else 0),
+                        "mmf_amil_infer_group", d, grp, (ptr(x_cat), 1 if bf16 else 0), hd, tg, (ptr(M), ptr(A_raw)), A_raw,
+                        sizes)
     return hz, S, Y_hat, risk, A_list, M, loss
 
 
@@ -580,39 +561,15 @@ def radio_infer_group(xs, sizes, Wr, br, stack, gated, Wk=None, bk=None, Y=None,
     over the modality segments and the stack's GEMMs once over all rows, pooling and the head per bag.  xs: 2 .. 4
     modality tensors, each [sum N x k] fp32 (the bags' rows in order); Wr, br: reduce_dim [k x nseg k], [k].  Other
     arguments and the result as amil_infer_group."""
-    xs = list(xs)
-    nseg = len(xs)
-    if nseg < 2 or nseg > 4:
-        raise _lib.MmfError(f"the grouped radio pass takes 2 .. 4 modalities, got {nseg}")
-    if any(x.dtype != torch.float32 for x in xs):
-        raise _lib.MmfError("the grouped radio pass takes fp32 bags only")
-    xs = [_f32c(x) for x in xs]
-    if any(x.dim() != 2 or tuple(x.shape) != tuple(xs[0].shape) for x in xs):
-        raise _lib.MmfError("every modality must be one [sum N x k] tensor of the same shape")
-    R, kseg = xs[0].shape
-    sizes, offs, grp = _infer_table(sizes, R)
-    G = len(sizes)
-    Wr, br = _f32c(Wr), _f32c(br)
-    head = None if Wk is None else (Wk, bk)
-    stack, head, H, D = _stack_operands(stack, kseg, head, "bags", fused_head=True)
-    if head is None and not want_M:
-        raise _lib.MmfError("nothing to compute: give the classifier or ask for M")
-    if tuple(Wr.shape) != (kseg, nseg * kseg) or tuple(br.shape) != (kseg,):
-        raise _lib.MmfError(f"reduce_dim must be [{kseg} x {nseg * kseg}] with a [{kseg}] bias for {nseg} modalities of {kseg}")
-    dev = xs[0].device
-    hd, tg, (hz, S, Y_hat, risk, loss), _keep = _infer_head(head, Y, c, alpha, eps, G, dev)
+    xs, R, nseg, kseg, rd = _radio_operands(xs, Wr, br, "pass")
+    sizes, Y, c, offs, grp = _group_table(sizes, R, Y, c, train=False)
+    G, dev = len(sizes), xs[0].device
+    stack, H, D, hd, tg, (hz, S, Y_hat, loss, risk), M, _keep = _infer_operands(stack, kseg, Wk, bk, Y, c, alpha, eps,
+                                                                                want_M, G, dev)
     d = _amil_desc(stack, R, kseg, H, D, gated, 0.0, 0.0, 0, None)
-    segs = (C.c_void_p * nseg)(*[ptr(x) for x in xs])
-    rd = _lib.RadioReduce(x=segs, nseg=nseg, kseg=kseg, W=ptr(Wr), bias=ptr(br), dW=None, db=None)
-    l = lib()
-    nbytes = l.mmf_radio_group_infer_workspace_bytes(offs, G, nseg, kseg, H, D, d.gated)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    M = torch.empty((G, H), dtype=torch.float32, device=dev) if want_M else None
     A_raw = torch.empty((R,), dtype=torch.float32, device=dev)
-    check(l.mmf_radio_infer_group(C.byref(d), C.byref(grp), C.byref(rd), ptr(ws), nbytes,
-                                  C.byref(hd) if hd is not None else None, C.byref(tg) if tg is not None else None,
-                                  ptr(M), ptr(A_raw), stream_ptr()), "mmf_radio_infer_group")
-    A_list = [v.view(1, -1) for v in torch.split(A_raw, sizes)]
+    A_list = _run_group("mmf_radio_group_infer_workspace_bytes", (offs, G, nseg, kseg, H, D, d.gated),
+                        "mmf_radio_infer_group", d, grp, (C.byref(rd),), hd, tg, (ptr(M), ptr(A_raw)), A_raw, sizes)
     return hz, S, Y_hat, risk, A_list, M, loss
 
 

@@ -163,13 +163,12 @@ class _Window:
         return True
 
 
-class _BagGroup:
-    """train_loop_survival(group=True): the eligible bags of the current window, held on the device until one grouped
-    call (model.nll_step_group) runs them.  Each bag is copied straight into its rows of one reusable device buffer
-    [n_mod x rows x L] (no concatenation pass): the pathology head's bag is one [n x L] tensor, the radiology head's one
-    per modality.  Its dropout seed is drawn when it arrives, so bag g of the loader gets the masks the per-bag route
-    gives it.  A bag that would take the group past ops.GROUP_MAX bags or the row limit flushes what is held first (the
-    window then runs as several grouped calls, accumulating)."""
+class _HeldBags:
+    """The bags a grouped call will take, held on the device until it runs (_BagGroup: a training window's; _EvalGroup: an
+    evaluation pass's).  Each bag is copied straight into its rows of one reusable device buffer [n_mod x rows x L] (no
+    concatenation pass; fp32, or bf16 pathology bags in an evaluation pass): the pathology head's bag is one [n x L]
+    tensor, the radiology head's one per modality.  A bag that would take the group past ops.GROUP_MAX bags or the row
+    limit, or one of the other storage type, flushes what is held first (the window then runs as several grouped calls)."""
 
     def __init__(self):
         self.buf = None
@@ -179,24 +178,37 @@ class _BagGroup:
         self.rows, self.sizes, self.labels, self.cs, self.seeds, self.slots = 0, [], [], [], [], []
 
     @staticmethod
-    def _row_limit(model, nmod, L):
+    def row_limit(model, nmod, L, dtype=torch.float32):
+        """Most rows of one grouped call (an fp32 window's are the same forward-only and in training)."""
         from .. import ops
         seq = model.attention_net_radio if hasattr(model, "attention_net_radio") else model.attention_net_WSI
         H, D = seq[0].out_features, seq[3].stack_params()[0].shape[0]
-        return ops.radio_group_row_limit(nmod, L, H, D) if nmod > 1 else ops.group_row_limit(L, H, D)
+        if nmod > 1:
+            return ops.radio_infer_group_row_limit(nmod, L, H, D)
+        return ops.infer_group_row_limit(L, H, D, bf16=dtype == torch.bfloat16)
 
-    def add(self, model, xs, label, c, seed, slot, device, flush):
-        """xs: the bag's [n x L] tensors, one per modality (the pathology head: one)."""
+    @staticmethod
+    def limit_of(model, xs, cache):
+        """row_limit for the bag xs, memoised in `cache` (a dict the pass keeps) by modality count, width and dtype."""
+        key = (len(xs), int(xs[0].shape[1]), xs[0].dtype)
+        if key not in cache:
+            cache[key] = _HeldBags.row_limit(model, *key)
+        return cache[key]
+
+    def add(self, xs, label, c, slot, limit, device, flush, seed=0):
+        """xs: the bag's [n x L] tensors, one per modality (the pathology head: one); label, c: device tensors; seed: its
+        dropout seed in a training window."""
         from .. import ops
-        nmod, n, L = len(xs), int(xs[0].shape[0]), int(xs[0].shape[1])
-        limit = self._row_limit(model, nmod, L)
-        if self.sizes and (len(self.sizes) >= ops.GROUP_MAX or self.rows + n > limit):
+        nmod, n, L, dtype = len(xs), int(xs[0].shape[0]), int(xs[0].shape[1]), xs[0].dtype
+        if device.type == "cuda" and device.index is None:        # compare with the buffer's device, which has its index
+            device = torch.device("cuda", torch.cuda.current_device())
+        if self.sizes and (len(self.sizes) >= ops.GROUP_MAX or self.rows + n > limit or self.buf.dtype != dtype):
             flush()
         need = self.rows + n
         if (self.buf is None or self.buf.shape[0] != nmod or self.buf.shape[2] != L or self.buf.shape[1] < need
-                or self.buf.device != device):
+                or self.buf.dtype != dtype or self.buf.device != device):
             grown = torch.empty((nmod, max(need, 2 * self.buf.shape[1] if self.buf is not None else need), L),
-                                dtype=torch.float32, device=device)
+                                dtype=dtype, device=device)
             if self.rows:
                 grown[:, :self.rows].copy_(self.buf[:, :self.rows])
             self.buf = grown
@@ -206,13 +218,23 @@ class _BagGroup:
         self.sizes.append(n); self.labels.append(label.reshape(1)); self.cs.append(c.reshape(1))
         self.seeds.append(seed); self.slots.append(slot)
 
+    def held(self, model):
+        """The held rows as the model's grouped calls take them: (x or [n_mod x rows x L], sizes)."""
+        x = self.buf[:, :self.rows] if hasattr(model, "attention_net_radio") else self.buf[0, :self.rows]
+        return x, list(self.sizes)
+
+
+class _BagGroup(_HeldBags):
+    """train_loop_survival(group=True): the eligible bags of the current window, until one grouped call
+    (model.nll_step_group) runs them.  A bag's dropout seed is drawn when it arrives, so bag g of the loader gets the
+    masks the per-bag route gives it.  fp32 only, by what the loop feeds it."""
+
     def run(self, model, alpha, loss_scale):
         """One grouped call over the held bags -> [(loader slot, loss [1], risk [1])]; the group is empty afterwards."""
         if not self.sizes:
             return []
         seeds = self.seeds if model.training else None
-        x = self.buf[:, :self.rows] if hasattr(model, "attention_net_radio") else self.buf[0, :self.rows]
-        _, _, _, _, loss, risk = model.nll_step_group((x, list(self.sizes)), torch.cat(self.labels), torch.cat(self.cs),
+        _, _, _, _, loss, risk = model.nll_step_group(self.held(model), torch.cat(self.labels), torch.cat(self.cs),
                                                       alpha=alpha, loss_scale=loss_scale, seeds=seeds)
         out = [(slot, loss[g:g + 1], risk[g:g + 1]) for g, slot in enumerate(self.slots)]
         self.reset()
@@ -406,7 +428,8 @@ def train_loop_survival(epoch, model, loader, optimizer, n_classes, mode, writer
                     xs = [radio_features[m] for m in model.modalities]
                 else:
                     xs = [path_features if direct else feats["path_features"]]
-                held.add(model, xs, label, c, ops.next_dropout_seed() if model.training else 0, len(losses), device, flush)
+                held.add(xs, label, c, len(losses), held.row_limit(model, len(xs), int(xs[0].shape[1])), device, flush,
+                         seed=ops.next_dropout_seed() if model.training else 0)
                 loss = risk = None
             elif fused_radio:
                 _, _, _, _, loss, risk = model.nll_step(label, c, alpha=loss_fn.alpha, loss_scale=1.0 / G, **feats)
@@ -534,66 +557,18 @@ def _eval_group_bags(model, radio_features, path_features, kind=0):
     return xs
 
 
-class _EvalGroup:
-    """validate_survival / summary_survival(group=True): the eligible bags of an evaluation pass, held on the device until
-    one grouped forward-only call (model.forward_group) runs them.  One per pass: nothing outlives the pass (an exception
-    leaves no held bags behind, and the buffer is freed with it).  As _BagGroup: each bag is copied straight into its rows
-    of one reusable device buffer [n_mod x rows x L] (fp32, or bf16 pathology bags); a bag that would take the group past
-    ops.GROUP_MAX bags or the row limit, or one of the other storage type, flushes what is held first."""
-
-    def __init__(self):
-        self.buf = None
-        self.reset()
-
-    def reset(self):
-        self.rows, self.sizes, self.labels, self.cs, self.slots = 0, [], [], [], []
-
-    @staticmethod
-    def row_limit(model, nmod, L, dtype):
-        from .. import ops
-        seq = model.attention_net_radio if hasattr(model, "attention_net_radio") else model.attention_net_WSI
-        H, D = seq[0].out_features, seq[3].stack_params()[0].shape[0]
-        if nmod > 1:
-            return ops.radio_infer_group_row_limit(nmod, L, H, D)
-        return ops.infer_group_row_limit(L, H, D, bf16=dtype == torch.bfloat16)
-
-    @staticmethod
-    def limit_of(model, xs, cache):
-        """row_limit for the bag xs, memoised in `cache` (a dict the pass keeps) by modality count, width and dtype."""
-        key = (len(xs), int(xs[0].shape[1]), xs[0].dtype)
-        if key not in cache:
-            cache[key] = _EvalGroup.row_limit(model, *key)
-        return cache[key]
-
-    def add(self, xs, label, c, slot, limit, device, flush):
-        """xs: the bag's [n x L] tensors, one per modality (the pathology head: one); label, c: device tensors."""
-        from .. import ops
-        nmod, n, L, dtype = len(xs), int(xs[0].shape[0]), int(xs[0].shape[1]), xs[0].dtype
-        if device.type == "cuda" and device.index is None:        # compare with the buffer's device, which has its index
-            device = torch.device("cuda", torch.cuda.current_device())
-        if self.sizes and (len(self.sizes) >= ops.GROUP_MAX or self.rows + n > limit or self.buf.dtype != dtype):
-            flush()
-        need = self.rows + n
-        if (self.buf is None or self.buf.shape[0] != nmod or self.buf.shape[2] != L or self.buf.shape[1] < need
-                or self.buf.dtype != dtype or self.buf.device != device):
-            grown = torch.empty((nmod, max(need, 2 * self.buf.shape[1] if self.buf is not None else need), L),
-                                dtype=dtype, device=device)
-            if self.rows:
-                grown[:, :self.rows].copy_(self.buf[:, :self.rows])
-            self.buf = grown
-        for m, x in enumerate(xs):
-            self.buf[m, self.rows:need].copy_(x, non_blocking=True)
-        self.rows = need
-        self.sizes.append(n); self.labels.append(label.reshape(1)); self.cs.append(c.reshape(1)); self.slots.append(slot)
+class _EvalGroup(_HeldBags):
+    """validate_survival / summary_survival(group=True): the eligible bags of an evaluation pass, until one grouped
+    forward-only call (model.forward_group) runs them.  One per pass: nothing outlives the pass (an exception leaves no
+    held bags behind, and the buffer is freed with it)."""
 
     def run(self, model, loss_alpha=None):
         """One grouped call over the held bags -> [(slot, hazards [1 x K], S [1 x K], loss (0-dim) or None, risk [1])];
         loss_alpha: each bag's NLLSurvLoss value with that alpha, or None for no loss.  The group is empty afterwards."""
         if not self.sizes:
             return []
-        x = self.buf[:, :self.rows] if hasattr(model, "attention_net_radio") else self.buf[0, :self.rows]
         want = loss_alpha is not None
-        hz, S, _, _, loss, risk = model.forward_group((x, list(self.sizes)), torch.cat(self.labels) if want else None,
+        hz, S, _, _, loss, risk = model.forward_group(self.held(model), torch.cat(self.labels) if want else None,
                                                       torch.cat(self.cs) if want else None,
                                                       alpha=loss_alpha if want else 0.0)
         out = [(slot, hz[g:g + 1], S[g:g + 1], loss[g] if want else None, risk[g:g + 1])

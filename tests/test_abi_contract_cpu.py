@@ -408,3 +408,170 @@ def test_linear_backward_contract():
     assert call(k=1022, wsb=1 << 40) == SHAPE
     assert call(nseg=2, xs=[fake(), None]) == ARG
     assert call(nseg=2, xs=[fake(), None], wsb=0) == WS               # the workspace before the segments
+
+
+# ---- grouped forward-only passes ------------------------------------------------------------------------------------
+def infer_target():
+    return target(dWk=None, dbk=None)              # forward-only: no classifier gradients
+
+
+@pytest.mark.parametrize("x_bf16", [0, 1])
+@pytest.mark.parametrize("gated", [0, 1])
+def test_infer_group_contract(x_bf16, gated):
+    f = lib().mmf_amil_infer_group
+
+    def query(d, offs=OFFS, bf16=x_bf16):
+        d = d or desc(N=3000, L=2048)
+        return lib().mmf_amil_group_infer_workspace_bytes((C.c_int64 * len(offs))(*offs), len(offs) - 1, d.L, d.H, d.D,
+                                                          d.gated, bf16)
+
+    def call(d, grp=True, h=True, t=True, x=True, ws=True, wsb=None, M=True, A=True):
+        wsb = query(d) if wsb is None else wsb
+        grp = group(OFFS, seeds=False) if grp is True else grp
+        h = head() if h is True else h
+        t = infer_target() if t is True else t
+        return f(ref(d), ref(grp), fake() if x is True else x, x_bf16, fake() if ws is True else ws, wsb, ref(h), ref(t),
+                 fake() if M else None, fake() if A else None, None)
+
+    mk = lambda **kw: desc(**{**dict(N=3000, L=2048, gated=gated), **kw})
+    d = mk()
+    full = query(d)
+    assert full > 0
+    # A bf16 window's query is the larger of its own carve and the fp32 one (one buffer serves either storage).  Where the
+    # bf16 carve is the larger (this gated shape), one byte less is refused; where it is not, query - 1 bytes would pass
+    # every check and launch, so the cases below that must get as far as the workspace check pass no bytes at all.
+    short = full - 1 if not x_bf16 or full > query(d, bf16=0) else 0
+    assert short or not gated
+    assert call(None) == ARG
+    assert call(d, grp=None) == ARG
+    assert call(d, x=None) == ARG
+    assert call(d, ws=None) == ARG
+    assert call(d, A=False) == ARG
+    # the head, the target and M are optional, but a loss needs the head and a call without a head exists for M
+    assert call(d, t=None, wsb=short) == WS
+    assert call(d, M=False, wsb=short) == WS
+    assert call(d, h=None, t=None, wsb=short) == WS
+    assert call(d, h=None, t=None, M=False) == ARG
+    assert call(d, h=None) == ARG
+    assert call(d, h=None, M=False) == ARG
+    assert call(d, grp=group(OFFS), wsb=short) == WS                 # seeds are not read
+    # refused before the offset table and the descriptor are checked: dropout, bf16x3
+    assert call(mk(p_h=0.25)) == ARG
+    assert call(mk(p_att=0.25)) == ARG
+    assert call(mk(gemm=BF16X3)) == ARG
+    assert call(mk(H=384, p_h=0.25), wsb=1 << 40) == ARG
+    assert call(mk(H=384, gemm=BF16X3), grp=group([5, 1000, 3000], seeds=False), wsb=1 << 40) == ARG
+    # the offset table, then the descriptor, then the head
+    assert call(d, grp=group([0, 1000, 1000, 3000], seeds=False)) == SHAPE
+    assert call(d, grp=group([5, 1000, 3000], seeds=False)) == SHAPE
+    assert call(mk(N=2999)) == SHAPE
+    assert call(mk(N=2999, W1=None)) == SHAPE
+    assert call(mk(H=384), wsb=1 << 40) == SHAPE
+    assert call(mk(W1=None)) == ARG
+    assert call(mk(H=384, W1=None), wsb=1 << 40) == ARG
+    assert call(d, h=head(K=33)) == SHAPE
+    assert call(d, h=head(K=0)) == SHAPE
+    assert call(mk(H=384), h=head(K=33), wsb=1 << 40) == SHAPE
+    assert call(mk(W1=None), h=head(K=33)) == ARG
+    hd = head()
+    hd.hazards = None
+    assert call(d, h=hd) == ARG
+    assert call(d, h=hd, x=fake() + 4) == ARG
+    assert call(d, h=head(K=33), x=None) == SHAPE                          # the head before the call's pointers
+    for n in ("Y", "c", "loss"):
+        assert call(d, t=target(dWk=None, dbk=None, **{n: None})) == ARG, n
+    assert call(d, t=target(), wsb=short) == WS                        # classifier gradient pointers are not read
+    # a gated H = D = 256 stack takes the fused bf16 forward one bag at a time: its bf16 windows are refused
+    small = mk(H=256, D=256)
+    assert call(small, wsb=0) == (SHAPE if x_bf16 and gated else WS)
+    assert call(small, h=head(K=33)) == SHAPE
+    assert call(small, h=None, M=False) == (SHAPE if x_bf16 and gated else ARG)   # the stack before the head
+    assert call(mk(L=1056), wsb=0) == (SHAPE if x_bf16 else WS)          # bf16: L % 64; fp32 takes L % 32
+    assert call(d, x=fake() + 4) == ALIGN
+    assert call(d, ws=fake() + 8) == ALIGN
+    assert call(d, x=fake() + 4, ws=None) == ARG                           # null before alignment
+    assert call(mk(W1=fake() + 4), wsb=short) == (WS if x_bf16 else ALIGN)   # bf16 converts the weights: any alignment
+    assert call(mk(Wa=fake() + 4), wsb=short) == (WS if x_bf16 else ALIGN)
+    if gated:
+        assert call(mk(Wb=fake() + 4), wsb=short) == (WS if x_bf16 else ALIGN)
+        assert call(mk(Wb=None)) == ARG
+    assert call(d, wsb=short) == WS
+    assert call(d, x=fake() + 4, wsb=short) == ALIGN                    # alignment before the workspace
+    assert call(d, A=False, wsb=short) == ARG
+
+
+def test_radio_infer_group_contract():
+    from multimodalfusion_amd import _lib
+    f = lib().mmf_radio_infer_group
+    L = 1024
+
+    def radio(nseg=4, kseg=L, xs=None, **kw):
+        xs = xs if xs is not None else [fake() for _ in range(nseg)]
+        arr = (C.c_void_p * len(xs))(*xs)
+        r = _lib.RadioReduce(x=C.cast(arr, C.POINTER(C.c_void_p)), nseg=nseg, kseg=kseg, W=fake(), bias=fake(),
+                             dW=None, db=None)
+        for k, v in kw.items():
+            setattr(r, k, v)
+        r._keep = arr
+        return r
+
+    def query(d, nseg=4, offs=OFFS):
+        d = d or desc(N=3000, L=L)
+        return lib().mmf_radio_group_infer_workspace_bytes((C.c_int64 * len(offs))(*offs), len(offs) - 1, nseg, L, d.H,
+                                                           d.D, d.gated)
+
+    def call(d, rd, grp=True, h=True, t=True, ws=True, wsb=None, M=True, A=True):
+        wsb = query(d, rd.nseg if rd is not None and 2 <= rd.nseg <= 4 else 4) if wsb is None else wsb
+        grp = group(OFFS, seeds=False) if grp is True else grp
+        h = head() if h is True else h
+        t = infer_target() if t is True else t
+        return f(ref(d), ref(grp), ref(rd), fake() if ws is True else ws, wsb, ref(h), ref(t), fake() if M else None,
+                 fake() if A else None, None)
+
+    d = desc(N=3000, L=L)
+    for nseg in (2, 3, 4):
+        full = query(d, nseg)
+        assert full > 0
+        assert call(d, radio(nseg), wsb=full - 1) == WS
+        assert call(d, radio(nseg), h=None, t=None, wsb=full - 1) == WS
+        assert call(d, radio(nseg, xs=[fake() + 4] + [fake()] * (nseg - 1)), wsb=full - 1) == ALIGN
+        assert call(d, radio(nseg, xs=[fake()] * (nseg - 1) + [fake() + 4]), wsb=full - 1) == ALIGN
+    assert call(d, None) == ARG
+    r = radio()
+    r.x = None
+    assert call(d, r) == ARG
+    assert call(None, radio()) == ARG
+    assert call(d, radio(), grp=None) == ARG
+    assert call(d, radio(nseg=1, xs=[fake()] * 4), wsb=1 << 40) == SHAPE
+    assert call(d, radio(nseg=5, xs=[fake()] * 5), wsb=1 << 40) == SHAPE
+    assert call(None, radio(nseg=5, xs=[fake()] * 5), wsb=1 << 40) == SHAPE      # the modality count before the descriptor
+    assert call(desc(N=3000, L=L, p_h=0.25), radio(nseg=5, xs=[fake()] * 5), wsb=1 << 40) == SHAPE
+    assert call(desc(N=3000, L=L, p_h=0.25), radio()) == ARG
+    assert call(desc(N=3000, L=L, p_att=0.25), radio()) == ARG
+    assert call(desc(N=3000, L=L, gemm=BF16X3), radio()) == ARG
+    assert call(desc(N=3000, L=L, H=384), radio(), wsb=1 << 40) == SHAPE
+    assert call(desc(N=2999, L=L), radio()) == SHAPE
+    assert call(d, radio(), h=None, M=False) == ARG
+    assert call(d, radio(), h=None) == ARG                                        # a target without a head
+    assert call(d, radio(), h=head(K=33)) == SHAPE
+    assert call(d, radio(), ws=None) == ARG
+    assert call(d, radio(), A=False) == ARG
+    assert call(d, radio(), ws=fake() + 8) == ALIGN
+    assert call(desc(N=3000, L=L, W1=fake() + 4), radio()) == ALIGN
+    assert call(d, radio(xs=[None, fake(), fake(), fake()])) == ARG               # the stack's input is x[0]
+    assert call(d, radio(xs=[fake() + 4, fake(), fake(), fake()])) == ALIGN
+    assert call(d, radio(xs=[fake() + 4, fake(), fake(), fake()], kseg=512)) == ALIGN   # ... checked before kseg
+    assert call(d, radio(kseg=512)) == SHAPE
+    assert call(d, radio(kseg=512, W=None)) == SHAPE
+    big = desc(N=140000, L=L)
+    big_offs = [0, 70000, 140000]
+    assert call(big, radio(), grp=group(big_offs, seeds=False), wsb=1 << 40) == SHAPE    # [sum N x 4 L] >= 2 GiB
+    for n in ("W", "bias"):
+        assert call(d, radio(**{n: None})) == ARG, n
+    assert call(d, radio(dW=fake(), db=fake()), wsb=query(d) - 1) == WS          # reduce_dim's gradient pointers are not read
+    assert call(d, radio(xs=[fake(), fake(), None, fake()])) == ARG
+    assert call(d, radio(xs=[fake(), fake(), fake() + 4, fake()])) == ALIGN
+    assert call(d, radio(xs=[fake(), fake(), fake() + 4, None])) == ARG           # every null before any alignment
+    assert call(d, radio(W=fake() + 4)) == ALIGN
+    assert call(d, radio(W=fake() + 4, xs=[fake(), None, fake(), fake()])) == ARG
+    assert call(d, radio(W=fake() + 4), wsb=query(d) - 1) == ALIGN               # alignment before the workspace

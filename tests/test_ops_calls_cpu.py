@@ -19,8 +19,12 @@ def _snap(a):
     """A call argument as plain values, taken when the call is made (structs are filled in place)."""
     if isinstance(a, type(C.byref(C.c_int()))):
         a = a._obj
+    if isinstance(a, _lib.BagGroup):     # host arrays behind pointers: read while the caller keeps them alive
+        return {"G": a.G, "offsets": a.offsets[:a.G + 1], "seeds": a.seeds[:a.G] if a.seeds else None}
     if isinstance(a, C.Structure):
         return {name: _snap(getattr(a, name)) for name, _ in a._fields_}
+    if isinstance(a, C._Pointer):
+        return C.cast(a, C.c_void_p).value
     if isinstance(a, C.Array):
         return [_snap(v) for v in a]
     return a
@@ -412,3 +416,137 @@ def test_mm_nll_step(rec, fusion, bf16):
     hazards, S, Y_hat, A_raw, loss, risk = out
     assert set(A_raw) == {"radiology", "pathology"} and A_raw["pathology"].shape == (1, 7)
     assert all(p.grad is not None for p in model.parameters())
+
+
+# ---- the grouped passes: one accumulation or evaluation window per call ----------------------------------------------
+SIZES = [3, 1, 4]
+
+
+def _group_case(rec, monkeypatch, gated, K, radio=0, grads=True):
+    """Stack, classifier, (reduce_dim) and their gradient buffers of a grouped call; the seed word is a live tensor."""
+    word = torch.zeros(1, dtype=torch.int32)
+    monkeypatch.setattr(ops, "_seed_word", word)
+    stack = _stack(gated, grad=False)
+    Wk, bk = torch.randn(K, 8), torch.randn(K)
+    red = (torch.randn(16, 16 * radio), torch.randn(16)) if radio else ()
+    ps = (*red, *stack, Wk, bk)
+    gs = tuple(None if p is None else torch.zeros_like(p) for p in ps) if grads else None
+    return word, stack, Wk, bk, red, gs
+
+
+def _check_window(rec, query, entry, qargs, ws_at):
+    """[query, entry] with the query's arguments; the entry gets a fresh workspace of the size just queried.
+    Returns the entry's labelled arguments."""
+    assert rec.names == [query, entry]
+    log, sizes = rec.log()
+    assert list(rec.calls[0][1][0]) == [0, 3, 4, 8] and rec.calls[0][1][1:] == qargs
+    args = log[1][1]
+    assert args[ws_at + 1] == log[0][2] and sizes[args[ws_at]] == log[0][2]
+    assert args[-1] == STREAM
+    return args
+
+
+def _check_desc(d, word, L, gated, p_h, p_att, train):
+    assert _desc_fields(d) == _expect(sum(SIZES), L, 8, 4, gated, p_h, p_att, 0)
+    assert (d["seed_dev"] is not None) == train              # the seed word: training only
+    assert (d["Wb"] is None) == (not gated) and d["W1"] is not None and d["trace"] is None
+
+
+def _check_group(grp, seeds):
+    assert grp == {"G": 3, "offsets": [0, 3, 4, 8], "seeds": seeds}
+
+
+@pytest.mark.parametrize("gated", [True, False])
+def test_amil_nll_step_group(rec, monkeypatch, gated):
+    word, stack, Wk, bk, _, gs = _group_case(rec, monkeypatch, gated, 4)
+    x = torch.randn(8, 16)
+    Y, c = torch.tensor([1, 0, 3]), torch.tensor([0.0, 1.0, 0.0])
+    hz, S, Y_hat, A, loss, risk = ops.amil_nll_step_group(x, SIZES, stack, Wk, bk, gated, Y, c, 0.4, gs, loss_scale=0.5,
+                                                          accumulate=True, p_h=0.25, p_att=0.125, seeds=[7, 8, 1 << 32 | 9])
+    a = _check_window(rec, "mmf_amil_group_workspace_bytes", "mmf_amil_nll_step_group", [3, 16, 8, 4, int(gated)], 3)
+    d, grp, xp, _, _, hd, tg, A_raw, g, _ = a
+    _check_desc(d, word, 16, gated, 0.25, 0.125, train=True)
+    _check_group(grp, [7, 8, 9])
+    assert hd["K"] == 4 and all(hd[n] is not None for n in ("Wk", "bk", "logits", "hazards", "S", "Y_hat", "risk"))
+    assert tg["alpha"] == pytest.approx(0.4) and tg["loss_scale"] == 0.5 and tg["accumulate"] == 1
+    assert all(tg[n] is not None for n in ("Y", "c", "loss", "dWk", "dbk"))
+    assert len({tg["dWk"], tg["dbk"], tg["loss"]}) == 3
+    assert g["dx"] is None and (g["dWb"] is None) == (not gated) and (g["dbb"] is None) == (not gated)
+    assert all(g[n] is not None for n in ("dW1", "db1", "dWa", "dba", "dWc", "dbc"))
+    assert hz.shape == (3, 4) and S.shape == (3, 4) and Y_hat.shape == (3, 1) and Y_hat.dtype == torch.int64
+    assert loss.shape == (3,) and risk.shape == (3,)
+    assert [tuple(v.shape) for v in A] == [(1, 3), (1, 1), (1, 4)]
+    assert A[1].data_ptr() == A[0].data_ptr() + 12 and rec.tensors[A[0].data_ptr()].numel() == 8   # views of one A_raw
+    with pytest.raises(IndexError, match="label out of range"):
+        ops.amil_nll_step_group(x, SIZES, stack, Wk, bk, gated, torch.tensor([1, 4, 3]), c, 0.4, gs)
+    assert len(rec.calls) == 2
+
+
+def test_radio_nll_step_group(rec, monkeypatch):
+    word, stack, Wk, bk, (Wr, br), gs = _group_case(rec, monkeypatch, True, 4, radio=3)
+    xs = [torch.randn(8, 16) for _ in range(3)]
+    Y, c = torch.tensor([1, 0, 3]), torch.tensor([0.0, 1.0, 0.0])
+    hz, S, Y_hat, A, loss, risk = ops.radio_nll_step_group(xs, SIZES, Wr, br, stack, Wk, bk, True, Y, c, 0.4, gs,
+                                                           p_h=0.25, p_att=0.25, seeds=[7, 8, 9])
+    a = _check_window(rec, "mmf_radio_group_workspace_bytes", "mmf_radio_nll_step_group", [3, 3, 16, 8, 4, 1], 3)
+    d, grp, rd, _, _, hd, tg, A_raw, g, _ = a
+    _check_desc(d, word, 16, True, 0.25, 0.25, train=True)
+    _check_group(grp, [7, 8, 9])
+    assert rd["nseg"] == 3 and rd["kseg"] == 16 and all(rd[n] is not None for n in ("x", "W", "bias", "dW", "db"))
+    assert rd["dW"] != rd["W"] and rd["db"] != rd["bias"]
+    assert hd["K"] == 4 and tg["loss_scale"] == 1.0 and tg["accumulate"] == 0
+    assert tg["dWk"] is not None and tg["dbk"] is not None
+    assert g["dx"] is None and g["dW1"] is not None and g["dWb"] is not None
+    assert hz.shape == (3, 4) and S.shape == (3, 4) and Y_hat.shape == (3, 1) and loss.shape == (3,) and risk.shape == (3,)
+    assert [tuple(v.shape) for v in A] == [(1, 3), (1, 1), (1, 4)]
+
+
+def test_amil_infer_group_fp32_with_head_and_labels(rec, monkeypatch):
+    word, stack, Wk, bk, _, _ = _group_case(rec, monkeypatch, True, 4, grads=False)
+    x = torch.randn(8, 16)
+    Y, c = torch.tensor([1, 9, 3]), torch.tensor([0.0, 1.0, 0.0])       # a label out of range goes through: NaN loss
+    hz, S, Y_hat, risk, A, M, loss = ops.amil_infer_group(x, SIZES, stack, True, Wk, bk, Y, c, alpha=0.4)
+    a = _check_window(rec, "mmf_amil_group_infer_workspace_bytes", "mmf_amil_infer_group", [3, 16, 8, 4, 1, 0], 4)
+    d, grp, xp, x_bf16, _, _, hd, tg, Mp, A_raw, _ = a
+    _check_desc(d, word, 16, True, 0.0, 0.0, train=False)
+    _check_group(grp, None)
+    assert x_bf16 == 0 and Mp is None and A_raw is not None
+    assert hd["K"] == 4 and all(hd[n] is not None for n in ("Wk", "bk", "logits", "hazards", "S", "Y_hat", "risk"))
+    assert tg["alpha"] == pytest.approx(0.4) and tg["eps"] == pytest.approx(1e-7) and tg["loss_scale"] == 1.0
+    assert tg["dWk"] is None and tg["dbk"] is None and tg["accumulate"] == 0
+    assert all(tg[n] is not None for n in ("Y", "c", "loss"))
+    assert M is None and hz.shape == (3, 4) and S.shape == (3, 4) and Y_hat.shape == (3, 1) and risk.shape == (3,)
+    assert loss.shape == (3,) and [tuple(v.shape) for v in A] == [(1, 3), (1, 1), (1, 4)]
+
+
+def test_amil_infer_group_bf16_for_M_alone(rec, monkeypatch):
+    word, stack, _, _, _, _ = _group_case(rec, monkeypatch, False, 4, grads=False)
+    x = torch.randn(8, 16).to(torch.bfloat16)
+    hz, S, Y_hat, risk, A, M, loss = ops.amil_infer_group(x, SIZES, stack, False, want_M=True)
+    a = _check_window(rec, "mmf_amil_group_infer_workspace_bytes", "mmf_amil_infer_group", [3, 16, 8, 4, 0, 1], 4)
+    d, grp, xp, x_bf16, _, _, hd, tg, Mp, A_raw, _ = a
+    _check_desc(d, word, 16, False, 0.0, 0.0, train=False)
+    _check_group(grp, None)
+    assert x_bf16 == 1 and hd is None and tg is None and Mp is not None
+    assert (hz, S, Y_hat, risk, loss) == (None,) * 5
+    assert M.shape == (3, 8) and M.dtype == torch.float32 and [tuple(v.shape) for v in A] == [(1, 3), (1, 1), (1, 4)]
+    with pytest.raises(_lib.MmfError, match="nothing to compute"):
+        ops.amil_infer_group(x, SIZES, stack, False)
+    with pytest.raises(_lib.MmfError, match="a loss needs the classifier head"):
+        ops.amil_infer_group(x, SIZES, stack, False, Y=torch.tensor([0, 0, 0]), c=torch.zeros(3), want_M=True)
+    assert len(rec.calls) == 2
+
+
+def test_radio_infer_group(rec, monkeypatch):
+    word, stack, Wk, bk, (Wr, br), _ = _group_case(rec, monkeypatch, True, 4, radio=2, grads=False)
+    xs = [torch.randn(8, 16) for _ in range(2)]
+    hz, S, Y_hat, risk, A, M, loss = ops.radio_infer_group(xs, SIZES, Wr, br, stack, True, Wk, bk, want_M=True)
+    a = _check_window(rec, "mmf_radio_group_infer_workspace_bytes", "mmf_radio_infer_group", [3, 2, 16, 8, 4, 1], 3)
+    d, grp, rd, _, _, hd, tg, Mp, A_raw, _ = a
+    _check_desc(d, word, 16, True, 0.0, 0.0, train=False)
+    _check_group(grp, None)
+    assert rd["nseg"] == 2 and rd["kseg"] == 16 and all(rd[n] is not None for n in ("x", "W", "bias"))
+    assert rd["dW"] is None and rd["db"] is None
+    assert hd["K"] == 4 and hd["risk"] is not None and tg is None and Mp is not None
+    assert loss is None and M.shape == (3, 8) and hz.shape == (3, 4) and S.shape == (3, 4) and Y_hat.shape == (3, 1)
+    assert risk.shape == (3,) and [tuple(v.shape) for v in A] == [(1, 3), (1, 1), (1, 4)]
