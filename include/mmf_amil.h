@@ -289,6 +289,53 @@ int mmf_surv_head_nll_step(const float* feat, int32_t F, const mmf_surv_head* he
                            float* dfeat, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Grouped training step of the multimodal concat head: the G patients of one accumulation window, each with up to three
+ *   branches, as one launch chain per branch around ONE head launch.  The reference runs models/model_mm_attention_mil.py:
+ *   128-200 once per patient inside the window of utils/core_utils.py:200-247; with fixed weights the patients are
+ *   independent forward passes, each stack's GEMMs run once over the window's concatenated rows (as in
+ *   mmf_amil_nll_step_group) and the classifier reads row g of a [G x F] feature matrix that the branches write side by
+ *   side (torch.cat of model_mm_attention_mil.py:168-187 is never a launch).  The caller sequences, on one stream:
+ *   radio forward, pathology forward, omic forward, mmf_surv_head_nll_step_group, then the three backward halves.
+ *
+ * mmf_amil_group_forward: the forward half of mmf_amil_nll_step_group's chain on the pathology stack
+ *   (model_mm_attention_mil.py:154-160 for every patient): per-row tables, projection, gate, pooling partials, and a per-bag
+ *   merge that writes M_g to M + g * ldm (ldm >= H floats: the stack's columns of the feature matrix) and A_raw [sum N].
+ *   Everything the backward half needs -- h, a, b, the row tables, M_g and the softmax statistics -- stays in the workspace
+ *   (mmf_amil_group_workspace_bytes), which must reach mmf_amil_group_backward unmodified.  desc, group, x and the masks as
+ *   in mmf_amil_nll_step_group.
+ * mmf_amil_group_backward: the backward half from dM (row g at dM + g * ldm: the stack's columns of
+ *   mmf_surv_head_nll_step_group's dfeat): K-prep, K-dh, split-K TN and the reduce launch.  grads: overwritten, or added
+ *   to when accumulate != 0; grads->dx must be NULL.  group->seeds is not read again (the row tables are in the workspace)
+ *   but must be given.  ldm == H: dM itself is read, and must be 16-byte aligned.
+ * mmf_radio_group_forward / mmf_radio_group_backward: the same pair behind reduce_dim (model_mm_attention_mil.py:132-150),
+ *   mmf_radio_nll_step_group's launches cut at the same point; rd and the workspace (mmf_radio_group_workspace_bytes) as there;
+ *   the forward reads neither rd->dW nor rd->db.
+ * All four return what mmf_amil_nll_step_group / mmf_radio_nll_step_group return for the same arguments, in the same order,
+ *   and MMF_ERR_SHAPE for ldm < H.  No workgroup waits for another; calls are deterministic.
+ *
+ * mmf_surv_head_nll_step_group: mmf_surv_head_nll_step for the G patients of the window (model_mm_attention_mil.py:190-194,
+ *   utils/loss_utils.py:22-39, utils/core_utils.py:207 per patient): one workgroup per patient over feat [G x F] (row g at
+ *   feat + g * ldf; F <= 1024, K <= 32, G <= MMF_GROUP_MAX) and one reduce launch.  The per-patient arrays of head / target
+ *   are G long, as in mmf_amil_nll_step_group.  dfeat [G x F] (row g at dfeat + g * F) = d(loss_g * loss_scale) / d feat_g.
+ *   dWk / dbk: the sum over the patients, in patient order, overwritten or (target->accumulate) added to.
+ *   workspace: mmf_surv_head_group_workspace_bytes(F, K, G) -- the per-patient slabs -- which is 0 for an F, K or G out of range.
+ * ------------------------------------------------------------------------------------------- */
+int mmf_amil_group_forward(const mmf_amil_desc* desc, const mmf_bag_group* group, const float* x, void* workspace,
+                           size_t workspace_bytes, float* M, int32_t ldm, float* A_raw /* [sum N] */, void* stream);
+int mmf_amil_group_backward(const mmf_amil_desc* desc, const mmf_bag_group* group, const float* x, void* workspace,
+                            size_t workspace_bytes, const float* dM, int32_t ldm, const float* A_raw,
+                            const mmf_amil_grads* grads, int32_t accumulate, void* stream);
+int mmf_radio_group_forward(const mmf_amil_desc* desc, const mmf_bag_group* group, const mmf_radio_reduce* rd,
+                            void* workspace, size_t workspace_bytes, float* M, int32_t ldm, float* A_raw, void* stream);
+int mmf_radio_group_backward(const mmf_amil_desc* desc, const mmf_bag_group* group, const mmf_radio_reduce* rd,
+                             void* workspace, size_t workspace_bytes, const float* dM, int32_t ldm, const float* A_raw,
+                             const mmf_amil_grads* grads, int32_t accumulate, void* stream);
+size_t mmf_surv_head_group_workspace_bytes(int32_t F, int32_t K, int32_t G);
+int mmf_surv_head_nll_step_group(const float* feat, int32_t ldf, int32_t F, int32_t G, const mmf_surv_head* head,
+                                 const mmf_nll_target* target, float* dfeat, void* workspace, size_t workspace_bytes,
+                                 void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Forward-only variants for the inference consumers of the path -- embedding export
  * (pre_trained_feature.py:116-162: model(..., return_features=True) under no_grad), per-patient inference and
  * attention heat-map scoring (utils/heatmap_utils.py:111-150,249-275: A_raw per bag / per 512-patch batch).
@@ -375,6 +422,20 @@ int mmf_dense_backward(const float* dy, const float* y, const float* x, const fl
                        int32_t B, int32_t K, int32_t N, int32_t act,
                        int32_t drop_kind, float drop_p, uint32_t seed, uint32_t site, const uint32_t* seed_dev,
                        float* dpre_scratch, float* dx, float* dW, float* db, void* stream);
+/* The dense pair on a batch whose rows are the patients of one accumulation window (the omic branch of the grouped
+ * multimodal step: models/model_mm_attention_mil.py:164-165 once per patient becomes one B = G batch): row b draws the
+ * mask of ITS OWN seed.  row_base: DEVICE [B], row_base[b] = mmf_dropout_row_base(seed_b) (host helper: seed_b times the
+ * inverse of the hash multiplier mod 2^32); element (b, n) then gets the mask mmf_dense_forward draws for a one-row call
+ * with seed_b at index n -- nn.Dropout and nn.AlphaDropout forms alike.  y (and dy) may be columns of a wider matrix:
+ * ldy / lddy >= N floats between rows.  Otherwise as mmf_dense_forward / mmf_dense_backward (dW, db: sums over the rows). */
+uint32_t mmf_dropout_row_base(uint32_t seed);
+int mmf_dense_forward_rows(const float* x, const float* W, const float* bias, int32_t B, int32_t K, int32_t N,
+                           int32_t act, int32_t drop_kind, float drop_p, uint32_t site, const uint32_t* seed_dev,
+                           const uint32_t* row_base, float* y, int32_t ldy, void* stream);
+int mmf_dense_backward_rows(const float* dy, int32_t lddy, const float* y, int32_t ldy, const float* x, const float* W,
+                            int32_t B, int32_t K, int32_t N, int32_t act, int32_t drop_kind, float drop_p, uint32_t site,
+                            const uint32_t* seed_dev, const uint32_t* row_base, float* dpre_scratch, float* dx, float* dW,
+                            float* db, void* stream);
 /* o = sigmoid(z) * h (n elements) and its backward. */
 int mmf_gate_mul_forward(const float* z, const float* h, float* o, int32_t n, void* stream);
 int mmf_gate_mul_backward(const float* g, const float* z, const float* h, float* dz, float* dh, int32_t n, void* stream);

@@ -115,6 +115,26 @@ SYMBOLS = {
                                            C.POINTER(AmilGrads), C.c_void_p]),
     "mmf_surv_head_nll_step": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(SurvHead), C.POINTER(NllTarget), C.c_void_p,
                                          C.c_void_p]),
+    "mmf_amil_group_forward": (C.c_int, [C.POINTER(AmilDesc), C.POINTER(BagGroup), C.c_void_p, C.c_void_p, C.c_size_t,
+                                         C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "mmf_amil_group_backward": (C.c_int, [C.POINTER(AmilDesc), C.POINTER(BagGroup), C.c_void_p, C.c_void_p, C.c_size_t,
+                                          C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(AmilGrads), C.c_int32, C.c_void_p]),
+    "mmf_radio_group_forward": (C.c_int, [C.POINTER(AmilDesc), C.POINTER(BagGroup), C.POINTER(RadioReduce), C.c_void_p,
+                                          C.c_size_t, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "mmf_radio_group_backward": (C.c_int, [C.POINTER(AmilDesc), C.POINTER(BagGroup), C.POINTER(RadioReduce), C.c_void_p,
+                                           C.c_size_t, C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(AmilGrads), C.c_int32,
+                                           C.c_void_p]),
+    "mmf_surv_head_group_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    "mmf_surv_head_nll_step_group": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(SurvHead),
+                                               C.POINTER(NllTarget), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "mmf_dropout_row_base": (C.c_uint32, [C.c_uint32]),
+    "mmf_dense_forward_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                         C.c_int32, C.c_int32, C.c_float, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_int32, C.c_void_p]),
+    "mmf_dense_backward_rows": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                          C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_uint32,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p]),
     "mmf_amil_group_infer_workspace_bytes": (C.c_size_t, [C.POINTER(C.c_int64), C.c_int32, C.c_int32, C.c_int32,
                                                            C.c_int32, C.c_int32, C.c_int32]),
     "mmf_amil_infer_group": (C.c_int, [C.POINTER(AmilDesc), C.POINTER(BagGroup), C.c_void_p, C.c_int32, C.c_void_p,

@@ -1188,6 +1188,110 @@ int launch_group_pool(PoolParams p, const SegTable& s, hipStream_t st) {
   return hipGetLastError() == hipSuccess ? MMF_OK : MMF_ERR_LAUNCH;
 }
 
+// ---- grouped multimodal step (mmf_amil_group_forward / _backward, mmf_surv_head_nll_step_group) ---------------------
+// One workgroup per bag: group_tail_kernel's merge without the head tail behind it -- the same partials, the same weights
+// in LDS, the same order of additions.  The body is a copy, as group_infer_tail_kernel's is, so that those two kernels
+// stay instruction for instruction what they were; a change to one of the three goes into the others.  M_g goes
+// to the caller's M + g * ldm -- a stack writes straight into its columns of the window's [G x F] feature matrix -- and,
+// with stats_g, to the workspace (Mw [G x H], p.stats [G x 2]), where the backward half reads them.
+__global__ __launch_bounds__(1024) void group_merge_kernel(PoolParams p, SegTable s, int ldm, float* Mw) {
+  __shared__ float wl[GROUP_BAG_MAX_PARTIALS];
+  __shared__ float red[32];
+  const int g = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int gb = s.gbeg[g], n = s.gbeg[g + 1] - gb, H = p.H;
+  const int stride = 2 + H;
+  const float* part = p.partials + (size_t)gb * stride;
+  float m = -INFINITY;
+  for (int i = tid; i < n; i += 1024) m = fmaxf(m, part[(size_t)i * stride]);
+  m = wave_max(m);
+  if (lane == 0) red[wave] = m;
+  __syncthreads();
+  m = red[0];
+#pragma unroll
+  for (int i = 1; i < 16; ++i) m = fmaxf(m, red[i]);
+  float l = 0.f;
+  for (int i = tid; i < n; i += 1024) {
+    const float mg = part[(size_t)i * stride];
+    const float w = mg > -INFINITY ? __expf(mg - m) : 0.f;
+    wl[i] = w;
+    l += part[(size_t)i * stride + 1] * w;
+  }
+  l = wave_sum(l);
+  if (lane == 0) red[16 + wave] = l;
+  __syncthreads();
+  l = 0.f;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) l += red[16 + i];
+  if (tid < H) {                           // pool_merge_kernel's order: 32 interleaved slices, then the slices in order
+    const float* col = part + 2 + tid;
+    float acc = 0.f;
+    for (int sl = 0; sl < 32; ++sl) {
+      float a = 0.f;
+      for (int i = sl; i < n; i += 32) a += col[(size_t)i * stride] * wl[i];
+      acc += a;
+    }
+    const float mv = acc / l;
+    p.M[(size_t)g * ldm + tid] = mv;
+    Mw[(size_t)g * H + tid] = mv;
+  }
+  if (tid == 0) { p.stats[2 * g] = m; p.stats[2 * g + 1] = l; }
+}
+
+int launch_group_merge(PoolParams p, const SegTable& s, int ldm, float* Mw, hipStream_t st) {
+  if (p.H != 256 && p.H != 512 && p.H != 1024) return MMF_ERR_SHAPE;
+  if (s.G < 1 || s.G > GROUP_MAX || ldm < p.H || !p.M || !Mw || !p.stats) return MMF_ERR_SHAPE;
+  for (int g = 0; g < s.G; ++g)
+    if (s.gbeg[g + 1] - s.gbeg[g] > GROUP_BAG_MAX_PARTIALS) return MMF_ERR_SHAPE;
+  ProfScope ps("group_merge_kernel", st);
+  hipLaunchKernelGGL(group_merge_kernel, dim3(s.G), dim3(1024), 0, st, p, s, ldm, Mw);
+  return hipGetLastError() == hipSuccess ? MMF_OK : MMF_ERR_LAUNCH;
+}
+
+// dst [G x H] <- the H columns of src [G x ld] that belong to one stack: the backward half's dM, which K-prep and K-dh
+// read as one [G x H] block
+__global__ __launch_bounds__(256) void group_dm_gather_kernel(const float* src, int ld, float* dst, int G, int H) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= G * H) return;
+  const int g = i / H, c = i - g * H;
+  dst[i] = src[(size_t)g * ld + c];
+}
+int launch_group_dm_gather(const float* src, int ld, float* dst, int G, int H, hipStream_t st) {
+  if (!src || !dst || G < 1 || G > GROUP_MAX || H < 1 || ld < H) return MMF_ERR_SHAPE;
+  ProfScope ps("group_dm_gather_kernel", st);
+  hipLaunchKernelGGL(group_dm_gather_kernel, dim3((G * H + 255) / 256), dim3(256), 0, st, src, ld, dst, G, H);
+  return hipGetLastError() == hipSuccess ? MMF_OK : MMF_ERR_LAUNCH;
+}
+
+// The hazard head of a window: one workgroup per patient g over feat [G x ldf] -- head_tail (the one-patient step's
+// device code, head_tail_kernel) on row g: classifier, sigmoid, cumprod, argmax, risk, nll_surv and its backward.  The
+// per-patient arrays of p.tail are G long; tail.dM is dfeat [G x F]; tail.dWk / dbk are per-patient slabs [G x K x F],
+// [G x K] (dbk_g = dlogits_g), overwritten: the reduce launch behind sums them in patient order.
+__global__ __launch_bounds__(1024) void surv_head_group_kernel(PoolParams p, int ldf) {
+  __shared__ float tail_sm[1024 + 160];
+  const int g = blockIdx.x, F = p.H, K = p.tail.K;
+  PoolParams q = p;
+  q.M = p.M + (size_t)g * ldf;
+  q.merge_in_tail = 0;
+  HeadTail& t = q.tail;
+  t.logits += (size_t)g * K; t.hazards += (size_t)g * K; t.S += (size_t)g * K; t.Y_hat += g;
+  if (t.risk) t.risk += g;
+  t.Y += g; t.c += g; t.loss += g;
+  t.dM += (size_t)g * F;
+  t.dWk += (size_t)g * K * F; t.dbk += (size_t)g * K;
+  t.accumulate = 0;
+  TailPre pre;
+  tail_preload(q, pre);
+  head_tail(q, pre, tail_sm);
+}
+
+int launch_surv_head_group(PoolParams p, int ldf, int G, hipStream_t st) {
+  if (!p.M || !p.tail.Wk || !p.tail.Y || !p.tail.dM || !p.tail.dWk || !p.tail.dbk) return MMF_ERR_ARG;
+  if (p.H < 1 || p.H > 1024 || ldf < p.H || p.tail.K < 1 || p.tail.K > 32 || G < 1 || G > GROUP_MAX) return MMF_ERR_SHAPE;
+  ProfScope ps("surv_head_group_kernel", st);
+  hipLaunchKernelGGL(surv_head_group_kernel, dim3(G), dim3(1024), 0, st, p, ldf);
+  return hipGetLastError() == hipSuccess ? MMF_OK : MMF_ERR_LAUNCH;
+}
+
 // ---- forward-only grouped pass (mmf_amil_infer_group) ----------------------------------------------------------------
 // One workgroup per bag: merge the bag's partials into M_g (written when p.M is given), then the classifier, hazards, S,
 // Y_hat, risk and -- when labels are given -- the bag's nll_surv value.  No dM, no classifier gradient.  The merge is

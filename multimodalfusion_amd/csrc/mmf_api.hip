@@ -837,12 +837,10 @@ static int group_check(const mmf_amil_desc* d, const mmf_bag_group* group, const
   return MMF_OK;
 }
 
-// the stack's chain over the window's rows x [sum N x L]: per-row tables, projection, gate, pooling + head tail per bag,
-// K-prep, K-dh, (du . W1), split-K TN.  The masks are those of the seed-0 keys at each row's index base (group_rows_kernel).
-// The stack's and the classifier's sums go on `rl`, for the caller's reduce launch.
-static int group_chain(const mmf_amil_desc* d, const SegTable& s, const float* x, const GroupWs& gw, const HeadTail& tl,
-                       int K, const mmf_nll_target* target, float* A_raw, const mmf_amil_grads* g,
-                       const GroupExtra* ex, ReduceList& rl, hipStream_t st) {
+// The stack's chain over the window's rows x [sum N x L], in three parts.  The masks are those of the seed-0 keys at each
+// row's index base (group_rows_kernel).
+// Forward, up to the scores: per-row tables, projection, gate.
+static int group_chain_fwd(const mmf_amil_desc* d, const SegTable& s, const float* x, const GroupWs& gw, hipStream_t st) {
   const AmilWs& w = gw.w;
 
   GroupRowsParams rp0{};
@@ -855,18 +853,19 @@ static int group_chain(const mmf_amil_desc* d, const SegTable& s, const float* x
 
   GateFwdParams gp = stack_gate_fwd(d, w, 0);
   gp.seg_ridx = gw.ridx_d;
-  if (int e = launch_gate_fwd_seg(gp, st)) return e;
+  return launch_gate_fwd_seg(gp, st);
+}
 
-  PoolParams pp = stack_pool(d, w, A_raw);
-  pp.partials = gw.partials; pp.M = gw.M; pp.stats = gw.stats;
-  pp.tail = tl; pp.tail.dM = gw.dM; pp.tail.dWk = gw.wk; pp.tail.dbk = gw.bk;
-  if (int e = launch_group_pool(pp, s, st)) return e;
-
-  const BwdPrepParams bp = stack_prep(d, w, A_raw, gw.stats, gw.M, gw.dM, nullptr);
+// Backward, from dM [G x H] (M and the softmax statistics per bag are in the workspace): K-prep, K-dh, (du . W1),
+// split-K TN.  The stack's sums go on `rl`, for the caller's reduce launch.
+static int group_chain_bwd(const mmf_amil_desc* d, const float* x, const GroupWs& gw, const float* dM, const float* A_raw,
+                           const mmf_amil_grads* g, const GroupExtra* ex, ReduceList& rl, hipStream_t st) {
+  const AmilWs& w = gw.w;
+  const BwdPrepParams bp = stack_prep(d, w, A_raw, gw.stats, gw.M, dM, nullptr);
   if (int e = launch_group_bwd_prep(bp, gw.bag, st)) return e;
 
   const GateBwdCtx gc = gate_bwd_ctx(d, w.a, w.b, w.ds, 0);
-  BwdDhParams dp = stack_dh(d, w, gc, gw.dM);
+  BwdDhParams dp = stack_dh(d, w, gc, dM);
   dp.seg_ridx = gw.ridx_d; dp.seg_bag = gw.bag;
   if (int e = launch_bwd_dh_seg(dp, st)) return e;
 
@@ -890,8 +889,63 @@ static int group_chain(const mmf_amil_desc* d, const SegTable& s, const float* x
   }
 
   stack_reduce(d, w, g, bp.n_groups, rl);
+  return MMF_OK;
+}
+
+// The single-head chain: forward, pooling + head tail per bag (which leaves dM in the workspace), backward.  The
+// classifier's sums go on `rl` behind the stack's.
+static int group_chain(const mmf_amil_desc* d, const SegTable& s, const float* x, const GroupWs& gw, const HeadTail& tl,
+                       int K, const mmf_nll_target* target, float* A_raw, const mmf_amil_grads* g,
+                       const GroupExtra* ex, ReduceList& rl, hipStream_t st) {
+  if (int e = group_chain_fwd(d, s, x, gw, st)) return e;
+
+  PoolParams pp = stack_pool(d, gw.w, A_raw);
+  pp.partials = gw.partials; pp.M = gw.M; pp.stats = gw.stats;
+  pp.tail = tl; pp.tail.dM = gw.dM; pp.tail.dWk = gw.wk; pp.tail.dbk = gw.bk;
+  if (int e = launch_group_pool(pp, s, st)) return e;
+
+  if (int e = group_chain_bwd(d, x, gw, gw.dM, A_raw, g, ex, rl, st)) return e;
   rl.add(gw.wk, target->dWk, K * d->H, s.G, (size_t)K * d->H);      // classifier: the bags' slabs in bag order
   rl.add(gw.bk, target->dbk, K, s.G, (size_t)K);
+  return MMF_OK;
+}
+
+// The multimodal window's halves of that chain (mmf_amil_group_forward / _backward, and the radio pair): the forward
+// ends in the per-bag merge, which writes M_g into the caller's feature matrix; the backward starts from the caller's
+// dM, whose H columns of this stack it first brings together as [G x H] (they are, when ldm == H).
+static int group_half_fwd(const mmf_amil_desc* d, const SegTable& s, const float* x, const GroupWs& gw, float* M, int ldm,
+                          float* A_raw, hipStream_t st) {
+  if (int e = group_chain_fwd(d, s, x, gw, st)) return e;
+  PoolParams pp = stack_pool(d, gw.w, A_raw);
+  pp.partials = gw.partials; pp.M = M; pp.stats = gw.stats;
+  if (int e = launch_group_pool_partial(pp, s, st)) return e;
+  return launch_group_merge(pp, s, ldm, gw.M, st);
+}
+static int group_half_bwd(const mmf_amil_desc* d, const SegTable& s, const float* x, const GroupWs& gw, const float* dM,
+                          int ldm, const float* A_raw, const mmf_amil_grads* g, const GroupExtra* ex, ReduceList& rl,
+                          hipStream_t st) {
+  if (ldm != d->H) {
+    if (int e = launch_group_dm_gather(dM, ldm, gw.dM, s.G, d->H, st)) return e;
+    dM = gw.dM;
+  }
+  return group_chain_bwd(d, x, gw, dM, A_raw, g, ex, rl, st);
+}
+
+// what the four half entry points check, in group_check's order without the head: fills the segment table (forward:
+// with each bag's mask index base).  g: the backward's gradients, null for a forward.
+static int group_half_check(const mmf_amil_desc* d, const mmf_bag_group* group, const void* x, const void* workspace,
+                            const float* M, int ldm, const float* A_raw, const mmf_amil_grads* g, bool bwd, SegTable& s) {
+  if (!d || !group || !M || (bwd && !g)) return MMF_ERR_ARG;
+  if (d->gemm != MMF_GEMM_F32 || (g && g->dx)) return MMF_ERR_ARG;
+  if (!group->seeds) return MMF_ERR_ARG;
+  if (int e = window_plan(d, group, 0, s)) return e;
+  if (ldm < d->H) return MMF_ERR_SHAPE;
+  if (g) if (int e = check_grads(d, g)) return e;
+  if (int e = check_operands(d, x, workspace, A_raw, false)) return e;
+  if (g && !grads_aligned(d, g)) return MMF_ERR_ALIGN;
+  if (bwd && ldm == d->H && !aligned16(M)) return MMF_ERR_ALIGN;     // K-dh reads an ungathered dM four floats at a time
+  const uint32_t inv = hash_mul_inverse();
+  for (int b = 0; b < s.G; ++b) s.ibase[b] = group->seeds[b] * inv;
   return MMF_OK;
 }
 
@@ -963,6 +1017,29 @@ static LinearParams radio_linear(const mmf_amil_desc* d, const mmf_radio_reduce*
   if (kpart && d->sync && d->sync_words > 0) { lr.kpart = kpart; lr.ktick = d->sync; lr.ktick_words = d->sync_words; }
   return lr;
 }
+// reduce_dim's backward as the chain's extra work: dW_r[:, m kseg : (m + 1) kseg] = dxr^T . x_m ; db_r = colsum(dxr) with the first
+static GroupExtra radio_extra(const mmf_amil_desc* d, const mmf_radio_reduce* rd, const RadioWs& r) {
+  const int nseg = rd->nseg, kseg = rd->kseg, L = d->L;
+  GroupExtra ex{};
+  ex.dx = r.dxr;
+  ex.separate = r.separate; ex.splits = r.splits; ex.k_per_split = r.k_per_split;
+  ex.nprob = nseg;
+  for (int m = 0; m < nseg; ++m) {
+    TnProblem& q = ex.prob[m];
+    q.kind = TN_A_PLAIN; q.A = r.dxr; q.lda = L; q.M = L;
+    q.B = rd->x[m]; q.ldb = kseg; q.Ncols = kseg;
+    q.out = r.slab + (size_t)m * kseg; q.split_stride = (size_t)L * nseg * kseg; q.ldc = nseg * kseg;
+    q.colsum = m == 0 ? r.cs : nullptr; q.colsum_stride = L;
+    q.splits = r.splits; q.k_per_split = r.k_per_split;
+  }
+  return ex;
+}
+// reduce_dim's two sums, behind the stack's on the reduce list (gated: the stack's 10 + these 2 = every slot)
+static void radio_reduce(const mmf_amil_desc* d, const mmf_radio_reduce* rd, const RadioWs& r, ReduceList& rl) {
+  const int n = d->L * rd->nseg * rd->kseg;
+  rl.add(r.slab, rd->dW, n, r.splits, (size_t)n);
+  rl.add(r.cs, rd->db, d->L, r.splits, (size_t)d->L);
+}
 }  // namespace mmf
 
 size_t mmf_amil_group_workspace_bytes(const int64_t* offsets, int32_t G, int32_t L, int32_t H, int32_t D, int32_t gated) {
@@ -1004,30 +1081,118 @@ int mmf_radio_nll_step_group(const mmf_amil_desc* d, const mmf_bag_group* group,
   HeadTail tl;
   if (int e = group_check(d, group, rd->x[0], workspace, head, target, A_raw, g, s, tl)) return e;
   if (int e = radio_operands(d, rd, true)) return e;
-  const int nseg = rd->nseg, kseg = rd->kseg, L = d->L;
   Carver c(workspace);
-  RadioWs r = carve_radio(c, s, nseg, kseg, d->H, d->D, d->gated);
+  RadioWs r = carve_radio(c, s, rd->nseg, rd->kseg, d->H, d->D, d->gated);
   if (r.bytes > workspace_bytes) return MMF_ERR_WORKSPACE;
   hipStream_t st = static_cast<hipStream_t>(stream);
   TraceScope ts(d->trace);
   if (int e = launch_linear(radio_linear(d, rd, r.xr, r.kpart, d->seed_dev), st)) return e;
 
-  GroupExtra ex{};
-  ex.dx = r.dxr;
-  ex.separate = r.separate; ex.splits = r.splits; ex.k_per_split = r.k_per_split;
-  ex.nprob = nseg;
-  for (int m = 0; m < nseg; ++m) {   // dW_r[:, m kseg : (m + 1) kseg] = dxr^T . x_m ; db_r = colsum(dxr) with the first
-    TnProblem& q = ex.prob[m];
-    q.kind = TN_A_PLAIN; q.A = r.dxr; q.lda = L; q.M = L;
-    q.B = rd->x[m]; q.ldb = kseg; q.Ncols = kseg;
-    q.out = r.slab + (size_t)m * kseg; q.split_stride = (size_t)L * nseg * kseg; q.ldc = nseg * kseg;
-    q.colsum = m == 0 ? r.cs : nullptr; q.colsum_stride = L;
-    q.splits = r.splits; q.k_per_split = r.k_per_split;
-  }
+  const GroupExtra ex = radio_extra(d, rd, r);
   ReduceList rl;
   if (int e = group_chain(d, s, r.xr, r.gw, tl, head->K, target, A_raw, g, &ex, rl, st)) return e;
-  rl.add(r.slab, rd->dW, L * nseg * kseg, r.splits, (size_t)L * nseg * kseg);   // gated: the stack's 10 + these 2 = every slot
-  rl.add(r.cs, rd->db, L, r.splits, (size_t)L);
+  radio_reduce(d, rd, r, rl);
+  return rl.launch(target->accumulate ? 1 : 0, st);
+}
+
+// ---- grouped multimodal step: the two stacks' halves, the window's hazard head ------------------------------------
+int mmf_amil_group_forward(const mmf_amil_desc* d, const mmf_bag_group* group, const float* x, void* workspace,
+                           size_t workspace_bytes, float* M, int32_t ldm, float* A_raw, void* stream) {
+  SegTable s;
+  if (int e = group_half_check(d, group, x, workspace, M, ldm, A_raw, nullptr, false, s)) return e;
+  Carver c(workspace);
+  const GroupWs gw = carve_group(c, s, d->L, d->H, d->D, d->gated);
+  if (gw.bytes > workspace_bytes) return MMF_ERR_WORKSPACE;
+  TraceScope ts(d->trace);
+  return group_half_fwd(d, s, x, gw, M, ldm, A_raw, static_cast<hipStream_t>(stream));
+}
+
+int mmf_amil_group_backward(const mmf_amil_desc* d, const mmf_bag_group* group, const float* x, void* workspace,
+                            size_t workspace_bytes, const float* dM, int32_t ldm, const float* A_raw,
+                            const mmf_amil_grads* g, int32_t accumulate, void* stream) {
+  SegTable s;
+  if (int e = group_half_check(d, group, x, workspace, dM, ldm, A_raw, g, true, s)) return e;
+  Carver c(workspace);
+  const GroupWs gw = carve_group(c, s, d->L, d->H, d->D, d->gated);
+  if (gw.bytes > workspace_bytes) return MMF_ERR_WORKSPACE;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  TraceScope ts(d->trace);
+  ReduceList rl;
+  if (int e = group_half_bwd(d, s, x, gw, dM, ldm, A_raw, g, nullptr, rl, st)) return e;
+  return rl.launch(accumulate ? 1 : 0, st);
+}
+
+int mmf_radio_group_forward(const mmf_amil_desc* d, const mmf_bag_group* group, const mmf_radio_reduce* rd,
+                            void* workspace, size_t workspace_bytes, float* M, int32_t ldm, float* A_raw, void* stream) {
+  if (int e = radio_modalities(rd)) return e;
+  SegTable s;
+  if (int e = group_half_check(d, group, rd->x[0], workspace, M, ldm, A_raw, nullptr, false, s)) return e;
+  if (int e = radio_operands(d, rd, false)) return e;
+  Carver c(workspace);
+  const RadioWs r = carve_radio(c, s, rd->nseg, rd->kseg, d->H, d->D, d->gated);
+  if (r.bytes > workspace_bytes) return MMF_ERR_WORKSPACE;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  TraceScope ts(d->trace);
+  if (int e = launch_linear(radio_linear(d, rd, r.xr, r.kpart, d->seed_dev), st)) return e;
+  return group_half_fwd(d, s, r.xr, r.gw, M, ldm, A_raw, st);
+}
+
+int mmf_radio_group_backward(const mmf_amil_desc* d, const mmf_bag_group* group, const mmf_radio_reduce* rd,
+                             void* workspace, size_t workspace_bytes, const float* dM, int32_t ldm, const float* A_raw,
+                             const mmf_amil_grads* g, int32_t accumulate, void* stream) {
+  if (int e = radio_modalities(rd)) return e;
+  SegTable s;
+  if (int e = group_half_check(d, group, rd->x[0], workspace, dM, ldm, A_raw, g, true, s)) return e;
+  if (int e = radio_operands(d, rd, true)) return e;
+  Carver c(workspace);
+  const RadioWs r = carve_radio(c, s, rd->nseg, rd->kseg, d->H, d->D, d->gated);
+  if (r.bytes > workspace_bytes) return MMF_ERR_WORKSPACE;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  TraceScope ts(d->trace);
+  const GroupExtra ex = radio_extra(d, rd, r);
+  ReduceList rl;
+  if (int e = group_half_bwd(d, s, r.xr, r.gw, dM, ldm, A_raw, g, &ex, rl, st)) return e;
+  radio_reduce(d, rd, r, rl);
+  return rl.launch(accumulate ? 1 : 0, st);
+}
+
+namespace mmf {
+// the window head's workspace: the per-patient classifier slabs the reduce launch sums
+struct HeadGroupWs { float *wk, *bk; size_t bytes; };
+static HeadGroupWs carve_head_group(Carver& c, int F, int K, int G) {
+  HeadGroupWs w{};
+  w.wk = c.take<float>((size_t)G * K * F);
+  w.bk = c.take<float>((size_t)G * K);
+  w.bytes = c.off;
+  return w;
+}
+}  // namespace mmf
+
+size_t mmf_surv_head_group_workspace_bytes(int32_t F, int32_t K, int32_t G) {
+  if (F < 1 || F > 1024 || K < 1 || K > 32 || G < 1 || G > GROUP_MAX) return 0;
+  Carver c;
+  return carve_head_group(c, F, K, G).bytes;
+}
+
+int mmf_surv_head_nll_step_group(const float* feat, int32_t ldf, int32_t F, int32_t G, const mmf_surv_head* head,
+                                 const mmf_nll_target* target, float* dfeat, void* workspace, size_t workspace_bytes,
+                                 void* stream) {
+  if (!feat || !target || !dfeat || !workspace) return MMF_ERR_ARG;
+  if (F < 1 || F > 1024 || ldf < F || G < 1 || G > GROUP_MAX) return MMF_ERR_SHAPE;
+  PoolParams p{};
+  if (int e = head_tail_of(head, target, p.tail)) return e;
+  if (!aligned16(workspace)) return MMF_ERR_ALIGN;
+  Carver c(workspace);
+  const HeadGroupWs w = carve_head_group(c, F, head->K, G);
+  if (w.bytes > workspace_bytes) return MMF_ERR_WORKSPACE;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  p.tail.dM = dfeat; p.tail.dWk = w.wk; p.tail.dbk = w.bk;
+  p.M = const_cast<float*>(feat);        // read only
+  p.H = F;
+  if (int e = launch_surv_head_group(p, ldf, G, st)) return e;
+  ReduceList rl;
+  rl.add(w.wk, target->dWk, head->K * F, G, (size_t)head->K * F);     // the patients' slabs in patient order
+  rl.add(w.bk, target->dbk, head->K, G, (size_t)head->K);
   return rl.launch(target->accumulate ? 1 : 0, st);
 }
 
@@ -1476,6 +1641,30 @@ int mmf_dense_backward(const float* dy, const float* y, const float* x, const fl
   if (!dy || !y || !x || !W || !dpre_scratch || B < 1 || K < 1 || N < 1) return MMF_ERR_ARG;
   if (act < 0 || act > ACT_SELU || drop_kind < 0 || drop_kind > 2) return MMF_ERR_ARG;
   DenseBwdParams p{dy, y, x, W, dpre_scratch, dx, dW, db, B, K, N, act, make_drop(drop_kind, drop_p, seed, site, seed_dev)};
+  return launch_dense_bwd(p, static_cast<hipStream_t>(stream));
+}
+
+uint32_t mmf_dropout_row_base(uint32_t seed) { return seed * hash_mul_inverse(); }
+
+int mmf_dense_forward_rows(const float* x, const float* W, const float* bias, int32_t B, int32_t K, int32_t N,
+                           int32_t act, int32_t drop_kind, float drop_p, uint32_t site, const uint32_t* seed_dev,
+                           const uint32_t* row_base, float* y, int32_t ldy, void* stream) {
+  if (!x || !W || !y || !row_base || B < 1 || K < 1 || N < 1) return MMF_ERR_ARG;
+  if (act < 0 || act > ACT_SELU || drop_kind < 0 || drop_kind > 2 || drop_p < 0.f || drop_p >= 1.f) return MMF_ERR_ARG;
+  if (ldy < N) return MMF_ERR_SHAPE;
+  DenseParams p{x, W, bias, y, B, K, N, act, make_drop(drop_kind, drop_p, 0, site, seed_dev), row_base, ldy};
+  return launch_dense_fwd(p, static_cast<hipStream_t>(stream));
+}
+
+int mmf_dense_backward_rows(const float* dy, int32_t lddy, const float* y, int32_t ldy, const float* x, const float* W,
+                            int32_t B, int32_t K, int32_t N, int32_t act, int32_t drop_kind, float drop_p, uint32_t site,
+                            const uint32_t* seed_dev, const uint32_t* row_base, float* dpre_scratch, float* dx, float* dW,
+                            float* db, void* stream) {
+  if (!dy || !y || !x || !W || !row_base || !dpre_scratch || B < 1 || K < 1 || N < 1) return MMF_ERR_ARG;
+  if (act < 0 || act > ACT_SELU || drop_kind < 0 || drop_kind > 2) return MMF_ERR_ARG;
+  if (ldy < N || lddy < N) return MMF_ERR_SHAPE;
+  DenseBwdParams p{dy, y, x, W, dpre_scratch, dx, dW, db, B, K, N, act, make_drop(drop_kind, drop_p, 0, site, seed_dev),
+                   row_base, ldy, lddy};
   return launch_dense_bwd(p, static_cast<hipStream_t>(stream));
 }
 

@@ -291,6 +291,13 @@ int launch_group_bwd_prep(BwdPrepParams p, const int* bag, hipStream_t st);
 // forward (p.tail per-bag outputs as in launch_group_pool; Y given: loss [G] only; dM / dWk / dbk are not read)
 int launch_group_pool_partial(PoolParams p, const SegTable& s, hipStream_t st);
 int launch_group_infer_tail(PoolParams p, const SegTable& s, hipStream_t st);
+// grouped multimodal step: the merge of launch_group_pool without the head tail -- M_g to p.M + g * ldm (the caller's
+// feature matrix) and to Mw [G x H], stats_g to p.stats [G x 2] (p.partials from launch_group_pool_partial); the dM
+// columns of one stack out of a [G x ld] matrix; and the hazard head of G patients over p.M = feat [G x ldf], p.H = F
+// (per-patient p.tail arrays as in launch_group_pool; tail.dM = dfeat [G x F])
+int launch_group_merge(PoolParams p, const SegTable& s, int ldm, float* Mw, hipStream_t st);
+int launch_group_dm_gather(const float* src, int ld, float* dst, int G, int H, hipStream_t st);
+int launch_surv_head_group(PoolParams p, int ldf, int G, hipStream_t st);
 int set_dyn_lds(const void* kern, int bytes);
 
 // Optional per-kernel timing with HIP events on the launch stream: records into the mmf_trace of the ABI call in

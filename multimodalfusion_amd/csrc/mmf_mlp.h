@@ -15,12 +15,19 @@ struct DenseParams {
   float* y;
   int B, K, N, act;
   DropSpec drop;
+  // Per-row mask index base [B], or null.  Given: element (b, n) hashes row_base[b] + n under drop.key where the plain
+  // form hashes b * N + n.  With drop.key the seed-0 key of the site and row_base[b] = seed_b * inverse(0x9E3779B1)
+  // (mmf_api.hip: hash_mul_inverse), row b gets the mask a one-row call with seed_b draws at index n.
+  const uint32_t* row_base;
+  int ldy;                     // row_base given: leading dimension of y (>= N)
 };
 struct DenseBwdParams {
   const float *dy, *y, *x, *W;
   float *dpre, *dx, *dW, *db;
   int B, K, N, act;
   DropSpec drop;
+  const uint32_t* row_base;   // as DenseParams::row_base
+  int ldy, lddy;              // row_base given: leading dimensions of y and dy (>= N)
 };
 struct KronParams {
   const float* o[3];

@@ -62,7 +62,10 @@ __device__ inline void drop_bwd(float yd, const DropSpec& d, uint32_t idx, float
   y = k ? (yd - af.b) / af.a : 0.f;
 }
 
-// one wave per output element (b, n); lanes stride over K
+// one wave per output element (b, n); lanes stride over K.  RB (grouped multimodal step: row b is patient b of a window):
+// the mask index of (b, n) is row_base[b] + n under the seed-0 key of the site -- patient b's own mask at index n, see
+// DenseParams::row_base -- where the plain form hashes b * N + n.
+template <bool RB>
 __global__ __launch_bounds__(256) void dense_fwd_kernel(DenseParams p) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int64_t total = (int64_t)p.B * p.N;
@@ -80,14 +83,18 @@ __global__ __launch_bounds__(256) void dense_fwd_kernel(DenseParams p) {
     float acc = wave_sum((a0 + a1) + (a2 + a3));
     if (lane == 0) {
       float y = act_fwd(acc + (p.bias ? p.bias[n] : 0.f), p.act);
-      p.y[o] = drop_fwd(y, p.drop, (uint32_t)o);
+      if (RB) p.y[(size_t)b * p.ldy + n] = drop_fwd(y, p.drop, p.row_base[b] + (uint32_t)n);
+      else p.y[o] = drop_fwd(y, p.drop, (uint32_t)o);
     }
   }
 }
 
+template <bool RB> __device__ inline float dense_dpre_at(const DenseBwdParams& p, int b, int n);
+template <bool RB>
 __global__ __launch_bounds__(256) void dense_dpre_kernel(DenseBwdParams p) {
   const int64_t total = (int64_t)p.B * p.N;
   for (int64_t o = (int64_t)blockIdx.x * 256 + threadIdx.x; o < total; o += (int64_t)gridDim.x * 256) {
+    if (RB) { p.dpre[o] = dense_dpre_at<true>(p, (int)(o / p.N), (int)(o % p.N)); continue; }
     float dydy, y;
     drop_bwd(p.y[o], p.drop, (uint32_t)o, dydy, y);
     p.dpre[o] = p.dy[o] * dydy * act_grad_from_y(y, p.act);
@@ -348,7 +355,9 @@ int launch_dense_fwd(DenseParams p, hipStream_t st) {
   const int64_t total = (int64_t)p.B * p.N;
   int blocks = cdiv(total, 4);
   if (blocks > 65535 * 16) blocks = 65535 * 16;
-  { ProfScope ps("dense_fwd_kernel", st); hipLaunchKernelGGL(dense_fwd_kernel, dim3(blocks), dim3(256), 0, st, p); }
+  { ProfScope ps("dense_fwd_kernel", st);
+    if (p.row_base) hipLaunchKernelGGL(dense_fwd_kernel<true>, dim3(blocks), dim3(256), 0, st, p);
+    else hipLaunchKernelGGL(dense_fwd_kernel<false>, dim3(blocks), dim3(256), 0, st, p); }
   return hipGetLastError() == hipSuccess ? MMF_OK : MMF_ERR_LAUNCH;
 }
 
@@ -356,12 +365,18 @@ int launch_dense_fwd(DenseParams p, hipStream_t st) {
 // dpre = dy . drop' . act'(y) is rebuilt through LDS by whoever needs it instead of a separate pass
 // (the layers are tiny: three launches of ~7 us each per layer were the cost, not the arithmetic).
 constexpr int DENSE_MAX_N = 2048, DENSE_MAX_B = 256;
+template <bool RB>
 __device__ inline float dense_dpre_at(const DenseBwdParams& p, int b, int n) {
   const int64_t o = (int64_t)b * p.N + n;
   float dydy, y;
+  if (RB) {               // y / dy rows may be columns of wider matrices (the fused feature matrix and its gradient)
+    drop_bwd(p.y[(size_t)b * p.ldy + n], p.drop, p.row_base[b] + (uint32_t)n, dydy, y);
+    return p.dy[(size_t)b * p.lddy + n] * dydy * act_grad_from_y(y, p.act);
+  }
   drop_bwd(p.y[o], p.drop, (uint32_t)o, dydy, y);
   return p.dy[o] * dydy * act_grad_from_y(y, p.act);
 }
+template <bool RB>
 __global__ __launch_bounds__(256) void dense_bwd_kernel(DenseBwdParams p, int nbx, int dx_blocks, int nbw) {
   __shared__ float sh[DENSE_MAX_N];
   const int tid = threadIdx.x;
@@ -371,7 +386,7 @@ __global__ __launch_bounds__(256) void dense_bwd_kernel(DenseBwdParams p, int nb
     // (the layer is latency-bound: B = 1, a handful of blocks, hundreds of dependent-address loads each)
     __shared__ float part[4][64];
     const int b = id / nbx, kl = tid & 63, sl = tid >> 6, k = (id % nbx) * 64 + kl;
-    for (int n = tid; n < p.N; n += 256) sh[n] = dense_dpre_at(p, b, n);
+    for (int n = tid; n < p.N; n += 256) sh[n] = dense_dpre_at<RB>(p, b, n);
     __syncthreads();
     float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
     if (k < p.K) {
@@ -391,7 +406,7 @@ __global__ __launch_bounds__(256) void dense_bwd_kernel(DenseBwdParams p, int nb
   } else {                                    // ---- dW[n][k] = sum_b dpre[b][n] x[b][k] ; db[n] = sum_b dpre[b][n]
     id -= dx_blocks;
     const int n = id / nbw, kb = id % nbw, k = kb * 256 + tid;
-    if (tid < p.B) sh[tid] = dense_dpre_at(p, tid, n);
+    if (tid < p.B) sh[tid] = dense_dpre_at<RB>(p, tid, n);
     __syncthreads();
     if (k < p.K) {
       float acc = 0.f;
@@ -414,10 +429,13 @@ int launch_dense_bwd(DenseBwdParams p, hipStream_t st) {
     const int dw_blocks = p.dW ? nbw * p.N : 0;
     if (dx_blocks + dw_blocks == 0) return MMF_OK;
     { ProfScope ps("dense_bwd_kernel", st);
-      hipLaunchKernelGGL(dense_bwd_kernel, dim3(dx_blocks + dw_blocks), dim3(256), 0, st, p, nbx, dx_blocks, nbw); }
+      if (p.row_base) hipLaunchKernelGGL(dense_bwd_kernel<true>, dim3(dx_blocks + dw_blocks), dim3(256), 0, st, p, nbx, dx_blocks, nbw);
+      else hipLaunchKernelGGL(dense_bwd_kernel<false>, dim3(dx_blocks + dw_blocks), dim3(256), 0, st, p, nbx, dx_blocks, nbw); }
     return hipGetLastError() == hipSuccess ? MMF_OK : MMF_ERR_LAUNCH;
   }
-  { ProfScope ps("dense_dpre_kernel", st); hipLaunchKernelGGL(dense_dpre_kernel, dim3(cdiv(total, 256)), dim3(256), 0, st, p); }
+  { ProfScope ps("dense_dpre_kernel", st);
+    if (p.row_base) hipLaunchKernelGGL(dense_dpre_kernel<true>, dim3(cdiv(total, 256)), dim3(256), 0, st, p);
+    else hipLaunchKernelGGL(dense_dpre_kernel<false>, dim3(cdiv(total, 256)), dim3(256), 0, st, p); }
   if (p.dx) { ProfScope ps("dense_dx_kernel", st); hipLaunchKernelGGL(dense_dx_kernel, dim3(cdiv(p.K, 256), p.B), dim3(256), 0, st, p); }
   if (p.dW) { ProfScope ps("dense_dw_kernel", st); hipLaunchKernelGGL(dense_dw_kernel, dim3(cdiv(p.K, 256), p.N), dim3(256), 0, st, p); }
   return hipGetLastError() == hipSuccess ? MMF_OK : MMF_ERR_LAUNCH;

@@ -309,6 +309,178 @@ class MM_MIL_Attention_fc_surv(MM_MIL_Attention_fc):
             hand_over_grads(params, grads, grad_out, accumulate)
         return hazards, S, Y_hat, A_raw, loss, risk
 
+    def _stacked_patients(self, patients):
+        """The window's inputs per branch: (path (x_cat [sum N x L], sizes) or None, radio ([modality tensors, each
+        [sum n x L]], sizes) or None, omic [G x input_dim] or None), from a list of per-patient kwarg dicts as nll_step
+        takes them or from the pre-stacked triple (path (x, sizes), radio ([n_mod x rows x L], sizes), omic [G x
+        input_dim]) with None for a branch outside `mode`.  Branches outside `mode` are dropped."""
+        MmfError = ops._lib.MmfError
+        has = lambda k: k in self.mode
+        if isinstance(patients, tuple) and len(patients) == 3 and not any(isinstance(p, dict) for p in patients):
+            path, radio, omic = patients
+            for k, v in (("path", path), ("radio", radio), ("omic", omic)):
+                if has(k) and v is None:
+                    raise MmfError(f"mode {self.mode!r} needs the {k} branch of the pre-stacked window")
+            if has("radio"):
+                x, sizes = radio
+                if x.dim() != 3 or x.shape[0] != len(self.modalities):
+                    raise MmfError(f"pre-stacked radio bags must be [{len(self.modalities)} x rows x L], got {tuple(x.shape)}")
+                radio = (list(x.unbind(0)), [int(n) for n in sizes])
+            if has("path"):
+                path = (path[0], [int(n) for n in path[1]])
+            return (path if has("path") else None, radio if has("radio") else None, omic if has("omic") else None)
+        if not isinstance(patients, (list, tuple)) or not all(isinstance(p, dict) for p in patients):
+            raise TypeError("patients: a list of per-patient kwarg dicts or a pre-stacked (path, radio, omic) triple")
+        if not patients:
+            raise MmfError(f"a group holds 1 .. {ops.GROUP_MAX} patients, got 0")
+        cat = lambda ts: torch.cat(ts, 0) if len(ts) > 1 else ts[0]
+        path = radio = omic = None
+        if has("path"):
+            bags = [p["path_features"] for p in patients]
+            path = (cat(bags), [int(b.shape[0]) for b in bags])
+        if has("radio"):
+            for p in patients:
+                if len({tuple(p[m].shape) for m in self.modalities}) != 1:
+                    raise MmfError("the modalities of a patient must have the same [n x L] shape")
+            radio = ([cat([p[m] for p in patients]) for m in self.modalities],
+                     [int(p[self.modalities[0]].shape[0]) for p in patients])
+        if has("omic"):
+            omic = cat([p["genomic_features"].reshape(1, -1) for p in patients])
+        return path, radio, omic
+
+    def nll_step_group(self, patients, labels, censors, alpha=0.0, loss_scale=1.0, grad_out=None, accumulate=None,
+                       seeds=None):
+        """nll_step for the G <= 64 patients of one accumulation window (fusion='concat', fp32 bags, exact-fp32 GEMMs):
+        within a window the weights are fixed (utils/core_utils.py:242-247 of the reference), so the patients are
+        independent forward passes and their summed gradient is one contraction over all rows.  Each stack runs once
+        over its branch's concatenated rows (ops._group_half_fwd_raw / _group_half_bwd_raw), the omic SNN as one B = G
+        batch whose row g draws patient g's masks (ops._dense_rows_*), and the classifier, hazards, loss and their
+        backward as one launch over the [G x F] feature matrix the branches write side by side
+        (ops.surv_head_nll_step_group).  Everything is issued on the current stream, in this order: radio forward,
+        pathology forward, omic forward, head, pathology backward, omic backward, radio backward, hand_over_grads -- no
+        side stream: the grouped chains fill the GPU themselves.
+
+        patients: a list of per-patient kwarg dicts as nll_step takes them, or the pre-stacked triple (path (x [sum N x
+        L], sizes), radio ([n_mod x rows x L], sizes), omic [G x input_dim]) with None for a branch outside `mode`;
+        pathology and radio sizes are independent and ragged.  labels / censors: G values.
+        Seeds: in train mode patient g draws ops.next_dropout_seed() in nll_step's order -- radio, path, omic for patient
+        0, then patient 1, ... -- so the same seed stream gives every patient the masks G nll_step calls give it; or
+        `seeds` = {"radio": [G], "path": [G], "omic": [G]} (the branches in `mode`).
+        Gradients of sum_g loss_g * loss_scale, same .grad / grad_out conventions as nll_step.
+        Returns (hazards [G x K], S [G x K], Y_hat [G], A_raw {"radiology": [per patient], "pathology": [per patient]},
+        loss [G], risk [G]), detached."""
+        from ..ops import (_dense_rows_bwd_raw, _dense_rows_fwd_raw, _group_half_bwd_raw, _group_half_fwd_raw)
+        MmfError = ops._lib.MmfError
+        if self.fusion != "concat":
+            raise NotImplementedError("nll_step_group covers fusion='concat'; XlinearFusion's kernels take one patient")
+        if ops._gemm != 0:
+            raise MmfError("nll_step_group runs the exact-fp32 GEMMs only (ops.set_gemm(0))")
+        order, cols, F = self._concat_layout()
+        params = list(self.parameters())
+        if any(not p.requires_grad for p in params):
+            raise RuntimeError("nll_step_group needs every parameter to require grad")
+        Wk, bk = self.classifier.weight, self.classifier.bias
+        if Wk.shape[0] > 32:
+            raise MmfError("nll_step_group: the fused hazard head takes K <= 32 classes")
+        path, radio, omic = self._stacked_patients(patients)
+        # ---- every refusal before the first launch
+        counts = {}
+        if path is not None:
+            counts["path"] = len(path[1])
+        if radio is not None:
+            counts["radio"] = len(radio[1])
+        if omic is not None:
+            if omic.dim() != 2:
+                raise MmfError(f"omic features must be [G x input_dim], got {tuple(omic.shape)}")
+            counts["omic"] = int(omic.shape[0])
+        if len(set(counts.values())) != 1:
+            raise MmfError(f"the branches hold different numbers of patients: {counts}")
+        G = next(iter(counts.values()))
+        if G < 1 or G > ops.GROUP_MAX:
+            raise MmfError(f"a group holds 1 .. {ops.GROUP_MAX} patients, got {G}")
+        for k, br in (("path", path), ("radio", radio)):
+            if br is None:
+                continue
+            xs = br[0] if k == "radio" else [br[0]]
+            if any(x.dtype != torch.float32 for x in xs):
+                raise MmfError("the grouped step takes fp32 bags only (bf16 bags: one nll_step per patient)")
+            if min(br[1]) < 1:
+                raise MmfError("empty bag in the group")
+            if any(x.dim() != 2 or x.shape[0] != sum(br[1]) for x in xs):
+                raise MmfError(f"the {k} bags hold {[tuple(x.shape) for x in xs]} rows, their sizes add up to {sum(br[1])}")
+        Y = torch.as_tensor(labels).reshape(-1)
+        cc = torch.as_tensor(censors).reshape(-1)
+        if Y.numel() != G or cc.numel() != G:
+            raise MmfError(f"{G} patients need {G} labels and censorships, got {Y.numel()} / {cc.numel()}")
+        if not Y.is_cuda and bool(((Y < 0) | (Y >= Wk.shape[0])).any()):
+            raise IndexError(f"nll_surv: label out of range [0, {Wk.shape[0]})")
+        tr = self.training
+        if seeds is None:
+            seeds = {k: [0] * G for k in order}
+            if tr:
+                for g in range(G):
+                    for k in ("radio", "path", "omic"):          # nll_step's order of draws
+                        if k in order:
+                            seeds[k][g] = ops.next_dropout_seed()
+        elif any(k not in seeds or len(seeds[k]) != G for k in order):
+            raise MmfError(f"seeds: {G} dropout seeds for each of {order}")
+        dev = (path[0] if path is not None else radio[0][0] if radio is not None else omic).device
+        grads = {}
+
+        def stack_forward(seq, xs, sizes, k, Wr=None, br=None):
+            gated, ps, p_h, p_att = stack_args(seq, tr)
+            A, state = _group_half_fwd_raw(xs, sizes, ps, gated, p_h, p_att, seeds[k], feat[:, cols[k]], Wr, br)
+            return A, (ps, state)
+
+        def stack_backward(run, k):
+            ps, state = run
+            ds, rd = _group_half_bwd_raw(state, dfeat[:, cols[k]])
+            grads.update((p, gr) for p, gr in zip(ps, ds) if p is not None)
+            return rd
+
+        with torch.no_grad():
+            feat = torch.empty((G, F), dtype=torch.float32, device=dev)
+            A_raw = {}
+            if "radio" in order:
+                many = len(radio[0]) > 1         # one modality: no reduce_dim, the pathology pair on that bag
+                A_raw["radiology"], run_r = stack_forward(self.attention_net_radio, radio[0], radio[1], "radio",
+                                                          *((self.reduce_dim.weight, self.reduce_dim.bias) if many else ()))
+            if "path" in order:
+                A_raw["pathology"], run_p = stack_forward(self.attention_net_WSI, [path[0]], path[1], "path")
+            if "omic" in order:
+                word = ops._seed_word
+                base = ops.dropout_row_base(seeds["omic"], dev)
+                acts = [ops._f32c(omic)]
+                nblk = len(self.fc_omic)
+                for i, blk in enumerate(self.fc_omic):
+                    lin, adrop = blk[0], blk[2]
+                    acts.append(_dense_rows_fwd_raw(acts[-1], lin.weight, lin.bias, "selu", "alpha" if tr else "none",
+                                                    adrop.p if tr else 0.0, i, base, word,
+                                                    out=feat[:, cols["omic"]] if i == nblk - 1 else None))
+            # ---- classifier + hazards + loss + their backward for every patient: one launch and its reduce
+            dWk, dbk = torch.empty_like(Wk), torch.empty_like(bk)
+            hazards, S, Y_hat, loss, risk, dfeat = ops.surv_head_nll_step_group(feat, Wk, bk, Y, cc, alpha, dWk, dbk,
+                                                                                loss_scale=loss_scale)
+            grads[Wk], grads[bk] = dWk, dbk
+            if "path" in order:
+                stack_backward(run_p, "path")
+            if "omic" in order:
+                g = dfeat[:, cols["omic"]]
+                for i in range(nblk - 1, -1, -1):
+                    lin, adrop = self.fc_omic[i][0], self.fc_omic[i][2]
+                    g, dW, db = _dense_rows_bwd_raw(g, acts[i + 1], acts[i], lin.weight, lin.bias is not None, "selu",
+                                                    "alpha" if tr else "none", adrop.p if tr else 0.0, i, base,
+                                                    need_dx=i > 0, word=word)
+                    grads[lin.weight] = dW
+                    if lin.bias is not None:
+                        grads[lin.bias] = db
+            if "radio" in order:
+                rd = stack_backward(run_r, "radio")
+                if rd is not None:
+                    grads[self.reduce_dim.weight], grads[self.reduce_dim.bias] = rd
+            hand_over_grads(params, grads, grad_out, accumulate)
+        return hazards, S, Y_hat.view(-1), A_raw, loss, risk
+
     def forward(self, **kwargs):
         A_raw = {}
         path_x = kwargs.get("path_features") if "path" in self.mode else None

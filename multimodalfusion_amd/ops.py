@@ -375,9 +375,10 @@ def radio_group_row_limit(nseg, L, H, D):
     return min(group_row_limit(L, H, D), ((1 << 31) - 1) // (4 * nseg * L))
 
 
-def _group_table(sizes, rows, Y, c, seeds=None, train=True):
+def _group_table(sizes, rows, Y, c, seeds=None, train=True, labels=True):
     """The bag table of a grouped call: sizes checked against the rows given, G labels / censorships (None: a forward-only
-    call without a loss) and, for a training call, G dropout seeds (a forward-only table carries none).
+    call without a loss; labels=False: a stack half of the multimodal step, whose labels go to the head) and, for a
+    training call, G dropout seeds (a forward-only table carries none).
     Returns (sizes, Y, c, offsets (host int64 [G + 1]), BagGroup); the BagGroup points into the offsets and seeds arrays,
     which it keeps alive as attributes."""
     sizes = [int(n) for n in sizes]
@@ -388,7 +389,7 @@ def _group_table(sizes, rows, Y, c, seeds=None, train=True):
         raise _lib.MmfError("empty bag in the group")
     if rows is not None and rows != sum(sizes):
         raise _lib.MmfError(f"the bags hold {rows} rows, their sizes add up to {sum(sizes)}")
-    if Y is not None or train:
+    if Y is not None or train and labels:
         Y = torch.as_tensor(Y).reshape(-1)
         c = torch.as_tensor(c).reshape(-1)
         if Y.numel() != G or c.numel() != G:
@@ -492,6 +493,160 @@ def radio_nll_step_group(xs, sizes, Wr, br, stack, Wk, bk, gated, Y, c, alpha, g
     A_list = _run_group("mmf_radio_group_workspace_bytes", (offs, G, nseg, kseg, H, D, d.gated), "mmf_radio_nll_step_group",
                         d, grp, (C.byref(rd),), hd, tg, (ptr(A_raw), C.byref(g)), A_raw, sizes)
     return hz, S, Y_hat, A_list, loss, risk
+
+
+def mm_group_row_limits(path=None, radio=None):
+    """The row limits of one grouped multimodal window (MM_MIL_Attention_fc_surv.nll_step_group): (pathology rows, radio
+    rows) one call takes, None for a branch that is not given.  path: (L, H, D) of the pathology stack; radio: (nseg, L, H,
+    D) of the radio stack behind reduce_dim (nseg = 1: no reduce_dim, the pathology limit of that stack)."""
+    lim_p = None if path is None else group_row_limit(*path)
+    lim_r = None
+    if radio is not None:
+        nseg, L, H, D = radio
+        lim_r = group_row_limit(L, H, D) if nseg == 1 else radio_group_row_limit(nseg, L, H, D)
+    return lim_p, lim_r
+
+
+def _rows_ptr(t, what):
+    """(device pointer, leading dimension in floats) of a [B x N] fp32 device tensor whose rows are contiguous: a plain
+    matrix, or some columns of a wider one (a branch's slot of the fused feature matrix)."""
+    if t.dim() != 2 or t.dtype != torch.float32 or t.shape[0] < 1 or (t.shape[1] > 1 and t.stride(1) != 1):
+        raise _lib.MmfError(f"{what} must be a [B x N] float32 tensor with contiguous rows")
+    return ptr(t[0]), max(int(t.stride(0)), int(t.shape[1]))
+
+
+def _group_half_fwd_raw(xs, sizes, stack, gated, p_h, p_att, seeds, M_out, Wr=None, br=None):
+    """The forward half of a grouped stack chain (mmf_amil_group_forward; with reduce_dim Wr, br over several modality
+    tensors xs: mmf_radio_group_forward): the window's rows through the stack, bag g's pooled embedding into row g of
+    M_out (a [G x H] tensor or H columns of a wider one).  xs: [x_cat [sum N x L]] or 2 .. 4 modality tensors.
+    Returns ([A_raw [1 x N_g]], state); state is what _group_half_bwd_raw takes."""
+    radio = len(xs) > 1
+    if any(x.dtype != torch.float32 for x in xs):
+        raise _lib.MmfError("the grouped step takes fp32 bags only")
+    if radio:
+        xs, R, nseg, L, rd = _radio_operands(xs, Wr, br, "pass")
+        Wr, br = _f32c(Wr), _f32c(br)
+    else:
+        xs = [_f32c(xs[0])]
+        if xs[0].dim() != 2:
+            raise _lib.MmfError(f"x_cat must be [sum N x L], got {tuple(xs[0].shape)}")
+        R, L = xs[0].shape
+        nseg = 1
+    sizes, _, _, offs, grp = _group_table(sizes, R, None, None, seeds, train=True, labels=False)
+    G = len(sizes)
+    stack, _, H, D = _stack_operands(stack, L, None, "bags")
+    mp, ldm = _rows_ptr(M_out, "M_out")
+    if M_out.shape[0] != G or M_out.shape[1] != H:
+        raise _lib.MmfError(f"M_out must be [{G} x {H}], got {tuple(M_out.shape)}")
+    word = _seed_word
+    d = _amil_desc(stack, R, L, H, D, gated, p_h, p_att, 0, word)
+    dev = xs[0].device
+    A_raw = torch.empty((R,), dtype=torch.float32, device=dev)
+    l = lib()
+    if radio:
+        nbytes = l.mmf_radio_group_workspace_bytes(offs, G, nseg, L, H, D, d.gated)
+    else:
+        nbytes = l.mmf_amil_group_workspace_bytes(offs, G, L, H, D, d.gated)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    if radio:
+        check(l.mmf_radio_group_forward(C.byref(d), C.byref(grp), C.byref(rd), ptr(ws), nbytes, mp, ldm, ptr(A_raw),
+                                        stream_ptr()), "mmf_radio_group_forward")
+    else:
+        check(l.mmf_amil_group_forward(C.byref(d), C.byref(grp), ptr(xs[0]), ptr(ws), nbytes, mp, ldm, ptr(A_raw),
+                                       stream_ptr()), "mmf_amil_group_forward")
+    state = (xs, sizes, stack, gated, (R, L, H, D, gated, p_h, p_att, 0), ws, word, grp, A_raw, Wr, br)
+    return [v.view(1, -1) for v in torch.split(A_raw, sizes)], state
+
+
+def _group_half_bwd_raw(state, dM):
+    """The backward half of a _group_half_fwd_raw call (mmf_amil_group_backward / mmf_radio_group_backward) from dM: a
+    [G x H] tensor or H columns of a wider one (the stack's slot of the head's dfeat).  Returns the stack's eight fresh
+    gradients (None for an ungated Wb, bb) of sum_g loss_g, and (dWr, dbr) or None."""
+    xs, sizes, stack, gated, cfg, ws, word, grp, A_raw, Wr, br = state
+    dp, ldm = _rows_ptr(dM, "dM")
+    if dM.shape[0] != len(sizes) or dM.shape[1] != cfg[2]:
+        raise _lib.MmfError(f"dM must be [{len(sizes)} x {cfg[2]}], got {tuple(dM.shape)}")
+    d = _amil_desc(stack, *cfg, word)
+    ds, _, g = _stack_grads(xs[0], stack, gated, False)
+    l = lib()
+    if len(xs) > 1:
+        dWr, dbr = torch.empty_like(Wr), torch.empty_like(br)
+        rd = _radio_operands(xs, Wr, br, "step", dWr, dbr)[4]
+        check(l.mmf_radio_group_backward(C.byref(d), C.byref(grp), C.byref(rd), ptr(ws), ws.numel(), dp, ldm, ptr(A_raw),
+                                         C.byref(g), 0, stream_ptr()), "mmf_radio_group_backward")
+        return ds, (dWr, dbr)
+    check(l.mmf_amil_group_backward(C.byref(d), C.byref(grp), ptr(xs[0]), ptr(ws), ws.numel(), dp, ldm, ptr(A_raw),
+                                    C.byref(g), 0, stream_ptr()), "mmf_amil_group_backward")
+    return ds, None
+
+
+def surv_head_nll_step_group(feat, Wk, bk, Y, c, alpha, dWk, dbk, loss_scale=1.0, accumulate=False, eps=1e-7):
+    """surv_head_nll_step for the G patients of one accumulation window (mmf_surv_head_nll_step_group): feat [G x F]
+    (F <= 1024, G <= GROUP_MAX), one workgroup per patient and one reduce launch; Y, c: G labels / censorships.  dWk / dbk
+    get the gradient of sum_g loss_g * loss_scale (added when `accumulate`).
+    Returns (hazards [G x K], S [G x K], Y_hat [G x 1], loss [G] (unscaled), risk [G], dfeat [G x F]), detached."""
+    Wk, bk = _f32c(Wk), _f32c(bk)
+    fp, ldf = _rows_ptr(feat, "feat")
+    G, F = feat.shape
+    K = Wk.shape[0]
+    if G < 1 or G > GROUP_MAX:
+        raise _lib.MmfError(f"a group holds 1 .. {GROUP_MAX} patients, got {G}")
+    if Wk.shape[1] != F or F > 1024 or K > 32:
+        raise _lib.MmfError("surv_head_nll_step_group: classifier does not match the feature matrix (F <= 1024, K <= 32)")
+    _check_grad_buffers(((dWk, Wk), (dbk, bk)))
+    Y = torch.as_tensor(Y).reshape(-1)
+    c = torch.as_tensor(c).reshape(-1)
+    if Y.numel() != G or c.numel() != G:
+        raise _lib.MmfError(f"{G} patients need {G} labels and censorships, got {Y.numel()} / {c.numel()}")
+    dev = feat.device
+    hd, tg, (hz, S, Y_hat, loss, risk), _keep = _nll_head(Wk, bk, Y, c, alpha, eps, loss_scale, dWk, dbk, accumulate, dev, G)
+    dfeat = torch.empty((G, F), dtype=torch.float32, device=dev)
+    l = lib()
+    nbytes = l.mmf_surv_head_group_workspace_bytes(F, K, G)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    check(l.mmf_surv_head_nll_step_group(fp, ldf, F, G, C.byref(hd), C.byref(tg), ptr(dfeat), ptr(ws), nbytes, stream_ptr()),
+          "mmf_surv_head_nll_step_group")
+    return hz, S, Y_hat, loss, risk, dfeat
+
+
+_HASH_MUL_INV = pow(0x9E3779B1, -1, 1 << 32)       # mmf_dropout_row_base: the inverse of the keep-hash's index multiplier
+
+
+def dropout_row_base(seeds, device):
+    """The per-row mask index bases of a dense batch whose row b draws with seeds[b] (mmf_dense_forward_rows): an int32
+    device tensor [B] holding seed_b * inverse(0x9E3779B1) mod 2^32."""
+    vals = [((int(v) & 0xFFFFFFFF) * _HASH_MUL_INV) & 0xFFFFFFFF for v in seeds]
+    return torch.tensor([v - (1 << 32) if v >= 1 << 31 else v for v in vals], dtype=torch.int32).to(device)
+
+
+def _dense_rows_fwd_raw(x, W, b, act, kind, p, site, row_base, word=None, out=None):
+    """_dense_fwd_raw on a batch whose row b draws the mask of its own seed (mmf_dense_forward_rows; row_base:
+    dropout_row_base of the seeds).  out: a [B x N] tensor or N columns of a wider one."""
+    B, K = x.shape
+    N = W.shape[0]
+    y = torch.empty((B, N), dtype=torch.float32, device=x.device) if out is None else out
+    yp, ldy = _rows_ptr(y, "out")
+    if tuple(y.shape) != (B, N) or row_base.numel() != B:
+        raise _lib.MmfError(f"dense rows: out must be [{B} x {N}] and row_base [{B}]")
+    check(lib().mmf_dense_forward_rows(ptr(x), ptr(W), ptr(b), B, K, N, ACT[act], DROP_KIND[kind], float(p), int(site),
+                                       ptr(word), ptr(row_base), yp, ldy, stream_ptr()), "mmf_dense_forward_rows")
+    return y
+
+
+def _dense_rows_bwd_raw(gy, y, x, W, has_bias, act, kind, p, site, row_base, need_dx=True, word=None):
+    """(dx, dW, db) of a _dense_rows_fwd_raw call (mmf_dense_backward_rows); gy and y may be columns of wider matrices."""
+    B, K = x.shape
+    N = W.shape[0]
+    gp, ldg = _rows_ptr(gy, "gy")
+    yp, ldy = _rows_ptr(y, "y")
+    dpre = torch.empty((B, N), dtype=torch.float32, device=x.device)
+    dx = torch.empty_like(x) if need_dx else None
+    dW = torch.empty_like(W)
+    db = torch.empty((N,), dtype=torch.float32, device=x.device) if has_bias else None
+    check(lib().mmf_dense_backward_rows(gp, ldg, yp, ldy, ptr(x), ptr(W), B, K, N, ACT[act], DROP_KIND[kind], float(p),
+                                        int(site), ptr(word), ptr(row_base), ptr(dpre), ptr(dx), ptr(dW), ptr(db),
+                                        stream_ptr()), "mmf_dense_backward_rows")
+    return dx, dW, db
 
 
 def infer_group_row_limit(L, H, D, bf16=False):

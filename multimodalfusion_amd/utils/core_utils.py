@@ -241,6 +241,80 @@ class _BagGroup(_HeldBags):
         return out
 
 
+class _MMGroup:
+    """train_loop_survival(group=True) with the multimodal concat head: the eligible patients of the current window, until
+    one grouped call (MM_MIL_Attention_fc_surv.nll_step_group) runs them.  A patient's bags are copied straight into their
+    rows of three reusable device buffers -- the pathology plane [1 x rows x L], the radio planes [n_mod x rows x L] and the
+    omic rows [GROUP_MAX x input_dim] -- and its up to three dropout seeds are drawn when it arrives, in nll_step's order
+    (radio, path, omic), so patient g of the loader gets the masks the per-patient route gives it.  A patient that would
+    take the group past ops.GROUP_MAX or past either branch's row limit flushes what is held first."""
+
+    def __init__(self):
+        self.path, self.radio, self.omic = _HeldBags(), _HeldBags(), None
+        self.limits = {}
+        self.reset()
+
+    def reset(self):
+        self.path.reset()
+        self.radio.reset()
+        self.labels, self.cs, self.slots = [], [], []
+        self.seeds = {"radio": [], "path": [], "omic": []}
+
+    def row_limits(self, model, L_path, L_radio):
+        """(pathology, radio) row limits of one grouped call (ops.mm_group_row_limits), memoised by the bags' widths."""
+        from .. import ops
+        key = (L_path, L_radio)
+        if key not in self.limits:
+            dims = lambda seq: (seq[0].out_features, seq[3].stack_params()[0].shape[0])
+            self.limits[key] = ops.mm_group_row_limits(
+                path=None if L_path is None else (L_path, *dims(model.attention_net_WSI)),
+                radio=None if L_radio is None else (len(model.modalities), L_radio, *dims(model.attention_net_radio)))
+        return self.limits[key]
+
+    def add(self, model, radio_features, path_features, genomic_features, label, c, slot, device, flush):
+        """One patient (host or device tensors; label, c: device tensors) of loader slot `slot`."""
+        from .. import ops
+        has = lambda k: k in model.mode
+        xs_r = [radio_features[m] for m in model.modalities] if has("radio") else None
+        n_p = int(path_features.shape[0]) if has("path") else 0
+        n_r = int(xs_r[0].shape[0]) if has("radio") else 0
+        lim_p, lim_r = self.row_limits(model, int(path_features.shape[1]) if has("path") else None,
+                                       int(xs_r[0].shape[1]) if has("radio") else None)
+        if self.slots and (len(self.slots) >= ops.GROUP_MAX or has("path") and self.path.rows + n_p > lim_p
+                           or has("radio") and self.radio.rows + n_r > lim_r):
+            flush()
+        for k in ("radio", "path", "omic"):
+            if has(k):
+                self.seeds[k].append(ops.next_dropout_seed() if model.training else 0)
+        never = lambda: None                   # the flush above has made room in both planes
+        if has("radio"):
+            self.radio.add(xs_r, label, c, slot, lim_r, device, never)
+        if has("path"):
+            self.path.add([path_features], label, c, slot, lim_p, device, never)
+        if has("omic"):
+            x = genomic_features.reshape(-1)
+            if self.omic is None or self.omic.shape[1] != x.numel() or self.omic.device != label.device:
+                self.omic = torch.empty((ops.GROUP_MAX, x.numel()), dtype=torch.float32, device=label.device)
+            self.omic[len(self.slots)].copy_(x, non_blocking=True)
+        self.labels.append(label.reshape(1)); self.cs.append(c.reshape(1)); self.slots.append(slot)
+
+    def run(self, model, alpha, loss_scale):
+        """One grouped call over the held patients -> [(loader slot, loss [1], risk [1])]; the group is empty afterwards."""
+        if not self.slots:
+            return []
+        has = lambda k: k in model.mode
+        G = len(self.slots)
+        window = ((self.path.buf[0, :self.path.rows], list(self.path.sizes)) if has("path") else None,
+                  (self.radio.buf[:, :self.radio.rows], list(self.radio.sizes)) if has("radio") else None,
+                  self.omic[:G] if has("omic") else None)
+        seeds = {k: v for k, v in self.seeds.items() if has(k)} if model.training else None
+        _, _, _, _, loss, risk = model.nll_step_group(window, torch.cat(self.labels), torch.cat(self.cs), alpha=alpha,
+                                                      loss_scale=loss_scale, seeds=seeds)
+        out = [(slot, loss[g:g + 1], risk[g:g + 1]) for g, slot in enumerate(self.slots)]
+        self.reset()
+        return out
+
+
 def _window_of(model, optimizer, world, grad_buffer, inflight, device):
     key = (world, inflight, id(model))
     w = getattr(optimizer, "_mmf_window", None)
@@ -294,10 +368,11 @@ def _fused_radio_ok(model, loss_fn, feats, on_host=False):
     return all(p.requires_grad for p in model.parameters())
 
 
-def _fused_mm_ok(model, loss_fn, feats):
+def _fused_mm_ok(model, loss_fn, feats, on_host=False):
     """One patient = one fixed sequence of C-ABI calls without an autograd graph (model.nll_step of the multimodal concat
     head).  Only where that is exactly what `model(**feats)` + the stock loss would compute: MM_MIL_Attention_fc_surv ITSELF
-    (concat fusion, or the tensor fusion as the heads configure it), the stock NLLSurvLoss, no hooks, every parameter trainable, inputs on the GPU."""
+    (concat fusion, or the tensor fusion as the heads configure it), the stock NLLSurvLoss, no hooks, every parameter trainable, inputs on the GPU.
+    on_host: the inputs may still be on the host (group=True asks before the copy)."""
     from ..models.model_mm_attention_mil import MM_MIL_Attention_fc_surv
     import torch.nn.modules.module as tm
     if type(loss_fn) is not NLLSurvLoss or type(model).forward is not MM_MIL_Attention_fc_surv.forward:
@@ -316,7 +391,7 @@ def _fused_mm_ok(model, loss_fn, feats):
     if head.out_features > 32:
         return False
     for v in feats.values():
-        if not (torch.is_tensor(v) and v.is_cuda):
+        if not (torch.is_tensor(v) and (v.is_cuda or on_host)):
             return False
     hooked = lambda m: bool(m._forward_hooks or m._forward_pre_hooks or m._backward_hooks or getattr(m, "_backward_pre_hooks", None))
     if any(hooked(m) for m in model.modules()):
@@ -324,6 +399,27 @@ def _fused_mm_ok(model, loss_fn, feats):
     if tm._global_forward_hooks or tm._global_forward_pre_hooks or tm._global_backward_hooks or getattr(tm, "_global_backward_pre_hooks", None):
         return False
     return all(p.requires_grad for p in model.parameters())
+
+
+def _mm_group_ok(model, loss_fn, radio_features, path_features, genomic_features):
+    """A multimodal patient the window's grouped call takes (model.nll_step_group): what _fused_mm_ok allows (asked on the
+    tensors as the loader delivers them, host or device), the concat fusion, and for every branch in model.mode a 2-D fp32
+    bag (the modalities of one shape) or an omic vector of the model's input width."""
+    if getattr(model, "fusion", None) != "concat" or not hasattr(model, "nll_step_group"):
+        return False
+    feats = dict(radio_features, path_features=path_features, genomic_features=genomic_features)
+    if not _fused_mm_ok(model, loss_fn, feats, on_host=True):
+        return False
+    bag = lambda t: t.dim() == 2 and t.dtype == torch.float32 and t.shape[0] >= 1
+    if "path" in model.mode and not bag(path_features):
+        return False
+    if "radio" in model.mode:
+        xs = [radio_features.get(m) for m in model.modalities]
+        if any(x is None or not bag(x) or x.shape != xs[0].shape for x in xs):
+            return False
+    if "omic" in model.mode and genomic_features.numel() != model.fc_omic[0][0].in_features:
+        return False
+    return True
 
 
 def train_loop_survival(epoch, model, loader, optimizer, n_classes, mode, writer=None, loss_fn=None, reg_fn=None,
@@ -346,7 +442,9 @@ def train_loop_survival(epoch, model, loader, optimizer, n_classes, mode, writer
                 of the epoch; more than ops.GROUP_MAX bags or the row limit split it into several calls.  Each bag's
                 dropout seed is drawn when it arrives; a bag the grouped call does not take flushes the group and runs
                 alone.  Losses and risks are logged in loader order as before.  Not with inflight > 1 or dp on several
-                ranks."""
+                ranks.  The multimodal concat head's patients (those its one-call step takes, fp32 bags) are held in the same
+                way -- a pathology plane, the radio planes and the omic rows -- and run as ONE nll_step_group per window;
+                the tensor fusion keeps the per-patient route."""
     from ..feed import RankShard
     from .utils import l1_reg_all, l1_reg_modules
     device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
@@ -377,7 +475,8 @@ def train_loop_survival(epoch, model, loader, optimizer, n_classes, mode, writer
         from .. import ops
         held = getattr(win, "group", None)
         if held is None:
-            held = win.group = _BagGroup()
+            held = win.group = _MMGroup() if hasattr(model, "attention_net_radio") and hasattr(model, "attention_net_WSI") \
+                else _BagGroup()
         alpha_g = getattr(loss_fn, "alpha", 0.0)
 
         def flush():      # the held bags' losses / risks land in their loader slots
@@ -399,7 +498,10 @@ def train_loop_survival(epoch, model, loader, optimizer, n_classes, mode, writer
             # stands in while the route is decided).  A radiology bag is judged on its host tensors, before any copy.
             direct = group and torch.is_tensor(path_features) and not path_features.is_cuda
             grouped_radio = group and ops._gemm == 0 and _fused_radio_ok(model, loss_fn, radio_features, on_host=True)
-            feats, label, c = _to_device({k: r[:0] for k, r in radio_features.items()} if grouped_radio else radio_features,
+            grouped_mm = group and ops._gemm == 0 and isinstance(held, _MMGroup) \
+                and _mm_group_ok(model, loss_fn, radio_features, path_features, genomic_features)
+            feats, label, c = _to_device({k: r[:0] for k, r in radio_features.items()} if grouped_radio or grouped_mm
+                                         else radio_features,
                                          path_features[:0] if direct else path_features, genomic_features, label, c,
                                          device)
 
@@ -412,8 +514,8 @@ def train_loop_survival(epoch, model, loader, optimizer, n_classes, mode, writer
                 raise NotImplementedError(type(loss_fn))
 
             fused_step = _fused_step_ok(model, loss_fn, feats)
-            grouped = grouped_radio or (group and fused_step and feats["path_features"].dtype == torch.float32
-                                        and ops._gemm == 0)
+            grouped = grouped_radio or grouped_mm or (group and fused_step and feats["path_features"].dtype == torch.float32
+                                                      and ops._gemm == 0)
             if group and not grouped:
                 flush()                  # the bags held so far run first: the window keeps loader order
                 if direct:
@@ -422,7 +524,11 @@ def train_loop_survival(epoch, model, loader, optimizer, n_classes, mode, writer
             fused_mm = (not fused_step) and (not fused_cox) and pipe is None and _fused_mm_ok(model, loss_fn, feats)
             fused_radio = (not grouped) and (not fused_step) and (not fused_cox) and (not fused_mm) and pipe is None \
                 and _fused_radio_ok(model, loss_fn, feats)
-            if grouped:
+            if grouped_mm:
+                # the multimodal patient, held for the window's grouped call: host tensors go straight into their rows
+                held.add(model, radio_features, path_features, genomic_features, label, c, len(losses), device, flush)
+                loss = risk = None
+            elif grouped:
                 # held for the window's grouped call; its loss and risk fill these slots when the group runs
                 if grouped_radio:
                     xs = [radio_features[m] for m in model.modalities]

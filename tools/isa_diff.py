@@ -1,7 +1,7 @@
 """Compare the gfx950 assembly of two `build.py --keep-temps` builds kernel by kernel: which kernels of the first build
 are instruction for instruction the same in the second.  Labels, comments and the kernel's own (mangled) name are
 normalised; a kernel whose name gained a defaulted template argument (`..., false>` / `..., -1, false>`) is matched to
-its new name.  Metadata lines (.amdhsa_*) are reported separately from instructions.  --sgpr renames every SGPR
+its new name, and so is a kernel that became a template on one flag (`dense_fwd_kernel` -> `dense_fwd_kernel<false>`).  Metadata lines (.amdhsa_*) are reported separately from instructions.  --sgpr renames every SGPR
 (`s12`, `s[28:29]`) to one placeholder first: a change to a kernel's arguments renumbers the scalar registers of the
 whole kernel, and this leaves only the lines that changed otherwise.
 usage: isa_diff.py [--sgpr] OLD_BUILD_DIR NEW_BUILD_DIR [UNIT ...]   (units default: every unit of build.SOURCES)"""
@@ -36,7 +36,8 @@ def main():
         a, b = kernels(os.path.join(old, f), sgpr), kernels(os.path.join(new, f), sgpr)
         same = meta_only = 0
         for k, v in sorted(a.items()):
-            cands = [n for n in b if n == k or n.replace("Lb0EEEv", "EEv") == k or n.replace("ELb0EEEvNS", "EEvNS") == k]
+            cands = [n for n in b if n == k or n.replace("Lb0EEEv", "EEv") == k or n.replace("ELb0EEEvNS", "EEvNS") == k
+                     or n.replace("ILb0EEEvNS", "ENS") == k]
             if not cands:
                 print(f"{u}: {k}: not found in the new build")
                 continue

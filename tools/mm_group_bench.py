@@ -1,0 +1,85 @@
+"""The multimodal concat head's grouped training step (MM_MIL_Attention_fc_surv.nll_step_group; gated heads, train mode,
+radio_path_omic, omic width 80) against (b) the same patients one nll_step at a time and (c) the two single-head grouped
+steps over the same rows -- mmf_amil_nll_step_group on the pathology rows plus mmf_radio_nll_step_group on the radio rows,
+with the model's own stacks -- in one process.  Device-event timing, warm-up first, median of three runs.  One JSON line
+per window; the yardstick is 1.10 x (c) + 0.030 ms per window (0.015 ms for each thing (c) lacks: the omic branch and the
+fused head).
+usage: mm_group_bench.py [--grouped-only] [CASE ...]   CASE = PATH:RADIO, each comma-separated sizes or GxN,
+       e.g. 16x1000:16x64 (default: 16x1000:16x64 64x1000:64x150 4x10000:4x512 and a ragged 8-patient window);
+       env GROUP_BENCH_ITERS (default 20);  --grouped-only: time the grouped leg alone (for a kernel trace of it)"""
+import json, os, sys
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch
+from group_bench import RAGGED as RAGGED_PATH, parse, timed
+from radio_group_bench import MODS, RAGGED as RAGGED_RADIO
+from multimodalfusion_amd import ops
+from multimodalfusion_amd.models import MM_MIL_Attention_fc_surv
+from multimodalfusion_amd.models.model_modules import amil_stack_nll_step_group, stack_args, step_grad_buffers
+
+DEFAULT = [([1000] * 16, [64] * 16), ([1000] * 64, [150] * 64), ([10000] * 4, [512] * 4), (RAGGED_PATH, RAGGED_RADIO)]
+
+
+def main():
+    args = sys.argv[1:]
+    grouped_only = "--grouped-only" in args
+    cases = [tuple(parse(h) for h in a.split(":")) for a in args if a != "--grouped-only"] or DEFAULT
+    iters = int(os.environ.get("GROUP_BENCH_ITERS", "20"))
+    dev = torch.device("cuda", 0)
+    torch.manual_seed(0)
+    model = MM_MIL_Attention_fc_surv(input_dim=80, radio_fusion="concat", fusion="concat", gate=True, gate_path=True,
+                                     gate_omic=True, gate_radio=True, dropout=True, n_classes=4,
+                                     mode="radio_path_omic").to(dev).train()
+    # leg (c): each stack behind a classifier of its own width
+    cls_p = torch.nn.Linear(model.attention_net_WSI[0].out_features, 4).to(dev)
+    cls_r = torch.nn.Linear(model.attention_net_radio[0].out_features, 4).to(dev)
+    gen = torch.Generator(device=dev); gen.manual_seed(7)
+    for psizes, rsizes in cases:
+        G = len(psizes)
+        assert len(rsizes) == G
+        xp = torch.randn(sum(psizes), 1024, device=dev, generator=gen)
+        xr = torch.randn(len(MODS), sum(rsizes), 1024, device=dev, generator=gen)
+        xo = torch.randn(G, 80, device=dev, generator=gen)
+        rparts = [torch.split(xr[m], rsizes) for m in range(len(MODS))]
+        patients = [dict({m: rparts[j][g] for j, m in enumerate(MODS)}, path_features=p, genomic_features=xo[g])
+                    for g, p in enumerate(torch.split(xp, psizes))]
+        Y = torch.tensor([g % 4 for g in range(G)], device=dev)
+        c = torch.tensor([float(g % 2) for g in range(G)], device=dev)
+        window = ((xp, psizes), (xr, rsizes), xo)
+
+        def grouped():
+            model.nll_step_group(window, Y, c, loss_scale=1.0 / G)
+
+        def sequential():
+            for g in range(G):
+                model.nll_step(Y[g:g + 1], c[g:g + 1], loss_scale=1.0 / G, **patients[g])
+
+        def single_heads():
+            amil_stack_nll_step_group(model.attention_net_WSI, cls_p, (xp, psizes), True, Y, c, 0.0, 1.0 / G)
+            gated, stack, p_h, p_att = stack_args(model.attention_net_radio, True)
+            Wr, br = model.reduce_dim.weight, model.reduce_dim.bias
+            grads, acc = step_grad_buffers([Wr, br, *stack, cls_r.weight, cls_r.bias], dev, None, None)
+            with torch.no_grad():
+                ops.radio_nll_step_group(list(xr.unbind(0)), rsizes, Wr, br, stack, cls_r.weight, cls_r.bias, gated, Y, c,
+                                         0.0, grads, loss_scale=1.0 / G, accumulate=acc, p_h=p_h, p_att=p_att,
+                                         seeds=[ops.next_dropout_seed() for _ in rsizes])
+
+        t_g = timed(grouped, iters)
+        tag = {"patients": G, "path_rows": sum(psizes), "radio_rows": sum(rsizes)}
+        if grouped_only:
+            print(json.dumps(dict(tag, grouped_ms_window=round(t_g, 4), grouped_ms_per_patient=round(t_g / G, 4))), flush=True)
+            continue
+        t_s, t_c = timed(sequential, max(2, iters // 4)), timed(single_heads, iters)
+        print(json.dumps(dict(tag, path=psizes if len(set(psizes)) > 1 else f"{G}x{psizes[0]}",
+                              radio=rsizes if len(set(rsizes)) > 1 else f"{G}x{rsizes[0]}",
+                              grouped_ms_window=round(t_g, 4), grouped_ms_per_patient=round(t_g / G, 4),
+                              sequential_ms_window=round(t_s, 4), sequential_ms_per_patient=round(t_s / G, 4),
+                              single_heads_ms_window=round(t_c, 4), single_heads_ms_per_patient=round(t_c / G, 4),
+                              grouped_vs_sequential=round(t_g / t_s, 3), grouped_vs_single_heads=round(t_g / t_c, 3),
+                              beats_sequential=t_g < t_s, yardstick_ok=t_g <= 1.10 * t_c + 0.030)), flush=True)
+        for p in [*model.parameters(), *cls_p.parameters(), *cls_r.parameters()]:
+            p.grad = None
+
+
+if __name__ == "__main__":
+    main()
