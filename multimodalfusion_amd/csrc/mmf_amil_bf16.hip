@@ -302,69 +302,9 @@ int launch_gate_bf16(GateBfParams p, hipStream_t st) {
 // =============================================================================================
 // K-pool : scores + per-group online-softmax partials over the bf16 h
 // =============================================================================================
-constexpr int POOLB_MAX_ROWS = 8192;
+constexpr int POOLB_MAX_ROWS = POOL_MAX_ROWS;
 
-// (Its body has a copy, pool_partial_bf16_rows below, for the grouped forward-only pass: a fix here belongs there too.)
-__global__ __launch_bounds__(256) void pool_partial_bf16_kernel(PoolBfParams pb) {
-  __shared__ float s_lds[POOLB_MAX_ROWS];
-  __shared__ float red[256];
-  __shared__ __align__(16) float vred[2048];   // RG * VPR == 256 slots of 8 floats
-  const PoolParams& p = pb.base;
-  const int tid = threadIdx.x, g = blockIdx.x;
-  const int64_t r0 = (int64_t)g * p.rows_per_group;
-  const int64_t r1 = r0 + p.rows_per_group < p.N ? r0 + p.rows_per_group : p.N;
-  const int nrows = r1 > r0 ? (int)(r1 - r0) : 0;
-  const float bc = p.bc ? p.bc[0] : 0.f;
-
-  float lmax = -INFINITY;
-  for (int i = tid; i < nrows; i += 256) {
-    float s = bc;
-    for (int t = 0; t < p.n_parts; ++t) s += p.s_part[(size_t)t * p.N + r0 + i];
-    p.A_raw[r0 + i] = s;
-    s_lds[i] = s;
-    lmax = fmaxf(lmax, s);
-  }
-  lmax = wave_max(lmax);
-  if ((tid & 63) == 0) red[tid >> 6] = lmax;
-  __syncthreads();
-  const float m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-  __syncthreads();
-
-  const int VPR = p.H / 8;          // 16-byte vectors per row: 32 (H=256), 64 (H=512), 128 (H=1024)
-  const int RG = 256 / VPR;
-  const int cv = tid % VPR, rg = tid / VPR;
-  float v[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  float lsum = 0.f;
-  for (int i = rg; i < nrows; i += RG) {
-    const float e = __expf(s_lds[i] - m);
-    const float4 raw = ld4(reinterpret_cast<const float*>(pb.h + (size_t)(r0 + i) * p.H + 8 * cv));
-    float hv[8];
-    unpack8(raw, hv);
-#pragma unroll
-    for (int k = 0; k < 8; ++k) v[k] += e * hv[k];
-    if (cv == 0) lsum += e;
-  }
-#pragma unroll
-  for (int k = 0; k < 8; ++k) vred[(rg * VPR + cv) * 8 + k] = v[k];
-  if (cv == 0) red[rg] = lsum;
-  __syncthreads();
-  float* out = p.partials + (size_t)g * (2 + p.H);
-  for (int c = tid; c < p.H; c += 256) {
-    float s = 0.f;
-    for (int q = 0; q < RG; ++q) s += vred[q * p.H + c];      // slot (q, cv) covers columns 8cv .. 8cv+7
-    out[2 + c] = s;
-  }
-  if (tid == 0) {
-    float l = 0.f;
-    for (int q = 0; q < RG; ++q) l += red[q];
-    out[0] = nrows > 0 ? m : -INFINITY;
-    out[1] = l;
-  }
-}
-
-// pool_partial_bf16_kernel's body on rows r0 .. r1 - 1 -> A_raw of those rows and partials[g] = {max, sum e, sum e h}.
-// (A copy, kept in step with pool_partial_bf16_kernel by hand: run through a shared inline function, the one-bag kernel
-// came out with one instruction scheduled differently, and the one-bag kernels are kept instruction for instruction.)
+// one partial group: rows r0 .. r1 - 1 -> A_raw of those rows and partials[g] = {max, sum e, sum e h}
 __device__ __forceinline__ void pool_partial_bf16_rows(const PoolBfParams& pb, int g, int64_t r0, int64_t r1) {
   __shared__ float s_lds[POOLB_MAX_ROWS];
   __shared__ float red[256];
@@ -420,6 +360,14 @@ __device__ __forceinline__ void pool_partial_bf16_rows(const PoolBfParams& pb, i
   }
 }
 
+__global__ __launch_bounds__(256) void pool_partial_bf16_kernel(PoolBfParams pb) {
+  const PoolParams& p = pb.base;
+  const int g = blockIdx.x;
+  const int64_t r0 = (int64_t)g * p.rows_per_group;
+  const int64_t r1 = r0 + p.rows_per_group < p.N ? r0 + p.rows_per_group : p.N;
+  pool_partial_bf16_rows(pb, g, r0, r1);
+}
+
 // forward-only grouped pass (mmf_amil_infer_group): partial group b of the window holds the rows of one bag only
 __global__ __launch_bounds__(256) void group_pool_partial_bf16_kernel(PoolBfParams pb, SegTable s) {
   const int b = blockIdx.x;
@@ -432,9 +380,7 @@ __global__ __launch_bounds__(256) void group_pool_partial_bf16_kernel(PoolBfPara
 }
 
 int launch_group_pool_partial_bf16(PoolBfParams pb, const SegTable& s, hipStream_t st) {
-  const PoolParams& p = pb.base;
-  if (p.H != 256 && p.H != 512 && p.H != 1024) return MMF_ERR_SHAPE;
-  if (s.G < 1 || s.G > GROUP_MAX || s.rows_per_group < 1 || s.rows_per_group > POOLB_MAX_ROWS) return MMF_ERR_SHAPE;
+  if (int e = group_pool_check(pb.base, s)) return e;
   { ProfScope ps("group_pool_partial_bf16_kernel", st);
     hipLaunchKernelGGL(group_pool_partial_bf16_kernel, dim3(s.gbeg[s.G]), dim3(256), 0, st, pb, s); }
   return hipGetLastError() == hipSuccess ? MMF_OK : MMF_ERR_LAUNCH;

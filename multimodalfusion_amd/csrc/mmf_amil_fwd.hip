@@ -445,7 +445,6 @@ __device__ inline void gate_fwd_tile(const GateFwdParams& p, float* lds, int row
 // =============================================================================================
 // K-pool : scores + per-group online-softmax partials.  HBM-bound (reads h once).
 // =============================================================================================
-constexpr int POOL_MAX_ROWS = 8192;
 
 // one partial group: rows r0 .. r1 - 1 -> A_raw of those rows and partials[g] = {max, sum e, sum e h}
 __device__ __forceinline__ void pool_partial_rows(const PoolParams& p, int g, int64_t r0, int64_t r1) {
@@ -545,6 +544,9 @@ __device__ inline void tail_preload(const PoolParams& p, TailPre& r) {
   r.c = (tid == 0 && t.c) ? t.c[0] : 0.f;
   r.y = (tid == 0 && t.Y) ? (long long)t.Y[0] : 0;
 }
+// M_IN_LDS: the caller has merged the bag itself and left M in sm[0 .. H) (else M is read from p.M).  BWD = false is
+// the forward-only tail: logits, hazards, S, Y_hat, risk and -- when Y is given -- the loss value, no dz / dM / dWk / dbk.
+template <bool M_IN_LDS, bool BWD = true>
 __device__ inline void head_tail(const PoolParams& p, const TailPre& r, float* sm /* 1024 + 160 floats */) {
   const HeadTail& t = p.tail;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -552,7 +554,7 @@ __device__ inline void head_tail(const PoolParams& p, const TailPre& r, float* s
   float* Ml = sm;                 // [H]
   float* z = sm + 1024;           // [K] logits, then dz
   float *hz = z + 32, *S = z + 64, *gH = z + 96, *gS = z + 128;   // K <= 32; in LDS: indexed arrays in registers would go to scratch
-  if (!p.merge_in_tail)           // M comes from the K-merge launch in front (else the caller has filled Ml)
+  if constexpr (!M_IN_LDS)        // M comes from the launch in front
     for (int c = tid; c < H; c += 1024) Ml[c] = p.M[c];
   __syncthreads();
   if (wave < K) {
@@ -587,7 +589,8 @@ __device__ inline void head_tail(const PoolParams& p, const TailPre& r, float* s
     if (t.risk) t.risk[0] = -ssum;
     if (t.Y) {
       // ... nll_surv for the one sample (nll_surv_kernel) ...
-      for (int k = 0; k < K; ++k) { gH[k] = 0.f; gS[k] = 0.f; }
+      if constexpr (BWD)
+        for (int k = 0; k < K; ++k) { gH[k] = 0.f; gS[k] = 0.f; }
       const long long y64 = r.y;
       float l;
       if (y64 < 0 || y64 >= K) {
@@ -598,28 +601,31 @@ __device__ inline void head_tail(const PoolParams& p, const TailPre& r, float* s
         const float sp_y = y == 0 ? 1.0f : S[y - 1];
         const float hy = hz[y];
         const float unc = -(1.f - c) * (logf(fmaxf(sp_y, t.eps)) + logf(fmaxf(hy, t.eps)));
-        if (y > 0 && sp_y >= t.eps) gS[y - 1] += -(1.f - c) / sp_y;
-        if (hy >= t.eps) gH[y] += -(1.f - c) / hy;
         const float sp_y1 = S[y];
         const float cen = -c * logf(fmaxf(sp_y1, t.eps));
-        if (sp_y1 >= t.eps) gS[y] += -(1.f - t.alpha) * c / sp_y1;
+        if constexpr (BWD) {
+          if (y > 0 && sp_y >= t.eps) gS[y - 1] += -(1.f - c) / sp_y;
+          if (hy >= t.eps) gH[y] += -(1.f - c) / hy;
+          if (sp_y1 >= t.eps) gS[y] += -(1.f - t.alpha) * c / sp_y1;
+        }
         l = (1.f - t.alpha) * (cen + unc) + t.alpha * unc;
       }
       t.loss[0] = l;
       // ... and the head's backward (surv_head_bwd_kernel): dz_t = (gH_t - sum_{j>=t} gS_j prod_{u<=j,u!=t}(1-h_u)) h_t (1-h_t)
-      for (int k = 0; k < K; ++k) {
-        float g = gH[k];
-        for (int j = k; j < K; ++j) {
-          float prod = 1.f;
-          for (int u = 0; u <= j; ++u)
-            if (u != k) prod *= (1.0f - hz[u]);
-          g -= gS[j] * prod;
+      if constexpr (BWD)
+        for (int k = 0; k < K; ++k) {
+          float g = gH[k];
+          for (int j = k; j < K; ++j) {
+            float prod = 1.f;
+            for (int u = 0; u <= j; ++u)
+              if (u != k) prod *= (1.0f - hz[u]);
+            g -= gS[j] * prod;
+          }
+          z[k] = g * hz[k] * (1.0f - hz[k]) * t.loss_scale;
         }
-        z[k] = g * hz[k] * (1.0f - hz[k]) * t.loss_scale;
-      }
     }
   }
-  if (!t.Y) return;
+  if (!BWD || !t.Y) return;
   __syncthreads();
   for (int c = tid; c < H; c += 1024) {
     float acc = 0.f;
@@ -641,7 +647,9 @@ __device__ inline void head_tail(const PoolParams& p, const TailPre& r, float* s
   if (tid < K) t.dbk[tid] = t.accumulate ? t.dbk[tid] + z[tid] : z[tid];
 }
 
-// H/32 workgroups of 1024 threads: merge the per-group partials.
+// H/32 workgroups of 1024 threads: merge the per-group partials.  The grouped routes merge one
+// bag per workgroup instead (bag_merge below) and share this kernel's order of additions: the one-bag and the grouped
+// forward-only passes agree to the bit (tests/test_gpu_pool_tails.py).
 // Group weights exp(m_g - m) are computed once into LDS; the column sums then run as independent, unrolled
 // loads (the first version's serial dependent loop over groups cost 115 us).
 constexpr int MERGE_MAX_GROUPS = 4096;
@@ -696,45 +704,14 @@ __global__ __launch_bounds__(1024) void pool_merge_kernel(PoolParams p) {
   if (blockIdx.x == 0 && tid == 0) { p.stats[0] = m; p.stats[1] = l; }
 }
 
-// The head tail as its own single-workgroup launch behind K-merge (HeadTail).  It can also merge up to TAIL_MERGE_MAX
-// partials itself (thread c sums column c over the groups: one launch less) -- off by default, see launch_pool_merge.
+// The head tail as its own single-workgroup launch behind K-merge (HeadTail).
 // (First version: tail run by the LAST workgroup of K-merge, found with a ticket counter -- the fences, the atomic and
 // the re-read of M through L2 cost 12 us, more than the 5 us of this launch.)
-constexpr int TAIL_MERGE_MAX = 64;
 __global__ __launch_bounds__(1024) void head_tail_kernel(PoolParams p) {
   __shared__ float tail_sm[1024 + 160];
-  __shared__ float wl[TAIL_MERGE_MAX];
-  __shared__ float ml[2];
   TailPre pre;
   tail_preload(p, pre);
-  const int tid = threadIdx.x;
-  if (p.merge_in_tail) {
-    const int stride = 2 + p.H;
-    if (tid < 64) {                                   // one wave: group maxima, weights exp(m_g - m), denominator
-      const float mg = tid < p.n_groups ? p.partials[(size_t)tid * stride] : -INFINITY;
-      const float m = wave_max(mg);
-      const float w = mg > -INFINITY ? __expf(mg - m) : 0.f;
-      const float l = wave_sum(tid < p.n_groups ? p.partials[(size_t)tid * stride + 1] * w : 0.f);
-      wl[tid] = w;
-      if (tid == 0) { ml[0] = m; ml[1] = l; p.stats[0] = m; p.stats[1] = l; }
-    }
-    __syncthreads();
-    if (tid < p.H) {
-      // the same order of additions as pool_merge_kernel (32 interleaved group slices, then the slices in order): the
-      // forward-only path merges there, and the two must agree to the bit (tests/test_gpu_infer.py)
-      const float* q = p.partials + 2 + tid;
-      float acc = 0.f;
-      for (int sl = 0; sl < 32; ++sl) {
-        float a = 0.f;
-        for (int g = sl; g < p.n_groups; g += 32) a += q[(size_t)g * stride] * wl[g];
-        acc += a;
-      }
-      const float mv = acc / ml[1];
-      p.M[tid] = mv;
-      tail_sm[tid] = mv;
-    }
-  }
-  head_tail(p, pre, tail_sm);
+  head_tail<false>(p, pre, tail_sm);
 }
 
 // A[i] = sum_t s_part[t][i] + bc : the scores alone (standalone Attn_Net / Attn_Net_Gated forward, no pooling)
@@ -1041,12 +1018,10 @@ int launch_pool(PoolParams p, hipStream_t st) {
 int launch_pool_merge(PoolParams p, hipStream_t st) {
   if (p.n_groups < 1 || p.n_groups > MERGE_MAX_GROUPS || p.H > 1024 || p.H % 32 != 0) return MMF_ERR_SHAPE;
   if (p.tail.Wk && (p.tail.K < 1 || p.tail.K > 32)) return MMF_ERR_SHAPE;
-  // Merging inside the single-workgroup tail kernel saves a launch and loses more than that: measured, one bag per
-  // step, separate merge vs merge in the tail: 1k 0.0995 vs 0.1016 ms, 2k 0.1085 vs 0.1146, 4,096 (64 groups) 0.1236 vs
-  // 0.1370.  Off by default; MMF_TAIL_MERGE=<max groups, <= 64> turns it back on.
-  static const int tail_merge = tune_int("MMF_TAIL_MERGE", 0);
-  p.merge_in_tail = p.tail.Wk && p.n_groups <= (tail_merge < TAIL_MERGE_MAX ? tail_merge : TAIL_MERGE_MAX) ? 1 : 0;
-  if (!p.merge_in_tail) {
+  // Always a merge launch of its own.  Letting the single-workgroup tail kernel merge a bag of <= 64 partials saved a
+  // launch and lost more than that: measured, one bag per step, separate merge vs merge in the tail: 1k 0.0995 vs
+  // 0.1016 ms, 2k 0.1085 vs 0.1146, 4,096 (64 groups) 0.1236 vs 0.1370.
+  {
     ProfScope ps("pool_merge_kernel", st);
     hipLaunchKernelGGL(pool_merge_kernel, dim3(p.H / 32), dim3(1024), 0, st, p);
   }
@@ -1061,7 +1036,6 @@ int launch_pool_merge(PoolParams p, hipStream_t st) {
 // side by side): classifier, hazards, nll_surv and its backward down to d(feature), one single-workgroup launch.
 int launch_head_tail(PoolParams p, hipStream_t st) {
   if (!p.M || !p.tail.Wk || p.H < 1 || p.H > 1024 || p.tail.K < 1 || p.tail.K > 32) return MMF_ERR_SHAPE;
-  p.merge_in_tail = 0;
   ProfScope ps("head_tail_kernel", st);
   hipLaunchKernelGGL(head_tail_kernel, dim3(1), dim3(1024), 0, st, p);
   return hipGetLastError() == hipSuccess ? MMF_OK : MMF_ERR_LAUNCH;
@@ -1112,125 +1086,126 @@ __global__ __launch_bounds__(256) void group_pool_partial_kernel(PoolParams p, S
 }
 
 constexpr int GROUP_BAG_MAX_PARTIALS = GROUP_POOL_GROUPS + 64;
+
+// One bag's merge on one 1024-thread workgroup: the n partials at `part` -> m, l (every thread) and, returned, column
+// tid of M (threads tid < H; 0 on the others).  wl [GROUP_BAG_MAX_PARTIALS] and red [32] are the caller's LDS.  The
+// column sums take pool_merge_kernel's order: 32 interleaved slices, then the slices in order.
+__device__ __forceinline__ float bag_merge(const float* part, int n, int H, float* wl, float* red, float& m, float& l) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int stride = 2 + H;
+  m = -INFINITY;
+  for (int i = tid; i < n; i += 1024) m = fmaxf(m, part[(size_t)i * stride]);
+  m = wave_max(m);
+  if (lane == 0) red[wave] = m;
+  __syncthreads();
+  m = red[0];
+#pragma unroll
+  for (int i = 1; i < 16; ++i) m = fmaxf(m, red[i]);
+  l = 0.f;
+  for (int i = tid; i < n; i += 1024) {
+    const float mg = part[(size_t)i * stride];
+    const float w = mg > -INFINITY ? __expf(mg - m) : 0.f;
+    wl[i] = w;
+    l += part[(size_t)i * stride + 1] * w;
+  }
+  l = wave_sum(l);
+  if (lane == 0) red[16 + wave] = l;
+  __syncthreads();
+  l = 0.f;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) l += red[16 + i];
+  float mv = 0.f;
+  if (tid < H) {
+    const float* col = part + 2 + tid;
+    float acc = 0.f;
+    for (int sl = 0; sl < 32; ++sl) {
+      float a = 0.f;
+      for (int i = sl; i < n; i += 32) a += col[(size_t)i * stride] * wl[i];
+      acc += a;
+    }
+    mv = acc / l;
+  }
+  return mv;
+}
+
+// Bag g's slice of every per-bag array of a window's PoolParams / HeadTail; ldm is the row stride of M (H, or the
+// width of a wider feature matrix).  Optional pointers that are null stay null; the gradient slabs are per bag, so
+// accumulate is off (the reduce launch behind sums them over the bags).
+__device__ __forceinline__ PoolParams bag_slice(const PoolParams& p, int g, int ldm) {
+  PoolParams q = p;
+  const int H = p.H, K = p.tail.K;
+  if (q.M) q.M += (size_t)g * ldm;
+  if (q.stats) q.stats += 2 * g;
+  HeadTail& t = q.tail;
+  t.logits += (size_t)g * K; t.hazards += (size_t)g * K; t.S += (size_t)g * K; t.Y_hat += g;
+  if (t.risk) t.risk += g;
+  if (t.Y) t.Y += g;
+  if (t.c) t.c += g;
+  if (t.loss) t.loss += g;
+  if (t.dM) t.dM += (size_t)g * H;
+  if (t.dWk) t.dWk += (size_t)g * K * H;
+  if (t.dbk) t.dbk += (size_t)g * K;
+  t.accumulate = 0;
+  return q;
+}
+
 // one workgroup per bag: merge the bag's partials (M_g, stats_g), then the head tail of that bag
 __global__ __launch_bounds__(1024) void group_tail_kernel(PoolParams p, SegTable s) {
   __shared__ float tail_sm[1024 + 160];
   __shared__ float wl[GROUP_BAG_MAX_PARTIALS];
   __shared__ float red[32];
-  const int g = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int gb = s.gbeg[g], n = s.gbeg[g + 1] - gb, H = p.H, K = p.tail.K;
-  PoolParams q = p;                        // this bag's slice of every per-bag array
-  q.M = p.M + (size_t)g * H;
-  q.stats = p.stats + 2 * g;
-  q.merge_in_tail = 1;
-  HeadTail& t = q.tail;
-  t.logits += (size_t)g * K; t.hazards += (size_t)g * K; t.S += (size_t)g * K; t.Y_hat += g;
-  if (t.risk) t.risk += g;
-  t.Y += g; t.c += g; t.loss += g;
-  t.dM += (size_t)g * H;
-  t.dWk += (size_t)g * K * H; t.dbk += (size_t)g * K;
-  t.accumulate = 0;                        // per-bag slabs; the reduce launch sums them over the bags
+  const int g = blockIdx.x, tid = threadIdx.x;
+  const int gb = s.gbeg[g], n = s.gbeg[g + 1] - gb, H = p.H;
+  const PoolParams q = bag_slice(p, g, H);
   TailPre pre;
   tail_preload(q, pre);
-  const int stride = 2 + H;
-  const float* part = p.partials + (size_t)gb * stride;
-  float m = -INFINITY;
-  for (int i = tid; i < n; i += 1024) m = fmaxf(m, part[(size_t)i * stride]);
-  m = wave_max(m);
-  if (lane == 0) red[wave] = m;
-  __syncthreads();
-  m = red[0];
-#pragma unroll
-  for (int i = 1; i < 16; ++i) m = fmaxf(m, red[i]);
-  float l = 0.f;
-  for (int i = tid; i < n; i += 1024) {
-    const float mg = part[(size_t)i * stride];
-    const float w = mg > -INFINITY ? __expf(mg - m) : 0.f;
-    wl[i] = w;
-    l += part[(size_t)i * stride + 1] * w;
-  }
-  l = wave_sum(l);
-  if (lane == 0) red[16 + wave] = l;
-  __syncthreads();
-  l = 0.f;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) l += red[16 + i];
-  if (tid < H) {                           // pool_merge_kernel's order: 32 interleaved slices, then the slices in order
-    const float* col = part + 2 + tid;
-    float acc = 0.f;
-    for (int sl = 0; sl < 32; ++sl) {
-      float a = 0.f;
-      for (int i = sl; i < n; i += 32) a += col[(size_t)i * stride] * wl[i];
-      acc += a;
-    }
-    const float mv = acc / l;
+  float m, l;
+  const float mv = bag_merge(p.partials + (size_t)gb * (2 + H), n, H, wl, red, m, l);
+  if (tid < H) {
     q.M[tid] = mv;
     tail_sm[tid] = mv;
   }
   if (tid == 0) { q.stats[0] = m; q.stats[1] = l; }
-  head_tail(q, pre, tail_sm);
+  head_tail<true>(q, pre, tail_sm);
+}
+
+// What every pooling launch over a window checks: H of the pooling kernels, the window's size, the rows of a partial
+// group, and no bag with more partials than one workgroup merges.
+int group_pool_check(const PoolParams& p, const SegTable& s) {
+  if (p.H != 256 && p.H != 512 && p.H != 1024) return MMF_ERR_SHAPE;
+  if (s.G < 1 || s.G > GROUP_MAX || s.rows_per_group < 1 || s.rows_per_group > POOL_MAX_ROWS) return MMF_ERR_SHAPE;
+  for (int g = 0; g < s.G; ++g)
+    if (s.gbeg[g + 1] - s.gbeg[g] > GROUP_BAG_MAX_PARTIALS) return MMF_ERR_SHAPE;
+  return MMF_OK;
+}
+
+int launch_group_pool_partial(PoolParams p, const SegTable& s, hipStream_t st) {
+  if (int e = group_pool_check(p, s)) return e;
+  ProfScope ps("group_pool_partial_kernel", st);
+  hipLaunchKernelGGL(group_pool_partial_kernel, dim3(s.gbeg[s.G]), dim3(256), 0, st, p, s);
+  return hipGetLastError() == hipSuccess ? MMF_OK : MMF_ERR_LAUNCH;
 }
 
 int launch_group_pool(PoolParams p, const SegTable& s, hipStream_t st) {
-  if (p.H != 256 && p.H != 512 && p.H != 1024) return MMF_ERR_SHAPE;
-  if (!p.tail.Wk || p.tail.K < 1 || p.tail.K > 32 || s.G < 1 || s.G > GROUP_MAX) return MMF_ERR_SHAPE;
-  if (s.rows_per_group < 1 || s.rows_per_group > POOL_MAX_ROWS) return MMF_ERR_SHAPE;
-  for (int g = 0; g < s.G; ++g)
-    if (s.gbeg[g + 1] - s.gbeg[g] > GROUP_BAG_MAX_PARTIALS) return MMF_ERR_SHAPE;
-  {
-    ProfScope ps("group_pool_partial_kernel", st);
-    hipLaunchKernelGGL(group_pool_partial_kernel, dim3(s.gbeg[s.G]), dim3(256), 0, st, p, s);
-  }
-  {
-    ProfScope ps("group_tail_kernel", st);
-    hipLaunchKernelGGL(group_tail_kernel, dim3(s.G), dim3(1024), 0, st, p, s);
-  }
+  if (!p.tail.Wk || p.tail.K < 1 || p.tail.K > 32) return MMF_ERR_SHAPE;
+  if (int e = launch_group_pool_partial(p, s, st)) return e;
+  ProfScope ps("group_tail_kernel", st);
+  hipLaunchKernelGGL(group_tail_kernel, dim3(s.G), dim3(1024), 0, st, p, s);
   return hipGetLastError() == hipSuccess ? MMF_OK : MMF_ERR_LAUNCH;
 }
 
 // ---- grouped multimodal step (mmf_amil_group_forward / _backward, mmf_surv_head_nll_step_group) ---------------------
-// One workgroup per bag: group_tail_kernel's merge without the head tail behind it -- the same partials, the same weights
-// in LDS, the same order of additions.  The body is a copy, as group_infer_tail_kernel's is, so that those two kernels
-// stay instruction for instruction what they were; a change to one of the three goes into the others.  M_g goes
-// to the caller's M + g * ldm -- a stack writes straight into its columns of the window's [G x F] feature matrix -- and,
-// with stats_g, to the workspace (Mw [G x H], p.stats [G x 2]), where the backward half reads them.
+// One workgroup per bag: group_tail_kernel's merge (bag_merge) without the head tail behind it.  M_g goes to the caller's
+// M + g * ldm -- a stack writes straight into its columns of the window's [G x F] feature matrix -- and, with stats_g,
+// to the workspace (Mw [G x H], p.stats [G x 2]), where the backward half reads them.
 __global__ __launch_bounds__(1024) void group_merge_kernel(PoolParams p, SegTable s, int ldm, float* Mw) {
   __shared__ float wl[GROUP_BAG_MAX_PARTIALS];
   __shared__ float red[32];
-  const int g = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int g = blockIdx.x, tid = threadIdx.x;
   const int gb = s.gbeg[g], n = s.gbeg[g + 1] - gb, H = p.H;
-  const int stride = 2 + H;
-  const float* part = p.partials + (size_t)gb * stride;
-  float m = -INFINITY;
-  for (int i = tid; i < n; i += 1024) m = fmaxf(m, part[(size_t)i * stride]);
-  m = wave_max(m);
-  if (lane == 0) red[wave] = m;
-  __syncthreads();
-  m = red[0];
-#pragma unroll
-  for (int i = 1; i < 16; ++i) m = fmaxf(m, red[i]);
-  float l = 0.f;
-  for (int i = tid; i < n; i += 1024) {
-    const float mg = part[(size_t)i * stride];
-    const float w = mg > -INFINITY ? __expf(mg - m) : 0.f;
-    wl[i] = w;
-    l += part[(size_t)i * stride + 1] * w;
-  }
-  l = wave_sum(l);
-  if (lane == 0) red[16 + wave] = l;
-  __syncthreads();
-  l = 0.f;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) l += red[16 + i];
-  if (tid < H) {                           // pool_merge_kernel's order: 32 interleaved slices, then the slices in order
-    const float* col = part + 2 + tid;
-    float acc = 0.f;
-    for (int sl = 0; sl < 32; ++sl) {
-      float a = 0.f;
-      for (int i = sl; i < n; i += 32) a += col[(size_t)i * stride] * wl[i];
-      acc += a;
-    }
-    const float mv = acc / l;
+  float m, l;
+  const float mv = bag_merge(p.partials + (size_t)gb * (2 + H), n, H, wl, red, m, l);
+  if (tid < H) {
     p.M[(size_t)g * ldm + tid] = mv;
     Mw[(size_t)g * H + tid] = mv;
   }
@@ -1238,10 +1213,8 @@ __global__ __launch_bounds__(1024) void group_merge_kernel(PoolParams p, SegTabl
 }
 
 int launch_group_merge(PoolParams p, const SegTable& s, int ldm, float* Mw, hipStream_t st) {
-  if (p.H != 256 && p.H != 512 && p.H != 1024) return MMF_ERR_SHAPE;
-  if (s.G < 1 || s.G > GROUP_MAX || ldm < p.H || !p.M || !Mw || !p.stats) return MMF_ERR_SHAPE;
-  for (int g = 0; g < s.G; ++g)
-    if (s.gbeg[g + 1] - s.gbeg[g] > GROUP_BAG_MAX_PARTIALS) return MMF_ERR_SHAPE;
+  if (int e = group_pool_check(p, s)) return e;
+  if (ldm < p.H || !p.M || !Mw || !p.stats) return MMF_ERR_SHAPE;
   ProfScope ps("group_merge_kernel", st);
   hipLaunchKernelGGL(group_merge_kernel, dim3(s.G), dim3(1024), 0, st, p, s, ldm, Mw);
   return hipGetLastError() == hipSuccess ? MMF_OK : MMF_ERR_LAUNCH;
@@ -1268,20 +1241,10 @@ int launch_group_dm_gather(const float* src, int ld, float* dst, int G, int H, h
 // [G x K] (dbk_g = dlogits_g), overwritten: the reduce launch behind sums them in patient order.
 __global__ __launch_bounds__(1024) void surv_head_group_kernel(PoolParams p, int ldf) {
   __shared__ float tail_sm[1024 + 160];
-  const int g = blockIdx.x, F = p.H, K = p.tail.K;
-  PoolParams q = p;
-  q.M = p.M + (size_t)g * ldf;
-  q.merge_in_tail = 0;
-  HeadTail& t = q.tail;
-  t.logits += (size_t)g * K; t.hazards += (size_t)g * K; t.S += (size_t)g * K; t.Y_hat += g;
-  if (t.risk) t.risk += g;
-  t.Y += g; t.c += g; t.loss += g;
-  t.dM += (size_t)g * F;
-  t.dWk += (size_t)g * K * F; t.dbk += (size_t)g * K;
-  t.accumulate = 0;
+  const PoolParams q = bag_slice(p, blockIdx.x, ldf);
   TailPre pre;
   tail_preload(q, pre);
-  head_tail(q, pre, tail_sm);
+  head_tail<false>(q, pre, tail_sm);
 }
 
 int launch_surv_head_group(PoolParams p, int ldf, int G, hipStream_t st) {
@@ -1293,107 +1256,31 @@ int launch_surv_head_group(PoolParams p, int ldf, int G, hipStream_t st) {
 }
 
 // ---- forward-only grouped pass (mmf_amil_infer_group) ----------------------------------------------------------------
-// One workgroup per bag: merge the bag's partials into M_g (written when p.M is given), then the classifier, hazards, S,
-// Y_hat, risk and -- when labels are given -- the bag's nll_surv value.  No dM, no classifier gradient.  The merge is
-// group_tail_kernel's: the same partials (group_plan: at most GROUP_BAG_MAX_PARTIALS per bag), the same weights in LDS,
-// the same order of additions.
+// One workgroup per bag: group_tail_kernel with the forward-only head tail -- merge the bag's partials into M_g (written
+// when p.M is given), then the classifier, hazards, S, Y_hat, risk and -- when labels are given -- the bag's nll_surv
+// value.  No dM, no classifier gradient.  Without a head (p.tail.Wk null) it is the merge alone.
 __global__ __launch_bounds__(1024) void group_infer_tail_kernel(PoolParams p, SegTable s) {
-  __shared__ float Ml[1024];
+  __shared__ float tail_sm[1024 + 160];
   __shared__ float wl[GROUP_BAG_MAX_PARTIALS];
-  __shared__ float z[32], hz[32], Sv[32];
   __shared__ float red[32];
-  const int g = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int g = blockIdx.x, tid = threadIdx.x;
   const int gb = s.gbeg[g], n = s.gbeg[g + 1] - gb, H = p.H;
-  const HeadTail& t = p.tail;
-  const int K = t.K;
-  const int stride = 2 + H;
-  const float* part = p.partials + (size_t)gb * stride;
-  float m = -INFINITY;
-  for (int i = tid; i < n; i += 1024) m = fmaxf(m, part[(size_t)i * stride]);
-  m = wave_max(m);
-  if (lane == 0) red[wave] = m;
-  __syncthreads();
-  m = red[0];
-#pragma unroll
-  for (int i = 1; i < 16; ++i) m = fmaxf(m, red[i]);
-  float l = 0.f;
-  for (int i = tid; i < n; i += 1024) {
-    const float mg = part[(size_t)i * stride];
-    const float w = mg > -INFINITY ? __expf(mg - m) : 0.f;
-    wl[i] = w;
-    l += part[(size_t)i * stride + 1] * w;
+  const PoolParams q = bag_slice(p, g, H);
+  TailPre pre;
+  if (q.tail.Wk) tail_preload(q, pre);
+  float m, l;
+  const float mv = bag_merge(p.partials + (size_t)gb * (2 + H), n, H, wl, red, m, l);
+  if (tid < H) {
+    if (q.M) q.M[tid] = mv;
+    tail_sm[tid] = mv;
   }
-  l = wave_sum(l);
-  if (lane == 0) red[16 + wave] = l;
-  __syncthreads();
-  l = 0.f;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) l += red[16 + i];
-  if (tid < H) {                           // pool_merge_kernel's order: 32 interleaved slices, then the slices in order
-    const float* col = part + 2 + tid;
-    float acc = 0.f;
-    for (int sl = 0; sl < 32; ++sl) {
-      float a = 0.f;
-      for (int i = sl; i < n; i += 32) a += col[(size_t)i * stride] * wl[i];
-      acc += a;
-    }
-    const float mv = acc / l;
-    if (p.M) p.M[(size_t)g * H + tid] = mv;
-    Ml[tid] = mv;
-  }
-  if (!t.Wk) return;
-  __syncthreads();
-  for (int k = wave; k < K; k += 16) {               // logit k on wave k % 16
-    float acc = 0.f;
-    for (int c = lane; c < H; c += 64) acc += Ml[c] * t.Wk[(size_t)k * H + c];
-    acc = wave_sum(acc);
-    if (lane == 0) z[k] = acc + t.bk[k];
-  }
-  __syncthreads();
-  if (tid != 0) return;
-  float run = 1.f, best = -INFINITY, ssum = 0.f;
-  int arg = 0;
-  for (int k = 0; k < K; ++k) {                      // head_tail's forward, into bag g's rows
-    const float zz = z[k];
-    hz[k] = 1.0f / (1.0f + expf(-zz));
-    run *= (1.0f - hz[k]);
-    Sv[k] = run;
-    ssum += run;
-    t.logits[(size_t)g * K + k] = zz; t.hazards[(size_t)g * K + k] = hz[k]; t.S[(size_t)g * K + k] = run;
-    if (zz > best) { best = zz; arg = k; }
-  }
-  t.Y_hat[g] = arg;
-  if (t.risk) t.risk[g] = -ssum;
-  if (!t.Y) return;
-  const long long y64 = (long long)t.Y[g];
-  float loss;
-  if (y64 < 0 || y64 >= K) {                         // as head_tail: an out-of-range label poisons the value only
-    loss = __builtin_nanf("");
-  } else {
-    const int y = (int)y64;
-    const float c = t.c[g];
-    const float sp_y = y == 0 ? 1.0f : Sv[y - 1];
-    const float unc = -(1.f - c) * (logf(fmaxf(sp_y, t.eps)) + logf(fmaxf(hz[y], t.eps)));
-    const float cen = -c * logf(fmaxf(Sv[y], t.eps));
-    loss = (1.f - t.alpha) * (cen + unc) + t.alpha * unc;
-  }
-  t.loss[g] = loss;
-}
-
-int launch_group_pool_partial(PoolParams p, const SegTable& s, hipStream_t st) {
-  if (p.H != 256 && p.H != 512 && p.H != 1024) return MMF_ERR_SHAPE;
-  if (s.G < 1 || s.G > GROUP_MAX || s.rows_per_group < 1 || s.rows_per_group > POOL_MAX_ROWS) return MMF_ERR_SHAPE;
-  ProfScope ps("group_pool_partial_kernel", st);
-  hipLaunchKernelGGL(group_pool_partial_kernel, dim3(s.gbeg[s.G]), dim3(256), 0, st, p, s);
-  return hipGetLastError() == hipSuccess ? MMF_OK : MMF_ERR_LAUNCH;
+  if (!q.tail.Wk) return;
+  head_tail<true, false>(q, pre, tail_sm);
 }
 
 int launch_group_infer_tail(PoolParams p, const SegTable& s, hipStream_t st) {
-  if (p.H != 256 && p.H != 512 && p.H != 1024) return MMF_ERR_SHAPE;
-  if (s.G < 1 || s.G > GROUP_MAX) return MMF_ERR_SHAPE;
+  if (int e = group_pool_check(p, s)) return e;
   if (p.tail.Wk && (p.tail.K < 1 || p.tail.K > 32)) return MMF_ERR_SHAPE;
-  for (int g = 0; g < s.G; ++g)
-    if (s.gbeg[g + 1] - s.gbeg[g] > GROUP_BAG_MAX_PARTIALS) return MMF_ERR_SHAPE;
   ProfScope ps("group_infer_tail_kernel", st);
   hipLaunchKernelGGL(group_infer_tail_kernel, dim3(s.G), dim3(1024), 0, st, p, s);
   return hipGetLastError() == hipSuccess ? MMF_OK : MMF_ERR_LAUNCH;

@@ -71,7 +71,7 @@ struct GateFwdParams {
   const uint32_t* seg_ridx;     // grouped step: [N] dropout index base per row (width D), or null (LinearParams::seg_ridx)
 };
 
-// Optional tail behind K-merge, ONE single-workgroup launch (head_tail_kernel; for small bags it does the merge too):
+// Optional tail behind K-merge, ONE single-workgroup launch (head_tail_kernel):
 // the classifier + hazard head of models/model_attention_mil_path.py:58-61 and, when Y is given, nll_surv
 // (utils/loss_utils.py:22-39) with its backward down to dM -- instead of the three launches surv_head_fwd, nll_surv,
 // surv_head_bwd, each ~5 us of pure launch latency.
@@ -103,8 +103,8 @@ struct PoolParams {
   float* stats;            // {max, denom}
   int n_groups, rows_per_group;
   HeadTail tail;
-  int merge_in_tail;       // set by launch_pool_merge: the tail launch merges the (few) partials itself
 };
+constexpr int POOL_MAX_ROWS = 8192;   // rows of one pooling partial group (its scores stay in LDS)
 
 struct BwdPrepParams {     // ds_i = p_i (dM.h_i - dM.M) + gA_i
   const float* h;
@@ -286,9 +286,12 @@ int launch_group_rows(const GroupRowsParams& p, hipStream_t st);
 int launch_group_pool(PoolParams p, const SegTable& s, hipStream_t st);
 // ds_i / p_i with the statistics, M and dM of row i's bag
 int launch_group_bwd_prep(BwdPrepParams p, const int* bag, hipStream_t st);
+// every pooling launch over a window checks it with this: H, G, rows per partial group, partials per bag
+int group_pool_check(const PoolParams& p, const SegTable& s);
 // forward-only grouped pass (mmf_amil_infer_group): the pooling partials of launch_group_pool alone, and a tail of one
 // workgroup per bag that merges the bag's partials into M_g (p.M [G x H], or null: not stored) and runs the head's
-// forward (p.tail per-bag outputs as in launch_group_pool; Y given: loss [G] only; dM / dWk / dbk are not read)
+// forward (p.tail per-bag outputs as in launch_group_pool; Y given: loss [G] only; dM / dWk / dbk are not read).  The
+// merge and the head are the device functions launch_group_pool's tail runs, the head with its backward compiled out.
 int launch_group_pool_partial(PoolParams p, const SegTable& s, hipStream_t st);
 int launch_group_infer_tail(PoolParams p, const SegTable& s, hipStream_t st);
 // grouped multimodal step: the merge of launch_group_pool without the head tail -- M_g to p.M + g * ldm (the caller's
