@@ -336,6 +336,57 @@ int mmf_surv_head_nll_step_group(const float* feat, int32_t ldf, int32_t F, int3
                                  void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Grouped forward-only pass of the multimodal head, both fusions: what the validation pass and the summary
+ *   (utils/core_utils.py:267-430) compute for G patients by running models/model_mm_attention_mil.py:128-200 once per
+ *   patient under no_grad.  The stacks and the omic branch need nothing new: mmf_amil_infer_group / mmf_radio_infer_group
+ *   with head = NULL write M [G x H] (model_mm_attention_mil.py:132-160), and the eval-mode SNN (:162-166,
+ *   models/model_modules.py:64-68) is mmf_dense_forward on a B = G batch.  Behind them, on the same stream:
+ *
+ * mmf_xfusion_infer_group (fusion = 'tensor'): the XlinearFusion block (models/model_modules.py:156-178 with gate = 1,
+ *   skip = 1) and classifier[0] + ReLU (model_mm_attention_mil.py:182-188) for G patients in FOUR launches:
+ *     1. the gating stage, one workgroup per patient (model_modules.py:158-165: h, z, sigmoid(z) * h, o);
+ *     2. the Kronecker product of [o_i, 1] (:164-171) fused into encoder1 (:172): the (sdim + 1)^m-wide product is never
+ *        written, and every row of encoder1's weight is fetched from memory once per window, not once per patient;
+ *     3. encoder2 (:173-176), which reads its skip connection [e1 | v_0 | v_1 (| v_2)] from where the parts lie;
+ *     4. classifier[0] + ReLU.
+ *   v: HOST array of m device pointers, each a dense [G x dim] matrix (16-byte aligned).  MM [G x mmhid2]: encoder2's
+ *   output (what forward(return_features=True) returns); hid [G x nhid].  Eval mode only: there is no dropout argument
+ *   and nothing is kept for a backward.  Every output element is summed in an order that depends on the element alone:
+ *   what a patient gets is bit for bit what the same call gives it alone (G = 1).
+ *   Returns MMF_ERR_SHAPE for m outside 2..3, sdim != 16, dim % 4 != 0, mmhid1 + m * dim or mmhid2 > 1536, G outside
+ *   1..MMF_GROUP_MAX; MMF_ERR_ARG for a null pointer; MMF_ERR_ALIGN for a misaligned v_i, Wh_i, Wz_i or workspace;
+ *   MMF_ERR_WORKSPACE.  Each refusal happens before any launch.
+ * mmf_xfusion_group_infer_workspace_bytes: its workspace (o and encoder1's output), or 0 for arguments out of range.
+ *
+ * mmf_surv_head_infer_group: the hazard head (model_mm_attention_mil.py:190-194; utils/loss_utils.py:22-39 and
+ *   utils/core_utils.py:207 when a target is given) for G patients, forward only, in ONE launch of one workgroup per
+ *   patient.  Patient g's feature row is the concatenation of row g of nseg (1..3) dense [G x widths[s]] device buffers
+ *   (segs, widths: HOST arrays) -- the branch embeddings of the concat fusion in the model's order, so torch.cat
+ *   (:168-187) is never a launch, or hid of the tensor fusion as one segment.  sum widths <= 1024, K <= 32,
+ *   G <= MMF_GROUP_MAX.  head: the per-patient arrays are G long, Wk is [K x sum widths].  target (optional): each
+ *   patient's nll_surv VALUE; only Y, c [G], alpha, eps and loss [G] are read, as in mmf_amil_infer_group.  The head is
+ *   the device code of mmf_surv_head_nll_step_group with its backward compiled out: the same outputs bit for bit.
+ *   Returns MMF_ERR_SHAPE / MMF_ERR_ARG on the lines of mmf_surv_head_nll_step_group, before any launch.
+ * No workgroup waits for another; no float atomics; the calls allocate nothing and keep no state.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct mmf_xfusion_weights {
+  int32_t m;                         /* modalities, 2 or 3 */
+  int32_t dim, sdim;                 /* embedding width (256), gated width (16) */
+  int32_t mmhid1, mmhid2, nhid;      /* rows of encoder1, encoder2, classifier[0] */
+  const float *Wh[3], *bh[3];        /* reduce.i.0.0: [sdim x dim], [sdim] */
+  const float *Wz[3], *bz[3];        /* reduce.i.1.0: [sdim x m * dim], [sdim] */
+  const float *Wo[3], *bo[3];        /* reduce.i.2.0: [sdim x sdim], [sdim] */
+  const float *We1, *be1;            /* encoder1.0: [mmhid1 x (sdim + 1)^m], [mmhid1] */
+  const float *We2, *be2;            /* encoder2.0: [mmhid2 x mmhid1 + m * dim], [mmhid2] */
+  const float *Wc0, *bc0;            /* classifier.0: [nhid x mmhid2], [nhid] */
+} mmf_xfusion_weights;
+size_t mmf_xfusion_group_infer_workspace_bytes(int32_t m, int32_t sdim, int32_t mmhid1, int32_t G);
+int mmf_xfusion_infer_group(const mmf_xfusion_weights* w, const float* const* v, int32_t G, void* workspace,
+                            size_t workspace_bytes, float* MM, float* hid, void* stream);
+int mmf_surv_head_infer_group(const float* const* segs, const int32_t* widths, int32_t nseg, int32_t G,
+                              const mmf_surv_head* head, const mmf_nll_target* target, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Forward-only variants for the inference consumers of the path -- embedding export
  * (pre_trained_feature.py:116-162: model(..., return_features=True) under no_grad), per-patient inference and
  * attention heat-map scoring (utils/heatmap_utils.py:111-150,249-275: A_raw per bag / per 512-patch batch).

@@ -83,6 +83,13 @@ class XReduceIO(C.Structure):
                                       "dWh", "dbh", "dWz", "dbz", "dWo", "dbo")]
 
 
+class XFusionWeights(C.Structure):
+    """struct mmf_xfusion_weights (include/mmf_amil.h)."""
+    _fields_ = [(n, C.c_int32) for n in ("m", "dim", "sdim", "mmhid1", "mmhid2", "nhid")] + [
+        (n, C.c_void_p * 3) for n in ("Wh", "bh", "Wz", "bz", "Wo", "bo")] + [
+        (n, C.c_void_p) for n in ("We1", "be1", "We2", "be2", "Wc0", "bc0")]
+
+
 # name -> (restype, argtypes): every symbol include/mmf_amil.h declares
 SYMBOLS = {
     "mmf_strerror": (C.c_char_p, [C.c_int]),
@@ -145,6 +152,11 @@ SYMBOLS = {
     "mmf_radio_infer_group": (C.c_int, [C.POINTER(AmilDesc), C.POINTER(BagGroup), C.POINTER(RadioReduce), C.c_void_p,
                                         C.c_size_t, C.POINTER(SurvHead), C.POINTER(NllTarget), C.c_void_p, C.c_void_p,
                                         C.c_void_p]),
+    "mmf_xfusion_group_infer_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "mmf_xfusion_infer_group": (C.c_int, [C.POINTER(XFusionWeights), C.POINTER(C.c_void_p), C.c_int32, C.c_void_p,
+                                          C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mmf_surv_head_infer_group": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.c_int32, C.c_int32,
+                                            C.POINTER(SurvHead), C.POINTER(NllTarget), C.c_void_p]),
     "mmf_amil_infer_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "mmf_amil_infer": (C.c_int, [C.POINTER(AmilDesc), C.c_void_p, C.c_void_p, C.c_size_t,
                                  C.c_void_p, C.c_void_p, C.c_void_p]),

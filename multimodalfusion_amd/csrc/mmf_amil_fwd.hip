@@ -1255,6 +1255,43 @@ int launch_surv_head_group(PoolParams p, int ldf, int G, hipStream_t st) {
   return hipGetLastError() == hipSuccess ? MMF_OK : MMF_ERR_LAUNCH;
 }
 
+// The hazard head of a window, forward only (mmf_surv_head_infer_group): one workgroup per patient, whose feature row is
+// the concatenation of row g of up to three dense [G x width] buffers -- the branch embeddings of the concat fusion where
+// the stacks left them (torch.cat of models/model_mm_attention_mil.py:168-187 is never a launch), or `hid` of the tensor
+// fusion.  The row is gathered into LDS and head_tail runs on it with its backward compiled out: logits, hazards, S,
+// Y_hat, risk and -- with labels -- the loss value.
+__global__ __launch_bounds__(1024) void surv_head_infer_group_kernel(PoolParams p, HeadSegs s) {
+  __shared__ float tail_sm[1024 + 160];
+  const int g = blockIdx.x, tid = threadIdx.x;
+  const PoolParams q = bag_slice(p, g, 0);            // p.M is null: the row comes from the segments
+  TailPre pre;
+  tail_preload(q, pre);
+  int off = 0;
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    if (i < s.n) {
+      for (int c = tid; c < s.width[i]; c += 1024) tail_sm[off + c] = s.x[i][(size_t)g * s.width[i] + c];
+      off += s.width[i];
+    }
+  }
+  head_tail<true, false>(q, pre, tail_sm);
+}
+
+int launch_surv_head_infer_group(PoolParams p, const HeadSegs& s, int G, hipStream_t st) {
+  if (!p.tail.Wk || p.M) return MMF_ERR_ARG;
+  if (s.n < 1 || s.n > 3 || p.tail.K < 1 || p.tail.K > 32 || G < 1 || G > GROUP_MAX) return MMF_ERR_SHAPE;
+  int F = 0;
+  for (int i = 0; i < s.n; ++i) {
+    if (!s.x[i]) return MMF_ERR_ARG;
+    if (s.width[i] < 1 || s.width[i] > 1024) return MMF_ERR_SHAPE;
+    F += s.width[i];
+  }
+  if (F != p.H || F > 1024) return MMF_ERR_SHAPE;
+  ProfScope ps("surv_head_infer_group_kernel", st);
+  hipLaunchKernelGGL(surv_head_infer_group_kernel, dim3(G), dim3(1024), 0, st, p, s);
+  return hipGetLastError() == hipSuccess ? MMF_OK : MMF_ERR_LAUNCH;
+}
+
 // ---- forward-only grouped pass (mmf_amil_infer_group) ----------------------------------------------------------------
 // One workgroup per bag: group_tail_kernel with the forward-only head tail -- merge the bag's partials into M_g (written
 // when p.M is given), then the classifier, hazards, S, Y_hat, risk and -- when labels are given -- the bag's nll_surv

@@ -1351,6 +1351,85 @@ int mmf_surv_head_nll_step(const float* feat, int32_t F, const mmf_surv_head* he
   return launch_head_tail(p, static_cast<hipStream_t>(stream));
 }
 
+// ---- forward-only grouped pass of the multimodal head: the fusion tail and the hazard head of a window -----------------
+int mmf_surv_head_infer_group(const float* const* segs, const int32_t* widths, int32_t nseg, int32_t G,
+                              const mmf_surv_head* head, const mmf_nll_target* target, void* stream) {
+  if (!segs || !widths) return MMF_ERR_ARG;
+  if (nseg < 1 || nseg > 3 || G < 1 || G > GROUP_MAX) return MMF_ERR_SHAPE;
+  HeadSegs s{};
+  s.n = nseg;
+  int F = 0;
+  for (int i = 0; i < nseg; ++i) {
+    if (!segs[i]) return MMF_ERR_ARG;
+    if (widths[i] < 1 || widths[i] > 1024) return MMF_ERR_SHAPE;
+    s.x[i] = segs[i]; s.width[i] = widths[i];
+    F += widths[i];
+  }
+  if (F > 1024) return MMF_ERR_SHAPE;
+  PoolParams p{};
+  if (int e = head_tail_of(head, target, p.tail, false)) return e;
+  p.H = F;
+  return launch_surv_head_infer_group(p, s, G, static_cast<hipStream_t>(stream));
+}
+
+namespace mmf {
+// the window's fusion workspace: o of the gating stage and encoder1's output
+struct XFusionWs { float *o, *e1; size_t bytes; };
+static XFusionWs carve_xfusion(Carver& c, int m, int sdim, int mmhid1, int G) {
+  XFusionWs w{};
+  w.o = c.take<float>((size_t)G * m * sdim);
+  w.e1 = c.take<float>((size_t)G * mmhid1);
+  w.bytes = c.off;
+  return w;
+}
+static bool xfusion_shape_ok(int m, int sdim, int mmhid1, int G) {
+  return m >= 2 && m <= 3 && sdim == 16 && mmhid1 >= 1 && mmhid1 <= 64 * DENSE_SEGS_MAXC && G >= 1 && G <= GROUP_MAX;
+}
+}  // namespace mmf
+
+size_t mmf_xfusion_group_infer_workspace_bytes(int32_t m, int32_t sdim, int32_t mmhid1, int32_t G) {
+  if (!xfusion_shape_ok(m, sdim, mmhid1, G)) return 0;
+  Carver c;
+  return carve_xfusion(c, m, sdim, mmhid1, G).bytes;
+}
+
+int mmf_xfusion_infer_group(const mmf_xfusion_weights* w, const float* const* v, int32_t G, void* workspace,
+                            size_t workspace_bytes, float* MM, float* hid, void* stream) {
+  if (!w || !v || !workspace || !MM || !hid) return MMF_ERR_ARG;
+  if (!xfusion_shape_ok(w->m, w->sdim, w->mmhid1, G)) return MMF_ERR_SHAPE;
+  if (w->dim < 4 || w->dim % 4 != 0 || w->mmhid2 < 1 || w->nhid < 1) return MMF_ERR_SHAPE;
+  if (w->mmhid1 + w->m * w->dim > 64 * DENSE_SEGS_MAXC || w->mmhid2 > 64 * DENSE_SEGS_MAXC) return MMF_ERR_SHAPE;
+  if (!w->We1 || !w->be1 || !w->We2 || !w->be2 || !w->Wc0 || !w->bc0) return MMF_ERR_ARG;
+  XGateGroupParams gp{};
+  gp.m = w->m; gp.G = G; gp.dim = w->dim; gp.sdim = w->sdim;
+  for (int i = 0; i < w->m; ++i) {
+    if (!v[i] || !w->Wh[i] || !w->bh[i] || !w->Wz[i] || !w->bz[i] || !w->Wo[i] || !w->bo[i]) return MMF_ERR_ARG;
+    if (!aligned16(v[i]) || !aligned16(w->Wh[i]) || !aligned16(w->Wz[i])) return MMF_ERR_ALIGN;     // float4 loads
+    gp.v[i] = v[i]; gp.Wh[i] = w->Wh[i]; gp.bh[i] = w->bh[i]; gp.Wz[i] = w->Wz[i]; gp.bz[i] = w->bz[i];
+    gp.Wo[i] = w->Wo[i]; gp.bo[i] = w->bo[i];
+  }
+  if (!aligned16(workspace)) return MMF_ERR_ALIGN;
+  Carver c(workspace);
+  const XFusionWs ws = carve_xfusion(c, w->m, w->sdim, w->mmhid1, G);
+  if (ws.bytes > workspace_bytes) return MMF_ERR_WORKSPACE;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  gp.o = ws.o;
+  if (int e = launch_xgate_group(gp, st)) return e;
+  KronDenseGroupParams kp{w->m, G, w->mmhid1, ws.o, w->We1, w->be1, ws.e1};
+  if (int e = launch_kron_dense_group(kp, st)) return e;
+  DenseSegsParams e2{};                 // encoder2 on [e1 | v_0 | v_1 (| v_2)], read where the parts lie
+  e2.nseg = 1 + w->m; e2.G = G; e2.N = w->mmhid2; e2.K = w->mmhid1 + w->m * w->dim;
+  e2.x[0] = ws.e1; e2.width[0] = w->mmhid1;
+  for (int i = 0; i < w->m; ++i) { e2.x[1 + i] = v[i]; e2.width[1 + i] = w->dim; }
+  e2.W = w->We2; e2.bias = w->be2; e2.y = MM;
+  if (int e = launch_dense_segs_group(e2, st)) return e;
+  DenseSegsParams c0{};                 // classifier[0] + ReLU
+  c0.nseg = 1; c0.G = G; c0.N = w->nhid; c0.K = w->mmhid2;
+  c0.x[0] = MM; c0.width[0] = w->mmhid2;
+  c0.W = w->Wc0; c0.bias = w->bc0; c0.y = hid;
+  return launch_dense_segs_group(c0, st);
+}
+
 // ---- standalone attention scorer: Attn_Net / Attn_Net_Gated .forward(x) -> (A, x) ------------------------------
 namespace mmf {
 struct AttnWs {

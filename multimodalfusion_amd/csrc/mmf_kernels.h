@@ -301,6 +301,10 @@ int launch_group_infer_tail(PoolParams p, const SegTable& s, hipStream_t st);
 int launch_group_merge(PoolParams p, const SegTable& s, int ldm, float* Mw, hipStream_t st);
 int launch_group_dm_gather(const float* src, int ld, float* dst, int G, int H, hipStream_t st);
 int launch_surv_head_group(PoolParams p, int ldf, int G, hipStream_t st);
+// forward-only hazard head of G patients (mmf_surv_head_infer_group): patient g's feature row is the concatenation of
+// row g of s.n dense [G x width] buffers (sum width = p.H <= 1024); p.M is null, p.tail as in launch_group_infer_tail
+struct HeadSegs { const float* x[3]; int width[3]; int n; };
+int launch_surv_head_infer_group(PoolParams p, const HeadSegs& s, int G, hipStream_t st);
 int set_dyn_lds(const void* kern, int bytes);
 
 // Optional per-kernel timing with HIP events on the launch stream: records into the mmf_trace of the ABI call in

@@ -65,6 +65,35 @@ struct XReduceParams {
 };
 int launch_xreduce_fwd(XReduceParams p, hipStream_t st);
 int launch_xreduce_bwd(XReduceParams p, hipStream_t st);
+
+// ---- forward-only XlinearFusion of a window of G patients (mmf_xfusion_infer_group): eval mode, nothing saved --------
+// the gating stage per patient: XReduceParams' arithmetic for B = 1 in workgroup g; only o leaves the kernel
+struct XGateGroupParams {
+  int m, G, dim, sdim;
+  const float* v[3];                    // [G x dim]
+  const float *Wh[3], *bh[3], *Wz[3], *bz[3], *Wo[3], *bo[3];
+  float* o;                             // [G x m x sdim]
+};
+// y[g][n] = relu(bias[n] + sum_e kron_g[e] W[n][e]), kron_g = [o_g0, 1] x [o_g1, 1] (x [o_g2, 1]) formed on the fly
+struct KronDenseGroupParams {
+  int m, G, N;                          // sdim = 16: rows of W are 17^m wide
+  const float* o;                       // [G x m x 16]
+  const float *W, *bias;                // [N x 17^m], [N]
+  float* y;                             // [G x N]
+};
+// y[g][n] = relu(bias[n] + sum_s sum_k x_s[g][k] W[n][off_s + k]): a dense layer whose input row is the concatenation
+// of up to 4 dense [G x width_s] buffers (encoder2's skip connection; one segment: a plain layer)
+struct DenseSegsParams {
+  int nseg, G, N, K;                    // K = sum width <= 64 * DENSE_SEGS_MAXC
+  const float* x[4];
+  int width[4];
+  const float *W, *bias;                // [N x K], [N]
+  float* y;                             // [G x N]
+};
+constexpr int DENSE_SEGS_MAXC = 24;
+int launch_xgate_group(XGateGroupParams p, hipStream_t st);
+int launch_kron_dense_group(KronDenseGroupParams p, hipStream_t st);
+int launch_dense_segs_group(DenseSegsParams p, hipStream_t st);
 }  // namespace mmf
 
 // ---- stage-2 (embedding-level) building blocks: SURVEY.md 8f row N3 --------------------------------------------

@@ -351,6 +351,169 @@ int launch_xreduce_bwd(XReduceParams p, hipStream_t st) {
 
 static inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 
+// ---------------------------------------------------------------------------------------------
+// Forward-only XlinearFusion of a window (mmf_xfusion_infer_group; models/model_modules.py:156-178 with gate = 1,
+// skip = 1 in eval mode, then classifier[0] + ReLU of models/model_mm_attention_mil.py:182-188): four launches for G
+// patients.  In each of them one output element is summed by one wave in an order fixed by the element alone, so what a
+// patient gets depends neither on G nor on its position in the window.
+// ---------------------------------------------------------------------------------------------
+constexpr int XG_MAX = 3 * 16;         // m * sdim values of one patient kept in LDS
+
+// Gating stage, one workgroup per patient: xreduce_fwd_kernel's arithmetic for B = 1 (h, z, the gate product, o), so the
+// B <= 8 cap of that kernel's LDS arrays does not apply; only o_g leaves the kernel.
+__global__ __launch_bounds__(XR_NT) void xgate_group_kernel(XGateGroupParams p) {
+  __shared__ float sh_h[XG_MAX], sh_z[XG_MAX], sh_gm[XG_MAX];
+  const int g = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  constexpr int NW = XR_NT / 64;
+  const int S = p.sdim, total = p.m * S;
+  for (int o = wave; o < 2 * total; o += NW) {       // one wave per h / z value
+    const bool is_z = o >= total;
+    const int q = is_z ? o - total : o;
+    const int i = q / S, j = q % S;
+    float acc = 0.f;
+    if (!is_z) {
+      acc = wave_dot(p.v[i] + (size_t)g * p.dim, p.Wh[i] + (size_t)j * p.dim, p.dim, lane);
+    } else {
+      for (int t = 0; t < p.m; ++t)                  // v_cat = [v_0 | v_1 | ...]
+        acc += wave_dot(p.v[t] + (size_t)g * p.dim, p.Wz[i] + (size_t)j * p.m * p.dim + (size_t)t * p.dim, p.dim, lane);
+    }
+    const float r = wave_sum(acc);
+    if (lane == 0) {
+      if (is_z) sh_z[q] = r + p.bz[i][j];
+      else sh_h[q] = fmaxf(r + p.bh[i][j], 0.f);
+    }
+  }
+  __syncthreads();
+  if (tid < total) sh_gm[tid] = (1.0f / (1.0f + expf(-sh_z[tid]))) * sh_h[tid];
+  __syncthreads();
+  if (tid < total) {
+    const int i = tid / S, j = tid % S;
+    float acc = p.bo[i][j];
+#pragma unroll 16
+    for (int t = 0; t < S; ++t) acc += sh_gm[i * S + t] * p.Wo[i][j * S + t];
+    p.o[(size_t)g * total + tid] = fmaxf(acc, 0.f);
+  }
+}
+
+// The Kronecker product fused into encoder1: the 17^m-wide product is never written.  Work unit = (row n of W, one of
+// `gsplit` interleaved shares of the patients), one wave each.  The wave keeps its row in registers -- lane l owns the
+// outer indices q = l, l + 64, ... < 17^(m-1) and the 17 consecutive weights W[n][17 q .. 17 q + 16] of each (the rows
+// are 17^m floats: odd, not 16-byte aligned, so they are read as single floats, and the last q-chunk is partly empty) --
+// and loops over its patients: the inner 17-term dot with [o_last, 1] (LDS broadcast reads), times the outer factor
+// o0'[i] (o1'[j]) of q, summed over the lane's q in order, then over the wave.  A row is fetched from memory once per
+// window (and again from L2 by the other shares), not once per patient.
+constexpr int KD_S1 = 17;
+template <int M>
+__global__ __launch_bounds__(256) void kron_dense_group_kernel(KronDenseGroupParams p, int gsplit) {
+  constexpr int Q = M == 3 ? KD_S1 * KD_S1 : KD_S1, NQ = (Q + 63) / 64, KK = Q * KD_S1;
+  __shared__ float so[GROUP_MAX * M * KD_S1];         // o' = [o, 1] of every patient and modality
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  for (int e = tid; e < p.G * M * KD_S1; e += 256) {
+    const int r = e / KD_S1, k = e - r * KD_S1;
+    so[e] = k < KD_S1 - 1 ? p.o[(size_t)r * (KD_S1 - 1) + k] : 1.f;
+  }
+  __syncthreads();
+  const int u = blockIdx.x * 4 + wave, n = u / gsplit, gp = u - n * gsplit;
+  if (n >= p.N) return;
+  const float* wr = p.W + (size_t)n * KK;
+  float w[NQ][KD_S1];
+  int oi[NQ], oj[NQ];
+  bool valid[NQ];
+#pragma unroll
+  for (int c = 0; c < NQ; ++c) {
+    const int q = lane + 64 * c;
+    valid[c] = q < Q;
+    oi[c] = valid[c] ? (M == 3 ? q / KD_S1 : q) : 0;
+    oj[c] = valid[c] ? q % KD_S1 : 0;
+#pragma unroll
+    for (int k = 0; k < KD_S1; ++k) w[c][k] = valid[c] ? wr[q * KD_S1 + k] : 0.f;
+  }
+  const float bias = p.bias ? p.bias[n] : 0.f;
+  for (int g = gp; g < p.G; g += gsplit) {
+    const float* og = so + g * M * KD_S1;
+    float last[KD_S1];
+#pragma unroll
+    for (int k = 0; k < KD_S1; ++k) last[k] = og[(M - 1) * KD_S1 + k];
+    float acc = 0.f;
+#pragma unroll
+    for (int c = 0; c < NQ; ++c) {
+      float inner = 0.f;
+#pragma unroll
+      for (int k = 0; k < KD_S1; ++k) inner += w[c][k] * last[k];
+      const float outer = M == 3 ? og[oi[c]] * og[KD_S1 + oj[c]] : og[oi[c]];
+      acc += valid[c] ? outer * inner : 0.f;
+    }
+    acc = wave_sum(acc);
+    if (lane == 0) p.y[(size_t)g * p.N + n] = fmaxf(acc + bias, 0.f);
+  }
+}
+
+// A dense layer + ReLU over a window whose input row is the concatenation of up to four [G x width] buffers -- encoder2
+// reads its skip connection [e1 | v_0 | ...] from where the parts lie (no concatenation launch); classifier[0] is the
+// one-segment case.  Work units as in kron_dense_group_kernel; lane l keeps W[n][l + 64 c] in registers with, for each,
+// the address of its input element in patient 0's row and that buffer's row stride.
+__global__ __launch_bounds__(256) void dense_segs_group_kernel(DenseSegsParams p, int gsplit) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int u = blockIdx.x * 4 + wave, n = u / gsplit, gp = u - n * gsplit;
+  if (n >= p.N) return;
+  const float* wr = p.W + (size_t)n * p.K;
+  float w[DENSE_SEGS_MAXC];
+  const float* xp[DENSE_SEGS_MAXC];
+  int ld[DENSE_SEGS_MAXC];
+#pragma unroll
+  for (int c = 0; c < DENSE_SEGS_MAXC; ++c) {
+    const int k = lane + 64 * c;
+    w[c] = k < p.K ? wr[k] : 0.f;
+    xp[c] = p.x[0];                    // k >= K: a readable address, weight 0, not added
+    ld[c] = 0;
+    int off = 0;
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+      if (s < p.nseg && k >= off && k < off + p.width[s]) { xp[c] = p.x[s] + (k - off); ld[c] = p.width[s]; }
+      off += s < p.nseg ? p.width[s] : 0;
+    }
+  }
+  const float bias = p.bias ? p.bias[n] : 0.f;
+  for (int g = gp; g < p.G; g += gsplit) {
+    float a[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int c = 0; c < DENSE_SEGS_MAXC; ++c)
+      if (lane + 64 * c < p.K) a[c & 3] += w[c] * xp[c][(size_t)g * ld[c]];
+    const float acc = wave_sum((a[0] + a[1]) + (a[2] + a[3]));
+    if (lane == 0) p.y[(size_t)g * p.N + n] = fmaxf(acc + bias, 0.f);
+  }
+}
+
+int launch_xgate_group(XGateGroupParams p, hipStream_t st) {
+  if (p.m < 2 || p.m > 3 || p.sdim < 1 || p.m * p.sdim > XG_MAX || p.G < 1 || p.G > GROUP_MAX) return MMF_ERR_SHAPE;
+  if (p.dim < 4 || p.dim % 4 != 0) return MMF_ERR_SHAPE;
+  { ProfScope ps("xgate_group_kernel", st); hipLaunchKernelGGL(xgate_group_kernel, dim3(p.G), dim3(XR_NT), 0, st, p); }
+  return hipGetLastError() == hipSuccess ? MMF_OK : MMF_ERR_LAUNCH;
+}
+// the patients' shares of a row: enough waves to fill the CUs at G = 64 (4 x 512 rows), never more shares than patients
+static inline int group_shares(int G) { return G < 4 ? G : 4; }
+int launch_kron_dense_group(KronDenseGroupParams p, hipStream_t st) {
+  if (p.m < 2 || p.m > 3 || p.G < 1 || p.G > GROUP_MAX || p.N < 1) return MMF_ERR_SHAPE;
+  const int gs = group_shares(p.G), blocks = cdiv((int64_t)p.N * gs, 4);
+  { ProfScope ps("kron_dense_group_kernel", st);
+    if (p.m == 3) hipLaunchKernelGGL(kron_dense_group_kernel<3>, dim3(blocks), dim3(256), 0, st, p, gs);
+    else hipLaunchKernelGGL(kron_dense_group_kernel<2>, dim3(blocks), dim3(256), 0, st, p, gs); }
+  return hipGetLastError() == hipSuccess ? MMF_OK : MMF_ERR_LAUNCH;
+}
+int launch_dense_segs_group(DenseSegsParams p, hipStream_t st) {
+  if (p.nseg < 1 || p.nseg > 4 || p.G < 1 || p.G > GROUP_MAX || p.N < 1) return MMF_ERR_SHAPE;
+  int K = 0;
+  for (int s = 0; s < p.nseg; ++s) {
+    if (p.width[s] < 1 || !p.x[s]) return MMF_ERR_SHAPE;
+    K += p.width[s];
+  }
+  if (K != p.K || K > 64 * DENSE_SEGS_MAXC) return MMF_ERR_SHAPE;
+  const int gs = group_shares(p.G), blocks = cdiv((int64_t)p.N * gs, 4);
+  { ProfScope ps("dense_segs_group_kernel", st);
+    hipLaunchKernelGGL(dense_segs_group_kernel, dim3(blocks), dim3(256), 0, st, p, gs); }
+  return hipGetLastError() == hipSuccess ? MMF_OK : MMF_ERR_LAUNCH;
+}
+
 int launch_dense_fwd(DenseParams p, hipStream_t st) {
   const int64_t total = (int64_t)p.B * p.N;
   int blocks = cdiv(total, 4);

@@ -481,6 +481,109 @@ class MM_MIL_Attention_fc_surv(MM_MIL_Attention_fc):
             hand_over_grads(params, grads, grad_out, accumulate)
         return hazards, S, Y_hat.view(-1), A_raw, loss, risk
 
+    def _xfusion_weights(self, m):
+        """XlinearFusion's weights in ops.xfusion's order: per modality (Wh, bh, Wz, bz, Wo, bo), then We1, be1, We2, be2."""
+        fus = self.mm
+        weights = []
+        for i in range(m):
+            for lin in (fus.reduce[i][0][0], fus.reduce[i][1][0], fus.reduce[i][2][0]):
+                weights += [lin.weight, lin.bias]
+        return weights + [fus.encoder1[0].weight, fus.encoder1[0].bias, fus.encoder2[0].weight, fus.encoder2[0].bias]
+
+    def forward_group(self, patients, labels=None, censors=None, alpha=0.0, return_features=False):
+        """The eval-mode forward of the G <= 64 patients of an evaluation window, both fusions -- validation and the
+        summary evaluate one patient at a time with fixed weights (utils/core_utils.py:267-430 of the reference), and the
+        patients are independent.  Each stack runs once over its branch's concatenated rows with no head behind it
+        (ops.radio_infer_group / ops.amil_infer_group: M [G x 256]), the eval-mode SNN as one B = G batch, then
+          concat: the hazard head on the embeddings where the branches left them (ops.surv_head_infer_group; no torch.cat);
+          tensor: XlinearFusion + classifier[0] in one call of four launches (ops.xfusion_infer_group), the hazard head on hid.
+        Everything is issued on the current stream, in the order radio, pathology, omic, fusion, head.
+
+        patients: as nll_step_group takes them (a list of per-patient kwarg dicts, or the pre-stacked triple); labels /
+        censors: G values for each patient's NLLSurvLoss(alpha) value, or None.  fp32 2-D bags, exact-fp32 GEMMs, K <= 32,
+        eval mode; every refusal comes before the first launch.  Each patient gets what `model(**kwargs)` gives it under
+        no_grad, to fp32 rounding.
+        Returns (hazards [G x K], S [G x K], Y_hat [G], A_raw {"radiology": [per patient], "pathology": [per patient]},
+        loss [G] or None, risk [G]), detached; return_features: the fused embedding [G x F] (concat) or [G x mmhid2]
+        (tensor), as forward(return_features=True) returns it per patient."""
+        from ..ops import _dense_fwd_raw
+        MmfError = ops._lib.MmfError
+        if self.training:
+            raise RuntimeError("forward_group is the eval-mode pass: call model.eval() first")
+        if ops._gemm != 0:
+            raise MmfError("forward_group runs the exact-fp32 GEMMs only (ops.set_gemm(0))")
+        order, _, F = self._concat_layout()
+        tensor = self.fusion == "tensor"
+        if tensor and not (self.mm.skip and len(order) * self.mm.reduce[0][0][0].weight.shape[0] <= 384):
+            raise NotImplementedError("forward_group covers the XlinearFusion configuration the heads use (skip)")
+        head = self.classifier[3] if tensor else self.classifier
+        Wk, bk = head.weight, head.bias
+        if Wk.shape[0] > 32:
+            raise MmfError("forward_group: the fused hazard head takes K <= 32 classes")
+        path, radio, omic = self._stacked_patients(patients)
+        # ---- every refusal before the first launch
+        counts = {}
+        if path is not None:
+            counts["path"] = len(path[1])
+        if radio is not None:
+            counts["radio"] = len(radio[1])
+        if omic is not None:
+            if omic.dim() != 2 or omic.dtype != torch.float32 or omic.shape[1] != self.fc_omic[0][0].in_features:
+                raise MmfError(f"omic features must be fp32 [G x {self.fc_omic[0][0].in_features}], got "
+                               f"{omic.dtype} {tuple(omic.shape)}")
+            counts["omic"] = int(omic.shape[0])
+        if len(set(counts.values())) != 1:
+            raise MmfError(f"the branches hold different numbers of patients: {counts}")
+        G = next(iter(counts.values()))
+        if G < 1 or G > ops.GROUP_MAX:
+            raise MmfError(f"a group holds 1 .. {ops.GROUP_MAX} patients, got {G}")
+        for k, br in (("path", path), ("radio", radio)):
+            if br is None:
+                continue
+            xs = br[0] if k == "radio" else [br[0]]
+            if any(x.dtype != torch.float32 for x in xs):
+                raise MmfError("the grouped pass takes fp32 bags only (bf16 bags: one forward per patient)")
+            if min(br[1]) < 1:
+                raise MmfError("empty bag in the group")
+            if any(x.dim() != 2 or x.shape[0] != sum(br[1]) for x in xs):
+                raise MmfError(f"the {k} bags hold {[tuple(x.shape) for x in xs]} rows, their sizes add up to {sum(br[1])}")
+        Y = cc = None
+        if labels is not None:
+            Y = torch.as_tensor(labels).reshape(-1)
+            cc = torch.as_tensor(censors).reshape(-1)
+            if Y.numel() != G or cc.numel() != G:
+                raise MmfError(f"{G} patients need {G} labels and censorships, got {Y.numel()} / {cc.numel()}")
+        with torch.no_grad():
+            A_raw, emb = {}, {}
+            if "radio" in order:
+                gated, stack, _, _ = stack_args(self.attention_net_radio, False)
+                if len(radio[0]) > 1:
+                    out = ops.radio_infer_group(radio[0], radio[1], self.reduce_dim.weight, self.reduce_dim.bias, stack,
+                                                gated, want_M=True)
+                else:                          # one modality: no reduce_dim, the pathology pass on that bag
+                    out = ops.amil_infer_group(radio[0][0], radio[1], stack, gated, want_M=True)
+                A_raw["radiology"], emb["radio"] = out[4], out[5]
+            if "path" in order:
+                gated, stack, _, _ = stack_args(self.attention_net_WSI, False)
+                out = ops.amil_infer_group(path[0], path[1], stack, gated, want_M=True)
+                A_raw["pathology"], emb["path"] = out[4], out[5]
+            if "omic" in order:
+                x = ops._f32c(omic)
+                for i, blk in enumerate(self.fc_omic):
+                    x = _dense_fwd_raw(x, blk[0].weight, blk[0].bias, "selu", "none", 0.0, 0, i)
+                emb["omic"] = x
+            vs = [emb[k] for k in order]
+            if tensor:
+                c0 = self.classifier[0]
+                MM, hid = ops.xfusion_infer_group(vs, self._xfusion_weights(len(order)), c0.weight, c0.bias)
+                segs = [hid]
+            else:
+                MM, segs = None, vs
+            if return_features:
+                return MM if tensor else torch.cat(vs, dim=1)
+            hazards, S, Y_hat, loss, risk = ops.surv_head_infer_group(segs, Wk, bk, Y, cc, alpha)
+        return hazards, S, Y_hat.view(-1), A_raw, loss, risk
+
     def forward(self, **kwargs):
         A_raw = {}
         path_x = kwargs.get("path_features") if "path" in self.mode else None

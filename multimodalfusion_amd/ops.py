@@ -728,6 +728,93 @@ def radio_infer_group(xs, sizes, Wr, br, stack, gated, Wk=None, bk=None, Y=None,
     return hz, S, Y_hat, risk, A_list, M, loss
 
 
+def _group_rows(ts, what):
+    """ts: 1 .. 3 dense fp32 matrices with the same number G of rows, 1 <= G <= GROUP_MAX.  Returns (ts contiguous, G)."""
+    ts = list(ts)
+    if any(not torch.is_tensor(t) or t.dim() != 2 for t in ts):
+        raise _lib.MmfError(f"{what}: [G x width] matrices expected")
+    ts = [_f32c(t) for t in ts]
+    G = int(ts[0].shape[0]) if ts else 0
+    if any(t.shape[0] != G for t in ts):
+        raise _lib.MmfError(f"{what}: the matrices hold different numbers of patients: {[int(t.shape[0]) for t in ts]}")
+    if G < 1 or G > GROUP_MAX:
+        raise _lib.MmfError(f"a group holds 1 .. {GROUP_MAX} patients, got {G}")
+    return ts, G
+
+
+def xfusion_infer_group(vs, weights, Wc0, bc0):
+    """The XlinearFusion block (gate, skip) and classifier[0] + ReLU for the G patients of an evaluation window, forward
+    only, in ONE C-ABI call of four launches (include/mmf_amil.h: mmf_xfusion_infer_group): the gating stage per
+    patient, the Kronecker product fused into encoder1 (never written; encoder1's weight is read once per window),
+    encoder2 on [e1 | v_0 | ...] read in place, classifier[0].  vs: 2 or 3 embedding matrices [G x dim]; weights as
+    xfusion takes them ([Wh_0, bh_0, Wz_0, bz_0, Wo_0, bo_0, ..., We1, be1, We2, be2]); Wc0, bc0: classifier[0].  Eval
+    mode: no dropout.  Returns (MM [G x mmhid2], hid [G x nhid]); row g is what the call gives patient g alone, bit for
+    bit."""
+    m = len(vs)
+    if m < 2 or m > 3 or len(weights) != 6 * m + 4:
+        raise _lib.MmfError(f"xfusion_infer_group takes 2 or 3 modalities with 6 m + 4 weights, got {m} / {len(weights)}")
+    vs, G = _group_rows(vs, "xfusion_infer_group")
+    w = [_f32c(t) for t in weights]
+    Wc0, bc0 = _f32c(Wc0), _f32c(bc0)
+    dim, sdim = int(vs[0].shape[1]), int(w[0].shape[0])
+    We1, be1, We2, be2 = w[6 * m:]
+    mmhid1, mmhid2, nhid = int(We1.shape[0]), int(We2.shape[0]), int(Wc0.shape[0])
+    ok = (all(tuple(v.shape) == (G, dim) for v in vs) and tuple(We1.shape) == (mmhid1, (sdim + 1) ** m)
+          and tuple(We2.shape) == (mmhid2, mmhid1 + m * dim) and tuple(Wc0.shape) == (nhid, mmhid2)
+          and be1.numel() == mmhid1 and be2.numel() == mmhid2 and bc0.numel() == nhid)
+    for i in range(m):
+        Wh, bh, Wz, bz, Wo, bo = w[6 * i:6 * i + 6]
+        ok = ok and (tuple(Wh.shape) == (sdim, dim) and tuple(Wz.shape) == (sdim, m * dim) and tuple(Wo.shape) == (sdim, sdim)
+                     and bh.numel() == bz.numel() == bo.numel() == sdim)
+    if not ok or dim % 4 != 0 or sdim != 16:
+        raise _lib.MmfError("xfusion_infer_group: the weights do not match the embeddings (dim % 4 == 0, scale width 16)")
+    xw = _lib.XFusionWeights(m=m, dim=dim, sdim=sdim, mmhid1=mmhid1, mmhid2=mmhid2, nhid=nhid, We1=ptr(We1), be1=ptr(be1),
+                             We2=ptr(We2), be2=ptr(be2), Wc0=ptr(Wc0), bc0=ptr(bc0))
+    for i in range(m):
+        for name, t in zip(("Wh", "bh", "Wz", "bz", "Wo", "bo"), w[6 * i:6 * i + 6]):
+            getattr(xw, name)[i] = ptr(t)
+    dev = vs[0].device
+    MM = torch.empty((G, mmhid2), dtype=torch.float32, device=dev)
+    hid = torch.empty((G, nhid), dtype=torch.float32, device=dev)
+    vp = (C.c_void_p * m)(*[ptr(v) for v in vs])
+    l = lib()
+    nbytes = l.mmf_xfusion_group_infer_workspace_bytes(m, sdim, mmhid1, G)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    check(l.mmf_xfusion_infer_group(C.byref(xw), vp, G, ptr(ws), nbytes, ptr(MM), ptr(hid), stream_ptr()),
+          "mmf_xfusion_infer_group")
+    return MM, hid
+
+
+def surv_head_infer_group(segs, Wk, bk, Y=None, c=None, alpha=0.0, eps=1e-7):
+    """The hazard head for the G patients of an evaluation window, forward only, in ONE launch (include/mmf_amil.h:
+    mmf_surv_head_infer_group).  segs: 1 .. 3 dense matrices [G x width_s]; patient g's feature row is the concatenation of
+    their rows g (the branch embeddings in the model's order -- no torch.cat -- or the tensor fusion's hid alone), sum
+    width <= 1024; Wk [K x sum width], K <= 32; Y, c: G labels / censorships for each patient's NLLSurvLoss(alpha) value,
+    or None.  Returns (hazards [G x K], S [G x K], Y_hat [G x 1], loss [G] or None, risk [G]): the forward outputs of
+    surv_head_nll_step_group on the concatenated matrix, bit for bit."""
+    Wk, bk = _f32c(Wk), _f32c(bk)
+    segs = list(segs)
+    if len(segs) < 1 or len(segs) > 3:
+        raise _lib.MmfError(f"surv_head_infer_group takes 1 .. 3 feature segments, got {len(segs)}")
+    segs, G = _group_rows(segs, "surv_head_infer_group")
+    widths = [int(t.shape[1]) for t in segs]
+    F, K = sum(widths), int(Wk.shape[0])
+    if min(widths) < 1 or Wk.dim() != 2 or Wk.shape[1] != F or F > 1024 or K > 32 or bk.numel() != K:
+        raise _lib.MmfError("surv_head_infer_group: classifier does not match the feature segments (sum width <= 1024, K <= 32)")
+    if Y is not None:
+        Y = torch.as_tensor(Y).reshape(-1)
+        c = torch.as_tensor(c).reshape(-1)
+        if Y.numel() != G or c.numel() != G:
+            raise _lib.MmfError(f"{G} patients need {G} labels and censorships, got {Y.numel()} / {c.numel()}")
+    dev = segs[0].device
+    hd, tg, (hz, S, Y_hat, loss, risk), _keep = _nll_head(Wk, bk, Y, c, alpha, eps, 1.0, None, None, False, dev, G)
+    sp = (C.c_void_p * len(segs))(*[ptr(t) for t in segs])
+    wd = (C.c_int32 * len(segs))(*widths)
+    check(lib().mmf_surv_head_infer_group(sp, wd, len(segs), G, C.byref(hd), tg and C.byref(tg), stream_ptr()),
+          "mmf_surv_head_infer_group")
+    return hz, S, Y_hat, loss, risk
+
+
 def amil_head(x, W1, b1, Wa, ba, Wb, bb, Wc, bc, Wk, bk, gated, p_h=0.0, p_att=0.0, seed=0):
     if not torch.is_grad_enabled() and p_h == 0.0 and p_att == 0.0:       # inference consumers: no-save kernels
         M, A_raw = amil_infer(x, W1, b1, Wa, ba, Wb, bb, Wc, bc, gated)

@@ -298,18 +298,21 @@ class _MMGroup:
             self.omic[len(self.slots)].copy_(x, non_blocking=True)
         self.labels.append(label.reshape(1)); self.cs.append(c.reshape(1)); self.slots.append(slot)
 
+    def window(self, model):
+        """The held patients as the model's grouped calls take them: the pre-stacked (path, radio, omic) triple."""
+        has = lambda k: k in model.mode
+        return ((self.path.buf[0, :self.path.rows], list(self.path.sizes)) if has("path") else None,
+                (self.radio.buf[:, :self.radio.rows], list(self.radio.sizes)) if has("radio") else None,
+                self.omic[:len(self.slots)] if has("omic") else None)
+
     def run(self, model, alpha, loss_scale):
         """One grouped call over the held patients -> [(loader slot, loss [1], risk [1])]; the group is empty afterwards."""
         if not self.slots:
             return []
         has = lambda k: k in model.mode
-        G = len(self.slots)
-        window = ((self.path.buf[0, :self.path.rows], list(self.path.sizes)) if has("path") else None,
-                  (self.radio.buf[:, :self.radio.rows], list(self.radio.sizes)) if has("radio") else None,
-                  self.omic[:G] if has("omic") else None)
         seeds = {k: v for k, v in self.seeds.items() if has(k)} if model.training else None
-        _, _, _, _, loss, risk = model.nll_step_group(window, torch.cat(self.labels), torch.cat(self.cs), alpha=alpha,
-                                                      loss_scale=loss_scale, seeds=seeds)
+        _, _, _, _, loss, risk = model.nll_step_group(self.window(model), torch.cat(self.labels), torch.cat(self.cs),
+                                                      alpha=alpha, loss_scale=loss_scale, seeds=seeds)
         out = [(slot, loss[g:g + 1], risk[g:g + 1]) for g, slot in enumerate(self.slots)]
         self.reset()
         return out
@@ -616,8 +619,8 @@ def train_loop_survival(epoch, model, loader, optimizer, n_classes, mode, writer
 
 
 def _eval_group_head(model):
-    """'path' / 'path_fp32' / 'radio' when the grouped forward-only pass (model.forward_group) computes what
-    `model(**feats)` does under no_grad -- the pathology or radiology head ITSELF (an overridden forward or any hook would
+    """'path' / 'path_fp32' / 'radio' / 'mm' when the grouped forward-only pass (model.forward_group) computes what
+    `model(**feats)` does under no_grad -- the pathology, radiology or multimodal head ITSELF (an overridden forward or any hook would
     be bypassed), a classifier of <= 32 classes, the exact-fp32 GEMM mode -- else None.  'path_fp32': a pathology head
     whose bf16 bags the grouped pass does not take (ops.infer_group_takes_bf16).  Asked once per pass: none of it changes
     between bags."""
@@ -625,9 +628,19 @@ def _eval_group_head(model):
     from ..models.model_attention_mil_path import MIL_Attention_fc_surv_path
     from ..models.model_attention_mil_radio import MIL_Attention_fc_surv_radio
     import torch.nn.modules.module as tm
-    if ops._gemm != 0 or getattr(getattr(model, "classifier", None), "out_features", 1 << 30) > 32:
+    from ..models.model_mm_attention_mil import MM_MIL_Attention_fc_surv
+    kind = {MIL_Attention_fc_surv_path.forward: "path", MIL_Attention_fc_surv_radio.forward: "radio",
+            MM_MIL_Attention_fc_surv.forward: "mm"}.get(type(model).forward)
+    head = getattr(model, "classifier", None)
+    if kind == "mm":             # both fusions; the tensor fusion in the configuration its kernels take (as nll_step)
+        if getattr(model, "fusion", None) == "tensor":
+            head = head[3]
+            if not (model.mm.skip and len(model._concat_order()) * model.mm.reduce[0][0][0].weight.shape[0] <= 384):
+                return None
+        elif getattr(model, "fusion", None) != "concat" or not hasattr(model, "forward_group"):
+            return None
+    if ops._gemm != 0 or getattr(head, "out_features", 1 << 30) > 32:
         return None
-    kind = {MIL_Attention_fc_surv_path.forward: "path", MIL_Attention_fc_surv_radio.forward: "radio"}.get(type(model).forward)
     hooked = lambda m: bool(m._forward_hooks or m._forward_pre_hooks or m._backward_hooks or getattr(m, "_backward_pre_hooks", None))
     if kind is None or any(hooked(m) for m in model.modules()):
         return None
@@ -683,6 +696,71 @@ class _EvalGroup(_HeldBags):
         return out
 
 
+def _mm_eval_ok(model, radio_features, path_features, genomic_features):
+    """A multimodal subject the grouped forward-only pass takes (MM_MIL_Attention_fc_surv.forward_group): for every
+    branch in model.mode a 2-D fp32 bag (the modalities of one shape) or an omic vector of the model's input width.  The
+    tensors may still be on the host."""
+    bag = lambda t: torch.is_tensor(t) and t.dim() == 2 and t.dtype == torch.float32 and t.shape[0] >= 1
+    if "path" in model.mode and not bag(path_features):
+        return False
+    if "radio" in model.mode:
+        xs = [radio_features.get(m) if isinstance(radio_features, dict) else None for m in model.modalities]
+        if any(not bag(x) or x.shape != xs[0].shape for x in xs):
+            return False
+    if "omic" in model.mode and not (torch.is_tensor(genomic_features) and genomic_features.is_floating_point()
+                                     and genomic_features.numel() == model.fc_omic[0][0].in_features):
+        return False
+    return True
+
+
+class _MMEvalGroup(_MMGroup):
+    """validate_survival / summary_survival(group=True) with the multimodal head: the forward-only sibling of _MMGroup --
+    the eligible patients of an evaluation pass in the same three buffers (pathology plane, radio planes, omic rows),
+    until one grouped forward-only call (model.forward_group) runs them.  One per pass, as _EvalGroup."""
+
+    def takes(self, model, radio_features, path_features, genomic_features):
+        """Whether the subject can be held: _mm_eval_ok, and each of its bags within that branch's row limit."""
+        if not _mm_eval_ok(model, radio_features, path_features, genomic_features):
+            return False
+        has = lambda k: k in model.mode
+        x_r = radio_features[model.modalities[0]] if has("radio") else None
+        lim_p, lim_r = self.row_limits(model, int(path_features.shape[1]) if has("path") else None,
+                                       int(x_r.shape[1]) if has("radio") else None)
+        return not (has("path") and int(path_features.shape[0]) > lim_p or has("radio") and int(x_r.shape[0]) > lim_r)
+
+    def run(self, model, loss_alpha=None):
+        """As _EvalGroup.run, over the held patients."""
+        if not self.slots:
+            return []
+        want = loss_alpha is not None
+        hz, S, _, _, loss, risk = model.forward_group(self.window(model), torch.cat(self.labels) if want else None,
+                                                      torch.cat(self.cs) if want else None,
+                                                      alpha=loss_alpha if want else 0.0)
+        out = [(slot, hz[g:g + 1], S[g:g + 1], loss[g] if want else None, risk[g:g + 1])
+               for g, slot in enumerate(self.slots)]
+        self.reset()
+        return out
+
+
+def _eval_hold(model, kind, held, limits, batch, slot, device, flush):
+    """Holds the subject `batch` (the loader's tuple) for the pass's grouped call when that call takes it (`kind`:
+    _eval_group_head's answer) and returns its (label, c) on the device; None: the subject runs alone."""
+    radio_features, path_features, genomic_features, label, _, c = batch
+    if kind == "mm":
+        if not held.takes(model, radio_features, path_features, genomic_features):
+            return None
+        label, c = label.to(device), c.to(device)
+        held.add(model, radio_features, path_features, genomic_features.float(), label, c, slot, device, flush)
+        return label, c
+    xs = _eval_group_bags(model, radio_features, path_features, kind)
+    limit = _EvalGroup.limit_of(model, xs, limits) if xs is not None else 0
+    if xs is None or int(xs[0].shape[0]) > limit:
+        return None
+    label, c = label.to(device), c.to(device)
+    held.add(xs, label, c, slot, limit, device, flush)
+    return label, c
+
+
 def validate_survival(cur, epoch, model, loader, n_classes, mode, early_stopping=None, writer=None, loss_fn=None,
                       reg_fn=None, lambda_reg=0., results_dir=None, t_bin=None, group=False):
     """utils/core_utils.py:267-355: eval-mode forward + loss + c-index (early stopping hook kept).
@@ -691,12 +769,15 @@ def validate_survival(cur, epoch, model, loader, n_classes, mode, early_stopping
     model.forward_group call per ops.GROUP_MAX bags or row limit, flushed at the end; each bag's loss and risk land in its
     loader slot, so every logged quantity is in the order of the per-bag loop.  A bag it does not take flushes the group
     and runs alone.  The stock NLLSurvLoss value comes from the grouped call, with the alpha the per-bag branch passes;
-    other losses are called on the bag's slice.  reg_fn(model) is evaluated once per pass (the weights are fixed)."""
+    other losses are called on the bag's slice.  reg_fn(model) is evaluated once per pass (the weights are fixed).
+    A multimodal model's patients (both fusions; _mm_eval_ok) are held the same way in _MMEvalGroup -- a pathology plane,
+    the radio planes and the omic rows -- and run as one MM_MIL_Attention_fc_surv.forward_group call per flush."""
     device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
     model.eval()
     losses, regs, all_risk, all_c, all_t = [], [], [], [], []
     if group:
-        held, reg_once, meta, kind, limits = _EvalGroup(), [], {}, _eval_group_head(model), {}
+        reg_once, meta, kind, limits = [], {}, _eval_group_head(model), {}
+        held = _MMEvalGroup() if kind == "mm" else _EvalGroup()
         kernel_loss = type(loss_fn) is NLLSurvLoss
 
         def flush():      # the held bags' losses / risks land in their loader slots
@@ -712,16 +793,14 @@ def validate_survival(cur, epoch, model, loader, n_classes, mode, early_stopping
                 losses[slot] = loss_g
                 all_risk[slot] = risk_g.reshape(-1)
     with torch.no_grad():
-        for (radio_features, path_features, genomic_features, label, event_time, c) in loader:
+        for batch in loader:
+            radio_features, path_features, genomic_features, label, event_time, c = batch
             if _skip(mode, radio_features, path_features, genomic_features):
                 continue
-            xs = _eval_group_bags(model, radio_features, path_features, kind) if group and kind else None
-            limit = _EvalGroup.limit_of(model, xs, limits) if xs is not None else 0
-            if xs is not None and int(xs[0].shape[0]) <= limit:
-                label, c = label.to(device), c.to(device)
-                slot = len(losses)
-                meta[slot] = (label, c, event_time)
-                held.add(xs, label, c, slot, limit, device, flush)
+            took = _eval_hold(model, kind, held, limits, batch, len(losses), device, flush) if group and kind else None
+            if took is not None:
+                label, c = took
+                meta[len(losses)] = (label, c, event_time)
                 if not reg_once:         # the weights are fixed: one value (one device tensor) for the pass
                     loss_reg = 0 if reg_fn is None else reg_fn(model) * lambda_reg
                     reg_once.append(loss_reg if torch.is_tensor(loss_reg) else torch.tensor(float(loss_reg), device=device))
@@ -789,23 +868,23 @@ def summary_survival(model, loader, n_classes, mode, t_bin=None, loss_fn=None, g
     count = 0
     head_risk = isinstance(loss_fn, (CoxSurvLoss, RankingSurvLoss))
     if group:
-        held, kind, limits = _EvalGroup(), _eval_group_head(model), {}
+        kind, limits = _eval_group_head(model), {}
+        held = _MMEvalGroup() if kind == "mm" else _EvalGroup()
 
         def flush():      # the held bags' risks land in their subjects' slots (the per-bag expressions, on the bag's slice)
             for slot, hz_g, S_g, _, _ in held.run(model):
                 all_risk[slot] = (hz_g if head_risk else -torch.sum(S_g, dim=1)).reshape(-1)
     with torch.no_grad():
-        for (radio_features, path_features, genomic_features, label, event_time, c) in loader:
+        for batch in loader:
+            radio_features, path_features, genomic_features, label, event_time, c = batch
             n = len(label)
             sid = ids[count:count + n] if ids is not None else list(range(count, count + n))
             count += n
             if _skip(mode, radio_features, path_features, genomic_features):
                 continue
-            xs = _eval_group_bags(model, radio_features, path_features, kind) if group and kind else None
-            limit = _EvalGroup.limit_of(model, xs, limits) if xs is not None else 0
-            if xs is not None and int(xs[0].shape[0]) <= limit:
-                label, c = label.to(device), c.to(device)
-                held.add(xs, label, c, len(all_risk), limit, device, flush)
+            took = _eval_hold(model, kind, held, limits, batch, len(all_risk), device, flush) if group and kind else None
+            if took is not None:
+                label, c = took
                 all_ids.extend(sid)
                 all_risk.append(None)
                 all_c.append(c.reshape(-1))
