@@ -418,7 +418,9 @@ int mmf_attn_net_backward(const mmf_amil_desc* desc, const float* x, void* works
  * Dense layer on MFMA:  y = dropout(act(concat_k(x_0..x_{nseg-1}) . W^T + bias))
  *   replaces torch.cat + nn.Linear of model_attention_mil_radio.py:80-82 (reduce_dim; the modality
  *   bags are never concatenated in memory) and the instance projections generally.
- *   x_segs: HOST array of nseg (<= 4) device pointers, each [M x kseg]; K = nseg*kseg; K % 32 == 0.
+ *   x_segs: HOST array of nseg (<= 4) device pointers, each [M x kseg]; K = nseg*kseg; K % 32 == 0 (and kseg % 32 == 0
+ *   when nseg > 1); N % 4 == 0 (the epilogue stores y and loads the bias four columns at a time): MMF_ERR_SHAPE
+ *   otherwise, before any launch.  Every x segment, W, y and a non-null bias are 16-byte aligned: MMF_ERR_ALIGN otherwise.
  *   workspace / sync (both optional, may be NULL): scratch for the K-split plan of short grids (a 512-row radiology bag
  *   against the 4096-wide reduce_dim is 128 output tiles with a 128-chunk K loop each: split four ways -- one modality
  *   segment per workgroup -- it fills the chip) and the tick words it needs, under mmf_amil_desc::sync's contract.
@@ -431,7 +433,8 @@ int mmf_linear_forward(const float* const* x_segs, int32_t nseg, int32_t kseg, i
 
 size_t mmf_linear_backward_workspace_bytes(int64_t M, int32_t N, int32_t K);
 /* dy [M x N] (gradient w.r.t. the pre-activation output) -> dW [N x K], db [N] (may be NULL),
- * dx [M x K] single buffer (may be NULL; only nseg == 1). */
+ * dx [M x K] single buffer (may be NULL; only nseg == 1).  N % 4 == 0, kseg % 4 == 0, and N % 32 == 0 when dx is asked for:
+ * MMF_ERR_SHAPE otherwise, before any launch (nothing is written). */
 int mmf_linear_backward(const float* dy, const float* const* x_segs, int32_t nseg, int32_t kseg, int64_t M,
                         const float* W, int32_t N, float* dW, float* db, float* dx,
                         void* workspace, size_t workspace_bytes, void* stream);

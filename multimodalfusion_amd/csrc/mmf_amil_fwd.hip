@@ -843,6 +843,7 @@ size_t linear_ksplit_floats(int64_t M, int N, int K, int nseg, int kseg) {
 template <bool SEG>
 static int launch_linear_impl(LinearParams p, hipStream_t st) {
   if (p.K % KC != 0 || (p.nseg > 1 && p.kseg % KC != 0)) return MMF_ERR_SHAPE;
+  if (p.N % 4 != 0) return MMF_ERR_SHAPE;     // linear_epilogue: float4 stores of y and loads of the bias, never across the edge
   if (p.ldx % 4 != 0) return MMF_ERR_ALIGN;
   if (p.M <= 0) return MMF_OK;
   const bool can_split = p.split && p.K % (4 * SKC) == 0 && p.nseg == 1;

@@ -473,7 +473,7 @@ const char* mmf_strerror(int code) {
   switch (code) {
     case MMF_OK: return "ok";
     case MMF_ERR_ARG: return "invalid argument (null pointer or bad flag)";
-    case MMF_ERR_SHAPE: return "unsupported shape (need L,H % 32 == 0, H in {256,512,1024}, D % 128 == 0, K % 32 == 0, every operand < 2 GiB)";
+    case MMF_ERR_SHAPE: return "unsupported shape (need L,H % 32 == 0, H in {256,512,1024}, D % 128 == 0, K % 32 == 0, N % 4 == 0 of a dense layer, every operand < 2 GiB)";
     case MMF_ERR_ALIGN: return "pointer or leading dimension not 16-byte aligned";
     case MMF_ERR_WORKSPACE: return "workspace too small (see mmf_*_workspace_bytes)";
     case MMF_ERR_LAUNCH: return "HIP launch failed";
@@ -1535,7 +1535,7 @@ int mmf_linear_forward(const float* const* x_segs, int32_t nseg, int32_t kseg, i
     if (!aligned16(x_segs[i])) return MMF_ERR_ALIGN;
     lp.x[i] = x_segs[i];
   }
-  if (!aligned16(W)) return MMF_ERR_ALIGN;
+  if (!aligned16(W) || !aligned16(y) || (bias && !aligned16(bias))) return MMF_ERR_ALIGN;   // y, bias: float4 in the epilogue
   lp.nseg = nseg; lp.kseg = kseg; lp.ldx = kseg;
   lp.w = W; lp.bias = bias; lp.y = y; lp.M = M; lp.N = N; lp.K = nseg * kseg;
   lp.act = act; lp.drop_p = drop_p; lp.drop_key = drop_key(drop_seed, drop_site); lp.seed_dev = seed_dev;
@@ -1576,6 +1576,7 @@ int mmf_linear_backward(const float* dy, const float* const* x_segs, int32_t nse
   if (dx && (nseg != 1 || !W)) return MMF_ERR_ARG;
   const int K = nseg * kseg;
   if (N % 4 != 0 || kseg % 4 != 0) return MMF_ERR_SHAPE;
+  if (dx && N % KC != 0) return MMF_ERR_SHAPE;           // dx = dy . W contracts over N in 32-chunks (launch_nn); every refusal comes before the first launch
   if (M * (int64_t)(N > kseg ? N : kseg) * 4 >= (int64_t)1 << 31 || (int64_t)N * K * 4 >= (int64_t)1 << 31) return MMF_ERR_SHAPE;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int splits = linear_bwd_splits(M, N, K);
@@ -1603,7 +1604,6 @@ int mmf_linear_backward(const float* dy, const float* const* x_segs, int32_t nse
     if (int e = rl.launch(0, st)) return e;
   }
   if (dx) {
-    if (N % KC != 0) return MMF_ERR_SHAPE;
     NnParams np{};
     np.A = dy; np.lda = N; np.B = W; np.ldb = K; np.C = dx; np.ldc = K; np.M = M; np.N = K; np.K = N;
     return launch_nn(np, st);

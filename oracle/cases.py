@@ -56,10 +56,10 @@ def shape_bag(x, kind):
 def path_inputs(m):
     sd = gen.path_state_dict(seed=m["seed"], gated=m["gated"], size=m["size"], n_classes=m["K"],
                              dropout=m["dropout"], bias_std=m["bias_std"])
-    x = shape_bag(gen.bag(m["x_seed"], m["N"]), m.get("x_kind"))
+    L, H, D = gen.stack_dims(m["size"])       # a size name, or explicit (L, H, D)
+    x = shape_bag(gen.bag(m["x_seed"], m["N"], dim=L), m.get("x_kind"))
     masks = None
     if m["train"]:
-        H, D = gen.SIZE_DICT[m["size"]][1:]
         masks = amil_masks(m["mask_seed"], m["N"], H, D, m["gated"], m["dropout"])
     return sd, x, masks
 

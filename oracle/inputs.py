@@ -85,6 +85,15 @@ SIZE_DICT_MM = {"small": [1024, 256, 256], "big": [1024, 256, 384]}
 SIZE_DICT_OMIC = {"small": [256, 256], "big": [1024, 256]}
 
 
+def stack_dims(size):
+    """[L, H, D] of a pathology stack: a size name of SIZE_DICT, or explicit (L, H, D) -- the widths the C ABI admits
+    beyond the two shipped heads (tests/abi_shapes.py)."""
+    if isinstance(size, str):
+        return list(SIZE_DICT[size])
+    L, H, D = (int(v) for v in size)
+    return [L, H, D]
+
+
 def _attn_stack(sd, prefix, size, gated, dropout, seed, stream, init, bias_std):
     """Sequential(Linear, ReLU, Dropout, Attn_Net[_Gated]) -- key names per Appendix B."""
     L, H, D = size
@@ -103,7 +112,7 @@ def _attn_stack(sd, prefix, size, gated, dropout, seed, stream, init, bias_std):
 
 def path_state_dict(seed=1, gated=True, size="small", n_classes=4, dropout=False, bias_std=0.0):
     sd = OrderedDict()
-    sz = SIZE_DICT[size]
+    sz = stack_dims(size)
     st = _attn_stack(sd, "attention_net_WSI", sz, gated, dropout, seed, 0, "xavier", bias_std)
     _linear(sd, "classifier", n_classes, sz[1], seed, st, "xavier", bias_std)
     return sd
