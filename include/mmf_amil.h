@@ -387,6 +387,56 @@ int mmf_surv_head_infer_group(const float* const* segs, const int32_t* widths, i
                               const mmf_surv_head* head, const mmf_nll_target* target, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Grouped training step of the tensor fusion: the XlinearFusion block (models/model_modules.py:156-178, gate = 1,
+ *   skip = 1) and classifier[0] + ReLU + Dropout (models/model_mm_attention_mil.py:182-188), forward and backward, for
+ *   the G patients of one accumulation window -- what the reference computes once per patient under autograd.  The
+ *   stacks and the omic branch write their embeddings with the existing grouped calls (mmf_amil_group_forward,
+ *   mmf_radio_group_forward, mmf_dense_forward_rows, all through a leading dimension); the hazard head on hid is
+ *   mmf_surv_head_nll_step_group with classifier[3].
+ *
+ * x2 [G x K2], K2 = mmhid1 + m * dim, dense, 16-byte aligned: encoder2's input matrix.  The caller puts v_i of patient
+ *   g at x2[g][mmhid1 + i * dim ..] (the branches write there: torch.cat is never a launch); the forward fills the first
+ *   mmhid1 columns with encoder1's output.  x2, MM, hid and the workspace must reach the backward unmodified.
+ * Dropout: patient g draws its own masks -- site i for o_i, 8 for the product, 9 encoder1, 10 encoder2 (drop_p) and 11
+ *   classifier[0] (cls_drop_p); within a site the mask index is the column index, as a B = 1 call draws it.  row_base:
+ *   DEVICE [G], row_base[g] = mmf_dropout_row_base(fusion seed of patient g); seed_dev as everywhere.  Both
+ *   probabilities 0: eval mode, MM and hid are those of mmf_xfusion_infer_group bit for bit.
+ * mmf_xfusion_group_forward, FOUR launches: the gating stage per patient (keeps h, z, gm and the dropped o, and hashes the
+ *   post-fusion mask once per patient and element into packed keep bits); the Kronecker product fused into encoder1 (the
+ *   product is never written, a row of encoder1's weight is fetched once per window, the keep bits are staged in LDS);
+ *   encoder2; classifier[0].  MM [G x mmhid2], hid [G x nhid].
+ * mmf_xfusion_group_backward, from dhid (row g at dhid + g * lddhid: mmf_surv_head_nll_step_group's dfeat): classifier[0]
+ *   and encoder2 through the dense backward on B = G rows; d of the product [G x (sdim + 1)^m] in one pass over encoder1's
+ *   weight; encoder1's weight gradient, written once, with the product rebuilt from [o, 1] and the keep bits (no
+ *   [G x mmhid1 x (sdim + 1)^m] intermediate); the gating stage per patient; the gating weights, one thread per element.
+ *   dx2 [G x K2]: columns mmhid1 + i * dim .. hold dv_i, skip connection included (the first mmhid1 columns hold d e1).
+ *   grads: sums over the patients in patient order, overwritten, or added to when accumulate != 0.
+ * No float atomics, no workgroup waits for another, calls are deterministic; what patient g gets (MM, hid, dx2 rows)
+ *   depends neither on G nor on its position.  The calls allocate nothing and keep no state.
+ * Returns, before any launch: MMF_ERR_SHAPE for m outside 2..3, sdim != 16, dim % 4 != 0, mmhid1 % 4 != 0, mmhid1 + m * dim,
+ *   mmhid2 or nhid > 1536, G outside 1..MMF_GROUP_MAX, lddhid < nhid; MMF_ERR_ARG for a null pointer or a probability
+ *   outside [0, 1); MMF_ERR_ALIGN for a misaligned x2, Wh_i, Wz_i or workspace; MMF_ERR_WORKSPACE.
+ * mmf_xfusion_group_workspace_bytes: the workspace of the pair, or 0 for arguments out of range.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct mmf_xfusion_grads {     /* mmf_xfusion_weights' order */
+  float *dWh[3], *dbh[3];
+  float *dWz[3], *dbz[3];
+  float *dWo[3], *dbo[3];
+  float *dWe1, *dbe1;
+  float *dWe2, *dbe2;
+  float *dWc0, *dbc0;
+} mmf_xfusion_grads;
+size_t mmf_xfusion_group_workspace_bytes(int32_t m, int32_t dim, int32_t sdim, int32_t mmhid1, int32_t mmhid2,
+                                         int32_t nhid, int32_t G);
+int mmf_xfusion_group_forward(const mmf_xfusion_weights* w, float* x2, int32_t G, float drop_p, float cls_drop_p,
+                              const uint32_t* row_base, const uint32_t* seed_dev, void* workspace, size_t workspace_bytes,
+                              float* MM, float* hid, void* stream);
+int mmf_xfusion_group_backward(const mmf_xfusion_weights* w, const float* x2, int32_t G, float drop_p, float cls_drop_p,
+                               const uint32_t* row_base, const uint32_t* seed_dev, const float* MM, const float* hid,
+                               const float* dhid, int32_t lddhid, void* workspace, size_t workspace_bytes, float* dx2,
+                               const mmf_xfusion_grads* grads, int32_t accumulate, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Forward-only variants for the inference consumers of the path -- embedding export
  * (pre_trained_feature.py:116-162: model(..., return_features=True) under no_grad), per-patient inference and
  * attention heat-map scoring (utils/heatmap_utils.py:111-150,249-275: A_raw per bag / per 512-patch batch).

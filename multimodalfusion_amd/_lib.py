@@ -90,6 +90,12 @@ class XFusionWeights(C.Structure):
         (n, C.c_void_p) for n in ("We1", "be1", "We2", "be2", "Wc0", "bc0")]
 
 
+class XFusionGrads(C.Structure):
+    """struct mmf_xfusion_grads (include/mmf_amil.h)."""
+    _fields_ = [(n, C.c_void_p * 3) for n in ("dWh", "dbh", "dWz", "dbz", "dWo", "dbo")] + [
+        (n, C.c_void_p) for n in ("dWe1", "dbe1", "dWe2", "dbe2", "dWc0", "dbc0")]
+
+
 # name -> (restype, argtypes): every symbol include/mmf_amil.h declares
 SYMBOLS = {
     "mmf_strerror": (C.c_char_p, [C.c_int]),
@@ -155,6 +161,14 @@ SYMBOLS = {
     "mmf_xfusion_group_infer_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "mmf_xfusion_infer_group": (C.c_int, [C.POINTER(XFusionWeights), C.POINTER(C.c_void_p), C.c_int32, C.c_void_p,
                                           C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mmf_xfusion_group_workspace_bytes": (C.c_size_t, [C.c_int32] * 7),
+    "mmf_xfusion_group_forward": (C.c_int, [C.POINTER(XFusionWeights), C.c_void_p, C.c_int32, C.c_float, C.c_float,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                            C.c_void_p]),
+    "mmf_xfusion_group_backward": (C.c_int, [C.POINTER(XFusionWeights), C.c_void_p, C.c_int32, C.c_float, C.c_float,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                             C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(XFusionGrads), C.c_int32,
+                                             C.c_void_p]),
     "mmf_surv_head_infer_group": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.c_int32, C.c_int32,
                                             C.POINTER(SurvHead), C.POINTER(NllTarget), C.c_void_p]),
     "mmf_amil_infer_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),

@@ -1430,6 +1430,147 @@ int mmf_xfusion_infer_group(const mmf_xfusion_weights* w, const float* const* v,
   return launch_dense_segs_group(c0, st);
 }
 
+// ---- grouped training step of the tensor fusion: the forward and the backward of the fusion tail of a window ----------
+static DropSpec make_drop(int kind, float p, uint32_t seed, uint32_t site, const uint32_t* seed_dev);
+namespace mmf {
+// What the forward keeps for the backward (o dropped, h, z, gm, the post-fusion keep bits) and the backward's own buffers.
+struct XFusionTrainWs {
+  float *o, *h, *z, *gm, *dpo, *dz, *dph, *dkr, *dMM, *dpre, *tmpW, *tmpb;
+  uint32_t* bits;
+  size_t bytes;
+};
+static int xfusion_elems(int m) { return m == 3 ? 17 * 17 * 17 : 17 * 17; }
+static XFusionTrainWs carve_xfusion_train(Carver& c, int m, int dim, int mmhid1, int mmhid2, int nhid, int G) {
+  XFusionTrainWs w{};
+  const size_t gate = (size_t)G * m * 16, K2 = (size_t)mmhid1 + (size_t)m * dim;
+  w.o = c.take<float>(gate); w.h = c.take<float>(gate); w.z = c.take<float>(gate); w.gm = c.take<float>(gate);
+  w.bits = c.take<uint32_t>((size_t)G * xfusion_bit_words(m));
+  w.dpo = c.take<float>(gate); w.dz = c.take<float>(gate); w.dph = c.take<float>(gate);
+  w.dkr = c.take<float>((size_t)G * xfusion_elems(m));
+  w.dMM = c.take<float>((size_t)G * mmhid2);
+  w.dpre = c.take<float>((size_t)G * (mmhid2 > nhid ? mmhid2 : nhid));
+  const size_t w2 = (size_t)mmhid2 * K2, w0 = (size_t)nhid * mmhid2;      // accumulate: the dense backward's fresh dW, db
+  w.tmpW = c.take<float>(w2 > w0 ? w2 : w0);
+  w.tmpb = c.take<float>(mmhid2 > nhid ? mmhid2 : nhid);
+  w.bytes = c.off;
+  return w;
+}
+static int xfusion_train_shape(const mmf_xfusion_weights* w, int G) {
+  if (!xfusion_shape_ok(w->m, w->sdim, w->mmhid1, G)) return MMF_ERR_SHAPE;
+  if (w->dim < 4 || w->dim % 4 != 0 || w->mmhid1 % 4 != 0 || w->mmhid2 < 1 || w->nhid < 1) return MMF_ERR_SHAPE;
+  if (w->mmhid1 + w->m * w->dim > 64 * DENSE_SEGS_MAXC || w->mmhid2 > 64 * DENSE_SEGS_MAXC || w->nhid > 64 * DENSE_SEGS_MAXC)
+    return MMF_ERR_SHAPE;
+  return MMF_OK;
+}
+static int xfusion_train_weights(const mmf_xfusion_weights* w) {
+  if (!w->We1 || !w->be1 || !w->We2 || !w->be2 || !w->Wc0 || !w->bc0) return MMF_ERR_ARG;
+  for (int i = 0; i < w->m; ++i)
+    if (!w->Wh[i] || !w->bh[i] || !w->Wz[i] || !w->bz[i] || !w->Wo[i] || !w->bo[i]) return MMF_ERR_ARG;
+  for (int i = 0; i < w->m; ++i)
+    if (!aligned16(w->Wh[i]) || !aligned16(w->Wz[i])) return MMF_ERR_ALIGN;     // float4 loads
+  return MMF_OK;
+}
+static XTrainParams xtrain(float p, uint32_t site, const uint32_t* row_base, const uint32_t* seed_dev) {
+  XTrainParams t{};
+  t.p = p; t.key = drop_key(0, site); t.dev = seed_dev; t.row_base = row_base;
+  return t;
+}
+}  // namespace mmf
+
+size_t mmf_xfusion_group_workspace_bytes(int32_t m, int32_t dim, int32_t sdim, int32_t mmhid1, int32_t mmhid2,
+                                         int32_t nhid, int32_t G) {
+  mmf_xfusion_weights w{};
+  w.m = m; w.dim = dim; w.sdim = sdim; w.mmhid1 = mmhid1; w.mmhid2 = mmhid2; w.nhid = nhid;
+  if (xfusion_train_shape(&w, G)) return 0;
+  Carver c;
+  return carve_xfusion_train(c, m, dim, mmhid1, mmhid2, nhid, G).bytes;
+}
+
+int mmf_xfusion_group_forward(const mmf_xfusion_weights* w, float* x2, int32_t G, float drop_p, float cls_drop_p,
+                              const uint32_t* row_base, const uint32_t* seed_dev, void* workspace, size_t workspace_bytes,
+                              float* MM, float* hid, void* stream) {
+  if (!w || !x2 || !row_base || !workspace || !MM || !hid) return MMF_ERR_ARG;
+  if (!(drop_p >= 0.f && drop_p < 1.f) || !(cls_drop_p >= 0.f && cls_drop_p < 1.f)) return MMF_ERR_ARG;
+  if (int e = xfusion_train_shape(w, G)) return e;
+  if (int e = xfusion_train_weights(w)) return e;
+  if (!aligned16(x2) || !aligned16(workspace)) return MMF_ERR_ALIGN;
+  Carver c(workspace);
+  const XFusionTrainWs ws = carve_xfusion_train(c, w->m, w->dim, w->mmhid1, w->mmhid2, w->nhid, G);
+  if (ws.bytes > workspace_bytes) return MMF_ERR_WORKSPACE;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const int K2 = w->mmhid1 + w->m * w->dim;
+  XGateGroupParams gp{};
+  gp.m = w->m; gp.G = G; gp.dim = w->dim; gp.sdim = w->sdim;
+  for (int i = 0; i < w->m; ++i) {
+    gp.v[i] = x2 + w->mmhid1 + i * w->dim; gp.Wh[i] = w->Wh[i]; gp.bh[i] = w->bh[i]; gp.Wz[i] = w->Wz[i];
+    gp.bz[i] = w->bz[i]; gp.Wo[i] = w->Wo[i]; gp.bo[i] = w->bo[i];
+  }
+  gp.o = ws.o;
+  XTrainParams tg = xtrain(drop_p, 0, row_base, seed_dev);
+  tg.key8 = drop_key(0, 8); tg.ld = K2; tg.h = ws.h; tg.z = ws.z; tg.gm = ws.gm; tg.bits = ws.bits;
+  if (int e = launch_xgate_group_train(gp, tg, st)) return e;
+  KronDenseGroupParams kp{w->m, G, w->mmhid1, ws.o, w->We1, w->be1, x2};      // e1 into the first columns of x2
+  XTrainParams tk = xtrain(drop_p, 9, row_base, seed_dev);
+  tk.ld = K2; tk.bits = ws.bits;
+  if (int e = launch_kron_dense_group_train(kp, tk, st)) return e;
+  DenseSegsParams e2{};                 // encoder2 on the rows of x2 = [e1 | v_0 | v_1 (| v_2)]
+  e2.nseg = 1; e2.G = G; e2.N = w->mmhid2; e2.K = K2;
+  e2.x[0] = x2; e2.width[0] = K2;
+  e2.W = w->We2; e2.bias = w->be2; e2.y = MM;
+  if (int e = launch_dense_segs_group_train(e2, xtrain(drop_p, 10, row_base, seed_dev), st)) return e;
+  DenseSegsParams c0{};                 // classifier[0] + ReLU + Dropout
+  c0.nseg = 1; c0.G = G; c0.N = w->nhid; c0.K = w->mmhid2;
+  c0.x[0] = MM; c0.width[0] = w->mmhid2;
+  c0.W = w->Wc0; c0.bias = w->bc0; c0.y = hid;
+  return launch_dense_segs_group_train(c0, xtrain(cls_drop_p, 11, row_base, seed_dev), st);
+}
+
+int mmf_xfusion_group_backward(const mmf_xfusion_weights* w, const float* x2, int32_t G, float drop_p, float cls_drop_p,
+                               const uint32_t* row_base, const uint32_t* seed_dev, const float* MM, const float* hid,
+                               const float* dhid, int32_t lddhid, void* workspace, size_t workspace_bytes, float* dx2,
+                               const mmf_xfusion_grads* grads, int32_t accumulate, void* stream) {
+  if (!w || !x2 || !row_base || !MM || !hid || !dhid || !workspace || !dx2 || !grads) return MMF_ERR_ARG;
+  if (!(drop_p >= 0.f && drop_p < 1.f) || !(cls_drop_p >= 0.f && cls_drop_p < 1.f)) return MMF_ERR_ARG;
+  if (int e = xfusion_train_shape(w, G)) return e;
+  if (lddhid < w->nhid) return MMF_ERR_SHAPE;
+  if (int e = xfusion_train_weights(w)) return e;
+  const mmf_xfusion_grads* g = grads;
+  if (!g->dWe1 || !g->dbe1 || !g->dWe2 || !g->dbe2 || !g->dWc0 || !g->dbc0) return MMF_ERR_ARG;
+  for (int i = 0; i < w->m; ++i)
+    if (!g->dWh[i] || !g->dbh[i] || !g->dWz[i] || !g->dbz[i] || !g->dWo[i] || !g->dbo[i]) return MMF_ERR_ARG;
+  if (!aligned16(x2) || !aligned16(workspace)) return MMF_ERR_ALIGN;
+  Carver c(workspace);
+  const XFusionTrainWs ws = carve_xfusion_train(c, w->m, w->dim, w->mmhid1, w->mmhid2, w->nhid, G);
+  if (ws.bytes > workspace_bytes) return MMF_ERR_WORKSPACE;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const int K2 = w->mmhid1 + w->m * w->dim;
+  // classifier[0] and encoder2: the dense backward on B = G rows (accumulate: into the workspace, then added)
+  DenseBwdParams c0{dhid, hid, MM, w->Wc0, ws.dpre, ws.dMM, accumulate ? ws.tmpW : g->dWc0, accumulate ? ws.tmpb : g->dbc0,
+                    G, w->mmhid2, w->nhid, ACT_RELU, make_drop(1, cls_drop_p, 0, 11, seed_dev), row_base, w->nhid, lddhid};
+  if (int e = launch_dense_bwd(c0, st)) return e;
+  if (accumulate) {
+    if (int e = launch_add_into(g->dWc0, ws.tmpW, (int64_t)w->nhid * w->mmhid2, st)) return e;
+    if (int e = launch_add_into(g->dbc0, ws.tmpb, w->nhid, st)) return e;
+  }
+  DenseBwdParams e2{ws.dMM, MM, x2, w->We2, ws.dpre, dx2, accumulate ? ws.tmpW : g->dWe2, accumulate ? ws.tmpb : g->dbe2,
+                    G, K2, w->mmhid2, ACT_RELU, make_drop(1, drop_p, 0, 10, seed_dev), row_base, w->mmhid2, w->mmhid2};
+  if (int e = launch_dense_bwd(e2, st)) return e;
+  if (accumulate) {
+    if (int e = launch_add_into(g->dWe2, ws.tmpW, (int64_t)w->mmhid2 * K2, st)) return e;
+    if (int e = launch_add_into(g->dbe2, ws.tmpb, w->mmhid2, st)) return e;
+  }
+  XFusionBwdParams p{};
+  p.m = w->m; p.G = G; p.dim = w->dim; p.N1 = w->mmhid1; p.K2 = K2; p.p = drop_p; p.accumulate = accumulate;
+  p.x2 = x2; p.dx2 = dx2; p.o = ws.o; p.h = ws.h; p.z = ws.z; p.gm = ws.gm; p.bits = ws.bits; p.dkr = ws.dkr;
+  p.dpo = ws.dpo; p.dz = ws.dz; p.dph = ws.dph; p.We1 = w->We1; p.dWe1 = g->dWe1; p.dbe1 = g->dbe1;
+  for (int i = 0; i < w->m; ++i) {
+    p.Wh[i] = w->Wh[i]; p.Wz[i] = w->Wz[i]; p.Wo[i] = w->Wo[i];
+    p.dWh[i] = g->dWh[i]; p.dbh[i] = g->dbh[i]; p.dWz[i] = g->dWz[i]; p.dbz[i] = g->dbz[i];
+    p.dWo[i] = g->dWo[i]; p.dbo[i] = g->dbo[i];
+  }
+  return launch_xfusion_group_bwd(p, st);
+}
+
 // ---- standalone attention scorer: Attn_Net / Attn_Net_Gated .forward(x) -> (A, x) ------------------------------
 namespace mmf {
 struct AttnWs {

@@ -94,6 +94,46 @@ constexpr int DENSE_SEGS_MAXC = 24;
 int launch_xgate_group(XGateGroupParams p, hipStream_t st);
 int launch_kron_dense_group(KronDenseGroupParams p, hipStream_t st);
 int launch_dense_segs_group(DenseSegsParams p, hipStream_t st);
+
+// ---- training step of the same window (mmf_xfusion_group_forward / mmf_xfusion_group_backward) ------------------------
+// What the TRAIN instantiations of the three kernels above take beside their parameter block (a trailing kernel argument:
+// the forward-only instantiations keep their argument offsets).  Patient g's mask of a site is that of the site's seed-0
+// key at index row_base[g] + column (DenseParams::row_base); p == 0 (eval mode) hashes nothing.
+struct XTrainParams {
+  float p;                      // dropout probability of the launch's site(s)
+  uint32_t key;                 // seed-0 key: xgate site 0 (site i adds i * 0x632BE5AB), kron_dense site 9, dense_segs its own
+  uint32_t key8;                // xgate: seed-0 key of the post-fusion site 8
+  int ld;                       // xgate: row stride of v_i; kron_dense: row stride of y
+  const uint32_t* dev;          // optional device seed word added to the keys
+  const uint32_t* row_base;     // [G]
+  float *h, *z, *gm;            // xgate keeps these for its backward: [G x m x sdim]
+  uint32_t* bits;               // post-fusion keep bits [G x xfusion_bit_words(m)]: xgate writes, kron_dense reads
+};
+constexpr int xfusion_bit_words(int m) { return ((m == 3 ? 17 * 17 * 17 : 17 * 17) + 63) / 64 * 2; }
+int launch_xgate_group_train(XGateGroupParams p, XTrainParams t, hipStream_t st);
+int launch_kron_dense_group_train(KronDenseGroupParams p, XTrainParams t, hipStream_t st);
+int launch_dense_segs_group_train(DenseSegsParams p, XTrainParams t, hipStream_t st);
+
+// The backward of the fusion tail in front of encoder2 (mmf_xfusion_group.hip).  x2 [G x K2] is encoder2's input row
+// [e1 (dropped) | v_0 | v_1 (| v_2)], dx2 its gradient as encoder2's backward left it: the kernels read d e1 from its first
+// N1 columns and ADD the gating stage's dv_i to the others (one thread per element).
+struct XFusionBwdParams {
+  int m, G, dim, N1, K2;        // sdim = 16; N1 = mmhid1; K2 = N1 + m * dim
+  float p;                      // dropout probability of sites 0 .. 10 (0: eval mode)
+  int accumulate;
+  const float* x2;
+  float* dx2;
+  const float *o, *h, *z, *gm;  // [G x m x 16], o dropped
+  const uint32_t* bits;         // [G x xfusion_bit_words(m)]
+  float* dkr;                   // [G x 17^m]: d of the dropped product
+  float *dpo, *dz, *dph;        // [G x m x 16]: the gating stage's pre-activation gradients, for the weight gradients
+  const float* We1;
+  const float *Wh[3], *Wz[3], *Wo[3];
+  float *dWe1, *dbe1;
+  float *dWh[3], *dbh[3], *dWz[3], *dbz[3], *dWo[3], *dbo[3];
+};
+int launch_xfusion_group_bwd(XFusionBwdParams p, hipStream_t st);
+int launch_add_into(float* out, const float* in, int64_t n, hipStream_t st);
 }  // namespace mmf
 
 // ---- stage-2 (embedding-level) building blocks: SURVEY.md 8f row N3 --------------------------------------------

@@ -361,7 +361,11 @@ constexpr int XG_MAX = 3 * 16;         // m * sdim values of one patient kept in
 
 // Gating stage, one workgroup per patient: xreduce_fwd_kernel's arithmetic for B = 1 (h, z, the gate product, o), so the
 // B <= 8 cap of that kernel's LDS arrays does not apply; only o_g leaves the kernel.
-__global__ __launch_bounds__(XR_NT) void xgate_group_kernel(XGateGroupParams p) {
+// TRAIN (mmf_xfusion_group_forward): v_i are columns of a wider matrix (t.ld), o_g is dropped under patient g's masks of
+// the sites i, h / z / gm are kept for the backward, and the post-fusion mask (site 8) is hashed ONCE per patient and
+// element into packed keep bits, which the encoder1 launch and the backward read.
+template <bool TRAIN>
+__global__ __launch_bounds__(XR_NT) void xgate_group_kernel(XGateGroupParams p, XTrainParams t) {
   __shared__ float sh_h[XG_MAX], sh_z[XG_MAX], sh_gm[XG_MAX];
   const int g = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   constexpr int NW = XR_NT / 64;
@@ -372,10 +376,10 @@ __global__ __launch_bounds__(XR_NT) void xgate_group_kernel(XGateGroupParams p) 
     const int i = q / S, j = q % S;
     float acc = 0.f;
     if (!is_z) {
-      acc = wave_dot(p.v[i] + (size_t)g * p.dim, p.Wh[i] + (size_t)j * p.dim, p.dim, lane);
+      acc = wave_dot(p.v[i] + (size_t)g * (TRAIN ? t.ld : p.dim), p.Wh[i] + (size_t)j * p.dim, p.dim, lane);
     } else {
-      for (int t = 0; t < p.m; ++t)                  // v_cat = [v_0 | v_1 | ...]
-        acc += wave_dot(p.v[t] + (size_t)g * p.dim, p.Wz[i] + (size_t)j * p.m * p.dim + (size_t)t * p.dim, p.dim, lane);
+      for (int u = 0; u < p.m; ++u)                  // v_cat = [v_0 | v_1 | ...]
+        acc += wave_dot(p.v[u] + (size_t)g * (TRAIN ? t.ld : p.dim), p.Wz[i] + (size_t)j * p.m * p.dim + (size_t)u * p.dim, p.dim, lane);
     }
     const float r = wave_sum(acc);
     if (lane == 0) {
@@ -390,8 +394,32 @@ __global__ __launch_bounds__(XR_NT) void xgate_group_kernel(XGateGroupParams p) 
     const int i = tid / S, j = tid % S;
     float acc = p.bo[i][j];
 #pragma unroll 16
-    for (int t = 0; t < S; ++t) acc += sh_gm[i * S + t] * p.Wo[i][j * S + t];
-    p.o[(size_t)g * total + tid] = fmaxf(acc, 0.f);
+    for (int u = 0; u < S; ++u) acc += sh_gm[i * S + u] * p.Wo[i][j * S + u];
+    if (TRAIN) {
+      const size_t at = (size_t)g * total + tid;
+      t.h[at] = sh_h[tid]; t.z[at] = sh_z[tid]; t.gm[at] = sh_gm[tid];
+      float ov = fmaxf(acc, 0.f);
+      if (t.p > 0.f) {                               // site i, index j: the B = 1 mask of xreduce_fwd_kernel
+        const uint32_t key = t.key + 0x632BE5ABu * (uint32_t)i + (t.dev ? *t.dev : 0u);
+        ov = keep(key, t.row_base[g] + (uint32_t)j, drop_threshold(t.p)) ? ov / (1.0f - t.p) : 0.f;
+      }
+      p.o[at] = ov;
+    } else {
+      p.o[(size_t)g * total + tid] = fmaxf(acc, 0.f);
+    }
+  }
+  if (TRAIN) {                                       // keep bits of the (S + 1)^m product: a wave's ballot is two words
+    const int E = p.m == 3 ? (S + 1) * (S + 1) * (S + 1) : (S + 1) * (S + 1), nw = (E + 63) / 64 * 2;
+    const uint32_t key = t.key8 + (t.dev ? *t.dev : 0u), thr = drop_threshold(t.p), base = t.row_base[g];
+    for (int e0 = wave * 64; e0 < nw * 32; e0 += XR_NT) {
+      const int e = e0 + lane;
+      const bool k = e < E && (t.p > 0.f ? keep(key, base + (uint32_t)e, thr) : true);
+      const unsigned long long b = __ballot(k);
+      if (lane == 0) {
+        t.bits[(size_t)g * nw + e0 / 32] = (uint32_t)b;
+        t.bits[(size_t)g * nw + e0 / 32 + 1] = (uint32_t)(b >> 32);
+      }
+    }
   }
 }
 
@@ -403,14 +431,24 @@ __global__ __launch_bounds__(XR_NT) void xgate_group_kernel(XGateGroupParams p) 
 // o0'[i] (o1'[j]) of q, summed over the lane's q in order, then over the wave.  A row is fetched from memory once per
 // window (and again from L2 by the other shares), not once per patient.
 constexpr int KD_S1 = 17;
-template <int M>
-__global__ __launch_bounds__(256) void kron_dense_group_kernel(KronDenseGroupParams p, int gsplit) {
+// TRAIN (mmf_xfusion_group_forward): the product is dropped under the keep bits the gating launch wrote (staged in LDS:
+// G x 154 words at m = 3; a lane's 17 consecutive elements are 17 consecutive bits), scaled once per sum, and the output
+// is dropped under patient g's mask of site 9 and written through a leading dimension (encoder2's input matrix).
+template <int M, bool TRAIN>
+__global__ __launch_bounds__(256) void kron_dense_group_kernel(KronDenseGroupParams p, int gsplit, XTrainParams t) {
   constexpr int Q = M == 3 ? KD_S1 * KD_S1 : KD_S1, NQ = (Q + 63) / 64, KK = Q * KD_S1;
+  constexpr int NWB = xfusion_bit_words(M);
   __shared__ float so[GROUP_MAX * M * KD_S1];         // o' = [o, 1] of every patient and modality
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   for (int e = tid; e < p.G * M * KD_S1; e += 256) {
     const int r = e / KD_S1, k = e - r * KD_S1;
     so[e] = k < KD_S1 - 1 ? p.o[(size_t)r * (KD_S1 - 1) + k] : 1.f;
+  }
+  uint32_t* sb = nullptr;
+  if constexpr (TRAIN) {
+    __shared__ uint32_t sbits[GROUP_MAX * NWB];
+    for (int e = tid; e < p.G * NWB; e += 256) sbits[e] = t.bits[e];
+    sb = sbits;
   }
   __syncthreads();
   const int u = blockIdx.x * 4 + wave, n = u / gsplit, gp = u - n * gsplit;
@@ -429,6 +467,7 @@ __global__ __launch_bounds__(256) void kron_dense_group_kernel(KronDenseGroupPar
     for (int k = 0; k < KD_S1; ++k) w[c][k] = valid[c] ? wr[q * KD_S1 + k] : 0.f;
   }
   const float bias = p.bias ? p.bias[n] : 0.f;
+  const float scale = TRAIN && t.p > 0.f ? 1.0f / (1.0f - t.p) : 1.0f;
   for (int g = gp; g < p.G; g += gsplit) {
     const float* og = so + g * M * KD_S1;
     float last[KD_S1];
@@ -438,13 +477,30 @@ __global__ __launch_bounds__(256) void kron_dense_group_kernel(KronDenseGroupPar
 #pragma unroll
     for (int c = 0; c < NQ; ++c) {
       float inner = 0.f;
+      if constexpr (TRAIN) {
+        const int b0 = valid[c] ? (lane + 64 * c) * KD_S1 : 0, wi = b0 >> 5;
+        const uint32_t lo = sb[g * NWB + wi], hi = wi + 1 < NWB ? sb[g * NWB + wi + 1] : 0u;
+        const uint32_t kb = (uint32_t)((((unsigned long long)hi << 32) | lo) >> (b0 & 31));
 #pragma unroll
-      for (int k = 0; k < KD_S1; ++k) inner += w[c][k] * last[k];
+        for (int k = 0; k < KD_S1; ++k) inner += w[c][k] * ((kb >> k) & 1u ? last[k] : 0.f);
+      } else {
+#pragma unroll
+        for (int k = 0; k < KD_S1; ++k) inner += w[c][k] * last[k];
+      }
       const float outer = M == 3 ? og[oi[c]] * og[KD_S1 + oj[c]] : og[oi[c]];
       acc += valid[c] ? outer * inner : 0.f;
     }
     acc = wave_sum(acc);
-    if (lane == 0) p.y[(size_t)g * p.N + n] = fmaxf(acc + bias, 0.f);
+    if constexpr (TRAIN) {
+      if (lane == 0) {
+        float y = fmaxf(acc * scale + bias, 0.f);
+        if (t.p > 0.f)
+          y = keep(t.key + (t.dev ? *t.dev : 0u), t.row_base[g] + (uint32_t)n, drop_threshold(t.p)) ? y / (1.0f - t.p) : 0.f;
+        p.y[(size_t)g * t.ld + n] = y;
+      }
+    } else {
+      if (lane == 0) p.y[(size_t)g * p.N + n] = fmaxf(acc + bias, 0.f);
+    }
   }
 }
 
@@ -452,7 +508,9 @@ __global__ __launch_bounds__(256) void kron_dense_group_kernel(KronDenseGroupPar
 // reads its skip connection [e1 | v_0 | ...] from where the parts lie (no concatenation launch); classifier[0] is the
 // one-segment case.  Work units as in kron_dense_group_kernel; lane l keeps W[n][l + 64 c] in registers with, for each,
 // the address of its input element in patient 0's row and that buffer's row stride.
-__global__ __launch_bounds__(256) void dense_segs_group_kernel(DenseSegsParams p, int gsplit) {
+// TRAIN: the output is dropped under patient g's mask of the site in t.key, index n.
+template <bool TRAIN>
+__global__ __launch_bounds__(256) void dense_segs_group_kernel(DenseSegsParams p, int gsplit, XTrainParams t) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int u = blockIdx.x * 4 + wave, n = u / gsplit, gp = u - n * gsplit;
   if (n >= p.N) return;
@@ -480,14 +538,35 @@ __global__ __launch_bounds__(256) void dense_segs_group_kernel(DenseSegsParams p
     for (int c = 0; c < DENSE_SEGS_MAXC; ++c)
       if (lane + 64 * c < p.K) a[c & 3] += w[c] * xp[c][(size_t)g * ld[c]];
     const float acc = wave_sum((a[0] + a[1]) + (a[2] + a[3]));
-    if (lane == 0) p.y[(size_t)g * p.N + n] = fmaxf(acc + bias, 0.f);
+    if (TRAIN) {
+      if (lane == 0) {
+        float y = fmaxf(acc + bias, 0.f);
+        if (t.p > 0.f)
+          y = keep(t.key + (t.dev ? *t.dev : 0u), t.row_base[g] + (uint32_t)n, drop_threshold(t.p)) ? y / (1.0f - t.p) : 0.f;
+        p.y[(size_t)g * p.N + n] = y;
+      }
+    } else {
+      if (lane == 0) p.y[(size_t)g * p.N + n] = fmaxf(acc + bias, 0.f);
+    }
   }
 }
 
-int launch_xgate_group(XGateGroupParams p, hipStream_t st) {
+static int xgate_group_check(const XGateGroupParams& p) {
   if (p.m < 2 || p.m > 3 || p.sdim < 1 || p.m * p.sdim > XG_MAX || p.G < 1 || p.G > GROUP_MAX) return MMF_ERR_SHAPE;
   if (p.dim < 4 || p.dim % 4 != 0) return MMF_ERR_SHAPE;
-  { ProfScope ps("xgate_group_kernel", st); hipLaunchKernelGGL(xgate_group_kernel, dim3(p.G), dim3(XR_NT), 0, st, p); }
+  return MMF_OK;
+}
+int launch_xgate_group(XGateGroupParams p, hipStream_t st) {
+  if (int e = xgate_group_check(p)) return e;
+  { ProfScope ps("xgate_group_kernel", st);
+    hipLaunchKernelGGL(xgate_group_kernel<false>, dim3(p.G), dim3(XR_NT), 0, st, p, XTrainParams{}); }
+  return hipGetLastError() == hipSuccess ? MMF_OK : MMF_ERR_LAUNCH;
+}
+int launch_xgate_group_train(XGateGroupParams p, XTrainParams t, hipStream_t st) {
+  if (int e = xgate_group_check(p)) return e;
+  if (p.sdim != KD_S1 - 1 || t.ld < p.dim || t.ld % 4 != 0 || !t.row_base || !t.h || !t.z || !t.gm || !t.bits) return MMF_ERR_SHAPE;
+  { ProfScope ps("xgate_group_train_kernel", st);
+    hipLaunchKernelGGL(xgate_group_kernel<true>, dim3(p.G), dim3(XR_NT), 0, st, p, t); }
   return hipGetLastError() == hipSuccess ? MMF_OK : MMF_ERR_LAUNCH;
 }
 // the patients' shares of a row: enough waves to fill the CUs at G = 64 (4 x 512 rows), never more shares than patients
@@ -496,11 +575,19 @@ int launch_kron_dense_group(KronDenseGroupParams p, hipStream_t st) {
   if (p.m < 2 || p.m > 3 || p.G < 1 || p.G > GROUP_MAX || p.N < 1) return MMF_ERR_SHAPE;
   const int gs = group_shares(p.G), blocks = cdiv((int64_t)p.N * gs, 4);
   { ProfScope ps("kron_dense_group_kernel", st);
-    if (p.m == 3) hipLaunchKernelGGL(kron_dense_group_kernel<3>, dim3(blocks), dim3(256), 0, st, p, gs);
-    else hipLaunchKernelGGL(kron_dense_group_kernel<2>, dim3(blocks), dim3(256), 0, st, p, gs); }
+    if (p.m == 3) hipLaunchKernelGGL((kron_dense_group_kernel<3, false>), dim3(blocks), dim3(256), 0, st, p, gs, XTrainParams{});
+    else hipLaunchKernelGGL((kron_dense_group_kernel<2, false>), dim3(blocks), dim3(256), 0, st, p, gs, XTrainParams{}); }
   return hipGetLastError() == hipSuccess ? MMF_OK : MMF_ERR_LAUNCH;
 }
-int launch_dense_segs_group(DenseSegsParams p, hipStream_t st) {
+int launch_kron_dense_group_train(KronDenseGroupParams p, XTrainParams t, hipStream_t st) {
+  if (p.m < 2 || p.m > 3 || p.G < 1 || p.G > GROUP_MAX || p.N < 1 || t.ld < p.N || !t.row_base || !t.bits) return MMF_ERR_SHAPE;
+  const int gs = group_shares(p.G), blocks = cdiv((int64_t)p.N * gs, 4);
+  { ProfScope ps("kron_dense_group_train_kernel", st);
+    if (p.m == 3) hipLaunchKernelGGL((kron_dense_group_kernel<3, true>), dim3(blocks), dim3(256), 0, st, p, gs, t);
+    else hipLaunchKernelGGL((kron_dense_group_kernel<2, true>), dim3(blocks), dim3(256), 0, st, p, gs, t); }
+  return hipGetLastError() == hipSuccess ? MMF_OK : MMF_ERR_LAUNCH;
+}
+static int dense_segs_group_check(const DenseSegsParams& p) {
   if (p.nseg < 1 || p.nseg > 4 || p.G < 1 || p.G > GROUP_MAX || p.N < 1) return MMF_ERR_SHAPE;
   int K = 0;
   for (int s = 0; s < p.nseg; ++s) {
@@ -508,9 +595,21 @@ int launch_dense_segs_group(DenseSegsParams p, hipStream_t st) {
     K += p.width[s];
   }
   if (K != p.K || K > 64 * DENSE_SEGS_MAXC) return MMF_ERR_SHAPE;
+  return MMF_OK;
+}
+int launch_dense_segs_group(DenseSegsParams p, hipStream_t st) {
+  if (int e = dense_segs_group_check(p)) return e;
   const int gs = group_shares(p.G), blocks = cdiv((int64_t)p.N * gs, 4);
   { ProfScope ps("dense_segs_group_kernel", st);
-    hipLaunchKernelGGL(dense_segs_group_kernel, dim3(blocks), dim3(256), 0, st, p, gs); }
+    hipLaunchKernelGGL(dense_segs_group_kernel<false>, dim3(blocks), dim3(256), 0, st, p, gs, XTrainParams{}); }
+  return hipGetLastError() == hipSuccess ? MMF_OK : MMF_ERR_LAUNCH;
+}
+int launch_dense_segs_group_train(DenseSegsParams p, XTrainParams t, hipStream_t st) {
+  if (int e = dense_segs_group_check(p)) return e;
+  if (!t.row_base) return MMF_ERR_SHAPE;
+  const int gs = group_shares(p.G), blocks = cdiv((int64_t)p.N * gs, 4);
+  { ProfScope ps("dense_segs_group_train_kernel", st);
+    hipLaunchKernelGGL(dense_segs_group_kernel<true>, dim3(blocks), dim3(256), 0, st, p, gs, t); }
   return hipGetLastError() == hipSuccess ? MMF_OK : MMF_ERR_LAUNCH;
 }
 

@@ -369,19 +369,52 @@ class MM_MIL_Attention_fc_surv(MM_MIL_Attention_fc):
         Gradients of sum_g loss_g * loss_scale, same .grad / grad_out conventions as nll_step.
         Returns (hazards [G x K], S [G x K], Y_hat [G], A_raw {"radiology": [per patient], "pathology": [per patient]},
         loss [G], risk [G]), detached."""
-        from ..ops import (_dense_rows_bwd_raw, _dense_rows_fwd_raw, _group_half_bwd_raw, _group_half_fwd_raw)
-        MmfError = ops._lib.MmfError
         if self.fusion != "concat":
             raise NotImplementedError("nll_step_group covers fusion='concat'; XlinearFusion's kernels take one patient")
+        return self._group_step("nll_step_group", patients, labels, censors, alpha, loss_scale, grad_out, accumulate, seeds)
+
+    def nll_step_group_tensor(self, patients, labels, censors, alpha=0.0, loss_scale=1.0, grad_out=None, accumulate=None,
+                              seeds=None):
+        """nll_step_group for fusion='tensor' (the XlinearFusion / Kronecker head in the configuration nll_step takes: skip,
+        scale width 16): the same window, the same `patients` forms, refusals and results.  The stacks and the omic batch
+        write their embeddings into the columns of encoder2's input matrix (ops.xfusion_group_input); the XlinearFusion
+        block and classifier[0] run as ONE call of four launches for the window (ops._xfusion_group_fwd_raw: encoder1's
+        10 MB weight is read once per window, not once per patient), the hazard head with classifier[3] on hid [G x 256],
+        and the fusion backward as one call (ops._xfusion_group_bwd_raw: encoder1's weight gradient is written once).
+        Everything is issued on the current stream, in this order: radio forward, pathology forward, omic forward, fusion
+        forward, head, fusion backward, pathology backward, omic backward, radio backward, hand_over_grads.
+
+        Seeds: in train mode patient g draws ops.next_dropout_seed() in nll_step's order -- radio, path, omic, fusion for
+        patient 0, then patient 1, ... -- so the same seed stream gives every patient the masks G nll_step calls give
+        it; or `seeds` = {"radio": [G], "path": [G], "omic": [G], "fusion": [G]} (the branches in `mode`, and "fusion").
+        The fusion seed of a patient keys its masks of the sites 0 .. 2 (o_i), 8 (product), 9, 10 (encoders) and 11
+        (classifier[2])."""
+        if self.fusion != "tensor":
+            raise NotImplementedError("nll_step_group_tensor covers fusion='tensor'; the concat head has nll_step_group")
+        if not (self.mm.skip and self.mm.reduce[0][0][0].weight.shape[0] == 16):
+            raise NotImplementedError("nll_step_group_tensor covers the XlinearFusion configuration the heads use "
+                                      "(skip, scale width 16)")
+        return self._group_step("nll_step_group_tensor", patients, labels, censors, alpha, loss_scale, grad_out, accumulate,
+                                seeds)
+
+    def _group_step(self, what, patients, labels, censors, alpha, loss_scale, grad_out, accumulate, seeds):
+        """The one body of nll_step_group and nll_step_group_tensor: the window checks, the seeds, the stack chains and
+        the omic batch are the same; the fusion decides where the embeddings are written and what runs between the
+        branches' forward and backward halves."""
+        from ..ops import (_dense_rows_bwd_raw, _dense_rows_fwd_raw, _group_half_bwd_raw, _group_half_fwd_raw,
+                           _xfusion_group_bwd_raw, _xfusion_group_fwd_raw)
+        MmfError = ops._lib.MmfError
+        tensor = self.fusion == "tensor"
         if ops._gemm != 0:
-            raise MmfError("nll_step_group runs the exact-fp32 GEMMs only (ops.set_gemm(0))")
+            raise MmfError(f"{what} runs the exact-fp32 GEMMs only (ops.set_gemm(0))")
         order, cols, F = self._concat_layout()
         params = list(self.parameters())
         if any(not p.requires_grad for p in params):
-            raise RuntimeError("nll_step_group needs every parameter to require grad")
-        Wk, bk = self.classifier.weight, self.classifier.bias
+            raise RuntimeError(f"{what} needs every parameter to require grad")
+        head = self.classifier[3] if tensor else self.classifier
+        Wk, bk = head.weight, head.bias
         if Wk.shape[0] > 32:
-            raise MmfError("nll_step_group: the fused hazard head takes K <= 32 classes")
+            raise MmfError(f"{what}: the fused hazard head takes K <= 32 classes")
         path, radio, omic = self._stacked_patients(patients)
         # ---- every refusal before the first launch
         counts = {}
@@ -415,31 +448,39 @@ class MM_MIL_Attention_fc_surv(MM_MIL_Attention_fc):
         if not Y.is_cuda and bool(((Y < 0) | (Y >= Wk.shape[0])).any()):
             raise IndexError(f"nll_surv: label out of range [0, {Wk.shape[0]})")
         tr = self.training
+        draws = [k for k in ("radio", "path", "omic") if k in order] + (["fusion"] if tensor else [])   # nll_step's order
         if seeds is None:
-            seeds = {k: [0] * G for k in order}
+            seeds = {k: [0] * G for k in draws}
             if tr:
                 for g in range(G):
-                    for k in ("radio", "path", "omic"):          # nll_step's order of draws
-                        if k in order:
-                            seeds[k][g] = ops.next_dropout_seed()
-        elif any(k not in seeds or len(seeds[k]) != G for k in order):
-            raise MmfError(f"seeds: {G} dropout seeds for each of {order}")
+                    for k in draws:
+                        seeds[k][g] = ops.next_dropout_seed()
+        elif any(k not in seeds or len(seeds[k]) != G for k in draws):
+            raise MmfError(f"seeds: {G} dropout seeds for each of {draws}")
         dev = (path[0] if path is not None else radio[0][0] if radio is not None else omic).device
         grads = {}
 
         def stack_forward(seq, xs, sizes, k, Wr=None, br=None):
             gated, ps, p_h, p_att = stack_args(seq, tr)
-            A, state = _group_half_fwd_raw(xs, sizes, ps, gated, p_h, p_att, seeds[k], feat[:, cols[k]], Wr, br)
+            A, state = _group_half_fwd_raw(xs, sizes, ps, gated, p_h, p_att, seeds[k], slot[k], Wr, br)
             return A, (ps, state)
 
         def stack_backward(run, k):
             ps, state = run
-            ds, rd = _group_half_bwd_raw(state, dfeat[:, cols[k]])
+            ds, rd = _group_half_bwd_raw(state, dslot[k])
             grads.update((p, gr) for p, gr in zip(ps, ds) if p is not None)
             return rd
 
         with torch.no_grad():
-            feat = torch.empty((G, F), dtype=torch.float32, device=dev)
+            # where branch k writes its embeddings: its columns of the [G x F] feature matrix (concat), or of encoder2's
+            # input matrix behind encoder1's columns (tensor) -- either way the concatenation is never a launch
+            if tensor:
+                xw = self._xfusion_weights(len(order))
+                x2, views = ops.xfusion_group_input(G, len(order), F // len(order), int(xw[6 * len(order)].shape[0]), dev)
+                slot = dict(zip(order, views))
+            else:
+                feat = torch.empty((G, F), dtype=torch.float32, device=dev)
+                slot = {k: feat[:, cols[k]] for k in order}
             A_raw = {}
             if "radio" in order:
                 many = len(radio[0]) > 1         # one modality: no reduce_dim, the pathology pair on that bag
@@ -456,16 +497,29 @@ class MM_MIL_Attention_fc_surv(MM_MIL_Attention_fc):
                     lin, adrop = blk[0], blk[2]
                     acts.append(_dense_rows_fwd_raw(acts[-1], lin.weight, lin.bias, "selu", "alpha" if tr else "none",
                                                     adrop.p if tr else 0.0, i, base, word,
-                                                    out=feat[:, cols["omic"]] if i == nblk - 1 else None))
+                                                    out=slot["omic"] if i == nblk - 1 else None))
             # ---- classifier + hazards + loss + their backward for every patient: one launch and its reduce
             dWk, dbk = torch.empty_like(Wk), torch.empty_like(bk)
-            hazards, S, Y_hat, loss, risk, dfeat = ops.surv_head_nll_step_group(feat, Wk, bk, Y, cc, alpha, dWk, dbk,
-                                                                                loss_scale=loss_scale)
+            if tensor:
+                # XlinearFusion + classifier[0] in front of it, their backward behind it (forward() lines 182-188)
+                c0 = self.classifier[0]
+                _, hid, xstate = _xfusion_group_fwd_raw(x2, len(order), xw, c0.weight, c0.bias,
+                                                        self.mm.dropout_rate if tr else 0.0,
+                                                        self.classifier[2].p if tr else 0.0, seeds["fusion"], ops._seed_word)
+                hazards, S, Y_hat, loss, risk, dhid = ops.surv_head_nll_step_group(hid, Wk, bk, Y, cc, alpha, dWk, dbk,
+                                                                                   loss_scale=loss_scale)
+                dvs, gw = _xfusion_group_bwd_raw(dhid, xstate)
+                grads.update(zip(xw + [c0.weight, c0.bias], gw))
+                dslot = dict(zip(order, dvs))
+            else:
+                hazards, S, Y_hat, loss, risk, dfeat = ops.surv_head_nll_step_group(feat, Wk, bk, Y, cc, alpha, dWk, dbk,
+                                                                                    loss_scale=loss_scale)
+                dslot = {k: dfeat[:, cols[k]] for k in order}
             grads[Wk], grads[bk] = dWk, dbk
             if "path" in order:
                 stack_backward(run_p, "path")
             if "omic" in order:
-                g = dfeat[:, cols["omic"]]
+                g = dslot["omic"]
                 for i in range(nblk - 1, -1, -1):
                     lin, adrop = self.fc_omic[i][0], self.fc_omic[i][2]
                     g, dW, db = _dense_rows_bwd_raw(g, acts[i + 1], acts[i], lin.weight, lin.bias is not None, "selu",

@@ -742,6 +742,33 @@ def _group_rows(ts, what):
     return ts, G
 
 
+def _xfusion_operands(m, G, dim, weights, Wc0, bc0, what):
+    """The XlinearFusion weights (xfusion's order) and classifier[0] of a grouped fusion call, checked against m
+    embeddings [G x dim].  Returns (mmf_xfusion_weights, the contiguous tensors it points to, (sdim, mmhid1, mmhid2, nhid))."""
+    if m < 2 or m > 3 or len(weights) != 6 * m + 4:
+        raise _lib.MmfError(f"{what} takes 2 or 3 modalities with 6 m + 4 weights, got {m} / {len(weights)}")
+    w = [_f32c(t) for t in weights]
+    Wc0, bc0 = _f32c(Wc0), _f32c(bc0)
+    sdim = int(w[0].shape[0])
+    We1, be1, We2, be2 = w[6 * m:]
+    mmhid1, mmhid2, nhid = int(We1.shape[0]), int(We2.shape[0]), int(Wc0.shape[0])
+    ok = (tuple(We1.shape) == (mmhid1, (sdim + 1) ** m)
+          and tuple(We2.shape) == (mmhid2, mmhid1 + m * dim) and tuple(Wc0.shape) == (nhid, mmhid2)
+          and be1.numel() == mmhid1 and be2.numel() == mmhid2 and bc0.numel() == nhid)
+    for i in range(m):
+        Wh, bh, Wz, bz, Wo, bo = w[6 * i:6 * i + 6]
+        ok = ok and (tuple(Wh.shape) == (sdim, dim) and tuple(Wz.shape) == (sdim, m * dim) and tuple(Wo.shape) == (sdim, sdim)
+                     and bh.numel() == bz.numel() == bo.numel() == sdim)
+    if not ok or dim % 4 != 0 or sdim != 16:
+        raise _lib.MmfError(f"{what}: the weights do not match the embeddings (dim % 4 == 0, scale width 16)")
+    xw = _lib.XFusionWeights(m=m, dim=dim, sdim=sdim, mmhid1=mmhid1, mmhid2=mmhid2, nhid=nhid, We1=ptr(We1), be1=ptr(be1),
+                             We2=ptr(We2), be2=ptr(be2), Wc0=ptr(Wc0), bc0=ptr(bc0))
+    for i in range(m):
+        for name, t in zip(("Wh", "bh", "Wz", "bz", "Wo", "bo"), w[6 * i:6 * i + 6]):
+            getattr(xw, name)[i] = ptr(t)
+    return xw, w + [Wc0, bc0], (sdim, mmhid1, mmhid2, nhid)
+
+
 def xfusion_infer_group(vs, weights, Wc0, bc0):
     """The XlinearFusion block (gate, skip) and classifier[0] + ReLU for the G patients of an evaluation window, forward
     only, in ONE C-ABI call of four launches (include/mmf_amil.h: mmf_xfusion_infer_group): the gating stage per
@@ -754,25 +781,10 @@ def xfusion_infer_group(vs, weights, Wc0, bc0):
     if m < 2 or m > 3 or len(weights) != 6 * m + 4:
         raise _lib.MmfError(f"xfusion_infer_group takes 2 or 3 modalities with 6 m + 4 weights, got {m} / {len(weights)}")
     vs, G = _group_rows(vs, "xfusion_infer_group")
-    w = [_f32c(t) for t in weights]
-    Wc0, bc0 = _f32c(Wc0), _f32c(bc0)
-    dim, sdim = int(vs[0].shape[1]), int(w[0].shape[0])
-    We1, be1, We2, be2 = w[6 * m:]
-    mmhid1, mmhid2, nhid = int(We1.shape[0]), int(We2.shape[0]), int(Wc0.shape[0])
-    ok = (all(tuple(v.shape) == (G, dim) for v in vs) and tuple(We1.shape) == (mmhid1, (sdim + 1) ** m)
-          and tuple(We2.shape) == (mmhid2, mmhid1 + m * dim) and tuple(Wc0.shape) == (nhid, mmhid2)
-          and be1.numel() == mmhid1 and be2.numel() == mmhid2 and bc0.numel() == nhid)
-    for i in range(m):
-        Wh, bh, Wz, bz, Wo, bo = w[6 * i:6 * i + 6]
-        ok = ok and (tuple(Wh.shape) == (sdim, dim) and tuple(Wz.shape) == (sdim, m * dim) and tuple(Wo.shape) == (sdim, sdim)
-                     and bh.numel() == bz.numel() == bo.numel() == sdim)
-    if not ok or dim % 4 != 0 or sdim != 16:
+    dim = int(vs[0].shape[1])
+    if any(tuple(v.shape) != (G, dim) for v in vs):
         raise _lib.MmfError("xfusion_infer_group: the weights do not match the embeddings (dim % 4 == 0, scale width 16)")
-    xw = _lib.XFusionWeights(m=m, dim=dim, sdim=sdim, mmhid1=mmhid1, mmhid2=mmhid2, nhid=nhid, We1=ptr(We1), be1=ptr(be1),
-                             We2=ptr(We2), be2=ptr(be2), Wc0=ptr(Wc0), bc0=ptr(bc0))
-    for i in range(m):
-        for name, t in zip(("Wh", "bh", "Wz", "bz", "Wo", "bo"), w[6 * i:6 * i + 6]):
-            getattr(xw, name)[i] = ptr(t)
+    xw, _keep, (sdim, mmhid1, mmhid2, nhid) = _xfusion_operands(m, G, dim, weights, Wc0, bc0, "xfusion_infer_group")
     dev = vs[0].device
     MM = torch.empty((G, mmhid2), dtype=torch.float32, device=dev)
     hid = torch.empty((G, nhid), dtype=torch.float32, device=dev)
@@ -783,6 +795,75 @@ def xfusion_infer_group(vs, weights, Wc0, bc0):
     check(l.mmf_xfusion_infer_group(C.byref(xw), vp, G, ptr(ws), nbytes, ptr(MM), ptr(hid), stream_ptr()),
           "mmf_xfusion_infer_group")
     return MM, hid
+
+
+def xfusion_group_input(G, m, dim, mmhid1, device):
+    """encoder2's input matrix x2 [G x mmhid1 + m dim] of a grouped tensor-fusion step and the m views [G x dim] where the
+    branches write v_i (columns mmhid1 + i dim ..): _xfusion_group_fwd_raw reads the embeddings there and fills the first
+    mmhid1 columns, so no concatenation is ever a launch."""
+    x2 = torch.empty((G, mmhid1 + m * dim), dtype=torch.float32, device=device)
+    return x2, [x2[:, mmhid1 + i * dim: mmhid1 + (i + 1) * dim] for i in range(m)]
+
+
+def _xfusion_group_fwd_raw(x2, m, weights, Wc0, bc0, p, p_c, seeds, word=None):
+    """The XlinearFusion block and classifier[0] + ReLU + Dropout for the G patients of one accumulation window, training
+    form, in ONE C-ABI call of four launches (include/mmf_amil.h: mmf_xfusion_group_forward).  x2: xfusion_group_input's
+    matrix with the embeddings in place; weights as xfusion takes them; p: XlinearFusion's dropout rate (sites 0 .. 10),
+    p_c: classifier[2]'s (site 11), both 0 in eval mode; seeds: the G fusion seeds -- patient g gets the masks a one-patient
+    call draws under seeds[g].  Returns (MM [G x mmhid2], hid [G x nhid], state for _xfusion_group_bwd_raw)."""
+    if not torch.is_tensor(x2) or x2.dim() != 2 or x2.dtype != torch.float32 or not x2.is_contiguous():
+        raise _lib.MmfError("xfusion group step: x2 must be a contiguous fp32 [G x mmhid1 + m dim] matrix")
+    G = int(x2.shape[0])
+    if G < 1 or G > GROUP_MAX:
+        raise _lib.MmfError(f"a group holds 1 .. {GROUP_MAX} patients, got {G}")
+    if len(seeds) != G:
+        raise _lib.MmfError(f"{G} patients need {G} fusion seeds, got {len(seeds)}")
+    mmhid1 = int(weights[6 * m].shape[0]) if 2 <= m <= 3 and len(weights) == 6 * m + 4 else 0
+    dim = (int(x2.shape[1]) - mmhid1) // max(m, 1)
+    xw, keep, (sdim, mmhid1, mmhid2, nhid) = _xfusion_operands(m, G, dim, weights, Wc0, bc0, "xfusion group step")
+    if x2.shape[1] != mmhid1 + m * dim:
+        raise _lib.MmfError(f"xfusion group step: x2 must be [G x {mmhid1} + {m} dim], got {tuple(x2.shape)}")
+    dev = x2.device
+    base = dropout_row_base(seeds, dev)
+    MM = torch.empty((G, mmhid2), dtype=torch.float32, device=dev)
+    hid = torch.empty((G, nhid), dtype=torch.float32, device=dev)
+    l = lib()
+    nbytes = l.mmf_xfusion_group_workspace_bytes(m, dim, sdim, mmhid1, mmhid2, nhid, G)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    check(l.mmf_xfusion_group_forward(C.byref(xw), ptr(x2), G, float(p), float(p_c), ptr(base), ptr(word), ptr(ws), nbytes,
+                                      ptr(MM), ptr(hid), stream_ptr()), "mmf_xfusion_group_forward")
+    return MM, hid, (xw, keep, x2, m, G, float(p), float(p_c), base, word, MM, hid, ws, mmhid1, dim)
+
+
+def _xfusion_group_bwd_raw(dhid, state, grads=None, accumulate=False):
+    """The backward of a _xfusion_group_fwd_raw call from dhid ([G x nhid] or columns of a wider matrix: the hazard
+    head's dfeat) (mmf_xfusion_group_backward).  grads: gradient tensors in the order of (weights, Wc0, bc0), overwritten
+    or, with `accumulate`, added to; None: fresh ones.  Returns ([dv_i: views of one [G x K2] matrix, skip connection
+    included], grads): sums over the patients in patient order."""
+    xw, keep, x2, m, G, p, p_c, base, word, MM, hid, ws, mmhid1, dim = state
+    dp, ldd = _rows_ptr(dhid, "dhid")
+    if tuple(dhid.shape) != tuple(hid.shape):
+        raise _lib.MmfError(f"dhid must be {tuple(hid.shape)}, got {tuple(dhid.shape)}")
+    if grads is None:
+        if accumulate:
+            raise _lib.MmfError("accumulate needs the gradient tensors to add to")
+        grads = [torch.empty_like(t) for t in keep]
+    else:
+        grads = list(grads)
+        if len(grads) != len(keep):
+            raise _lib.MmfError(f"xfusion group step: {len(keep)} gradient tensors expected, got {len(grads)}")
+        _check_grad_buffers(tuple(zip(grads, keep)))
+    xg = _lib.XFusionGrads()
+    for i in range(m):
+        for name, t in zip(("dWh", "dbh", "dWz", "dbz", "dWo", "dbo"), grads[6 * i:6 * i + 6]):
+            getattr(xg, name)[i] = ptr(t)
+    for name, t in zip(("dWe1", "dbe1", "dWe2", "dbe2", "dWc0", "dbc0"), grads[6 * m:]):
+        setattr(xg, name, ptr(t))
+    dx2 = torch.empty_like(x2)
+    check(lib().mmf_xfusion_group_backward(C.byref(xw), ptr(x2), G, p, p_c, ptr(base), ptr(word), ptr(MM), ptr(hid), dp, ldd,
+                                           ptr(ws), ws.numel(), ptr(dx2), C.byref(xg), 1 if accumulate else 0,
+                                           stream_ptr()), "mmf_xfusion_group_backward")
+    return [dx2[:, mmhid1 + i * dim: mmhid1 + (i + 1) * dim] for i in range(m)], grads
 
 
 def surv_head_infer_group(segs, Wk, bk, Y=None, c=None, alpha=0.0, eps=1e-7):

@@ -241,12 +241,21 @@ class _BagGroup(_HeldBags):
         return out
 
 
+def _group_tensor(model):
+    """The tensor fusion on the grouped route: a per-instance opt-in (model.mmf_group_tensor = True; absent means off),
+    like mmf_one_call_step / mmf_side_stream / mmf_fork_min_one_call."""
+    return (getattr(model, "fusion", None) == "tensor" and bool(getattr(model, "mmf_group_tensor", False))
+            and hasattr(model, "nll_step_group_tensor"))
+
+
 class _MMGroup:
-    """train_loop_survival(group=True) with the multimodal concat head: the eligible patients of the current window, until
-    one grouped call (MM_MIL_Attention_fc_surv.nll_step_group) runs them.  A patient's bags are copied straight into their
+    """train_loop_survival(group=True) with the multimodal head: the eligible patients of the current window, until
+    one grouped call (MM_MIL_Attention_fc_surv.nll_step_group; nll_step_group_tensor for a tensor-fusion model that opted
+    in) runs them.  A patient's bags are copied straight into their
     rows of three reusable device buffers -- the pathology plane [1 x rows x L], the radio planes [n_mod x rows x L] and the
     omic rows [GROUP_MAX x input_dim] -- and its up to three dropout seeds are drawn when it arrives, in nll_step's order
-    (radio, path, omic), so patient g of the loader gets the masks the per-patient route gives it.  A patient that would
+    (radio, path, omic; then the fusion seed of the tensor fusion), so patient g of the loader gets the masks the per-patient
+    route gives it.  A patient that would
     take the group past ops.GROUP_MAX or past either branch's row limit flushes what is held first."""
 
     def __init__(self):
@@ -286,6 +295,8 @@ class _MMGroup:
         for k in ("radio", "path", "omic"):
             if has(k):
                 self.seeds[k].append(ops.next_dropout_seed() if model.training else 0)
+        if _group_tensor(model):               # nll_step draws the fusion seed after the branches'
+            self.seeds.setdefault("fusion", []).append(ops.next_dropout_seed() if model.training else 0)
         never = lambda: None                   # the flush above has made room in both planes
         if has("radio"):
             self.radio.add(xs_r, label, c, slot, lim_r, device, never)
@@ -311,8 +322,13 @@ class _MMGroup:
             return []
         has = lambda k: k in model.mode
         seeds = {k: v for k, v in self.seeds.items() if has(k)} if model.training else None
-        _, _, _, _, loss, risk = model.nll_step_group(self.window(model), torch.cat(self.labels), torch.cat(self.cs),
-                                                      alpha=alpha, loss_scale=loss_scale, seeds=seeds)
+        step = model.nll_step_group
+        if _group_tensor(model):
+            step = model.nll_step_group_tensor
+            if seeds is not None:
+                seeds["fusion"] = self.seeds["fusion"]
+        _, _, _, _, loss, risk = step(self.window(model), torch.cat(self.labels), torch.cat(self.cs), alpha=alpha,
+                                      loss_scale=loss_scale, seeds=seeds)
         out = [(slot, loss[g:g + 1], risk[g:g + 1]) for g, slot in enumerate(self.slots)]
         self.reset()
         return out
@@ -406,9 +422,13 @@ def _fused_mm_ok(model, loss_fn, feats, on_host=False):
 
 def _mm_group_ok(model, loss_fn, radio_features, path_features, genomic_features):
     """A multimodal patient the window's grouped call takes (model.nll_step_group): what _fused_mm_ok allows (asked on the
-    tensors as the loader delivers them, host or device), the concat fusion, and for every branch in model.mode a 2-D fp32
-    bag (the modalities of one shape) or an omic vector of the model's input width."""
-    if getattr(model, "fusion", None) != "concat" or not hasattr(model, "nll_step_group"):
+    tensors as the loader delivers them, host or device), the concat fusion -- or the tensor fusion with scale width 16 on a
+    model that opted in (model.mmf_group_tensor = True: nll_step_group_tensor) --, and for every branch in model.mode a
+    2-D fp32 bag (the modalities of one shape) or an omic vector of the model's input width."""
+    if _group_tensor(model):
+        if model.mm.reduce[0][0][0].weight.shape[0] != 16:
+            return False
+    elif getattr(model, "fusion", None) != "concat" or not hasattr(model, "nll_step_group"):
         return False
     feats = dict(radio_features, path_features=path_features, genomic_features=genomic_features)
     if not _fused_mm_ok(model, loss_fn, feats, on_host=True):

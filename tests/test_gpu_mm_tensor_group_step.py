@@ -1,0 +1,519 @@
+"""GPU parity of the multimodal tensor-fusion head's grouped training step
+(MM_MIL_Attention_fc_surv.nll_step_group_tensor over include/mmf_amil.h: mmf_xfusion_group_forward / _backward beside the
+grouped stack chains, the omic batch and mmf_surv_head_nll_step_group).  Per patient, hazards / S / Y_hat / both score
+vectors / loss / risk against the fp64 oracle of that patient alone (train mode: with the masks of that patient's own four
+seeds); the summed gradients against the oracle's sum_g loss_scale * grads_g; the grouped route against G nll_step calls on
+the same seed stream; the call mechanics, the refusals, and the two raw entry points on their own.
+
+The fusion tail has five ReLU layers (h_i, o_i, encoder1, encoder2, classifier[0]) and no kink allowance: every test
+that compares against fp64 asserts that each of those pre-activations, of every patient, lies farther than 4e-6 (the
+project's relu_kink_units threshold) from zero in the oracle.  The seeds and the bias scale below were chosen, on the CPU,
+so that this holds."""
+import numpy as np
+import pytest
+import torch
+
+from oracle import cases
+from oracle import inputs as gen
+from oracle import torch_port as tp
+from test_gpu_mm_group_step import (BRANCHES, SIXTY_FOUR_P, SIXTY_FOUR_R, _kinks, _labels, _model, _patient, _sd, _split,
+                                    _stacked, _ulps)
+from test_gpu_path import DEV, _grads, _t, compare
+from test_gpu_poison import poison  # noqa: F401  (fixture)
+
+pytestmark = pytest.mark.gpu
+
+DRAWS = BRANCHES + ("fusion",)               # nll_step's order of seed draws with the tensor fusion
+KINK = 4e-6                                  # test_gpu_path.relu_kink_units' threshold
+TAIL_RELU = ("mm.reduce.0.0.0", "mm.reduce.1.0.0", "mm.reduce.2.0.0", "mm.reduce.0.2.0", "mm.reduce.1.2.0",
+             "mm.reduce.2.2.0", "mm.encoder1.0", "mm.encoder2.0", "classifier.0")
+P_FUS = 0.25                                 # XlinearFusion's dropout_rate and classifier[2].p
+
+
+def _order(mode):
+    return [k for k in BRANCHES if k in mode] + ["fusion"]
+
+
+def _metas(base, path_sizes, radio_sizes):
+    out = []
+    for g, (Np, nr) in enumerate(zip(path_sizes, radio_sizes)):
+        m = dict(base, Np=Np, nr=nr, x_seed=base["x_seed"] + 101 * g, y=(g + 1) % base["K"], c=g % 2)
+        m["seeds"] = {k: base["mask_seed"] + 1000 * g + 17 * i for i, k in enumerate(DRAWS)}
+        out.append(m)
+    return out
+
+
+def _base(mode, gate_path, gate_radio, K, train, dropout, **kw):
+    # bias_std 0.5: the tail's pre-activations then have a spread of ~0.5, and among the ~1,400 of them per patient none
+    # need lie within 4e-6 of zero (at 0.05 a 64-patient window expects five that do)
+    base = dict(mode=mode, gate_path=gate_path, gate_radio=gate_radio, K=K, train=train, dropout=dropout, G=80, alpha=0.3,
+                bias_std=0.5, seed=4343, x_seed=510, mask_seed=910, fusion="tensor")
+    base.update(kw)
+    return base
+
+
+def _seed_stream(monkeypatch, metas):
+    from multimodalfusion_amd import ops
+    it = iter([m["seeds"][k] for m in metas for k in _order(m["mode"])])
+    monkeypatch.setattr(ops, "next_dropout_seed", lambda: next(it))
+
+
+def run_group(metas, monkeypatch, loss_scale, model=None, patients=None, **kw):
+    model = _model(metas[0]) if model is None else model
+    if metas[0]["train"] and "seeds" not in kw:
+        _seed_stream(monkeypatch, metas)
+    patients = [_patient(m) for m in metas] if patients is None else patients
+    Y, c = _labels(metas)
+    hz, S, Yh, A, loss, risk = model.nll_step_group_tensor(patients, Y, c, alpha=metas[0]["alpha"], loss_scale=loss_scale,
+                                                           **kw)
+    torch.cuda.synchronize()
+    return dict(hazards=hz.cpu().numpy(), S=S.cpu().numpy(), Y_hat=Yh.cpu().numpy(),
+                A={k: [a.cpu().numpy() for a in v] for k, v in A.items()}, loss=loss.cpu().numpy(),
+                risk=risk.cpu().numpy(), grads=_grads(model))
+
+
+def run_per_patient(metas, monkeypatch, loss_scale):
+    model = _model(metas[0])
+    if metas[0]["train"]:
+        _seed_stream(monkeypatch, metas)
+    out = dict(hazards=[], S=[], Y_hat=[], A=[], loss=[])
+    for m in metas:
+        hz, S, Yh, A, loss, _ = model.nll_step(torch.tensor([m["y"]]), torch.tensor([float(m["c"])]), alpha=m["alpha"],
+                                               loss_scale=loss_scale, **_patient(m))
+        for k, v in (("hazards", hz), ("S", S), ("Y_hat", Yh), ("loss", loss)):
+            out[k].append(v.cpu().numpy())
+        out["A"].append({k: v.cpu().numpy() for k, v in A.items()})
+    torch.cuda.synchronize()
+    out["grads"] = _grads(model)
+    return out
+
+
+def fusion_masks(seed, m, T=None):
+    """The seven masks of the fusion tail under one fusion seed, as test_gpu_omic_mm.test_mm_tensor_train_mode_masks builds
+    them: sites i (o_i), 8 (product), 9, 10 (encoders), 11 (classifier[2])."""
+    T = T or (lambda a: torch.as_tensor(np.asarray(a)).double())
+    mk = lambda site, c: T(gen.drop_scale_mask(seed, site, 1, c, P_FUS, np.float64))
+    mm = {f"o{i}": mk(i, 16) for i in range(m)}
+    mm.update(post=mk(8, 17 ** m), enc1=mk(9, 512), enc2=mk(10, 512))
+    return mm, mk(11, 256)
+
+
+_ORACLE = {}
+
+
+def oracle_patient(m):
+    """The fp64 oracle of one patient alone, tp.mm_forward(fusion="tensor"), in train mode with that patient's masks (the
+    stacks' cases.amil_masks, the omic keep_masks, the seven fusion masks); computed once per patient and shared.  Also
+    the smallest distance from zero of the fusion tail's ReLU pre-activations ("margin")."""
+    key = repr(sorted((k, repr(v)) for k, v in m.items()))
+    if key in _ORACLE:
+        return _ORACLE[key]
+    _, xs, xp, xo = cases.mm_inputs(dict(m, fusion="concat"))
+    sd = tp.to_torch(_sd(m), torch.float64)
+    T = lambda a: torch.as_tensor(np.asarray(a)).double()
+    masks = None
+    if m["train"]:
+        tm = lambda d: {k: T(v) for k, v in d.items()}
+        s = m["seeds"]
+        mm, cls = fusion_masks(s["fusion"], len(_order(m["mode"])) - 1, T)
+        masks = {"radio": tm(cases.amil_masks(s["radio"], max(m["nr"], 1), 256, 256, m["gate_radio"], m["dropout"])),
+                 "path": tm(cases.amil_masks(s["path"], max(m["Np"], 1), 256, 256, m["gate_path"], m["dropout"])),
+                 "omic_keeps": [T(gen.keep_mask(s["omic"], i, 1, 256, 0.25).astype(np.float64)) for i in range(2)],
+                 "mm": mm, "cls": cls}
+    else:
+        assert not m["dropout"]
+    pre, lin = {}, tp._lin
+
+    def spy(sd_, name, x):
+        y = lin(sd_, name, x)
+        if name in TAIL_RELU:
+            pre[name] = float(y.detach().abs().min())
+        return y
+
+    tp._lin = spy
+    try:
+        hz, S, Yh, A_raw, _ = tp.mm_forward(sd, [T(x) for x in xs], T(xp), T(xo), fusion="tensor", gate_path=m["gate_path"],
+                                            gate_radio=m["gate_radio"], dropout=m["dropout"], mode=m["mode"], masks=masks)
+    finally:
+        tp._lin = lin
+    loss = tp.nll_loss(hz, S, torch.tensor([m["y"]]), torch.tensor([float(m["c"])]), alpha=m["alpha"])
+    gr = tp.grads_of(loss, sd)
+    assert len(pre) == 2 * (len(_order(m["mode"])) - 1) + 3       # h_i, o_i per modality, the encoders, classifier[0]
+    out = dict(hazards=hz.detach().numpy(), S=S.detach().numpy(), Y_hat=Yh.numpy(), loss=float(loss.detach()),
+               A_raw={k: v.detach().numpy() for k, v in A_raw.items()},
+               grads={k: v.detach().numpy() for k, v in gr.items()}, margin=min(pre.values()), margins=pre)
+    _ORACLE[key] = out
+    return out
+
+
+def assert_no_tail_kink(metas):
+    """No tail unit is excused: every ReLU pre-activation of the fusion tail, of every patient, is farther than KINK
+    from zero in the fp64 oracle, so fp32 and fp64 take the same side of every ReLU there."""
+    for g, m in enumerate(metas):
+        ref = oracle_patient(m)
+        assert ref["margin"] > KINK, (g, ref["margins"])
+
+
+def check_group(res, scale, metas):
+    assert_no_tail_kink(metas)
+    gsum = None
+    worst = dict(hazards=0.0, S=0.0, loss=0.0)
+    for g, m in enumerate(metas):
+        ref = oracle_patient(m)
+        keys = {"radiology": "radio", "pathology": "path"}
+        one = dict(hazards=res["hazards"][g:g + 1], S=res["S"][g:g + 1], loss=float(res["loss"][g]), grads={},
+                   A_raw={k: res["A"][k][g] for k in ref["A_raw"]})
+        assert set(res["A"]) == set(ref["A_raw"]) == {k for k, b in keys.items() if b in m["mode"]}
+        worst["hazards"] = max(worst["hazards"], float(np.abs(one["hazards"] - ref["hazards"]).max()))
+        worst["S"] = max(worst["S"], float(np.abs(one["S"] - ref["S"]).max()))
+        worst["loss"] = max(worst["loss"], abs(one["loss"] - ref["loss"]))
+        gsum = {k: scale * v for k, v in ref["grads"].items()} if gsum is None else \
+            {k: gsum[k] + scale * v for k, v in ref["grads"].items()}
+    print("max abs error over the window:", worst)
+    for k, v in gsum.items():
+        print(f"  grad {k}: err {float(np.abs(res['grads'][k] - v).max()):.3e} bar {1e-5 + 1e-4 * float(np.abs(v).max()):.3e}")
+    for g, m in enumerate(metas):
+        ref = oracle_patient(m)
+        one = dict(hazards=res["hazards"][g:g + 1], S=res["S"][g:g + 1], loss=float(res["loss"][g]), grads={},
+                   A_raw={k: res["A"][k][g] for k in ref["A_raw"]})
+        compare(one, dict(ref, grads={}), f"patient {g}")
+        assert int(res["Y_hat"][g]) == int(np.asarray(ref["Y_hat"]).reshape(-1)[0]), f"patient {g}"
+        assert abs(float(res["risk"][g]) + float(res["S"][g].sum())) < 1e-5, f"patient {g}"
+    assert set(gsum) == set(res["grads"])
+    kp, kr = _kinks(metas)
+    zero = dict(hazards=0, S=0, A_raw=0, loss=0.0)
+    rd_ref, radio_ref, rest_ref = _split(gsum)
+    compare(dict(zero, grads=res["grads"]), dict(zero, grads=rest_ref), "summed grads", kink_units=kp)
+    compare(dict(zero, grads=res["grads"]), dict(zero, grads=radio_ref), "summed radio grads", kink_units=kr,
+            kink_prefix="attention_net_radio")
+    for k, v in rd_ref.items():
+        err = float(np.abs(res["grads"][k] - v).max())
+        top = float(np.abs(v).max())
+        bar = 1e-2 * top if kr else 1e-5 + 1e-4 * top        # check_group of test_gpu_mm_group_step: a radio kink unit
+        assert err <= bar, (k, err, bar, sorted(kr))
+
+
+# mode, gate_path, gate_radio, K, pathology sizes, radio sizes, train, attention dropout   (G = 5, 3, 2, 3, 1, 2, 2, 64, 64)
+CASES = [
+    ("radio_path_omic", True, True, 4, [1, 999, 300, 1200, 64], [1, 17, 100, 300, 33], True, True),
+    ("radio_path_omic", False, True, 4, [700, 50, 5], [64, 5, 20], False, False),
+    ("radio_path", True, False, 32, [300, 50], [20, 64], True, True),
+    ("path_omic", False, True, 1, [5, 700, 64], [1, 1, 1], False, False),
+    ("radio_omic", True, False, 4, [1], [33], True, False),
+    ("path_omic", True, True, 4, [64, 1200], [1, 1], True, True),
+    ("radio_omic", True, True, 32, [1, 1], [150, 40], False, False),
+    ("radio_path_omic", True, True, 4, SIXTY_FOUR_P, SIXTY_FOUR_R, True, True),
+    ("radio_path_omic", False, False, 1, SIXTY_FOUR_P, SIXTY_FOUR_R, False, False),
+]
+# one (seed, x_seed, mask_seed) per case, chosen on the CPU for assert_no_tail_kink
+CASE_SEEDS = [(4343, 510, 910)] * 7 + [(4344, 511, 911), (4343, 510, 910)]
+
+
+def case_metas(i, **kw):
+    mode, gate_path, gate_radio, K, psizes, rsizes, train, dropout = CASES[i]
+    seed, x_seed, mask_seed = CASE_SEEDS[i]
+    return _metas(_base(mode, gate_path, gate_radio, K, train, dropout, seed=seed, x_seed=x_seed, mask_seed=mask_seed, **kw),
+                  psizes, rsizes)
+
+
+@pytest.mark.parametrize("i", range(len(CASES)))
+def test_tensor_group_matches_oracle_per_patient(i, monkeypatch):
+    metas = case_metas(i)
+    scale = 1.0 / len(metas)
+    check_group(run_group(metas, monkeypatch, scale), scale, metas)
+
+
+@pytest.mark.parametrize("i", [0, 2, 4, 5, 7])
+def test_tensor_group_equals_per_patient_route(i, monkeypatch):
+    """Against G nll_step calls on the same seed stream, at the bars of test_mm_group_equals_per_patient_route."""
+    metas = case_metas(i)
+    assert metas[0]["train"]
+    assert_no_tail_kink(metas)                # both fp32 routes then take the oracle's side of every tail ReLU
+    a = run_group(metas, monkeypatch, 0.25)
+    b = run_per_patient(metas, monkeypatch, 0.25)
+    assert np.array_equal(a["Y_hat"].reshape(-1), np.concatenate(b["Y_hat"]).reshape(-1))
+    hb = np.concatenate(b["hazards"])
+    lb = np.array([float(v) for v in b["loss"]])
+    print("hazards", float(np.abs(a["hazards"] - hb).max()), _ulps(hb), "loss", float(np.abs(a["loss"] - lb).max()), _ulps(lb))
+    for k, v in b["grads"].items():
+        print(f"  grad {k}: err {float(np.abs(a['grads'][k] - v).max()):.3e} max {float(np.abs(v).max()):.3e}")
+    np.testing.assert_allclose(a["hazards"], hb, rtol=0, atol=_ulps(hb))
+    np.testing.assert_allclose(a["loss"], lb, rtol=0, atol=_ulps(lb))
+    for g in range(len(metas)):
+        for k, v in b["A"][g].items():
+            np.testing.assert_allclose(a["A"][k][g], v, rtol=0, atol=_ulps(v))
+    kp, kr = _kinks(metas)
+    for k, v in b["grads"].items():
+        tol = 1e-5 * float(np.abs(v).max()) + 1e-6
+        bad = np.abs(a["grads"][k] - v) > tol + 1e-5 * np.abs(v)
+        kinked = (kr and (k.startswith("reduce_dim") or k.startswith("attention_net_radio.0."))
+                  or kp and k.startswith("attention_net_WSI.0."))
+        if bad.any() and kinked:
+            assert float(np.abs(a["grads"][k] - v).max()) <= 1e-2 * float(np.abs(v).max()), k
+            continue
+        assert not bad.any(), (k, float(np.abs(a["grads"][k] - v).max()), tol)
+
+
+MECH = _base("radio_path_omic", True, True, 4, True, True, alpha=0.2, seed=91, x_seed=92, mask_seed=93)
+
+
+def test_tensor_group_accumulate_and_grad_out(monkeypatch):
+    metas = _metas(MECH, [200, 17, 901], [30, 64, 7])
+    model = _model(metas[0])
+    first = run_group(metas, monkeypatch, 0.5, model=model)["grads"]           # .grad None: written
+    again = run_group(metas, monkeypatch, 0.5, model=model)["grads"]           # .grad set: added to
+    for k, v in first.items():
+        np.testing.assert_allclose(again[k], 2 * v, rtol=1e-5, atol=1e-6 * float(np.abs(v).max()) + 1e-12, err_msg=k)
+    views = [torch.full_like(p, 3.0) for p in model.parameters()]
+    for p in model.parameters():
+        p.grad = None
+    run_group(metas, monkeypatch, 0.5, model=model, grad_out=views, accumulate=False)
+    assert all(p.grad is None for p in model.parameters())
+    for (k, _), v in zip(model.named_parameters(), views):
+        np.testing.assert_allclose(v.cpu().numpy(), first[k], rtol=1e-5, atol=1e-6 * float(np.abs(first[k]).max()) + 1e-12,
+                                   err_msg=k)
+    run_group(metas, monkeypatch, 0.5, model=model, grad_out=views, accumulate=True)
+    for (k, _), v in zip(model.named_parameters(), views):
+        np.testing.assert_allclose(v.cpu().numpy(), 2 * first[k], rtol=1e-5,
+                                   atol=1e-6 * float(np.abs(first[k]).max()) + 1e-12, err_msg=k)
+
+
+def test_tensor_group_pre_stacked_equals_dicts_and_explicit_seeds(monkeypatch):
+    metas = _metas(MECH, [65, 130], [12, 300])
+    model = _model(metas[0])
+    patients = [_patient(m) for m in metas]
+    a = run_group(metas, monkeypatch, 1.0, model=model, patients=patients)
+    ga = {k: p.grad.clone() for k, p in model.named_parameters()}
+    for p in model.parameters():
+        p.grad = None
+    b = run_group(metas, monkeypatch, 1.0, model=model, patients=_stacked(patients))
+    for p in model.parameters():
+        p.grad = None
+    c = run_group(metas, monkeypatch, 1.0, model=model, patients=patients,
+                  seeds={k: [m["seeds"][k] for m in metas] for k in DRAWS})
+    for r in (b, c):
+        for k in ("hazards", "S", "loss", "risk", "Y_hat"):
+            assert np.array_equal(r[k], a[k]), k
+        for k in a["A"]:
+            assert all(np.array_equal(x, y) for x, y in zip(r["A"][k], a["A"][k])), k
+        for k, v in ga.items():
+            assert np.array_equal(r["grads"][k], v.cpu().numpy()), k
+
+
+def test_tensor_group_repeat_is_bit_identical_and_leaves_sync_words_zero(monkeypatch):
+    from multimodalfusion_amd import ops
+    metas = _metas(MECH, [300, 12, 99], [5, 77, 210])
+    runs = [run_group(metas, monkeypatch, 0.5) for _ in range(2)]
+    for k in ("hazards", "S", "loss", "risk"):
+        assert np.array_equal(runs[0][k], runs[1][k]), k
+    for k, v in runs[0]["grads"].items():
+        assert np.array_equal(v, runs[1]["grads"][k]), k
+    torch.cuda.synchronize()
+    assert int(ops.sync_words(torch.device(DEV)).abs().sum()) == 0
+
+
+@pytest.mark.parametrize("mode", ["radio_path_omic", "path_omic"])
+def test_tensor_group_on_poisoned_memory(mode, poison, monkeypatch):  # noqa: F811
+    """Workspaces and outputs pre-filled with NaN: every output finite, every gradient equal to the clean run's."""
+    metas = _metas(dict(MECH, mode=mode), [150, 9, 1100], [40, 3, 90])
+    clean = run_group(metas, monkeypatch, 0.5)
+    got = poison.run("nan", run_group, metas, monkeypatch, 0.5)
+    for k in ("hazards", "S", "loss", "risk"):
+        assert np.isfinite(got[k]).all(), k
+        assert np.array_equal(got[k], clean[k]), k
+    for k in got["A"]:
+        assert all(np.isfinite(a).all() for a in got["A"][k]), k
+    for k, v in clean["grads"].items():
+        assert np.isfinite(got["grads"][k]).all(), k
+        assert np.array_equal(got["grads"][k], v), k
+
+
+def test_tensor_group_rejects_bad_calls(monkeypatch):
+    """Argument checks: each raises before anything is launched, and a valid call afterwards still works."""
+    from multimodalfusion_amd import _lib, ops
+    metas = _metas(MECH, [64, 64], [8, 8])
+    model = _model(metas[0])
+    patients = [_patient(m) for m in metas]
+    Y, c = _labels(metas)
+    launches = []
+    real = ops.stream_ptr
+    monkeypatch.setattr(ops, "stream_ptr", lambda: launches.append(1) or real())     # every C-ABI launch asks for the stream
+
+    def refused(exc, pts, Y=Y, c=c, model=model, **kw):
+        n = len(launches)
+        with pytest.raises(exc):
+            model.nll_step_group_tensor(pts, Y, c, **kw)
+        assert len(launches) == n, "a refused call launched something"
+
+    refused(NotImplementedError, patients, model=_model(dict(metas[0], fusion="concat")))      # the concat head
+    noskip = _model(metas[0])
+    noskip.mm.skip = 0
+    refused(NotImplementedError, patients, model=noskip)                     # a configuration nll_step refuses
+    bf = [dict(p, path_features=p["path_features"].to(torch.bfloat16)) for p in patients]
+    refused((TypeError, _lib.MmfError), bf)                                  # bf16 bags
+    refused(_lib.MmfError, [patients[0]] * 65, Y=[0] * 65, c=[0.0] * 65)     # G = 65
+    empty = [patients[0], dict(patients[1], path_features=patients[1]["path_features"][:0])]
+    refused(_lib.MmfError, empty)                                            # an empty bag
+    path, radio, omic = _stacked(patients)
+    refused(_lib.MmfError, (path, radio, omic[:1]))                          # patient counts differ between branches
+    refused(_lib.MmfError, ((path[0], [128]), radio, omic))
+    refused(_lib.MmfError, patients, model=_model(dict(metas[0], K=33)))     # K = 33
+    refused(_lib.MmfError, patients, seeds={k: [1, 2] for k in BRANCHES})    # no fusion seeds
+    prev = ops.set_gemm(1)
+    try:
+        refused(_lib.MmfError, patients)                                     # bf16x3 GEMMs
+    finally:
+        ops.set_gemm(prev)
+    _seed_stream(monkeypatch, metas)
+    hz, *_ = model.nll_step_group_tensor(patients, Y, c)                     # still fine afterwards
+    torch.cuda.synchronize()
+    assert launches and bool(torch.isfinite(hz).all())
+
+
+# ---- the raw entry points on their own ------------------------------------------------------------------------------
+RAW_SEEDS = {2: 8, 3: 8}                     # the weights' seed per m, chosen on the CPU for the kink condition below
+
+
+def _raw_inputs(m, G):
+    """Weights of the tail (xavier, bias spread 0.5), embeddings v_i [G x 256] ~ N(0, 1), an upstream gradient for hid
+    and one fusion seed per patient."""
+    mode = "radio_path_omic" if m == 3 else "radio_path"
+    sd = {k: v for k, v in gen.mm_state_dict(seed=RAW_SEEDS[m], fusion="tensor", mode=mode, bias_std=0.5).items()
+          if k.startswith("mm.") or k.startswith("classifier.0")}
+    vs = [gen.normal(31 + i, (64, 256), stream=5)[:G] for i in range(m)]      # patient g's row does not depend on G
+    dhid = gen.normal(37, (64, 256), stream=6)[:G]
+    seeds = [(2654435761 * (g + 1) + 12345) & 0xFFFFFFFF for g in range(G)]
+    return sd, vs, dhid, seeds
+
+
+def _raw_weights(sd, m):
+    w = []
+    for i in range(m):
+        for j in range(3):
+            w += [_t(sd[f"mm.reduce.{i}.{j}.0.weight"]), _t(sd[f"mm.reduce.{i}.{j}.0.bias"])]
+    for k in ("mm.encoder1.0", "mm.encoder2.0"):
+        w += [_t(sd[k + ".weight"]), _t(sd[k + ".bias"])]
+    return w, _t(sd["classifier.0.weight"]), _t(sd["classifier.0.bias"])
+
+
+def _raw_names(m):
+    names = [f"mm.reduce.{i}.{j}.0.{t}" for i in range(m) for j in range(3) for t in ("weight", "bias")]
+    return names + [f"{k}.{t}" for k in ("mm.encoder1.0", "mm.encoder2.0", "classifier.0") for t in ("weight", "bias")]
+
+
+_RAW_REF = {}
+
+
+def _raw_oracle(m, G, train):
+    """torch fp64 autograd of tp.xfusion + classifier[0] (+ masks) on every patient alone, for loss = sum hid . dhid.
+    Returns (MM, hid, [dv_i], {weight gradient sums}, smallest |ReLU pre-activation|)."""
+    if (m, G, train) in _RAW_REF:
+        return _RAW_REF[(m, G, train)]
+    sd_np, vs, dhid, seeds = _raw_inputs(m, G)
+    sd = tp.to_torch(sd_np, torch.float64)
+    tv = [torch.as_tensor(v).double().requires_grad_(True) for v in vs]
+    pre, lin = [], tp._lin
+
+    def spy(sd_, name, x):
+        y = lin(sd_, name, x)
+        if name in TAIL_RELU:
+            pre.append(float(y.detach().abs().min()))
+        return y
+
+    tp._lin = spy
+    try:
+        MMs, hids = [], []
+        for g in range(G):
+            mm, cls = fusion_masks(seeds[g], m) if train else (None, None)
+            MM = tp.xfusion(sd, "mm", [v[g:g + 1] for v in tv], mm)
+            hid = torch.relu(tp._lin(sd, "classifier.0", MM))
+            MMs.append(MM)
+            hids.append(hid * cls if train else hid)
+    finally:
+        tp._lin = lin
+    MM, hid = torch.cat(MMs), torch.cat(hids)
+    (hid * torch.as_tensor(dhid).double()).sum().backward()
+    out = (MM.detach().numpy(), hid.detach().numpy(), [v.grad.numpy() for v in tv],
+           {k: sd[k].grad.numpy() for k in _raw_names(m)}, min(pre))
+    _RAW_REF[(m, G, train)] = out
+    return out
+
+
+def _raw_run(m, G, train, grads=None, accumulate=False):
+    from multimodalfusion_amd import ops
+    sd, vs, dhid, seeds = _raw_inputs(m, G)
+    w, Wc0, bc0 = _raw_weights(sd, m)
+    x2, views = ops.xfusion_group_input(G, m, 256, 512, DEV)
+    for view, v in zip(views, vs):
+        view.copy_(_t(v))
+    p = P_FUS if train else 0.0
+    MM, hid, state = ops._xfusion_group_fwd_raw(x2, m, w, Wc0, bc0, p, p, seeds)
+    wide = torch.full((G, 256 + 6), float("nan"), device=DEV)      # dhid as columns of a wider matrix
+    wide[:, 3:259] = _t(dhid)
+    dvs, gw = ops._xfusion_group_bwd_raw(wide[:, 3:259], state, grads=grads, accumulate=accumulate)
+    torch.cuda.synchronize()
+    return MM, hid, dvs, gw
+
+
+@pytest.mark.parametrize("train", [True, False])
+@pytest.mark.parametrize("m,G", [(3, 1), (3, 3), (2, 4), (3, 5), (2, 64), (3, 64)])
+def test_raw_pair_matches_fp64_autograd(m, G, train):
+    """_xfusion_group_fwd_raw / _bwd_raw on given v against torch fp64 autograd of tp.xfusion + classifier[0] with each
+    patient's masks: MM, hid at the suite's 1e-4, dv and every weight gradient at 1e-5 + 1e-4 max (test_gpu_path.compare's
+    bars), overwritten and accumulated."""
+    rMM, rhid, rdv, rgw, margin = _raw_oracle(m, G, train)
+    assert margin > KINK, margin
+    MM, hid, dvs, gw = _raw_run(m, G, train)
+    print("MM", float(np.abs(MM.cpu().numpy() - rMM).max()), "hid", float(np.abs(hid.cpu().numpy() - rhid).max()))
+    np.testing.assert_allclose(MM.cpu().numpy(), rMM, rtol=0, atol=1e-4)
+    np.testing.assert_allclose(hid.cpu().numpy(), rhid, rtol=0, atol=1e-4)
+    checks = [(f"dv{i}", dvs[i].cpu().numpy(), rdv[i]) for i in range(m)]
+    checks += [(k, g.cpu().numpy(), rgw[k]) for k, g in zip(_raw_names(m), gw)]
+    for k, got, ref in checks:
+        err, bar = float(np.abs(got - ref).max()), 1e-5 + 1e-4 * float(np.abs(ref).max())
+        print(f"  {k}: err {err:.3e} bar {bar:.3e}")
+    for k, got, ref in checks:
+        assert float(np.abs(got - ref).max()) <= 1e-5 + 1e-4 * float(np.abs(ref).max()), k
+    # accumulate: added to what the buffers hold (one fp32 rounding of the sum)
+    held = [torch.full_like(g, 0.5) for g in gw]
+    _, _, _, gw2 = _raw_run(m, G, train, grads=held, accumulate=True)
+    for k, a, b in zip(_raw_names(m), gw2, gw):
+        assert a is not b
+        np.testing.assert_allclose(a.cpu().numpy(), b.cpu().numpy() + 0.5, rtol=1e-6, atol=1e-7, err_msg=k)
+    # overwrite: whatever the buffers held is gone
+    junk = [torch.full_like(g, float("nan")) for g in gw]
+    _, _, _, gw3 = _raw_run(m, G, train, grads=junk, accumulate=False)
+    for k, a, b in zip(_raw_names(m), gw3, gw):
+        assert torch.equal(a, b), k
+
+
+@pytest.mark.parametrize("m,G", [(2, 1), (3, 5), (3, 64)])
+def test_raw_forward_without_dropout_equals_the_forward_only_pass_bitwise(m, G):
+    from multimodalfusion_amd import ops
+    sd, vs, _, _ = _raw_inputs(m, G)
+    w, Wc0, bc0 = _raw_weights(sd, m)
+    MM, hid, _, _ = _raw_run(m, G, False)
+    MM0, hid0 = ops.xfusion_infer_group([_t(v) for v in vs], w, Wc0, bc0)
+    torch.cuda.synchronize()
+    assert torch.equal(MM, MM0) and torch.equal(hid, hid0)
+
+
+@pytest.mark.parametrize("train", [True, False])
+@pytest.mark.parametrize("m", [2, 3])
+def test_raw_rows_do_not_depend_on_the_window(m, train):
+    """A patient's MM, hid and dv rows are bit for bit those of a G = 1 call on that patient alone, wherever it stands."""
+    from multimodalfusion_amd import ops
+    sd, vs, dhid, seeds = _raw_inputs(m, 64)
+    w, Wc0, bc0 = _raw_weights(sd, m)
+    MM, hid, dvs, _ = _raw_run(m, 64, train)
+    p = P_FUS if train else 0.0
+    for g in (0, 7, 8, 63):
+        x2, views = ops.xfusion_group_input(1, m, 256, 512, DEV)
+        for view, v in zip(views, vs):
+            view.copy_(_t(v[g:g + 1]))
+        MM1, hid1, state = ops._xfusion_group_fwd_raw(x2, m, w, Wc0, bc0, p, p, seeds[g:g + 1])
+        dv1, _ = ops._xfusion_group_bwd_raw(_t(dhid[g:g + 1]), state)
+        torch.cuda.synchronize()
+        assert torch.equal(MM1[0], MM[g]) and torch.equal(hid1[0], hid[g]), g
+        for a, b in zip(dv1, dvs):
+            assert torch.equal(a[0], b[g]), g

@@ -1,7 +1,9 @@
 """Compare the gfx950 assembly of two `build.py --keep-temps` builds kernel by kernel: which kernels of the first build
 are instruction for instruction the same in the second.  Labels, comments and the kernel's own (mangled) name are
 normalised; a kernel whose name gained a defaulted template argument (`..., false>` / `..., -1, false>`) is matched to
-its new name, and so is a kernel that became a template on one flag (`dense_fwd_kernel` -> `dense_fwd_kernel<false>`).  Metadata lines (.amdhsa_*) are reported separately from instructions.  --sgpr renames every SGPR
+its new name, and so is a kernel that became a template on one flag (`dense_fwd_kernel` -> `dense_fwd_kernel<false>`),
+also where the flag came with a trailing `XTrainParams` argument (`kron_dense_group_kernel<3>(p, gsplit)` ->
+`kron_dense_group_kernel<3, false>(p, gsplit, XTrainParams)`).  A unit the first build does not have is listed as new.  Metadata lines (.amdhsa_*) are reported separately from instructions.  --sgpr renames every SGPR
 (`s12`, `s[28:29]`) to one placeholder first: a change to a kernel's arguments renumbers the scalar registers of the
 whole kernel, and this leaves only the lines that changed otherwise.
 usage: isa_diff.py [--sgpr] OLD_BUILD_DIR NEW_BUILD_DIR [UNIT ...]   (units default: every unit of build.SOURCES)"""
@@ -33,11 +35,16 @@ def main():
     units = args[2:] or [s.replace(".hip", "") for s in B.SOURCES]
     for u in units:
         f = f"{u}-hip-amdgcn-amd-amdhsa-gfx950.s"
+        if not os.path.exists(os.path.join(old, f)):
+            print(f"{u}: new unit, {len(kernels(os.path.join(new, f)))} kernels")
+            continue
         a, b = kernels(os.path.join(old, f), sgpr), kernels(os.path.join(new, f), sgpr)
         same = meta_only = 0
         for k, v in sorted(a.items()):
+            tail = lambda n: re.sub(r"NS_\d+XTrainParamsE$", "", n)
             cands = [n for n in b if n == k or n.replace("Lb0EEEv", "EEv") == k or n.replace("ELb0EEEvNS", "EEvNS") == k
-                     or n.replace("ILb0EEEvNS", "ENS") == k]
+                     or n.replace("ILb0EEEvNS", "ENS") == k or tail(n).replace("ILb0EEEvNS", "ENS") == k
+                     or tail(n).replace("Lb0E", "", 1) == k]
             if not cands:
                 print(f"{u}: {k}: not found in the new build")
                 continue

@@ -4,7 +4,10 @@ steps over the same rows -- mmf_amil_nll_step_group on the pathology rows plus m
 with the model's own stacks -- in one process.  Device-event timing, warm-up first, median of three runs.  One JSON line
 per window; the yardstick is 1.10 x (c) + 0.030 ms per window (0.015 ms for each thing (c) lacks: the omic branch and the
 fused head).
-usage: mm_group_bench.py [--grouped-only] [CASE ...]   CASE = PATH:RADIO, each comma-separated sizes or GxN,
+--fusion tensor: the same windows and three legs for the tensor-fusion head -- (a) nll_step_group_tensor, (b) G nll_step
+calls on the same (tensor) model, (c) the grouped CONCAT step (nll_step_group of a concat model) over the same patients;
+(a) - (c) is then what the fusion tail costs per window.  The only bound is (a) < (b).
+usage: mm_group_bench.py [--grouped-only] [--fusion tensor] [CASE ...]   CASE = PATH:RADIO, each comma-separated sizes or GxN,
        e.g. 16x1000:16x64 (default: 16x1000:16x64 64x1000:64x150 4x10000:4x512 and a ragged 8-patient window);
        env GROUP_BENCH_ITERS (default 20);  --grouped-only: time the grouped leg alone (for a kernel trace of it)"""
 import json, os, sys
@@ -23,13 +26,22 @@ DEFAULT = [([1000] * 16, [64] * 16), ([1000] * 64, [150] * 64), ([10000] * 4, [5
 def main():
     args = sys.argv[1:]
     grouped_only = "--grouped-only" in args
+    tensor = False
+    if "--fusion" in args:
+        at = args.index("--fusion")
+        if at + 1 >= len(args) or args[at + 1] not in ("concat", "tensor"):
+            sys.exit("--fusion takes concat or tensor")
+        tensor = args[at + 1] == "tensor"
+        del args[at:at + 2]
     cases = [tuple(parse(h) for h in a.split(":")) for a in args if a != "--grouped-only"] or DEFAULT
     iters = int(os.environ.get("GROUP_BENCH_ITERS", "20"))
     dev = torch.device("cuda", 0)
     torch.manual_seed(0)
-    model = MM_MIL_Attention_fc_surv(input_dim=80, radio_fusion="concat", fusion="concat", gate=True, gate_path=True,
-                                     gate_omic=True, gate_radio=True, dropout=True, n_classes=4,
-                                     mode="radio_path_omic").to(dev).train()
+    make = lambda fusion: MM_MIL_Attention_fc_surv(input_dim=80, radio_fusion="concat", fusion=fusion, gate=True,
+                                                   gate_path=True, gate_omic=True, gate_radio=True, dropout=True,
+                                                   n_classes=4, mode="radio_path_omic").to(dev).train()
+    model = make("tensor" if tensor else "concat")
+    concat = make("concat") if tensor else None          # leg (c) of --fusion tensor
     # leg (c): each stack behind a classifier of its own width
     cls_p = torch.nn.Linear(model.attention_net_WSI[0].out_features, 4).to(dev)
     cls_r = torch.nn.Linear(model.attention_net_radio[0].out_features, 4).to(dev)
@@ -48,7 +60,13 @@ def main():
         window = ((xp, psizes), (xr, rsizes), xo)
 
         def grouped():
-            model.nll_step_group(window, Y, c, loss_scale=1.0 / G)
+            if tensor:
+                model.nll_step_group_tensor(window, Y, c, loss_scale=1.0 / G)
+            else:
+                model.nll_step_group(window, Y, c, loss_scale=1.0 / G)
+
+        def grouped_concat():
+            concat.nll_step_group(window, Y, c, loss_scale=1.0 / G)
 
         def sequential():
             for g in range(G):
@@ -68,6 +86,17 @@ def main():
         tag = {"patients": G, "path_rows": sum(psizes), "radio_rows": sum(rsizes)}
         if grouped_only:
             print(json.dumps(dict(tag, grouped_ms_window=round(t_g, 4), grouped_ms_per_patient=round(t_g / G, 4))), flush=True)
+            continue
+        if tensor:
+            t_s, t_c = timed(sequential, max(2, iters // 4)), timed(grouped_concat, iters)
+            print(json.dumps(dict(tag, fusion="tensor", path=psizes if len(set(psizes)) > 1 else f"{G}x{psizes[0]}",
+                                  radio=rsizes if len(set(rsizes)) > 1 else f"{G}x{rsizes[0]}",
+                                  grouped_ms_window=round(t_g, 4), grouped_ms_per_patient=round(t_g / G, 4),
+                                  sequential_ms_window=round(t_s, 4), sequential_ms_per_patient=round(t_s / G, 4),
+                                  grouped_concat_ms_window=round(t_c, 4), fusion_tail_ms_window=round(t_g - t_c, 4),
+                                  grouped_vs_sequential=round(t_g / t_s, 3), beats_sequential=t_g < t_s)), flush=True)
+            for p in [*model.parameters(), *concat.parameters()]:
+                p.grad = None
             continue
         t_s, t_c = timed(sequential, max(2, iters // 4)), timed(single_heads, iters)
         print(json.dumps(dict(tag, path=psizes if len(set(psizes)) > 1 else f"{G}x{psizes[0]}",
