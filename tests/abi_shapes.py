@@ -19,12 +19,19 @@ K loops run in chunks of KC = 32 (csrc/mmf_gemm_core.h:31).  Chunk classes:
   odd    an odd count >= 3: (K / KC) % 4 != 0, the launchers stay out of the deep-prefetch loop (gemm_mainloop_deep)
   four   exactly 4: one round of the deep loop on a short grid
   mult4  a multiple of 4 above 4: the deep loop's steady state
+
+The tensor-fusion tail (mmf_xfusion_infer_group, mmf_xfusion_group_forward / _backward) has a table of its own, XFUSION,
+run by tests/test_gpu_xfusion_shapes.py.  Its kernels are VALU code with fixed work units, restated below beside
+XFusion: classes are named after what a dimension does to a work unit -- lanes of a wave_dot round, rows of a dW block,
+passes and wave quarters of the dkr launch, chunks a lane of dense_segs_group_kernel keeps, slices and column blocks of
+dense_bwd_kernel, which layer sizes the shared backward buffers, patient groups and shares.
 """
 from __future__ import annotations
 
 from dataclasses import dataclass
 
 OK, ERR_ARG, ERR_SHAPE, ERR_ALIGN = 0, -1, -2, -3      # csrc/mmf_common.h:29-32
+ERR_WORKSPACE = -4                                       # csrc/mmf_common.h:33
 KC = 32
 SKC = 16                                                 # csrc/mmf_gemm_split.h:27
 TILE = 64                                                # rows and columns of the small-shape tiles (TileNT64, K-nn, K-dh)
@@ -390,7 +397,199 @@ REQUIRED_BF16 = (
     | {("bf16 forward", f) for f in ("fused, two-step L", "not the two-workgroup fused form", "unfused kernels")}
     | {("refused", ERR_SHAPE, "L=96 H=256 D=128 bf16=1")})
 
+# ---- the tensor-fusion tail: mmf_xfusion_infer_group, mmf_xfusion_group_forward / _backward -------------------------------
+GROUP_MAX = 64                                           # include/mmf_amil.h MMF_GROUP_MAX
+XF_S1 = 17                                               # sdim + 1 (csrc/mmf_xfusion_group.hip:19, csrc/mmf_mlp.hip:433)
+XB_PG = 16                                               # csrc/mmf_xfusion_group.hip:20: patients per workgroup, dkr launch
+XB_NC = 512                                              # csrc/mmf_xfusion_group.hip:21: rows of encoder1 staged per pass
+XB_ROWS = 32                                             # csrc/mmf_xfusion_group.hip:22: rows of dWe1 per workgroup
+DENSE_SEGS_MAXC = 24                                     # csrc/mmf_mlp.h:93: chunks of 64 weights a lane keeps
+XF_CAP = 64 * DENSE_SEGS_MAXC                            # 1536
+WAVE_DOT_ROUND = 256                                     # csrc/mmf_mlp.hip:212: one float4 per lane and round
+DENSE_BWD_DX_COLS, DENSE_BWD_DW_COLS = 64, 256           # csrc/mmf_mlp.hip:689: columns of a dx / a dW block
+
+
+def group_shares(G):
+    return min(G, 4)                                     # csrc/mmf_mlp.hip:573
+
+
+@dataclass(frozen=True)
+class XFusion:
+    m: int
+    dim: int
+    mmhid1: int
+    mmhid2: int
+    nhid: int
+    G: int
+    lddhid_pad: int = 0          # dhid's leading dimension is nhid + lddhid_pad
+    why: str = ""
+    sdim: int = 16
+    seed: int = 1                # of the weights and the patients' masks, chosen on the CPU (tests/xfusion_cases.py): no ReLU
+                                 # pre-activation of the fp64 oracle within KINK of 0, no patient or gradient all zero
+
+    @property
+    def K2(self):
+        return self.mmhid1 + self.m * self.dim
+
+    @property
+    def E(self):
+        return (self.sdim + 1) ** self.m
+
+    @property
+    def lddhid(self):
+        return self.nhid + self.lddhid_pad
+
+
+def xfusion_window_ok(m, sdim, mmhid1, G):
+    """csrc/mmf_api.hip xfusion_shape_ok: all that mmf_xfusion_group_infer_workspace_bytes(m, sdim, mmhid1, G) sees."""
+    return 2 <= m <= 3 and sdim == 16 and 1 <= mmhid1 <= XF_CAP and 1 <= G <= GROUP_MAX
+
+
+def xfusion_infer_rule(c):
+    """include/mmf_amil.h mmf_xfusion_infer_group ("Returns MMF_ERR_SHAPE for m outside 2..3, sdim != 16, dim % 4 != 0,
+    mmhid1 + m * dim or mmhid2 > 1536, G outside 1..MMF_GROUP_MAX"); csrc/mmf_api.hip xfusion_shape_ok and the checks of
+    mmf_xfusion_infer_group.  nhid has no cap here: classifier[0]'s rows are the grid, its K is mmhid2."""
+    if not xfusion_window_ok(c.m, c.sdim, c.mmhid1, c.G):
+        return ERR_SHAPE
+    if c.dim < 4 or c.dim % 4 != 0 or c.mmhid2 < 1 or c.nhid < 1:
+        return ERR_SHAPE
+    if c.K2 > XF_CAP or c.mmhid2 > XF_CAP:
+        return ERR_SHAPE
+    return OK
+
+
+def xfusion_train_rule(c):
+    """include/mmf_amil.h mmf_xfusion_group_forward / _backward ("... mmhid1 % 4 != 0, mmhid1 + m * dim, mmhid2 or nhid >
+    1536, G outside 1..MMF_GROUP_MAX, lddhid < nhid"); csrc/mmf_api.hip xfusion_train_shape, and mmf_xfusion_group_backward
+    for lddhid."""
+    if xfusion_infer_rule(c) != OK:
+        return ERR_SHAPE
+    if c.mmhid1 % 4 != 0 or c.nhid > XF_CAP:
+        return ERR_SHAPE
+    if c.lddhid < c.nhid:
+        return ERR_SHAPE
+    return OK
+
+
+def _dense_bwd_tags(N, K):
+    """dense_bwd_kernel (csrc/mmf_mlp.hip:642-684): a dx block sums N in four slices of (N + 3) / 4, four at a time with a
+    scalar remainder loop, over 64 columns of K; a dW block takes 256 columns of K."""
+    sl = (N + 3) // 4
+    lens = [max(0, min(N, (s + 1) * sl) - s * sl) for s in range(4)]
+    t = set()
+    if 0 in lens:
+        t.add(("dense_bwd N", "empty slices"))
+    if any(n % 4 for n in lens):
+        t.add(("dense_bwd N", "scalar remainder"))
+    if K == 1:
+        t.add(("dense_bwd K", "1"))
+    elif K % DENSE_BWD_DX_COLS:
+        t.add(("dense_bwd K", "% 64 != 0"))
+    elif K % DENSE_BWD_DW_COLS:
+        t.add(("dense_bwd K", "% 256 != 0"))
+    else:
+        t.add(("dense_bwd K", "% 256 == 0"))
+    return t
+
+
+def xfusion_tags(c):
+    """What a case of XFUSION exercises.  A case the forward-only pass admits and the training pair refuses carries both
+    the refusal and the forward-only classes."""
+    infer, train = xfusion_infer_rule(c), xfusion_train_rule(c)
+    what = f"m={c.m} sdim={c.sdim} dim={c.dim} mmhid1={c.mmhid1} mmhid2={c.mmhid2} nhid={c.nhid} G={c.G} pad={c.lddhid_pad}"
+    if infer != OK:
+        return {("refused", "both", what)}
+    t = {("m", c.m)}
+    if train != OK:
+        t.add(("refused", "training", what))
+    # wave_dot: lane l reads the float4 at 4 l, 4 l + 256, ...
+    t.add(("dim", "4: one lane" if c.dim == 4 else "below one round, an idle tail lane" if c.dim < WAVE_DOT_ROUND else
+           "256: one full round" if c.dim == WAVE_DOT_ROUND else "just past one round" if c.dim < 2 * WAVE_DOT_ROUND else
+           "two rounds or more"))
+    # encoder1's rows: XB_ROWS per workgroup of the dW launch, XB_NC per pass of the dkr launch (a wave takes a quarter)
+    rows = ("one ragged row block" if c.mmhid1 < XB_ROWS else "several row blocks, the last ragged" if c.mmhid1 % XB_ROWS else
+            "whole row blocks")
+    passes = ("below one pass" if c.mmhid1 < XB_NC else "512: one full pass" if c.mmhid1 == XB_NC else
+              "a second pass inside the first wave's quarter" if c.mmhid1 <= XB_NC + XB_NC // 4 else
+              "three passes, the last ragged" if c.mmhid1 > 2 * XB_NC and c.mmhid1 % XB_NC else "other")
+    t |= {("mmhid1 rows", rows), ("mmhid1 passes", passes), ("mmhid1 rows", rows, "m", c.m), ("mmhid1 passes", passes, "m", c.m)}
+    if c.mmhid1 % 4:
+        t.add(("mmhid1", "% 4 != 0: e1's segment of encoder2 unaligned (forward-only)"))
+    # dense_segs_group_kernel: lane l keeps W[n][l + 64 c], c < DENSE_SEGS_MAXC
+    if c.K2 <= 64:
+        t.add(("K2", "one chunk"))
+    if c.K2 % 64:
+        t.add(("K2", "% 64 != 0"))
+    if c.K2 == XF_CAP:
+        t.add(("K2", "1536: all 24 chunks full"))
+    t.add(("mmhid2", "1" if c.mmhid2 == 1 else "1536" if c.mmhid2 == XF_CAP else "% 4 != 0" if c.mmhid2 % 4 else "% 4 == 0"))
+    t.add(("nhid", "1" if c.nhid == 1 else "1536" if c.nhid == XF_CAP else
+           "% 4 != 0, lddhid > nhid" if c.nhid % 4 and c.lddhid_pad > 0 else "above the training cap" if c.nhid > XF_CAP else
+           "other"))
+    t.add(("G", "1" if c.G == 1 else "2..3: group_shares < 4" if group_shares(c.G) < 4 else
+           "64" if c.G == GROUP_MAX else "17: a ragged second patient group, G % 4 != 0" if c.G == XB_PG + 1 else "other"))
+    if train == OK:
+        # carve_xfusion_train (csrc/mmf_api.hip:1443-1457): dpre / tmpb and tmpW are sized by the larger of two layers
+        t.add(("dpre / tmpb", "classifier[0] the larger" if c.nhid > c.mmhid2 else "encoder2 the larger"))
+        t.add(("tmpW", "classifier[0] the larger" if c.nhid * c.mmhid2 > c.mmhid2 * c.K2 else "encoder2 the larger"))
+        t |= _dense_bwd_tags(c.nhid, c.mmhid2) | _dense_bwd_tags(c.mmhid2, c.K2)
+    return t
+
+
+XFUSION = [
+    XFusion(2, 4, 4, 1, 1, 1, why="every dimension at its minimum: one-wave grids, K = 1 for classifier[0], one patient", seed=2),
+    XFusion(2, 4, 4, 8, 40, 3, 6, why="nhid > mmhid2 and nhid > K2 = 12: classifier[0] sizes dpre, tmpb and tmpW; three patients", seed=1),
+    XFusion(3, 20, 20, 6, 7, 5, 1, why="m = 3 on one ragged row block; mmhid2 % 4, nhid % 4 with lddhid = nhid + 1", seed=1),
+    XFusion(2, 100, 100, 36, 12, 17, 6, why="m = 2, four row blocks (the last 4 rows); 17 patients: a second patient group of one", seed=1),
+    XFusion(3, 4, 516, 8, 4, 4, 6, why="m = 3, 17 row blocks (the last 4 rows) and a second pass of 4 rows: three waves of the dkr launch have empty ranges", seed=1),
+    XFusion(2, 4, 1528, 4, 4, 4, 6, why="m = 2, three passes (the last 504 rows); K2 = 1536: all 24 chunks of a lane full", seed=1),
+    XFusion(2, 8, 16, 1536, 4, 4, why="mmhid2 = 1536: classifier[0] over 24 full chunks, encoder2's widest grid", seed=1),
+    XFusion(2, 8, 16, 4, 1536, 4, 6, why="nhid = 1536: the widest dpre staging of dense_bwd_kernel", seed=1),
+    XFusion(2, 260, 32, 16, 8, 1, why="dim = 260: a second wave_dot round of one lane", seed=1),
+    XFusion(3, 256, 512, 64, 32, 4, 6, why="the shipped dim and mmhid1 (one round, one pass) with m = 3, narrow behind", seed=1),
+    XFusion(2, 8, 8, 8, 8, 64, 6, why="a full window of 64 patients at small dimensions", seed=31),
+    # the training pair refuses these three; the forward-only pass admits them
+    XFusion(2, 8, 5, 6, 3, 4, why="mmhid1 % 4 != 0: refused for training; forward-only, e1's segment of encoder2 is unaligned", seed=1),
+    XFusion(2, 8, 8, 4, 1537, 4, why="nhid = 1537: refused for training; forward-only, nhid has no cap", seed=2),
+    XFusion(2, 8, 8, 8, 8, 4, -1, why="lddhid < nhid: refused for training (the forward-only pass has no dhid)"),
+    # refused by both
+    XFusion(2, 6, 8, 8, 8, 2, why="dim % 4"),
+    XFusion(2, 4, 1532, 8, 8, 2, why="K2 = 1540"),
+    XFusion(2, 8, 8, 1537, 8, 2, why="mmhid2 = 1537"),
+    XFusion(2, 8, 8, 8, 8, 0, why="G = 0"),
+    XFusion(2, 8, 8, 8, 8, 65, why="G = 65"),
+    XFusion(1, 8, 8, 8, 8, 2, why="m = 1"),
+    XFusion(4, 8, 8, 8, 8, 2, why="m = 4"),
+    XFusion(2, 8, 8, 8, 8, 2, why="sdim = 8", sdim=8),
+]
+
+_XF_REFUSED = "m={} sdim={} dim={} mmhid1={} mmhid2={} nhid={} G={} pad={}"
+REQUIRED_XFUSION = (
+    {("m", 2), ("m", 3)}
+    | {("dim", d) for d in ("4: one lane", "below one round, an idle tail lane", "just past one round", "256: one full round")}
+    | {("mmhid1 rows", r) for r in ("one ragged row block", "several row blocks, the last ragged")}
+    | {("mmhid1 rows", "several row blocks, the last ragged", "m", m) for m in (2, 3)}
+    | {("mmhid1 passes", p) for p in ("a second pass inside the first wave's quarter", "three passes, the last ragged",
+                                      "512: one full pass")}
+    | {("mmhid1 passes", "a second pass inside the first wave's quarter", "m", 3),
+       ("mmhid1 passes", "three passes, the last ragged", "m", 2)}
+    | {("mmhid1", "% 4 != 0: e1's segment of encoder2 unaligned (forward-only)")}
+    | {("K2", k) for k in ("one chunk", "% 64 != 0", "1536: all 24 chunks full")}
+    | {("mmhid2", v) for v in ("1", "% 4 != 0", "1536")}
+    | {("nhid", v) for v in ("1", "% 4 != 0, lddhid > nhid", "1536", "above the training cap")}
+    | {("dpre / tmpb", s) for s in ("classifier[0] the larger", "encoder2 the larger")}
+    | {("tmpW", s) for s in ("classifier[0] the larger", "encoder2 the larger")}
+    | {("G", g) for g in ("1", "2..3: group_shares < 4", "17: a ragged second patient group, G % 4 != 0", "64")}
+    | {("dense_bwd N", "empty slices"), ("dense_bwd N", "scalar remainder"), ("dense_bwd K", "1"), ("dense_bwd K", "% 64 != 0")}
+    | {("refused", "training", _XF_REFUSED.format(2, 16, 8, 5, 6, 3, 4, 0)),
+       ("refused", "training", _XF_REFUSED.format(2, 16, 8, 8, 4, 1537, 4, 0)),
+       ("refused", "training", _XF_REFUSED.format(2, 16, 8, 8, 8, 8, 4, -1))}
+    | {("refused", "both", _XF_REFUSED.format(*v)) for v in (
+        (2, 16, 6, 8, 8, 8, 2, 0), (2, 16, 4, 1532, 8, 8, 2, 0), (2, 16, 8, 8, 1537, 8, 2, 0), (2, 16, 8, 8, 8, 8, 0, 0),
+        (2, 16, 8, 8, 8, 8, 65, 0), (1, 16, 8, 8, 8, 8, 2, 0), (4, 16, 8, 8, 8, 8, 2, 0), (2, 8, 8, 8, 8, 8, 2, 0))})
+
 TABLES = {
+    "XFUSION": (XFUSION, xfusion_tags, REQUIRED_XFUSION),
     "mmf_linear_forward": (LINEAR_FORWARD, linear_forward_tags, REQUIRED_LINEAR_FORWARD),
     "mmf_linear_backward": (LINEAR_BACKWARD, linear_backward_tags, REQUIRED_LINEAR_BACKWARD),
     "mmf_attn_net": (ATTN, attn_tags, REQUIRED_ATTN),

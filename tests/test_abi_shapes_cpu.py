@@ -1,9 +1,12 @@
-"""CPU: the admitted envelope of the scorer, the dense layer and the stack (tests/abi_shapes.py) -- the restated rules
-against the library where it refuses before any HIP call, the restated planners against the library's, and the case
-tables of tests/test_gpu_abi_shapes.py against the shape classes the rules make reachable."""
+"""CPU: the admitted envelope of the scorer, the dense layer, the stack and the tensor-fusion tail (tests/abi_shapes.py) --
+the restated rules against the library where it refuses before any HIP call, the restated planners against the library's,
+and the case tables of tests/test_gpu_abi_shapes.py and tests/test_gpu_xfusion_shapes.py against the shape classes the
+rules make reachable; for the fusion tail also the two workspace queries over a grid on both sides of every limit, and the
+fp64 oracle of every case clear of every ReLU kink under the seed the case records."""
 import ctypes as C
 import dataclasses
 
+import numpy as np
 import pytest
 
 import abi_shapes as ab
@@ -172,3 +175,126 @@ def test_strerror_and_header_state_the_dense_layer_rule():
     hdr = open(os.path.join(ROOT, "include", "mmf_amil.h")).read()
     dense = hdr[hdr.index("Dense layer on MFMA"):hdr.index("mmf_linear_backward_workspace_bytes")]
     assert "N % 4 == 0" in dense and "MMF_ERR_SHAPE" in dense and "MMF_ERR_ALIGN" in dense and "bias" in dense
+
+
+# ---- the tensor-fusion tail: the rules against both workspace queries and the entry points ---------------------------------
+XF_GRID = dict(m=(1, 2, 3, 4), sdim=(8, 16, 17), dim=(0, 4, 6, 8, 252, 256, 260, 768), mmhid1=(0, 1, 4, 5, 512, 516, 1528, 1532, 1536, 1537),
+               mmhid2=(0, 1, 6, 1536, 1537), nhid=(0, 1, 7, 1536, 1537), G=(0, 1, 3, 17, 64, 65))
+
+
+def _xf_grid():
+    import itertools
+    for m, sdim, dim, mmhid1, mmhid2, nhid, G in itertools.product(*(XF_GRID[k] for k in ("m", "sdim", "dim", "mmhid1", "mmhid2", "nhid", "G"))):
+        yield ab.XFusion(m, dim, mmhid1, mmhid2, nhid, G, sdim=sdim)
+
+
+def test_xfusion_grid_straddles_every_limit():
+    got = {"infer": set(), "train": set()}
+    K2 = set()
+    for c in _xf_grid():
+        got["infer"].add(ab.xfusion_infer_rule(c))
+        got["train"].add(ab.xfusion_train_rule(c))
+        if ab.xfusion_infer_rule(dataclasses.replace(c, dim=4, mmhid1=4)) == ab.OK:
+            K2.add(c.K2)
+    assert got == {"infer": {ab.OK, ab.ERR_SHAPE}, "train": {ab.OK, ab.ERR_SHAPE}}
+    assert {1536, 1540} <= K2 and any(k > 1536 and k - 1536 < 8 for k in K2)        # the cap from both sides
+    trains = [c for c in _xf_grid() if ab.xfusion_train_rule(c) == ab.OK]
+    only_infer = [c for c in _xf_grid() if ab.xfusion_infer_rule(c) == ab.OK and ab.xfusion_train_rule(c) != ab.OK]
+    assert len(trains) > 500 and {c.mmhid1 % 4 != 0 or c.nhid > 1536 for c in only_infer} == {True}
+    assert any(c.mmhid1 % 4 for c in only_infer) and any(c.nhid > 1536 for c in only_infer)
+
+
+def test_xfusion_workspace_queries_answer_zero_exactly_where_the_rules_refuse():
+    """mmf_xfusion_group_workspace_bytes against xfusion_train_rule at every grid point; the forward-only query sees only
+    (m, sdim, mmhid1, G): against xfusion_window_ok.  Where they accept: at least the buffers the header names."""
+    m_, l = _lib()
+    qt, qi = l.mmf_xfusion_group_workspace_bytes, l.mmf_xfusion_group_infer_workspace_bytes
+    n_ok = 0
+    for c in _xf_grid():
+        got = qt(c.m, c.dim, c.sdim, c.mmhid1, c.mmhid2, c.nhid, c.G)
+        if ab.xfusion_train_rule(c) != ab.OK:
+            assert got == 0, c
+            continue
+        n_ok += 1
+        gate, bits = c.G * c.m * 16, c.G * ((c.E + 63) // 64 * 2)
+        # o, h, z, gm, dpo, dz, dph; the keep bits; d of the product; dMM; with accumulate the dense backward's fresh dW and
+        # db of classifier[0] and of encoder2, one after the other, go through the workspace: the larger of each
+        named = 7 * gate + bits + c.G * c.E + c.G * c.mmhid2 + max(c.mmhid2 * c.K2, c.nhid * c.mmhid2) + max(c.mmhid2, c.nhid)
+        assert got >= 4 * named, (c, got, 4 * named)
+    assert n_ok > 500
+    for m in XF_GRID["m"]:
+        for sdim in XF_GRID["sdim"]:
+            for mmhid1 in XF_GRID["mmhid1"]:
+                for G in XF_GRID["G"]:
+                    got = qi(m, sdim, mmhid1, G)
+                    if not ab.xfusion_window_ok(m, sdim, mmhid1, G):
+                        assert got == 0, (m, sdim, mmhid1, G)
+                    else:
+                        assert got >= 4 * (G * m * 16 + G * mmhid1), (m, sdim, mmhid1, G)      # o and encoder1's output
+
+
+def _xf_calls(l, c, nbytes):
+    """The three entry points on never-dereferenced pointers: a refused shape returns its code before any pointer is read,
+    an admitted one goes on to the workspace check (nbytes = 0: MMF_ERR_WORKSPACE, still before any launch)."""
+    from test_mm_infer_group_abi_cpu import _weights
+    fake = P[0]
+    w = _weights(fake, m=c.m, dim=c.dim, sdim=c.sdim, mmhid1=c.mmhid1, mmhid2=c.mmhid2, nhid=c.nhid)
+    v = (C.c_void_p * 3)(fake, fake, fake)
+    from multimodalfusion_amd import _lib as m_
+    g = m_.XFusionGrads(dWe1=fake, dbe1=fake, dWe2=fake, dbe2=fake, dWc0=fake, dbc0=fake)
+    for n in ("dWh", "dbh", "dWz", "dbz", "dWo", "dbo"):
+        for i in range(3):
+            getattr(g, n)[i] = fake
+    infer = l.mmf_xfusion_infer_group(C.byref(w), v, c.G, fake, nbytes, fake, fake, None)
+    fwd = l.mmf_xfusion_group_forward(C.byref(w), fake, c.G, C.c_float(0.25), C.c_float(0.25), fake, None, fake, nbytes, fake,
+                                      fake, None)
+    bwd = l.mmf_xfusion_group_backward(C.byref(w), fake, c.G, C.c_float(0.25), C.c_float(0.25), fake, None, fake, fake, fake,
+                                       c.lddhid, fake, nbytes, fake, C.byref(g), 0, None)
+    return infer, fwd, bwd
+
+
+def test_xfusion_entry_points_follow_the_rules_before_any_launch():
+    """Every case of the table and a thinned grid: a refusal is MMF_ERR_SHAPE, an admitted shape reaches the workspace
+    check.  The forward has no dhid: lddhid is the backward's alone."""
+    m_, l = _lib()
+    cases = list(ab.XFUSION) + [c for i, c in enumerate(_xf_grid()) if i % 37 == 0]
+    cases += [dataclasses.replace(c, lddhid_pad=p) for c in ab.accepted(ab.XFUSION, ab.xfusion_train_rule)[:3] for p in (-1, 0, 5)]
+    for c in cases:
+        infer, fwd, bwd = _xf_calls(l, c, 0)
+        want = lambda code: ab.ERR_WORKSPACE if code == ab.OK else code
+        assert infer == want(ab.xfusion_infer_rule(c)), c
+        assert fwd == want(ab.xfusion_train_rule(dataclasses.replace(c, lddhid_pad=0))), c
+        assert bwd == want(ab.xfusion_train_rule(c)), c
+
+
+def test_xfusion_table_is_what_the_issue_asks_for():
+    acc_t, acc_i = ab.accepted(ab.XFUSION, ab.xfusion_train_rule), ab.accepted(ab.XFUSION, ab.xfusion_infer_rule)
+    assert set(acc_t) <= set(acc_i) and 10 <= len(acc_i) <= 14
+    assert {c.dim for c in acc_t} >= {4, 256, 260} and any(8 <= c.dim <= 252 for c in acc_t)
+    assert {c.mmhid1 for c in acc_t} >= {512, 516, 1528} and any(c.mmhid1 < 32 for c in acc_t)
+    assert any(c.mmhid1 % 4 for c in acc_i) and not any(c.mmhid1 % 4 for c in acc_t)
+    assert {c.K2 for c in acc_t} >= {12, 1536} and {c.mmhid2 for c in acc_t} >= {1, 1536} and {c.nhid for c in acc_t} >= {1, 1536}
+    assert {c.G for c in acc_t} >= {1, 17, 64} and {2, 3} & {c.G for c in acc_t}
+    assert all(c.G <= 17 for c in acc_i if not (c.G == 64 and c.K2 <= 64 and c.mmhid2 <= 64 and c.nhid <= 64))
+    assert all(c.mmhid1 <= 516 for c in acc_i if c.m == 3)
+    for c in acc_t:          # what the header says of x2 and dhid
+        assert c.K2 % 4 == 0 and c.lddhid >= c.nhid
+    whys = {c.why.split(":")[0] for c in ab.XFUSION if ab.xfusion_infer_rule(c) != ab.OK or ab.xfusion_train_rule(c) != ab.OK}
+    assert {"dim % 4", "K2 = 1540", "mmhid2 = 1537", "G = 0", "G = 65", "m = 1", "m = 4", "sdim = 8", "lddhid < nhid",
+            "mmhid1 % 4 != 0", "nhid = 1537"} <= whys
+
+
+def test_xfusion_oracles_keep_clear_of_every_relu_kink():
+    """Under the seed each case records, no ReLU pre-activation of the fusion tail, of any patient, in train or eval mode,
+    lies within KINK of zero in the fp64 oracle: fp32 and fp64 take the same side of every ReLU, and the GPU file excuses no
+    unit; and no case is dead behind a ReLU or a mask.  Also: the shipped shape is admitted by both rules."""
+    import xfusion_cases as xc
+    for c in ab.accepted(ab.XFUSION, ab.xfusion_infer_rule):
+        for train in ((True, False) if ab.xfusion_train_rule(c) == ab.OK else (False,)):
+            MM, hid, dv, gw, margin = xc.oracle(c, train)
+            assert margin > 2 * xc.KINK, (c, train, margin)
+            # and the case checks something: every patient has a live unit in MM and in hid, no gradient is all zero
+            assert (np.abs(MM).max(1) > 0).all() and (np.abs(hid).max(1) > 0).all(), (c, train)
+            assert all(np.abs(v).max() > 0 for v in dv) and all(np.abs(v).max() > 0 for v in gw.values()), (c, train)
+    for m in (2, 3):
+        assert ab.xfusion_train_rule(ab.XFusion(m, 256, 512, 512, 256, 64)) == ab.xfusion_infer_rule(ab.XFusion(m, 256, 512, 512, 256, 64)) == ab.OK

@@ -88,14 +88,15 @@ def run_per_patient(metas, monkeypatch, loss_scale):
     return out
 
 
-def fusion_masks(seed, m, T=None):
+def fusion_masks(seed, m, T=None, mmhid1=512, mmhid2=512, nhid=256):
     """The seven masks of the fusion tail under one fusion seed, as test_gpu_omic_mm.test_mm_tensor_train_mode_masks builds
-    them: sites i (o_i), 8 (product), 9, 10 (encoders), 11 (classifier[2])."""
+    them: sites i (o_i), 8 (product), 9, 10 (encoders), 11 (classifier[2]); the widths of encoder1, encoder2 and
+    classifier[0] default to the shipped model's."""
     T = T or (lambda a: torch.as_tensor(np.asarray(a)).double())
     mk = lambda site, c: T(gen.drop_scale_mask(seed, site, 1, c, P_FUS, np.float64))
     mm = {f"o{i}": mk(i, 16) for i in range(m)}
-    mm.update(post=mk(8, 17 ** m), enc1=mk(9, 512), enc2=mk(10, 512))
-    return mm, mk(11, 256)
+    mm.update(post=mk(8, 17 ** m), enc1=mk(9, mmhid1), enc2=mk(10, mmhid2))
+    return mm, mk(11, nhid)
 
 
 _ORACLE = {}
