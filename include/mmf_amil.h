@@ -649,6 +649,27 @@ int mmf_hazards_backward(const float* g_hazards, const float* g_S, const float* 
                          const float* hazards, int32_t B, int32_t K, float* dlogits, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Bag feed: a grouped window out of bags that stay resident in HBM across epochs (feed.ResidentBagCache).
+ * ------------------------------------------------------------------------------------------- */
+/* Rows of G bags, each contiguous somewhere in HBM, into rows offsets[g] .. offsets[g+1]-1 of one [offsets[G] x L]
+ * matrix per plane (a pathology window: 1 plane; a radio window: one per modality), in ONE launch.
+ * Storage types: src_bf16 / dst_bf16 != 0 say bf16, else fp32, for every source / every destination.  fp32 -> fp32 and
+ * bf16 -> bf16 copy bit for bit; bf16 -> fp32 widens exactly; fp32 -> bf16 rounds to nearest even (the bits of torch's
+ * tensor.to(torch.bfloat16) for every finite value, +-0, +-inf and denormals; a NaN stays a NaN, its payload does not).
+ * Refused before any launch, nothing written: MMF_ERR_SHAPE for G outside 1..MMF_GROUP_MAX, nplane outside 1..4, an empty
+ * bag or offsets not strictly increasing from 0, L % 8 != 0 (the unit of work is 16 bytes of the narrower type);
+ * MMF_ERR_ARG for a null pointer (offsets, src, dst, or any entry of src / dst); MMF_ERR_ALIGN for a source or a
+ * destination that is not 16-byte aligned.
+ * Rows of a destination beyond offsets[G] are not touched.  Whether a source overlaps a destination is the caller's
+ * business: the result is then unspecified.  The call keeps no state, allocates nothing and copies no table to the
+ * device (the pointer and offset tables travel in the kernel arguments); no workgroup waits for another and there are no
+ * atomics, so the result is deterministic.  Byte offsets are 64-bit: sources and destinations may lie anywhere. */
+int mmf_bag_gather(const int64_t* offsets /* HOST [G+1] */, int32_t G, int32_t nplane /* 1..4 */,
+                   const void* const* src /* HOST [nplane*G] device pointers, plane-major */,
+                   void* const* dst /* HOST [nplane] device pointers, row pitch L */,
+                   int32_t L, int32_t src_bf16, int32_t dst_bf16, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Kernel trace: per-kernel device time of the attention-stack entry points, from HIP events recorded on the LAUNCH
  * stream around every kernel of a call whose desc->trace is set (bench.py's roofline leg).  A trace is a caller-owned
  * object (create / destroy); calls that carry the same trace must not run concurrently.  capacity = kernel launches

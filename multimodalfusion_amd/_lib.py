@@ -231,6 +231,8 @@ SYMBOLS = {
     "mmf_ranking_loss": (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 3 + [C.c_void_p] * 3),
     "mmf_hazards_forward": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 5),
     "mmf_hazards_backward": (C.c_int, [C.c_void_p] * 4 + [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "mmf_bag_gather": (C.c_int, [C.POINTER(C.c_int64), C.c_int32, C.c_int32, C.POINTER(C.c_void_p),
+                                 C.POINTER(C.c_void_p), C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "mmf_trace_create": (C.c_void_p, [C.c_int32]),
     "mmf_trace_destroy": (None, [C.c_void_p]),
     "mmf_trace_dump": (C.c_int, [C.c_void_p, C.c_char_p, C.c_size_t]),

@@ -182,7 +182,7 @@ class RankShard:
     only those bags are read from disk, collated and copied.  Iterating yields the reference's batch tuples in
     position order; `n_total` is the length of the whole (unsharded) loader, `position(i)` the loader position of the
     i-th yielded batch.  Works for a torch DataLoader (a new DataLoader over the same dataset whose batch sampler is
-    the strided view of the original one), for a DevicePrefetcher around one, for indexable sequences, and for any
+    the strided view of the original one), for a DevicePrefetcher or a ResidentBagCache around one, for indexable sequences, and for any
     other sized iterable (there the skipped items are still produced by the iterable, then dropped)."""
 
     def __init__(self, loader, rank: int, world: int):
@@ -194,6 +194,8 @@ class RankShard:
         r, w = self.rank, self.world
         if isinstance(loader, DevicePrefetcher):
             return DevicePrefetcher(self._shard(loader.loader), loader.device, loader.depth, loader.path_dtype)
+        if isinstance(loader, ResidentBagCache):
+            return loader.shard(r, w, self._shard)       # the rank's own cache, kept from one epoch's RankShard to the next's
         if isinstance(loader, torch.utils.data.DataLoader):
             kw = dict(collate_fn=loader.collate_fn, num_workers=loader.num_workers, pin_memory=loader.pin_memory,
                       timeout=loader.timeout, worker_init_fn=loader.worker_init_fn)
@@ -210,3 +212,320 @@ class RankShard:
 
     def __iter__(self):
         return iter(self._src)
+
+
+# ---- bags resident in HBM across epochs ----------------------------------------------------------------------------
+def _rng_state(gen):
+    return torch.get_rng_state() if gen is None else gen.get_state()
+
+
+def _set_rng_state(gen, state):
+    torch.set_rng_state(state) if gen is None else gen.set_state(state)
+
+
+class _StridedIter:
+    """Positions rank, rank + world, ... of a sized iterable, itself sized and iterable again every epoch."""
+
+    def __init__(self, base, rank, world):
+        self.base, self.rank, self.world = base, rank, world
+
+    def __len__(self):
+        return (len(self.base) - self.rank + self.world - 1) // self.world
+
+    def __iter__(self):
+        import itertools
+        return itertools.islice(iter(self.base), self.rank, None, self.world)
+
+
+class _StridedSeq(_StridedIter):
+    """The same of an indexable sequence: only the rank's positions are ever read."""
+
+    def __getitem__(self, i):
+        return self.base[self.rank + i * self.world]
+
+    def __iter__(self):
+        return (self[i] for i in range(len(self)))
+
+
+class _Arena:
+    """Device memory of a ResidentBagCache: a few large uint8 slabs, each taken once and never returned to the allocator
+    while the cache lives, handed out by bump allocation at 256-byte alignment."""
+    ALIGN = 256
+
+    def __init__(self, capacity_bytes, device, slab_bytes=1 << 30):
+        self.capacity, self.device, self.slab_bytes = int(capacity_bytes), device, int(slab_bytes)
+        self.slabs, self.reserved, self.top, self.used = [], 0, 0, 0
+
+    @classmethod
+    def round_up(cls, n):
+        return (int(n) + cls.ALIGN - 1) // cls.ALIGN * cls.ALIGN
+
+    def take(self, nbytes):
+        """A [nbytes] uint8 view (nbytes a multiple of ALIGN) at a 256-byte aligned address, or None: no room left."""
+        if not self.slabs or self.top + nbytes > self.slabs[-1].numel():
+            size = min(max(nbytes, self.slab_bytes), self.capacity - self.reserved)
+            if size < nbytes:
+                return None
+            slab = torch.empty(size + self.ALIGN, dtype=torch.uint8, device=self.device)
+            self.slabs.append(slab[(-slab.data_ptr()) % self.ALIGN:][:size])
+            self.reserved += size
+            self.top = 0
+        out = self.slabs[-1][self.top:self.top + nbytes]
+        self.top += nbytes
+        self.used += nbytes
+        return out
+
+
+class _Resident:
+    """One batch kept in the arena: its leaves (the radio modalities in the loader's order, then path, genomic, label, c --
+    arena views, or whatever the loader gave where that was no tensor), the dtype each is delivered in, event_time, and
+    the event recorded behind its copies."""
+    __slots__ = ("names", "leaves", "deliver", "event_time", "event", "nbytes")
+
+
+class ResidentBagCache:
+    """Feeds a training or evaluation loop from HBM from the second epoch on: wraps whatever DevicePrefetcher wraps (or a
+    DevicePrefetcher, whose path_dtype and loader it takes over) and yields the six-tuple a DevicePrefetcher around the
+    same loader yields -- same tensors, same devices; sentinels and event_time handled as there -- but every batch it has
+    seen stays on the device, in an arena of a few large slabs (bump allocation, 256-byte aligned, never freed).  Wrap the
+    loader ONCE, outside the epoch loop: the cache is the state.
+
+    Keys and order.  For a torch DataLoader the key of a batch is its dataset indices, and each epoch's order is drawn
+    from the loader's own batch_sampler, consuming the torch RNG exactly as iterating the loader would (the iterator's
+    base seed first, then the sampler's draws): shuffled and weighted samplers visit the same subjects in the same order
+    with or without the cache, and an index drawn twice in one epoch (WeightedRandomSampler samples with replacement) hits
+    the second time.  Indexable sequences and other sized iterables are keyed by POSITION, which is only right when
+    their order is the same every epoch.
+
+    Hits and misses.  A hit is served from the arena.  The misses of an epoch are loaded in order, ahead of need, by a
+    DataLoader over just those batches (the _StridedBatches technique of RankShard) with the pinned, side-stream,
+    event-per-batch staging of DevicePrefetcher, `depth` batches in flight, and are interleaved with the hits in epoch
+    order.  A missed batch is admitted whenever it still fits in `capacity_bytes` (default: half of the free device
+    memory at construction).  Nothing is ever evicted: under a cyclic scan of the epochs least-recently-used is the
+    worst policy (every batch is thrown out just before it is needed again), and "whoever got in stays" keeps
+    capacity / cohort of the epochs' traffic off PCIe.  A batch that does not fit flows through every epoch as it would
+    through a DevicePrefetcher.  stats() counts hits, misses, resident bytes and the batches refused for space.
+
+    Storage type.  store_dtype=None keeps a bag as it is delivered: its H2D copy lands directly in its arena slot, and
+    the delivered tensor is a view of the arena -- no second copy, no launch.  store_dtype=torch.bfloat16 narrows fp32
+    bags ([n x L], L % 8 == 0) into the arena with ops.bag_gather on the copy stream, so the same HBM holds twice the
+    cohort.  That is LOSSY (round to nearest even) and opt-in; every delivery then widens out of the arena, in the first
+    epoch too, so all epochs see the same values x.to(bfloat16).float() -- except a consumer that takes bf16 bags
+    (path_dtype=torch.bfloat16 on the wrapped feed), which gets the view.  The delivered dtype follows the wrapped feed's
+    path_dtype rule: the pathology bag in path_dtype when that is set, everything else as the loader gave it.
+
+    Streams, as DevicePrefetcher: the compute stream waits for the batch's event; arena views need no record_stream
+    (the arena is never freed); a widened temporary is made on the consuming stream.  A delivered bag carries the
+    attribute `_mmf_resident` (True: it is an arena view; a tensor: the arena view it was widened from), by which the
+    grouped loops take it by reference (utils/core_utils.py: _HeldBags)."""
+
+    def __init__(self, loader, device=None, capacity_bytes=None, store_dtype=None, depth=2):
+        self.path_dtype = None
+        if isinstance(loader, DevicePrefetcher):
+            self.path_dtype, device = loader.path_dtype, loader.device if device is None else device
+            loader = loader.loader
+        if store_dtype not in (None, torch.bfloat16):
+            raise ValueError("store_dtype is None (keep as delivered) or torch.bfloat16")
+        self.loader, self.store_dtype, self.depth = loader, store_dtype, max(1, int(depth))
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        self.stream = torch.cuda.Stream(self.device) if self.device.type == "cuda" else None
+        if capacity_bytes is None:
+            capacity_bytes = torch.cuda.mem_get_info(self.device)[0] // 2
+        self.capacity_bytes = int(capacity_bytes)
+        self.arena = _Arena(self.capacity_bytes, self.device)
+        self.items = {}
+        self.hits = self.misses = 0
+        self._refused = set()
+        self._shards = {}
+
+    def __len__(self):
+        return len(self.loader)
+
+    def stats(self):
+        return dict(hits=self.hits, misses=self.misses, items=len(self.items), resident_bytes=self.arena.used,
+                    refused=len(self._refused))
+
+    def shard(self, rank, world, shard):
+        """The cache of rank `rank` of `world` (RankShard): over `shard(self.loader)`, made once and kept, so that the
+        rank's bags stay resident from one epoch's RankShard to the next's."""
+        key = (int(rank), int(world))
+        if key not in self._shards:
+            ld = self.loader
+            part = shard(ld) if isinstance(ld, torch.utils.data.DataLoader) \
+                else (_StridedSeq if hasattr(ld, "__getitem__") else _StridedIter)(ld, key[0], key[1])
+            sub = ResidentBagCache(part, self.device, self.capacity_bytes, self.store_dtype, self.depth)
+            sub.path_dtype = self.path_dtype
+            self._shards[key] = sub
+        return self._shards[key]
+
+    # -- the epoch's order ---------------------------------------------------------------------------------------
+    def _sampled(self):
+        ld = self.loader
+        return isinstance(ld, torch.utils.data.DataLoader) and not isinstance(ld.dataset, torch.utils.data.IterableDataset)
+
+    def _draw(self):
+        """(keys, what to fetch a miss by) of this epoch, in order."""
+        ld = self.loader
+        if not self._sampled():
+            return list(range(len(ld))), list(range(len(ld)))
+        self._rng0 = _rng_state(ld.generator)
+        torch.empty((), dtype=torch.int64).random_(generator=ld.generator)     # the base seed iter(loader) draws first
+        if ld.batch_sampler is not None:
+            fetch = [list(b) for b in ld.batch_sampler]
+            return [tuple(b) for b in fetch], fetch
+        fetch = list(ld.sampler)
+        return fetch, fetch
+
+    def _miss_iter(self, fetch, flags):
+        """The epoch's missed batches (fetch[i] where flags[i]), host side, in order."""
+        ld = self.loader
+        if not any(flags):
+            return iter(())
+        if self._sampled():
+            kw = dict(collate_fn=ld.collate_fn, num_workers=ld.num_workers, pin_memory=ld.pin_memory, timeout=ld.timeout,
+                      worker_init_fn=ld.worker_init_fn, generator=ld.generator)
+            if ld.num_workers > 0:
+                kw.update(prefetch_factor=ld.prefetch_factor)
+            want = [f for f, m in zip(fetch, flags) if m]
+            sub = torch.utils.data.DataLoader(ld.dataset, batch_sampler=want, **kw) if ld.batch_sampler is not None \
+                else torch.utils.data.DataLoader(ld.dataset, sampler=want, batch_size=None, **kw)
+            after = _rng_state(ld.generator)
+            _set_rng_state(ld.generator, self._rng0)     # its iterator draws the base seed the wrapped loader's would have
+            it = iter(sub)
+            _set_rng_state(ld.generator, after)
+            return it
+        if hasattr(ld, "__getitem__"):
+            return (ld[i] for i, m in zip(fetch, flags) if m)
+        import itertools
+        return itertools.compress(iter(ld), flags)
+
+    # -- staging ---------------------------------------------------------------------------------------------------
+    def _on_copy_stream(self):
+        import contextlib
+        return torch.cuda.stream(self.stream) if self.stream is not None else contextlib.nullcontext()
+
+    def _event(self):
+        if self.stream is None:
+            return None
+        ev = torch.cuda.Event()
+        ev.record(self.stream)
+        return ev
+
+    def _stored_dtype(self, t, is_path):
+        bag = t.dim() == 2 and t.shape[1] > 1
+        if bag and t.dtype == torch.float32 and t.shape[1] % 8 == 0 and t.shape[0] >= 1 and (
+                self.store_dtype == torch.bfloat16 or is_path and self.path_dtype == torch.bfloat16):
+            return torch.bfloat16
+        return t.dtype
+
+    def _stage(self, key, batch):
+        """Copies of one missed batch issued on the copy stream: into the arena when it fits (-> its _Resident, now in
+        self.items), else as DevicePrefetcher stages it (-> the device tuple and its event)."""
+        from . import ops
+        radio, path, genomic, label, event_time, c = batch
+        if torch.is_tensor(genomic):
+            genomic = genomic.float()
+        names = list(radio.keys())
+        leaves = [radio[k] for k in names] + [path, genomic, label, c]
+        i_path = len(names)
+        pin = _pin if self.device.type == "cuda" else (lambda t: t)
+        stored = [self._stored_dtype(t, i == i_path) if torch.is_tensor(t) else None for i, t in enumerate(leaves)]
+        sizes = [_Arena.round_up(max(t.numel(), 1) * sd.itemsize) if sd is not None else 0 for t, sd in zip(leaves, stored)]
+        block = self.arena.take(sum(sizes))
+        with self._on_copy_stream():
+            if block is None:
+                self._refused.add(key)
+                move = lambda t: pin(t).to(self.device, non_blocking=True) if torch.is_tensor(t) else t
+                dev = [move(t) for t in leaves]
+                p = dev[i_path]
+                if self.path_dtype is not None and torch.is_tensor(p) and p.dim() == 2 and p.shape[1] > 1 \
+                        and p.dtype != self.path_dtype:
+                    dev[i_path] = p.to(self.path_dtype)
+                out = (dict(zip(names, dev[:i_path])), dev[i_path], dev[i_path + 1], dev[i_path + 2], event_time,
+                       dev[i_path + 3])
+                return out, self._event()
+            self._refused.discard(key)
+            it = _Resident()
+            it.names, it.event_time, it.nbytes, it.leaves, it.deliver = names, event_time, sum(sizes), [], []
+            at = 0
+            for i, (t, sd, nb) in enumerate(zip(leaves, stored, sizes)):
+                if sd is None:
+                    it.leaves.append(t)
+                    it.deliver.append(None)
+                    continue
+                slot = block[at:at + t.numel() * sd.itemsize].view(sd).view(t.shape)
+                at += nb
+                if sd == t.dtype:
+                    slot.copy_(pin(t), non_blocking=True)           # the H2D copy lands in the arena: no second copy
+                else:
+                    ops.bag_gather([[pin(t).to(self.device, non_blocking=True)]], [slot])      # narrowed on the copy stream
+                slot._mmf_resident = True
+                it.leaves.append(slot)
+                it.deliver.append(self.path_dtype if i == i_path and self.path_dtype is not None and t.dim() == 2
+                                  and t.shape[1] > 1 else t.dtype)
+            it.event = self._event()
+        self.items[key] = it
+        return it, it.event
+
+    def _deliver(self, it):
+        """The six-tuple of a resident batch on the current stream."""
+        from . import ops
+        if it.event is not None:
+            torch.cuda.current_stream(self.device).wait_event(it.event)
+        out = []
+        for t, dd in zip(it.leaves, it.deliver):
+            if dd is not None and t.dtype != dd and t.shape[1] % 8:
+                t = t.to(dd)                           # a width the gather does not take: the wrapped feed's conversion
+            elif dd is not None and t.dtype != dd:     # a bf16-stored bag for an fp32 consumer: widened, exactly
+                wide = torch.empty(t.shape, dtype=dd, device=t.device)
+                ops.bag_gather([[t]], [wide])
+                wide._mmf_resident = t
+                t = wide
+            out.append(t)
+        n = len(it.names)
+        return dict(zip(it.names, out[:n])), out[n], out[n + 1], out[n + 2], it.event_time, out[n + 3]
+
+    def __iter__(self):
+        keys, fetch = self._draw()
+        left, flags, seen = {}, [], set()
+        for k in keys:
+            left[k] = left.get(k, 0) + 1
+            flags.append(k not in self.items and k not in seen)
+            seen.add(k)
+        miss_keys = iter([k for k, m in zip(keys, flags) if m])
+        host = self._miss_iter(fetch, flags)
+        q, spill = deque(), {}
+
+        def stage_next():
+            try:
+                batch = next(host)
+            except StopIteration:
+                return
+            q.append(self._stage(next(miss_keys), batch))
+
+        for _ in range(self.depth):
+            stage_next()
+        for k, miss in zip(keys, flags):
+            left[k] -= 1
+            if miss:
+                self.misses += 1
+                got, ev = q.popleft()
+                stage_next()
+            else:
+                self.hits += 1
+                got, ev = spill[k] if k in spill else (self.items[k], None)
+            if isinstance(got, _Resident):
+                yield self._deliver(got)
+                continue
+            # not resident (no room): through, as DevicePrefetcher delivers it; kept for a repeat later in this epoch
+            if ev is not None:
+                cur = torch.cuda.current_stream(self.device)
+                cur.wait_event(ev)
+                for t in list(got[0].values()) + [got[1], got[2], got[3], got[5]]:
+                    if torch.is_tensor(t) and t.is_cuda:
+                        t.record_stream(cur)
+            if left[k]:
+                spill[k] = (got, ev)
+            else:
+                spill.pop(k, None)
+            yield got

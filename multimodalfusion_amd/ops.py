@@ -408,6 +408,39 @@ def _group_table(sizes, rows, Y, c, seeds=None, train=True, labels=True):
     return sizes, Y, c, offs, grp
 
 
+def bag_gather(planes, dst):
+    """mmf_bag_gather: the bags of a grouped window, each contiguous somewhere in HBM, into the leading rows of one
+    matrix per plane, in ONE launch on the current stream.  planes: n_plane (1 .. 4) lists of the same G bags' tensors
+    ([n_g x L], fp32 or bf16, one type for all); dst: n_plane tensors [rows >= sum n_g x L] of row pitch L (or one
+    [n_plane x rows x L] tensor), fp32 or bf16: the storage type is converted on the way (narrowing rounds to nearest
+    even, as tensor.to(torch.bfloat16)).  Rows of dst beyond sum n_g are left alone.  Returns the bags' sizes."""
+    planes = [list(p) for p in planes]
+    dst = list(dst)
+    nplane, G = len(planes), len(planes[0]) if planes else 0
+    if nplane < 1 or nplane > 4 or len(dst) != nplane or any(len(p) != G for p in planes):
+        raise _lib.MmfError(f"bag_gather takes 1 .. 4 planes of the same bags and one destination each, got {nplane} / {len(dst)}")
+    if G < 1 or G > GROUP_MAX:
+        raise _lib.MmfError(f"a group holds 1 .. {GROUP_MAX} bags, got {G}")
+    store = {torch.float32: 0, torch.bfloat16: 1}
+    sdt, ddt, L = planes[0][0].dtype, dst[0].dtype, int(dst[0].shape[-1])
+    if sdt not in store or ddt not in store:
+        raise _lib.MmfError(f"bag_gather moves fp32 and bf16 bags, got {sdt} -> {ddt}")
+    sizes = [int(x.shape[0]) for x in planes[0]]
+    for p in planes:
+        if any(x.dim() != 2 or x.dtype != sdt or int(x.shape[1]) != L for x in p) or [int(x.shape[0]) for x in p] != sizes:
+            raise _lib.MmfError(f"every plane holds the same [n_g x {L}] bags of one storage type")
+    rows = sum(sizes)
+    if any(d.dim() != 2 or d.dtype != ddt or int(d.shape[1]) != L or int(d.shape[0]) < rows for d in dst):
+        raise _lib.MmfError(f"every destination is [>= {rows} x {L}] of one storage type")
+    offs = (C.c_int64 * (G + 1))()
+    for i, n in enumerate(sizes):
+        offs[i + 1] = offs[i] + n
+    src = (C.c_void_p * (nplane * G))(*[ptr(x) for p in planes for x in p])
+    out = (C.c_void_p * nplane)(*[ptr(d) for d in dst])
+    check(lib().mmf_bag_gather(offs, G, nplane, src, out, L, store[sdt], store[ddt], stream_ptr()), "mmf_bag_gather")
+    return sizes
+
+
 def _radio_operands(xs, Wr, br, kind, dWr=None, dbr=None):
     """The modality tensors xs (2 .. 4, each [sum N x k] fp32) and reduce_dim (Wr [k x nseg k], br [k]; dWr, dbr: its
     gradient buffers, None for a forward-only call) of a grouped radio `kind` ("step" / "pass"), checked.

@@ -168,7 +168,11 @@ class _HeldBags:
     evaluation pass's).  Each bag is copied straight into its rows of one reusable device buffer [n_mod x rows x L] (no
     concatenation pass; fp32, or bf16 pathology bags in an evaluation pass): the pathology head's bag is one [n x L]
     tensor, the radiology head's one per modality.  A bag that would take the group past ops.GROUP_MAX bags or the row
-    limit, or one of the other storage type, flushes what is held first (the window then runs as several grouped calls)."""
+    limit, or one of the other storage type, flushes what is held first (the window then runs as several grouped calls).
+    A bag that feed.ResidentBagCache keeps in HBM (it carries `_mmf_resident`) is held BY REFERENCE instead -- its arena view,
+    no copy -- and reaches its rows when the grouped call is about to run: ONE ops.bag_gather for all planes of a window of
+    resident bags (one per run of consecutive resident bags when a window mixes both kinds), which also widens the bags of a
+    bf16-stored cache."""
 
     def __init__(self):
         self.buf = None
@@ -176,6 +180,31 @@ class _HeldBags:
 
     def reset(self):
         self.rows, self.sizes, self.labels, self.cs, self.seeds, self.slots = 0, [], [], [], [], []
+        self.refs = []       # (first row, rows, [arena view per modality]) of the bags held by reference
+
+    @staticmethod
+    def resident_source(x, device):
+        """The arena view behind a bag feed.ResidentBagCache delivered (the bag itself, or what it was widened from), or
+        None: any other tensor, which is copied as it arrives."""
+        r = getattr(x, "_mmf_resident", None)
+        if r is None:
+            return None
+        src = x if r is True else r
+        return src if src.device == device and src.dim() == 2 and src.shape[1] % 8 == 0 and src.is_contiguous() else None
+
+    def materialise(self):
+        """The bags held by reference, into their rows of the buffer."""
+        from .. import ops
+        refs, self.refs = self.refs, []
+        i = 0
+        while i < len(refs):
+            j = i + 1
+            while j < len(refs) and refs[j][0] == refs[j - 1][0] + refs[j - 1][1] and refs[j][2][0].dtype == refs[i][2][0].dtype:
+                j += 1
+            r0 = refs[i][0]
+            ops.bag_gather([[ref[2][m] for ref in refs[i:j]] for m in range(self.buf.shape[0])],
+                           [self.buf[m, r0:] for m in range(self.buf.shape[0])])
+            i = j
 
     @staticmethod
     def row_limit(model, nmod, L, dtype=torch.float32):
@@ -209,17 +238,22 @@ class _HeldBags:
                 or self.buf.dtype != dtype or self.buf.device != device):
             grown = torch.empty((nmod, max(need, 2 * self.buf.shape[1] if self.buf is not None else need), L),
                                 dtype=dtype, device=device)
-            if self.rows:
+            if self.rows and len(self.refs) < len(self.sizes):       # some held bag is in the buffer already
                 grown[:, :self.rows].copy_(self.buf[:, :self.rows])
             self.buf = grown
-        for m, x in enumerate(xs):
-            self.buf[m, self.rows:need].copy_(x, non_blocking=True)
+        srcs = [self.resident_source(x, device) for x in xs]
+        if all(src is not None for src in srcs):
+            self.refs.append((self.rows, n, srcs))
+        else:
+            for m, x in enumerate(xs):
+                self.buf[m, self.rows:need].copy_(x, non_blocking=True)
         self.rows = need
         self.sizes.append(n); self.labels.append(label.reshape(1)); self.cs.append(c.reshape(1))
         self.seeds.append(seed); self.slots.append(slot)
 
     def held(self, model):
         """The held rows as the model's grouped calls take them: (x or [n_mod x rows x L], sizes)."""
+        self.materialise()
         x = self.buf[:, :self.rows] if hasattr(model, "attention_net_radio") else self.buf[0, :self.rows]
         return x, list(self.sizes)
 
@@ -312,6 +346,8 @@ class _MMGroup:
     def window(self, model):
         """The held patients as the model's grouped calls take them: the pre-stacked (path, radio, omic) triple."""
         has = lambda k: k in model.mode
+        self.path.materialise()
+        self.radio.materialise()
         return ((self.path.buf[0, :self.path.rows], list(self.path.sizes)) if has("path") else None,
                 (self.radio.buf[:, :self.radio.rows], list(self.radio.sizes)) if has("radio") else None,
                 self.omic[:len(self.slots)] if has("omic") else None)
