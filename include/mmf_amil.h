@@ -492,6 +492,9 @@ int mmf_linear_backward(const float* dy, const float* const* x_segs, int32_t nse
 /* ---------------------------------------------------------------------------------------------
  * Survival head:  logits = f.Wk^T + bk; hazards = sigmoid(logits); S = cumprod(1-hazards); Y_hat = argmax
  *   replaces models/model_attention_mil_path.py:58-61.
+ * One workgroup keeps the B x K logits in LDS: B * K <= 256 (hence B <= 256), any F >= 1; a larger batch is
+ * MMF_ERR_SHAPE, before any launch (nothing is written).  B < 1 or K < 1: MMF_ERR_ARG.
+ * The backward reads the forward's hazards; g_hazards / g_S are the loss's gradients (mmf_nll_surv writes both).
  * ------------------------------------------------------------------------------------------- */
 int mmf_surv_head_forward(const float* feat, const float* Wk, const float* bk, int32_t B, int32_t F, int32_t K,
                           float* logits, float* hazards, float* S, int64_t* Y_hat, void* stream);
@@ -501,16 +504,19 @@ int mmf_surv_head_backward(const float* g_hazards, const float* g_S, const float
 
 /* nll_surv loss (utils/loss_utils.py:22-39): loss [1], and its gradients g_hazards, g_S [B x K].
  * A label outside [0, K) (the reference's gather raises an index error) poisons the result instead of the memory:
- * loss = NaN, that sample's gradients = 0; nothing is read or written out of bounds. */
+ * loss = NaN, that sample's gradients = 0; nothing is read or written out of bounds.
+ * One workgroup strides over the samples: any B >= 1, K >= 1 (MMF_ERR_ARG below that). */
 int mmf_nll_surv(const float* hazards, const float* S, const int64_t* Y, const float* c, int32_t B, int32_t K,
                  float alpha, float eps, float* loss, float* g_hazards, float* g_S, void* stream);
 
-/* Cox partial-likelihood loss (utils/loss_utils.py:124-139): loss [1], d_risks [B].  times is float64. */
+/* Cox partial-likelihood loss (utils/loss_utils.py:124-139): loss [1], d_risks [B].  times is float64.
+ * One workgroup keeps exp(risk) and the risk-set weights of the whole batch in LDS (8 bytes a sample): B <= 8192,
+ * MMF_ERR_SHAPE above, before any launch (nothing is written).  B < 1: MMF_ERR_ARG. */
 int mmf_cox_surv(const float* risks, const double* times, const float* c, int32_t B,
                  float* loss, float* d_risks, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
- * Small dense layers (any dimensions, batch 1..128) and the Kronecker fusion block.
+ * Small dense layers (any B, K, N >= 1; sized for batches of a few hundred rows at most) and the Kronecker fusion block.
  *   replaces SNN_Block (models/model_modules.py:64-68: Linear+SELU+AlphaDropout), the Linear+ReLU+Dropout
  *   stacks and gating of XlinearFusion (models/model_modules.py:133-178), and the fusion classifiers
  *   (models/model_mm_attention_mil.py:91,95).
@@ -521,7 +527,9 @@ int mmf_dense_forward(const float* x, const float* W, const float* bias, int32_t
                       int32_t act, int32_t drop_kind, float drop_p, uint32_t seed, uint32_t site,
                       const uint32_t* seed_dev, float* y, void* stream);
 /* dy, y (the forward OUTPUT) -> dx [B x K] (may be NULL), dW [N x K], db [N] (may be NULL);
- * dpre_scratch: [B x N] floats. */
+ * dpre_scratch: [B x N] floats.  No cap on B, K or N: with N <= 2048 and B <= 256 the backward is one launch that rebuilds
+ * dpre in LDS and leaves dpre_scratch untouched; above either it is three launches through dpre_scratch.  act outside
+ * MMF_ACT_NONE..MMF_ACT_SELU or drop_kind outside 0..2: MMF_ERR_ARG; the _rows forms with ldy < N or lddy < N: MMF_ERR_SHAPE. */
 int mmf_dense_backward(const float* dy, const float* y, const float* x, const float* W,
                        int32_t B, int32_t K, int32_t N, int32_t act,
                        int32_t drop_kind, float drop_p, uint32_t seed, uint32_t site, const uint32_t* seed_dev,
@@ -558,6 +566,8 @@ int mmf_kron_backward(const float* g, const float* const* o, int32_t m, int32_t 
  *   l1_mask: NULL = the L1 term covers every element (l1_reg_all); else [n] floats in {0, 1} selecting the elements it
  *   covers (l1_reg_modules, utils/utils.py:259-268: fc_omic and mm only).
  * mmf_abs_sum: out[0] = sum_i |w_i| (the value of l1_reg_all); partials = 512 floats of scratch.
+ * Any n >= 1 (a tail of n % 4 elements is updated one by one); n < 1 or step < 1: MMF_ERR_ARG.  w, g, m, v and a non-null
+ * l1_mask must be 16-byte aligned: MMF_ERR_ALIGN otherwise.  An element with w = +-0 gets no L1 term (sign(0) = 0).
  * ------------------------------------------------------------------------------------------- */
 /* ---------------------------------------------------------------------------------------------
  * Omic head, ONE training step in ONE launch:  MaxNet forward (two SNN blocks + classifier -> risk), CoxSurvLoss, and
@@ -620,7 +630,10 @@ int mmf_xreduce_backward(const mmf_xreduce_io* io, float drop_p, uint32_t seed, 
  * ------------------------------------------------------------------------------------------- */
 /* y = dropout(act(BatchNorm1d(x) [+ res])), x / y / res: [B x F].  training != 0: batch statistics (biased variance),
  * running_mean / running_var updated in place with `momentum` and the unbiased variance (torch semantics; B >= 2);
- * training == 0: running statistics.  save_mean / save_invstd [F] are what backward reads.
+ * training == 0: running statistics (required then: MMF_ERR_ARG without them; any B >= 1).  Training with B = 1 is
+ * MMF_ERR_SHAPE, before any launch.  res, gamma / beta, and in training mode the running statistics may be NULL; so may
+ * dres and dgamma / dbeta of the backward, which takes the same `training` flag (eval mode: dx = gamma * invstd * dpre).
+ * Any F >= 1.  save_mean / save_invstd [F] are what backward reads.
  * Replaces nn.BatchNorm1d (+ the ReLU / Dropout / residual add that follow it) in models/model_modules.py:5-49 and
  * models/nll_models_pretrained.py:82-90. */
 int mmf_batchnorm_forward(const float* x, const float* res, const float* gamma, const float* beta,
@@ -631,18 +644,21 @@ int mmf_batchnorm_backward(const float* dy, const float* y, const float* x, cons
                            const float* save_mean, const float* save_invstd, int32_t B, int32_t F, int32_t training,
                            int32_t act, float drop_p, uint32_t seed, uint32_t site, const uint32_t* seed_dev,
                            float* dx, float* dres /* or NULL */, float* dgamma, float* dbeta, void* stream);
-/* Highway mix, models/model_modules.py:21-25: y = sigmoid(zg) * relu(zn) + (1 - sigmoid(zg)) * zl, elementwise over n. */
+/* Highway mix, models/model_modules.py:21-25: y = sigmoid(zg) * relu(zn) + (1 - sigmoid(zg)) * zl, elementwise over any
+ * n >= 1 (MMF_ERR_ARG below).  The derivative of relu at zn = 0 is 0. */
 int mmf_highway_mix_forward(const float* zg, const float* zn, const float* zl, int64_t n, float* y, void* stream);
 int mmf_highway_mix_backward(const float* dy, const float* zg, const float* zn, const float* zl, int64_t n,
                              float* dzg, float* dzn, float* dzl, void* stream);
 /* ranking_loss, utils/loss_utils.py:58-101 (a Python loop over all pairs): loss = -(mean | sum) over comparable pairs of
  * phi(risk_more - risk_less); phi 0 = sigmoid, 1 = relu; reduction 0 = mean, 1 = sum; 0 when no pair is comparable.
  * times: device double[B] (event times, or the bin labels for RankingNLLSurvLoss, loss_utils.py:160).  Writes the loss
- * and its gradient w.r.t. risks.  B >= 2. */
+ * and its gradient w.r.t. risks.  B >= 2 (B < 2: MMF_ERR_SHAPE, before any launch; the reference raises); no upper cap: one
+ * workgroup strides over the samples.  phi or reduction outside 0..1: MMF_ERR_ARG. */
 int mmf_ranking_loss(const float* risks, const double* times, const float* c, int32_t B, int32_t phi, int32_t reduction,
                      float* loss, float* d_risks, void* stream);
 /* logits [B x K] -> hazards = sigmoid, S = cumprod(1 - hazards), Y_hat = argmax, risk = -sum_k S
- * (models/nll_models_pretrained.py:58-62,193-197).  K <= 32. */
+ * (models/nll_models_pretrained.py:58-62,193-197).  Any B >= 1; 1 <= K <= 32 (the backward keeps a sample's hazards in
+ * registers): MMF_ERR_SHAPE outside, before any launch.  Y_hat and risk may be NULL. */
 int mmf_hazards_forward(const float* logits, int32_t B, int32_t K, float* hazards, float* S, int64_t* Y_hat, float* risk,
                         void* stream);
 int mmf_hazards_backward(const float* g_hazards, const float* g_S, const float* g_risk /* each may be NULL */,

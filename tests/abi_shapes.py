@@ -25,6 +25,12 @@ run by tests/test_gpu_xfusion_shapes.py.  Its kernels are VALU code with fixed w
 XFusion: classes are named after what a dimension does to a work unit -- lanes of a wave_dot round, rows of a dW block,
 passes and wave quarters of the dkr launch, chunks a lane of dense_segs_group_kernel keeps, slices and column blocks of
 dense_bwd_kernel, which layer sizes the shared backward buffers, patient groups and shares.
+
+The other half of the ABI -- the single-workgroup and one-thread-per-element kernels every training step ends in: the
+survival head, nll_surv, Cox, the ranking loss, the hazard head, the highway mix, batch norm, the Adam + L1 step, abs_sum and
+the dense backward -- has one table per entry point below XFUSION, run by tests/test_gpu_small_shapes.py on the inputs and
+float64 references of tests/small_cases.py.  Their classes: a size against the 256-thread stride (1, stride - 1, stride,
+stride + 1, three strides or more), the caps from both sides, every combination of optional pointers the header allows.
 """
 from __future__ import annotations
 
@@ -588,6 +594,471 @@ REQUIRED_XFUSION = (
         (2, 16, 6, 8, 8, 8, 2, 0), (2, 16, 4, 1532, 8, 8, 2, 0), (2, 16, 8, 8, 1537, 8, 2, 0), (2, 16, 8, 8, 8, 8, 0, 0),
         (2, 16, 8, 8, 8, 8, 65, 0), (1, 16, 8, 8, 8, 8, 2, 0), (4, 16, 8, 8, 8, 8, 2, 0), (2, 8, 8, 8, 8, 8, 2, 0))})
 
+# ---- the single-workgroup and one-thread-per-element half: csrc/mmf_small.hip, the stage-2 block and the dense backward -----
+# of csrc/mmf_mlp.hip.  Run by tests/test_gpu_small_shapes.py on the inputs of tests/small_cases.py.  Classes are named after
+# the work unit: the 256-thread stride of a single-workgroup loop or of a one-thread-per-element grid, the 4-wave and
+# 64-lane strides of the head forward, the 4-float vector of the Adam step, the 512 x 256 grid of abs_sum.
+NT = 256                                                 # threads of every kernel below
+HEAD_MAX_BK = 256                                        # csrc/mmf_small.hip:14: B * K values of the head kept in LDS
+COX_MAX_B = 8192                                         # csrc/mmf_small.hip launch_cox: exp(theta) and w, 2 * B floats of LDS
+HAZ_MAX_K = 32                                           # csrc/mmf_mlp.hip hazard_bwd_kernel: float h[32]
+ABS_GRID = 512 * NT                                      # csrc/mmf_small.hip launch_abs_sum: 512 blocks of 256 threads
+DENSE_MAX_N, DENSE_MAX_B = 2048, 256                     # csrc/mmf_mlp.hip:629: above either, launch_dense_bwd takes three launches
+
+
+def stride_class(n, stride=NT):
+    """n against a loop or a grid that advances `stride` at a time."""
+    return {1: "1", stride - 1: "stride - 1", stride: "stride", stride + 1: "stride + 1"}.get(
+        n, "three strides or more" if n > 2 * stride else "other")
+
+
+def _stride_tags(key, n):
+    c = stride_class(n)
+    return set() if c == "other" else {(key, c)}
+
+
+# mmf_surv_head_forward / _backward
+@dataclass(frozen=True)
+class Head:
+    B: int
+    F: int
+    K: int
+    steep: bool = False          # the bias puts logits at +-30: hazards at the ends of (0, 1), S underflowing
+    why: str = ""
+
+
+def head_rule(c):
+    """include/mmf_amil.h "Survival head" (B * K <= 256); csrc/mmf_api.hip mmf_surv_head_forward / _backward (B, K < 1),
+    csrc/mmf_small.hip launch_head_fwd / launch_head_bwd -- before any launch."""
+    if c.B < 1 or c.K < 1:
+        return ERR_ARG
+    if c.B * c.K > HEAD_MAX_BK or c.B > NT:
+        return ERR_SHAPE
+    return OK
+
+
+def head_tags(c):
+    code = head_rule(c)
+    if code != OK:
+        return {("refused", code, f"B={c.B} K={c.K}")}
+    t = set()
+    if c.B * c.K in (3, 4, 5):
+        t.add(("B*K against the 4-wave stride", c.B * c.K))
+    if c.F in (1, 63, 64, 65, 1024):
+        t.add(("F against the 64-lane stride", c.F))
+    if c.F == NT + 1:
+        t.add(("backward: F against the 256-column stride", c.F))
+    if c.B * c.K == HEAD_MAX_BK:
+        t.add(("cap B*K = 256", (c.B, c.K)))
+    if c.steep:
+        t.add(("logits", "+-30"))
+    return t
+
+
+HEAD = [
+    Head(3, 1, 1, why="B*K = 3: the fourth wave idle; F = 1: one lane of the dot product"),
+    Head(1, 63, 4, why="B*K = 4: one output per wave; F = 63: the last lane idle"),
+    Head(5, 64, 1, why="B*K = 5: a second round of wave 0 alone; F = 64: every lane once"),
+    Head(2, 65, 3, steep=True, why="F = 65: a second round of lane 0; logits at +-30: (1 - h) underflows in the cumprod backward"),
+    Head(2, 1024, 4, why="F = 1024: sixteen rounds of the lane loop"),
+    Head(3, 257, 4, why="backward: F = 257, a second round of thread 0 over the columns"),
+    Head(8, 8, 32, why="the cap B*K = 256 as (8, 32): the deepest cumprod"),
+    Head(256, 8, 1, why="the cap B*K = 256 as (256, 1): every thread a sample"),
+    # refused
+    Head(9, 8, 29, why="B*K = 261"),
+    Head(257, 8, 1, why="B = 257"),
+]
+REQUIRED_HEAD = (
+    {("B*K against the 4-wave stride", v) for v in (3, 4, 5)} | {("F against the 64-lane stride", v) for v in (1, 63, 64, 65, 1024)}
+    | {("backward: F against the 256-column stride", 257), ("cap B*K = 256", (8, 32)), ("cap B*K = 256", (256, 1)), ("logits", "+-30")}
+    | {("refused", ERR_SHAPE, "B=9 K=29"), ("refused", ERR_SHAPE, "B=257 K=1")})
+
+
+# mmf_nll_surv
+@dataclass(frozen=True)
+class Nll:
+    B: int
+    K: int
+    bad_row: int = -1            # the row whose device label is K (out of range), or -1
+    why: str = ""
+
+
+def nll_rule(c):
+    """include/mmf_amil.h mmf_nll_surv; csrc/mmf_api.hip mmf_nll_surv -- any B >= 1, K >= 1: one workgroup strides over B."""
+    return ERR_ARG if c.B < 1 or c.K < 1 else OK
+
+
+def nll_tags(c):
+    if nll_rule(c) != OK:
+        return {("refused", nll_rule(c), f"B={c.B} K={c.K}")}
+    t = _stride_tags("B", c.B)
+    if c.bad_row >= 0:
+        t.add(("label", "out of range in a row >= 256" if c.bad_row >= NT else "out of range"))
+    return t
+
+
+NLL = [
+    Nll(1, 1, why="one sample, one bin: S_padded[y] is the padding, S_padded[y + 1] the only S"),
+    Nll(255, 4, why="the last thread idle"),
+    Nll(256, 4, why="every thread one sample"),
+    Nll(257, 4, why="thread 0 takes a second sample"),
+    Nll(700, 4, why="three rounds of the stride loop, the last ragged"),
+    Nll(300, 4, bad_row=280, why="label K on a device label in row 280: NaN loss, that row's gradients zero, the others right"),
+    Nll(0, 4, why="refused: B = 0"),
+]
+REQUIRED_NLL = ({("B", s) for s in ("1", "stride - 1", "stride", "stride + 1", "three strides or more")}
+                | {("label", "out of range in a row >= 256"), ("refused", ERR_ARG, "B=0 K=4")})
+
+
+# mmf_cox_surv
+@dataclass(frozen=True)
+class Cox:
+    B: int
+    all_censored: bool = False
+    why: str = ""
+
+
+def cox_rule(c):
+    """include/mmf_amil.h mmf_cox_surv (B <= 8192); csrc/mmf_api.hip mmf_cox_surv, csrc/mmf_small.hip launch_cox."""
+    if c.B < 1:
+        return ERR_ARG
+    return ERR_SHAPE if c.B > COX_MAX_B else OK
+
+
+def cox_tags(c):
+    if cox_rule(c) != OK:
+        return {("refused", cox_rule(c), f"B={c.B}")}
+    return {("censoring", "all censored")} if c.all_censored else {("B", c.B)}
+
+
+COX = [
+    Cox(2, why="the smallest batch with a risk set of two"),
+    Cox(256, why="every thread one sample"),
+    Cox(257, why="thread 0 takes a second sample"),
+    Cox(1000, why="four rounds, the last ragged; beyond the sizes the suite's bar was set on"),
+    Cox(6145, why="2 * 6145 * 4 bytes of dynamic LDS: the first B above 48 KiB"),
+    Cox(8192, why="the cap: 64 KiB of dynamic LDS on top of 1 KiB static"),
+    Cox(5, all_censored=True, why="all censored: loss 0, gradient 0, log(D_i) still finite"),
+    Cox(8193, why="refused: above the cap"),
+]
+REQUIRED_COX = ({("B", b) for b in (2, 256, 257, 1000, 6145, 8192)} | {("censoring", "all censored"), ("refused", ERR_SHAPE, "B=8193")})
+
+
+# mmf_ranking_loss
+@dataclass(frozen=True)
+class Rank:
+    B: int
+    phi: int                     # 0 sigmoid, 1 relu
+    reduction: int               # 0 mean, 1 sum
+    kind: str = "many"           # many / none / one / tied / equal risks: what tests/small_cases.py rank_inputs generates
+    why: str = ""
+
+
+def rank_rule(c):
+    """include/mmf_amil.h mmf_ranking_loss (B >= 2); csrc/mmf_api.hip mmf_ranking_loss, csrc/mmf_mlp.hip launch_rank_loss."""
+    if c.phi not in (0, 1) or c.reduction not in (0, 1):
+        return ERR_ARG
+    return ERR_SHAPE if c.B < 2 else OK
+
+
+def rank_tags(c):
+    if rank_rule(c) != OK:
+        return {("refused", rank_rule(c), f"B={c.B}")}
+    t = _stride_tags("B", c.B) | {("phi, reduction", (c.phi, c.reduction))}
+    t.add({"many": ("pairs", "many"), "none": ("pairs", "none"), "one": ("pairs", "one"), "tied": ("times", "tied"),
+           "equal risks": ("risks", "equal under phi = relu")}[c.kind])
+    return t
+
+
+RANK = [
+    Rank(255, 0, 0, why="sigmoid / mean; the last thread idle"),
+    Rank(256, 1, 1, why="relu / sum; every thread one sample"),
+    Rank(257, 0, 1, why="sigmoid / sum; thread 0 takes a second sample"),
+    Rank(700, 1, 0, why="relu / mean; three rounds of the stride loop"),
+    Rank(4, 0, 0, "none", why="no comparable pair: loss 0, gradient 0"),
+    Rank(4, 0, 0, "one", why="exactly one comparable pair: n = 1"),
+    Rank(6, 0, 1, "tied", why="tied times: a tie is not comparable in either order"),
+    Rank(6, 1, 0, "equal risks", why="equal risks under relu: phi(0) = 0 with derivative 0"),
+    Rank(1, 0, 0, why="refused: B = 1"),
+]
+REQUIRED_RANK = ({("B", s) for s in ("stride - 1", "stride", "stride + 1", "three strides or more")}
+                 | {("phi, reduction", (p, r)) for p in (0, 1) for r in (0, 1)}
+                 | {("pairs", "none"), ("pairs", "one"), ("times", "tied"), ("risks", "equal under phi = relu"),
+                    ("refused", ERR_SHAPE, "B=1")})
+
+
+# mmf_hazards_forward / _backward
+@dataclass(frozen=True)
+class Haz:
+    B: int
+    K: int
+    Y_hat: bool = True           # optional outputs of the forward: given or NULL
+    risk: bool = True
+    gH: bool = True              # optional gradients of the backward: given or NULL
+    gS: bool = True
+    gR: bool = True
+    steep: bool = False
+    why: str = ""
+
+
+def haz_rule(c):
+    """include/mmf_amil.h mmf_hazards_forward / _backward (K <= 32); csrc/mmf_mlp.hip launch_hazard_fwd / _bwd."""
+    return ERR_SHAPE if c.B < 1 or c.K < 1 or c.K > HAZ_MAX_K else OK
+
+
+def haz_tags(c):
+    if haz_rule(c) != OK:
+        return {("refused", haz_rule(c), f"B={c.B} K={c.K}")}
+    t = _stride_tags("B", c.B) | {("forward: Y_hat, risk", (c.Y_hat, c.risk)), ("backward: g_hazards, g_S, g_risk", (c.gH, c.gS, c.gR))}
+    if c.K in (1, 4, HAZ_MAX_K):
+        t.add(("K", c.K))
+    if c.steep:
+        t.add(("logits", "+-30"))
+    return t
+
+
+HAZ = [
+    Haz(1, 1, Y_hat=False, risk=False, gH=False, gS=False, gR=False, why="one sample, K = 1; no optional pointer at all: dlogits = 0"),
+    Haz(255, 4, Y_hat=True, risk=False, gH=True, gS=False, gR=False, why="the last thread idle; Y_hat alone; g_hazards alone"),
+    Haz(256, 32, Y_hat=False, risk=True, gH=False, gS=True, gR=False, why="one full block, K = 32: the whole h[32]; risk alone; g_S alone"),
+    Haz(257, 4, gH=False, gS=False, gR=True, why="a second block of one sample; g_risk alone"),
+    Haz(700, 4, gH=True, gS=True, gR=False, why="three blocks; g_hazards and g_S"),
+    Haz(3, 4, gH=True, gS=False, gR=True, why="g_hazards and g_risk"),
+    Haz(3, 5, gH=False, gS=True, gR=True, why="g_S and g_risk"),
+    Haz(3, 32, steep=True, why="all three gradients; logits at +-30 over K = 32: S underflows, (1 - h) rounds to 0"),
+    Haz(3, 0, why="refused: K = 0"),
+    Haz(3, 33, why="refused: K = 33"),
+]
+REQUIRED_HAZ = ({("B", s) for s in ("1", "stride - 1", "stride", "stride + 1", "three strides or more")} | {("K", k) for k in (1, 4, 32)}
+                | {("forward: Y_hat, risk", (a, b)) for a in (True, False) for b in (True, False)}
+                | {("backward: g_hazards, g_S, g_risk", (a, b, d)) for a in (True, False) for b in (True, False) for d in (True, False)}
+                | {("logits", "+-30"), ("refused", ERR_SHAPE, "B=3 K=0"), ("refused", ERR_SHAPE, "B=3 K=33")})
+
+
+# mmf_highway_mix_forward / _backward
+@dataclass(frozen=True)
+class Highway:
+    n: int
+    why: str = ""
+
+
+def highway_rule(c):
+    """include/mmf_amil.h mmf_highway_mix_*; csrc/mmf_api.hip mmf_highway_mix_forward / _backward: any n >= 1."""
+    return ERR_ARG if c.n < 1 else OK
+
+
+def highway_tags(c):
+    return {("refused", ERR_ARG, f"n={c.n}")} if c.n < 1 else _stride_tags("n", c.n)
+
+
+HIGHWAY = [Highway(1, why="one element"), Highway(255, why="the last thread idle"), Highway(256, why="one full block"),
+           Highway(257, why="a second block of one element"), Highway(700, why="three blocks, the last ragged"),
+           Highway(0, why="refused: n = 0")]
+REQUIRED_HIGHWAY = ({("n", s) for s in ("1", "stride - 1", "stride", "stride + 1", "three strides or more")}
+                    | {("refused", ERR_ARG, "n=0")})
+
+
+# mmf_batchnorm_forward / _backward
+@dataclass(frozen=True)
+class Bn:
+    B: int
+    F: int
+    training: bool = True
+    act: int = 0
+    drop_p: float = 0.0
+    res: bool = False
+    affine: bool = False         # gamma and beta given
+    running: bool = False        # running statistics given (eval mode needs them)
+    dres: bool = False
+    dgb: bool = False            # dgamma and dbeta given
+    shifted: bool = False        # every feature has mean 8 and std 1/8
+    why: str = ""
+
+
+def bn_rule(c):
+    """include/mmf_amil.h mmf_batchnorm_forward ("B >= 2" in training mode); csrc/mmf_api.hip mmf_batchnorm_forward,
+    csrc/mmf_mlp.hip launch_bn_fwd.  The backward has no B >= 2 rule of its own."""
+    if c.B < 1 or c.F < 1 or (not c.training and not c.running) or not 0 <= c.act <= 4 or not 0.0 <= c.drop_p < 1.0:
+        return ERR_ARG
+    return ERR_SHAPE if c.training and c.B < 2 else OK
+
+
+def bn_tags(c):
+    if bn_rule(c) != OK:
+        return {("refused", bn_rule(c), f"B={c.B} training={int(c.training)}")}
+    t = _stride_tags("F", c.F) | {("act", c.act), ("drop_p", c.drop_p), ("res", c.res), ("gamma / beta", c.affine),
+                                  ("dres", c.dres), ("dgamma / dbeta", c.dgb)}
+    if c.training:
+        t |= {("training B", c.B), ("running statistics", c.running)}
+    else:
+        t |= {("eval B", c.B), ("backward", "eval mode")}
+    if c.shifted:
+        t.add(("feature", "mean 8, std 1/8"))
+    return t
+
+
+BN = [
+    Bn(2, 1, why="the smallest training batch, one feature; every optional pointer NULL"),
+    Bn(32, 255, act=1, drop_p=0.25, res=True, affine=True, running=True, dres=True, dgb=True,
+       why="the shipped B; the last thread idle; ReLU + dropout + residual, every optional pointer given"),
+    Bn(300, 256, act=2, affine=True, running=True, dgb=True, why="B = 300: the longest sums; one full block; tanh"),
+    Bn(1, 257, training=False, act=3, affine=True, running=True, dgb=True, why="eval mode with B = 1; a second block of one feature; sigmoid"),
+    Bn(4, 700, act=4, res=True, dres=True, why="three blocks of features; SELU"),
+    Bn(32, 8, affine=True, running=True, dgb=True, shifted=True, why="features of mean 8 and std 1/8: the two-pass variance"),
+    Bn(1, 8, why="refused: training with B = 1"),
+]
+REQUIRED_BN = ({("F", s) for s in ("1", "stride - 1", "stride", "stride + 1", "three strides or more")}
+               | {("training B", b) for b in (2, 32, 300)} | {("eval B", 1), ("backward", "eval mode")}
+               | {(k, v) for k in ("res", "gamma / beta", "running statistics", "dres", "dgamma / dbeta") for v in (True, False)}
+               | {("act", a) for a in range(5)} | {("drop_p", 0.0), ("drop_p", 0.25), ("feature", "mean 8, std 1/8"),
+                                                   ("refused", ERR_SHAPE, "B=1 training=1")})
+
+
+# mmf_adam_l1_step
+@dataclass(frozen=True)
+class Adam:
+    n: int
+    mask: bool = False
+    l1: float = 3e-4
+    wd: float = 1e-3
+    step: int = 1
+    misalign: bool = False
+    why: str = ""
+
+
+def adam_rule(c):
+    """include/mmf_amil.h "Per-step tail"; csrc/mmf_api.hip mmf_adam_l1_step: w, g, m, v and a non-null mask 16-byte aligned."""
+    if c.n < 1 or c.step < 1:
+        return ERR_ARG
+    return ERR_ALIGN if c.misalign else OK
+
+
+def adam_tags(c):
+    if adam_rule(c) != OK:
+        return {("refused", adam_rule(c), "misaligned w" if c.misalign else f"n={c.n} step={c.step}")}
+    t = {("n", c.n), ("mask", c.mask), ("step", c.step)}
+    if c.l1 == 0:
+        t.add(("l1", 0))
+    if c.wd == 0:
+        t.add(("wd", 0))
+    return t
+
+
+ADAM = [
+    Adam(1, why="n = 1: the tail branch alone, one element"),
+    Adam(3, mask=True, why="n = 3: the tail branch alone, with a mask"),
+    Adam(4, step=2, why="n = 4: one vector, no tail; step 2"),
+    Adam(5, l1=0.0, why="n = 5: one vector and a tail of one; l1 = 0"),
+    Adam(1023, mask=True, wd=0.0, why="n = 1023: 255 vectors and a tail of three in the last thread, both under a mask; wd = 0"),
+    Adam(1024, step=1000, why="n = 1024: one full block; step 1000: both bias corrections near 1"),
+    Adam(1025, why="n = 1025: a second block that is all tail"),
+    Adam(1027, mask=True, why="n = 1027: a second block with a tail of three; a mask over full vectors and the tail"),
+    Adam(8, step=0, why="refused: step 0"),
+    Adam(8, misalign=True, why="refused: w 4 bytes off a 16-byte boundary"),
+]
+REQUIRED_ADAM = ({("n", n) for n in (1, 3, 4, 5, 1023, 1024, 1025, 1027)} | {("mask", True), ("mask", False), ("l1", 0), ("wd", 0)}
+                 | {("step", s) for s in (1, 2, 1000)} | {("refused", ERR_ARG, "n=8 step=0"), ("refused", ERR_ALIGN, "misaligned w")})
+
+
+# mmf_abs_sum
+@dataclass(frozen=True)
+class AbsSum:
+    n: int
+    why: str = ""
+
+
+def abs_sum_rule(c):
+    """include/mmf_amil.h mmf_abs_sum; csrc/mmf_api.hip mmf_abs_sum: any n >= 1."""
+    return ERR_ARG if c.n < 1 else OK
+
+
+def abs_sum_chain(n):
+    """The longest add chain of mmf_abs_sum: a thread's share of the grid-stride loop, wave_sum (6) and the four waves (3)
+    in the first launch; two partials a thread, wave_sum and the four waves again in the second."""
+    return -(-n // ABS_GRID) + 6 + 3 + 2 + 6 + 3
+
+
+def abs_sum_tags(c):
+    if c.n < 1:
+        return {("refused", ERR_ARG, f"n={c.n}")}
+    t = {("n against the 512 x 256 grid", stride_class(c.n, ABS_GRID))}
+    if -(-c.n // ABS_GRID) >= 8:
+        t.add(("per-thread chain", ">= 8"))
+    return t
+
+
+ABS_SUM = [AbsSum(1, why="below one block: 511 blocks add nothing"), AbsSum(ABS_GRID - 1, why="the last thread of the grid idle"),
+           AbsSum(ABS_GRID, why="every thread one element"), AbsSum(ABS_GRID + 1, why="thread 0 of block 0 takes a second element"),
+           AbsSum(1000003, why="a per-thread chain of eight, ragged"), AbsSum(0, why="refused: n = 0")]
+REQUIRED_ABS_SUM = ({("n against the 512 x 256 grid", s) for s in ("1", "stride - 1", "stride", "stride + 1")}
+                    | {("per-thread chain", ">= 8"), ("refused", ERR_ARG, "n=0")})
+
+
+# mmf_dense_backward / mmf_dense_backward_rows
+@dataclass(frozen=True)
+class DenseBwd:
+    B: int
+    K: int
+    N: int
+    act: int = 0                 # 0 none, 1 relu, 4 selu
+    drop_kind: int = 0           # 0 none, 1 nn.Dropout, 2 nn.AlphaDropout (p = 0.25)
+    dx: bool = True
+    db: bool = True
+    rows: int = 0                # > 0: mmf_dense_backward_rows with ldy = lddy = N + rows.  "Both _rows forms" of the backward are
+                                 # its two kernels built for row_base: the fused launch and the three-launch fallback; the
+                                 # forward _rows entry point is not in this table (tests/test_gpu_mm_group_step.py runs it)
+    why: str = ""
+
+
+def dense_bwd_rule(c):
+    """include/mmf_amil.h mmf_dense_backward / _rows; csrc/mmf_api.hip: no cap on B, K or N -- above N = 2048 or B = 256
+    launch_dense_bwd (csrc/mmf_mlp.hip) takes the three-launch form."""
+    if c.B < 1 or c.K < 1 or c.N < 1 or not 0 <= c.act <= 4 or not 0 <= c.drop_kind <= 2:
+        return ERR_ARG
+    return ERR_SHAPE if c.rows < 0 else OK
+
+
+def dense_bwd_path(c):
+    if c.B > DENSE_MAX_B:
+        return "fallback by B"
+    if c.N > DENSE_MAX_N:
+        return "fallback by N"
+    return "fused at the cap" if (c.B, c.N) == (DENSE_MAX_B, DENSE_MAX_N) else "fused"
+
+
+def dense_bwd_tags(c):
+    if dense_bwd_rule(c) != OK:
+        return {("refused", dense_bwd_rule(c), f"act={c.act} drop_kind={c.drop_kind} rows={c.rows}")}
+    path = dense_bwd_path(c)
+    t = {("path, K", (path, c.K)), ("act", c.act), ("drop_kind", c.drop_kind), ("dx", c.dx), ("db", c.db)}
+    if c.rows > 0:
+        t.add(("_rows with ldy > N", "fused" if path.startswith("fused") else "fallback"))
+    if path != "fused at the cap" and c.dx and c.N % 2:
+        t.add(("dense_dx_kernel", "odd N"))
+    return t
+
+
+DENSE_BWD = [
+    DenseBwd(256, 36, 2048, act=1, drop_kind=1, why="fused at the cap, K = 36: one ragged dx block, one ragged dW block a row"),
+    DenseBwd(256, 257, 2048, act=4, rows=4, why="fused at the cap, K = 257: a second dW block of one column; _rows, ldy = N + 4"),
+    DenseBwd(256, 300, 2048, dx=False, why="fused at the cap, K = 300; no dx: dW blocks alone"),
+    DenseBwd(257, 36, 8, act=4, drop_kind=2, why="fallback by B, K = 36; SELU + AlphaDropout"),
+    DenseBwd(257, 257, 8, act=1, db=False, why="fallback by B, K = 257: a second column block of one; no db"),
+    DenseBwd(257, 300, 7, drop_kind=1, rows=3, why="fallback by B, K = 300, odd N = 7: dense_dx_kernel's remainder; _rows, ldy = N + 3"),
+    DenseBwd(2, 36, 2052, act=1, drop_kind=1, why="fallback by N = 2052, K = 36"),
+    DenseBwd(2, 257, 2052, act=4, drop_kind=2, dx=False, why="fallback by N, K = 257; no dx; SELU + AlphaDropout"),
+    DenseBwd(2, 300, 2052, why="fallback by N, K = 300"),
+    DenseBwd(2, 8, 8, act=5, why="refused: unknown activation"),
+    DenseBwd(2, 8, 8, drop_kind=3, why="refused: unknown dropout kind"),
+    DenseBwd(2, 8, 8, rows=-1, why="refused: _rows with ldy < N"),
+]
+REQUIRED_DENSE_BWD = (
+    {("path, K", (p, k)) for p in ("fused at the cap", "fallback by B", "fallback by N") for k in (36, 257, 300)}
+    | {("act", a) for a in (0, 1, 4)} | {("drop_kind", d) for d in (0, 1, 2)} | {(k, v) for k in ("dx", "db") for v in (True, False)}
+    | {("_rows with ldy > N", f) for f in ("fused", "fallback")} | {("dense_dx_kernel", "odd N")}
+    | {("refused", ERR_ARG, "act=5 drop_kind=0 rows=0"), ("refused", ERR_ARG, "act=0 drop_kind=3 rows=0"),
+       ("refused", ERR_SHAPE, "act=0 drop_kind=0 rows=-1")})
+
 TABLES = {
     "XFUSION": (XFUSION, xfusion_tags, REQUIRED_XFUSION),
     "mmf_linear_forward": (LINEAR_FORWARD, linear_forward_tags, REQUIRED_LINEAR_FORWARD),
@@ -595,6 +1066,16 @@ TABLES = {
     "mmf_attn_net": (ATTN, attn_tags, REQUIRED_ATTN),
     "mmf_amil (fp32)": (STACK_F32, stack_tags, REQUIRED_STACK),
     "mmf_amil_bf16": (STACK_BF16, stack_tags, REQUIRED_BF16),
+    "mmf_surv_head": (HEAD, head_tags, REQUIRED_HEAD),
+    "mmf_nll_surv": (NLL, nll_tags, REQUIRED_NLL),
+    "mmf_cox_surv": (COX, cox_tags, REQUIRED_COX),
+    "mmf_ranking_loss": (RANK, rank_tags, REQUIRED_RANK),
+    "mmf_hazards": (HAZ, haz_tags, REQUIRED_HAZ),
+    "mmf_highway_mix": (HIGHWAY, highway_tags, REQUIRED_HIGHWAY),
+    "mmf_batchnorm": (BN, bn_tags, REQUIRED_BN),
+    "mmf_adam_l1_step": (ADAM, adam_tags, REQUIRED_ADAM),
+    "mmf_abs_sum": (ABS_SUM, abs_sum_tags, REQUIRED_ABS_SUM),
+    "mmf_dense_backward": (DENSE_BWD, dense_bwd_tags, REQUIRED_DENSE_BWD),
 }
 
 

@@ -2,7 +2,9 @@
 the restated rules against the library where it refuses before any HIP call, the restated planners against the library's,
 and the case tables of tests/test_gpu_abi_shapes.py and tests/test_gpu_xfusion_shapes.py against the shape classes the
 rules make reachable; for the fusion tail also the two workspace queries over a grid on both sides of every limit, and the
-fp64 oracle of every case clear of every ReLU kink under the seed the case records."""
+fp64 oracle of every case clear of every ReLU kink under the seed the case records; for the small ops (losses, hazard heads,
+batch norm, the step tail, the dense backward) also the conditions their generated inputs must meet (tests/small_cases.py) and
+the vectorised Cox and ranking restatements against the ports."""
 import ctypes as C
 import dataclasses
 
@@ -298,3 +300,187 @@ def test_xfusion_oracles_keep_clear_of_every_relu_kink():
             assert all(np.abs(v).max() > 0 for v in dv) and all(np.abs(v).max() > 0 for v in gw.values()), (c, train)
     for m in (2, 3):
         assert ab.xfusion_train_rule(ab.XFusion(m, 256, 512, 512, 256, 64)) == ab.xfusion_infer_rule(ab.XFusion(m, 256, 512, 512, 256, 64)) == ab.OK
+
+
+# ---- the small ops: the rules against the library, and the conditions the GPU file's inputs must meet ----------------------
+def _small(table, rule):
+    return pytest.mark.parametrize("c", ab.refused(table, rule), ids=lambda c: c.why)
+
+
+@_small(ab.HEAD, ab.head_rule)
+def test_surv_head_refusals_in_the_library(c):
+    m, l = _lib()
+    assert l.mmf_surv_head_forward(P[0], P[1], P[2], c.B, c.F, c.K, P[3], P[4], P[5], P[6], None) == ab.head_rule(c)
+    assert l.mmf_surv_head_backward(P[0], P[1], P[2], P[3], P[4], c.B, c.F, c.K, P[5], P[6], P[7], None) == ab.head_rule(c)
+
+
+def test_small_loss_refusals_in_the_library():
+    m, l = _lib()
+    for c in ab.refused(ab.NLL, ab.nll_rule):
+        assert l.mmf_nll_surv(P[0], P[1], P[2], P[3], c.B, c.K, C.c_float(0.4), C.c_float(1e-7), P[4], P[5], P[6], None) == ab.nll_rule(c)
+    for c in ab.refused(ab.COX, ab.cox_rule):
+        assert l.mmf_cox_surv(P[0], P[1], P[2], c.B, P[3], P[4], None) == ab.cox_rule(c) == ab.ERR_SHAPE
+    for c in ab.refused(ab.RANK, ab.rank_rule):
+        assert l.mmf_ranking_loss(P[0], P[1], P[2], c.B, c.phi, c.reduction, P[3], P[4], None) == ab.rank_rule(c) == ab.ERR_SHAPE
+    for phi, red in ((2, 0), (0, 2), (-1, 0)):
+        assert ab.rank_rule(ab.Rank(4, phi, red)) == l.mmf_ranking_loss(P[0], P[1], P[2], 4, phi, red, P[3], P[4], None) == ab.ERR_ARG
+    for c in ab.refused(ab.HAZ, ab.haz_rule):
+        assert l.mmf_hazards_forward(P[0], c.B, c.K, P[1], P[2], P[3], P[4], None) == ab.haz_rule(c) == ab.ERR_SHAPE
+        assert l.mmf_hazards_backward(P[0], P[1], P[2], P[3], c.B, c.K, P[4], None) == ab.ERR_SHAPE
+    for c in ab.refused(ab.HIGHWAY, ab.highway_rule):
+        assert l.mmf_highway_mix_forward(P[0], P[1], P[2], c.n, P[3], None) == ab.highway_rule(c)
+        assert l.mmf_highway_mix_backward(P[0], P[1], P[2], P[3], c.n, P[4], P[5], P[6], None) == ab.highway_rule(c)
+    for c in ab.refused(ab.ABS_SUM, ab.abs_sum_rule):
+        assert l.mmf_abs_sum(P[0], c.n, P[1], P[2], None) == ab.abs_sum_rule(c)
+
+
+def test_batchnorm_adam_and_dense_backward_refusals_in_the_library():
+    m, l = _lib()
+    f = C.c_float
+    for c in ab.refused(ab.BN, ab.bn_rule) + [ab.Bn(4, 8, training=False), ab.Bn(4, 8, act=5), ab.Bn(4, 8, drop_p=1.0)]:
+        rm, rv = (P[4], P[5]) if c.running else (None, None)
+        rc = l.mmf_batchnorm_forward(P[0], None, None, None, rm, rv, c.B, c.F, int(c.training), f(1e-5), f(0.1), c.act, f(c.drop_p),
+                                     1, 1, None, P[1], P[2], P[3], None)
+        assert rc == ab.bn_rule(c) != ab.OK, c
+    for c in ab.refused(ab.ADAM, ab.adam_rule):
+        rc = l.mmf_adam_l1_step(P[0] + (4 if c.misalign else 0), P[1], P[2], P[3], c.n, f(1e-3), f(0.9), f(0.999), f(1e-8), f(c.wd),
+                                f(c.l1), None, c.step, None)
+        assert rc == ab.adam_rule(c), c
+    assert l.mmf_adam_l1_step(P[0], P[1], P[2], P[3], 8, f(1e-3), f(0.9), f(0.999), f(1e-8), f(0), f(0), P[4] + 4, 1, None) == ab.ERR_ALIGN
+    for c in ab.refused(ab.DENSE_BWD, ab.dense_bwd_rule):
+        if c.rows:
+            rc = l.mmf_dense_backward_rows(P[0], c.N + c.rows, P[1], c.N + c.rows, P[2], P[3], c.B, c.K, c.N, c.act, c.drop_kind,
+                                           f(0.25), 1, None, P[4], P[5], P[6], P[7], P[8], None)
+        else:
+            rc = l.mmf_dense_backward(P[0], P[1], P[2], P[3], c.B, c.K, c.N, c.act, c.drop_kind, f(0.25), 1, 1, None, P[5], P[6],
+                                      P[7], P[8], None)
+        assert rc == ab.dense_bwd_rule(c), c
+
+
+def test_header_states_every_cap_the_small_rules_restate():
+    import os
+    from conftest import ROOT
+    hdr = " ".join(open(os.path.join(ROOT, "include", "mmf_amil.h")).read().split())
+    for text in ("B * K <= 256", "B <= 8192", "K <= 32", "B >= 2", "N <= 2048 and B <= 256"):
+        assert text in hdr, text
+    assert "batch 1..128" not in hdr
+    from multimodalfusion_amd import _lib as m
+    assert m.ABI_VERSION == 12
+
+
+def test_small_tables_hold_what_the_issue_lists():
+    acc = lambda t, r: ab.accepted(t, r)
+    assert {(c.B, c.K) for c in acc(ab.HEAD, ab.head_rule) if c.B * c.K == 256} == {(8, 32), (256, 1)}
+    assert {(c.B, c.K) for c in ab.refused(ab.HEAD, ab.head_rule)} == {(9, 29), (257, 1)}
+    assert {c.B for c in acc(ab.COX, ab.cox_rule)} >= {2, 256, 257, 1000, 6145, 8192} and [c.B for c in ab.refused(ab.COX, ab.cox_rule)] == [8193]
+    assert {c.n for c in acc(ab.ADAM, ab.adam_rule)} == {1, 3, 4, 5, 1023, 1024, 1025, 1027}
+    assert {c.n for c in acc(ab.ABS_SUM, ab.abs_sum_rule)} >= {1, 131071, 131072, 131073} and max(c.n for c in ab.ABS_SUM) >= 7 * 131072 + 1
+    assert {c.K for c in acc(ab.HAZ, ab.haz_rule)} >= {1, 4, 32} and {c.K for c in ab.refused(ab.HAZ, ab.haz_rule)} == {0, 33}
+    assert {(c.B, c.N) for c in acc(ab.DENSE_BWD, ab.dense_bwd_rule)} >= {(256, 2048), (257, 8), (2, 2052)}
+    assert [c.bad_row for c in ab.NLL if c.bad_row >= 0] == [280]
+
+
+def test_small_inputs_meet_the_conditions_the_gpu_file_relies_on():
+    import small_cases as sc
+    # argmax is unambiguous: the top two logits of every row differ by >= 1e-3
+    for c in ab.accepted(ab.HEAD, ab.head_rule):
+        assert sc.top_two_gap(sc.head_ref(c)[0]["logits"]) >= 1e-3, c
+    for c in ab.accepted(ab.HAZ, ab.haz_rule):
+        assert sc.top_two_gap(sc.haz_inputs(c)["logits"]) >= 1e-3, c
+        if c.steep:         # (1 - h) underflows: some fp32 hazard is exactly 1
+            assert (sc.haz_ref(c)[0]["h32"] == 1).any() and (np.abs(sc.haz_inputs(c)["logits"]) > 25).all()
+    assert any((sc.head_ref(c)[0]["h32"] == 1).any() for c in ab.HEAD if c.steep)
+    # nll: labels 0 and K - 1, each under both censorship values; the bad label sits in a row >= 256
+    for c in ab.accepted(ab.NLL, ab.nll_rule):
+        i = sc.nll_inputs(c)
+        if c.B >= 2 * c.K:
+            assert {(y, v) for y, v in zip(i["Y"].tolist(), i["c"].tolist())} >= {(y, v) for y in (0, c.K - 1) for v in (0.0, 1.0)}, c
+        used = np.concatenate([i["hazards"].ravel(), i["S"].ravel()])          # the eps clamp: no input near eps = 1e-7
+        assert ((used > 1e-6) | (used < 1e-8)).all(), c
+        if c.bad_row >= 0:
+            assert c.bad_row >= 256 and i["Y"][c.bad_row] == c.K and int((i["Y"] >= c.K).sum()) == 1
+            assert np.isnan(sc.nll_ref(c)[0]["loss"]) and not sc.nll_ref(c)[0]["gH"][c.bad_row].any()
+    # Adam: the live elements do not cancel, the pad-like ones are +0 and -0 under a non-zero l1
+    for c in ab.accepted(ab.ADAM, ab.adam_rule):
+        for rnd in range(4):
+            i = sc.adam_inputs(c, rnd)
+            live = ~i["zeros"]
+            assert live.any() and (np.abs(i["g"][live]) >= 100 * (c.l1 + c.wd * np.abs(i["w"][live]))).all(), c
+            assert (np.sign(i["g"][live]) == np.sign(i["m"][live])).all() and (i["v"][live] > 0).all()
+            assert not i["w"][i["zeros"]].any() and not i["g"][i["zeros"]].any()
+        if c.n >= 4:
+            z = sc.adam_inputs(c)["w"][sc.adam_inputs(c)["zeros"]]
+            assert {bool(np.signbit(v)) for v in z} == {True, False}
+        if c.mask:          # live elements with w != 0 under mask 0 and under mask 1: in the tail, and from n = 1023 in the vectors
+            i, t0 = sc.adam_inputs(c), c.n - c.n % 4
+            live = ~i["zeros"] & (i["w"] != 0)
+            parts = [np.arange(c.n) >= t0] + ([np.arange(c.n) < t0] if c.n >= 1023 else [])
+            for part in parts:
+                assert {float(v) for v in i["mask"][live & part]} == {0.0, 1.0}, c
+    assert any(c.l1 > 0 and c.n >= 3 and c.n % 4 for c in ab.accepted(ab.ADAM, ab.adam_rule))       # a zero in a scalar tail
+    assert any(c.mask and c.l1 > 0 and c.n >= 1023 and c.n % 4 == 3 for c in ab.accepted(ab.ADAM, ab.adam_rule))
+    # Cox: every float64 risk-set sum inside fp32 range; the all-censored case is all censored
+    for c in ab.accepted(ab.COX, ab.cox_rule):
+        D = sc.cox_ref(c)[0]["D"]
+        assert np.isfinite(D).all() and D.min() > 1e-30 and D.max() < 1e30, c
+        assert bool(sc.cox_inputs(c)["c"].all()) == c.all_censored
+        assert c.B == 2 or len(set(sc.cox_inputs(c)["times"])) < c.B           # tied times
+    # ranking: the comparable-pair counts the cases claim
+    for c in ab.accepted(ab.RANK, ab.rank_rule):
+        n, i = sc.rank_ref(c)[0]["pairs"], sc.rank_inputs(c)
+        assert {"none": n == 0, "one": n == 1, "many": n > 1000, "tied": 1 < n < 15, "equal risks": n == 15}[c.kind], (c, n)
+        if c.kind == "tied":
+            assert len(set(i["times"])) < c.B
+        if c.kind == "equal risks":
+            assert c.phi == 1 and int((i["risks"] == 0.25).sum()) >= 3
+    # highway: zn exactly 0 somewhere; the dense backward: no recovered y within 1e-5 of SELU's kink under AlphaDropout
+    assert all((sc.highway_inputs(c)["zn"] == 0).any() for c in ab.accepted(ab.HIGHWAY, ab.highway_rule) if c.n >= 4)
+    for c in ab.accepted(ab.DENSE_BWD, ab.dense_bwd_rule):
+        out, _ = sc.dense_ref(c)
+        if c.drop_kind == 2:
+            kept = sc.dense_inputs(c)["keep"]
+            assert c.act == 4 and np.abs(out["y_rec"][kept]).min() > 1e-5, c
+        if c.act in (1, 4):
+            assert (out["y_act"] != 0).all() or c.act == 1
+        assert np.abs(out["dpre"]).max() > 0
+
+
+def test_small_bars_cover_every_element():
+    """No comparison leaves an element out: every bar has a finite, non-negative value for every element of its reference."""
+    import small_cases as sc
+    refs = [(ab.HEAD, ab.head_rule, sc.head_ref), (ab.NLL, ab.nll_rule, sc.nll_ref), (ab.COX, ab.cox_rule, sc.cox_ref),
+            (ab.RANK, ab.rank_rule, sc.rank_ref), (ab.HAZ, ab.haz_rule, sc.haz_ref), (ab.HIGHWAY, ab.highway_rule, sc.highway_ref),
+            (ab.BN, ab.bn_rule, sc.bn_ref), (ab.DENSE_BWD, ab.dense_bwd_rule, sc.dense_ref)]
+    for table, rule, ref in refs:
+        for c in ab.accepted(table, rule):
+            out, bar = ref(c)
+            for k, b in bar.items():
+                b = np.broadcast_to(np.asarray(b, np.float64), np.shape(out[k]))
+                assert np.isfinite(b).all() and (b >= 0).all(), (c, k)
+                assert (b[np.asarray(out[k]) != 0] > 0).all(), (c, k)
+
+
+def test_vectorised_restatements_match_the_ports():
+    """The sorted-cumulative-sum Cox and the pair-matrix ranking loss (needed at B = 700 and 8192) against oracle.torch_port
+    and oracle.stage2_port, loss and gradient, at sizes the ports' loops afford."""
+    import torch
+    import small_cases as sc
+    from oracle import stage2_port as s2
+    from oracle import torch_port as tp
+    for c in (ab.Cox(2), ab.Cox(5, all_censored=True), ab.Cox(40), ab.Cox(257)):
+        i = sc.cox_inputs(c)
+        r = sc.T(i["risks"]).requires_grad_(True)
+        want = tp.cox_loss(r, i["times"], torch.as_tensor(i["c"]))
+        want.backward()
+        loss, d = sc.cox_vectorised(i["risks"], i["times"], i["c"])[:2]
+        assert abs(loss - float(want.detach())) <= 1e-12 * max(1, abs(loss)) and np.abs(d - r.grad.numpy()).max() <= 1e-13
+    small = [c for c in ab.accepted(ab.RANK, ab.rank_rule) if c.B <= 6]
+    for c in small + [ab.Rank(40, p, r) for p in (0, 1) for r in (0, 1)]:
+        i = sc.rank_inputs(c)
+        r = sc.T(i["risks"]).requires_grad_(True)
+        want = s2.ranking_loss(r, torch.as_tensor(i["times"]), sc.T(i["c"]), "sigmoid" if c.phi == 0 else "relu",
+                               "mean" if c.reduction == 0 else "sum")
+        want.sum().backward()
+        grad = np.zeros(c.B) if r.grad is None else r.grad.numpy()
+        loss, d = sc.rank_vectorised(i["risks"], i["times"], i["c"], c.phi, c.reduction)[:2]
+        assert abs(loss - float(want.detach().sum())) <= 1e-12 * max(1, abs(loss)) and np.abs(d - grad).max() <= 1e-13, c
