@@ -48,18 +48,18 @@ class _ExportGroup:
         self.model, self.bags, self.entries, self.rows, self.limit = model, [], [], 0, None
 
     def takes(self, xs):
-        """xs: the bag's tensors (one per modality), or None when the grouped pass does not take the bag."""
-        from .utils.core_utils import _EvalGroup
+        """xs: the bag's tensors (one per modality), or None when the grouped pass does not take the bag.  Leaves the
+        bag's row limit in self.limit, for full()."""
+        from .utils.core_utils import _HeldBags
         if xs is None:
             return False
-        limit = _EvalGroup.row_limit(self.model, len(xs), int(xs[0].shape[1]), xs[0].dtype)
-        return int(xs[0].shape[0]) <= limit and (not self.bags or self.bags[0][0].dtype == xs[0].dtype)
+        self.limit = _HeldBags.row_limit(self.model, len(xs), int(xs[0].shape[1]), xs[0].dtype)
+        return int(xs[0].shape[0]) <= self.limit and (not self.bags or self.bags[0][0].dtype == xs[0].dtype)
 
     def full(self, xs):
+        """Whether what is held must run before the bag takes() just passed joins it."""
         from . import ops
-        from .utils.core_utils import _EvalGroup
-        limit = _EvalGroup.row_limit(self.model, len(xs), int(xs[0].shape[1]), xs[0].dtype)
-        return bool(self.bags) and (len(self.bags) >= ops.GROUP_MAX or self.rows + int(xs[0].shape[0]) > limit
+        return bool(self.bags) and (len(self.bags) >= ops.GROUP_MAX or self.rows + int(xs[0].shape[0]) > self.limit
                                     or self.bags[0][0].dtype != xs[0].dtype)
 
     def add(self, xs, entry):

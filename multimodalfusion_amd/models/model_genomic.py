@@ -39,9 +39,10 @@ class MaxNet(MaxNet_base):
     def __init__(self, input_dim: int, model_size_omic: str = "small", bag_loss=None, n_classes: int = 4):
         super().__init__(input_dim, model_size_omic, bag_loss, n_classes)
 
-    def cox_step_ok(self, x):
-        """True when cox_step can take this batch: the `small` net with a Cox head, B <= 256, input_dim <= 256."""
-        return ("nll" not in self.bag_loss and torch.is_tensor(x) and x.is_cuda and x.dim() == 2 and 1 <= x.shape[0] <= 256
+    def cox_step_ok(self, x, on_host=False):
+        """True when cox_step can take this batch: the `small` net with a Cox head, B <= 256, input_dim <= 256.  on_host: the
+        batch may still be on the host (the training loop asks before its copy)."""
+        return ("nll" not in self.bag_loss and torch.is_tensor(x) and (x.is_cuda or on_host) and x.dim() == 2 and 1 <= x.shape[0] <= 256
                 and x.shape[1] <= 256 and self.fc_omic[0][0].weight.shape[0] == 256 and self.fc_omic[1][0].weight.shape[0] == 256
                 and len(self.fc_omic) == 2 and self.classifier.weight.shape[0] == 1
                 and all(p.requires_grad for p in self.parameters()))

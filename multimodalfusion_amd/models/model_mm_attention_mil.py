@@ -167,6 +167,54 @@ class MM_MIL_Attention_fc_surv(MM_MIL_Attention_fc):
             F += width[k]
         return order, cols, F
 
+    def xfusion_step_ok(self):
+        """The XlinearFusion configuration nll_step and forward_group take: skip, the scaled embeddings within 384 columns."""
+        return bool(self.mm.skip) and len(self._concat_order()) * self.mm.reduce[0][0][0].weight.shape[0] <= 384
+
+    def xfusion_group_ok(self):
+        """The XlinearFusion configuration nll_step_group_tensor takes: skip, scale width 16."""
+        return bool(self.mm.skip) and self.mm.reduce[0][0][0].weight.shape[0] == 16
+
+    def _window_checks(self, path, radio, omic, labels, censors, forward_only=False):
+        """Every refusal of a window (_stacked_patients' branches) before the first launch -> (G, labels [G], censors [G]);
+        forward_only: forward_group's window -- a stricter omic check, labels optional."""
+        MmfError = ops._lib.MmfError
+        counts = {}
+        if path is not None:
+            counts["path"] = len(path[1])
+        if radio is not None:
+            counts["radio"] = len(radio[1])
+        if omic is not None:
+            G_in = self.fc_omic[0][0].in_features
+            if forward_only and (omic.dim() != 2 or omic.dtype != torch.float32 or omic.shape[1] != G_in):
+                raise MmfError(f"omic features must be fp32 [G x {G_in}], got {omic.dtype} {tuple(omic.shape)}")
+            if omic.dim() != 2:
+                raise MmfError(f"omic features must be [G x input_dim], got {tuple(omic.shape)}")
+            counts["omic"] = int(omic.shape[0])
+        if len(set(counts.values())) != 1:
+            raise MmfError(f"the branches hold different numbers of patients: {counts}")
+        G = next(iter(counts.values()))
+        if G < 1 or G > ops.GROUP_MAX:
+            raise MmfError(f"a group holds 1 .. {ops.GROUP_MAX} patients, got {G}")
+        for k, br in (("path", path), ("radio", radio)):
+            if br is None:
+                continue
+            xs = br[0] if k == "radio" else [br[0]]
+            if any(x.dtype != torch.float32 for x in xs):
+                raise MmfError("the grouped pass takes fp32 bags only (bf16 bags: one forward per patient)" if forward_only
+                               else "the grouped step takes fp32 bags only (bf16 bags: one nll_step per patient)")
+            if min(br[1]) < 1:
+                raise MmfError("empty bag in the group")
+            if any(x.dim() != 2 or x.shape[0] != sum(br[1]) for x in xs):
+                raise MmfError(f"the {k} bags hold {[tuple(x.shape) for x in xs]} rows, their sizes add up to {sum(br[1])}")
+        if forward_only and labels is None:
+            return G, None, None
+        Y = torch.as_tensor(labels).reshape(-1)
+        cc = torch.as_tensor(censors).reshape(-1)
+        if Y.numel() != G or cc.numel() != G:
+            raise MmfError(f"{G} patients need {G} labels and censorships, got {Y.numel()} / {cc.numel()}")
+        return G, Y, cc
+
     def nll_step(self, label, c, alpha=0.0, loss_scale=1.0, grad_out=None, accumulate=None, **kwargs):
         """Extension of the reference surface (the training-loop mirror uses it, utils/core_utils.py): the whole training
         step of one patient (fusion='concat'; fusion='tensor' in the heads' configuration) -- what `hazards, S, Y_hat, A_raw = model(**kwargs)`,
@@ -182,7 +230,7 @@ class MM_MIL_Attention_fc_surv(MM_MIL_Attention_fc):
         from ..ops import (_dense_bwd_raw, _dense_fwd_raw, _linear_cat_bwd_raw, _linear_cat_fwd_raw, _stack_bwd_raw,
                            _stack_fwd_raw, _xfusion_bwd_raw, _xfusion_fwd_raw)
         order, cols, F = self._concat_layout()
-        if self.fusion == "tensor" and not (self.mm.skip and len(order) * self.mm.reduce[0][0][0].weight.shape[0] <= 384):
+        if self.fusion == "tensor" and not self.xfusion_step_ok():
             raise NotImplementedError("nll_step covers the XlinearFusion configuration the heads use (skip, one patient)")
         params = list(self.parameters())
         if any(not p.requires_grad for p in params):
@@ -259,13 +307,8 @@ class MM_MIL_Attention_fc_surv(MM_MIL_Attention_fc):
                 # hazards + loss + their backward in one launch (forward() lines 182-188)
                 seed_f = ops.next_dropout_seed() if tr else 0
                 word_f = ops._seed_word
-                fus = self.mm
-                weights = []
-                for i in range(len(order)):
-                    for lin in (fus.reduce[i][0][0], fus.reduce[i][1][0], fus.reduce[i][2][0]):
-                        weights += [lin.weight, lin.bias]
-                weights += [fus.encoder1[0].weight, fus.encoder1[0].bias, fus.encoder2[0].weight, fus.encoder2[0].bias]
-                p_f = fus.dropout_rate if tr else 0.0
+                weights = self._xfusion_weights(len(order))
+                p_f = self.mm.dropout_rate if tr else 0.0
                 MMv, saved_x, state_x = _xfusion_fwd_raw([feat[:, cols[k]] for k in order], weights, p_f, seed_f)
                 c0, c3 = self.classifier[0], self.classifier[3]
                 p_c = self.classifier[2].p if tr else 0.0
@@ -391,7 +434,7 @@ class MM_MIL_Attention_fc_surv(MM_MIL_Attention_fc):
         (classifier[2])."""
         if self.fusion != "tensor":
             raise NotImplementedError("nll_step_group_tensor covers fusion='tensor'; the concat head has nll_step_group")
-        if not (self.mm.skip and self.mm.reduce[0][0][0].weight.shape[0] == 16):
+        if not self.xfusion_group_ok():
             raise NotImplementedError("nll_step_group_tensor covers the XlinearFusion configuration the heads use "
                                       "(skip, scale width 16)")
         return self._group_step("nll_step_group_tensor", patients, labels, censors, alpha, loss_scale, grad_out, accumulate,
@@ -416,35 +459,7 @@ class MM_MIL_Attention_fc_surv(MM_MIL_Attention_fc):
         if Wk.shape[0] > 32:
             raise MmfError(f"{what}: the fused hazard head takes K <= 32 classes")
         path, radio, omic = self._stacked_patients(patients)
-        # ---- every refusal before the first launch
-        counts = {}
-        if path is not None:
-            counts["path"] = len(path[1])
-        if radio is not None:
-            counts["radio"] = len(radio[1])
-        if omic is not None:
-            if omic.dim() != 2:
-                raise MmfError(f"omic features must be [G x input_dim], got {tuple(omic.shape)}")
-            counts["omic"] = int(omic.shape[0])
-        if len(set(counts.values())) != 1:
-            raise MmfError(f"the branches hold different numbers of patients: {counts}")
-        G = next(iter(counts.values()))
-        if G < 1 or G > ops.GROUP_MAX:
-            raise MmfError(f"a group holds 1 .. {ops.GROUP_MAX} patients, got {G}")
-        for k, br in (("path", path), ("radio", radio)):
-            if br is None:
-                continue
-            xs = br[0] if k == "radio" else [br[0]]
-            if any(x.dtype != torch.float32 for x in xs):
-                raise MmfError("the grouped step takes fp32 bags only (bf16 bags: one nll_step per patient)")
-            if min(br[1]) < 1:
-                raise MmfError("empty bag in the group")
-            if any(x.dim() != 2 or x.shape[0] != sum(br[1]) for x in xs):
-                raise MmfError(f"the {k} bags hold {[tuple(x.shape) for x in xs]} rows, their sizes add up to {sum(br[1])}")
-        Y = torch.as_tensor(labels).reshape(-1)
-        cc = torch.as_tensor(censors).reshape(-1)
-        if Y.numel() != G or cc.numel() != G:
-            raise MmfError(f"{G} patients need {G} labels and censorships, got {Y.numel()} / {cc.numel()}")
+        G, Y, cc = self._window_checks(path, radio, omic, labels, censors)
         if not Y.is_cuda and bool(((Y < 0) | (Y >= Wk.shape[0])).any()):
             raise IndexError(f"nll_surv: label out of range [0, {Wk.shape[0]})")
         tr = self.training
@@ -568,45 +583,14 @@ class MM_MIL_Attention_fc_surv(MM_MIL_Attention_fc):
             raise MmfError("forward_group runs the exact-fp32 GEMMs only (ops.set_gemm(0))")
         order, _, F = self._concat_layout()
         tensor = self.fusion == "tensor"
-        if tensor and not (self.mm.skip and len(order) * self.mm.reduce[0][0][0].weight.shape[0] <= 384):
+        if tensor and not self.xfusion_step_ok():
             raise NotImplementedError("forward_group covers the XlinearFusion configuration the heads use (skip)")
         head = self.classifier[3] if tensor else self.classifier
         Wk, bk = head.weight, head.bias
         if Wk.shape[0] > 32:
             raise MmfError("forward_group: the fused hazard head takes K <= 32 classes")
         path, radio, omic = self._stacked_patients(patients)
-        # ---- every refusal before the first launch
-        counts = {}
-        if path is not None:
-            counts["path"] = len(path[1])
-        if radio is not None:
-            counts["radio"] = len(radio[1])
-        if omic is not None:
-            if omic.dim() != 2 or omic.dtype != torch.float32 or omic.shape[1] != self.fc_omic[0][0].in_features:
-                raise MmfError(f"omic features must be fp32 [G x {self.fc_omic[0][0].in_features}], got "
-                               f"{omic.dtype} {tuple(omic.shape)}")
-            counts["omic"] = int(omic.shape[0])
-        if len(set(counts.values())) != 1:
-            raise MmfError(f"the branches hold different numbers of patients: {counts}")
-        G = next(iter(counts.values()))
-        if G < 1 or G > ops.GROUP_MAX:
-            raise MmfError(f"a group holds 1 .. {ops.GROUP_MAX} patients, got {G}")
-        for k, br in (("path", path), ("radio", radio)):
-            if br is None:
-                continue
-            xs = br[0] if k == "radio" else [br[0]]
-            if any(x.dtype != torch.float32 for x in xs):
-                raise MmfError("the grouped pass takes fp32 bags only (bf16 bags: one forward per patient)")
-            if min(br[1]) < 1:
-                raise MmfError("empty bag in the group")
-            if any(x.dim() != 2 or x.shape[0] != sum(br[1]) for x in xs):
-                raise MmfError(f"the {k} bags hold {[tuple(x.shape) for x in xs]} rows, their sizes add up to {sum(br[1])}")
-        Y = cc = None
-        if labels is not None:
-            Y = torch.as_tensor(labels).reshape(-1)
-            cc = torch.as_tensor(censors).reshape(-1)
-            if Y.numel() != G or cc.numel() != G:
-                raise MmfError(f"{G} patients need {G} labels and censorships, got {Y.numel()} / {cc.numel()}")
+        G, Y, cc = self._window_checks(path, radio, omic, labels, censors, forward_only=True)
         with torch.no_grad():
             A_raw, emb = {}, {}
             if "radio" in order:

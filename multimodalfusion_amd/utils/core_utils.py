@@ -65,27 +65,46 @@ def _skip(mode, radio_features, path_features, genomic_features):
     return False
 
 
-def _fused_step_ok(model, loss_fn, feats):
-    """One bag = one C-ABI call (model.nll_step).  Only where that is exactly what `model(**feats)` + the stock loss would
-    compute: the pathology head ITSELF (a subclass that overrides forward(), or any module / global hook, would be bypassed
-    by a graph-free step -- those take the autograd path), the stock NLLSurvLoss, one 2-D fp32 / bf16 bag on the GPU, a
-    classifier the kernel's single-workgroup tail holds (<= 32 classes), every parameter trainable."""
-    from ..models.model_attention_mil_path import MIL_Attention_fc_surv_path
+def _unhooked(model):
+    """Nothing that a call which goes round `model(...)` would bypass: no hook on any module of `model`, no global hook."""
     import torch.nn.modules.module as tm
-    x = feats.get("path_features")
-    if not (type(loss_fn) is NLLSurvLoss and torch.is_tensor(x) and x.dim() == 2 and x.is_cuda
-            and x.dtype in (torch.float32, torch.bfloat16)):
-        return False
-    if type(model).forward is not MIL_Attention_fc_surv_path.forward or not hasattr(model, "nll_step"):
-        return False
-    if getattr(getattr(model, "classifier", None), "out_features", 1 << 30) > 32:
-        return False
-    hooked = lambda m: bool(m._forward_hooks or m._forward_pre_hooks or m._backward_hooks or getattr(m, "_backward_pre_hooks", None))
-    if any(hooked(m) for m in model.modules()):
-        return False
     if tm._global_forward_hooks or tm._global_forward_pre_hooks or tm._global_backward_hooks or getattr(tm, "_global_backward_pre_hooks", None):
         return False
-    return all(p.requires_grad for p in model.parameters())
+    return not any(m._forward_hooks or m._forward_pre_hooks or m._backward_hooks or getattr(m, "_backward_pre_hooks", None)
+                   for m in model.modules())
+
+
+def _stock_head(model, step):
+    """(kind, hazard-head Linear) when a graph-free call computes what `model(**feats)` does, else (None, None).  kind:
+    'path' / 'radio' / 'mm' / 'omic' -- type(model).forward IS that head's (a subclass that overrides forward() would be
+    bypassed), the multimodal head with the concat fusion or the tensor fusion as the heads configure it
+    (xfusion_step_ok), a hazard head of <= 32 classes (the kernels' single-workgroup tail), nothing hooked (_unhooked: the
+    one walk over the modules).  step: asked for the one-call training steps -- every parameter trainable (the omic head:
+    cox_step_ok asks that itself) and, for the radiology and multimodal heads, the per-instance switch mmf_one_call_step (the
+    pathology step ignores it) -- or, False, for the grouped forward-only pass, which has no omic form.  DESIGN.md 7m."""
+    from ..models.model_attention_mil_path import MIL_Attention_fc_surv_path
+    from ..models.model_attention_mil_radio import MIL_Attention_fc_surv_radio
+    from ..models.model_genomic import MaxNet
+    from ..models.model_mm_attention_mil import MM_MIL_Attention_fc_surv
+    kind = {MIL_Attention_fc_surv_path.forward: "path", MIL_Attention_fc_surv_radio.forward: "radio",
+            MM_MIL_Attention_fc_surv.forward: "mm", MaxNet.forward: "omic"}.get(type(model).forward)
+    entry = ("cox_step" if kind == "omic" else "nll_step") if step else "forward_group"
+    if kind is None or (kind == "omic" and not step) or not hasattr(model, entry):
+        return None, None
+    head = getattr(model, "classifier", None)
+    if kind == "mm":
+        fusion = getattr(model, "fusion", None)
+        if fusion == "tensor" and model.xfusion_step_ok():
+            head = head[3]
+        elif fusion != "concat":
+            return None, None
+    if getattr(head, "out_features", 1 << 30) > 32:
+        return None, None
+    if step and kind in ("radio", "mm") and not getattr(model, "mmf_one_call_step", True):
+        return None, None
+    if not _unhooked(model) or (step and kind != "omic" and not all(p.requires_grad for p in model.parameters())):
+        return None, None
+    return kind, head
 
 
 class _Window:
@@ -163,9 +182,40 @@ class _Window:
         return True
 
 
-class _HeldBags:
-    """The bags a grouped call will take, held on the device until it runs (_BagGroup: a training window's; _EvalGroup: an
-    evaluation pass's).  Each bag is copied straight into its rows of one reusable device buffer [n_mod x rows x L] (no
+class _Group:
+    """What the two holders share.  Each exposes `held(model)`, what the model's grouped calls take, and `slots`, the
+    loader slots of what it holds (with `labels`, `cs`, `seeds` beside them); the training and the evaluation call are here."""
+
+    def run_step(self, model, alpha, loss_scale):
+        """One grouped training call (model.nll_step_group; nll_step_group_tensor for the tensor fusion) over what is held
+        -> [(loader slot, loss [1], risk [1])]; the holder is empty afterwards."""
+        if not self.slots:
+            return []
+        step = model.nll_step_group_tensor if getattr(model, "fusion", None) == "tensor" else model.nll_step_group
+        _, _, _, _, loss, risk = step(self.held(model), torch.cat(self.labels), torch.cat(self.cs), alpha=alpha,
+                                      loss_scale=loss_scale, seeds=self.seeds if model.training else None)
+        out = [(slot, loss[g:g + 1], risk[g:g + 1]) for g, slot in enumerate(self.slots)]
+        self.reset()
+        return out
+
+    def run_eval(self, model, loss_alpha=None):
+        """One grouped forward-only call (model.forward_group) over what is held -> [(slot, hazards [1 x K], S [1 x K], loss
+        (0-dim) or None)]; loss_alpha: each subject's NLLSurvLoss value with that alpha, or None for no loss.  The holder
+        is empty afterwards."""
+        if not self.slots:
+            return []
+        want = loss_alpha is not None
+        hz, S, _, _, loss, _ = model.forward_group(self.held(model), torch.cat(self.labels) if want else None,
+                                                   torch.cat(self.cs) if want else None, alpha=loss_alpha if want else 0.0)
+        out = [(slot, hz[g:g + 1], S[g:g + 1], loss[g] if want else None) for g, slot in enumerate(self.slots)]
+        self.reset()
+        return out
+
+
+class _HeldBags(_Group):
+    """The pathology and radiology heads' holder: the bags a grouped call will take, held on the device until it runs (a
+    training window's -- each with the dropout seed drawn when it arrived, so bag g of the loader gets the masks the per-bag
+    route gives it -- or an evaluation pass's).  Each bag is copied straight into its rows of one reusable device buffer [n_mod x rows x L] (no
     concatenation pass; fp32, or bf16 pathology bags in an evaluation pass): the pathology head's bag is one [n x L]
     tensor, the radiology head's one per modality.  A bag that would take the group past ops.GROUP_MAX bags or the row
     limit, or one of the other storage type, flushes what is held first (the window then runs as several grouped calls).
@@ -251,46 +301,24 @@ class _HeldBags:
         self.sizes.append(n); self.labels.append(label.reshape(1)); self.cs.append(c.reshape(1))
         self.seeds.append(seed); self.slots.append(slot)
 
-    def held(self, model):
-        """The held rows as the model's grouped calls take them: (x or [n_mod x rows x L], sizes)."""
+    def planes(self, stacked):
+        """The held rows, (x [rows x L] or, stacked, [n_mod x rows x L], sizes); the bags held by reference reach them here."""
         self.materialise()
-        x = self.buf[:, :self.rows] if hasattr(model, "attention_net_radio") else self.buf[0, :self.rows]
-        return x, list(self.sizes)
+        return (self.buf[:, :self.rows] if stacked else self.buf[0, :self.rows]), list(self.sizes)
+
+    def held(self, model):
+        """The held rows as the model's grouped calls take them: the radiology head's stacked, the pathology head's not."""
+        return self.planes(hasattr(model, "attention_net_radio"))
 
 
-class _BagGroup(_HeldBags):
-    """train_loop_survival(group=True): the eligible bags of the current window, until one grouped call
-    (model.nll_step_group) runs them.  A bag's dropout seed is drawn when it arrives, so bag g of the loader gets the
-    masks the per-bag route gives it.  fp32 only, by what the loop feeds it."""
-
-    def run(self, model, alpha, loss_scale):
-        """One grouped call over the held bags -> [(loader slot, loss [1], risk [1])]; the group is empty afterwards."""
-        if not self.sizes:
-            return []
-        seeds = self.seeds if model.training else None
-        _, _, _, _, loss, risk = model.nll_step_group(self.held(model), torch.cat(self.labels), torch.cat(self.cs),
-                                                      alpha=alpha, loss_scale=loss_scale, seeds=seeds)
-        out = [(slot, loss[g:g + 1], risk[g:g + 1]) for g, slot in enumerate(self.slots)]
-        self.reset()
-        return out
-
-
-def _group_tensor(model):
-    """The tensor fusion on the grouped route: a per-instance opt-in (model.mmf_group_tensor = True; absent means off),
-    like mmf_one_call_step / mmf_side_stream / mmf_fork_min_one_call."""
-    return (getattr(model, "fusion", None) == "tensor" and bool(getattr(model, "mmf_group_tensor", False))
-            and hasattr(model, "nll_step_group_tensor"))
-
-
-class _MMGroup:
-    """train_loop_survival(group=True) with the multimodal head: the eligible patients of the current window, until
-    one grouped call (MM_MIL_Attention_fc_surv.nll_step_group; nll_step_group_tensor for a tensor-fusion model that opted
-    in) runs them.  A patient's bags are copied straight into their
-    rows of three reusable device buffers -- the pathology plane [1 x rows x L], the radio planes [n_mod x rows x L] and the
-    omic rows [GROUP_MAX x input_dim] -- and its up to three dropout seeds are drawn when it arrives, in nll_step's order
-    (radio, path, omic; then the fusion seed of the tensor fusion), so patient g of the loader gets the masks the per-patient
-    route gives it.  A patient that would
-    take the group past ops.GROUP_MAX or past either branch's row limit flushes what is held first."""
+class _MMGroup(_Group):
+    """The multimodal head's holder: the eligible patients of a training window or of an evaluation pass, until one grouped
+    call (MM_MIL_Attention_fc_surv.nll_step_group, nll_step_group_tensor for a tensor-fusion model that opted in, or
+    forward_group) runs them.  A patient's bags are copied straight into their rows of three reusable device buffers -- the
+    pathology plane [1 x rows x L], the radio planes [n_mod x rows x L] and the omic rows [GROUP_MAX x input_dim] -- and its
+    dropout seeds are drawn when it arrives, in nll_step's order (radio, path, omic; then the fusion seed of the tensor
+    fusion), so patient g of the loader gets the masks the per-patient route gives it.  A patient that would take the group
+    past ops.GROUP_MAX or past either branch's row limit flushes what is held first."""
 
     def __init__(self):
         self.path, self.radio, self.omic = _HeldBags(), _HeldBags(), None
@@ -300,8 +328,7 @@ class _MMGroup:
     def reset(self):
         self.path.reset()
         self.radio.reset()
-        self.labels, self.cs, self.slots = [], [], []
-        self.seeds = {"radio": [], "path": [], "omic": []}
+        self.labels, self.cs, self.slots, self.seeds = [], [], [], {}
 
     def row_limits(self, model, L_path, L_radio):
         """(pathology, radio) row limits of one grouped call (ops.mm_group_row_limits), memoised by the bags' widths."""
@@ -313,6 +340,15 @@ class _MMGroup:
                 path=None if L_path is None else (L_path, *dims(model.attention_net_WSI)),
                 radio=None if L_radio is None else (len(model.modalities), L_radio, *dims(model.attention_net_radio)))
         return self.limits[key]
+
+    def takes(self, model, radio_features, path_features):
+        """Whether each bag of a patient _mm_bags_ok passed is within its branch's row limit (an evaluation pass asks; a
+        training window splits instead)."""
+        has = lambda k: k in model.mode
+        x_r = radio_features[model.modalities[0]] if has("radio") else None
+        lim_p, lim_r = self.row_limits(model, int(path_features.shape[1]) if has("path") else None,
+                                       int(x_r.shape[1]) if has("radio") else None)
+        return not (has("path") and int(path_features.shape[0]) > lim_p or has("radio") and int(x_r.shape[0]) > lim_r)
 
     def add(self, model, radio_features, path_features, genomic_features, label, c, slot, device, flush):
         """One patient (host or device tensors; label, c: device tensors) of loader slot `slot`."""
@@ -326,11 +362,9 @@ class _MMGroup:
         if self.slots and (len(self.slots) >= ops.GROUP_MAX or has("path") and self.path.rows + n_p > lim_p
                            or has("radio") and self.radio.rows + n_r > lim_r):
             flush()
-        for k in ("radio", "path", "omic"):
-            if has(k):
-                self.seeds[k].append(ops.next_dropout_seed() if model.training else 0)
-        if _group_tensor(model):               # nll_step draws the fusion seed after the branches'
-            self.seeds.setdefault("fusion", []).append(ops.next_dropout_seed() if model.training else 0)
+        # nll_step's order; a held tensor-fusion patient is one of a model that opted in (_bag_route)
+        for k in [k for k in ("radio", "path", "omic") if has(k)] + (["fusion"] if model.fusion == "tensor" else []):
+            self.seeds.setdefault(k, []).append(ops.next_dropout_seed() if model.training else 0)
         never = lambda: None                   # the flush above has made room in both planes
         if has("radio"):
             self.radio.add(xs_r, label, c, slot, lim_r, device, never)
@@ -343,31 +377,12 @@ class _MMGroup:
             self.omic[len(self.slots)].copy_(x, non_blocking=True)
         self.labels.append(label.reshape(1)); self.cs.append(c.reshape(1)); self.slots.append(slot)
 
-    def window(self, model):
+    def held(self, model):
         """The held patients as the model's grouped calls take them: the pre-stacked (path, radio, omic) triple."""
         has = lambda k: k in model.mode
-        self.path.materialise()
-        self.radio.materialise()
-        return ((self.path.buf[0, :self.path.rows], list(self.path.sizes)) if has("path") else None,
-                (self.radio.buf[:, :self.radio.rows], list(self.radio.sizes)) if has("radio") else None,
+        return (self.path.planes(False) if has("path") else None,
+                self.radio.planes(True) if has("radio") else None,
                 self.omic[:len(self.slots)] if has("omic") else None)
-
-    def run(self, model, alpha, loss_scale):
-        """One grouped call over the held patients -> [(loader slot, loss [1], risk [1])]; the group is empty afterwards."""
-        if not self.slots:
-            return []
-        has = lambda k: k in model.mode
-        seeds = {k: v for k, v in self.seeds.items() if has(k)} if model.training else None
-        step = model.nll_step_group
-        if _group_tensor(model):
-            step = model.nll_step_group_tensor
-            if seeds is not None:
-                seeds["fusion"] = self.seeds["fusion"]
-        _, _, _, _, loss, risk = step(self.window(model), torch.cat(self.labels), torch.cat(self.cs), alpha=alpha,
-                                      loss_scale=loss_scale, seeds=seeds)
-        out = [(slot, loss[g:g + 1], risk[g:g + 1]) for g, slot in enumerate(self.slots)]
-        self.reset()
-        return out
 
 
 def _window_of(model, optimizer, world, grad_buffer, inflight, device):
@@ -383,102 +398,65 @@ def _window_of(model, optimizer, world, grad_buffer, inflight, device):
     return w
 
 
-def _fused_cox_ok(model, loss_fn, feats):
-    """One omic batch = one launch (model.cox_step: MaxNet forward + CoxSurvLoss + backward).  Only where that is exactly what
-    `model(**feats)` + the stock loss would compute: MaxNet ITSELF with a Cox head, the stock CoxSurvLoss, no hooks."""
-    from ..models.model_genomic import MaxNet
-    import torch.nn.modules.module as tm
-    x = feats.get("genomic_features")
-    if type(loss_fn) is not CoxSurvLoss or type(model).forward is not MaxNet.forward or not hasattr(model, "cox_step"):
-        return False
-    hooked = lambda m: bool(m._forward_hooks or m._forward_pre_hooks or m._backward_hooks or getattr(m, "_backward_pre_hooks", None))
-    if any(hooked(m) for m in model.modules()):
-        return False
-    if tm._global_forward_hooks or tm._global_forward_pre_hooks or tm._global_backward_hooks or getattr(tm, "_global_backward_pre_hooks", None):
-        return False
-    return x is not None and x.dtype == torch.float32 and model.cox_step_ok(x)
-
-
-def _fused_radio_ok(model, loss_fn, feats, on_host=False):
-    """The radiology head's step without an autograd graph (model.nll_step: reduce_dim, then stack + head + loss + backward
-    in one call, then reduce_dim's backward).  Only where that is exactly what `model(**feats)` + the stock loss would
-    compute: MIL_Attention_fc_surv_radio ITSELF, the stock NLLSurvLoss, fp32 2-D modality bags of one shape on the GPU, no
-    hooks, every parameter trainable.  on_host: the bags may still be on the host (group=True asks before the copy)."""
-    from ..models.model_attention_mil_radio import MIL_Attention_fc_surv_radio
-    import torch.nn.modules.module as tm
-    if type(loss_fn) is not NLLSurvLoss or type(model).forward is not MIL_Attention_fc_surv_radio.forward:
-        return False
-    if not getattr(model, "mmf_one_call_step", True) or getattr(model.classifier, "out_features", 1 << 30) > 32:
-        return False
-    bags = [feats.get(m) for m in model.modalities]
-    if any(not (torch.is_tensor(b) and (b.is_cuda or on_host) and b.dim() == 2 and b.dtype == torch.float32) for b in bags):
-        return False
-    if any(b.shape != bags[0].shape for b in bags):
-        return False
-    hooked = lambda m: bool(m._forward_hooks or m._forward_pre_hooks or m._backward_hooks or getattr(m, "_backward_pre_hooks", None))
-    if any(hooked(m) for m in model.modules()):
-        return False
-    if tm._global_forward_hooks or tm._global_forward_pre_hooks or tm._global_backward_hooks or getattr(tm, "_global_backward_pre_hooks", None):
-        return False
-    return all(p.requires_grad for p in model.parameters())
-
-
-def _fused_mm_ok(model, loss_fn, feats, on_host=False):
-    """One patient = one fixed sequence of C-ABI calls without an autograd graph (model.nll_step of the multimodal concat
-    head).  Only where that is exactly what `model(**feats)` + the stock loss would compute: MM_MIL_Attention_fc_surv ITSELF
-    (concat fusion, or the tensor fusion as the heads configure it), the stock NLLSurvLoss, no hooks, every parameter trainable, inputs on the GPU.
-    on_host: the inputs may still be on the host (group=True asks before the copy)."""
-    from ..models.model_mm_attention_mil import MM_MIL_Attention_fc_surv
-    import torch.nn.modules.module as tm
-    if type(loss_fn) is not NLLSurvLoss or type(model).forward is not MM_MIL_Attention_fc_surv.forward:
-        return False
-    if not getattr(model, "mmf_one_call_step", True):
-        return False
-    fusion = getattr(model, "fusion", None)
-    if fusion == "concat":
-        head = model.classifier
-    elif fusion == "tensor":
-        head = model.classifier[3]
-        if not (model.mm.skip and len(model._concat_order()) * model.mm.reduce[0][0][0].weight.shape[0] <= 384):
-            return False
-    else:
-        return False
-    if head.out_features > 32:
-        return False
-    for v in feats.values():
-        if not (torch.is_tensor(v) and (v.is_cuda or on_host)):
-            return False
-    hooked = lambda m: bool(m._forward_hooks or m._forward_pre_hooks or m._backward_hooks or getattr(m, "_backward_pre_hooks", None))
-    if any(hooked(m) for m in model.modules()):
-        return False
-    if tm._global_forward_hooks or tm._global_forward_pre_hooks or tm._global_backward_hooks or getattr(tm, "_global_backward_pre_hooks", None):
-        return False
-    return all(p.requires_grad for p in model.parameters())
-
-
-def _mm_group_ok(model, loss_fn, radio_features, path_features, genomic_features):
-    """A multimodal patient the window's grouped call takes (model.nll_step_group): what _fused_mm_ok allows (asked on the
-    tensors as the loader delivers them, host or device), the concat fusion -- or the tensor fusion with scale width 16 on a
-    model that opted in (model.mmf_group_tensor = True: nll_step_group_tensor) --, and for every branch in model.mode a
-    2-D fp32 bag (the modalities of one shape) or an omic vector of the model's input width."""
-    if _group_tensor(model):
-        if model.mm.reduce[0][0][0].weight.shape[0] != 16:
-            return False
-    elif getattr(model, "fusion", None) != "concat" or not hasattr(model, "nll_step_group"):
-        return False
-    feats = dict(radio_features, path_features=path_features, genomic_features=genomic_features)
-    if not _fused_mm_ok(model, loss_fn, feats, on_host=True):
-        return False
-    bag = lambda t: t.dim() == 2 and t.dtype == torch.float32 and t.shape[0] >= 1
+def _mm_bags_ok(model, radio_features, path_features, genomic_features):
+    """A multimodal patient's tensors as the grouped calls take them (nll_step_group[_tensor], forward_group): for every
+    branch in model.mode a 2-D fp32 bag of >= 1 rows (the modalities of one shape) or an omic vector of the model's input
+    width -- its dtype is the caller's question.  The tensors may still be on the host."""
+    bag = lambda t: torch.is_tensor(t) and t.dim() == 2 and t.dtype == torch.float32 and t.shape[0] >= 1
     if "path" in model.mode and not bag(path_features):
         return False
     if "radio" in model.mode:
-        xs = [radio_features.get(m) for m in model.modalities]
-        if any(x is None or not bag(x) or x.shape != xs[0].shape for x in xs):
+        xs = [radio_features.get(m) if isinstance(radio_features, dict) else None for m in model.modalities]
+        if any(not bag(x) or x.shape != xs[0].shape for x in xs):
             return False
-    if "omic" in model.mode and genomic_features.numel() != model.fc_omic[0][0].in_features:
+    if "omic" in model.mode and not (torch.is_tensor(genomic_features)
+                                     and genomic_features.numel() == model.fc_omic[0][0].in_features):
         return False
     return True
+
+
+def _bag_route(model, loss_fn, radio_features, path_features, genomic_features, group=False, inflight=1, gemm=0):
+    """The one route a bag takes through train_loop_survival (the table of DESIGN.md 7m), from the tensors as the loader
+    delivers them -- nothing is copied to decide it -- and with one walk over the model's modules (_stock_head):
+      held-path / held-radio / held-mm   held for the window's grouped call (group, exact-fp32 GEMMs, fp32 bags);
+      step-path / step-radio / step-mm   the head's nll_step, no autograd graph;   step-cox   MaxNet.cox_step;
+      pipe-fused / pipe-autograd         inflight > 1: only the pathology head has a fused form there;
+      autograd                           model(**feats), the loss, backward().
+    A graph-free route only where it is exactly what `model(**feats)` + the stock loss would compute: a stock head
+    (_stock_head) and the stock loss class.  The one-call steps need their inputs on the GPU, where the loop's copy leaves
+    them whenever there is one; a held bag may stay where it is."""
+    kind, _ = _stock_head(model, step=True)
+    piped, hold, fp32 = inflight > 1, group and gemm == 0, torch.float32
+    on_gpu = lambda t: t.is_cuda or torch.cuda.is_available()
+    nll = type(loss_fn) is NLLSurvLoss
+    if kind == "path" and nll:
+        x = path_features
+        if torch.is_tensor(x) and x.dim() == 2 and on_gpu(x) and x.dtype in (fp32, torch.bfloat16):
+            if piped:
+                return "pipe-fused"
+            return "held-path" if hold and x.dtype == fp32 else "step-path"       # a bf16 bag runs alone
+    elif kind == "radio" and nll:
+        xs = [radio_features.get(m) for m in model.modalities]
+        if all(torch.is_tensor(x) and x.dim() == 2 and x.dtype == fp32 and x.shape == xs[0].shape for x in xs):
+            if hold:
+                return "held-radio"
+            if not piped and all(on_gpu(x) for x in xs):
+                return "step-radio"
+    elif kind == "mm" and nll:
+        every = [*radio_features.values(), path_features, genomic_features]
+        if all(torch.is_tensor(t) for t in every):
+            opted = model.fusion == "tensor" and bool(getattr(model, "mmf_group_tensor", False))   # per instance; absent: off
+            if hold and (model.xfusion_group_ok() if opted else model.fusion == "concat") \
+                    and _mm_bags_ok(model, radio_features, path_features, genomic_features):
+                return "held-mm"
+            if not piped and all(on_gpu(t) for t in every):
+                return "step-mm"
+    elif kind == "omic" and type(loss_fn) is CoxSurvLoss and not piped:
+        # cox_step_ok: the batch's shape, a Cox head, every parameter trainable; the loop's copy makes the batch fp32
+        x = genomic_features
+        if torch.is_tensor(x) and on_gpu(x) and model.cox_step_ok(x, on_host=True):
+            return "step-cox"
+    return "pipe-autograd" if piped else "autograd"
 
 
 def train_loop_survival(epoch, model, loader, optimizer, n_classes, mode, writer=None, loss_fn=None, reg_fn=None,
@@ -501,9 +479,11 @@ def train_loop_survival(epoch, model, loader, optimizer, n_classes, mode, writer
                 of the epoch; more than ops.GROUP_MAX bags or the row limit split it into several calls.  Each bag's
                 dropout seed is drawn when it arrives; a bag the grouped call does not take flushes the group and runs
                 alone.  Losses and risks are logged in loader order as before.  Not with inflight > 1 or dp on several
-                ranks.  The multimodal concat head's patients (those its one-call step takes, fp32 bags) are held in the same
+                ranks.  The multimodal head's patients (those its one-call step takes, fp32 bags) are held in the same
                 way -- a pathology plane, the radio planes and the omic rows -- and run as ONE nll_step_group per window;
-                the tensor fusion keeps the per-patient route."""
+                a tensor-fusion model's when it opted in (model.mmf_group_tensor = True, scale width 16:
+                nll_step_group_tensor), else they keep the per-patient route.  _bag_route picks each bag's route."""
+    from .. import ops
     from ..feed import RankShard
     from .utils import l1_reg_all, l1_reg_modules
     device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
@@ -529,17 +509,15 @@ def train_loop_survival(epoch, model, loader, optimizer, n_classes, mode, writer
     n_total = shard.n_total if shard is not None else None
     losses, regs, all_risk, all_c, all_t = [], [], [], [], []
     n_pos = 0
-    held = None
     if group:
-        from .. import ops
         held = getattr(win, "group", None)
         if held is None:
             held = win.group = _MMGroup() if hasattr(model, "attention_net_radio") and hasattr(model, "attention_net_WSI") \
-                else _BagGroup()
+                else _HeldBags()
         alpha_g = getattr(loss_fn, "alpha", 0.0)
 
         def flush():      # the held bags' losses / risks land in their loader slots
-            for slot, loss_g, risk_g in held.run(model, alpha_g, 1.0 / G):
+            for slot, loss_g, risk_g in held.run_step(model, alpha_g, 1.0 / G):
                 losses[slot] = loss_g.reshape(())
                 all_risk[slot] = risk_g.reshape(-1)
     for i, batch in enumerate(shard if shard is not None else loader):
@@ -553,16 +531,16 @@ def train_loop_survival(epoch, model, loader, optimizer, n_classes, mode, writer
                 # the reference's gather (utils/loss_utils.py:30-33) raises on such a label; on the device the kernels
                 # would write a NaN loss instead, which only shows in the epoch mean -- so check while it is on the host
                 raise IndexError(f"survival bin label {label.tolist()} outside [0, {n_classes})")
-            # group: a host bag goes straight from the loader into its rows of the group buffer (an empty slice of it
-            # stands in while the route is decided).  A radiology bag is judged on its host tensors, before any copy.
-            direct = group and torch.is_tensor(path_features) and not path_features.is_cuda
-            grouped_radio = group and ops._gemm == 0 and _fused_radio_ok(model, loss_fn, radio_features, on_host=True)
-            grouped_mm = group and ops._gemm == 0 and isinstance(held, _MMGroup) \
-                and _mm_group_ok(model, loss_fn, radio_features, path_features, genomic_features)
-            feats, label, c = _to_device({k: r[:0] for k, r in radio_features.items()} if grouped_radio or grouped_mm
-                                         else radio_features,
-                                         path_features[:0] if direct else path_features, genomic_features, label, c,
-                                         device)
+            # one route per bag, asked per bag (a hook registered mid-epoch takes effect at the next one) on the tensors as
+            # they arrive: a held bag goes straight from where it is into its rows of the group buffer
+            route = _bag_route(model, loss_fn, radio_features, path_features, genomic_features, group, inflight, ops._gemm)
+            holds = route.startswith("held-")
+            if group and not holds:
+                flush()                  # the bags held so far run first: the window keeps loader order
+            if holds:
+                label, c = label.to(device), c.to(device)
+            else:
+                feats, label, c = _to_device(radio_features, path_features, genomic_features, label, c, device)
 
             def forward_loss():
                 hazards, S, Y_hat, _ = model(**feats)
@@ -572,46 +550,27 @@ def train_loop_survival(epoch, model, loader, optimizer, n_classes, mode, writer
                     return -torch.sum(S, dim=1), loss_fn(hazards=hazards, S=S, Y=label, c=c)
                 raise NotImplementedError(type(loss_fn))
 
-            fused_step = _fused_step_ok(model, loss_fn, feats)
-            grouped = grouped_radio or grouped_mm or (group and fused_step and feats["path_features"].dtype == torch.float32
-                                                      and ops._gemm == 0)
-            if group and not grouped:
-                flush()                  # the bags held so far run first: the window keeps loader order
-                if direct:
-                    feats["path_features"] = path_features.to(device, non_blocking=True)
-            fused_cox = (not fused_step) and pipe is None and _fused_cox_ok(model, loss_fn, feats)
-            fused_mm = (not fused_step) and (not fused_cox) and pipe is None and _fused_mm_ok(model, loss_fn, feats)
-            fused_radio = (not grouped) and (not fused_step) and (not fused_cox) and (not fused_mm) and pipe is None \
-                and _fused_radio_ok(model, loss_fn, feats)
-            if grouped_mm:
-                # the multimodal patient, held for the window's grouped call: host tensors go straight into their rows
+            loss = risk = None           # a held bag's fill these slots when its group runs
+            if route == "held-mm":
                 held.add(model, radio_features, path_features, genomic_features, label, c, len(losses), device, flush)
-                loss = risk = None
-            elif grouped:
-                # held for the window's grouped call; its loss and risk fill these slots when the group runs
-                if grouped_radio:
-                    xs = [radio_features[m] for m in model.modalities]
-                else:
-                    xs = [path_features if direct else feats["path_features"]]
+            elif holds:
+                xs = [radio_features[m] for m in model.modalities] if route == "held-radio" else [path_features]
                 held.add(xs, label, c, len(losses), held.row_limit(model, len(xs), int(xs[0].shape[1])), device, flush,
                          seed=ops.next_dropout_seed() if model.training else 0)
-                loss = risk = None
-            elif fused_radio:
+            elif route in ("step-radio", "step-mm"):
+                # reduce_dim / the branches, one head + loss launch, their backwards -- no autograd graph
                 _, _, _, _, loss, risk = model.nll_step(label, c, alpha=loss_fn.alpha, loss_scale=1.0 / G, **feats)
-                fused_step = True
-            elif fused_mm:
-                # the multimodal concat head: branches, one head + loss launch, branch backwards -- no autograd graph; the
-                # gradient of loss / G is already in .grad
-                _, _, _, _, loss, risk = model.nll_step(label, c, alpha=loss_fn.alpha, loss_scale=1.0 / G, **feats)
-                fused_step = True
-            elif fused_cox:
-                # the omic batch: MaxNet forward + Cox + backward in one launch; the gradient of loss / G is already in .grad
+            elif route == "step-path":
+                # forward + nll_surv + backward of the bag in one call
+                _, _, _, _, loss, risk = model.nll_step(feats["path_features"], label, c, alpha=loss_fn.alpha,
+                                                        loss_scale=1.0 / G)
+            elif route == "step-cox":
+                # the omic batch: MaxNet forward + Cox + backward in one launch
                 risk, loss = model.cox_step(feats["genomic_features"], event_time, c, loss_scale=1.0 / G)
-                fused_step = True
-            elif pipe is not None and fused_step:
+            elif route == "pipe-fused":
                 _, _, _, _, loss, risk = pipe.run_fused(model, feats["path_features"], label, c, loss_fn.alpha,
                                                         loss_scale=1.0 / G)
-            elif pipe is not None:
+            elif route == "pipe-autograd":
                 box = {}
 
                 def bag():
@@ -620,10 +579,6 @@ def train_loop_survival(epoch, model, loader, optimizer, n_classes, mode, writer
 
                 pipe.run(bag, inputs=list(feats.values()) + [label, c])
                 risk, loss = box["risk"], box["loss"]
-            elif fused_step:
-                # forward + nll_surv + backward of the bag in one call; the gradient of loss / G is already in .grad
-                _, _, _, _, loss, risk = model.nll_step(feats["path_features"], label, c, alpha=loss_fn.alpha,
-                                                        loss_scale=1.0 / G)
             else:
                 risk, loss = forward_loss()
             if fused_tail:
@@ -632,17 +587,18 @@ def train_loop_survival(epoch, model, loader, optimizer, n_classes, mode, writer
                 loss_reg = optimizer.l1_value() if (reg_fn is not None and lambda_reg) else 0
             else:
                 loss_reg = 0 if reg_fn is None else reg_fn(model) * lambda_reg
-            losses.append(None if grouped else loss.detach())
+            losses.append(None if holds else loss.detach())
             regs.append(loss_reg.detach() if torch.is_tensor(loss_reg) else torch.tensor(float(loss_reg), device=device))
-            all_risk.append(None if grouped else risk.detach().reshape(-1))
+            all_risk.append(None if holds else risk.detach().reshape(-1))
             all_c.append(c.detach().reshape(-1))
             all_t.append(np.asarray(event_time).reshape(-1))
             # the reference: loss = loss / gc + loss_reg ; backward (core_utils.py:242-243)
-            if fused_step or grouped:
+            if route == "autograd":
+                (loss / G if fused_tail else loss / G + loss_reg).backward()
+            elif not route.startswith("pipe-"):
+                # held or a one-call step: the gradient of loss / G is (or will be) in .grad already
                 if not fused_tail and torch.is_tensor(loss_reg) and loss_reg.requires_grad:
                     loss_reg.backward()          # the autograd L1 term touches parameters only
-            elif pipe is None:
-                (loss / G if fused_tail else loss / G + loss_reg).backward()
             win.kept += 1
         # window boundary: the last position of this rank's window is `last`; (last + 1) % G == 0 as the reference's
         # (batch_idx + 1) % gc == 0.  With world > 1 `last` belongs to rank world - 1 and must exist in the loader.
@@ -676,31 +632,12 @@ def train_loop_survival(epoch, model, loader, optimizer, n_classes, mode, writer
 
 def _eval_group_head(model):
     """'path' / 'path_fp32' / 'radio' / 'mm' when the grouped forward-only pass (model.forward_group) computes what
-    `model(**feats)` does under no_grad -- the pathology, radiology or multimodal head ITSELF (an overridden forward or any hook would
-    be bypassed), a classifier of <= 32 classes, the exact-fp32 GEMM mode -- else None.  'path_fp32': a pathology head
-    whose bf16 bags the grouped pass does not take (ops.infer_group_takes_bf16).  Asked once per pass: none of it changes
-    between bags."""
+    `model(**feats)` does under no_grad -- a stock pathology, radiology or multimodal head (_stock_head) in the exact-fp32
+    GEMM mode -- else None.  'path_fp32': a pathology head whose bf16 bags the grouped pass does not take
+    (ops.infer_group_takes_bf16).  Asked once per pass: none of it changes between bags."""
     from .. import ops
-    from ..models.model_attention_mil_path import MIL_Attention_fc_surv_path
-    from ..models.model_attention_mil_radio import MIL_Attention_fc_surv_radio
-    import torch.nn.modules.module as tm
-    from ..models.model_mm_attention_mil import MM_MIL_Attention_fc_surv
-    kind = {MIL_Attention_fc_surv_path.forward: "path", MIL_Attention_fc_surv_radio.forward: "radio",
-            MM_MIL_Attention_fc_surv.forward: "mm"}.get(type(model).forward)
-    head = getattr(model, "classifier", None)
-    if kind == "mm":             # both fusions; the tensor fusion in the configuration its kernels take (as nll_step)
-        if getattr(model, "fusion", None) == "tensor":
-            head = head[3]
-            if not (model.mm.skip and len(model._concat_order()) * model.mm.reduce[0][0][0].weight.shape[0] <= 384):
-                return None
-        elif getattr(model, "fusion", None) != "concat" or not hasattr(model, "forward_group"):
-            return None
-    if ops._gemm != 0 or getattr(head, "out_features", 1 << 30) > 32:
-        return None
-    hooked = lambda m: bool(m._forward_hooks or m._forward_pre_hooks or m._backward_hooks or getattr(m, "_backward_pre_hooks", None))
-    if kind is None or any(hooked(m) for m in model.modules()):
-        return None
-    if tm._global_forward_hooks or tm._global_forward_pre_hooks or tm._global_backward_hooks or getattr(tm, "_global_backward_pre_hooks", None):
+    kind, _ = _stock_head(model, step=False)
+    if kind is None or ops._gemm != 0:
         return None
     if kind == "path":           # bf16 bags too, unless the head's one-bag bf16 route is a fused form
         from ..models.model_modules import stack_args
@@ -732,89 +669,60 @@ def _eval_group_bags(model, radio_features, path_features, kind=0):
     return xs
 
 
-class _EvalGroup(_HeldBags):
-    """validate_survival / summary_survival(group=True): the eligible bags of an evaluation pass, until one grouped
-    forward-only call (model.forward_group) runs them.  One per pass: nothing outlives the pass (an exception leaves no
-    held bags behind, and the buffer is freed with it)."""
-
-    def run(self, model, loss_alpha=None):
-        """One grouped call over the held bags -> [(slot, hazards [1 x K], S [1 x K], loss (0-dim) or None, risk [1])];
-        loss_alpha: each bag's NLLSurvLoss value with that alpha, or None for no loss.  The group is empty afterwards."""
-        if not self.sizes:
-            return []
-        want = loss_alpha is not None
-        hz, S, _, _, loss, risk = model.forward_group(self.held(model), torch.cat(self.labels) if want else None,
-                                                      torch.cat(self.cs) if want else None,
-                                                      alpha=loss_alpha if want else 0.0)
-        out = [(slot, hz[g:g + 1], S[g:g + 1], loss[g] if want else None, risk[g:g + 1])
-               for g, slot in enumerate(self.slots)]
-        self.reset()
-        return out
-
-
-def _mm_eval_ok(model, radio_features, path_features, genomic_features):
-    """A multimodal subject the grouped forward-only pass takes (MM_MIL_Attention_fc_surv.forward_group): for every
-    branch in model.mode a 2-D fp32 bag (the modalities of one shape) or an omic vector of the model's input width.  The
-    tensors may still be on the host."""
-    bag = lambda t: torch.is_tensor(t) and t.dim() == 2 and t.dtype == torch.float32 and t.shape[0] >= 1
-    if "path" in model.mode and not bag(path_features):
-        return False
-    if "radio" in model.mode:
-        xs = [radio_features.get(m) if isinstance(radio_features, dict) else None for m in model.modalities]
-        if any(not bag(x) or x.shape != xs[0].shape for x in xs):
-            return False
-    if "omic" in model.mode and not (torch.is_tensor(genomic_features) and genomic_features.is_floating_point()
-                                     and genomic_features.numel() == model.fc_omic[0][0].in_features):
-        return False
-    return True
-
-
-class _MMEvalGroup(_MMGroup):
-    """validate_survival / summary_survival(group=True) with the multimodal head: the forward-only sibling of _MMGroup --
-    the eligible patients of an evaluation pass in the same three buffers (pathology plane, radio planes, omic rows),
-    until one grouped forward-only call (model.forward_group) runs them.  One per pass, as _EvalGroup."""
-
-    def takes(self, model, radio_features, path_features, genomic_features):
-        """Whether the subject can be held: _mm_eval_ok, and each of its bags within that branch's row limit."""
-        if not _mm_eval_ok(model, radio_features, path_features, genomic_features):
-            return False
-        has = lambda k: k in model.mode
-        x_r = radio_features[model.modalities[0]] if has("radio") else None
-        lim_p, lim_r = self.row_limits(model, int(path_features.shape[1]) if has("path") else None,
-                                       int(x_r.shape[1]) if has("radio") else None)
-        return not (has("path") and int(path_features.shape[0]) > lim_p or has("radio") and int(x_r.shape[0]) > lim_r)
-
-    def run(self, model, loss_alpha=None):
-        """As _EvalGroup.run, over the held patients."""
-        if not self.slots:
-            return []
-        want = loss_alpha is not None
-        hz, S, _, _, loss, risk = model.forward_group(self.window(model), torch.cat(self.labels) if want else None,
-                                                      torch.cat(self.cs) if want else None,
-                                                      alpha=loss_alpha if want else 0.0)
-        out = [(slot, hz[g:g + 1], S[g:g + 1], loss[g] if want else None, risk[g:g + 1])
-               for g, slot in enumerate(self.slots)]
-        self.reset()
-        return out
-
-
 def _eval_hold(model, kind, held, limits, batch, slot, device, flush):
     """Holds the subject `batch` (the loader's tuple) for the pass's grouped call when that call takes it (`kind`:
-    _eval_group_head's answer) and returns its (label, c) on the device; None: the subject runs alone."""
+    _eval_group_head's answer) and returns its (label, c) on the device; None: the subject runs alone.  A multimodal
+    patient: _mm_bags_ok, a floating-point omic vector, each bag within its branch's row limit."""
     radio_features, path_features, genomic_features, label, _, c = batch
     if kind == "mm":
-        if not held.takes(model, radio_features, path_features, genomic_features):
+        if not (_mm_bags_ok(model, radio_features, path_features, genomic_features)
+                and ("omic" not in model.mode or genomic_features.is_floating_point())
+                and held.takes(model, radio_features, path_features)):
             return None
         label, c = label.to(device), c.to(device)
         held.add(model, radio_features, path_features, genomic_features.float(), label, c, slot, device, flush)
         return label, c
     xs = _eval_group_bags(model, radio_features, path_features, kind)
-    limit = _EvalGroup.limit_of(model, xs, limits) if xs is not None else 0
+    limit = _HeldBags.limit_of(model, xs, limits) if xs is not None else 0
     if xs is None or int(xs[0].shape[0]) > limit:
         return None
     label, c = label.to(device), c.to(device)
     held.add(xs, label, c, slot, limit, device, flush)
     return label, c
+
+
+def _eval_pass(model, loader, mode, group, device, land, loss_alpha=None):
+    """The one skeleton of validate_survival and summary_survival, to be advanced under torch.no_grad(): yields (batch,
+    label, c on the device, held) for every subject the reference does not skip, in loader order, one batch at a time.
+    Slot s belongs to the s-th subject yielded; `land(slot, event_time, label, c, hazards, S, loss)` receives its outputs:
+    before the yield for a subject that ran alone (loss None), and for a held one (group=True, a head the grouped pass
+    takes: _eval_hold) when its grouped call runs -- before any subject that runs alone, and at the end of the pass --
+    with its NLLSurvLoss(loss_alpha) value when loss_alpha is given.  One holder per pass: nothing outlives it (an
+    exception leaves no held bags behind, and the buffer is freed with it)."""
+    kind = _eval_group_head(model) if group else None
+    held, limits, meta = _MMGroup() if kind == "mm" else _HeldBags(), {}, {}
+
+    def flush():
+        for slot, hz, S, loss in held.run_eval(model, loss_alpha):
+            land(slot, *meta.pop(slot), hz, S, loss)
+
+    slot = 0
+    for batch in loader:
+        radio_features, path_features, genomic_features, label, event_time, c = batch
+        if _skip(mode, radio_features, path_features, genomic_features):
+            continue
+        took = _eval_hold(model, kind, held, limits, batch, slot, device, flush) if kind else None
+        if took is not None:
+            meta[slot] = (event_time, *took)
+            yield batch, *took, True
+        else:
+            flush()                      # the bags held so far run first
+            feats, label, c = _to_device(radio_features, path_features, genomic_features, label, c, device)
+            hazards, S, _, _ = model(**feats)
+            land(slot, event_time, label, c, hazards, S, None)
+            yield batch, label, c, False
+        slot += 1
+    flush()
 
 
 def validate_survival(cur, epoch, model, loader, n_classes, mode, early_stopping=None, writer=None, loss_fn=None,
@@ -825,71 +733,42 @@ def validate_survival(cur, epoch, model, loader, n_classes, mode, early_stopping
     model.forward_group call per ops.GROUP_MAX bags or row limit, flushed at the end; each bag's loss and risk land in its
     loader slot, so every logged quantity is in the order of the per-bag loop.  A bag it does not take flushes the group
     and runs alone.  The stock NLLSurvLoss value comes from the grouped call, with the alpha the per-bag branch passes;
-    other losses are called on the bag's slice.  reg_fn(model) is evaluated once per pass (the weights are fixed).
-    A multimodal model's patients (both fusions; _mm_eval_ok) are held the same way in _MMEvalGroup -- a pathology plane,
-    the radio planes and the omic rows -- and run as one MM_MIL_Attention_fc_surv.forward_group call per flush."""
+    other losses are called on the bag's slice.  reg_fn(model) is evaluated once per pass for the held bags (the weights
+    are fixed).  A multimodal model's patients (both fusions; _mm_bags_ok) are held the same way in _MMGroup -- a pathology
+    plane, the radio planes and the omic rows -- and run as one MM_MIL_Attention_fc_surv.forward_group call per flush."""
     device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
     model.eval()
-    losses, regs, all_risk, all_c, all_t = [], [], [], [], []
-    if group:
-        reg_once, meta, kind, limits = [], {}, _eval_group_head(model), {}
-        held = _MMEvalGroup() if kind == "mm" else _EvalGroup()
-        kernel_loss = type(loss_fn) is NLLSurvLoss
+    losses, all_risk = {}, {}            # by slot: a held bag's land after later bags were logged
+    regs, all_c, all_t, reg_once = [], [], [], []
 
-        def flush():      # the held bags' losses / risks land in their loader slots
-            for slot, hz_g, S_g, loss_g, _ in held.run(model, 0.0 if kernel_loss else None):
-                label_g, c_g, t_g = meta.pop(slot)
-                if isinstance(loss_fn, CoxSurvLoss):
-                    risk_g = hz_g
-                    loss_g = loss_fn(risks=risk_g, times=torch.as_tensor(np.asarray(t_g)), c=c_g)
-                else:
-                    risk_g = -torch.sum(S_g, dim=1)          # the per-bag branch's expression, on the bag's S
-                    if not kernel_loss:
-                        loss_g = loss_fn(hazards=hz_g, S=S_g, Y=label_g, c=c_g, alpha=0)
-                losses[slot] = loss_g
-                all_risk[slot] = risk_g.reshape(-1)
-    with torch.no_grad():
-        for batch in loader:
-            radio_features, path_features, genomic_features, label, event_time, c = batch
-            if _skip(mode, radio_features, path_features, genomic_features):
-                continue
-            took = _eval_hold(model, kind, held, limits, batch, len(losses), device, flush) if group and kind else None
-            if took is not None:
-                label, c = took
-                meta[len(losses)] = (label, c, event_time)
-                if not reg_once:         # the weights are fixed: one value (one device tensor) for the pass
-                    loss_reg = 0 if reg_fn is None else reg_fn(model) * lambda_reg
-                    reg_once.append(loss_reg if torch.is_tensor(loss_reg) else torch.tensor(float(loss_reg), device=device))
-                losses.append(None)
-                regs.append(reg_once[0])
-                all_risk.append(None)
-                all_c.append(c.reshape(-1))
-                all_t.append(np.asarray(event_time).reshape(-1))
-                continue
-            if group:
-                flush()                  # the bags held so far run first
-            feats, label, c = _to_device(radio_features, path_features, genomic_features, label, c, device)
-            hazards, S, Y_hat, _ = model(**feats)
-            if isinstance(loss_fn, CoxSurvLoss):
-                risk = hazards
-                loss = loss_fn(risks=risk, times=torch.as_tensor(np.asarray(event_time)), c=c)
-            else:
-                risk = -torch.sum(S, dim=1)
+    def land(slot, event_time, label, c, hazards, S, loss):     # the per-bag expressions, on the bag's slice when held
+        if isinstance(loss_fn, CoxSurvLoss):
+            risk = hazards
+            loss = loss_fn(risks=risk, times=torch.as_tensor(np.asarray(event_time)), c=c)
+        else:
+            risk = -torch.sum(S, dim=1)
+            if loss is None:
                 loss = loss_fn(hazards=hazards, S=S, Y=label, c=c, alpha=0)
-            loss_reg = 0 if reg_fn is None else reg_fn(model) * lambda_reg
-            losses.append(loss)
-            regs.append(loss_reg if torch.is_tensor(loss_reg) else torch.tensor(float(loss_reg), device=device))
-            all_risk.append(risk.reshape(-1))
+        losses[slot] = loss
+        all_risk[slot] = risk.reshape(-1)
+
+    with torch.no_grad():
+        for batch, label, c, was_held in _eval_pass(model, loader, mode, group, device, land,
+                                                    0.0 if type(loss_fn) is NLLSurvLoss else None):
+            if not (was_held and reg_once):
+                loss_reg = 0 if reg_fn is None else reg_fn(model) * lambda_reg
+                reg = loss_reg if torch.is_tensor(loss_reg) else torch.tensor(float(loss_reg), device=device)
+                if was_held:             # the weights are fixed: one value (one device tensor) for the pass's held bags
+                    reg_once.append(reg)
+            regs.append(reg_once[0] if was_held else reg)
             all_c.append(c.reshape(-1))
-            all_t.append(np.asarray(event_time).reshape(-1))
-        if group:
-            flush()
-    n = max(len(losses), 1)
-    loss_vals = torch.stack(losses).float().cpu().numpy()
+            all_t.append(np.asarray(batch[4]).reshape(-1))
+    n = max(len(regs), 1)
+    loss_vals = torch.stack([losses[s] for s in range(len(regs))]).float().cpu().numpy()
     reg_vals = torch.stack(regs).float().cpu().numpy()
     val_loss_surv = float(loss_vals.sum()) / n
     val_loss = float((loss_vals + reg_vals).sum()) / n
-    risks = torch.cat(all_risk).cpu().numpy()
+    risks = torch.cat([all_risk[s] for s in range(len(regs))]).cpu().numpy()
     cens = torch.cat(all_c).cpu().numpy()
     times = np.concatenate(all_t)
     c_index = concordance_index_censored((1 - cens).astype(bool), times, risks, tied_tol=1e-08)[0]
@@ -920,46 +799,28 @@ def summary_survival(model, loader, n_classes, mode, t_bin=None, loss_fn=None, g
     ds = getattr(loader, "dataset", None)
     if ds is not None and hasattr(ds, "slides_radio_data"):
         ids = list(ds.slides_radio_data["subject_id"])
-    all_ids, all_risk, all_c, all_t, all_y = [], [], [], [], []
-    count = 0
+    all_ids, all_risk, all_c, all_t, all_y = [], {}, [], [], []          # all_risk by slot
     head_risk = isinstance(loss_fn, (CoxSurvLoss, RankingSurvLoss))
-    if group:
-        kind, limits = _eval_group_head(model), {}
-        held = _MMEvalGroup() if kind == "mm" else _EvalGroup()
+    sid = []
 
-        def flush():      # the held bags' risks land in their subjects' slots (the per-bag expressions, on the bag's slice)
-            for slot, hz_g, S_g, _, _ in held.run(model):
-                all_risk[slot] = (hz_g if head_risk else -torch.sum(S_g, dim=1)).reshape(-1)
-    with torch.no_grad():
+    def counted():               # the ids go by loader position, skipped subjects included; `sid`: the current batch's
+        count = 0
         for batch in loader:
-            radio_features, path_features, genomic_features, label, event_time, c = batch
-            n = len(label)
-            sid = ids[count:count + n] if ids is not None else list(range(count, count + n))
+            n = len(batch[3])
+            sid[:] = ids[count:count + n] if ids is not None else range(count, count + n)
             count += n
-            if _skip(mode, radio_features, path_features, genomic_features):
-                continue
-            took = _eval_hold(model, kind, held, limits, batch, len(all_risk), device, flush) if group and kind else None
-            if took is not None:
-                label, c = took
-                all_ids.extend(sid)
-                all_risk.append(None)
-                all_c.append(c.reshape(-1))
-                all_t.append(np.asarray(event_time).reshape(-1))
-                all_y.append(label.reshape(-1))
-                continue
-            if group:
-                flush()                  # the bags held so far run first
-            feats, label, c = _to_device(radio_features, path_features, genomic_features, label, c, device)
-            hazards, S, Y_hat, _ = model(**feats)
-            risk = hazards if head_risk else -torch.sum(S, dim=1)
+            yield batch
+
+    def land(slot, event_time, label, c, hazards, S, loss):
+        all_risk[slot] = (hazards if head_risk else -torch.sum(S, dim=1)).reshape(-1)
+
+    with torch.no_grad():
+        for batch, label, c, _ in _eval_pass(model, counted(), mode, group, device, land):
             all_ids.extend(sid)
-            all_risk.append(risk.reshape(-1))
             all_c.append(c.reshape(-1))
-            all_t.append(np.asarray(event_time).reshape(-1))
+            all_t.append(np.asarray(batch[4]).reshape(-1))
             all_y.append(label.reshape(-1))
-        if group:
-            flush()
-    risks = torch.cat(all_risk).cpu().numpy()
+    risks = torch.cat([all_risk[s] for s in range(len(all_c))]).cpu().numpy()
     cens = torch.cat(all_c).cpu().numpy()
     labels = torch.cat(all_y).cpu().numpy()
     times = np.concatenate(all_t)

@@ -274,16 +274,20 @@ def test_one_call_step_is_taken_only_for_the_stock_head():
     x = torch.randn(4, 1024).as_subclass(FakeCuda)
     feats = {"path_features": x}
     stock = MIL_Attention_fc_surv_path(n_classes=4)
-    assert core_utils._fused_step_ok(stock, NLLSurvLoss(alpha=0.0), feats)
+
+    def _fused_step_ok(model, loss_fn, feats):       # the predicate: the loop's route for the bag is the one-call step
+        return core_utils._bag_route(model, loss_fn, {}, feats["path_features"], torch.zeros(1, 1)) == "step-path"
+
+    assert _fused_step_ok(stock, NLLSurvLoss(alpha=0.0), feats)
 
     class Tweaked(MIL_Attention_fc_surv_path):
         def forward(self, **kw):
             return super().forward(**kw)
 
-    assert not core_utils._fused_step_ok(Tweaked(n_classes=4), NLLSurvLoss(alpha=0.0), feats)
-    assert not core_utils._fused_step_ok(MIL_Attention_fc_surv_path(n_classes=40), NLLSurvLoss(alpha=0.0), feats)   # > 32 classes
-    assert not core_utils._fused_step_ok(stock, _stub_loss(), feats)                                                 # not the stock loss
+    assert not _fused_step_ok(Tweaked(n_classes=4), NLLSurvLoss(alpha=0.0), feats)
+    assert not _fused_step_ok(MIL_Attention_fc_surv_path(n_classes=40), NLLSurvLoss(alpha=0.0), feats)   # > 32 classes
+    assert not _fused_step_ok(stock, _stub_loss(), feats)                                                 # not the stock loss
     hooked = MIL_Attention_fc_surv_path(n_classes=4)
     hooked.classifier.register_forward_hook(lambda m, i, o: None)                                                    # a SUB-module hook
-    assert not core_utils._fused_step_ok(hooked, NLLSurvLoss(alpha=0.0), feats)
-    assert not core_utils._fused_step_ok(stock, NLLSurvLoss(alpha=0.0), {"path_features": x.to(torch.float64).as_subclass(FakeCuda)})
+    assert not _fused_step_ok(hooked, NLLSurvLoss(alpha=0.0), feats)
+    assert not _fused_step_ok(stock, NLLSurvLoss(alpha=0.0), {"path_features": x.to(torch.float64).as_subclass(FakeCuda)})

@@ -126,7 +126,7 @@ def test_training_loop_takes_the_one_launch_step(monkeypatch):
             orig = MaxNet.cox_step
             monkeypatch.setattr(MaxNet, "cox_step", lambda self, *a, **k: (calls.append(1), orig(self, *a, **k))[1])
         else:
-            monkeypatch.setattr(cu, "_fused_cox_ok", lambda *a: False)
+            monkeypatch.setattr(cu, "_bag_route", lambda *a: "autograd")
         cu.train_loop_survival(0, model, batches, opt, 4, "omic", loss_fn=CoxSurvLoss(), gc=1)
         monkeypatch.undo()
         assert bool(calls) == fused
