@@ -522,6 +522,11 @@ int mmf_cox_surv(const float* risks, const double* times, const float* c, int32_
  *   (models/model_mm_attention_mil.py:91,95).
  *   drop_kind: 0 none, 1 nn.Dropout, 2 nn.AlphaDropout; the mask is the keep-hash of (seed, site, element).
  *   seed_dev (everywhere below): optional device word added to `seed`, or NULL -- see mmf_amil_desc.
+ * mmf_dense_forward / _rows: y = drop(act(x W^T + bias)), x [B x K], W [N x K], bias [N] or NULL (no bias), y [B x N].  Any
+ *   B, K, N >= 1; no alignment requirement.  act in MMF_ACT_NONE..MMF_ACT_SELU, drop_kind in 0..2, 0 <= drop_p < 1,
+ *   non-null x, W, y (and row_base): MMF_ERR_ARG otherwise.  mmf_dense_forward draws the mask of element (b, n) at the
+ *   32-bit index b * N + n: with dropout on (drop_kind != 0, drop_p > 0) B * N >= 2^32 is MMF_ERR_SHAPE.  The _rows form
+ *   draws at row_base[b] + n and has no such limit; ldy < N there: MMF_ERR_SHAPE.  Every refusal returns before any launch.
  * ------------------------------------------------------------------------------------------- */
 int mmf_dense_forward(const float* x, const float* W, const float* bias, int32_t B, int32_t K, int32_t N,
                       int32_t act, int32_t drop_kind, float drop_p, uint32_t seed, uint32_t site,
@@ -548,10 +553,13 @@ int mmf_dense_backward_rows(const float* dy, int32_t lddy, const float* y, int32
                             int32_t B, int32_t K, int32_t N, int32_t act, int32_t drop_kind, float drop_p, uint32_t site,
                             const uint32_t* seed_dev, const uint32_t* row_base, float* dpre_scratch, float* dx, float* dW,
                             float* db, void* stream);
-/* o = sigmoid(z) * h (n elements) and its backward. */
+/* o = sigmoid(z) * h (n elements) and its backward (dz, dh from g, z, h).  Any n >= 1; n < 1 or a NULL pointer: MMF_ERR_ARG. */
 int mmf_gate_mul_forward(const float* z, const float* h, float* o, int32_t n, void* stream);
 int mmf_gate_mul_backward(const float* g, const float* z, const float* h, float* dz, float* dh, int32_t n, void* stream);
-/* out[b] = [o0,1] (x) [o1,1] ((x) [o2,1]) followed by Dropout(drop_p); o_t: [B x dim]; m = 2 or 3 (HOST array of ptrs). */
+/* out[b] = [o0,1] (x) [o1,1] ((x) [o2,1]) followed by Dropout(drop_p); o_t: [B x dim]; m = 2 or 3 (HOST array of ptrs).
+ * out and g: [B x S^m], S = dim + 1.  m outside {2, 3}, dim < 1, B < 1 or a NULL pointer (o_t, d_o[t] for t < m included):
+ * MMF_ERR_ARG.  An element is indexed, and its mask drawn, at the 32-bit b * S^m + e, and B is a grid dimension:
+ * B * S^m < 2^31 and B <= 65535, MMF_ERR_SHAPE otherwise -- both entry points, before any launch. */
 int mmf_kron_forward(const float* const* o, int32_t m, int32_t dim, int32_t B,
                      float drop_p, uint32_t seed, uint32_t site, const uint32_t* seed_dev, float* out, void* stream);
 int mmf_kron_backward(const float* g, const float* const* o, int32_t m, int32_t dim, int32_t B,
@@ -575,7 +583,14 @@ int mmf_kron_backward(const float* g, const float* const* o, int32_t m, int32_t 
  *   replaces models/model_genomic.py:53-72 (MaxNet.forward, bag_loss = cox_surv), models/model_modules.py:64-68 (SNN_Block:
  *   Linear + SELU + AlphaDropout), utils/loss_utils.py:124-139 (CoxSurvLoss) and the backward autograd derives from them --
  *   ~20 framework launches in the reference, 9 through the composable entry points above (mmf_dense_*, mmf_cox_surv).
- *   `small` net only (H0 = H1 = 256), B <= 256, G <= 256; other shapes: MMF_ERR_SHAPE (use the composable entry points).
+ *   `small` net only (H0 = H1 = 256), any 1 <= B <= 256 and any 1 <= G <= 256; other shapes: MMF_ERR_SHAPE (use the
+ *   composable entry points).  W1 and the workspace are read and written 16 bytes at a time and must be 16-byte aligned,
+ *   times 8-byte aligned: MMF_ERR_ALIGN otherwise.  Every other pointer is read or written one float at a time; W0 too may sit on any
+ *   4-byte boundary: with G <= 64, G % 4 == 0 and a
+ *   16-byte aligned W0 the first layer keeps each row of W0 in registers (16-byte loads); any other G or a W0 off a 16-byte
+ *   boundary takes the chunked route through LDS -- the same sums in another order.  A batch with every sample censored
+ *   gives loss 0 and every gradient 0.  p_drop outside [0, 1), sync_words < 3 or a NULL pointer: MMF_ERR_ARG; a workspace
+ *   smaller than mmf_maxnet_cox_step_workspace_bytes(B): MMF_ERR_WORKSPACE; all before any launch.
  *   times: DEVICE float64 [B] (the reference compares event times in float64); loss: unscaled; gradients are those of
  *   loss * loss_scale, written or (accumulate) added.  Needs 3 tick words (mmf_amil_desc::sync's contract).
  * ------------------------------------------------------------------------------------------- */
@@ -609,7 +624,12 @@ int mmf_abs_sum(const float* w, int64_t n, float* partials, float* out, void* st
  * single-workgroup launch:  h_i = relu(Wh_i v_i + bh_i); z_i = Wz_i [v_0|..|v_{m-1}] + bz_i;
  * gm_i = sigmoid(z_i) * h_i;  o_i = Dropout(relu(Wo_i gm_i + bo_i))  (dropout site i of `seed`).
  * forward writes h, z, gm, o ([B x sdim] each); backward reads them plus d_o and writes dv (incl. the v_cat path) and
- * every weight gradient.  All arrays are indexed by modality; entries >= m are ignored.  B * m * sdim <= 384. */
+ * every weight gradient.  All arrays are indexed by modality; entries >= m are ignored.  B * m * sdim <= 384
+ * (MMF_ERR_SHAPE above: the stage's values live in LDS); m outside 1..3, B, dim or sdim < 1, drop_p outside [0, 1) or a
+ * NULL member of a modality < m (h, z, gm, o in both directions; d_o, dv and the weight gradients in the backward):
+ * MMF_ERR_ARG.  The forward reads v_i, Wh_i and Wz_i with 16-byte loads: dim % 4 == 0 (MMF_ERR_SHAPE otherwise) and
+ * 16-byte aligned v_i, Wh_i, Wz_i (MMF_ERR_ALIGN otherwise).  The backward reads one float at a time and takes any dim
+ * and any 4-byte aligned pointer.  Every refusal returns before any launch. */
 typedef struct mmf_xreduce_io {
   int32_t m, B, dim, sdim;
   const float* v[3];

@@ -1795,6 +1795,8 @@ int mmf_maxnet_cox_step(const mmf_maxnet_desc* d, const double* times, const flo
   if (!d->sync || d->sync_words < 3) return MMF_ERR_ARG;          // the two grid barriers live in the caller's tick words
   if (d->p_drop < 0.f || d->p_drop >= 1.f) return MMF_ERR_ARG;
   if (workspace_bytes < mmf_maxnet_cox_step_workspace_bytes(d->B)) return MMF_ERR_WORKSPACE;
+  // layer 1 and phase 3 read W1 with 16-byte loads, dpre1 / dpre0 leave as 16-byte stores into the workspace; times is double
+  if (!aligned16(d->W1) || !aligned16(workspace) || (reinterpret_cast<uintptr_t>(times) & 7) != 0) return MMF_ERR_ALIGN;
   MaxnetStepParams p{};
   p.B = d->B; p.G = d->G;
   p.x = d->x; p.W0 = d->W0; p.b0 = d->b0; p.W1 = d->W1; p.b1 = d->b1; p.Wc = d->Wc; p.bc = d->bc;
@@ -1850,6 +1852,8 @@ int mmf_dense_forward(const float* x, const float* W, const float* bias, int32_t
                       const uint32_t* seed_dev, float* y, void* stream) {
   if (!x || !W || !y || B < 1 || K < 1 || N < 1) return MMF_ERR_ARG;
   if (act < 0 || act > ACT_SELU || drop_kind < 0 || drop_kind > 2 || drop_p < 0.f || drop_p >= 1.f) return MMF_ERR_ARG;
+  // the mask of element (b, n) is drawn at the 32-bit index b * N + n: beyond 2^32 elements indices would repeat
+  if (drop_kind != 0 && drop_p > 0.f && (int64_t)B * N >= ((int64_t)1 << 32)) return MMF_ERR_SHAPE;
   DenseParams p{x, W, bias, y, B, K, N, act, make_drop(drop_kind, drop_p, seed, site, seed_dev)};
   return launch_dense_fwd(p, static_cast<hipStream_t>(stream));
 }
@@ -1897,11 +1901,21 @@ int mmf_gate_mul_backward(const float* g, const float* z, const float* h, float*
   return launch_gate_mul_bwd(g, z, h, dz, dh, n, static_cast<hipStream_t>(stream));
 }
 
+// The kron kernels index an element as b * S^m + e in int (S = dim + 1), hash that index into the 32-bit mask counter, and
+// put B in grid.y: B * S^m < 2^31 and B <= 65535, or the call is refused before any launch.
+static bool kron_shape_ok(int m, int dim, int B) {
+  const int64_t S = (int64_t)dim + 1;
+  if (B > 65535 || S > 46340) return false;                // 46341^2 > 2^31 already; below it S^3 fits int64
+  const int64_t total = m == 3 ? S * S * S : S * S;
+  return (int64_t)B * total < ((int64_t)1 << 31);
+}
+
 int mmf_kron_forward(const float* const* o, int32_t m, int32_t dim, int32_t B,
                      float drop_p, uint32_t seed, uint32_t site, const uint32_t* seed_dev, float* out, void* stream) {
   if (!o || (m != 2 && m != 3) || dim < 1 || B < 1 || !out) return MMF_ERR_ARG;
   KronParams p{};
   for (int i = 0; i < m; ++i) { if (!o[i]) return MMF_ERR_ARG; p.o[i] = o[i]; }
+  if (!kron_shape_ok(m, dim, B)) return MMF_ERR_SHAPE;
   p.out = out; p.m = m; p.dim = dim; p.B = B; p.drop = make_drop(1, drop_p, seed, site, seed_dev);
   return launch_kron_fwd(p, static_cast<hipStream_t>(stream));
 }
@@ -1911,6 +1925,7 @@ int mmf_kron_backward(const float* g, const float* const* o, int32_t m, int32_t 
   if (!g || !o || !d_o || (m != 2 && m != 3) || dim < 1 || B < 1) return MMF_ERR_ARG;
   KronParams p{};
   for (int i = 0; i < m; ++i) { if (!o[i] || !d_o[i]) return MMF_ERR_ARG; p.o[i] = o[i]; p.d[i] = d_o[i]; }
+  if (!kron_shape_ok(m, dim, B)) return MMF_ERR_SHAPE;
   p.g = g; p.m = m; p.dim = dim; p.B = B; p.drop = make_drop(1, drop_p, seed, site, seed_dev);
   return launch_kron_bwd(p, static_cast<hipStream_t>(stream));
 }
@@ -1941,6 +1956,8 @@ static int xreduce_params(const mmf_xreduce_io* io, float drop_p, uint32_t seed,
 int mmf_xreduce_forward(const mmf_xreduce_io* io, float drop_p, uint32_t seed, const uint32_t* seed_dev, void* stream) {
   XReduceParams p;
   if (int e = xreduce_params(io, drop_p, seed, seed_dev, false, p)) return e;
+  for (int i = 0; i < p.m; ++i)       // wave_dot's 16-byte loads (the backward reads scalars and needs neither this nor dim % 4)
+    if (!aligned16(p.v[i]) || !aligned16(p.Wh[i]) || !aligned16(p.Wz[i])) return MMF_ERR_ALIGN;
   return launch_xreduce_fwd(p, static_cast<hipStream_t>(stream));
 }
 int mmf_xreduce_backward(const mmf_xreduce_io* io, float drop_p, uint32_t seed, const uint32_t* seed_dev, void* stream) {

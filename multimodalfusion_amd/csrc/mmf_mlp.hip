@@ -337,14 +337,19 @@ __global__ __launch_bounds__(XR_NT) void xreduce_bwd_kernel(XReduceParams p) {
   }
 }
 
+// m * B * sdim > XR_MAX without wrapping: B * sdim fits int64 for any int32 pair, and m <= 3 multiplies a value <= XR_MAX
+static bool xreduce_over_cap(const XReduceParams& p) {
+  const int64_t per = (int64_t)p.B * p.sdim;
+  return per > XR_MAX || p.m * per > XR_MAX;
+}
 int launch_xreduce_fwd(XReduceParams p, hipStream_t st) {
-  if (p.m * p.B * p.sdim > XR_MAX || p.m < 1 || p.m > 3) return MMF_ERR_SHAPE;
+  if (p.m < 1 || p.m > 3 || xreduce_over_cap(p)) return MMF_ERR_SHAPE;
   if (p.dim % 4 != 0) return MMF_ERR_SHAPE;
   { ProfScope ps("xreduce_fwd_kernel", st); hipLaunchKernelGGL(xreduce_fwd_kernel, dim3(1), dim3(XR_NT), 0, st, p); }
   return hipGetLastError() == hipSuccess ? MMF_OK : MMF_ERR_LAUNCH;
 }
 int launch_xreduce_bwd(XReduceParams p, hipStream_t st) {
-  if (p.m * p.B * p.sdim > XR_MAX || p.m < 1 || p.m > 3) return MMF_ERR_SHAPE;
+  if (p.m < 1 || p.m > 3 || xreduce_over_cap(p)) return MMF_ERR_SHAPE;
   { ProfScope ps("xreduce_bwd_kernel", st); hipLaunchKernelGGL(xreduce_bwd_kernel, dim3(1), dim3(XR_NT), 0, st, p); }
   return hipGetLastError() == hipSuccess ? MMF_OK : MMF_ERR_LAUNCH;
 }

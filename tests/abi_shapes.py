@@ -31,6 +31,10 @@ survival head, nll_surv, Cox, the ranking loss, the hazard head, the highway mix
 the dense backward -- has one table per entry point below XFUSION, run by tests/test_gpu_small_shapes.py on the inputs and
 float64 references of tests/small_cases.py.  Their classes: a size against the 256-thread stride (1, stride - 1, stride,
 stride + 1, three strides or more), the caps from both sides, every combination of optional pointers the header allows.
+
+The entry points that were reached only through the models -- the dense forward and its _rows form, gate_mul, the Kronecker
+product, the fused gating stage (xreduce) and the omic head's one-launch step -- follow below DENSE_BWD, run by
+tests/test_gpu_tail_shapes.py on the inputs, references and bars of tests/small_cases.py.
 """
 from __future__ import annotations
 
@@ -1059,6 +1063,371 @@ REQUIRED_DENSE_BWD = (
     | {("refused", ERR_ARG, "act=5 drop_kind=0 rows=0"), ("refused", ERR_ARG, "act=0 drop_kind=3 rows=0"),
        ("refused", ERR_SHAPE, "act=0 drop_kind=0 rows=-1")})
 
+# ---- the omic step, the dense forward and the fusion ops (tests/test_gpu_tail_shapes.py) -----------------------------------
+# Classes are named after each kernel's own work unit: the 64 lanes and the 4 x 64 unrolled round of dense_fwd_kernel's K
+# loop and the 4 waves of its blocks, the 256-thread blocks of gate_mul and kron_fwd, the 64 lanes kron_bwd strides over the
+# "other" indices with, wave_dot's 256-float round and the 16 waves / 1024 threads of the xreduce pair, and for the omic
+# step the first layer's three routes, the 4 rows a workgroup owns, the Cox loop tiers and the 64-thread risk-set stride.
+DENSE_FWD_GRID = 65535 * 16                              # csrc/mmf_mlp.hip launch_dense_fwd: blocks of 4 waves, one output each
+KRON_MAX_B = 65535                                       # csrc/mmf_api.hip kron_shape_ok: B is grid.y
+XR_MAX = 384                                             # csrc/mmf_mlp.hip:202: m * B * sdim values of the gating stage in LDS
+
+
+# mmf_dense_forward / mmf_dense_forward_rows
+@dataclass(frozen=True)
+class DenseFwd:
+    B: int
+    K: int
+    N: int
+    act: int = 0
+    drop_kind: int = 0           # 0 none, 1 nn.Dropout, 2 nn.AlphaDropout
+    bias: bool = True
+    rows: int = 0                # 0: mmf_dense_forward; 1: the _rows form with ldy = N; > 1: ldy = N + rows; -1: ldy = N - 1
+    drop_p: float = 0.25         # used where drop_kind != 0 (and checked by the library whatever drop_kind is)
+    base: bool = True            # False: the _rows form with row_base = NULL
+    why: str = ""
+
+
+def dense_fwd_rule(c):
+    """include/mmf_amil.h mmf_dense_forward / _rows; csrc/mmf_api.hip -- in the library's order."""
+    if c.B < 1 or c.K < 1 or c.N < 1 or (c.rows and not c.base):
+        return ERR_ARG
+    if not 0 <= c.act <= 4 or not 0 <= c.drop_kind <= 2 or not 0.0 <= c.drop_p < 1.0:
+        return ERR_ARG
+    if not c.rows and c.drop_kind and c.drop_p > 0 and c.B * c.N >= 2**32:
+        return ERR_SHAPE                                  # the plain form's 32-bit mask index b * N + n would repeat
+    return ERR_SHAPE if c.rows < 0 else OK
+
+
+def dense_fwd_tags(c):
+    if dense_fwd_rule(c) != OK:
+        return {("refused", dense_fwd_rule(c), f"B={c.B} K={c.K} N={c.N} act={c.act} drop_kind={c.drop_kind} drop_p={c.drop_p} rows={c.rows} base={c.base}")}
+    t = {("act", c.act), ("drop_kind", c.drop_kind)}
+    if c.K in (1, 63, 64, 65, 255, 256, 257, 513):
+        t.add(("K against the 64-lane tail and the 4 x 64 round", c.K))
+    if c.N == 1:
+        t.add(("N", "1"))
+    if c.N % 4:
+        t.add(("N", "not a multiple of 4"))
+    if c.B * c.N in (1, 3, 4, 5):
+        t.add(("B*N against the 4 waves of a block", c.B * c.N))
+    if c.B * c.N > 4 * DENSE_FWD_GRID:
+        t.add(("grid", "the grid-stride loop wraps"))
+    if not c.bias:
+        t.add(("bias", "NULL"))
+    if c.rows:
+        t.add(("_rows", "ldy = N" if c.rows == 1 else "ldy > N"))
+    return t
+
+
+DENSE_FWD = [
+    DenseFwd(1, 1, 1, why="K = 1: lane 0 alone, once; N = 1; B*N = 1: three waves idle"),
+    DenseFwd(1, 63, 3, act=1, why="K = 63: the last lane idle; B*N = 3: the fourth wave idle"),
+    DenseFwd(2, 64, 2, act=2, why="K = 64: every lane one tail step; B*N = 4: one output per wave; tanh"),
+    DenseFwd(1, 65, 5, act=3, why="K = 65: a second tail step of lane 0; B*N = 5: a second block of one wave; sigmoid"),
+    DenseFwd(3, 255, 6, act=4, drop_kind=2, why="K = 255: lane 63 takes three tail steps, the others the unrolled round; SELU + AlphaDropout"),
+    DenseFwd(3, 256, 8, act=1, drop_kind=1, why="K = 256: one unrolled round, no tail; ReLU + Dropout"),
+    DenseFwd(2, 257, 7, bias=False, why="K = 257: an unrolled round and a tail step of lane 0; no bias"),
+    DenseFwd(3, 513, 10, act=4, drop_kind=2, rows=1, why="K = 513: two unrolled rounds and a tail step; _rows with ldy = N"),
+    DenseFwd(5, 36, 9, act=1, drop_kind=1, rows=5, why="_rows with ldy = N + 5, every row its own seed"),
+    DenseFwd(2049, 1, 2048, act=1, drop_kind=1, why="4,196,352 outputs against 4,194,240 waves: the grid-stride loop wraps"),
+    # refused
+    DenseFwd(2, 8, 8, drop_kind=1, drop_p=1.0, why="refused: drop_p = 1"),
+    DenseFwd(2, 8, 8, act=5, why="refused: unknown activation"),
+    DenseFwd(2, 8, 8, drop_kind=3, why="refused: unknown dropout kind"),
+    DenseFwd(2, 8, 8, rows=-1, why="refused: _rows with ldy < N"),
+    DenseFwd(2, 8, 8, rows=1, base=False, why="refused: _rows with row_base = NULL"),
+    DenseFwd(0, 8, 8, why="refused: B = 0"),
+    DenseFwd(2, 0, 8, why="refused: K = 0"),
+    DenseFwd(2, 8, 0, why="refused: N = 0"),
+]
+REQUIRED_DENSE_FWD = (
+    {("K against the 64-lane tail and the 4 x 64 round", k) for k in (1, 63, 64, 65, 255, 256, 257, 513)}
+    | {("N", "1"), ("N", "not a multiple of 4"), ("grid", "the grid-stride loop wraps"), ("bias", "NULL")}
+    | {("B*N against the 4 waves of a block", v) for v in (1, 3, 4, 5)} | {("act", a) for a in range(5)}
+    | {("drop_kind", d) for d in range(3)} | {("_rows", "ldy = N"), ("_rows", "ldy > N")}
+    | {t for c in DENSE_FWD if dense_fwd_rule(c) != OK for t in dense_fwd_tags(c)})
+
+
+# mmf_gate_mul_forward / _backward
+@dataclass(frozen=True)
+class GateMul:
+    n: int
+    why: str = ""
+
+
+def gate_mul_rule(c):
+    """include/mmf_amil.h mmf_gate_mul_*; csrc/mmf_api.hip: any n >= 1."""
+    return ERR_ARG if c.n < 1 else OK
+
+
+def gate_mul_tags(c):
+    return {("refused", ERR_ARG, f"n={c.n}")} if c.n < 1 else {("n against the 256-thread block", c.n)}
+
+
+GATE_MUL = [GateMul(1, why="one element"), GateMul(255, why="the last thread idle"), GateMul(256, why="one full block"),
+            GateMul(257, why="a second block of one thread"), GateMul(1000, why="four blocks, the last ragged"),
+            GateMul(0, why="refused: n = 0")]
+REQUIRED_GATE_MUL = {("n against the 256-thread block", n) for n in (1, 255, 256, 257, 1000)} | {("refused", ERR_ARG, "n=0")}
+
+
+# mmf_kron_forward / _backward
+@dataclass(frozen=True)
+class Kron:
+    m: int
+    dim: int
+    B: int = 1
+    drop_p: float = 0.0
+    null: bool = False           # o[m - 1] = NULL
+    why: str = ""
+
+
+def kron_rule(c):
+    """include/mmf_amil.h mmf_kron_*; csrc/mmf_api.hip mmf_kron_forward / _backward, kron_shape_ok -- in the library's order."""
+    if c.m not in (2, 3) or c.dim < 1 or c.B < 1 or c.null:
+        return ERR_ARG
+    if c.B > KRON_MAX_B or c.B * (c.dim + 1) ** c.m >= 2**31:
+        return ERR_SHAPE
+    return OK
+
+
+def kron_tags(c):
+    if kron_rule(c) != OK:
+        return {("refused", kron_rule(c), f"m={c.m} dim={c.dim} B={c.B} null={c.null}")}
+    S = c.dim + 1
+    t = {("B", c.B), ("dropout", c.drop_p > 0)}
+    if (c.m, c.dim) in ((2, 1), (2, 15), (2, 16), (3, 5), (3, 6), (3, 16)):
+        t.add(("S^m against the forward's 256-thread blocks", (c.m, S ** c.m)))
+    if (c.m, c.dim) in ((2, 63), (2, 64), (3, 7), (3, 8)):
+        t.add(("the backward's others against its 64 lanes", (c.m, S ** (c.m - 1))))
+    if c.m == 3:
+        t |= {("m = 3 backward, operand role", r) for r in range(3)}
+    return t
+
+
+KRON = [
+    Kron(2, 1, why="S^2 = 4: four threads of one block"),
+    Kron(2, 15, B=3, drop_p=0.25, why="S^2 = 256: one block exactly; three samples"),
+    Kron(2, 16, why="S^2 = 289: a second block of 33 threads"),
+    Kron(3, 5, B=3, why="S^3 = 216: the last 40 threads idle"),
+    Kron(3, 6, drop_p=0.25, why="S^3 = 343: a second block of 87 threads"),
+    Kron(3, 16, B=3, drop_p=0.25, why="S^3 = 4913, the shipped size: twenty blocks, the last ragged"),
+    Kron(2, 63, drop_p=0.25, why="backward: 64 others, every lane once"),
+    Kron(2, 64, B=3, why="backward: 65 others, a second step of lane 0"),
+    Kron(3, 7, B=3, drop_p=0.25, why="backward: 8 x 8 = 64 others, every lane once"),
+    Kron(3, 8, why="backward: 9 x 9 = 81 others, a ragged second step"),
+    # refused
+    Kron(1, 4, why="refused: m = 1"),
+    Kron(4, 4, why="refused: m = 4"),
+    Kron(2, 0, why="refused: dim = 0"),
+    Kron(3, 4, null=True, why="refused: a NULL operand"),
+    Kron(3, 1290, why="refused: S^3 = 1291^3 >= 2^31"),
+    Kron(2, 46340, why="refused: S^2 = 46341^2 >= 2^31"),
+    Kron(2, 255, B=32768, why="refused: B * S^2 = 2^31"),
+    Kron(2, 1, B=65536, why="refused: B above grid.y"),
+]
+KRON_CAPS = {(3, 1290, 1), (2, 46340, 1), (2, 255, 32768), (2, 1, 65536)}      # refused by the caps: never given real buffers
+REQUIRED_KRON = (
+    {("S^m against the forward's 256-thread blocks", v) for v in ((2, 4), (2, 256), (2, 289), (3, 216), (3, 343), (3, 4913))}
+    | {("the backward's others against its 64 lanes", v) for v in ((2, 64), (2, 65), (3, 64), (3, 81))}
+    | {("B", 1), ("B", 3), ("dropout", True), ("dropout", False)} | {("m = 3 backward, operand role", r) for r in range(3)}
+    | {t for c in KRON if kron_rule(c) != OK for t in kron_tags(c)})
+
+
+# mmf_xreduce_forward / _backward
+@dataclass(frozen=True)
+class XReduce:
+    m: int
+    B: int
+    dim: int
+    sdim: int
+    drop_p: float = 0.0
+    misalign: bool = False       # v[0] 4 bytes off a 16-byte boundary
+    null: str = ""               # that member of modality m - 1 is NULL
+    why: str = ""
+
+
+def _xreduce_args(c):
+    if not 1 <= c.m <= 3 or c.B < 1 or c.dim < 1 or c.sdim < 1 or not 0.0 <= c.drop_p < 1.0 or c.null:
+        return ERR_ARG
+    return OK
+
+
+def xreduce_fwd_rule(c):
+    """include/mmf_amil.h mmf_xreduce_io; csrc/mmf_api.hip xreduce_params, mmf_xreduce_forward (alignment), csrc/mmf_mlp.hip
+    launch_xreduce_fwd -- in the library's order."""
+    if _xreduce_args(c) != OK:
+        return ERR_ARG
+    if c.misalign:
+        return ERR_ALIGN
+    return ERR_SHAPE if c.m * c.B * c.sdim > XR_MAX or c.dim % 4 else OK
+
+
+def xreduce_bwd_rule(c):
+    """The backward reads one float at a time: no dim % 4, no alignment (csrc/mmf_mlp.hip launch_xreduce_bwd)."""
+    if _xreduce_args(c) != OK:
+        return ERR_ARG
+    return ERR_SHAPE if c.m * c.B * c.sdim > XR_MAX else OK
+
+
+def xreduce_tags(c):
+    fw, bw = xreduce_fwd_rule(c), xreduce_bwd_rule(c)
+    what = f"m={c.m} B={c.B} dim={c.dim} sdim={c.sdim} drop_p={c.drop_p} misalign={c.misalign} null={c.null}"
+    if bw != OK:
+        return {("refused", fw, bw, what)}
+    if fw != OK:
+        return {("forward refused, backward admitted", fw, what)}
+    t = {("B", c.B), ("dropout", c.drop_p > 0)}
+    if c.dim in (4, 252, 256, 260, 1024, 1028):
+        t.add(("dim against wave_dot's 256-float round", c.dim))
+    if 2 * c.m * c.B * c.sdim in (2, 64, 96, 768):
+        t.add(("h and z values against a sweep of 64", 2 * c.m * c.B * c.sdim))
+    if c.sdim in (15, 16, 17):
+        t.add(("sdim against the unroll of 16", c.sdim))
+    if c.m * c.sdim * c.sdim in (1024, 1089) or c.m * c.sdim * c.sdim > 100 * 1024:
+        t.add(("dWo elements against 1024 threads", min(c.m * c.sdim * c.sdim, 100 * 1024 + 1)))
+    if c.m == 3 and c.drop_p > 0:
+        t.add(("dropout", "three sites"))
+    return t
+
+
+XREDUCE = [
+    XReduce(1, 1, 4, 1, why="two values: 14 waves idle; dim = 4: lane 0 alone"),
+    XReduce(2, 1, 252, 16, why="64 values: one sweep exactly; dim = 252: the last lane idle"),
+    XReduce(3, 1, 256, 16, drop_p=0.25, why="the shipped size: 96 values, dim = 256 one full round; three dropout sites"),
+    XReduce(3, 8, 260, 16, drop_p=0.25, why="768 values on the cap m*B*sdim = 384; dim = 260: a second round of lane 0; B = 8"),
+    XReduce(1, 2, 1024, 15, why="dim = 1024: the four unrolled rounds; sdim = 15; B = 2"),
+    XReduce(1, 1, 1028, 17, why="dim = 1028: a fifth round of lane 0; sdim = 17: one step past the unroll"),
+    XReduce(1, 1, 4, 32, why="dWo: 1024 elements, one per thread"),
+    XReduce(1, 1, 4, 33, why="dWo: 1089 elements, a second step of 65 threads"),
+    XReduce(1, 1, 4, 384, why="sdim = 384, the cap alone: dWo takes 144 strides"),
+    XReduce(2, 1, 6, 3, why="dim = 6: the forward refuses (16-byte loads), the backward runs"),
+    XReduce(2, 1, 8, 3, misalign=True, why="v[0] 4 bytes off: the forward refuses, the backward runs"),
+    # refused by both
+    XReduce(3, 8, 4, 17, why="refused: m*B*sdim = 408"),
+    XReduce(1, 1, 4, 385, why="refused: sdim = 385"),
+    XReduce(0, 1, 4, 4, why="refused: m = 0"),
+    XReduce(4, 1, 4, 4, why="refused: m = 4"),
+    XReduce(2, 1, 4, 4, null="Wz", why="refused: Wz of the last modality NULL"),
+    XReduce(2, 1, 4, 4, null="gm", why="refused: gm of the last modality NULL"),
+    XReduce(2, 1, 4, 4, drop_p=1.0, why="refused: drop_p = 1"),
+]
+REQUIRED_XREDUCE = (
+    {("dim against wave_dot's 256-float round", d) for d in (4, 252, 256, 260, 1024, 1028)}
+    | {("h and z values against a sweep of 64", v) for v in (2, 64, 96, 768)} | {("sdim against the unroll of 16", v) for v in (15, 16, 17)}
+    | {("dWo elements against 1024 threads", v) for v in (1024, 1089, 100 * 1024 + 1)} | {("B", b) for b in (1, 2, 8)}
+    | {("dropout", False), ("dropout", True), ("dropout", "three sites")}
+    | {t for c in XREDUCE if xreduce_fwd_rule(c) != OK for t in xreduce_tags(c)})
+
+
+# mmf_maxnet_cox_step
+MX_H, MX_R = 256, 4                                      # csrc/mmf_maxnet.hip:31-32: hidden width, rows a workgroup owns
+MX_PTRS = ("x", "W0", "b0", "W1", "b1", "Wc", "bc", "sync", "times", "c", "workspace", "risk", "loss",
+           "dW0", "db0", "dW1", "db1", "dWc", "dbc")
+
+
+@dataclass(frozen=True)
+class MaxStep:
+    B: int
+    G: int
+    p_drop: float = 0.0
+    censor: str = "mixed"        # "mixed" (distinct times, 30 % censored), "none", "all", "tied", "last event" (the only event has the largest time)
+    misalign: bool = False       # W0 4 bytes off a 16-byte boundary
+    word: int = 0                # non-zero: seed_dev points at this device word, the masks are those of seed + word
+    accumulate: int = 0          # 1: the gradients are added onto known values
+    loss_scale: float = 1.0
+    H0: int = MX_H
+    sync_words: int = 3
+    ws_short: bool = False       # the workspace one byte short of the query
+    null: str = ""               # that pointer NULL (MX_PTRS)
+    off: str = ""                # that pointer ("W1", "workspace", "times") 4 bytes off its required alignment
+    why: str = ""
+
+
+def maxstep_workgroups(B):
+    return 64 if B > MX_R * 32 else 32                   # csrc/mmf_maxnet.hip maxnet_step_workgroups
+
+
+def maxstep_workspace_bytes(B):
+    """csrc/mmf_maxnet.hip maxnet_step_workspace_floats: y0, y1 [B x 256]; dpre1, dpre0 [256 x 4 workgroups]; dr; the dWc shares."""
+    B = max(B, 1)
+    return 4 * (2 * B * MX_H + 2 * MX_H * maxstep_workgroups(B) * MX_R + (B + 63) // 64 * 64 + 64 * MX_H)
+
+
+def maxstep_rule(c):
+    """include/mmf_amil.h mmf_maxnet_cox_step; csrc/mmf_api.hip mmf_maxnet_cox_step -- in the library's order."""
+    if c.null and c.null != "sync":
+        return ERR_ARG
+    if not (1 <= c.B <= 256 and 1 <= c.G <= 256 and c.H0 == MX_H):
+        return ERR_SHAPE
+    if c.null == "sync" or c.sync_words < 3 or not 0.0 <= c.p_drop < 1.0:
+        return ERR_ARG
+    if c.ws_short:
+        return ERR_WORKSPACE
+    return ERR_ALIGN if c.off else OK                     # W1, workspace: 16-byte loads and stores; times: double
+
+
+def maxstep_route(c):
+    """Layer 0 of maxnet_cox_step_kernel (csrc/mmf_maxnet.hip:284)."""
+    if c.G <= 64 and c.G % 4 == 0:
+        return "narrow shape, W0 misaligned: chunked" if c.misalign else "narrow"
+    return "chunked"
+
+
+def maxstep_tags(c):
+    if maxstep_rule(c) != OK:
+        return {("refused", maxstep_rule(c), f"B={c.B} G={c.G} H0={c.H0} sync_words={c.sync_words} p_drop={c.p_drop} ws_short={c.ws_short} null={c.null} off={c.off}")}
+    t = {("layer 0", (maxstep_route(c), c.G)), ("p_drop", c.p_drop), ("seed_dev", "a word" if c.word else "NULL"), ("accumulate", c.accumulate),
+         ("loss_scale", "1" if c.loss_scale == 1.0 else "not 1")}
+    if c.B in (1, 3, 4, 5, 127, 128, 129, 255, 256):
+        t.add(("rows against 4 a workgroup and 32 / 64 workgroups", c.B))
+    if c.B in (15, 16, 17, 19):
+        t.add(("Cox loop tiers", c.B))
+    if c.B in (63, 64, 65):
+        t.add(("risk-set gradient, 64-thread stride", c.B))
+    if c.censor != "mixed":
+        t.add(("censoring", c.censor))
+    return t
+
+
+MAXSTEP = [
+    MaxStep(1, 4, censor="none", why="B = 1, an event whose risk set is itself: 31 workgroups own no row; G = 4: the narrow route's partial group alone"),
+    MaxStep(3, 16, p_drop=0.25, why="B = 3: one workgroup, its fourth row beyond the batch; G = 16: one full group of the narrow route"),
+    MaxStep(4, 36, p_drop=0.25, why="B = 4: one workgroup's rows exactly; G = 36: the shipped narrow shape, two full groups and a partial"),
+    MaxStep(5, 36, p_drop=0.25, misalign=True, why="B = 5: a second workgroup with one row; G = 36 with W0 4 bytes off: the chunked route"),
+    MaxStep(127, 60, loss_scale=0.5, why="B = 127: the last row of 32 workgroups missing; G = 60: three full groups and three quarters; loss_scale 0.5"),
+    MaxStep(128, 1, p_drop=0.25, why="B = 128: 32 workgroups full; G = 1: one column of the chunked route"),
+    MaxStep(129, 65, p_drop=0.25, word=77, why="B = 129: the 64-workgroup kernel; G = 65: a second chunk of one column; seed_dev"),
+    MaxStep(255, 193, p_drop=0.25, accumulate=1, why="B = 255; G = 193: a fourth chunk, the refetch of staging buffer 1; accumulate"),
+    MaxStep(256, 256, p_drop=0.25, why="the cap on both: 64 workgroups full, four full chunks"),
+    MaxStep(15, 64, p_drop=0.25, censor="all", why="B = 15: the Cox 4-member tier and the scalar tail only; G = 64: four full groups; all censored"),
+    MaxStep(16, 63, censor="tied", why="B = 16: one pass of the 16-member tier; G = 63: one ragged chunk; tied times"),
+    MaxStep(17, 128, censor="last event", why="B = 17: 16-member tier and one tail step; G = 128: one round, both staging buffers; one event at the largest time"),
+    MaxStep(19, 129, censor="none", why="B = 19: 16-member tier and three tail steps; G = 129: a second round, the refetch of buffer 0; none censored"),
+    MaxStep(63, 80, why="B = 63: the last thread of a risk-set row idle"),
+    MaxStep(64, 186, p_drop=0.25, why="B = 64: every thread of a risk-set row one member"),
+    MaxStep(65, 36, why="B = 65: a second member for thread 0"),
+    # refused
+    MaxStep(0, 36, why="refused: B = 0"),
+    MaxStep(257, 36, why="refused: B = 257"),
+    MaxStep(8, 0, why="refused: G = 0"),
+    MaxStep(8, 257, why="refused: G = 257"),
+    MaxStep(8, 36, H0=128, why="refused: H0 = 128"),
+    MaxStep(8, 36, sync_words=2, why="refused: two tick words"),
+    MaxStep(8, 36, p_drop=1.0, why="refused: p_drop = 1"),
+    MaxStep(8, 36, ws_short=True, why="refused: the workspace one byte short"),
+] + [MaxStep(8, 36, null=n, why=f"refused: {n} = NULL") for n in MX_PTRS] + [
+    MaxStep(8, 36, off=n, why=f"refused: {n} 4 bytes off") for n in ("W1", "workspace", "times")]
+REQUIRED_MAXSTEP = (
+    {("layer 0", ("narrow", g)) for g in (4, 16, 36, 60, 64)} | {("layer 0", ("narrow shape, W0 misaligned: chunked", 36))}
+    | {("layer 0", ("chunked", g)) for g in (1, 63, 65, 128, 129, 193, 256)}
+    | {("rows against 4 a workgroup and 32 / 64 workgroups", b) for b in (1, 3, 4, 5, 127, 128, 129, 255, 256)}
+    | {("Cox loop tiers", b) for b in (15, 16, 17, 19)} | {("risk-set gradient, 64-thread stride", b) for b in (63, 64, 65)}
+    | {("censoring", k) for k in ("none", "all", "tied", "last event")} | {("p_drop", 0.0), ("p_drop", 0.25)}
+    | {("seed_dev", "NULL"), ("seed_dev", "a word"), ("accumulate", 0), ("accumulate", 1), ("loss_scale", "1"), ("loss_scale", "not 1")}
+    | {t for c in MAXSTEP if maxstep_rule(c) != OK for t in maxstep_tags(c)})
+
+
 TABLES = {
     "XFUSION": (XFUSION, xfusion_tags, REQUIRED_XFUSION),
     "mmf_linear_forward": (LINEAR_FORWARD, linear_forward_tags, REQUIRED_LINEAR_FORWARD),
@@ -1076,6 +1445,11 @@ TABLES = {
     "mmf_adam_l1_step": (ADAM, adam_tags, REQUIRED_ADAM),
     "mmf_abs_sum": (ABS_SUM, abs_sum_tags, REQUIRED_ABS_SUM),
     "mmf_dense_backward": (DENSE_BWD, dense_bwd_tags, REQUIRED_DENSE_BWD),
+    "mmf_dense_forward": (DENSE_FWD, dense_fwd_tags, REQUIRED_DENSE_FWD),
+    "mmf_gate_mul": (GATE_MUL, gate_mul_tags, REQUIRED_GATE_MUL),
+    "mmf_kron": (KRON, kron_tags, REQUIRED_KRON),
+    "mmf_xreduce": (XREDUCE, xreduce_tags, REQUIRED_XREDUCE),
+    "mmf_maxnet_cox_step": (MAXSTEP, maxstep_tags, REQUIRED_MAXSTEP),
 }
 
 

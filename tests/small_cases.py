@@ -569,3 +569,352 @@ def dense_ref(c):
     bar = dict(dx=(n_dx + 8) * U * (np.abs(dpre) @ aW) + e_dpre @ aW, dW=(c.B + 8) * U * (np.abs(dpre).T @ ax) + e_dpre.T @ ax,
                db=(c.B + 8) * U * np.abs(dpre).sum(0) + e_dpre.sum(0), dpre=e_dpre)
     return out, bar
+
+
+# ==== the dense forward, gate_mul, kron and xreduce (tests/test_gpu_tail_shapes.py) ==========================================
+def _drop_out_bar(e_y, y, yd, kind, p):
+    """The bar of drop(y) from the bar e_y of y: nn.Dropout divides by 1 - p, AlphaDropout is a * y + b -- the error of y
+    scaled, plus 8 ulp of what the last operation adds up (|a y| + |b| for the affine form)."""
+    if kind == 0:
+        return e_y
+    if kind == 1:
+        return e_y / (1 - p) + 8 * U * np.abs(yd)
+    a, b, alpha_p = alpha_affine(p)
+    return a * e_y + 8 * U * (np.abs(a * y) + abs(b) + abs(a * alpha_p))
+
+
+# ---- dense forward -------------------------------------------------------------------------------------------------------------
+def dense_fwd_row_seeds(c):
+    return [100 + 7 * b for b in range(c.B)]
+
+
+@functools.lru_cache(maxsize=None)
+def dense_fwd_inputs(c):
+    p = c.drop_p if c.drop_kind else 0.0
+    if not c.drop_kind:
+        keep = np.ones((c.B, c.N), bool)
+    elif c.rows:          # row b: the mask a one-row call with seed_b draws at index n (include/mmf_amil.h mmf_dense_forward_rows)
+        keep = np.concatenate([gen.keep_mask(s, SITE, 1, c.N, p) for s in dense_fwd_row_seeds(c)], 0)
+    else:
+        keep = gen.keep_mask(SEED, SITE, c.B, c.N, p)
+    return dict(x=gen.normal(111, (c.B, c.K), stream=c.K), W=gen.normal(112, (c.N, c.K), stream=c.N % 67, std=1.0 / np.sqrt(c.K)),
+                b=gen.normal(113, (c.N,), stream=1, std=0.3), keep=keep, p=p)
+
+
+def dense_fwd_chain(K):
+    """The longest add chain of one output of dense_fwd_kernel: accumulator a0 takes K / 256 unrolled rounds and up to three
+    tail steps, then (a0 + a1) + (a2 + a3), wave_sum (6) and the bias."""
+    return K // 256 + 3 + 2 + 6 + 1
+
+
+@functools.lru_cache(maxsize=None)
+def dense_fwd_ref(c):
+    i = dense_fwd_inputs(c)
+    x, W = np.asarray(i["x"], f64), np.asarray(i["W"], f64)
+    b = np.asarray(i["b"], f64) if c.bias else np.zeros(c.N)
+    pre = x @ W.T + b
+    e_pre = (dense_fwd_chain(c.K) + 8) * U * (np.abs(x) @ np.abs(W).T + np.abs(b))
+    y = act_ref(pre, c.act)
+    # |act'| <= 1 for none / relu / tanh / sigmoid; SELU: scale above zero, scale * alpha * e^v <= scale * alpha below
+    slope = {0: 1.0, 1: 1.0, 2: 1.0, 3: 0.25, 4: SELU_SCALE * SELU_ALPHA}[c.act]
+    e_y = slope * e_pre + (8 * U * (np.abs(y) + (SELU_SCALE * SELU_ALPHA if c.act == 4 else 0.0)) if c.act >= 2 else 0.0)
+    yd = drop_fwd(y, i["keep"], c.drop_kind, i["p"])
+    return dict(y=yd, y_act=y), dict(y=_drop_out_bar(e_y, y, yd, c.drop_kind, i["p"]))
+
+
+# ---- gate_mul ----------------------------------------------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def gate_mul_inputs(c):
+    return dict(z=gen.normal(121, (c.n,), stream=c.n % 61, std=2.0), h=gen.normal(122, (c.n,), stream=1), g=gen.normal(123, (c.n,), stream=2))
+
+
+@functools.lru_cache(maxsize=None)
+def gate_mul_ref(c):
+    i = gate_mul_inputs(c)
+    z, h, g = (np.asarray(i[k], f64) for k in ("z", "h", "g"))
+    s = 1 / (1 + np.exp(-z))
+    out = dict(o=s * h, dz=g * h * s * (1 - s), dh=g * s)
+    # single terms: 8 ulp; dz holds 1 - s, where the 4 ulp of s (expf, the add, the division) are absolute: |g h| 4U s on top
+    bar = dict(o=8 * U * np.abs(out["o"]), dh=8 * U * np.abs(out["dh"]), dz=8 * U * np.abs(out["dz"]) + np.abs(g * h) * 4 * U * s)
+    return out, bar
+
+
+# ---- kron ------------------------------------------------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def kron_inputs(c):
+    S = c.dim + 1
+    o = [gen.normal(131 + t, (c.B, c.dim), stream=c.dim % 59) for t in range(c.m)]
+    keep = gen.keep_mask(SEED, SITE, c.B, S ** c.m, c.drop_p) if c.drop_p > 0 else np.ones((c.B, S ** c.m), bool)
+    return dict(o=o, g=gen.normal(135, (c.B, S ** c.m), stream=c.m), keep=keep)
+
+
+@functools.lru_cache(maxsize=None)
+def kron_ref(c):
+    i = kron_inputs(c)
+    S = c.dim + 1
+    ext = [np.concatenate([np.asarray(o, f64), np.ones((c.B, 1))], 1) for o in i["o"]]
+    scale = np.where(i["keep"], 1 / (1 - c.drop_p), 0.0) if c.drop_p > 0 else np.ones((c.B, S ** c.m))
+    letters = "ijk"[:c.m]
+    full = np.einsum(",".join("b" + l for l in letters) + "->b" + letters, *ext).reshape(c.B, -1)
+    out = dict(out=full * scale)
+    bar = dict(out=8 * U * np.abs(out["out"]))
+    gs = (np.asarray(i["g"], f64) * scale).reshape((c.B,) + (S,) * c.m)
+    n_chain = -(-(S ** (c.m - 1)) // 64) + 6            # a lane's share of the others, then wave_sum
+    for t in range(c.m):
+        rest = [ext[u] for u in range(c.m) if u != t]
+        rl = [letters[u] for u in range(c.m) if u != t]
+        spec = "b" + letters + "," + ",".join("b" + l for l in rl) + "->b" + letters[t]
+        out[f"d{t}"] = np.einsum(spec, gs, *rest)[:, :c.dim]
+        bar[f"d{t}"] = (n_chain + 8) * U * np.einsum(spec, np.abs(gs), *[np.abs(r) for r in rest])[:, :c.dim]
+    return out, bar
+
+
+# ---- xreduce -----------------------------------------------------------------------------------------------------------------------
+XR_KEYS = ("Wh", "bh", "Wz", "bz", "Wo", "bo")
+
+
+@functools.lru_cache(maxsize=None)
+def xreduce_inputs(c):
+    m, B, dim, S = c.m, c.B, c.dim, c.sdim
+    st = (dim + 3 * S) % 53
+    i = dict(v=[gen.normal(141 + t, (B, dim), stream=st) for t in range(m)],
+             Wh=[gen.normal(145 + t, (S, dim), stream=st, std=1 / np.sqrt(dim)) for t in range(m)],
+             bh=[0.5 + gen.normal(149 + t, (S,), stream=st, std=0.3) for t in range(m)],      # shifted: a one-unit stage still has a live unit
+             Wz=[gen.normal(153 + t, (S, m * dim), stream=st, std=1 / np.sqrt(m * dim)) for t in range(m)],
+             bz=[gen.normal(157 + t, (S,), stream=st, std=0.3) for t in range(m)],
+             Wo=[gen.normal(161 + t, (S, S), stream=st, std=1 / np.sqrt(S)) for t in range(m)],
+             bo=[0.5 + gen.normal(165 + t, (S,), stream=st, std=0.3) for t in range(m)],
+             d_o=[gen.normal(169 + t, (B, S), stream=st) for t in range(m)])
+    # site t of the seed, element b * sdim + j (csrc/mmf_mlp.hip site_drop)
+    i["keep"] = [gen.keep_mask(SEED, t, B, S, c.drop_p) if c.drop_p > 0 else np.ones((B, S), bool) for t in range(m)]
+    return i
+
+
+def _wave_dot_chain(dim):
+    return 4 * (-(-dim // 256))                # a lane's rounds, four adds each (three inside the float4, one onto acc)
+
+
+@functools.lru_cache(maxsize=None)
+def xreduce_ref(c):
+    i = xreduce_inputs(c)
+    m, B, dim, S, p = c.m, c.B, c.dim, c.sdim, c.drop_p
+    A = lambda k: [np.asarray(a, f64) for a in i[k]]
+    v, Wh, bh, Wz, bz, Wo, bo, d_o = (A(k) for k in ("v", "Wh", "bh", "Wz", "bz", "Wo", "bo", "d_o"))
+    vcat = np.concatenate(v, 1)
+    nh, nz = _wave_dot_chain(dim) + 7, m * (_wave_dot_chain(dim) + 1) + 7          # + wave_sum (6) + the bias
+    out, bar = {}, {}
+    for t in range(m):
+        hp = v[t] @ Wh[t].T + bh[t]
+        h = np.maximum(hp, 0)
+        e_h = (nh + 8) * U * (np.abs(v[t]) @ np.abs(Wh[t]).T + np.abs(bh[t]))
+        z = vcat @ Wz[t].T + bz[t]
+        e_z = (nz + 8) * U * (np.abs(vcat) @ np.abs(Wz[t]).T + np.abs(bz[t]))
+        s = 1 / (1 + np.exp(-z))
+        gm = s * h
+        e_gm = 8 * U * np.abs(gm) + h * s * (1 - s) * e_z + s * e_h
+        op = gm @ Wo[t].T + bo[t]
+        e_op = (S + 1 + 8) * U * (np.abs(gm) @ np.abs(Wo[t]).T + np.abs(bo[t])) + e_gm @ np.abs(Wo[t]).T
+        o = np.maximum(op, 0)
+        od = np.where(i["keep"][t], o / (1 - p), 0.0) if p > 0 else o
+        out.update({f"h{t}": h, f"z{t}": z, f"gm{t}": gm, f"o{t}": od, f"hp{t}": hp, f"op{t}": op})
+        bar.update({f"h{t}": e_h, f"z{t}": e_z, f"gm{t}": e_gm, f"o{t}": np.where(i["keep"][t], e_op / (1 - p) + 8 * U * np.abs(od), 0.0)})
+    # backward, from the forward outputs rounded to fp32 (what the kernel is given)
+    h32, z32, gm32, o32 = ([r32(out[f"{k}{t}"]) for t in range(m)] for k in ("h", "z", "gm", "o"))
+    out.update(h32=h32, z32=z32, gm32=gm32, o32=o32)
+    dz, dph, e_dz, e_dph = [], [], [], []
+    for t in range(m):
+        hh, zz, gg, oo = (np.asarray(a[t], f64) for a in (h32, z32, gm32, o32))
+        dydy = np.where(i["keep"][t], 1 / (1 - p), 0.0) if p > 0 else np.ones((B, S))
+        dpo = d_o[t] * dydy * (oo > 0)
+        e_dpo = 8 * U * np.abs(dpo)
+        dgm = dpo @ Wo[t]
+        e_dgm = (S + 8) * U * (np.abs(dpo) @ np.abs(Wo[t])) + e_dpo @ np.abs(Wo[t])
+        s = 1 / (1 + np.exp(-zz))
+        dz.append(dgm * hh * s * (1 - s))
+        e_dz.append(8 * U * np.abs(dz[t]) + e_dgm * np.abs(hh) * s * (1 - s) + np.abs(dgm * hh) * 4 * U * s)
+        dph.append(np.where(hh > 0, dgm * s, 0.0))
+        e_dph.append(np.where(hh > 0, 8 * U * np.abs(dph[t]) + e_dgm * s, 0.0))
+        out[f"dWo{t}"], bar[f"dWo{t}"] = dpo.T @ gg, (B + 8) * U * (np.abs(dpo).T @ np.abs(gg)) + e_dpo.T @ np.abs(gg)
+        out[f"dbo{t}"], bar[f"dbo{t}"] = dpo.sum(0), (B + 8) * U * np.abs(dpo).sum(0) + e_dpo.sum(0)
+        out[f"dbh{t}"], bar[f"dbh{t}"] = dph[t].sum(0), (B + 8) * U * np.abs(dph[t]).sum(0) + e_dph[t].sum(0)
+        out[f"dbz{t}"], bar[f"dbz{t}"] = dz[t].sum(0), (B + 8) * U * np.abs(dz[t]).sum(0) + e_dz[t].sum(0)
+        out[f"dWh{t}"], bar[f"dWh{t}"] = dph[t].T @ v[t], (B + 8) * U * (np.abs(dph[t]).T @ np.abs(v[t])) + e_dph[t].T @ np.abs(v[t])
+        out[f"dWz{t}"], bar[f"dWz{t}"] = dz[t].T @ vcat, (B + 8) * U * (np.abs(dz[t]).T @ np.abs(vcat)) + e_dz[t].T @ np.abs(vcat)
+    for t in range(m):      # dv_t = dph_t Wh_t + sum_i dz_i Wz_i[:, block t]: chains of S, then the m partial sums onto acc
+        blk = slice(t * dim, (t + 1) * dim)
+        out[f"dv{t}"] = dph[t] @ Wh[t] + sum(dz[u] @ Wz[u][:, blk] for u in range(m))
+        mag = np.abs(dph[t]) @ np.abs(Wh[t]) + sum(np.abs(dz[u]) @ np.abs(Wz[u][:, blk]) for u in range(m))
+        bar[f"dv{t}"] = (S + m + 8) * U * mag + e_dph[t] @ np.abs(Wh[t]) + sum(e_dz[u] @ np.abs(Wz[u][:, blk]) for u in range(m))
+    return out, bar
+
+
+XR_FWD_KEYS = ("h", "z", "gm", "o")
+XR_BWD_KEYS = ("dv", "dWh", "dbh", "dWz", "dbz", "dWo", "dbo")
+
+
+# ---- the omic step (mmf_maxnet_cox_step) ---------------------------------------------------------------------------------------
+MX_SEED = 4242
+MX_SPREAD, MX_BIAS = 1.2, 2.0          # the largest |x . W^T| of a layer after scaling W; |b| in units of that spread
+
+
+def _selu_drop(pre, keep, p):
+    y = act_ref(pre, 4)
+    return y, (drop_fwd(y, keep, 2, p) if p > 0 else y)
+
+
+@functools.lru_cache(maxsize=None)
+def maxstep_inputs(c):
+    """A state dict of the case's own: in each layer the weights are scaled so that the largest |in . W^T| of the float64
+    reference is MX_SPREAD, and feature n has the bias (-1)^n (layer 0) or -(-1)^n (layer 1) times MX_BIAS spreads.  Every
+    pre-activation then lies between 1 and 3 spreads from zero on its feature's side: far from SELU's kink, both branches
+    in every row, and the negative ones above -3.6, where y + scale * alpha is well above its rounding."""
+    B, G, p = c.B, c.G, c.p_drop
+    x = gen.normal(201, (B, G), stream=G % 47)
+    sign = np.where(np.arange(256) % 2 == 0, 1.0, -1.0)
+    W0 = gen.normal(202, (256, G), stream=G % 43)
+    W0 = (W0 * (MX_SPREAD / np.abs(np.asarray(x, f64) @ np.asarray(W0, f64).T).max())).astype(np.float32)
+    s0 = np.abs(np.asarray(x, f64) @ np.asarray(W0, f64).T).max()
+    b0 = (sign * MX_BIAS * s0).astype(np.float32)
+    seed = (MX_SEED + c.word) & 0xFFFFFFFF
+    keep0 = gen.keep_mask(seed, 0, B, 256, p) if p > 0 else np.ones((B, 256), bool)
+    keep1 = gen.keep_mask(seed, 1, B, 256, p) if p > 0 else np.ones((B, 256), bool)
+    _, y0d = _selu_drop(np.asarray(x, f64) @ np.asarray(W0, f64).T + b0, keep0, p)
+    W1 = gen.normal(203, (256, 256), stream=B % 41)
+    W1 = (W1 * (MX_SPREAD / np.abs(y0d @ np.asarray(W1, f64).T).max())).astype(np.float32)
+    s1 = np.abs(y0d @ np.asarray(W1, f64).T).max()
+    b1 = (-sign * MX_BIAS * s1).astype(np.float32)
+    Wc = gen.normal(204, (1, 256), stream=3, std=1 / 16)
+    bc = np.array([0.1], np.float32)
+    u = gen.uniform01(205, B, stream=B % 37)
+    times = (np.argsort(np.argsort(u)) + 1).astype(f64)                     # distinct
+    cens = (gen.uniform01(206, B, stream=5) < 0.3).astype(np.float32)
+    if c.censor == "none":
+        cens[:] = 0
+    elif c.censor == "all":
+        cens[:] = 1
+    elif c.censor == "tied":
+        times = (np.floor(u * 3) + 1).astype(f64)
+        cens[0] = 0
+    elif c.censor == "last event":
+        cens[:] = 1
+        cens[int(np.argmax(times))] = 0
+    prior = {k: gen.normal(210 + j, shape, stream=1, std=0.01) for j, (k, shape) in enumerate(
+        dict(dW0=(256, G), db0=(256,), dW1=(256, 256), db1=(256,), dWc=(1, 256), dbc=(1,)).items())} if c.accumulate else None
+    return dict(x=x, W0=W0, b0=b0, W1=W1, b1=b1, Wc=Wc, bc=bc, times=times, c=cens, keep0=keep0, keep1=keep1, prior=prior)
+
+
+def maxstep_state_dict(i):
+    return {"fc_omic.0.0.weight": i["W0"], "fc_omic.0.0.bias": i["b0"], "fc_omic.1.0.weight": i["W1"], "fc_omic.1.0.bias": i["b1"],
+            "classifier.weight": i["Wc"], "classifier.bias": i["bc"]}
+
+
+def _selu_bars(pre, e_pre, y, yd, keep, p):
+    """Bars of y = selu(pre) and of its AlphaDropout from the bar of pre: SELU's slope (scale above zero, scale * alpha *
+    e^v below, taken at the near end of the bar) times e_pre, and 8 ulp of what the last operation adds up."""
+    SA = SELU_SCALE * SELU_ALPHA
+    slope = np.where(pre > 0, SELU_SCALE, SA * np.exp(np.minimum(pre + e_pre, 0)))
+    e_y = slope * e_pre + 8 * U * (np.abs(y) + np.where(pre > 0, 0.0, SA))
+    if p == 0:
+        return e_y, e_y
+    a, b, alpha_p = alpha_affine(p)
+    return e_y, np.where(keep, a * e_y, 0.0) + 8 * U * (np.abs(a * np.where(keep, y, alpha_p)) + abs(b))
+
+
+def _selu_grad_bars(y, e_y, yd, keep, p):
+    """(dydy, selu'(y), bar of selu'(y)) as the kernel derives them from its own dropped output: y recovered as (yd - b) / a,
+    then y + scale * alpha below zero -- the error of y, 4 ulp of the recovery's operands and of the constant."""
+    SA = SELU_SCALE * SELU_ALPHA
+    if p > 0:
+        a, b, _ = alpha_affine(p)
+        dydy, e_rec = np.where(keep, a, 0.0), e_y + 4 * U * (np.abs(yd) + abs(b)) / a
+    else:
+        dydy, e_rec = np.ones_like(y), e_y
+    sg = np.where(y > 0, SELU_SCALE, y + SA)
+    return dydy, sg, np.where(y > 0, 0.0, e_rec + 4 * U * SA)
+
+
+@functools.lru_cache(maxsize=None)
+def maxstep_ref(c):
+    """-> (out, bar, facts).  out: risk, loss and the six gradients (of loss * loss_scale, on top of the prior values under
+    accumulate) in float64; bar: the summation bound of each, cut at the bar tests/test_gpu_maxnet_step.py:30-35 holds
+    (1e-5 max(1, |loss|); 1e-4 on risks; 1e-5 + 1e-4 max|g| on gradients).  Under accumulate the cut applies to the gradient's
+    own error, and the one rounding of the add onto the known value, 2^-24 (|prior| + |g|), comes on top: that case's bar may
+    sit that much above the existing one.  Chains, read from csrc/mmf_maxnet.hip:
+      layer 0   four accumulators of G / 4 k each, up to three more steps on the first in a ragged chunk, (0 + 1) + (2 + 3), bias
+      layer 1   four accumulators of 64, the two adds, the bias: 67         risk  wave_sum (6), the four waves (3), bc: 10
+      D_i       four accumulators over B / 4 members, three tail steps, two adds      loss  wave_sum, four waves, 1 / B: 10
+      a_k       64 threads over B / 64 members each, six shuffles            dbc   wave_sum, four waves: 9
+      dWc       a workgroup's four rows, the shares in eight interleaved sums of NW / 8, three adds
+      dy0       four accumulators of 64, two adds: 66        dW1  two accumulators over B / 2 rows, one add
+      db1, db0  16 lanes over B / 16 rows, four shuffles      dW0  256 / G parts over B / parts rows each, then the parts in order"""
+    i = maxstep_inputs(c)
+    B, G, p = c.B, c.G, c.p_drop
+    x, W0, b0, W1, b1, Wc, bc = (np.asarray(i[k], f64) for k in ("x", "W0", "b0", "W1", "b1", "Wc", "bc"))
+    Wc = Wc.reshape(-1)
+    k0, k1 = i["keep0"], i["keep1"]
+    # forward
+    pre0 = x @ W0.T + b0
+    e_pre0 = (G // 4 + 3 + 3 + 8) * U * (np.abs(x) @ np.abs(W0).T + np.abs(b0))
+    y0, y0d = _selu_drop(pre0, k0, p)
+    e_y0, e_y0d = _selu_bars(pre0, e_pre0, y0, y0d, k0, p)
+    pre1 = y0d @ W1.T + b1
+    e_pre1 = (67 + 8) * U * (np.abs(y0d) @ np.abs(W1).T + np.abs(b1)) + e_y0d @ np.abs(W1).T
+    y1, y1d = _selu_drop(pre1, k1, p)
+    e_y1, e_y1d = _selu_bars(pre1, e_pre1, y1, y1d, k1, p)
+    risk = y1d @ Wc + bc[0]
+    e_risk = (10 + 8) * U * (np.abs(y1d) @ np.abs(Wc) + abs(bc[0])) + e_y1d @ np.abs(Wc)
+    # Cox
+    t, unc = np.asarray(i["times"], f64), 1 - np.asarray(i["c"], f64)
+    R = (t[None, :] >= t[:, None]).astype(f64)                              # R[i, j] = t_j >= t_i
+    et = np.exp(risk)
+    e_et = et * (e_risk + 4 * U)
+    D = R @ et
+    e_D = (-(-B // 4) + 3 + 2 + 8) * U * D + R @ e_et
+    lterm = (risk - np.log(D)) * unc
+    e_l = unc * (e_risk + e_D / D + 4 * U * np.abs(np.log(D)) + 4 * U * np.abs(risk - np.log(D)))
+    loss = -lterm.sum() / B
+    e_loss = ((10 + 8) * U * np.abs(lterm).sum() + e_l.sum()) / B
+    wq = unc / D
+    e_wq = wq * (e_D / D + 4 * U)
+    acc = R.T @ wq                                                          # a_k = sum_i [t_k >= t_i] w_i
+    e_acc = (-(-B // 64) + 6 + 8) * U * acc + R.T @ e_wq
+    ls = float(np.float32(c.loss_scale))
+    dr = -(unc - et * acc) / B * ls
+    e_dr = (et * e_acc + acc * e_et + 8 * U * (unc + et * acc)) / B * ls
+    # backward
+    NW = ab.maxstep_workgroups(B)
+    g = dict(dbc=np.array([dr.sum()]), dWc=(dr @ y1d)[None, :])
+    e = dict(dbc=np.array([(9 + 8) * U * np.abs(dr).sum() + e_dr.sum()]),
+             dWc=((4 + NW // 8 + 3 + 8) * U * (np.abs(dr) @ np.abs(y1d)) + e_dr @ np.abs(y1d) + np.abs(dr) @ e_y1d)[None, :])
+    dydy1, sg1, e_sg1 = _selu_grad_bars(y1, e_y1, y1d, k1, p)
+    dpre1 = dr[:, None] * Wc[None, :] * dydy1 * sg1
+    e_dpre1 = np.abs(Wc[None, :] * dydy1) * (e_dr[:, None] * np.abs(sg1) + np.abs(dr)[:, None] * e_sg1) + 8 * U * np.abs(dpre1)
+    n_db = -(-B // 16) + 4
+    g["db1"], e["db1"] = dpre1.sum(0), (n_db + 8) * U * np.abs(dpre1).sum(0) + e_dpre1.sum(0)
+    g["dW1"] = dpre1.T @ y0d
+    e["dW1"] = (B // 2 + 2 + 8) * U * (np.abs(dpre1).T @ np.abs(y0d)) + e_dpre1.T @ np.abs(y0d) + np.abs(dpre1).T @ e_y0d
+    dy0 = dpre1 @ W1
+    e_dy0 = (66 + 8) * U * (np.abs(dpre1) @ np.abs(W1)) + e_dpre1 @ np.abs(W1)
+    dydy0, sg0, e_sg0 = _selu_grad_bars(y0, e_y0, y0d, k0, p)
+    dpre0 = dy0 * dydy0 * sg0
+    e_dpre0 = np.abs(dydy0) * (e_dy0 * np.abs(sg0) + np.abs(dy0) * e_sg0) + 8 * U * np.abs(dpre0)
+    g["db0"], e["db0"] = dpre0.sum(0), (n_db + 8) * U * np.abs(dpre0).sum(0) + e_dpre0.sum(0)
+    parts = 256 // G
+    g["dW0"], e["dW0"] = dpre0.T @ x, (-(-B // parts) + parts + 8) * U * (np.abs(dpre0).T @ np.abs(x)) + e_dpre0.T @ np.abs(x)
+    out = dict(risk=risk, loss=float(loss))
+    bar = dict(risk=np.minimum(e_risk, 1e-4), loss=min(float(e_loss), 1e-5 * max(1.0, abs(float(loss)))))
+    for k in g:
+        old = 1e-5 + 1e-4 * float(np.abs(g[k]).max())
+        if c.accumulate:                                                    # one more add, onto the known value
+            prior = np.asarray(i["prior"][k], f64)
+            out[k], bar[k] = prior + g[k], np.minimum(e[k], old) + U * (np.abs(prior) + np.abs(g[k]))
+        else:
+            out[k], bar[k] = g[k], np.minimum(e[k], old)
+    facts = dict(kink0=float((np.abs(pre0) / e_pre0).min()), kink1=float((np.abs(pre1) / e_pre1).min()),
+                 branches=[bool((q > 0).any() and (q < 0).any()) for q in (pre0, pre1)], min_pre=float(min(pre0.min(), pre1.min())),
+                 masks=[bool(k.any() and not k.all()) for k in (k0, k1)], loose={k: float((e[k] > 1e-5 + 1e-4 * np.abs(g[k]).max()).mean()) for k in g},
+                 pure=dict(loss=float(loss), **g))
+    return out, bar, facts
+
+
+MX_GRADS = ("dW0", "db0", "dW1", "db1", "dWc", "dbc")

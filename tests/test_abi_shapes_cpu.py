@@ -4,7 +4,9 @@ and the case tables of tests/test_gpu_abi_shapes.py and tests/test_gpu_xfusion_s
 rules make reachable; for the fusion tail also the two workspace queries over a grid on both sides of every limit, and the
 fp64 oracle of every case clear of every ReLU kink under the seed the case records; for the small ops (losses, hazard heads,
 batch norm, the step tail, the dense backward) also the conditions their generated inputs must meet (tests/small_cases.py) and
-the vectorised Cox and ranking restatements against the ports."""
+the vectorised Cox and ranking restatements against the ports; for the dense forward, gate_mul, kron, xreduce and the omic
+step (the tables below DENSE_BWD) the same, the kron caps from both sides, the omic step's workspace query, its margin to
+SELU's kink and its censoring patterns, and each numpy reference against oracle/torch_port.py through autograd."""
 import ctypes as C
 import dataclasses
 
@@ -484,3 +486,263 @@ def test_vectorised_restatements_match_the_ports():
         grad = np.zeros(c.B) if r.grad is None else r.grad.numpy()
         loss, d = sc.rank_vectorised(i["risks"], i["times"], i["c"], c.phi, c.reduction)[:2]
         assert abs(loss - float(want.detach().sum())) <= 1e-12 * max(1, abs(loss)) and np.abs(d - grad).max() <= 1e-13, c
+
+
+# ---- the dense forward, gate_mul, kron, xreduce and the omic step -------------------------------------------------------------
+def _xreduce_io(m_, c, bwd):
+    io = m_.XReduceIO(m=c.m, B=c.B, dim=c.dim, sdim=c.sdim)
+    names = ["v", "Wh", "bh", "Wz", "bz", "Wo", "bo", "h", "z", "gm", "o"] + (["d_o", "dv", "dWh", "dbh", "dWz", "dbz", "dWo", "dbo"] if bwd else [])
+    for k, n in enumerate(names):
+        for i in range(max(0, min(c.m, 3))):
+            getattr(io, n)[i] = 0x100000 * (k + 1) + 0x1000 * i
+    if c.misalign:
+        io.v[0] = io.v[0] + 4
+    if c.null:
+        getattr(io, c.null)[c.m - 1] = None
+    return io
+
+
+def _maxstep_call(m_, l, c):
+    names = {n: 0x100000 * (k + 1) for k, n in enumerate(ab.MX_PTRS)}
+    if c.null:
+        names[c.null] = None
+    if c.off:
+        names[c.off] += 4
+    d = m_.MaxnetDesc(B=c.B, G=c.G, H0=c.H0, H1=256, p_drop=c.p_drop, seed=1, seed_dev=None, sync_words=c.sync_words, trace=None,
+                      **{k: names[k] for k in ("x", "W0", "b0", "W1", "b1", "Wc", "bc", "sync")})
+    g = m_.MaxnetGrads(**{k: names[k] for k in ("dW0", "db0", "dW1", "db1", "dWc", "dbc")})
+    ws = l.mmf_maxnet_cox_step_workspace_bytes(c.B) - (1 if c.ws_short else 0)
+    return l.mmf_maxnet_cox_step(C.byref(d), names["times"], names["c"], C.c_float(c.loss_scale), names["workspace"], ws,
+                                 names["risk"], names["loss"], C.byref(g), c.accumulate, None)
+
+
+def test_tail_refusals_in_the_library():
+    """Every refusal of the five new tables returns before a launch: reproduced with pointers that are never read."""
+    m_, l = _lib()
+    f = C.c_float
+    for c in ab.refused(ab.DENSE_FWD, ab.dense_fwd_rule):
+        if c.rows:
+            rc = l.mmf_dense_forward_rows(P[0], P[1], P[2], c.B, c.K, c.N, c.act, c.drop_kind, f(c.drop_p), 1, None,
+                                          P[3] if c.base else None, P[4], c.N - 1 if c.rows < 0 else c.N, None)
+        else:
+            rc = l.mmf_dense_forward(P[0], P[1], P[2], c.B, c.K, c.N, c.act, c.drop_kind, f(c.drop_p), 1, 1, None, P[4], None)
+        assert rc == ab.dense_fwd_rule(c) != ab.OK, c
+    for ptrs in ((None, P[1], P[2]), (P[0], None, P[2]), (P[0], P[1], None)):       # x, W, y
+        assert l.mmf_dense_forward(ptrs[0], ptrs[1], P[3], 2, 8, 8, 0, 0, f(0), 1, 1, None, ptrs[2], None) == ab.ERR_ARG
+    for c in ab.refused(ab.GATE_MUL, ab.gate_mul_rule):
+        assert l.mmf_gate_mul_forward(P[0], P[1], P[2], c.n, None) == ab.gate_mul_rule(c)
+        assert l.mmf_gate_mul_backward(P[0], P[1], P[2], P[3], P[4], c.n, None) == ab.gate_mul_rule(c)
+    for c in ab.refused(ab.KRON, ab.kron_rule):
+        n = max(c.m, 1)
+        o = (C.c_void_p * n)(*[None if c.null and t == c.m - 1 else P[t] for t in range(n)])
+        d = (C.c_void_p * n)(*P[4:4 + n])
+        assert l.mmf_kron_forward(o, c.m, c.dim, c.B, f(c.drop_p), 1, 1, None, P[8], None) == ab.kron_rule(c) != ab.OK, c
+        assert l.mmf_kron_backward(P[9], o, c.m, c.dim, c.B, f(c.drop_p), 1, 1, None, d, None) == ab.kron_rule(c), c
+    for c in ab.XREDUCE:
+        if ab.xreduce_fwd_rule(c) != ab.OK:
+            assert l.mmf_xreduce_forward(C.byref(_xreduce_io(m_, c, False)), f(c.drop_p), 1, None, None) == ab.xreduce_fwd_rule(c), c
+        if ab.xreduce_bwd_rule(c) != ab.OK:
+            assert l.mmf_xreduce_backward(C.byref(_xreduce_io(m_, c, True)), f(c.drop_p), 1, None, None) == ab.xreduce_bwd_rule(c), c
+    for name in ("v", "Wh", "bh", "Wz", "bz", "Wo", "bo", "h", "z", "gm", "o"):      # any NULL member, both directions
+        c = ab.XReduce(2, 1, 4, 4, null=name)
+        assert l.mmf_xreduce_forward(C.byref(_xreduce_io(m_, c, False)), f(0), 1, None, None) == ab.xreduce_fwd_rule(c) == ab.ERR_ARG, name
+        assert l.mmf_xreduce_backward(C.byref(_xreduce_io(m_, c, True)), f(0), 1, None, None) == ab.xreduce_bwd_rule(c) == ab.ERR_ARG, name
+    for name in ("d_o", "dv", "dWh", "dbh", "dWz", "dbz", "dWo", "dbo"):            # the backward's own members
+        c = ab.XReduce(2, 1, 4, 4, null=name)
+        assert l.mmf_xreduce_backward(C.byref(_xreduce_io(m_, c, True)), f(0), 1, None, None) == ab.ERR_ARG, name
+    for c in (ab.XReduce(1, 65536, 4, 65536), ab.XReduce(3, 46341, 4, 46341), ab.XReduce(3, 2**31 - 1, 4, 2**31 - 1)):
+        # m * B * sdim wraps an int (to 0, to a negative value) or an int64: still above the cap of 384, in both directions
+        assert ab.xreduce_fwd_rule(c) == ab.xreduce_bwd_rule(c) == ab.ERR_SHAPE
+        assert l.mmf_xreduce_forward(C.byref(_xreduce_io(m_, c, False)), f(0), 1, None, None) == ab.ERR_SHAPE, c
+        assert l.mmf_xreduce_backward(C.byref(_xreduce_io(m_, c, True)), f(0), 1, None, None) == ab.ERR_SHAPE, c
+    # the plain dense forward's 32-bit mask index: B * N >= 2^32 is refused where a mask is drawn (never launched: no such
+    # shape is called without dropout here); the _rows form indexes row_base[b] + n and has no such limit in its rule
+    for B, N in ((65536, 65536), (2**31 - 1, 3)):
+        c = ab.DenseFwd(B, 8, N, drop_kind=1)
+        assert ab.dense_fwd_rule(c) == ab.ERR_SHAPE == l.mmf_dense_forward(P[0], P[1], P[2], B, 8, N, 0, 1, f(0.25), 1, 1, None, P[4], None)
+        assert ab.dense_fwd_rule(dataclasses.replace(c, drop_kind=0)) == ab.dense_fwd_rule(dataclasses.replace(c, rows=1)) == ab.OK
+    assert ab.dense_fwd_rule(ab.DenseFwd(65536, 8, 65535, drop_kind=2)) == ab.OK
+    for c in ab.refused(ab.MAXSTEP, ab.maxstep_rule):
+        assert _maxstep_call(m_, l, c) == ab.maxstep_rule(c) != ab.OK, c
+
+
+def test_kron_caps_from_both_sides():
+    """F1: B * S^m < 2^31 and B <= 65535 -- the rule on both sides of every limit (the admitted side is never launched)."""
+    K = ab.Kron
+    for c, want in ((K(3, 1289), ab.OK), (K(3, 1290), ab.ERR_SHAPE), (K(2, 46339), ab.OK), (K(2, 46340), ab.ERR_SHAPE),
+                    (K(2, 255, B=32767), ab.OK), (K(2, 255, B=32768), ab.ERR_SHAPE), (K(2, 1, B=65535), ab.OK), (K(2, 1, B=65536), ab.ERR_SHAPE),
+                    (K(3, 2**31 - 2), ab.ERR_SHAPE), (K(2, 2**31 - 1), ab.ERR_SHAPE)):
+        assert ab.kron_rule(c) == want, c
+    assert 1290 ** 3 < 2**31 <= 1291 ** 3 and 46340 ** 2 < 2**31 <= 46341 ** 2
+    m_, l = _lib()
+    o, d = (C.c_void_p * 3)(*P[:3]), (C.c_void_p * 3)(*P[4:7])
+    for m, dim in ((3, 2**31 - 2), (2, 2**31 - 1), (3, 65535), (2, 65536)):          # S^m beyond int64 / int: still refused, not wrapped
+        assert l.mmf_kron_forward(o, m, dim, 1, C.c_float(0), 1, 1, None, P[8], None) == ab.ERR_SHAPE
+        assert l.mmf_kron_backward(P[9], o, m, dim, 1, C.c_float(0), 1, 1, None, d, None) == ab.ERR_SHAPE
+    assert {(c.m, c.dim, c.B) for c in ab.KRON if ab.kron_rule(c) == ab.ERR_SHAPE} == ab.KRON_CAPS
+
+
+def test_maxstep_workspace_query_matches_the_restated_size():
+    m_, l = _lib()
+    for B in (-3, 0, 1, 4, 5, 63, 64, 65, 127, 128, 129, 200, 255, 256):
+        assert l.mmf_maxnet_cox_step_workspace_bytes(B) == ab.maxstep_workspace_bytes(B), B
+
+
+def test_tail_header_changes_keep_the_abi_version():
+    """The header changes of these entry points are comments, and refusals of shapes and pointers that were never valid: the
+    ABI version stays where it was.  (What the header says is checked against the library by the refusal pins above.)"""
+    from multimodalfusion_amd import _lib as m
+    assert m.ABI_VERSION == 12
+
+
+def test_tail_tables_hold_what_the_issue_lists():
+    acc = ab.accepted
+    d = acc(ab.DENSE_FWD, ab.dense_fwd_rule)
+    assert {c.K for c in d} >= {1, 63, 64, 65, 255, 256, 257, 513} and {c.B * c.N for c in d} >= {1, 3, 4, 5}
+    assert (2049, 1, 2048) in {(c.B, c.K, c.N) for c in d} and 2049 * 2048 > 4 * ab.DENSE_FWD_GRID == 4194240
+    assert {c.act for c in d} == {0, 1, 2, 3, 4} and {c.drop_kind for c in d} == {0, 1, 2} and any(not c.bias for c in d)
+    assert {c.rows == 1 for c in d if c.rows} == {True, False} and len(ab.refused(ab.DENSE_FWD, ab.dense_fwd_rule)) == 8
+    assert [c.n for c in acc(ab.GATE_MUL, ab.gate_mul_rule)] == [1, 255, 256, 257, 1000]
+    k = acc(ab.KRON, ab.kron_rule)
+    assert {(c.m, c.dim) for c in k} == {(2, 1), (2, 15), (2, 16), (3, 5), (3, 6), (3, 16), (2, 63), (2, 64), (3, 7), (3, 8)}
+    assert {c.B for c in k} == {1, 3} and {c.drop_p > 0 for c in k} == {True, False}
+    assert {(c.m, c.dim, c.null) for c in ab.refused(ab.KRON, ab.kron_rule) if ab.kron_rule(c) == ab.ERR_ARG} == {(1, 4, False), (4, 4, False), (2, 0, False), (3, 4, True)}
+    x = acc(ab.XREDUCE, ab.xreduce_fwd_rule)
+    assert {c.dim for c in x} >= {4, 252, 256, 260, 1024, 1028} and {c.sdim for c in x} >= {1, 15, 16, 17, 32, 33, 384}
+    assert {(c.m, c.B, c.sdim) for c in x} >= {(1, 1, 1), (2, 1, 16), (3, 1, 16), (3, 8, 16), (1, 1, 32), (1, 1, 33), (1, 1, 384)}
+    assert {c.B for c in x} >= {1, 2, 8}
+    one_sided = [c for c in ab.XREDUCE if ab.xreduce_fwd_rule(c) != ab.OK and ab.xreduce_bwd_rule(c) == ab.OK]
+    assert sorted((ab.xreduce_fwd_rule(c), c.dim % 4 != 0, c.misalign) for c in one_sided) == [(ab.ERR_ALIGN, False, True), (ab.ERR_SHAPE, True, False)]
+    assert {(c.m, c.B, c.sdim) for c in ab.XREDUCE if ab.xreduce_bwd_rule(c) == ab.ERR_SHAPE} == {(3, 8, 17), (1, 1, 385)}
+    s = acc(ab.MAXSTEP, ab.maxstep_rule)
+    assert {c.G for c in s if ab.maxstep_route(c) == "narrow"} == {4, 16, 36, 60, 64}
+    assert {c.G for c in s if ab.maxstep_route(c) == "chunked"} >= {1, 63, 65, 128, 129, 193, 256}
+    assert [c.G for c in s if c.misalign] == [36]
+    assert {c.B for c in s} >= {1, 3, 4, 5, 127, 128, 129, 255, 256, 15, 16, 17, 19, 63, 64, 65} and 10 <= len(s) <= 16
+    assert {n.null for n in ab.MAXSTEP if n.null} == set(ab.MX_PTRS)
+    assert {(c.B, c.G) for c in ab.refused(ab.MAXSTEP, ab.maxstep_rule) if not c.null} >= {(0, 36), (257, 36), (8, 0), (8, 257)}
+
+
+def test_tail_inputs_meet_the_conditions_the_gpu_file_relies_on():
+    import small_cases as sc
+    # the omic step: no unit of either layer within 4 worst-case summation bounds of SELU's kink (the share excused is 0), both
+    # SELU branches in both layers, both mask states in both layers of a train-mode case, negative pre-activations above -4
+    for c in ab.accepted(ab.MAXSTEP, ab.maxstep_rule):
+        out, bar, facts = sc.maxstep_ref(c)
+        i = sc.maxstep_inputs(c)
+        assert facts["kink0"] >= 4 and facts["kink1"] >= 4, (c, facts["kink0"], facts["kink1"])
+        assert facts["branches"] == [True, True] and facts["min_pre"] > -4, c
+        assert facts["masks"] == ([True, True] if c.p_drop > 0 else [False, False]), c
+        t, cens = i["times"], i["c"]
+        if c.censor == "all":
+            assert cens.all() and out["loss"] == 0 and all(not out[k].any() for k in sc.MX_GRADS)
+        elif c.censor == "none":
+            assert not cens.any()
+        elif c.censor == "tied":
+            assert len(set(t)) < c.B and not cens.all()
+        elif c.censor == "last event":
+            assert int((cens == 0).sum()) == 1 and t[cens == 0][0] == t.max() and len(set(t)) == c.B
+        else:
+            assert len(set(t)) == c.B and (c.B < 3 or 0 < cens.sum() < c.B), c
+        if c.accumulate:
+            assert all(np.abs(i["prior"][k]).min() > 0 for k in sc.MX_GRADS)
+        if c.word:           # the masks of seed + word differ from those of the seed alone
+            assert (i["keep0"] != sc.maxstep_inputs(dataclasses.replace(c, word=0))["keep0"]).any()
+    # xreduce: the masks of the three sites differ pairwise, and each has both states
+    for c in ab.accepted(ab.XREDUCE, ab.xreduce_bwd_rule):
+        if c.drop_p > 0:
+            ks = sc.xreduce_inputs(c)["keep"]
+            assert all((ks[a] != ks[b]).any() for a in range(c.m) for b in range(a)) and all(k.any() and not k.all() for k in ks), c
+        out, _ = sc.xreduce_ref(c)
+        for t in range(c.m):      # the ReLUs the backward branches on: read off fp32 values that are what the kernel is given
+            assert (out["h32"][t] > 0).any() and np.abs(out[f"dv{t}"]).max() > 0, c
+    for c in ab.accepted(ab.KRON, ab.kron_rule):
+        if c.drop_p > 0:
+            k = sc.kron_inputs(c)["keep"]
+            assert k.any() and not k.all(), c
+    for c in ab.accepted(ab.DENSE_FWD, ab.dense_fwd_rule):
+        i = sc.dense_fwd_inputs(c)
+        if c.drop_kind:
+            assert i["keep"].any() and (c.B * c.N < 8 or not i["keep"].all()), c
+        if c.rows:                # rows draw different masks: row b is not row 0 of the plain form shifted
+            assert len(set(sc.dense_fwd_row_seeds(c))) == c.B
+            if c.drop_kind:
+                assert (i["keep"] != sc.gen.keep_mask(sc.SEED, sc.SITE, c.B, c.N, i["p"])).any(), c
+
+
+def test_tail_bars_cover_every_element():
+    import small_cases as sc
+    refs = [(ab.DENSE_FWD, ab.dense_fwd_rule, sc.dense_fwd_ref), (ab.GATE_MUL, ab.gate_mul_rule, sc.gate_mul_ref),
+            (ab.KRON, ab.kron_rule, sc.kron_ref), (ab.XREDUCE, ab.xreduce_bwd_rule, sc.xreduce_ref),
+            (ab.MAXSTEP, ab.maxstep_rule, lambda c: sc.maxstep_ref(c)[:2])]
+    for table, rule, ref in refs:
+        for c in ab.accepted(table, rule):
+            out, bar = ref(c)
+            for k, b in bar.items():
+                b = np.broadcast_to(np.asarray(b, np.float64), np.shape(out[k]))
+                assert np.isfinite(b).all() and (b >= 0).all(), (c, k)
+                if not (table is ab.MAXSTEP and c.censor in ("all", "last event")):      # exact zeros of censored rows: bar 0
+                    assert (b[np.asarray(out[k]) != 0] > 0).all(), (c, k)
+
+
+def test_tail_restatements_match_the_ports():
+    """The numpy references against oracle/torch_port.py through autograd, at the shipped sizes: the omic step (maxnet_forward,
+    cox_loss) at G = 36 and 186; xreduce at m = 2 and m = 3 through xfusion with encoder weights that pass the Kronecker product through; the
+    Kronecker product and its backward against the bmm chain xfusion uses."""
+    import torch
+    import small_cases as sc
+    from oracle import torch_port as tp
+    for c in (ab.MaxStep(4, 36, p_drop=0.25), ab.MaxStep(64, 186, p_drop=0.25), ab.MaxStep(65, 36), ab.MaxStep(16, 63, censor="tied")):
+        i = sc.maxstep_inputs(c)
+        sd = tp.to_torch(sc.maxstep_state_dict(i))
+        keeps = [sc.T(i["keep0"]), sc.T(i["keep1"])] if c.p_drop > 0 else None
+        risk = tp.maxnet_forward(sd, sc.T(i["x"]), nll=False, keeps=keeps)[0]
+        loss = tp.cox_loss(risk, i["times"], torch.as_tensor(i["c"]))
+        grads = tp.grads_of(loss, sd)
+        out, _, facts = sc.maxstep_ref(c)
+        assert np.abs(out["risk"] - risk.detach().numpy()).max() <= 1e-12 and abs(out["loss"] - float(loss.detach())) <= 1e-12
+        for k, name in zip(sc.MX_GRADS, ("fc_omic.0.0.weight", "fc_omic.0.0.bias", "fc_omic.1.0.weight", "fc_omic.1.0.bias",
+                                         "classifier.weight", "classifier.bias")):
+            want = grads[name].numpy()
+            assert np.abs(facts["pure"][k].reshape(want.shape) - want).max() <= 1e-12 * max(1.0, np.abs(want).max()), (c, k)
+    # xreduce at both shipped sizes (m = 2 and m = 3): encoder1 = I, encoder2 = [I | 0] hand xfusion's Kronecker product through,
+    # o_t is read off it where every other operand contributes its appended 1, and the loss weights those entries by d_o
+    for c in (ab.XReduce(2, 1, 256, 16, drop_p=0.25), ab.XReduce(3, 1, 256, 16, drop_p=0.25)):
+        i = sc.xreduce_inputs(c)
+        m, n = c.m, 17 ** c.m
+        sd = {}
+        for t in range(m):
+            for j, (w, b) in enumerate((("Wh", "bh"), ("Wz", "bz"), ("Wo", "bo"))):
+                sd[f"mm.reduce.{t}.{j}.0.weight"], sd[f"mm.reduce.{t}.{j}.0.bias"] = i[w][t], i[b][t]
+        sd = tp.to_torch(sd)
+        eye = torch.eye(n, dtype=torch.float64)
+        sd.update({"mm.encoder1.0.weight": eye, "mm.encoder1.0.bias": torch.zeros(n, dtype=torch.float64),
+                   "mm.encoder2.0.weight": torch.cat([eye, torch.zeros(n, m * 256, dtype=torch.float64)], 1),
+                   "mm.encoder2.0.bias": torch.zeros(n, dtype=torch.float64)})
+        vs = [sc.T(v).requires_grad_(True) for v in i["v"]]
+        masks = {f"o{t}": sc.T(i["keep"][t]) / (1 - c.drop_p) for t in range(m)}
+        full = tp.xfusion(sd, "mm", vs, masks).reshape((17,) * m)
+        out, _ = sc.xreduce_ref(c)
+        L = 0
+        for t in range(m):
+            o_t = full[tuple(slice(0, 16) if u == t else 16 for u in range(m))]
+            assert np.abs(o_t.detach().numpy() - out[f"o{t}"][0]).max() <= 1e-12, (c, t)
+            L = L + (o_t * sc.T(i["d_o"][t][0])).sum()
+        g = torch.autograd.grad(L, vs + [sd[f"mm.reduce.{t}.{j}.0.{w}"] for t in range(m) for j in range(3) for w in ("weight", "bias")])
+        names = [f"dv{t}" for t in range(m)] + [f"d{w}{t}" for t in range(m) for w in ("Wh", "bh", "Wz", "bz", "Wo", "bo")]
+        for k, want in zip(names, g):        # the backward reference starts from the forward rounded to fp32: 2^-24 relative apart
+            want = want.numpy()
+            assert np.abs(want).max() > 0 and np.abs(out[k].reshape(want.shape) - want).max() <= 1e-6 * max(1.0, np.abs(want).max()), (c, k)
+    for c in (ab.Kron(2, 16), ab.Kron(3, 16, B=3, drop_p=0.25)):
+        i = sc.kron_inputs(c)
+        os_ = [sc.T(o).requires_grad_(True) for o in i["o"]]
+        ext = [torch.cat((o, torch.ones(c.B, 1, dtype=o.dtype)), 1) for o in os_]
+        fus = ext[0]
+        for o in ext[1:]:
+            fus = torch.bmm(fus.unsqueeze(2), o.unsqueeze(1)).flatten(start_dim=1)
+        if c.drop_p > 0:
+            fus = fus * sc.T(i["keep"]) / (1 - c.drop_p)
+        out, _ = sc.kron_ref(c)
+        assert np.abs(out["out"] - fus.detach().numpy()).max() <= 1e-13
+        for t, want in enumerate(torch.autograd.grad((fus * sc.T(i["g"])).sum(), os_)):
+            assert np.abs(out[f"d{t}"] - want.numpy()).max() <= 1e-12, (c, t)
