@@ -279,6 +279,60 @@ int mmf_radio_infer_group(const mmf_amil_desc* desc, const mmf_bag_group* group,
                           void* workspace, size_t workspace_bytes, const mmf_surv_head* head,
                           const mmf_nll_target* target, float* M, float* A_raw, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Integrated-gradients patch attribution of the pathology head in one call: how much each patch of a slide contributes to
+ *   the predicted risk.  The reference computes it with captum (create_attributions.py:94-102: IntegratedGradients of
+ *   risk = -sum(S) from a zero baseline, n_steps = 20, reduced per patch by sum |attr|) through the captum methods of its
+ *   models (models/model_mm_attention_mil.py:246-301) -- n_steps forward and backward passes of the bag through autograd.
+ *   With baseline 0 the interpolated input is alpha_k x, so the projection is linear in alpha, u_k = alpha_k (x W1^T) + b1,
+ *   and the input gradient is linear in du: sum_k w_k dx_k = (sum_k w_k du_k) W1.  The two L-wide contractions run ONCE
+ *   per call and the weight gradients not at all; only the H-wide part (ReLU, gate, pooling, head, K-prep, K-dh) runs per
+ *   step, the steps of a window standing in as the bags of the grouped chain.  The chain:
+ *     1. U = x W1^T, one launch of the projection (no bias, no activation);
+ *     2. per window of steps: h[s N + i, :] = relu(alpha_s U[i, :] + b1) and its ReLU bits; the grouped gate forward,
+ *        per-step pooling and merge; the hazard head forward and the backward of risk over the [steps x H] embeddings;
+ *        K-prep and K-dh; Gacc[N x H] += sum_s w_s du[s N + i, :], in step order whatever the windows are;
+ *     3. P = Gacc W1 with an epilogue that multiplies by x in registers and reduces each row: attr = x * P.
+ *   No weight-gradient (TN) launch, no reduce list.
+ * desc: the stack, fp32, exact-fp32 GEMMs, gated or not, both head sizes; desc->N rows.  Eval mode: desc->p_h and p_att must
+ *   be 0 (with dropout the integrand would be random).  head: the stock hazard head -- Wk, bk, K <= 32 are read; logits,
+ *   hazards, S, Y_hat and risk are optional outputs (NULL: not written) and receive the head's values at alpha = 1, the
+ *   bag itself.  The target is risk = -sum_k S_k.
+ * ig->alpha / weight: HOST arrays of the quadrature's n_steps nodes and weights -- the caller supplies the rule, the library
+ *   knows none.  ig->window_steps: steps evaluated per grouped window; 0 lets the library choose; either is clamped to
+ *   what the row limits of the grouped chain admit (window_steps x N rows of H- and D-wide operands, as
+ *   mmf_amil_nll_step_group's sum N).  alpha = 1 and alpha = 0 ride along as two more forward steps of weight 0.
+ * Outputs (device): row_sum [N] = sum_l attr[i, l]; row_abs [N] = sum_l |attr[i, l]|; attr [N x L] or NULL -- with NULL
+ *   the N x L product never reaches memory; risk_x [1], risk_base [1]: the risk at alpha = 1 and at alpha = 0 (with row_sum
+ *   they give the completeness gap); step_risk [n_steps]: the risk at each node.
+ * Every sum is taken in a fixed order and there are no float atomics: two calls agree bit for bit.  No workgroup waits for
+ *   another; the call allocates nothing and keeps no state.
+ * Returns, before any launch: MMF_ERR_ARG for a null pointer, p_h or p_att != 0, gemm = MMF_GEMM_BF16X3, n_steps outside
+ *   1..MMF_GROUP_MAX or window_steps < 0 (a bf16 bag has no entry here: the call takes fp32 rows only); MMF_ERR_SHAPE,
+ *   MMF_ERR_ALIGN and MMF_ERR_WORKSPACE as the one-bag entry points, MMF_ERR_SHAPE also for a head with K > 32 and a bag
+ *   too long for one step to be a window.
+ * mmf_amil_ig_workspace_bytes: the workspace of that call, or 0 for n_steps or window_steps out of range or a bag too long.
+ *   It does not shrink as window_steps grows.
+ * Out of scope: the radio and multimodal heads; non-zero baselines (they need a second projection, U' + alpha (U - U'));
+ *   bf16 bags; targets other than risk.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct mmf_ig_desc {
+  int32_t n_steps;           /* quadrature nodes, 1 .. MMF_GROUP_MAX */
+  const float* alpha;        /* HOST [n_steps] nodes in [0, 1] */
+  const float* weight;       /* HOST [n_steps] weights */
+  int32_t window_steps;      /* steps per grouped window; 0: the library chooses */
+  float* row_sum;            /* [N] out */
+  float* row_abs;            /* [N] out */
+  float* attr;               /* [N x L] out, or NULL */
+  float* risk_x;             /* [1] out */
+  float* risk_base;          /* [1] out */
+  float* step_risk;          /* [n_steps] out */
+} mmf_ig_desc;
+size_t mmf_amil_ig_workspace_bytes(int64_t N, int32_t L, int32_t H, int32_t D, int32_t gated, int32_t n_steps,
+                                   int32_t window_steps);
+int mmf_amil_ig(const mmf_amil_desc* desc, const float* x, void* workspace, size_t workspace_bytes,
+                const mmf_surv_head* head, const mmf_ig_desc* ig, void* stream);
+
 /* The hazard head's training step on a feature vector that is already on the device: what
  *   `hazards, S, Y_hat = head(classifier(feat)); loss = NLLSurvLoss(alpha)(hazards, S, Y, c); (loss * loss_scale).backward()`
  * computes between the embedding and the loss (models/model_mm_attention_mil.py:190-191 with fusion = 'concat': feat is the

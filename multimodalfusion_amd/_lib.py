@@ -56,6 +56,13 @@ class BagGroup(C.Structure):
     _fields_ = [("G", C.c_int32), ("offsets", C.POINTER(C.c_int64)), ("seeds", C.POINTER(C.c_uint32))]
 
 
+class IgDesc(C.Structure):
+    """struct mmf_ig_desc (include/mmf_amil.h): alpha / weight are host arrays, the outputs device pointers."""
+    _fields_ = [("n_steps", C.c_int32), ("alpha", C.POINTER(C.c_float)), ("weight", C.POINTER(C.c_float)),
+                ("window_steps", C.c_int32), ("row_sum", C.c_void_p), ("row_abs", C.c_void_p), ("attr", C.c_void_p),
+                ("risk_x", C.c_void_p), ("risk_base", C.c_void_p), ("step_risk", C.c_void_p)]
+
+
 class RadioReduce(C.Structure):
     """mmf_radio_reduce: the radiology head's reduce_dim in a grouped step (x: host array of nseg device pointers)."""
     _fields_ = [("x", C.POINTER(C.c_void_p)), ("nseg", C.c_int32), ("kseg", C.c_int32), ("W", c_f32p),
@@ -153,6 +160,10 @@ SYMBOLS = {
     "mmf_amil_infer_group": (C.c_int, [C.POINTER(AmilDesc), C.POINTER(BagGroup), C.c_void_p, C.c_int32, C.c_void_p,
                                        C.c_size_t, C.POINTER(SurvHead), C.POINTER(NllTarget), C.c_void_p, C.c_void_p,
                                        C.c_void_p]),
+    "mmf_amil_ig_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                                  C.c_int32]),
+    "mmf_amil_ig": (C.c_int, [C.POINTER(AmilDesc), C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(SurvHead),
+                              C.POINTER(IgDesc), C.c_void_p]),
     "mmf_radio_group_infer_workspace_bytes": (C.c_size_t, [C.POINTER(C.c_int64), C.c_int32, C.c_int32, C.c_int32,
                                                             C.c_int32, C.c_int32, C.c_int32]),
     "mmf_radio_infer_group": (C.c_int, [C.POINTER(AmilDesc), C.POINTER(BagGroup), C.POINTER(RadioReduce), C.c_void_p,

@@ -750,7 +750,10 @@ __global__ __launch_bounds__(T::NT) void bwd_dh_kernel(BwdDhParams p) {
 // =============================================================================================
 // K-nn : plain NN GEMM
 // =============================================================================================
-template <class T>
+// ATTR (mmf_amil_ig's attribution GEMM, P = Gacc . W1): the epilogue multiplies the product by mulx -- the bag -- in
+// registers and reduces each row's 32 columns of a block over the 8 lanes that hold them (xor butterfly: the same sum in
+// every lane); the product itself is stored only when C is given.  N % 32 == 0 there, so a block is inside or outside.
+template <class T, bool ATTR = false>
 __global__ __launch_bounds__(T::NT) void gemm_nn_kernel(NnParams p) {
   extern __shared__ __align__(16) float lds[];
   int mt, nt;
@@ -765,12 +768,70 @@ __global__ __launch_bounds__(T::NT) void gemm_nn_kernel(NnParams p) {
   epilogue_rows<T>(acc, lds, [&](int mb, int nb, int r, int c, const float4 (&v)[4]) {
     const int col = col0 + c;
     if (col >= p.N) return;
+    if constexpr (ATTR) {
+      float4 xv[4];
 #pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      const int row = row0 + r + 8 * t;
-      if (row < p.M) st4(p.C + (size_t)row * p.ldc + col, v[t]);
+      for (int t = 0; t < 4; ++t) {            // every load before the first store
+        const int row = row0 + r + 8 * t;
+        xv[t] = row < p.M ? ld4(p.mulx + (size_t)row * p.ldx + col) : zero4();
+      }
+      const size_t cb = (size_t)(col >> 5);
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+        const int row = row0 + r + 8 * t;
+        const float4 a = make_float4(v[t].x * xv[t].x, v[t].y * xv[t].y, v[t].z * xv[t].z, v[t].w * xv[t].w);
+        float s = (a.x + a.y) + (a.z + a.w);
+        float m = (fabsf(a.x) + fabsf(a.y)) + (fabsf(a.z) + fabsf(a.w));
+#pragma unroll
+        for (int o = 1; o < 8; o <<= 1) {
+          s += __shfl_xor(s, o, 64);
+          m += __shfl_xor(m, o, 64);
+        }
+        if (row < p.M) {
+          if ((threadIdx.x & 7) == 0) {
+            p.rs_part[cb * (size_t)p.M + row] = s;
+            p.ra_part[cb * (size_t)p.M + row] = m;
+          }
+          if (p.C) st4(p.C + (size_t)row * p.ldc + col, a);
+        }
+      }
+    } else {
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+        const int row = row0 + r + 8 * t;
+        if (row < p.M) st4(p.C + (size_t)row * p.ldc + col, v[t]);
+      }
     }
   });
+}
+
+// row_sum[i] / row_abs[i] = the row's per-block partials of the attribution GEMM, added in column-block order
+__global__ __launch_bounds__(256) void ig_rows_kernel(const float* rs_part, const float* ra_part, int64_t M, int nblk,
+                                                      float* row_sum, float* row_abs) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= M) return;
+  float s = 0.f, m = 0.f;
+  for (int b = 0; b < nblk; ++b) {
+    s += rs_part[(size_t)b * M + i];
+    m += ra_part[(size_t)b * M + i];
+  }
+  row_sum[i] = s;
+  row_abs[i] = m;
+}
+
+// Gacc[i, :] (+)= sum_s w_s du[s * N + i, :]: one thread per four columns, the steps in order -- the same additions in
+// the same order however the call's steps were cut into windows
+__global__ __launch_bounds__(256) void ig_fold_kernel(IgFoldParams p) {
+  const size_t n4 = (size_t)p.N * p.H / 4, i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n4) return;
+  float4 acc = p.first ? zero4() : ld4(p.G + 4 * i);
+  const size_t stride = (size_t)p.N * p.H;
+  for (int s = 0; s < p.st.S; ++s) {
+    const float4 d = ld4(p.du + s * stride + 4 * i);
+    const float w = p.st.w[s];
+    acc.x = fmaf(w, d.x, acc.x); acc.y = fmaf(w, d.y, acc.y); acc.z = fmaf(w, d.z, acc.z); acc.w = fmaf(w, d.w, acc.w);
+  }
+  st4(p.G + 4 * i, acc);
 }
 
 // =============================================================================================
@@ -1526,6 +1587,40 @@ int launch_nn(NnParams p, hipStream_t st) {
   using T = Tile<64, 64, 2, 2, true, false>;
   p.mt_count = (int)((p.M + 63) / 64); p.nt_count = (p.N + 63) / 64;
   return launch_tiled<T>("gemm_nn_kernel", gemm_nn_kernel<T>, p, grid_for_tiles(p.mt_count, p.nt_count), st);
+}
+
+// launch_nn's tile plan with the attribution epilogue, then the rows kernel over its partials
+int launch_nn_attr(NnParams p, float* row_sum, float* row_abs, hipStream_t st) {
+  if (!p.mulx || !p.rs_part || !p.ra_part || !row_sum || !row_abs) return MMF_ERR_ARG;
+  if (p.K % KC != 0 || p.lda % 4 != 0 || p.ldb % 4 != 0 || p.N % 32 != 0 || p.ldx % 4 != 0 || (p.C && p.ldc % 4 != 0))
+    return MMF_ERR_SHAPE;
+  if (p.M <= 0) return MMF_OK;
+  const int ntn = (p.N + 127) / 128;
+  if ((p.M / 128) * ntn >= 256) {
+    using T = Tile<128, 128, 2, 2, true, false>;
+    p.mt_count = (int)((p.M + 127) / 128); p.nt_count = ntn;
+    if (int e = launch_tiled<T>("gemm_nn_attr_kernel", gemm_nn_kernel<T, true>, p, grid_for_tiles(p.mt_count, p.nt_count), st))
+      return e;
+  } else {
+    using T = Tile<64, 64, 2, 2, true, false>;
+    p.mt_count = (int)((p.M + 63) / 64); p.nt_count = (p.N + 63) / 64;
+    if (int e = launch_tiled<T>("gemm_nn_attr_kernel", gemm_nn_kernel<T, true>, p, grid_for_tiles(p.mt_count, p.nt_count), st))
+      return e;
+  }
+  ProfScope ps("ig_rows_kernel", st);
+  hipLaunchKernelGGL(ig_rows_kernel, dim3((unsigned)((p.M + 255) / 256)), dim3(256), 0, st, p.rs_part, p.ra_part, p.M,
+                     p.N / 32, row_sum, row_abs);
+  return hipGetLastError() == hipSuccess ? MMF_OK : MMF_ERR_LAUNCH;
+}
+
+int launch_ig_fold(const IgFoldParams& p, hipStream_t st) {
+  if (!p.du || !p.G) return MMF_ERR_ARG;
+  if (p.H % 4 != 0 || p.N < 1 || p.st.S < 0 || p.st.S > GROUP_MAX) return MMF_ERR_SHAPE;
+  if (p.st.S == 0 && !p.first) return MMF_OK;
+  const size_t n4 = (size_t)p.N * p.H / 4;
+  ProfScope ps("ig_fold_kernel", st);
+  hipLaunchKernelGGL(ig_fold_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, p);
+  return hipGetLastError() == hipSuccess ? MMF_OK : MMF_ERR_LAUNCH;
 }
 
 // Tile / split plan of the TN GEMM.  256x256 tiles (8 waves, one workgroup per CU): 65 FLOP per operand byte

@@ -1324,4 +1324,123 @@ int launch_group_infer_tail(PoolParams p, const SegTable& s, hipStream_t st) {
   return hipGetLastError() == hipSuccess ? MMF_OK : MMF_ERR_LAUNCH;
 }
 
+// ---- integrated gradients (mmf_amil_ig) -------------------------------------------------------------------------------
+// With a zero baseline the projection is linear in the interpolation factor: relu(alpha_s x W1^T + b1) = relu(alpha_s U +
+// b1), U = x W1^T computed once.  One wave per 16 x 32 block of the window's [S * N x H] rows: lane 8 rr + c4 takes rows
+// rr, rr + 8 and columns 4 c4 .. 4 c4 + 3, K-lin's epilogue lanes, so the ballots are LinearParams::relu_bits words.
+__global__ __launch_bounds__(256) void ig_expand_kernel(IgExpandParams p) {
+  __shared__ float al[GROUP_MAX];
+  for (int i = threadIdx.x; i < p.st.S; i += 256) al[i] = p.st.alpha[i];
+  __syncthreads();
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int rr = lane >> 3, c4 = lane & 7;
+  const int64_t R = (int64_t)p.st.S * p.N, rb16 = blockIdx.x;
+  const int cbn = p.H >> 5;
+  bool ok[2];
+  float a[2];
+  const float* u[2];
+  float* y[2];
+#pragma unroll
+  for (int t = 0; t < 2; ++t) {
+    const int64_t row = rb16 * 16 + rr + 8 * t;
+    ok[t] = row < R;
+    const int s = ok[t] ? (int)(row / p.N) : 0;
+    a[t] = al[s];
+    u[t] = p.U + (size_t)(row - (int64_t)s * p.N) * p.H;
+    y[t] = p.h + (size_t)row * p.H;
+  }
+  for (int cb = wave; cb < cbn; cb += 4) {
+    const int col = cb * 32 + 4 * c4;
+    const float4 b4 = ld4(p.b1 + col);
+    unsigned long long mine = 0ull;
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      float v[4] = {0.f, 0.f, 0.f, 0.f};
+      if (ok[t]) {
+        const float4 u4 = ld4(u[t] + col);
+        v[0] = fmaxf(fmaf(a[t], u4.x, b4.x), 0.f); v[1] = fmaxf(fmaf(a[t], u4.y, b4.y), 0.f);
+        v[2] = fmaxf(fmaf(a[t], u4.z, b4.z), 0.f); v[3] = fmaxf(fmaf(a[t], u4.w, b4.w), 0.f);
+        st4(y[t] + col, make_float4(v[0], v[1], v[2], v[3]));
+      }
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const unsigned long long bal = __ballot(ok[t] && v[e] > 0.f);
+        if (lane == 4 * t + e) mine = bal;
+      }
+    }
+    if (lane < 8) p.relu_bits[((size_t)rb16 * cbn + cb) * 8 + lane] = mine;
+  }
+}
+
+int launch_ig_expand(const IgExpandParams& p, hipStream_t st) {
+  if (!p.U || !p.b1 || !p.h || !p.relu_bits) return MMF_ERR_ARG;
+  if (p.H % 32 != 0 || p.N < 1 || p.st.S < 1 || p.st.S > GROUP_MAX) return MMF_ERR_SHAPE;
+  const int64_t R = (int64_t)p.st.S * p.N;
+  ProfScope ps("ig_expand_kernel", st);
+  hipLaunchKernelGGL(ig_expand_kernel, dim3((unsigned)((R + 15) / 16)), dim3(256), 0, st, p);
+  return hipGetLastError() == hipSuccess ? MMF_OK : MMF_ERR_LAUNCH;
+}
+
+// The hazard head of models/model_attention_mil_path.py:58-61 on a step's pooled embedding and the gradient of
+// risk = -sum_k S_k back to it.  S_k = prod_{i <= k} (1 - h_i), so d risk / d h_j = sum_{k >= j} prod_{i <= k, i != j}
+// (1 - h_i): built from the products themselves, never divided by 1 - h_j.
+__global__ __launch_bounds__(256) void ig_head_kernel(IgHeadParams p) {
+  __shared__ float lg[32], hz[32], sv[32], dl[32];
+  const int s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int H = p.H, K = p.K;
+  const float* M = p.M + (size_t)s * H;
+  for (int k = wave; k < K; k += 4) {
+    float t = 0.f;
+    for (int c = lane; c < H; c += 64) t += p.Wk[(size_t)k * H + c] * M[c];
+    t = wave_sum(t);
+    if (lane == 0) lg[k] = t + p.bk[k];
+  }
+  __syncthreads();
+  if (tid == 0) {
+    float surv = 1.f, risk = 0.f;
+    int best = 0;
+    for (int k = 0; k < K; ++k) {
+      const float h = 1.0f / (1.0f + __expf(-lg[k]));
+      hz[k] = h;
+      surv *= 1.0f - h;
+      sv[k] = surv;
+      risk -= surv;
+      if (lg[k] > lg[best]) best = k;
+    }
+    float pre = 1.f;                       // prod_{i < j} (1 - h_i)
+    for (int j = 0; j < K; ++j) {
+      float run = pre, g = pre;
+      for (int k = j + 1; k < K; ++k) { run *= 1.0f - hz[k]; g += run; }
+      dl[j] = g * hz[j] * (1.0f - hz[j]);
+      pre *= 1.0f - hz[j];
+    }
+    const int q = p.step0 + s;
+    if (q < p.n_steps) p.step_risk[q] = risk;
+    else if (q == p.n_steps) {
+      p.risk_x[0] = risk;
+      if (p.risk) p.risk[0] = risk;
+      if (p.Y_hat) p.Y_hat[0] = best;
+      for (int k = 0; k < K; ++k) {
+        if (p.logits) p.logits[k] = lg[k];
+        if (p.hazards) p.hazards[k] = hz[k];
+        if (p.S) p.S[k] = sv[k];
+      }
+    } else p.risk_base[0] = risk;
+  }
+  __syncthreads();
+  for (int c = tid; c < H; c += 256) {
+    float t = 0.f;
+    for (int j = 0; j < K; ++j) t += dl[j] * p.Wk[(size_t)j * H + c];
+    p.dM[(size_t)s * H + c] = t;
+  }
+}
+
+int launch_ig_head(const IgHeadParams& p, int S, hipStream_t st) {
+  if (!p.M || !p.Wk || !p.bk || !p.dM || !p.step_risk || !p.risk_x || !p.risk_base) return MMF_ERR_ARG;
+  if (p.K < 1 || p.K > 32 || p.H < 1 || S < 1 || S > GROUP_MAX) return MMF_ERR_SHAPE;
+  ProfScope ps("ig_head_kernel", st);
+  hipLaunchKernelGGL(ig_head_kernel, dim3(S), dim3(256), 0, st, p);
+  return hipGetLastError() == hipSuccess ? MMF_OK : MMF_ERR_LAUNCH;
+}
+
 }  // namespace mmf

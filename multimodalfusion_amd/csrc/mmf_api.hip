@@ -1339,6 +1339,187 @@ int mmf_radio_infer_group(const mmf_amil_desc* d, const mmf_bag_group* group, co
   return group_infer_chain(d, s, r.xr, r.gw, tl, M, A_raw, st);
 }
 
+// ---- integrated gradients of the pathology head: the quadrature's steps as the bags of grouped windows ----------------
+namespace mmf {
+// The call evaluates n_steps + 2 steps: the quadrature's, then alpha = 1 and alpha = 0 with weight 0 (risk_x, risk_base).
+// A window is `steps` of them over the bag's N rows, steps * N rows of H- and D-wide operands: the grouped chain's row
+// limits (check_desc on sum N, without the L-wide bag, and group_plan's pooling groups).
+static int64_t ig_row_limit(int H, int D) {
+  const int64_t hd = H > D ? H : D, wide = H > 2 * D ? H : 2 * D;
+  int64_t lim = (((int64_t)1 << 32) - 1) / hd;
+  const int64_t bytes = (((int64_t)1 << 31) - 1) / (4 * wide), pool = (int64_t)GROUP_POOL_GROUPS * POOL_MAX_ROWS;
+  if (bytes < lim) lim = bytes;
+  return pool < lim ? pool : lim;
+}
+// steps per window: the caller's, or -- 0 -- windows of at most 2^18 rows (enough to fill the chip; the workspace stays
+// near 1 GB for the small head) cut evenly; clamped to the row limit.  0: not even one step fits.
+static int ig_window_steps(int64_t N, int H, int D, int total, int window_steps) {
+  if (N < 1 || H < 1 || D < 1) return 0;
+  int64_t smax = ig_row_limit(H, D) / N;
+  if (smax < 1) return 0;
+  if (smax > GROUP_MAX) smax = GROUP_MAX;
+  if (smax > total) smax = total;
+  if (window_steps > 0) return (int)(window_steps < smax ? window_steps : smax);
+  int64_t s = ((int64_t)1 << 18) / N;
+  if (s < 1) s = 1;
+  if (s > smax) s = smax;
+  const int64_t nwin = (total + s - 1) / s;
+  return (int)((total + nwin - 1) / nwin);
+}
+
+struct IgWs {
+  AmilWs w;                  // the window's rows: h, relu_bits, a, b, s_part, p, ds, dbc_part, du (nothing else is set)
+  float *U, *G;              // [N x H]: x . W1^T, and the folded sum_s w_s du_s
+  float *rs_part, *ra_part;  // [(L / 32) x N]: the attribution GEMM's per-block row sums
+  float* kpart;              // the projection's K-split partial tiles, or null
+  float *M, *dM, *stats, *partials, *A_raw;
+  uint32_t *ridx_h, *ridx_d;
+  int* bag;
+  size_t bytes;
+};
+static IgWs carve_ig(Carver& c, int64_t N, int L, int H, int D, int gated, int steps) {
+  IgWs g{};
+  auto take = [&](size_t n) { return c.take<float>(n); };
+  const int64_t R = N * steps;
+  g.U = take((size_t)N * H);
+  g.G = take((size_t)N * H);
+  g.rs_part = take((size_t)(L / 32) * N);
+  g.ra_part = take((size_t)(L / 32) * N);
+  {
+    const size_t kf = linear_ksplit_floats(N, H, L, 1, L);
+    g.kpart = kf ? take(kf) : nullptr;
+  }
+  AmilWs& w = g.w;
+  w.parts = gate_parts(D, gated, R);
+  w.h = take((size_t)R * H);
+  w.relu_bits = c.take<unsigned long long>((size_t)((R + 15) / 16 + 2) * (H / 32) * 8);
+  w.a = take((size_t)R * D);
+  w.b = take(gated ? (size_t)R * D : 0);
+  w.s_part = take((size_t)w.parts * R);
+  w.p = take((size_t)R);
+  w.ds = take((size_t)R);
+  w.dbc_part = take(PREP_GROUPS);
+  w.du = take((size_t)R * H);
+  g.M = take((size_t)steps * H);
+  g.dM = take((size_t)steps * H);
+  g.stats = take((size_t)2 * steps);
+  g.partials = take((size_t)(GROUP_POOL_GROUPS + 2 * GROUP_MAX) * (2 + H));   // sum_s ceil(N / rpg) <= R / rpg + S
+  g.A_raw = take((size_t)R);
+  g.ridx_h = c.take<uint32_t>((size_t)R);
+  g.ridx_d = c.take<uint32_t>((size_t)R);
+  g.bag = c.take<int>((size_t)R);
+  g.bytes = c.off;
+  return g;
+}
+
+// one window: steps q0 .. q0 + S - 1 of the call (alpha, weight: the call's n_steps + 2), the first `nfold` of them folded
+static int ig_window(const mmf_amil_desc* d, const IgWs& g, const float* alpha, const float* weight, int q0, int S,
+                     int nfold, bool first, IgHeadParams hp, hipStream_t st) {
+  const int64_t N = d->N;
+  mmf_amil_desc dw = *d;                  // the window as a bag of S * N rows
+  dw.N = N * S;
+  int64_t offsets[GROUP_MAX + 1];
+  for (int s = 0; s <= S; ++s) offsets[s] = s * N;
+  SegTable seg;
+  if (int e = group_plan(offsets, S, seg)) return e;
+  if (seg.gbeg[S] > GROUP_POOL_GROUPS + 2 * GROUP_MAX) return MMF_ERR_SHAPE;
+  const AmilWs& w = g.w;
+
+  IgExpandParams ep{};
+  ep.U = g.U; ep.b1 = d->b1; ep.h = w.h; ep.relu_bits = w.relu_bits; ep.N = N; ep.H = d->H;
+  ep.st.S = S;
+  for (int s = 0; s < S; ++s) { ep.st.alpha[s] = alpha[q0 + s]; ep.st.w[s] = weight[q0 + s]; }
+  if (int e = launch_ig_expand(ep, st)) return e;
+
+  GroupRowsParams rp{};
+  rp.s = seg; rp.H = d->H; rp.D = d->D; rp.ridx_h = g.ridx_h; rp.ridx_d = g.ridx_d; rp.bag = g.bag;
+  if (int e = launch_group_rows(rp, st)) return e;
+
+  GateFwdParams gp = stack_gate_fwd(&dw, w, 0);
+  gp.seg_ridx = g.ridx_d;
+  if (int e = launch_gate_fwd_seg(gp, st)) return e;
+
+  PoolParams pp = stack_pool(&dw, w, g.A_raw);
+  pp.partials = g.partials; pp.M = g.M; pp.stats = g.stats;
+  if (int e = launch_group_pool_partial(pp, seg, st)) return e;
+  if (int e = launch_group_merge(pp, seg, d->H, g.M, st)) return e;
+
+  hp.M = g.M; hp.dM = g.dM; hp.step0 = q0;
+  if (int e = launch_ig_head(hp, S, st)) return e;
+
+  const BwdPrepParams bp = stack_prep(&dw, w, g.A_raw, g.stats, g.M, g.dM, nullptr);
+  if (int e = launch_group_bwd_prep(bp, g.bag, st)) return e;
+  const GateBwdCtx gc = gate_bwd_ctx(&dw, w.a, w.b, w.ds, 0);
+  BwdDhParams dp = stack_dh(&dw, w, gc, g.dM);
+  dp.seg_ridx = g.ridx_d; dp.seg_bag = g.bag;
+  if (int e = launch_bwd_dh_seg(dp, st)) return e;
+
+  IgFoldParams fp{};
+  fp.du = w.du; fp.G = g.G; fp.N = N; fp.H = d->H; fp.first = first ? 1 : 0;
+  fp.st = ep.st; fp.st.S = nfold;
+  return launch_ig_fold(fp, st);
+}
+}  // namespace mmf
+
+size_t mmf_amil_ig_workspace_bytes(int64_t N, int32_t L, int32_t H, int32_t D, int32_t gated, int32_t n_steps,
+                                   int32_t window_steps) {
+  if (n_steps < 1 || n_steps > GROUP_MAX || window_steps < 0 || L < 32 || H < 32) return 0;
+  const int steps = ig_window_steps(N, H, D, n_steps + 2, window_steps);
+  if (steps < 1) return 0;
+  Carver c;
+  return carve_ig(c, N, L, H, D, gated, steps).bytes;
+}
+
+int mmf_amil_ig(const mmf_amil_desc* d, const float* x, void* workspace, size_t workspace_bytes,
+                const mmf_surv_head* head, const mmf_ig_desc* ig, void* stream) {
+  if (!d || !ig || !head) return MMF_ERR_ARG;
+  if (d->gemm != MMF_GEMM_F32 || d->p_h != 0.f || d->p_att != 0.f) return MMF_ERR_ARG;
+  if (ig->n_steps < 1 || ig->n_steps > GROUP_MAX || ig->window_steps < 0 || !ig->alpha || !ig->weight) return MMF_ERR_ARG;
+  if (!ig->row_sum || !ig->row_abs || !ig->risk_x || !ig->risk_base || !ig->step_risk) return MMF_ERR_ARG;
+  if (!head->Wk || !head->bk) return MMF_ERR_ARG;
+  if (int e = check_desc(d)) return e;
+  if (head->K < 1 || head->K > 32) return MMF_ERR_SHAPE;
+  const int total = ig->n_steps + 2;
+  const int steps = ig_window_steps(d->N, d->H, d->D, total, ig->window_steps);
+  if (steps < 1) return MMF_ERR_SHAPE;
+  if (int e = check_operands(d, x, workspace, ig->row_sum, false)) return e;
+  if (ig->attr && !aligned16(ig->attr)) return MMF_ERR_ALIGN;
+  Carver c(workspace);
+  const IgWs g = carve_ig(c, d->N, d->L, d->H, d->D, d->gated, steps);
+  if (g.bytes > workspace_bytes) return MMF_ERR_WORKSPACE;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  TraceScope ts(d->trace);
+
+  float alpha[GROUP_MAX + 2], weight[GROUP_MAX + 2];
+  for (int q = 0; q < ig->n_steps; ++q) { alpha[q] = ig->alpha[q]; weight[q] = ig->weight[q]; }
+  alpha[ig->n_steps] = 1.f; alpha[ig->n_steps + 1] = 0.f;
+  weight[ig->n_steps] = weight[ig->n_steps + 1] = 0.f;
+
+  {   // U = x . W1^T: the stack's projection without bias, activation or bits
+    AmilWs wp{};
+    wp.h = g.U; wp.kpart = g.kpart;
+    LinearParams lp = stack_linear(d, wp, x, 0);
+    lp.bias = nullptr; lp.act = ACT_NONE; lp.drop_p = 0.f; lp.seed_dev = nullptr;
+    if (int e = launch_linear(lp, st)) return e;
+  }
+  IgHeadParams hp{};
+  hp.Wk = head->Wk; hp.bk = head->bk; hp.K = head->K; hp.H = d->H; hp.n_steps = ig->n_steps;
+  hp.step_risk = ig->step_risk; hp.risk_x = ig->risk_x; hp.risk_base = ig->risk_base;
+  hp.logits = head->logits; hp.hazards = head->hazards; hp.S = head->S; hp.risk = head->risk; hp.Y_hat = head->Y_hat;
+  for (int q0 = 0; q0 < total; q0 += steps) {
+    const int S = total - q0 < steps ? total - q0 : steps;
+    int nfold = ig->n_steps - q0;                    // the two riders carry weight 0: they are not folded
+    if (nfold > S) nfold = S;
+    if (nfold < 0) nfold = 0;
+    if (int e = ig_window(d, g, alpha, weight, q0, S, nfold, q0 == 0, hp, st)) return e;
+  }
+  NnParams np{};                                     // attr = x * (Gacc . W1), and its row sums
+  np.A = g.G; np.lda = d->H; np.B = d->W1; np.ldb = d->L; np.C = ig->attr; np.ldc = d->L;
+  np.M = d->N; np.N = d->L; np.K = d->H;
+  np.mulx = x; np.ldx = d->L; np.rs_part = g.rs_part; np.ra_part = g.ra_part;
+  return launch_nn_attr(np, ig->row_sum, ig->row_abs, st);
+}
+
 int mmf_surv_head_nll_step(const float* feat, int32_t F, const mmf_surv_head* head, const mmf_nll_target* target,
                            float* dfeat, void* stream) {
   if (!feat || !target || !dfeat) return MMF_ERR_ARG;

@@ -235,6 +235,11 @@ struct NnParams {          // C[M x N] = A[M x K] . B[K x N]   (plain; radio: dh
   int64_t M;
   int N, K;
   int mt_count, nt_count;
+  // attribution epilogue (launch_nn_attr, mmf_amil_ig): the product is multiplied by mulx [M x N] (row pitch ldx) in
+  // registers; C may then be null (the product never reaches memory); per row and 32-column block the sum and the sum of
+  // absolute values of the products go to rs_part / ra_part [(N / 32) x M], for ig_rows_kernel to add in block order
+  const float* mulx; int ldx;
+  float *rs_part, *ra_part;
 };
 
 struct ReduceSeg { const float* in; float* out; int len; int nsplit; size_t stride; int block_begin; int tall; };
@@ -305,6 +310,42 @@ int launch_surv_head_group(PoolParams p, int ldf, int G, hipStream_t st);
 // row g of s.n dense [G x width] buffers (sum width = p.H <= 1024); p.M is null, p.tail as in launch_group_infer_tail
 struct HeadSegs { const float* x[3]; int width[3]; int n; };
 int launch_surv_head_infer_group(PoolParams p, const HeadSegs& s, int G, hipStream_t st);
+
+// ---- integrated gradients of the pathology head (mmf_amil_ig): the steps of a window stand in as its bags ------------
+// step s of the window: interpolation factor alpha[s] and quadrature weight w[s] (kernel arguments: no device table)
+struct IgSteps { int S; float alpha[GROUP_MAX]; float w[GROUP_MAX]; };
+// h[s * N + i, :] = relu(alpha_s * U[i, :] + b1) and its bits (LinearParams::relu_bits' layout) over the window's S * N rows
+struct IgExpandParams {
+  const float* U;            // [N x H] = x . W1^T, no bias
+  const float* b1;           // [H]
+  float* h;                  // [S * N x H]
+  unsigned long long* relu_bits;
+  int64_t N;
+  int H;
+  IgSteps st;
+};
+int launch_ig_expand(const IgExpandParams& p, hipStream_t st);
+// The hazard head forward and the backward of risk = -sum_k S_k, one workgroup per step of the window: M [S x H] -> dM
+// [S x H] = d risk / d M_s, and the risk where the step's place in the call says -- steps 0 .. n_steps - 1 of the call
+// are the quadrature's (step_risk), step n_steps is alpha = 1 (risk_x and the optional head outputs), n_steps + 1 alpha = 0
+struct IgHeadParams {
+  const float* M;
+  const float *Wk, *bk;
+  int K, H;
+  float* dM;
+  int step0, n_steps;        // the window's first step in the call, and the call's quadrature steps
+  float *step_risk, *risk_x, *risk_base;
+  float *logits, *hazards, *S, *risk;   // [K], [K], [K], [1] at alpha = 1, each may be null
+  int64_t* Y_hat;                       // [1] or null
+};
+int launch_ig_head(const IgHeadParams& p, int S, hipStream_t st);
+// G[i, :] (first: =, else +=) sum_s w[s] * du[s * N + i, :] over the first st.S steps of the window, in step order
+struct IgFoldParams { const float* du; float* G; int64_t N; int H; int first; IgSteps st; };
+int launch_ig_fold(const IgFoldParams& p, hipStream_t st);
+// P = A . B times mulx, never stored unless p.C is given, and its per-row sums (NnParams' attribution fields), then
+// row_sum / row_abs [M] from the partials in column-block order: fixed order, no atomics
+int launch_nn_attr(NnParams p, float* row_sum, float* row_abs, hipStream_t st);
+
 int set_dyn_lds(const void* kern, int bytes);
 
 // Optional per-kernel timing with HIP events on the launch stream: records into the mmf_trace of the ABI call in

@@ -173,6 +173,52 @@ def infer_patient(model, features, bins=None, label=None, verbose=False):
     return Y_hat_model, risk, A_final
 
 
+def integrated_gradients_autograd(model, bag, alphas, weights):
+    """Integrated gradients of risk = -sum(S) from a zero baseline by the definition, one autograd pass per node: for each
+    (alpha_k, w_k) `model(path_features=(alpha_k * bag).requires_grad_())`, the gradient of the risk with respect to that
+    input, and attr = bag * sum_k w_k grad_k -- what captum's IntegratedGradients does around the reference's models
+    (create_attributions.py:94-102), and the route to attributions without model.integrated_gradients: n_steps training-
+    sized backward passes, weight gradients included.  The yardstick of the fused call (tools/ig_bench.py, the tests).
+    Returns (patch_attr [N], patch_abs [N], attr [N x L], risk, risk_baseline, step_risk [n_steps]) on the device."""
+    if model.training:
+        raise RuntimeError("integrated gradients are an eval-mode pass: call model.eval() first")
+    x = bag.to(_dev(model)).float()
+    acc = torch.zeros_like(x)
+    step_risk = []
+    for a, w in zip(alphas, weights):
+        xi = (x * float(a)).requires_grad_()
+        _, S, _, _ = model(path_features=xi)
+        risk = -S.sum()
+        (g,) = torch.autograd.grad(risk, xi)
+        acc.add_(g, alpha=float(w))
+        step_risk.append(risk.detach())
+    attr = acc * x
+    with torch.no_grad():
+        risk_x = -model(path_features=x)[1].sum()
+        risk_base = -model(path_features=torch.zeros_like(x))[1].sum()
+    return attr.sum(1), attr.abs().sum(1), attr, risk_x, risk_base, torch.stack(step_risk)
+
+
+def attribute_patches(model, bag, n_steps=20, method="gausslegendre", return_full=False, window_steps=0, top_k=None):
+    """Patch attribution of one slide, create_attributions.py:94-102 for the pathology head: integrated gradients of the
+    risk from a zero baseline in one fused call (model.integrated_gradients; `patch_abs` is the reference's per-patch
+    sum |attr|).  The model is put in eval mode for the call and restored.  Returns the PatchAttribution, or with top_k the
+    pair (PatchAttribution, indices of the top_k patches by patch_abs, largest first)."""
+    if not isinstance(model, MIL_Attention_fc_surv_path):
+        raise NotImplementedError("attribute_patches serves the pathology head")
+    was_training = model.training
+    model.eval()
+    try:
+        out = model.integrated_gradients(bag.to(_dev(model)), n_steps=n_steps, method=method, return_full=return_full,
+                                         window_steps=window_steps)
+    finally:
+        model.train(was_training)
+    if top_k is None:
+        return out
+    k = min(int(top_k), int(out.patch_abs.numel()))
+    return out, torch.topk(out.patch_abs, k).indices
+
+
 # score_patch_batches(group=True): rows of one grouped scoring call per 256 hidden units.  Up to 128 projection tiles of 64 x
 # 64 (2,048 rows of the `small` head, 1,024 of `big`) a window of fp32 batches keeps the projection plan of a 512-patch
 # batch -- the same four-way K split, the same order of additions -- and with it every score bit for bit.

@@ -2,12 +2,17 @@
 (same class names, ctor signatures :13 / :46, forward(**kwargs) contract :50-72, state_dict keys)."""
 from __future__ import annotations
 
+from collections import namedtuple
+
 import torch
 import torch.nn as nn
 
 from ..utils.utils import initialize_weights
 from .model_modules import (AMIL_SIZES, amil_stack, amil_stack_head, amil_stack_infer_group, amil_stack_nll_step,
-                            amil_stack_nll_step_group, make_amil_stack)
+                            amil_stack_nll_step_group, make_amil_stack, stack_args)
+
+PatchAttribution = namedtuple("PatchAttribution", ["patch_attr", "patch_abs", "total", "total_abs", "risk", "risk_baseline",
+                                                   "delta", "step_risk", "attr"])
 
 
 class MIL_Attention_fc_path(nn.Module):
@@ -75,3 +80,32 @@ class MIL_Attention_fc_surv_path(MIL_Attention_fc_path):
             raise RuntimeError("forward_group is the eval-mode pass: call model.eval() first")
         return amil_stack_infer_group(self.attention_net_WSI, self.classifier, bags, labels, censors, alpha,
                                       return_features)
+
+    def integrated_gradients(self, path_features, n_steps=20, method="gausslegendre", return_full=False, window_steps=0):
+        """Integrated-gradients patch attribution of risk = -sum(S) from a zero baseline in ONE C-ABI call
+        (ops.amil_integrated_gradients) -- what the reference's create_attributions.py:94-102 gets from captum's
+        IntegratedGradients(n_steps=20) through n_steps autograd passes.  method: `gausslegendre` (captum's default),
+        `riemann_trapezoid` or `riemann_middle`; the nodes and weights are computed on the host in float64 and rounded once
+        to fp32 (ops.ig_quadrature).  window_steps: nodes per grouped window, 0 lets the library choose.
+        Returns PatchAttribution(patch_attr [N] = sum_l attr, patch_abs [N] = sum_l |attr| (the reference's reduction),
+        total, total_abs, risk, risk_baseline, delta = total - (risk - risk_baseline) (captum's convergence delta),
+        step_risk [n_steps], attr [N x L] when return_full else None).  Eval mode, fp32 bags, the stock head only."""
+        from .. import ops
+        from ..utils.core_utils import _stock_head
+        if self.training:
+            raise RuntimeError("integrated_gradients is an eval-mode pass (dropout would make the integrand random): "
+                               "call model.eval() first")
+        if _stock_head(self, step=False)[0] != "path":
+            raise NotImplementedError("integrated_gradients serves the stock pathology head only (no overridden forward, "
+                                      "no hooks, at most 32 classes)")
+        if path_features.dtype == torch.bfloat16:
+            raise NotImplementedError("integrated_gradients takes fp32 bags: the bf16 path has no input gradient")
+        gated, stack, _, _ = stack_args(self.attention_net_WSI, False)
+        alphas, weights = ops.ig_quadrature(method, n_steps)
+        with torch.no_grad():
+            rs, ra, attr, risk, base, step_risk = ops.amil_integrated_gradients(
+                path_features, stack, self.classifier.weight, self.classifier.bias, gated, alphas, weights,
+                want_attr=return_full, window_steps=window_steps)
+            total, total_abs = rs.sum(), ra.sum()
+            delta = total - (risk[0] - base[0])
+        return PatchAttribution(rs, ra, total, total_abs, risk[0], base[0], delta, step_risk, attr)

@@ -743,6 +743,70 @@ def amil_infer_group(x_cat, sizes, stack, gated, Wk=None, bk=None, Y=None, c=Non
     return hz, S, Y_hat, risk, A_list, M, loss
 
 
+IG_METHODS = ("gausslegendre", "riemann_trapezoid", "riemann_middle")
+
+
+def ig_quadrature(method, n_steps):
+    """(nodes, weights) of an n_steps-point rule on [0, 1], float64 numpy arrays: `gausslegendre` (captum's default, what
+    the reference's create_attributions.py gets), `riemann_trapezoid` (nodes linspace(0, 1, n), the end weights halved;
+    n >= 2) or `riemann_middle` (midpoints, equal weights).  The weights sum to 1."""
+    import numpy as np
+    n = int(n_steps)
+    if n < 1 or n > GROUP_MAX:
+        raise ValueError(f"n_steps must be in 1..{GROUP_MAX}, got {n_steps}")
+    if method == "gausslegendre":
+        t, w = np.polynomial.legendre.leggauss(n)
+        return 0.5 * (1.0 + t), 0.5 * w
+    if method == "riemann_trapezoid":
+        if n < 2:
+            raise ValueError("riemann_trapezoid needs n_steps >= 2")
+        w = np.full(n, 1.0 / (n - 1))
+        w[0] *= 0.5
+        w[-1] *= 0.5
+        return np.linspace(0.0, 1.0, n), w
+    if method == "riemann_middle":
+        return (np.arange(n) + 0.5) / n, np.full(n, 1.0 / n)
+    raise ValueError(f"method must be one of {IG_METHODS}, got {method!r}")
+
+
+def amil_integrated_gradients(x, stack, Wk, bk, gated, alphas, weights, want_attr=False, window_steps=0):
+    """Integrated gradients of risk = -sum(S) with respect to the bag x [N x L] (fp32), from a zero baseline, in ONE C-ABI
+    call (include/mmf_amil.h: mmf_amil_ig): the L-wide contractions run once, the H-wide part once per quadrature node.
+    alphas, weights: the rule's nodes and weights (host sequences, rounded once to fp32); window_steps: nodes per grouped
+    window (0: the library chooses).  Eval mode: no dropout.  Returns (row_sum [N], row_abs [N], attr [N x L] or None,
+    risk_x [1], risk_base [1], step_risk [n_steps])."""
+    import numpy as np
+    if x.dtype == torch.bfloat16:
+        raise NotImplementedError("integrated gradients take fp32 bags: the bf16 path has no input gradient")
+    x = _f32c(x)
+    if x.dim() != 2:
+        raise _lib.MmfError(f"bag must be [N x L], got {tuple(x.shape)}")
+    N, L = x.shape
+    stack, (Wk, bk), H, D = _stack_operands(stack, L, (Wk, bk), "bag", fused_head=True)
+    a = np.ascontiguousarray(np.asarray(alphas, dtype=np.float64).astype(np.float32))
+    w = np.ascontiguousarray(np.asarray(weights, dtype=np.float64).astype(np.float32))
+    if a.ndim != 1 or a.shape != w.shape or not 1 <= a.size <= GROUP_MAX:
+        raise _lib.MmfError(f"alphas / weights: two sequences of 1..{GROUP_MAX} values each")
+    n = int(a.size)
+    dev = x.device
+    d = _amil_desc(stack, N, L, H, D, gated, 0.0, 0.0, 0, None)
+    l = lib()
+    nbytes = l.mmf_amil_ig_workspace_bytes(N, L, H, D, d.gated, n, int(window_steps))
+    if nbytes == 0:
+        raise _lib.MmfError("mmf_amil_ig: n_steps, window_steps or the bag's size out of range")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    rows = torch.empty((2, N), dtype=torch.float32, device=dev)
+    attr = torch.empty((N, L), dtype=torch.float32, device=dev) if want_attr else None
+    risks = torch.empty(2 + n, dtype=torch.float32, device=dev)
+    sh = SurvHead(Wk=ptr(Wk), bk=ptr(bk), K=Wk.shape[0], logits=None, hazards=None, S=None, Y_hat=None, risk=None)
+    fp = C.POINTER(C.c_float)
+    ig = _lib.IgDesc(n_steps=n, alpha=a.ctypes.data_as(fp), weight=w.ctypes.data_as(fp), window_steps=int(window_steps),
+                     row_sum=ptr(rows[0]), row_abs=ptr(rows[1]), attr=ptr(attr), risk_x=ptr(risks[0:1]),
+                     risk_base=ptr(risks[1:2]), step_risk=ptr(risks[2:]))
+    check(l.mmf_amil_ig(C.byref(d), ptr(x), ptr(ws), nbytes, C.byref(sh), C.byref(ig), stream_ptr()), "mmf_amil_ig")
+    return rows[0], rows[1], attr, risks[0:1], risks[1:2], risks[2:]
+
+
 def radio_infer_group(xs, sizes, Wr, br, stack, gated, Wk=None, bk=None, Y=None, c=None, alpha=0.0, want_M=False,
                       eps=1e-7):
     """The radiology head's G bags evaluated in ONE C-ABI call (include/mmf_amil.h: mmf_radio_infer_group): reduce_dim
