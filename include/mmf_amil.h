@@ -48,8 +48,13 @@ int mmf_abi_version(void);
 struct mmf_trace;
 
 typedef struct mmf_amil_desc {
-  int64_t N;          /* instances in the bag */
-  int32_t L, H, D;    /* feature dim, hidden dim, attention dim: small 1024/256/256, big 1024/512/384 */
+  int64_t N;          /* instances in the bag.  Row cap: every operand that grows with N is addressed with 32-bit byte
+                       * offsets and stays below 2 GiB, so N * max(L, H, 2 * D) * 4 < 2^31 (fp32 storage), else
+                       * MMF_ERR_SHAPE before any launch: 524,287 rows where the widest of L, H, 2 D is 1024 (both
+                       * shipped heads), 2,097,151 where it is 256.  Every entry point that takes this descriptor
+                       * applies it; the grouped ones apply it to sum N. */
+  int32_t L, H, D;    /* feature dim, hidden dim, attention dim: small 1024/256/256, big 1024/512/384.
+                       * L % 32 == 0, H in {256, 512, 1024}, D % 128 == 0, else MMF_ERR_SHAPE. */
   int32_t gated;      /* 1 = Attn_Net_Gated, 0 = Attn_Net */
   const float* W1;    /* [H x L]  attention_net.0.weight */
   const float* b1;    /* [H] */
@@ -125,6 +130,8 @@ int mmf_amil_backward(const mmf_amil_desc* desc, const float* x, void* workspace
  *   bf16, multiplies on v_mfma_f32_32x32x16_bf16 with fp32 accumulation, and runs every epilogue
  *   (bias, ReLU, tanh, sigmoid, dropout, scores, softmax pooling) in fp32.  M and A_raw are fp32.
  *   Same desc, same dropout masks as the fp32 entry points.  Needs L % 64 == 0, H % 256 == 0.
+ *   Row cap: mmf_amil_desc::N's with 2-byte elements, N * max(L, H, 2 * D) * 2 < 2^31 (1,048,575 rows for both
+ *   shipped heads), else MMF_ERR_SHAPE.
  *   grads->dx must be NULL (the bag is a leaf).
  * ------------------------------------------------------------------------------------------- */
 size_t mmf_amil_bf16_workspace_bytes(int64_t N, int32_t L, int32_t H, int32_t D, int32_t gated);
@@ -194,7 +201,8 @@ int mmf_amil_nll_step(const mmf_amil_desc* desc, const void* x, int32_t x_bf16, 
  *   mmf_amil_nll_step draws for that bag alone with desc->seed = seeds[g] (bag-local row indices).
  *   Returns MMF_ERR_ARG for gemm = MMF_GEMM_BF16X3 or grads->dx != NULL; MMF_ERR_SHAPE for G outside 1..MMF_GROUP_MAX, an
  *   empty bag, offsets that are not strictly increasing from 0, desc->N != offsets[G], or totals beyond the limits of the
- *   single-bag entry points (applied to sum N).  No workgroup waits for another; calls are deterministic.
+ *   single-bag entry points (mmf_amil_desc::N's row cap applied to sum N) or beyond 256 pooling groups of 8192 rows
+ *   (sum N <= 2,097,152).  No workgroup waits for another; calls are deterministic.
  * mmf_amil_group_workspace_bytes: the workspace of that window, or 0 when the offset table is invalid.
  * ------------------------------------------------------------------------------------------- */
 #define MMF_GROUP_MAX 64
@@ -260,7 +268,8 @@ int mmf_radio_nll_step_group(const mmf_amil_desc* desc, const mmf_bag_group* gro
  *   Eval mode only: desc->p_h and desc->p_att must be 0, else MMF_ERR_ARG; MMF_ERR_ARG also for gemm = MMF_GEMM_BF16X3.
  *   MMF_ERR_SHAPE for G outside 1..MMF_GROUP_MAX, an empty bag, offsets that are not strictly increasing from 0,
  *   desc->N != offsets[G], a head with K > 32, a bf16 window of a gated H = D = 256 stack, or totals beyond the limits of
- *   the one-bag entry points (applied to sum N).
+ *   the one-bag entry points (mmf_amil_desc::N's row cap, or the bf16 section's, applied to sum N) or beyond 256 pooling
+ *   groups of 8192 rows (sum N <= 2,097,152).
  *   No workgroup waits for another; calls are deterministic; the call allocates nothing and keeps no state.
  * mmf_amil_group_infer_workspace_bytes: the workspace of that window, or 0 when the offset table is invalid.  With x_bf16 it
  *   is at least the fp32 size, so one buffer serves a window of either storage.
@@ -509,7 +518,8 @@ int mmf_amil_bf16_infer(const mmf_amil_desc* desc, const uint16_t* x, void* work
  *   (models/model_modules.py:84-85 and :105-110; n_classes = 1):  A[i] = (tanh(x_i Wa^T + ba) [. sigmoid(x_i Wb^T + bb)]) Wc^T + bc,
  *   with Dropout(0.25) on the branches when desc->p_att > 0.  Same kernels as inside the stack (K-gate, K-dh, K-tn).
  *   desc: N, H (= the scorer's input width L), D, gated, Wa..bc, p_att, seed[, seed_dev, trace]; L, W1, b1, p_h are ignored.
- *   H % 32 == 0, D % 32 == 0.  forward keeps a, b in the workspace for the matching backward.
+ *   H % 32 == 0, D % 32 == 0, and mmf_amil_desc::N's row cap without L: N * max(H, 2 * D) * 4 < 2^31, else
+ *   MMF_ERR_SHAPE.  forward keeps a, b in the workspace for the matching backward.
  *   backward: gA [N] = dL/dA -> grads->dWa, dba, (dWb, dbb,) dWc, dbc and, when grads->dx != NULL, dx [N x H].
  * ------------------------------------------------------------------------------------------- */
 size_t mmf_attn_net_workspace_bytes(int64_t N, int32_t H, int32_t D, int32_t gated);

@@ -208,8 +208,10 @@ static int check_desc(const mmf_amil_desc* d, int elem_bytes = 4) {
   if (d->H != 256 && d->H != 512 && d->H != 1024) return MMF_ERR_SHAPE;
   if (d->D % 128 != 0) return MMF_ERR_SHAPE;
   if (d->N * (int64_t)(d->H > d->D ? d->H : d->D) >= (int64_t)1 << 32) return MMF_ERR_SHAPE;  // 32-bit mask index
-  // buffer loads: 32-bit byte offsets, and the "reads as zero" sentinel is 2^31 => every operand < 2 GiB
-  const int64_t widest = d->L > 2 * d->D ? d->L : 2 * d->D;
+  // buffer loads: 32-bit byte offsets, and the "reads as zero" sentinel is 2^31 => every operand < 2 GiB: the bag
+  // [N x L], h / du [N x H], the gate rows [N x 2 D] (check_attn and ig_row_limit take the same three)
+  int64_t widest = d->L > 2 * d->D ? d->L : 2 * d->D;
+  if (d->H > widest) widest = d->H;
   if (d->N * widest * elem_bytes >= (int64_t)1 << 31) return MMF_ERR_SHAPE;
   if (d->p_h < 0.f || d->p_h >= 1.f || d->p_att < 0.f || d->p_att >= 1.f) return MMF_ERR_ARG;
   if (d->gemm != MMF_GEMM_F32 && d->gemm != MMF_GEMM_BF16X3) return MMF_ERR_ARG;

@@ -20,6 +20,10 @@ K loops run in chunks of KC = 32 (csrc/mmf_gemm_core.h:31).  Chunk classes:
   four   exactly 4: one round of the deep loop on a short grid
   mult4  a multiple of 4 above 4: the deep loop's steady state
 
+The stack's row cap (stack_row_cap, group_row_cap) is restated beside stack_rule, with a census per chain of every operand
+whose size grows with N (census): tests/test_abi_shapes_cpu.py holds each below 2 GiB at the cap the library enforces, and
+tests/test_gpu_row_caps.py runs every chain at its cap on the inputs of tests/cap_cases.py.
+
 The tensor-fusion tail (mmf_xfusion_infer_group, mmf_xfusion_group_forward / _backward) has a table of its own, XFUSION,
 run by tests/test_gpu_xfusion_shapes.py.  Its kernels are VALU code with fixed work units, restated below beside
 XFusion: classes are named after what a dimension does to a work unit -- lanes of a wave_dot round, rows of a dW block,
@@ -331,9 +335,30 @@ class Stack:
         return (self.L, self.H, self.D)
 
 
-def stack_rule(c):
-    """include/mmf_amil.h mmf_amil_desc and "bf16-storage variant"; csrc/mmf_api.hip check_desc / check_desc_bf16."""
+def stack_widest(c):
+    """The widest row of an operand that grows with N: the bag [N x L], h / du [N x H], the gate rows [N x 2 D]
+    (include/mmf_amil.h mmf_amil_desc::N; csrc/mmf_api.hip check_desc `widest`)."""
+    return max(c.L, c.H, 2 * c.D)
+
+
+def stack_row_cap(c):
+    """The largest N the stack admits: N * max(L, H, 2 D) * elem_bytes < 2^31 (include/mmf_amil.h mmf_amil_desc::N and
+    "bf16-storage variant"; csrc/mmf_api.hip check_desc, which check_desc_bf16 calls with 2-byte elements)."""
+    return (2**31 - 1) // (stack_widest(c) * (2 if c.bf16 else 4))
+
+
+def stack_rule(c, N=1):
+    """include/mmf_amil.h mmf_amil_desc and "bf16-storage variant"; csrc/mmf_api.hip check_desc / check_desc_bf16 -- in
+    the library's order."""
+    if N < 1:
+        return ERR_SHAPE
     if c.L % KC != 0 or c.H % KC != 0 or c.H not in (256, 512, 1024) or c.D % 128 != 0:
+        return ERR_SHAPE
+    # the 32-bit mask index.  It can never bind: D % 128 == 0 makes 2 D >= 256, so the row cap below holds N to
+    # (2^31 - 1) / (4 max(L, H, 2 D)) (or / 2 for bf16), and N max(H, D) <= N max(L, H, 2 D) < 2^30 < 2^32
+    if N * max(c.H, c.D) >= 2**32:
+        return ERR_SHAPE
+    if N > stack_row_cap(c):
         return ERR_SHAPE
     if c.bf16 and (c.L % 64 != 0 or c.H % 256 != 0):
         return ERR_SHAPE
@@ -394,6 +419,121 @@ GROUPED = [
     ("mmf_amil_infer_group", (1, 65, 300), (96, 256, 128), False),
     ("mmf_amil_nll_step_group", (1, 65, 300), (160, 512, 640), True),
 ]
+
+# ---- the row cap: every operand that grows with N, per chain ----------------------------------------------------------------
+# The kernels address each of these through a buffer resource: 32-bit byte offsets, a record count (unsigned)rows *
+# (unsigned)ld * elem, and 0x80000000 as the offset that reads as zero (csrc/mmf_gemm_core.h LoadK / LoadM / OOB), which is
+# right only while the operand is below 2^31 bytes.  Read off the carve functions of csrc/mmf_api.hip (AmilWs `carve`,
+# AmilWsBf `carve_bf16`, GroupWs `carve_group`, `carve_group_infer`, AttnWs `carve_attn`) and the kernels' make_rsrc calls.
+# An entry: (name, rows, row width in elements, element bytes, in the workspace?).  rows is a function of N.
+GROUP_POOL_GROUPS, POOL_MAX_ROWS = 256, 8192             # csrc/mmf_kernels.h:277, :107
+GROUP_BAG_MAX_PARTIALS = GROUP_POOL_GROUPS + 64          # csrc/mmf_amil_fwd.hip:1089: pooling groups of one bag of a window
+
+
+def _rows(N):
+    return N
+
+
+def _tiles128(N):
+    return (N + 127) // 128                              # fused_fwd_tiles / dh_bf16_row_tiles (csrc/mmf_amil_bf16.hip)
+
+
+def census(chain, c):
+    """The operands of one chain whose size grows with N.  chain: "f32" / "f32 infer" (mmf_amil_forward, _backward,
+    _head_forward, _nll_step / mmf_amil_infer), "bf16 fused" / "bf16 unfused" / "bf16 infer" (the same calls on a bf16 bag:
+    both training routes carve the same workspace; the fused forward alone writes one pooling partial per 128-row tile),
+    "group" / "group infer" (mmf_amil_nll_step_group, mmf_amil_infer_group over sum N rows), "scorer" (mmf_attn_net_*)."""
+    L, H, D, mstk = getattr(c, "L", c.H), c.H, c.D, (2 if c.gated else 1) * c.D
+    parts = (D + 63) // 64 if c.gated else (D + 127) // 128          # gate_parts (csrc/mmf_amil_fwd.hip)
+    parts16 = (D + 127) // 128 if c.gated else (D + 255) // 256      # gate_parts_bf16 (csrc/mmf_amil_bf16.hip)
+    relu_bits = ("relu_bits", lambda N: (N + 15) // 16 + 2, (H // 32) * 8, 8, True)
+    if chain == "scorer":
+        ops = [("x", _rows, H, 4, False), ("A", _rows, 1, 4, False), ("dx", _rows, H, 4, False),
+               ("a", _rows, D, 4, True), ("s_part", _rows, parts, 4, True)]
+        return ops + ([("b", _rows, D, 4, True)] if c.gated else [])
+    if chain in ("f32", "f32 infer", "group", "group infer"):
+        ops = [("x", _rows, L, 4, False), ("A_raw", _rows, 1, 4, False), ("h", _rows, H, 4, True), ("s_part", _rows, parts, 4, True)]
+        if chain in ("f32", "group"):
+            ops += [relu_bits, ("a", _rows, D, 4, True), ("p", _rows, 1, 4, True), ("ds", _rows, 1, 4, True), ("du", _rows, H, 4, True)]
+            ops += [("b", _rows, D, 4, True)] if c.gated else []
+        if chain == "group":
+            ops += [("ridx_h", _rows, 1, 4, True), ("ridx_d", _rows, 1, 4, True), ("bag", _rows, 1, 4, True)]
+        return ops
+    assert chain in ("bf16 fused", "bf16 unfused", "bf16 infer"), chain
+    ops = [("x", _rows, L, 2, False), ("A_raw", _rows, 1, 4, False), ("h", _rows, H, 2, True), ("s_part", _rows, parts16, 4, True)]
+    if chain != "bf16 unfused":
+        ops += [("partials", _tiles128, 2 + H, 4, True)]
+    if chain != "bf16 infer":
+        ops += [("a", _rows, D, 2, True), ("du", _rows, H, 2, True), ("dP", _rows, mstk, 2, True), ("p", _rows, 1, 4, True),
+                ("ds", _rows, 1, 4, True), ("dbc_part", _tiles128, 1, 4, True), ("dwc_part", _tiles128, D, 4, True)]
+        ops += [("b", _rows, D, 2, True)] if c.gated else []
+    return ops
+
+
+def census_bytes(chain, c, N):
+    """{operand: bytes} of one chain at N rows."""
+    return {name: rows(N) * width * elem for name, rows, width, elem, _ in census(chain, c)}
+
+
+def census_workspace(chain, c, N):
+    """What the chain's census puts into the workspace, each slot rounded up to the carver's 256 bytes."""
+    return sum((rows(N) * width * elem + 255) // 256 * 256 for _, rows, width, elem, ws in census(chain, c) if ws)
+
+
+def census_slack(chain, c):
+    """stack_widest over the widest row the chain really holds.  1 wherever L or H is the widest, and for every bf16
+    training chain (dP is [N x 2 D] when gated).  Above 1 only where 2 D is the widest of an fp32 chain or of an ungated
+    bf16 chain: those keep a and b apart ([N x D] each) and store no dP, so check_desc's 2 D term -- one formula for both
+    storages -- refuses such a stack while its largest operand is still `slack` times below 2 GiB.  Conservative, not a
+    hole: see DESIGN.md 7p."""
+    widest = max(width for _, rows, width, _, _ in census(chain, c) if rows is _rows)
+    scorer = chain == "scorer"
+    return (max(c.H, 2 * c.D) if scorer else stack_widest(c)) / widest
+
+
+def bf16_chain(c):
+    return "bf16 fused" if c.gated and c.H == 256 and c.D == 256 else "bf16 unfused"
+
+
+def group_row_cap(c):
+    """sum N of a window: the one-bag cap, and group_plan's 256 pooling groups of at most 8192 rows (csrc/mmf_api.hip).  A
+    single bag of a window may span at most GROUP_BAG_MAX_PARTIALS groups (launch_group_pool_partial), which at 8192-row
+    groups is more rows than any window holds: the per-bag limit never binds below the window's."""
+    return min(stack_row_cap(c), GROUP_POOL_GROUPS * POOL_MAX_ROWS)
+
+
+def group_rule(c, sizes):
+    """include/mmf_amil.h "Grouped training step" / "Grouped forward-only pass"; csrc/mmf_api.hip group_plan, window_plan."""
+    if not 1 <= len(sizes) <= GROUP_MAX or any(n < 1 for n in sizes):
+        return ERR_SHAPE
+    if sum(sizes) > GROUP_POOL_GROUPS * POOL_MAX_ROWS:
+        return ERR_SHAPE
+    return stack_rule(c, sum(sizes))
+
+
+SHIPPED_HEADS = {"small": (1024, 256, 256), "big": (1024, 512, 384)}     # multimodalfusion_amd/models/model_modules.py AMIL_SIZES
+
+
+def cap_stacks():
+    """(chain, stack) for every admitted stack of the tables and the shipped heads: what the row-cap census covers."""
+    out = [("f32", c) for c in STACK_F32 if stack_rule(c) == OK] + [("f32 infer", c) for c in STACK_F32 if stack_rule(c) == OK]
+    for c in STACK_BF16:
+        if stack_rule(c) == OK:
+            out += [(bf16_chain(c), c), ("bf16 infer", c)]
+    for _, _, size, gated in GROUPED:
+        out += [("group", Stack(*size, gated)), ("group infer", Stack(*size, gated))]
+    for size in SHIPPED_HEADS.values():
+        out += [("f32", Stack(*size, True)), ("f32 infer", Stack(*size, True)), ("group", Stack(*size, True)),
+                ("group infer", Stack(*size, True))]
+        b = Stack(*size, True, bf16=True)
+        out += [(bf16_chain(b), b), ("bf16 infer", b)]
+    seen, uniq = set(), []
+    for k in out:
+        if k not in seen:
+            seen.add(k)
+            uniq.append(k)
+    return uniq
+
 
 REQUIRED_STACK = (
     {("shape", s) for s in ((32, 256, 128, False), (96, 256, 128, True), (160, 512, 640, True), (32, 1024, 384, False),

@@ -35,7 +35,8 @@ import numpy as np
 
 # ---- shapes and limits ----------------------------------------------------------------------------------------------
 HEADS = {"small": (1024, 256, 256), "big": (1024, 512, 384)}       # (L, H, D): models/model_modules.py AMIL_SIZES
-# check_desc (csrc/mmf_api.hip:212-213): N * max(L, 2 D) * bytes < 2 GiB; L = 1024 >= 2 D for both heads
+# check_desc (csrc/mmf_api.hip): N * max(L, H, 2 D) * bytes < 2 GiB; L = 1024 >= H, 2 D for both heads (the rule for every
+# admitted stack: tests/abi_shapes.py stack_row_cap)
 N_MAX = {"fp32": (2**31 - 1) // (1024 * 4), "bf16": (2**31 - 1) // (1024 * 2)}
 # mmf_radio_nll_step_group (csrc/mmf_api.hip:949): the [sum N x nseg * kseg] input < 2 GiB, kseg = L = 1024
 RADIO_R_MAX = {nseg: min(N_MAX["fp32"], (2**31 - 1) // (nseg * 1024 * 4)) for nseg in (2, 3, 4)}

@@ -746,3 +746,186 @@ def test_tail_restatements_match_the_ports():
         assert np.abs(out["out"] - fus.detach().numpy()).max() <= 1e-13
         for t, want in enumerate(torch.autograd.grad((fus * sc.T(i["g"])).sum(), os_)):
             assert np.abs(out[f"d{t}"] - want.numpy()).max() <= 1e-12, (c, t)
+
+
+# ---- the row cap of the attention stack: the rule, the operand census, the library at cap and cap + 1 --------------------
+CAP_STACKS = ab.cap_stacks()
+_cap_id = lambda k: f"{k[0]} {k[1].size} {'gated' if k[1].gated else 'ungated'}"
+
+
+def _chain_cap(chain, c):
+    return ab.group_row_cap(c) if chain.startswith("group") else ab.stack_row_cap(c)
+
+
+def test_row_cap_restates_check_desc():
+    """stack_rule with N: the cap from both sides, for every admitted stack; the issue's figures."""
+    for chain, c in CAP_STACKS:
+        cap = ab.stack_row_cap(c)
+        assert ab.stack_rule(c, cap) == ab.OK and ab.stack_rule(c, cap + 1) == ab.ERR_SHAPE, (chain, c)
+        assert ab.stack_rule(c, 0) == ab.ERR_SHAPE
+        assert cap * max(c.H, c.D) < 2**30, "the mask-index rule would bind"
+    S = ab.Stack
+    assert ab.stack_row_cap(S(32, 256, 128, False)) == 2**21 - 1 and ab.stack_row_cap(S(160, 512, 640, True)) == 419430
+    assert ab.stack_row_cap(S(128, 1024, 128, True)) == ab.stack_row_cap(S(32, 1024, 384, False)) == 2**19 - 1
+    assert ab.stack_row_cap(S(1024, 256, 256, True)) == 2**19 - 1 == lp.N_MAX["fp32"]
+    assert ab.stack_row_cap(S(1024, 256, 256, True, bf16=True)) == ab.stack_row_cap(S(64, 1024, 128, True, bf16=True)) == 2**20 - 1
+    assert ab.stack_row_cap(S(1024, 256, 256, True, bf16=True)) == lp.N_MAX["bf16"]
+    assert ab.stack_row_cap(S(64, 512, 384, False, bf16=True)) == 1398101
+    assert ab.group_row_cap(S(96, 256, 128, False)) == 2**21 - 1 and ab.GROUP_POOL_GROUPS * ab.POOL_MAX_ROWS == 2**21
+    assert ab.GROUP_BAG_MAX_PARTIALS * ab.POOL_MAX_ROWS > ab.GROUP_POOL_GROUPS * ab.POOL_MAX_ROWS     # the per-bag limit never binds
+    assert ab.group_rule(S(96, 256, 128, False), (337, 2**21 - 1 - 337)) == ab.OK
+    assert ab.group_rule(S(96, 256, 128, False), (338, 2**21 - 1 - 337)) == ab.ERR_SHAPE
+    assert ab.group_rule(S(96, 256, 128, False), (1,) * 65) == ab.ERR_SHAPE
+
+
+def _library_cap(chain, c):
+    """The largest N the library itself admits for the chain's forward call (bisection over fake-pointer calls that stop at
+    the zero-byte workspace): the census below is taken at the library's cap, not at the restated one."""
+    m, l = _lib()
+    first = {"f32": "forward", "f32 infer": "infer", "bf16 fused": "forward", "bf16 unfused": "forward", "bf16 infer": "infer",
+             "group": "mmf_amil_nll_step_group", "group infer": "mmf_amil_infer_group"}[chain]
+    pins = "group" if chain.startswith("group") else chain.replace(" infer", "") if chain != "bf16 infer" else "bf16 unfused"
+    lo, hi = 338, 2**33                      # admitted, refused
+    assert _stack_calls(m, l, pins, c, lo)[first] == ab.ERR_WORKSPACE and _stack_calls(m, l, pins, c, hi)[first] == ab.ERR_SHAPE
+    while hi - lo > 1:
+        mid = (lo + hi) // 2
+        lo, hi = (mid, hi) if _stack_calls(m, l, pins, c, mid)[first] == ab.ERR_WORKSPACE else (lo, mid)
+    return lo
+
+
+@pytest.mark.parametrize("chain,c", CAP_STACKS, ids=map(_cap_id, CAP_STACKS))
+def test_every_operand_is_below_2_gib_at_the_row_cap(chain, c):
+    """The census, at the cap the library itself enforces: at the cap no operand of the chain reaches 2^31 bytes -- the condition under which the kernels' 32-bit
+    offsets, record counts and the reads-as-zero offset are right.  With max(L, 2 D) as check_desc's `widest` this fails for
+    h and du of Stack(128, 1024, 128) (8 GiB at 2,097,151 rows) and Stack(32, 1024, 384) (2.7 GiB at 699,050)."""
+    cap = _library_cap(chain, c)
+    over = {k: v for k, v in ab.census_bytes(chain, c, cap).items() if v >= 2**31}
+    assert not over, (chain, c.size, cap, over)
+    assert cap == _chain_cap(chain, c)
+
+
+@pytest.mark.parametrize("chain,c", CAP_STACKS, ids=map(_cap_id, CAP_STACKS))
+def test_the_row_cap_is_tight(chain, c):
+    """At cap + 1 an operand reaches 2^31 bytes.  Where 2 D is the widest of a chain that stores no 2 D-wide row (fp32: a and
+    b apart; an ungated bf16 stack: dP is [N x D]) the rule's 2 D term is conservative by census_slack: there the largest
+    operand, scaled by that factor, reaches 2^31 -- the rule refuses exactly what its formula says, no earlier."""
+    if chain.startswith("group") and ab.group_row_cap(c) < ab.stack_row_cap(c):
+        pytest.fail("a window whose pooling-group limit binds below the byte cap: restate its tightness here")
+    n = _chain_cap(chain, c) + 1
+    slack = ab.census_slack(chain, c)
+    assert slack >= 1
+    rows = [name for name, rows, *_ in ab.census(chain, c) if rows is ab._rows]
+    top = max(v for k, v in ab.census_bytes(chain, c, n).items() if k in rows)
+    assert top * slack >= 2**31, (chain, c.size, n, top, slack)
+    if max(c.L, c.H) >= 2 * c.D or (chain.startswith("bf16") and chain != "bf16 infer" and c.gated):
+        assert slack == 1
+
+
+def _head(m):
+    return m.SurvHead(Wk=P[8], bk=P[9], K=4, logits=P[10], hazards=P[11], S=P[12], Y_hat=P[13], risk=None)
+
+
+def _target(m):
+    return m.NllTarget(Y=P[8], c=P[9], alpha=0.0, eps=1e-7, loss_scale=1.0, loss=P[10], dWk=P[11], dbk=P[12], accumulate=0)
+
+
+def _grads_p(m):
+    return m.AmilGrads(dW1=P[8], db1=P[9], dWa=P[10], dba=P[11], dWb=P[12], dbb=P[13], dWc=P[14], dbc=P[15], dx=None)
+
+
+def _stack_calls(m, l, chain, c, N):
+    """Every entry point of the chain at N rows on fake pointers with a zero-byte workspace: an admitted shape gets as far as
+    the workspace check (MMF_ERR_WORKSPACE), which comes before the first launch and the first pointer read."""
+    d = _desc(m, c, N=N)
+    by, x, ws, A = C.byref, P[8], P[9], P[10]
+    head, tgt, g = _head(m), _target(m), _grads_p(m)
+    if chain == "scorer":
+        return {"mmf_attn_net_forward": l.mmf_attn_net_forward(by(d), x, ws, 0, A, None),
+                "mmf_attn_net_backward": l.mmf_attn_net_backward(by(d), x, ws, 0, A, by(g), None)}
+    if chain.startswith("group"):
+        offs = (C.c_int64 * 3)(0, 337, N)
+        seeds = (C.c_uint32 * 2)(1, 2)
+        grp = m.BagGroup(G=2, offsets=offs, seeds=seeds)
+        return {"mmf_amil_nll_step_group": l.mmf_amil_nll_step_group(by(d), by(grp), x, ws, 0, by(head), by(tgt), A, by(g), None),
+                "mmf_amil_infer_group": l.mmf_amil_infer_group(by(d), by(grp), x, 0, ws, 0, by(head), None, P[11], A, None),
+                "mmf_amil_group_forward": l.mmf_amil_group_forward(by(d), by(grp), x, ws, 0, P[11], c.H, A, None),
+                "mmf_amil_group_backward": l.mmf_amil_group_backward(by(d), by(grp), x, ws, 0, P[11], c.H, A, by(g), 0, None)}
+    b = 1 if c.bf16 else 0
+    fwd, bwd, infer = ((l.mmf_amil_bf16_forward, l.mmf_amil_bf16_backward, l.mmf_amil_bf16_infer) if b else
+                       (l.mmf_amil_forward, l.mmf_amil_backward, l.mmf_amil_infer))
+    return {"forward": fwd(by(d), x, ws, 0, P[11], A, None),
+            "backward": bwd(by(d), x, ws, 0, P[11], A, P[12], None, by(g), None),
+            "infer": infer(by(d), x, ws, 0, P[11], A, None),
+            "mmf_amil_head_forward": l.mmf_amil_head_forward(by(d), x, b, ws, 0, by(head), P[11], A, None),
+            "mmf_amil_nll_step": l.mmf_amil_nll_step(by(d), x, b, ws, 0, by(head), by(tgt), A, by(g), None)}
+
+
+CAP_PINS = [k for k in CAP_STACKS if k[0] in ("f32", "bf16 fused", "bf16 unfused", "group")]
+SCORERS = [ab.Attn(1, 256, 128, True), ab.Attn(1, 1024, 128, True), ab.Attn(1, 160, 256, False), ab.Attn(1, 128, 160, True)]
+CAP_PINS += [("scorer", a) for a in SCORERS]
+
+
+@pytest.mark.parametrize("chain,c", CAP_PINS, ids=[f"{k[0]} {getattr(k[1], 'size', (k[1].H, k[1].D))}" for k in CAP_PINS])
+def test_the_library_refuses_cap_plus_one_and_admits_the_cap(chain, c):
+    """Forward, backward, head_forward, nll_step, their bf16 forms, both infer calls, the grouped calls on sum N, the scorer."""
+    m, l = _lib()
+    cap = (2**31 - 1) // (max(c.H, 2 * c.D) * 4) if chain == "scorer" else _chain_cap(chain, c)
+    if chain == "scorer":
+        assert ab.attn_rule(dataclasses.replace(c, N=cap)) == ab.OK and ab.attn_rule(dataclasses.replace(c, N=cap + 1)) == ab.ERR_SHAPE
+    for name, rc in _stack_calls(m, l, chain, c, cap).items():
+        assert rc == ab.ERR_WORKSPACE, (name, rc, "at the cap: admitted, stopped by the zero-byte workspace")
+    for name, rc in _stack_calls(m, l, chain, c, cap + 1).items():
+        assert rc == ab.ERR_SHAPE, (name, rc, "at cap + 1")
+
+
+def _ws_bytes(l, chain, c, N):
+    a = (N, c.L, c.H, c.D, 1 if c.gated else 0) if chain != "scorer" else None
+    if chain.startswith("group"):
+        offs = (C.c_int64 * 3)(0, 337, N)
+        if chain == "group":
+            return l.mmf_amil_group_workspace_bytes(offs, 2, *a[1:])
+        return l.mmf_amil_group_infer_workspace_bytes(offs, 2, *a[1:], 0)
+    return {"f32": l.mmf_amil_workspace_bytes, "f32 infer": l.mmf_amil_infer_workspace_bytes,
+            "bf16 fused": l.mmf_amil_bf16_workspace_bytes, "bf16 unfused": l.mmf_amil_bf16_workspace_bytes,
+            "bf16 infer": l.mmf_amil_bf16_infer_workspace_bytes}[chain](*a)
+
+
+@pytest.mark.parametrize("chain,c", CAP_STACKS, ids=map(_cap_id, CAP_STACKS))
+def test_workspace_queries_do_not_wrap_at_the_cap(chain, c):
+    """The query at the cap holds every workspace operand of the census (each in its 256-byte slot) and is no smaller than
+    at cap - 1: no 32-bit product inside the carve."""
+    m, l = _lib()
+    cap = _chain_cap(chain, c)
+    at, below = _ws_bytes(l, chain, c, cap), _ws_bytes(l, chain, c, cap - 1)
+    assert at >= ab.census_workspace(chain, c, cap), (chain, c.size, at, ab.census_workspace(chain, c, cap))
+    assert at >= below > 0
+    if chain == "group infer":      # with x_bf16 the query is the larger of the two storages
+        offs = (C.c_int64 * 3)(0, 337, cap)
+        assert l.mmf_amil_group_infer_workspace_bytes(offs, 2, c.L, c.H, c.D, 1 if c.gated else 0, 1) >= at
+
+
+def test_scorer_workspace_query_does_not_wrap_at_the_cap():
+    m, l = _lib()
+    for a in SCORERS:
+        cap = (2**31 - 1) // (max(a.H, 2 * a.D) * 4)
+        c = dataclasses.replace(a, N=cap)
+        assert max(ab.census_bytes("scorer", c, cap).values()) < 2**31
+        at = l.mmf_attn_net_workspace_bytes(cap, a.H, a.D, 1 if a.gated else 0)
+        assert at >= ab.census_workspace("scorer", c, cap) and at >= l.mmf_attn_net_workspace_bytes(cap - 1, a.H, a.D, 1 if a.gated else 0)
+
+
+def test_header_states_the_row_cap():
+    import os
+    from conftest import ROOT
+    from multimodalfusion_amd import _lib as m
+    hdr = open(os.path.join(ROOT, "include", "mmf_amil.h")).read()
+    desc = hdr[hdr.index("typedef struct mmf_amil_desc"):hdr.index("} mmf_amil_desc;")]
+    assert "N * max(L, H, 2 * D) * 4 < 2^31" in desc and "MMF_ERR_SHAPE" in desc and "524,287" in desc
+    bf = hdr[hdr.index("bf16-storage variant"):hdr.index("mmf_amil_bf16_workspace_bytes")]
+    assert "N * max(L, H, 2 * D) * 2 < 2^31" in bf and "mmf_amil_desc::N" in bf
+    for section in ("Grouped training step:", "Grouped forward-only pass:"):
+        s = hdr[hdr.index(section):]
+        assert "mmf_amil_desc::N's row cap" in s[:s.index("-- */")] and "2,097,152" in s[:s.index("-- */")]
+    scorer = hdr[hdr.index("The attention scorer on its own"):hdr.index("mmf_attn_net_workspace_bytes")]
+    assert "N * max(H, 2 * D) * 4 < 2^31" in scorer
+    assert m.ABI_VERSION == 12
