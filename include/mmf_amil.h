@@ -231,7 +231,8 @@ int mmf_amil_nll_step_group(const mmf_amil_desc* desc, const mmf_bag_group* grou
  *   stack's gradients do.
  *   Returns as mmf_amil_nll_step_group, and MMF_ERR_SHAPE for nseg outside 2..4, kseg != desc->L or an
  *   [offsets[G] x nseg * kseg] input of 2 GiB or more; MMF_ERR_ALIGN for a misaligned segment, reduce_dim weight or dW.
- * mmf_radio_group_workspace_bytes: the workspace of that window (L = kseg), or 0 when the offset table or nseg is invalid.
+ * mmf_radio_group_workspace_bytes: the workspace of that window (L = kseg), or 0 when the offset table is invalid, nseg is
+ *   outside 2..4 or kseg < 1 (the widths are the descriptor's to refuse: the query does not see it).
  * ------------------------------------------------------------------------------------------- */
 typedef struct mmf_radio_reduce {
   const float* const* x;     /* HOST [nseg] device pointers, each [sum N x kseg]: modality m of every bag, in bag order */
@@ -275,7 +276,8 @@ int mmf_radio_nll_step_group(const mmf_amil_desc* desc, const mmf_bag_group* gro
  *   is at least the fp32 size, so one buffer serves a window of either storage.
  * mmf_radio_infer_group: the same behind the radiology head's reduce_dim (mmf_radio_nll_step_group's layout; desc->L ==
  *   kseg, nseg 2..4, fp32); rd->dW / rd->db are not read.  Returns as mmf_amil_infer_group, and as
- *   mmf_radio_nll_step_group for rd.  mmf_radio_group_infer_workspace_bytes: its workspace, or 0 (invalid table or nseg).
+ *   mmf_radio_nll_step_group for rd.  mmf_radio_group_infer_workspace_bytes: its workspace, or 0 (invalid table, nseg
+ *   outside 2..4 or kseg < 1).
  * ------------------------------------------------------------------------------------------- */
 size_t mmf_amil_group_infer_workspace_bytes(const int64_t* offsets, int32_t G, int32_t L, int32_t H, int32_t D,
                                             int32_t gated, int32_t x_bf16);

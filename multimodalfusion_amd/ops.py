@@ -366,7 +366,7 @@ GROUP_MAX = 64       # include/mmf_amil.h: MMF_GROUP_MAX
 def group_row_limit(L, H, D):
     """Most rows one grouped call takes (the single-bag limits of include/mmf_amil.h applied to sum N: 32-bit mask
     indices, every [sum N x *] operand < 2 GiB, pooling groups of <= 8192 rows)."""
-    return min(((1 << 32) - 1) // max(H, D), ((1 << 31) - 1) // (4 * max(L, 2 * D)), 256 * 8192)
+    return min(((1 << 32) - 1) // max(H, D), ((1 << 31) - 1) // (4 * max(L, H, 2 * D)), 256 * 8192)
 
 
 def radio_group_row_limit(nseg, L, H, D):
@@ -687,7 +687,7 @@ def infer_group_row_limit(L, H, D, bf16=False):
     operands of a bf16 window two bytes wide."""
     if not bf16:
         return group_row_limit(L, H, D)
-    return min(((1 << 32) - 1) // max(H, D), ((1 << 31) - 1) // (2 * max(L, 2 * D)), 256 * 8192)
+    return min(((1 << 32) - 1) // max(H, D), ((1 << 31) - 1) // (2 * max(L, H, 2 * D)), 256 * 8192)
 
 
 def infer_group_takes_bf16(gated, H, D):

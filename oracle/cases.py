@@ -72,9 +72,10 @@ def run_path(m, dtype=torch.float64):
 
 def radio_inputs(m):
     sd = gen.radio_state_dict(seed=m["seed"], gated=m["gated"], n_classes=m["K"], dropout=m["dropout"],
-                              n_mod=m["n_mod"], bias_std=m["bias_std"])
-    xs = [gen.bag(m["x_seed"], m["n"], stream=7 * i) for i in range(m["n_mod"])]
-    masks = amil_masks(m["mask_seed"], m["n"], 256, 256, m["gated"], m["dropout"]) if m["train"] else None
+                              n_mod=m["n_mod"], bias_std=m["bias_std"], size=m.get("size", "small"))
+    L, H, D = gen.stack_dims(m.get("size", "small"))       # the shipped head, or explicit (L, H, D)
+    xs = [gen.bag(m["x_seed"], m["n"], dim=L, stream=7 * i) for i in range(m["n_mod"])]
+    masks = amil_masks(m["mask_seed"], m["n"], H, D, m["gated"], m["dropout"]) if m["train"] else None
     return sd, xs, masks
 
 

@@ -118,9 +118,10 @@ def path_state_dict(seed=1, gated=True, size="small", n_classes=4, dropout=False
     return sd
 
 
-def radio_state_dict(seed=1, gated=True, n_classes=4, dropout=True, n_mod=4, bias_std=0.0):
+def radio_state_dict(seed=1, gated=True, n_classes=4, dropout=True, n_mod=4, bias_std=0.0, size="small"):
     sd = OrderedDict()
-    sz = SIZE_DICT["small"]  # model_attention_mil_radio.py:70 forces 'small'
+    # model_attention_mil_radio.py:70 forces 'small'; explicit (L, H, D): the widths the C ABI admits beyond it (stack_dims)
+    sz = stack_dims(size)
     st = 0
     if n_mod > 1:
         st = _linear(sd, "reduce_dim", sz[0], sz[0] * n_mod, seed, st, "xavier", bias_std)

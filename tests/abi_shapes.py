@@ -39,6 +39,11 @@ stride + 1, three strides or more), the caps from both sides, every combination 
 The entry points that were reached only through the models -- the dense forward and its _rows form, gate_mul, the Kronecker
 product, the fused gating stage (xreduce) and the omic head's one-launch step -- follow below DENSE_BWD, run by
 tests/test_gpu_tail_shapes.py on the inputs, references and bars of tests/small_cases.py.
+
+The radiology window (mmf_radio_nll_step_group, mmf_radio_infer_group) and the grouped half chains (mmf_amil_group_forward /
+_backward, mmf_radio_group_forward / _backward) have the RADIO and HALF tables above TABLES, run by
+tests/test_gpu_radio_shapes.py on the inputs and float64 references of tests/radio_cases.py and pinned to the library by
+tests/test_radio_shapes_cpu.py; census() covers their chains ("radio", "radio infer") and radio_row_cap restates their cap.
 """
 from __future__ import annotations
 
@@ -442,7 +447,16 @@ def census(chain, c):
     """The operands of one chain whose size grows with N.  chain: "f32" / "f32 infer" (mmf_amil_forward, _backward,
     _head_forward, _nll_step / mmf_amil_infer), "bf16 fused" / "bf16 unfused" / "bf16 infer" (the same calls on a bf16 bag:
     both training routes carve the same workspace; the fused forward alone writes one pooling partial per 128-row tile),
-    "group" / "group infer" (mmf_amil_nll_step_group, mmf_amil_infer_group over sum N rows), "scorer" (mmf_attn_net_*)."""
+    "group" / "group infer" (mmf_amil_nll_step_group, mmf_amil_infer_group over sum N rows), "scorer" (mmf_attn_net_*),
+    "radio" / "radio infer" (mmf_radio_nll_step_group and the radio half pair / mmf_radio_infer_group on a Radio case: the
+    group chains with L = kseg, reduce_dim's output xr and -- training -- its gradient dxr [R x L] (carve_radio,
+    carve_radio_infer), each modality segment [R x kseg], and the concatenated input [R x nseg kseg] that radio_operands
+    holds below 2 GiB: no kernel reads it as one operand, the refusal is the header's)."""
+    if chain in ("radio", "radio infer"):
+        ops = census("group" if chain == "radio" else "group infer", c)
+        ops += [("xr", _rows, c.L, 4, True)] + ([("dxr", _rows, c.L, 4, True)] if chain == "radio" else [])
+        ops += [(f"x[{m}]", _rows, c.kseg, 4, False) for m in range(c.nseg)]
+        return ops + [("x concatenated", _rows, c.nseg * c.kseg, 4, False)]
     L, H, D, mstk = getattr(c, "L", c.H), c.H, c.D, (2 if c.gated else 1) * c.D
     parts = (D + 63) // 64 if c.gated else (D + 127) // 128          # gate_parts (csrc/mmf_amil_fwd.hip)
     parts16 = (D + 127) // 128 if c.gated else (D + 255) // 256      # gate_parts_bf16 (csrc/mmf_amil_bf16.hip)
@@ -1568,7 +1582,231 @@ REQUIRED_MAXSTEP = (
     | {t for c in MAXSTEP if maxstep_rule(c) != OK for t in maxstep_tags(c)})
 
 
+# ---- the radiology window (mmf_radio_nll_step_group, mmf_radio_infer_group) and the grouped half chains ---------------------
+# (mmf_amil_group_forward / _backward, mmf_radio_group_forward / _backward).  Run by tests/test_gpu_radio_shapes.py on the
+# inputs and float64 references of tests/radio_cases.py.  reduce_dim is a dense layer over nseg segments of kseg columns
+# with N = L = kseg outputs, so the classes are those of a short L: chunks of kseg, the K split of a short grid
+# (linear_ksplit), the splits of the dW_r TN launch over tiles wider than L (tn_splits), and -- for the halves -- where the
+# stack's H columns sit in the caller's feature matrix.
+SIXTY_FOUR = tuple(1 + (37 * g) % 90 for g in range(64))      # tests/test_gpu_radio_group_step.py SIXTY_FOUR: 64 bags of 1..90 rows
+TN_WIDE_MIN = 12288                                      # csrc/mmf_amil_bwd.hip tn_tile_dim: 256-wide TN tiles from here on
+
+
+def window_class(sizes):
+    return {(1, 65, 300): "(1, 65, 300)", SIXTY_FOUR: "64 bags of 1..90 rows"}.get(
+        tuple(sizes), "one bag alone" if len(sizes) == 1 else "other")
+
+
+@dataclass(frozen=True)
+class Radio:
+    nseg: int
+    kseg: int
+    H: int
+    D: int
+    gated: bool
+    sizes: tuple
+    train: bool                  # True: p_h = p_att = 0.25, both dropout sites (a third, b, when gated); False: eval mode
+    accumulate: int = 0          # 1: the gradients are added onto known non-zero values
+    stack_L: int = 0             # the stack's L where it is not kseg (refused)
+    misalign: str = ""           # "segment" (x[1]), "W", "dW": that pointer 4 bytes off a 16-byte boundary
+    seed: int = 1                # of the weights; chosen on the CPU (tests/radio_cases.py) for the ReLU kink condition
+    why: str = ""
+
+    @property
+    def L(self):
+        return self.stack_L or self.kseg
+
+    @property
+    def stack(self):
+        return Stack(self.L, self.H, self.D, self.gated)
+
+    @property
+    def size(self):
+        return (self.L, self.H, self.D)
+
+    @property
+    def R(self):
+        return sum(self.sizes)
+
+
+def radio_row_cap(c):
+    """sum N of a radio window: the stack's window cap, and the [sum N x nseg kseg] input below 2 GiB (include/mmf_amil.h
+    mmf_radio_nll_step_group; csrc/mmf_api.hip radio_operands) -- 131,071 rows at four 1024-wide modalities."""
+    return min(group_row_cap(c.stack), (2**31 - 1) // (4 * c.nseg * c.kseg))
+
+
+def radio_rule(c, grads=True):
+    """include/mmf_amil.h mmf_radio_nll_step_group / mmf_radio_infer_group / mmf_radio_group_forward / _backward;
+    csrc/mmf_api.hip radio_modalities, then group_check / infer_group_check / group_half_check (window_plan), then
+    radio_operands -- in the library's order.  grads: the entry point writes dW / db (the step, the backward half)."""
+    if c.nseg < 2 or c.nseg > 4:
+        return ERR_SHAPE
+    code = group_rule(c.stack, c.sizes)
+    if code != OK:
+        return code
+    if c.kseg != c.L:
+        return ERR_SHAPE
+    if c.R * c.nseg * c.kseg * 4 >= 2**31:
+        return ERR_SHAPE
+    if c.misalign in ("segment", "W") or (grads and c.misalign == "dW"):
+        return ERR_ALIGN
+    return OK
+
+
+def radio_tn_splits(c):
+    """csrc/mmf_api.hip carve_radio `most`: the dW_r problems as a TN launch of their own (MMF_RADIO_TN_SEPARATE unset)."""
+    td = 256 if c.R >= TN_WIDE_MIN else 128
+    cdiv = lambda a, b: (a + b - 1) // b
+    return tn_splits(c.R, c.nseg * cdiv(c.L, td) * cdiv(c.kseg, td), td)
+
+
+def radio_tags(c):
+    code = radio_rule(c)
+    if code != OK:
+        return {("refused", code, f"nseg={c.nseg} kseg={c.kseg} L={c.L} H={c.H} D={c.D} misalign={c.misalign}")}
+    per_tile = 64 if c.gated else 128
+    return {("stack", (c.kseg, c.H, c.D, c.gated)), ("nseg", c.nseg), ("kseg", c.kseg), ("kseg chunks", chunks(c.kseg)), ("H", c.H),
+            ("gated" if c.gated else "ungated",), ("D tiles", "one" if c.D // per_tile == 1 else "many"),
+            ("window", window_class(c.sizes)),
+            ("reduce_dim forward", "K split" if linear_ksplit(c.R, c.L, c.nseg * c.kseg, c.nseg, c.kseg) > 1 else "plain"),
+            ("dW_r TN launch", "several" if radio_tn_splits(c) > 1 else "one split"),
+            ("mode", "train, both dropout sites" if c.train else "eval"), ("accumulate", c.accumulate)}
+
+
+RADIO = [
+    Radio(2, 32, 256, 128, False, (1, 65, 300), True, seed=3,
+          why="two modalities of one chunk: the 128-wide TN tile of modality 0's problem reaches over modality 1's columns of dW_r [32 x 64]; 3 TN splits"),
+    Radio(3, 96, 256, 128, True, SIXTY_FOUR, False, seed=1,
+          why="three modalities of three chunks, 64 bags: each problem's 128-wide tile ends 32 columns inside the next modality's; eval"),
+    Radio(4, 160, 512, 640, True, (65,), True, accumulate=1, seed=1,
+          why="four modalities of five chunks, one bag of 65 rows: one TN split, q.M = 160 over two row tiles; accumulate"),
+    Radio(4, 128, 1024, 128, True, (1, 65, 300), True, seed=3,
+          why="four modalities of four chunks: reduce_dim takes its two-way K split over the segments; H = 1024"),
+    Radio(2, 32, 1024, 384, False, (1, 65, 300), False, seed=9,
+          why="the H = 1024 stack behind a 32-wide reduce_dim, ungated with three D tiles; eval"),
+    # refused
+    Radio(1, 32, 256, 128, False, (1, 65, 300), True, why="nseg = 1: no reduce_dim, the pathology calls"),
+    Radio(5, 32, 256, 128, False, (1, 65, 300), True, why="nseg = 5"),
+    Radio(2, 32, 256, 128, False, (1, 65, 300), True, stack_L=64, why="kseg != L"),
+    Radio(2, 128, 768, 128, True, (1, 65, 300), True, why="H outside {256, 512, 1024}: check_desc, through window_plan"),
+    Radio(2, 32, 256, 128, False, (1, 65, 300), True, misalign="segment", why="x[1] 4 bytes off: the segments are read 16 bytes at a time"),
+    Radio(2, 32, 256, 128, False, (1, 65, 300), True, misalign="W", why="reduce_dim's W 4 bytes off"),
+    Radio(2, 32, 256, 128, False, (1, 65, 300), True, misalign="dW", why="dW 4 bytes off: refused where it is written, admitted forward-only"),
+]
+REQUIRED_RADIO = (
+    {("stack", (c.L, c.H, c.D, c.gated)) for c in STACK_F32 if stack_rule(c) == OK}
+    | {("nseg", n) for n in (2, 3, 4)} | {("kseg", k) for k in (32, 96, 128, 160)}
+    | {("kseg chunks", k) for k in ("one", "odd", "four")} | {("H", h) for h in (256, 512, 1024)} | {("gated",), ("ungated",)}
+    | {("D tiles", "one"), ("D tiles", "many")}
+    | {("window", w) for w in ("(1, 65, 300)", "one bag alone", "64 bags of 1..90 rows")}
+    | {("reduce_dim forward", "K split"), ("reduce_dim forward", "plain")}
+    | {("dW_r TN launch", "one split"), ("dW_r TN launch", "several")}
+    | {("mode", "train, both dropout sites"), ("mode", "eval")} | {("accumulate", 0), ("accumulate", 1)}
+    | {("refused", ERR_SHAPE, f"nseg={n} kseg=32 L=32 H=256 D=128 misalign=") for n in (1, 5)}
+    | {("refused", ERR_SHAPE, "nseg=2 kseg=32 L=64 H=256 D=128 misalign="), ("refused", ERR_SHAPE, "nseg=2 kseg=128 L=128 H=768 D=128 misalign=")}
+    | {("refused", ERR_ALIGN, f"nseg=2 kseg=32 L=32 H=256 D=128 misalign={m}") for m in ("segment", "W", "dW")})
+
+
+@dataclass(frozen=True)
+class Half:
+    radio: int                   # nseg of the radio pair, or 0: mmf_amil_group_forward / _backward
+    L: int
+    H: int
+    D: int
+    gated: bool
+    sizes: tuple
+    ldm_extra: int               # ldm = H + ldm_extra: the width of the caller's feature matrix
+    m_offset: int                # the column of that matrix the stack's H columns start at
+    train: bool = True           # True: p_h = p_att = 0.25; False: eval mode
+    accumulate: int = 0          # of the backward
+    misalign: str = ""           # "dM": the backward's dM 4 bytes off a 16-byte boundary
+    seed: int = 1
+    why: str = ""
+
+    @property
+    def ldm(self):
+        return self.H + self.ldm_extra
+
+    @property
+    def stack(self):
+        return Stack(self.L, self.H, self.D, self.gated)
+
+    @property
+    def size(self):
+        return (self.L, self.H, self.D)
+
+    @property
+    def nseg(self):
+        return self.radio
+
+    @property
+    def kseg(self):
+        return self.L
+
+    @property
+    def R(self):
+        return sum(self.sizes)
+
+
+def half_rule(c, bwd=True):
+    """include/mmf_amil.h mmf_amil_group_forward / _backward and the radio pair; csrc/mmf_api.hip radio_modalities (radio),
+    group_half_check, radio_operands (radio) -- in the library's order.  bwd: the backward half, which reads an ungathered
+    dM (ldm == H) four floats at a time."""
+    if c.radio and (c.radio < 2 or c.radio > 4):
+        return ERR_SHAPE
+    code = group_rule(c.stack, c.sizes)
+    if code != OK:
+        return code
+    if c.ldm < c.H:
+        return ERR_SHAPE
+    if bwd and c.ldm == c.H and c.misalign == "dM":
+        return ERR_ALIGN
+    if c.radio and c.R * c.radio * c.L * 4 >= 2**31:
+        return ERR_SHAPE
+    return OK
+
+
+def half_tags(c):
+    code = half_rule(c)
+    if code != OK:
+        return {("refused", code, f"radio={c.radio} H={c.H} ldm={c.ldm} misalign={c.misalign}")}
+    ldm = "== H" if c.ldm_extra == 0 else "H + 1" if c.ldm_extra == 1 else "3 H" if c.ldm == 3 * c.H else "other"
+    kind = "radio" if c.radio else "plain"
+    t = {("ldm", ldm), ("H", c.H), (kind,), ("mode", "train" if c.train else "eval"), ("accumulate", c.accumulate)}
+    if c.ldm != c.H:
+        t |= {("dM gathered, M merged into a wider matrix", kind), ("slot starts at a non-zero column", c.m_offset > 0)}
+    return t
+
+
+HALF = [
+    Half(0, 96, 256, 128, True, SIXTY_FOUR, 0, 0, seed=50, why="the pathology half on a matrix of its own, 64 bags: ldm == H, dM read in place"),
+    Half(2, 160, 512, 640, True, (1, 65, 300), 1, 1, train=False, accumulate=1, seed=1,
+         why="the radio half, its 512 columns from column 1 of a [3 x 513] matrix: rows of M and dM at every alignment; eval; accumulate"),
+    Half(4, 128, 1024, 128, True, (1, 65, 300), 2048, 1024, seed=3,
+         why="the radio half in the middle third of a [3 x 3072] matrix: H = 1024, the K-split reduce_dim"),
+    Half(0, 32, 1024, 384, False, (1, 65, 300), 1, 1, train=False, seed=83,
+         why="the pathology half with a gathered dM: mmf_amil_group_backward's own call of launch_group_dm_gather"),
+    # refused
+    Half(0, 96, 256, 128, True, (1, 65, 300), -1, 0, why="ldm < H"),
+    Half(0, 96, 256, 128, True, (1, 65, 300), 0, 0, misalign="dM", why="ldm == H and dM 4 bytes off: K-dh reads it four floats at a time"),
+]
+REQUIRED_HALF = (
+    {("ldm", l) for l in ("== H", "H + 1", "3 H")} | {("H", h) for h in (256, 512, 1024)} | {("radio",), ("plain",)}
+    | {("mode", "train"), ("mode", "eval")} | {("accumulate", 0), ("accumulate", 1)}
+    | {("dM gathered, M merged into a wider matrix", k) for k in ("radio", "plain")} | {("slot starts at a non-zero column", True)}
+    | {("refused", ERR_SHAPE, "radio=0 H=256 ldm=255 misalign="), ("refused", ERR_ALIGN, "radio=0 H=256 ldm=256 misalign=dM")})
+
+
+def radio_cap_stacks():
+    """(nseg, stack) the radio row-cap census covers: every admitted stack of the tables above (kseg = L) and the shipped
+    head, each at nseg 2..4."""
+    stacks = [c for c in STACK_F32 if stack_rule(c) == OK] + [Stack(*SHIPPED_HEADS["small"], True)]
+    return [Radio(n, s.L, s.H, s.D, s.gated, (337, 338), True) for s in stacks for n in (2, 3, 4)]
+
+
 TABLES = {
+    "RADIO": (RADIO, radio_tags, REQUIRED_RADIO),
+    "HALF": (HALF, half_tags, REQUIRED_HALF),
     "XFUSION": (XFUSION, xfusion_tags, REQUIRED_XFUSION),
     "mmf_linear_forward": (LINEAR_FORWARD, linear_forward_tags, REQUIRED_LINEAR_FORWARD),
     "mmf_linear_backward": (LINEAR_BACKWARD, linear_backward_tags, REQUIRED_LINEAR_BACKWARD),
