@@ -20,14 +20,6 @@
 
 namespace mmf {
 
-template <class T, class P>
-static int launch_tiled_b(const char* name, void (*kern)(P), const P& p, int grid, int lds_bytes, hipStream_t st) {
-  if (int e = set_dyn_lds(reinterpret_cast<const void*>(kern), lds_bytes)) return e;
-  ProfScope ps(name, st);
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(T::NT), lds_bytes, st, p);
-  return hipGetLastError() == hipSuccess ? MMF_OK : MMF_ERR_LAUNCH;
-}
-
 // =============================================================================================
 // K-cvt : fp32 parameters -> bf16 copies (optionally transposed), a few hundred thousand elements
 // =============================================================================================
@@ -138,11 +130,11 @@ int launch_linear_bf16(LinearBfParams p, hipStream_t st) {
   if (pick_bm(p.M, p.nt_count) == 128) {
     using T = TileS128;
     p.mt_count = (int)((p.M + T::BM - 1) / T::BM);
-    return launch_tiled_b<T>("linear_bf16_kernel", linear_bf16_dma_kernel<T>, p, grid_for_tiles(p.mt_count, p.nt_count), T::LDS_BYTES, st);
+    return launch_tiled<T>("linear_bf16_kernel", linear_bf16_dma_kernel<T>, p, grid_for_tiles(p.mt_count, p.nt_count), st);
   }
   using T = TileS256;
   p.mt_count = (int)((p.M + T::BM - 1) / T::BM);
-  return launch_tiled_b<T>("linear_bf16_kernel", linear_bf16_dma_kernel<T>, p, grid_for_tiles(p.mt_count, p.nt_count), T::LDS_BYTES, st);
+  return launch_tiled<T>("linear_bf16_kernel", linear_bf16_dma_kernel<T>, p, grid_for_tiles(p.mt_count, p.nt_count), st);
 }
 
 // =============================================================================================
@@ -288,8 +280,8 @@ template <class T>
 static int launch_gate_bf16_t(GateBfParams p, hipStream_t st) {
   p.mt_count = (int)((p.N + T::BM - 1) / T::BM);
   const int grid = grid_for_tiles(p.mt_count, p.nt_count);
-  return p.gated ? launch_tiled_b<T>("gate_bf16_kernel", gate_bf16_kernel<T, true>, p, grid, T::LDS_BYTES, st)
-                 : launch_tiled_b<T>("gate_bf16_kernel", gate_bf16_kernel<T, false>, p, grid, T::LDS_BYTES, st);
+  return p.gated ? launch_tiled<T>("gate_bf16_kernel", gate_bf16_kernel<T, true>, p, grid, st)
+                 : launch_tiled<T>("gate_bf16_kernel", gate_bf16_kernel<T, false>, p, grid, st);
 }
 
 int launch_gate_bf16(GateBfParams p, hipStream_t st) {
@@ -934,11 +926,11 @@ int dh_bf16_tiles_used(int64_t N, int ntn) { (void)ntn; return (int)((N + 127) /
 template <class T>
 static int launch_dh_bf16_t(DhBfParams p, hipStream_t st) {
   p.mt_count = (int)((p.N + T::BM - 1) / T::BM);
-  const int bytes = T::LDS_BYTES + (3 * T::BM + 16 + (T::NT / 64) * p.g.D) * 4;
-  if (bytes > 160 * 1024) return MMF_ERR_SHAPE;
+  const int extra = (3 * T::BM + 16 + (T::NT / 64) * p.g.D) * 4;
+  if (T::LDS_BYTES + extra > 160 * 1024) return MMF_ERR_SHAPE;
   const int grid = grid_for_tiles(p.mt_count, p.nt_count);
-  return p.g.gated ? launch_tiled_b<T>("dh_bf16_kernel", dh_bf16_kernel<T, true>, p, grid, bytes, st)
-                   : launch_tiled_b<T>("dh_bf16_kernel", dh_bf16_kernel<T, false>, p, grid, bytes, st);
+  return p.g.gated ? launch_tiled<T>("dh_bf16_kernel", dh_bf16_kernel<T, true>, p, grid, st, extra)
+                   : launch_tiled<T>("dh_bf16_kernel", dh_bf16_kernel<T, false>, p, grid, st, extra);
 }
 
 int launch_dh_bf16(DhBfParams p, hipStream_t st) {
@@ -1175,7 +1167,7 @@ int launch_tn_bf16(TnBfParams p, hipStream_t st) {
   p.total_tiles = blocks;
   static const int env_xcd = tune_int("MMF_BF16_TN_XCD", 1);   // tuning override
   p.xcd_map = env_xcd && p.splits % 8 == 0;
-  return launch_tiled_b<T>("tn_bf16_kernel", tn_bf16_kernel<T>, p, p.splits * blocks, T::LDS_BYTES, st);
+  return launch_tiled<T>("tn_bf16_kernel", tn_bf16_kernel<T>, p, p.splits * blocks, st);
 }
 
 }  // namespace mmf

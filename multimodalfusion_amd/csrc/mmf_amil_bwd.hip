@@ -1337,196 +1337,147 @@ __global__ __launch_bounds__(256) void reduce_kernel(ReduceParams p) {
 // =============================================================================================
 // host launchers
 // =============================================================================================
-template <class T, class P>
-static int launch_tiled(const char* name, void (*kern)(P), const P& p, int grid, hipStream_t st) {
-  if (int e = set_dyn_lds(reinterpret_cast<const void*>(kern), T::LDS_BYTES)) return e;
-  ProfScope ps(name, st);
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(T::NT), T::LDS_BYTES, st, p);
-  return hipGetLastError() == hipSuccess ? MMF_OK : MMF_ERR_LAUNCH;
-}
-
 int launch_bwd_prep(BwdPrepParams p, hipStream_t st) {
   if (p.H % 4 != 0 || p.H > 1024) return MMF_ERR_SHAPE;
   { ProfScope ps("bwd_prep_kernel", st); hipLaunchKernelGGL(bwd_prep_kernel, dim3(p.n_groups), dim3(256), 0, st, p); }
   return hipGetLastError() == hipSuccess ? MMF_OK : MMF_ERR_LAUNCH;
 }
 
-// launch with extra dynamic LDS behind the staging buffers (fused prep scratch)
-template <class T, class P>
-static int launch_tiled_extra(const char* name, void (*kern)(P), const P& p, int grid, int extra_bytes, hipStream_t st) {
-  const int bytes = T::LDS_BYTES + extra_bytes;
-  if (int e = set_dyn_lds(reinterpret_cast<const void*>(kern), bytes)) return e;
-  ProfScope ps(name, st);
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(T::NT), bytes, st, p);
-  return hipGetLastError() == hipSuccess ? MMF_OK : MMF_ERR_LAUNCH;
-}
-
-template <int ROWS>
-static int launch_bwd_dh_wide(BwdDhParams p, hipStream_t st) {
-  using T = Tile<ROWS, 256, 1, 8, true, false>;
-  p.mt_count = (int)((p.N + T::BM - 1) / T::BM); p.nt_count = p.H / 256;
-  const int grid = grid_for_tiles(p.mt_count, p.nt_count);
-  if (p.fused_prep) {
-    constexpr int extra = (3 * T::BM + 16) * 4;
-    switch ((p.g.gated ? 2 : 0) + (p.g.drop_p > 0.f ? 1 : 0)) {      // gate / dropout switches compiled in
-      case 0: return launch_tiled_extra<T>("bwd_dh_kernel", bwd_dh_kernel<T, true, 0>, p, grid, extra, st);
-      case 1: return launch_tiled_extra<T>("bwd_dh_kernel", bwd_dh_kernel<T, true, 1>, p, grid, extra, st);
-      case 2: return launch_tiled_extra<T>("bwd_dh_kernel", bwd_dh_kernel<T, true, 2>, p, grid, extra, st);
-      // gated + attention dropout: two hashes per element inlined 16 times overflow the 256 VGPRs (48 spilled
-      // inside the loop) -- that combination keeps the run-time switches
-      default: return launch_tiled_extra<T>("bwd_dh_kernel", bwd_dh_kernel<T, true>, p, grid, extra, st);
-    }
-  }
-  return launch_tiled<T>("bwd_dh_kernel", bwd_dh_kernel<T, false>, p, grid, st);
-}
-
-// > 0: the wide path will be taken and the kernel does K-prep itself, writing that many dbc partials
-static inline bool dh_short_grid(int64_t N, int H, int split = 0) {       // the 64x64 tiles on a grid of at most 512 workgroups
-  static const int cap = tune_int("MMF_DH_SHORT_MAX", 1024);   // tuning override (round 4, 10k-14k bags: K-prep inside the 64 x 64 tiles, +5.4 us, against its own launch, 9.7 us)
-  return !use_wide_tiles(N, H, split) && (N / 128) * ((H + 127) / 128) < 256 && ((N + 63) / 64) * ((H + 63) / 64) <= cap;
-}
-// the split-operand mode's 64 x 64 K-dh tiles: every bag below its wide tiles
-static inline bool dh_split_small_ok(int64_t N, int H, int D, int gated, int split) {
-  return split && !use_wide_tiles(N, H, 1) && N >= split_min_rows() && ((gated ? 2 : 1) * D / SKC) % 4 == 0;
-}
-// the split-operand K-dh: the training step's shape only (fused K-prep, wide tiles)
-bool bwd_dh_split_ok(int64_t N, int H, int D, int gated, int split) {
-  return split && use_wide_tiles(N, H, 1) && ((gated ? 2 : 1) * D / SKC) % 4 == 0;
-}
-int bwd_dh_split_rows(int64_t N) { (void)N; return 224; }
-
+// ---- K-dh: one plan, one launcher ----------------------------------------------------------------------------------
 // K-dh's tallest tile: the 240-row tile of the training variant (gated, relu bits) spills 28 registers (112 B per lane)
 constexpr int DH_MAX_ROWS = 224;
+
+DhPlan plan_bwd_dh(int64_t N, int H, int D, int gated, int dropout, int split, int concurrent, int can_fuse, int dbc_cap) {
+  static const int fuse_env = tune_int("MMF_FUSED_PREP", 1);
+  static const int short_max = tune_int("MMF_DH_SHORT_MAX", 1024);   // tuning override (round 4, 10k-14k bags: K-prep inside the 64 x 64 tiles, +5.4 us, against its own launch, 9.7 us)
+  // 64 x 128 tiles (two column tiles of a row tile instead of four: the dP operand and K-prep are built twice, not four
+  // times, and a workgroup's chunk holds 32 MFMAs per wave instead of 16) where they fill the 512 slots once: measured
+  // (round 4, same call, K-dh us 64 x 64 -> 64 x 128): 14,000 rows 56.7 -> 50.0, 16,000 57.1 -> 50.1; 12,288 43.2 -> 49.1,
+  // 10,000 42.6 -> 49.0, 4,096 23.8 -> 33.1 -- a round of these tiles is 50 us whatever fills it, so only from 13,000 rows
+  static const int min_64x128 = tune_int("MMF_DH_64X128", 13000);
+  const int mode = (gated ? 2 : 0) + (dropout ? 1 : 0);
+  // the split-operand core: its wide tile exists with K-prep fused in only (the training step's shape), its 64 x 64 tile
+  // takes every bag below the wide tiles
+  const bool split_k = split && ((gated ? 2 : 1) * D / SKC) % 4 == 0;
+  const bool split_wide = split_k && use_wide_tiles(N, H, 1);
+  const bool split_64 = split_k && !use_wide_tiles(N, H, 1) && N >= split_min_rows();
+  const bool wide = use_wide_tiles(N, H, split);
+  const bool big = (N / 128) * ((H + 127) / 128) >= 256;
+  const bool deep_k = gated && (2 * D / KC) % 4 == 0;         // dh_mainloop_deep: the gated loaders, four chunks a step
+  // short grids of 64-row tiles: every column tile redoes K-prep for its 64 rows (64 KB of h) -- cheaper than a launch of its own
+  const bool short_64 = !use_wide_tiles(N, H, split_64) && !big && ((N + 63) / 64) * ((H + 63) / 64) <= short_max;
+  auto wide_rows = [&](bool allow_half) {      // a height no tile is compiled for (an override's) runs as 224 rows
+    const int r = pick_wide_rows(N, H / 256, allow_half, concurrent != 0, DH_MAX_ROWS);
+    return r >= 64 && r <= DH_MAX_ROWS && r % 16 == 0 ? r : 224;
+  };
+
+  // The height K-dh would run at with K-prep fused in (0: no such tile), and whether its dbc partials, one per row tile,
+  // fit dbc_part.  The fused launch has the forward's relu bits, and with them the epilogue of the 16-row half block.
+  int fuse_rows = 0;
+  if (short_64) fuse_rows = 64;
+  else if (split_64 || !wide) fuse_rows = 0;
+  else fuse_rows = split_wide ? 224 : wide_rows(true);
+  DhPlan pl{};
+  pl.fused = can_fuse && fuse_env && fuse_rows > 0 && (N + fuse_rows - 1) / fuse_rows <= dbc_cap;
+  pl.variant = -1;
+  if (pl.fused && split_wide) {
+    pl.kind = DH_SPLIT_WIDE; pl.rows = 224; pl.nt_count = H / 256; pl.variant = mode;
+  } else if (split_64) {
+    pl.kind = DH_SPLIT_64; pl.rows = 64; pl.nt_count = (H + 63) / 64; pl.variant = mode;
+  } else if (wide) {
+    pl.kind = DH_WIDE; pl.rows = pl.fused ? fuse_rows : wide_rows(false); pl.nt_count = H / 256;
+    // gated + attention dropout: two hashes per element inlined 16 times overflow the 256 VGPRs (48 spilled inside the
+    // loop) -- that combination keeps the run-time switches
+    if (pl.fused && mode < 3) pl.variant = mode;
+  } else if (big) {
+    pl.kind = DH_128; pl.rows = 128; pl.nt_count = (H + 127) / 128;
+  } else if (min_64x128 > 0 && N >= min_64x128 && pl.fused && deep_k && H % 128 == 0) {
+    pl.kind = DH_64X128; pl.rows = 64; pl.nt_count = H / 128; pl.deep = 1;
+  } else {
+    pl.kind = DH_64; pl.rows = 64; pl.nt_count = (H + 63) / 64;
+  }
+  pl.mt_count = (int)((N + pl.rows - 1) / pl.rows);
+  if (pl.kind == DH_64) pl.deep = short_grid((int64_t)pl.mt_count * pl.nt_count) && deep_k ? 1 : 0;
+  pl.grid = grid_for_tiles(pl.mt_count, pl.nt_count);
+  pl.extra_lds = pl.fused ? (3 * pl.rows + 16) * 4 : 0;
+  pl.dbc_groups = pl.fused ? pl.mt_count : 0;
+  return pl;
+}
 int bwd_dh_fused_groups(int64_t N, int H, int allow_half, int D, int gated, int split, int concurrent) {
-  static const int env = tune_int("MMF_FUSED_PREP", 1);
-  if (!env) return 0;
-  // short grids: every column tile redoes K-prep for its 64 rows (64 KB of h) -- cheaper than a launch of its own
-  const int sm = dh_split_small_ok(N, H, D, gated, split);
-  if (dh_short_grid(N, H, sm)) return (int)((N + 63) / 64);
-  if (sm || !use_wide_tiles(N, H, split)) return 0;
-  if (bwd_dh_split_ok(N, H, D, gated, split)) return (int)((N + bwd_dh_split_rows(N) - 1) / bwd_dh_split_rows(N));
-  const int rows = pick_wide_rows(N, H / 256, allow_half != 0, concurrent != 0, DH_MAX_ROWS);   // the fused launch always has the forward's relu bits
-  return (int)((N + rows - 1) / rows);
+  (void)allow_half;
+  return plan_bwd_dh(N, H, D, gated, 0, split, concurrent, 1, 0x7fffffff).dbc_groups;
 }
 
+// The tile of each (kind, height) and the forms it is compiled in: FUSED (K-prep inside) and PLAIN (after a K-prep launch;
+// the grouped step's SEG instantiations are PLAIN forms of the exact-fp32 tiles).  The plain epilogue has no code for the
+// 16-row half block, so a half-block height is compiled fused only.
+template <class T_, bool FUSED_, bool PLAIN_>
+struct DhTile { using T = T_; static constexpr bool FUSED = FUSED_, PLAIN = PLAIN_; };
 template <int ROWS>
-static int launch_bwd_dh_split(BwdDhParams p, hipStream_t st) {
-  using T = TileSp<ROWS, 256, 1, 8>;
-  p.mt_count = (int)((p.N + T::BM - 1) / T::BM); p.nt_count = p.H / 256;
-  const int grid = grid_for_tiles(p.mt_count, p.nt_count);
-  constexpr int extra = (3 * T::BM + 16) * 4;
-  switch ((p.g.gated ? 2 : 0) + (p.g.drop_p > 0.f ? 1 : 0)) {
-    case 0: return launch_tiled_extra<T>("bwd_dh_split_kernel", bwd_dh_kernel<T, true, 0>, p, grid, extra, st);
-    case 1: return launch_tiled_extra<T>("bwd_dh_split_kernel", bwd_dh_kernel<T, true, 1>, p, grid, extra, st);
-    case 2: return launch_tiled_extra<T>("bwd_dh_split_kernel", bwd_dh_kernel<T, true, 2>, p, grid, extra, st);
-    default: return launch_tiled_extra<T>("bwd_dh_split_kernel", bwd_dh_kernel<T, true, 3>, p, grid, extra, st);
-  }
-}
+using DhWide = DhTile<Tile<ROWS, 256, 1, 8, true, false>, true, ROWS % 32 == 0>;
 
-// 64 x 64 split tiles for bags below the wide tiles (with or without the fused K-prep)
-static int launch_bwd_dh_split_small(BwdDhParams p, hipStream_t st) {
-  using T = TileSp<64, 64, 2, 2>;
-  p.mt_count = (int)((p.N + 63) / 64); p.nt_count = (p.H + 63) / 64;
-  const int grid = grid_for_tiles(p.mt_count, p.nt_count);
-  constexpr int extra = (3 * T::BM + 16) * 4;
-  const int mode = (p.g.gated ? 2 : 0) + (p.g.drop_p > 0.f ? 1 : 0);
-  if (p.fused_prep) {
-    switch (mode) {
-      case 0: return launch_tiled_extra<T>("bwd_dh_split_kernel", bwd_dh_kernel<T, true, 0>, p, grid, extra, st);
-      case 1: return launch_tiled_extra<T>("bwd_dh_split_kernel", bwd_dh_kernel<T, true, 1>, p, grid, extra, st);
-      case 2: return launch_tiled_extra<T>("bwd_dh_split_kernel", bwd_dh_kernel<T, true, 2>, p, grid, extra, st);
-      default: return launch_tiled_extra<T>("bwd_dh_split_kernel", bwd_dh_kernel<T, true, 3>, p, grid, extra, st);
-    }
-  }
-  switch (mode) {
-    case 0: return launch_tiled<T>("bwd_dh_split_kernel", bwd_dh_kernel<T, false, 0>, p, grid, st);
-    case 1: return launch_tiled<T>("bwd_dh_split_kernel", bwd_dh_kernel<T, false, 1>, p, grid, st);
-    case 2: return launch_tiled<T>("bwd_dh_split_kernel", bwd_dh_kernel<T, false, 2>, p, grid, st);
-    default: return launch_tiled<T>("bwd_dh_split_kernel", bwd_dh_kernel<T, false, 3>, p, grid, st);
-  }
-}
-
-int launch_bwd_dh(BwdDhParams p, hipStream_t st) {
-  if (p.g.D % KC != 0 || p.H % 4 != 0) return MMF_ERR_SHAPE;
-  if (p.N <= 0) return MMF_OK;
-  if (p.fused_prep && bwd_dh_split_ok(p.N, p.H, p.g.D, p.g.gated, p.split)) return launch_bwd_dh_split<224>(p, st);
-  if (dh_split_small_ok(p.N, p.H, p.g.D, p.g.gated, p.split) && (!p.fused_prep || dh_short_grid(p.N, p.H, 1)))
-    return launch_bwd_dh_split_small(p, st);
-  if (use_wide_tiles(p.N, p.H, p.split)) {
-    // the half-block tile's epilogue exists for the relu-bits path only (every stack backward; not the standalone scorer)
-    switch (pick_wide_rows(p.N, p.H / 256, p.allow_half && p.fused_prep && p.relu_bits, p.concurrent != 0, DH_MAX_ROWS)) {
-#define MMF_WIDE_CASE(R) case R: return launch_bwd_dh_wide<R>(p, st);
-      MMF_WIDE_CASE(64) MMF_WIDE_CASE(80) MMF_WIDE_CASE(96) MMF_WIDE_CASE(112) MMF_WIDE_CASE(128)
-      MMF_WIDE_CASE(144) MMF_WIDE_CASE(160) MMF_WIDE_CASE(176) MMF_WIDE_CASE(192) MMF_WIDE_CASE(208)
+template <class F>
+static int with_dh_tile(const DhPlan& pl, F&& f) {
+  switch (pl.kind) {
+    case DH_SPLIT_WIDE: return f(DhTile<TileSp<224, 256, 1, 8>, true, false>{});
+    case DH_SPLIT_64: return f(DhTile<TileSp<64, 64, 2, 2>, true, true>{});
+    case DH_128: return f(DhTile<Tile<128, 128, 2, 2, true, false>, false, true>{});
+    case DH_64X128: return f(DhTile<Tile<64, 128, 2, 2, true, false>, true, false>{});
+    case DH_64: return f(DhTile<Tile<64, 64, 2, 2, true, false>, true, true>{});
+    case DH_WIDE:
+      switch (pl.rows) {
+#define MMF_WIDE_CASE(R) case R: return f(DhWide<R>{});
+        MMF_WIDE_CASE(64) MMF_WIDE_CASE(80) MMF_WIDE_CASE(96) MMF_WIDE_CASE(112) MMF_WIDE_CASE(128) MMF_WIDE_CASE(144)
+        MMF_WIDE_CASE(160) MMF_WIDE_CASE(176) MMF_WIDE_CASE(192) MMF_WIDE_CASE(208) MMF_WIDE_CASE(224)
 #undef MMF_WIDE_CASE
-      default: return launch_bwd_dh_wide<224>(p, st);
-    }
+      }
   }
-  if (p.fused_prep && !dh_short_grid(p.N, p.H)) return MMF_ERR_ARG;
-  const int ntn = (p.H + 127) / 128;
-  if ((p.N / 128) * ntn >= 256) {
-    using T = Tile<128, 128, 2, 2, true, false>;
-    p.mt_count = (int)((p.N + 127) / 128); p.nt_count = ntn;
-    return launch_tiled<T>("bwd_dh_kernel", bwd_dh_kernel<T, false>, p, grid_for_tiles(p.mt_count, p.nt_count), st);
-  }
-  {
-    // 64 x 128 tiles (two column tiles of a row tile instead of four: the dP operand and K-prep are built twice, not four
-    // times, and a workgroup's chunk holds 32 MFMAs per wave instead of 16) where they fill the 512 slots once: measured
-    // (round 4, same call, K-dh us 64 x 64 -> 64 x 128): 14,000 rows 56.7 -> 50.0, 16,000 57.1 -> 50.1; 12,288 43.2 -> 49.1,
-    // 10,000 42.6 -> 49.0, 4,096 23.8 -> 33.1 -- a round of these tiles is 50 us whatever fills it, so only from 13,000 rows
-    static const int wide_min = tune_int("MMF_DH_64X128", 13000);
-    if (wide_min > 0 && p.N >= wide_min && p.fused_prep && p.g.gated && p.H % 128 == 0 && (2 * p.g.D / KC) % 4 == 0) {
-      using T2 = Tile<64, 128, 2, 2, true, false>;
-      p.mt_count = (int)((p.N + 63) / 64); p.nt_count = p.H / 128;
-      p.deep = 1;
-      return launch_tiled_extra<T2>("bwd_dh_kernel", bwd_dh_kernel<T2, true>, p, grid_for_tiles(p.mt_count, p.nt_count),
-                                    (3 * T2::BM + 16) * 4, st);
-    }
-  }
-  using T = Tile<64, 64, 2, 2, true, false>;
-  p.mt_count = (int)((p.N + 63) / 64); p.nt_count = (p.H + 63) / 64;
-  static const int env_deep = tune_int("MMF_DEEP", 1);     // A/B switch
-  static const int deep_cap = tune_int("MMF_DEEP_MAX", 1024);   // tuning override (10k bag, 628 workgroups: 252 -> 242 us per step)
-  p.deep = env_deep && (int64_t)p.mt_count * p.nt_count <= deep_cap && p.g.gated && (2 * p.g.D / KC) % 4 == 0 ? 1 : 0;
-  if (p.fused_prep)
-    return launch_tiled_extra<T>("bwd_dh_kernel", bwd_dh_kernel<T, true>, p, grid_for_tiles(p.mt_count, p.nt_count),
-                                 (3 * T::BM + 16) * 4, st);
-  return launch_tiled<T>("bwd_dh_kernel", bwd_dh_kernel<T, false>, p, grid_for_tiles(p.mt_count, p.nt_count), st);
+  return MMF_ERR_ARG;
 }
 
-// Grouped step: the same tile plan as launch_bwd_dh without fused prep (K-prep ran as group_bwd_prep_kernel), the SEG
-// instantiations.  Wide tiles take whole 32-row blocks only (the half block's epilogue needs fused prep).
-template <int ROWS>
-static int launch_bwd_dh_wide_seg(BwdDhParams p, hipStream_t st) {
-  using T = Tile<ROWS, 256, 1, 8, true, false>;
-  p.mt_count = (int)((p.N + T::BM - 1) / T::BM); p.nt_count = p.H / 256;
-  return launch_tiled<T>("bwd_dh_kernel", bwd_dh_kernel<T, false, -1, true>, p, grid_for_tiles(p.mt_count, p.nt_count), st);
+// the plan's variant number as a template argument: 0 .. 2 as they are, anything else as LAST
+template <int LAST, class F>
+static int with_variant(int variant, F&& f) {
+  switch (variant) {
+    case 0: return f(std::integral_constant<int, 0>{});
+    case 1: return f(std::integral_constant<int, 1>{});
+    case 2: return f(std::integral_constant<int, 2>{});
+    default: return f(std::integral_constant<int, LAST>{});
+  }
 }
-int launch_bwd_dh_seg(BwdDhParams p, hipStream_t st) {
+
+template <bool SEG>
+static int launch_dh_plan(const DhPlan& pl, BwdDhParams p, hipStream_t st) {
   if (p.g.D % KC != 0 || p.H % 4 != 0) return MMF_ERR_SHAPE;
-  if (p.fused_prep || p.split || !p.seg_bag || !p.seg_ridx || !p.dM || !p.p || !p.h) return MMF_ERR_ARG;
+  if (SEG && (pl.fused || p.split || !p.seg_bag || !p.seg_ridx || !p.dM || !p.p || !p.h)) return MMF_ERR_ARG;
   if (p.N <= 0) return MMF_OK;
-  if (use_wide_tiles(p.N, p.H, 0)) {
-    switch (pick_wide_rows(p.N, p.H / 256, false, p.concurrent != 0, DH_MAX_ROWS)) {
-#define MMF_WIDE_CASE(R) case R: return launch_bwd_dh_wide_seg<R>(p, st);
-      MMF_WIDE_CASE(64) MMF_WIDE_CASE(96) MMF_WIDE_CASE(128) MMF_WIDE_CASE(160) MMF_WIDE_CASE(192)
-#undef MMF_WIDE_CASE
-      default: return launch_bwd_dh_wide_seg<224>(p, st);
+  p.mt_count = pl.mt_count; p.nt_count = pl.nt_count; p.deep = pl.deep; p.fused_prep = pl.fused;
+  return with_dh_tile(pl, [&](auto tile) -> int {
+    using E = decltype(tile);
+    using T = typename E::T;
+    using Yes = std::true_type;
+    using No = std::false_type;
+    using RunTime = std::integral_constant<int, -1>;
+    auto go = [&](auto fused, auto mode) -> int {
+      return launch_tiled<T>(T::SPLIT ? "bwd_dh_split_kernel" : "bwd_dh_kernel",
+                             bwd_dh_kernel<T, decltype(fused)::value, decltype(mode)::value, SEG>, p, pl.grid, st, pl.extra_lds);
+    };
+    // compiled-in variants: all four on the split-operand tiles, 0 .. 2 on the fused wide ones, none elsewhere
+    if constexpr (SEG) {
+      if constexpr (E::PLAIN && !T::SPLIT) return go(No{}, RunTime{});
+    } else if (pl.fused) {
+      if constexpr (E::FUSED && T::SPLIT) return with_variant<3>(pl.variant, [&](auto mode) { return go(Yes{}, mode); });
+      else if constexpr (E::FUSED && T::BN == 256) return with_variant<-1>(pl.variant, [&](auto mode) { return go(Yes{}, mode); });
+      else if constexpr (E::FUSED) return go(Yes{}, RunTime{});
+    } else if constexpr (E::PLAIN) {
+      if constexpr (T::SPLIT) return with_variant<3>(pl.variant, [&](auto mode) { return go(No{}, mode); });
+      else return go(No{}, RunTime{});
     }
-  }
-  const int ntn = (p.H + 127) / 128;
-  if ((p.N / 128) * ntn >= 256) {
-    using T = Tile<128, 128, 2, 2, true, false>;
-    p.mt_count = (int)((p.N + 127) / 128); p.nt_count = ntn;
-    return launch_tiled<T>("bwd_dh_kernel", bwd_dh_kernel<T, false, -1, true>, p, grid_for_tiles(p.mt_count, p.nt_count), st);
-  }
-  using T = Tile<64, 64, 2, 2, true, false>;
-  p.mt_count = (int)((p.N + 63) / 64); p.nt_count = (p.H + 63) / 64;
-  static const int env_deep = tune_int("MMF_DEEP", 1);
-  static const int deep_cap = tune_int("MMF_DEEP_MAX", 1024);
-  p.deep = env_deep && (int64_t)p.mt_count * p.nt_count <= deep_cap && p.g.gated && (2 * p.g.D / KC) % 4 == 0 ? 1 : 0;
-  return launch_tiled<T>("bwd_dh_kernel", bwd_dh_kernel<T, false, -1, true>, p, grid_for_tiles(p.mt_count, p.nt_count), st);
+    return MMF_ERR_ARG;      // a plan pairs no tile with a form it is not compiled in
+  });
 }
+int launch_bwd_dh(const DhPlan& pl, BwdDhParams p, hipStream_t st) { return launch_dh_plan<false>(pl, p, st); }
+int launch_bwd_dh_seg(const DhPlan& pl, BwdDhParams p, hipStream_t st) { return launch_dh_plan<true>(pl, p, st); }
 
 // Grouped K-prep: one wave per instance (as bwd_prep_kernel), with the softmax statistics, M and dM of the instance's
 // bag (p.stats [G x 2], p.M / p.dM [G x H]); dM.M is recomputed when a wave's next instance lies in another bag.
@@ -1575,38 +1526,34 @@ int launch_group_bwd_prep(BwdPrepParams p, const int* bag, hipStream_t st) {
   return hipGetLastError() == hipSuccess ? MMF_OK : MMF_ERR_LAUNCH;
 }
 
-int launch_nn(NnParams p, hipStream_t st) {
-  if (p.K % KC != 0 || p.lda % 4 != 0 || p.ldb % 4 != 0 || p.N % 4 != 0) return MMF_ERR_SHAPE;
-  if (p.M <= 0) return MMF_OK;
+// the NN GEMM's tiles: 128 x 128 once they fill the chip, else 64 x 64; ATTR: the attribution epilogue
+template <bool ATTR>
+static int launch_nn_tiles(NnParams p, hipStream_t st) {
+  const char* name = ATTR ? "gemm_nn_attr_kernel" : "gemm_nn_kernel";
   const int ntn = (p.N + 127) / 128;
   if ((p.M / 128) * ntn >= 256) {
     using T = Tile<128, 128, 2, 2, true, false>;
     p.mt_count = (int)((p.M + 127) / 128); p.nt_count = ntn;
-    return launch_tiled<T>("gemm_nn_kernel", gemm_nn_kernel<T>, p, grid_for_tiles(p.mt_count, p.nt_count), st);
+    return launch_tiled<T>(name, gemm_nn_kernel<T, ATTR>, p, grid_for_tiles(p.mt_count, p.nt_count), st);
   }
   using T = Tile<64, 64, 2, 2, true, false>;
   p.mt_count = (int)((p.M + 63) / 64); p.nt_count = (p.N + 63) / 64;
-  return launch_tiled<T>("gemm_nn_kernel", gemm_nn_kernel<T>, p, grid_for_tiles(p.mt_count, p.nt_count), st);
+  return launch_tiled<T>(name, gemm_nn_kernel<T, ATTR>, p, grid_for_tiles(p.mt_count, p.nt_count), st);
 }
 
-// launch_nn's tile plan with the attribution epilogue, then the rows kernel over its partials
+int launch_nn(NnParams p, hipStream_t st) {
+  if (p.K % KC != 0 || p.lda % 4 != 0 || p.ldb % 4 != 0 || p.N % 4 != 0) return MMF_ERR_SHAPE;
+  if (p.M <= 0) return MMF_OK;
+  return launch_nn_tiles<false>(p, st);
+}
+
+// launch_nn's tiles with the attribution epilogue, then the rows kernel over its partials
 int launch_nn_attr(NnParams p, float* row_sum, float* row_abs, hipStream_t st) {
   if (!p.mulx || !p.rs_part || !p.ra_part || !row_sum || !row_abs) return MMF_ERR_ARG;
   if (p.K % KC != 0 || p.lda % 4 != 0 || p.ldb % 4 != 0 || p.N % 32 != 0 || p.ldx % 4 != 0 || (p.C && p.ldc % 4 != 0))
     return MMF_ERR_SHAPE;
   if (p.M <= 0) return MMF_OK;
-  const int ntn = (p.N + 127) / 128;
-  if ((p.M / 128) * ntn >= 256) {
-    using T = Tile<128, 128, 2, 2, true, false>;
-    p.mt_count = (int)((p.M + 127) / 128); p.nt_count = ntn;
-    if (int e = launch_tiled<T>("gemm_nn_attr_kernel", gemm_nn_kernel<T, true>, p, grid_for_tiles(p.mt_count, p.nt_count), st))
-      return e;
-  } else {
-    using T = Tile<64, 64, 2, 2, true, false>;
-    p.mt_count = (int)((p.M + 63) / 64); p.nt_count = (p.N + 63) / 64;
-    if (int e = launch_tiled<T>("gemm_nn_attr_kernel", gemm_nn_kernel<T, true>, p, grid_for_tiles(p.mt_count, p.nt_count), st))
-      return e;
-  }
+  if (int e = launch_nn_tiles<true>(p, st)) return e;
   ProfScope ps("ig_rows_kernel", st);
   hipLaunchKernelGGL(ig_rows_kernel, dim3((unsigned)((p.M + 255) / 256)), dim3(256), 0, st, p.rs_part, p.ra_part, p.M,
                      p.N / 32, row_sum, row_abs);

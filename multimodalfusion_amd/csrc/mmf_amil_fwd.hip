@@ -731,16 +731,8 @@ int launch_score_sum(const float* s_part, int n_parts, const float* bc, float* A
 // =============================================================================================
 // host launchers
 // =============================================================================================
-template <class T, class P>
-static int launch_tiled(const char* name, void (*kern)(P), const P& p, int grid, hipStream_t st) {
-  if (int e = set_dyn_lds(reinterpret_cast<const void*>(kern), T::LDS_BYTES)) return e;
-  ProfScope ps(name, st);
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(T::NT), T::LDS_BYTES, st, p);
-  return hipGetLastError() == hipSuccess ? MMF_OK : MMF_ERR_LAUNCH;
-}
-
 // a grid this short leaves every workgroup alone on its CU: nothing hides a memory round trip but deeper prefetch
-static inline bool short_grid(int64_t workgroups) {
+bool short_grid(int64_t workgroups) {
   static const int env = tune_int("MMF_DEEP", 1);     // A/B switch
   static const int cap = tune_int("MMF_DEEP_MAX", 1024);   // tuning override (10k bag, 628 workgroups: 252 -> 242 us per step)
   return env && workgroups <= cap;

@@ -79,8 +79,6 @@ void prof_end(hipStream_t st) {
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
-constexpr int PREP_GROUPS = 512;
-
 // Bump allocator over a caller's workspace: every slot starts on a 256-byte boundary.  With a null base it only counts
 // (the *_workspace_bytes queries); `off` is the size carved so far.
 struct Carver {
@@ -232,8 +230,8 @@ static int check_operands(const mmf_amil_desc* d, const void* x, const void* wor
 // uses the gate builders with h = x.  Each chain then sets only what is its own.
 //
 // The grouped chain runs the same fields through its `_seg` launchers, where they end up the same or are not read:
-// `split` is derived from desc->gemm and is 0 there, because group_check refuses bf16x3; launch_bwd_dh_seg never reads
-// BwdDhParams::allow_half and refuses fused_prep.  A carve for inference leaves relu_bits, a and b null.
+// `split` is derived from desc->gemm and is 0 there, because group_check refuses bf16x3; K-dh's plan is asked for without
+// fused K-prep (dh_plan).  A carve for inference leaves relu_bits, a and b null.
 
 static GateFwdParams gate_fwd_params(const mmf_amil_desc* d, const float* h, float* a, float* b, float* s_part,
                                      uint32_t seed) {
@@ -300,15 +298,20 @@ static BwdPrepParams stack_prep(const mmf_amil_desc* d, const AmilWs& w, const f
   return bp;
 }
 
-// K-dh: du = (dP.Wab + p dM) * relu'(h) * scale_h; fused_prep 0 (the one-bag chain may fuse K-prep in)
+// K-dh: du = (dP.Wab + p dM) * relu'(h) * scale_h, without the inputs of a fused K-prep (the one-bag chain adds them)
 static BwdDhParams stack_dh(const mmf_amil_desc* d, const AmilWs& w, const GateBwdCtx& gc, const float* dM) {
   BwdDhParams dp{};
   dp.g = gc; dp.Wa = d->Wa; dp.Wb = d->Wb; dp.p = w.p; dp.dM = dM; dp.h = w.h; dp.du = w.du;
   dp.relu_bits = w.relu_bits;
-  dp.allow_half = 1; dp.concurrent = d->concurrent ? 1 : 0;
+  dp.concurrent = d->concurrent ? 1 : 0;
   dp.split = d->gemm == MMF_GEMM_BF16X3;
   dp.N = d->N; dp.H = d->H; dp.scale_h = d->p_h > 0.f ? 1.0f / (1.0f - d->p_h) : 1.0f;
   return dp;
+}
+
+// K-dh's plan for these parameters; can_fuse: the caller can hand K-dh what K-prep reads (DhPlan)
+static DhPlan dh_plan(const BwdDhParams& p, bool can_fuse) {
+  return plan_bwd_dh(p.N, p.H, p.g.D, p.g.gated, p.g.drop_p > 0.f, p.split, p.concurrent, can_fuse, PREP_GROUPS);
 }
 
 // d(input) = du . W1
@@ -541,10 +544,10 @@ static int amil_backward_impl(const mmf_amil_desc* d, const float* x, void* work
 
   const GateBwdCtx gc = gate_bwd_ctx(d, w.a, w.b, w.ds, d->seed);
   BwdDhParams dp = stack_dh(d, w, gc, dM);
-  // K-prep (softmax weights, ds) either fused into the wide K-dh kernel or as its own launch
-  int dbc_groups = bwd_dh_fused_groups(d->N, d->H, 1, d->D, d->gated, dp.split, d->concurrent ? 1 : 0);
-  if (dbc_groups > 0 && dbc_groups <= PREP_GROUPS) {
-    dp.fused_prep = 1;
+  // K-prep (softmax weights, ds) either inside K-dh or as its own launch
+  const DhPlan pl = dh_plan(dp, true);
+  int dbc_groups = pl.dbc_groups;
+  if (pl.fused) {
     dp.A_raw = A_raw; dp.stats = w.stats; dp.Mpool = M; dp.gA = gA;
     dp.p_out = w.p; dp.ds_out = w.ds; dp.dbc_part = w.dbc_part;
   } else {
@@ -552,7 +555,7 @@ static int amil_backward_impl(const mmf_amil_desc* d, const float* x, void* work
     dbc_groups = bp.n_groups;
     if (int e = launch_bwd_prep(bp, st)) return e;
   }
-  if (int e = launch_bwd_dh(dp, st)) return e;
+  if (int e = launch_bwd_dh(pl, dp, st)) return e;
   if (g->dx) {   // radio: the input is reduce_dim's output
     if (int e = launch_nn(stack_dx(d, w, g->dx), st)) return e;
   }
@@ -869,7 +872,7 @@ static int group_chain_bwd(const mmf_amil_desc* d, const float* x, const GroupWs
   const GateBwdCtx gc = gate_bwd_ctx(d, w.a, w.b, w.ds, 0);
   BwdDhParams dp = stack_dh(d, w, gc, dM);
   dp.seg_ridx = gw.ridx_d; dp.seg_bag = gw.bag;
-  if (int e = launch_bwd_dh_seg(dp, st)) return e;
+  if (int e = launch_bwd_dh_seg(dh_plan(dp, false), dp, st)) return e;
 
   if (ex && ex->dx) {   // d(x) = du . W1: du carries every bag's ReLU and dropout masks
     if (int e = launch_nn(stack_dx(d, w, ex->dx), st)) return e;
@@ -1454,7 +1457,7 @@ static int ig_window(const mmf_amil_desc* d, const IgWs& g, const float* alpha, 
   const GateBwdCtx gc = gate_bwd_ctx(&dw, w.a, w.b, w.ds, 0);
   BwdDhParams dp = stack_dh(&dw, w, gc, g.dM);
   dp.seg_ridx = g.ridx_d; dp.seg_bag = g.bag;
-  if (int e = launch_bwd_dh_seg(dp, st)) return e;
+  if (int e = launch_bwd_dh_seg(dh_plan(dp, false), dp, st)) return e;
 
   IgFoldParams fp{};
   fp.du = w.du; fp.G = g.G; fp.N = N; fp.H = d->H; fp.first = first ? 1 : 0;
@@ -1825,7 +1828,7 @@ int mmf_attn_net_backward(const mmf_amil_desc* d, const float* x, void* workspac
   if (g->dx) {          // dx = dP . [Wa ; Wb]  (K-dh without relu' mask and pooling term)
     BwdDhParams dp{};
     dp.g = gc; dp.Wa = d->Wa; dp.Wb = d->Wb; dp.du = g->dx; dp.N = d->N; dp.H = d->H; dp.scale_h = 1.0f;
-    if (int e = launch_bwd_dh(dp, st)) return e;
+    if (int e = launch_bwd_dh(dh_plan(dp, false), dp, st)) return e;
   }
   TnParams tp{};
   tp.nprob = 1; tp.K = d->N; tp.splits = w.splits; tp.k_per_split = w.k_per_split; tp.g = gc; tp.tile = w.tile;

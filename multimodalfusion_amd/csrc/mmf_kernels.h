@@ -182,11 +182,11 @@ struct BwdDhParams {       // du = (dP.Wab + p dM) * relu'(h) * scale_h
   int H;
   float scale_h;           // 1/(1-p_h) in train mode, 1 in eval
   int mt_count, nt_count;
-  int deep;                // set by launch_bwd_dh: short grid, deep-prefetch main loop (dh_mainloop_deep)
-  int allow_half;          // 1: half-block tile heights may be chosen (needs fused_prep and relu_bits)
+  int deep;                // DhPlan::deep, as are mt_count and nt_count: set by launch_bwd_dh from the plan
+  int allow_half;          // not read: the plan allows half-block heights exactly where it fuses K-prep
   int concurrent;          // mmf_amil_desc::concurrent
-  int split;               // 1: the split-operand core (mmf_gemm_split.h): gated stacks with fused K-prep on wide tiles
-  // fused prep (wide tiles own whole rows of h): the kernel computes p_i, ds_i itself (K-prep's job), keeps them
+  int split;               // 1: the split-operand core (mmf_gemm_split.h) where the plan has a tile for it
+  // fused prep (DhPlan::fused, set by launch_bwd_dh): the kernel computes p_i, ds_i itself (K-prep's job), keeps them
   // in LDS for its loader / epilogue and publishes them for the TN kernel
   int fused_prep;
   const float *A_raw, *stats, *Mpool, *gA;
@@ -256,16 +256,39 @@ int launch_score_sum(const float* s_part, int n_parts, const float* bc, float* A
 int launch_head_tail(PoolParams p, hipStream_t st);    // head_tail_kernel alone on the feature vector p.M [p.H]
 int launch_pool_merge(PoolParams p, hipStream_t st);   // single-workgroup merge of p.n_groups partials -> M, stats
 int launch_bwd_prep(BwdPrepParams p, hipStream_t st);
-int launch_bwd_dh(BwdDhParams p, hipStream_t st);
-int launch_bwd_dh_seg(BwdDhParams p, hipStream_t st);     // grouped step: per-row bag dM and mask index, no fused prep
+
+// K-dh's launch plan: every choice between bwd_dh_kernel's launch forms, made once.  A caller builds it, runs K-prep as
+// its own launch where the plan does not fuse it, hands `dbc_groups` (or its own K-prep's) to the reduce list and the
+// plan to the launcher.
+constexpr int PREP_GROUPS = 512;           // capacity of dbc_part: K-prep's partials, its own launch's or K-dh's
+enum : int { DH_SPLIT_WIDE, DH_SPLIT_64, DH_WIDE, DH_128, DH_64X128, DH_64 };
+struct DhPlan {
+  int kind;                // DH_*: split-operand rows x 256 and 64 x 64; exact fp32 rows x 256, 128 x 128, 64 x 128, 64 x 64
+  int rows;                // the tile's height: 64 .. 224 in steps of 16 for DH_WIDE (odd multiples end in a half block)
+  int fused;               // K-prep runs inside K-dh: the caller launches none
+  int variant;             // gate / dropout switches compiled in, (gated ? 2 : 0) + (dropout ? 1 : 0); -1: kept at run time
+  int deep;                // short grid of 64-row tiles: the deep-prefetch main loop (dh_mainloop_deep)
+  int mt_count, nt_count, grid;
+  int extra_lds;           // dynamic LDS bytes behind the staging buffers (fused K-prep's ds, p and scratch)
+  int dbc_groups;          // dbc partials K-dh writes: mt_count when fused (dbc_part[mt]), else 0
+};
+// can_fuse: the caller has A_raw, the softmax statistics, M and the forward's relu bits (the stack's one-bag backward; not the
+// scorer, not the grouped chain, whose plan is otherwise the same); dbc_cap: the capacity of dbc_part
+DhPlan plan_bwd_dh(int64_t N, int H, int D, int gated, int dropout, int split, int concurrent, int can_fuse, int dbc_cap);
+int launch_bwd_dh(const DhPlan& pl, BwdDhParams p, hipStream_t st);
+// grouped step (the SEG instantiations): per-row bag dM and mask index; refuses a fused or split-operand plan
+int launch_bwd_dh_seg(const DhPlan& pl, BwdDhParams p, hipStream_t st);
 // split-operand mode on bags below the wide tiles: instances from which the small split tiles (64-row GEMM tiles, 128 x 128
 // TN tile) are taken instead of the exact-fp32 ones (default 1: every bag, which keeps an instance's score independent of its bag's size)
 int split_min_rows();
-int bwd_dh_fused_groups(int64_t N, int H, int allow_half, int D, int gated, int split, int concurrent);   // > 0: launch_bwd_dh computes p/ds itself and writes that many dbc partials
+// the dbc partials of a K-dh that may fuse K-prep, whatever dbc_part holds (allow_half is not read: see DhPlan); 0: it cannot
+int bwd_dh_fused_groups(int64_t N, int H, int allow_half, int D, int gated, int split, int concurrent);
 int launch_tn(TnParams p, hipStream_t st);
 // wide (32*MB x 256, one 8-wave workgroup per CU) tile selection, shared by the row-parallel GEMMs
 int pick_wide_rows(int64_t M, int ntn, bool allow_half, bool concurrent, int max_rows);
 bool use_wide_tiles(int64_t M, int N, int split = 0);   // split: the bf16x3 mode's (later) crossover
+// a grid this short leaves every workgroup alone on its CU: the deep-prefetch main loops (projection, gate, K-dh)
+bool short_grid(int64_t workgroups);
 // split-K plan shared by the workspace carving and the launcher
 int tn_tile_dim(int64_t K, int D_gate);                    // 256: one 8-wave 256x256 workgroup per CU; else 128
 int tn_splits(int64_t K, int total_tiles, int tile);
@@ -357,5 +380,15 @@ struct ProfScope {
   ProfScope(const char* name, hipStream_t s) : st(s) { prof_begin(name, s); }
   ~ProfScope() { prof_end(st); }
 };
+
+// One launch of a tiled kernel: T::NT threads, T's dynamic LDS and `extra_bytes` behind it
+template <class T, class P>
+int launch_tiled(const char* name, void (*kern)(P), const P& p, int grid, hipStream_t st, int extra_bytes = 0) {
+  const int bytes = T::LDS_BYTES + extra_bytes;
+  if (int e = set_dyn_lds(reinterpret_cast<const void*>(kern), bytes)) return e;
+  ProfScope ps(name, st);
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(T::NT), bytes, st, p);
+  return hipGetLastError() == hipSuccess ? MMF_OK : MMF_ERR_LAUNCH;
+}
 
 }  // namespace mmf

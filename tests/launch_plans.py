@@ -5,7 +5,7 @@ picks a tile height per bag size, and each height (and each K-dh variant) is its
 
   * binds the library's exported planner functions with ctypes, by their mangled names (`bound()`),
   * restates them, and the few decisions written inline in the launchers, in Python (vectorised over N where the CPU
-    test sweeps them), each with the source line it restates,
+    test sweeps them), each with the function it restates,
   * `plan(...)`: the set of large-bag kernel instantiations one training step takes, as plan keys,
   * `reachable()`: every plan key any bag size reaches, per configuration,
   * the size tables the GPU tests run (ONE_BAG, GROUPED, RADIO, BF16), each case with the plan it is meant to reach.
@@ -38,21 +38,31 @@ HEADS = {"small": (1024, 256, 256), "big": (1024, 512, 384)}       # (L, H, D): 
 # check_desc (csrc/mmf_api.hip): N * max(L, H, 2 D) * bytes < 2 GiB; L = 1024 >= H, 2 D for both heads (the rule for every
 # admitted stack: tests/abi_shapes.py stack_row_cap)
 N_MAX = {"fp32": (2**31 - 1) // (1024 * 4), "bf16": (2**31 - 1) // (1024 * 2)}
-# mmf_radio_nll_step_group (csrc/mmf_api.hip:949): the [sum N x nseg * kseg] input < 2 GiB, kseg = L = 1024
+# mmf_radio_nll_step_group (csrc/mmf_api.hip radio_operands): the [sum N x nseg * kseg] input < 2 GiB, kseg = L = 1024
 RADIO_R_MAX = {nseg: min(N_MAX["fp32"], (2**31 - 1) // (nseg * 1024 * 4)) for nseg in (2, 3, 4)}
-PREP_GROUPS = 512          # csrc/mmf_api.hip:82
-DH_MAX_ROWS = 224          # csrc/mmf_amil_bwd.hip:1337
-LINEAR_MAX_ROWS = 240      # csrc/mmf_amil_fwd.hip:881
-CUS, CUS_CONCURRENT = 256, 224      # pick_wide_rows (csrc/mmf_amil_fwd.hip:797)
+PREP_GROUPS = 512          # csrc/mmf_kernels.h PREP_GROUPS
+DH_MAX_ROWS = 224          # csrc/mmf_amil_bwd.hip DH_MAX_ROWS
+LINEAR_MAX_ROWS = 240      # csrc/mmf_amil_fwd.hip launch_linear_impl's pick_wide_rows call
+CUS, CUS_CONCURRENT = 256, 224      # csrc/mmf_amil_fwd.hip pick_wide_rows
 
 
 # ---- the library's exported planner functions -----------------------------------------------------------------------
+class DhPlan(C.Structure):
+    """csrc/mmf_kernels.h DhPlan"""
+    _fields_ = [(f, C.c_int) for f in ("kind", "rows", "fused", "variant", "deep", "mt_count", "nt_count", "grid",
+                                       "extra_lds", "dbc_groups")]
+
+
+DH_SPLIT_WIDE, DH_SPLIT_64, DH_WIDE, DH_128, DH_64X128, DH_64 = range(6)      # csrc/mmf_kernels.h DH_*
+
 SYMBOLS = {
     # name: (mangled, restype, argtypes) -- the C++ signatures of csrc/mmf_kernels.h and csrc/mmf_bf16.h
     "pick_wide_rows": ("_ZN3mmf14pick_wide_rowsElibbi", C.c_int, [C.c_int64, C.c_int, C.c_bool, C.c_bool, C.c_int]),
     "use_wide_tiles": ("_ZN3mmf14use_wide_tilesElii", C.c_bool, [C.c_int64, C.c_int, C.c_int]),
     "bwd_dh_fused_groups": ("_ZN3mmf19bwd_dh_fused_groupsEliiiiii", C.c_int,
                             [C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    # (N, H, D, gated, dropout, split, concurrent, can_fuse, dbc_cap)
+    "plan_bwd_dh": ("_ZN3mmf11plan_bwd_dhEliiiiiiii", DhPlan, [C.c_int64] + [C.c_int] * 8),
     "tn_tile_dim": ("_ZN3mmf11tn_tile_dimEli", C.c_int, [C.c_int64, C.c_int]),
     "tn_splits": ("_ZN3mmf9tn_splitsElii", C.c_int, [C.c_int64, C.c_int, C.c_int]),
     "linear_ksplit": ("_ZN3mmf13linear_ksplitEliiii", C.c_int, [C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int]),
@@ -90,13 +100,13 @@ def bound():
 
 # ---- the Python restatement ---------------------------------------------------------------------------------------
 def use_wide_tiles(M, N, split=0):
-    """csrc/mmf_amil_fwd.hip:809-815 (no tuning overrides).  M may be an array."""
+    """csrc/mmf_amil_fwd.hip use_wide_tiles (no tuning overrides).  M may be an array."""
     min_rows = 80 * 256 if split else 64 * 256
     return (N % 256 == 0) & (np.asarray(M, np.int64) * (N // 256) >= min_rows)
 
 
 def pick_wide_rows(M, ntn, allow_half, concurrent, max_rows):
-    """csrc/mmf_amil_fwd.hip:794-808: the height (multiple of 16, 64..max_rows; odd multiples only with allow_half) with
+    """csrc/mmf_amil_fwd.hip pick_wide_rows: the height (multiple of 16, 64..max_rows; odd multiples only with allow_half) with
     the least rounds x (rows / 32 + 0.35); ties keep the taller tile.  M may be an array."""
     Ms = np.atleast_1d(np.asarray(M, np.int64))
     cus = CUS_CONCURRENT if concurrent else CUS
@@ -114,13 +124,13 @@ def pick_wide_rows(M, ntn, allow_half, concurrent, max_rows):
 
 
 def dh_short_grid(N, H):
-    """csrc/mmf_amil_bwd.hip:1323-1326 (split 0): the 64 x 64 K-dh tiles on at most 1,024 workgroups."""
+    """plan_bwd_dh's `short_64` (csrc/mmf_amil_bwd.hip; split 0): the 64 x 64 K-dh tiles on at most 1,024 workgroups."""
     N = np.asarray(N, np.int64)
     return ~use_wide_tiles(N, H) & ((N // 128) * ((H + 127) // 128) < 256) & (((N + 63) // 64) * ((H + 63) // 64) <= 1024)
 
 
 def bwd_dh_fused_groups(N, H, concurrent):
-    """csrc/mmf_amil_bwd.hip:1338-1349 with allow_half 1 and split 0 (the fp32 stack's call, csrc/mmf_api.hip:484):
+    """csrc/mmf_amil_bwd.hip bwd_dh_fused_groups with split 0 (the fp32 stack: amil_backward_impl, csrc/mmf_api.hip):
     > 0: the number of K-prep tiles when K-dh does K-prep itself; 0: it does not."""
     N = np.asarray(N, np.int64)
     rows = pick_wide_rows(N, H // 256, True, concurrent, DH_MAX_ROWS)
@@ -129,38 +139,58 @@ def bwd_dh_fused_groups(N, H, concurrent):
 
 
 def dh_fused(N, H, concurrent):
-    """csrc/mmf_api.hip:484-485: K-prep runs inside K-dh when it takes at most PREP_GROUPS tiles."""
+    """plan_bwd_dh's `fused`: K-prep runs inside K-dh when it takes at most PREP_GROUPS (the dbc_cap of dh_plan,
+    csrc/mmf_api.hip) tiles."""
     g = bwd_dh_fused_groups(N, H, concurrent)
     return (g > 0) & (g <= PREP_GROUPS)
 
 
 def dh_allow_half(fused, relu_bits=True):
-    """csrc/mmf_amil_bwd.hip:1396: the half-block K-dh tile needs `allow_half && fused_prep && relu_bits`; the stack's
-    backward always sets allow_half (csrc/mmf_api.hip:296) and has the forward's relu bits (:187, all but inference)."""
+    """plan_bwd_dh's wide height: the half-block K-dh tile needs fused K-prep and the forward's relu bits, which the
+    stack's backward has (carve, csrc/mmf_api.hip: all but inference) and a caller that can fuse offers."""
     return bool(fused) and relu_bits
 
 
 def dh_64x128(N, H, D, gated, fused):
-    """csrc/mmf_amil_bwd.hip:1416-1417: below the wide tiles, K-dh takes 64 x 128 tiles from 13,000 rows (fused K-prep,
+    """plan_bwd_dh's DH_64X128: below the wide tiles, K-dh takes 64 x 128 tiles from 13,000 rows (fused K-prep,
     gated, H % 128 == 0, (2 D / 32) % 4 == 0)."""
-    return (not use_wide_tiles(N, H)) and N >= 13000 and fused and gated and H % 128 == 0 and (2 * D // 32) % 4 == 0
+    return ~use_wide_tiles(N, H) & (np.asarray(N) >= 13000) & fused & bool(gated and H % 128 == 0 and (2 * D // 32) % 4 == 0)
+
+
+def dh_plan(N, H, D, gated, p_att, concurrent, can_fuse):
+    """K-dh's plan as plan() below derives it, for an array N (fp32, split 0): the DhPlan fields kind, rows, fused,
+    variant and dbc_groups.  can_fuse False: the grouped chain and the scorer, which run K-prep on their own.  Below the
+    wide and the 64 x 128 tiles the kind is 128 x 128 where those fill the chip (the projection's rule), else 64 x 64."""
+    N = np.asarray(N, np.int64)
+    wide = use_wide_tiles(N, H)
+    fused = dh_fused(N, H, concurrent) if can_fuse else np.zeros(N.shape, bool)
+    mid = dh_64x128(N, H, D, gated, fused)
+    kind = np.where(wide, DH_WIDE, np.where(mid, DH_64X128, np.where(use_big_tiles(N, H), DH_128, DH_64)))
+    rows = np.where(fused, pick_wide_rows(N, H // 256, dh_allow_half(True), concurrent, DH_MAX_ROWS),
+                    pick_wide_rows(N, H // 256, dh_allow_half(False), concurrent, DH_MAX_ROWS))
+    rows = np.where(wide, rows, np.where(kind == DH_128, 128, 64))
+    mode = (2 if gated else 0) + (1 if p_att else 0)
+    variant = np.where(wide & fused, -1 if mode == 3 else mode, -1)       # 3: the run-time switches, template argument -1
+    groups = np.where(fused, bwd_dh_fused_groups(N, H, concurrent), 0)
+    return {"kind": kind, "rows": rows, "fused": fused.astype(np.int64), "variant": variant, "dbc_groups": groups}
 
 
 def tn_tile_dim(K):
-    """csrc/mmf_amil_bwd.hip:1534-1539: 256 x 256 TN tiles from 12,288 rows."""
+    """csrc/mmf_amil_bwd.hip tn_tile_dim: 256 x 256 TN tiles from 12,288 rows."""
     return np.where(np.asarray(K, np.int64) >= 12288, 256, 128)
 
 
 def use_big_tiles(M, N):
-    """csrc/mmf_amil_fwd.hip:777: the projection's 128 x 128 tiles below the wide ones."""
+    """csrc/mmf_amil_fwd.hip use_big_tiles: the projection's 128 x 128 tiles below the wide ones (plan_bwd_dh's `big` is
+    the same rule for K-dh)."""
     return (np.asarray(M, np.int64) // 128) * ((N + 127) // 128) >= 256
 
 
-GATE_BIG_MIN = 400     # csrc/mmf_amil_fwd.hip:956: the fp32 gate's 128-row tiles from 400 of them
+GATE_BIG_MIN = 400     # csrc/mmf_amil_fwd.hip launch_gate_fwd_impl: the fp32 gate's 128-row tiles from 400 of them
 
 
 def gate_parts(D, gated):
-    """csrc/mmf_amil_fwd.hip:933-937"""
+    """csrc/mmf_amil_fwd.hip gate_parts"""
     return (D + 63) // 64 if gated else (D + 127) // 128
 
 
@@ -169,7 +199,7 @@ def gate_big_tiles(N, D, gated):
 
 
 def pick_bm(rows, ntn):
-    """csrc/mmf_amil_bf16.hip:74-80 (static there): 256-row bf16 tiles unless 128-row ones take fewer half-length rounds."""
+    """csrc/mmf_amil_bf16.hip pick_bm (static there): 256-row bf16 tiles unless 128-row ones take fewer half-length rounds."""
     rows = np.asarray(rows, np.int64)
     t256 = ((rows + 255) // 256) * ntn
     t128 = ((rows + 127) // 128) * ntn
@@ -179,18 +209,18 @@ def pick_bm(rows, ntn):
 
 
 def gate_parts_bf16(D, gated):
-    """csrc/mmf_amil_bf16.hip:285"""
+    """csrc/mmf_amil_bf16.hip gate_parts_bf16"""
     return (D + 127) // 128 if gated else (D + 255) // 256
 
 
 def bf16_fused_route(N, L, H, D, gated):
-    """csrc/mmf_api.hip:540 and :553: the `small` gated head's bf16 forward is one fused kernel (fused_fwd2_ok /
+    """csrc/mmf_api.hip amil_bf16_forward_impl and stack_cvt_bf16: the `small` gated head's bf16 forward is one fused kernel (fused_fwd2_ok /
     fused_fwd_ok, mmf_amil_bf16*.hip), its K-dh the dh2 form (dh2_bf16_ok); every other head takes the unfused route."""
     return bool(gated) and H == 256 and D == 256 and L % 128 == 0 and (N + 127) // 128 <= 4096
 
 
 def dh2_bf16_ok(N, H, D, gated):
-    """csrc/mmf_amil_bf16_dh2.hip:351-354"""
+    """csrc/mmf_amil_bf16_dh2.hip dh2_bf16_ok"""
     return bool(gated) and H == 256 and D == 256 and N > 0
 
 
@@ -224,12 +254,12 @@ def plan(N, head="small", gated=True, attn_dropout=False, train=False, concurren
         if radio_nseg and use_wide_tiles(N, L):     # reduce_dim: LinearParams zeroed, so whole blocks, not concurrent
             keys.add(("linear", "wide", pick_wide_rows(N, L // 256, False, False, LINEAR_MAX_ROWS), False))
         if wide:
-            # launch_linear_seg (csrc/mmf_amil_fwd.hip:913): the per-bag-mask instantiation only with dropout
+            # launch_linear_seg (csrc/mmf_amil_fwd.hip): the per-bag-mask instantiation only with dropout
             keys.add(("linear", "wide", pick_wide_rows(N, ntn, True, concurrent, LINEAR_MAX_ROWS), p_h))
-            # launch_bwd_dh_seg (csrc/mmf_amil_bwd.hip:1448): whole blocks only
+            # the grouped chain cannot fuse K-prep (dh_plan(dp, false), csrc/mmf_api.hip): whole blocks only
             keys.add(("dh", "wide_seg", pick_wide_rows(N, ntn, False, concurrent, DH_MAX_ROWS)))
         if tn_tile_dim(N) == 256:
-            keys.add(("tn", 256, 2 if p_att else 0))        # launch_tn_grid (csrc/mmf_amil_bwd.hip:1549)
+            keys.add(("tn", 256, 2 if p_att else 0))        # launch_tn_grid (csrc/mmf_amil_bwd.hip)
         return frozenset(keys)
 
     fused = bool(dh_fused(N, H, concurrent))

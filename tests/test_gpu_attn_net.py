@@ -35,6 +35,7 @@ def _case(N, L, D, gated, dropout, train, seed):
     (1000, 512, 384, False, True, True),     # the `big` scorer, ungated
     (4099, 256, 256, False, False, False),
     (20011, 256, 256, True, False, False),   # the large-bag kernels (wide K-dh tile without its fused prep, 256x256 K-tn)
+    (16384, 256, 256, True, False, False),   # exactly the wide threshold: the one bag size on the 64-row K-dh tile without fused prep
 ])
 def test_attn_net_forward_backward(N, L, D, gated, dropout, train, monkeypatch):
     from multimodalfusion_amd import ops

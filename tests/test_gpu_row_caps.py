@@ -219,7 +219,7 @@ def test_f32_step_at_the_row_cap(c):
     if shipped:
         # the plan: wide projection and K-dh tiles, 256 x 256 split-K TN tiles (tests/launch_plans.py, pinned to the library's
         # planner by tests/test_launch_plans_cpu.py), and the kernels of the gemm mode, none of the other's -- but for K-dh:
-        # its split-operand form exists only with K-prep fused in (csrc/mmf_amil_bwd.hip bwd_dh_split_ok, launch_bwd_dh), and
+        # its split-operand form exists only with K-prep fused in (csrc/mmf_amil_bwd.hip plan_bwd_dh, DH_SPLIT_WIDE), and
         # 524,287 rows are 2,341 row tiles, above the 512 K-prep takes inside K-dh, so K-prep is a launch of its own and K-dh
         # the exact-fp32 wide kernel in both modes
         names = set(tr.dump())

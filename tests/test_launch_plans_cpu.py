@@ -58,6 +58,16 @@ def test_restatement_matches_library(head):
             np.testing.assert_array_equal(lp.bwd_dh_fused_groups(N, H, conc),
                                           _lib_vec(b["bwd_dh_fused_groups"], N, H, 1, D, gated, 0, conc),
                                           err_msg=f"bwd_dh_fused_groups {head} gated={gated} concurrent={conc}")
+            # K-dh's whole plan: one bag (the caller can fuse K-prep) and the grouped form (it cannot), fp32 (split 0)
+            for p_att in (0, 1):
+                for can_fuse in (1, 0):
+                    want = lp.dh_plan(N, H, D, gated, p_att, conc, can_fuse)
+                    got = [b["plan_bwd_dh"](int(n), H, D, gated, p_att, 0, conc, can_fuse, lp.PREP_GROUPS) for n in N]
+                    for field, w in want.items():
+                        np.testing.assert_array_equal(
+                            w, np.array([getattr(g, field) for g in got]),
+                            err_msg=f"plan_bwd_dh.{field} {head} gated={gated} dropout={p_att} concurrent={conc} "
+                                    f"can_fuse={can_fuse}")
     # reduce_dim of the radio window: four 256-column tiles, whole blocks, not concurrent
     R = N[N <= lp.RADIO_R_MAX[2]]
     np.testing.assert_array_equal(lp.pick_wide_rows(R, L // 256, False, False, 240),
@@ -177,10 +187,12 @@ def _compiled_wide_keys():
     return keys
 
 
-# Compiled but never launched: launch_bwd_dh_wide<ROWS> instantiates its K-dh without fused K-prep at every height, but
-# a half-block height is only chosen with fused K-prep (csrc/mmf_amil_bwd.hip:1396); a bag with K-prep of its own runs
-# whole blocks.  Of those, only 128, 160, 192 and 224 rows come up where K-prep takes more than PREP_GROUPS tiles.
-COMPILED_UNREACHABLE = {("dh", "wide", r, False, None) for r in (64, 80, 96, 112, 144, 176, 208)}
+# Compiled, and launched by no stack configuration: K-dh without fused K-prep is compiled at the whole-block heights only
+# (DhWide, csrc/mmf_amil_bwd.hip: its epilogue has no half-block code), and of those the stack reaches 128, 160, 192 and 224
+# rows, where K-prep takes more than PREP_GROUPS tiles.  The scorer's backward with dx (mmf_attn_net_backward), which never
+# fuses K-prep, takes the other two at and just above the wide threshold: tests/test_gpu_attn_net.py runs the 96-row tile
+# at N = 20011 and the 64-row tile at N = 16384 (H = 256, gated).
+SCORER_ONLY = {("dh", "wide", r, False, None) for r in (64, 96)}
 
 
 @pytest.mark.skipif(shutil.which("nm") is None, reason="needs binutils nm")
@@ -190,7 +202,12 @@ def test_compiled_wide_kernels_are_the_reachable_ones():
     for cfg in lp.configs():
         reach |= {k for k in lp.reachable(cfg) if k[:2] in (("linear", "wide"), ("dh", "wide"), ("dh", "wide_seg"))}
     assert reach <= compiled, sorted(reach - compiled, key=str)
-    assert compiled - reach == COMPILED_UNREACHABLE, sorted((compiled - reach) ^ COMPILED_UNREACHABLE, key=str)
+    assert compiled - reach == SCORER_ONLY, sorted((compiled - reach) ^ SCORER_ONLY, key=str)
+    # ... and the scorer does reach them: without fused K-prep, not concurrent (the library's plan at those sizes)
+    b = lp.bound()
+    for n, rows in ((16384, 64), (20011, 96)):
+        pl = b["plan_bwd_dh"](n, 256, 256, 1, 0, 0, 0, 0, lp.PREP_GROUPS)
+        assert (pl.kind, pl.rows, pl.fused) == (lp.DH_WIDE, rows, 0), (n, pl.kind, pl.rows, pl.fused)
 
 
 def test_tables_hold_the_named_cases():
