@@ -322,8 +322,12 @@ int mmf_radio_infer_group(const mmf_amil_desc* desc, const mmf_bag_group* group,
  *   1..MMF_GROUP_MAX or window_steps < 0 (a bf16 bag has no entry here: the call takes fp32 rows only); MMF_ERR_SHAPE,
  *   MMF_ERR_ALIGN and MMF_ERR_WORKSPACE as the one-bag entry points, MMF_ERR_SHAPE also for a head with K > 32 and a bag
  *   too long for one step to be a window.
- * mmf_amil_ig_workspace_bytes: the workspace of that call, or 0 for n_steps or window_steps out of range or a bag too long.
- *   It does not shrink as window_steps grows.
+ * mmf_amil_ig_workspace_bytes: the workspace of that call, or 0 for n_steps outside 1..MMF_GROUP_MAX, window_steps < 0,
+ *   N < 1, L < 32, H < 32, or N above the row limit of one window -- min(2^32 / max(H, D), 2^31 / (4 max(H, 2 D)),
+ *   2,097,152) rows: not even one step fits.  The query has no descriptor: it applies neither mmf_amil_desc::N's row cap
+ *   (which the L-wide bag can set below that limit; the call then returns MMF_ERR_SHAPE) nor the rules for L, H and D, so a
+ *   non-zero answer does not say that the call admits the shape.  For a shape the call admits it is never 0: the row cap is
+ *   at or below the window's limit.  It does not shrink as window_steps grows.
  * Out of scope: the radio and multimodal heads; non-zero baselines (they need a second projection, U' + alpha (U - U'));
  *   bf16 bags; targets other than risk.
  * ------------------------------------------------------------------------------------------- */

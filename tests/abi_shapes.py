@@ -44,6 +44,11 @@ The radiology window (mmf_radio_nll_step_group, mmf_radio_infer_group) and the g
 _backward, mmf_radio_group_forward / _backward) have the RADIO and HALF tables above TABLES, run by
 tests/test_gpu_radio_shapes.py on the inputs and float64 references of tests/radio_cases.py and pinned to the library by
 tests/test_radio_shapes_cpu.py; census() covers their chains ("radio", "radio infer") and radio_row_cap restates their cap.
+
+Integrated gradients (mmf_amil_ig) has the IG table above TABLES with its window planner (ig_row_limit, ig_window_steps,
+ig_windows), refusal order (ig_rule) and attribution tile (attr_tile) restated, pinned to the library by
+tests/test_ig_shapes_cpu.py and run by tests/test_gpu_ig_shapes.py on the inputs and float64 oracle of tests/ig_cases.py;
+census("ig") holds the operands of carve_ig.
 """
 from __future__ import annotations
 
@@ -451,7 +456,19 @@ def census(chain, c):
     "radio" / "radio infer" (mmf_radio_nll_step_group and the radio half pair / mmf_radio_infer_group on a Radio case: the
     group chains with L = kseg, reduce_dim's output xr and -- training -- its gradient dxr [R x L] (carve_radio,
     carve_radio_infer), each modality segment [R x kseg], and the concatenated input [R x nseg kseg] that radio_operands
-    holds below 2 GiB: no kernel reads it as one operand, the refusal is the header's)."""
+    holds below 2 GiB: no kernel reads it as one operand, the refusal is the header's), "ig" (mmf_amil_ig on an Ig case, read
+    off carve_ig: the bag and attr [N x L], U and Gacc [N x H], the attribution GEMM's row partials [(L / 32) x N], and the
+    grouped chain's operands over the R = steps x N rows of one window, steps = ig_window_steps at that N)."""
+    if chain == "ig":
+        L, H, D = c.size
+        R = lambda N: N * ig_window_steps(N, H, D, c.total, c.window_steps)
+        parts = (D + 63) // 64 if c.gated else (D + 127) // 128
+        ops = [("x", _rows, L, 4, False), ("attr", _rows, L, 4, False), ("row_sum", _rows, 1, 4, False), ("row_abs", _rows, 1, 4, False),
+               ("U", _rows, H, 4, True), ("Gacc", _rows, H, 4, True), ("rs_part", _rows, L // 32, 4, True), ("ra_part", _rows, L // 32, 4, True),
+               ("h", R, H, 4, True), ("relu_bits", lambda N: (R(N) + 15) // 16 + 2, (H // 32) * 8, 8, True), ("a", R, D, 4, True),
+               ("s_part", R, parts, 4, True), ("p", R, 1, 4, True), ("ds", R, 1, 4, True), ("du", R, H, 4, True), ("A_raw", R, 1, 4, True),
+               ("ridx_h", R, 1, 4, True), ("ridx_d", R, 1, 4, True), ("bag", R, 1, 4, True)]
+        return ops + ([("b", R, D, 4, True)] if c.gated else [])
     if chain in ("radio", "radio infer"):
         ops = census("group" if chain == "radio" else "group infer", c)
         ops += [("xr", _rows, c.L, 4, True)] + ([("dxr", _rows, c.L, 4, True)] if chain == "radio" else [])
@@ -1804,7 +1821,231 @@ def radio_cap_stacks():
     return [Radio(n, s.L, s.H, s.D, s.gated, (337, 338), True) for s in stacks for n in (2, 3, 4)]
 
 
+# ---- integrated gradients: mmf_amil_ig ------------------------------------------------------------------------------------
+# The call runs n_steps + 2 steps (the quadrature's, then alpha = 1 and alpha = 0 with weight 0: the riders) as the bags of
+# grouped windows of `steps` steps over the bag's N rows.  Restated below: the window planner, the refusal order, the
+# attribution GEMM's tile; census("ig") holds the operands of carve_ig.  tests/test_ig_shapes_cpu.py pins all of it to the
+# library; tests/test_gpu_ig_shapes.py runs every accepted case on the inputs and float64 oracle of tests/ig_cases.py.
+IG_LIB_WINDOW_ROWS = 2**18                               # csrc/mmf_api.hip ig_window_steps: rows of a window the library cuts itself
+IG_BAD = ("", "p_h", "p_att", "gemm", "null row_sum", "attr misaligned", "workspace short")
+
+
+@dataclass(frozen=True)
+class Ig:
+    L: int
+    H: int
+    D: int
+    gated: bool
+    N: int
+    K: int = 4
+    n_steps: int = 20
+    window_steps: int = 0
+    method: str = "gausslegendre"
+    n0: int = 0                  # rows of the base bag of a periodic case (row i = base[i mod n0]); 0: the bag itself, direct oracle
+    attr: bool = True            # the [N x L] output is requested
+    bad: str = ""                # one of IG_BAD: what else is wrong with the call (refused)
+    why: str = ""
+
+    @property
+    def size(self):
+        return (self.L, self.H, self.D)
+
+    @property
+    def stack(self):
+        return Stack(self.L, self.H, self.D, self.gated)
+
+    @property
+    def total(self):
+        return self.n_steps + 2
+
+    @property
+    def name(self):
+        return (f"{self.L}_{self.H}_{self.D}_{'gated' if self.gated else 'ungated'}_n{self.N}_k{self.K}_s{self.n_steps}"
+                f"_w{self.window_steps}")
+
+
+def ig_row_limit(H, D):
+    """csrc/mmf_api.hip ig_row_limit: the rows of one window -- the 32-bit mask index over max(H, D), every H- and 2 D-wide
+    operand below 2^31 bytes (check_desc on the window without the L-wide bag), group_plan's 256 pooling groups of 8192."""
+    return min((2**32 - 1) // max(H, D), (2**31 - 1) // (4 * max(H, 2 * D)), GROUP_POOL_GROUPS * POOL_MAX_ROWS)
+
+
+def ig_window_steps(N, H, D, total, window_steps):
+    """csrc/mmf_api.hip ig_window_steps: steps per window -- the caller's, or (0) windows of at most 2^18 rows cut evenly;
+    clamped to the row limit, MMF_GROUP_MAX and the call's steps.  0: not even one step fits."""
+    if N < 1 or H < 1 or D < 1:
+        return 0
+    smax = ig_row_limit(H, D) // N
+    if smax < 1:
+        return 0
+    smax = min(smax, GROUP_MAX, total)
+    if window_steps > 0:
+        return min(window_steps, smax)
+    s = min(max(IG_LIB_WINDOW_ROWS // N, 1), smax)
+    nwin = (total + s - 1) // s
+    return (total + nwin - 1) // nwin
+
+
+def ig_windows(c):
+    """csrc/mmf_api.hip mmf_amil_ig's window loop: (q0, S, nfold) per window -- its first step in the call, its steps, and how
+    many of them are folded into Gacc (the riders carry weight 0 and are not)."""
+    steps = ig_window_steps(c.N, c.H, c.D, c.total, c.window_steps)
+    out = []
+    for q0 in range(0, c.total, steps):
+        S = min(steps, c.total - q0)
+        out.append((q0, S, max(0, min(S, c.n_steps - q0))))
+    return out
+
+
+def ig_pool_groups(N, S):
+    """csrc/mmf_api.hip group_plan on S equal bags of N rows: seg.gbeg[S], the pooling groups of one window."""
+    rpg = max(64, (S * N + GROUP_POOL_GROUPS - 1) // GROUP_POOL_GROUPS)
+    return S * ((N + rpg - 1) // rpg)
+
+
+def attr_tile(N, L):
+    """csrc/mmf_amil_bwd.hip launch_nn_tiles: the attribution GEMM [N x H] . [H x L] on 128 x 128 tiles once they fill the
+    chip, else 64 x 64."""
+    return 128 if (N // 128) * ((L + 127) // 128) >= 256 else 64
+
+
+def ig_projection(N, L, H):
+    """The tile of the call's projection U = x . W1^T (csrc/mmf_amil_fwd.hip launch_linear_impl, fp32 mode), by the
+    restatements of tests/launch_plans.py and linear_ksplit above."""
+    import launch_plans as lp
+    if bool(lp.use_wide_tiles(N, H)):
+        return "wide"
+    if bool(lp.use_big_tiles(N, H)):
+        return "128 x 128"
+    return "64 x 64, K split" if linear_ksplit(N, H, L, 1, L) > 1 else "64 x 64"
+
+
+def ig_rule(c):
+    """include/mmf_amil.h "Integrated-gradients patch attribution"; csrc/mmf_api.hip mmf_amil_ig -- in the library's order:
+    null structs, mode, the step counts and tables, the outputs, the head's operands (all MMF_ERR_ARG); check_desc; the
+    head's K; ig_window_steps; check_operands and attr's alignment; the workspace size."""
+    assert c.bad in IG_BAD, c.bad
+    if c.bad in ("gemm", "p_h", "p_att"):
+        return ERR_ARG
+    if c.n_steps < 1 or c.n_steps > GROUP_MAX or c.window_steps < 0:
+        return ERR_ARG
+    if c.bad == "null row_sum":
+        return ERR_ARG
+    code = stack_rule(c.stack, c.N)
+    if code != OK:
+        return code
+    if c.K < 1 or c.K > 32:
+        return ERR_SHAPE
+    # "a bag too long for one step to be a window": never after check_desc, whose cap is at or below the window's row limit
+    # for every admitted (H, D) (tests/test_ig_shapes_cpu.py); the query, which has no descriptor, does return 0 there
+    if ig_window_steps(c.N, c.H, c.D, c.total, c.window_steps) < 1:
+        return ERR_SHAPE
+    if c.bad == "attr misaligned":
+        return ERR_ALIGN
+    if c.bad == "workspace short":
+        return ERR_WORKSPACE
+    return OK
+
+
+def _ig_sizes(w):
+    return tuple(S for _, S, _ in w)
+
+
+def ig_tags(c):
+    code = ig_rule(c)
+    if code != OK:
+        return {("refused", code, f"N={c.N} K={c.K} n_steps={c.n_steps} window_steps={c.window_steps} {c.bad}".rstrip())}
+    t = {("stack", (c.L, c.H, c.D, c.gated)), ("K", c.K), ("attr", "requested" if c.attr else "NULL"),
+         ("projection", ig_projection(c.N, c.L, c.H))}
+    t |= {("head", name) for name, size in SHIPPED_HEADS.items() if size == c.size}
+    tile = attr_tile(c.N, c.L)
+    t.add(("attr tile", tile))
+    if c.L % tile:
+        t.add(("a column tile partly outside L", tile))
+    w = ig_windows(c)
+    steps = ig_window_steps(c.N, c.H, c.D, c.total, c.window_steps)
+    t.add(("window sizes", _ig_sizes(w)))
+    if len(w) == 1:
+        t.add(("windows", "one window"))
+    elif c.window_steps == 0:
+        t.add(("windows", "a library cut into even windows" if len(set(_ig_sizes(w))) == 1 else "a library cut with a ragged last window"))
+    if any(nfold == 0 for _, _, nfold in w):
+        t.add(("windows", "a window of riders alone"))
+    if any(q0 == c.n_steps + 1 for q0, _, _ in w):
+        t.add(("windows", "the two riders in different windows"))
+    if any(S == GROUP_MAX for _, S, _ in w):
+        t.add(("windows", "S = GROUP_MAX"))
+    if c.window_steps > 0 and steps < min(c.window_steps, c.total, GROUP_MAX):
+        t.add(("windows", "window_steps clamped by the row limit"))
+    if c.n_steps in (1, GROUP_MAX):
+        t.add(("n_steps", c.n_steps))
+    if c.N == 1:
+        t.add(("N", 1))
+    if c.N == stack_row_cap(c.stack):
+        widest = "L" if c.L >= max(c.H, 2 * c.D) else "H" if c.H > 2 * c.D else "H = 2 D"
+        t.add(("N at the cap, set by", widest))
+    if c.n0 and c.N % c.n0:
+        t.add(("multiplicities", "two different"))
+    return t
+
+
+_IG_CAP = 2**21 - 1
+IG = [
+    Ig(96, 256, 128, True, 65, why="three chunks: 3 column blocks for ig_rows_kernel, the second 64-wide column tile half outside L"),
+    Ig(160, 512, 640, True, 300, K=32, why="ten gate tiles, five column blocks, the head's 32 classes: every lane of its wave loop and tid-0 loop"),
+    Ig(32, 1024, 384, False, 300, K=5, why="H = 1024: the dM loop over four strides, the widest pooling rows, K = 1024 in the attribution GEMM; K % 4 != 0"),
+    Ig(32, 1024, 384, False, 1, why="one row: every tile, group and step holds one row"),
+    Ig(128, 1024, 128, True, 65, K=1, n_steps=4, method="riemann_middle", why="one gate tile under H = 1024, four column blocks, a one-class head"),
+    Ig(32, 256, 128, False, 17, n_steps=64, why="66 steps cannot be one window: the library cuts 33 + 33"),
+    Ig(32, 256, 128, False, 17, n_steps=64, window_steps=64, why="a window of 64 fills al[GROUP_MAX] and IgSteps; the two riders are a window of their own, nfold = 0"),
+    Ig(32, 256, 128, False, 17, n_steps=1, window_steps=1, method="riemann_middle", why="one node; three one-step windows, alpha = 1 and alpha = 0 each alone"),
+    Ig(256, 256, 128, False, 16384, why="the 128 x 128 attribution tile at its threshold, two full column tiles; 11 + 11; the projection on wide tiles; direct oracle"),
+    Ig(32, 256, 256, True, 32768, n0=337, why="the 128 tile with 32 of its 128 columns inside L; 8 + 8 + 6: four folded steps and both riders last"),
+    Ig(32, 256, 256, True, 131072, n0=337, why="eleven windows of two steps, the last the two riders alone behind ten folds"),
+    Ig(128, 1024, 128, True, 30000, window_steps=22, n0=375, why="window_steps 22 clamped to 17 by the row limit: 17 + 5, h of a window at 2.09e9 bytes"),
+    Ig(32, 256, 128, False, _IG_CAP, n_steps=4, n0=337, attr=False, why="the cap where H = 2 D binds: six one-step windows, h and du 1 KiB below 2 GiB"),
+    Ig(128, 1024, 128, True, 2**19 - 1, n_steps=4, n0=337, attr=False, why="the cap where H binds; 2^19 - 1 is prime: two multiplicities"),
+    Ig(1024, 256, 256, True, 2**19 - 1, n_steps=2, method="riemann_middle", n0=337,
+       why="the shipped small head at the cap L sets: x and attr each 4 KiB below 2 GiB, eight column tiles of the 128 tile"),
+    Ig(1024, 512, 384, True, 33, n_steps=2, method="riemann_middle", why="the shipped big head, gated"),
+    # refused
+    Ig(32, 256, 128, False, 17, bad="p_h", why="train mode: the integrand would be random"),
+    Ig(32, 256, 128, False, 17, bad="gemm", why="MMF_GEMM_BF16X3: exact-fp32 GEMMs only"),
+    Ig(32, 256, 128, False, 17, n_steps=0, why="no node"),
+    Ig(32, 256, 128, False, 17, n_steps=65, why="more nodes than MMF_GROUP_MAX"),
+    Ig(32, 256, 128, False, 17, window_steps=-1, why="window_steps < 0"),
+    Ig(32, 256, 128, False, 17, bad="null row_sum", why="a required output missing"),
+    Ig(32, 256, 128, False, 17, K=33, why="more classes than the stock head's 32"),
+    Ig(32, 256, 128, False, _IG_CAP + 1, n_steps=4, why="cap + 1: h of one step would reach 2 GiB"),
+    Ig(32, 256, 128, False, 17, bad="attr misaligned", why="attr 4 bytes off: the epilogue stores four floats at a time"),
+    Ig(32, 256, 128, False, 17, bad="workspace short", why="one byte less than the query"),
+]
+REQUIRED_IG = (
+    {("stack", (c.L, c.H, c.D, c.gated)) for c in STACK_F32 if stack_rule(c) == OK} | {("head", "small"), ("head", "big")}
+    | {("attr tile", 64), ("attr tile", 128), ("a column tile partly outside L", 64), ("a column tile partly outside L", 128)}
+    | {("windows", w) for w in ("one window", "a library cut into even windows", "a library cut with a ragged last window",
+                                "a window of riders alone", "the two riders in different windows", "S = GROUP_MAX",
+                                "window_steps clamped by the row limit")}
+    | {("window sizes", s) for s in ((22,), (33, 33), (64, 2), (1, 1, 1), (11, 11), (8, 8, 6), (2,) * 11, (17, 5), (1,) * 6)}
+    | {("K", k) for k in (1, 5, 32)} | {("n_steps", 1), ("n_steps", 64)} | {("N", 1)}
+    | {("N at the cap, set by", w) for w in ("L", "H", "H = 2 D")} | {("multiplicities", "two different")}
+    | {("projection", "wide"), ("projection", "64 x 64")} | {("attr", "requested"), ("attr", "NULL")}
+    | {("refused", ERR_ARG, f"N=17 K=4 n_steps=20 window_steps=0 {b}") for b in ("p_h", "gemm", "null row_sum")}
+    | {("refused", ERR_ARG, "N=17 K=4 n_steps=0 window_steps=0"), ("refused", ERR_ARG, "N=17 K=4 n_steps=65 window_steps=0"),
+       ("refused", ERR_ARG, "N=17 K=4 n_steps=20 window_steps=-1"), ("refused", ERR_SHAPE, "N=17 K=33 n_steps=20 window_steps=0"),
+       ("refused", ERR_SHAPE, f"N={_IG_CAP + 1} K=4 n_steps=4 window_steps=0"),
+       ("refused", ERR_ALIGN, "N=17 K=4 n_steps=20 window_steps=0 attr misaligned"),
+       ("refused", ERR_WORKSPACE, "N=17 K=4 n_steps=20 window_steps=0 workspace short")})
+
+
+def ig_cap_stacks():
+    """The Ig cases the row-cap census covers: every admitted stack of STACK_F32 and both shipped heads, at 4 and 20 nodes."""
+    stacks = [c for c in STACK_F32 if stack_rule(c) == OK] + [Stack(*s, True) for s in SHIPPED_HEADS.values()]
+    return [Ig(s.L, s.H, s.D, s.gated, 1, n_steps=n) for s in stacks for n in (4, 20)]
+
+
 TABLES = {
+    "mmf_amil_ig": (IG, ig_tags, REQUIRED_IG),
     "RADIO": (RADIO, radio_tags, REQUIRED_RADIO),
     "HALF": (HALF, half_tags, REQUIRED_HALF),
     "XFUSION": (XFUSION, xfusion_tags, REQUIRED_XFUSION),
