@@ -348,6 +348,50 @@ size_t mmf_amil_ig_workspace_bytes(int64_t N, int32_t L, int32_t H, int32_t D, i
 int mmf_amil_ig(const mmf_amil_desc* desc, const float* x, void* workspace, size_t workspace_bytes,
                 const mmf_surv_head* head, const mmf_ig_desc* ig, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Integrated-gradients attribution of the radiology head in one call: which MRI sequence and which slices carry the
+ *   predicted risk.  The reference attributes its radiology branch with captum as it does the pathology one
+ *   (create_attributions.py:94-147 through the captum methods of models/model_mm_attention_mil.py:202-355, on the forward
+ *   of models/model_attention_mil_radio.py:73-115): n_steps autograd passes, each through reduce_dim and the stack, each
+ *   computing weight gradients nobody reads.  The identity of mmf_amil_ig survives reduce_dim, bias included.  With X =
+ *   [x_0 | ... | x_{nseg-1}], reduce_dim (Wr, br) and a zero baseline, node alpha feeds alpha X:
+ *     xr(alpha) = alpha (X Wr^T) + br,   u(alpha) = alpha U + b1',   U = (X Wr^T) W1^T,   b1' = W1 br + b1,
+ *   so u is still linear in alpha with a composed bias that does not depend on the bag, and the input gradient is still
+ *   linear in du: sum_k w_k dX_k = ((sum_k w_k du_k) W1) Wr, attr_m = x_m * (that product's columns m kseg .. (m + 1) kseg
+ *   - 1).  The two nseg kseg-wide contractions and the two L-wide ones run ONCE per call, the weight gradients never; only
+ *   the H-wide part runs per node, in mmf_amil_ig's windows unchanged.  The chain:
+ *     1. Y = X Wr^T, reduce_dim over the segments without its bias (the plan of mmf_radio_infer_group for N rows);
+ *     2. U = Y W1^T, the stack's projection (no bias, no activation);
+ *     3. b1' = b1 + W1 br, one wave per output: a dependent chain of ceil(L / 64) + 7 additions;
+ *     4. mmf_amil_ig's windows on U and b1';
+ *     5. P = Gacc W1 [N x L], a plain GEMM (P takes Y's place);
+ *     6. Q = P Wr with an epilogue that multiplies each 32-column block by the modality that owns it, in registers, and
+ *        reduces each row of the block: nothing N x nseg kseg wide reaches memory unless attr is given;
+ *     7. per modality, the kseg / 32 partials of each row added in block order.
+ *   No weight-gradient (TN) launch, no reduce list.
+ * desc: the stack, as for mmf_amil_ig, with desc->L == rd->kseg and desc->N rows.  rd: as in mmf_radio_infer_group -- x[m]
+ *   [N x kseg] fp32, nseg 2..4; dW and db are not read.  head: as for mmf_amil_ig; the optional outputs receive the values
+ *   at alpha = 1.
+ * ig: mmf_ig_desc with modality-major extents -- row_sum, row_abs [nseg x N]; attr [nseg x N x kseg] or NULL, so that
+ *   attr + m N kseg has x[m]'s layout; alpha, weight, window_steps, risk_x, risk_base, step_risk and the two riders as for
+ *   mmf_amil_ig.
+ * Every sum is taken in a fixed order and there are no float atomics: two calls agree bit for bit.  No workgroup waits for
+ *   another; the call allocates nothing and keeps no state.
+ * Returns, before any launch and in this order: MMF_ERR_ARG for what mmf_amil_ig refuses with it and for a null rd, rd->x,
+ *   rd->x[m], rd->W or rd->bias; MMF_ERR_SHAPE for nseg outside 2..4, what the descriptor's rules refuse, kseg != desc->L,
+ *   N nseg kseg 4 >= 2^31 (mmf_radio_nll_step_group's rule), a head with K outside 1..32, or a bag too long for one step to
+ *   be a window; MMF_ERR_ALIGN for a segment, rd->W, a stack weight, the workspace or attr off 16 bytes; MMF_ERR_WORKSPACE.
+ * mmf_radio_ig_workspace_bytes: the workspace of that call, or 0 for n_steps outside 1..MMF_GROUP_MAX, window_steps < 0,
+ *   N < 1, nseg outside 2..4, kseg < 32, H < 32, N above the row limit of one window (mmf_amil_ig_workspace_bytes) or
+ *   N nseg kseg 4 >= 2^31.  It does not shrink as window_steps grows.
+ * Out of scope: the multimodal heads (the chain cut at the embedding, the omic network per node); non-zero baselines; bf16
+ *   bags; targets other than risk.
+ * ------------------------------------------------------------------------------------------- */
+size_t mmf_radio_ig_workspace_bytes(int64_t N, int32_t nseg, int32_t kseg, int32_t H, int32_t D, int32_t gated,
+                                    int32_t n_steps, int32_t window_steps);
+int mmf_radio_ig(const mmf_amil_desc* desc, const mmf_radio_reduce* rd, void* workspace, size_t workspace_bytes,
+                 const mmf_surv_head* head, const mmf_ig_desc* ig, void* stream);
+
 /* The hazard head's training step on a feature vector that is already on the device: what
  *   `hazards, S, Y_hat = head(classifier(feat)); loss = NLLSurvLoss(alpha)(hazards, S, Y, c); (loss * loss_scale).backward()`
  * computes between the embedding and the loss (models/model_mm_attention_mil.py:190-191 with fusion = 'concat': feat is the
@@ -558,6 +602,14 @@ size_t mmf_linear_backward_workspace_bytes(int64_t M, int32_t N, int32_t K);
 int mmf_linear_backward(const float* dy, const float* const* x_segs, int32_t nseg, int32_t kseg, int64_t M,
                         const float* W, int32_t N, float* dW, float* db, float* dx,
                         void* workspace, size_t workspace_bytes, void* stream);
+/* The input gradient of a linear layer over nseg (1..4) concatenated segments, which mmf_linear_backward leaves out because
+ * training bags are leaves: dx_segs[i] [M x kseg] = dy [M x N] . W[:, i kseg : (i + 1) kseg], W [N x nseg kseg]; dx_segs is
+ * a HOST array of device pointers.  One plain GEMM launch per segment.  Attribution by autograd needs it (one pass per
+ * quadrature node through reduce_dim: infer.radio_integrated_gradients_autograd).  MMF_ERR_ARG for a null pointer or nseg
+ * outside 1..4; MMF_ERR_SHAPE unless N % 32 == 0, kseg % 4 == 0, M >= 1 and every operand stays below 2 GiB;
+ * MMF_ERR_ALIGN unless dy, W and every segment are 16-byte aligned; all before any launch. */
+int mmf_linear_input_grad(const float* dy, const float* W, int32_t nseg, int32_t kseg, int64_t M, int32_t N,
+                          float* const* dx_segs, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Survival head:  logits = f.Wk^T + bk; hazards = sigmoid(logits); S = cumprod(1-hazards); Y_hat = argmax

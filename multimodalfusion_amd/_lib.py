@@ -164,6 +164,10 @@ SYMBOLS = {
                                                   C.c_int32]),
     "mmf_amil_ig": (C.c_int, [C.POINTER(AmilDesc), C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(SurvHead),
                               C.POINTER(IgDesc), C.c_void_p]),
+    "mmf_radio_ig_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                                   C.c_int32, C.c_int32]),
+    "mmf_radio_ig": (C.c_int, [C.POINTER(AmilDesc), C.POINTER(RadioReduce), C.c_void_p, C.c_size_t, C.POINTER(SurvHead),
+                               C.POINTER(IgDesc), C.c_void_p]),
     "mmf_radio_group_infer_workspace_bytes": (C.c_size_t, [C.POINTER(C.c_int64), C.c_int32, C.c_int32, C.c_int32,
                                                             C.c_int32, C.c_int32, C.c_int32]),
     "mmf_radio_infer_group": (C.c_int, [C.POINTER(AmilDesc), C.POINTER(BagGroup), C.POINTER(RadioReduce), C.c_void_p,
@@ -204,6 +208,8 @@ SYMBOLS = {
     "mmf_linear_backward": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int32, C.c_int32, C.c_int64,
                                       C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_size_t, C.c_void_p]),
+    "mmf_linear_input_grad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int32,
+                                        C.POINTER(C.c_void_p), C.c_void_p]),
     "mmf_surv_head_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mmf_surv_head_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -753,7 +753,10 @@ __global__ __launch_bounds__(T::NT) void bwd_dh_kernel(BwdDhParams p) {
 // ATTR (mmf_amil_ig's attribution GEMM, P = Gacc . W1): the epilogue multiplies the product by mulx -- the bag -- in
 // registers and reduces each row's 32 columns of a block over the 8 lanes that hold them (xor butterfly: the same sum in
 // every lane); the product itself is stored only when C is given.  N % 32 == 0 there, so a block is inside or outside.
-template <class T, bool ATTR = false>
+// SEG (mmf_radio_ig's Q = P . Wr): the multiplier and the product's place are chosen per 32-column block from the segment
+// that owns it, col / kseg; kseg % 32 == 0, so a 64- or 128-wide tile may hold several segments but a block -- the eight
+// lanes of one row, the wave of one accumulator block -- never does, and the choice is uniform over the wave.
+template <class T, bool ATTR = false, bool SEG = false>
 __global__ __launch_bounds__(T::NT) void gemm_nn_kernel(NnParams p) {
   extern __shared__ __align__(16) float lds[];
   int mt, nt;
@@ -769,11 +772,24 @@ __global__ __launch_bounds__(T::NT) void gemm_nn_kernel(NnParams p) {
     const int col = col0 + c;
     if (col >= p.N) return;
     if constexpr (ATTR) {
+      const float* mulx;
+      float* cout;
+      int ldx, ldc;
+      if constexpr (SEG) {
+        const int m = col / p.kseg, cs = col - m * p.kseg;
+        mulx = (m == 0 ? p.segx[0] : m == 1 ? p.segx[1] : m == 2 ? p.segx[2] : p.segx[3]) + cs;
+        cout = p.C ? p.C + (size_t)m * p.M * p.kseg + cs : nullptr;
+        ldx = ldc = p.kseg;
+      } else {
+        mulx = p.mulx + col;
+        cout = p.C ? p.C + col : nullptr;
+        ldx = p.ldx; ldc = p.ldc;
+      }
       float4 xv[4];
 #pragma unroll
       for (int t = 0; t < 4; ++t) {            // every load before the first store
         const int row = row0 + r + 8 * t;
-        xv[t] = row < p.M ? ld4(p.mulx + (size_t)row * p.ldx + col) : zero4();
+        xv[t] = row < p.M ? ld4(mulx + (size_t)row * ldx) : zero4();
       }
       const size_t cb = (size_t)(col >> 5);
 #pragma unroll
@@ -792,7 +808,7 @@ __global__ __launch_bounds__(T::NT) void gemm_nn_kernel(NnParams p) {
             p.rs_part[cb * (size_t)p.M + row] = s;
             p.ra_part[cb * (size_t)p.M + row] = m;
           }
-          if (p.C) st4(p.C + (size_t)row * p.ldc + col, a);
+          if (cout) st4(cout + (size_t)row * ldc, a);
         }
       }
     } else {
@@ -817,6 +833,22 @@ __global__ __launch_bounds__(256) void ig_rows_kernel(const float* rs_part, cons
   }
   row_sum[i] = s;
   row_abs[i] = m;
+}
+
+// the same per modality: row_sum[m, i] / row_abs[m, i] = modality m's nblk partials, blocks m * nblk .. (m + 1) * nblk - 1
+__global__ __launch_bounds__(256) void ig_rows_seg_kernel(const float* rs_part, const float* ra_part, int64_t M, int nblk,
+                                                          int nseg, float* row_sum, float* row_abs) {
+  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (t >= M * nseg) return;
+  const int seg = (int)(t / M);
+  const int64_t i = t - seg * M;
+  float s = 0.f, m = 0.f;
+  for (int b = seg * nblk; b < (seg + 1) * nblk; ++b) {
+    s += rs_part[(size_t)b * M + i];
+    m += ra_part[(size_t)b * M + i];
+  }
+  row_sum[t] = s;
+  row_abs[t] = m;
 }
 
 // Gacc[i, :] (+)= sum_s w_s du[s * N + i, :]: one thread per four columns, the steps in order -- the same additions in
@@ -1526,19 +1558,19 @@ int launch_group_bwd_prep(BwdPrepParams p, const int* bag, hipStream_t st) {
   return hipGetLastError() == hipSuccess ? MMF_OK : MMF_ERR_LAUNCH;
 }
 
-// the NN GEMM's tiles: 128 x 128 once they fill the chip, else 64 x 64; ATTR: the attribution epilogue
-template <bool ATTR>
+// the NN GEMM's tiles: 128 x 128 once they fill the chip, else 64 x 64; ATTR: the attribution epilogue, SEG: per segment
+template <bool ATTR, bool SEG = false>
 static int launch_nn_tiles(NnParams p, hipStream_t st) {
-  const char* name = ATTR ? "gemm_nn_attr_kernel" : "gemm_nn_kernel";
+  const char* name = SEG ? "gemm_nn_attr_seg_kernel" : ATTR ? "gemm_nn_attr_kernel" : "gemm_nn_kernel";
   const int ntn = (p.N + 127) / 128;
   if ((p.M / 128) * ntn >= 256) {
     using T = Tile<128, 128, 2, 2, true, false>;
     p.mt_count = (int)((p.M + 127) / 128); p.nt_count = ntn;
-    return launch_tiled<T>(name, gemm_nn_kernel<T, ATTR>, p, grid_for_tiles(p.mt_count, p.nt_count), st);
+    return launch_tiled<T>(name, gemm_nn_kernel<T, ATTR, SEG>, p, grid_for_tiles(p.mt_count, p.nt_count), st);
   }
   using T = Tile<64, 64, 2, 2, true, false>;
   p.mt_count = (int)((p.M + 63) / 64); p.nt_count = (p.N + 63) / 64;
-  return launch_tiled<T>(name, gemm_nn_kernel<T, ATTR>, p, grid_for_tiles(p.mt_count, p.nt_count), st);
+  return launch_tiled<T>(name, gemm_nn_kernel<T, ATTR, SEG>, p, grid_for_tiles(p.mt_count, p.nt_count), st);
 }
 
 int launch_nn(NnParams p, hipStream_t st) {
@@ -1557,6 +1589,22 @@ int launch_nn_attr(NnParams p, float* row_sum, float* row_abs, hipStream_t st) {
   ProfScope ps("ig_rows_kernel", st);
   hipLaunchKernelGGL(ig_rows_kernel, dim3((unsigned)((p.M + 255) / 256)), dim3(256), 0, st, p.rs_part, p.ra_part, p.M,
                      p.N / 32, row_sum, row_abs);
+  return hipGetLastError() == hipSuccess ? MMF_OK : MMF_ERR_LAUNCH;
+}
+
+int launch_nn_attr_seg(NnParams p, float* row_sum, float* row_abs, hipStream_t st) {
+  if (!p.rs_part || !p.ra_part || !row_sum || !row_abs) return MMF_ERR_ARG;
+  if (p.kseg < 32 || p.kseg % 32 != 0 || p.N % p.kseg != 0 || p.N / p.kseg < 1 || p.N / p.kseg > 4) return MMF_ERR_SHAPE;
+  const int nseg = p.N / p.kseg;
+  for (int m = 0; m < nseg; ++m)
+    if (!p.segx[m]) return MMF_ERR_ARG;
+  if (p.K % KC != 0 || p.lda % 4 != 0 || p.ldb % 4 != 0) return MMF_ERR_SHAPE;
+  if (p.M <= 0) return MMF_OK;
+  if (int e = launch_nn_tiles<true, true>(p, st)) return e;
+  const int64_t n = p.M * nseg;
+  ProfScope ps("ig_rows_seg_kernel", st);
+  hipLaunchKernelGGL(ig_rows_seg_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, p.rs_part, p.ra_part, p.M,
+                     p.kseg / 32, nseg, row_sum, row_abs);
   return hipGetLastError() == hipSuccess ? MMF_OK : MMF_ERR_LAUNCH;
 }
 

@@ -1373,6 +1373,28 @@ int launch_ig_expand(const IgExpandParams& p, hipStream_t st) {
   return hipGetLastError() == hipSuccess ? MMF_OK : MMF_ERR_LAUNCH;
 }
 
+// The radiology head (mmf_radio_ig): reduce_dim's bias passes through the projection once per call, out[j] = b1[j] +
+// sum_l W1[j, l] br[l].  One wave per output, four outputs per workgroup: lane t adds its products l = t, t + 64, ... in
+// that order (ceil(L / 64) fused multiply-adds), the xor butterfly adds the 64 lanes (6), then b1 -- a dependent chain of
+// ceil(L / 64) + 7 additions, the same in every call; no atomics.
+__global__ __launch_bounds__(256) void ig_bias_kernel(const float* W1, const float* br, const float* b1, float* out,
+                                                      int H, int L) {
+  const int lane = threadIdx.x & 63, j = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (j >= H) return;
+  float t = 0.f;
+  for (int l = lane; l < L; l += 64) t = fmaf(W1[(size_t)j * L + l], br[l], t);
+  t = wave_sum(t);
+  if (lane == 0) out[j] = t + b1[j];
+}
+
+int launch_ig_bias(const float* W1, const float* br, const float* b1, float* out, int H, int L, hipStream_t st) {
+  if (!W1 || !br || !b1 || !out) return MMF_ERR_ARG;
+  if (H < 1 || L < 1) return MMF_ERR_SHAPE;
+  ProfScope ps("ig_bias_kernel", st);
+  hipLaunchKernelGGL(ig_bias_kernel, dim3((unsigned)((H + 3) / 4)), dim3(256), 0, st, W1, br, b1, out, H, L);
+  return hipGetLastError() == hipSuccess ? MMF_OK : MMF_ERR_LAUNCH;
+}
+
 // The hazard head of models/model_attention_mil_path.py:58-61 on a step's pooled embedding and the gradient of
 // risk = -sum_k S_k back to it.  S_k = prod_{i <= k} (1 - h_i), so d risk / d h_j = sum_{k >= j} prod_{i <= k, i != j}
 // (1 - h_i): built from the products themselves, never divided by 1 - h_j.

@@ -1375,21 +1375,23 @@ static int ig_window_steps(int64_t N, int H, int D, int total, int window_steps)
 struct IgWs {
   AmilWs w;                  // the window's rows: h, relu_bits, a, b, s_part, p, ds, dbc_part, du (nothing else is set)
   float *U, *G;              // [N x H]: x . W1^T, and the folded sum_s w_s du_s
-  float *rs_part, *ra_part;  // [(L / 32) x N]: the attribution GEMM's per-block row sums
+  float *rs_part, *ra_part;  // [(attr_cols / 32) x N]: the attribution GEMM's per-block row sums
   float* kpart;              // the projection's K-split partial tiles, or null
   float *M, *dM, *stats, *partials, *A_raw;
   uint32_t *ridx_h, *ridx_d;
   int* bag;
   size_t bytes;
 };
-static IgWs carve_ig(Carver& c, int64_t N, int L, int H, int D, int gated, int steps) {
+// attr_cols: the attribution GEMM's columns -- L, or the radiology head's nseg * kseg (0: L)
+static IgWs carve_ig(Carver& c, int64_t N, int L, int H, int D, int gated, int steps, int attr_cols = 0) {
   IgWs g{};
+  if (attr_cols == 0) attr_cols = L;
   auto take = [&](size_t n) { return c.take<float>(n); };
   const int64_t R = N * steps;
   g.U = take((size_t)N * H);
   g.G = take((size_t)N * H);
-  g.rs_part = take((size_t)(L / 32) * N);
-  g.ra_part = take((size_t)(L / 32) * N);
+  g.rs_part = take((size_t)(attr_cols / 32) * N);
+  g.ra_part = take((size_t)(attr_cols / 32) * N);
   {
     const size_t kf = linear_ksplit_floats(N, H, L, 1, L);
     g.kpart = kf ? take(kf) : nullptr;
@@ -1523,6 +1525,112 @@ int mmf_amil_ig(const mmf_amil_desc* d, const float* x, void* workspace, size_t 
   np.M = d->N; np.N = d->L; np.K = d->H;
   np.mulx = x; np.ldx = d->L; np.rs_part = g.rs_part; np.ra_part = g.ra_part;
   return launch_nn_attr(np, ig->row_sum, ig->row_abs, st);
+}
+
+// ---- integrated gradients of the radiology head: reduce_dim folded into the same windows -------------------------------
+namespace mmf {
+struct RadioIgWs {
+  IgWs g;
+  float* Y;        // [N x L]: X Wr^T without bias, then P = Gacc W1 (Y is dead once U is formed)
+  float* b1c;      // [H]: b1 + W1 br
+  float* kpart;    // reduce_dim's K-split partial tiles, or null
+  size_t bytes;
+};
+static RadioIgWs carve_radio_ig(Carver& c, int64_t N, int nseg, int kseg, int H, int D, int gated, int steps) {
+  RadioIgWs r{};
+  r.Y = c.take<float>((size_t)N * kseg);
+  r.b1c = c.take<float>((size_t)H);
+  const size_t kf = linear_ksplit_floats(N, kseg, nseg * kseg, nseg, kseg);
+  r.kpart = kf ? c.take<float>(kf) : nullptr;
+  r.g = carve_ig(c, N, kseg, H, D, gated, steps, nseg * kseg);
+  r.bytes = c.off;
+  return r;
+}
+}  // namespace mmf
+
+size_t mmf_radio_ig_workspace_bytes(int64_t N, int32_t nseg, int32_t kseg, int32_t H, int32_t D, int32_t gated,
+                                    int32_t n_steps, int32_t window_steps) {
+  if (n_steps < 1 || n_steps > GROUP_MAX || window_steps < 0 || N < 1 || nseg < 2 || nseg > 4 || kseg < 32 || H < 32)
+    return 0;
+  if (N * nseg * (int64_t)kseg * 4 >= (int64_t)1 << 31) return 0;
+  const int steps = ig_window_steps(N, H, D, n_steps + 2, window_steps);
+  if (steps < 1) return 0;
+  Carver c;
+  return carve_radio_ig(c, N, nseg, kseg, H, D, gated, steps).bytes;
+}
+
+int mmf_radio_ig(const mmf_amil_desc* d, const mmf_radio_reduce* rd, void* workspace, size_t workspace_bytes,
+                 const mmf_surv_head* head, const mmf_ig_desc* ig, void* stream) {
+  if (!d || !ig || !head) return MMF_ERR_ARG;
+  if (d->gemm != MMF_GEMM_F32 || d->p_h != 0.f || d->p_att != 0.f) return MMF_ERR_ARG;
+  if (ig->n_steps < 1 || ig->n_steps > GROUP_MAX || ig->window_steps < 0 || !ig->alpha || !ig->weight) return MMF_ERR_ARG;
+  if (!ig->row_sum || !ig->row_abs || !ig->risk_x || !ig->risk_base || !ig->step_risk) return MMF_ERR_ARG;
+  if (!head->Wk || !head->bk) return MMF_ERR_ARG;
+  if (!rd || !rd->x || !rd->W || !rd->bias) return MMF_ERR_ARG;
+  const bool nseg_ok = rd->nseg >= 2 && rd->nseg <= 4;
+  for (int m = 0; nseg_ok && m < rd->nseg; ++m)
+    if (!rd->x[m]) return MMF_ERR_ARG;
+  if (!nseg_ok) return MMF_ERR_SHAPE;
+  if (int e = check_desc(d)) return e;
+  const int nseg = rd->nseg, kseg = rd->kseg, L = d->L, H = d->H;
+  if (kseg != L) return MMF_ERR_SHAPE;
+  if (d->N * nseg * (int64_t)kseg * 4 >= (int64_t)1 << 31) return MMF_ERR_SHAPE;     // mmf_radio_nll_step_group's input rule
+  if (head->K < 1 || head->K > 32) return MMF_ERR_SHAPE;
+  const int total = ig->n_steps + 2;
+  const int steps = ig_window_steps(d->N, d->H, d->D, total, ig->window_steps);
+  if (steps < 1) return MMF_ERR_SHAPE;
+  if (int e = radio_operands(d, rd, false)) return e;                                // what is left of it: the alignments
+  if (int e = check_operands(d, rd->x[0], workspace, ig->row_sum, false)) return e;
+  if (ig->attr && !aligned16(ig->attr)) return MMF_ERR_ALIGN;
+  Carver c(workspace);
+  const RadioIgWs r = carve_radio_ig(c, d->N, nseg, kseg, H, d->D, d->gated, steps);
+  if (r.bytes > workspace_bytes) return MMF_ERR_WORKSPACE;
+  const IgWs& g = r.g;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  TraceScope ts(d->trace);
+
+  float alpha[GROUP_MAX + 2], weight[GROUP_MAX + 2];
+  for (int q = 0; q < ig->n_steps; ++q) { alpha[q] = ig->alpha[q]; weight[q] = ig->weight[q]; }
+  alpha[ig->n_steps] = 1.f; alpha[ig->n_steps + 1] = 0.f;
+  weight[ig->n_steps] = weight[ig->n_steps + 1] = 0.f;
+
+  {   // Y = X Wr^T: reduce_dim over the segments without its bias, the forward-only pass's plan for N rows
+    LinearParams lr = radio_linear(d, rd, r.Y, r.kpart, nullptr);
+    lr.bias = nullptr;
+    if (int e = launch_linear(lr, st)) return e;
+  }
+  {   // U = Y W1^T: the stack's projection without bias, activation or bits
+    AmilWs wp{};
+    wp.h = g.U; wp.kpart = g.kpart;
+    LinearParams lp = stack_linear(d, wp, r.Y, 0);
+    lp.bias = nullptr; lp.act = ACT_NONE; lp.drop_p = 0.f; lp.seed_dev = nullptr;
+    if (int e = launch_linear(lp, st)) return e;
+  }
+  if (int e = launch_ig_bias(d->W1, rd->bias, d->b1, r.b1c, H, L, st)) return e;   // b1' = b1 + W1 br
+  mmf_amil_desc db = *d;               // the windows see the stack behind reduce_dim: u = alpha U + b1'
+  db.b1 = r.b1c;
+  IgHeadParams hp{};
+  hp.Wk = head->Wk; hp.bk = head->bk; hp.K = head->K; hp.H = H; hp.n_steps = ig->n_steps;
+  hp.step_risk = ig->step_risk; hp.risk_x = ig->risk_x; hp.risk_base = ig->risk_base;
+  hp.logits = head->logits; hp.hazards = head->hazards; hp.S = head->S; hp.risk = head->risk; hp.Y_hat = head->Y_hat;
+  for (int q0 = 0; q0 < total; q0 += steps) {
+    const int S = total - q0 < steps ? total - q0 : steps;
+    int nfold = ig->n_steps - q0;                    // the two riders carry weight 0: they are not folded
+    if (nfold > S) nfold = S;
+    if (nfold < 0) nfold = 0;
+    if (int e = ig_window(&db, g, alpha, weight, q0, S, nfold, q0 == 0, hp, st)) return e;
+  }
+  float* P = r.Y;                                    // P = Gacc W1 [N x L]
+  NnParams np{};
+  np.A = g.G; np.lda = H; np.B = d->W1; np.ldb = L; np.C = P; np.ldc = L;
+  np.M = d->N; np.N = L; np.K = H;
+  if (int e = launch_nn(np, st)) return e;
+  NnParams nq{};                                     // attr_m = x_m * (P Wr)[:, m kseg ..], and its row sums per modality
+  nq.A = P; nq.lda = L; nq.B = rd->W; nq.ldb = nseg * kseg; nq.C = ig->attr;
+  nq.M = d->N; nq.N = nseg * kseg; nq.K = L;
+  for (int m = 0; m < nseg; ++m) nq.segx[m] = rd->x[m];
+  nq.kseg = kseg; nq.rs_part = g.rs_part; nq.ra_part = g.ra_part;
+  return launch_nn_attr_seg(nq, ig->row_sum, ig->row_abs, st);
 }
 
 int mmf_surv_head_nll_step(const float* feat, int32_t F, const mmf_surv_head* head, const mmf_nll_target* target,
@@ -1934,6 +2042,27 @@ int mmf_linear_backward(const float* dy, const float* const* x_segs, int32_t nse
     NnParams np{};
     np.A = dy; np.lda = N; np.B = W; np.ldb = K; np.C = dx; np.ldc = K; np.M = M; np.N = K; np.K = N;
     return launch_nn(np, st);
+  }
+  return MMF_OK;
+}
+
+int mmf_linear_input_grad(const float* dy, const float* W, int32_t nseg, int32_t kseg, int64_t M, int32_t N,
+                          float* const* dx_segs, void* stream) {
+  if (!dy || !W || !dx_segs || nseg < 1 || nseg > 4) return MMF_ERR_ARG;
+  for (int i = 0; i < nseg; ++i)
+    if (!dx_segs[i]) return MMF_ERR_ARG;
+  if (M < 1 || N < KC || N % KC != 0 || kseg < 4 || kseg % 4 != 0) return MMF_ERR_SHAPE;
+  const int K = nseg * kseg;
+  if (M * (int64_t)(N > kseg ? N : kseg) * 4 >= (int64_t)1 << 31 || (int64_t)N * K * 4 >= (int64_t)1 << 31) return MMF_ERR_SHAPE;
+  if (!aligned16(dy) || !aligned16(W)) return MMF_ERR_ALIGN;
+  for (int i = 0; i < nseg; ++i)
+    if (!aligned16(dx_segs[i])) return MMF_ERR_ALIGN;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  for (int i = 0; i < nseg; ++i) {       // dx_i = dy . W[:, i kseg : (i + 1) kseg]
+    NnParams np{};
+    np.A = dy; np.lda = N; np.B = W + (size_t)i * kseg; np.ldb = K; np.C = dx_segs[i]; np.ldc = kseg;
+    np.M = M; np.N = kseg; np.K = N;
+    if (int e = launch_nn(np, st)) return e;
   }
   return MMF_OK;
 }

@@ -240,6 +240,10 @@ struct NnParams {          // C[M x N] = A[M x K] . B[K x N]   (plain; radio: dh
   // absolute values of the products go to rs_part / ra_part [(N / 32) x M], for ig_rows_kernel to add in block order
   const float* mulx; int ldx;
   float *rs_part, *ra_part;
+  // segmented attribution (launch_nn_attr_seg, mmf_radio_ig): the N = nseg * kseg columns are nseg modalities side by side,
+  // kseg % 32 == 0; 32-column block b belongs to segment b * 32 / kseg, whose multiplier is segx[m] [M x kseg] and whose
+  // product, when C is given, goes to C + m * M * kseg [M x kseg]; mulx, ldx and ldc are not read
+  const float* segx[4]; int kseg;
 };
 
 struct ReduceSeg { const float* in; float* out; int len; int nsplit; size_t stride; int block_begin; int tall; };
@@ -368,6 +372,11 @@ int launch_ig_fold(const IgFoldParams& p, hipStream_t st);
 // P = A . B times mulx, never stored unless p.C is given, and its per-row sums (NnParams' attribution fields), then
 // row_sum / row_abs [M] from the partials in column-block order: fixed order, no atomics
 int launch_nn_attr(NnParams p, float* row_sum, float* row_abs, hipStream_t st);
+// the radiology head (mmf_radio_ig).  out[j] = b1[j] + sum_l W1[j, l] br[l]: reduce_dim's bias behind the projection [H]
+int launch_ig_bias(const float* W1, const float* br, const float* b1, float* out, int H, int L, hipStream_t st);
+// launch_nn_attr over nseg = p.N / p.kseg modalities (NnParams' segmented fields): row_sum / row_abs [nseg x M], each
+// modality's kseg / 32 partials added in block order
+int launch_nn_attr_seg(NnParams p, float* row_sum, float* row_abs, hipStream_t st);
 
 int set_dyn_lds(const void* kern, int bytes);
 

@@ -219,6 +219,57 @@ def attribute_patches(model, bag, n_steps=20, method="gausslegendre", return_ful
     return out, torch.topk(out.patch_abs, k).indices
 
 
+def radio_integrated_gradients_autograd(model, bags, alphas, weights):
+    """integrated_gradients_autograd for the radiology head: for each (alpha_k, w_k) one
+    `model(**{m: (alpha_k * x_m).requires_grad_()})` pass, the gradient of risk = -sum(S) with respect to every modality,
+    and attr_m = x_m * sum_k w_k grad_km -- what captum does around the reference's radiology branch
+    (create_attributions.py:94-147), reduce_dim's and the stack's weight gradients included.  The yardstick of the fused
+    call (tools/radio_ig_bench.py, the tests).  Returns (inst_attr [n_mod x N], inst_abs [n_mod x N], attr [n_mod x N x k],
+    risk, risk_baseline, step_risk [n_steps]) on the device, the modalities in model.modalities order."""
+    if model.training:
+        raise RuntimeError("integrated gradients are an eval-mode pass: call model.eval() first")
+    dev = _dev(model)
+    mods = list(model.modalities)
+    xs = [bags[m].to(dev).float() for m in mods]
+    acc = [torch.zeros_like(x) for x in xs]
+    step_risk = []
+    for a, w in zip(alphas, weights):
+        xi = [(x * float(a)).requires_grad_() for x in xs]
+        _, S, _, _ = model(**dict(zip(mods, xi)))
+        risk = -S.sum()
+        gs = torch.autograd.grad(risk, xi)
+        for t, g in zip(acc, gs):
+            t.add_(g, alpha=float(w))
+        step_risk.append(risk.detach())
+    attr = torch.stack([t * x for t, x in zip(acc, xs)])
+    with torch.no_grad():
+        risk_x = -model(**dict(zip(mods, xs)))[1].sum()
+        risk_base = -model(**{m: torch.zeros_like(x) for m, x in zip(mods, xs)})[1].sum()
+    return attr.sum(2), attr.abs().sum(2), attr, risk_x, risk_base, torch.stack(step_risk)
+
+
+def attribute_radiology(model, bags, n_steps=20, method="gausslegendre", return_full=False, top_k=None):
+    """Attribution of one patient's MRI sequences, create_attributions.py:94-147 for the radiology head: integrated
+    gradients of the risk from a zero baseline in one fused call (model.integrated_gradients; `modality_abs` is the
+    reference's radio_attr per sequence, `inst_abs` per slice of each).  bags: {modality: [N x k]}.  The model is put in
+    eval mode for the call and restored.  Returns the RadioAttribution, or with top_k the pair (RadioAttribution, indices
+    of the top_k instances by sum_m inst_abs, largest first)."""
+    if not isinstance(model, MIL_Attention_fc_surv_radio):
+        raise NotImplementedError("attribute_radiology serves the radiology head")
+    dev = _dev(model)
+    was_training = model.training
+    model.eval()
+    try:
+        out = model.integrated_gradients(n_steps=n_steps, method=method, return_full=return_full,
+                                         **{m: bags[m].to(dev) for m in model.modalities})
+    finally:
+        model.train(was_training)
+    if top_k is None:
+        return out
+    score = out.inst_abs.sum(0)
+    return out, torch.topk(score, min(int(top_k), int(score.numel()))).indices
+
+
 # score_patch_batches(group=True): rows of one grouped scoring call per 256 hidden units.  Up to 128 projection tiles of 64 x
 # 64 (2,048 rows of the `small` head, 1,024 of `big`) a window of fp32 batches keeps the projection plan of a 512-patch
 # batch -- the same four-way K split, the same order of additions -- and with it every score bit for bit.

@@ -2,6 +2,8 @@
 (ctor signatures :14-15 / :67-68, forward(**kwargs) :73-115, state_dict keys)."""
 from __future__ import annotations
 
+from collections import namedtuple
+
 import torch
 import torch.nn as nn
 
@@ -9,6 +11,10 @@ from .. import ops
 from ..utils.utils import initialize_weights
 from .model_modules import (AMIL_SIZES, amil_stack, amil_stack_head, amil_stack_infer_group, amil_stack_nll_step,
                             amil_stack_nll_step_group, hand_over_grads, make_amil_stack, stack_args, step_grad_buffers)
+
+
+RadioAttribution = namedtuple("RadioAttribution", ["inst_attr", "inst_abs", "modality_attr", "modality_abs", "total",
+                                                   "total_abs", "risk", "risk_baseline", "delta", "step_risk", "attr"])
 
 
 class MIL_Attention_fc_radio(nn.Module):
@@ -141,6 +147,45 @@ class MIL_Attention_fc_surv_radio(MIL_Attention_fc_radio):
             hz, S, Y_hat, risk, A, _, loss = ops.radio_infer_group(xs, sizes, Wr, br, stack, gated, self.classifier.weight,
                                                                    self.classifier.bias, labels, censors, alpha)
         return hz, S, Y_hat, A, loss, risk
+
+    def integrated_gradients(self, n_steps=20, method="gausslegendre", return_full=False, window_steps=0, **bags):
+        """Integrated-gradients attribution of risk = -sum(S) to every instance of every modality, from a zero baseline,
+        in ONE C-ABI call (ops.radio_integrated_gradients) -- what the reference's create_attributions.py:94-147 gets from
+        captum through n_steps autograd passes of models/model_attention_mil_radio.py:73-115.  bags: {modality: [N x k]}
+        fp32 tensors of one shape; method, window_steps as MIL_Attention_fc_surv_path.integrated_gradients.
+        Returns RadioAttribution(inst_attr [n_mod x N] = sum_l attr, inst_abs [n_mod x N] = sum_l |attr|, modality_attr /
+        modality_abs [n_mod]: their sums over the instances (the reference's radio_attr per sequence), total, total_abs,
+        risk, risk_baseline, delta = total - (risk - risk_baseline), step_risk [n_steps], attr [n_mod x N x k] when
+        return_full else None), the modalities in self.modalities order.  One modality (no reduce_dim): the pathology
+        call on that bag, n_mod = 1.  Eval mode, fp32 bags, the stock head only."""
+        from ..utils.core_utils import _stock_head
+        if self.training:
+            raise RuntimeError("integrated_gradients is an eval-mode pass (dropout would make the integrand random): "
+                               "call model.eval() first")
+        if _stock_head(self, step=False)[0] != "radio":
+            raise NotImplementedError("integrated_gradients serves the stock radiology head only (no overridden forward, "
+                                      "no hooks, at most 32 classes)")
+        xs = [bags[m] for m in self.modalities]
+        if any(x.dtype == torch.bfloat16 for x in xs):
+            raise NotImplementedError("integrated_gradients takes fp32 bags: the bf16 path has no input gradient")
+        if len({tuple(x.shape) for x in xs}) != 1:
+            raise ops._lib.MmfError("the modalities of a bag must have the same [n x k] shape")
+        gated, stack, _, _ = stack_args(self.attention_net_radio, False)
+        alphas, weights = ops.ig_quadrature(method, n_steps)
+        Wk, bk = self.classifier.weight, self.classifier.bias
+        with torch.no_grad():
+            if len(xs) == 1:
+                rs, ra, attr, risk, base, step_risk = ops.amil_integrated_gradients(
+                    xs[0], stack, Wk, bk, gated, alphas, weights, want_attr=return_full, window_steps=window_steps)
+                rs, ra, attr = rs[None], ra[None], None if attr is None else attr[None]
+            else:
+                rs, ra, attr, risk, base, step_risk = ops.radio_integrated_gradients(
+                    xs, self.reduce_dim.weight, self.reduce_dim.bias, stack, Wk, bk, gated, alphas, weights,
+                    want_attr=return_full, window_steps=window_steps)
+            mod_attr, mod_abs = rs.sum(1), ra.sum(1)
+            total, total_abs = mod_attr.sum(), mod_abs.sum()
+            delta = total - (risk[0] - base[0])
+        return RadioAttribution(rs, ra, mod_attr, mod_abs, total, total_abs, risk[0], base[0], delta, step_risk, attr)
 
     def forward(self, **kwargs):
         bags = [kwargs[m] for m in self.modalities]

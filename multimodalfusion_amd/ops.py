@@ -807,6 +807,41 @@ def amil_integrated_gradients(x, stack, Wk, bk, gated, alphas, weights, want_att
     return rows[0], rows[1], attr, risks[0:1], risks[1:2], risks[2:]
 
 
+def radio_integrated_gradients(xs, Wr, br, stack, Wk, bk, gated, alphas, weights, want_attr=False, window_steps=0):
+    """Integrated gradients of the radiology head's risk = -sum(S) with respect to every modality, from a zero baseline, in
+    ONE C-ABI call (include/mmf_amil.h: mmf_radio_ig): reduce_dim and its transpose, the projection and its transpose run
+    once, the H-wide part once per quadrature node.  xs: 2 .. 4 modality tensors, each [N x k] fp32; Wr, br: reduce_dim
+    [k x nseg k], [k]; the other arguments as amil_integrated_gradients.  Returns (row_sum [nseg x N], row_abs [nseg x N],
+    attr [nseg x N x k] or None, risk_x [1], risk_base [1], step_risk [n_steps])."""
+    import numpy as np
+    if any(x.dtype == torch.bfloat16 for x in xs):
+        raise NotImplementedError("integrated gradients take fp32 bags: the bf16 path has no input gradient")
+    xs, N, nseg, kseg, rd = _radio_operands(xs, Wr, br, "pass")
+    stack, (Wk, bk), H, D = _stack_operands(stack, kseg, (Wk, bk), "bags", fused_head=True)
+    a = np.ascontiguousarray(np.asarray(alphas, dtype=np.float64).astype(np.float32))
+    w = np.ascontiguousarray(np.asarray(weights, dtype=np.float64).astype(np.float32))
+    if a.ndim != 1 or a.shape != w.shape or not 1 <= a.size <= GROUP_MAX:
+        raise _lib.MmfError(f"alphas / weights: two sequences of 1..{GROUP_MAX} values each")
+    n = int(a.size)
+    dev = xs[0].device
+    d = _amil_desc(stack, N, kseg, H, D, gated, 0.0, 0.0, 0, None)
+    l = lib()
+    nbytes = l.mmf_radio_ig_workspace_bytes(N, nseg, kseg, H, D, d.gated, n, int(window_steps))
+    if nbytes == 0:
+        raise _lib.MmfError("mmf_radio_ig: n_steps, window_steps, the modalities or the bag's size out of range")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    rows = torch.empty((2, nseg, N), dtype=torch.float32, device=dev)
+    attr = torch.empty((nseg, N, kseg), dtype=torch.float32, device=dev) if want_attr else None
+    risks = torch.empty(2 + n, dtype=torch.float32, device=dev)
+    sh = SurvHead(Wk=ptr(Wk), bk=ptr(bk), K=Wk.shape[0], logits=None, hazards=None, S=None, Y_hat=None, risk=None)
+    fp = C.POINTER(C.c_float)
+    ig = _lib.IgDesc(n_steps=n, alpha=a.ctypes.data_as(fp), weight=w.ctypes.data_as(fp), window_steps=int(window_steps),
+                     row_sum=ptr(rows[0]), row_abs=ptr(rows[1]), attr=ptr(attr), risk_x=ptr(risks[0:1]),
+                     risk_base=ptr(risks[1:2]), step_risk=ptr(risks[2:]))
+    check(l.mmf_radio_ig(C.byref(d), C.byref(rd), ptr(ws), nbytes, C.byref(sh), C.byref(ig), stream_ptr()), "mmf_radio_ig")
+    return rows[0], rows[1], attr, risks[0:1], risks[1:2], risks[2:]
+
+
 def radio_infer_group(xs, sizes, Wr, br, stack, gated, Wk=None, bk=None, Y=None, c=None, alpha=0.0, want_M=False,
                       eps=1e-7):
     """The radiology head's G bags evaluated in ONE C-ABI call (include/mmf_amil.h: mmf_radio_infer_group): reduce_dim
@@ -1083,6 +1118,20 @@ def _linear_cat_bwd_raw(gy, saved, has_bias, need_dx):
     return dW, db, dx
 
 
+def _linear_cat_dx_raw(gy, saved):
+    """The input gradients of a _linear_cat_fwd_raw call over several segments, one [M x k] tensor per segment
+    (mmf_linear_input_grad) -- the training steps never ask for them (bags are leaves); attribution by autograd does."""
+    W, *xs = saved
+    gy = _f32c(gy)
+    M, kseg = xs[0].shape
+    nseg = len(xs)
+    dxs = tuple(torch.empty_like(x) for x in xs)
+    segs = (C.c_void_p * nseg)(*[ptr(t) for t in dxs])
+    check(lib().mmf_linear_input_grad(ptr(gy), ptr(W), nseg, kseg, M, W.shape[0], segs, stream_ptr()),
+          "mmf_linear_input_grad")
+    return dxs
+
+
 class LinearCatFn(torch.autograd.Function):
     """y = cat(xs, dim=1) @ W.T + b without materialising the concatenation
     (models/model_attention_mil_radio.py:80-82)."""
@@ -1097,8 +1146,11 @@ class LinearCatFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gy):
         nseg = len(ctx.needs_input_grad) - 2
-        dW, db, dx = _linear_cat_bwd_raw(gy, ctx.saved_tensors, ctx.has_bias, any(ctx.needs_input_grad[2:]))
-        return (dW, db) + ((dx,) if nseg == 1 else (None,) * nseg)
+        need_dx = any(ctx.needs_input_grad[2:])
+        dW, db, dx = _linear_cat_bwd_raw(gy, ctx.saved_tensors, ctx.has_bias, need_dx and nseg == 1)
+        if nseg == 1:
+            return dW, db, dx
+        return (dW, db) + (_linear_cat_dx_raw(gy, ctx.saved_tensors) if need_dx else (None,) * nseg)
 
 
 def linear_cat(xs, W, b):
