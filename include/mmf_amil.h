@@ -328,8 +328,8 @@ int mmf_radio_infer_group(const mmf_amil_desc* desc, const mmf_bag_group* group,
  *   (which the L-wide bag can set below that limit; the call then returns MMF_ERR_SHAPE) nor the rules for L, H and D, so a
  *   non-zero answer does not say that the call admits the shape.  For a shape the call admits it is never 0: the row cap is
  *   at or below the window's limit.  It does not shrink as window_steps grows.
- * Out of scope: the radio and multimodal heads; non-zero baselines (they need a second projection, U' + alpha (U - U'));
- *   bf16 bags; targets other than risk.
+ * Out of scope: the multimodal heads (the radiology head: mmf_radio_ig); non-zero baselines (they need a second projection,
+ *   U' + alpha (U - U')); bf16 bags; targets other than risk.
  * ------------------------------------------------------------------------------------------- */
 typedef struct mmf_ig_desc {
   int32_t n_steps;           /* quadrature nodes, 1 .. MMF_GROUP_MAX */

@@ -781,11 +781,15 @@ static int group_plan(const int64_t* offsets, int G, SegTable& s) {
   return MMF_OK;
 }
 
-struct GroupWs {
-  AmilWs w;
-  float *M, *dM, *stats, *wk, *bk, *partials;
+// what every window of bags carries -- the grouped chain's, and integrated gradients' steps (IgWs)
+struct WindowWs {
+  AmilWs w;                  // the window's rows
+  float *M, *dM, *stats, *partials;
   uint32_t *ridx_h, *ridx_d;
   int* bag;
+};
+struct GroupWs : WindowWs {
+  float *wk, *bk;
   size_t bytes;
 };
 static GroupWs carve_group(Carver& c, const SegTable& s, int L, int H, int D, int gated) {
@@ -844,13 +848,35 @@ static int group_check(const mmf_amil_desc* d, const mmf_bag_group* group, const
 
 // The stack's chain over the window's rows x [sum N x L], in three parts.  The masks are those of the seed-0 keys at each
 // row's index base (group_rows_kernel).
+// The launch groups a window of integrated-gradients steps (ig_window) takes as they are.  The per-row tables:
+static int window_rows(const mmf_amil_desc* d, const SegTable& s, const WindowWs& g, hipStream_t st) {
+  GroupRowsParams rp{};
+  rp.s = s; rp.H = d->H; rp.D = d->D; rp.ridx_h = g.ridx_h; rp.ridx_d = g.ridx_d; rp.bag = g.bag;
+  return launch_group_rows(rp, st);
+}
+// the pooling partials, then the per-bag merge: M_g into M's rows, ldm floats apart, and into the workspace with its statistics
+static int window_pool(const mmf_amil_desc* d, const SegTable& s, const WindowWs& g, float* M, int ldm, float* A_raw,
+                       hipStream_t st) {
+  PoolParams pp = stack_pool(d, g.w, A_raw);
+  pp.partials = g.partials; pp.M = M; pp.stats = g.stats;
+  if (int e = launch_group_pool_partial(pp, s, st)) return e;
+  return launch_group_merge(pp, s, ldm, g.M, st);
+}
+// K-prep per bag and the segmented K-dh, from dM [G x H]; dbc_parts: the dbc partials K-prep leaves for a reduce launch
+static int window_dh(const mmf_amil_desc* d, const WindowWs& g, const GateBwdCtx& gc, const float* dM, const float* A_raw,
+                     int& dbc_parts, hipStream_t st) {
+  const BwdPrepParams bp = stack_prep(d, g.w, A_raw, g.stats, g.M, dM, nullptr);
+  dbc_parts = bp.n_groups;
+  if (int e = launch_group_bwd_prep(bp, g.bag, st)) return e;
+  BwdDhParams dp = stack_dh(d, g.w, gc, dM);
+  dp.seg_ridx = g.ridx_d; dp.seg_bag = g.bag;
+  return launch_bwd_dh_seg(dh_plan(dp, false), dp, st);
+}
+
 // Forward, up to the scores: per-row tables, projection, gate.
 static int group_chain_fwd(const mmf_amil_desc* d, const SegTable& s, const float* x, const GroupWs& gw, hipStream_t st) {
   const AmilWs& w = gw.w;
-
-  GroupRowsParams rp0{};
-  rp0.s = s; rp0.H = d->H; rp0.D = d->D; rp0.ridx_h = gw.ridx_h; rp0.ridx_d = gw.ridx_d; rp0.bag = gw.bag;
-  if (int e = launch_group_rows(rp0, st)) return e;
+  if (int e = window_rows(d, s, gw, st)) return e;
 
   LinearParams lp = stack_linear(d, w, x, 0);
   lp.seg_ridx = gw.ridx_h;
@@ -866,13 +892,9 @@ static int group_chain_fwd(const mmf_amil_desc* d, const SegTable& s, const floa
 static int group_chain_bwd(const mmf_amil_desc* d, const float* x, const GroupWs& gw, const float* dM, const float* A_raw,
                            const mmf_amil_grads* g, const GroupExtra* ex, ReduceList& rl, hipStream_t st) {
   const AmilWs& w = gw.w;
-  const BwdPrepParams bp = stack_prep(d, w, A_raw, gw.stats, gw.M, dM, nullptr);
-  if (int e = launch_group_bwd_prep(bp, gw.bag, st)) return e;
-
   const GateBwdCtx gc = gate_bwd_ctx(d, w.a, w.b, w.ds, 0);
-  BwdDhParams dp = stack_dh(d, w, gc, dM);
-  dp.seg_ridx = gw.ridx_d; dp.seg_bag = gw.bag;
-  if (int e = launch_bwd_dh_seg(dh_plan(dp, false), dp, st)) return e;
+  int dbc_parts;
+  if (int e = window_dh(d, gw, gc, dM, A_raw, dbc_parts, st)) return e;
 
   if (ex && ex->dx) {   // d(x) = du . W1: du carries every bag's ReLU and dropout masks
     if (int e = launch_nn(stack_dx(d, w, ex->dx), st)) return e;
@@ -893,7 +915,7 @@ static int group_chain_bwd(const mmf_amil_desc* d, const float* x, const GroupWs
     if (int e = launch_tn(tr, st)) return e;
   }
 
-  stack_reduce(d, w, g, bp.n_groups, rl);
+  stack_reduce(d, w, g, dbc_parts, rl);
   return MMF_OK;
 }
 
@@ -921,10 +943,7 @@ static int group_chain(const mmf_amil_desc* d, const SegTable& s, const float* x
 static int group_half_fwd(const mmf_amil_desc* d, const SegTable& s, const float* x, const GroupWs& gw, float* M, int ldm,
                           float* A_raw, hipStream_t st) {
   if (int e = group_chain_fwd(d, s, x, gw, st)) return e;
-  PoolParams pp = stack_pool(d, gw.w, A_raw);
-  pp.partials = gw.partials; pp.M = M; pp.stats = gw.stats;
-  if (int e = launch_group_pool_partial(pp, s, st)) return e;
-  return launch_group_merge(pp, s, ldm, gw.M, st);
+  return window_pool(d, s, gw, M, ldm, A_raw, st);
 }
 static int group_half_bwd(const mmf_amil_desc* d, const SegTable& s, const float* x, const GroupWs& gw, const float* dM,
                           int ldm, const float* A_raw, const mmf_amil_grads* g, const GroupExtra* ex, ReduceList& rl,
@@ -1372,14 +1391,11 @@ static int ig_window_steps(int64_t N, int H, int D, int total, int window_steps)
   return (int)((total + nwin - 1) / nwin);
 }
 
-struct IgWs {
-  AmilWs w;                  // the window's rows: h, relu_bits, a, b, s_part, p, ds, dbc_part, du (nothing else is set)
+struct IgWs : WindowWs {     // w: h, relu_bits, a, b, s_part, p, ds, dbc_part, du (nothing else is set)
   float *U, *G;              // [N x H]: x . W1^T, and the folded sum_s w_s du_s
   float *rs_part, *ra_part;  // [(attr_cols / 32) x N]: the attribution GEMM's per-block row sums
   float* kpart;              // the projection's K-split partial tiles, or null
-  float *M, *dM, *stats, *partials, *A_raw;
-  uint32_t *ridx_h, *ridx_d;
-  int* bag;
+  float* A_raw;
   size_t bytes;
 };
 // attr_cols: the attribution GEMM's columns -- L, or the radiology head's nseg * kseg (0: L)
@@ -1437,34 +1453,63 @@ static int ig_window(const mmf_amil_desc* d, const IgWs& g, const float* alpha, 
   ep.st.S = S;
   for (int s = 0; s < S; ++s) { ep.st.alpha[s] = alpha[q0 + s]; ep.st.w[s] = weight[q0 + s]; }
   if (int e = launch_ig_expand(ep, st)) return e;
-
-  GroupRowsParams rp{};
-  rp.s = seg; rp.H = d->H; rp.D = d->D; rp.ridx_h = g.ridx_h; rp.ridx_d = g.ridx_d; rp.bag = g.bag;
-  if (int e = launch_group_rows(rp, st)) return e;
+  if (int e = window_rows(&dw, seg, g, st)) return e;
 
   GateFwdParams gp = stack_gate_fwd(&dw, w, 0);
   gp.seg_ridx = g.ridx_d;
   if (int e = launch_gate_fwd_seg(gp, st)) return e;
-
-  PoolParams pp = stack_pool(&dw, w, g.A_raw);
-  pp.partials = g.partials; pp.M = g.M; pp.stats = g.stats;
-  if (int e = launch_group_pool_partial(pp, seg, st)) return e;
-  if (int e = launch_group_merge(pp, seg, d->H, g.M, st)) return e;
+  if (int e = window_pool(&dw, seg, g, g.M, d->H, g.A_raw, st)) return e;
 
   hp.M = g.M; hp.dM = g.dM; hp.step0 = q0;
   if (int e = launch_ig_head(hp, S, st)) return e;
 
-  const BwdPrepParams bp = stack_prep(&dw, w, g.A_raw, g.stats, g.M, g.dM, nullptr);
-  if (int e = launch_group_bwd_prep(bp, g.bag, st)) return e;
-  const GateBwdCtx gc = gate_bwd_ctx(&dw, w.a, w.b, w.ds, 0);
-  BwdDhParams dp = stack_dh(&dw, w, gc, g.dM);
-  dp.seg_ridx = g.ridx_d; dp.seg_bag = g.bag;
-  if (int e = launch_bwd_dh_seg(dh_plan(dp, false), dp, st)) return e;
+  int dbc_parts;                                     // no weight gradients: nothing reduces them
+  if (int e = window_dh(&dw, g, gate_bwd_ctx(&dw, w.a, w.b, w.ds, 0), g.dM, g.A_raw, dbc_parts, st)) return e;
 
   IgFoldParams fp{};
   fp.du = w.du; fp.G = g.G; fp.N = N; fp.H = d->H; fp.first = first ? 1 : 0;
   fp.st = ep.st; fp.st.S = nfold;
   return launch_ig_fold(fp, st);
+}
+
+// what both heads' calls refuse first: a null pointer, or a setting the call does not take
+static int ig_args(const mmf_amil_desc* d, const mmf_surv_head* head, const mmf_ig_desc* ig) {
+  if (!d || !ig || !head) return MMF_ERR_ARG;
+  if (d->gemm != MMF_GEMM_F32 || d->p_h != 0.f || d->p_att != 0.f) return MMF_ERR_ARG;
+  if (ig->n_steps < 1 || ig->n_steps > GROUP_MAX || ig->window_steps < 0 || !ig->alpha || !ig->weight) return MMF_ERR_ARG;
+  if (!ig->row_sum || !ig->row_abs || !ig->risk_x || !ig->risk_base || !ig->step_risk) return MMF_ERR_ARG;
+  return !head->Wk || !head->bk ? MMF_ERR_ARG : MMF_OK;
+}
+
+// The quadrature over the stack d from its input rows [N x L]: U = rows . W1^T, then the windows, `steps` steps each,
+// which leave the folded sum_s w_s du_s in g.G and the risks where ig says.
+static int ig_run(const mmf_amil_desc* d, const float* rows, const IgWs& g, int steps, const mmf_surv_head* head,
+                  const mmf_ig_desc* ig, hipStream_t st) {
+  const int n = ig->n_steps, total = n + 2;
+  float alpha[GROUP_MAX + 2], weight[GROUP_MAX + 2];
+  for (int q = 0; q < n; ++q) { alpha[q] = ig->alpha[q]; weight[q] = ig->weight[q]; }
+  alpha[n] = 1.f; alpha[n + 1] = 0.f;                // the two riders: risk_x, risk_base
+  weight[n] = weight[n + 1] = 0.f;
+
+  {   // the stack's projection without bias, activation or bits
+    AmilWs wp{};
+    wp.h = g.U; wp.kpart = g.kpart;
+    LinearParams lp = stack_linear(d, wp, rows, 0);
+    lp.bias = nullptr; lp.act = ACT_NONE; lp.drop_p = 0.f; lp.seed_dev = nullptr;
+    if (int e = launch_linear(lp, st)) return e;
+  }
+  IgHeadParams hp{};
+  hp.Wk = head->Wk; hp.bk = head->bk; hp.K = head->K; hp.H = d->H; hp.n_steps = n;
+  hp.step_risk = ig->step_risk; hp.risk_x = ig->risk_x; hp.risk_base = ig->risk_base;
+  hp.logits = head->logits; hp.hazards = head->hazards; hp.S = head->S; hp.risk = head->risk; hp.Y_hat = head->Y_hat;
+  for (int q0 = 0; q0 < total; q0 += steps) {
+    const int S = total - q0 < steps ? total - q0 : steps;
+    int nfold = n - q0;                              // the two riders carry weight 0: they are not folded
+    if (nfold > S) nfold = S;
+    if (nfold < 0) nfold = 0;
+    if (int e = ig_window(d, g, alpha, weight, q0, S, nfold, q0 == 0, hp, st)) return e;
+  }
+  return MMF_OK;
 }
 }  // namespace mmf
 
@@ -1479,15 +1524,10 @@ size_t mmf_amil_ig_workspace_bytes(int64_t N, int32_t L, int32_t H, int32_t D, i
 
 int mmf_amil_ig(const mmf_amil_desc* d, const float* x, void* workspace, size_t workspace_bytes,
                 const mmf_surv_head* head, const mmf_ig_desc* ig, void* stream) {
-  if (!d || !ig || !head) return MMF_ERR_ARG;
-  if (d->gemm != MMF_GEMM_F32 || d->p_h != 0.f || d->p_att != 0.f) return MMF_ERR_ARG;
-  if (ig->n_steps < 1 || ig->n_steps > GROUP_MAX || ig->window_steps < 0 || !ig->alpha || !ig->weight) return MMF_ERR_ARG;
-  if (!ig->row_sum || !ig->row_abs || !ig->risk_x || !ig->risk_base || !ig->step_risk) return MMF_ERR_ARG;
-  if (!head->Wk || !head->bk) return MMF_ERR_ARG;
+  if (int e = ig_args(d, head, ig)) return e;
   if (int e = check_desc(d)) return e;
   if (head->K < 1 || head->K > 32) return MMF_ERR_SHAPE;
-  const int total = ig->n_steps + 2;
-  const int steps = ig_window_steps(d->N, d->H, d->D, total, ig->window_steps);
+  const int steps = ig_window_steps(d->N, d->H, d->D, ig->n_steps + 2, ig->window_steps);
   if (steps < 1) return MMF_ERR_SHAPE;
   if (int e = check_operands(d, x, workspace, ig->row_sum, false)) return e;
   if (ig->attr && !aligned16(ig->attr)) return MMF_ERR_ALIGN;
@@ -1496,30 +1536,7 @@ int mmf_amil_ig(const mmf_amil_desc* d, const float* x, void* workspace, size_t 
   if (g.bytes > workspace_bytes) return MMF_ERR_WORKSPACE;
   hipStream_t st = static_cast<hipStream_t>(stream);
   TraceScope ts(d->trace);
-
-  float alpha[GROUP_MAX + 2], weight[GROUP_MAX + 2];
-  for (int q = 0; q < ig->n_steps; ++q) { alpha[q] = ig->alpha[q]; weight[q] = ig->weight[q]; }
-  alpha[ig->n_steps] = 1.f; alpha[ig->n_steps + 1] = 0.f;
-  weight[ig->n_steps] = weight[ig->n_steps + 1] = 0.f;
-
-  {   // U = x . W1^T: the stack's projection without bias, activation or bits
-    AmilWs wp{};
-    wp.h = g.U; wp.kpart = g.kpart;
-    LinearParams lp = stack_linear(d, wp, x, 0);
-    lp.bias = nullptr; lp.act = ACT_NONE; lp.drop_p = 0.f; lp.seed_dev = nullptr;
-    if (int e = launch_linear(lp, st)) return e;
-  }
-  IgHeadParams hp{};
-  hp.Wk = head->Wk; hp.bk = head->bk; hp.K = head->K; hp.H = d->H; hp.n_steps = ig->n_steps;
-  hp.step_risk = ig->step_risk; hp.risk_x = ig->risk_x; hp.risk_base = ig->risk_base;
-  hp.logits = head->logits; hp.hazards = head->hazards; hp.S = head->S; hp.risk = head->risk; hp.Y_hat = head->Y_hat;
-  for (int q0 = 0; q0 < total; q0 += steps) {
-    const int S = total - q0 < steps ? total - q0 : steps;
-    int nfold = ig->n_steps - q0;                    // the two riders carry weight 0: they are not folded
-    if (nfold > S) nfold = S;
-    if (nfold < 0) nfold = 0;
-    if (int e = ig_window(d, g, alpha, weight, q0, S, nfold, q0 == 0, hp, st)) return e;
-  }
+  if (int e = ig_run(d, x, g, steps, head, ig, st)) return e;
   NnParams np{};                                     // attr = x * (Gacc . W1), and its row sums
   np.A = g.G; np.lda = d->H; np.B = d->W1; np.ldb = d->L; np.C = ig->attr; np.ldc = d->L;
   np.M = d->N; np.N = d->L; np.K = d->H;
@@ -1561,11 +1578,7 @@ size_t mmf_radio_ig_workspace_bytes(int64_t N, int32_t nseg, int32_t kseg, int32
 
 int mmf_radio_ig(const mmf_amil_desc* d, const mmf_radio_reduce* rd, void* workspace, size_t workspace_bytes,
                  const mmf_surv_head* head, const mmf_ig_desc* ig, void* stream) {
-  if (!d || !ig || !head) return MMF_ERR_ARG;
-  if (d->gemm != MMF_GEMM_F32 || d->p_h != 0.f || d->p_att != 0.f) return MMF_ERR_ARG;
-  if (ig->n_steps < 1 || ig->n_steps > GROUP_MAX || ig->window_steps < 0 || !ig->alpha || !ig->weight) return MMF_ERR_ARG;
-  if (!ig->row_sum || !ig->row_abs || !ig->risk_x || !ig->risk_base || !ig->step_risk) return MMF_ERR_ARG;
-  if (!head->Wk || !head->bk) return MMF_ERR_ARG;
+  if (int e = ig_args(d, head, ig)) return e;
   if (!rd || !rd->x || !rd->W || !rd->bias) return MMF_ERR_ARG;
   const bool nseg_ok = rd->nseg >= 2 && rd->nseg <= 4;
   for (int m = 0; nseg_ok && m < rd->nseg; ++m)
@@ -1576,8 +1589,7 @@ int mmf_radio_ig(const mmf_amil_desc* d, const mmf_radio_reduce* rd, void* works
   if (kseg != L) return MMF_ERR_SHAPE;
   if (d->N * nseg * (int64_t)kseg * 4 >= (int64_t)1 << 31) return MMF_ERR_SHAPE;     // mmf_radio_nll_step_group's input rule
   if (head->K < 1 || head->K > 32) return MMF_ERR_SHAPE;
-  const int total = ig->n_steps + 2;
-  const int steps = ig_window_steps(d->N, d->H, d->D, total, ig->window_steps);
+  const int steps = ig_window_steps(d->N, d->H, d->D, ig->n_steps + 2, ig->window_steps);
   if (steps < 1) return MMF_ERR_SHAPE;
   if (int e = radio_operands(d, rd, false)) return e;                                // what is left of it: the alignments
   if (int e = check_operands(d, rd->x[0], workspace, ig->row_sum, false)) return e;
@@ -1589,37 +1601,15 @@ int mmf_radio_ig(const mmf_amil_desc* d, const mmf_radio_reduce* rd, void* works
   hipStream_t st = static_cast<hipStream_t>(stream);
   TraceScope ts(d->trace);
 
-  float alpha[GROUP_MAX + 2], weight[GROUP_MAX + 2];
-  for (int q = 0; q < ig->n_steps; ++q) { alpha[q] = ig->alpha[q]; weight[q] = ig->weight[q]; }
-  alpha[ig->n_steps] = 1.f; alpha[ig->n_steps + 1] = 0.f;
-  weight[ig->n_steps] = weight[ig->n_steps + 1] = 0.f;
-
   {   // Y = X Wr^T: reduce_dim over the segments without its bias, the forward-only pass's plan for N rows
     LinearParams lr = radio_linear(d, rd, r.Y, r.kpart, nullptr);
     lr.bias = nullptr;
     if (int e = launch_linear(lr, st)) return e;
   }
-  {   // U = Y W1^T: the stack's projection without bias, activation or bits
-    AmilWs wp{};
-    wp.h = g.U; wp.kpart = g.kpart;
-    LinearParams lp = stack_linear(d, wp, r.Y, 0);
-    lp.bias = nullptr; lp.act = ACT_NONE; lp.drop_p = 0.f; lp.seed_dev = nullptr;
-    if (int e = launch_linear(lp, st)) return e;
-  }
   if (int e = launch_ig_bias(d->W1, rd->bias, d->b1, r.b1c, H, L, st)) return e;   // b1' = b1 + W1 br
-  mmf_amil_desc db = *d;               // the windows see the stack behind reduce_dim: u = alpha U + b1'
+  mmf_amil_desc db = *d;               // the windows see the stack behind reduce_dim: U = Y W1^T, u = alpha U + b1'
   db.b1 = r.b1c;
-  IgHeadParams hp{};
-  hp.Wk = head->Wk; hp.bk = head->bk; hp.K = head->K; hp.H = H; hp.n_steps = ig->n_steps;
-  hp.step_risk = ig->step_risk; hp.risk_x = ig->risk_x; hp.risk_base = ig->risk_base;
-  hp.logits = head->logits; hp.hazards = head->hazards; hp.S = head->S; hp.risk = head->risk; hp.Y_hat = head->Y_hat;
-  for (int q0 = 0; q0 < total; q0 += steps) {
-    const int S = total - q0 < steps ? total - q0 : steps;
-    int nfold = ig->n_steps - q0;                    // the two riders carry weight 0: they are not folded
-    if (nfold > S) nfold = S;
-    if (nfold < 0) nfold = 0;
-    if (int e = ig_window(&db, g, alpha, weight, q0, S, nfold, q0 == 0, hp, st)) return e;
-  }
+  if (int e = ig_run(&db, r.Y, g, steps, head, ig, st)) return e;
   float* P = r.Y;                                    // P = Gacc W1 [N x L]
   NnParams np{};
   np.A = g.G; np.lda = H; np.B = d->W1; np.ldb = L; np.C = P; np.ldc = L;

@@ -173,6 +173,44 @@ def infer_patient(model, features, bins=None, label=None, verbose=False):
     return Y_hat_model, risk, A_final
 
 
+def _ig_autograd(model, inputs, alphas, weights, call):
+    """The loop of both autograd routes over the tensors `inputs`; call(list of tensors) runs the model on them.  Returns
+    ([attr per input], risk, risk_baseline, step_risk [n_steps]) on the device."""
+    if model.training:
+        raise RuntimeError("integrated gradients are an eval-mode pass: call model.eval() first")
+    dev = _dev(model)
+    xs = [x.to(dev).float() for x in inputs]
+    acc = [torch.zeros_like(x) for x in xs]
+    step_risk = []
+    for a, w in zip(alphas, weights):
+        xi = [(x * float(a)).requires_grad_() for x in xs]
+        _, S, _, _ = call(xi)
+        risk = -S.sum()
+        gs = torch.autograd.grad(risk, xi)
+        for t, g in zip(acc, gs):
+            t.add_(g, alpha=float(w))
+        step_risk.append(risk.detach())
+    with torch.no_grad():
+        risk_x = -call(xs)[1].sum()
+        risk_base = -call([torch.zeros_like(x) for x in xs])[1].sum()
+    return [t * x for t, x in zip(acc, xs)], risk_x, risk_base, torch.stack(step_risk)
+
+
+def _attribute_in_eval(model, call, score, top_k):
+    """call() -- the model's integrated_gradients -- with the model in eval mode for the call and restored; with top_k the
+    pair (its result, indices of the top_k entries of score(result), largest first)."""
+    was_training = model.training
+    model.eval()
+    try:
+        out = call()
+    finally:
+        model.train(was_training)
+    if top_k is None:
+        return out
+    s = score(out)
+    return out, torch.topk(s, min(int(top_k), int(s.numel()))).indices
+
+
 def integrated_gradients_autograd(model, bag, alphas, weights):
     """Integrated gradients of risk = -sum(S) from a zero baseline by the definition, one autograd pass per node: for each
     (alpha_k, w_k) `model(path_features=(alpha_k * bag).requires_grad_())`, the gradient of the risk with respect to that
@@ -180,23 +218,8 @@ def integrated_gradients_autograd(model, bag, alphas, weights):
     (create_attributions.py:94-102), and the route to attributions without model.integrated_gradients: n_steps training-
     sized backward passes, weight gradients included.  The yardstick of the fused call (tools/ig_bench.py, the tests).
     Returns (patch_attr [N], patch_abs [N], attr [N x L], risk, risk_baseline, step_risk [n_steps]) on the device."""
-    if model.training:
-        raise RuntimeError("integrated gradients are an eval-mode pass: call model.eval() first")
-    x = bag.to(_dev(model)).float()
-    acc = torch.zeros_like(x)
-    step_risk = []
-    for a, w in zip(alphas, weights):
-        xi = (x * float(a)).requires_grad_()
-        _, S, _, _ = model(path_features=xi)
-        risk = -S.sum()
-        (g,) = torch.autograd.grad(risk, xi)
-        acc.add_(g, alpha=float(w))
-        step_risk.append(risk.detach())
-    attr = acc * x
-    with torch.no_grad():
-        risk_x = -model(path_features=x)[1].sum()
-        risk_base = -model(path_features=torch.zeros_like(x))[1].sum()
-    return attr.sum(1), attr.abs().sum(1), attr, risk_x, risk_base, torch.stack(step_risk)
+    (attr,), *risks = _ig_autograd(model, [bag], alphas, weights, lambda xs: model(path_features=xs[0]))
+    return (attr.sum(1), attr.abs().sum(1), attr, *risks)
 
 
 def attribute_patches(model, bag, n_steps=20, method="gausslegendre", return_full=False, window_steps=0, top_k=None):
@@ -206,17 +229,9 @@ def attribute_patches(model, bag, n_steps=20, method="gausslegendre", return_ful
     pair (PatchAttribution, indices of the top_k patches by patch_abs, largest first)."""
     if not isinstance(model, MIL_Attention_fc_surv_path):
         raise NotImplementedError("attribute_patches serves the pathology head")
-    was_training = model.training
-    model.eval()
-    try:
-        out = model.integrated_gradients(bag.to(_dev(model)), n_steps=n_steps, method=method, return_full=return_full,
-                                         window_steps=window_steps)
-    finally:
-        model.train(was_training)
-    if top_k is None:
-        return out
-    k = min(int(top_k), int(out.patch_abs.numel()))
-    return out, torch.topk(out.patch_abs, k).indices
+    return _attribute_in_eval(model, lambda: model.integrated_gradients(
+        bag.to(_dev(model)), n_steps=n_steps, method=method, return_full=return_full, window_steps=window_steps),
+        lambda out: out.patch_abs, top_k)
 
 
 def radio_integrated_gradients_autograd(model, bags, alphas, weights):
@@ -224,28 +239,12 @@ def radio_integrated_gradients_autograd(model, bags, alphas, weights):
     `model(**{m: (alpha_k * x_m).requires_grad_()})` pass, the gradient of risk = -sum(S) with respect to every modality,
     and attr_m = x_m * sum_k w_k grad_km -- what captum does around the reference's radiology branch
     (create_attributions.py:94-147), reduce_dim's and the stack's weight gradients included.  The yardstick of the fused
-    call (tools/radio_ig_bench.py, the tests).  Returns (inst_attr [n_mod x N], inst_abs [n_mod x N], attr [n_mod x N x k],
-    risk, risk_baseline, step_risk [n_steps]) on the device, the modalities in model.modalities order."""
-    if model.training:
-        raise RuntimeError("integrated gradients are an eval-mode pass: call model.eval() first")
-    dev = _dev(model)
+    call (tools/ig_bench.py --head radio, the tests).  Returns (inst_attr [n_mod x N], inst_abs [n_mod x N],
+    attr [n_mod x N x k], risk, risk_baseline, step_risk [n_steps]) on the device, the modalities in model.modalities order."""
     mods = list(model.modalities)
-    xs = [bags[m].to(dev).float() for m in mods]
-    acc = [torch.zeros_like(x) for x in xs]
-    step_risk = []
-    for a, w in zip(alphas, weights):
-        xi = [(x * float(a)).requires_grad_() for x in xs]
-        _, S, _, _ = model(**dict(zip(mods, xi)))
-        risk = -S.sum()
-        gs = torch.autograd.grad(risk, xi)
-        for t, g in zip(acc, gs):
-            t.add_(g, alpha=float(w))
-        step_risk.append(risk.detach())
-    attr = torch.stack([t * x for t, x in zip(acc, xs)])
-    with torch.no_grad():
-        risk_x = -model(**dict(zip(mods, xs)))[1].sum()
-        risk_base = -model(**{m: torch.zeros_like(x) for m, x in zip(mods, xs)})[1].sum()
-    return attr.sum(2), attr.abs().sum(2), attr, risk_x, risk_base, torch.stack(step_risk)
+    attrs, *risks = _ig_autograd(model, [bags[m] for m in mods], alphas, weights, lambda xs: model(**dict(zip(mods, xs))))
+    attr = torch.stack(attrs)
+    return (attr.sum(2), attr.abs().sum(2), attr, *risks)
 
 
 def attribute_radiology(model, bags, n_steps=20, method="gausslegendre", return_full=False, top_k=None):
@@ -257,17 +256,9 @@ def attribute_radiology(model, bags, n_steps=20, method="gausslegendre", return_
     if not isinstance(model, MIL_Attention_fc_surv_radio):
         raise NotImplementedError("attribute_radiology serves the radiology head")
     dev = _dev(model)
-    was_training = model.training
-    model.eval()
-    try:
-        out = model.integrated_gradients(n_steps=n_steps, method=method, return_full=return_full,
-                                         **{m: bags[m].to(dev) for m in model.modalities})
-    finally:
-        model.train(was_training)
-    if top_k is None:
-        return out
-    score = out.inst_abs.sum(0)
-    return out, torch.topk(score, min(int(top_k), int(score.numel()))).indices
+    return _attribute_in_eval(model, lambda: model.integrated_gradients(
+        n_steps=n_steps, method=method, return_full=return_full, **{m: bags[m].to(dev) for m in model.modalities}),
+        lambda out: out.inst_abs.sum(0), top_k)
 
 
 # score_patch_batches(group=True): rows of one grouped scoring call per 256 hidden units.  Up to 128 projection tiles of 64 x

@@ -8,8 +8,8 @@ import torch
 import torch.nn as nn
 
 from ..utils.utils import initialize_weights
-from .model_modules import (AMIL_SIZES, amil_stack, amil_stack_head, amil_stack_infer_group, amil_stack_nll_step,
-                            amil_stack_nll_step_group, make_amil_stack, stack_args)
+from .model_modules import (AMIL_SIZES, amil_stack, amil_stack_head, amil_stack_ig, amil_stack_infer_group,
+                            amil_stack_nll_step, amil_stack_nll_step_group, make_amil_stack)
 
 PatchAttribution = namedtuple("PatchAttribution", ["patch_attr", "patch_abs", "total", "total_abs", "risk", "risk_baseline",
                                                    "delta", "step_risk", "attr"])
@@ -91,21 +91,7 @@ class MIL_Attention_fc_surv_path(MIL_Attention_fc_path):
         total, total_abs, risk, risk_baseline, delta = total - (risk - risk_baseline) (captum's convergence delta),
         step_risk [n_steps], attr [N x L] when return_full else None).  Eval mode, fp32 bags, the stock head only."""
         from .. import ops
-        from ..utils.core_utils import _stock_head
-        if self.training:
-            raise RuntimeError("integrated_gradients is an eval-mode pass (dropout would make the integrand random): "
-                               "call model.eval() first")
-        if _stock_head(self, step=False)[0] != "path":
-            raise NotImplementedError("integrated_gradients serves the stock pathology head only (no overridden forward, "
-                                      "no hooks, at most 32 classes)")
-        if path_features.dtype == torch.bfloat16:
-            raise NotImplementedError("integrated_gradients takes fp32 bags: the bf16 path has no input gradient")
-        gated, stack, _, _ = stack_args(self.attention_net_WSI, False)
-        alphas, weights = ops.ig_quadrature(method, n_steps)
-        with torch.no_grad():
-            rs, ra, attr, risk, base, step_risk = ops.amil_integrated_gradients(
-                path_features, stack, self.classifier.weight, self.classifier.bias, gated, alphas, weights,
-                want_attr=return_full, window_steps=window_steps)
-            total, total_abs = rs.sum(), ra.sum()
-            delta = total - (risk[0] - base[0])
-        return PatchAttribution(rs, ra, total, total_abs, risk[0], base[0], delta, step_risk, attr)
+        rs, ra, _, _, *rest = amil_stack_ig(self, "path", self.attention_net_WSI, [path_features],
+                                            ops.amil_integrated_gradients, (path_features,), n_steps, method, return_full,
+                                            window_steps)
+        return PatchAttribution(rs, ra, *rest)

@@ -9,8 +9,9 @@ import torch.nn as nn
 
 from .. import ops
 from ..utils.utils import initialize_weights
-from .model_modules import (AMIL_SIZES, amil_stack, amil_stack_head, amil_stack_infer_group, amil_stack_nll_step,
-                            amil_stack_nll_step_group, hand_over_grads, make_amil_stack, stack_args, step_grad_buffers)
+from .model_modules import (AMIL_SIZES, amil_stack, amil_stack_head, amil_stack_ig, amil_stack_infer_group,
+                            amil_stack_nll_step, amil_stack_nll_step_group, hand_over_grads, make_amil_stack, stack_args,
+                            step_grad_buffers)
 
 
 RadioAttribution = namedtuple("RadioAttribution", ["inst_attr", "inst_abs", "modality_attr", "modality_abs", "total",
@@ -158,34 +159,16 @@ class MIL_Attention_fc_surv_radio(MIL_Attention_fc_radio):
         risk, risk_baseline, delta = total - (risk - risk_baseline), step_risk [n_steps], attr [n_mod x N x k] when
         return_full else None), the modalities in self.modalities order.  One modality (no reduce_dim): the pathology
         call on that bag, n_mod = 1.  Eval mode, fp32 bags, the stock head only."""
-        from ..utils.core_utils import _stock_head
-        if self.training:
-            raise RuntimeError("integrated_gradients is an eval-mode pass (dropout would make the integrand random): "
-                               "call model.eval() first")
-        if _stock_head(self, step=False)[0] != "radio":
-            raise NotImplementedError("integrated_gradients serves the stock radiology head only (no overridden forward, "
-                                      "no hooks, at most 32 classes)")
         xs = [bags[m] for m in self.modalities]
-        if any(x.dtype == torch.bfloat16 for x in xs):
-            raise NotImplementedError("integrated_gradients takes fp32 bags: the bf16 path has no input gradient")
-        if len({tuple(x.shape) for x in xs}) != 1:
-            raise ops._lib.MmfError("the modalities of a bag must have the same [n x k] shape")
-        gated, stack, _, _ = stack_args(self.attention_net_radio, False)
-        alphas, weights = ops.ig_quadrature(method, n_steps)
-        Wk, bk = self.classifier.weight, self.classifier.bias
-        with torch.no_grad():
-            if len(xs) == 1:
-                rs, ra, attr, risk, base, step_risk = ops.amil_integrated_gradients(
-                    xs[0], stack, Wk, bk, gated, alphas, weights, want_attr=return_full, window_steps=window_steps)
-                rs, ra, attr = rs[None], ra[None], None if attr is None else attr[None]
-            else:
-                rs, ra, attr, risk, base, step_risk = ops.radio_integrated_gradients(
-                    xs, self.reduce_dim.weight, self.reduce_dim.bias, stack, Wk, bk, gated, alphas, weights,
-                    want_attr=return_full, window_steps=window_steps)
-            mod_attr, mod_abs = rs.sum(1), ra.sum(1)
-            total, total_abs = mod_attr.sum(), mod_abs.sum()
-            delta = total - (risk[0] - base[0])
-        return RadioAttribution(rs, ra, mod_attr, mod_abs, total, total_abs, risk[0], base[0], delta, step_risk, attr)
+        if len(xs) > 1:
+            call, lead = ops.radio_integrated_gradients, (xs, self.reduce_dim.weight, self.reduce_dim.bias)
+        else:
+            def call(*args, **kw):
+                rs, ra, attr, *risks = ops.amil_integrated_gradients(*args, **kw)
+                return (rs[None], ra[None], None if attr is None else attr[None], *risks)
+            lead = (xs[0],)
+        return RadioAttribution(*amil_stack_ig(self, "radio", self.attention_net_radio, xs, call, lead, n_steps, method,
+                                               return_full, window_steps))
 
     def forward(self, **kwargs):
         bags = [kwargs[m] for m in self.modalities]

@@ -396,6 +396,36 @@ def amil_stack_infer_group(seq, classifier, bags, Y=None, c=None, alpha=0.0, ret
     return hz, S, Y_hat, A, loss, risk
 
 
+def amil_stack_ig(model, kind, seq, xs, call, lead, n_steps, method, return_full, window_steps):
+    """What the heads' integrated_gradients methods share: the refusals (eval mode; the stock head `kind`, `path` or
+    `radio`, of core_utils._stock_head; fp32 tensors xs of one shape), the rule's nodes (ops.ig_quadrature), the call
+    `call(*lead, stack, Wk, bk, gated, alphas, weights, ...)` (ops.amil_ / radio_integrated_gradients) and the sums over
+    its result.  Returns (row_sum, row_abs, their sums over the rows, total, total_abs, risk, risk_baseline,
+    delta = total - (risk - risk_baseline), step_risk, attr)."""
+    from .. import ops
+    from ..utils.core_utils import _stock_head
+    if model.training:
+        raise RuntimeError("integrated_gradients is an eval-mode pass (dropout would make the integrand random): "
+                           "call model.eval() first")
+    if _stock_head(model, step=False)[0] != kind:
+        name = {"path": "pathology", "radio": "radiology"}[kind]
+        raise NotImplementedError(f"integrated_gradients serves the stock {name} head only (no overridden forward, "
+                                  "no hooks, at most 32 classes)")
+    if any(x.dtype == torch.bfloat16 for x in xs):
+        raise NotImplementedError("integrated_gradients takes fp32 bags: the bf16 path has no input gradient")
+    if len({tuple(x.shape) for x in xs}) != 1:
+        raise ops._lib.MmfError("the modalities of a bag must have the same [n x k] shape")
+    gated, stack, _, _ = stack_args(seq, False)
+    alphas, weights = ops.ig_quadrature(method, n_steps)
+    with torch.no_grad():
+        rs, ra, attr, risk, base, step_risk = call(*lead, stack, model.classifier.weight, model.classifier.bias, gated,
+                                                   alphas, weights, want_attr=return_full, window_steps=window_steps)
+        row_attr, row_abs = rs.sum(-1), ra.sum(-1)          # per modality; the pathology call's are the totals already
+        total, total_abs = (row_attr.sum(), row_abs.sum()) if rs.dim() > 1 else (row_attr, row_abs)
+        delta = total - (risk[0] - base[0])
+    return rs, ra, row_attr, row_abs, total, total_abs, risk[0], base[0], delta, step_risk, attr
+
+
 def amil_stack_head(seq, classifier, x, training):
     """amil_stack followed by the classifier / hazard head as one autograd node -> (hazards, S, Y_hat, A_raw)."""
     from .. import ops

@@ -769,13 +769,43 @@ def ig_quadrature(method, n_steps):
     raise ValueError(f"method must be one of {IG_METHODS}, got {method!r}")
 
 
+def _integrated_gradients(name, dims, lead, ranged, stack, H, D, gated, Wk, bk, alphas, weights, want_attr, window_steps,
+                          dev):
+    """What both integrated-gradients calls do once their operands are prepared.  name: the entry point; dims: the leading
+    arguments of its workspace query, (N, L) or (N, nseg, kseg), whose middle ones are the leading extents of the row sums
+    and of attr; lead: the call's arguments between the descriptor and the workspace; ranged: what the query's refusal
+    names as out of range."""
+    import numpy as np
+    a = np.ascontiguousarray(np.asarray(alphas, dtype=np.float64).astype(np.float32))
+    w = np.ascontiguousarray(np.asarray(weights, dtype=np.float64).astype(np.float32))
+    if a.ndim != 1 or a.shape != w.shape or not 1 <= a.size <= GROUP_MAX:
+        raise _lib.MmfError(f"alphas / weights: two sequences of 1..{GROUP_MAX} values each")
+    n = int(a.size)
+    N, ext, L = dims[0], tuple(dims[1:-1]), dims[-1]
+    d = _amil_desc(stack, N, L, H, D, gated, 0.0, 0.0, 0, None)
+    l = lib()
+    nbytes = getattr(l, name + "_workspace_bytes")(*dims, H, D, d.gated, n, int(window_steps))
+    if nbytes == 0:
+        raise _lib.MmfError(f"{name}: n_steps, window_steps{ranged} or the bag's size out of range")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    rows = torch.empty((2,) + ext + (N,), dtype=torch.float32, device=dev)
+    attr = torch.empty(ext + (N, L), dtype=torch.float32, device=dev) if want_attr else None
+    risks = torch.empty(2 + n, dtype=torch.float32, device=dev)
+    sh = SurvHead(Wk=ptr(Wk), bk=ptr(bk), K=Wk.shape[0], logits=None, hazards=None, S=None, Y_hat=None, risk=None)
+    fp = C.POINTER(C.c_float)
+    ig = _lib.IgDesc(n_steps=n, alpha=a.ctypes.data_as(fp), weight=w.ctypes.data_as(fp), window_steps=int(window_steps),
+                     row_sum=ptr(rows[0]), row_abs=ptr(rows[1]), attr=ptr(attr), risk_x=ptr(risks[0:1]),
+                     risk_base=ptr(risks[1:2]), step_risk=ptr(risks[2:]))
+    check(getattr(l, name)(C.byref(d), lead, ptr(ws), nbytes, C.byref(sh), C.byref(ig), stream_ptr()), name)
+    return rows[0], rows[1], attr, risks[0:1], risks[1:2], risks[2:]
+
+
 def amil_integrated_gradients(x, stack, Wk, bk, gated, alphas, weights, want_attr=False, window_steps=0):
     """Integrated gradients of risk = -sum(S) with respect to the bag x [N x L] (fp32), from a zero baseline, in ONE C-ABI
     call (include/mmf_amil.h: mmf_amil_ig): the L-wide contractions run once, the H-wide part once per quadrature node.
     alphas, weights: the rule's nodes and weights (host sequences, rounded once to fp32); window_steps: nodes per grouped
     window (0: the library chooses).  Eval mode: no dropout.  Returns (row_sum [N], row_abs [N], attr [N x L] or None,
     risk_x [1], risk_base [1], step_risk [n_steps])."""
-    import numpy as np
     if x.dtype == torch.bfloat16:
         raise NotImplementedError("integrated gradients take fp32 bags: the bf16 path has no input gradient")
     x = _f32c(x)
@@ -783,28 +813,8 @@ def amil_integrated_gradients(x, stack, Wk, bk, gated, alphas, weights, want_att
         raise _lib.MmfError(f"bag must be [N x L], got {tuple(x.shape)}")
     N, L = x.shape
     stack, (Wk, bk), H, D = _stack_operands(stack, L, (Wk, bk), "bag", fused_head=True)
-    a = np.ascontiguousarray(np.asarray(alphas, dtype=np.float64).astype(np.float32))
-    w = np.ascontiguousarray(np.asarray(weights, dtype=np.float64).astype(np.float32))
-    if a.ndim != 1 or a.shape != w.shape or not 1 <= a.size <= GROUP_MAX:
-        raise _lib.MmfError(f"alphas / weights: two sequences of 1..{GROUP_MAX} values each")
-    n = int(a.size)
-    dev = x.device
-    d = _amil_desc(stack, N, L, H, D, gated, 0.0, 0.0, 0, None)
-    l = lib()
-    nbytes = l.mmf_amil_ig_workspace_bytes(N, L, H, D, d.gated, n, int(window_steps))
-    if nbytes == 0:
-        raise _lib.MmfError("mmf_amil_ig: n_steps, window_steps or the bag's size out of range")
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    rows = torch.empty((2, N), dtype=torch.float32, device=dev)
-    attr = torch.empty((N, L), dtype=torch.float32, device=dev) if want_attr else None
-    risks = torch.empty(2 + n, dtype=torch.float32, device=dev)
-    sh = SurvHead(Wk=ptr(Wk), bk=ptr(bk), K=Wk.shape[0], logits=None, hazards=None, S=None, Y_hat=None, risk=None)
-    fp = C.POINTER(C.c_float)
-    ig = _lib.IgDesc(n_steps=n, alpha=a.ctypes.data_as(fp), weight=w.ctypes.data_as(fp), window_steps=int(window_steps),
-                     row_sum=ptr(rows[0]), row_abs=ptr(rows[1]), attr=ptr(attr), risk_x=ptr(risks[0:1]),
-                     risk_base=ptr(risks[1:2]), step_risk=ptr(risks[2:]))
-    check(l.mmf_amil_ig(C.byref(d), ptr(x), ptr(ws), nbytes, C.byref(sh), C.byref(ig), stream_ptr()), "mmf_amil_ig")
-    return rows[0], rows[1], attr, risks[0:1], risks[1:2], risks[2:]
+    return _integrated_gradients("mmf_amil_ig", (N, L), ptr(x), "", stack, H, D, gated, Wk, bk, alphas, weights, want_attr,
+                                 window_steps, x.device)
 
 
 def radio_integrated_gradients(xs, Wr, br, stack, Wk, bk, gated, alphas, weights, want_attr=False, window_steps=0):
@@ -813,33 +823,12 @@ def radio_integrated_gradients(xs, Wr, br, stack, Wk, bk, gated, alphas, weights
     once, the H-wide part once per quadrature node.  xs: 2 .. 4 modality tensors, each [N x k] fp32; Wr, br: reduce_dim
     [k x nseg k], [k]; the other arguments as amil_integrated_gradients.  Returns (row_sum [nseg x N], row_abs [nseg x N],
     attr [nseg x N x k] or None, risk_x [1], risk_base [1], step_risk [n_steps])."""
-    import numpy as np
     if any(x.dtype == torch.bfloat16 for x in xs):
         raise NotImplementedError("integrated gradients take fp32 bags: the bf16 path has no input gradient")
     xs, N, nseg, kseg, rd = _radio_operands(xs, Wr, br, "pass")
     stack, (Wk, bk), H, D = _stack_operands(stack, kseg, (Wk, bk), "bags", fused_head=True)
-    a = np.ascontiguousarray(np.asarray(alphas, dtype=np.float64).astype(np.float32))
-    w = np.ascontiguousarray(np.asarray(weights, dtype=np.float64).astype(np.float32))
-    if a.ndim != 1 or a.shape != w.shape or not 1 <= a.size <= GROUP_MAX:
-        raise _lib.MmfError(f"alphas / weights: two sequences of 1..{GROUP_MAX} values each")
-    n = int(a.size)
-    dev = xs[0].device
-    d = _amil_desc(stack, N, kseg, H, D, gated, 0.0, 0.0, 0, None)
-    l = lib()
-    nbytes = l.mmf_radio_ig_workspace_bytes(N, nseg, kseg, H, D, d.gated, n, int(window_steps))
-    if nbytes == 0:
-        raise _lib.MmfError("mmf_radio_ig: n_steps, window_steps, the modalities or the bag's size out of range")
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    rows = torch.empty((2, nseg, N), dtype=torch.float32, device=dev)
-    attr = torch.empty((nseg, N, kseg), dtype=torch.float32, device=dev) if want_attr else None
-    risks = torch.empty(2 + n, dtype=torch.float32, device=dev)
-    sh = SurvHead(Wk=ptr(Wk), bk=ptr(bk), K=Wk.shape[0], logits=None, hazards=None, S=None, Y_hat=None, risk=None)
-    fp = C.POINTER(C.c_float)
-    ig = _lib.IgDesc(n_steps=n, alpha=a.ctypes.data_as(fp), weight=w.ctypes.data_as(fp), window_steps=int(window_steps),
-                     row_sum=ptr(rows[0]), row_abs=ptr(rows[1]), attr=ptr(attr), risk_x=ptr(risks[0:1]),
-                     risk_base=ptr(risks[1:2]), step_risk=ptr(risks[2:]))
-    check(l.mmf_radio_ig(C.byref(d), C.byref(rd), ptr(ws), nbytes, C.byref(sh), C.byref(ig), stream_ptr()), "mmf_radio_ig")
-    return rows[0], rows[1], attr, risks[0:1], risks[1:2], risks[2:]
+    return _integrated_gradients("mmf_radio_ig", (N, nseg, kseg), C.byref(rd), ", the modalities", stack, H, D, gated, Wk,
+                                 bk, alphas, weights, want_attr, window_steps, xs[0].device)
 
 
 def radio_infer_group(xs, sizes, Wr, br, stack, gated, Wk=None, bk=None, Y=None, c=None, alpha=0.0, want_M=False,
