@@ -1435,10 +1435,6 @@ DhPlan plan_bwd_dh(int64_t N, int H, int D, int gated, int dropout, int split, i
   pl.dbc_groups = pl.fused ? pl.mt_count : 0;
   return pl;
 }
-int bwd_dh_fused_groups(int64_t N, int H, int allow_half, int D, int gated, int split, int concurrent) {
-  (void)allow_half;
-  return plan_bwd_dh(N, H, D, gated, 0, split, concurrent, 1, 0x7fffffff).dbc_groups;
-}
 
 // The tile of each (kind, height) and the forms it is compiled in: FUSED (K-prep inside) and PLAIN (after a K-prep launch;
 // the grouped step's SEG instantiations are PLAIN forms of the exact-fp32 tiles).  The plain epilogue has no code for the
@@ -1456,13 +1452,7 @@ static int with_dh_tile(const DhPlan& pl, F&& f) {
     case DH_128: return f(DhTile<Tile<128, 128, 2, 2, true, false>, false, true>{});
     case DH_64X128: return f(DhTile<Tile<64, 128, 2, 2, true, false>, true, false>{});
     case DH_64: return f(DhTile<Tile<64, 64, 2, 2, true, false>, true, true>{});
-    case DH_WIDE:
-      switch (pl.rows) {
-#define MMF_WIDE_CASE(R) case R: return f(DhWide<R>{});
-        MMF_WIDE_CASE(64) MMF_WIDE_CASE(80) MMF_WIDE_CASE(96) MMF_WIDE_CASE(112) MMF_WIDE_CASE(128) MMF_WIDE_CASE(144)
-        MMF_WIDE_CASE(160) MMF_WIDE_CASE(176) MMF_WIDE_CASE(192) MMF_WIDE_CASE(208) MMF_WIDE_CASE(224)
-#undef MMF_WIDE_CASE
-      }
+    case DH_WIDE: return with_wide_rows<DH_MAX_ROWS>(pl.rows, [&](auto r) { return f(DhWide<decltype(r)::value>{}); });
   }
   return MMF_ERR_ARG;
 }
@@ -1621,20 +1611,43 @@ int launch_ig_fold(const IgFoldParams& p, hipStream_t st) {
 // Tile / split plan of the TN GEMM.  256x256 tiles (8 waves, one workgroup per CU): 65 FLOP per operand byte
 // instead of 32, which is what the per-CU load rate needs (profiles/r01/load_rate.txt); the price is twice the
 // splits (slab traffic) for the same number of workgroups, so it is used only for long K.
-int tn_tile_dim(int64_t K, int D_gate) {
-  static const int env = tune_int("MMF_TN_WIDE", 1);
+TnPlan plan_tn(int64_t K, int split, const TnShape* shapes, int nshape) {
+  static const int env_wide = tune_int("MMF_TN_WIDE", 1);
   static const int kmin = tune_int("MMF_TN_WIDE_MIN", 12288);   // tuning override
-  if (!env || K < kmin) return 128;       // measured crossover: 10k bags 236 vs 243 us per step, 14k 294 vs 289
-  (void)D_gate;
-  return 256;
-}
-int tn_splits(int64_t K, int total_tiles, int tile) {
   static const int env_splits = tune_int("MMF_TN_SPLITS", 0);   // tuning override
-  int splits = (tile == 256 ? 256 : 512) / (total_tiles > 0 ? total_tiles : 1);
-  if (env_splits > 0) splits = env_splits;
-  const int64_t max_splits = (K + 127) / 128;
-  if (splits > max_splits) splits = (int)max_splits;
-  return splits < 1 ? 1 : splits;
+  static const int env_gate = tune_int("MMF_TN_GATE_SPLITS", -1);   // tuning override
+  TnPlan pl{};
+  // measured crossover: 10k bags 236 vs 243 us per step, 14k 294 vs 289
+  pl.tile = env_wide && K >= kmin ? 256 : 128;
+  pl.kind = pl.tile == 256 ? (split ? TN_SPLIT_256 : TN_256) : (split && K >= split_min_rows() ? TN_SPLIT_128 : TN_128);
+  // a gate problem's tiles: ceil(2 D / tile) gated, the same number as launch_tn's ceil(D / (tile / 2))
+  const int td = pl.tile;
+  int t_plain = 0, t_gate = 0;
+  for (int i = 0; i < nshape; ++i)
+    (shapes[i].gate ? t_gate : t_plain) += ((shapes[i].M + td - 1) / td) * ((shapes[i].Ncols + td - 1) / td);
+  pl.tiles = t_plain + t_gate;
+  // one workgroup per CU (two of the 128 x 128 tiles), at least 128 instances a split
+  auto capped = [&](int64_t s) { if (s > (K + 127) / 128) s = (K + 127) / 128; return (int)(s < 1 ? 1 : s); };   // K <= 0: 1
+  // Rows per split: splits are cut at multiples of 4 instances (one MFMA k-step of the TN tile), not of whole 32-instance
+  // chunks: all splits then have the same length and end with a partial chunk whose empty fragment groups are skipped.
+  auto kps = [&](int s) { return (int)(((K + s - 1) / s + 3) / 4 * 4); };
+  pl.splits = capped(env_splits > 0 ? env_splits : (td == 256 ? 256 : 512) / (pl.tiles > 0 ? pl.tiles : 1));
+  pl.k_per_split = kps(pl.splits);
+  // A gate tile builds its A operand (dP from a, b, ds) in the staging path and lives ~8 % longer per K row than a
+  // dW1 tile (in-kernel cycle stamps: 710 k vs 659 k with equal splits), so the whole launch waited for the gate tiles.  The
+  // workgroups the uniform split leaves over (256 - 6 x 42 = 4) go to the gate problem: 44 splits of 36 chunks beside
+  // 42 of 38 at N = 50k.  Large-bag tile only, at most 12 % more splits.
+  pl.splits_g = pl.splits;
+  if (t_plain > 0 && t_gate > 0) {
+    if (td == 256 && pl.splits >= 8) {
+      const int cap = pl.splits + (pl.splits * 12 + 99) / 100;
+      const int sg = (256 - t_plain * pl.splits) / t_gate;
+      pl.splits_g = sg > cap ? cap : sg < pl.splits ? pl.splits : sg;
+    }
+    if (env_gate > 0) pl.splits_g = env_gate;
+  }
+  pl.k_per_split_g = kps(pl.splits_g);
+  return pl;
 }
 
 // the large-bag tile is instantiated per attention-dropout state (no per-element test in the gate tiles' staging path)
@@ -1647,19 +1660,21 @@ static int launch_tn_grid(const TnParams& p, int grid, hipStream_t st) {
     const char* name = T::SPLIT ? "tn_split_kernel" : "tn_kernel";
     if (p.g.drop_p > 0.f) return launch_tiled<T>(name, tn_kernel<T, 1>, p, grid, st);
     return launch_tiled<T>(name, tn_kernel<T, 0>, p, grid, st);
+  } else {
+    return launch_tiled<T>("tn_kernel", tn_kernel<T>, p, grid, st);
   }
-  return launch_tiled<T>("tn_kernel", tn_kernel<T>, p, grid, st);
 }
 
 template <class T>
-static int launch_tn_t(TnParams p, hipStream_t st) {
-  if (p.k_per_split % 4 != 0 || p.splits < 1) return MMF_ERR_ARG;
+static int launch_tn_t(const TnPlan& pl, TnParams p, hipStream_t st) {
+  p.tile = pl.tile; p.splits = pl.splits; p.k_per_split = pl.k_per_split;
   int tiles = 0, blocks = 0;
   for (int i = 0; i < p.nprob; ++i) {
     TnProblem& q = p.prob[i];
     if (q.Ncols % 4 != 0 || q.ldb % 4 != 0 || q.M % 4 != 0) return MMF_ERR_SHAPE;
     if (q.kind == TN_A_PLAIN && q.lda % 4 != 0) return MMF_ERR_SHAPE;
-    if (q.splits <= 0) { q.splits = p.splits; q.k_per_split = p.k_per_split; }
+    q.splits = q.kind == TN_A_GATE ? pl.splits_g : pl.splits;
+    q.k_per_split = q.kind == TN_A_GATE ? pl.k_per_split_g : pl.k_per_split;
     if (q.k_per_split % 4 != 0 || q.k_per_split < 4) return MMF_ERR_ARG;
     if (q.kind == TN_A_GATE) {
       const int dt = p.g.gated ? T::BM / 2 : T::BM;      // attention dims per tile (both halves together when gated)
@@ -1713,11 +1728,14 @@ static int launch_tn_t(TnParams p, hipStream_t st) {
   return launch_tn_grid<T>(p, blocks, st);
 }
 
-int launch_tn(TnParams p, hipStream_t st) {
-  if (p.tile == 256 && p.split) return launch_tn_t<TileSp<256, 256, 2, 4>>(p, st);
-  if (p.tile == 256) return launch_tn_t<Tile<256, 256, 2, 4, false, false, 2>>(p, st);
-  if (p.split && p.K >= split_min_rows()) return launch_tn_t<TileSp<128, 128, 2, 2>>(p, st);
-  return launch_tn_t<Tile<128, 128, 2, 2, false, false, 2>>(p, st);
+int launch_tn(const TnPlan& pl, TnParams p, hipStream_t st) {
+  switch (pl.kind) {
+    case TN_SPLIT_256: return launch_tn_t<TileSp<256, 256, 2, 4>>(pl, p, st);
+    case TN_256: return launch_tn_t<Tile<256, 256, 2, 4, false, false, 2>>(pl, p, st);
+    case TN_SPLIT_128: return launch_tn_t<TileSp<128, 128, 2, 2>>(pl, p, st);
+    case TN_128: return launch_tn_t<Tile<128, 128, 2, 2, false, false, 2>>(pl, p, st);
+  }
+  return MMF_ERR_ARG;
 }
 
 int launch_reduce(ReduceParams p, hipStream_t st) {

@@ -740,7 +740,6 @@ bool short_grid(int64_t workgroups) {
 
 using TileNT128 = Tile<128, 128, 2, 2, true, true>;
 using TileNT64 = Tile<64, 64, 2, 2, true, true>;
-using TileNT32 = Tile<32, 64, 1, 2, true, true>;     // two waves: fills the chip where 64 x 64 tiles make <= 128 workgroups
 
 // rows-per-tile choice: big tiles once there is enough work to fill 256 CUs twice over
 static inline bool use_big_tiles(int64_t M, int N) { return (M / 128) * ((N + 127) / 128) >= 256; }
@@ -784,13 +783,6 @@ bool use_wide_tiles(int64_t M, int N, int split) {
   return env && N % 256 == 0 && M * (int64_t)(N / 256) >= min_rows;
 }
 
-template <int ROWS, bool SEG = false>
-static int launch_linear_wide(LinearParams p, hipStream_t st) {
-  using T = TileW<ROWS>;
-  p.mt_count = (int)((p.M + T::BM - 1) / T::BM); p.nt_count = p.N / 256;
-  return launch_tiled<T>("linear_nt_kernel", linear_nt_kernel<T, SEG>, p, grid_for_tiles(p.mt_count, p.nt_count), st);
-}
-
 int split_min_rows() {
   // measured one bag per step, exact fp32 -> bf16x3: 1k 0.101 -> 0.096 ms, 2k 0.115 -> 0.106, 4,096 0.137 -> 0.127,
   // 6k 0.165 -> 0.140, 10k 0.235 -> 0.190, 14k 0.285 -> 0.235 (profiles/r02/d_split_sizes.txt): never slower.  Default 1:
@@ -800,35 +792,54 @@ int split_min_rows() {
   static const int env = tune_int("MMF_SPLIT_MIN", 1);   // tuning override
   return env;
 }
-template <int ROWS, int WM, int WN, int GM = 1>
-static int launch_linear_split(LinearParams p, hipStream_t st) {
-  using T = TileSp<ROWS, 256, WM, WN, GM>;
-  p.mt_count = (int)((p.M + T::BM - 1) / T::BM); p.nt_count = p.N / 256;
-  return launch_tiled<T>("linear_nt_split_kernel", linear_nt_split_kernel<T>, p, grid_for_tiles(p.mt_count, p.nt_count), st);
-}
 
+// ---- the projection: one plan, one launcher ------------------------------------------------------------------------
 // K split of the 64 x 64 projection tiles on short grids (LinearParams::ksplit).  A bag of 1,000 instances is 64 tiles, each
 // a serial loop over 32 k-chunks (~25 us whatever the tile does: one MFMA block per wave and chunk), on 256 CUs; the radio
 // head's reduce_dim (M = 512, K = 4 x 1024) is 128 tiles of 128 chunks.  Split S ways they are S times as many workgroups with
 // loops 1 / S as long; the partial tiles (S x M x N floats) cross L2 / Infinity Cache once each way.
-int linear_ksplit(int64_t M, int N, int K, int nseg, int kseg) {
+LinearPlan plan_linear(int64_t M, int N, int K, int nseg, int kseg, int allow_half, int concurrent, int split, int tick_words) {
   static const int max_wg = tune_int("MMF_KSPLIT_MAX_WG", 512);     // tuning override: 0 = never split
-  if (M <= 0 || N % 4 != 0 || K % KC != 0 || use_wide_tiles(M, N, 0) || use_big_tiles(M, N)) return 1;
-  const int64_t tiles = ((M + 63) / 64) * ((N + 63) / 64);
-  const int nk = K / KC;
-  if (nseg > 1 && (kseg % (4 * KC) != 0)) return 1;
   // measured (round 4, path bags, projection kernel us unsplit -> split): 512 rows 25.4 -> 23.2, 1,000 26.4 -> 20.3, 2,000
   // 26.5 -> 24.5, 4,096 (256 tiles, two ways) 26.4 -> 29.3: from one tile per CU on, splitting only adds the partial traffic
   static const int max_tiles = tune_int("MMF_KSPLIT_MAX_TILES", 128);
-  if (tiles > max_tiles) return 1;
-  for (int S = 4; S >= 2; S -= 2)
-    if (tiles * S <= max_wg && nk % (4 * S) == 0 && nk / S >= 8) return S;
-  return 1;
+  static const int deep_seg = tune_int("MMF_DEEP_SEG", 1);      // A/B switch: deep prefetch for segmented inputs too
+  LinearPlan pl{};
+  pl.kind = LIN_64; pl.rows = 64; pl.ksplit = 1;
+  if (M <= 0) return pl;
+  const bool can_split = split && K % (4 * SKC) == 0 && nseg == 1;
+  if (can_split && use_wide_tiles(M, N, 1)) {
+    pl.kind = LIN_SPLIT_WIDE; pl.rows = 224;
+  } else if (use_wide_tiles(M, N, can_split)) {      // a height no tile is compiled for (an override's) runs as 224 rows
+    const int r = pick_wide_rows(M, N / 256, allow_half != 0, concurrent != 0, 240);
+    pl.kind = LIN_WIDE; pl.rows = r >= 64 && r <= 240 && r % 16 == 0 ? r : 224;
+  } else if (!can_split && use_big_tiles(M, N)) {
+    pl.kind = LIN_128; pl.rows = 128;
+  } else if (can_split && M >= split_min_rows()) {
+    pl.kind = LIN_SPLIT_64;
+  }
+  const int bn = pl.kind == LIN_SPLIT_WIDE || pl.kind == LIN_WIDE ? 256 : pl.rows;
+  pl.mt_count = (int)((M + pl.rows - 1) / pl.rows); pl.nt_count = (N + bn - 1) / bn;
+  const int64_t tiles = (int64_t)pl.mt_count * pl.nt_count;
+  const int nk = K / KC;
+  const bool seg_deep = nseg == 1 || kseg % (4 * KC) == 0;      // a segment boundary never falls inside a four-chunk step
+  if (pl.kind == LIN_64) {
+    if (tiles <= tick_words && tiles <= max_tiles && N % 4 == 0 && K % KC == 0 && seg_deep)
+      for (int S = 4; S >= 2 && pl.ksplit == 1; S -= 2)
+        if (tiles * S <= max_wg && nk % (4 * S) == 0 && nk / S >= 8) pl.ksplit = S;
+    if (pl.ksplit > 1) {
+      pl.kind = LIN_KSPLIT_64;
+      pl.deep = short_grid(tiles * pl.ksplit) ? 1 : 0;        // (K / KC / S) % 4 == 0 by the rule above
+      pl.kpart_floats = pl.ksplit * (int)tiles * 64 * 64;
+    } else {
+      pl.deep = short_grid(tiles) && nk % 4 == 0 && (nseg == 1 || (deep_seg && seg_deep)) ? 1 : 0;
+    }
+  }
+  pl.grid = grid_for_tiles(pl.mt_count, pl.nt_count * pl.ksplit);
+  return pl;
 }
 size_t linear_ksplit_floats(int64_t M, int N, int K, int nseg, int kseg) {
-  const int S = linear_ksplit(M, N, K, nseg, kseg);
-  if (S <= 1) return 0;
-  return (size_t)S * (size_t)((M + 63) / 64) * (size_t)((N + 63) / 64) * 64 * 64;
+  return (size_t)plan_linear(M, N, K, nseg, kseg, 0, 0, 0, 0x7fffffff).kpart_floats;
 }
 
 // SEG: the grouped step's projection (ReLU + dropout with per-bag masks, fp32 mode only); the plan is the same
@@ -838,51 +849,24 @@ static int launch_linear_impl(LinearParams p, hipStream_t st) {
   if (p.N % 4 != 0) return MMF_ERR_SHAPE;     // linear_epilogue: float4 stores of y and loads of the bias, never across the edge
   if (p.ldx % 4 != 0) return MMF_ERR_ALIGN;
   if (p.M <= 0) return MMF_OK;
-  const bool can_split = p.split && p.K % (4 * SKC) == 0 && p.nseg == 1;
-  if (can_split && use_wide_tiles(p.M, p.N, 1)) {
-    static const int rows = tune_int("MMF_SPLIT_ROWS", 224);
-    static const int gm = tune_int("MMF_SPLIT_GM", 1);      // A/B switch
-    if (gm == 2 && rows == 224) return launch_linear_split<224, 1, 8, 2>(p, st);
-    if (rows == 256) return launch_linear_split<256, 2, 4>(p, st);
-    if (rows == 192) return launch_linear_split<192, 1, 8>(p, st);
-    return launch_linear_split<224, 1, 8>(p, st);
+  const LinearPlan pl = plan_linear(p.M, p.N, p.K, p.nseg, p.kseg, p.allow_half, p.concurrent, p.split,
+                                    p.kpart && p.ktick ? p.ktick_words : 0);
+  p.mt_count = pl.mt_count; p.nt_count = pl.nt_count; p.ksplit = pl.ksplit; p.deep = pl.deep;
+  auto go = [&](auto tile) -> int {
+    using T = decltype(tile);
+    void (*kern)(LinearParams);       // the split-operand tiles have no grouped form: launch_linear_seg refuses them
+    if constexpr (T::SPLIT) kern = linear_nt_split_kernel<T>; else kern = linear_nt_kernel<T, SEG>;
+    return launch_tiled<T>(T::SPLIT ? "linear_nt_split_kernel" : "linear_nt_kernel", kern, p, pl.grid, st);
+  };
+  switch (pl.kind) {
+    case LIN_SPLIT_WIDE: return go(TileSp<224, 256, 1, 8>{});
+    case LIN_SPLIT_64: return go(TileSp<64, 64, 2, 2>{});
+    case LIN_128: return go(TileNT128{});
+    case LIN_KSPLIT_64:
+    case LIN_64: return go(TileNT64{});
+    case LIN_WIDE: return with_wide_rows<240>(pl.rows, [&](auto r) { return go(TileW<decltype(r)::value>{}); });
   }
-  if (use_wide_tiles(p.M, p.N, can_split)) {
-    switch (pick_wide_rows(p.M, p.N / 256, p.allow_half != 0, p.concurrent != 0, 240)) {
-#define MMF_WIDE_CASE(R) case R: return launch_linear_wide<R, SEG>(p, st);
-      MMF_WIDE_CASE(64) MMF_WIDE_CASE(80) MMF_WIDE_CASE(96) MMF_WIDE_CASE(112) MMF_WIDE_CASE(128)
-      MMF_WIDE_CASE(144) MMF_WIDE_CASE(160) MMF_WIDE_CASE(176) MMF_WIDE_CASE(192) MMF_WIDE_CASE(208) MMF_WIDE_CASE(240)
-#undef MMF_WIDE_CASE
-      default: return launch_linear_wide<224, SEG>(p, st);
-    }
-  }
-  if (!can_split && use_big_tiles(p.M, p.N)) {
-    p.mt_count = (int)((p.M + 127) / 128); p.nt_count = (p.N + 127) / 128;
-    return launch_tiled<TileNT128>("linear_nt_kernel", linear_nt_kernel<TileNT128, SEG>, p, grid_for_tiles(p.mt_count, p.nt_count), st);
-  }
-  p.mt_count = (int)((p.M + 63) / 64); p.nt_count = (p.N + 63) / 64;
-  if (can_split && p.M >= split_min_rows()) {
-    using T = TileSp<64, 64, 2, 2>;
-    return launch_tiled<T>("linear_nt_split_kernel", linear_nt_split_kernel<T>, p, grid_for_tiles(p.mt_count, p.nt_count), st);
-  }
-  {
-    const int S = (p.kpart && p.ktick) ? linear_ksplit(p.M, p.N, p.K, p.nseg, p.kseg) : 1;
-    if (S > 1 && p.mt_count * p.nt_count <= p.ktick_words) {
-      p.ksplit = S;
-      p.deep = short_grid((int64_t)p.mt_count * p.nt_count * S) ? 1 : 0;        // (K / KC / S) % 4 == 0 by linear_ksplit
-      return launch_tiled<TileNT64>("linear_nt_kernel", linear_nt_kernel<TileNT64, SEG>, p, grid_for_tiles(p.mt_count, p.nt_count * S), st);
-    }
-  }
-  // a segmented (radio: M = 512, K = 4 x 1024) or otherwise long-K projection on <= 128 workgroups leaves half the CUs
-  // idle for the whole K loop: half-height tiles (two waves) put it on twice as many
-  static const int half_tiles = tune_int("MMF_LINEAR_HALF_TILES", 0);   // A/B switch (off: measured slower or equal)
-  static const int deep_seg = tune_int("MMF_DEEP_SEG", 1);      // A/B switch: deep prefetch for segmented inputs too
-  p.deep = short_grid(p.mt_count * p.nt_count) && (p.K / KC) % 4 == 0 && (p.nseg == 1 || (deep_seg && p.kseg % (4 * KC) == 0)) ? 1 : 0;
-  if (!SEG && half_tiles && !p.deep && p.mt_count * p.nt_count <= 128 && p.M > 32 && p.K >= 1024) {   // (short plain grids: deep prefetch instead)
-    p.mt_count = (int)((p.M + 31) / 32);
-    return launch_tiled<TileNT32>("linear_nt_kernel", linear_nt_kernel<TileNT32>, p, grid_for_tiles(p.mt_count, p.nt_count), st);
-  }
-  return launch_tiled<TileNT64>("linear_nt_kernel", linear_nt_kernel<TileNT64, SEG>, p, grid_for_tiles(p.mt_count, p.nt_count), st);
+  return MMF_ERR_ARG;
 }
 
 int launch_linear(LinearParams p, hipStream_t st) { return launch_linear_impl<false>(p, st); }
@@ -891,41 +875,26 @@ int launch_linear_seg(LinearParams p, hipStream_t st) {
   return p.drop_p > 0.f ? launch_linear_impl<true>(p, st) : launch_linear_impl<false>(p, st);
 }
 
-int gate_parts(int D, int gated, int64_t N) {
-  (void)N;
-  // one s_part row per attention-dim tile; tile width must match launch_gate_fwd()
-  return gated ? (D + 63) / 64 : (D + 127) / 128;
-}
+// ---- the gate forward: one plan, one launcher ------------------------------------------------------------------------
+// one s_part row per attention-dim tile: BN = 128 always (64 gated dims, or 128 ungated dims, per tile), whatever the bag size
+int gate_parts(int D, int gated) { return gated ? (D + 63) / 64 : (D + 127) / 128; }
 
-template <bool SEG>
-static int launch_gate_fwd_impl(GateFwdParams p, hipStream_t st) {
-  if (p.H % KC != 0 || p.D % 32 != 0) return MMF_ERR_SHAPE;
-  if (p.N <= 0) return MMF_OK;
-  // BN = 128 always (64 gated dims, or 128 ungated dims, per tile) so that gate_parts() is size independent
-  p.nt_count = gate_parts(p.D, p.gated, p.N);
-  p.row_begin = 0; p.row_end = p.N;
-  using TS = Tile<64, 128, 2, 2, true, true>;
-  using SB = TileSp<128, 128, 2, 2>;
-  using SS = TileSp<64, 128, 2, 2>;
-  const bool split = p.split && p.H % (4 * SKC) == 0;
-  auto small = [&](GateFwdParams q) {
-    q.mt_count = (int)((q.row_end - q.row_begin + 63) / 64);
-    if (split && q.N >= split_min_rows()) {
-      const int grid = grid_for_tiles(q.mt_count, q.nt_count);
-      return q.gated ? launch_tiled<SS>("gate_fwd_split_kernel", gate_fwd_kernel<SS, true>, q, grid, st)
-                     : launch_tiled<SS>("gate_fwd_split_kernel", gate_fwd_kernel<SS, false>, q, grid, st);
-    }
-    q.deep = short_grid(q.mt_count * q.nt_count) && (q.H / KC) % 4 == 0 ? 1 : 0;
-    const int grid = grid_for_tiles(q.mt_count, q.nt_count);
-    return q.gated ? launch_tiled<TS>("gate_fwd_kernel", gate_fwd_kernel<TS, true, SEG>, q, grid, st)
-                   : launch_tiled<TS>("gate_fwd_kernel", gate_fwd_kernel<TS, false, SEG>, q, grid, st);
-  };
+GatePlan plan_gate_fwd(int64_t N, int H, int D, int gated, int split) {
   // 128-row tiles only once they fill most of the 512 slots (two workgroups per CU): a 10k bag is 316 tall tiles -- every
   // CU busy for a tall tile's time, 60 of them twice -- or 628 short ones in 1.2 rounds: measured 40.6 vs 35.1 us (round 4,
   // DESIGN.md §5, profiles/r04/d_mid_size_knobs.txt; 12,288 rows: 40.3 vs 35.3; from 12,800 rows the tall tiles win, 14k: 41.0 vs 44.0)
   static const int big_min = tune_int("MMF_GATE_BIG_MIN", 400);
-  const bool big = (p.N / 128) * p.nt_count >= big_min;
-  if (!big) return small(p);
+  static const int env_gate = tune_int("MMF_GATE_MIXED", -1);   // A/B switch
+  GatePlan pl{};
+  pl.kind = GATE_64; pl.nt_count = gate_parts(D, gated);
+  if (N <= 0) return pl;
+  const bool split_k = split && H % (4 * SKC) == 0;
+  if ((N / 128) * pl.nt_count < big_min) {
+    pl.split = split_k && N >= split_min_rows(); pl.mt_count = (int)((N + 63) / 64);
+    pl.deep = !pl.split && short_grid((int64_t)pl.mt_count * pl.nt_count) && (H / KC) % 4 == 0 ? 1 : 0;
+    pl.grid = grid_for_tiles(pl.mt_count, pl.nt_count);
+    return pl;
+  }
   // 128x128 tiles run two per CU: 512 slots.  Two things cost this launch time: a sparse last round (a 50k bag is
   // 1564 tiles = 3 rounds + 28 tiles, which cost most of a 4th round: 132 us against 116 us for the 1536 tiles of
   // 49,152 rows) and the two workgroups of a CU running IN PHASE -- both in their main loops, then both in their
@@ -940,46 +909,64 @@ static int launch_gate_fwd_impl(GateFwdParams p, hipStream_t st) {
   // R = whole rounds of 512 tall tiles in the bag.  MMF_GATE_MIXED=2: A + E only (the first version of this: 133 -> 128 us).
   // split-operand tiles: their main loop is short against their epilogue, and the out-of-phase plan's extra short tiles
   // cost more than the phase offset wins (A + E only: 91.2 us; dephased: 96.4; uniform tiles: 94.5)
-  static const int env_gate = tune_int("MMF_GATE_MIXED", -1);   // A/B switch
-  const int env_mixed = env_gate >= 0 ? env_gate : (split ? 2 : 1);
-  int64_t mt = (p.N + 127) / 128;
-  const int64_t slots = 512, total = mt * p.nt_count;
+  pl.split = split_k;
+  const int mixed = env_gate >= 0 ? env_gate : (split_k ? 2 : 1);
+  const int64_t mt = (N + 127) / 128, slots = 512, total = mt * pl.nt_count;
   const int R = (int)(total / slots);
-  if (env_mixed && R >= 2 && slots % (2 * p.nt_count) == 0) {
-    const int half_m = (int)(slots / 2 / p.nt_count);          // m-tiles in a wave of 256 workgroups
-    int64_t row = 0;
-    int grid = 0, n = 0;
-    auto region = [&](int tall, int64_t m_tiles) {
-      if (m_tiles <= 0) return;
-      p.reg[n].row0 = row; p.reg[n].mt_count = (int)m_tiles; p.reg[n].grid_begin = grid; p.reg[n].tall = tall;
-      grid += grid_for_tiles((int)m_tiles, p.nt_count);
-      row += m_tiles * (tall ? 128 : 64);
-      ++n;
-    };
-    if (env_mixed == 2) {
-      const int64_t rem = total % slots;
-      region(1, (total - rem) / p.nt_count);
-    } else {
-      region(1, half_m);
-      region(0, half_m);
-      region(1, (int64_t)half_m * (2 * R - 2));
-      region(0, half_m);
-    }
-    region(0, (p.N - row + 63) / 64);
-    p.nreg = n;
-    if (split)
-      return p.gated ? launch_tiled<SB>("gate_fwd_split_kernel", gate_fwd_mixed_kernel<SB, SS, true>, p, grid, st)
-                     : launch_tiled<SB>("gate_fwd_split_kernel", gate_fwd_mixed_kernel<SB, SS, false>, p, grid, st);
-    return p.gated ? launch_tiled<TileNT128>("gate_fwd_kernel", gate_fwd_mixed_kernel<TileNT128, TS, true, SEG>, p, grid, st)
-                   : launch_tiled<TileNT128>("gate_fwd_kernel", gate_fwd_mixed_kernel<TileNT128, TS, false, SEG>, p, grid, st);
+  if (!mixed || R < 2 || slots % (2 * pl.nt_count) != 0) {
+    pl.kind = GATE_128; pl.mt_count = (int)mt;
+    pl.grid = grid_for_tiles(pl.mt_count, pl.nt_count);
+    return pl;
   }
-  p.mt_count = (int)mt;
-  const int grid = grid_for_tiles(p.mt_count, p.nt_count);
-  if (split)
-    return p.gated ? launch_tiled<SB>("gate_fwd_split_kernel", gate_fwd_kernel<SB, true>, p, grid, st)
-                   : launch_tiled<SB>("gate_fwd_split_kernel", gate_fwd_kernel<SB, false>, p, grid, st);
-  return p.gated ? launch_tiled<TileNT128>("gate_fwd_kernel", gate_fwd_kernel<TileNT128, true, SEG>, p, grid, st)
-                 : launch_tiled<TileNT128>("gate_fwd_kernel", gate_fwd_kernel<TileNT128, false, SEG>, p, grid, st);
+  pl.kind = GATE_MIXED;
+  const int half_m = (int)(slots / 2 / pl.nt_count);          // m-tiles in a wave of 256 workgroups
+  int64_t row = 0;
+  auto region = [&](int tall, int64_t m_tiles) {
+    if (m_tiles <= 0) return;
+    pl.reg[pl.nreg++] = {(int)row, (int)m_tiles, pl.grid, tall};
+    pl.grid += grid_for_tiles((int)m_tiles, pl.nt_count);
+    pl.mt_count += (int)m_tiles;
+    row += m_tiles * (tall ? 128 : 64);
+  };
+  if (mixed == 2) {
+    region(1, (total - total % slots) / pl.nt_count);
+  } else {
+    region(1, half_m);
+    region(0, half_m);
+    region(1, (int64_t)half_m * (2 * R - 2));
+    region(0, half_m);
+  }
+  region(0, (N - row + 63) / 64);
+  return pl;
+}
+
+template <bool SEG>
+static int launch_gate_fwd_impl(GateFwdParams p, hipStream_t st) {
+  if (p.H % KC != 0 || p.D % 32 != 0) return MMF_ERR_SHAPE;
+  if (p.N <= 0) return MMF_OK;
+  const GatePlan pl = plan_gate_fwd(p.N, p.H, p.D, p.gated, p.split);
+  p.nt_count = pl.nt_count; p.mt_count = pl.mt_count; p.deep = pl.deep; p.nreg = pl.nreg;
+  p.row_begin = 0; p.row_end = p.N;
+  for (int i = 0; i < pl.nreg; ++i) p.reg[i] = {pl.reg[i].row0, pl.reg[i].mt_count, pl.reg[i].grid_begin, pl.reg[i].tall};
+  // ts: the short tile of a mixed launch, of tb's thread count and column width.  The split-operand tiles have no grouped
+  // form: launch_gate_fwd_seg refuses them.
+  auto go = [&](auto tb, auto... ts) -> int {
+    using TB = decltype(tb);
+    constexpr bool S = SEG && !TB::SPLIT;
+    void (*kern)(GateFwdParams);
+    if constexpr (sizeof...(ts) == 0) kern = p.gated ? gate_fwd_kernel<TB, true, S> : gate_fwd_kernel<TB, false, S>;
+    else kern = p.gated ? gate_fwd_mixed_kernel<TB, decltype(ts)..., true, S> : gate_fwd_mixed_kernel<TB, decltype(ts)..., false, S>;
+    return launch_tiled<TB>(TB::SPLIT ? "gate_fwd_split_kernel" : "gate_fwd_kernel", kern, p, pl.grid, st);
+  };
+  using TS = Tile<64, 128, 2, 2, true, true>;
+  using SB = TileSp<128, 128, 2, 2>;
+  using SS = TileSp<64, 128, 2, 2>;
+  switch (pl.kind) {
+    case GATE_64: return pl.split ? go(SS{}) : go(TS{});
+    case GATE_128: return pl.split ? go(SB{}) : go(TileNT128{});
+    case GATE_MIXED: return pl.split ? go(SB{}, SS{}) : go(TileNT128{}, TS{});
+  }
+  return MMF_ERR_ARG;
 }
 
 int launch_gate_fwd(GateFwdParams p, hipStream_t st) { return launch_gate_fwd_impl<false>(p, st); }

@@ -92,14 +92,6 @@ struct Carver {
   }
 };
 
-// Rows per split of a split-K TN launch over K >= 1 rows.  Splits are cut at multiples of 4 instances (one MFMA k-step
-// of the TN tile), not of whole 32-instance chunks: all splits then have the same length and end with a partial chunk
-// whose empty fragment groups are skipped.
-static int k_per_split(int64_t K, int splits) {
-  const int64_t kps = (K + splits - 1) / splits;
-  return (int)((kps + 3) / 4 * 4);
-}
-
 // The segments of one reduce launch.  add() refuses a segment past the last slot, and the launch then refuses the list.
 struct ReduceList {
   ReduceParams p{};
@@ -134,40 +126,20 @@ struct AmilWs {
   float *h, *a, *b, *s_part, *partials, *stats, *p, *ds, *dbc_part, *du;
   float *slab_w1, *slab_wab, *cs_b1, *cs_bab, *cs_wc;
   float* kpart;                      // partial tiles of a K-split projection (LinearParams::kpart), or null
-  int parts, groups, splits, k_per_split, mstk, tile;
-  int splits_g, k_per_split_g;      // K split of the gate problem (d[Wa;Wb]): more, shorter splits than dW1
+  int parts, groups, mstk;
+  TnPlan tn;                         // the split-K plan of the stack's two problems (its splits size the slabs)
   size_t bytes;
 };
 
 static AmilWs carve(Carver& c, int64_t N, int L, int H, int D, int gated, bool infer = false) {
   AmilWs w{};
   auto take = [&](size_t n) { return c.take<float>(n); };
-  w.parts = gate_parts(D, gated, N);
+  w.parts = gate_parts(D, gated);
   w.groups = pool_groups(N);
   w.mstk = gated ? 2 * D : D;
-  const int td = tn_tile_dim(N, D);
-  const int tiles = ((H + td - 1) / td) * ((L + td - 1) / td) + ((w.mstk + td - 1) / td) * ((H + td - 1) / td);
-  int splits = tn_splits(N, tiles, td);
-  w.tile = td;
-  w.splits = splits;
-  w.k_per_split = k_per_split(N, splits);
-  // A gate tile builds its A operand (dP from a, b, ds) in the staging path and lives ~8 % longer per K row than a
-  // dW1 tile (in-kernel cycle stamps: 710 k vs 659 k with equal splits), so the whole launch waited for the gate tiles.  The
-  // workgroups the uniform split leaves over (256 - 6 x 42 = 4) go to the gate problem: 44 splits of 36 chunks beside
-  // 42 of 38 at N = 50k.  Large-bag tile only, at most 12 % more splits.
-  {
-    static const int env = mmf::tune_int("MMF_TN_GATE_SPLITS", -1);   // tuning override
-    const int t1 = ((H + td - 1) / td) * ((L + td - 1) / td), t2 = tiles - t1;
-    int sg = splits;
-    if (td == 256 && t2 > 0 && splits >= 8) {
-      sg = (256 - t1 * splits) / t2;
-      const int cap = splits + (splits * 12 + 99) / 100;
-      if (sg > cap) sg = cap;
-      if (sg < splits) sg = splits;
-    }
-    if (env > 0) sg = env;
-    w.splits_g = sg; w.k_per_split_g = k_per_split(N, sg);
-  }
+  const TnShape shapes[2] = {{H, L, 0}, {w.mstk, H, 1}};       // dW1 beside the gate problem d[Wa ; Wb]
+  w.tn = plan_tn(N, 0, shapes, 2);
+  const int splits = w.tn.splits;
   w.M_step = take(H);
   w.dM_step = take(H);
   w.h = take((size_t)N * H);
@@ -190,10 +162,10 @@ static AmilWs carve(Carver& c, int64_t N, int L, int H, int D, int gated, bool i
   w.dbc_part = take(PREP_GROUPS);
   w.du = take((size_t)N * H);
   w.slab_w1 = take((size_t)splits * H * L);
-  w.slab_wab = take((size_t)w.splits_g * w.mstk * H);
+  w.slab_wab = take((size_t)w.tn.splits_g * w.mstk * H);
   w.cs_b1 = take((size_t)splits * H);
-  w.cs_bab = take((size_t)w.splits_g * w.mstk);
-  w.cs_wc = take((size_t)w.splits_g * D);
+  w.cs_bab = take((size_t)w.tn.splits_g * w.mstk);
+  w.cs_wc = take((size_t)w.tn.splits_g * D);
   w.bytes = c.off;
   return w;
 }
@@ -322,20 +294,21 @@ static NnParams stack_dx(const mmf_amil_desc* d, const AmilWs& w, float* dx) {
   return np;
 }
 
-// the stack's two problems, appended to the tp.nprob already there: dW1[H x L] = du^T . x ; db1 = colsum(du), and the
-// gate problem over h with its own (more, shorter) splits
-static void stack_tn(const mmf_amil_desc* d, const AmilWs& w, const float* x, const GateBwdCtx& gc, TnParams& tp) {
-  const int n = tp.nprob;
-  tp.nprob = n + 2; tp.K = d->N; tp.splits = w.splits; tp.k_per_split = w.k_per_split; tp.g = gc; tp.tile = w.tile;
+// the stack's two problems: dW1[H x L] = du^T . x ; db1 = colsum(du), and the gate problem over h, which takes the plan's
+// own (more, shorter) splits.  Returns the carving's plan; the bf16x3 mode, which the carving does not know, changes its
+// tile's kind alone (a function of K and the mode), never the splits the slabs are sized by.
+static TnPlan stack_tn(const mmf_amil_desc* d, const AmilWs& w, const float* x, const GateBwdCtx& gc, TnParams& tp) {
+  tp.nprob = 2; tp.K = d->N; tp.g = gc;
   tp.split = d->gemm == MMF_GEMM_BF16X3;
-  TnProblem& q1 = tp.prob[n];
+  TnProblem& q1 = tp.prob[0];
   q1.kind = TN_A_PLAIN; q1.A = w.du; q1.lda = d->H; q1.M = d->H;
   q1.B = x; q1.ldb = d->L; q1.Ncols = d->L;
   q1.out = w.slab_w1; q1.split_stride = (size_t)d->H * d->L; q1.ldc = d->L;
   q1.colsum = w.cs_b1; q1.colsum_stride = d->H; q1.colsum2 = nullptr; q1.colsum2_stride = 0;
-  TnProblem& q2 = tp.prob[n + 1];
-  q2 = tn_gate_problem(d, w.h, w.slab_wab, w.cs_bab, w.cs_wc);
-  q2.splits = w.splits_g; q2.k_per_split = w.k_per_split_g;
+  tp.prob[1] = tn_gate_problem(d, w.h, w.slab_wab, w.cs_bab, w.cs_wc);
+  TnPlan pl = w.tn;
+  if (tp.split) pl.kind = plan_tn(d->N, 1, nullptr, 0).kind;
+  return pl;
 }
 
 // a stack backward's split-K sums, fp32 or bf16 (W: AmilWs / AmilWsBf): dW1 / db1 over `splits` slabs, the gate's over `splits_g`
@@ -352,8 +325,8 @@ static void reduce_slabs(const mmf_amil_desc* d, const W& w, const mmf_amil_grad
 
 // the stack's eight sums (six when ungated): its split-K slabs and the dbc partials of K-prep
 static void stack_reduce(const mmf_amil_desc* d, const AmilWs& w, const mmf_amil_grads* g, int dbc_parts, ReduceList& rl) {
-  reduce_slabs(d, w, g, w.splits, w.splits_g, rl);
-  rl.add(w.cs_wc, g->dWc, d->D, w.splits_g, d->D);
+  reduce_slabs(d, w, g, w.tn.splits, w.tn.splits_g, rl);
+  rl.add(w.cs_wc, g->dWc, d->D, w.tn.splits_g, d->D);
   rl.add(w.dbc_part, g->dbc, 1, dbc_parts, 1);
 }
 
@@ -561,8 +534,8 @@ static int amil_backward_impl(const mmf_amil_desc* d, const float* x, void* work
   }
 
   TnParams tp{};
-  stack_tn(d, w, x, gc, tp);
-  if (int e = launch_tn(tp, st)) return e;
+  const TnPlan tn = stack_tn(d, w, x, gc, tp);
+  if (int e = launch_tn(tn, tp, st)) return e;
 
   ReduceList rl;
   stack_reduce(d, w, g, dbc_groups, rl);
@@ -813,13 +786,12 @@ static GroupWs carve_group(Carver& c, const SegTable& s, int L, int H, int D, in
 
 namespace mmf {
 // reduce_dim's backward on the grouped chain's launches (mmf_radio_nll_step_group): its input gradient du . W1 over every
-// row, its weight-gradient problems in a TN launch of their own after the stack's (or, tuning, in the stack's launch,
-// ahead of the stack's two: they are the long ones).  Its sums are entries on the stack's reduce list.
+// row, its weight-gradient problems in a TN launch of their own after the stack's, planned over their own tiles.  Its
+// sums are entries on the stack's reduce list.
 struct GroupExtra {
   float* dx;                    // [R x L] <- du . W1
   TnProblem prob[4]; int nprob;
-  int separate;                 // 1: the problems as a TN launch of their own; 0 (tuning): in the stack's launch
-  int splits, k_per_split;
+  TnPlan tn;
 };
 
 // the window contract every grouped entry point checks after its own refusals and before the head and check_operands
@@ -901,18 +873,14 @@ static int group_chain_bwd(const mmf_amil_desc* d, const float* x, const GroupWs
   }
 
   TnParams tp{};
-  if (ex && !ex->separate) {
-    for (int i = 0; i < ex->nprob; ++i) tp.prob[i] = ex->prob[i];
-    tp.nprob = ex->nprob;
-  }
-  stack_tn(d, w, x, gc, tp);
+  const TnPlan tn = stack_tn(d, w, x, gc, tp);
   tp.seg_ridx = gw.ridx_d;
-  if (int e = launch_tn(tp, st)) return e;
-  if (ex && ex->separate) {
+  if (int e = launch_tn(tn, tp, st)) return e;
+  if (ex) {
     TnParams tr{};
     for (int i = 0; i < ex->nprob; ++i) tr.prob[i] = ex->prob[i];
-    tr.nprob = ex->nprob; tr.K = d->N; tr.splits = ex->splits; tr.k_per_split = ex->k_per_split; tr.tile = w.tile;
-    if (int e = launch_tn(tr, st)) return e;
+    tr.nprob = ex->nprob; tr.K = d->N;
+    if (int e = launch_tn(ex->tn, tr, st)) return e;
   }
 
   stack_reduce(d, w, g, dbc_parts, rl);
@@ -978,7 +946,7 @@ static int group_half_check(const mmf_amil_desc* d, const mmf_bag_group* group, 
 struct RadioWs {
   GroupWs gw;
   float *xr, *dxr, *slab, *cs, *kpart;
-  int splits, k_per_split, separate;
+  TnPlan tn;                    // dW_r's launch: one problem per modality, planned over their own tiles
   size_t bytes;
 };
 static RadioWs carve_radio(Carver& c, const SegTable& s, int nseg, int kseg, int H, int D, int gated) {
@@ -987,23 +955,15 @@ static RadioWs carve_radio(Carver& c, const SegTable& s, int nseg, int kseg, int
   const int L = kseg;
   r.gw = carve_group(c, s, L, H, D, gated);
   auto take = [&](size_t n) { return c.take<float>(n); };
-  // dW_r as a TN launch of its own after the stack's, planned over its own tiles (mmf_linear_backward's plan), or as
-  // more problems of the stack's launch, planned with the stack's tiles (fewer splits).  Measured: the
-  // separate launch is faster, 1.295 vs 1.366 ms at 16 x 512 rows.  The slabs are sized by the separate plan, which has
-  // at least as many splits.
-  const int td = r.gw.w.tile, mstk = gated ? 2 * D : D;
-  auto cdiv = [](int a, int b) { return (a + b - 1) / b; };
-  const int t_stack = cdiv(H, td) * cdiv(L, td) + cdiv(mstk, td) * cdiv(H, td);
-  const int t_rd = nseg * cdiv(L, td) * cdiv(kseg, td);
-  const int most = tn_splits(R, t_rd, td);
-  static const int env = tune_int("MMF_RADIO_TN_SEPARATE", 1);   // tuning override: 0 = in the stack's TN launch
-  r.separate = env ? 1 : 0;
-  r.splits = r.separate ? most : tn_splits(R, t_stack + t_rd, td);
-  r.k_per_split = k_per_split(R, r.splits);
+  // dW_r as a TN launch of its own after the stack's, planned over its own tiles, not as more problems of the stack's
+  // launch (fewer splits).  Measured: the separate launch is faster, 1.295 vs 1.366 ms at 16 x 512 rows.
+  TnShape shapes[4];
+  for (int m = 0; m < nseg; ++m) shapes[m] = {L, kseg, 0};
+  r.tn = plan_tn(R, 0, shapes, nseg);
   r.xr = take((size_t)R * L);
   r.dxr = take((size_t)R * L);
-  r.slab = take((size_t)most * L * nseg * kseg);
-  r.cs = take((size_t)most * L);
+  r.slab = take((size_t)r.tn.splits * L * nseg * kseg);
+  r.cs = take((size_t)r.tn.splits * L);
   const size_t kf = linear_ksplit_floats(R, L, nseg * kseg, nseg, kseg);
   r.kpart = kf ? take(kf) : nullptr;
   r.bytes = c.off;
@@ -1046,7 +1006,7 @@ static GroupExtra radio_extra(const mmf_amil_desc* d, const mmf_radio_reduce* rd
   const int nseg = rd->nseg, kseg = rd->kseg, L = d->L;
   GroupExtra ex{};
   ex.dx = r.dxr;
-  ex.separate = r.separate; ex.splits = r.splits; ex.k_per_split = r.k_per_split;
+  ex.tn = r.tn;
   ex.nprob = nseg;
   for (int m = 0; m < nseg; ++m) {
     TnProblem& q = ex.prob[m];
@@ -1054,15 +1014,14 @@ static GroupExtra radio_extra(const mmf_amil_desc* d, const mmf_radio_reduce* rd
     q.B = rd->x[m]; q.ldb = kseg; q.Ncols = kseg;
     q.out = r.slab + (size_t)m * kseg; q.split_stride = (size_t)L * nseg * kseg; q.ldc = nseg * kseg;
     q.colsum = m == 0 ? r.cs : nullptr; q.colsum_stride = L;
-    q.splits = r.splits; q.k_per_split = r.k_per_split;
   }
   return ex;
 }
 // reduce_dim's two sums, behind the stack's on the reduce list (gated: the stack's 10 + these 2 = every slot)
 static void radio_reduce(const mmf_amil_desc* d, const mmf_radio_reduce* rd, const RadioWs& r, ReduceList& rl) {
   const int n = d->L * rd->nseg * rd->kseg;
-  rl.add(r.slab, rd->dW, n, r.splits, (size_t)n);
-  rl.add(r.cs, rd->db, d->L, r.splits, (size_t)d->L);
+  rl.add(r.slab, rd->dW, n, r.tn.splits, (size_t)n);
+  rl.add(r.cs, rd->db, d->L, r.tn.splits, (size_t)d->L);
 }
 }  // namespace mmf
 
@@ -1413,7 +1372,7 @@ static IgWs carve_ig(Carver& c, int64_t N, int L, int H, int D, int gated, int s
     g.kpart = kf ? take(kf) : nullptr;
   }
   AmilWs& w = g.w;
-  w.parts = gate_parts(D, gated, R);
+  w.parts = gate_parts(D, gated);
   w.h = take((size_t)R * H);
   w.relu_bits = c.take<unsigned long long>((size_t)((R + 15) / 16 + 2) * (H / 32) * 8);
   w.a = take((size_t)R * D);
@@ -1859,27 +1818,24 @@ int mmf_xfusion_group_backward(const mmf_xfusion_weights* w, const float* x2, in
 namespace mmf {
 struct AttnWs {
   float *a, *b, *s_part, *slab, *cs_bab, *cs_wc;
-  int parts, mstk, splits, k_per_split, tile;
+  int parts, mstk;
+  TnPlan tn;                    // the gate problem alone (exact fp32: the scorer has no bf16x3 mode)
   size_t bytes;
 };
 static AttnWs carve_attn(void* base, int64_t N, int H, int D, int gated) {
   AttnWs w{};
   Carver c(base);
   auto take = [&](size_t n) { return c.take<float>(n); };
-  w.parts = gate_parts(D, gated, N);
+  w.parts = gate_parts(D, gated);
   w.mstk = gated ? 2 * D : D;
-  w.tile = tn_tile_dim(N, D);
-  const int td = w.tile;
-  const int dt = gated ? td / 2 : td;
-  const int tiles = ((D + dt - 1) / dt) * ((H + td - 1) / td);
-  w.splits = tn_splits(N, tiles, td);
-  w.k_per_split = k_per_split(N, w.splits);
+  const TnShape shape = {w.mstk, H, 1};
+  w.tn = plan_tn(N, 0, &shape, 1);
   w.a = take((size_t)N * D);
   w.b = take(gated ? (size_t)N * D : 0);
   w.s_part = take((size_t)w.parts * N);
-  w.slab = take((size_t)w.splits * w.mstk * H);
-  w.cs_bab = take((size_t)w.splits * w.mstk);
-  w.cs_wc = take((size_t)w.splits * D);
+  w.slab = take((size_t)w.tn.splits_g * w.mstk * H);
+  w.cs_bab = take((size_t)w.tn.splits_g * w.mstk);
+  w.cs_wc = take((size_t)w.tn.splits_g * D);
   w.bytes = c.off;
   return w;
 }
@@ -1929,15 +1885,15 @@ int mmf_attn_net_backward(const mmf_amil_desc* d, const float* x, void* workspac
     if (int e = launch_bwd_dh(dh_plan(dp, false), dp, st)) return e;
   }
   TnParams tp{};
-  tp.nprob = 1; tp.K = d->N; tp.splits = w.splits; tp.k_per_split = w.k_per_split; tp.g = gc; tp.tile = w.tile;
+  tp.nprob = 1; tp.K = d->N; tp.g = gc;
   tp.prob[0] = tn_gate_problem(d, x, w.slab, w.cs_bab, w.cs_wc);
-  if (int e = launch_tn(tp, st)) return e;
+  if (int e = launch_tn(w.tn, tp, st)) return e;
   ReduceList rl;
-  rl.add(w.slab, g->dWa, d->D * d->H, w.splits, (size_t)w.mstk * d->H);
-  if (d->gated) rl.add(w.slab + (size_t)d->D * d->H, g->dWb, d->D * d->H, w.splits, (size_t)w.mstk * d->H);
-  rl.add(w.cs_bab, g->dba, d->D, w.splits, w.mstk);
-  if (d->gated) rl.add(w.cs_bab + d->D, g->dbb, d->D, w.splits, w.mstk);
-  rl.add(w.cs_wc, g->dWc, d->D, w.splits, d->D);
+  rl.add(w.slab, g->dWa, d->D * d->H, w.tn.splits_g, (size_t)w.mstk * d->H);
+  if (d->gated) rl.add(w.slab + (size_t)d->D * d->H, g->dWb, d->D * d->H, w.tn.splits_g, (size_t)w.mstk * d->H);
+  rl.add(w.cs_bab, g->dba, d->D, w.tn.splits_g, w.mstk);
+  if (d->gated) rl.add(w.cs_bab + d->D, g->dbb, d->D, w.tn.splits_g, w.mstk);
+  rl.add(w.cs_wc, g->dWc, d->D, w.tn.splits_g, d->D);
   rl.add(gA, g->dbc, 1, (int)d->N, 1);         // d(bc) = sum_i dL/dA_i
   return rl.launch(0, st);
 }
@@ -1971,11 +1927,9 @@ int mmf_linear_forward(const float* const* x_segs, int32_t nseg, int32_t kseg, i
   return launch_linear(lp, static_cast<hipStream_t>(stream));
 }
 
-static int linear_bwd_splits(int64_t M, int N, int K) {
-  const int td = tn_tile_dim(M, 0);
-  const int tiles = ((N + td - 1) / td) * ((K + td - 1) / td);
-  return tn_splits(M, tiles, td);
-}
+// dW[N x K] as one problem over all K columns: the workspace query has no segments, so the splits are planned over
+// ceil(K / tile) column tiles even where the launch's nseg problems of kseg columns round up to more
+static TnPlan linear_bwd_plan(int64_t M, int N, int K) { const TnShape shape = {N, K, 0}; return plan_tn(M, 0, &shape, 1); }
 
 // mmf_linear_backward's split-K slabs: dW's, then db's
 struct LinearBwdWs { float *slab, *cs; size_t bytes; };
@@ -1989,7 +1943,7 @@ static LinearBwdWs carve_linear_bwd(void* base, int splits, int N, int K) {
 }
 
 size_t mmf_linear_backward_workspace_bytes(int64_t M, int32_t N, int32_t K) {
-  const int s = linear_bwd_splits(M, N, K);
+  const int s = linear_bwd_plan(M, N, K).splits;
   if (s == 1) return 256;
   return carve_linear_bwd(nullptr, s, N, K).bytes;
 }
@@ -2004,15 +1958,15 @@ int mmf_linear_backward(const float* dy, const float* const* x_segs, int32_t nse
   if (dx && N % KC != 0) return MMF_ERR_SHAPE;           // dx = dy . W contracts over N in 32-chunks (launch_nn); every refusal comes before the first launch
   if (M * (int64_t)(N > kseg ? N : kseg) * 4 >= (int64_t)1 << 31 || (int64_t)N * K * 4 >= (int64_t)1 << 31) return MMF_ERR_SHAPE;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const int splits = linear_bwd_splits(M, N, K);
+  const TnPlan tn = linear_bwd_plan(M, N, K);
+  const int splits = tn.splits;
   if (splits > 1 && (!workspace || workspace_bytes < mmf_linear_backward_workspace_bytes(M, N, K))) return MMF_ERR_WORKSPACE;
   const LinearBwdWs lw = carve_linear_bwd(workspace, splits, N, K);
   float* slab = splits > 1 ? lw.slab : dW;
   float* cs = splits > 1 ? lw.cs : db;
 
   TnParams tp{};
-  tp.nprob = nseg; tp.K = M; tp.splits = splits; tp.tile = tn_tile_dim(M, 0);
-  tp.k_per_split = k_per_split(M, splits);
+  tp.nprob = nseg; tp.K = M;
   for (int i = 0; i < nseg; ++i) {
     if (!x_segs[i]) return MMF_ERR_ARG;
     TnProblem& q = tp.prob[i];
@@ -2021,7 +1975,7 @@ int mmf_linear_backward(const float* dy, const float* const* x_segs, int32_t nse
     q.out = slab + (size_t)i * kseg; q.split_stride = (size_t)N * K; q.ldc = K;
     q.colsum = (i == 0 && db) ? cs : nullptr; q.colsum_stride = N;
   }
-  if (int e = launch_tn(tp, st)) return e;
+  if (int e = launch_tn(tn, tp, st)) return e;
   if (splits > 1) {
     ReduceList rl;
     rl.add(slab, dW, N * K, splits, (size_t)N * K);

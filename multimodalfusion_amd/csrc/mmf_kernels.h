@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 
 #include "mmf_common.h"
 
@@ -37,7 +38,7 @@ struct LinearParams {      // y[M x N] = drop(act(concat_k(x_s)[M x K] . W[N x K
   // each contracts 1 / ksplit of K and writes its partial tile to kpart[(tile * ksplit + s)][BM x BN] with device-scope
   // stores; the LAST to arrive (ktick[tile]: a device-scope counter, zero before the launch and left zero by it) sums the
   // partials in split order -- deterministic -- and runs the epilogue.  No workgroup ever waits for another.
-  // launch_linear sets ksplit from linear_ksplit() when kpart / ktick are given; 1 otherwise.
+  // launch_linear sets ksplit from the plan (LinearPlan::ksplit: above 1 only when kpart / ktick are given).
   int ksplit;
   float* kpart;
   unsigned* ktick;
@@ -46,9 +47,20 @@ struct LinearParams {      // y[M x N] = drop(act(concat_k(x_s)[M x K] . W[N x K
   // row's bag (group_rows_kernel).  Read only by the SEG instantiations; null otherwise.
   const uint32_t* seg_ridx;
 };
-// K split launch_linear will use for this shape when it is given partial-tile space and tick words; 1 = none
-int linear_ksplit(int64_t M, int N, int K, int nseg, int kseg);
-size_t linear_ksplit_floats(int64_t M, int N, int K, int nseg, int kseg);   // size of LinearParams::kpart (0: no split)
+// The projection's launch plan: every choice between linear_nt_kernel's launch forms, made once.
+enum : int { LIN_SPLIT_WIDE, LIN_WIDE, LIN_128, LIN_SPLIT_64, LIN_KSPLIT_64, LIN_64 };
+struct LinearPlan {
+  int kind;                // LIN_*: split-operand 224 x 256 and 64 x 64; exact fp32 rows x 256, 128 x 128, 64 x 64 K-split, 64 x 64
+  int rows;                // the tile's height: 64 .. 240 in steps of 16 for LIN_WIDE (odd multiples end in a half block)
+  int ksplit;              // LinearParams::ksplit: 2 or 4 for LIN_KSPLIT_64, else 1
+  int deep;                // short grid of 64-row tiles: the deep-prefetch main loop
+  int mt_count, nt_count, grid;
+  int kpart_floats;        // floats of LinearParams::kpart the launch writes (0: no K split)
+};
+// tick_words: the tick words on offer with partial-tile space (0: none, so no K split)
+LinearPlan plan_linear(int64_t M, int N, int K, int nseg, int kseg, int allow_half, int concurrent, int split, int tick_words);
+// size of LinearParams::kpart for this shape, whatever the mode and the tick words on offer: the exact-fp32 plan's
+size_t linear_ksplit_floats(int64_t M, int N, int K, int nseg, int kseg);
 
 struct GateFwdParams {
   const float* h;          // [N x H] (post ReLU/dropout)
@@ -208,17 +220,17 @@ struct TnProblem {         // C[M x Ncols] (+)= A^T . B over a slice of the K (i
   float* colsum2; size_t colsum2_stride;     // TN_A_GATE only: dWc partials, length D
   int tiles_m, tiles_n, block_begin;       // block_begin: first workgroup of the problem in the plain block order
   int tile_begin;                          // first tile index of the problem (over all problems, set by launch_tn)
-  int splits, k_per_split;                 // this problem's K split (0 = TnParams::splits / k_per_split)
+  int splits, k_per_split;                 // this problem's K split (set by launch_tn: the plan's, a gate problem its own)
 };
 
 struct TnParams {
   TnProblem prob[6];
   int nprob;
   int64_t K;               // number of instances (rows of A and B)
-  int splits, k_per_split; // k_per_split is a multiple of KC
+  int splits, k_per_split; // TnPlan's, set by launch_tn
   int total_tiles;         // tiles over all problems (set by launch_tn)
   int xcd_map;             // 0: plain order (problem, split, tile); 2: block -> (split, tile) through `map`
-  int tile;                // 128 or 256 (set by the caller from tn_tile_dim)
+  int tile;                // 128 or 256 (TnPlan::tile, set by launch_tn)
   int split;               // 1: split-operand 256 x 256 tiles (mmf_gemm_split.h) when tile == 256
   GateBwdCtx g;
   // xcd_map == 2: map[b] = split << 5 | tile (0xFFFF: no work).  Blocks b, b+8, b+16, ... run on the same XCD, and
@@ -251,7 +263,18 @@ struct ReduceParams { ReduceSeg seg[12]; int nseg; int accumulate; };   // accum
 
 int launch_linear(LinearParams p, hipStream_t st);
 int launch_linear_seg(LinearParams p, hipStream_t st);   // grouped step: the dropout epilogue indexes through p.seg_ridx
-int gate_parts(int D, int gated, int64_t N);
+// The gate forward's launch plan: 64-row tiles, uniform 128-row tiles, or both heights in one launch (GateFwdParams::reg).
+enum : int { GATE_64, GATE_128, GATE_MIXED };
+struct GatePlan {
+  int kind;                // GATE_*
+  int split;               // the split-operand tiles (mmf_gemm_split.h) are taken
+  int deep;                // short grid of exact-fp32 64-row tiles: the deep-prefetch main loop
+  int mt_count, nt_count, grid;   // nt_count: gate_parts; mt_count: row tiles (GATE_MIXED: over all regions)
+  int nreg;                // GATE_MIXED: the regions, in workgroup order (GateFwdParams::Region, rows as int)
+  struct Region { int row0, mt_count, grid_begin, tall; } reg[5];
+};
+GatePlan plan_gate_fwd(int64_t N, int H, int D, int gated, int split);
+int gate_parts(int D, int gated);
 int launch_gate_fwd(GateFwdParams p, hipStream_t st);
 int launch_gate_fwd_seg(GateFwdParams p, hipStream_t st);
 int pool_groups(int64_t N);
@@ -285,17 +308,24 @@ int launch_bwd_dh_seg(const DhPlan& pl, BwdDhParams p, hipStream_t st);
 // split-operand mode on bags below the wide tiles: instances from which the small split tiles (64-row GEMM tiles, 128 x 128
 // TN tile) are taken instead of the exact-fp32 ones (default 1: every bag, which keeps an instance's score independent of its bag's size)
 int split_min_rows();
-// the dbc partials of a K-dh that may fuse K-prep, whatever dbc_part holds (allow_half is not read: see DhPlan); 0: it cannot
-int bwd_dh_fused_groups(int64_t N, int H, int allow_half, int D, int gated, int split, int concurrent);
-int launch_tn(TnParams p, hipStream_t st);
+// The split-K plan of the TN GEMM, shared by the workspace carving and the launcher.  256 x 256 tiles (8 waves, one workgroup
+// per CU) from 12,288 instances; `splits` workgroups share a tile, each over k_per_split instances.
+enum : int { TN_128, TN_256, TN_SPLIT_128, TN_SPLIT_256 };
+struct TnShape { int M, Ncols, gate; };     // one problem: C[M x Ncols]; gate: TN_A_GATE (M = 2 D gated, D ungated)
+struct TnPlan {
+  int kind, tile;          // TN_*: exact fp32 128 x 128, 256 x 256; split-operand 128 x 128, 256 x 256; tile: 128 or 256
+  int splits, k_per_split; // k_per_split is a multiple of 4
+  int splits_g, k_per_split_g;   // the gate problems' split: more, shorter splits beside a plain problem on 256 x 256 tiles
+  int tiles;               // tiles over all shapes
+};
+TnPlan plan_tn(int64_t K, int split, const TnShape* shapes, int nshape);
+// sets tile, splits and k_per_split of p and of every problem from the plan
+int launch_tn(const TnPlan& pl, TnParams p, hipStream_t st);
 // wide (32*MB x 256, one 8-wave workgroup per CU) tile selection, shared by the row-parallel GEMMs
 int pick_wide_rows(int64_t M, int ntn, bool allow_half, bool concurrent, int max_rows);
 bool use_wide_tiles(int64_t M, int N, int split = 0);   // split: the bf16x3 mode's (later) crossover
 // a grid this short leaves every workgroup alone on its CU: the deep-prefetch main loops (projection, gate, K-dh)
 bool short_grid(int64_t workgroups);
-// split-K plan shared by the workspace carving and the launcher
-int tn_tile_dim(int64_t K, int D_gate);                    // 256: one 8-wave 256x256 workgroup per CU; else 128
-int tn_splits(int64_t K, int total_tiles, int tile);
 int launch_nn(NnParams p, hipStream_t st);
 int launch_reduce(ReduceParams p, hipStream_t st);
 
@@ -389,6 +419,13 @@ struct ProfScope {
   ProfScope(const char* name, hipStream_t s) : st(s) { prof_begin(name, s); }
   ~ProfScope() { prof_end(st); }
 };
+
+// a wide tile's height (64 .. MAX rows in steps of 16) as a compile-time constant: f(std::integral_constant<int, rows>)
+template <int MAX, int R = 64, class F>
+int with_wide_rows(int rows, F&& f) {
+  if constexpr (R <= MAX) return rows == R ? f(std::integral_constant<int, R>{}) : with_wide_rows<MAX, R + 16>(rows, f);
+  else return MMF_ERR_ARG;
+}
 
 // One launch of a tiled kernel: T::NT threads, T's dynamic LDS and `extra_bytes` behind it
 template <class T, class P>

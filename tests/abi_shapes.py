@@ -122,7 +122,8 @@ def use_big_tiles(M, N):
 
 
 def linear_ksplit(M, N, K, nseg, kseg):
-    """csrc/mmf_amil_fwd.hip linear_ksplit (no tuning overrides): the K split of a short grid of 64 x 64 tiles."""
+    """csrc/mmf_amil_fwd.hip plan_linear's ksplit (exact fp32, tick words on offer; no tuning overrides): the K split of a short
+    grid of 64 x 64 tiles."""
     if M <= 0 or N % 4 != 0 or K % KC != 0 or use_wide_tiles(M, N) or use_big_tiles(M, N):
         return 1
     tiles = ((M + 63) // 64) * ((N + 63) // 64)
@@ -226,13 +227,13 @@ def linear_backward_rule(c):
 
 
 def tn_splits(K, total_tiles, tile):
-    """csrc/mmf_amil_bwd.hip tn_splits (no tuning overrides)."""
+    """csrc/mmf_amil_bwd.hip plan_tn's splits over total_tiles tiles (no tuning overrides)."""
     splits = (256 if tile == 256 else 512) // max(total_tiles, 1)
     return max(1, min(splits, (K + 127) // 128))
 
 
 def linear_bwd_splits(M, N, K):
-    """csrc/mmf_api.hip linear_bwd_splits; 128 x 128 TN tiles below 12,288 rows (tn_tile_dim)."""
+    """csrc/mmf_api.hip linear_bwd_plan; 128 x 128 TN tiles below 12,288 rows (plan_tn)."""
     td = 256 if M >= 12288 else 128
     return tn_splits(M, ((N + td - 1) // td) * ((K + td - 1) // td), td)
 
@@ -1603,10 +1604,10 @@ REQUIRED_MAXSTEP = (
 # (mmf_amil_group_forward / _backward, mmf_radio_group_forward / _backward).  Run by tests/test_gpu_radio_shapes.py on the
 # inputs and float64 references of tests/radio_cases.py.  reduce_dim is a dense layer over nseg segments of kseg columns
 # with N = L = kseg outputs, so the classes are those of a short L: chunks of kseg, the K split of a short grid
-# (linear_ksplit), the splits of the dW_r TN launch over tiles wider than L (tn_splits), and -- for the halves -- where the
+# (plan_linear), the splits of the dW_r TN launch over tiles wider than L (plan_tn), and -- for the halves -- where the
 # stack's H columns sit in the caller's feature matrix.
 SIXTY_FOUR = tuple(1 + (37 * g) % 90 for g in range(64))      # tests/test_gpu_radio_group_step.py SIXTY_FOUR: 64 bags of 1..90 rows
-TN_WIDE_MIN = 12288                                      # csrc/mmf_amil_bwd.hip tn_tile_dim: 256-wide TN tiles from here on
+TN_WIDE_MIN = 12288                                      # csrc/mmf_amil_bwd.hip plan_tn: 256-wide TN tiles from here on
 
 
 def window_class(sizes):
@@ -1671,7 +1672,7 @@ def radio_rule(c, grads=True):
 
 
 def radio_tn_splits(c):
-    """csrc/mmf_api.hip carve_radio `most`: the dW_r problems as a TN launch of their own (MMF_RADIO_TN_SEPARATE unset)."""
+    """csrc/mmf_api.hip carve_radio: the dW_r problems as a TN launch of their own, planned over their own tiles."""
     td = 256 if c.R >= TN_WIDE_MIN else 128
     cdiv = lambda a, b: (a + b - 1) // b
     return tn_splits(c.R, c.nseg * cdiv(c.L, td) * cdiv(c.kseg, td), td)

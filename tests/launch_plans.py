@@ -4,8 +4,8 @@ Above 16,384 rows (8,192 for the `big` head) the fp32 stack's projection and K-d
 picks a tile height per bag size, and each height (and each K-dh variant) is its own compiled kernel.  This module
 
   * binds the library's exported planner functions with ctypes, by their mangled names (`bound()`),
-  * restates them, and the few decisions written inline in the launchers, in Python (vectorised over N where the CPU
-    test sweeps them), each with the function it restates,
+  * restates them in Python (vectorised over N where the CPU test sweeps them), each with the function it restates:
+    the plans of the projection, the gate forward, K-dh and the split-K TN GEMM, and the rules they are built from,
   * `plan(...)`: the set of large-bag kernel instantiations one training step takes, as plan keys,
   * `reachable()`: every plan key any bag size reaches, per configuration,
   * the size tables the GPU tests run (ONE_BAG, GROUPED, RADIO, BF16), each case with the plan it is meant to reach.
@@ -23,6 +23,10 @@ Plan keys (what `plan` returns; only the launches whose tile depends on the bag 
   ("dh", "wide_seg", rows)                     grouped K-dh, bwd_dh_kernel<Tile<rows, 256 ...>, false, -1, true>
   ("tn", 256, mode)                            split-K TN on 256 x 256 tiles, tn_kernel<T, mode>: 0 plain, 1 attention
                                                 dropout, 2 per-bag attention-dropout masks (grouped step)
+  ("tn", 128, mode)                            ... on 128 x 128 tiles (below 12,288 rows): None the run-time switches, 2 as above
+  ("gate", "128")                              gate forward on uniform 128-row tiles
+  ("gate", "mixed", seg_masks)                 gate forward on 128- and 64-row tiles in one launch (gate_fwd_mixed_kernel);
+                                                seg_masks: the grouped step's per-bag attention-dropout masks
   ("linear_bf16", 256), ("gate_bf16", 256)     bf16 storage, unfused route: 256-row tiles (pick_bm)
   ("dh_bf16", gated)                           bf16 storage, unfused route: dh_bf16_kernel<TileB128, gated>
 """
@@ -42,7 +46,7 @@ N_MAX = {"fp32": (2**31 - 1) // (1024 * 4), "bf16": (2**31 - 1) // (1024 * 2)}
 RADIO_R_MAX = {nseg: min(N_MAX["fp32"], (2**31 - 1) // (nseg * 1024 * 4)) for nseg in (2, 3, 4)}
 PREP_GROUPS = 512          # csrc/mmf_kernels.h PREP_GROUPS
 DH_MAX_ROWS = 224          # csrc/mmf_amil_bwd.hip DH_MAX_ROWS
-LINEAR_MAX_ROWS = 240      # csrc/mmf_amil_fwd.hip launch_linear_impl's pick_wide_rows call
+LINEAR_MAX_ROWS = 240      # csrc/mmf_amil_fwd.hip plan_linear's pick_wide_rows call
 CUS, CUS_CONCURRENT = 256, 224      # csrc/mmf_amil_fwd.hip pick_wide_rows
 
 
@@ -55,17 +59,53 @@ class DhPlan(C.Structure):
 
 DH_SPLIT_WIDE, DH_SPLIT_64, DH_WIDE, DH_128, DH_64X128, DH_64 = range(6)      # csrc/mmf_kernels.h DH_*
 
+
+class LinearPlan(C.Structure):
+    """csrc/mmf_kernels.h LinearPlan"""
+    _fields_ = [(f, C.c_int) for f in ("kind", "rows", "ksplit", "deep", "mt_count", "nt_count", "grid", "kpart_floats")]
+
+
+LIN_SPLIT_WIDE, LIN_WIDE, LIN_128, LIN_SPLIT_64, LIN_KSPLIT_64, LIN_64 = range(6)      # csrc/mmf_kernels.h LIN_*
+
+
+class GateRegion(C.Structure):
+    _fields_ = [(f, C.c_int) for f in ("row0", "mt_count", "grid_begin", "tall")]
+
+
+class GatePlan(C.Structure):
+    """csrc/mmf_kernels.h GatePlan"""
+    _fields_ = [(f, C.c_int) for f in ("kind", "split", "deep", "mt_count", "nt_count", "grid", "nreg")] + [("reg", GateRegion * 5)]
+
+
+GATE_64, GATE_128, GATE_MIXED = range(3)      # csrc/mmf_kernels.h GATE_*
+
+
+class TnShape(C.Structure):
+    """csrc/mmf_kernels.h TnShape"""
+    _fields_ = [(f, C.c_int) for f in ("M", "Ncols", "gate")]
+
+
+class TnPlan(C.Structure):
+    """csrc/mmf_kernels.h TnPlan"""
+    _fields_ = [(f, C.c_int) for f in ("kind", "tile", "splits", "k_per_split", "splits_g", "k_per_split_g", "tiles")]
+
+
+TN_128, TN_256, TN_SPLIT_128, TN_SPLIT_256 = range(4)      # csrc/mmf_kernels.h TN_*
+KC, SKC = 32, 16       # csrc/mmf_gemm_core.h KC, csrc/mmf_gemm_split.h SKC: k-values per staged chunk
+
 SYMBOLS = {
     # name: (mangled, restype, argtypes) -- the C++ signatures of csrc/mmf_kernels.h and csrc/mmf_bf16.h
     "pick_wide_rows": ("_ZN3mmf14pick_wide_rowsElibbi", C.c_int, [C.c_int64, C.c_int, C.c_bool, C.c_bool, C.c_int]),
     "use_wide_tiles": ("_ZN3mmf14use_wide_tilesElii", C.c_bool, [C.c_int64, C.c_int, C.c_int]),
-    "bwd_dh_fused_groups": ("_ZN3mmf19bwd_dh_fused_groupsEliiiiii", C.c_int,
-                            [C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     # (N, H, D, gated, dropout, split, concurrent, can_fuse, dbc_cap)
     "plan_bwd_dh": ("_ZN3mmf11plan_bwd_dhEliiiiiiii", DhPlan, [C.c_int64] + [C.c_int] * 8),
-    "tn_tile_dim": ("_ZN3mmf11tn_tile_dimEli", C.c_int, [C.c_int64, C.c_int]),
-    "tn_splits": ("_ZN3mmf9tn_splitsElii", C.c_int, [C.c_int64, C.c_int, C.c_int]),
-    "linear_ksplit": ("_ZN3mmf13linear_ksplitEliiii", C.c_int, [C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int]),
+    # (M, N, K, nseg, kseg, allow_half, concurrent, split, tick_words)
+    "plan_linear": ("_ZN3mmf11plan_linearEliiiiiiii", LinearPlan, [C.c_int64] + [C.c_int] * 8),
+    # (N, H, D, gated, split)
+    "plan_gate_fwd": ("_ZN3mmf13plan_gate_fwdEliiii", GatePlan, [C.c_int64] + [C.c_int] * 4),
+    "gate_parts": ("_ZN3mmf10gate_partsEii", C.c_int, [C.c_int, C.c_int]),
+    # (K, split, shapes, nshape): lib_plan_tn() below builds the array
+    "plan_tn": ("_ZN3mmf7plan_tnEliPKNS_7TnShapeEi", TnPlan, [C.c_int64, C.c_int, C.POINTER(TnShape), C.c_int]),
     "fused_fwd2_ok": ("_ZN3mmf13fused_fwd2_okEliii", C.c_bool, [C.c_int64, C.c_int, C.c_int, C.c_int]),
     "dh2_bf16_ok": ("_ZN3mmf11dh2_bf16_okEliii", C.c_bool, [C.c_int64, C.c_int, C.c_int, C.c_int]),
 }
@@ -96,6 +136,12 @@ def bound():
             out[name] = f
         _bound = out
     return _bound
+
+
+def lib_plan_tn(K, split, shapes):
+    """The library's plan_tn for a list of (M, Ncols, gate) problem shapes."""
+    arr = (TnShape * len(shapes))(*[TnShape(*sh) for sh in shapes])
+    return bound()["plan_tn"](int(K), int(split), arr, len(shapes))
 
 
 # ---- the Python restatement ---------------------------------------------------------------------------------------
@@ -130,8 +176,8 @@ def dh_short_grid(N, H):
 
 
 def bwd_dh_fused_groups(N, H, concurrent):
-    """csrc/mmf_amil_bwd.hip bwd_dh_fused_groups with split 0 (the fp32 stack: amil_backward_impl, csrc/mmf_api.hip):
-    > 0: the number of K-prep tiles when K-dh does K-prep itself; 0: it does not."""
+    """plan_bwd_dh's dbc_groups with split 0 (the fp32 stack: amil_backward_impl, csrc/mmf_api.hip) for a caller that can fuse
+    and a dbc_part of any size: > 0: the number of K-prep tiles when K-dh does K-prep itself; 0: it does not."""
     N = np.asarray(N, np.int64)
     rows = pick_wide_rows(N, H // 256, True, concurrent, DH_MAX_ROWS)
     wide = use_wide_tiles(N, H)
@@ -176,8 +222,35 @@ def dh_plan(N, H, D, gated, p_att, concurrent, can_fuse):
 
 
 def tn_tile_dim(K):
-    """csrc/mmf_amil_bwd.hip tn_tile_dim: 256 x 256 TN tiles from 12,288 rows."""
+    """csrc/mmf_amil_bwd.hip plan_tn's tile: 256 x 256 TN tiles from 12,288 rows."""
     return np.where(np.asarray(K, np.int64) >= 12288, 256, 128)
+
+
+def tn_plan(K, split, shapes):
+    """csrc/mmf_amil_bwd.hip plan_tn (no tuning overrides) for an array K: the TnPlan fields.  shapes: (M, Ncols, gate) per
+    problem; a gate problem's M is 2 D (gated) or D."""
+    K = np.asarray(K, np.int64)
+    tile = tn_tile_dim(K)
+    kind = np.where(tile == 256, TN_SPLIT_256 if split else TN_256, TN_SPLIT_128 if split else TN_128)
+    count = lambda want: sum((((M + tile - 1) // tile) * ((Nc + tile - 1) // tile) for M, Nc, g in shapes if bool(g) == want),
+                             np.zeros(K.shape, np.int64))
+    t_plain, t_gate = count(False), count(True)
+    tiles = t_plain + t_gate
+    splits = np.maximum(1, np.minimum(np.where(tile == 256, 256, 512) // np.maximum(tiles, 1), (K + 127) // 128))
+    kps = lambda sp: ((K + sp - 1) // sp + 3) // 4 * 4
+    splits_g = splits
+    if any(g for _, _, g in shapes) and not all(g for _, _, g in shapes):
+        # the workgroups the uniform split leaves over go to the gate problem, at most 12 % more splits
+        left = (256 - t_plain * splits) // t_gate
+        cap = splits + (splits * 12 + 99) // 100
+        splits_g = np.where((tile == 256) & (splits >= 8), np.minimum(np.maximum(left, splits), cap), splits)
+    return {"kind": kind, "tile": tile, "splits": splits, "k_per_split": kps(splits), "splits_g": splits_g,
+            "k_per_split_g": kps(splits_g), "tiles": tiles}
+
+
+def stack_tn_shapes(L, H, D, gated):
+    """csrc/mmf_api.hip stack_tn_plan: dW1 [H x L] beside the gate problem d[Wa ; Wb] [2 D (gated) or D x H]"""
+    return [(H, L, 0), (2 * D if gated else D, H, 1)]
 
 
 def use_big_tiles(M, N):
@@ -186,7 +259,42 @@ def use_big_tiles(M, N):
     return (np.asarray(M, np.int64) // 128) * ((N + 127) // 128) >= 256
 
 
-GATE_BIG_MIN = 400     # csrc/mmf_amil_fwd.hip launch_gate_fwd_impl: the fp32 gate's 128-row tiles from 400 of them
+def grid_for_tiles(mt, nt):
+    """csrc/mmf_gemm_core.h grid_for_tiles: row tiles in groups of 8 per column tile"""
+    return ((mt + 7) // 8) * 8 * nt
+
+
+def short_grid(workgroups):
+    """csrc/mmf_amil_fwd.hip short_grid (no tuning overrides)"""
+    return workgroups <= 1024
+
+
+def linear_plan(M, N, K, nseg, kseg, allow_half, concurrent, split, tick_words):
+    """csrc/mmf_amil_fwd.hip plan_linear (no tuning overrides) for an array M: the LinearPlan fields."""
+    M = np.asarray(M, np.int64)
+    can_split = bool(split) and K % (4 * SKC) == 0 and nseg == 1
+    split_wide = use_wide_tiles(M, N, 1) & can_split
+    wide = ~split_wide & use_wide_tiles(M, N, int(can_split))
+    small = ~split_wide & ~wide
+    big = small & use_big_tiles(M, N) & (not can_split)
+    kind = np.select([split_wide, wide, big, small & can_split], [LIN_SPLIT_WIDE, LIN_WIDE, LIN_128, LIN_SPLIT_64], LIN_64)
+    rows = np.select([split_wide, wide, big], [224, pick_wide_rows(M, N // 256, allow_half, concurrent, LINEAR_MAX_ROWS), 128], 64)
+    bn = np.where(split_wide | wide, 256, rows)
+    mt, nt = (M + rows - 1) // rows, (N + bn - 1) // bn
+    tiles, nk = mt * nt, K // KC
+    seg_ok = nseg == 1 or kseg % (4 * KC) == 0
+    ksplit = np.ones(M.shape, np.int64)
+    if N % 4 == 0 and K % KC == 0 and seg_ok:
+        for S in (2, 4):        # the larger split where both fit
+            if nk % (4 * S) == 0 and nk // S >= 8:
+                ksplit = np.where((kind == LIN_64) & (tiles <= min(tick_words, 128)) & (tiles * S <= 512), S, ksplit)
+    kind = np.where(ksplit > 1, LIN_KSPLIT_64, kind)
+    deep = np.where(ksplit > 1, short_grid(tiles * ksplit), (kind == LIN_64) & short_grid(tiles) & (nk % 4 == 0) & seg_ok)
+    return {"kind": kind, "rows": rows, "mt_count": mt, "nt_count": nt, "ksplit": ksplit, "deep": deep.astype(np.int64),
+            "grid": grid_for_tiles(mt, nt * ksplit), "kpart_floats": np.where(ksplit > 1, ksplit * tiles * 64 * 64, 0)}
+
+
+GATE_BIG_MIN = 400     # csrc/mmf_amil_fwd.hip plan_gate_fwd: the fp32 gate's 128-row tiles from 400 of them
 
 
 def gate_parts(D, gated):
@@ -196,6 +304,50 @@ def gate_parts(D, gated):
 
 def gate_big_tiles(N, D, gated):
     return (np.asarray(N, np.int64) // 128) * gate_parts(D, gated) >= GATE_BIG_MIN
+
+
+def gate_kind(N, D, gated):
+    """plan_gate_fwd's kind (the same in both operand modes), for an array N"""
+    N = np.asarray(N, np.int64)
+    nt = gate_parts(D, gated)
+    mixed = (((N + 127) // 128) * nt // 512 >= 2) & (512 % (2 * nt) == 0)      # two whole rounds of tall tiles
+    big = gate_big_tiles(N, D, gated)
+    return np.where(big & mixed, GATE_MIXED, np.where(big, GATE_128, GATE_64))
+
+
+def gate_plan(N, H, D, gated, split):
+    """csrc/mmf_amil_fwd.hip plan_gate_fwd (no tuning overrides) for an array N: the GatePlan fields, `reg` as an
+    [len(N), 5, 4] array of (row0, mt_count, grid_begin, tall), zero past nreg."""
+    N = np.asarray(N, np.int64)
+    nt = gate_parts(D, gated)
+    split_k = bool(split) and H % (4 * SKC) == 0
+    kind = gate_kind(N, D, gated)
+    big, mixed = kind != GATE_64, kind == GATE_MIXED
+    mt128 = (N + 127) // 128
+    total = mt128 * nt
+    R = total // 512          # whole rounds of 512 tall tiles (two workgroups per CU)
+    half_m = 256 // nt
+    if split_k:               # one tall region over the whole rounds, then short tiles
+        lens = [(1, (total - total % 512) // nt)]
+    else:                     # the dephased launch: tall, short, tall, short, then short tiles
+        lens = [(1, half_m + 0 * R), (0, half_m + 0 * R), (1, half_m * (2 * R - 2)), (0, half_m + 0 * R)]
+    reg = np.zeros(N.shape + (5, 4), np.int64)
+    row = np.zeros(N.shape, np.int64)
+    grid = np.zeros(N.shape, np.int64)
+    for i, (tall, m) in enumerate(lens):
+        reg[:, i] = np.stack([row, m, grid, np.full(N.shape, tall)], 1)
+        grid = grid + grid_for_tiles(m, nt)
+        row = row + m * (128 if tall else 64)
+    last = (N - row + 63) // 64
+    reg[:, len(lens)] = np.where((last > 0)[:, None], np.stack([row, last, grid, np.zeros(N.shape, np.int64)], 1), 0)
+    nreg = len(lens) + (last > 0)
+    grid = grid + np.where(last > 0, grid_for_tiles(last, nt), 0)
+    reg = np.where(mixed[:, None, None], reg, 0)
+    mt = np.where(mixed, reg[:, :, 1].sum(1), np.where(big, mt128, (N + 63) // 64))
+    deep = (kind == GATE_64) & (not split_k) & short_grid(mt * nt) & ((H // KC) % 4 == 0)
+    return {"kind": kind, "split": np.full(N.shape, int(split_k)), "nt_count": np.full(N.shape, nt), "mt_count": mt,
+            "deep": deep.astype(np.int64), "grid": np.where(mixed, grid, grid_for_tiles(mt, nt)),
+            "nreg": np.where(mixed, nreg, 0), "reg": reg}
 
 
 def pick_bm(rows, ntn):
@@ -260,6 +412,9 @@ def plan(N, head="small", gated=True, attn_dropout=False, train=False, concurren
             keys.add(("dh", "wide_seg", pick_wide_rows(N, ntn, False, concurrent, DH_MAX_ROWS)))
         if tn_tile_dim(N) == 256:
             keys.add(("tn", 256, 2 if p_att else 0))        # launch_tn_grid (csrc/mmf_amil_bwd.hip)
+        else:
+            keys.add(("tn", 128, 2 if p_att else None))
+        keys |= gate_keys(N, D, gated, bool(p_att))
         return frozenset(keys)
 
     fused = bool(dh_fused(N, H, concurrent))
@@ -274,7 +429,16 @@ def plan(N, head="small", gated=True, attn_dropout=False, train=False, concurren
         keys.add(("dh", "64x128"))
     if tn_tile_dim(N) == 256:
         keys.add(("tn", 256, 1 if p_att else 0))
+    else:
+        keys.add(("tn", 128, None))
+    keys |= gate_keys(N, D, gated, False)
     return frozenset(keys)
+
+
+def gate_keys(N, D, gated, seg_masks):
+    """The gate forward's plan keys; seg_masks: the grouped step with attention dropout (launch_gate_fwd_seg)"""
+    kind = int(gate_kind(N, D, gated))
+    return {GATE_64: set(), GATE_128: {("gate", "128")}, GATE_MIXED: {("gate", "mixed", seg_masks)}}[kind]
 
 
 def cover_keys(keys):
@@ -346,7 +510,7 @@ def _signature(cfg, N):
     ntn, conc = H // 256, cfg.concurrent
     if cfg.dtype == "bf16":
         return np.stack([pick_bm(N, ntn), pick_bm(N, gate_parts_bf16(D, cfg.gated)), (N + 127) // 128 <= 4096], 1)
-    cols = [use_wide_tiles(N, H), tn_tile_dim(N), dh_fused(N, H, conc), N >= 13000,
+    cols = [use_wide_tiles(N, H), tn_tile_dim(N), gate_kind(N, D, cfg.gated), dh_fused(N, H, conc), N >= 13000,
             pick_wide_rows(N, ntn, True, conc, LINEAR_MAX_ROWS), pick_wide_rows(N, ntn, True, conc, DH_MAX_ROWS),
             pick_wide_rows(N, ntn, False, conc, DH_MAX_ROWS)]
     if cfg.radio_nseg:
@@ -360,7 +524,7 @@ _reps = {}
 def _representatives(cfg):
     """One N per distinct signature over [1, limit], the smallest; cached per the columns' inputs."""
     key = (cfg.head if not cfg.radio_nseg else "radio", cfg.concurrent, cfg.dtype, cfg.radio_nseg,
-           cfg.gated if cfg.dtype == "bf16" else None)
+           cfg.gated)
     if key not in _reps:
         N = np.arange(1, cfg.limit() + 1, dtype=np.int64)
         _, first = np.unique(_signature(cfg, N), axis=0, return_index=True)
@@ -427,6 +591,10 @@ GROUPED = [
     ([12000, 1, 12577], "small", True, 8, False, False, "24,578 rows, eval: 112 / 128"),
     ([9935, 1, 6466], "big", False, 4, True, True, "16,402 rows: 144 (masks, a bag edge in the half block) / 160"),
     ([8064, 8193, 1, 10442], "big", True, 8, True, True, "26,700 rows: 224 (masks) / 224, a bag edge on a tile edge"),
+    ([5000, 5000, 1, 22700], "small", True, 4, True, True,
+     "32,701 rows: the gate's tall and short tiles in one launch with per-bag masks, a bag edge inside a tall tile (row 5,000) "
+     "and inside a short one (row 10,000); 128 (masks) / 128"),
+    ([300, 1, 200], "small", True, 4, True, True, "501 rows: the 128 x 128 TN tile with per-bag masks (mode 2)"),
 ]
 
 # Grouped radio windows through MIL_Attention_fc_surv_radio.nll_step_group.  (sizes, n_mod, gated, K, train, dropout, plan)

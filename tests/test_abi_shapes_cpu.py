@@ -88,7 +88,9 @@ def test_ksplit_and_tn_split_restatements_match_the_library():
             for nseg, kseg in ((1, 32), (1, 96), (1, 128), (1, 256), (1, 512), (1, 768), (1, 1024), (2, 32), (3, 96), (4, 128),
                                (2, 512), (4, 1024)):
                 S = ab.linear_ksplit(M, N, nseg * kseg, nseg, kseg)
-                assert S == b["linear_ksplit"](M, N, nseg * kseg, nseg, kseg), (M, N, nseg, kseg)
+                # the exact-fp32 plan with tick words for every tile on offer: what the workspace query sizes
+                pl = b["plan_linear"](M, N, nseg * kseg, nseg, kseg, 0, 0, 0, 2**31 - 1)
+                assert S == pl.ksplit and (pl.kind == lp.LIN_KSPLIT_64) == (S > 1), (M, N, nseg, kseg)
                 want = S * ((M + 63) // 64) * ((N + 63) // 64) * 64 * 64 * 4 if S > 1 else 0
                 assert l.mmf_linear_forward_workspace_bytes(M, N, nseg, kseg) == want
     for c in ab.accepted(ab.LINEAR_FORWARD, ab.linear_forward_rule):
@@ -96,9 +98,7 @@ def test_ksplit_and_tn_split_restatements_match_the_library():
             assert ab.linear_ksplit(c.M, c.N, c.K, 1, c.K) == (4 if c.K == 1024 else 2), c
     for M in (1, 3, 5, 64, 65, 129, 1000, 12288):
         for N, K in ((4, 4), (36, 72), (100, 300), (256, 4096), (36, 100)):
-            td = int(b["tn_tile_dim"](M, 0))
-            tiles = ((N + td - 1) // td) * ((K + td - 1) // td)
-            assert ab.linear_bwd_splits(M, N, K) == b["tn_splits"](M, tiles, td), (M, N, K)
+            assert ab.linear_bwd_splits(M, N, K) == lp.lib_plan_tn(M, 0, [(N, K, 0)]).splits, (M, N, K)
             one = ab.linear_bwd_splits(M, N, K) == 1
             assert (l.mmf_linear_backward_workspace_bytes(M, N, K) == 256) == one
     split = [c for c in ab.accepted(ab.LINEAR_BACKWARD, ab.linear_backward_rule) if ab.linear_bwd_splits(c.M, c.N, c.K) > 1]

@@ -10,7 +10,7 @@ canaries, the bands around it intact; the buffers the test hands in carry a cana
 unwritten workspace word summed into a store past a gradient's end cannot pass for an intact band.  Every accepted case
 runs twice, to identical bits.  Refused cases are those the CPU
 file has shown to return before the workspace check; here they get device pointers and must leave every buffer untouched.
-The dW_r problems run as a TN launch of their own; MMF_RADIO_TN_SEPARATE is read once per process and stays unset."""
+The dW_r problems run as a TN launch of their own, the only route there is."""
 import ctypes as C
 
 import numpy as np

@@ -19,7 +19,7 @@ from multimodalfusion_amd import build as B   # noqa: E402
 def kernels(path, sgpr=False):
     out = {}
     for m in re.finditer(r"; -- Begin function (\S+)\n(.*?); -- End function", open(path).read(), re.S):
-        body = re.sub(r"\.Lfunc_end\d+|\.LBB\d+_\d+|\.Ltmp\d+", "L", m.group(2).replace(m.group(1), "FN"))
+        body = re.sub(r"\.Lfunc_end\d+|\.LBB\d+_\d+|\.Ltmp\d+|\.Lpost_getpc\d+", "L", m.group(2).replace(m.group(1), "FN"))
         if sgpr:
             body = re.sub(r"\bs(\d+|\[\d+:\d+\])(?![\w:])", "sX", body)
         lines = [l.split(";")[0].rstrip() for l in body.splitlines()]
