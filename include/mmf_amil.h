@@ -328,7 +328,8 @@ int mmf_radio_infer_group(const mmf_amil_desc* desc, const mmf_bag_group* group,
  *   (which the L-wide bag can set below that limit; the call then returns MMF_ERR_SHAPE) nor the rules for L, H and D, so a
  *   non-zero answer does not say that the call admits the shape.  For a shape the call admits it is never 0: the row cap is
  *   at or below the window's limit.  It does not shrink as window_steps grows.
- * Out of scope: the multimodal heads (the radiology head: mmf_radio_ig); non-zero baselines (they need a second projection,
+ * Out of scope: the multimodal tensor-fusion head (the radiology head: mmf_radio_ig; the multimodal concat head: mmf_mm_ig);
+ *   non-zero baselines (they need a second projection,
  *   U' + alpha (U - U')); bf16 bags; targets other than risk.
  * ------------------------------------------------------------------------------------------- */
 typedef struct mmf_ig_desc {
@@ -384,13 +385,100 @@ int mmf_amil_ig(const mmf_amil_desc* desc, const float* x, void* workspace, size
  * mmf_radio_ig_workspace_bytes: the workspace of that call, or 0 for n_steps outside 1..MMF_GROUP_MAX, window_steps < 0,
  *   N < 1, nseg outside 2..4, kseg < 32, H < 32, N above the row limit of one window (mmf_amil_ig_workspace_bytes) or
  *   N nseg kseg 4 >= 2^31.  It does not shrink as window_steps grows.
- * Out of scope: the multimodal heads (the chain cut at the embedding, the omic network per node); non-zero baselines; bf16
- *   bags; targets other than risk.
+ * Out of scope: the multimodal tensor-fusion head (the concat head -- the chain cut at the embedding, the omic network per
+ *   node -- has mmf_mm_ig); non-zero baselines; bf16 bags; targets other than risk.
  * ------------------------------------------------------------------------------------------- */
 size_t mmf_radio_ig_workspace_bytes(int64_t N, int32_t nseg, int32_t kseg, int32_t H, int32_t D, int32_t gated,
                                     int32_t n_steps, int32_t window_steps);
 int mmf_radio_ig(const mmf_amil_desc* desc, const mmf_radio_reduce* rd, void* workspace, size_t workspace_bytes,
                  const mmf_surv_head* head, const mmf_ig_desc* ig, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Integrated-gradients attribution of the multimodal concat head in one call: how much of a patient's predicted risk comes
+ *   from radiology, pathology and omics.  The reference's attribution script (create_attributions.py:93-164) runs captum's
+ *   IntegratedGradients(n_steps = 20) on risk = -sum(S) from a joint zero baseline over all inputs through the captum
+ *   methods of models/model_mm_attention_mil.py:202-396 and reduces each modality by sum |attr| (radio_attr, path_attr,
+ *   omic_attr): n_steps autograd passes of the whole multimodal step.  captum interpolates all inputs with one alpha, so
+ *   at node alpha, with a zero baseline,
+ *     pathology  u_p = alpha (x_p W1p^T) + b1p                                   (mmf_amil_ig)
+ *     radiology  u_r = alpha U_r + b1',  U_r = (X Wr^T) W1r^T,  b1' = W1r br + b1r  (mmf_radio_ig)
+ *     omic       z1 = alpha Z + b_o0,  Z = W_o0 x_o;  h1 = selu(z1), z2 = W_o1 h1 + b_o1, O = selu(z2)
+ *   and the input gradient is linear in the first pre-activation's gradient in all three: sum_k w_k dx_p,k = (sum_k w_k
+ *   du_p,k) W1p;  sum_k w_k dX_r,k = ((sum_k w_k du_r,k) W1r) Wr;  sum_k w_k dx_o,k = W_o0^T (sum_k w_k dz1_k).  The L-wide
+ *   contractions, reduce_dim, their transposes and W_o0 x_o run ONCE per call, the weight gradients never; only the H-wide
+ *   part of each stack, the omic hidden layers and one head launch run per node.  The chain:
+ *     1. once: U_p (the projection, no bias, no activation); Y = X Wr^T, U_r = Y W1r^T and b1' as mmf_radio_ig's steps 1-3;
+ *        Z = W_o0 x_o, one wave per output (ceil(Gin / 64) + 6 dependent additions);
+ *     2. per window of S nodes -- one S for the whole call: the smaller of what the window rule of mmf_amil_ig gives each
+ *        present stack for window_steps -- for each stack its expansion, per-row tables, gate forward and pooling, whose merge
+ *        writes the node's embedding into the stack's columns of feat [S x F]; the omic forward, one workgroup per node,
+ *        O_s into its columns; the hazard head forward and the backward of risk over feat, giving dfeat [S x F] and the
+ *        risks; for each stack the gather of its columns of dfeat, K-prep, K-dh and the fold into its Gacc; the omic
+ *        backward, one workgroup per node, and the fold Gz += sum_s w_s dz1_s, in node order whatever the windows are;
+ *     3. once: the pathology attribution GEMM (mmf_amil_ig's step 3); the radiology P = Gacc W1r and the segmented
+ *        Q = P Wr (mmf_radio_ig's steps 5-7); attr_o[j] = x_o[j] sum_c Gz[c] W_o0[c, j], one wave per gene in a fixed order.
+ *   No weight-gradient (TN) launch, no reduce list.  A branch that is absent contributes no launch.
+ * mm: which branches are present (at least two) and where each one's embedding stands in the fused row -- path_col,
+ *   radio_col, omic_col, the caller's order (the reference puts omic first when radiology is absent).  F = the sum of the
+ *   present widths (path->H, radio->H, omic_We) <= 1024; the column ranges must tile 0 .. F - 1.  path / path_x: as desc / x
+ *   of mmf_amil_ig, or path = NULL: no pathology branch.  radio / rd: as desc / rd of mmf_radio_ig, or radio = NULL.
+ *   omic_x [Gin], or NULL: no omic branch; omic_W0 [W0 x Gin], omic_b0 [W0], omic_W1 [We x W0], omic_b1 [We]: fc_omic.0.0
+ *   and fc_omic.1.0; Gin >= 1, W0 in 1..1024, We >= 1.  n_steps, alpha, weight, window_steps and the two riders as in
+ *   mmf_ig_desc.  head: Wk [K x F], bk, K in 1..32; the optional outputs receive the values at alpha = 1.
+ * Outputs (device): path_row_sum, path_row_abs [N_p], path_attr [N_p x L] or NULL; radio_row_sum, radio_row_abs
+ *   [nseg x N_r], radio_attr [nseg x N_r x kseg] or NULL; omic_attr [Gin]; risk_x [1], risk_base [1], step_risk [n_steps].
+ *   The outputs of an absent branch are neither read nor written.
+ * Eval mode (dropout in either descriptor is refused), fp32 rows, exact-fp32 GEMMs.  Every sum is taken in a fixed order and
+ *   there are no float atomics: two calls agree bit for bit.  No workgroup waits for another; the call allocates nothing,
+ *   keeps no state and runs on one stream.
+ * Returns, before any launch and in this order:
+ *   MMF_ERR_ARG for a null mm, head, head->Wk or bk; n_steps outside 1..MMF_GROUP_MAX, window_steps < 0, a null alpha,
+ *     weight, risk_x, risk_base or step_risk; fewer than two branches; then per present branch in the order pathology,
+ *     radiology, omic: a null input, row_sum / row_abs (omic: omic_attr, a weight or a bias), p_h or p_att != 0, gemm =
+ *     MMF_GEMM_BF16X3, a null rd, rd->x, rd->W, rd->bias or (nseg in 2..4) rd->x[m];
+ *   MMF_ERR_SHAPE for what mmf_amil_ig / mmf_radio_ig refuse of a stack with it (nseg outside 2..4, the descriptor's rules,
+ *     kseg != radio->L, N_r nseg kseg 4 >= 2^31), Gin < 1, W0 outside 1..1024, We < 1, F > 1024, columns that overlap or
+ *     leave 0 .. F - 1, K outside 1..32, or a bag too long for one step to be a window;
+ *   MMF_ERR_ALIGN for what the single-head calls refuse with it (the omic operands are read element by element: any
+ *     alignment; a null workspace is MMF_ERR_ARG and is found here, as in the single-head calls); MMF_ERR_WORKSPACE.
+ * mmf_mm_ig_workspace_bytes: the workspace of that call; a branch is absent with N_p = 0, N_r = 0 or Gin = 0.  0 for
+ *   n_steps outside 1..MMF_GROUP_MAX, window_steps < 0, fewer than two branches, a negative extent, and for a present branch
+ *   what mmf_amil_ig_workspace_bytes / mmf_radio_ig_workspace_bytes answer 0 for, W0 outside 1..1024, We < 1 or
+ *   F > 1024.  It does not shrink as window_steps grows.
+ * Out of scope: fusion = 'tensor' (it needs an input-gradient-only XlinearFusion tail); radio_fusion = 'tensor'; non-zero
+ *   baselines; bf16 bags; targets other than risk; the stage-2 pretrained models; the omic-only MaxNet.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct mmf_mm_ig_desc {
+  int32_t n_steps;               /* quadrature nodes, 1 .. MMF_GROUP_MAX */
+  int32_t window_steps;          /* nodes per window; 0: the library chooses */
+  const float* alpha;            /* HOST [n_steps] */
+  const float* weight;           /* HOST [n_steps] */
+  const mmf_amil_desc* path;     /* the pathology stack, or NULL: no pathology branch */
+  const float* path_x;           /* [N_p x L] */
+  float* path_row_sum;           /* [N_p] out */
+  float* path_row_abs;           /* [N_p] out */
+  float* path_attr;              /* [N_p x L] out, or NULL */
+  const mmf_amil_desc* radio;    /* the radiology stack, or NULL: no radiology branch */
+  const mmf_radio_reduce* rd;    /* reduce_dim and the modalities, nseg 2..4 */
+  float* radio_row_sum;          /* [nseg x N_r] out */
+  float* radio_row_abs;          /* [nseg x N_r] out */
+  float* radio_attr;             /* [nseg x N_r x kseg] out, or NULL */
+  const float* omic_x;           /* [Gin], or NULL: no omic branch */
+  const float* omic_W0;          /* [W0 x Gin] fc_omic.0.0.weight */
+  const float* omic_b0;          /* [W0] */
+  const float* omic_W1;          /* [We x W0] fc_omic.1.0.weight */
+  const float* omic_b1;          /* [We] */
+  float* omic_attr;              /* [Gin] out */
+  int32_t omic_Gin, omic_W0n, omic_We;
+  int32_t path_col, radio_col, omic_col;   /* first column of each present branch in the fused row */
+  float* risk_x;                 /* [1] out */
+  float* risk_base;              /* [1] out */
+  float* step_risk;              /* [n_steps] out */
+} mmf_mm_ig_desc;
+size_t mmf_mm_ig_workspace_bytes(int64_t N_p, int32_t L_p, int32_t H_p, int32_t D_p, int32_t gated_p, int64_t N_r,
+                                 int32_t nseg, int32_t kseg, int32_t H_r, int32_t D_r, int32_t gated_r, int32_t Gin,
+                                 int32_t W0, int32_t We, int32_t n_steps, int32_t window_steps);
+int mmf_mm_ig(const mmf_mm_ig_desc* mm, void* workspace, size_t workspace_bytes, const mmf_surv_head* head, void* stream);
 
 /* The hazard head's training step on a feature vector that is already on the device: what
  *   `hazards, S, Y_hat = head(classifier(feat)); loss = NLLSurvLoss(alpha)(hazards, S, Y, c); (loss * loss_scale).backward()`

@@ -69,6 +69,22 @@ class RadioReduce(C.Structure):
                 ("bias", c_f32p), ("dW", c_f32p), ("db", c_f32p)]
 
 
+class MmIgDesc(C.Structure):
+    """struct mmf_mm_ig_desc (include/mmf_amil.h): alpha / weight are host arrays, path / radio / rd point at host structs
+    (NULL: the branch is absent; omic: omic_x NULL), everything else is a device pointer."""
+    _fields_ = [("n_steps", C.c_int32), ("window_steps", C.c_int32), ("alpha", C.POINTER(C.c_float)),
+                ("weight", C.POINTER(C.c_float)),
+                ("path", C.POINTER(AmilDesc)), ("path_x", C.c_void_p), ("path_row_sum", C.c_void_p),
+                ("path_row_abs", C.c_void_p), ("path_attr", C.c_void_p),
+                ("radio", C.POINTER(AmilDesc)), ("rd", C.POINTER(RadioReduce)), ("radio_row_sum", C.c_void_p),
+                ("radio_row_abs", C.c_void_p), ("radio_attr", C.c_void_p),
+                ("omic_x", C.c_void_p), ("omic_W0", C.c_void_p), ("omic_b0", C.c_void_p), ("omic_W1", C.c_void_p),
+                ("omic_b1", C.c_void_p), ("omic_attr", C.c_void_p),
+                ("omic_Gin", C.c_int32), ("omic_W0n", C.c_int32), ("omic_We", C.c_int32),
+                ("path_col", C.c_int32), ("radio_col", C.c_int32), ("omic_col", C.c_int32),
+                ("risk_x", C.c_void_p), ("risk_base", C.c_void_p), ("step_risk", C.c_void_p)]
+
+
 class MaxnetDesc(C.Structure):
     """struct mmf_maxnet_desc (include/mmf_amil.h)."""
     _fields_ = [("B", C.c_int32), ("G", C.c_int32), ("H0", C.c_int32), ("H1", C.c_int32),
@@ -168,6 +184,8 @@ SYMBOLS = {
                                                    C.c_int32, C.c_int32]),
     "mmf_radio_ig": (C.c_int, [C.POINTER(AmilDesc), C.POINTER(RadioReduce), C.c_void_p, C.c_size_t, C.POINTER(SurvHead),
                                C.POINTER(IgDesc), C.c_void_p]),
+    "mmf_mm_ig_workspace_bytes": (C.c_size_t, [C.c_int64] + [C.c_int32] * 4 + [C.c_int64] + [C.c_int32] * 10),
+    "mmf_mm_ig": (C.c_int, [C.POINTER(MmIgDesc), C.c_void_p, C.c_size_t, C.POINTER(SurvHead), C.c_void_p]),
     "mmf_radio_group_infer_workspace_bytes": (C.c_size_t, [C.POINTER(C.c_int64), C.c_int32, C.c_int32, C.c_int32,
                                                             C.c_int32, C.c_int32, C.c_int32]),
     "mmf_radio_infer_group": (C.c_int, [C.POINTER(AmilDesc), C.POINTER(BagGroup), C.POINTER(RadioReduce), C.c_void_p,

@@ -1444,4 +1444,148 @@ int launch_ig_head(const IgHeadParams& p, int S, hipStream_t st) {
   return hipGetLastError() == hipSuccess ? MMF_OK : MMF_ERR_LAUNCH;
 }
 
+// ---- the omic branch of the multimodal head's integrated gradients (mmf_mm_ig) ----------------------------------------
+// The two SNN blocks of models/model_mm_attention_mil.py:44-47 in eval mode, O = selu(W1 selu(W0 x + b0) + b1).  With a zero
+// baseline the first pre-activation is linear in the node, z1 = alpha Z + b0 with Z = W0 x formed once, and the input
+// gradient is linear in dz1: sum_k w_k dx_k = W0^T (sum_k w_k dz1_k).  Per node only the two hidden layers run.
+constexpr float IG_SELU_ALPHA = 1.6732632423543772f;
+constexpr float IG_SELU_SCALE = 1.0507009873554805f;
+__device__ inline float ig_selu(float z) { return IG_SELU_SCALE * (z > 0.f ? z : IG_SELU_ALPHA * (expf(z) - 1.0f)); }
+__device__ inline float ig_selu_grad(float z) { return z > 0.f ? IG_SELU_SCALE : IG_SELU_SCALE * IG_SELU_ALPHA * expf(z); }
+
+// Z[c] = sum_j W0[c, j] x[j].  One wave per output, four per workgroup: lane t adds its products j = t, t + 64, ... in that
+// order, the xor butterfly adds the lanes -- ceil(Gin / 64) + 6 dependent additions, the same in every call.
+__global__ __launch_bounds__(256) void ig_omic_z_kernel(IgOmicParams p) {
+  const int lane = threadIdx.x & 63, c = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (c >= p.W0n) return;
+  float t = 0.f;
+  for (int j = lane; j < p.Gin; j += 64) t = fmaf(p.W0[(size_t)c * p.Gin + j], p.x[j], t);
+  t = wave_sum(t);
+  if (lane == 0) p.Z[c] = t;
+}
+
+// One workgroup of 16 waves per node s of the window: z1 = alpha_s Z + b0 (kept), h1 = selu(z1) in LDS; then one wave per
+// output of the second layer, as above over the W0n hidden units (ceil(W0n / 64) + 7 additions with the bias): z2 (kept),
+// and O_s = selu(z2) into the omic columns of row s of feat [S x F].  A wave takes four outputs at a time, so that their
+// loads are in flight together: the window has few nodes, and a node's outputs one after the other wait for memory.
+__global__ __launch_bounds__(1024) void ig_omic_fwd_kernel(IgOmicParams p) {
+  __shared__ float h1[1024];
+  const int s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const float a = p.st.alpha[s];
+  for (int c = tid; c < p.W0n; c += 1024) {
+    const float z = fmaf(a, p.Z[c], p.b0[c]);
+    p.z1[(size_t)s * p.W0n + c] = z;
+    h1[c] = ig_selu(z);
+  }
+  __syncthreads();
+  for (int e0 = 4 * wave; e0 < p.We; e0 += 64) {
+    float t[4] = {0.f, 0.f, 0.f, 0.f};
+    const float* w[4];                     // a row past the last output reads the last one again and is not stored: no branch
+#pragma unroll                             // between the loads, so the compiler keeps all of an iteration's in flight
+    for (int i = 0; i < 4; ++i) w[i] = p.W1 + (size_t)(e0 + i < p.We ? e0 + i : p.We - 1) * p.W0n;
+#pragma unroll 4
+    for (int c = lane; c < p.W0n; c += 64) {
+      const float h = h1[c];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) t[i] = fmaf(w[i][c], h, t[i]);
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const float v = wave_sum(t[i]);
+      if (lane == 0 && e0 + i < p.We) {
+        const float z = v + p.b1[e0 + i];
+        p.z2[(size_t)s * p.We + e0 + i] = z;
+        p.feat[(size_t)s * p.F + p.col + e0 + i] = ig_selu(z);
+      }
+    }
+  }
+}
+
+// One workgroup per node: dz2 = dO_s selu'(z2) in LDS; then dz1[c] = selu'(z1[c]) sum_e W1[e, c] dz2[e].  Four groups of 256
+// threads take a quarter of the outputs e each, in order, one thread per hidden unit c (W1 is read along c: coalesced);
+// the four partial sums of a unit are added in group order.
+__global__ __launch_bounds__(1024) void ig_omic_bwd_kernel(IgOmicParams p) {
+  __shared__ float dz2[1024];
+  __shared__ float part[4][1024];
+  const int s = blockIdx.x, tid = threadIdx.x, g = tid >> 8, t256 = tid & 255;
+  for (int e = tid; e < p.We; e += 1024)
+    dz2[e] = p.dfeat[(size_t)s * p.F + p.col + e] * ig_selu_grad(p.z2[(size_t)s * p.We + e]);
+  __syncthreads();
+  const int per = (p.We + 3) / 4, e_beg = g * per, e_end = e_beg + per < p.We ? e_beg + per : p.We;
+  for (int c = t256; c < p.W0n; c += 256) {
+    float t = 0.f;
+#pragma unroll 8
+    for (int e = e_beg; e < e_end; ++e) t = fmaf(p.W1[(size_t)e * p.W0n + c], dz2[e], t);
+    part[g][c] = t;
+  }
+  __syncthreads();
+  for (int c = tid; c < p.W0n; c += 1024) {
+    const float t = ((part[0][c] + part[1][c]) + part[2][c]) + part[3][c];
+    p.dz1[(size_t)s * p.W0n + c] = t * ig_selu_grad(p.z1[(size_t)s * p.W0n + c]);
+  }
+}
+
+// Gz[c] (first: =, else +=) sum_s w_s dz1[s, c] over the first st.S nodes of the window, in node order: ig_fold_kernel's
+// sum for a width that need be no multiple of four
+__global__ __launch_bounds__(256) void ig_omic_fold_kernel(IgOmicParams p) {
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  if (c >= p.W0n) return;
+  float acc = p.first ? 0.f : p.Gz[c];
+  for (int s = 0; s < p.st.S; ++s) acc = fmaf(p.st.w[s], p.dz1[(size_t)s * p.W0n + c], acc);
+  p.Gz[c] = acc;
+}
+
+// attr[j] = x[j] sum_c Gz[c] W0[c, j]: one wave per gene, four per workgroup -- lane t adds its hidden units c = t, t + 64,
+// ... in that order, the butterfly adds the lanes (W0 is 320 KB at most: its columns come from L2)
+__global__ __launch_bounds__(256) void ig_omic_attr_kernel(IgOmicParams p) {
+  const int lane = threadIdx.x & 63, j = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (j >= p.Gin) return;
+  float t = 0.f;
+  for (int c = lane; c < p.W0n; c += 64) t = fmaf(p.Gz[c], p.W0[(size_t)c * p.Gin + j], t);
+  t = wave_sum(t);
+  if (lane == 0) p.attr[j] = p.x[j] * t;
+}
+
+int launch_ig_omic(int stage, const IgOmicParams& p, hipStream_t st) {
+  if (!p.x || !p.W0 || !p.b0 || !p.W1 || !p.b1 || !p.Z || !p.z1 || !p.z2 || !p.dz1 || !p.Gz) return MMF_ERR_ARG;
+  if (p.Gin < 1 || p.W0n < 1 || p.W0n > 1024 || p.We < 1 || p.We > 1024) return MMF_ERR_SHAPE;
+  const int S = p.st.S;
+  const bool per_node = stage == IG_OMIC_FWD || stage == IG_OMIC_BWD;
+  if (per_node && (S < 1 || S > GROUP_MAX || p.col < 0 || p.col + p.We > p.F)) return MMF_ERR_SHAPE;
+  switch (stage) {
+    case IG_OMIC_Z: {
+      ProfScope ps("ig_omic_z_kernel", st);
+      hipLaunchKernelGGL(ig_omic_z_kernel, dim3((unsigned)((p.W0n + 3) / 4)), dim3(256), 0, st, p);
+      break;
+    }
+    case IG_OMIC_FWD: {
+      if (!p.feat) return MMF_ERR_ARG;
+      ProfScope ps("ig_omic_fwd_kernel", st);
+      hipLaunchKernelGGL(ig_omic_fwd_kernel, dim3(S), dim3(1024), 0, st, p);
+      break;
+    }
+    case IG_OMIC_BWD: {
+      if (!p.dfeat) return MMF_ERR_ARG;
+      ProfScope ps("ig_omic_bwd_kernel", st);
+      hipLaunchKernelGGL(ig_omic_bwd_kernel, dim3(S), dim3(1024), 0, st, p);
+      break;
+    }
+    case IG_OMIC_FOLD: {
+      if (S < 0 || S > GROUP_MAX) return MMF_ERR_SHAPE;
+      if (S == 0 && !p.first) return MMF_OK;           // a window of riders: nothing to add (launch_ig_fold)
+      ProfScope ps("ig_omic_fold_kernel", st);
+      hipLaunchKernelGGL(ig_omic_fold_kernel, dim3((unsigned)((p.W0n + 255) / 256)), dim3(256), 0, st, p);
+      break;
+    }
+    case IG_OMIC_ATTR: {
+      if (!p.attr) return MMF_ERR_ARG;
+      ProfScope ps("ig_omic_attr_kernel", st);
+      hipLaunchKernelGGL(ig_omic_attr_kernel, dim3((unsigned)((p.Gin + 3) / 4)), dim3(256), 0, st, p);
+      break;
+    }
+    default: return MMF_ERR_ARG;
+  }
+  return hipGetLastError() == hipSuccess ? MMF_OK : MMF_ERR_LAUNCH;
+}
+
 }  // namespace mmf

@@ -1394,10 +1394,35 @@ static IgWs carve_ig(Carver& c, int64_t N, int L, int H, int D, int gated, int s
   return g;
 }
 
-// one window: steps q0 .. q0 + S - 1 of the call (alpha, weight: the call's n_steps + 2), the first `nfold` of them folded
-static int ig_window(const mmf_amil_desc* d, const IgWs& g, const float* alpha, const float* weight, int q0, int S,
-                     int nfold, bool first, IgHeadParams hp, hipStream_t st) {
+// The halves of one window, steps q0 .. q0 + S - 1 of the call, which the multimodal call (mmf_mm_ig) interleaves around its
+// one head launch and the single-head calls run back to back (ig_window).
+// the call's steps: the quadrature's, then the two riders alpha = 1 and alpha = 0 with weight 0 (risk_x, risk_base)
+struct IgNodes { int n, total; float alpha[GROUP_MAX + 2], weight[GROUP_MAX + 2]; };
+static IgNodes ig_nodes(int n_steps, const float* alpha, const float* weight) {
+  IgNodes q{};
+  q.n = n_steps; q.total = n_steps + 2;
+  for (int k = 0; k < n_steps; ++k) { q.alpha[k] = alpha[k]; q.weight[k] = weight[k]; }
+  q.alpha[n_steps] = 1.f; q.alpha[n_steps + 1] = 0.f;
+  q.weight[n_steps] = q.weight[n_steps + 1] = 0.f;
+  return q;
+}
+static IgSteps ig_steps(const IgNodes& q, int q0, int S) {
+  IgSteps t{};
+  t.S = S;
+  for (int s = 0; s < S; ++s) { t.alpha[s] = q.alpha[q0 + s]; t.w[s] = q.weight[q0 + s]; }
+  return t;
+}
+// of the window's S steps, the first `nfold` are the quadrature's: the two riders carry weight 0 and are not folded
+static int ig_nfold(const IgNodes& q, int q0, int S) {
+  int nfold = q.n - q0;
+  if (nfold > S) nfold = S;
+  return nfold < 0 ? 0 : nfold;
+}
+
+// forward, to the steps' embeddings: M_s into row s of M, ldm floats apart (and into g.M [S x H], with its statistics)
+static int ig_window_fwd(const mmf_amil_desc* d, const IgWs& g, const IgSteps& steps, float* M, int ldm, hipStream_t st) {
   const int64_t N = d->N;
+  const int S = steps.S;
   mmf_amil_desc dw = *d;                  // the window as a bag of S * N rows
   dw.N = N * S;
   int64_t offsets[GROUP_MAX + 1];
@@ -1409,26 +1434,36 @@ static int ig_window(const mmf_amil_desc* d, const IgWs& g, const float* alpha, 
 
   IgExpandParams ep{};
   ep.U = g.U; ep.b1 = d->b1; ep.h = w.h; ep.relu_bits = w.relu_bits; ep.N = N; ep.H = d->H;
-  ep.st.S = S;
-  for (int s = 0; s < S; ++s) { ep.st.alpha[s] = alpha[q0 + s]; ep.st.w[s] = weight[q0 + s]; }
+  ep.st = steps;
   if (int e = launch_ig_expand(ep, st)) return e;
   if (int e = window_rows(&dw, seg, g, st)) return e;
 
   GateFwdParams gp = stack_gate_fwd(&dw, w, 0);
   gp.seg_ridx = g.ridx_d;
   if (int e = launch_gate_fwd_seg(gp, st)) return e;
-  if (int e = window_pool(&dw, seg, g, g.M, d->H, g.A_raw, st)) return e;
-
-  hp.M = g.M; hp.dM = g.dM; hp.step0 = q0;
-  if (int e = launch_ig_head(hp, S, st)) return e;
-
+  return window_pool(&dw, seg, g, M, ldm, g.A_raw, st);
+}
+// backward, from dM [S x H]: K-prep, K-dh, and the first `nfold` steps folded into g.G
+static int ig_window_bwd(const mmf_amil_desc* d, const IgWs& g, const IgSteps& steps, const float* dM, int nfold, bool first,
+                         hipStream_t st) {
+  mmf_amil_desc dw = *d;
+  dw.N = d->N * steps.S;
+  const AmilWs& w = g.w;
   int dbc_parts;                                     // no weight gradients: nothing reduces them
-  if (int e = window_dh(&dw, g, gate_bwd_ctx(&dw, w.a, w.b, w.ds, 0), g.dM, g.A_raw, dbc_parts, st)) return e;
+  if (int e = window_dh(&dw, g, gate_bwd_ctx(&dw, w.a, w.b, w.ds, 0), dM, g.A_raw, dbc_parts, st)) return e;
 
   IgFoldParams fp{};
-  fp.du = w.du; fp.G = g.G; fp.N = N; fp.H = d->H; fp.first = first ? 1 : 0;
-  fp.st = ep.st; fp.st.S = nfold;
+  fp.du = w.du; fp.G = g.G; fp.N = d->N; fp.H = d->H; fp.first = first ? 1 : 0;
+  fp.st = steps; fp.st.S = nfold;
   return launch_ig_fold(fp, st);
+}
+// one window of a single head: the head's launch between the halves
+static int ig_window(const mmf_amil_desc* d, const IgWs& g, const IgNodes& q, int q0, int S, IgHeadParams hp, hipStream_t st) {
+  const IgSteps steps = ig_steps(q, q0, S);
+  if (int e = ig_window_fwd(d, g, steps, g.M, d->H, st)) return e;
+  hp.M = g.M; hp.dM = g.dM; hp.step0 = q0;
+  if (int e = launch_ig_head(hp, S, st)) return e;
+  return ig_window_bwd(d, g, steps, g.dM, ig_nfold(q, q0, S), q0 == 0, st);
 }
 
 // what both heads' calls refuse first: a null pointer, or a setting the call does not take
@@ -1440,35 +1475,44 @@ static int ig_args(const mmf_amil_desc* d, const mmf_surv_head* head, const mmf_
   return !head->Wk || !head->bk ? MMF_ERR_ARG : MMF_OK;
 }
 
-// The quadrature over the stack d from its input rows [N x L]: U = rows . W1^T, then the windows, `steps` steps each,
-// which leave the folded sum_s w_s du_s in g.G and the risks where ig says.
-static int ig_run(const mmf_amil_desc* d, const float* rows, const IgWs& g, int steps, const mmf_surv_head* head,
-                  const mmf_ig_desc* ig, hipStream_t st) {
-  const int n = ig->n_steps, total = n + 2;
-  float alpha[GROUP_MAX + 2], weight[GROUP_MAX + 2];
-  for (int q = 0; q < n; ++q) { alpha[q] = ig->alpha[q]; weight[q] = ig->weight[q]; }
-  alpha[n] = 1.f; alpha[n + 1] = 0.f;                // the two riders: risk_x, risk_base
-  weight[n] = weight[n + 1] = 0.f;
-
-  {   // the stack's projection without bias, activation or bits
-    AmilWs wp{};
-    wp.h = g.U; wp.kpart = g.kpart;
-    LinearParams lp = stack_linear(d, wp, rows, 0);
-    lp.bias = nullptr; lp.act = ACT_NONE; lp.drop_p = 0.f; lp.seed_dev = nullptr;
-    if (int e = launch_linear(lp, st)) return e;
-  }
+// the stack's projection without bias, activation or bits: g.U = rows . W1^T, once per call
+static int ig_project(const mmf_amil_desc* d, const float* rows, const IgWs& g, hipStream_t st) {
+  AmilWs wp{};
+  wp.h = g.U; wp.kpart = g.kpart;
+  LinearParams lp = stack_linear(d, wp, rows, 0);
+  lp.bias = nullptr; lp.act = ACT_NONE; lp.drop_p = 0.f; lp.seed_dev = nullptr;
+  return launch_linear(lp, st);
+}
+// the head's launch parameters over embeddings `width` wide, but for the window's M, dM and first step
+static IgHeadParams ig_head_params(const mmf_surv_head* head, int width, int n_steps, float* step_risk, float* risk_x,
+                                   float* risk_base) {
   IgHeadParams hp{};
-  hp.Wk = head->Wk; hp.bk = head->bk; hp.K = head->K; hp.H = d->H; hp.n_steps = n;
-  hp.step_risk = ig->step_risk; hp.risk_x = ig->risk_x; hp.risk_base = ig->risk_base;
+  hp.Wk = head->Wk; hp.bk = head->bk; hp.K = head->K; hp.H = width; hp.n_steps = n_steps;
+  hp.step_risk = step_risk; hp.risk_x = risk_x; hp.risk_base = risk_base;
   hp.logits = head->logits; hp.hazards = head->hazards; hp.S = head->S; hp.risk = head->risk; hp.Y_hat = head->Y_hat;
-  for (int q0 = 0; q0 < total; q0 += steps) {
-    const int S = total - q0 < steps ? total - q0 : steps;
-    int nfold = n - q0;                              // the two riders carry weight 0: they are not folded
-    if (nfold > S) nfold = S;
-    if (nfold < 0) nfold = 0;
-    if (int e = ig_window(d, g, alpha, weight, q0, S, nfold, q0 == 0, hp, st)) return e;
+  return hp;
+}
+
+// The quadrature over the stack d behind its projection (g.U): the windows, `steps` steps each, which leave the folded
+// sum_s w_s du_s in g.G and the risks where ig says.
+static int ig_windows(const mmf_amil_desc* d, const IgWs& g, int steps, const mmf_surv_head* head, const mmf_ig_desc* ig,
+                      hipStream_t st) {
+  const IgNodes q = ig_nodes(ig->n_steps, ig->alpha, ig->weight);
+  const IgHeadParams hp = ig_head_params(head, d->H, q.n, ig->step_risk, ig->risk_x, ig->risk_base);
+  for (int q0 = 0; q0 < q.total; q0 += steps) {
+    const int S = q.total - q0 < steps ? q.total - q0 : steps;
+    if (int e = ig_window(d, g, q, q0, S, hp, st)) return e;
   }
   return MMF_OK;
+}
+// the pathology head's last launch: attr = x * (Gacc . W1), and its row sums
+static int ig_attr(const mmf_amil_desc* d, const float* x, const IgWs& g, float* row_sum, float* row_abs, float* attr,
+                   hipStream_t st) {
+  NnParams np{};
+  np.A = g.G; np.lda = d->H; np.B = d->W1; np.ldb = d->L; np.C = attr; np.ldc = d->L;
+  np.M = d->N; np.N = d->L; np.K = d->H;
+  np.mulx = x; np.ldx = d->L; np.rs_part = g.rs_part; np.ra_part = g.ra_part;
+  return launch_nn_attr(np, row_sum, row_abs, st);
 }
 }  // namespace mmf
 
@@ -1495,12 +1539,9 @@ int mmf_amil_ig(const mmf_amil_desc* d, const float* x, void* workspace, size_t 
   if (g.bytes > workspace_bytes) return MMF_ERR_WORKSPACE;
   hipStream_t st = static_cast<hipStream_t>(stream);
   TraceScope ts(d->trace);
-  if (int e = ig_run(d, x, g, steps, head, ig, st)) return e;
-  NnParams np{};                                     // attr = x * (Gacc . W1), and its row sums
-  np.A = g.G; np.lda = d->H; np.B = d->W1; np.ldb = d->L; np.C = ig->attr; np.ldc = d->L;
-  np.M = d->N; np.N = d->L; np.K = d->H;
-  np.mulx = x; np.ldx = d->L; np.rs_part = g.rs_part; np.ra_part = g.ra_part;
-  return launch_nn_attr(np, ig->row_sum, ig->row_abs, st);
+  if (int e = ig_project(d, x, g, st)) return e;
+  if (int e = ig_windows(d, g, steps, head, ig, st)) return e;
+  return ig_attr(d, x, g, ig->row_sum, ig->row_abs, ig->attr, st);
 }
 
 // ---- integrated gradients of the radiology head: reduce_dim folded into the same windows -------------------------------
@@ -1522,6 +1563,46 @@ static RadioIgWs carve_radio_ig(Carver& c, int64_t N, int nseg, int kseg, int H,
   r.bytes = c.off;
   return r;
 }
+// what mmf_radio_ig refuses of rd before the descriptor's rules: the null pointers, then the modality count
+static int radio_ig_args(const mmf_radio_reduce* rd) {
+  if (!rd || !rd->x || !rd->W || !rd->bias) return MMF_ERR_ARG;
+  const bool nseg_ok = rd->nseg >= 2 && rd->nseg <= 4;
+  for (int m = 0; nseg_ok && m < rd->nseg; ++m)
+    if (!rd->x[m]) return MMF_ERR_ARG;
+  return nseg_ok ? MMF_OK : MMF_ERR_SHAPE;
+}
+// once per call, before the windows: Y = X Wr^T, b1' = b1 + W1 br and, through the stack `db` behind reduce_dim (u =
+// alpha U + b1'), U = Y W1^T
+static int radio_ig_project(const mmf_amil_desc* d, const mmf_radio_reduce* rd, const RadioIgWs& r, mmf_amil_desc& db,
+                            hipStream_t st) {
+  {   // reduce_dim over the segments without its bias, the forward-only pass's plan for N rows
+    LinearParams lr = radio_linear(d, rd, r.Y, r.kpart, nullptr);
+    lr.bias = nullptr;
+    if (int e = launch_linear(lr, st)) return e;
+  }
+  if (int e = launch_ig_bias(d->W1, rd->bias, d->b1, r.b1c, d->H, d->L, st)) return e;
+  db = *d;
+  db.b1 = r.b1c;
+  return ig_project(&db, r.Y, r.g, st);
+}
+// once per call, behind the windows: P = Gacc W1 [N x L] in Y's place, then attr_m = x_m * (P Wr)[:, m kseg ..] and its row
+// sums per modality
+static int radio_ig_attr(const mmf_amil_desc* d, const mmf_radio_reduce* rd, const RadioIgWs& r, float* row_sum,
+                         float* row_abs, float* attr, hipStream_t st) {
+  const int nseg = rd->nseg, kseg = rd->kseg, L = d->L, H = d->H;
+  const IgWs& g = r.g;
+  float* P = r.Y;
+  NnParams np{};
+  np.A = g.G; np.lda = H; np.B = d->W1; np.ldb = L; np.C = P; np.ldc = L;
+  np.M = d->N; np.N = L; np.K = H;
+  if (int e = launch_nn(np, st)) return e;
+  NnParams nq{};
+  nq.A = P; nq.lda = L; nq.B = rd->W; nq.ldb = nseg * kseg; nq.C = attr;
+  nq.M = d->N; nq.N = nseg * kseg; nq.K = L;
+  for (int m = 0; m < nseg; ++m) nq.segx[m] = rd->x[m];
+  nq.kseg = kseg; nq.rs_part = g.rs_part; nq.ra_part = g.ra_part;
+  return launch_nn_attr_seg(nq, row_sum, row_abs, st);
+}
 }  // namespace mmf
 
 size_t mmf_radio_ig_workspace_bytes(int64_t N, int32_t nseg, int32_t kseg, int32_t H, int32_t D, int32_t gated,
@@ -1538,11 +1619,7 @@ size_t mmf_radio_ig_workspace_bytes(int64_t N, int32_t nseg, int32_t kseg, int32
 int mmf_radio_ig(const mmf_amil_desc* d, const mmf_radio_reduce* rd, void* workspace, size_t workspace_bytes,
                  const mmf_surv_head* head, const mmf_ig_desc* ig, void* stream) {
   if (int e = ig_args(d, head, ig)) return e;
-  if (!rd || !rd->x || !rd->W || !rd->bias) return MMF_ERR_ARG;
-  const bool nseg_ok = rd->nseg >= 2 && rd->nseg <= 4;
-  for (int m = 0; nseg_ok && m < rd->nseg; ++m)
-    if (!rd->x[m]) return MMF_ERR_ARG;
-  if (!nseg_ok) return MMF_ERR_SHAPE;
+  if (int e = radio_ig_args(rd)) return e;
   if (int e = check_desc(d)) return e;
   const int nseg = rd->nseg, kseg = rd->kseg, L = d->L, H = d->H;
   if (kseg != L) return MMF_ERR_SHAPE;
@@ -1556,30 +1633,223 @@ int mmf_radio_ig(const mmf_amil_desc* d, const mmf_radio_reduce* rd, void* works
   Carver c(workspace);
   const RadioIgWs r = carve_radio_ig(c, d->N, nseg, kseg, H, d->D, d->gated, steps);
   if (r.bytes > workspace_bytes) return MMF_ERR_WORKSPACE;
-  const IgWs& g = r.g;
   hipStream_t st = static_cast<hipStream_t>(stream);
   TraceScope ts(d->trace);
+  mmf_amil_desc db;
+  if (int e = radio_ig_project(d, rd, r, db, st)) return e;
+  if (int e = ig_windows(&db, r.g, steps, head, ig, st)) return e;
+  return radio_ig_attr(d, rd, r, ig->row_sum, ig->row_abs, ig->attr, st);
+}
 
-  {   // Y = X Wr^T: reduce_dim over the segments without its bias, the forward-only pass's plan for N rows
-    LinearParams lr = radio_linear(d, rd, r.Y, r.kpart, nullptr);
-    lr.bias = nullptr;
-    if (int e = launch_linear(lr, st)) return e;
+// ---- integrated gradients of the multimodal concat head: two stacks and the omic SNN around one head launch -------------
+namespace mmf {
+struct MmIgWs {
+  IgWs gp;                   // the pathology stack's
+  RadioIgWs gr;              // the radiology stack's
+  float *Z, *z1, *z2, *dz1, *Gz;   // omic: [W0], [S x W0], [S x We], [S x W0], [W0]
+  float *feat, *dfeat;       // [S x F] each
+  size_t bytes;
+};
+// a branch is absent with Np = 0, Nr = 0, Gin = 0
+static MmIgWs carve_mm_ig(Carver& c, int64_t Np, int Lp, int Hp, int Dp, int gated_p, int64_t Nr, int nseg, int kseg, int Hr,
+                          int Dr, int gated_r, int Gin, int W0, int We, int F, int steps) {
+  MmIgWs m{};
+  if (Np > 0) m.gp = carve_ig(c, Np, Lp, Hp, Dp, gated_p, steps);
+  if (Nr > 0) m.gr = carve_radio_ig(c, Nr, nseg, kseg, Hr, Dr, gated_r, steps);
+  if (Gin > 0) {
+    m.Z = c.take<float>((size_t)W0);
+    m.z1 = c.take<float>((size_t)steps * W0);
+    m.z2 = c.take<float>((size_t)steps * We);
+    m.dz1 = c.take<float>((size_t)steps * W0);
+    m.Gz = c.take<float>((size_t)W0);
   }
-  if (int e = launch_ig_bias(d->W1, rd->bias, d->b1, r.b1c, H, L, st)) return e;   // b1' = b1 + W1 br
-  mmf_amil_desc db = *d;               // the windows see the stack behind reduce_dim: U = Y W1^T, u = alpha U + b1'
-  db.b1 = r.b1c;
-  if (int e = ig_run(&db, r.Y, g, steps, head, ig, st)) return e;
-  float* P = r.Y;                                    // P = Gacc W1 [N x L]
-  NnParams np{};
-  np.A = g.G; np.lda = H; np.B = d->W1; np.ldb = L; np.C = P; np.ldc = L;
-  np.M = d->N; np.N = L; np.K = H;
-  if (int e = launch_nn(np, st)) return e;
-  NnParams nq{};                                     // attr_m = x_m * (P Wr)[:, m kseg ..], and its row sums per modality
-  nq.A = P; nq.lda = L; nq.B = rd->W; nq.ldb = nseg * kseg; nq.C = ig->attr;
-  nq.M = d->N; nq.N = nseg * kseg; nq.K = L;
-  for (int m = 0; m < nseg; ++m) nq.segx[m] = rd->x[m];
-  nq.kseg = kseg; nq.rs_part = g.rs_part; nq.ra_part = g.ra_part;
-  return launch_nn_attr_seg(nq, ig->row_sum, ig->row_abs, st);
+  m.feat = c.take<float>((size_t)steps * F);
+  m.dfeat = c.take<float>((size_t)steps * F);
+  m.bytes = c.off;
+  return m;
+}
+// one S for the whole call: the smaller of what ig_window_steps gives each present stack; 0: some stack admits no window
+static int mm_ig_steps(int64_t Np, int Hp, int Dp, int64_t Nr, int Hr, int Dr, int total, int window_steps) {
+  int steps = total;
+  if (Np > 0) {
+    const int s = ig_window_steps(Np, Hp, Dp, total, window_steps);
+    if (s < steps) steps = s;
+  }
+  if (Nr > 0) {
+    const int s = ig_window_steps(Nr, Hr, Dr, total, window_steps);
+    if (s < steps) steps = s;
+  }
+  return steps;
+}
+// the present branches' column ranges must tile 0 .. F - 1
+static bool mm_ig_columns(const int* col, const int* width, int n, int F) {
+  int at = 0;
+  for (int done = 0; done < n; ++done) {
+    int k = -1;
+    for (int i = 0; i < n; ++i)
+      if (col[i] == at) k = i;
+    if (k < 0) return false;
+    at += width[k];
+  }
+  return at == F;
+}
+// a stack in eval mode with the exact-fp32 GEMMs, as ig_args asks of the single heads
+static int mm_ig_stack_args(const mmf_amil_desc* d, const float* row_sum, const float* row_abs) {
+  if (!row_sum || !row_abs) return MMF_ERR_ARG;
+  return d->gemm != MMF_GEMM_F32 || d->p_h != 0.f || d->p_att != 0.f ? MMF_ERR_ARG : MMF_OK;
+}
+}  // namespace mmf
+
+size_t mmf_mm_ig_workspace_bytes(int64_t N_p, int32_t L_p, int32_t H_p, int32_t D_p, int32_t gated_p, int64_t N_r,
+                                 int32_t nseg, int32_t kseg, int32_t H_r, int32_t D_r, int32_t gated_r, int32_t Gin,
+                                 int32_t W0, int32_t We, int32_t n_steps, int32_t window_steps) {
+  if (n_steps < 1 || n_steps > GROUP_MAX || window_steps < 0 || N_p < 0 || N_r < 0 || Gin < 0) return 0;
+  if ((N_p > 0) + (N_r > 0) + (Gin > 0) < 2) return 0;
+  int64_t F = 0;
+  if (N_p > 0) {
+    if (!mmf_amil_ig_workspace_bytes(N_p, L_p, H_p, D_p, gated_p, n_steps, window_steps)) return 0;
+    F += H_p;
+  }
+  if (N_r > 0) {
+    if (!mmf_radio_ig_workspace_bytes(N_r, nseg, kseg, H_r, D_r, gated_r, n_steps, window_steps)) return 0;
+    F += H_r;
+  }
+  if (Gin > 0) {
+    if (W0 < 1 || W0 > 1024 || We < 1) return 0;
+    F += We;
+  }
+  if (F > 1024) return 0;
+  const int steps = mm_ig_steps(N_p, H_p, D_p, N_r, H_r, D_r, n_steps + 2, window_steps);
+  if (steps < 1) return 0;
+  Carver c;
+  return carve_mm_ig(c, N_p, L_p, H_p, D_p, gated_p, N_r, nseg, kseg, H_r, D_r, gated_r, Gin, W0, We, (int)F, steps).bytes;
+}
+
+int mmf_mm_ig(const mmf_mm_ig_desc* mm, void* workspace, size_t workspace_bytes, const mmf_surv_head* head, void* stream) {
+  // MMF_ERR_ARG
+  if (!mm || !head || !head->Wk || !head->bk) return MMF_ERR_ARG;
+  if (mm->n_steps < 1 || mm->n_steps > GROUP_MAX || mm->window_steps < 0 || !mm->alpha || !mm->weight) return MMF_ERR_ARG;
+  if (!mm->risk_x || !mm->risk_base || !mm->step_risk) return MMF_ERR_ARG;
+  const mmf_amil_desc *dp = mm->path, *dr = mm->radio;
+  const mmf_radio_reduce* rd = mm->rd;
+  const bool omic = mm->omic_x != nullptr;
+  if ((dp != nullptr) + (dr != nullptr) + (omic ? 1 : 0) < 2) return MMF_ERR_ARG;
+  int radio_shape = MMF_OK;                          // nseg outside 2..4: refused behind every null pointer
+  if (dp) {
+    if (!mm->path_x) return MMF_ERR_ARG;
+    if (int e = mm_ig_stack_args(dp, mm->path_row_sum, mm->path_row_abs)) return e;
+  }
+  if (dr) {
+    if (int e = mm_ig_stack_args(dr, mm->radio_row_sum, mm->radio_row_abs)) return e;
+    radio_shape = radio_ig_args(rd);
+    if (radio_shape == MMF_ERR_ARG) return radio_shape;
+  }
+  if (omic && (!mm->omic_W0 || !mm->omic_b0 || !mm->omic_W1 || !mm->omic_b1 || !mm->omic_attr)) return MMF_ERR_ARG;
+  if (dp)
+    if (int e = check_desc(dp); e == MMF_ERR_ARG) return e;
+  if (dr)
+    if (int e = check_desc(dr); e == MMF_ERR_ARG) return e;
+  // MMF_ERR_SHAPE
+  if (radio_shape) return radio_shape;
+  int col[3], width[3], nb = 0;
+  if (dp) {
+    if (int e = check_desc(dp)) return e;
+    col[nb] = mm->path_col; width[nb++] = dp->H;
+  }
+  if (dr) {
+    if (int e = check_desc(dr)) return e;
+    if (rd->kseg != dr->L) return MMF_ERR_SHAPE;
+    if (dr->N * rd->nseg * (int64_t)rd->kseg * 4 >= (int64_t)1 << 31) return MMF_ERR_SHAPE;
+    col[nb] = mm->radio_col; width[nb++] = dr->H;
+  }
+  if (omic) {
+    if (mm->omic_Gin < 1 || mm->omic_W0n < 1 || mm->omic_W0n > 1024 || mm->omic_We < 1) return MMF_ERR_SHAPE;
+    col[nb] = mm->omic_col; width[nb++] = mm->omic_We;
+  }
+  int64_t F64 = 0;
+  for (int i = 0; i < nb; ++i) F64 += width[i];
+  if (F64 > 1024) return MMF_ERR_SHAPE;
+  const int F = (int)F64;
+  if (!mm_ig_columns(col, width, nb, F)) return MMF_ERR_SHAPE;
+  if (head->K < 1 || head->K > 32) return MMF_ERR_SHAPE;
+  const int steps = mm_ig_steps(dp ? dp->N : 0, dp ? dp->H : 0, dp ? dp->D : 0, dr ? dr->N : 0, dr ? dr->H : 0,
+                                dr ? dr->D : 0, mm->n_steps + 2, mm->window_steps);
+  if (steps < 1) return MMF_ERR_SHAPE;
+  // MMF_ERR_ALIGN
+  if (!workspace) return MMF_ERR_ARG;
+  if (dp) {
+    if (int e = check_operands(dp, mm->path_x, workspace, mm->path_row_sum, false)) return e;
+    if (mm->path_attr && !aligned16(mm->path_attr)) return MMF_ERR_ALIGN;
+  }
+  if (dr) {
+    if (int e = radio_operands(dr, rd, false)) return e;
+    if (int e = check_operands(dr, rd->x[0], workspace, mm->radio_row_sum, false)) return e;
+    if (mm->radio_attr && !aligned16(mm->radio_attr)) return MMF_ERR_ALIGN;
+  }
+  if (!aligned16(workspace)) return MMF_ERR_ALIGN;
+  Carver c(workspace);
+  const MmIgWs w = carve_mm_ig(c, dp ? dp->N : 0, dp ? dp->L : 0, dp ? dp->H : 0, dp ? dp->D : 0, dp ? dp->gated : 0,
+                               dr ? dr->N : 0, dr ? rd->nseg : 0, dr ? rd->kseg : 0, dr ? dr->H : 0, dr ? dr->D : 0,
+                               dr ? dr->gated : 0, omic ? mm->omic_Gin : 0, mm->omic_W0n, mm->omic_We, F, steps);
+  if (w.bytes > workspace_bytes) return MMF_ERR_WORKSPACE;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  TraceScope ts(dp && dp->trace ? dp->trace : dr ? dr->trace : nullptr);   // either stack's descriptor may carry it
+
+  // 1. once per call
+  mmf_amil_desc db{};                                // the radiology stack behind reduce_dim
+  IgOmicParams op{};
+  if (dp)
+    if (int e = ig_project(dp, mm->path_x, w.gp, st)) return e;
+  if (dr)
+    if (int e = radio_ig_project(dr, rd, w.gr, db, st)) return e;
+  if (omic) {
+    op.x = mm->omic_x; op.W0 = mm->omic_W0; op.b0 = mm->omic_b0; op.W1 = mm->omic_W1; op.b1 = mm->omic_b1;
+    op.Gin = mm->omic_Gin; op.W0n = mm->omic_W0n; op.We = mm->omic_We;
+    op.Z = w.Z; op.z1 = w.z1; op.z2 = w.z2; op.dz1 = w.dz1; op.Gz = w.Gz;
+    op.feat = w.feat; op.dfeat = w.dfeat; op.F = F; op.col = mm->omic_col; op.attr = mm->omic_attr;
+    if (int e = launch_ig_omic(IG_OMIC_Z, op, st)) return e;
+  }
+  // 2. the windows
+  const IgNodes q = ig_nodes(mm->n_steps, mm->alpha, mm->weight);
+  IgHeadParams hp = ig_head_params(head, F, q.n, mm->step_risk, mm->risk_x, mm->risk_base);
+  hp.M = w.feat; hp.dM = w.dfeat;
+  for (int q0 = 0; q0 < q.total; q0 += steps) {
+    const int S = q.total - q0 < steps ? q.total - q0 : steps;
+    const int nfold = ig_nfold(q, q0, S);
+    const bool first = q0 == 0;
+    const IgSteps sw = ig_steps(q, q0, S);
+    if (dp)
+      if (int e = ig_window_fwd(dp, w.gp, sw, w.feat + mm->path_col, F, st)) return e;
+    if (dr)
+      if (int e = ig_window_fwd(&db, w.gr.g, sw, w.feat + mm->radio_col, F, st)) return e;
+    if (omic) {
+      op.st = sw;
+      if (int e = launch_ig_omic(IG_OMIC_FWD, op, st)) return e;
+    }
+    hp.step0 = q0;
+    if (int e = launch_ig_head(hp, S, st)) return e;
+    if (dp) {
+      if (int e = launch_group_dm_gather(w.dfeat + mm->path_col, F, w.gp.dM, S, dp->H, st)) return e;
+      if (int e = ig_window_bwd(dp, w.gp, sw, w.gp.dM, nfold, first, st)) return e;
+    }
+    if (dr) {
+      if (int e = launch_group_dm_gather(w.dfeat + mm->radio_col, F, w.gr.g.dM, S, dr->H, st)) return e;
+      if (int e = ig_window_bwd(&db, w.gr.g, sw, w.gr.g.dM, nfold, first, st)) return e;
+    }
+    if (omic) {
+      if (int e = launch_ig_omic(IG_OMIC_BWD, op, st)) return e;
+      op.st.S = nfold; op.first = first ? 1 : 0;
+      if (int e = launch_ig_omic(IG_OMIC_FOLD, op, st)) return e;
+    }
+  }
+  // 3. once per call
+  if (dp)
+    if (int e = ig_attr(dp, mm->path_x, w.gp, mm->path_row_sum, mm->path_row_abs, mm->path_attr, st)) return e;
+  if (dr)
+    if (int e = radio_ig_attr(dr, rd, w.gr, mm->radio_row_sum, mm->radio_row_abs, mm->radio_attr, st)) return e;
+  if (omic)
+    if (int e = launch_ig_omic(IG_OMIC_ATTR, op, st)) return e;
+  return MMF_OK;
 }
 
 int mmf_surv_head_nll_step(const float* feat, int32_t F, const mmf_surv_head* head, const mmf_nll_target* target,

@@ -407,6 +407,23 @@ int launch_ig_bias(const float* W1, const float* br, const float* b1, float* out
 // launch_nn_attr over nseg = p.N / p.kseg modalities (NnParams' segmented fields): row_sum / row_abs [nseg x M], each
 // modality's kseg / 32 partials added in block order
 int launch_nn_attr_seg(NnParams p, float* row_sum, float* row_abs, hipStream_t st);
+// the multimodal head (mmf_mm_ig): the omic SNN without weight gradients.  x [Gin]; W0 [W0n x Gin], b0; W1 [We x W0n], b1.
+// Stages: Z = W0 x once per call; per window the forward (z1, z2 kept; O_s into columns col .. col + We - 1 of feat [S x F])
+// and the backward (dfeat's same columns -> dz1 [S x W0n]) with one workgroup per node, and the fold Gz (+)= sum_s w_s
+// dz1_s over the first st.S nodes; attr[j] = x[j] sum_c Gz[c] W0[c, j] once per call.  W0n, We <= 1024.
+enum : int { IG_OMIC_Z, IG_OMIC_FWD, IG_OMIC_BWD, IG_OMIC_FOLD, IG_OMIC_ATTR };
+struct IgOmicParams {
+  const float *x, *W0, *b0, *W1, *b1;
+  int Gin, W0n, We;
+  float *Z, *z1, *z2, *dz1, *Gz;   // [W0n], [S x W0n], [S x We], [S x W0n], [W0n]
+  float* feat;
+  const float* dfeat;
+  int F, col;
+  float* attr;                     // [Gin]
+  int first;                       // the fold overwrites Gz
+  IgSteps st;
+};
+int launch_ig_omic(int stage, const IgOmicParams& p, hipStream_t st);
 
 int set_dyn_lds(const void* kern, int bytes);
 

@@ -261,6 +261,49 @@ def attribute_radiology(model, bags, n_steps=20, method="gausslegendre", return_
         lambda out: out.inst_abs.sum(0), top_k)
 
 
+def mm_integrated_gradients_autograd(model, features, alphas, weights):
+    """integrated_gradients_autograd for the multimodal head: for each (alpha_k, w_k) one `model(**(alpha_k * every input))`
+    pass, the gradient of risk = -sum(S) with respect to every input, and attr = input * sum_k w_k grad_k -- what captum
+    does around the reference's multimodal model (create_attributions.py:93-164), every weight gradient included.  The
+    yardstick of the fused call (tools/ig_bench.py --head mm, the tests).  features: what forward takes for model.mode.
+    Returns ({"radio": [n_mod x N_r x k], "path": [N_p x L], "omic": [G]} for the branches of the mode, risk,
+    risk_baseline, step_risk [n_steps]) on the device."""
+    order = model._concat_order()
+    names = ((list(model.modalities) if "radio" in order else []) + (["path_features"] if "path" in order else [])
+             + (["genomic_features"] if "omic" in order else []))
+    attrs, *risks = _ig_autograd(model, [features[k] for k in names], alphas, weights,
+                                 lambda xs: model(**dict(zip(names, xs))))
+    by_name = dict(zip(names, attrs))
+    out = {}
+    if "radio" in order:
+        out["radio"] = torch.stack([by_name[m] for m in model.modalities])
+    if "path" in order:
+        out["path"] = by_name["path_features"]
+    if "omic" in order:
+        out["omic"] = by_name["genomic_features"].reshape(-1)
+    return (out, *risks)
+
+
+def attribute_modalities(model, features, n_steps=20, method="gausslegendre", return_full=False, top_k=None):
+    """How much of one patient's predicted risk comes from radiology, pathology and omics, create_attributions.py:93-164:
+    integrated gradients of the risk from a joint zero baseline in one fused call (model.integrated_gradients;
+    `modality_abs` holds the reference's radio_attr, path_attr and omic_attr, `share` their fractions).  features: what
+    forward takes for model.mode.  The model is put in eval mode for the call and restored.  Returns the
+    ModalityAttribution, or with top_k the triple (ModalityAttribution, indices of the top_k patches by patch_abs, indices
+    of the top_k slices by sum_m inst_abs), largest first, None for an absent branch."""
+    from .models.model_mm_attention_mil import MM_MIL_Attention_fc_surv
+    if not isinstance(model, MM_MIL_Attention_fc_surv):
+        raise NotImplementedError("attribute_modalities serves the multimodal head")
+    dev = _dev(model)
+    feats = {k: (v.to(dev) if torch.is_tensor(v) else v) for k, v in features.items()}
+    out = _attribute_in_eval(model, lambda: model.integrated_gradients(
+        n_steps=n_steps, method=method, return_full=return_full, **feats), None, None)
+    if top_k is None:
+        return out
+    top = lambda s: None if s is None else torch.topk(s, min(int(top_k), int(s.numel()))).indices
+    return out, top(out.patch_abs), top(None if out.inst_abs is None else out.inst_abs.sum(0))
+
+
 # score_patch_batches(group=True): rows of one grouped scoring call per 256 hidden units.  Up to 128 projection tiles of 64 x
 # 64 (2,048 rows of the `small` head, 1,024 of `big`) a window of fp32 batches keeps the projection plan of a 512-patch
 # batch -- the same four-way K split, the same order of additions -- and with it every score bit for bit.

@@ -14,6 +14,7 @@ about each defect -- the signature and the mathematics are kept, nothing else is
 """
 from __future__ import annotations
 
+import collections
 import contextlib
 
 import torch
@@ -21,8 +22,13 @@ import torch.nn as nn
 
 from .. import ops
 from ..utils.utils import initialize_weights
-from .model_modules import (Attn_Net, Attn_Net_Gated, SNN_Block, XlinearFusion, amil_stack, hand_over_grads, snn_stack,
-                            stack_args)
+from .model_modules import (Attn_Net, Attn_Net_Gated, SNN_Block, XlinearFusion, amil_stack, hand_over_grads, ig_refusals,
+                            snn_stack, stack_args)
+
+
+ModalityAttribution = collections.namedtuple("ModalityAttribution", [
+    "modality_attr", "modality_abs", "share", "patch_attr", "patch_abs", "inst_attr", "inst_abs", "sequence_abs", "gene_attr",
+    "total", "total_abs", "risk", "risk_baseline", "delta", "step_risk", "hazards", "S", "Y_hat", "attr"])
 
 
 class MM_MIL_Attention_fc(nn.Module):
@@ -621,6 +627,72 @@ class MM_MIL_Attention_fc_surv(MM_MIL_Attention_fc):
                 return MM if tensor else torch.cat(vs, dim=1)
             hazards, S, Y_hat, loss, risk = ops.surv_head_infer_group(segs, Wk, bk, Y, cc, alpha)
         return hazards, S, Y_hat.view(-1), A_raw, loss, risk
+
+    def integrated_gradients(self, n_steps=20, method="gausslegendre", return_full=False, window_steps=0, **features):
+        """How much of the predicted risk comes from radiology, pathology and omics: integrated gradients of
+        risk = -sum(S) with respect to every input from a joint zero baseline, in ONE C-ABI call
+        (ops.mm_integrated_gradients) -- what the reference's create_attributions.py:93-164 gets from captum through n_steps
+        autograd passes of the whole forward.  features: what forward takes for self.mode ({modality: [N_r x k]},
+        path_features [N_p x L], genomic_features [G] or [1 x G]), fp32; method, window_steps as
+        MIL_Attention_fc_surv_path.integrated_gradients.  fusion='concat', eval mode, the stock head only.
+        Returns ModalityAttribution: modality_attr / modality_abs {radio, path, omic} (the abs values are the reference's
+        radio_attr, path_attr, omic_attr), share = modality_abs / their sum, patch_attr / patch_abs [N_p], inst_attr /
+        inst_abs [n_mod x N_r], sequence_abs [n_mod], gene_attr [G], total, total_abs, risk, risk_baseline,
+        delta = total - (risk - risk_baseline), step_risk [n_steps], hazards, S, Y_hat at alpha = 1, and with return_full
+        attr {radio: [n_mod x N_r x k], path: [N_p x L], omic: [G]}.  The fields of an absent branch are None."""
+        MmfError = ops._lib.MmfError
+        if self.fusion == "tensor":
+            raise NotImplementedError("integrated_gradients covers fusion='concat' (the tensor fusion needs an "
+                                      "input-gradient-only XlinearFusion tail)")
+        order, _, _ = self._concat_layout()
+        need = {"radio": list(self.modalities), "path": ["path_features"], "omic": ["genomic_features"]}
+        missing = [k for b in order for k in need[b] if features.get(k) is None]
+        if missing:
+            raise MmfError(f"mode {self.mode!r} needs {missing}")
+        bags = [features[m] for m in self.modalities] if "radio" in order else []
+        tensors = bags + [features[k] for b in order if b != "radio" for k in need[b]]
+        ig_refusals(self, "mm", tensors, bags)
+        if "radio" in order and len(bags) < 2:
+            raise NotImplementedError("integrated_gradients takes 2 .. 4 radiology sequences behind reduce_dim")
+        branches = []
+        for b in order:
+            if b == "radio":
+                gated, stack, _, _ = stack_args(self.attention_net_radio, False)
+                branches.append(("radio", bags, self.reduce_dim.weight, self.reduce_dim.bias, stack, gated))
+            elif b == "path":
+                gated, stack, _, _ = stack_args(self.attention_net_WSI, False)
+                branches.append(("path", features["path_features"], stack, gated))
+            else:
+                x = features["genomic_features"]
+                G_in = self.fc_omic[0][0].in_features
+                if x.numel() != G_in or x.dim() > 2:
+                    raise MmfError(f"genomic_features must be [{G_in}] or [1 x {G_in}], got {tuple(x.shape)}")
+                l0, l1 = self.fc_omic[0][0], self.fc_omic[1][0]
+                branches.append(("omic", x.reshape(-1), l0.weight, l0.bias, l1.weight, l1.bias))
+        alphas, weights = ops.ig_quadrature(method, n_steps)
+        with torch.no_grad():
+            out, risk, base, step_risk, (hazards, S, Y_hat) = ops.mm_integrated_gradients(
+                branches, self.classifier.weight, self.classifier.bias, alphas, weights, want_attr=return_full,
+                window_steps=window_steps)
+            f = dict.fromkeys(("patch_attr", "patch_abs", "inst_attr", "inst_abs", "sequence_abs", "gene_attr"))
+            m_attr, m_abs, full = dict.fromkeys(need), dict.fromkeys(need), dict.fromkeys(need)
+            if "path" in out:
+                f["patch_attr"], f["patch_abs"], full["path"] = out["path"]
+                m_attr["path"], m_abs["path"] = f["patch_attr"].sum(), f["patch_abs"].sum()
+            if "radio" in out:
+                f["inst_attr"], f["inst_abs"], full["radio"] = out["radio"]
+                f["sequence_abs"] = f["inst_abs"].sum(-1)
+                m_attr["radio"], m_abs["radio"] = f["inst_attr"].sum(), f["sequence_abs"].sum()
+            if "omic" in out:
+                f["gene_attr"] = full["omic"] = out["omic"]
+                m_attr["omic"], m_abs["omic"] = out["omic"].sum(), out["omic"].abs().sum()
+            total = sum(m_attr[b] for b in order)
+            total_abs = sum(m_abs[b] for b in order)
+            share = {b: (m_abs[b] / total_abs if b in order else None) for b in need}
+            delta = total - (risk[0] - base[0])
+        return ModalityAttribution(m_attr, m_abs, share, f["patch_attr"], f["patch_abs"], f["inst_attr"], f["inst_abs"],
+                                   f["sequence_abs"], f["gene_attr"], total, total_abs, risk[0], base[0], delta, step_risk,
+                                   hazards, S, Y_hat, full if return_full else None)
 
     def forward(self, **kwargs):
         A_raw = {}

@@ -396,6 +396,25 @@ def amil_stack_infer_group(seq, classifier, bags, Y=None, c=None, alpha=0.0, ret
     return hz, S, Y_hat, A, loss, risk
 
 
+def ig_refusals(model, kind, tensors, modalities):
+    """What every integrated_gradients method refuses before its call: train mode; a model that is not the stock head
+    `kind` (`path`, `radio` or `mm`) of core_utils._stock_head; a bf16 tensor among `tensors`; `modalities` (the radiology
+    bags) of different shapes."""
+    from .. import ops
+    from ..utils.core_utils import _stock_head
+    if model.training:
+        raise RuntimeError("integrated_gradients is an eval-mode pass (dropout would make the integrand random): "
+                           "call model.eval() first")
+    if _stock_head(model, step=False)[0] != kind:
+        name = {"path": "pathology", "radio": "radiology", "mm": "multimodal"}[kind]
+        raise NotImplementedError(f"integrated_gradients serves the stock {name} head only (no overridden forward, "
+                                  "no hooks, at most 32 classes)")
+    if any(x.dtype == torch.bfloat16 for x in tensors):
+        raise NotImplementedError("integrated_gradients takes fp32 bags: the bf16 path has no input gradient")
+    if len({tuple(x.shape) for x in modalities}) > 1:
+        raise ops._lib.MmfError("the modalities of a bag must have the same [n x k] shape")
+
+
 def amil_stack_ig(model, kind, seq, xs, call, lead, n_steps, method, return_full, window_steps):
     """What the heads' integrated_gradients methods share: the refusals (eval mode; the stock head `kind`, `path` or
     `radio`, of core_utils._stock_head; fp32 tensors xs of one shape), the rule's nodes (ops.ig_quadrature), the call
@@ -403,18 +422,7 @@ def amil_stack_ig(model, kind, seq, xs, call, lead, n_steps, method, return_full
     its result.  Returns (row_sum, row_abs, their sums over the rows, total, total_abs, risk, risk_baseline,
     delta = total - (risk - risk_baseline), step_risk, attr)."""
     from .. import ops
-    from ..utils.core_utils import _stock_head
-    if model.training:
-        raise RuntimeError("integrated_gradients is an eval-mode pass (dropout would make the integrand random): "
-                           "call model.eval() first")
-    if _stock_head(model, step=False)[0] != kind:
-        name = {"path": "pathology", "radio": "radiology"}[kind]
-        raise NotImplementedError(f"integrated_gradients serves the stock {name} head only (no overridden forward, "
-                                  "no hooks, at most 32 classes)")
-    if any(x.dtype == torch.bfloat16 for x in xs):
-        raise NotImplementedError("integrated_gradients takes fp32 bags: the bf16 path has no input gradient")
-    if len({tuple(x.shape) for x in xs}) != 1:
-        raise ops._lib.MmfError("the modalities of a bag must have the same [n x k] shape")
+    ig_refusals(model, kind, xs, xs)
     gated, stack, _, _ = stack_args(seq, False)
     alphas, weights = ops.ig_quadrature(method, n_steps)
     with torch.no_grad():

@@ -831,6 +831,104 @@ def radio_integrated_gradients(xs, Wr, br, stack, Wk, bk, gated, alphas, weights
                                  bk, alphas, weights, want_attr, window_steps, xs[0].device)
 
 
+def mm_integrated_gradients(branches, Wk, bk, alphas, weights, want_attr=False, window_steps=0):
+    """Integrated gradients of the multimodal concat head's risk = -sum(S) with respect to every input of every branch, from
+    a joint zero baseline, in ONE C-ABI call (include/mmf_amil.h: mmf_mm_ig): the L-wide contractions, reduce_dim and
+    W_o0 x_o run once, the H-wide part of each stack, the omic hidden layers and one head launch once per node.
+    branches: two or three of ("path", x [N x L], stack, gated), ("radio", xs (2 .. 4 of [N x k]), Wr, br, stack, gated) and
+    ("omic", x_o [Gin], W0, b0, W1, b1) in the order of their columns in the fused row; Wk [K x F], bk the hazard head over
+    it; alphas, weights, want_attr, window_steps as amil_integrated_gradients.  Returns ({"path": (row_sum [N], row_abs
+    [N], attr [N x L] or None), "radio": (row_sum [nseg x N], row_abs [nseg x N], attr [nseg x N x k] or None), "omic":
+    attr [Gin]} for the branches given, risk_x [1], risk_base [1], step_risk [n_steps], (hazards [1 x K], S [1 x K],
+    Y_hat [1 x 1]) at alpha = 1)."""
+    import numpy as np
+    a = np.ascontiguousarray(np.asarray(alphas, dtype=np.float64).astype(np.float32))
+    w = np.ascontiguousarray(np.asarray(weights, dtype=np.float64).astype(np.float32))
+    if a.ndim != 1 or a.shape != w.shape or not 1 <= a.size <= GROUP_MAX:
+        raise _lib.MmfError(f"alphas / weights: two sequences of 1..{GROUP_MAX} values each")
+    n = int(a.size)
+    kinds = [b[0] for b in branches]
+    if len(set(kinds)) != len(kinds) or len(kinds) < 2 or any(k not in ("path", "radio", "omic") for k in kinds):
+        raise _lib.MmfError(f"branches: two or three of path, radio and omic, each once, got {kinds}")
+    for b in branches:
+        xs = b[1] if b[0] == "radio" else [b[1]]
+        if any(x.dtype == torch.bfloat16 for x in xs):
+            raise NotImplementedError("integrated gradients take fp32 inputs: the bf16 path has no input gradient")
+    fp = C.POINTER(C.c_float)
+    mm = _lib.MmIgDesc(n_steps=n, window_steps=int(window_steps), alpha=a.ctypes.data_as(fp), weight=w.ctypes.data_as(fp))
+    q = dict(Np=0, Lp=0, Hp=0, Dp=0, gp=0, Nr=0, nseg=0, kseg=0, Hr=0, Dr=0, gr=0, Gin=0, W0=0, We=0)
+    keep, out, F, dev = [], {}, 0, None
+
+    def outputs(ext, N, L):
+        rows = torch.empty((2,) + ext + (N,), dtype=torch.float32, device=dev)
+        attr = torch.empty(ext + (N, L), dtype=torch.float32, device=dev) if want_attr else None
+        return rows, attr
+
+    for b in branches:
+        if b[0] == "path":
+            _, x, stack, gated = b
+            x = _f32c(x)
+            if x.dim() != 2:
+                raise _lib.MmfError(f"bag must be [N x L], got {tuple(x.shape)}")
+            dev = x.device
+            N, L = x.shape
+            stack, _, H, D = _stack_operands(stack, L, None, "bag")
+            d = _amil_desc(stack, N, L, H, D, gated, 0.0, 0.0, 0, None)
+            rows, attr = outputs((), N, L)
+            mm.path, mm.path_x, mm.path_col = C.pointer(d), ptr(x), F
+            mm.path_row_sum, mm.path_row_abs, mm.path_attr = ptr(rows[0]), ptr(rows[1]), ptr(attr)
+            q.update(Np=N, Lp=L, Hp=H, Dp=D, gp=d.gated)
+            out["path"] = (rows[0], rows[1], attr)
+            keep += [x, stack, d]
+            F += H
+        elif b[0] == "radio":
+            _, xs, Wr, br, stack, gated = b
+            xs, N, nseg, kseg, rd = _radio_operands(xs, Wr, br, "pass")
+            dev = xs[0].device
+            stack, _, H, D = _stack_operands(stack, kseg, None, "bags")
+            d = _amil_desc(stack, N, kseg, H, D, gated, 0.0, 0.0, 0, None)
+            rows, attr = outputs((nseg,), N, kseg)
+            mm.radio, mm.rd, mm.radio_col = C.pointer(d), C.pointer(rd), F
+            mm.radio_row_sum, mm.radio_row_abs, mm.radio_attr = ptr(rows[0]), ptr(rows[1]), ptr(attr)
+            q.update(Nr=N, nseg=nseg, kseg=kseg, Hr=H, Dr=D, gr=d.gated)
+            out["radio"] = (rows[0], rows[1], attr)
+            keep += [xs, stack, d, rd]
+            F += H
+        else:
+            _, x, W0, b0, W1, b1 = b
+            x, W0, b0, W1, b1 = (_f32c(t) for t in (x, W0, b0, W1, b1))
+            Gin = x.numel()
+            if (x.dim() != 1 or W0.dim() != 2 or W0.shape[1] != Gin or W1.dim() != 2 or W1.shape[1] != W0.shape[0]
+                    or tuple(b0.shape) != (W0.shape[0],) or tuple(b1.shape) != (W1.shape[0],)):
+                raise _lib.MmfError(f"omic: x [Gin], W0 [W0 x Gin], b0 [W0], W1 [We x W0], b1 [We]; got {tuple(x.shape)}, "
+                                    f"{tuple(W0.shape)}, {tuple(b0.shape)}, {tuple(W1.shape)}, {tuple(b1.shape)}")
+            dev = x.device if dev is None else dev
+            attr_o = torch.empty((Gin,), dtype=torch.float32, device=x.device)
+            mm.omic_x, mm.omic_W0, mm.omic_b0, mm.omic_W1, mm.omic_b1 = ptr(x), ptr(W0), ptr(b0), ptr(W1), ptr(b1)
+            mm.omic_attr, mm.omic_Gin, mm.omic_W0n, mm.omic_We, mm.omic_col = ptr(attr_o), Gin, W0.shape[0], W1.shape[0], F
+            q.update(Gin=Gin, W0=W0.shape[0], We=W1.shape[0])
+            out["omic"] = attr_o
+            keep += [x, W0, b0, W1, b1]
+            F += W1.shape[0]
+    Wk, bk = _f32c(Wk), _f32c(bk)
+    K = Wk.shape[0]
+    if Wk.dim() != 2 or Wk.shape[1] != F or tuple(bk.shape) != (K,) or K > 32:
+        raise _lib.MmfError(f"the hazard head must be [K <= 32 x {F}] over the fused row, got {tuple(Wk.shape)}")
+    l = lib()
+    nbytes = l.mmf_mm_ig_workspace_bytes(q["Np"], q["Lp"], q["Hp"], q["Dp"], q["gp"], q["Nr"], q["nseg"], q["kseg"], q["Hr"],
+                                         q["Dr"], q["gr"], q["Gin"], q["W0"], q["We"], n, int(window_steps))
+    if nbytes == 0:
+        raise _lib.MmfError("mmf_mm_ig: n_steps, window_steps, a branch's widths, the fused width or a bag's size out of range")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    risks = torch.empty(2 + n, dtype=torch.float32, device=dev)
+    hz = torch.empty((2, 1, K), dtype=torch.float32, device=dev)
+    Y_hat = torch.empty((1, 1), dtype=torch.int64, device=dev)
+    mm.risk_x, mm.risk_base, mm.step_risk = ptr(risks[0:1]), ptr(risks[1:2]), ptr(risks[2:])
+    sh = SurvHead(Wk=ptr(Wk), bk=ptr(bk), K=K, logits=None, hazards=ptr(hz[0]), S=ptr(hz[1]), Y_hat=ptr(Y_hat), risk=None)
+    check(l.mmf_mm_ig(C.byref(mm), ptr(ws), nbytes, C.byref(sh), stream_ptr()), "mmf_mm_ig")
+    return out, risks[0:1], risks[1:2], risks[2:], (hz[0], hz[1], Y_hat)
+
+
 def radio_infer_group(xs, sizes, Wr, br, stack, gated, Wk=None, bk=None, Y=None, c=None, alpha=0.0, want_M=False,
                       eps=1e-7):
     """The radiology head's G bags evaluated in ONE C-ABI call (include/mmf_amil.h: mmf_radio_infer_group): reduce_dim

@@ -6,7 +6,13 @@ warm-up first, median of three runs.  One JSON line per bag size; `ratio` = fuse
 <= 0.5 at 50,000 rows of the pathology head and at 150 and 512 rows of the radiology head); `kernels`: the fused call's
 per-kernel device time from one traced call; `patch_abs_max_rel_diff` / `inst_abs_max_rel_diff`: the worst difference of
 the per-row sums of |attr| between the routes.
-usage: ig_bench.py [--head path|radio] [ROWS ...]   (default rows: 1000 10000 50000, radio 150 512 4096);
+--head mm: the multimodal concat head (one mmf_mm_ig), radio_path_omic, small gated stacks, four sequences, an 80-gene omic
+vector, every first-layer bias ~ N(0, 0.1); ROWS are (N_p, N_r) pairs; the yardstick is
+infer.mm_integrated_gradients_autograd (required: ratio < 1 everywhere); `single_heads_ms`: mmf_amil_ig on the pathology bag
+plus mmf_radio_ig on the radiology bags in the same process, each with the classifier's columns of its branch as its head,
+and `vs_single_heads` = fused / that sum (reported, not gated); `*_max_rel_diff`: modality_abs, patch_abs, inst_abs.
+usage: ig_bench.py [--head path|radio|mm] [ROWS ...]   (default rows: 1000 10000 50000, radio 150 512 4096, mm 1000 150
+10000 512 50000 512);
 env IG_BENCH_ITERS (default 5), IG_BENCH_STEPS (default 20)"""
 import argparse, json, os, statistics, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -33,11 +39,92 @@ def timed(fn, iters):
     return statistics.median(runs)
 
 
+def timed_alternating(routes):
+    """timed() for several (fn, iters) routes at once: every route warmed up, then three rounds that time each route in turn,
+    so that a drift of the clocks meets all of them alike; the median per route."""
+    for fn, _ in routes:
+        for _ in range(2):
+            fn()
+    runs = [[] for _ in routes]
+    for _ in range(3):
+        for r, (fn, iters) in zip(runs, routes):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for _ in range(iters):
+                fn()
+            b.record()
+            b.synchronize()
+            r.append(a.elapsed_time(b) / iters)
+    return [statistics.median(r) for r in runs]
+
+
+def main_mm(rows, iters, steps):
+    from multimodalfusion_amd.models.model_mm_attention_mil import MM_MIL_Attention_fc_surv
+    from multimodalfusion_amd.models.model_modules import stack_args
+    rows = rows or [1000, 150, 10000, 512, 50000, 512]
+    if len(rows) % 2:
+        sys.exit("--head mm takes (N_p, N_r) pairs")
+    dev = torch.device("cuda", 0)
+    torch.manual_seed(0)
+    with torch.no_grad():
+        model = MM_MIL_Attention_fc_surv(input_dim=80, fusion="concat", dropout=False, n_classes=4,
+                                         mode="radio_path_omic").to(dev).eval()
+        for b in (model.attention_net_WSI[0].bias, model.attention_net_radio[0].bias, model.reduce_dim.bias,
+                  model.fc_omic[0][0].bias, model.fc_omic[1][0].bias):
+            b.normal_(0.0, 0.1)
+    gen = torch.Generator(device=dev); gen.manual_seed(7)
+    a, w = (v.astype(np.float32) for v in ops.ig_quadrature("gausslegendre", steps))
+    _, cols, _ = model._concat_layout()
+    Wk, bk = model.classifier.weight, model.classifier.bias
+    gp, sp, _, _ = stack_args(model.attention_net_WSI, False)
+    gr, sr, _, _ = stack_args(model.attention_net_radio, False)
+    Wk_p, Wk_r = Wk[:, cols["path"]].contiguous(), Wk[:, cols["radio"]].contiguous()
+    for Np, Nr in zip(rows[0::2], rows[1::2]):
+        feats = {m: torch.randn(Nr, 1024, device=dev, generator=gen) for m in MODS}
+        feats["path_features"] = torch.randn(Np, 1024, device=dev, generator=gen)
+        feats["genomic_features"] = torch.randn(80, device=dev, generator=gen)
+        xs = [feats[m] for m in MODS]
+
+        def fused():
+            return model.integrated_gradients(n_steps=steps, **feats)
+
+        def autograd():
+            return infer.mm_integrated_gradients_autograd(model, feats, a, w)
+
+        def single_heads():
+            with torch.no_grad():
+                ops.amil_integrated_gradients(feats["path_features"], sp, Wk_p, bk, gp, a, w)
+                ops.radio_integrated_gradients(xs, model.reduce_dim.weight, model.reduce_dim.bias, sr, Wk_r, bk, gr, a, w)
+
+        f, (g, *_) = fused(), autograd()
+        torch.cuda.synchronize()
+        ref = {"path": g["path"].abs().sum(1), "radio": g["radio"].abs().sum(2)}
+        mod = {b: float(v.abs().sum()) for b, v in g.items()}
+        err = {"modality_abs": max(abs(float(f.modality_abs[b]) - mod[b]) / mod[b] for b in mod),
+               "patch_abs": float((f.patch_abs - ref["path"]).abs().max() / ref["path"].max()),
+               "inst_abs": float((f.inst_abs - ref["radio"]).abs().max() / ref["radio"].max())}
+        t_f, t_a, t_s = timed_alternating([(fused, iters), (autograd, max(1, iters // 2)), (single_heads, iters)])
+        trace = _lib.KernelTrace()
+        with trace:
+            fused()
+            torch.cuda.synchronize()
+        kernels = {k: [c, round(ms, 4)] for k, (c, ms) in sorted(trace.dump().items(), key=lambda kv: -kv[1][1])}
+        trace.close()
+        ratio = t_f / t_a
+        print(json.dumps({"rows": [Np, Nr], "modalities": len(MODS), "n_steps": steps, "fused_ms": round(t_f, 4),
+                          "autograd_ms": round(t_a, 4), "ratio": round(ratio, 4), "required": 1.0, "ok": ratio < 1.0,
+                          "single_heads_ms": round(t_s, 4), "vs_single_heads": round(t_f / t_s, 4),
+                          **{k + "_max_rel_diff": float(f"{v:.3e}") for k, v in err.items()},
+                          "share": {b: round(float(v), 4) for b, v in f.share.items()}, "kernels": kernels}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--head", choices=["path", "radio"], default="path")
+    ap.add_argument("--head", choices=["path", "radio", "mm"], default="path")
     ap.add_argument("rows", nargs="*", type=int)
     args = ap.parse_args()
+    if args.head == "mm":
+        return main_mm(args.rows, int(os.environ.get("IG_BENCH_ITERS", "5")), int(os.environ.get("IG_BENCH_STEPS", "20")))
     radio = args.head == "radio"
     rows = args.rows or ([150, 512, 4096] if radio else [1000, 10000, 50000])
     iters = int(os.environ.get("IG_BENCH_ITERS", "5"))
