@@ -328,8 +328,8 @@ int mmf_radio_infer_group(const mmf_amil_desc* desc, const mmf_bag_group* group,
  *   (which the L-wide bag can set below that limit; the call then returns MMF_ERR_SHAPE) nor the rules for L, H and D, so a
  *   non-zero answer does not say that the call admits the shape.  For a shape the call admits it is never 0: the row cap is
  *   at or below the window's limit.  It does not shrink as window_steps grows.
- * Out of scope: the multimodal tensor-fusion head (the radiology head: mmf_radio_ig; the multimodal concat head: mmf_mm_ig);
- *   non-zero baselines (they need a second projection,
+ * Out of scope (the radiology head: mmf_radio_ig; the multimodal head: mmf_mm_ig for fusion = 'concat', mmf_mm_ig_tensor for
+ *   fusion = 'tensor'): non-zero baselines (they need a second projection,
  *   U' + alpha (U - U')); bf16 bags; targets other than risk.
  * ------------------------------------------------------------------------------------------- */
 typedef struct mmf_ig_desc {
@@ -385,8 +385,8 @@ int mmf_amil_ig(const mmf_amil_desc* desc, const float* x, void* workspace, size
  * mmf_radio_ig_workspace_bytes: the workspace of that call, or 0 for n_steps outside 1..MMF_GROUP_MAX, window_steps < 0,
  *   N < 1, nseg outside 2..4, kseg < 32, H < 32, N above the row limit of one window (mmf_amil_ig_workspace_bytes) or
  *   N nseg kseg 4 >= 2^31.  It does not shrink as window_steps grows.
- * Out of scope: the multimodal tensor-fusion head (the concat head -- the chain cut at the embedding, the omic network per
- *   node -- has mmf_mm_ig); non-zero baselines; bf16 bags; targets other than risk.
+ * Out of scope (the multimodal head -- the chain cut at the embedding, the omic network per node -- has mmf_mm_ig and, for
+ *   the tensor fusion, mmf_mm_ig_tensor): non-zero baselines; bf16 bags; targets other than risk.
  * ------------------------------------------------------------------------------------------- */
 size_t mmf_radio_ig_workspace_bytes(int64_t N, int32_t nseg, int32_t kseg, int32_t H, int32_t D, int32_t gated,
                                     int32_t n_steps, int32_t window_steps);
@@ -445,7 +445,7 @@ int mmf_radio_ig(const mmf_amil_desc* desc, const mmf_radio_reduce* rd, void* wo
  *   n_steps outside 1..MMF_GROUP_MAX, window_steps < 0, fewer than two branches, a negative extent, and for a present branch
  *   what mmf_amil_ig_workspace_bytes / mmf_radio_ig_workspace_bytes answer 0 for, W0 outside 1..1024, We < 1 or
  *   F > 1024.  It does not shrink as window_steps grows.
- * Out of scope: fusion = 'tensor' (it needs an input-gradient-only XlinearFusion tail); radio_fusion = 'tensor'; non-zero
+ * fusion = 'tensor' has mmf_mm_ig_tensor (below, behind mmf_xfusion_weights).  Out of scope: radio_fusion = 'tensor'; non-zero
  *   baselines; bf16 bags; targets other than risk; the stage-2 pretrained models; the omic-only MaxNet.
  * ------------------------------------------------------------------------------------------- */
 typedef struct mmf_mm_ig_desc {
@@ -636,6 +636,57 @@ int mmf_xfusion_group_backward(const mmf_xfusion_weights* w, const float* x2, in
                                const uint32_t* row_base, const uint32_t* seed_dev, const float* MM, const float* hid,
                                const float* dhid, int32_t lddhid, void* workspace, size_t workspace_bytes, float* dx2,
                                const mmf_xfusion_grads* grads, int32_t accumulate, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Integrated-gradients attribution of the multimodal tensor-fusion head in one call (fusion = 'tensor', the model's
+ *   default): mmf_mm_ig's question for the head whose embeddings meet in the XlinearFusion block.  The reference's captum
+ *   methods (models/model_mm_attention_mil.py:202-396) take that branch like any other: n_steps autograd passes, each with
+ *   every weight gradient of both stacks and of the tail, encoder1's 10 MB weight gradient among them.
+ * The identity of mmf_mm_ig holds unchanged up to the embeddings: the L-wide contractions, reduce_dim, their transposes
+ *   and W_o0 x_o run once per call, the H-wide part of each stack and the omic hidden layers per node.  The tail -- the
+ *   gating stage, the Kronecker product fused into encoder1, encoder2 with its skip connection, classifier[0] and
+ *   classifier[3] -- is nonlinear in the embeddings: nothing of it folds, and for the S nodes of a window it is the
+ *   "G patients of a window" problem of mmf_xfusion_group_forward / _backward with G = S in eval mode, without its weight
+ *   gradients.  The chain, on one stream, nothing allocated:
+ *     1. once: step 1 of mmf_mm_ig;
+ *     2. per window of S nodes (S as in mmf_mm_ig; S <= MMF_GROUP_MAX): the branches' forward halves as in mmf_mm_ig, each
+ *        writing its embedding into its columns of encoder2's input rows x2 [S x K2], K2 = mmhid1 + m dim, column
+ *        mmhid1 + {path,radio,omic}_col; then SEVEN launches: the gating stage, the product fused into encoder1, encoder2
+ *        (mmf_xfusion_group_forward's first three at p = 0); one workgroup per node for hid = relu(Wc0 MM_s + bc0) kept in
+ *        LDS, the hazard head and the backward of risk (the device body of mmf_mm_ig's head launch), dpre0 = dhid . [hid >
+ *        0] and dMM_s = dpre0 Wc0; encoder2's input gradient (the dense backward's dx blocks alone); d of the product in one
+ *        pass over encoder1's weight; the gating stage's backward, which adds dv_i to the skip connection's gradient in
+ *        dx2.  Then the branches' backward halves as in mmf_mm_ig on their columns of dx2 (pitch K2);
+ *     3. once: step 3 of mmf_mm_ig.
+ *   No weight-gradient launch (no TN, no dWe1, no gating dW), no add-into, no float atomics, no workgroup waits for another;
+ *   every sum is taken in an order fixed by its output element: two calls agree bit for bit.
+ * mm: mmf_mm_ig_desc as for mmf_mm_ig, except that path_col / radio_col / omic_col are the branch's first column within the
+ *   m dim embedding columns of encoder2's input row: they must tile 0 .. m dim - 1 in steps of dim, every present width
+ *   (path->H, radio->H, omic_We) must equal xf->dim, and xf->m the number of present branches.  xf: the tail's weights,
+ *   classifier[0] included, as for mmf_xfusion_group_forward.  head: classifier[3], Wk [K x nhid], bk, K in 1..32; the
+ *   optional outputs receive the values at alpha = 1.  Outputs as mmf_mm_ig.
+ * Returns, before any launch and in this order:
+ *   MMF_ERR_ARG for everything mmf_mm_ig refuses with it, a null xf, or a null weight or bias of xf;
+ *   MMF_ERR_SHAPE for everything mmf_mm_ig refuses of the stacks and the omic widths, what mmf_xfusion_group_forward
+ *     refuses of xf with G = S, xf->m != the number of branches, a width != xf->dim, columns that do not tile, nhid > 1024
+ *     (hid is kept in LDS), K outside 1..32, or a bag too long for one step to be a window;
+ *   MMF_ERR_ALIGN for everything mmf_mm_ig refuses with it, then Wh_i or Wz_i off 16 bytes; MMF_ERR_WORKSPACE.
+ * mmf_mm_ig_tensor_workspace_bytes: mmf_mm_ig_workspace_bytes' arguments, then the tail's extents (m is the number of
+ *   present branches).  0 for what that query answers 0 for but F > 1024, and for a tail refused by shape.  Otherwise that
+ *   query's stack and omic parts (no feat / dfeat) plus, with S the window's nodes and every array rounded up to 256 bytes,
+ *     4 S (2 K2 + 3 mmhid2 + 7 m 16 + (sdim + 1)^m + 1) + 4 S words((sdim + 1)^m)  bytes:
+ *   x2, dx2 [S x K2]; MM, dMM and the dense backward's dpre [S x mmhid2]; o, h, z, gm, dpo, dz, dph [S x m x 16]; dkr
+ *   [S x (sdim + 1)^m]; the seed table the forward launches ask for [S]; the keep bits, words(E) = 2 ceil(E / 64) per node.
+ *   Monotone in S; it does not shrink as window_steps grows.
+ * Out of scope: radio_fusion = 'tensor'; non-zero baselines; bf16 bags; targets other than risk; the stage-2 pretrained
+ *   models; the omic-only MaxNet.
+ * ------------------------------------------------------------------------------------------- */
+size_t mmf_mm_ig_tensor_workspace_bytes(int64_t N_p, int32_t L_p, int32_t H_p, int32_t D_p, int32_t gated_p, int64_t N_r,
+                                        int32_t nseg, int32_t kseg, int32_t H_r, int32_t D_r, int32_t gated_r, int32_t Gin,
+                                        int32_t W0, int32_t We, int32_t n_steps, int32_t window_steps, int32_t dim,
+                                        int32_t sdim, int32_t mmhid1, int32_t mmhid2, int32_t nhid);
+int mmf_mm_ig_tensor(const mmf_mm_ig_desc* mm, const mmf_xfusion_weights* xf, void* workspace, size_t workspace_bytes,
+                     const mmf_surv_head* head, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Forward-only variants for the inference consumers of the path -- embedding export

@@ -186,6 +186,9 @@ SYMBOLS = {
                                C.POINTER(IgDesc), C.c_void_p]),
     "mmf_mm_ig_workspace_bytes": (C.c_size_t, [C.c_int64] + [C.c_int32] * 4 + [C.c_int64] + [C.c_int32] * 10),
     "mmf_mm_ig": (C.c_int, [C.POINTER(MmIgDesc), C.c_void_p, C.c_size_t, C.POINTER(SurvHead), C.c_void_p]),
+    "mmf_mm_ig_tensor_workspace_bytes": (C.c_size_t, [C.c_int64] + [C.c_int32] * 4 + [C.c_int64] + [C.c_int32] * 15),
+    "mmf_mm_ig_tensor": (C.c_int, [C.POINTER(MmIgDesc), C.POINTER(XFusionWeights), C.c_void_p, C.c_size_t,
+                                   C.POINTER(SurvHead), C.c_void_p]),
     "mmf_radio_group_infer_workspace_bytes": (C.c_size_t, [C.POINTER(C.c_int64), C.c_int32, C.c_int32, C.c_int32,
                                                             C.c_int32, C.c_int32, C.c_int32]),
     "mmf_radio_infer_group": (C.c_int, [C.POINTER(AmilDesc), C.POINTER(BagGroup), C.POINTER(RadioReduce), C.c_void_p,

@@ -11,6 +11,7 @@
 #include "mmf_gemm_core.h"
 #include "mmf_gemm_split.h"
 #include "mmf_kernels.h"
+#include "mmf_ig_head.h"
 
 namespace mmf {
 
@@ -1383,52 +1384,13 @@ int launch_ig_bias(const float* W1, const float* br, const float* b1, float* out
 }
 
 // The hazard head of models/model_attention_mil_path.py:58-61 on a step's pooled embedding and the gradient of
-// risk = -sum_k S_k back to it.  S_k = prod_{i <= k} (1 - h_i), so d risk / d h_j = sum_{k >= j} prod_{i <= k, i != j}
-// (1 - h_i): built from the products themselves, never divided by 1 - h_j.
+// risk = -sum_k S_k back to it: the head and d risk / d logits are ig_hazard_body (mmf_ig_head.h), the one body the
+// tensor fusion's node kernel shares; this launch takes the logits' gradient on to the embedding.
 __global__ __launch_bounds__(256) void ig_head_kernel(IgHeadParams p) {
   __shared__ float lg[32], hz[32], sv[32], dl[32];
-  const int s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int s = blockIdx.x, tid = threadIdx.x;
   const int H = p.H, K = p.K;
-  const float* M = p.M + (size_t)s * H;
-  for (int k = wave; k < K; k += 4) {
-    float t = 0.f;
-    for (int c = lane; c < H; c += 64) t += p.Wk[(size_t)k * H + c] * M[c];
-    t = wave_sum(t);
-    if (lane == 0) lg[k] = t + p.bk[k];
-  }
-  __syncthreads();
-  if (tid == 0) {
-    float surv = 1.f, risk = 0.f;
-    int best = 0;
-    for (int k = 0; k < K; ++k) {
-      const float h = 1.0f / (1.0f + __expf(-lg[k]));
-      hz[k] = h;
-      surv *= 1.0f - h;
-      sv[k] = surv;
-      risk -= surv;
-      if (lg[k] > lg[best]) best = k;
-    }
-    float pre = 1.f;                       // prod_{i < j} (1 - h_i)
-    for (int j = 0; j < K; ++j) {
-      float run = pre, g = pre;
-      for (int k = j + 1; k < K; ++k) { run *= 1.0f - hz[k]; g += run; }
-      dl[j] = g * hz[j] * (1.0f - hz[j]);
-      pre *= 1.0f - hz[j];
-    }
-    const int q = p.step0 + s;
-    if (q < p.n_steps) p.step_risk[q] = risk;
-    else if (q == p.n_steps) {
-      p.risk_x[0] = risk;
-      if (p.risk) p.risk[0] = risk;
-      if (p.Y_hat) p.Y_hat[0] = best;
-      for (int k = 0; k < K; ++k) {
-        if (p.logits) p.logits[k] = lg[k];
-        if (p.hazards) p.hazards[k] = hz[k];
-        if (p.S) p.S[k] = sv[k];
-      }
-    } else p.risk_base[0] = risk;
-  }
-  __syncthreads();
+  ig_hazard_body<4>(p, p.M + (size_t)s * H, s, lg, hz, sv, dl);
   for (int c = tid; c < H; c += 256) {
     float t = 0.f;
     for (int j = 0; j < K; ++j) t += dl[j] * p.Wk[(size_t)j * H + c];

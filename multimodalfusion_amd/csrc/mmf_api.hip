@@ -1725,132 +1725,7 @@ size_t mmf_mm_ig_workspace_bytes(int64_t N_p, int32_t L_p, int32_t H_p, int32_t 
   return carve_mm_ig(c, N_p, L_p, H_p, D_p, gated_p, N_r, nseg, kseg, H_r, D_r, gated_r, Gin, W0, We, (int)F, steps).bytes;
 }
 
-int mmf_mm_ig(const mmf_mm_ig_desc* mm, void* workspace, size_t workspace_bytes, const mmf_surv_head* head, void* stream) {
-  // MMF_ERR_ARG
-  if (!mm || !head || !head->Wk || !head->bk) return MMF_ERR_ARG;
-  if (mm->n_steps < 1 || mm->n_steps > GROUP_MAX || mm->window_steps < 0 || !mm->alpha || !mm->weight) return MMF_ERR_ARG;
-  if (!mm->risk_x || !mm->risk_base || !mm->step_risk) return MMF_ERR_ARG;
-  const mmf_amil_desc *dp = mm->path, *dr = mm->radio;
-  const mmf_radio_reduce* rd = mm->rd;
-  const bool omic = mm->omic_x != nullptr;
-  if ((dp != nullptr) + (dr != nullptr) + (omic ? 1 : 0) < 2) return MMF_ERR_ARG;
-  int radio_shape = MMF_OK;                          // nseg outside 2..4: refused behind every null pointer
-  if (dp) {
-    if (!mm->path_x) return MMF_ERR_ARG;
-    if (int e = mm_ig_stack_args(dp, mm->path_row_sum, mm->path_row_abs)) return e;
-  }
-  if (dr) {
-    if (int e = mm_ig_stack_args(dr, mm->radio_row_sum, mm->radio_row_abs)) return e;
-    radio_shape = radio_ig_args(rd);
-    if (radio_shape == MMF_ERR_ARG) return radio_shape;
-  }
-  if (omic && (!mm->omic_W0 || !mm->omic_b0 || !mm->omic_W1 || !mm->omic_b1 || !mm->omic_attr)) return MMF_ERR_ARG;
-  if (dp)
-    if (int e = check_desc(dp); e == MMF_ERR_ARG) return e;
-  if (dr)
-    if (int e = check_desc(dr); e == MMF_ERR_ARG) return e;
-  // MMF_ERR_SHAPE
-  if (radio_shape) return radio_shape;
-  int col[3], width[3], nb = 0;
-  if (dp) {
-    if (int e = check_desc(dp)) return e;
-    col[nb] = mm->path_col; width[nb++] = dp->H;
-  }
-  if (dr) {
-    if (int e = check_desc(dr)) return e;
-    if (rd->kseg != dr->L) return MMF_ERR_SHAPE;
-    if (dr->N * rd->nseg * (int64_t)rd->kseg * 4 >= (int64_t)1 << 31) return MMF_ERR_SHAPE;
-    col[nb] = mm->radio_col; width[nb++] = dr->H;
-  }
-  if (omic) {
-    if (mm->omic_Gin < 1 || mm->omic_W0n < 1 || mm->omic_W0n > 1024 || mm->omic_We < 1) return MMF_ERR_SHAPE;
-    col[nb] = mm->omic_col; width[nb++] = mm->omic_We;
-  }
-  int64_t F64 = 0;
-  for (int i = 0; i < nb; ++i) F64 += width[i];
-  if (F64 > 1024) return MMF_ERR_SHAPE;
-  const int F = (int)F64;
-  if (!mm_ig_columns(col, width, nb, F)) return MMF_ERR_SHAPE;
-  if (head->K < 1 || head->K > 32) return MMF_ERR_SHAPE;
-  const int steps = mm_ig_steps(dp ? dp->N : 0, dp ? dp->H : 0, dp ? dp->D : 0, dr ? dr->N : 0, dr ? dr->H : 0,
-                                dr ? dr->D : 0, mm->n_steps + 2, mm->window_steps);
-  if (steps < 1) return MMF_ERR_SHAPE;
-  // MMF_ERR_ALIGN
-  if (!workspace) return MMF_ERR_ARG;
-  if (dp) {
-    if (int e = check_operands(dp, mm->path_x, workspace, mm->path_row_sum, false)) return e;
-    if (mm->path_attr && !aligned16(mm->path_attr)) return MMF_ERR_ALIGN;
-  }
-  if (dr) {
-    if (int e = radio_operands(dr, rd, false)) return e;
-    if (int e = check_operands(dr, rd->x[0], workspace, mm->radio_row_sum, false)) return e;
-    if (mm->radio_attr && !aligned16(mm->radio_attr)) return MMF_ERR_ALIGN;
-  }
-  if (!aligned16(workspace)) return MMF_ERR_ALIGN;
-  Carver c(workspace);
-  const MmIgWs w = carve_mm_ig(c, dp ? dp->N : 0, dp ? dp->L : 0, dp ? dp->H : 0, dp ? dp->D : 0, dp ? dp->gated : 0,
-                               dr ? dr->N : 0, dr ? rd->nseg : 0, dr ? rd->kseg : 0, dr ? dr->H : 0, dr ? dr->D : 0,
-                               dr ? dr->gated : 0, omic ? mm->omic_Gin : 0, mm->omic_W0n, mm->omic_We, F, steps);
-  if (w.bytes > workspace_bytes) return MMF_ERR_WORKSPACE;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  TraceScope ts(dp && dp->trace ? dp->trace : dr ? dr->trace : nullptr);   // either stack's descriptor may carry it
-
-  // 1. once per call
-  mmf_amil_desc db{};                                // the radiology stack behind reduce_dim
-  IgOmicParams op{};
-  if (dp)
-    if (int e = ig_project(dp, mm->path_x, w.gp, st)) return e;
-  if (dr)
-    if (int e = radio_ig_project(dr, rd, w.gr, db, st)) return e;
-  if (omic) {
-    op.x = mm->omic_x; op.W0 = mm->omic_W0; op.b0 = mm->omic_b0; op.W1 = mm->omic_W1; op.b1 = mm->omic_b1;
-    op.Gin = mm->omic_Gin; op.W0n = mm->omic_W0n; op.We = mm->omic_We;
-    op.Z = w.Z; op.z1 = w.z1; op.z2 = w.z2; op.dz1 = w.dz1; op.Gz = w.Gz;
-    op.feat = w.feat; op.dfeat = w.dfeat; op.F = F; op.col = mm->omic_col; op.attr = mm->omic_attr;
-    if (int e = launch_ig_omic(IG_OMIC_Z, op, st)) return e;
-  }
-  // 2. the windows
-  const IgNodes q = ig_nodes(mm->n_steps, mm->alpha, mm->weight);
-  IgHeadParams hp = ig_head_params(head, F, q.n, mm->step_risk, mm->risk_x, mm->risk_base);
-  hp.M = w.feat; hp.dM = w.dfeat;
-  for (int q0 = 0; q0 < q.total; q0 += steps) {
-    const int S = q.total - q0 < steps ? q.total - q0 : steps;
-    const int nfold = ig_nfold(q, q0, S);
-    const bool first = q0 == 0;
-    const IgSteps sw = ig_steps(q, q0, S);
-    if (dp)
-      if (int e = ig_window_fwd(dp, w.gp, sw, w.feat + mm->path_col, F, st)) return e;
-    if (dr)
-      if (int e = ig_window_fwd(&db, w.gr.g, sw, w.feat + mm->radio_col, F, st)) return e;
-    if (omic) {
-      op.st = sw;
-      if (int e = launch_ig_omic(IG_OMIC_FWD, op, st)) return e;
-    }
-    hp.step0 = q0;
-    if (int e = launch_ig_head(hp, S, st)) return e;
-    if (dp) {
-      if (int e = launch_group_dm_gather(w.dfeat + mm->path_col, F, w.gp.dM, S, dp->H, st)) return e;
-      if (int e = ig_window_bwd(dp, w.gp, sw, w.gp.dM, nfold, first, st)) return e;
-    }
-    if (dr) {
-      if (int e = launch_group_dm_gather(w.dfeat + mm->radio_col, F, w.gr.g.dM, S, dr->H, st)) return e;
-      if (int e = ig_window_bwd(&db, w.gr.g, sw, w.gr.g.dM, nfold, first, st)) return e;
-    }
-    if (omic) {
-      if (int e = launch_ig_omic(IG_OMIC_BWD, op, st)) return e;
-      op.st.S = nfold; op.first = first ? 1 : 0;
-      if (int e = launch_ig_omic(IG_OMIC_FOLD, op, st)) return e;
-    }
-  }
-  // 3. once per call
-  if (dp)
-    if (int e = ig_attr(dp, mm->path_x, w.gp, mm->path_row_sum, mm->path_row_abs, mm->path_attr, st)) return e;
-  if (dr)
-    if (int e = radio_ig_attr(dr, rd, w.gr, mm->radio_row_sum, mm->radio_row_abs, mm->radio_attr, st)) return e;
-  if (omic)
-    if (int e = launch_ig_omic(IG_OMIC_ATTR, op, st)) return e;
-  return MMF_OK;
-}
+// mmf_mm_ig and mmf_mm_ig_tensor: one body, behind the fusion tail it may run (mm_ig_call, below)
 
 int mmf_surv_head_nll_step(const float* feat, int32_t F, const mmf_surv_head* head, const mmf_nll_target* target,
                            float* dfeat, void* stream) {
@@ -1975,18 +1850,69 @@ static int xfusion_train_shape(const mmf_xfusion_weights* w, int G) {
     return MMF_ERR_SHAPE;
   return MMF_OK;
 }
-static int xfusion_train_weights(const mmf_xfusion_weights* w) {
+// the null pointers of the weights (m is clamped: mm_ig_call asks before the shape is known), then the float4 operands
+static int xfusion_weights_args(const mmf_xfusion_weights* w) {
   if (!w->We1 || !w->be1 || !w->We2 || !w->be2 || !w->Wc0 || !w->bc0) return MMF_ERR_ARG;
-  for (int i = 0; i < w->m; ++i)
+  for (int i = 0; i < w->m && i < 3; ++i)
     if (!w->Wh[i] || !w->bh[i] || !w->Wz[i] || !w->bz[i] || !w->Wo[i] || !w->bo[i]) return MMF_ERR_ARG;
+  return MMF_OK;
+}
+static int xfusion_weights_aligned(const mmf_xfusion_weights* w) {
   for (int i = 0; i < w->m; ++i)
     if (!aligned16(w->Wh[i]) || !aligned16(w->Wz[i])) return MMF_ERR_ALIGN;     // float4 loads
   return MMF_OK;
+}
+static int xfusion_train_weights(const mmf_xfusion_weights* w) {
+  if (int e = xfusion_weights_args(w)) return e;
+  return xfusion_weights_aligned(w);
 }
 static XTrainParams xtrain(float p, uint32_t site, const uint32_t* row_base, const uint32_t* seed_dev) {
   XTrainParams t{};
   t.p = p; t.key = drop_key(0, site); t.dev = seed_dev; t.row_base = row_base;
   return t;
+}
+// the gating stage, the Kronecker product fused into encoder1 and encoder2 over the rows of x2 [G x K2], whose embedding
+// columns the caller filled: e1 into x2's first columns, MM [G x mmhid2] (mmf_xfusion_group_forward; mm_ig_call at p = 0)
+static int xfusion_group_fwd_launches(const mmf_xfusion_weights* w, float* x2, int G, float drop_p, const uint32_t* row_base,
+                                      const uint32_t* seed_dev, const XFusionTrainWs& ws, float* MM, hipStream_t st) {
+  const int K2 = w->mmhid1 + w->m * w->dim;
+  XGateGroupParams gp{};
+  gp.m = w->m; gp.G = G; gp.dim = w->dim; gp.sdim = w->sdim;
+  for (int i = 0; i < w->m; ++i) {
+    gp.v[i] = x2 + w->mmhid1 + i * w->dim; gp.Wh[i] = w->Wh[i]; gp.bh[i] = w->bh[i]; gp.Wz[i] = w->Wz[i];
+    gp.bz[i] = w->bz[i]; gp.Wo[i] = w->Wo[i]; gp.bo[i] = w->bo[i];
+  }
+  gp.o = ws.o;
+  XTrainParams tg = xtrain(drop_p, 0, row_base, seed_dev);
+  tg.key8 = drop_key(0, 8); tg.ld = K2; tg.h = ws.h; tg.z = ws.z; tg.gm = ws.gm; tg.bits = ws.bits;
+  if (int e = launch_xgate_group_train(gp, tg, st)) return e;
+  KronDenseGroupParams kp{w->m, G, w->mmhid1, ws.o, w->We1, w->be1, x2};      // e1 into the first columns of x2
+  XTrainParams tk = xtrain(drop_p, 9, row_base, seed_dev);
+  tk.ld = K2; tk.bits = ws.bits;
+  if (int e = launch_kron_dense_group_train(kp, tk, st)) return e;
+  DenseSegsParams e2{};                 // encoder2 on the rows of x2 = [e1 | v_0 | v_1 (| v_2)]
+  e2.nseg = 1; e2.G = G; e2.N = w->mmhid2; e2.K = K2;
+  e2.x[0] = x2; e2.width[0] = K2;
+  e2.W = w->We2; e2.bias = w->be2; e2.y = MM;
+  return launch_dense_segs_group_train(e2, xtrain(drop_p, 10, row_base, seed_dev), st);
+}
+// the parameter block of the backward in front of encoder2; g null: the input-gradient launches alone read it
+static XFusionBwdParams xfusion_bwd_params(const mmf_xfusion_weights* w, const float* x2, float* dx2, int G, float drop_p,
+                                           int accumulate, const XFusionTrainWs& ws, const mmf_xfusion_grads* g) {
+  const int K2 = w->mmhid1 + w->m * w->dim;
+  XFusionBwdParams p{};
+  p.m = w->m; p.G = G; p.dim = w->dim; p.N1 = w->mmhid1; p.K2 = K2; p.p = drop_p; p.accumulate = accumulate;
+  p.x2 = x2; p.dx2 = dx2; p.o = ws.o; p.h = ws.h; p.z = ws.z; p.gm = ws.gm; p.bits = ws.bits; p.dkr = ws.dkr;
+  p.dpo = ws.dpo; p.dz = ws.dz; p.dph = ws.dph; p.We1 = w->We1;
+  for (int i = 0; i < w->m; ++i) {
+    p.Wh[i] = w->Wh[i]; p.Wz[i] = w->Wz[i]; p.Wo[i] = w->Wo[i];
+    if (g) {
+      p.dWh[i] = g->dWh[i]; p.dbh[i] = g->dbh[i]; p.dWz[i] = g->dWz[i]; p.dbz[i] = g->dbz[i];
+      p.dWo[i] = g->dWo[i]; p.dbo[i] = g->dbo[i];
+    }
+  }
+  if (g) { p.dWe1 = g->dWe1; p.dbe1 = g->dbe1; }
+  return p;
 }
 }  // namespace mmf
 
@@ -2011,26 +1937,7 @@ int mmf_xfusion_group_forward(const mmf_xfusion_weights* w, float* x2, int32_t G
   const XFusionTrainWs ws = carve_xfusion_train(c, w->m, w->dim, w->mmhid1, w->mmhid2, w->nhid, G);
   if (ws.bytes > workspace_bytes) return MMF_ERR_WORKSPACE;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const int K2 = w->mmhid1 + w->m * w->dim;
-  XGateGroupParams gp{};
-  gp.m = w->m; gp.G = G; gp.dim = w->dim; gp.sdim = w->sdim;
-  for (int i = 0; i < w->m; ++i) {
-    gp.v[i] = x2 + w->mmhid1 + i * w->dim; gp.Wh[i] = w->Wh[i]; gp.bh[i] = w->bh[i]; gp.Wz[i] = w->Wz[i];
-    gp.bz[i] = w->bz[i]; gp.Wo[i] = w->Wo[i]; gp.bo[i] = w->bo[i];
-  }
-  gp.o = ws.o;
-  XTrainParams tg = xtrain(drop_p, 0, row_base, seed_dev);
-  tg.key8 = drop_key(0, 8); tg.ld = K2; tg.h = ws.h; tg.z = ws.z; tg.gm = ws.gm; tg.bits = ws.bits;
-  if (int e = launch_xgate_group_train(gp, tg, st)) return e;
-  KronDenseGroupParams kp{w->m, G, w->mmhid1, ws.o, w->We1, w->be1, x2};      // e1 into the first columns of x2
-  XTrainParams tk = xtrain(drop_p, 9, row_base, seed_dev);
-  tk.ld = K2; tk.bits = ws.bits;
-  if (int e = launch_kron_dense_group_train(kp, tk, st)) return e;
-  DenseSegsParams e2{};                 // encoder2 on the rows of x2 = [e1 | v_0 | v_1 (| v_2)]
-  e2.nseg = 1; e2.G = G; e2.N = w->mmhid2; e2.K = K2;
-  e2.x[0] = x2; e2.width[0] = K2;
-  e2.W = w->We2; e2.bias = w->be2; e2.y = MM;
-  if (int e = launch_dense_segs_group_train(e2, xtrain(drop_p, 10, row_base, seed_dev), st)) return e;
+  if (int e = xfusion_group_fwd_launches(w, x2, G, drop_p, row_base, seed_dev, ws, MM, st)) return e;
   DenseSegsParams c0{};                 // classifier[0] + ReLU + Dropout
   c0.nseg = 1; c0.G = G; c0.N = w->nhid; c0.K = w->mmhid2;
   c0.x[0] = MM; c0.width[0] = w->mmhid2;
@@ -2072,16 +1979,244 @@ int mmf_xfusion_group_backward(const mmf_xfusion_weights* w, const float* x2, in
     if (int e = launch_add_into(g->dWe2, ws.tmpW, (int64_t)w->mmhid2 * K2, st)) return e;
     if (int e = launch_add_into(g->dbe2, ws.tmpb, w->mmhid2, st)) return e;
   }
-  XFusionBwdParams p{};
-  p.m = w->m; p.G = G; p.dim = w->dim; p.N1 = w->mmhid1; p.K2 = K2; p.p = drop_p; p.accumulate = accumulate;
-  p.x2 = x2; p.dx2 = dx2; p.o = ws.o; p.h = ws.h; p.z = ws.z; p.gm = ws.gm; p.bits = ws.bits; p.dkr = ws.dkr;
-  p.dpo = ws.dpo; p.dz = ws.dz; p.dph = ws.dph; p.We1 = w->We1; p.dWe1 = g->dWe1; p.dbe1 = g->dbe1;
-  for (int i = 0; i < w->m; ++i) {
-    p.Wh[i] = w->Wh[i]; p.Wz[i] = w->Wz[i]; p.Wo[i] = w->Wo[i];
-    p.dWh[i] = g->dWh[i]; p.dbh[i] = g->dbh[i]; p.dWz[i] = g->dWz[i]; p.dbz[i] = g->dbz[i];
-    p.dWo[i] = g->dWo[i]; p.dbo[i] = g->dbo[i];
-  }
+  const XFusionBwdParams p = xfusion_bwd_params(w, x2, dx2, G, drop_p, accumulate, ws, g);
   return launch_xfusion_group_bwd(p, st);
+}
+
+// ---- integrated gradients of the multimodal head, both fusions: mmf_mm_ig and mmf_mm_ig_tensor ------------------------
+namespace mmf {
+// The tensor fusion's buffers at S rows: encoder2's input rows and their gradient, encoder2's output, the seed table the
+// forward launches ask for (read, never used at p = 0) and the training tail's own (tmpW / tmpb are not carved: no weight
+// gradient is formed).
+struct MmIgTailWs {
+  XFusionTrainWs x;
+  float *x2, *dx2, *MM;
+  uint32_t* row_base;
+};
+static MmIgTailWs carve_mm_ig_tail(Carver& c, int m, int dim, int mmhid1, int mmhid2, int S) {
+  MmIgTailWs t{};
+  const size_t gate = (size_t)S * m * 16, K2 = (size_t)mmhid1 + (size_t)m * dim;
+  t.x2 = c.take<float>(S * K2); t.dx2 = c.take<float>(S * K2);
+  t.MM = c.take<float>((size_t)S * mmhid2); t.x.dMM = c.take<float>((size_t)S * mmhid2);
+  t.x.o = c.take<float>(gate); t.x.h = c.take<float>(gate); t.x.z = c.take<float>(gate); t.x.gm = c.take<float>(gate);
+  t.x.bits = c.take<uint32_t>((size_t)S * xfusion_bit_words(m));
+  t.x.dkr = c.take<float>((size_t)S * xfusion_elems(m));
+  t.x.dpo = c.take<float>(gate); t.x.dz = c.take<float>(gate); t.x.dph = c.take<float>(gate);
+  t.x.dpre = c.take<float>((size_t)S * mmhid2);
+  t.row_base = c.take<uint32_t>((size_t)S);
+  t.x.bytes = c.off;
+  return t;
+}
+// what the tensor fusion adds to the shape rules, for a window of S nodes: the tail's own, one embedding per modality,
+// each xf->dim wide, and the node kernel's bound on nhid
+static int mm_ig_tail_shape(const mmf_xfusion_weights* xf, int S, const int* width, int nb) {
+  if (int e = xfusion_train_shape(xf, S)) return e;
+  if (xf->m != nb) return MMF_ERR_SHAPE;
+  for (int i = 0; i < nb; ++i)
+    if (width[i] != xf->dim) return MMF_ERR_SHAPE;
+  return xf->nhid > 1024 ? MMF_ERR_SHAPE : MMF_OK;
+}
+// The tail of a window between the branches' forward and backward halves, seven launches: the gating stage, the Kronecker
+// product fused into encoder1 and encoder2 (the training forward's launches at p = 0), the node kernel (classifier[0], the
+// hazard head, the backward of risk, classifier[0]'s input gradient), encoder2's input gradient (the dense backward's dx
+// blocks), dkr and the gating stage's backward.  dx2's embedding columns then hold d risk / d v_i of every node.
+static int mm_ig_tail(const mmf_xfusion_weights* xf, const MmIgTailWs& t, const IgHeadParams& hp, int S, hipStream_t st) {
+  if (int e = xfusion_group_fwd_launches(xf, t.x2, S, 0.f, t.row_base, nullptr, t.x, t.MM, st)) return e;
+  XIgHeadParams xp{};
+  xp.hp = hp; xp.MM = t.MM; xp.Wc0 = xf->Wc0; xp.bc0 = xf->bc0; xp.dMM = t.x.dMM; xp.N2 = xf->mmhid2;
+  if (int e = launch_xfusion_ig_head(xp, S, st)) return e;
+  const int K2 = xf->mmhid1 + xf->m * xf->dim;
+  DenseBwdParams e2{t.x.dMM, t.MM, t.x2, xf->We2, t.x.dpre, t.dx2, nullptr, nullptr,
+                    S, K2, xf->mmhid2, ACT_RELU, make_drop(1, 0.f, 0, 10, nullptr), nullptr, xf->mmhid2, xf->mmhid2};
+  if (int e = launch_dense_bwd(e2, st)) return e;
+  return launch_xfusion_group_bwd_dx(xfusion_bwd_params(xf, t.x2, t.dx2, S, 0.f, 0, t.x, nullptr), st);
+}
+
+// Both fusions' call.  xf null: the concat head -- the embeddings side by side in feat [S x F], one head launch over them.
+// xf given: the tensor fusion -- the embeddings in their columns of encoder2's input rows x2 [S x K2], mm_ig_tail between
+// the halves.  Everything else is the same code.
+static int mm_ig_call(const mmf_mm_ig_desc* mm, const mmf_xfusion_weights* xf, bool tensor, void* workspace,
+                      size_t workspace_bytes, const mmf_surv_head* head, void* stream) {
+  // MMF_ERR_ARG
+  if (!mm || !head || !head->Wk || !head->bk) return MMF_ERR_ARG;
+  if (mm->n_steps < 1 || mm->n_steps > GROUP_MAX || mm->window_steps < 0 || !mm->alpha || !mm->weight) return MMF_ERR_ARG;
+  if (!mm->risk_x || !mm->risk_base || !mm->step_risk) return MMF_ERR_ARG;
+  const mmf_amil_desc *dp = mm->path, *dr = mm->radio;
+  const mmf_radio_reduce* rd = mm->rd;
+  const bool omic = mm->omic_x != nullptr;
+  if ((dp != nullptr) + (dr != nullptr) + (omic ? 1 : 0) < 2) return MMF_ERR_ARG;
+  int radio_shape = MMF_OK;                          // nseg outside 2..4: refused behind every null pointer
+  if (dp) {
+    if (!mm->path_x) return MMF_ERR_ARG;
+    if (int e = mm_ig_stack_args(dp, mm->path_row_sum, mm->path_row_abs)) return e;
+  }
+  if (dr) {
+    if (int e = mm_ig_stack_args(dr, mm->radio_row_sum, mm->radio_row_abs)) return e;
+    radio_shape = radio_ig_args(rd);
+    if (radio_shape == MMF_ERR_ARG) return radio_shape;
+  }
+  if (omic && (!mm->omic_W0 || !mm->omic_b0 || !mm->omic_W1 || !mm->omic_b1 || !mm->omic_attr)) return MMF_ERR_ARG;
+  if (dp)
+    if (int e = check_desc(dp); e == MMF_ERR_ARG) return e;
+  if (dr)
+    if (int e = check_desc(dr); e == MMF_ERR_ARG) return e;
+  if (tensor) {
+    if (!xf) return MMF_ERR_ARG;
+    if (int e = xfusion_weights_args(xf)) return e;
+  }
+  // MMF_ERR_SHAPE
+  if (radio_shape) return radio_shape;
+  int col[3], width[3], nb = 0;
+  if (dp) {
+    if (int e = check_desc(dp)) return e;
+    col[nb] = mm->path_col; width[nb++] = dp->H;
+  }
+  if (dr) {
+    if (int e = check_desc(dr)) return e;
+    if (rd->kseg != dr->L) return MMF_ERR_SHAPE;
+    if (dr->N * rd->nseg * (int64_t)rd->kseg * 4 >= (int64_t)1 << 31) return MMF_ERR_SHAPE;
+    col[nb] = mm->radio_col; width[nb++] = dr->H;
+  }
+  if (omic) {
+    if (mm->omic_Gin < 1 || mm->omic_W0n < 1 || mm->omic_W0n > 1024 || mm->omic_We < 1) return MMF_ERR_SHAPE;
+    col[nb] = mm->omic_col; width[nb++] = mm->omic_We;
+  }
+  const int steps = mm_ig_steps(dp ? dp->N : 0, dp ? dp->H : 0, dp ? dp->D : 0, dr ? dr->N : 0, dr ? dr->H : 0,
+                                dr ? dr->D : 0, mm->n_steps + 2, mm->window_steps);
+  int64_t F64 = 0;
+  for (int i = 0; i < nb; ++i) F64 += width[i];
+  if (steps < 1) return MMF_ERR_SHAPE;
+  if (tensor) {
+    if (int e = mm_ig_tail_shape(xf, steps, width, nb)) return e;        // bounds F: every width is xf->dim, K2 <= 1536
+  } else if (F64 > 1024) return MMF_ERR_SHAPE;
+  const int F = (int)F64;                            // the embeddings' columns: the fused row, or m dim of x2's K2
+  if (!mm_ig_columns(col, width, nb, F)) return MMF_ERR_SHAPE;
+  if (head->K < 1 || head->K > 32) return MMF_ERR_SHAPE;
+  // MMF_ERR_ALIGN
+  if (!workspace) return MMF_ERR_ARG;
+  if (dp) {
+    if (int e = check_operands(dp, mm->path_x, workspace, mm->path_row_sum, false)) return e;
+    if (mm->path_attr && !aligned16(mm->path_attr)) return MMF_ERR_ALIGN;
+  }
+  if (dr) {
+    if (int e = radio_operands(dr, rd, false)) return e;
+    if (int e = check_operands(dr, rd->x[0], workspace, mm->radio_row_sum, false)) return e;
+    if (mm->radio_attr && !aligned16(mm->radio_attr)) return MMF_ERR_ALIGN;
+  }
+  if (!aligned16(workspace)) return MMF_ERR_ALIGN;
+  if (tensor)
+    if (int e = xfusion_weights_aligned(xf)) return e;
+  Carver c(workspace);
+  const MmIgWs w = carve_mm_ig(c, dp ? dp->N : 0, dp ? dp->L : 0, dp ? dp->H : 0, dp ? dp->D : 0, dp ? dp->gated : 0,
+                               dr ? dr->N : 0, dr ? rd->nseg : 0, dr ? rd->kseg : 0, dr ? dr->H : 0, dr ? dr->D : 0,
+                               dr ? dr->gated : 0, omic ? mm->omic_Gin : 0, mm->omic_W0n, mm->omic_We, tensor ? 0 : F, steps);
+  MmIgTailWs t{};
+  if (tensor) t = carve_mm_ig_tail(c, xf->m, xf->dim, xf->mmhid1, xf->mmhid2, steps);
+  if (c.off > workspace_bytes) return MMF_ERR_WORKSPACE;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  TraceScope ts(dp && dp->trace ? dp->trace : dr ? dr->trace : nullptr);   // either stack's descriptor may carry it
+  // where the embeddings of a window stand, and their gradient: S rows, `ld` floats apart
+  float* emb = tensor ? t.x2 + xf->mmhid1 : w.feat;
+  const float* demb = tensor ? t.dx2 + xf->mmhid1 : w.dfeat;
+  const int ld = tensor ? xf->mmhid1 + F : F;
+
+  // 1. once per call
+  mmf_amil_desc db{};                                // the radiology stack behind reduce_dim
+  IgOmicParams op{};
+  if (dp)
+    if (int e = ig_project(dp, mm->path_x, w.gp, st)) return e;
+  if (dr)
+    if (int e = radio_ig_project(dr, rd, w.gr, db, st)) return e;
+  if (omic) {
+    op.x = mm->omic_x; op.W0 = mm->omic_W0; op.b0 = mm->omic_b0; op.W1 = mm->omic_W1; op.b1 = mm->omic_b1;
+    op.Gin = mm->omic_Gin; op.W0n = mm->omic_W0n; op.We = mm->omic_We;
+    op.Z = w.Z; op.z1 = w.z1; op.z2 = w.z2; op.dz1 = w.dz1; op.Gz = w.Gz;
+    op.feat = emb; op.dfeat = demb; op.F = ld; op.col = mm->omic_col; op.attr = mm->omic_attr;
+    if (int e = launch_ig_omic(IG_OMIC_Z, op, st)) return e;
+  }
+  // 2. the windows
+  const IgNodes q = ig_nodes(mm->n_steps, mm->alpha, mm->weight);
+  IgHeadParams hp = ig_head_params(head, tensor ? xf->nhid : F, q.n, mm->step_risk, mm->risk_x, mm->risk_base);
+  if (!tensor) { hp.M = w.feat; hp.dM = w.dfeat; }
+  for (int q0 = 0; q0 < q.total; q0 += steps) {
+    const int S = q.total - q0 < steps ? q.total - q0 : steps;
+    const int nfold = ig_nfold(q, q0, S);
+    const bool first = q0 == 0;
+    const IgSteps sw = ig_steps(q, q0, S);
+    if (dp)
+      if (int e = ig_window_fwd(dp, w.gp, sw, emb + mm->path_col, ld, st)) return e;
+    if (dr)
+      if (int e = ig_window_fwd(&db, w.gr.g, sw, emb + mm->radio_col, ld, st)) return e;
+    if (omic) {
+      op.st = sw;
+      if (int e = launch_ig_omic(IG_OMIC_FWD, op, st)) return e;
+    }
+    hp.step0 = q0;
+    if (tensor) {
+      if (int e = mm_ig_tail(xf, t, hp, S, st)) return e;
+    } else if (int e = launch_ig_head(hp, S, st)) return e;
+    if (dp) {
+      if (int e = launch_group_dm_gather(demb + mm->path_col, ld, w.gp.dM, S, dp->H, st)) return e;
+      if (int e = ig_window_bwd(dp, w.gp, sw, w.gp.dM, nfold, first, st)) return e;
+    }
+    if (dr) {
+      if (int e = launch_group_dm_gather(demb + mm->radio_col, ld, w.gr.g.dM, S, dr->H, st)) return e;
+      if (int e = ig_window_bwd(&db, w.gr.g, sw, w.gr.g.dM, nfold, first, st)) return e;
+    }
+    if (omic) {
+      if (int e = launch_ig_omic(IG_OMIC_BWD, op, st)) return e;
+      op.st.S = nfold; op.first = first ? 1 : 0;
+      if (int e = launch_ig_omic(IG_OMIC_FOLD, op, st)) return e;
+    }
+  }
+  // 3. once per call
+  if (dp)
+    if (int e = ig_attr(dp, mm->path_x, w.gp, mm->path_row_sum, mm->path_row_abs, mm->path_attr, st)) return e;
+  if (dr)
+    if (int e = radio_ig_attr(dr, rd, w.gr, mm->radio_row_sum, mm->radio_row_abs, mm->radio_attr, st)) return e;
+  if (omic)
+    if (int e = launch_ig_omic(IG_OMIC_ATTR, op, st)) return e;
+  return MMF_OK;
+}
+}  // namespace mmf
+
+int mmf_mm_ig(const mmf_mm_ig_desc* mm, void* workspace, size_t workspace_bytes, const mmf_surv_head* head, void* stream) {
+  return mm_ig_call(mm, nullptr, false, workspace, workspace_bytes, head, stream);
+}
+
+size_t mmf_mm_ig_tensor_workspace_bytes(int64_t N_p, int32_t L_p, int32_t H_p, int32_t D_p, int32_t gated_p, int64_t N_r,
+                                        int32_t nseg, int32_t kseg, int32_t H_r, int32_t D_r, int32_t gated_r, int32_t Gin,
+                                        int32_t W0, int32_t We, int32_t n_steps, int32_t window_steps, int32_t dim,
+                                        int32_t sdim, int32_t mmhid1, int32_t mmhid2, int32_t nhid) {
+  if (n_steps < 1 || n_steps > GROUP_MAX || window_steps < 0 || N_p < 0 || N_r < 0 || Gin < 0) return 0;
+  mmf_xfusion_weights xf{};
+  xf.m = (N_p > 0) + (N_r > 0) + (Gin > 0); xf.dim = dim; xf.sdim = sdim; xf.mmhid1 = mmhid1; xf.mmhid2 = mmhid2;
+  xf.nhid = nhid;
+  if (xf.m < 2) return 0;
+  int width[3], nb = 0;
+  if (N_p > 0) {
+    if (!mmf_amil_ig_workspace_bytes(N_p, L_p, H_p, D_p, gated_p, n_steps, window_steps)) return 0;
+    width[nb++] = H_p;
+  }
+  if (N_r > 0) {
+    if (!mmf_radio_ig_workspace_bytes(N_r, nseg, kseg, H_r, D_r, gated_r, n_steps, window_steps)) return 0;
+    width[nb++] = H_r;
+  }
+  if (Gin > 0) {
+    if (W0 < 1 || W0 > 1024 || We < 1) return 0;
+    width[nb++] = We;
+  }
+  const int steps = mm_ig_steps(N_p, H_p, D_p, N_r, H_r, D_r, n_steps + 2, window_steps);
+  if (steps < 1 || mm_ig_tail_shape(&xf, steps, width, nb)) return 0;
+  Carver c;
+  carve_mm_ig(c, N_p, L_p, H_p, D_p, gated_p, N_r, nseg, kseg, H_r, D_r, gated_r, Gin, W0, We, 0, steps);
+  carve_mm_ig_tail(c, xf.m, dim, mmhid1, mmhid2, steps);
+  return c.off;
+}
+
+int mmf_mm_ig_tensor(const mmf_mm_ig_desc* mm, const mmf_xfusion_weights* xf, void* workspace, size_t workspace_bytes,
+                     const mmf_surv_head* head, void* stream) {
+  return mm_ig_call(mm, xf, true, workspace, workspace_bytes, head, stream);
 }
 
 // ---- standalone attention scorer: Attn_Net / Attn_Net_Gated .forward(x) -> (A, x) ------------------------------

@@ -396,6 +396,16 @@ struct IgHeadParams {
   int64_t* Y_hat;                       // [1] or null
 };
 int launch_ig_head(const IgHeadParams& p, int S, hipStream_t st);
+// The tensor fusion's node launch (mmf_mm_ig_tensor), one workgroup per node s of the window: hid = relu(Wc0 MM_s + bc0)
+// kept in LDS, the hazard head over it and the backward of risk (hp, whose H is nhid <= 1024 and whose M / dM are not
+// read), dpre0 = dhid . [hid > 0], dMM_s = dpre0 . Wc0 into dMM [S x N2].  MM [S x N2], Wc0 [nhid x N2], N2 <= 1536.
+struct XIgHeadParams {
+  IgHeadParams hp;
+  const float *MM, *Wc0, *bc0;
+  float* dMM;
+  int N2;
+};
+int launch_xfusion_ig_head(const XIgHeadParams& p, int S, hipStream_t st);
 // G[i, :] (first: =, else +=) sum_s w[s] * du[s * N + i, :] over the first st.S steps of the window, in step order
 struct IgFoldParams { const float* du; float* G; int64_t N; int H; int first; IgSteps st; };
 int launch_ig_fold(const IgFoldParams& p, hipStream_t st);

@@ -133,6 +133,9 @@ struct XFusionBwdParams {
   float *dWh[3], *dbh[3], *dWz[3], *dbz[3], *dWo[3], *dbo[3];
 };
 int launch_xfusion_group_bwd(XFusionBwdParams p, hipStream_t st);
+// its two input-gradient launches alone (mmf_mm_ig_tensor): dkr, then the gating stage's backward, which still writes dpo,
+// dz and dph; We1's and the gating stage's weight gradients are neither launched nor read (dW*, db* may be null)
+int launch_xfusion_group_bwd_dx(XFusionBwdParams p, hipStream_t st);
 int launch_add_into(float* out, const float* in, int64_t n, hipStream_t st);
 }  // namespace mmf
 

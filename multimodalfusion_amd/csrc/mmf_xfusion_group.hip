@@ -242,23 +242,42 @@ int launch_add_into(float* out, const float* in, int64_t n, hipStream_t st) {
   return launched();
 }
 
-int launch_xfusion_group_bwd(XFusionBwdParams p, hipStream_t st) {
+static int xfusion_bwd_check(const XFusionBwdParams& p) {
   if (p.m < 2 || p.m > 3 || p.G < 1 || p.G > GROUP_MAX || p.N1 < 1 || p.dim < 1 || p.K2 != p.N1 + p.m * p.dim) return MMF_ERR_SHAPE;
-  const int E = p.m == 3 ? XB_S1 * XB_S1 * XB_S1 : XB_S1 * XB_S1;
+  return MMF_OK;
+}
+static inline int xfusion_elems_of(int m) { return m == 3 ? XB_S1 * XB_S1 * XB_S1 : XB_S1 * XB_S1; }
+static int launch_kron_dense_dkr(const XFusionBwdParams& p, hipStream_t st) {
+  const int E = xfusion_elems_of(p.m);
   { ProfScope ps("kron_dense_dkr_group_kernel", st);
     hipLaunchKernelGGL(kron_dense_dkr_group_kernel, dim3(cdiv(E, 64), cdiv(p.G, XB_PG)), dim3(256), 0, st, p, E); }
-  if (int e = launched()) return e;
+  return launched();
+}
+static int launch_xgate_bwd(const XFusionBwdParams& p, hipStream_t st) {
+  { ProfScope ps("xgate_bwd_group_kernel", st); hipLaunchKernelGGL(xgate_bwd_group_kernel, dim3(p.G), dim3(1024), 0, st, p); }
+  return launched();
+}
+
+int launch_xfusion_group_bwd(XFusionBwdParams p, hipStream_t st) {
+  if (int e = xfusion_bwd_check(p)) return e;
+  const int E = xfusion_elems_of(p.m);
+  if (int e = launch_kron_dense_dkr(p, st)) return e;
   { ProfScope ps("kron_dense_dw_group_kernel", st);
     const dim3 grid(cdiv(E, 256), cdiv(p.N1, XB_ROWS));
     if (p.m == 3) hipLaunchKernelGGL(kron_dense_dw_group_kernel<3>, grid, dim3(256), 0, st, p);
     else hipLaunchKernelGGL(kron_dense_dw_group_kernel<2>, grid, dim3(256), 0, st, p); }
   if (int e = launched()) return e;
-  { ProfScope ps("xgate_bwd_group_kernel", st); hipLaunchKernelGGL(xgate_bwd_group_kernel, dim3(p.G), dim3(1024), 0, st, p); }
-  if (int e = launched()) return e;
+  if (int e = launch_xgate_bwd(p, st)) return e;
   const int S = XB_S1 - 1, per = S * p.dim + S * p.m * p.dim + S * S + 3 * S;
   { ProfScope ps("xgate_dw_group_kernel", st);
     hipLaunchKernelGGL(xgate_dw_group_kernel, dim3(cdiv((int64_t)p.m * per, 256)), dim3(256), 0, st, p); }
   return launched();
+}
+
+int launch_xfusion_group_bwd_dx(XFusionBwdParams p, hipStream_t st) {
+  if (int e = xfusion_bwd_check(p)) return e;
+  if (int e = launch_kron_dense_dkr(p, st)) return e;
+  return launch_xgate_bwd(p, st);
 }
 
 }  // namespace mmf

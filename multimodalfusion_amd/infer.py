@@ -286,9 +286,10 @@ def mm_integrated_gradients_autograd(model, features, alphas, weights):
 
 def attribute_modalities(model, features, n_steps=20, method="gausslegendre", return_full=False, top_k=None):
     """How much of one patient's predicted risk comes from radiology, pathology and omics, create_attributions.py:93-164:
-    integrated gradients of the risk from a joint zero baseline in one fused call (model.integrated_gradients;
-    `modality_abs` holds the reference's radio_attr, path_attr and omic_attr, `share` their fractions).  features: what
-    forward takes for model.mode.  The model is put in eval mode for the call and restored.  Returns the
+    integrated gradients of the risk from a joint zero baseline in one fused call (model.integrated_gradients, or
+    model.integrated_gradients_tensor for fusion='tensor'; `modality_abs` holds the reference's radio_attr, path_attr and
+    omic_attr, `share` their fractions).  features: what forward takes for model.mode.  The model is put in eval mode for
+    the call and restored.  Returns the
     ModalityAttribution, or with top_k the triple (ModalityAttribution, indices of the top_k patches by patch_abs, indices
     of the top_k slices by sum_m inst_abs), largest first, None for an absent branch."""
     from .models.model_mm_attention_mil import MM_MIL_Attention_fc_surv
@@ -296,8 +297,8 @@ def attribute_modalities(model, features, n_steps=20, method="gausslegendre", re
         raise NotImplementedError("attribute_modalities serves the multimodal head")
     dev = _dev(model)
     feats = {k: (v.to(dev) if torch.is_tensor(v) else v) for k, v in features.items()}
-    out = _attribute_in_eval(model, lambda: model.integrated_gradients(
-        n_steps=n_steps, method=method, return_full=return_full, **feats), None, None)
+    call = model.integrated_gradients_tensor if model.fusion == "tensor" else model.integrated_gradients
+    out = _attribute_in_eval(model, lambda: call(n_steps=n_steps, method=method, return_full=return_full, **feats), None, None)
     if top_k is None:
         return out
     top = lambda s: None if s is None else torch.topk(s, min(int(top_k), int(s.numel()))).indices

@@ -634,16 +634,36 @@ class MM_MIL_Attention_fc_surv(MM_MIL_Attention_fc):
         (ops.mm_integrated_gradients) -- what the reference's create_attributions.py:93-164 gets from captum through n_steps
         autograd passes of the whole forward.  features: what forward takes for self.mode ({modality: [N_r x k]},
         path_features [N_p x L], genomic_features [G] or [1 x G]), fp32; method, window_steps as
-        MIL_Attention_fc_surv_path.integrated_gradients.  fusion='concat', eval mode, the stock head only.
+        MIL_Attention_fc_surv_path.integrated_gradients.  fusion='concat' (fusion='tensor': integrated_gradients_tensor),
+        eval mode, the stock head only.
         Returns ModalityAttribution: modality_attr / modality_abs {radio, path, omic} (the abs values are the reference's
         radio_attr, path_attr, omic_attr), share = modality_abs / their sum, patch_attr / patch_abs [N_p], inst_attr /
         inst_abs [n_mod x N_r], sequence_abs [n_mod], gene_attr [G], total, total_abs, risk, risk_baseline,
         delta = total - (risk - risk_baseline), step_risk [n_steps], hazards, S, Y_hat at alpha = 1, and with return_full
         attr {radio: [n_mod x N_r x k], path: [N_p x L], omic: [G]}.  The fields of an absent branch are None."""
-        MmfError = ops._lib.MmfError
         if self.fusion == "tensor":
-            raise NotImplementedError("integrated_gradients covers fusion='concat' (the tensor fusion needs an "
-                                      "input-gradient-only XlinearFusion tail)")
+            raise NotImplementedError("integrated_gradients covers fusion='concat'; a tensor-fusion model has "
+                                      "integrated_gradients_tensor")
+        return self._integrated_gradients(False, n_steps, method, return_full, window_steps, features)
+
+    def integrated_gradients_tensor(self, n_steps=20, method="gausslegendre", return_full=False, window_steps=0, **features):
+        """integrated_gradients for fusion='tensor', the default: the same question, arguments and ModalityAttribution, in ONE
+        C-ABI call (ops.mm_integrated_gradients with xfusion) -- per window of nodes the XlinearFusion block, classifier[0],
+        the hazard head and their input gradients run as seven launches between the branches' halves, and no weight
+        gradient is formed.  The XlinearFusion configuration nll_step_group_tensor takes (skip, scale width 16), eval mode,
+        the stock head only; a concat model has integrated_gradients."""
+        if self.fusion != "tensor":
+            raise NotImplementedError("integrated_gradients_tensor covers fusion='tensor'; a concat model has "
+                                      "integrated_gradients")
+        if not self.xfusion_group_ok():
+            raise NotImplementedError("integrated_gradients_tensor covers the XlinearFusion configuration the heads use "
+                                      "(skip, scale width 16)")
+        return self._integrated_gradients(True, n_steps, method, return_full, window_steps, features)
+
+    def _integrated_gradients(self, tensor, n_steps, method, return_full, window_steps, features):
+        """The one body of integrated_gradients and integrated_gradients_tensor: the refusals, the branches' operands, the
+        call and the ModalityAttribution."""
+        MmfError = ops._lib.MmfError
         order, _, _ = self._concat_layout()
         need = {"radio": list(self.modalities), "path": ["path_features"], "omic": ["genomic_features"]}
         missing = [k for b in order for k in need[b] if features.get(k) is None]
@@ -671,9 +691,13 @@ class MM_MIL_Attention_fc_surv(MM_MIL_Attention_fc):
                 branches.append(("omic", x.reshape(-1), l0.weight, l0.bias, l1.weight, l1.bias))
         alphas, weights = ops.ig_quadrature(method, n_steps)
         with torch.no_grad():
+            head, xfusion = self.classifier, None
+            if tensor:
+                c0, head = self.classifier[0], self.classifier[3]
+                xfusion = (self._xfusion_weights(len(order)), c0.weight, c0.bias)
             out, risk, base, step_risk, (hazards, S, Y_hat) = ops.mm_integrated_gradients(
-                branches, self.classifier.weight, self.classifier.bias, alphas, weights, want_attr=return_full,
-                window_steps=window_steps)
+                branches, head.weight, head.bias, alphas, weights, want_attr=return_full, window_steps=window_steps,
+                xfusion=xfusion)
             f = dict.fromkeys(("patch_attr", "patch_abs", "inst_attr", "inst_abs", "sequence_abs", "gene_attr"))
             m_attr, m_abs, full = dict.fromkeys(need), dict.fromkeys(need), dict.fromkeys(need)
             if "path" in out:

@@ -831,7 +831,7 @@ def radio_integrated_gradients(xs, Wr, br, stack, Wk, bk, gated, alphas, weights
                                  bk, alphas, weights, want_attr, window_steps, xs[0].device)
 
 
-def mm_integrated_gradients(branches, Wk, bk, alphas, weights, want_attr=False, window_steps=0):
+def mm_integrated_gradients(branches, Wk, bk, alphas, weights, want_attr=False, window_steps=0, xfusion=None):
     """Integrated gradients of the multimodal concat head's risk = -sum(S) with respect to every input of every branch, from
     a joint zero baseline, in ONE C-ABI call (include/mmf_amil.h: mmf_mm_ig): the L-wide contractions, reduce_dim and
     W_o0 x_o run once, the H-wide part of each stack, the omic hidden layers and one head launch once per node.
@@ -840,7 +840,11 @@ def mm_integrated_gradients(branches, Wk, bk, alphas, weights, want_attr=False, 
     it; alphas, weights, want_attr, window_steps as amil_integrated_gradients.  Returns ({"path": (row_sum [N], row_abs
     [N], attr [N x L] or None), "radio": (row_sum [nseg x N], row_abs [nseg x N], attr [nseg x N x k] or None), "omic":
     attr [Gin]} for the branches given, risk_x [1], risk_base [1], step_risk [n_steps], (hazards [1 x K], S [1 x K],
-    Y_hat [1 x 1]) at alpha = 1)."""
+    Y_hat [1 x 1]) at alpha = 1).
+    xfusion = (weights, Wc0, bc0): the tensor-fusion head instead (mmf_mm_ig_tensor) -- the XlinearFusion weights as xfusion
+    takes them and classifier[0]; every branch's embedding is dim wide, the branches stand in the order of the fusion's
+    v_list, Wk [K x nhid], bk are classifier[3], and the tail (seven launches) runs once per window between the branches'
+    halves, without a weight gradient."""
     import numpy as np
     a = np.ascontiguousarray(np.asarray(alphas, dtype=np.float64).astype(np.float32))
     w = np.ascontiguousarray(np.asarray(weights, dtype=np.float64).astype(np.float32))
@@ -912,20 +916,34 @@ def mm_integrated_gradients(branches, Wk, bk, alphas, weights, want_attr=False, 
             F += W1.shape[0]
     Wk, bk = _f32c(Wk), _f32c(bk)
     K = Wk.shape[0]
+    name, xw, tail = "mmf_mm_ig", None, ()
+    if xfusion is not None:
+        name = "mmf_mm_ig_tensor"
+        xweights, Wc0, bc0 = xfusion
+        m = len(branches)
+        if F % m != 0:
+            raise _lib.MmfError(f"{name}: the {m} embeddings must be equally wide, the fused row has {F} columns")
+        xw, xkeep, (sdim, mmhid1, mmhid2, nhid) = _xfusion_operands(m, 1, F // m, xweights, Wc0, bc0, name)
+        keep += xkeep
+        tail, F = (F // m, sdim, mmhid1, mmhid2, nhid), nhid
     if Wk.dim() != 2 or Wk.shape[1] != F or tuple(bk.shape) != (K,) or K > 32:
-        raise _lib.MmfError(f"the hazard head must be [K <= 32 x {F}] over the fused row, got {tuple(Wk.shape)}")
+        raise _lib.MmfError(f"the hazard head must be [K <= 32 x {F}] over the {'fused row' if xw is None else 'hidden layer'}, "
+                            f"got {tuple(Wk.shape)}")
     l = lib()
-    nbytes = l.mmf_mm_ig_workspace_bytes(q["Np"], q["Lp"], q["Hp"], q["Dp"], q["gp"], q["Nr"], q["nseg"], q["kseg"], q["Hr"],
-                                         q["Dr"], q["gr"], q["Gin"], q["W0"], q["We"], n, int(window_steps))
+    nbytes = getattr(l, name + "_workspace_bytes")(q["Np"], q["Lp"], q["Hp"], q["Dp"], q["gp"], q["Nr"], q["nseg"], q["kseg"],
+                                                   q["Hr"], q["Dr"], q["gr"], q["Gin"], q["W0"], q["We"], n,
+                                                   int(window_steps), *tail)
     if nbytes == 0:
-        raise _lib.MmfError("mmf_mm_ig: n_steps, window_steps, a branch's widths, the fused width or a bag's size out of range")
+        raise _lib.MmfError(f"{name}: n_steps, window_steps, a branch's widths, the fused width{'' if xw is None else ', the tail'} "
+                            "or a bag's size out of range")
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     risks = torch.empty(2 + n, dtype=torch.float32, device=dev)
     hz = torch.empty((2, 1, K), dtype=torch.float32, device=dev)
     Y_hat = torch.empty((1, 1), dtype=torch.int64, device=dev)
     mm.risk_x, mm.risk_base, mm.step_risk = ptr(risks[0:1]), ptr(risks[1:2]), ptr(risks[2:])
     sh = SurvHead(Wk=ptr(Wk), bk=ptr(bk), K=K, logits=None, hazards=ptr(hz[0]), S=ptr(hz[1]), Y_hat=ptr(Y_hat), risk=None)
-    check(l.mmf_mm_ig(C.byref(mm), ptr(ws), nbytes, C.byref(sh), stream_ptr()), "mmf_mm_ig")
+    lead = (C.byref(mm),) if xw is None else (C.byref(mm), C.byref(xw))
+    check(getattr(l, name)(*lead, ptr(ws), nbytes, C.byref(sh), stream_ptr()), name)
     return out, risks[0:1], risks[1:2], risks[2:], (hz[0], hz[1], Y_hat)
 
 

@@ -11,7 +11,11 @@ vector, every first-layer bias ~ N(0, 0.1); ROWS are (N_p, N_r) pairs; the yards
 infer.mm_integrated_gradients_autograd (required: ratio < 1 everywhere); `single_heads_ms`: mmf_amil_ig on the pathology bag
 plus mmf_radio_ig on the radiology bags in the same process, each with the classifier's columns of its branch as its head,
 and `vs_single_heads` = fused / that sum (reported, not gated); `*_max_rel_diff`: modality_abs, patch_abs, inst_abs.
-usage: ig_bench.py [--head path|radio|mm] [ROWS ...]   (default rows: 1000 10000 50000, radio 150 512 4096, mm 1000 150
+--head mm --fusion tensor: the tensor-fusion head (one mmf_mm_ig_tensor) on a fusion='tensor' model, every first-layer bias
+~ N(0, 0.1) again; the yardstick is the same autograd route on that model (required: ratio < 1 everywhere); `concat_ms`:
+mmf_mm_ig on a concat model over the same inputs in the same process, and `tail_ms` = fused - concat, what the fusion tail
+costs (reported, not gated).
+usage: ig_bench.py [--head path|radio|mm] [--fusion concat|tensor] [ROWS ...]   (default rows: 1000 10000 50000, radio 150 512 4096, mm 1000 150
 10000 512 50000 512);
 env IG_BENCH_ITERS (default 5), IG_BENCH_STEPS (default 20)"""
 import argparse, json, os, statistics, sys
@@ -58,7 +62,7 @@ def timed_alternating(routes):
     return [statistics.median(r) for r in runs]
 
 
-def main_mm(rows, iters, steps):
+def main_mm(rows, iters, steps, fusion="concat"):
     from multimodalfusion_amd.models.model_mm_attention_mil import MM_MIL_Attention_fc_surv
     from multimodalfusion_amd.models.model_modules import stack_args
     rows = rows or [1000, 150, 10000, 512, 50000, 512]
@@ -66,12 +70,17 @@ def main_mm(rows, iters, steps):
         sys.exit("--head mm takes (N_p, N_r) pairs")
     dev = torch.device("cuda", 0)
     torch.manual_seed(0)
-    with torch.no_grad():
-        model = MM_MIL_Attention_fc_surv(input_dim=80, fusion="concat", dropout=False, n_classes=4,
-                                         mode="radio_path_omic").to(dev).eval()
-        for b in (model.attention_net_WSI[0].bias, model.attention_net_radio[0].bias, model.reduce_dim.bias,
-                  model.fc_omic[0][0].bias, model.fc_omic[1][0].bias):
-            b.normal_(0.0, 0.1)
+
+    def make(fusion):
+        with torch.no_grad():
+            m = MM_MIL_Attention_fc_surv(input_dim=80, fusion=fusion, dropout=False, n_classes=4, mode="radio_path_omic").to(dev).eval()
+            for b in (m.attention_net_WSI[0].bias, m.attention_net_radio[0].bias, m.reduce_dim.bias, m.fc_omic[0][0].bias,
+                      m.fc_omic[1][0].bias):
+                b.normal_(0.0, 0.1)
+        return m
+
+    model = make("concat")
+    tensor = make("tensor") if fusion == "tensor" else None
     gen = torch.Generator(device=dev); gen.manual_seed(7)
     a, w = (v.astype(np.float32) for v in ops.ig_quadrature("gausslegendre", steps))
     _, cols, _ = model._concat_layout()
@@ -88,32 +97,39 @@ def main_mm(rows, iters, steps):
         def fused():
             return model.integrated_gradients(n_steps=steps, **feats)
 
+        def fused_tensor():
+            return tensor.integrated_gradients_tensor(n_steps=steps, **feats)
+
         def autograd():
-            return infer.mm_integrated_gradients_autograd(model, feats, a, w)
+            return infer.mm_integrated_gradients_autograd(tensor or model, feats, a, w)
 
         def single_heads():
             with torch.no_grad():
                 ops.amil_integrated_gradients(feats["path_features"], sp, Wk_p, bk, gp, a, w)
                 ops.radio_integrated_gradients(xs, model.reduce_dim.weight, model.reduce_dim.bias, sr, Wk_r, bk, gr, a, w)
 
-        f, (g, *_) = fused(), autograd()
+        f, (g, *_) = (fused_tensor if tensor else fused)(), autograd()
         torch.cuda.synchronize()
         ref = {"path": g["path"].abs().sum(1), "radio": g["radio"].abs().sum(2)}
         mod = {b: float(v.abs().sum()) for b, v in g.items()}
         err = {"modality_abs": max(abs(float(f.modality_abs[b]) - mod[b]) / mod[b] for b in mod),
                "patch_abs": float((f.patch_abs - ref["path"]).abs().max() / ref["path"].max()),
                "inst_abs": float((f.inst_abs - ref["radio"]).abs().max() / ref["radio"].max())}
-        t_f, t_a, t_s = timed_alternating([(fused, iters), (autograd, max(1, iters // 2)), (single_heads, iters)])
+        if tensor:                    # (a) the fused call, (b) the autograd passes on the same model, (c) mmf_mm_ig on a concat model
+            t_f, t_a, t_c = timed_alternating([(fused_tensor, iters), (autograd, max(1, iters // 2)), (fused, iters)])
+            other = {"concat_ms": round(t_c, 4), "tail_ms": round(t_f - t_c, 4)}
+        else:
+            t_f, t_a, t_s = timed_alternating([(fused, iters), (autograd, max(1, iters // 2)), (single_heads, iters)])
+            other = {"single_heads_ms": round(t_s, 4), "vs_single_heads": round(t_f / t_s, 4)}
         trace = _lib.KernelTrace()
         with trace:
-            fused()
+            (fused_tensor if tensor else fused)()
             torch.cuda.synchronize()
         kernels = {k: [c, round(ms, 4)] for k, (c, ms) in sorted(trace.dump().items(), key=lambda kv: -kv[1][1])}
         trace.close()
         ratio = t_f / t_a
-        print(json.dumps({"rows": [Np, Nr], "modalities": len(MODS), "n_steps": steps, "fused_ms": round(t_f, 4),
-                          "autograd_ms": round(t_a, 4), "ratio": round(ratio, 4), "required": 1.0, "ok": ratio < 1.0,
-                          "single_heads_ms": round(t_s, 4), "vs_single_heads": round(t_f / t_s, 4),
+        print(json.dumps({"rows": [Np, Nr], "modalities": len(MODS), "n_steps": steps, "fusion": fusion, "fused_ms": round(t_f, 4),
+                          "autograd_ms": round(t_a, 4), "ratio": round(ratio, 4), "required": 1.0, "ok": ratio < 1.0, **other,
                           **{k + "_max_rel_diff": float(f"{v:.3e}") for k, v in err.items()},
                           "share": {b: round(float(v), 4) for b, v in f.share.items()}, "kernels": kernels}), flush=True)
 
@@ -121,10 +137,14 @@ def main_mm(rows, iters, steps):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--head", choices=["path", "radio", "mm"], default="path")
+    ap.add_argument("--fusion", choices=["concat", "tensor"], default="concat")
     ap.add_argument("rows", nargs="*", type=int)
     args = ap.parse_args()
+    if args.fusion == "tensor" and args.head != "mm":
+        sys.exit("--fusion tensor goes with --head mm")
     if args.head == "mm":
-        return main_mm(args.rows, int(os.environ.get("IG_BENCH_ITERS", "5")), int(os.environ.get("IG_BENCH_STEPS", "20")))
+        return main_mm(args.rows, int(os.environ.get("IG_BENCH_ITERS", "5")), int(os.environ.get("IG_BENCH_STEPS", "20")),
+                       args.fusion)
     radio = args.head == "radio"
     rows = args.rows or ([150, 512, 4096] if radio else [1000, 10000, 50000])
     iters = int(os.environ.get("IG_BENCH_ITERS", "5"))
