@@ -446,7 +446,7 @@ int mmf_radio_ig(const mmf_amil_desc* desc, const mmf_radio_reduce* rd, void* wo
  *   what mmf_amil_ig_workspace_bytes / mmf_radio_ig_workspace_bytes answer 0 for, W0 outside 1..1024, We < 1 or
  *   F > 1024.  It does not shrink as window_steps grows.
  * fusion = 'tensor' has mmf_mm_ig_tensor (below, behind mmf_xfusion_weights).  Out of scope: radio_fusion = 'tensor'; non-zero
- *   baselines; bf16 bags; targets other than risk; the stage-2 pretrained models; the omic-only MaxNet.
+ *   baselines; bf16 bags; targets other than risk; the omic-only MaxNet.  The stage-2 pretrained models have mmf_stage2_ig.
  * ------------------------------------------------------------------------------------------- */
 typedef struct mmf_mm_ig_desc {
   int32_t n_steps;               /* quadrature nodes, 1 .. MMF_GROUP_MAX */
@@ -678,8 +678,8 @@ int mmf_xfusion_group_backward(const mmf_xfusion_weights* w, const float* x2, in
  *   x2, dx2 [S x K2]; MM, dMM and the dense backward's dpre [S x mmhid2]; o, h, z, gm, dpo, dz, dph [S x m x 16]; dkr
  *   [S x (sdim + 1)^m]; the seed table the forward launches ask for [S]; the keep bits, words(E) = 2 ceil(E / 64) per node.
  *   Monotone in S; it does not shrink as window_steps grows.
- * Out of scope: radio_fusion = 'tensor'; non-zero baselines; bf16 bags; targets other than risk; the stage-2 pretrained
- *   models; the omic-only MaxNet.
+ * Out of scope: radio_fusion = 'tensor'; non-zero baselines; bf16 bags; targets other than risk; the omic-only MaxNet.  The
+ *   stage-2 pretrained models have mmf_stage2_ig.
  * ------------------------------------------------------------------------------------------- */
 size_t mmf_mm_ig_tensor_workspace_bytes(int64_t N_p, int32_t L_p, int32_t H_p, int32_t D_p, int32_t gated_p, int64_t N_r,
                                         int32_t nseg, int32_t kseg, int32_t H_r, int32_t D_r, int32_t gated_r, int32_t Gin,
@@ -687,6 +687,131 @@ size_t mmf_mm_ig_tensor_workspace_bytes(int64_t N_p, int32_t L_p, int32_t H_p, i
                                         int32_t sdim, int32_t mmhid1, int32_t mmhid2, int32_t nhid);
 int mmf_mm_ig_tensor(const mmf_mm_ig_desc* mm, const mmf_xfusion_weights* xf, void* workspace, size_t workspace_bytes,
                      const mmf_surv_head* head, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Integrated-gradients attribution of the stage-2 fusion models, a cohort of P patients in one call: how much of each
+ *   patient's predicted risk comes from the radiology, pathology and omic embeddings.  This is what the reference's
+ *   attribution script runs (create_attributions.py:93-164): captum's IntegratedGradients(n_steps = 20) from a zero
+ *   baseline through the captum* methods of a multimodal_pretrained (models/nll_models_pretrained.py:200-320, the
+ *   cox / ranking twin likewise), one patient at a time, reduced per modality to sum attr (attr_orig.csv) and sum |attr|
+ *   (attr.csv): n_steps autograd passes per patient through 10-30 small launches, weight gradients included.
+ * In eval mode BatchNorm1d is a per-feature affine map (s = weight / sqrt(var + eps), t = bias - mean s) and dropout is
+ *   off, so a row's result depends on that row alone: P patients x S nodes are independent rows.  The first layer of every
+ *   train type but kronecker is linear in alpha -- fcnn blocks: u(alpha) = alpha (v W0^T) + b0; Highway layer 0 behind bn1:
+ *   z_*(alpha) = alpha ((v . s1) W_*^T) + (W_* t1 + b_*) for * in {gate, nonlinear, linear} -- and the input gradient
+ *   folds the same way: sum_k w_k d risk / d(alpha_k v) = (sum_k w_k du_k) W0, respectively s1 . sum_* (sum_k w_k dz_*,k) W_*.
+ *   With n_layers = 1 nothing that remains per node is a contraction wider than the K-row classifier.  The chain, on one
+ *   stream, THREE launches whatever P and n_steps are:
+ *     1. U [(P + 1) x ldU] = the packed rows [v_0 | .. | v_{m-1}] (times s1) against every first-layer matrix of the model;
+ *        row P is t1 (0 without a bn1) and receives the biases: the constants of every pre-activation;
+ *     2. the node sweep, one workgroup per patient: pre-activations and accumulators in registers; per node the activations
+ *        (BN + ReLU, or the sigmoid / ReLU mix and bn2), the classifier, the hazard head and the backward of risk (or the cox
+ *        scalar), the gradient down to the pre-activations, G += w_k d.  Per node it writes step_risk only;
+ *     3. dx = G against the transposed first layer, attr = v . s1 . dx, and its sums per patient and modality.
+ *   No weight-gradient launch, no float atomics, no workgroup waits for another; every sum is taken in an order fixed by
+ *   its output element: two calls agree bit for bit, and a patient's results do not depend on the cohort around it.
+ * Highway with n_layers >= 2 (up to 8): layer 0 folds as above (launches 1 and 3 unchanged); in the sweep's place the call's
+ *   P (n_steps + 2) rows -- patient-major, a patient's nodes, then its riders alpha = 1 and alpha = 0 -- pass in windows
+ *   of up to 256 rows, which may straddle patients: a launch that forms layer 0's output of every row from U; per layer
+ *   >= 1 and Highway the three dense forwards and the mix (the kernels of mmf_dense_forward and mmf_highway_mix_forward);
+ *   a head launch (bn2, the classifier, the hazard head and the backward of risk, or the cox scalar); per layer and
+ *   Highway, backwards, the mix's backward, the three dense input gradients (mmf_dense_backward's kernel without dW and
+ *   db) and their sum; and a launch that rebuilds layer 0's derivative from U and adds w_k d risk / d z_* to the patient's
+ *   G in node order whatever the windows are.  No weight-gradient launch.
+ * kronecker: nothing folds.  The call's P (n_steps + 2) rows -- patient-major, a patient's nodes, then its riders alpha = 1
+ *   and alpha = 0 -- are the "G patients" of mmf_xfusion_group_forward in eval mode and pass in windows of up to
+ *   MMF_GROUP_MAX rows, which may straddle patients: an expansion launch (alpha_k v_i into encoder2's input rows), the SEVEN
+ *   tail launches of mmf_mm_ig_tensor's step 2 -- the gating stage, the product fused into encoder1, encoder2; a head
+ *   launch without classifier[0] (the stage-2 classifier is Linear(256, K) on the fusion's output); encoder2's input
+ *   gradient, d of the product, the gating stage's backward -- and a fold launch that adds w_k d risk / d(alpha_k v) to
+ *   each patient's accumulator in node order whatever the windows are.  One launch ends the call: attr = v . accumulator
+ *   and its sums.  No weight-gradient launch (encoder1's 10 MB gradient among them).
+ * desc: family (MMF_STAGE2_NLL: risk = -sum_k S_k of the sigmoid hazards, K in 1..32; MMF_STAGE2_COX: the model's scalar
+ *   output, K = 1); train_type; radio / path / omic != 0: the modalities the mode keeps -- two or three, in the reference's
+ *   cat / v_list order [radio, path] | [radio, omic] | [omic, path] | [radio, path, omic]; v[i] [P x 256], blk[i] and attr[i]
+ *   follow that order, m is their number.  A modality the mode drops takes no part (the late types evaluate it in forward,
+ *   captum_* does not take it as an input).  n_layers: the Highways' depth.  alpha / weight: HOST arrays of the n_steps
+ *   nodes and weights, as in mmf_ig_desc; alpha = 1 and alpha = 0 ride along with weight 0.
+ *   blk: the early types use blk[0] (over the 256 m wide cat), the late types blk[i] for v[i].  fcnn: W0 [128 x Kin], b0, bn
+ *   (BatchNorm1d(128)); the cox late-fcnn blocks end in their own Linear(128, 1): W4 [1 x 128], b4 [1].  highway: bn1, bn2
+ *   [Kin], and HOST arrays of n_layers device pointers Wgate, bgate, Wnl, bnl, Wlin, blin ([Kin x Kin], [Kin] each).
+ *   Wk, bk: the classifier behind them -- [K x 128] early-fcnn, [K x 128 m] late-fcnn (cox: [1 x m], over the blocks'
+ *   scalars), [K x 256 m] the highway types, [K x 256] kronecker (xf: the XlinearFusion weights; Wc0, bc0 and nhid are
+ *   not read).
+ * Outputs (device): mod_sum, mod_abs [P x m] = sum attr, sum |attr| over a modality's 256 columns; attr[i] [P x 256] or
+ *   NULL; risk [P] at alpha = 1, risk_base [P] at alpha = 0, step_risk [P x n_steps]; hazards, S [P x K] at alpha = 1 (nll;
+ *   each may be NULL; not written for cox).
+ * Returns, before any launch and in this order:
+ *   MMF_ERR_ARG for a null desc, alpha, weight, Wk, bk, mod_sum, mod_abs, risk, risk_base or step_risk, a family or
+ *     train_type the header does not name, a null v[i], a null weight, bias or BatchNorm array of a block the type reads
+ *     (a null entry of the per-layer arrays included), kronecker without xf;
+ *   MMF_ERR_SHAPE for fewer than two modalities, P outside 1..1,048,576, n_steps outside 1..MMF_GROUP_MAX, K outside 1..32
+ *     (cox: K != 1), n_layers < 1, a highway type with n_layers > 8, an xf that is not the stage-2 fusion's (m modalities,
+ *     dim 256, sdim 16, mmhid1 = mmhid2 = 256);
+ *   MMF_ERR_ALIGN for a v[i], a non-null attr[i] or the workspace off 16 bytes (a null workspace is MMF_ERR_ARG, found
+ *     here), kronecker: Wh_i or Wz_i off 16 bytes; MMF_ERR_WORKSPACE.
+ * mmf_stage2_ig_workspace_bytes: U [(P + 1) x ldU] and G [P x ldU] floats, each rounded up to 256 bytes, ldU = 128
+ *   (early-fcnn), 128 m (late-fcnn) or 768 m (highway); m: the number of modalities.  highway with n_layers >= 2: 4 n_layers +
+ *   5 more buffers of S x 256 m floats, S = min(256, P (n_steps + 2)).  kronecker: the accumulator
+ *   [P x 256 m] and the tail's buffers of mmf_mm_ig_tensor_workspace_bytes' formula for S = min(MMF_GROUP_MAX, P (n_steps +
+ *   2)) rows (K2 = 256 + 256 m, mmhid2 = 256).  0 for what the call refuses by shape or for an unknown enum.  Monotone in P
+ *   and in n_steps.
+ * The ABI version is unchanged: the entry points are additive.
+ * Out of scope: unimonal_pretrained; the `residual` type; train mode; non-zero baselines; targets other than risk.
+ * ------------------------------------------------------------------------------------------- */
+#define MMF_STAGE2_NLL 0
+#define MMF_STAGE2_COX 1
+#define MMF_STAGE2_EARLY_FCNN 0
+#define MMF_STAGE2_LATE_FCNN 1
+#define MMF_STAGE2_EARLY_HIGHWAY 2
+#define MMF_STAGE2_LATE_HIGHWAY 3
+#define MMF_STAGE2_KRONECKER 4
+typedef struct mmf_bn1d {            /* nn.BatchNorm1d in eval mode */
+  const float* weight;               /* [F] */
+  const float* bias;                 /* [F] */
+  const float* mean;                 /* [F] running_mean */
+  const float* var;                  /* [F] running_var */
+  float eps;                         /* 1e-5 */
+} mmf_bn1d;
+typedef struct mmf_stage2_block {
+  const float* W0;                   /* fcnn: [128 x Kin] */
+  const float* b0;                   /* [128] */
+  mmf_bn1d bn;                       /* fcnn: BatchNorm1d(128) */
+  const float* W4;                   /* cox late-fcnn: [1 x 128] */
+  const float* b4;                   /* [1] */
+  mmf_bn1d bn1, bn2;                 /* highway: [Kin] each */
+  const float* const* Wgate;         /* highway: HOST [n_layers] device pointers, [Kin x Kin] */
+  const float* const* bgate;         /* HOST [n_layers], [Kin] */
+  const float* const* Wnl;
+  const float* const* bnl;
+  const float* const* Wlin;
+  const float* const* blin;
+} mmf_stage2_block;
+typedef struct mmf_stage2_ig_desc {
+  int32_t family, train_type;
+  int32_t radio, path, omic;         /* != 0: the mode keeps the modality */
+  int32_t n_layers;
+  int32_t P, K, n_steps;
+  const float* alpha;                /* HOST [n_steps] */
+  const float* weight;               /* HOST [n_steps] */
+  const float* v[3];                 /* [P x 256] each, the present modalities in cat order */
+  mmf_stage2_block blk[3];
+  const mmf_xfusion_weights* xf;     /* kronecker, else NULL */
+  const float* Wk;
+  const float* bk;
+  float* mod_sum;                    /* [P x m] out */
+  float* mod_abs;                    /* [P x m] out */
+  float* attr[3];                    /* [P x 256] out each, or NULL */
+  float* risk;                       /* [P] out */
+  float* risk_base;                  /* [P] out */
+  float* step_risk;                  /* [P x n_steps] out */
+  float* hazards;                    /* [P x K] out (nll), or NULL */
+  float* S;                          /* [P x K] out (nll), or NULL */
+  struct mmf_trace* trace;           /* optional kernel trace, or NULL */
+} mmf_stage2_ig_desc;
+size_t mmf_stage2_ig_workspace_bytes(int32_t family, int32_t train_type, int32_t m, int32_t n_layers, int32_t P, int32_t K,
+                                     int32_t n_steps);
+int mmf_stage2_ig(const mmf_stage2_ig_desc* desc, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Forward-only variants for the inference consumers of the path -- embedding export

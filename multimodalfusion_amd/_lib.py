@@ -119,6 +119,27 @@ class XFusionGrads(C.Structure):
         (n, C.c_void_p) for n in ("dWe1", "dbe1", "dWe2", "dbe2", "dWc0", "dbc0")]
 
 
+class Bn1d(C.Structure):
+    """struct mmf_bn1d (include/mmf_amil.h): nn.BatchNorm1d in eval mode."""
+    _fields_ = [("weight", C.c_void_p), ("bias", C.c_void_p), ("mean", C.c_void_p), ("var", C.c_void_p), ("eps", C.c_float)]
+
+
+class Stage2Block(C.Structure):
+    """struct mmf_stage2_block (include/mmf_amil.h): the per-layer members are host arrays of device pointers."""
+    _fields_ = [("W0", C.c_void_p), ("b0", C.c_void_p), ("bn", Bn1d), ("W4", C.c_void_p), ("b4", C.c_void_p),
+                ("bn1", Bn1d), ("bn2", Bn1d)] + [
+        (n, C.POINTER(C.c_void_p)) for n in ("Wgate", "bgate", "Wnl", "bnl", "Wlin", "blin")]
+
+
+class Stage2IgDesc(C.Structure):
+    """struct mmf_stage2_ig_desc (include/mmf_amil.h): alpha / weight are host arrays, xf points at a host struct."""
+    _fields_ = [(n, C.c_int32) for n in ("family", "train_type", "radio", "path", "omic", "n_layers", "P", "K", "n_steps")] + [
+        ("alpha", C.POINTER(C.c_float)), ("weight", C.POINTER(C.c_float)), ("v", C.c_void_p * 3), ("blk", Stage2Block * 3),
+        ("xf", C.POINTER(XFusionWeights)), ("Wk", C.c_void_p), ("bk", C.c_void_p), ("mod_sum", C.c_void_p),
+        ("mod_abs", C.c_void_p), ("attr", C.c_void_p * 3), ("risk", C.c_void_p), ("risk_base", C.c_void_p),
+        ("step_risk", C.c_void_p), ("hazards", C.c_void_p), ("S", C.c_void_p), ("trace", C.c_void_p)]
+
+
 # name -> (restype, argtypes): every symbol include/mmf_amil.h declares
 SYMBOLS = {
     "mmf_strerror": (C.c_char_p, [C.c_int]),
@@ -189,6 +210,8 @@ SYMBOLS = {
     "mmf_mm_ig_tensor_workspace_bytes": (C.c_size_t, [C.c_int64] + [C.c_int32] * 4 + [C.c_int64] + [C.c_int32] * 15),
     "mmf_mm_ig_tensor": (C.c_int, [C.POINTER(MmIgDesc), C.POINTER(XFusionWeights), C.c_void_p, C.c_size_t,
                                    C.POINTER(SurvHead), C.c_void_p]),
+    "mmf_stage2_ig_workspace_bytes": (C.c_size_t, [C.c_int32] * 7),
+    "mmf_stage2_ig": (C.c_int, [C.POINTER(Stage2IgDesc), C.c_void_p, C.c_size_t, C.c_void_p]),
     "mmf_radio_group_infer_workspace_bytes": (C.c_size_t, [C.POINTER(C.c_int64), C.c_int32, C.c_int32, C.c_int32,
                                                             C.c_int32, C.c_int32, C.c_int32]),
     "mmf_radio_infer_group": (C.c_int, [C.POINTER(AmilDesc), C.POINTER(BagGroup), C.POINTER(RadioReduce), C.c_void_p,

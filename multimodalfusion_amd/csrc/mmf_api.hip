@@ -2219,6 +2219,253 @@ int mmf_mm_ig_tensor(const mmf_mm_ig_desc* mm, const mmf_xfusion_weights* xf, vo
   return mm_ig_call(mm, xf, true, workspace, workspace_bytes, head, stream);
 }
 
+// ---- integrated gradients of the stage-2 fusion models --------------------------------------------------------------
+namespace mmf {
+constexpr int S2_PMAX = 1 << 20;
+constexpr int S2_HW_LAYERS = 8;     // a Highway's depth: the window keeps every layer's pre-activations
+static bool s2_highway(int tt) { return tt == MMF_STAGE2_EARLY_HIGHWAY || tt == MMF_STAGE2_LATE_HIGHWAY; }
+static bool s2_late(int tt) { return tt == MMF_STAGE2_LATE_FCNN || tt == MMF_STAGE2_LATE_HIGHWAY; }
+// U's and G's row: the units behind the first layer (one plane per fcnn block, three per Highway)
+static int s2_ldu(int tt, int m) {
+  return tt == MMF_STAGE2_EARLY_FCNN ? 128 : tt == MMF_STAGE2_LATE_FCNN ? 128 * m : 3 * 256 * m;
+}
+// what the call and the query refuse by shape
+static int s2_shape(int family, int tt, int m, int n_layers, int P, int K, int n_steps) {
+  if (m < 2 || m > 3 || P < 1 || P > S2_PMAX || n_steps < 1 || n_steps > GROUP_MAX || n_layers < 1) return MMF_ERR_SHAPE;
+  if (K < 1 || K > 32 || (family == MMF_STAGE2_COX && K != 1)) return MMF_ERR_SHAPE;
+  if (s2_highway(tt) && n_layers > S2_HW_LAYERS) return MMF_ERR_SHAPE;
+  return MMF_OK;
+}
+// highway with n_layers >= 2: the windows hold up to S2_HW_ROWS of the call's P (n_steps + 2) rows
+static int s2_hw_rows(int P, int n_steps) {
+  const int64_t R = (int64_t)P * (n_steps + 2);
+  return R < S2_HW_ROWS ? (int)R : S2_HW_ROWS;
+}
+// kronecker: the windows hold up to GROUP_MAX of the call's P (n_steps + 2) rows
+static int s2_kron_rows(int P, int n_steps) {
+  const int64_t R = (int64_t)P * (n_steps + 2);
+  return R < GROUP_MAX ? (int)R : GROUP_MAX;
+}
+// the stage-2 models' XlinearFusion: its widths are the class's (models/nll_models_pretrained.py:124)
+static void s2_kron_tail(mmf_xfusion_weights& x, int m) {
+  x.m = m; x.dim = 256; x.sdim = 16; x.mmhid1 = 256; x.mmhid2 = 256; x.nhid = 256;
+}
+static bool s2_bn_ok(const mmf_bn1d& b) { return b.weight && b.bias && b.mean && b.var; }
+static S2Bn s2_bn(const mmf_bn1d& b, int off) { return S2Bn{b.weight + off, b.bias + off, b.mean + off, b.var + off, b.eps}; }
+// deep Highways: per window the layers' outputs X[l], the pre-activations Z[l][gate, nonlinear, linear] of layers >= 1,
+// the running gradient dX, a layer's dZ and its three input gradients, each [rows x 256 m] block by block
+struct S2Ws { float *U, *G; MmIgTailWs t; float *X[S2_HW_LAYERS], *Z[S2_HW_LAYERS][3], *dX, *dZ[3], *dx3[3], *dpre; };
+static S2Ws carve_s2(Carver& c, int tt, int m, int P, int n_steps, int n_layers) {
+  S2Ws w{};
+  if (tt == MMF_STAGE2_KRONECKER) {
+    w.G = c.take<float>((size_t)P * m * 256);
+    w.t = carve_mm_ig_tail(c, m, 256, 256, 256, s2_kron_rows(P, n_steps));
+    return w;
+  }
+  const size_t ld = (size_t)s2_ldu(tt, m);
+  w.U = c.take<float>(((size_t)P + 1) * ld);
+  w.G = c.take<float>((size_t)P * ld);
+  if (s2_highway(tt) && n_layers > 1) {
+    const size_t n = (size_t)s2_hw_rows(P, n_steps) * 256 * m;
+    for (int l = 0; l < n_layers; ++l) {
+      w.X[l] = c.take<float>(n);
+      if (l > 0)
+        for (int g = 0; g < 3; ++g) w.Z[l][g] = c.take<float>(n);
+    }
+    w.dX = c.take<float>(n); w.dpre = c.take<float>(n);
+    for (int g = 0; g < 3; ++g) { w.dZ[g] = c.take<float>(n); w.dx3[g] = c.take<float>(n); }
+  }
+  return w;
+}
+// highway with n_layers >= 2, between the folded forward and the attribution launch: layer 0 from U per row, layers >= 1
+// per window through the dense row kernels (the input gradient alone) and the highway mix, the head, and the fold of layer
+// 0's gradient into G in node order
+static int s2_hw_chain(const mmf_stage2_ig_desc* d, int m, bool late, const S2Ws& w, const IgNodes& q, hipStream_t st) {
+  const int L = d->n_layers, W = 256 * m, nblk = late ? m : 1, wd = W / nblk;
+  const int cap = s2_hw_rows(d->P, d->n_steps);
+  const size_t stride = (size_t)cap * wd;
+  S2HwParams hp{};
+  hp.U = w.U; hp.ldU = 3 * W; hp.W = W; hp.wd = wd; hp.P = d->P; hp.n_steps = d->n_steps; hp.T = q.total; hp.K = d->K;
+  hp.cox = d->family == MMF_STAGE2_COX; hp.blk_stride = stride;
+  for (int k = 0; k < q.total; ++k) { hp.alpha[k] = q.alpha[k]; hp.weight[k] = q.weight[k]; }
+  hp.X0 = w.X[0]; hp.XL = w.X[L - 1]; hp.dXL = w.dX; hp.dX0 = w.dX; hp.G = w.G;
+  for (int b = 0; b < nblk; ++b) hp.bn2[b] = s2_bn(d->blk[b].bn2, 0);
+  hp.Wk = d->Wk; hp.bk = d->bk; hp.step_risk = d->step_risk; hp.risk = d->risk; hp.risk_base = d->risk_base;
+  hp.hazards = hp.cox ? nullptr : d->hazards; hp.S_out = hp.cox ? nullptr : d->S;
+  const DropSpec none = make_drop(0, 0.f, 0, 0, nullptr);
+  const int64_t R = (int64_t)d->P * q.total;
+  for (int64_t g0 = 0; g0 < R; g0 += cap) {
+    const int S = R - g0 < cap ? (int)(R - g0) : cap;
+    hp.g0 = (int)g0; hp.S = S;
+    if (int e = launch_stage2_hw(S2_HW_BEGIN, hp, st)) return e;
+    for (int l = 1; l < L; ++l)
+      for (int b = 0; b < nblk; ++b) {
+        const mmf_stage2_block& k = d->blk[b];
+        const float* Wl[3] = {k.Wgate[l], k.Wnl[l], k.Wlin[l]};
+        const float* bl[3] = {k.bgate[l], k.bnl[l], k.blin[l]};
+        const size_t o = b * stride;
+        for (int g = 0; g < 3; ++g) {
+          DenseParams dp{w.X[l - 1] + o, Wl[g], bl[g], w.Z[l][g] + o, S, wd, wd, ACT_NONE, none, nullptr, wd};
+          if (int e = launch_dense_fwd(dp, st)) return e;
+        }
+        HighwayParams mix{w.Z[l][0] + o, w.Z[l][1] + o, w.Z[l][2] + o, w.X[l] + o, nullptr, nullptr, nullptr, nullptr,
+                          (int64_t)S * wd};
+        if (int e = launch_highway_fwd(mix, st)) return e;
+      }
+    if (int e = launch_stage2_hw(S2_HW_HEAD, hp, st)) return e;
+    for (int l = L - 1; l >= 1; --l)
+      for (int b = 0; b < nblk; ++b) {
+        const mmf_stage2_block& k = d->blk[b];
+        const float* Wl[3] = {k.Wgate[l], k.Wnl[l], k.Wlin[l]};
+        const size_t o = b * stride;
+        HighwayParams mix{w.Z[l][0] + o, w.Z[l][1] + o, w.Z[l][2] + o, nullptr, w.dX + o, w.dZ[0] + o, w.dZ[1] + o,
+                          w.dZ[2] + o, (int64_t)S * wd};
+        if (int e = launch_highway_bwd(mix, st)) return e;
+        for (int g = 0; g < 3; ++g) {     // the input gradient alone: no dW, no db
+          DenseBwdParams bp{w.dZ[g] + o, w.Z[l][g] + o, w.X[l - 1] + o, Wl[g], w.dpre, w.dx3[g] + o, nullptr, nullptr,
+                            S, wd, wd, ACT_NONE, none, nullptr, wd, wd};
+          if (int e = launch_dense_bwd(bp, st)) return e;
+        }
+        if (int e = launch_stage2_hw_add3(w.dx3[0] + o, w.dx3[1] + o, w.dx3[2] + o, w.dX + o, S * wd, st)) return e;
+      }
+    if (int e = launch_stage2_hw(S2_HW_END, hp, st)) return e;
+  }
+  return MMF_OK;
+}
+// kronecker: nothing folds.  The call's P (n_steps + 2) rows (patient-major, a patient's nodes then its two riders) pass in
+// windows of up to GROUP_MAX rows, which may straddle patients, through mmf_mm_ig_tensor's seven tail launches -- the
+// gating stage, the product fused into encoder1, encoder2; the head launch (here without classifier[0]); encoder2's input
+// gradient, dkr, the gating stage's backward -- between an expansion and a fold; one attribution launch ends the call.
+static int s2_kron_chain(const mmf_stage2_ig_desc* d, const mmf_xfusion_weights& xf, int m, const S2Ws& w, const IgNodes& q,
+                         hipStream_t st) {
+  const int K2 = xf.mmhid1 + m * xf.dim;
+  S2KronParams kp{};
+  for (int i = 0; i < m; ++i) { kp.v[i] = d->v[i]; kp.attr[i] = d->attr[i]; }
+  kp.m = m; kp.P = d->P; kp.n_steps = d->n_steps; kp.T = q.total; kp.N1 = xf.mmhid1; kp.K2 = K2; kp.K = d->K;
+  kp.cox = d->family == MMF_STAGE2_COX;
+  for (int k = 0; k < q.total; ++k) { kp.alpha[k] = q.alpha[k]; kp.weight[k] = q.weight[k]; }
+  kp.x2 = w.t.x2; kp.MM = w.t.MM; kp.dx2 = w.t.dx2; kp.dMM = w.t.x.dMM; kp.Gacc = w.G;
+  kp.Wk = d->Wk; kp.bk = d->bk; kp.step_risk = d->step_risk; kp.risk = d->risk; kp.risk_base = d->risk_base;
+  kp.hazards = kp.cox ? nullptr : d->hazards; kp.S_out = kp.cox ? nullptr : d->S;
+  kp.mod_sum = d->mod_sum; kp.mod_abs = d->mod_abs;
+  const int64_t R = (int64_t)d->P * q.total;
+  const int rows = s2_kron_rows(d->P, d->n_steps);
+  for (int64_t g0 = 0; g0 < R; g0 += rows) {
+    const int S = R - g0 < rows ? (int)(R - g0) : rows;
+    kp.g0 = (int)g0; kp.S = S;
+    if (int e = launch_stage2_kron(S2_KRON_EXPAND, kp, st)) return e;
+    if (int e = xfusion_group_fwd_launches(&xf, w.t.x2, S, 0.f, w.t.row_base, nullptr, w.t.x, w.t.MM, st)) return e;
+    if (int e = launch_stage2_kron(S2_KRON_HEAD, kp, st)) return e;
+    DenseBwdParams e2{w.t.x.dMM, w.t.MM, w.t.x2, xf.We2, w.t.x.dpre, w.t.dx2, nullptr, nullptr,
+                      S, K2, xf.mmhid2, ACT_RELU, make_drop(1, 0.f, 0, 10, nullptr), nullptr, xf.mmhid2, xf.mmhid2};
+    if (int e = launch_dense_bwd(e2, st)) return e;
+    if (int e = launch_xfusion_group_bwd_dx(xfusion_bwd_params(&xf, w.t.x2, w.t.dx2, S, 0.f, 0, w.t.x, nullptr), st)) return e;
+    if (int e = launch_stage2_kron(S2_KRON_FOLD, kp, st)) return e;
+  }
+  kp.g0 = 0; kp.S = 1;
+  return launch_stage2_kron(S2_KRON_ATTR, kp, st);
+}
+}  // namespace mmf
+
+size_t mmf_stage2_ig_workspace_bytes(int32_t family, int32_t train_type, int32_t m, int32_t n_layers, int32_t P, int32_t K,
+                                     int32_t n_steps) {
+  if (family < MMF_STAGE2_NLL || family > MMF_STAGE2_COX || train_type < 0 || train_type > MMF_STAGE2_KRONECKER) return 0;
+  if (s2_shape(family, train_type, m, n_layers, P, K, n_steps)) return 0;
+  Carver c;
+  carve_s2(c, train_type, m, P, n_steps, n_layers);
+  return c.off;
+}
+
+int mmf_stage2_ig(const mmf_stage2_ig_desc* d, void* workspace, size_t workspace_bytes, void* stream) {
+  // MMF_ERR_ARG
+  if (!d || !d->alpha || !d->weight || !d->Wk || !d->bk) return MMF_ERR_ARG;
+  if (!d->mod_sum || !d->mod_abs || !d->risk || !d->risk_base || !d->step_risk) return MMF_ERR_ARG;
+  if (d->family < MMF_STAGE2_NLL || d->family > MMF_STAGE2_COX || d->train_type < 0 || d->train_type > MMF_STAGE2_KRONECKER)
+    return MMF_ERR_ARG;
+  const int tt = d->train_type, m = (d->radio != 0) + (d->path != 0) + (d->omic != 0);
+  const bool hw = s2_highway(tt), late = s2_late(tt), cox = d->family == MMF_STAGE2_COX;
+  const int nblk = late ? m : 1;
+  for (int i = 0; i < m; ++i)
+    if (!d->v[i]) return MMF_ERR_ARG;
+  if (tt == MMF_STAGE2_KRONECKER) {
+    const mmf_xfusion_weights* x = d->xf;
+    if (!x || !x->We1 || !x->be1 || !x->We2 || !x->be2) return MMF_ERR_ARG;
+    for (int i = 0; i < m; ++i)
+      if (!x->Wh[i] || !x->bh[i] || !x->Wz[i] || !x->bz[i] || !x->Wo[i] || !x->bo[i]) return MMF_ERR_ARG;
+  } else {
+    for (int i = 0; i < nblk; ++i) {
+      const mmf_stage2_block& b = d->blk[i];
+      if (hw) {
+        if (!s2_bn_ok(b.bn1) || !s2_bn_ok(b.bn2)) return MMF_ERR_ARG;
+        if (!b.Wgate || !b.bgate || !b.Wnl || !b.bnl || !b.Wlin || !b.blin) return MMF_ERR_ARG;
+        for (int l = 0; l < d->n_layers; ++l)
+          if (!b.Wgate[l] || !b.bgate[l] || !b.Wnl[l] || !b.bnl[l] || !b.Wlin[l] || !b.blin[l]) return MMF_ERR_ARG;
+      } else {
+        if (!b.W0 || !b.b0 || !s2_bn_ok(b.bn)) return MMF_ERR_ARG;
+        if (cox && late && (!b.W4 || !b.b4)) return MMF_ERR_ARG;
+      }
+    }
+  }
+  // MMF_ERR_SHAPE
+  if (int e = s2_shape(d->family, tt, m, d->n_layers, d->P, d->K, d->n_steps)) return e;
+  mmf_xfusion_weights xf{};
+  if (tt == MMF_STAGE2_KRONECKER) {
+    xf = *d->xf;
+    if (xf.m != m || xf.dim != 256 || xf.sdim != 16 || xf.mmhid1 != 256 || xf.mmhid2 != 256) return MMF_ERR_SHAPE;
+    s2_kron_tail(xf, m);                            // nhid is not read: the classifier stands on encoder2's output
+    if (int e = xfusion_train_shape(&xf, s2_kron_rows(d->P, d->n_steps))) return e;
+  }
+  // MMF_ERR_ALIGN
+  if (!workspace) return MMF_ERR_ARG;
+  for (int i = 0; i < m; ++i)
+    if (!aligned16(d->v[i]) || (d->attr[i] && !aligned16(d->attr[i]))) return MMF_ERR_ALIGN;
+  if (!aligned16(workspace)) return MMF_ERR_ALIGN;
+  if (tt == MMF_STAGE2_KRONECKER)
+    if (int e = xfusion_weights_aligned(&xf)) return e;
+  Carver c(workspace);
+  const S2Ws w = carve_s2(c, tt, m, d->P, d->n_steps, d->n_layers);
+  if (c.off > workspace_bytes) return MMF_ERR_WORKSPACE;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  TraceScope ts(d->trace);
+  const IgNodes q = ig_nodes(d->n_steps, d->alpha, d->weight);
+  if (tt == MMF_STAGE2_KRONECKER) return s2_kron_chain(d, xf, m, w, q, st);
+
+  // the first-layer matrices: which columns of the packed row each reads, which columns of U it owns
+  const int ldU = s2_ldu(tt, m), W = hw ? 256 * m : ldU, kin = late ? 256 : 256 * m, nout = hw ? kin : 128;
+  S2FoldParams fp{};
+  fp.m = m; fp.P = d->P; fp.ldU = ldU; fp.U = w.U; fp.G = w.G; fp.mod_sum = d->mod_sum; fp.mod_abs = d->mod_abs;
+  for (int i = 0; i < m; ++i) {
+    fp.v[i] = d->v[i]; fp.attr[i] = d->attr[i];
+    if (hw) fp.in_bn[i] = late ? s2_bn(d->blk[i].bn1, 0) : s2_bn(d->blk[0].bn1, 256 * i);
+  }
+  for (int i = 0; i < nblk; ++i) {
+    const mmf_stage2_block& b = d->blk[i];
+    if (hw) {
+      const float* Wg[3] = {b.Wgate[0], b.Wnl[0], b.Wlin[0]};
+      const float* bg[3] = {b.bgate[0], b.bnl[0], b.blin[0]};
+      for (int g = 0; g < 3; ++g) fp.prob[fp.nprob++] = S2Lin{Wg[g], bg[g], nout, kin, kin * i, g * W + nout * i};
+    } else {
+      fp.prob[fp.nprob++] = S2Lin{b.W0, b.b0, nout, kin, kin * i, nout * i};
+    }
+  }
+  S2SweepParams sp{};
+  sp.U = w.U; sp.G = w.G; sp.ldU = ldU; sp.W = W; sp.P = d->P; sp.K = d->K; sp.n_steps = d->n_steps;
+  sp.highway = hw; sp.cox = cox; sp.late_cox = cox && tt == MMF_STAGE2_LATE_FCNN; sp.bn_span = nout;
+  for (int i = 0; i < nblk; ++i) {
+    sp.bn[i] = s2_bn(hw ? d->blk[i].bn2 : d->blk[i].bn, 0);
+    sp.W4[i] = d->blk[i].W4; sp.b4[i] = d->blk[i].b4;
+  }
+  sp.Wk = d->Wk; sp.bk = d->bk;
+  for (int k = 0; k < q.total; ++k) { sp.alpha[k] = q.alpha[k]; sp.weight[k] = q.weight[k]; }
+  sp.step_risk = d->step_risk; sp.risk = d->risk; sp.risk_base = d->risk_base;
+  sp.hazards = cox ? nullptr : d->hazards; sp.S = cox ? nullptr : d->S;
+  if (int e = launch_stage2_fold_fwd(fp, st)) return e;
+  if (hw && d->n_layers > 1) {
+    if (int e = s2_hw_chain(d, m, late, w, q, st)) return e;
+  } else if (int e = launch_stage2_sweep(sp, st)) return e;
+  return launch_stage2_attr(fp, st);
+}
+
 // ---- standalone attention scorer: Attn_Net / Attn_Net_Gated .forward(x) -> (A, x) ------------------------------
 namespace mmf {
 struct AttnWs {

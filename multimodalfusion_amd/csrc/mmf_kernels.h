@@ -435,6 +435,86 @@ struct IgOmicParams {
 };
 int launch_ig_omic(int stage, const IgOmicParams& p, hipStream_t st);
 
+// ---- integrated gradients of the stage-2 fusion models (mmf_stage2_ig, csrc/mmf_stage2_ig.hip) ---------------------------
+constexpr int S2_MAXW = 768;        // the packed row [v_0 | v_1 | v_2] and the widest layer behind it
+constexpr int S2_MAXPROB = 9;       // first-layer matrices of a model: three gates of three Highway blocks
+struct S2Bn { const float *w, *b, *mean, *var; float eps; };      // eval-mode BatchNorm1d; w null: none
+// one first-layer matrix W [n_out x k_in]: it reads columns in_col .. in_col + k_in - 1 of the packed row (whole
+// modalities) and owns columns out_col .. out_col + n_out - 1 of U and G
+struct S2Lin { const float *W, *bias; int n_out, k_in, in_col, out_col; };
+// the two contractions of a call.  fold_fwd: U [(P + 1) x ldU] = (v . s1) W^T per problem, row P = t1 W^T + bias (in_bn[i]:
+// the bn1 that modality i's columns pass, or none).  attr: dx = sum_prob G W, attr[i] [P x 256] (or null) = v_i . s1 . dx and
+// its sums mod_sum / mod_abs [P x m]
+struct S2FoldParams {
+  const float* v[3];
+  S2Bn in_bn[3];
+  S2Lin prob[S2_MAXPROB];
+  int m, P, nprob, ldU;
+  float* U;
+  const float* G;
+  float* attr[3];
+  float *mod_sum, *mod_abs;
+};
+int launch_stage2_fold_fwd(const S2FoldParams& p, hipStream_t st);
+int launch_stage2_attr(const S2FoldParams& p, hipStream_t st);
+// the node sweep, one workgroup per patient: W units behind the first layer (fcnn: one plane of U, BN bn[j / bn_span] and
+// ReLU; highway: the planes gate | nonlinear | linear, the mix and bn2 = bn[j / bn_span]), the classifier Wk [K x W] and
+// the hazard head (nll) or the scalar risk (cox, K = 1; late_cox: Wk [1 x W / 128] over the blocks' own Linear(128, 1) W4,
+// b4).  alpha / weight: the n_steps nodes, then the riders alpha = 1 and alpha = 0.  G [P x ldU] = sum_k w_k d risk_k / d U
+struct S2SweepParams {
+  const float* U;
+  float* G;
+  int ldU, W, P, K, n_steps, highway, cox, late_cox, bn_span;
+  S2Bn bn[3];
+  const float *Wk, *bk;
+  const float *W4[3], *b4[3];
+  float alpha[GROUP_MAX + 2], weight[GROUP_MAX + 2];
+  float *step_risk, *risk, *risk_base, *hazards, *S;   // [P x n_steps], [P], [P], [P x K] or null twice
+};
+int launch_stage2_sweep(const S2SweepParams& p, hipStream_t st);
+// kronecker: the launches around the tensor fusion's grouped tail for one window of S (patient, node) rows, row g0 + s of
+// the call = patient * T + node, T = n_steps + 2.  EXPAND: the embedding columns of x2 [S x K2] (first column N1) = alpha_node
+// v_i; HEAD: MM [S x 256] -> the risks at the rows' places and dMM [S x 256] = d risk / d MM (Wk [K x 256]; cox: K = 1, the
+// scalar); FOLD: Gacc [P x m 256] (=, +=) sum_node w_node dx2's embedding columns, in node order whatever the windows are;
+// ATTR, once per call: attr_i = v_i . Gacc, mod_sum / mod_abs [P x m].  alpha / weight: T values, the riders' weights 0
+enum : int { S2_KRON_EXPAND, S2_KRON_HEAD, S2_KRON_FOLD, S2_KRON_ATTR };
+struct S2KronParams {
+  const float* v[3];
+  int m, P, n_steps, T, g0, S, N1, K2, K, cox;
+  float alpha[GROUP_MAX + 2], weight[GROUP_MAX + 2];
+  float* x2;
+  const float *MM, *dx2;
+  float *dMM, *Gacc;
+  const float *Wk, *bk;
+  float *step_risk, *risk, *risk_base, *hazards, *S_out;
+  float* attr[3];
+  float *mod_sum, *mod_abs;
+};
+int launch_stage2_kron(int stage, const S2KronParams& p, hipStream_t st);
+// highway with n_layers >= 2: the launches around the window's layers >= 1 (dense row kernels and the highway mix), rows as
+// for kronecker, up to S2_HW_ROWS a window.  Activations lie block by block (W / wd Highways of wd units): unit j of row
+// s at [(j / wd) * blk_stride + s * wd + j % wd].  BEGIN: X0 = layer 0's output from U [(P + 1) x 3 W]; HEAD: XL (the last
+// layer's output) -> bn2, the risks at the rows' places, dXL = d risk / d XL; END: G [P x 3 W] (=, +=) sum_node w_node d
+// risk / d z_* of layer 0, from dX0 and U, in node order whatever the windows are
+constexpr int S2_HW_ROWS = 256;      // the dense backward's one-launch form takes up to 256 rows
+enum : int { S2_HW_BEGIN, S2_HW_HEAD, S2_HW_END };
+struct S2HwParams {
+  const float* U;
+  int ldU, W, wd, P, n_steps, T, g0, S, K, cox;
+  size_t blk_stride;
+  float alpha[GROUP_MAX + 2], weight[GROUP_MAX + 2];
+  float* X0;
+  const float* XL;
+  float* dXL;
+  const float* dX0;
+  float* G;
+  S2Bn bn2[3];
+  const float *Wk, *bk;
+  float *step_risk, *risk, *risk_base, *hazards, *S_out;
+};
+int launch_stage2_hw(int stage, const S2HwParams& p, hipStream_t st);
+int launch_stage2_hw_add3(const float* a, const float* b, const float* c, float* out, int n, hipStream_t st);
+
 int set_dyn_lds(const void* kern, int bytes);
 
 // Optional per-kernel timing with HIP events on the launch stream: records into the mmf_trace of the ABI call in

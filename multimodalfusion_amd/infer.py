@@ -305,6 +305,69 @@ def attribute_modalities(model, features, n_steps=20, method="gausslegendre", re
     return out, top(out.patch_abs), top(None if out.inst_abs is None else out.inst_abs.sum(0))
 
 
+def _stage2_names(model):
+    from .models.nll_models_pretrained import _names
+    return _names(model.mode)
+
+
+def stage2_integrated_gradients_autograd(model, h_radio, h_path, h_omic, alphas, weights):
+    """Integrated gradients of a stage-2 multimodal_pretrained's risk by the definition: for each (alpha_k, w_k) one autograd
+    pass of the captum method of the model's mode over alpha_k * the [P x 256] embeddings (in eval mode a row's risk
+    depends on that row alone, so the gradient of sum_p risk_p is every patient's own), attr = embedding * sum_k w_k grad_k
+    -- what captum does around the reference's models, one patient at a time (create_attributions.py:93-164), every
+    weight gradient included.  The yardstick of the fused call (tools/ig_bench.py --head stage2, the tests).
+    Returns ({name: attr [P x 256]} for the modalities the mode keeps, risk [P], risk_baseline [P], step_risk [P x n_steps])
+    on the device."""
+    if model.training:
+        raise RuntimeError("integrated gradients are an eval-mode pass: call model.eval() first")
+    names = _stage2_names(model)
+    dev = _dev(model)
+    given = dict(radio=h_radio, path=h_path, omic=h_omic)
+    xs = [given[n].to(dev).float() for n in names]
+    risk_of = lambda ts: model._risk(**{"h_" + n: t for n, t in zip(names, ts)}).reshape(-1)
+    acc = [torch.zeros_like(x) for x in xs]
+    step_risk = []
+    for a, w in zip(alphas, weights):
+        xi = [(x * float(a)).requires_grad_() for x in xs]
+        risk = risk_of(xi)
+        gs = torch.autograd.grad(risk.sum(), xi)
+        for t, g in zip(acc, gs):
+            t.add_(g, alpha=float(w))
+        step_risk.append(risk.detach())
+    with torch.no_grad():
+        risk_x = risk_of(xs)
+        risk_base = risk_of([torch.zeros_like(x) for x in xs])
+    return {n: t * x for n, t, x in zip(names, acc, xs)}, risk_x, risk_base, torch.stack(step_risk, 1)
+
+
+def attribute_embeddings(model, h_radio=None, h_path=None, h_omic=None, subject_ids=None, n_steps=20,
+                         method="gausslegendre"):
+    """The columns of the reference's attr.csv and attr_orig.csv for a cohort (create_attributions.py:93-175): integrated
+    gradients of a stage-2 multimodal_pretrained's risk with respect to the [P x 256] embeddings of the modalities its mode
+    keeps, from a zero baseline, in one fused call (model.integrated_gradients), reduced per modality to sum |attr| and
+    sum attr.  subject_ids (a sequence of P ids): rows of one id are averaged, as the script's groupby('subject_id').mean()
+    does over the splits, and the ids come back sorted.  The model is put in eval mode for the call and restored.
+    Returns dict(attr={"radio_attr": array, ...}, attr_orig={...}, subject_id=array or None): float64 numpy arrays, one
+    value per patient (or per distinct id), the present modalities only."""
+    if not hasattr(model, "integrated_gradients") or not hasattr(model, "captum"):
+        raise NotImplementedError("attribute_embeddings serves the stage-2 multimodal_pretrained models")
+    dev = _dev(model)
+    to = lambda h: None if h is None else h.to(dev)
+    out = _attribute_in_eval(model, lambda: model.integrated_gradients(to(h_radio), to(h_path), to(h_omic), n_steps=n_steps,
+                                                                       method=method), None, None)
+    cols = {n + "_attr": out.modality_abs[n].double().cpu().numpy() for n in out.modality_abs}
+    orig = {n + "_attr": out.modality_attr[n].double().cpu().numpy() for n in out.modality_attr}
+    if subject_ids is None:
+        return dict(attr=cols, attr_orig=orig, subject_id=None)
+    ids = np.asarray(subject_ids)
+    if ids.shape != next(iter(cols.values())).shape:
+        raise ValueError(f"subject_ids: one id per patient expected, got {ids.shape}")
+    uniq, inv = np.unique(ids, return_inverse=True)
+    cnt = np.bincount(inv, minlength=len(uniq))
+    mean = lambda v: np.bincount(inv, weights=v, minlength=len(uniq)) / cnt
+    return dict(attr={k: mean(v) for k, v in cols.items()}, attr_orig={k: mean(v) for k, v in orig.items()}, subject_id=uniq)
+
+
 # score_patch_batches(group=True): rows of one grouped scoring call per 256 hidden units.  Up to 128 projection tiles of 64 x
 # 64 (2,048 rows of the `small` head, 1,024 of `big`) a window of fp32 batches keeps the projection plan of a 512-patch
 # batch -- the same four-way K split, the same order of additions -- and with it every score bit for bit.

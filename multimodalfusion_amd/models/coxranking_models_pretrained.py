@@ -9,7 +9,7 @@ import torch.nn as nn
 from .. import ops
 from ..utils.utils_pretrained import initialize_weights
 from .model_modules import Highway, Residual, XlinearFusion, fcnn_block
-from .nll_models_pretrained import _pick, _seed
+from .nll_models_pretrained import _pick, _seed, late_branches, stage2_integrated_gradients
 
 
 class unimonal_pretrained(nn.Module):
@@ -85,29 +85,45 @@ class multimodal_pretrained(nn.Module):
     def relocate(self):
         self.to(torch.device("cuda" if torch.cuda.is_available() else "cpu"))
 
-    def forward(self, h_radio, h_path, h_omic):
+    def _risk(self, h_radio=None, h_path=None, h_omic=None):
+        """The scalar output for the embeddings that are given: forward hands in all three (a late type evaluates the one
+        the mode drops too, as the reference does), the captum_* methods leave that one out (None)."""
         seed = _seed(self.training) if self.training else None
         if "late" in self.train_type:
-            if self.train_type == "late-fcnn":
-                r = fcnn_block(self.layer_MRI, h_radio, seed or 0, 0)
-                p = fcnn_block(self.layer_WSI, h_path, seed or 0, 1)
-                o = fcnn_block(self.layer_omic, h_omic, seed or 0, 2)
-            else:
-                r = self.highway_radio(h_radio, seed=seed)
-                p = self.highway_path(h_path, seed=None if seed is None else seed + 1)
-                o = self.highway_omic(h_omic, seed=None if seed is None else seed + 2)
-            mm = torch.cat(_pick(self.mode, r, p, o), dim=1)
+            out = late_branches(self, h_radio, h_path, h_omic, seed)
+            mm = torch.cat(_pick(self.mode, *out), dim=1)
             cls = self.classifier[0] if isinstance(self.classifier, nn.Sequential) else self.classifier
-            risk = ops.dense(mm, cls.weight, cls.bias).squeeze()
-        elif "early" in self.train_type:
+            return ops.dense(mm, cls.weight, cls.bias).squeeze()
+        if "early" in self.train_type:
             mm = torch.cat(_pick(self.mode, h_radio, h_path, h_omic), dim=1)
             if self.train_type == "early-fcnn":
-                risk = fcnn_block(self.classifier, mm, seed or 0, 0)
-            else:
-                risk = ops.dense(self.highway(mm, seed=seed), self.classifier.weight, self.classifier.bias)
-        elif self.train_type == "kronecker":
+                return fcnn_block(self.classifier, mm, seed or 0, 0)
+            return ops.dense(self.highway(mm, seed=seed), self.classifier.weight, self.classifier.bias)
+        if self.train_type == "kronecker":
             mm = self.xfusion(v_list=_pick(self.mode, h_radio, h_path, h_omic), seed=seed)
-            risk = ops.dense(mm, self.classifier.weight, self.classifier.bias)
-        else:
-            raise NotImplementedError(f"train_type {self.train_type!r}")
-        return risk, None, None
+            return ops.dense(mm, self.classifier.weight, self.classifier.bias)
+        raise NotImplementedError(f"train_type {self.train_type!r}")
+
+    def forward(self, h_radio, h_path, h_omic):
+        return self._risk(h_radio, h_path, h_omic), None, None
+
+    # the methods captum is pointed at (models/coxranking_models_pretrained.py:202-305): the risk alone, as a function of
+    # the embeddings the mode keeps, through the same autograd ops as forward
+    def captum_radio_path(self, h_radio, h_path):
+        return self._risk(h_radio, h_path, None)
+
+    def captum_path_omic(self, h_omic, h_path):
+        return self._risk(None, h_path, h_omic)
+
+    def captum_radio_omic(self, h_radio, h_omic):
+        return self._risk(h_radio, None, h_omic)
+
+    def captum(self, h_radio, h_path, h_omic):
+        return self._risk(h_radio, h_path, h_omic)
+
+    def integrated_gradients(self, h_radio=None, h_path=None, h_omic=None, n_steps=20, method="gausslegendre",
+                             return_full=False):
+        """Integrated gradients of the scalar risk with respect to the embeddings the mode keeps, from a zero baseline, for
+        a cohort [P x 256] in ONE fused call (ops.stage2_integrated_gradients).  Eval mode, fp32.  Returns a
+        Stage2Attribution (nll_models_pretrained.py) without hazards and S."""
+        return stage2_integrated_gradients(self, "cox", h_radio, h_path, h_omic, n_steps, method, return_full)

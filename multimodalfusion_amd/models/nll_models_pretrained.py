@@ -5,6 +5,8 @@ All arithmetic runs in the HIP kernels behind include/mmf_amil.h (dense, batchno
 hazards)."""
 from __future__ import annotations
 
+import collections
+
 import torch
 import torch.nn as nn
 
@@ -66,6 +68,105 @@ def _pick(mode, h_radio, h_path, h_omic):
     raise NotImplementedError(f"mode {mode!r}")
 
 
+# what integrated_gradients returns: dicts by modality name ("radio", "path", "omic": the ones the mode keeps) of
+# per-patient tensors [P]; attr: dict of [P x 256] or None; the risks [P]; step_risk [P x n_steps]; hazards, S [P x K] or None
+Stage2Attribution = collections.namedtuple("Stage2Attribution", [
+    "modality_attr", "modality_abs", "share", "attr", "risk", "risk_baseline", "delta", "step_risk", "hazards", "S"])
+
+
+def _names(mode):
+    """The present modalities in _pick's order."""
+    return _pick(mode, "radio", "path", "omic")
+
+
+def _bn_args(bn):
+    return (bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps)
+
+
+def _highway_args(hw):
+    pairs = lambda layers: [(l.weight, l.bias) for l in layers]
+    return dict(bn1=_bn_args(hw.bn1), bn2=_bn_args(hw.bn2), gate=pairs(hw.gate), nonlinear=pairs(hw.nonlinear),
+                linear=pairs(hw.linear))
+
+
+def _fcnn_args(seq):
+    d = dict(W0=seq[0].weight, b0=seq[0].bias, bn=_bn_args(seq[1]))
+    if len(seq) > 4:
+        d.update(W4=seq[4].weight, b4=seq[4].bias)
+    return d
+
+
+def stage2_ig_operands(model, family):
+    """(blocks, Wk, bk, n_layers, xfusion weights or None) of a multimodal_pretrained for
+    ops.stage2_integrated_gradients."""
+    tt, names = model.train_type, _names(model.mode)
+    late = {"radio": "MRI", "path": "WSI", "omic": "omic"}
+    if tt == "early-fcnn":
+        seq = model.classifier
+        return [dict(W0=seq[0].weight, b0=seq[0].bias, bn=_bn_args(seq[1]))], seq[4].weight, seq[4].bias, 1, None
+    if tt == "late-fcnn":
+        cls = model.classifier[0]
+        return [_fcnn_args(getattr(model, "layer_" + late[n])) for n in names], cls.weight, cls.bias, 1, None
+    if tt == "early-highway":
+        return [_highway_args(model.highway)], model.classifier.weight, model.classifier.bias, model.highway.num_layers, None
+    if tt == "late-highway":
+        hws = [getattr(model, "highway_" + n) for n in names]
+        return [_highway_args(h) for h in hws], model.classifier.weight, model.classifier.bias, hws[0].num_layers, None
+    if tt == "kronecker":
+        xw = []
+        for i in range(len(names)):
+            for lin in (model.xfusion.reduce[i][0][0], model.xfusion.reduce[i][1][0], model.xfusion.reduce[i][2][0]):
+                xw += [lin.weight, lin.bias]
+        e1, e2 = model.xfusion.encoder1[0], model.xfusion.encoder2[0]
+        return [], model.classifier.weight, model.classifier.bias, 1, xw + [e1.weight, e1.bias, e2.weight, e2.bias]
+    raise NotImplementedError(f"integrated_gradients: train_type {tt!r}")
+
+
+def stage2_integrated_gradients(model, family, h_radio, h_path, h_omic, n_steps, method, return_full):
+    """integrated_gradients of both multimodal_pretrained classes: the refusals (train mode, non-fp32 or CPU-side shapes),
+    the rule's nodes, the one fused call and the per-patient sums."""
+    if model.training:
+        raise RuntimeError("integrated_gradients is an eval-mode pass (dropout and batch statistics would make the "
+                           "integrand depend on the cohort): call model.eval() first")
+    names = _names(model.mode)
+    given = dict(radio=h_radio, path=h_path, omic=h_omic)
+    vs = [given[n] for n in names]
+    if any(v is None for v in vs):
+        raise ops._lib.MmfError(f"mode {model.mode!r} needs the embeddings {names}")
+    if any(v.dtype != torch.float32 for v in vs):
+        raise NotImplementedError("integrated_gradients takes fp32 embeddings")
+    alphas, weights = ops.ig_quadrature(method, n_steps)
+    blocks, Wk, bk, n_layers, xfusion = stage2_ig_operands(model, family)
+    present = tuple(n in names for n in ("radio", "path", "omic"))
+    with torch.no_grad():
+        r = ops.stage2_integrated_gradients(family, model.train_type, present, vs, blocks, Wk, bk, alphas, weights,
+                                            n_layers=n_layers, want_attr=return_full, xfusion=xfusion)
+        m_attr = {n: r["mod_sum"][:, i] for i, n in enumerate(names)}
+        m_abs = {n: r["mod_abs"][:, i] for i, n in enumerate(names)}
+        tot_abs = r["mod_abs"].sum(1)
+        share = {n: m_abs[n] / tot_abs for n in names}
+        delta = r["mod_sum"].sum(1) - (r["risk"] - r["risk_base"])
+    attr = dict(zip(names, r["attr"])) if return_full else None
+    return Stage2Attribution(m_attr, m_abs, share, attr, r["risk"], r["risk_base"], delta, r["step_risk"], r["hazards"],
+                             r["S"])
+
+
+def late_branches(model, h_radio, h_path, h_omic, seed):
+    """The late types' per-modality blocks (layer_MRI / layer_WSI / layer_omic, or the three Highways) on every embedding
+    that is given, dropout sites 0, 1, 2: forward hands in all three, as the reference does (:144-151), even if the mode
+    drops one; the captum_* methods leave that one out (None).  Shared by both families' multimodal_pretrained."""
+    late = {"radio": "MRI", "path": "WSI", "omic": "omic"}
+    out = []
+    for site, (n, h) in enumerate((("radio", h_radio), ("path", h_path), ("omic", h_omic))):
+        if h is None:
+            out.append(None)
+        elif model.train_type == "late-fcnn":
+            out.append(fcnn_block(getattr(model, "layer_" + late[n]), h, seed or 0, site))
+        else:
+            out.append(getattr(model, "highway_" + n)(h, seed=None if seed is None else seed + site))
+    return out
+
+
 class multimodal_pretrained(nn.Module):
     """models/nll_models_pretrained.py:66-197."""
 
@@ -101,19 +202,10 @@ class multimodal_pretrained(nn.Module):
     def relocate(self):
         self.to(torch.device("cuda" if torch.cuda.is_available() else "cpu"))
 
-    def _late_layers(self, h_radio, h_path, h_omic, seed):
-        """All three branches are evaluated, as the reference does (:144-151), even if the mode drops one."""
-        if self.train_type == "late-fcnn":
-            return (fcnn_block(self.layer_MRI, h_radio, seed or 0, 0), fcnn_block(self.layer_WSI, h_path, seed or 0, 1),
-                    fcnn_block(self.layer_omic, h_omic, seed or 0, 2))
-        return (self.highway_radio(h_radio, seed=None if seed is None else seed),
-                self.highway_path(h_path, seed=None if seed is None else seed + 1),
-                self.highway_omic(h_omic, seed=None if seed is None else seed + 2))
-
     def _logits(self, h_radio, h_path, h_omic):
         seed = _seed(self.training) if self.training else None
         if "late" in self.train_type:
-            r, p, o = self._late_layers(h_radio, h_path, h_omic, seed)
+            r, p, o = late_branches(self, h_radio, h_path, h_omic, seed)
             mm = torch.cat(_pick(self.mode, r, p, o), dim=1)
             cls = self.classifier[0] if isinstance(self.classifier, nn.Sequential) else self.classifier
             return ops.dense(mm, cls.weight, cls.bias)
@@ -131,3 +223,28 @@ class multimodal_pretrained(nn.Module):
         logits = self._logits(h_radio, h_path, h_omic)
         risk, hazards, S, _ = ops.hazards_from_logits(logits)
         return risk, hazards, S
+
+    # the methods captum is pointed at (models/nll_models_pretrained.py:200-320): the risk alone, as a function of the
+    # embeddings the mode keeps, through the same autograd ops as forward
+    def _risk(self, h_radio=None, h_path=None, h_omic=None):
+        return ops.hazards_from_logits(self._logits(h_radio, h_path, h_omic))[0]
+
+    def captum_radio_path(self, h_radio, h_path):
+        return self._risk(h_radio=h_radio, h_path=h_path)
+
+    def captum_path_omic(self, h_omic, h_path):
+        return self._risk(h_path=h_path, h_omic=h_omic)
+
+    def captum_radio_omic(self, h_radio, h_omic):
+        return self._risk(h_radio=h_radio, h_omic=h_omic)
+
+    def captum(self, h_radio, h_path, h_omic):
+        return self._risk(h_radio, h_path, h_omic)
+
+    def integrated_gradients(self, h_radio=None, h_path=None, h_omic=None, n_steps=20, method="gausslegendre",
+                             return_full=False):
+        """Integrated gradients of risk = -sum(S) with respect to the embeddings the mode keeps, from a zero baseline, for
+        a cohort [P x 256] in ONE fused call (ops.stage2_integrated_gradients): create_attributions.py:93-164 for every
+        patient at once.  Eval mode, fp32.  Returns a Stage2Attribution; modality_abs holds the columns of attr.csv,
+        modality_attr those of attr_orig.csv."""
+        return stage2_integrated_gradients(self, "nll", h_radio, h_path, h_omic, n_steps, method, return_full)

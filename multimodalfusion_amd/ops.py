@@ -947,6 +947,116 @@ def mm_integrated_gradients(branches, Wk, bk, alphas, weights, want_attr=False, 
     return out, risks[0:1], risks[1:2], risks[2:], (hz[0], hz[1], Y_hat)
 
 
+STAGE2_FAMILIES = {"nll": 0, "cox": 1}
+STAGE2_TYPES = {"early-fcnn": 0, "late-fcnn": 1, "early-highway": 2, "late-highway": 3, "kronecker": 4}
+
+
+def _bn1d(bn, keep):
+    """mmf_bn1d of (weight, bias, running_mean, running_var, eps)."""
+    w, b, mean, var, eps = bn
+    w, b, mean, var = (_f32c(t) for t in (w, b, mean, var))
+    keep += [w, b, mean, var]
+    return _lib.Bn1d(weight=ptr(w), bias=ptr(b), mean=ptr(mean), var=ptr(var), eps=float(eps))
+
+
+def stage2_integrated_gradients(family, train_type, present, vs, blocks, Wk, bk, alphas, weights, n_layers=1,
+                                want_attr=False, xfusion=None):
+    """Integrated gradients of a stage-2 fusion model's risk with respect to the embeddings of a cohort, from a zero
+    baseline, in ONE C-ABI call (include/mmf_amil.h: mmf_stage2_ig): the first layer runs once per patient, everything
+    behind it once per patient and node inside one launch.
+    family: "nll" (risk = -sum S) or "cox" (the scalar output); train_type: a key of STAGE2_TYPES; present: (radio, path,
+    omic) booleans; vs: the present embeddings, [P x 256] fp32 each, in the reference's cat order; blocks: one dict (early
+    types) or one per embedding (late types) -- fcnn: W0, b0, bn = (weight, bias, running_mean, running_var, eps) and, for
+    the cox late blocks, W4, b4; highway: bn1, bn2 and gate, nonlinear, linear = lists of n_layers (W, b) pairs; Wk, bk: the
+    classifier behind them; alphas, weights: the rule's nodes (host sequences, rounded once to fp32).  kronecker: blocks
+    is empty and xfusion holds the XlinearFusion weights as ops.xfusion takes them; its (patient, node) rows pass in
+    windows of up to GROUP_MAX through the tensor fusion's grouped tail, nothing folds.
+    Returns dict(mod_sum [P x m], mod_abs [P x m], attr (list of m [P x 256]) or None, risk [P], risk_base [P],
+    step_risk [P x n_steps], hazards, S ([P x K], or None for cox))."""
+    import numpy as np
+    if family not in STAGE2_FAMILIES or train_type not in STAGE2_TYPES:
+        raise ValueError(f"family in {sorted(STAGE2_FAMILIES)}, train_type in {sorted(STAGE2_TYPES)}; got {family!r}, {train_type!r}")
+    a = np.ascontiguousarray(np.asarray(alphas, dtype=np.float64).astype(np.float32))
+    w = np.ascontiguousarray(np.asarray(weights, dtype=np.float64).astype(np.float32))
+    if a.ndim != 1 or a.shape != w.shape or not 1 <= a.size <= GROUP_MAX:
+        raise _lib.MmfError(f"alphas / weights: two sequences of 1..{GROUP_MAX} values each")
+    if any(v.dtype != torch.float32 for v in vs):
+        raise NotImplementedError("integrated gradients take fp32 embeddings")
+    n, m = int(a.size), len(vs)
+    if m != sum(1 for f in present if f) or m not in (2, 3):
+        raise _lib.MmfError(f"two or three embeddings, one per present modality; got {m} for {tuple(present)}")
+    vs = [_f32c(v) for v in vs]
+    P = vs[0].shape[0]
+    if any(v.dim() != 2 or tuple(v.shape) != (P, 256) for v in vs):
+        raise _lib.MmfError(f"every embedding must be [P x 256], got {[tuple(v.shape) for v in vs]}")
+    hw, late = "highway" in train_type, "late" in train_type
+    kron = train_type == "kronecker"
+    if len(blocks) != (0 if kron else m if late else 1):
+        raise _lib.MmfError(f"{train_type}: {0 if kron else m if late else 1} block(s) expected, got {len(blocks)}")
+    Wk, bk = _f32c(Wk), _f32c(bk)
+    K = bk.numel()
+    dev, keep = vs[0].device, []
+    fp = C.POINTER(C.c_float)
+    d = _lib.Stage2IgDesc(family=STAGE2_FAMILIES[family], train_type=STAGE2_TYPES[train_type], radio=int(bool(present[0])),
+                          path=int(bool(present[1])), omic=int(bool(present[2])), n_layers=int(n_layers), P=P, K=K, n_steps=n,
+                          alpha=a.ctypes.data_as(fp), weight=w.ctypes.data_as(fp), Wk=ptr(Wk), bk=ptr(bk), trace=_trace)
+    kin = 256 if late else 256 * m
+    width = 256 if kron else (kin if hw else 128) * len(blocks)
+    want_k = (1, m) if (family == "cox" and train_type == "late-fcnn") else (K, width)
+    if Wk.dim() != 2 or tuple(Wk.shape) != want_k:
+        raise _lib.MmfError(f"{train_type}: the classifier must be {want_k}, got {tuple(Wk.shape)}")
+    for i, b in enumerate(blocks):
+        blk = d.blk[i]
+        if hw:
+            blk.bn1, blk.bn2 = _bn1d(b["bn1"], keep), _bn1d(b["bn2"], keep)
+            for name, key in (("gate", "gate"), ("nl", "nonlinear"), ("lin", "linear")):
+                pairs = [(_f32c(W_), _f32c(b_)) for W_, b_ in b[key]]
+                if len(pairs) != n_layers or any(tuple(W_.shape) != (kin, kin) or b_.numel() != kin for W_, b_ in pairs):
+                    raise _lib.MmfError(f"{train_type}: {n_layers} {key} layer(s) of [{kin} x {kin}] expected")
+                Ws = (C.c_void_p * n_layers)(*[ptr(W_) for W_, _ in pairs])
+                bs = (C.c_void_p * n_layers)(*[ptr(b_) for _, b_ in pairs])
+                setattr(blk, "W" + name, Ws)
+                setattr(blk, "b" + name, bs)
+                keep += [pairs, Ws, bs]
+        else:
+            W0, b0 = _f32c(b["W0"]), _f32c(b["b0"])
+            if tuple(W0.shape) != (128, kin) or b0.numel() != 128:
+                raise _lib.MmfError(f"{train_type}: W0 must be [128 x {kin}], got {tuple(W0.shape)}")
+            blk.W0, blk.b0, blk.bn = ptr(W0), ptr(b0), _bn1d(b["bn"], keep)
+            keep += [W0, b0]
+            if b.get("W4") is not None:
+                W4, b4 = _f32c(b["W4"]), _f32c(b["b4"])
+                if W4.numel() != 128 or b4.numel() != 1:
+                    raise _lib.MmfError(f"{train_type}: W4 must be [1 x 128], b4 [1]")
+                blk.W4, blk.b4 = ptr(W4), ptr(b4)
+                keep += [W4, b4]
+    if kron:
+        xw, xkeep, dims = _xfusion_operands(m, 1, 256, xfusion, Wk, bk, "mmf_stage2_ig")     # Wc0, bc0 are not read
+        if dims[:3] != (16, 256, 256):
+            raise _lib.MmfError(f"mmf_stage2_ig: the stage-2 fusion is 16 / 256 / 256 wide, got {dims[:3]}")
+        d.xf = C.pointer(xw)
+        keep += [xw, xkeep]
+    l = lib()
+    nbytes = l.mmf_stage2_ig_workspace_bytes(d.family, d.train_type, m, d.n_layers, P, K, n)
+    if nbytes == 0:
+        raise _lib.MmfError("mmf_stage2_ig: P, n_steps, K or n_layers out of range")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    sums = torch.empty((2, P, m), dtype=torch.float32, device=dev)
+    risks = torch.empty((2, P), dtype=torch.float32, device=dev)
+    step_risk = torch.empty((P, n), dtype=torch.float32, device=dev)
+    hz = torch.empty((2, P, K), dtype=torch.float32, device=dev) if family == "nll" else None
+    attr = [torch.empty((P, 256), dtype=torch.float32, device=dev) for _ in range(m)] if want_attr else None
+    for i in range(m):
+        d.v[i] = ptr(vs[i])
+        d.attr[i] = ptr(attr[i]) if attr else None
+    d.mod_sum, d.mod_abs, d.risk, d.risk_base, d.step_risk = ptr(sums[0]), ptr(sums[1]), ptr(risks[0]), ptr(risks[1]), ptr(step_risk)
+    if hz is not None:
+        d.hazards, d.S = ptr(hz[0]), ptr(hz[1])
+    check(l.mmf_stage2_ig(C.byref(d), ptr(ws), nbytes, stream_ptr()), "mmf_stage2_ig")
+    return dict(mod_sum=sums[0], mod_abs=sums[1], attr=attr, risk=risks[0], risk_base=risks[1], step_risk=step_risk,
+                hazards=None if hz is None else hz[0], S=None if hz is None else hz[1])
+
+
 def radio_infer_group(xs, sizes, Wr, br, stack, gated, Wk=None, bk=None, Y=None, c=None, alpha=0.0, want_M=False,
                       eps=1e-7):
     """The radiology head's G bags evaluated in ONE C-ABI call (include/mmf_amil.h: mmf_radio_infer_group): reduce_dim

@@ -15,7 +15,11 @@ and `vs_single_heads` = fused / that sum (reported, not gated); `*_max_rel_diff`
 ~ N(0, 0.1) again; the yardstick is the same autograd route on that model (required: ratio < 1 everywhere); `concat_ms`:
 mmf_mm_ig on a concat model over the same inputs in the same process, and `tail_ms` = fused - concat, what the fusion tail
 costs (reported, not gated).
-usage: ig_bench.py [--head path|radio|mm] [--fusion concat|tensor] [ROWS ...]   (default rows: 1000 10000 50000, radio 150 512 4096, mm 1000 150
+--head stage2 [--train-type T ...]: the stage-2 multimodal_pretrained (nll, radio_path_omic, n_classes 4, every bias and
+BatchNorm statistic drawn) on a cohort of ROWS patients (one mmf_stage2_ig); `autograd_ms`: infer.stage2_integrated_
+gradients_autograd over the whole [P x 256] batch; `per_patient_autograd_ms`: the same route one patient at a time, what
+the reference's script does (timed on min(P, 8) patients and scaled); required: ratio < 1 everywhere.
+usage: ig_bench.py [--head path|radio|mm|stage2] [--fusion concat|tensor] [--train-type T ...] [ROWS ...]   (default rows: 1000 10000 50000, radio 150 512 4096, mm 1000 150
 10000 512 50000 512);
 env IG_BENCH_ITERS (default 5), IG_BENCH_STEPS (default 20)"""
 import argparse, json, os, statistics, sys
@@ -134,14 +138,63 @@ def main_mm(rows, iters, steps, fusion="concat"):
                           "share": {b: round(float(v), 4) for b, v in f.share.items()}, "kernels": kernels}), flush=True)
 
 
+STAGE2_TYPES = ["early-fcnn", "late-fcnn", "early-highway", "late-highway", "kronecker"]
+
+
+def main_stage2(rows, iters, steps, types):
+    from multimodalfusion_amd.models.nll_models_pretrained import multimodal_pretrained
+    dev = torch.device("cuda", 0)
+    a, w = (v.astype(np.float32) for v in ops.ig_quadrature("gausslegendre", steps))
+    for tt in types or STAGE2_TYPES:
+        torch.manual_seed(0)
+        model = multimodal_pretrained(n_classes=4, mode="radio_path_omic", train_type=tt).to(dev).eval()
+        with torch.no_grad():
+            for k, v in model.state_dict().items():
+                if k.endswith("running_var"):
+                    v.uniform_(0.5, 1.5)
+                elif k.endswith("running_mean") or (v.dim() == 1 and v.dtype.is_floating_point):
+                    v.add_(torch.randn_like(v) * 0.1)
+        gen = torch.Generator(device=dev); gen.manual_seed(7)
+        for P in rows or [1, 32, 256]:
+            hs = [torch.randn(P, 256, device=dev, generator=gen) for _ in range(3)]
+            few = min(P, 8)
+            fused = lambda: model.integrated_gradients(*hs, n_steps=steps)
+            autograd = lambda: infer.stage2_integrated_gradients_autograd(model, *hs, a, w)
+
+            def per_patient():
+                for p in range(few):
+                    infer.stage2_integrated_gradients_autograd(model, *[h[p:p + 1] for h in hs], a, w)
+
+            f, g = fused(), autograd()
+            torch.cuda.synchronize()
+            ref = torch.stack([g[0][n].abs().sum(1) for n in ("radio", "path", "omic")], 1)
+            got = torch.stack([f.modality_abs[n] for n in ("radio", "path", "omic")], 1)
+            err = float((got - ref).abs().max() / ref.max())
+            t_f, t_a, t_p = timed_alternating([(fused, iters), (autograd, max(1, iters // 2)), (per_patient, 1)])
+            trace = _lib.KernelTrace()
+            with trace:
+                fused()
+                torch.cuda.synchronize()
+            kernels = {k: [c, round(ms, 4)] for k, (c, ms) in sorted(trace.dump().items(), key=lambda kv: -kv[1][1])}
+            trace.close()
+            print(json.dumps({"train_type": tt, "patients": P, "n_steps": steps, "fused_ms": round(t_f, 4),
+                              "autograd_ms": round(t_a, 4), "per_patient_autograd_ms": round(t_p * P / few, 4),
+                              "ratio": round(t_f / t_a, 4), "required": 1.0, "ok": t_f < t_a,
+                              "modality_abs_max_rel_diff": float(f"{err:.3e}"), "kernels": kernels}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--head", choices=["path", "radio", "mm"], default="path")
+    ap.add_argument("--head", choices=["path", "radio", "mm", "stage2"], default="path")
     ap.add_argument("--fusion", choices=["concat", "tensor"], default="concat")
+    ap.add_argument("--train-type", choices=STAGE2_TYPES, action="append")
     ap.add_argument("rows", nargs="*", type=int)
     args = ap.parse_args()
     if args.fusion == "tensor" and args.head != "mm":
         sys.exit("--fusion tensor goes with --head mm")
+    if args.head == "stage2":
+        return main_stage2(args.rows, int(os.environ.get("IG_BENCH_ITERS", "5")), int(os.environ.get("IG_BENCH_STEPS", "20")),
+                           args.train_type)
     if args.head == "mm":
         return main_mm(args.rows, int(os.environ.get("IG_BENCH_ITERS", "5")), int(os.environ.get("IG_BENCH_STEPS", "20")),
                        args.fusion)
