@@ -814,6 +814,141 @@ size_t mmf_stage2_ig_workspace_bytes(int32_t family, int32_t train_type, int32_t
 int mmf_stage2_ig(const mmf_stage2_ig_desc* desc, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Stage-2 fcnn and highway models, ONE training step in ONE call: the forward of a batch [B x 256] per modality, the loss,
+ *   every parameter gradient and the BatchNorm running statistics.
+ *   replaces multimodal_pretrained.forward of both families (models/nll_models_pretrained.py:66-197: the hazards head, risk =
+ *   -sum S; models/coxranking_models_pretrained.py:62-200: the scalar output) for train_type early-fcnn, late-fcnn,
+ *   early-highway and late-highway, the Highway and the fcnn blocks (models/model_modules.py:5-27, nll_models_pretrained.py:
+ *   82-90), NLLSurvLoss / CoxSurvLoss / RankingSurvLoss / RankingNLLSurvLoss (utils/loss_utils.py:22-39, 58-101, 124-164) and
+ *   the backward autograd derives from them, as utils/core_utils_pretrained.py:185-232 runs them per batch: 20 to 45
+ *   launches through the composable entry points below (mmf_dense_*, mmf_batchnorm_*, mmf_highway_mix_*, mmf_hazards_*,
+ *   mmf_nll_surv / mmf_cox_surv / mmf_ranking_loss).
+ * No workgroup waits for another; launch boundaries are the only ordering between workgroups, there are no tick words and
+ *   no atomics, and every sum runs in an order fixed by its output element: two calls agree bit for bit.  A workgroup owns
+ *   four features for all B rows, so a feature's batch statistics, its BatchNorm, the activation, dropout, the running
+ *   statistics and, on the way back, dgamma, dbeta, db and its rows of dW never leave the CU.  The chain, on one stream:
+ *   fcnn types, THREE launches (forward only: two):
+ *     1. per block (every block of a late type in the same launch): u = x W0^T + b0, the statistics, y = drop(relu(bn(u))),
+ *        the running statistics;
+ *     2. row tiles: the classifier (the cox late blocks' own Linear(128, 1) first), hazards, S, risk;
+ *     3. every workgroup rebuilds d loss / d logits of all rows from the B risks, labels and times (at most 256^2 pair
+ *        terms); the first one writes the loss; each then takes its columns' dy, the dropout / ReLU / BatchNorm backward,
+ *        its rows of dW0, db0 and its elements of the classifier's gradient.
+ *   highway types, 2 n_layers + 3 launches (forward only: n_layers + 2):
+ *     1. x0 = drop(bn1(h)) and the running statistics;  2 .. n_layers + 1. one launch per layer: the three contractions and
+ *        the mix, bn2 and its running statistics folded into the last;  then the head as above;
+ *     backwards: the owners of the last layer's features take d loss / d logits as above, the classifier's gradient, bn2's
+ *        backward, the mix's backward, dz and the layer's dW rows and db; per layer below, the owner of column j forms dx[:, j]
+ *        = sum_n dz_*[:, n] W_*[n, j] of the layer above and does the same; the last launch takes dx of layer 0 through the
+ *        dropout mask and bn1's backward.
+ *   A forward-only call (grads == NULL: validation) runs its head as one workgroup, which ends with the loss.
+ * desc: family, train_type (MMF_STAGE2_*; kronecker is not taken); radio / path / omic != 0: the modalities the mode keeps, two or
+ *   three, the classifier's input in the reference's cat order [radio, path] | [radio, omic] | [omic, path] | [radio, path,
+ *   omic]; n_layers: the Highways' depth, 1..8; B rows; K logits (cox: 1); training != 0: batch statistics (B >= 2), running
+ *   statistics updated in place with bn.momentum and the unbiased variance, dropout p_drop; training == 0: running statistics,
+ *   no dropout.  h[0..2]: the radio, path and omic embeddings [B x 256].  The early types read the present ones and blk[0]
+ *   (over the 256 m wide cat); the late types read ALL THREE and blk[0..2] = the radio, path and omic block: the forward
+ *   evaluates the block of the modality the mode drops too, as the reference's does, so its running statistics move in
+ *   train mode; it feeds nothing and its gradients are neither read nor written.  Blocks as mmf_stage2_block, with mutable
+ *   running statistics.  Wk, bk: the classifier, [K x 128] early-fcnn, [K x 128 m] late-fcnn (cox: [1 x m] over the blocks'
+ *   scalars), [K x 256 m] the highway types.
+ *   Dropout draws the composable route's masks: the keep-hash of (seed, site, element b * F + f), F the BatchNorm's width:
+ *   fcnn block i site i of seed (early: site 0); Highway i site 0 of seed + i (early: seed).  seed_dev: optional device word
+ *   added to the seed, or NULL.
+ * target: loss = MMF_STAGE2_LOSS_NLL (Y, c, alpha), _COX (times, c), _RANK (times, c, phi, reduction) or _RANK_NLL (ranking
+ *   over the labels Y + nll_ratio x nll(alpha)); phi 0 = sigmoid, 1 = relu; reduction 0 = mean, 1 = sum; times: DEVICE float64
+ *   [B]; Y: int64 [B]; c: float [B].  Ties, an all-censored Cox batch and a batch without a comparable pair (loss 0, every
+ *   gradient 0) as in mmf_cox_surv / mmf_ranking_loss; nll_surv's eps is 1e-7.
+ * Outputs: risk [B]; hazards, S [B x K] (nll family; not written for cox); loss [1], unscaled.  grads: the gradients of
+ *   loss x loss_scale, written or (accumulate != 0) added; members mirror the blocks; NULL: forward and loss only.
+ * Returns, before any launch and in this order:
+ *   MMF_ERR_ARG for a null desc, target, Wk, bk, risk, loss or c; a family, train_type, loss, phi or reduction the header does
+ *     not name; kronecker; nll or rank_nll on the cox family; p_drop outside [0, 1); a null h[i], weight, bias or BatchNorm
+ *     array the type reads (the per-layer arrays' entries included); null hazards or S with the nll family; a null Y or
+ *     times the loss reads; a null gradient of a parameter that takes part, when grads is given;
+ *   MMF_ERR_SHAPE for fewer than two modalities, B outside 1..256, training with B = 1, K outside 1..32 (cox: K != 1), a
+ *     highway type with n_layers outside 1..8, a ranking loss with B < 2;
+ *   MMF_ERR_ALIGN for an h[i] the type reads, a Highway weight matrix or the workspace off 16 bytes (a null workspace is
+ *     MMF_ERR_ARG, found here), times off 8 bytes;  MMF_ERR_WORKSPACE.
+ * mmf_stage2_step_workspace_bytes (m: the number of modalities the mode keeps), with ldB = B rounded up to 4, nb = 1 (early)
+ *   or 3 (late), every slot rounded up to 256 bytes, in floats: fcnn: nb slots of 128 ldB, one of 128 m' ldB (m' = 1 early, m
+ *   late), nb of 256, one of 3 B; highway, D = 256 m (early) or 256 (late): per Highway (nb of them) n_layers + 1 slots of
+ *   D ldB, n_layers of B D, 3 n_layers + 6 of D ldB, two of 2 D; one slot of 256 m ldB.  0 for what the call refuses by
+ *   shape or for an unknown enum; monotone in B.
+ * The ABI version is unchanged: the entry points are additive.
+ * Out of scope: kronecker, `residual`, unimonal_pretrained, bf16 embeddings.
+ * ------------------------------------------------------------------------------------------- */
+#define MMF_STAGE2_LOSS_NLL 0
+#define MMF_STAGE2_LOSS_COX 1
+#define MMF_STAGE2_LOSS_RANK 2
+#define MMF_STAGE2_LOSS_RANK_NLL 3
+typedef struct mmf_stage2_bn_train {  /* nn.BatchNorm1d whose running statistics a training step moves */
+  const float* weight;               /* [F] */
+  const float* bias;                 /* [F] */
+  float* running_mean;               /* [F] */
+  float* running_var;                /* [F] */
+  float eps;                         /* 1e-5 */
+  float momentum;                    /* 0.1 */
+} mmf_stage2_bn_train;
+typedef struct mmf_stage2_step_block {
+  const float* W0;                   /* fcnn: [128 x Kin] */
+  const float* b0;                   /* [128] */
+  mmf_stage2_bn_train bn;            /* fcnn: BatchNorm1d(128) */
+  const float* W4;                   /* cox late-fcnn: [1 x 128] */
+  const float* b4;                   /* [1] */
+  mmf_stage2_bn_train bn1, bn2;      /* highway: [Kin] each */
+  const float* const* Wgate;         /* highway: HOST [n_layers] device pointers, [Kin x Kin] */
+  const float* const* bgate;         /* HOST [n_layers], [Kin] */
+  const float* const* Wnl;
+  const float* const* bnl;
+  const float* const* Wlin;
+  const float* const* blin;
+} mmf_stage2_step_block;
+typedef struct mmf_stage2_step_desc {
+  int32_t family, train_type;
+  int32_t radio, path, omic;         /* != 0: the mode keeps the modality */
+  int32_t n_layers;
+  int32_t B, K, training;
+  const float* h[3];                 /* [B x 256]: radio, path, omic */
+  mmf_stage2_step_block blk[3];
+  const float* Wk;
+  const float* bk;
+  float p_drop;                      /* 0.7 */
+  uint32_t seed;
+  const uint32_t* seed_dev;          /* optional device word added to the seed, or NULL */
+  struct mmf_trace* trace;           /* optional kernel trace, or NULL */
+} mmf_stage2_step_desc;
+typedef struct mmf_stage2_target {
+  int32_t loss;                      /* MMF_STAGE2_LOSS_* */
+  const int64_t* Y;                  /* [B] bin labels (nll, rank_nll) */
+  const float* c;                    /* [B] censorship */
+  const double* times;               /* [B] event times (cox, rank) */
+  float alpha, nll_ratio;
+  int32_t phi, reduction;
+  float loss_scale;
+} mmf_stage2_target;
+typedef struct mmf_stage2_block_grads {
+  float *dW0, *db0, *dbn_weight, *dbn_bias, *dW4, *db4;
+  float *dbn1_weight, *dbn1_bias, *dbn2_weight, *dbn2_bias;
+  float* const* dWgate;              /* HOST [n_layers] device pointers, as the block's */
+  float* const* dbgate;
+  float* const* dWnl;
+  float* const* dbnl;
+  float* const* dWlin;
+  float* const* dblin;
+} mmf_stage2_block_grads;
+typedef struct mmf_stage2_step_grads {
+  mmf_stage2_block_grads blk[3];
+  float* dWk;
+  float* dbk;
+} mmf_stage2_step_grads;
+size_t mmf_stage2_step_workspace_bytes(int32_t family, int32_t train_type, int32_t m, int32_t n_layers, int32_t B, int32_t K,
+                                       int32_t training);
+int mmf_stage2_step(const mmf_stage2_step_desc* desc, const mmf_stage2_target* target, void* workspace,
+                    size_t workspace_bytes, float* risk, float* hazards, float* S, float* loss,
+                    const mmf_stage2_step_grads* grads, int32_t accumulate, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Forward-only variants for the inference consumers of the path -- embedding export
  * (pre_trained_feature.py:116-162: model(..., return_features=True) under no_grad), per-patient inference and
  * attention heat-map scoring (utils/heatmap_utils.py:111-150,249-275: A_raw per bag / per 512-patch batch).

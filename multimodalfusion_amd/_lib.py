@@ -140,6 +140,44 @@ class Stage2IgDesc(C.Structure):
         ("step_risk", C.c_void_p), ("hazards", C.c_void_p), ("S", C.c_void_p), ("trace", C.c_void_p)]
 
 
+class Stage2BnTrain(C.Structure):
+    """struct mmf_stage2_bn_train (include/mmf_amil.h): nn.BatchNorm1d with running statistics a step moves."""
+    _fields_ = [("weight", C.c_void_p), ("bias", C.c_void_p), ("running_mean", C.c_void_p), ("running_var", C.c_void_p),
+                ("eps", C.c_float), ("momentum", C.c_float)]
+
+
+class Stage2StepBlock(C.Structure):
+    """struct mmf_stage2_step_block (include/mmf_amil.h): the per-layer members are host arrays of device pointers."""
+    _fields_ = [("W0", C.c_void_p), ("b0", C.c_void_p), ("bn", Stage2BnTrain), ("W4", C.c_void_p), ("b4", C.c_void_p),
+                ("bn1", Stage2BnTrain), ("bn2", Stage2BnTrain)] + [
+        (n, C.POINTER(C.c_void_p)) for n in ("Wgate", "bgate", "Wnl", "bnl", "Wlin", "blin")]
+
+
+class Stage2StepDesc(C.Structure):
+    """struct mmf_stage2_step_desc (include/mmf_amil.h)."""
+    _fields_ = [(n, C.c_int32) for n in ("family", "train_type", "radio", "path", "omic", "n_layers", "B", "K", "training")] + [
+        ("h", C.c_void_p * 3), ("blk", Stage2StepBlock * 3), ("Wk", C.c_void_p), ("bk", C.c_void_p), ("p_drop", C.c_float),
+        ("seed", C.c_uint32), ("seed_dev", C.c_void_p), ("trace", C.c_void_p)]
+
+
+class Stage2Target(C.Structure):
+    """struct mmf_stage2_target (include/mmf_amil.h)."""
+    _fields_ = [("loss", C.c_int32), ("Y", C.c_void_p), ("c", C.c_void_p), ("times", C.c_void_p), ("alpha", C.c_float),
+                ("nll_ratio", C.c_float), ("phi", C.c_int32), ("reduction", C.c_int32), ("loss_scale", C.c_float)]
+
+
+class Stage2BlockGrads(C.Structure):
+    """struct mmf_stage2_block_grads (include/mmf_amil.h): the per-layer members are host arrays of device pointers."""
+    _fields_ = [(n, C.c_void_p) for n in ("dW0", "db0", "dbn_weight", "dbn_bias", "dW4", "db4", "dbn1_weight", "dbn1_bias",
+                                          "dbn2_weight", "dbn2_bias")] + [
+        (n, C.POINTER(C.c_void_p)) for n in ("dWgate", "dbgate", "dWnl", "dbnl", "dWlin", "dblin")]
+
+
+class Stage2StepGrads(C.Structure):
+    """struct mmf_stage2_step_grads (include/mmf_amil.h)."""
+    _fields_ = [("blk", Stage2BlockGrads * 3), ("dWk", C.c_void_p), ("dbk", C.c_void_p)]
+
+
 # name -> (restype, argtypes): every symbol include/mmf_amil.h declares
 SYMBOLS = {
     "mmf_strerror": (C.c_char_p, [C.c_int]),
@@ -212,6 +250,9 @@ SYMBOLS = {
                                    C.POINTER(SurvHead), C.c_void_p]),
     "mmf_stage2_ig_workspace_bytes": (C.c_size_t, [C.c_int32] * 7),
     "mmf_stage2_ig": (C.c_int, [C.POINTER(Stage2IgDesc), C.c_void_p, C.c_size_t, C.c_void_p]),
+    "mmf_stage2_step_workspace_bytes": (C.c_size_t, [C.c_int32] * 7),
+    "mmf_stage2_step": (C.c_int, [C.POINTER(Stage2StepDesc), C.POINTER(Stage2Target), C.c_void_p, C.c_size_t, C.c_void_p,
+                                  C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stage2StepGrads), C.c_int32, C.c_void_p]),
     "mmf_radio_group_infer_workspace_bytes": (C.c_size_t, [C.POINTER(C.c_int64), C.c_int32, C.c_int32, C.c_int32,
                                                             C.c_int32, C.c_int32, C.c_int32]),
     "mmf_radio_infer_group": (C.c_int, [C.POINTER(AmilDesc), C.POINTER(BagGroup), C.POINTER(RadioReduce), C.c_void_p,

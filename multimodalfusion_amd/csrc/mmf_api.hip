@@ -2466,6 +2466,255 @@ int mmf_stage2_ig(const mmf_stage2_ig_desc* d, void* workspace, size_t workspace
   return launch_stage2_attr(fp, st);
 }
 
+// ---- one-call training step of the stage-2 fcnn and highway models ------------------------------------------------------------
+namespace mmf {
+static int s2s_shape(int family, int tt, int m, int n_layers, int B, int K, int training) {
+  if (m < 2 || m > 3 || B < 1 || B > 256 || (training && B < 2) || K < 1 || K > 32 || (family == MMF_STAGE2_COX && K != 1))
+    return MMF_ERR_SHAPE;
+  if (s2_highway(tt) && (n_layers < 1 || n_layers > 8)) return MMF_ERR_SHAPE;
+  return MMF_OK;
+}
+struct S2sWs {
+  int ldB;
+  float *uT[3], *stat[3], *yT, *sblk;                          // fcnn
+  float *xT[3][9], *xR[3][8], *zT[3][8][3], *dzT[3][2][3], *stat1[3], *stat2[3], *fT;   // highway
+};
+static S2sWs carve_s2s(Carver& c, int tt, int m, int n_layers, int B) {
+  S2sWs w{};
+  const bool hw = s2_highway(tt), late = s2_late(tt);
+  const int nb = late ? 3 : 1;
+  const size_t ldB = (size_t)((B + 3) / 4 * 4);
+  w.ldB = (int)ldB;
+  if (!hw) {
+    for (int i = 0; i < nb; ++i) w.uT[i] = c.take<float>(128 * ldB);
+    w.yT = c.take<float>((size_t)128 * (late ? m : 1) * ldB);
+    for (int i = 0; i < nb; ++i) w.stat[i] = c.take<float>(256);
+    w.sblk = c.take<float>((size_t)3 * B);
+    return w;
+  }
+  const size_t D = late ? 256 : 256 * (size_t)m;
+  for (int i = 0; i < nb; ++i) {
+    for (int l = 0; l <= n_layers; ++l) w.xT[i][l] = c.take<float>(D * ldB);
+    for (int l = 0; l < n_layers; ++l) w.xR[i][l] = c.take<float>((size_t)B * D);
+    for (int l = 0; l < n_layers; ++l)
+      for (int q = 0; q < 3; ++q) w.zT[i][l][q] = c.take<float>(D * ldB);
+    for (int s = 0; s < 2; ++s)
+      for (int q = 0; q < 3; ++q) w.dzT[i][s][q] = c.take<float>(D * ldB);
+    w.stat1[i] = c.take<float>(2 * D);
+    w.stat2[i] = c.take<float>(2 * D);
+  }
+  w.fT = c.take<float>((size_t)256 * m * ldB);
+  return w;
+}
+static bool s2s_bn_ok(const mmf_stage2_bn_train& b) { return b.weight && b.bias && b.running_mean && b.running_var; }
+static S2sBn s2s_bn(const mmf_stage2_bn_train& b) {
+  return S2sBn{b.weight, b.bias, b.running_mean, b.running_var, b.eps, b.momentum};
+}
+}  // namespace mmf
+
+size_t mmf_stage2_step_workspace_bytes(int32_t family, int32_t train_type, int32_t m, int32_t n_layers, int32_t B, int32_t K,
+                                       int32_t training) {
+  if (family < MMF_STAGE2_NLL || family > MMF_STAGE2_COX || train_type < 0 || train_type > MMF_STAGE2_LATE_HIGHWAY) return 0;
+  if (s2s_shape(family, train_type, m, n_layers, B, K, training)) return 0;
+  Carver c;
+  carve_s2s(c, train_type, m, n_layers, B);
+  return c.off;
+}
+
+int mmf_stage2_step(const mmf_stage2_step_desc* d, const mmf_stage2_target* t, void* workspace, size_t workspace_bytes,
+                    float* risk, float* hazards, float* S, float* loss, const mmf_stage2_step_grads* grads,
+                    int32_t accumulate, void* stream) {
+  // MMF_ERR_ARG
+  if (!d || !t || !d->Wk || !d->bk || !risk || !loss || !t->c) return MMF_ERR_ARG;
+  if (d->family < MMF_STAGE2_NLL || d->family > MMF_STAGE2_COX || d->train_type < 0 || d->train_type > MMF_STAGE2_KRONECKER)
+    return MMF_ERR_ARG;
+  if (t->loss < MMF_STAGE2_LOSS_NLL || t->loss > MMF_STAGE2_LOSS_RANK_NLL || t->phi < 0 || t->phi > 1 || t->reduction < 0 ||
+      t->reduction > 1)
+    return MMF_ERR_ARG;
+  if (d->train_type == MMF_STAGE2_KRONECKER) return MMF_ERR_ARG;
+  const int tt = d->train_type, L = d->n_layers;
+  const bool hw = s2_highway(tt), late = s2_late(tt), cox = d->family == MMF_STAGE2_COX;
+  const bool has_nll = t->loss == MMF_STAGE2_LOSS_NLL || t->loss == MMF_STAGE2_LOSS_RANK_NLL;
+  if (cox && has_nll) return MMF_ERR_ARG;
+  if (!(d->p_drop >= 0.f && d->p_drop < 1.f)) return MMF_ERR_ARG;
+  const bool present[3] = {d->radio != 0, d->path != 0, d->omic != 0};
+  const int m = present[0] + present[1] + present[2];
+  // the cat order: [radio, path] | [radio, omic] | [omic, path] | [radio, path, omic]
+  int ord[3] = {0, 1, 2}, slot[3] = {-1, -1, -1};
+  if (m == 2) {
+    if (!present[2]) { ord[0] = 0; ord[1] = 1; }
+    else if (!present[1]) { ord[0] = 0; ord[1] = 2; }
+    else { ord[0] = 2; ord[1] = 1; }
+  }
+  for (int i = 0; i < m && m >= 2; ++i) slot[ord[i]] = i;
+  const int nb = late ? 3 : 1;
+  for (int i = 0; i < 3; ++i)
+    if ((late || present[i]) && !d->h[i]) return MMF_ERR_ARG;
+  const int Lc = L < 0 ? 0 : L > 8 ? 8 : L;           // the per-layer entries that exist to be looked at
+  for (int i = 0; i < nb; ++i) {
+    const mmf_stage2_step_block& b = d->blk[i];
+    if (hw) {
+      if (!s2s_bn_ok(b.bn1) || !s2s_bn_ok(b.bn2)) return MMF_ERR_ARG;
+      if (!b.Wgate || !b.bgate || !b.Wnl || !b.bnl || !b.Wlin || !b.blin) return MMF_ERR_ARG;
+      for (int l = 0; l < Lc; ++l)
+        if (!b.Wgate[l] || !b.bgate[l] || !b.Wnl[l] || !b.bnl[l] || !b.Wlin[l] || !b.blin[l]) return MMF_ERR_ARG;
+    } else {
+      if (!b.W0 || !b.b0 || !s2s_bn_ok(b.bn)) return MMF_ERR_ARG;
+      if (cox && late && (!b.W4 || !b.b4)) return MMF_ERR_ARG;
+    }
+  }
+  if (!cox && (!hazards || !S)) return MMF_ERR_ARG;
+  if (has_nll && !t->Y) return MMF_ERR_ARG;
+  if (!has_nll && !t->times) return MMF_ERR_ARG;
+  if (grads) {
+    if (!grads->dWk || !grads->dbk) return MMF_ERR_ARG;
+    for (int i = 0; i < nb; ++i) {
+      if (late && slot[i] < 0 && m >= 2) continue;   // the dropped modality's block gets no gradient
+      const mmf_stage2_block_grads& g = grads->blk[i];
+      if (hw) {
+        if (!g.dbn1_weight || !g.dbn1_bias || !g.dbn2_weight || !g.dbn2_bias) return MMF_ERR_ARG;
+        if (!g.dWgate || !g.dbgate || !g.dWnl || !g.dbnl || !g.dWlin || !g.dblin) return MMF_ERR_ARG;
+        for (int l = 0; l < Lc; ++l)
+          if (!g.dWgate[l] || !g.dbgate[l] || !g.dWnl[l] || !g.dbnl[l] || !g.dWlin[l] || !g.dblin[l]) return MMF_ERR_ARG;
+      } else {
+        if (!g.dW0 || !g.db0 || !g.dbn_weight || !g.dbn_bias) return MMF_ERR_ARG;
+        if (cox && late && (!g.dW4 || !g.db4)) return MMF_ERR_ARG;
+      }
+    }
+  }
+  // MMF_ERR_SHAPE
+  if (int e = s2s_shape(d->family, tt, m, L, d->B, d->K, d->training)) return e;
+  const bool has_rank = t->loss == MMF_STAGE2_LOSS_RANK || t->loss == MMF_STAGE2_LOSS_RANK_NLL;
+  if (has_rank && d->B < 2) return MMF_ERR_SHAPE;
+  // MMF_ERR_ALIGN
+  if (!workspace) return MMF_ERR_ARG;
+  for (int i = 0; i < 3; ++i)
+    if ((late || present[i]) && !aligned16(d->h[i])) return MMF_ERR_ALIGN;
+  if (hw)
+    for (int i = 0; i < nb; ++i)
+      for (int l = 0; l < L; ++l)
+        if (!aligned16(d->blk[i].Wgate[l]) || !aligned16(d->blk[i].Wnl[l]) || !aligned16(d->blk[i].Wlin[l])) return MMF_ERR_ALIGN;
+  if (!aligned16(workspace)) return MMF_ERR_ALIGN;
+  if (t->times && (reinterpret_cast<uintptr_t>(t->times) & 7)) return MMF_ERR_ALIGN;
+  Carver c(workspace);
+  const S2sWs w = carve_s2s(c, tt, m, L, d->B);
+  if (c.off > workspace_bytes) return MMF_ERR_WORKSPACE;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  TraceScope ts(d->trace);
+
+  const int B = d->B, K = d->K, ldB = w.ldB, training = d->training != 0, acc = accumulate != 0;
+  const float p = training ? d->p_drop : 0.f;
+  S2sLoss lq{};
+  lq.kind = t->loss; lq.phi = t->phi; lq.reduction = t->reduction; lq.K = K; lq.B = B; lq.cox = cox;
+  lq.alpha = t->alpha; lq.ratio = t->nll_ratio; lq.scale = t->loss_scale;
+  lq.Y = t->Y; lq.c = t->c; lq.times = t->times; lq.risk = risk; lq.hazards = hazards; lq.S = S; lq.loss = loss;
+  // the branches the head and the backward see, in their own order; early: the one block over the cat
+  int act[3], nact = 0;
+  for (int i = 0; i < nb; ++i)
+    if (!late || slot[i] >= 0) act[nact++] = i;
+
+  S2sHead hp{};
+  hp.B = B; hp.ldB = ldB; hp.K = K; hp.cox = cox; hp.m = m; hp.with_loss = grads ? 0 : 1;
+  hp.Wk = d->Wk; hp.bk = d->bk; hp.risk = risk; hp.hazards = hazards; hp.S = S; hp.loss = lq; hp.sblk = w.sblk;
+
+  if (!hw) {
+    const int wb = 128;                                        // a block's width in the classifier's input
+    S2sFcnnFwd fp{};
+    fp.nbr = nb; fp.B = B; fp.ldB = ldB; fp.training = training; fp.p = p; fp.seed_dev = d->seed_dev;
+    for (int i = 0; i < nb; ++i) {
+      S2sFcnnFwdBr& br = fp.br[i];
+      const mmf_stage2_step_block& b = d->blk[i];
+      if (late) { br.x[0] = d->h[i]; br.nseg = 1; }
+      else { for (int s = 0; s < m; ++s) br.x[s] = d->h[ord[s]]; br.nseg = m; }
+      br.W0 = b.W0; br.b0 = b.b0; br.bn = s2s_bn(b.bn); br.key = drop_key(d->seed, (uint32_t)i);
+      br.uT = w.uT[i]; br.stat = w.stat[i];
+      br.yT = late ? (slot[i] >= 0 ? w.yT + (size_t)slot[i] * wb * ldB : nullptr) : w.yT;
+    }
+    if (int e = launch_s2s_fcnn_fwd(fp, st)) return e;
+    hp.fT = w.yT; hp.W = late ? wb * m : wb; hp.late_cox = cox && late;
+    for (int a = 0; a < nact && late; ++a) { hp.W4[slot[act[a]]] = d->blk[act[a]].W4; hp.b4[slot[act[a]]] = d->blk[act[a]].b4; }
+    if (int e = launch_s2s_head(hp, st)) return e;
+    if (!grads) return MMF_OK;
+    S2sFcnnBwd bp{};
+    bp.nbr = nact; bp.B = B; bp.ldB = ldB; bp.training = training; bp.accumulate = acc; bp.late_cox = hp.late_cox;
+    bp.W = hp.W; bp.p = p; bp.yT = w.yT; bp.Wk = d->Wk; bp.sblk = w.sblk; bp.dWk = grads->dWk; bp.dbk = grads->dbk; bp.loss = lq;
+    for (int a = 0; a < nact; ++a) {
+      const int i = act[a];
+      S2sFcnnBwdBr& br = bp.br[a];
+      const mmf_stage2_step_block& b = d->blk[i];
+      const mmf_stage2_block_grads& g = grads->blk[i];
+      for (int s = 0; s < 3; ++s) br.x[s] = fp.br[i].x[s];
+      br.nseg = fp.br[i].nseg; br.slot = late ? slot[i] : 0; br.ycol0 = br.slot * wb;
+      br.uT = w.uT[i]; br.stat = w.stat[i]; br.bn = s2s_bn(b.bn); br.W4 = b.W4;
+      br.dW0 = g.dW0; br.db0 = g.db0; br.dgamma = g.dbn_weight; br.dbeta = g.dbn_bias; br.dW4 = g.dW4; br.db4 = g.db4;
+    }
+    return launch_s2s_fcnn_bwd(bp, st);
+  }
+
+  const int D = late ? 256 : 256 * m;
+  S2sBn1Fwd b1{};
+  b1.nbr = nb; b1.D = D; b1.B = B; b1.ldB = ldB; b1.training = training; b1.p = p; b1.seed_dev = d->seed_dev;
+  for (int i = 0; i < nb; ++i) {
+    S2sBn1FwdBr& br = b1.br[i];
+    if (late) br.x[0] = d->h[i];
+    else for (int s = 0; s < m; ++s) br.x[s] = d->h[ord[s]];
+    br.bn = s2s_bn(d->blk[i].bn1); br.key = drop_key(d->seed + (uint32_t)i, 0u);
+    br.xT = w.xT[i][0]; br.xR = w.xR[i][0]; br.stat = w.stat1[i];
+  }
+  if (int e = launch_s2s_bn1_fwd(b1, st)) return e;
+  for (int l = 0; l < L; ++l) {
+    S2sHwFwd fp{};
+    fp.nbr = nb; fp.D = D; fp.B = B; fp.ldB = ldB; fp.training = training; fp.last = l == L - 1;
+    for (int i = 0; i < nb; ++i) {
+      S2sHwFwdBr& br = fp.br[i];
+      const mmf_stage2_step_block& b = d->blk[i];
+      br.xT = w.xT[i][l];
+      br.W[0] = b.Wgate[l]; br.W[1] = b.Wnl[l]; br.W[2] = b.Wlin[l];
+      br.bias[0] = b.bgate[l]; br.bias[1] = b.bnl[l]; br.bias[2] = b.blin[l];
+      for (int q = 0; q < 3; ++q) br.zT[q] = w.zT[i][l][q];
+      br.yT = w.xT[i][l + 1]; br.yR = fp.last ? nullptr : w.xR[i][l + 1];
+      br.bn2 = s2s_bn(b.bn2); br.stat2 = w.stat2[i];
+      br.fT = late ? (slot[i] >= 0 ? w.fT + (size_t)slot[i] * 256 * ldB : nullptr) : w.fT;
+    }
+    if (int e = launch_s2s_hw_fwd(fp, st)) return e;
+  }
+  hp.fT = w.fT; hp.W = 256 * m; hp.late_cox = 0;
+  if (int e = launch_s2s_head(hp, st)) return e;
+  if (!grads) return MMF_OK;
+  for (int l = L; l >= 0; --l) {                               // level l: the gradient arrives at x_l
+    S2sHwBwd bp{};
+    bp.nbr = nact; bp.D = D; bp.B = B; bp.ldB = ldB; bp.training = training; bp.accumulate = acc; bp.W = 256 * m; bp.p = p;
+    bp.mode = l == L ? S2S_HW_TOP : l == 0 ? S2S_HW_BN1 : S2S_HW_MID;
+    bp.seed_dev = d->seed_dev; bp.Wk = d->Wk; bp.dWk = grads->dWk; bp.dbk = grads->dbk; bp.loss = lq;
+    for (int a = 0; a < nact; ++a) {
+      const int i = act[a];
+      S2sHwBwdBr& br = bp.br[a];
+      const mmf_stage2_step_block& b = d->blk[i];
+      const mmf_stage2_block_grads& g = grads->blk[i];
+      if (l < L) {                                             // from the layer above: layer index l (0-based) reads x_l
+        for (int q = 0; q < 3; ++q) br.dzT_in[q] = w.dzT[i][(l + 1) & 1][q];
+        br.Wup[0] = b.Wgate[l]; br.Wup[1] = b.Wnl[l]; br.Wup[2] = b.Wlin[l];
+      } else {
+        br.fcol0 = late ? slot[i] * 256 : 0;
+        br.fT = w.fT + (size_t)br.fcol0 * ldB; br.yT = w.xT[i][L]; br.stat2 = w.stat2[i]; br.bn2 = s2s_bn(b.bn2);
+        br.dgamma2 = g.dbn2_weight; br.dbeta2 = g.dbn2_bias;
+      }
+      if (l > 0) {                                             // x_l is the mix of layer index l - 1 over x_{l-1}
+        for (int q = 0; q < 3; ++q) { br.zT[q] = w.zT[i][l - 1][q]; br.dzT_out[q] = w.dzT[i][l & 1][q]; }
+        br.xR = w.xR[i][l - 1];
+        br.dW[0] = g.dWgate[l - 1]; br.dW[1] = g.dWnl[l - 1]; br.dW[2] = g.dWlin[l - 1];
+        br.db[0] = g.dbgate[l - 1]; br.db[1] = g.dbnl[l - 1]; br.db[2] = g.dblin[l - 1];
+      } else {
+        for (int s = 0; s < 3; ++s) br.x[s] = b1.br[i].x[s];
+        br.bn1 = s2s_bn(b.bn1); br.stat1 = w.stat1[i]; br.key = b1.br[i].key;
+        br.dgamma1 = g.dbn1_weight; br.dbeta1 = g.dbn1_bias;
+      }
+    }
+    if (int e = launch_s2s_hw_bwd(bp, st)) return e;
+  }
+  return MMF_OK;
+}
+
 // ---- standalone attention scorer: Attn_Net / Attn_Net_Gated .forward(x) -> (A, x) ------------------------------
 namespace mmf {
 struct AttnWs {

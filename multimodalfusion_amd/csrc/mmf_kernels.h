@@ -515,6 +515,120 @@ struct S2HwParams {
 int launch_stage2_hw(int stage, const S2HwParams& p, hipStream_t st);
 int launch_stage2_hw_add3(const float* a, const float* b, const float* c, float* out, int n, hipStream_t st);
 
+// ---- one-call training step of the stage-2 fcnn and highway models (csrc/mmf_stage2_step.hip) -----------------------------------
+// A "branch" is one fcnn block or one Highway: the early types have one over the cat, the late types one per modality (the
+// forward runs all three, the head and the backward the ones the mode keeps).  Activations lie feature-major, [feature x ldB].
+struct S2sBn { const float *w, *b; float *rmean, *rvar; float eps, momentum; };
+enum : int { S2S_LOSS_NLL, S2S_LOSS_COX, S2S_LOSS_RANK, S2S_LOSS_RANK_NLL };
+// the loss over the head's outputs: risk [B], hazards / S [B x K] (nll family); scale multiplies the gradient alone
+struct S2sLoss {
+  int kind, phi, reduction, K, B, cox;
+  float alpha, ratio, scale;
+  const int64_t* Y;
+  const float* c;
+  const double* times;
+  const float *risk, *hazards, *S;
+  float* loss;
+};
+struct S2sFcnnFwdBr {
+  const float* x[3];                 // the block's input: nseg embeddings [B x 256]
+  int nseg;
+  const float *W0, *b0;              // [128 x 256 nseg], [128]
+  S2sBn bn;
+  uint32_t key;                      // drop_key(seed, site)
+  float *uT, *yT, *stat;             // pre-BN [128 x ldB]; output [128 x ldB] or null (the dropped modality); mean | invstd [256]
+};
+struct S2sFcnnFwd {
+  S2sFcnnFwdBr br[3];
+  int nbr, B, ldB, training;
+  float p;
+  const uint32_t* seed_dev;
+};
+int launch_s2s_fcnn_fwd(const S2sFcnnFwd& p, hipStream_t st);
+struct S2sBn1FwdBr {
+  const float* x[3];
+  S2sBn bn;
+  uint32_t key;
+  float *xT, *xR, *stat;             // x0 feature-major [D x ldB] and row-major [B x D]; mean | invstd [2 D]
+};
+struct S2sBn1Fwd {
+  S2sBn1FwdBr br[3];
+  int nbr, D, B, ldB, training;
+  float p;
+  const uint32_t* seed_dev;
+};
+int launch_s2s_bn1_fwd(const S2sBn1Fwd& p, hipStream_t st);
+struct S2sHwFwdBr {
+  const float* xT;                   // the layer's input [D x ldB]
+  const float *W[3], *bias[3];       // gate | nonlinear | linear
+  float* zT[3];                      // the three pre-activations [D x ldB]
+  float *yT, *yR;                    // the mix [D x ldB]; row-major [B x D] unless last
+  S2sBn bn2;                         // last layer
+  float *stat2, *fT;                 // mean | invstd [2 D]; bn2's output [D x ldB] or null (the dropped modality)
+};
+struct S2sHwFwd {
+  S2sHwFwdBr br[3];
+  int nbr, D, B, ldB, training, last;
+};
+int launch_s2s_hw_fwd(const S2sHwFwd& p, hipStream_t st);
+// the classifier over fT [W x ldB], the hazard head (nll) or the scalar (cox); late_cox: m blocks of 128 features pass their
+// own W4 [128], b4 [1] first (the scalars kept in sblk [B x 3]), Wk [m].  with_loss: one workgroup, which ends with the loss
+struct S2sHead {
+  const float* fT;
+  int W, B, ldB, K, cox, late_cox, m, with_loss;
+  const float *Wk, *bk;
+  const float *W4[3], *b4[3];
+  float* sblk;
+  float *risk, *hazards, *S;
+  S2sLoss loss;
+};
+int launch_s2s_head(const S2sHead& p, hipStream_t st);
+struct S2sFcnnBwdBr {
+  const float* x[3];
+  int nseg, ycol0, slot;             // the block's first column in the classifier's input; its place in the cat
+  const float *uT, *stat;
+  S2sBn bn;
+  const float* W4;
+  float *dW0, *db0, *dgamma, *dbeta, *dW4, *db4;
+};
+struct S2sFcnnBwd {
+  S2sFcnnBwdBr br[3];                // the blocks the mode keeps
+  int nbr, B, ldB, training, accumulate, late_cox, W;
+  float p;
+  const float* yT;                   // [W x ldB], as the head read it
+  const float *Wk, *sblk;
+  float *dWk, *dbk;
+  S2sLoss loss;
+};
+int launch_s2s_fcnn_bwd(const S2sFcnnBwd& p, hipStream_t st);
+enum : int { S2S_HW_TOP, S2S_HW_MID, S2S_HW_BN1 };
+struct S2sHwBwdBr {
+  const float *dzT_in[3], *Wup[3];   // MID, BN1: dz of the layer above [D x ldB] and its weights
+  const float *fT, *yT, *stat2;      // TOP: bn2's output and input, its statistics
+  int fcol0;                         // TOP: the Highway's first column in the classifier's input
+  S2sBn bn2;
+  float *dgamma2, *dbeta2;
+  const float* zT[3];                // TOP, MID: this layer's pre-activations, its input row-major, where dz and the
+  float* dzT_out[3];                 // gradients go
+  const float* xR;
+  float *dW[3], *db[3];
+  const float* x[3];                 // BN1: the embeddings, bn1, its statistics, the dropout key
+  S2sBn bn1;
+  const float* stat1;
+  uint32_t key;
+  float *dgamma1, *dbeta1;
+};
+struct S2sHwBwd {
+  S2sHwBwdBr br[3];                  // the Highways the mode keeps
+  int nbr, D, B, ldB, training, mode, accumulate, W;
+  float p;
+  const uint32_t* seed_dev;
+  const float* Wk;
+  float *dWk, *dbk;
+  S2sLoss loss;
+};
+int launch_s2s_hw_bwd(const S2sHwBwd& p, hipStream_t st);
+
 int set_dyn_lds(const void* kern, int bytes);
 
 // Optional per-kernel timing with HIP events on the launch stream: records into the mmf_trace of the ABI call in

@@ -9,7 +9,7 @@ import torch.nn as nn
 from .. import ops
 from ..utils.utils_pretrained import initialize_weights
 from .model_modules import Highway, Residual, XlinearFusion, fcnn_block
-from .nll_models_pretrained import _pick, _seed, late_branches, stage2_integrated_gradients
+from .nll_models_pretrained import _pick, _seed, late_branches, stage2_integrated_gradients, stage2_step, stage2_step_ok
 
 
 class unimonal_pretrained(nn.Module):
@@ -106,6 +106,18 @@ class multimodal_pretrained(nn.Module):
 
     def forward(self, h_radio, h_path, h_omic):
         return self._risk(h_radio, h_path, h_omic), None, None
+
+    def step_ok(self, h_radio, h_path, h_omic, loss_fn):
+        """True when step can take this batch (nll_models_pretrained.multimodal_pretrained.step_ok; the scalar head takes
+        CoxSurvLoss and RankingSurvLoss)."""
+        return stage2_step_ok(self, "cox", h_radio, h_path, h_omic, loss_fn)
+
+    def step(self, h_radio, h_path, h_omic, loss_fn, label=None, event_time=None, c=None, loss_scale=1.0, grad_out=None,
+             accumulate=None, backward=True):
+        """forward, the loss and `(loss * loss_scale).backward()` as ONE C-ABI call (ops.stage2_step); see
+        nll_models_pretrained.multimodal_pretrained.step.  Returns (risk [B], None, None, loss), detached."""
+        return stage2_step(self, "cox", h_radio, h_path, h_omic, loss_fn, label, event_time, c, loss_scale, grad_out,
+                           accumulate, backward)
 
     # the methods captum is pointed at (models/coxranking_models_pretrained.py:202-305): the risk alone, as a function of
     # the embeddings the mode keeps, through the same autograd ops as forward

@@ -7,7 +7,7 @@ import torch.nn as nn
 
 from .. import ops
 from ..utils.utils import init_max_weights
-from .model_modules import SNN_Block, snn_stack, step_grad_buffers
+from .model_modules import SNN_Block, snn_stack, step_grad_buffers, times_to_device
 
 
 OMIC_SIZES = {"small": (256, 256), "big": (1024, 256)}         # hidden widths of the SNN (model_genomic.py:17)
@@ -48,27 +48,8 @@ class MaxNet(MaxNet_base):
                 and all(p.requires_grad for p in self.parameters()))
 
     def _times_to_device(self, t, device):
-        """Event times as the loader delivers them (a host array) -> float64 on the device through a small ring of PINNED
-        staging buffers and an asynchronous copy: no pageable copy, no host synchronisation per step (the reference's loop
-        does `torch.tensor(event_time)` + a blocking .to(device) every step, utils/core_utils.py:204).  A ring slot is
-        reused only after the copy that last read it has completed (an event per slot, normally long done)."""
-        n = int(t.size)
-        ring = self.__dict__.get("_mmf_times_ring")
-        if ring is None or ring["cap"] < n or ring["device"] != device:
-            cap = max(256, n)
-            ring = dict(cap=cap, device=device, i=0, bufs=[torch.empty(cap, dtype=torch.float64).pin_memory() for _ in range(4)],
-                        evs=[None] * 4)
-            self.__dict__["_mmf_times_ring"] = ring          # not a parameter / buffer: stays out of state_dict
-        k = ring["i"] = (ring["i"] + 1) % 4
-        if ring["evs"][k] is not None:
-            ring["evs"][k].synchronize()
-        buf = ring["bufs"][k][:n]
-        buf.numpy()[:] = t.reshape(-1)
-        out = buf.to(device, non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record(torch.cuda.current_stream(device))
-        ring["evs"][k] = ev
-        return out
+        """Event times as the loader delivers them (a host array) -> float64 on the device: model_modules.times_to_device."""
+        return times_to_device(self, t, device)
 
     def cox_step(self, genomic_features, times, c, loss_scale=1.0, grad_out=None, accumulate=None):
         """Extension of the reference surface (the training-loop mirror uses it): `risk = model(genomic_features=x)[0]`,

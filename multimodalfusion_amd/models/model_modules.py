@@ -269,6 +269,30 @@ def amil_stack(seq, x, training):
     return ops.amil_pool(x, *stack, gated, p_h, p_att, seed)
 
 
+def times_to_device(owner, t, device):
+    """Event times as the loader delivers them (a host array) -> float64 on the device through a small ring of PINNED
+    staging buffers and an asynchronous copy: no pageable copy, no host synchronisation per step (the reference's loop
+    does `torch.tensor(event_time)` + a blocking .to(device) every step, utils/core_utils.py:204).  A ring slot is
+    reused only after the copy that last read it has completed (an event per slot, normally long done)."""
+    n = int(t.size)
+    ring = owner.__dict__.get("_mmf_times_ring")
+    if ring is None or ring["cap"] < n or ring["device"] != device:
+        cap = max(256, n)
+        ring = dict(cap=cap, device=device, i=0, bufs=[torch.empty(cap, dtype=torch.float64).pin_memory() for _ in range(4)],
+                    evs=[None] * 4)
+        owner.__dict__["_mmf_times_ring"] = ring          # not a parameter / buffer: stays out of state_dict
+    k = ring["i"] = (ring["i"] + 1) % 4
+    if ring["evs"][k] is not None:
+        ring["evs"][k].synchronize()
+    buf = ring["bufs"][k][:n]
+    buf.numpy()[:] = t.reshape(-1)
+    out = buf.to(device, non_blocking=True)
+    ev = torch.cuda.Event()
+    ev.record(torch.cuda.current_stream(device))
+    ring["evs"][k] = ev
+    return out
+
+
 def step_grad_buffers(params, device, grad_out, accumulate):
     """The gradient destinations of a one-call step whose kernels write or accumulate in place: `grad_out` (tensors in
     the order of the non-None `params`; `accumulate` as given) or .grad -- parameters whose .grad is None get a fresh

@@ -12,7 +12,7 @@ import torch.nn as nn
 
 from .. import ops
 from ..utils.utils_pretrained import initialize_weights
-from .model_modules import Highway, XlinearFusion, fcnn_block
+from .model_modules import Highway, XlinearFusion, fcnn_block, step_grad_buffers, times_to_device
 
 
 def _seed(training):
@@ -151,6 +151,164 @@ def stage2_integrated_gradients(model, family, h_radio, h_path, h_omic, n_steps,
                              r["S"])
 
 
+STEP_TYPES = ("early-fcnn", "late-fcnn", "early-highway", "late-highway")
+STEP_MAX_ROWS = 256
+# Where the one-call step did NOT beat the existing route on an MI355X (tools/stage2_step_bench.py, radio_path_omic,
+# profiles/r18/stage2_step_bench.txt), step_ok says no -- early-highway only, whose 768-wide contractions run one thread
+# per row:
+#   forward only (eval mode: validation): 1.14 to 2.40 x the validation route at 32 to 128 rows, 0.80 to 1.02 x at 256;
+#   training with n_layers >= 2 below 128 rows: 1.00 to 1.28 x the autograd route at 32 and 64 rows (nll B=32: 1.00,
+#   nll B=64: 1.07, cox B=32: 1.28, cox B=64: 1.15), 0.48 to 0.84 x from 128 rows on.
+STEP_EARLY_HIGHWAY_DEEP_MIN_ROWS = 128
+
+
+def _step_loss(loss_fn, family):
+    """The loss of a one-call step as ops.stage2_step takes it, or None: a class the loop does not dispatch, or one the
+    family's head cannot feed (hazards are an nll-family output)."""
+    from ..utils.loss_utils import CoxSurvLoss, NLLSurvLoss, RankingNLLSurvLoss, RankingSurvLoss
+    if type(loss_fn) is CoxSurvLoss:
+        return dict(kind="cox")
+    if type(loss_fn) is RankingSurvLoss:
+        spec = dict(kind="rank", phi=loss_fn.phi, reduction=loss_fn.reduction)
+    elif family == "nll" and type(loss_fn) is NLLSurvLoss:
+        return dict(kind="nll", alpha=loss_fn.alpha)
+    elif family == "nll" and type(loss_fn) is RankingNLLSurvLoss:
+        spec = dict(kind="rank_nll", phi=loss_fn.phi, reduction=loss_fn.reduction, alpha=loss_fn.alpha, nll_ratio=loss_fn.nll_ratio)
+    else:
+        return None
+    return spec if spec["phi"] in ("sigmoid", "relu") and spec["reduction"] in ("mean", "sum") else None
+
+
+def _step_blocks(model):
+    """(modules, classifier) of a step: per block the dict of ops.stage2_step with nn.Parameters / buffers in it -- one
+    block for the early types, the radio / path / omic blocks for the late ones -- and the BatchNorm modules it evaluates."""
+    tt = model.train_type
+    bn = lambda b: (b.weight, b.bias, b.running_mean, b.running_var, b.eps, 0.0 if b.momentum is None else b.momentum)
+    pairs = lambda layers: [(l.weight, l.bias) for l in layers]
+
+    def fcnn(seq):
+        d = dict(W0=seq[0].weight, b0=seq[0].bias, bn=bn(seq[1]))
+        if len(seq) > 4 and tt == "late-fcnn":
+            d.update(W4=seq[4].weight, b4=seq[4].bias)
+        return d, [seq[1]]
+
+    def highway(hw):
+        return dict(bn1=bn(hw.bn1), bn2=bn(hw.bn2), gate=pairs(hw.gate), nonlinear=pairs(hw.nonlinear),
+                    linear=pairs(hw.linear)), [hw.bn1, hw.bn2]
+
+    if tt == "early-fcnn":
+        seq = model.classifier
+        return [fcnn(seq)], seq[4]
+    if tt == "late-fcnn":
+        return [fcnn(getattr(model, "layer_" + n)) for n in ("MRI", "WSI", "omic")], model.classifier[0]
+    if tt == "early-highway":
+        return [highway(model.highway)], model.classifier
+    return [highway(getattr(model, "highway_" + n)) for n in ("radio", "path", "omic")], model.classifier
+
+
+def _block_params(b):
+    """(parameter, path into the block's dict) of one block, in a fixed order."""
+    out = []
+    for k in ("W0", "b0", "W4", "b4"):
+        if b.get(k) is not None:
+            out.append((b[k], (k,)))
+    for k in ("bn", "bn1", "bn2"):
+        if k in b:
+            out += [(b[k][0], (k, 0)), (b[k][1], (k, 1))]
+    for k in ("gate", "nonlinear", "linear"):
+        for l, (W, bias) in enumerate(b.get(k, ())):
+            out += [(W, (k, l, 0)), (bias, (k, l, 1))]
+    return out
+
+
+def stage2_step_ok(model, family, h_radio, h_path, h_omic, loss_fn):
+    """True when stage2_step can take this batch -- both multimodal_pretrained classes."""
+    spec = _step_loss(loss_fn, family) if model.train_type in STEP_TYPES else None
+    if spec is None:
+        return False
+    hs = (h_radio, h_path, h_omic)
+    late = "late" in model.train_type
+    read = [h for h, n in zip(hs, ("radio", "path", "omic")) if late or n in model.mode]
+    if len(read) < 2 or any(not torch.is_tensor(h) or not h.is_cuda or h.dtype != torch.float32 or h.dim() != 2
+                            or h.shape[1] != 256 for h in read):
+        return False
+    B = read[0].shape[0]
+    if any(h.shape[0] != B for h in read) or not (2 if model.training else 1) <= B <= STEP_MAX_ROWS:
+        return False
+    if spec["kind"] in ("rank", "rank_nll") and B < 2:             # the reference raises: leave that to the existing route
+        return False
+    if model.train_type == "early-highway":                        # the measured exceptions, see STEP_EARLY_HIGHWAY_DEEP_MIN_ROWS
+        if not model.training or (model.highway.num_layers >= 2 and B < STEP_EARLY_HIGHWAY_DEEP_MIN_ROWS):
+            return False
+    return all(p.requires_grad for p in model.parameters())
+
+
+def stage2_step(model, family, h_radio, h_path, h_omic, loss_fn, label, event_time, c, loss_scale, grad_out, accumulate,
+                backward):
+    """step of both multimodal_pretrained classes: the operands, the gradient destinations, the one dropout draw, the one
+    fused call, num_batches_tracked."""
+    import numpy as np
+    spec = _step_loss(loss_fn, family)
+    if model.train_type not in STEP_TYPES or spec is None:
+        raise NotImplementedError(f"step: train_type {model.train_type!r} with {type(loss_fn).__name__} (see step_ok)")
+    blocks_bns, cls = _step_blocks(model)
+    blocks = [b for b, _ in blocks_bns]
+    late = "late" in model.train_type
+    present = tuple(n in model.mode for n in ("radio", "path", "omic"))
+    dev = h_path.device if h_path is not None else h_radio.device
+    times = None
+    if spec["kind"] in ("cox", "rank"):
+        times = event_time
+        if not (torch.is_tensor(times) and times.is_cuda and times.dtype == torch.float64):
+            times = times_to_device(model, np.asarray(times.cpu() if torch.is_tensor(times) else times, dtype=np.float64), dev)
+    grads = None
+    if backward:
+        # the parameters that take part, in a fixed order: the blocks the mode keeps, then the classifier
+        live = []
+        for i, b in enumerate(blocks):
+            if not late or present[i]:
+                live += [(p, (i,) + path) for p, path in _block_params(b)]
+        live += [(cls.weight, ("dWk",)), (cls.bias, ("dbk",))]
+        params = [p for p, _ in live]
+        if grad_out is not None:
+            where = {id(p): t for p, t in zip(model.parameters(), grad_out)}
+            taken = {id(p) for p in params}
+            if not accumulate:
+                idle = [t for p, t in zip(model.parameters(), grad_out) if id(p) not in taken]
+                if idle:
+                    torch._foreach_zero_(idle)
+            grad_out = [where[id(p)] for p in params]
+        dst, accumulate = step_grad_buffers(params, dev, grad_out, accumulate)
+        gblocks = [None if (late and not present[i]) else {} for i in range(len(blocks))]
+        grads = dict(blocks=gblocks)
+        for (p, path), t in zip(live, dst):
+            if len(path) == 1:
+                grads[path[0]] = t
+                continue
+            g, key = gblocks[path[0]], path[1]
+            if len(path) == 2:
+                g[key] = t
+            elif len(path) == 3:
+                g.setdefault(key, [None, None])[path[2]] = t
+            else:
+                lst = g.setdefault(key, [[None, None] for _ in blocks[path[0]][key]])
+                lst[path[2]][path[3]] = t
+    tr = model.training
+    seed = ops.next_dropout_seed() if tr else 0
+    n_layers = len(blocks[0]["gate"]) if "gate" in blocks[0] else 1
+    drop = model.highway.dropout1 if model.train_type == "early-highway" else model.highway_radio.dropout1 \
+        if model.train_type == "late-highway" else (model.classifier if model.train_type == "early-fcnn" else model.layer_MRI)[3]
+    with torch.no_grad():
+        out = ops.stage2_step(family, model.train_type, present, (h_radio, h_path, h_omic), blocks, cls.weight, cls.bias, spec,
+                              Y=label, c=c, times=times, grads=grads, accumulate=bool(accumulate), loss_scale=loss_scale,
+                              training=tr, n_layers=n_layers, p_drop=drop.p, seed=seed)
+        if tr:
+            tracked = [bn.num_batches_tracked for _, bns in blocks_bns for bn in bns if bn.num_batches_tracked is not None]
+            if tracked:
+                torch._foreach_add_(tracked, 1)
+    return out
+
+
 def late_branches(model, h_radio, h_path, h_omic, seed):
     """The late types' per-modality blocks (layer_MRI / layer_WSI / layer_omic, or the three Highways) on every embedding
     that is given, dropout sites 0, 1, 2: forward hands in all three, as the reference does (:144-151), even if the mode
@@ -223,6 +381,24 @@ class multimodal_pretrained(nn.Module):
         logits = self._logits(h_radio, h_path, h_omic)
         risk, hazards, S, _ = ops.hazards_from_logits(logits)
         return risk, hazards, S
+
+    def step_ok(self, h_radio, h_path, h_omic, loss_fn):
+        """True when step can take this batch: an fcnn or highway type, a loss class the loop dispatches, fp32 CUDA
+        embeddings [B x 256] with B <= 256 (train mode: B >= 2), every parameter trainable -- and not one of the measured
+        exceptions (early-highway in eval mode, or with two or more layers below 128 rows: STEP_EARLY_HIGHWAY_DEEP_MIN_ROWS).
+        Otherwise callers keep to forward, the loss and .backward()."""
+        return stage2_step_ok(self, "nll", h_radio, h_path, h_omic, loss_fn)
+
+    def step(self, h_radio, h_path, h_omic, loss_fn, label=None, event_time=None, c=None, loss_scale=1.0, grad_out=None,
+             accumulate=None, backward=True):
+        """Extension of the reference surface (the training-loop mirror uses it with fused=True): `risk, hazards, S =
+        model(h_radio, h_path, h_omic)`, the loss the loop would dispatch for loss_fn and `(loss * loss_scale).backward()` as
+        ONE C-ABI call (ops.stage2_step), with the same dropout draw, the same running-statistics update and the same
+        num_batches_tracked.  Gradients land in the parameters' .grad (accumulated; a late type's dropped modality keeps
+        None) -- or in `grad_out` (tensors in self.parameters() order; overwritten unless `accumulate`).  backward=False:
+        forward and loss only (validation).  Returns (risk [B], hazards, S, loss), detached; the loss is unscaled."""
+        return stage2_step(self, "nll", h_radio, h_path, h_omic, loss_fn, label, event_time, c, loss_scale, grad_out,
+                           accumulate, backward)
 
     # the methods captum is pointed at (models/nll_models_pretrained.py:200-320): the risk alone, as a function of the
     # embeddings the mode keeps, through the same autograd ops as forward

@@ -1057,6 +1057,120 @@ def stage2_integrated_gradients(family, train_type, present, vs, blocks, Wk, bk,
                 hazards=None if hz is None else hz[0], S=None if hz is None else hz[1])
 
 
+STAGE2_LOSSES = {"nll": 0, "cox": 1, "rank": 2, "rank_nll": 3}
+_S2_LAYERS = (("gate", "gate"), ("nl", "nonlinear"), ("lin", "linear"))
+
+
+def _bn_train(bn, keep):
+    """mmf_stage2_bn_train of (weight, bias, running_mean, running_var, eps, momentum)."""
+    w, b, mean, var, eps, mom = bn
+    keep += [w, b, mean, var]
+    return _lib.Stage2BnTrain(weight=ptr(w), bias=ptr(b), running_mean=ptr(mean), running_var=ptr(var), eps=float(eps),
+                              momentum=float(mom))
+
+
+def stage2_step(family, train_type, present, hs, blocks, Wk, bk, loss, Y=None, c=None, times=None, grads=None,
+                accumulate=False, loss_scale=1.0, training=True, n_layers=1, p_drop=0.7, seed=0):
+    """One training step of a stage-2 fcnn or highway model -- forward, loss, every parameter gradient, the BatchNorm
+    running statistics -- in ONE C-ABI call (include/mmf_amil.h: mmf_stage2_step), three launches for the fcnn types and
+    2 n_layers + 3 for the highway types.
+    family: "nll" or "cox"; train_type: early-fcnn, late-fcnn, early-highway or late-highway; present: (radio, path, omic)
+    booleans; hs: (h_radio, h_path, h_omic), [B x 256] fp32 each (the late types read all three, the early types the present
+    ones).  blocks: one dict (early types) or three, radio / path / omic (late types: the forward runs the block of the
+    modality the mode drops too) -- fcnn: W0, b0, bn = (weight, bias, running_mean, running_var, eps, momentum) and, for the cox
+    late blocks, W4, b4; highway: bn1, bn2 and gate, nonlinear, linear = lists of n_layers (W, b) pairs.  Wk, bk: the
+    classifier.  loss: dict(kind = a key of STAGE2_LOSSES, alpha, nll_ratio, phi = "sigmoid" | "relu", reduction = "mean" |
+    "sum"); Y int64 [B], c [B], times float64 CUDA [B] as the loss needs them.
+    grads: None (forward and loss only: validation) or dict(blocks = a list like `blocks` of the gradient tensors under the
+    same keys -- bn, bn1, bn2 = (dweight, dbias); None for the block without a gradient --, dWk, dbk): the gradients of
+    loss * loss_scale are written there, or added when `accumulate`.
+    Returns (risk [B], hazards, S ([B x K], or None for cox), loss), detached; the loss is unscaled."""
+    if family not in STAGE2_FAMILIES or train_type not in STAGE2_TYPES or train_type == "kronecker":
+        raise ValueError(f"stage2_step: family in {sorted(STAGE2_FAMILIES)}, train_type fcnn or highway; got {family!r}, {train_type!r}")
+    hw, late = "highway" in train_type, "late" in train_type
+    m = sum(1 for f in present if f)
+    read = [late or bool(f) for f in present]
+    hs = [_f32c(h) if r else None for h, r in zip(hs, read)]
+    first = next(h for h in hs if h is not None)
+    B, dev = first.shape[0], first.device
+    if any(h is not None and tuple(h.shape) != (B, 256) for h in hs):
+        raise _lib.MmfError(f"stage2_step: every embedding must be [B x 256], got {[None if h is None else tuple(h.shape) for h in hs]}")
+    nb = 3 if late else 1
+    if len(blocks) != nb:
+        raise _lib.MmfError(f"{train_type}: {nb} block(s) expected, got {len(blocks)}")
+    K = bk.numel()
+    kin = 256 if late else 256 * m
+    want_k = (1, m) if (family == "cox" and train_type == "late-fcnn") else (K, (kin if hw else 128) * (m if late else 1))
+    if tuple(Wk.shape) != want_k:
+        raise _lib.MmfError(f"{train_type}: the classifier must be {want_k}, got {tuple(Wk.shape)}")
+    for b in blocks:                                   # the kernels index by these widths
+        if hw:
+            if any(len(b[key]) != n_layers or any(tuple(W_.shape) != (kin, kin) or b_.numel() != kin for W_, b_ in b[key])
+                   for _, key in _S2_LAYERS) or any(t.numel() != kin for bn in (b["bn1"], b["bn2"]) for t in bn[:4]):
+                raise _lib.MmfError(f"{train_type}: {n_layers} layer(s) of [{kin} x {kin}] and BatchNorm1d({kin}) expected")
+        elif tuple(b["W0"].shape) != (128, kin) or b["b0"].numel() != 128 or any(t.numel() != 128 for t in b["bn"][:4]) or (
+                b.get("W4") is not None and (b["W4"].numel() != 128 or b["b4"].numel() != 1)):
+            raise _lib.MmfError(f"{train_type}: W0 must be [128 x {kin}] with BatchNorm1d(128), W4 [1 x 128]")
+    keep = []
+    d = _lib.Stage2StepDesc(family=STAGE2_FAMILIES[family], train_type=STAGE2_TYPES[train_type], radio=int(bool(present[0])),
+                            path=int(bool(present[1])), omic=int(bool(present[2])), n_layers=int(n_layers), B=B, K=K,
+                            training=1 if training else 0, Wk=ptr(Wk), bk=ptr(bk), p_drop=float(p_drop),
+                            seed=int(seed) & 0xFFFFFFFF, seed_dev=ptr(_seed_word), trace=_trace)
+    for i, h in enumerate(hs):
+        d.h[i] = ptr(h)
+    g = _lib.Stage2StepGrads(dWk=ptr(grads["dWk"]), dbk=ptr(grads["dbk"])) if grads is not None else None
+    for i, b in enumerate(blocks):
+        blk = d.blk[i]
+        gb = grads["blocks"][i] if grads is not None else None
+        gblk = g.blk[i] if gb is not None else None
+        if hw:
+            blk.bn1, blk.bn2 = _bn_train(b["bn1"], keep), _bn_train(b["bn2"], keep)
+            if gb is not None:
+                gblk.dbn1_weight, gblk.dbn1_bias = ptr(gb["bn1"][0]), ptr(gb["bn1"][1])
+                gblk.dbn2_weight, gblk.dbn2_bias = ptr(gb["bn2"][0]), ptr(gb["bn2"][1])
+            for name, key in _S2_LAYERS:
+                Ws = (C.c_void_p * n_layers)(*[ptr(W_) for W_, _ in b[key]])
+                bs = (C.c_void_p * n_layers)(*[ptr(b_) for _, b_ in b[key]])
+                setattr(blk, "W" + name, Ws)
+                setattr(blk, "b" + name, bs)
+                keep += [Ws, bs]
+                if gb is not None:
+                    dWs = (C.c_void_p * n_layers)(*[ptr(W_) for W_, _ in gb[key]])
+                    dbs = (C.c_void_p * n_layers)(*[ptr(b_) for _, b_ in gb[key]])
+                    setattr(gblk, "dW" + name, dWs)
+                    setattr(gblk, "db" + name, dbs)
+                    keep += [dWs, dbs]
+        else:
+            blk.W0, blk.b0, blk.bn = ptr(b["W0"]), ptr(b["b0"]), _bn_train(b["bn"], keep)
+            if b.get("W4") is not None:
+                blk.W4, blk.b4 = ptr(b["W4"]), ptr(b["b4"])
+            if gb is not None:
+                gblk.dW0, gblk.db0 = ptr(gb["W0"]), ptr(gb["b0"])
+                gblk.dbn_weight, gblk.dbn_bias = ptr(gb["bn"][0]), ptr(gb["bn"][1])
+                if gb.get("W4") is not None:
+                    gblk.dW4, gblk.db4 = ptr(gb["W4"]), ptr(gb["b4"])
+    kind = loss["kind"]
+    if Y is not None:
+        Y = Y.reshape(B).to(device=dev, dtype=torch.int64).contiguous()
+    if times is not None and (times.dtype != torch.float64 or not times.is_cuda):
+        raise _lib.MmfError("stage2_step: event times must be a float64 CUDA tensor")
+    cc = c.reshape(B).to(device=dev, dtype=torch.float32).contiguous()
+    t = _lib.Stage2Target(loss=STAGE2_LOSSES[kind], Y=ptr(Y), c=ptr(cc), times=ptr(times),
+                          alpha=float(loss.get("alpha", 0.0)), nll_ratio=float(loss.get("nll_ratio", 0.0)),
+                          phi={"sigmoid": 0, "relu": 1}[loss.get("phi", "sigmoid")],
+                          reduction={"mean": 0, "sum": 1}[loss.get("reduction", "mean")], loss_scale=float(loss_scale))
+    l = lib()
+    nbytes = l.mmf_stage2_step_workspace_bytes(d.family, d.train_type, m, d.n_layers, B, K, d.training)
+    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+    risk = torch.empty((B,), dtype=torch.float32, device=dev)
+    hz = torch.empty((2, B, K), dtype=torch.float32, device=dev) if family == "nll" else None
+    out = torch.empty((), dtype=torch.float32, device=dev)
+    check(l.mmf_stage2_step(C.byref(d), C.byref(t), ptr(ws), nbytes, ptr(risk), None if hz is None else ptr(hz[0]),
+                            None if hz is None else ptr(hz[1]), ptr(out), None if g is None else C.byref(g),
+                            1 if accumulate else 0, stream_ptr()), "mmf_stage2_step")
+    return risk, (None if hz is None else hz[0]), (None if hz is None else hz[1]), out
+
+
 def radio_infer_group(xs, sizes, Wr, br, stack, gated, Wk=None, bk=None, Y=None, c=None, alpha=0.0, want_M=False,
                       eps=1e-7):
     """The radiology head's G bags evaluated in ONE C-ABI call (include/mmf_amil.h: mmf_radio_infer_group): reduce_dim

@@ -26,18 +26,24 @@ def _loss(loss_fn, risk, hazards, S, label, event_time, c, device):
     raise NotImplementedError(type(loss_fn).__name__)
 
 
-def _run(model, loader, loss_fn, reg_fn, lambda_reg, device, train, optimizer=None, gc=16):
+def _run(model, loader, loss_fn, reg_fn, lambda_reg, device, train, optimizer=None, gc=16, fused=False):
     loss_surv_sum, loss_sum = 0.0, 0.0
     all_risk, all_c, all_t = [], [], []
     for batch_idx, (radio_features, path_features, genomic_features, label, event_time, c, masks) in enumerate(loader):
         radio_features, path_features = radio_features.to(device), path_features.to(device)
         genomic_features, label, c = genomic_features.to(device), label.to(device), c.to(device)
-        if train:
+        # fused: forward, loss and backward of the batch as ONE call (model.step) where the model says it can take it
+        one_call = fused and hasattr(model, "step_ok") and model.step_ok(radio_features, path_features, genomic_features, loss_fn)
+        if one_call:
+            risk, hazards, S, loss = model.step(radio_features, path_features, genomic_features, loss_fn, label=label,
+                                                event_time=event_time, c=c, loss_scale=1.0 / gc, backward=train)
+        elif train:
             risk, hazards, S = model(h_radio=radio_features, h_path=path_features, h_omic=genomic_features)
         else:
             with torch.no_grad():
                 risk, hazards, S = model(h_radio=radio_features, h_path=path_features, h_omic=genomic_features)
-        loss = _loss(loss_fn, risk, hazards, S, label, event_time, c, device)
+        if not one_call:
+            loss = _loss(loss_fn, risk, hazards, S, label, event_time, c, device)
         loss_value = loss.item()
         loss_reg = 0 if reg_fn is None else float((reg_fn(model) * lambda_reg).detach().cpu().numpy().item())
         all_risk.append(np.atleast_1d(risk.detach().cpu().numpy().squeeze()))
@@ -46,7 +52,8 @@ def _run(model, loader, loss_fn, reg_fn, lambda_reg, device, train, optimizer=No
         loss_surv_sum += loss_value
         loss_sum += loss_value + loss_reg
         if train:
-            (loss / gc + loss_reg).backward()
+            if not one_call:                     # loss_reg is a float (see above): it never reaches the gradients
+                (loss / gc + loss_reg).backward()
             if (batch_idx + 1) % gc == 0:
                 optimizer.step()
                 optimizer.zero_grad()
@@ -57,10 +64,12 @@ def _run(model, loader, loss_fn, reg_fn, lambda_reg, device, train, optimizer=No
 
 
 def train_loop_survival(epoch, model, loader, optimizer, n_classes, mode, writer=None, loss_fn=None, reg_fn=None,
-                        lambda_reg=0., gc=16, t_bin=None, train_type=None, verbose=True):
+                        lambda_reg=0., gc=16, t_bin=None, train_type=None, verbose=True, fused=False):
+    """fused (extension, default off): a batch the model's step_ok accepts runs as one call, model.step with loss_scale =
+    1 / gc; every other batch, and everything around the batch, as before."""
     device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
     model.train()
-    loss_surv, loss, c_index = _run(model, loader, loss_fn, reg_fn, lambda_reg, device, True, optimizer, gc)
+    loss_surv, loss, c_index = _run(model, loader, loss_fn, reg_fn, lambda_reg, device, True, optimizer, gc, fused)
     if verbose:
         print('Epoch: {}, train_loss_surv: {:.4f}, train_loss: {:.4f}, train_c_index: {:.4f}'.format(epoch, loss_surv, loss, c_index))
     if writer:
@@ -71,11 +80,12 @@ def train_loop_survival(epoch, model, loader, optimizer, n_classes, mode, writer
 
 
 def validate_survival(cur, epoch, model, loader, n_classes, mode, early_stopping=None, writer=None, loss_fn=None,
-                      reg_fn=None, lambda_reg=0., results_dir=None, t_bin=None, train_type=None, verbose=True):
+                      reg_fn=None, lambda_reg=0., results_dir=None, t_bin=None, train_type=None, verbose=True, fused=False):
+    """fused (extension, default off): forward and loss of a batch the model's step_ok accepts as one call."""
     import os
     device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
     model.eval()
-    loss_surv, loss, c_index = _run(model, loader, loss_fn, reg_fn, lambda_reg, device, False)
+    loss_surv, loss, c_index = _run(model, loader, loss_fn, reg_fn, lambda_reg, device, False, fused=fused)
     if writer:
         writer.add_scalar('val/loss_surv', loss_surv, epoch)
         writer.add_scalar('val/loss', loss, epoch)
